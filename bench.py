@@ -2,14 +2,22 @@
 """bench.py -- ALM iterations per second of the DOTs-SOCP hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload knot|sphere10k|knot63|torus100k|torus65k_T127|torus500k|plane20]
+                    [--dump-outputs DIR] [--full]
 
 One "step" is one full pass of the solver's main loop (reference solver_socp.py:656-823): steps 1-3 (Laplacian solve,
 cone projection, (q, lambda) + multiplier update) plus whatever KKT evaluation / penalty update the reference's lazy
 schedule puts on that iteration.  All state is resident in HBM before the timed region starts.  Rank 0 prints ONE
 JSON line.
 
+A plain run sets up, runs W untimed and K timed steps and prints the headline (plus the ``config`` the line describes):
+
 * ``value`` / ``ms_per_step``: the workload BASELINE.json's metric is quoted on (``knot``: the knots_5 stand-in, T=31),
   W untimed + exactly K timed iterations as the driver asks.
+* ``--dump-outputs DIR``: after the timed steps, the state they left as a caller of the solver receives it (reference layout,
+  un-scaled: AlmSolver.finalize) as float64 DIR/<name>.npy (dump_outputs), so that two builds can be compared output for output.
+
+``--full`` adds everything else the line has held (the ``--no-*`` options trim it):
+
 * ``steady_state``: the same solver run on to iteration 100, then 200 iterations timed (independent of K / W: the first
   25 iterations are dense in penalty updates and KKT checks, admm_tools.py:43-48).
 * ``configs``: all five BASELINE.json configurations (N = 1): steady-state it/s, ms/step, time to tol, roofline.
@@ -22,7 +30,7 @@ For N > 1 the iteration is sharded over time slabs (dots_socp_amd/distributed.py
 ``python bench.py --gpus N`` the script launches its N ranks itself (torch.distributed.run, before anything touches the GPU) and
 relays rank 0's line and the ranks' exit code; started by torch.distributed.run it reads RANK / LOCAL_RANK / WORLD_SIZE.  ``value``
 is whole-job iterations/s of the metric's configuration (the iterations are collective: every rank advances the same ALM
-iteration), "scaling": "strong"; ``sharded_configs`` times the configurations BASELINE.json places on several GPUs
+iteration), "scaling": "strong"; with ``--full``, ``sharded_configs`` times the configurations BASELINE.json places on several GPUs
 (torus100k: configs[3], torus65k_T127: configs[4]) on the same ranks: steady it/s, exchange seconds, per-rank device bytes, a
 run to tol.  With fewer GPUs than ranks (a one-GPU box) the ranks share the GPUs over gloo (a rehearsal of the command, not a
 scaling measurement; DOTS_DIST_BACKEND overrides).
@@ -81,6 +89,9 @@ def parse():
                     help="wall-clock cap of a sharded run to tol (default: 150 s over RCCL; 20 s when the ranks share GPUs over gloo, a rehearsal)")
     ap.add_argument("--no-reorder", action="store_true", help="keep the generator's vertex numbering (A/B of the renumbering)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="CPU budget of the cpu_baseline sample")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the state the last timed step left as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the steady state, roofline, time to tol, the other configurations and the CPU baseline")
     return ap.parse_args()
 
 
@@ -423,6 +434,33 @@ def kernel_digest():
     return h.hexdigest()
 
 
+DUMP_BYTES = 63_000_000     # data written by --dump-outputs: under 64 MB in all with the .npy headers
+DUMP_SEED = 20261016
+
+
+def dump_outputs(alm, out_dir, write):
+    """--dump-outputs: every state array as AlmSolver.finalize() hands it to a caller (reference layout, un-scaled), as float64
+    ``out_dir/<name>.npy`` -- all but z_mid, which the timed path stores only on the iterations that read back.  Above DUMP_BYTES in
+    all, every array keeps the same fraction of its entries (flattened, at positions drawn from a generator seeded per array: the
+    same positions in every run of the same workload).  On several ranks a download is collective and rank 0 writes (``write``)."""
+    import numpy as np
+    from dots_socp_amd.device import STATE_NAMES
+
+    names = [n for n in STATE_NAMES if n != "z_mid"]
+    sizes = [int(np.prod(alm.dev.full_shape(n))) for n in names]
+    frac = min(1.0, DUMP_BYTES / (8.0 * sum(sizes)))
+    if write:
+        os.makedirs(out_dir, exist_ok=True)
+    for i, (name, size) in enumerate(zip(names, sizes)):
+        out = alm.recovered(name, alm._download(name))
+        if not write:
+            continue
+        if frac < 1.0:
+            keep = np.random.default_rng([DUMP_SEED, i]).choice(size, int(size * frac), replace=False)
+            out = out.reshape(-1)[np.sort(keep)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.asarray(out, dtype=np.float64))
+
+
 def launch_ranks(args):
     """``python bench.py --gpus N`` without a launcher: start the N ranks (one per GPU) before anything in this process touches
     the GPU, let rank 0's JSON line through, return the ranks' exit code."""
@@ -486,6 +524,7 @@ def main():
             dist.init_process_group(backend=backend)
 
     steady_first, steady_count = STEADY.get(args.workload, (100, 200))
+    # the iteration cap is the same with and without --full: the solver's schedule looks at it, and the K timed steps stay the same iterations
     total = max(args.warmup + args.steps, steady_first) + steady_count + 8
     alm = build_solver(args, wl, geom, total, local_rank, world)
     tm = Timer(alm, dist)
@@ -495,24 +534,32 @@ def main():
     cg0 = alm.cg_total
     elapsed = tm.run(args.steps)                                   # the driver's K steps after W warm-up steps
     cg_per_it = (alm.cg_total - cg0) / max(args.steps, 1)
-    done = args.warmup + args.steps
-    for _ in range(max(0, steady_first - done)):
-        alm.iterate()
-    steady_from = max(done, steady_first)
-    steady_el = tm.run(steady_count)
-    steady_ms = 1e3 * steady_el / steady_count
+    if args.dump_outputs:
+        dump_outputs(alm, args.dump_outputs, rank == 0)
 
-    roofline, solve_bytes = solve_roofline(alm, V, n_time)
-    if solve_bytes is None:
-        solve_bytes = cg_per_it * (roofline["algorithmic_bytes_per_launch"] + roofline["second_kernel"]["algorithmic_bytes_per_launch"])
-    roofline["whole_iteration"] = whole_iteration(n_time, V, F, solve_bytes, steady_ms, f"iterations {steady_from}..{steady_from + steady_count - 1}")
-    # one streaming launch of known size: calibrates the FETCH_SIZE / WRITE_SIZE counters when this command runs
-    # under rocprofv3 --pmc (profiles/tools/pmc_summary.py); a single launch, outside the timed region
-    _, calib_bytes = alm.dev.bench_kernel(which=4, reps=1)
-    roofline["pmc_calibration_bytes_each_way"] = calib_bytes
-    if world == 1 and args.lap_solver == "modal_direct":
-        roofline["traffic"], roofline["traffic_source"] = traffic_record(args.workload)
-    roofline["kernel_sources_sha256"] = kernel_digest()
+    full = {}
+    if args.full:
+        done = args.warmup + args.steps
+        for _ in range(max(0, steady_first - done)):
+            alm.iterate()
+        steady_from = max(done, steady_first)
+        steady_el = tm.run(steady_count)
+        steady_ms = 1e3 * steady_el / steady_count
+
+        roofline, solve_bytes = solve_roofline(alm, V, n_time)
+        if solve_bytes is None:
+            solve_bytes = cg_per_it * (roofline["algorithmic_bytes_per_launch"] + roofline["second_kernel"]["algorithmic_bytes_per_launch"])
+        roofline["whole_iteration"] = whole_iteration(n_time, V, F, solve_bytes, steady_ms, f"iterations {steady_from}..{steady_from + steady_count - 1}")
+        # one streaming launch of known size: calibrates the FETCH_SIZE / WRITE_SIZE counters when this command runs
+        # under rocprofv3 --pmc (profiles/tools/pmc_summary.py); a single launch, outside the timed region
+        _, calib_bytes = alm.dev.bench_kernel(which=4, reps=1)
+        roofline["pmc_calibration_bytes_each_way"] = calib_bytes
+        if world == 1 and args.lap_solver == "modal_direct":
+            roofline["traffic"], roofline["traffic_source"] = traffic_record(args.workload)
+        roofline["kernel_sources_sha256"] = kernel_digest()
+        full["steady_state"] = {"iterations_per_s": steady_count / steady_el, "ms_per_step": steady_ms,
+                                "window": f"iterations {steady_from}..{steady_from + steady_count - 1}"}
+        full["roofline"] = roofline
     dev_bytes = alm.dev.device_bytes()
     dev_bytes_ranks = gather_ints(dist, dev_bytes)
     alm._collect_step_times(wait=True)
@@ -520,10 +567,9 @@ def main():
     steps_note = alm.run_history.steps_time_note
     alm.close()
 
-    extra = {}
-    if rank == 0 and world == 1 and not args.no_time_to_tol:
-        extra["time_to_tol"] = time_to_tol(args, wl, geom, local_rank)
-    if rank == 0 and world == 1 and not args.no_configs and args.lap_solver == "modal_direct":
+    if args.full and rank == 0 and world == 1 and not args.no_time_to_tol:
+        full["time_to_tol"] = time_to_tol(args, wl, geom, local_rank)
+    if args.full and rank == 0 and world == 1 and not args.no_configs and args.lap_solver == "modal_direct":
         table = []
         for name in ALL_CONFIGS:
             if name == args.workload:
@@ -532,16 +578,16 @@ def main():
                      "window": f"iterations {steady_from}..{steady_from + steady_count - 1}", "device_bytes": dev_bytes,
                      "roofline": {k: roofline[k] for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "ms_per_solve",
                                                            "launches_per_solve", "algorithmic_bytes_per_solve", "whole_iteration") if k in roofline}}
-                if "time_to_tol" in extra:
-                    e["time_to_tol"] = extra["time_to_tol"]
+                if "time_to_tol" in full:
+                    e["time_to_tol"] = full["time_to_tol"]
                 table.append(e)
             else:
                 table.append(config_entry(args, name, local_rank))
-        extra["configs"] = table
-    if rank == 0 and world == 1 and not args.no_alternatives and not args.no_configs and args.lap_solver == "modal_direct":
-        extra["solver_alternatives"] = solver_alternatives(args, local_rank)
-    if world > 1 and not args.no_configs and args.lap_solver == "modal_direct":      # collective: every rank takes part
-        extra["sharded_configs"] = [sharded_entry(args, name, local_rank, world, dist) for name in SHARDED_CONFIGS]
+        full["configs"] = table
+    if args.full and rank == 0 and world == 1 and not args.no_alternatives and not args.no_configs and args.lap_solver == "modal_direct":
+        full["solver_alternatives"] = solver_alternatives(args, local_rank)
+    if args.full and world > 1 and not args.no_configs and args.lap_solver == "modal_direct":      # collective: every rank takes part
+        full["sharded_configs"] = [sharded_entry(args, name, local_rank, world, dist) for name in SHARDED_CONFIGS]
 
     if rank != 0:
         if dist is not None:
@@ -562,15 +608,13 @@ def main():
             "world_size": world, "backend": ("rccl (torch.distributed nccl)" if backend == "nccl" else backend) if world > 1 else None,
             "gpus_visible": n_dev,
         },
-        "steady_state": {"iterations_per_s": steady_count / steady_el, "ms_per_step": steady_ms,
-                         "window": f"iterations {steady_from}..{steady_from + steady_count - 1}"},
-        "roofline": roofline,
     }
-    line.update(extra)
-    if world == 1 and not args.no_cpu_baseline:
-        line["cpu_baseline"] = cpu_baseline(geom, n_time, congestion, args.cpu_seconds)
-    else:
-        line["cpu_baseline"] = None
+    if args.full:
+        line.update(full)
+        if world == 1 and not args.no_cpu_baseline:
+            line["cpu_baseline"] = cpu_baseline(geom, n_time, congestion, args.cpu_seconds)
+        else:
+            line["cpu_baseline"] = None
     print(json.dumps(line))
     if dist is not None:
         dist.destroy_process_group()

@@ -4,7 +4,7 @@ out=gpurun_out/ab_bench.txt
 for rep in 1 2; do
   for setting in "$@"; do
     for w in ${AB_WORKLOADS:-knot sphere10k torus100k}; do
-      env $setting python bench.py --no-cpu-baseline --no-time-to-tol --no-configs --no-alternatives --workload $w > /tmp/ab_bench.json 2>/dev/null || { echo "[$setting] $w FAILED" >> $out; continue; }
+      env $setting python bench.py --full --no-cpu-baseline --no-time-to-tol --no-configs --no-alternatives --workload $w > /tmp/ab_bench.json 2>/dev/null || { echo "[$setting] $w FAILED" >> $out; continue; }
       python - "$setting" $w >> $out <<'PY'
 import json, sys
 d = json.load(open("/tmp/ab_bench.json"))

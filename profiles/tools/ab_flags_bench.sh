@@ -5,7 +5,7 @@ for rep in 1 2; do
 for flags in "$@"; do
   DOTS_HIPCC_FLAGS="$flags" python -m dots_socp_amd.build > /dev/null 2>&1 || { echo "build failed: $flags" >> $out; exit 1; }
   for w in ${AB_WORKLOADS:-knot sphere10k torus100k}; do
-    DOTS_HIPCC_FLAGS="$flags" python bench.py --no-cpu-baseline --no-time-to-tol --no-configs --no-alternatives --workload $w > /tmp/ab_bench.json 2>/dev/null || { echo "[$flags] $w FAILED" >> $out; continue; }
+    DOTS_HIPCC_FLAGS="$flags" python bench.py --full --no-cpu-baseline --no-time-to-tol --no-configs --no-alternatives --workload $w > /tmp/ab_bench.json 2>/dev/null || { echo "[$flags] $w FAILED" >> $out; continue; }
     python - "$flags" $w >> $out <<'PY'
 import json, sys
 d = json.load(open("/tmp/ab_bench.json"))

@@ -8,7 +8,7 @@ tag=$1; w=$2; commit=${3:-unknown}
 out=gpurun_out
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt_${tag}_$w -o s -- python bench.py --no-cpu-baseline --no-time-to-tol --no-configs --workload $w > $out/${tag}_${w}_bench_under_rocprof.json 2> $out/${tag}_${w}_rocprof.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt_${tag}_$w -o s -- python bench.py --full --no-cpu-baseline --no-time-to-tol --no-configs --workload $w > $out/${tag}_${w}_bench_under_rocprof.json 2> $out/${tag}_${w}_rocprof.log
 cp $(find $out/kt_${tag}_$w -name "s_kernel_stats.csv" | head -1) $out/${tag}_${w}_kernel_stats.csv
 python profiles/tools/trace_by_grid.py $(find $out/kt_${tag}_$w -name "s_kernel_trace.csv" | head -1) > $out/${tag}_${w}_by_grid.txt
 rm -rf $out/kt_${tag}_$w

@@ -7,7 +7,7 @@ w=$1; out=$2
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 run() {   # <tag> <counters...>
   tag=$1; shift
-  rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $out/sq_${w}_$tag -o s -- python bench.py --no-cpu-baseline --no-time-to-tol --no-configs --steps 20 --warmup 5 --workload $w > $out/sq_${w}_$tag.json 2> $out/sq_${w}_$tag.log
+  rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $out/sq_${w}_$tag -o s -- python bench.py --full --no-cpu-baseline --no-time-to-tol --no-configs --steps 20 --warmup 5 --workload $w > $out/sq_${w}_$tag.json 2> $out/sq_${w}_$tag.log
 }
 run waves SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE
 run insts SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INST_LEVEL_VMEM SQ_LDS_BANK_CONFLICT

@@ -7,7 +7,7 @@ set -e
 w=$1; out=$2; commit=${3:-unknown}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $out/pmc_${w}_$c -o s -- python bench.py --no-cpu-baseline --no-time-to-tol --no-configs --steps 20 --warmup 5 --workload $w > $out/pmc_${w}_$c.json 2> $out/pmc_${w}_$c.log
+  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $out/pmc_${w}_$c -o s -- python bench.py --full --no-cpu-baseline --no-time-to-tol --no-configs --steps 20 --warmup 5 --workload $w > $out/pmc_${w}_$c.json 2> $out/pmc_${w}_$c.log
 done
 levels=$(python -c "import json;print(json.load(open('$out/pmc_${w}_FETCH_SIZE.json'))['roofline']['launches_per_solve'] // 2)")   # forward launches of one solve = bands of tree heights
 calib=$(python -c "import json;print(json.load(open('$out/pmc_${w}_FETCH_SIZE.json'))['roofline']['pmc_calibration_bytes_each_way'])")
@@ -22,7 +22,7 @@ json.dump({"bytes_per_solve": s["front_solve"]["bytes_per_solve"], "read_bytes_p
            "factor_bytes_per_solve_as_installed": b["roofline"]["factor"].get("bytes_per_solve_as_installed"),
            "bands": b["roofline"]["factor"].get("bands"),
            "kernel_sources_sha256": b["roofline"]["kernel_sources_sha256"],
-           "source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (two passes) of 'bench.py --workload $w --steps 20 --warmup 5 --no-configs', commit $commit, "
+           "source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (two passes) of 'bench.py --full --workload $w --steps 20 --warmup 5 --no-configs', commit $commit, "
                      "calibrated on k_calib_stream of the same run (profiles/tools/collect_traffic.sh)"},
           open("$out/traffic_${w}.json", "w"), indent=1)
 PY

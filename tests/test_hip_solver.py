@@ -428,3 +428,34 @@ def test_patch_tiles_are_bit_identical(fname):
     for k in ("phi", "mu", "E", "A", "B", "z_fst", "z_end", "beta_mid"):
         assert np.array_equal(s0[k], s2[k]), k
         assert np.array_equal(s0[k], runs["2"][0][k]), k        # mode 2: the plain launch, its tiles cut from the patch order
+
+
+def test_bench_plain_run_dumps_what_the_solver_hands_out(tmp_path):
+    """A plain ``bench.py`` run in a process of its own prints the headline over exactly the K timed steps and nothing of --full;
+    its --dump-outputs hold the state of the last timed step as the solver hands it to a caller: the same problem solved for
+    W + K iterations."""
+    import json
+    import subprocess
+    import sys
+
+    from conftest import ROOT
+    from dots_socp_amd import meshes
+    from dots_socp_amd.device import STATE_NAMES
+    from dots_socp_amd.socp import solver_socp
+
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "7", "--warmup", "3", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-4000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["metric"] == "ALM iterations/s" and line["steps"] == 7 and line["warmup"] == 3 and line["dtype"] == "f64"
+    assert line["ms_per_step"] == pytest.approx(1e3 / line["value"])
+    assert not {"steady_state", "roofline", "time_to_tol", "configs", "solver_alternatives", "cpu_baseline"} & set(line)
+    geom, _ = meshes.example("knot")
+    sol, _ = solver_socp(31, geom, nit=10, tol=1e-30)
+    assert not (out / "z_mid.npy").exists()
+    for name in STATE_NAMES:
+        if name != "z_mid":
+            got = np.load(out / f"{name}.npy")
+            assert got.dtype == np.float64 and got.shape == sol[name].shape, name
+            assert rel(got, sol[name]) < 1e-9, name

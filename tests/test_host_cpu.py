@@ -491,6 +491,53 @@ def test_bench_launches_its_own_ranks(monkeypatch, capsys):
     assert e.value.code == 0
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """``bench.py --dump-outputs DIR``: every state array but z_mid as float64 DIR/<name>.npy, as the solver hands it out
+    (recovered); a rank other than 0 takes part in the (collective) downloads and writes nothing; above the size cap every array
+    keeps the same fraction of its entries, at the same positions in every run."""
+    import importlib.util
+    import types
+
+    from dots_socp_amd.device import STATE_NAMES
+
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    class FakeSolver:
+        def __init__(self, shape):
+            self.dev = types.SimpleNamespace(full_shape=lambda name: shape)
+            self.shape, self.downloads = shape, []
+
+        def _download(self, name):
+            self.downloads.append(name)
+            return np.arange(np.prod(self.shape), dtype=np.float64).reshape(self.shape) + STATE_NAMES.index(name)
+
+        def recovered(self, name, arr):
+            return 2.0 * arr
+
+    names = [n for n in STATE_NAMES if n != "z_mid"]
+    bench.dump_outputs(FakeSolver((3, 4)), str(tmp_path / "whole"), True)
+    assert sorted(os.listdir(tmp_path / "whole")) == sorted(f"{n}.npy" for n in names)
+    for n in names:
+        got = np.load(tmp_path / "whole" / f"{n}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, 2.0 * (np.arange(12.0).reshape(3, 4) + STATE_NAMES.index(n)))
+    other = FakeSolver((3, 4))
+    bench.dump_outputs(other, str(tmp_path / "other_rank"), False)
+    assert other.downloads == names and not (tmp_path / "other_rank").exists()
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 8 * 100 * len(names))       # room for 100 of the 1000 entries of each array
+    for d in ("first", "second"):
+        bench.dump_outputs(FakeSolver((10, 100)), str(tmp_path / d), True)
+    written = 0
+    for n in names:
+        a, b = np.load(tmp_path / "first" / f"{n}.npy"), np.load(tmp_path / "second" / f"{n}.npy")
+        assert a.dtype == np.float64 and a.shape == (100,) and np.array_equal(a, b)
+        assert np.all(np.diff(a) > 0) and np.all((a - 2.0 * STATE_NAMES.index(n)) % 2.0 == 0)       # distinct entries, in order
+        written += a.nbytes
+    assert written <= bench.DUMP_BYTES
+
+
 def test_native_assembly_matches_the_numpy_reference():
     """dots_assemble (host code of the library) against the numpy functions of geometry.py, which the oracle tests pin to the
     reference's assembly (surface_pre_computations_socp.py:11-132): areas, hat gradients, masses and corner lists identical,
