@@ -31,6 +31,7 @@ EXPORTS = [
     "dots_slab_elems", "dots_slab_set_buffers", "dots_slab_stage", "dots_kkt_sums", "dots_kkt_sums_device", "dots_debug_counter", "dots_kkt_combine", "dots_objective_sums",
     "dots_objective_combine", "dots_front_launches", "dots_front_info", "dots_front_setup", "dots_front_enable", "dots_front_pitch", "dots_penalty_ahead", "dots_step_flags", "dots_step_times", "dots_stream_wait", "dots_tree_build", "dots_tree_nodes", "dots_tree_copy", "dots_tree_free",
     "dots_patch_order", "dots_assemble", "dots_assemble_nnz", "dots_assemble_copy", "dots_assemble_free", "dots_symbolic_build", "dots_symbolic_front_rows", "dots_symbolic_copy", "dots_symbolic_free",
+    "dots_front_share", "dots_laplacian_solve_many", "dots_step_many", "dots_bench_many",
 ]
 
 
@@ -43,6 +44,8 @@ class HipLibraryError(RuntimeError):
     status = None      # the library's status code (dots_status) when the error comes from an entry point
 
 
+ERR_ARGUMENT = -1
+ERR_STATE = -5
 ERR_MEMORY = -6
 
 
@@ -130,7 +133,7 @@ SLAB_SIZES = {"vertex_halo": 0, "b_chunk": 1, "x_chunk": 2, "triangle_halo": 3}
 KNOWN_ENV = {
     # read by the library (csrc/dots_api.hip: env_int)
     "DOTS_CG_STAGE_LDS", "DOTS_MG_TAIL_ROWS", "DOTS_SOC_WITH_RHS", "DOTS_QL_TWO", "DOTS_KKT_TWO", "DOTS_RHS_TWO", "DOTS_RHS_TILES", "DOTS_CARRY", "DOTS_CARRY_MIN", "DOTS_BM_NT", "DOTS_LAZY_DIV", "DOTS_ZMID_DEFER", "DOTS_MEM_BUDGET", "DOTS_SPIN_FETCH",
-    "DOTS_FRONT_VEC2", "DOTS_FRONT_RB", "DOTS_FRONT_ROWS", "DOTS_FRONT_XCD", "DOTS_FRONT_LEAFINV", "DOTS_FRONT_TUNE", "DOTS_FRONT_CFG", "DOTS_MAIL_TEST_DROP",
+    "DOTS_FRONT_VEC2", "DOTS_FRONT_RB", "DOTS_FRONT_ROWS", "DOTS_FRONT_XCD", "DOTS_FRONT_LEAFINV", "DOTS_FRONT_TUNE", "DOTS_FRONT_CFG", "DOTS_FRONT_NR", "DOTS_MAIL_TEST_DROP",
     "DOTS_MAIL_SPINS", "DOTS_ND_PCA_MIN",
     # read by the host side
     "DOTS_RHS_AHEAD", "DOTS_TIME_EVERY", "DOTS_FRONT_BANDS", "DOTS_FRONT_TOPINV", "DOTS_TORCH_FIRST", "DOTS_DIST_BACKEND", "DOTS_HIPCC_FLAGS",
@@ -282,6 +285,10 @@ def load(host_only=False):
     lib.dots_symbolic_copy.argtypes = [vp, _i32p, _i32p, _i32p, _i32p]
     lib.dots_symbolic_free.argtypes = [vp]
     lib.dots_symbolic_free.restype = None
+    lib.dots_front_share.argtypes = [vp, vp]
+    lib.dots_laplacian_solve_many.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(_f64p), C.POINTER(_f64p)]
+    lib.dots_step_many.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(StepStats)]
+    lib.dots_bench_many.argtypes = [C.POINTER(vp), C.c_int, C.c_int, _f64p]
     lib.dots_device_bytes.argtypes = [vp]
     lib.dots_device_bytes.restype = C.c_int64
     for n in EXPORTS:

@@ -132,6 +132,18 @@ static int build(Ctx *c, const dots_problem_desc *p) {
     d.h = 1.0 / d.T;
     d.cg_ncol = d.T + 1;
     c->nnz = p->lap_nnz;
+    {   // what the factor is built from, in this numbering (dots_front_share)
+        uint64_t h = 1469598103934665603ull;
+        auto mix = [&h](const void *data, size_t bytes) {
+            const unsigned char *b = static_cast<const unsigned char *>(data);
+            for (size_t i = 0; i < bytes; ++i) h = (h ^ b[i]) * 1099511628211ull;
+        };
+        mix(p->lap_rowptr, sizeof(int32_t) * ((size_t)p->n_vertices + 1));
+        mix(p->lap_col, sizeof(int32_t) * (size_t)p->lap_nnz);
+        mix(p->lap_val, sizeof(double) * (size_t)p->lap_nnz);
+        mix(p->mass_vert, sizeof(double) * (size_t)p->n_vertices);
+        c->lap_hash = h;
+    }
     c->lap_solver = p->lap_solver;
 
     const int V = d.V, F = d.F, nC = p->n_corners;
@@ -409,7 +421,19 @@ static hipEvent_t *time_slot(Ctx *c, int kind) {
     return c->tev[s];
 }
 
-static int run_iteration_body(Ctx *c, dots_step_stats *st, hipEvent_t *tv) {
+// What the first half of an iteration decided, for its second half (iteration_before / iteration_after)
+struct IterPlan {
+    double dv = 0.0;          // a pending penalty division the iteration's kernels apply as they read
+    int zmode = 1;            // steps 2+3: 1 store z_mid, 2 skip it
+    int ahead_kind = 0;       // the right-hand side (1) / and the projection (2) were enqueued ahead (DOTS_STEP_RHS_AHEAD)
+    bool fused_rhs = false;   // the projection rides in the right-hand-side launch
+    bool fuse = false;        // the projection takes the inverse time transform
+};
+
+// First half of an enqueue-only iteration, up to the right-hand side of step 1 (dots_step and dots_step_many); `timed`: the caller
+// brackets the phases with events and waits (no division rides in the kernels then).  The solve follows: cg_solve, or in a batch the
+// time transform, front_solve_many and the inverse transform.
+static int iteration_before(Ctx *c, bool timed, IterPlan &p, hipEvent_t *tv) {
     int rc;
 #define MARK(i) do { if (tv) DOTS_HIP(hipEventRecord(tv[i], c->stream)); } while (0)
     MARK(0);
@@ -418,14 +442,14 @@ static int run_iteration_body(Ctx *c, dots_step_stats *st, hipEvent_t *tv) {
         else { c->zmid_deferred = 0; c->zmid_stale = 1; }
     }
     // a pending penalty division rides in this iteration's kernels when both of them can apply it; otherwise it is carried out first
-    const int zmode = c->step_skip_zmid ? 2 : 1;
-    double dv = 0.0;
+    p.zmode = c->step_skip_zmid ? 2 : 1;
+    p.dv = 0.0;
     if (c->pending_div != 0.0) {
-        if (!st && !c->step_palm && c->rhs_ahead == 2 && c->ahead_div == c->pending_div && ql_divides(c, zmode)) {
-            dv = c->pending_div;      // the launch ahead (penalty_decision_ahead) divided as it read: steps 2+3 do the same and write back divided
+        if (!timed && !c->step_palm && c->rhs_ahead == 2 && c->ahead_div == c->pending_div && ql_divides(c, p.zmode)) {
+            p.dv = c->pending_div;      // the launch ahead (penalty_decision_ahead) divided as it read: steps 2+3 do the same and write back divided
             c->pending_div = 0.0;
-        } else if (!st && !c->step_palm && !c->rhs_ahead && rhs_takes_soc(c) && rhs_divides(c) && ql_divides(c, zmode)) {
-            dv = c->pending_div;
+        } else if (!timed && !c->step_palm && !c->rhs_ahead && rhs_takes_soc(c) && rhs_divides(c) && ql_divides(c, p.zmode)) {
+            p.dv = c->pending_div;
             c->pending_div = 0.0;
         } else if ((rc = flush_division(c))) return rc;      // (a launch ahead that divided as it read saw the values the arrays now hold)
     }
@@ -433,10 +457,10 @@ static int run_iteration_body(Ctx *c, dots_step_stats *st, hipEvent_t *tv) {
     if ((rc = palm_step0(c))) return rc;
     // the right-hand side of this iteration was enqueued behind the KKT kernels of the last one (DOTS_STEP_RHS_AHEAD) and nothing
     // it reads has changed since: start at the solve; the projection then runs with the inverse transform
-    const int ahead_kind = (c->step_palm || c->rhs_ahead > 2) ? 0 : c->rhs_ahead;      // (3, 4: an anticipated penalty update the caller did not confirm)
-    const bool ahead = ahead_kind != 0;
+    p.ahead_kind = (c->step_palm || c->rhs_ahead > 2) ? 0 : c->rhs_ahead;      // (3, 4: an anticipated penalty update the caller did not confirm)
+    const bool ahead = p.ahead_kind != 0;
     c->rhs_ahead = 0;
-    if (ahead_kind == 2) {      // the projection ran ahead too: its results become the current z_fst, z_end and cone multiplier
+    if (p.ahead_kind == 2) {      // the projection ran ahead too: its results become the current z_fst, z_end and cone multiplier
         std::swap(c->d.zf, c->zf_alt);
         std::swap(c->d.ze, c->ze_alt);
         std::swap(c->d.lamc, c->lamc_alt);
@@ -444,33 +468,47 @@ static int run_iteration_body(Ctx *c, dots_step_stats *st, hipEvent_t *tv) {
         c->dcg.ze = c->dgt.ze = c->d.ze;
         c->dcg.lamc = c->dgt.lamc = c->d.lamc;
     }
-    if (!st) {   // asynchronous: enqueue only (the direct solver needs no host round trip); nothing is timed
-        c->zmid_stale = c->step_skip_zmid;
-        if (rhs_takes_soc(c) && !ahead) {   // [right-hand side + projection] -> sweeps -> inverse transform -> steps 2+3
-            if ((rc = launch_rhs(c, true, dv))) return rc;
-            MARK(1);
-            if ((rc = cg_solve(c, nullptr))) return rc;
-            MARK(2);
-            MARK(3);      // (no separate projection launch: dots_step_times splits the first phase between ms_rhs and ms_soc)
-            if ((rc = launch_q_lambda_mult(c, zmode, dv))) return rc;
-            MARK(4);
-            MARK(5);      // back to back with 4: what one event costs on the stream, taken off every phase (dots_step_times)
-            if (tv) c->tkind[(c->t_head + c->t_count - 1) % Ctx::TIME_SLOTS] = TKIND_FUSED;
-            return 0;
-        }
-        const bool fuse = soc_takes_inverse(c) && ahead_kind != 2;
-        if (!ahead && (rc = launch_rhs(c))) return rc;
-        MARK(1);
-        if ((rc = cg_solve(c, nullptr, fuse))) return rc;
-        MARK(2);
-        if (ahead_kind != 2 && (rc = launch_soc_projection(c, 1, fuse))) return rc;
-        MARK(3);
-        if ((rc = launch_q_lambda_mult(c, zmode, dv))) return rc;
+    if (timed) return 0;      // (the timed path of run_iteration_body goes on itself)
+    c->zmid_stale = c->step_skip_zmid;
+    p.fused_rhs = rhs_takes_soc(c) && !ahead;      // [right-hand side + projection] -> sweeps -> inverse transform -> steps 2+3
+    p.fuse = !p.fused_rhs && soc_takes_inverse(c) && p.ahead_kind != 2;
+    if (p.fused_rhs) { if ((rc = launch_rhs(c, true, p.dv))) return rc; }
+    else if (!ahead && (rc = launch_rhs(c))) return rc;
+    MARK(1);
+    return 0;
+}
+
+// Second half, behind the solve: the projection (unless it rode in the right-hand side or ran ahead) and steps 2+3
+static int iteration_after(Ctx *c, const IterPlan &p, hipEvent_t *tv) {
+    int rc;
+    MARK(2);
+    if (p.fused_rhs) {
+        MARK(3);      // (no separate projection launch: dots_step_times splits the first phase between ms_rhs and ms_soc)
+        if ((rc = launch_q_lambda_mult(c, p.zmode, p.dv))) return rc;
         MARK(4);
-        MARK(5);
+        MARK(5);      // back to back with 4: what one event costs on the stream, taken off every phase (dots_step_times)
+        if (tv) c->tkind[(c->t_head + c->t_count - 1) % Ctx::TIME_SLOTS] = TKIND_FUSED;
         return 0;
     }
+    if (p.ahead_kind != 2 && (rc = launch_soc_projection(c, 1, p.fuse))) return rc;
+    MARK(3);
+    if ((rc = launch_q_lambda_mult(c, p.zmode, p.dv))) return rc;
+    MARK(4);
+    MARK(5);
+    return 0;
 #undef MARK
+}
+
+static int run_iteration_body(Ctx *c, dots_step_stats *st, hipEvent_t *tv) {
+    int rc;
+    IterPlan p;
+    if ((rc = iteration_before(c, st != nullptr, p, tv))) return rc;
+    if (!st) {   // asynchronous: enqueue only (the direct solver needs no host round trip); nothing is timed
+        if ((rc = cg_solve(c, nullptr, p.fuse))) return rc;
+        return iteration_after(c, p, tv);
+    }
+    const int ahead_kind = p.ahead_kind;
+    const bool ahead = ahead_kind != 0;
     DOTS_HIP(hipEventRecord(c->ev[0], c->stream));
     if (!ahead && (rc = launch_rhs(c))) return rc;
     DOTS_HIP(hipEventRecord(c->ev[1], c->stream));
@@ -576,6 +614,8 @@ int dots_create(const dots_problem_desc *desc, dots_ctx **out) {
         ok &= env_int("DOTS_FRONT_XCD", 0, 1, &c->front_xcd);
         ok &= env_int("DOTS_FRONT_LEAFINV", 0, 2, &c->front_leafinv);
         ok &= env_int("DOTS_FRONT_TUNE", 0, 2, &c->front_tune);
+        ok &= env_int("DOTS_FRONT_NR", 2, 8, &c->front_nr_max);      // right-hand sides per launch of a batched solve (2, 4 or 8; A/B measurements)
+        if (c->front_nr_max != 2 && c->front_nr_max != 4 && c->front_nr_max != 8) { set_error("DOTS_FRONT_NR must be 2, 4 or 8"); ok = false; }
         ok &= env_int("DOTS_MAIL_TEST_DROP", 0, 1 << 20, &c->mail_test_drop);
         int spins = -1;
         ok &= env_int("DOTS_MAIL_SPINS", 0, 2000000000, &spins);
@@ -606,6 +646,8 @@ int dots_destroy(dots_ctx *c) {
     if (c->h_flags) (void)hipHostFree(c->h_flags);
     if (c->h_mail) (void)hipHostFree(c->h_mail);
     for (auto &ev : c->ev) if (ev) (void)hipEventDestroy(ev);
+    if (c->ev_batch) (void)hipEventDestroy(c->ev_batch);
+    c->front_store.reset();      // (a shared factor: freed with its last holder)
     for (auto &slot : c->tev)
         for (auto &ev : slot) if (ev) (void)hipEventDestroy(ev);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -632,6 +674,7 @@ int dots_set_params(dots_ctx *c, const dots_params *p) {
 int dots_penalty_ahead(dots_ctx *c, const dots_penalty_policy *policy) {
     int rc = check(c, true, true);
     if (rc) return rc;
+    if (c->batched) { set_error("penalty_ahead: the context is stepped in a batch (dots_step_many)"); return DOTS_ERR_STATE; }
     if (!policy || policy->n_steps < 0 || policy->n_steps > 16 || !(policy->tol > 0) || !(policy->r_lower > 0) || !(policy->r_upper >= policy->r_lower)) {
         set_error("penalty_ahead: bad policy");
         return DOTS_ERR_ARGUMENT;
@@ -789,6 +832,7 @@ int dots_stream_wait(dots_ctx *c, void *other_stream, int ctx_waits) {
 int dots_step(dots_ctx *c, int n_iters, dots_step_stats *stats) {
     int rc = check(c, true, true);      // (run_iteration consumes the flags and a pending penalty division itself)
     if (rc) return rc;
+    c->batched = 0;
     if (n_iters < 0) { set_error("n_iters < 0"); return DOTS_ERR_ARGUMENT; }
     if (c->shard_stride != 0) { set_error("dots_step on a time slab: use dots_slab_stage"); return DOTS_ERR_STATE; }
     dots_step_stats local;
@@ -1130,6 +1174,40 @@ int dots_mg_enable(dots_ctx *c, int on) {
     return 0;
 }
 
+// DOTS_STEP_CARRY: the per-corner gathers steps 2+3 leave for the next right-hand side / projection (one GPU, pitch <= 128);
+// they belong to the direct solver's iteration and are released with the factor (per context: a sharer of a factor has its own)
+static int front_carry_alloc(Ctx *c) {
+    int rc;
+    if (c->d.TP <= 128 && c->carry_arrays && c->d.nl > 0) {      // (one GPU or a time slab with nodes)
+        const int64_t rows = (int64_t)3 * c->d.F;
+        const double *sq = nullptr, *g = nullptr, *lo = nullptr, *e = nullptr;
+        if ((rc = front_upload<double>(c, &sq, nullptr, (2 * rows) << c->d.tp_shift)) || (rc = front_upload<double>(c, &g, nullptr, rows << c->d.tp_shift)) ||
+            (rc = front_upload<double>(c, &lo, nullptr, rows)) || (c->shard_stride == 0 && (rc = front_upload<double>(c, &e, nullptr, rows << c->d.tp_shift)))) {
+            front_release(c);
+            return rc;
+        }
+        c->d.cn_sq = const_cast<double *>(sq);
+        c->d.cn_g = const_cast<double *>(g);
+        c->d.cn_lo = const_cast<double *>(lo);
+        c->d.cn_e = const_cast<double *>(e);
+    }
+    return 0;
+}
+
+// a context with its own direct solver on one GPU: what the batched calls take
+static bool front_batchable(const Ctx *c) {
+    return c->use_front && c->front.n_nodes > 0 && c->shard_stride == 0 && c->lap_solver == DOTS_LAP_MODAL_PCG;
+}
+
+// c's stream waits for what is enqueued on `other`'s stream so far
+static int batch_wait(Ctx *c, Ctx *other) {
+    if (c == other) return 0;
+    if (!other->ev_batch) DOTS_HIP(hipEventCreateWithFlags(&other->ev_batch, hipEventDisableTiming));
+    DOTS_HIP(hipEventRecord(other->ev_batch, other->stream));
+    DOTS_HIP(hipStreamWaitEvent(c->stream, other->ev_batch, 0));
+    return 0;
+}
+
 int dots_front_setup(dots_ctx *c, const dots_front_desc *desc) {
     int rc = check(c);
     if (rc) return rc;
@@ -1150,19 +1228,212 @@ int dots_front_setup(dots_ctx *c, const dots_front_desc *desc) {
         const double factor = 0.5 * c->front_bytes;      // what the sweeps touch: every block is read by both sweeps (the zero blocks of merged nodes are never read)
         c->bm_nt = nt >= 0 ? nt : (factor < 0.9e9 && factor + touched > mall ? 1 : 0);
     }
-    if (c->d.TP <= 128 && c->carry_arrays && c->d.nl > 0) {      // (one GPU or a time slab with nodes)
-        const int64_t rows = (int64_t)3 * c->d.F;
-        const double *sq = nullptr, *g = nullptr, *lo = nullptr, *e = nullptr;
-        if ((rc = front_upload<double>(c, &sq, nullptr, (2 * rows) << c->d.tp_shift)) || (rc = front_upload<double>(c, &g, nullptr, rows << c->d.tp_shift)) ||
-            (rc = front_upload<double>(c, &lo, nullptr, rows)) || (c->shard_stride == 0 && (rc = front_upload<double>(c, &e, nullptr, rows << c->d.tp_shift)))) {
-            front_release(c);
-            return rc;
+    return front_carry_alloc(c);
+}
+
+int dots_front_share(dots_ctx *c, dots_ctx *owner) {
+    int rc = check(c);
+    if (rc) return rc;
+    if ((rc = check(owner, true, true))) return rc;
+    if (owner == c) { set_error("front_share: a context cannot share its own factor"); return DOTS_ERR_ARGUMENT; }
+    if (owner->front.n_nodes == 0) { set_error("front_share: the owner has no factor installed"); return DOTS_ERR_STATE; }
+    if (owner->shard_stride != 0 || c->shard_stride != 0) { set_error("front_share: time slabs cannot share a factor"); return DOTS_ERR_STATE; }
+    if (c->lap_solver != DOTS_LAP_MODAL_PCG) { set_error("the direct solve needs the modal solver"); return DOTS_ERR_ARGUMENT; }
+    char buf[256] = {0};
+    const Dev &a = c->d, &b = owner->d;
+    if (c->device != owner->device) snprintf(buf, sizeof buf, "device %d, the owner's %d", c->device, owner->device);
+    else if (a.V != b.V || a.F != b.F || a.T != b.T) snprintf(buf, sizeof buf, "V, F, T = %d, %d, %d, the owner's %d, %d, %d", a.V, a.F, a.T, b.V, b.F, b.T);
+    else if (c->nnz != owner->nnz) snprintf(buf, sizeof buf, "%d Laplacian entries, the owner's %d", c->nnz, owner->nnz);
+    else if (c->prm.eps != owner->front_eps) snprintf(buf, sizeof buf, "eps %.17g, the owner's factor was built with %.17g", c->prm.eps, owner->front_eps);
+    else if (c->dcg.TP != owner->dcg.TP || c->dcg.cg_ncol != owner->dcg.cg_ncol) snprintf(buf, sizeof buf, "mode pitch %d, the owner's %d", c->dcg.TP, owner->dcg.TP);
+    else if (c->lap_hash != owner->lap_hash) snprintf(buf, sizeof buf, "another mesh or vertex numbering (the Laplacian or the vertex masses differ)");
+    if (buf[0]) { set_error(std::string("front_share: the factor does not fit this context: ") + buf); return DOTS_ERR_ARGUMENT; }
+    // what every sharer reads moves into one store the first time the factor is shared; W and the carried gathers stay the owner's
+    if (!owner->front_store) {
+        auto st = std::make_shared<FrontStore>();
+        st->device = owner->device;
+        const void *own[5] = {owner->front.W, owner->d.cn_sq, owner->d.cn_g, owner->d.cn_lo, owner->d.cn_e};
+        int kept = 0;
+        for (int i = 0; i < owner->n_front_allocs; ++i) {
+            void *p = owner->front_allocs[i];
+            if (std::find(own, own + 5, p) != own + 5) owner->front_allocs[kept++] = p;
+            else st->allocs.push_back(p);
         }
-        c->d.cn_sq = const_cast<double *>(sq);
-        c->d.cn_g = const_cast<double *>(g);
-        c->d.cn_lo = const_cast<double *>(lo);
-        c->d.cn_e = const_cast<double *>(e);
+        owner->n_front_allocs = kept;
+        owner->front_store = st;
     }
+    c->d.cn_sq = c->d.cn_g = c->d.cn_lo = c->d.cn_e = nullptr;
+    front_release(c);
+    c->front = owner->front;
+    c->front.W = nullptr;
+    std::copy(std::begin(owner->front_fwd_ptr), std::end(owner->front_fwd_ptr), std::begin(c->front_fwd_ptr));
+    std::copy(std::begin(owner->front_bwd_ptr), std::end(owner->front_bwd_ptr), std::begin(c->front_bwd_ptr));
+    std::copy(std::begin(owner->front_fwd_rb), std::end(owner->front_fwd_rb), std::begin(c->front_fwd_rb));
+    std::copy(std::begin(owner->front_bwd_cb), std::end(owner->front_bwd_cb), std::begin(c->front_bwd_cb));
+    std::copy(std::begin(owner->front_fwd_nb), std::end(owner->front_fwd_nb), std::begin(c->front_fwd_nb));
+    std::copy(std::begin(owner->front_bwd_nb), std::end(owner->front_bwd_nb), std::begin(c->front_bwd_nb));
+    std::copy(std::begin(owner->front_fwd_qw), std::end(owner->front_fwd_qw), std::begin(c->front_fwd_qw));
+    std::copy(std::begin(owner->front_fwd_lds), std::end(owner->front_fwd_lds), std::begin(c->front_fwd_lds));
+    std::copy(std::begin(owner->front_planes), std::end(owner->front_planes), std::begin(c->front_planes));
+    c->front_vec2 = owner->front_vec2;
+    c->front_bytes = owner->front_bytes;
+    c->front_bytes_unmerged = owner->front_bytes_unmerged;
+    c->front_heights = owner->front_heights;
+    c->front_top_inverse = owner->front_top_inverse;
+    c->front_eps = owner->front_eps;
+    c->bm_nt = owner->bm_nt;
+    const double *w = nullptr;
+    if ((rc = front_upload<double>(c, &w, nullptr, owner->front_w_rows << c->dcg.tp_shift))) { front_release(c); return rc; }
+    c->front.W = const_cast<double *>(w);
+    c->front_w_rows = owner->front_w_rows;
+    c->front_store = owner->front_store;
+    c->use_front = 1;
+    return front_carry_alloc(c);
+}
+
+int dots_laplacian_solve_many(dots_ctx *const *cs, int n, const double *const *host_in, double *const *host_out) {
+    if (!cs || n < 1 || !host_in || !host_out) { set_error("laplacian_solve_many: bad arguments"); return DOTS_ERR_ARGUMENT; }
+    int rc;
+    for (int k = 0; k < n; ++k) {
+        if ((rc = check(cs[k]))) return rc;
+        if (!host_in[k] || !host_out[k]) { set_error("laplacian_solve_many: null array"); return DOTS_ERR_ARGUMENT; }
+        if (!front_batchable(cs[k])) { set_error("laplacian_solve_many: every context needs an installed or shared factor on one GPU (no PCG, no time slab)"); return DOTS_ERR_STATE; }
+        if (cs[k]->front.F != cs[0]->front.F) { set_error("laplacian_solve_many: the contexts do not share one factor (dots_front_share)"); return DOTS_ERR_ARGUMENT; }
+        for (int j = 0; j < k; ++j)
+            if (cs[j] == cs[k]) { set_error("laplacian_solve_many: a context is listed twice"); return DOTS_ERR_ARGUMENT; }
+    }
+    const int64_t cnt = array_count_device(cs[0]->d, DOTS_PHI), nh = array_count_host(cs[0]->d, DOTS_PHI);
+    std::vector<double *> din((size_t)n, nullptr), dout((size_t)n, nullptr);
+    std::vector<const double *> bh((size_t)n);
+    std::vector<double *> ys((size_t)n), xs((size_t)n);
+    std::vector<Ctx *> cv(cs, cs + n);
+    auto release = [&]() {
+        for (int k = 0; k < n; ++k) (void)hipStreamSynchronize(cs[k]->stream);
+        for (auto p : din) if (p) (void)hipFree(p);
+        for (auto p : dout) if (p) (void)hipFree(p);
+    };
+    // per member, on its own stream: the input in device layout and its forward time transform (as step 1 forms them)
+    for (int k = 0; k < n && !rc; ++k) {
+        Ctx *c = cs[k];
+        hipError_t e = hipMalloc((void **)&din[k], sizeof(double) * (size_t)cnt);
+        if (e == hipSuccess) e = hipMalloc((void **)&dout[k], sizeof(double) * (size_t)cnt);
+        if (e == hipSuccess) e = hipMemcpyAsync(c->stage, host_in[k], sizeof(double) * (size_t)nh, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) { rc = hip_fail(e, "laplacian_solve_many", __FILE__, __LINE__); break; }
+        Ctx tmp = *c;
+        tmp.d.phi = din[k];
+        if ((rc = launch_to_device_layout(&tmp, DOTS_PHI, c->stage))) break;
+        modes_forward(c, din[k], c->d.cg_p0, true);
+        bh[(size_t)k] = c->d.cg_p0;
+        ys[(size_t)k] = c->dcg.cg_z;
+        xs[(size_t)k] = c->dcg.cg_x;
+    }
+    // the sweeps of all members on the first member's stream, then each member's inverse transform on its own
+    for (int k = 1; k < n && !rc; ++k) rc = batch_wait(cs[0], cs[k]);
+    if (!rc) rc = front_solve_many(cv.data(), n, bh.data(), ys.data(), xs.data());
+    for (int k = 0; k < n && !rc; ++k) {
+        Ctx *c = cs[k];
+        if ((rc = batch_wait(c, cs[0]))) break;
+        modes_inverse(c, c->dcg.cg_x, dout[k], true);
+        Ctx tmp = *c;
+        tmp.d.phi = dout[k];
+        if ((rc = launch_from_device_layout(&tmp, DOTS_PHI, c->stage))) break;
+        hipError_t e = hipMemcpyAsync(host_out[k], c->stage, sizeof(double) * (size_t)nh, hipMemcpyDeviceToHost, c->stream);
+        if (e != hipSuccess) rc = hip_fail(e, "laplacian_solve_many", __FILE__, __LINE__);
+    }
+    release();
+    if (rc) return rc;
+    DOTS_HIP(hipGetLastError());
+    return 0;
+}
+
+int dots_step_many(dots_ctx *const *cs, int n, dots_step_stats *stats) {
+    if (!cs || n < 1) { set_error("step_many: bad arguments"); return DOTS_ERR_ARGUMENT; }
+    int rc;
+    for (int k = 0; k < n; ++k) {
+        if ((rc = check(cs[k], true, true))) return rc;      // (the iteration consumes the flags and a pending division itself)
+        if (!front_batchable(cs[k])) { set_error("step_many: every context needs an installed or shared factor on one GPU (no PCG, no time slab)"); return DOTS_ERR_STATE; }
+        if (cs[k]->front.F != cs[0]->front.F) { set_error("step_many: the contexts do not share one factor (dots_front_share)"); return DOTS_ERR_ARGUMENT; }
+        for (int j = 0; j < k; ++j)
+            if (cs[j] == cs[k]) { set_error("step_many: a context is listed twice"); return DOTS_ERR_ARGUMENT; }
+    }
+    Ctx *c0 = cs[0];
+    std::vector<Ctx *> cv(cs, cs + n);
+    std::vector<IterPlan> plan((size_t)n);
+    std::vector<const double *> bh((size_t)n);
+    std::vector<double *> ys((size_t)n), xs((size_t)n);
+    const bool timed = stats != nullptr;
+    hipEvent_t *ev = c0->ev;      // (stats: the batch's phases on the first member's stream)
+    if (timed) {
+        for (int k = 1; k < n; ++k) if ((rc = batch_wait(c0, cv[k]))) return rc;
+        DOTS_HIP(hipEventRecord(ev[0], c0->stream));
+        for (int k = 1; k < n; ++k) if ((rc = batch_wait(cv[k], c0))) return rc;
+    }
+    // each member on its own stream: the first half of its iteration and the forward time transform of its right-hand side
+    for (int k = 0; k < n; ++k) {
+        Ctx *c = cv[k];
+        c->rhs_ahead_armed = 0;      // (DOTS_STEP_RHS_AHEAD is ignored in a batch; a launch ahead already enqueued is still taken)
+        c->batched = 1;
+        IterPlan &p = plan[(size_t)k];
+        if ((rc = iteration_before(c, false, p, nullptr))) return rc;
+        if (!rhs_writes_modes(c)) modes_forward(c, c->d.cg_b, c->d.cg_p0, true);
+        c->last_cg_iters = 0;
+        bh[(size_t)k] = c->d.cg_p0;
+        ys[(size_t)k] = c->dcg.cg_z;
+        xs[(size_t)k] = c->dcg.cg_x;
+    }
+    for (int k = 1; k < n; ++k) if ((rc = batch_wait(c0, cv[k]))) return rc;
+    if (timed) DOTS_HIP(hipEventRecord(ev[1], c0->stream));
+    if ((rc = front_solve_many(cv.data(), n, bh.data(), ys.data(), xs.data()))) return rc;
+    if (timed) DOTS_HIP(hipEventRecord(ev[2], c0->stream));
+    // each member behind the sweeps: inverse transform (unless its projection takes it), projection, steps 2+3
+    for (int k = 0; k < n; ++k) {
+        Ctx *c = cv[k];
+        if ((rc = batch_wait(c, c0))) return rc;
+        if (!plan[(size_t)k].fuse) modes_inverse(c, c->dcg.cg_x, c->d.phi, true);
+        if ((rc = iteration_after(c, plan[(size_t)k], nullptr))) return rc;
+    }
+    DOTS_HIP(hipGetLastError());
+    if (timed) {
+        for (int k = 1; k < n; ++k) if ((rc = batch_wait(c0, cv[k]))) return rc;
+        DOTS_HIP(hipEventRecord(ev[3], c0->stream));
+        DOTS_HIP(hipEventSynchronize(ev[3]));
+        memset(stats, 0, sizeof *stats);
+        float t;
+        DOTS_HIP(hipEventElapsedTime(&t, ev[0], ev[1])); stats->ms_rhs = t;
+        DOTS_HIP(hipEventElapsedTime(&t, ev[1], ev[2])); stats->ms_laplacian = t;
+        DOTS_HIP(hipEventElapsedTime(&t, ev[2], ev[3])); stats->ms_q_lambda_multiplier = t;      // (projection included)
+        DOTS_HIP(hipEventElapsedTime(&t, ev[0], ev[3])); stats->ms_total = t;
+        stats->alm_iterations = n;
+    }
+    return 0;
+}
+
+int dots_bench_many(dots_ctx *const *cs, int n, int reps, double *ms) {
+    if (!cs || n < 1 || reps < 1 || !ms) { set_error("bench_many: bad arguments"); return DOTS_ERR_ARGUMENT; }
+    int rc;
+    for (int k = 0; k < n; ++k) {
+        if ((rc = check(cs[k]))) return rc;
+        if (!front_batchable(cs[k]) || cs[k]->front.F != cs[0]->front.F) { set_error("bench_many: the contexts do not share one factor"); return DOTS_ERR_STATE; }
+    }
+    std::vector<Ctx *> cv(cs, cs + n);
+    std::vector<const double *> bh((size_t)n);
+    std::vector<double *> ys((size_t)n), xs((size_t)n);
+    for (int k = 0; k < n; ++k) {
+        bh[(size_t)k] = cv[k]->d.cg_p0;
+        ys[(size_t)k] = cv[k]->dcg.cg_z;
+        xs[(size_t)k] = cv[k]->dcg.cg_x;
+    }
+    Ctx *c0 = cv[0];
+    for (int k = 1; k < n; ++k) if ((rc = batch_wait(c0, cv[k]))) return rc;
+    for (int i = 0; i < 2; ++i) if ((rc = front_solve_many(cv.data(), n, bh.data(), ys.data(), xs.data()))) return rc;
+    DOTS_HIP(hipEventRecord(c0->ev[6], c0->stream));
+    for (int i = 0; i < reps; ++i) if ((rc = front_solve_many(cv.data(), n, bh.data(), ys.data(), xs.data()))) return rc;
+    DOTS_HIP(hipEventRecord(c0->ev[7], c0->stream));
+    DOTS_HIP(hipEventSynchronize(c0->ev[7]));
+    float t;
+    DOTS_HIP(hipEventElapsedTime(&t, c0->ev[6], c0->ev[7]));
+    *ms = t / reps;
+    for (int k = 1; k < n; ++k) if ((rc = batch_wait(cv[k], c0))) return rc;
     return 0;
 }
 

@@ -19,6 +19,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -286,6 +287,10 @@ int front_setup(Ctx *c, const dots_front_desc *desc);
 void front_release(Ctx *c);
 int front_factorize(Ctx *c, const dots_front_desc *desc, FrontDev &f, const std::vector<FrontNode> &nodes, double *T, const int *grounded_host);
 int front_solve(Ctx *c, const double *bhat, double *y, double *x);   // x = A^-1 bhat for every mode of the PCG view (y: scratch)
+// the same for n problems on one shared factor (dots_front_share), up to Ctx::front_nr_max per launch, on cs[0]'s stream; n = 1 is front_solve
+int front_solve_many(Ctx *const *cs, int n, const double *const *bhat, double *const *y, double *const *x);
+void modes_forward(Ctx *c, const double *in, double *out, bool direct);   // the time transforms around step 1's solve (one GPU)
+void modes_inverse(Ctx *c, const double *x, double *phi, bool direct);
 int mg_vcycle(Ctx *c, const double *r, double *z, double *t0, double *rz_part, int nb, int ept, int vt, int G);  // enqueue z = MG(r); z holds D^-1 r on entry
 int kkt_evaluate(Ctx *c, uint32_t mask, double *out);
 int kkt_sums(Ctx *c, uint32_t mask, double *sums);                          // the weighted sums of this context's time slab
@@ -299,6 +304,17 @@ int objective_sums(Ctx *c, double *sums);
 int objective_combine(Ctx *c, const double *sums, double *out);
 int norm_square(Ctx *c, int array_id, int part, double *out);
 int reduce_partials(Ctx *c, const double *partials, int n_slots, int n_blocks, int first_slot);  // -> scal[SUMS+first_slot+slot]
+
+// device allocations of a factor shared by several contexts (Ctx::front_store)
+struct FrontStore {
+    int device = 0;
+    std::vector<void *> allocs;
+    ~FrontStore() {
+        if (allocs.empty()) return;
+        (void)hipSetDevice(device);
+        for (void *p : allocs) (void)hipFree(p);
+    }
+};
 
 struct Ctx {
     Dev d{};
@@ -409,6 +425,17 @@ struct Ctx {
     int front_top_inverse = 0;    // the top band holds explicit inverses: its forward launch writes x, the backward sweep skips it
     void *front_allocs[48]{};
     int n_front_allocs = 0;
+    // Factor shared by several contexts (dots_front_share): the allocations every sharer reads (factor, descriptors, maps, leaf records)
+    // move from front_allocs into one reference-counted store, freed with its last holder; W (update planes) and the carried gathers stay
+    // per context, in front_allocs
+    std::shared_ptr<FrontStore> front_store;
+    int64_t front_w_rows = 0;     // rows of W (the sharers allocate as many)
+    double front_eps = 0.0;       // eps the installed factor was built with
+    int front_nr_max = 4;         // right-hand sides per launch of front_solve_many (DOTS_FRONT_NR: 2, 4 or 8)
+    hipEvent_t ev_batch = nullptr;   // orders this context's stream against the others of a batched solve (created on first use)
+    int front_cap_fault = 0;      // a multi-rhs launch was asked for more right-hand sides than its workgroup shape takes (front_solve_many reports it)
+    uint64_t lap_hash = 0;        // FNV-1a of the Laplacian (rowptr, col, val) and the vertex masses: dots_front_share compares it with the owner's
+    int batched = 0;              // stepped by dots_step_many since its last dots_step: dots_penalty_ahead is refused
     void *mg_allocs[160]{};
     int n_mg_allocs = 0;
     // constants of the KKT normalisation (solver_socp.py:303-313)

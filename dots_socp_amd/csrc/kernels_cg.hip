@@ -722,6 +722,30 @@ __global__ __launch_bounds__(BLOCK) void k_time_modes_inv_gathered_tile(Dev dt, 
     }
 }
 
+// The time transforms around the solve of one GPU: b^ = Q^T b of `in` into `out` (mode space), and phi = Q x^ back.  `direct`: the
+// sweeps solve (no warm start, no mean removal); the kernels are chosen as step 1 chooses them (cg_solve_impl, dots_laplacian_solve_many)
+void modes_forward(Ctx *c, const double *in, double *out, bool direct) {
+    const Dev &d = c->d;
+    const int gt = xcd_grid(d.n_vtiles);
+    if (direct && time_modes_tile_ok(d))
+        hipLaunchKernelGGL((k_time_modes_tile<true>), dim3(gt), dim3(BLOCK), time_modes_tile_lds(d), c->stream, d, in, out, time_modes_chunk(d));
+    else
+        hipLaunchKernelGGL((k_time_modes<true>), dim3(gt), dim3(BLOCK), 0, c->stream, d, in, out, 1);
+}
+void modes_inverse(Ctx *c, const double *x, double *phi, bool direct) {
+    const Dev &d = c->d;
+    const int gt = xcd_grid(d.n_vtiles);
+    if (time_modes_mfma_ok(d))
+        hipLaunchKernelGGL(k_time_modes_mfma, dim3((d.V + TM_ROWS - 1) / TM_ROWS), dim3(BLOCK), sizeof(double) * TM_ROWS * (d.TP + 1), c->stream, d, d.QpadT,
+                           x, phi);
+    else if (time_modes_tile_ok(d) && direct && d.n_vtiles <= 512)      // small meshes, behind the sweeps: latency-bound, one output per thread (knot: 9.5 -> 6 us; no gain at 10^5 vertices)
+        hipLaunchKernelGGL((k_time_modes_tile<false, 1024>), dim3(gt), dim3(1024), time_modes_tile_lds(d), c->stream, d, x, phi, time_modes_chunk(d));
+    else if (time_modes_tile_ok(d))
+        hipLaunchKernelGGL((k_time_modes_tile<false>), dim3(gt), dim3(BLOCK), time_modes_tile_lds(d), c->stream, d, x, phi, time_modes_chunk(d));
+    else
+        hipLaunchKernelGGL((k_time_modes<false>), dim3(gt), dim3(BLOCK), 0, c->stream, d, x, phi, 0);
+}
+
 // Step 1 for the modes of this context.  Unsharded: also transforms back (phi is complete on return).
 // Sharded: the local mode-space solution stays in dcg.cg_x for the caller to exchange (cg_finish_sharded).
 template <bool MODAL>
@@ -755,10 +779,7 @@ static int cg_solve_impl(Ctx *c, dots_step_stats *stats, bool defer_inverse) {
             // b^ = Q^T b (into p0 as scratch), x^ = Q^T phi (warm start in mode space)
             if (rhs_writes_modes(c)) {
                 // k_rhs_modes (kernels_alm.hip) already left the mode-space right-hand side in cg_p0
-            } else if (direct && time_modes_tile_ok(d))
-                hipLaunchKernelGGL((k_time_modes_tile<true>), dim3(gt), dim3(BLOCK), time_modes_tile_lds(d), c->stream, d, d.cg_b, d.cg_p0, time_modes_chunk(d));
-            else
-                hipLaunchKernelGGL((k_time_modes<true>), dim3(gt), dim3(BLOCK), 0, c->stream, d, d.cg_b, d.cg_p0, 1);
+            } else modes_forward(c, d.cg_b, d.cg_p0, direct);
             if (!direct) hipLaunchKernelGGL((k_time_modes<true>), dim3(gt), dim3(BLOCK), 0, c->stream, d, d.phi, d.cg_x, 0);
             b = d.cg_p0;   // consumed by k_cg_r0 before iteration 0 (which reads no p_old: beta = 0) writes p1
         }
@@ -777,15 +798,7 @@ static int cg_solve_impl(Ctx *c, dots_step_stats *stats, bool defer_inverse) {
     }
     if (rc) return rc;
     if (MODAL && !sharded && !defer_inverse) {
-        if (time_modes_mfma_ok(d))
-            hipLaunchKernelGGL(k_time_modes_mfma, dim3((d.V + TM_ROWS - 1) / TM_ROWS), dim3(BLOCK), sizeof(double) * TM_ROWS * (d.TP + 1), c->stream, d, d.QpadT,
-                               d.cg_x, d.phi);
-        else if (time_modes_tile_ok(d) && direct && d.n_vtiles <= 512)      // small meshes, behind the sweeps: latency-bound, one output per thread (knot: 9.5 -> 6 us; no gain at 10^5 vertices)
-            hipLaunchKernelGGL((k_time_modes_tile<false, 1024>), dim3(gt), dim3(1024), time_modes_tile_lds(d), c->stream, d, d.cg_x, d.phi, time_modes_chunk(d));
-        else if (time_modes_tile_ok(d))
-            hipLaunchKernelGGL((k_time_modes_tile<false>), dim3(gt), dim3(BLOCK), time_modes_tile_lds(d), c->stream, d, d.cg_x, d.phi, time_modes_chunk(d));
-        else
-            hipLaunchKernelGGL((k_time_modes<false>), dim3(gt), dim3(BLOCK), 0, c->stream, d, d.cg_x, d.phi, 0);
+        modes_inverse(c, d.cg_x, d.phi, direct);
         DOTS_HIP(hipGetLastError());
     }
     return 0;

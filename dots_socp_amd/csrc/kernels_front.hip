@@ -127,15 +127,25 @@ __device__ __forceinline__ Vd<1> front_folded_wide(const double *red, int r, int
     return s;
 }
 
+// right-hand sides 1 .. NR-1 of a multi-rhs launch (front_solve_many): rhs 0 is the launch's own vectors and f.W.  The factor entries of a
+// step are loaded ONCE and applied to all NR vectors, the rhs loop innermost: every rhs sees the operations of an NR = 1 launch in the same
+// order (the sums of a thread run over its columns in column order whatever the unroll; the folds are the NR = 1 folds, one rhs after the other)
+template <int NR> struct MoreRhs {
+    static constexpr int M = NR > 1 ? NR - 1 : 1;
+    const double *b[M];
+    double *y[M], *x[M], *W[M];
+};
+#define RHS_PICK(p0, arr, k) ((k) == 0 ? (p0) : mr.arr[(k) > 0 ? (k) - 1 : 0])
+
 // forward sweep of one band of tree heights.  Workgroup = (node, rb <= RB rows); thread = (VEC modes from a, part q of
 // the dot product).  Every load of the loop body is unconditional (rows past the block are clamped to its first row
 // and their sums dropped; planes no child writes hold zeros; the upper triangle of L^-1 is stored as zeros), so that
 // the compiler issues the RB + 1 + KP loads of a step back to back and waits once.
 // RB is the band's exact block size (1, 2 or 4: no duplicate loads); KP the update planes the band's nodes read
 // (0 on the bottom band: leaves only).
-template <int NB, int RB, bool VMAP, int KP, int VEC>
+template <int NB, int RB, bool VMAP, int KP, int VEC, int NR = 1>
 __global__ __launch_bounds__(NB) void k_front_fwd(FrontArgs g, FrontDev f, const FrontWork *__restrict__ desc, int rb, const double *__restrict__ bhat,
-                                                  double *__restrict__ Y) {
+                                                  double *__restrict__ Y, MoreRhs<NR> mr) {
     __shared__ double red[RB * (NB / 64) * 64 * VEC];
     const FrontWork wk = desc[blockIdx.x];
     const SweepNode &nd = wk.nd;
@@ -146,24 +156,26 @@ __global__ __launch_bounds__(NB) void k_front_fwd(FrontArgs g, FrontDev f, const
     const bool wide = (g.TP / VEC) > 64;                         // only with VEC == 1
     const int n = nd.n, m = n + nd.b;
     const double *__restrict__ Fp = f.F + (nd.foff << sh) + a;
-    const double *__restrict__ W0 = f.W + (nd.woff << sh) + a;         // plane 0; plane k is k * m rows further
     const int64_t plane = (int64_t)m << sh;
     const bool live = a < g.ncol;
     const int nr = min(rb, m - row0);
 
-    Vd<VEC> acc[RB];
+    Vd<VEC> acc[RB][NR];
     const double *rowp[RB];
 #pragma unroll
     for (int r = 0; r < RB; ++r) {
 #pragma unroll
-        for (int c = 0; c < VEC; ++c) acc[r].v[c] = 0.0;
+        for (int k = 0; k < NR; ++k)
+#pragma unroll
+            for (int c = 0; c < VEC; ++c) acc[r][k].v[c] = 0.0;
         rowp[r] = Fp + (((int64_t)(r < nr ? row0 + r : row0) * n) << sh);
     }
     // where this thread's (first) update row goes in the parent's plane: loaded now, needed after the fold
     const bool upd0 = q < nr && row0 + q >= n;
     const int cm0 = upd0 ? f.cmap[nd.bdoff + (row0 + q - n)] : 0;
-    Vd<VEC> cp0[KP > 0 ? KP : 1];      // ... and what the children carried to that row
-    if (KP > 0 && upd0 && live) {
+    Vd<VEC> cp0[KP > 0 && NR == 1 ? KP : 1];      // ... and what the children carried to that row (one rhs: loaded now too)
+    if (KP > 0 && NR == 1 && upd0 && live) {
+        const double *__restrict__ W0 = f.W + (nd.woff << sh) + a;
 #pragma unroll
         for (int k = 0; k < KP; ++k) cp0[k] = vload<VEC>(W0 + k * plane + ((int64_t)(row0 + q) << sh));
     }
@@ -173,11 +185,12 @@ __global__ __launch_bounds__(NB) void k_front_fwd(FrontArgs g, FrontDev f, const
     const int jmax = wk.end > 0 ? wk.end : (last < n ? last + 1 : n);
     // U steps of the dot product are loaded before the first is used (merged nodes have long rows: a step per
     // memory round trip would leave the workgroup waiting on latency).  One-mode lanes only: measured +1...7 % on the
-    // merged small meshes, -2 % on the bandwidth-bound two-mode sweeps of torus100k (profiles/studies/band_cuts.txt)
-    constexpr int U = !DOTS_FRONT_UNROLL ? 1 : (VEC > 1 ? DOTS_FRONT_U2 : ((1 + KP + RB) <= 6) ? 4 : (((1 + KP + RB) <= 12) ? 2 : 1));
+    // merged small meshes, -2 % on the bandwidth-bound two-mode sweeps of torus100k (profiles/studies/band_cuts.txt).
+    // Several right-hand sides: their vectors are loads enough in flight
+    constexpr int U = NR > 1 ? 1 : (!DOTS_FRONT_UNROLL ? 1 : (VEC > 1 ? DOTS_FRONT_U2 : ((1 + KP + RB) <= 6) ? 4 : (((1 + KP + RB) <= 12) ? 2 : 1)));
     if (live) {
         for (int j0 = wk.lo + q; j0 < jmax; j0 += U * Q) {
-            Vd<VEC> wb[U], wp[U][KP > 0 ? KP : 1], fv[U][RB];
+            Vd<VEC> wb[U][NR], wp[U][KP > 0 ? KP : 1][NR], fv[U][RB];
             bool ok[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
@@ -186,9 +199,13 @@ __global__ __launch_bounds__(NB) void k_front_fwd(FrontArgs g, FrontDev f, const
                 if (ok[u]) {
                     const int64_t jo = (int64_t)j << sh;
                     const int64_t row = VMAP ? (int64_t)f.vmap[nd.k0 + j] : (int64_t)(nd.k0 + j);
-                    wb[u] = vload<VEC>(bhat + (row << sh) + a);
 #pragma unroll
-                    for (int k = 0; k < KP; ++k) wp[u][k] = vload<VEC>(W0 + k * plane + jo);
+                    for (int s = 0; s < NR; ++s) {
+                        wb[u][s] = vload<VEC>(RHS_PICK(bhat, b, s) + (row << sh) + a);
+                        const double *__restrict__ W0 = RHS_PICK(f.W, W, s) + (nd.woff << sh) + a;
+#pragma unroll
+                        for (int k = 0; k < KP; ++k) wp[u][k][s] = vload<VEC>(W0 + k * plane + jo);
+                    }
 #pragma unroll
                     for (int r = 0; r < RB; ++r) fv[u][r] = vload<VEC>(rowp[r] + jo);
                 }
@@ -196,45 +213,57 @@ __global__ __launch_bounds__(NB) void k_front_fwd(FrontArgs g, FrontDev f, const
 #pragma unroll
             for (int u = 0; u < U; ++u)
 #pragma unroll
-                for (int c = 0; c < VEC; ++c) {
-                    double w = wb[u].v[c];
-                    if (KP > 0) {
-                        double t = wp[u][0].v[c];
+                for (int s = 0; s < NR; ++s)
 #pragma unroll
-                        for (int k = 1; k < KP; ++k) t += wp[u][k].v[c];
-                        w -= t;
-                    }
-                    if (ok[u]) {
+                    for (int c = 0; c < VEC; ++c) {
+                        double w = wb[u][s].v[c];
+                        if (KP > 0) {
+                            double t = wp[u][0][s].v[c];
 #pragma unroll
-                        for (int r = 0; r < RB; ++r) acc[r].v[c] += fv[u][r].v[c] * w;
+                            for (int k = 1; k < KP; ++k) t += wp[u][k][s].v[c];
+                            w -= t;
+                        }
+                        if (ok[u]) {
+#pragma unroll
+                            for (int r = 0; r < RB; ++r) acc[r][s].v[c] += fv[u][r].v[c] * w;
+                        }
                     }
-                }
         }
     }
-    if (VEC == 1 && wide) front_fold_wide<NB, RB>(reinterpret_cast<Vd<1>(&)[RB]>(acc), red, tid);
-    else front_fold<NB, RB, VEC>(acc, red, g.TP, a, tid);
-    for (int r = q; r < nr && live; r += Q) {
-        Vd<VEC> s;
-        if (VEC == 1 && wide) s.v[0] = front_folded_wide<NB>(red, r, sh, a).v[0];
-        else s = front_folded<NB, VEC>(red, r, g.TP, a);
-        const int i = row0 + r;
-        if (i < n) {
-            vstore<VEC>(Y + (front_row(f, nd.k0 + i) << sh) + a, s);
-        } else {   // update row: carry the children's contributions on, hand the sum to the parent's plane
-            if (KP > 0) {
-                Vd<VEC> cp[KP > 0 ? KP : 1];
 #pragma unroll
-                for (int k = 0; k < KP; ++k) cp[k] = r == q ? cp0[k] : vload<VEC>(W0 + k * plane + ((int64_t)i << sh));
+    for (int s = 0; s < NR; ++s) {
+        if (s > 0) __syncthreads();      // (the folds of the rhs before have read their sums)
+        Vd<VEC> as[RB];
 #pragma unroll
-                for (int c = 0; c < VEC; ++c) {
-                    double u = cp[0].v[c];
+        for (int r = 0; r < RB; ++r) as[r] = acc[r][s];
+        if (VEC == 1 && wide) front_fold_wide<NB, RB>(reinterpret_cast<Vd<1>(&)[RB]>(as), red, tid);
+        else front_fold<NB, RB, VEC>(as, red, g.TP, a, tid);
+        double *__restrict__ Ys = RHS_PICK(Y, y, s);
+        double *__restrict__ Ws = RHS_PICK(f.W, W, s);
+        const double *__restrict__ W0 = Ws + (nd.woff << sh) + a;
+        for (int r = q; r < nr && live; r += Q) {
+            Vd<VEC> sm;
+            if (VEC == 1 && wide) sm.v[0] = front_folded_wide<NB>(red, r, sh, a).v[0];
+            else sm = front_folded<NB, VEC>(red, r, g.TP, a);
+            const int i = row0 + r;
+            if (i < n) {
+                vstore<VEC>(Ys + (front_row(f, nd.k0 + i) << sh) + a, sm);
+            } else {   // update row: carry the children's contributions on, hand the sum to the parent's plane
+                if (KP > 0) {
+                    Vd<VEC> cp[KP > 0 ? KP : 1];
 #pragma unroll
-                    for (int k = 1; k < KP; ++k) u += cp[k].v[c];
-                    s.v[c] += u;
+                    for (int k = 0; k < KP; ++k) cp[k] = (NR == 1 && r == q) ? cp0[k] : vload<VEC>(W0 + k * plane + ((int64_t)i << sh));
+#pragma unroll
+                    for (int c = 0; c < VEC; ++c) {
+                        double u = cp[0].v[c];
+#pragma unroll
+                        for (int k = 1; k < KP; ++k) u += cp[k].v[c];
+                        sm.v[c] += u;
+                    }
                 }
+                const int cm = r == q ? cm0 : f.cmap[nd.bdoff + (i - n)];
+                vstore<VEC>(Ws + ((nd.parent_w + cm) << sh) + a, sm);
             }
-            const int cm = r == q ? cm0 : f.cmap[nd.bdoff + (i - n)];
-            vstore<VEC>(f.W + ((nd.parent_w + cm) << sh) + a, s);
         }
     }
 }
@@ -252,10 +281,11 @@ __global__ __launch_bounds__(NB) void k_front_fwd(FrontArgs g, FrontDev f, const
 constexpr size_t FWD_ROWS_LDS_MAX = 40 * 1024;      // LDS a workgroup of the row kernel may take for w (4 workgroups per CU stay resident)
 constexpr double FWD_ROWS_MEAN_MAX = 30.0;          // bands whose rows are longer on average keep the fold kernel unless they read 4+ planes (DOTS_FRONT_ROWS=2: no limit)
 constexpr int FWD_ROWS_PAD = 2;      // doubles of padding per staged row of w (rows of exactly TP doubles would share their banks)
-template <bool VMAP, int KP, int VEC>
+// Several right-hand sides (NR > 1): one region of LDS per rhs, the row's entries loaded once for all of them.
+template <bool VMAP, int KP, int VEC, int NR = 1>
 __global__ __launch_bounds__(256) void k_front_fwd_rows(FrontArgs g, FrontDev f, const FrontWork *__restrict__ desc, int qw_shift,
-                                                       const double *__restrict__ bhat, double *__restrict__ Y) {
-    extern __shared__ __attribute__((aligned(16))) double wsh[];      // [columns of the block][TP + FWD_ROWS_PAD]
+                                                       const double *__restrict__ bhat, double *__restrict__ Y, MoreRhs<NR> mr) {
+    extern __shared__ __attribute__((aligned(16))) double wsh[];      // [rhs][columns of the block][TP + FWD_ROWS_PAD]
     const FrontWork wk = desc[blockIdx.x];
     const SweepNode &nd = wk.nd;
     const int sh = g.sh, tid = threadIdx.x;
@@ -271,16 +301,20 @@ __global__ __launch_bounds__(256) void k_front_fwd_rows(FrontArgs g, FrontDev f,
     const int last = row0 + nr - 1;
     const int jmax = wk.end > 0 ? wk.end : (last < n ? last + 1 : n);
     const int64_t plane = (int64_t)m << sh;
-    const double *__restrict__ W0 = f.W + (nd.woff << sh) + a;         // plane 0; plane k is k * m rows further
     const int ldw = g.TP + FWD_ROWS_PAD;
+    const int64_t rgn = (int64_t)(jmax - lo) * ldw;              // LDS of one rhs
     // where an update row goes in the parent's plane, and what the children carried to it: loaded now, needed after the loop
     const bool store = part == 0 && rowok && live;
     const bool upd = store && i >= n;
     const int cm = upd ? f.cmap[nd.bdoff + (i - n)] : 0;
-    Vd<VEC> cp[KP > 0 ? KP : 1];
+    Vd<VEC> cp[KP > 0 ? KP : 1][NR];
     if (KP > 0 && upd) {
 #pragma unroll
-        for (int k = 0; k < KP; ++k) cp[k] = vload<VEC>(W0 + k * plane + ((int64_t)i << sh));
+        for (int s = 0; s < NR; ++s) {
+            const double *__restrict__ W0 = RHS_PICK(f.W, W, s) + (nd.woff << sh) + a;      // plane 0; plane k is k * m rows further
+#pragma unroll
+            for (int k = 0; k < KP; ++k) cp[k][s] = vload<VEC>(W0 + k * plane + ((int64_t)i << sh));
+        }
     }
     // The row's entries are loaded one BATCH of U columns ahead of their use: the first batch is in flight while w is staged
     // (it does not depend on w), every later one while the batch before it is multiplied -- a row of 25 columns is 4-5 memory
@@ -301,29 +335,35 @@ __global__ __launch_bounds__(256) void k_front_fwd_rows(FrontArgs g, FrontDev f,
     if (live) {
         for (int js = lo + grp; js < jmax; js += 256 >> shv) {
             const int64_t row = VMAP ? (int64_t)f.vmap[nd.k0 + js] : (int64_t)(nd.k0 + js);
-            Vd<VEC> w = vload<VEC>(bhat + (row << sh) + a);
-            if (KP > 0) {
-                Vd<VEC> wp[KP > 0 ? KP : 1];
 #pragma unroll
-                for (int k = 0; k < KP; ++k) wp[k] = vload<VEC>(W0 + k * plane + ((int64_t)js << sh));
+            for (int s = 0; s < NR; ++s) {
+                Vd<VEC> w = vload<VEC>(RHS_PICK(bhat, b, s) + (row << sh) + a);
+                if (KP > 0) {
+                    const double *__restrict__ W0 = RHS_PICK(f.W, W, s) + (nd.woff << sh) + a;
+                    Vd<VEC> wp[KP > 0 ? KP : 1];
 #pragma unroll
-                for (int c = 0; c < VEC; ++c) {
-                    double t = wp[0].v[c];
+                    for (int k = 0; k < KP; ++k) wp[k] = vload<VEC>(W0 + k * plane + ((int64_t)js << sh));
 #pragma unroll
-                    for (int k = 1; k < KP; ++k) t += wp[k].v[c];
-                    w.v[c] -= t;
+                    for (int c = 0; c < VEC; ++c) {
+                        double t = wp[0].v[c];
+#pragma unroll
+                        for (int k = 1; k < KP; ++k) t += wp[k].v[c];
+                        w.v[c] -= t;
+                    }
                 }
+                vstore<VEC>(wsh + s * rgn + (js - lo) * ldw + a, w);
             }
-            vstore<VEC>(wsh + (js - lo) * ldw + a, w);
         }
     }
     __syncthreads();
-    Vd<VEC> acc;
+    Vd<VEC> acc[NR];
 #pragma unroll
-    for (int c = 0; c < VEC; ++c) acc.v[c] = 0.0;
+    for (int s = 0; s < NR; ++s)
+#pragma unroll
+        for (int c = 0; c < VEC; ++c) acc[s].v[c] = 0.0;
     const double *ws = wsh + a - lo * ldw;
     while (j < jend) {
-        Vd<VEC> nx[U], wv[U];
+        Vd<VEC> nx[U], wv[U][NR];
         const int jn = j + U * QW;
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -336,35 +376,45 @@ __global__ __launch_bounds__(256) void k_front_fwd_rows(FrontArgs g, FrontDev f,
         for (int u = 0; u < U; ++u) {
             const int ju = j + u * QW;
 #pragma unroll
-            for (int c = 0; c < VEC; ++c) wv[u].v[c] = 0.0;
-            if (ju < jend) wv[u] = vload<VEC>(ws + ju * ldw);
+            for (int s = 0; s < NR; ++s) {
+#pragma unroll
+                for (int c = 0; c < VEC; ++c) wv[u][s].v[c] = 0.0;
+                if (ju < jend) wv[u][s] = vload<VEC>(ws + s * rgn + ju * ldw);
+            }
         }
 #pragma unroll
         for (int u = 0; u < U; ++u)
 #pragma unroll
-            for (int c = 0; c < VEC; ++c) acc.v[c] += fv[u].v[c] * wv[u].v[c];
+            for (int s = 0; s < NR; ++s)
+#pragma unroll
+                for (int c = 0; c < VEC; ++c) acc[s].v[c] += fv[u].v[c] * wv[u][s].v[c];
 #pragma unroll
         for (int u = 0; u < U; ++u) fv[u] = nx[u];
         j = jn;
     }
-    for (int o = 1 << shv; o < (1 << (shv + qw_shift)); o <<= 1) {
 #pragma unroll
-        for (int c = 0; c < VEC; ++c) acc.v[c] += __shfl_xor(acc.v[c], o, 64);
-    }
+    for (int s = 0; s < NR; ++s)
+        for (int o = 1 << shv; o < (1 << (shv + qw_shift)); o <<= 1) {
+#pragma unroll
+            for (int c = 0; c < VEC; ++c) acc[s].v[c] += __shfl_xor(acc[s].v[c], o, 64);
+        }
     if (store) {
-        if (i < n) {
-            vstore<VEC>(Y + (front_row(f, nd.k0 + i) << sh) + a, acc);
-        } else {   // update row: carry the children's contributions on, hand the sum to the parent's plane
-            if (KP > 0) {
 #pragma unroll
-                for (int c = 0; c < VEC; ++c) {
-                    double u = cp[0].v[c];
+        for (int s = 0; s < NR; ++s) {
+            if (i < n) {
+                vstore<VEC>(RHS_PICK(Y, y, s) + (front_row(f, nd.k0 + i) << sh) + a, acc[s]);
+            } else {   // update row: carry the children's contributions on, hand the sum to the parent's plane
+                if (KP > 0) {
 #pragma unroll
-                    for (int k = 1; k < KP; ++k) u += cp[k].v[c];
-                    acc.v[c] += u;
+                    for (int c = 0; c < VEC; ++c) {
+                        double u = cp[0][s].v[c];
+#pragma unroll
+                        for (int k = 1; k < KP; ++k) u += cp[k][s].v[c];
+                        acc[s].v[c] += u;
+                    }
                 }
+                vstore<VEC>(RHS_PICK(f.W, W, s) + ((nd.parent_w + cm) << sh) + a, acc[s]);
             }
-            vstore<VEC>(f.W + ((nd.parent_w + cm) << sh) + a, acc);
         }
     }
 }
@@ -372,9 +422,9 @@ __global__ __launch_bounds__(256) void k_front_fwd_rows(FrontArgs g, FrontDev f,
 // backward sweep of one band.  Workgroup = (node, cb <= RB columns of ONE member of the node).  Same load discipline.
 // The rows that can be nonzero in these columns: the member's own rows from the block's first column on, the rows of
 // its ancestors inside the band (wk.rs / wk.re, wk.lo ranges), the boundary rows.
-template <int NB, int RB, bool VMAP, int VEC>
+template <int NB, int RB, bool VMAP, int VEC, int NR = 1>
 __global__ __launch_bounds__(NB) void k_front_bwd(FrontArgs g, FrontDev f, const FrontWork *__restrict__ desc, int cb, const double *__restrict__ Y,
-                                                  double *X) {
+                                                  double *X, MoreRhs<NR> mr) {
     __shared__ double red[RB * (NB / 64) * 64 * VEC];
     const FrontWork wk = desc[blockIdx.x];
     const SweepNode &nd = wk.nd;
@@ -389,15 +439,17 @@ __global__ __launch_bounds__(NB) void k_front_bwd(FrontArgs g, FrontDev f, const
     const bool live = a < g.ncol;
     const int nc = min(cb, wk.end - col0);
 
-    Vd<VEC> acc[RB];
+    Vd<VEC> acc[RB][NR];
     int64_t co[RB];      // column offsets (columns past the block: its first column, sums dropped)
 #pragma unroll
     for (int r = 0; r < RB; ++r) {
 #pragma unroll
-        for (int c = 0; c < VEC; ++c) acc[r].v[c] = 0.0;
+        for (int s = 0; s < NR; ++s)
+#pragma unroll
+            for (int c = 0; c < VEC; ++c) acc[r][s].v[c] = 0.0;
         co[r] = (int64_t)(r < nc ? col0 + r : col0) << sh;
     }
-    constexpr int U = !DOTS_FRONT_UNROLL ? 1 : (VEC > 1 ? DOTS_FRONT_U2B : ((1 + RB) <= 4) ? 4 : 2);      // as in the forward sweep
+    constexpr int U = NR > 1 ? 1 : (!DOTS_FRONT_UNROLL ? 1 : (VEC > 1 ? DOTS_FRONT_U2B : ((1 + RB) <= 4) ? 4 : 2));      // as in the forward sweep
     if (live) {
         // rows of the separators: y.  Column i of L^-1 is zero above the diagonal: start at the block's first column
 #pragma unroll
@@ -405,7 +457,7 @@ __global__ __launch_bounds__(NB) void k_front_bwd(FrontArgs g, FrontDev f, const
             if (rg < wk.lo) {
                 const int r1 = wk.re[rg];
                 for (int j0 = wk.rs[rg] + q; j0 < r1; j0 += U * Q) {
-                    Vd<VEC> v[U], fv[U][RB];
+                    Vd<VEC> v[U][NR], fv[U][RB];
                     bool ok[U];
 #pragma unroll
                     for (int u = 0; u < U; ++u) {
@@ -413,7 +465,8 @@ __global__ __launch_bounds__(NB) void k_front_bwd(FrontArgs g, FrontDev f, const
                         ok[u] = u == 0 || j < r1;
                         if (ok[u]) {
                             const int64_t row = VMAP ? (int64_t)f.vmap[nd.k0 + j] : (int64_t)(nd.k0 + j);
-                            v[u] = vload<VEC>(Y + (row << sh) + a);
+#pragma unroll
+                            for (int s = 0; s < NR; ++s) v[u][s] = vload<VEC>(RHS_PICK(Y, y, s) + (row << sh) + a);
                             const double *__restrict__ Fj = Fp + (((int64_t)j * n) << sh);
 #pragma unroll
                             for (int r = 0; r < RB; ++r) fv[u][r] = vload<VEC>(Fj + co[r]);
@@ -425,21 +478,25 @@ __global__ __launch_bounds__(NB) void k_front_bwd(FrontArgs g, FrontDev f, const
 #pragma unroll
                             for (int r = 0; r < RB; ++r)
 #pragma unroll
-                                for (int c = 0; c < VEC; ++c) acc[r].v[c] += fv[u][r].v[c] * v[u].v[c];
+                                for (int s = 0; s < NR; ++s)
+#pragma unroll
+                                    for (int c = 0; c < VEC; ++c) acc[r][s].v[c] += fv[u][r].v[c] * v[u][s].v[c];
                         }
                 }
             }
         }
         // boundary rows: -x of the ancestors (written by the launches of the bands above)
         for (int j0 = n + q; j0 < m; j0 += U * Q) {
-            Vd<VEC> v[U], fv[U][RB];
+            Vd<VEC> v[U][NR], fv[U][RB];
             bool ok[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int j = j0 + u * Q;
                 ok[u] = u == 0 || j < m;
                 if (ok[u]) {
-                    v[u] = vload<VEC>(X + ((int64_t)bdv[j - n] << sh) + a);
+                    const int64_t bv = (int64_t)bdv[j - n] << sh;
+#pragma unroll
+                    for (int s = 0; s < NR; ++s) v[u][s] = vload<VEC>(RHS_PICK(X, x, s) + bv + a);
                     const double *__restrict__ Fj = Fp + (((int64_t)j * n) << sh);
 #pragma unroll
                     for (int r = 0; r < RB; ++r) fv[u][r] = vload<VEC>(Fj + co[r]);
@@ -451,17 +508,27 @@ __global__ __launch_bounds__(NB) void k_front_bwd(FrontArgs g, FrontDev f, const
 #pragma unroll
                     for (int r = 0; r < RB; ++r)
 #pragma unroll
-                        for (int c = 0; c < VEC; ++c) acc[r].v[c] -= fv[u][r].v[c] * v[u].v[c];
+                        for (int s = 0; s < NR; ++s)
+#pragma unroll
+                            for (int c = 0; c < VEC; ++c) acc[r][s].v[c] -= fv[u][r].v[c] * v[u][s].v[c];
                 }
         }
     }
-    if (VEC == 1 && wide) front_fold_wide<NB, RB>(reinterpret_cast<Vd<1>(&)[RB]>(acc), red, tid);
-    else front_fold<NB, RB, VEC>(acc, red, g.TP, a, tid);
-    for (int r = q; r < nc && live; r += Q) {
-        Vd<VEC> s;
-        if (VEC == 1 && wide) s.v[0] = front_folded_wide<NB>(red, r, sh, a).v[0];
-        else s = front_folded<NB, VEC>(red, r, g.TP, a);
-        vstore<VEC>(X + (front_row(f, nd.k0 + col0 + r) << sh) + a, s);
+#pragma unroll
+    for (int s = 0; s < NR; ++s) {
+        if (s > 0) __syncthreads();      // (the folds of the rhs before have read their sums)
+        Vd<VEC> as[RB];
+#pragma unroll
+        for (int r = 0; r < RB; ++r) as[r] = acc[r][s];
+        if (VEC == 1 && wide) front_fold_wide<NB, RB>(reinterpret_cast<Vd<1>(&)[RB]>(as), red, tid);
+        else front_fold<NB, RB, VEC>(as, red, g.TP, a, tid);
+        double *Xs = RHS_PICK(X, x, s);
+        for (int r = q; r < nc && live; r += Q) {
+            Vd<VEC> sm;
+            if (VEC == 1 && wide) sm.v[0] = front_folded_wide<NB>(red, r, sh, a).v[0];
+            else sm = front_folded<NB, VEC>(red, r, g.TP, a);
+            vstore<VEC>(Xs + (front_row(f, nd.k0 + col0 + r) << sh) + a, sm);
+        }
     }
 }
 
@@ -496,42 +563,53 @@ __device__ __forceinline__ void leaf_row_load(Vd<VEC> (&s)[LEAF_PRE], const doub
         if (u < n && i < n) s[u] = vload<VEC>(P + (leaf_entry(i, u) << sh));
     }
 }
-template <int VEC>
-__device__ __forceinline__ Vd<VEC> leaf_row_dot(const Vd<VEC> (&s)[LEAF_PRE], const double *__restrict__ P, const double *vsh, int i, int n, int TP, int sh) {
-    Vd<VEC> acc;
+// the rows' sums for NR vectors, vsh + k * rgn the k-th (each entry of S loaded once)
+template <int VEC, int NR>
+__device__ __forceinline__ void leaf_row_dot(Vd<VEC> (&acc)[NR], const Vd<VEC> (&s)[LEAF_PRE], const double *__restrict__ P, const double *vsh, int64_t rgn,
+                                             int i, int n, int TP, int sh) {
 #pragma unroll
-    for (int c = 0; c < VEC; ++c) acc.v[c] = 0.0;
+    for (int k = 0; k < NR; ++k)
+#pragma unroll
+        for (int c = 0; c < VEC; ++c) acc[k].v[c] = 0.0;
 #pragma unroll
     for (int u = 0; u < LEAF_PRE; ++u)
         if (u < n) {
-            const Vd<VEC> v = vload<VEC>(vsh + u * TP);
 #pragma unroll
-            for (int c = 0; c < VEC; ++c) acc.v[c] += s[u].v[c] * v.v[c];
+            for (int k = 0; k < NR; ++k) {
+                const Vd<VEC> v = vload<VEC>(vsh + k * rgn + u * TP);
+#pragma unroll
+                for (int c = 0; c < VEC; ++c) acc[k].v[c] += s[u].v[c] * v.v[c];
+            }
         }
     for (int j = LEAF_PRE; j < n; ++j) {
-        const Vd<VEC> s0 = vload<VEC>(P + (leaf_entry(i, j) << sh)), v0 = vload<VEC>(vsh + j * TP);
+        const Vd<VEC> s0 = vload<VEC>(P + (leaf_entry(i, j) << sh));
 #pragma unroll
-        for (int c = 0; c < VEC; ++c) acc.v[c] += s0.v[c] * v0.v[c];
+        for (int k = 0; k < NR; ++k) {
+            const Vd<VEC> v0 = vload<VEC>(vsh + k * rgn + j * TP);
+#pragma unroll
+            for (int c = 0; c < VEC; ++c) acc[k].v[c] += s0.v[c] * v0.v[c];
+        }
     }
-    return acc;
 }
-template <int VEC>
-__device__ __forceinline__ Vd<VEC> leaf_row(const double *__restrict__ P, const double *vsh, int i, int n, int TP, int sh) {
+template <int VEC, int NR>
+__device__ __forceinline__ void leaf_row(Vd<VEC> (&acc)[NR], const double *__restrict__ P, const double *vsh, int64_t rgn, int i, int n, int TP, int sh) {
     Vd<VEC> s[LEAF_PRE];
     leaf_row_load<VEC>(s, P, i, n, sh);
-    return leaf_row_dot<VEC>(s, P, vsh, i, n, TP, sh);
+    leaf_row_dot<VEC, NR>(acc, s, P, vsh, rgn, i, n, TP, sh);
 }
 
-template <int VEC, int NB, bool TAB>
+// (several right-hand sides: one region of LDS per rhs, every entry of S and every coupling record loaded once for all of them)
+template <int VEC, int NB, bool TAB, int NR = 1>
 __global__ __launch_bounds__(NB) void k_front_leaf_fwd(FrontArgs g, FrontDev f, const int *__restrict__ rowptr, const int *__restrict__ col,
-                                                       const double *__restrict__ val, const double *__restrict__ bhat) {
-    extern __shared__ __attribute__((aligned(16))) double lsh[];      // w [n][TP], then t [n][TP]
+                                                       const double *__restrict__ val, const double *__restrict__ bhat, MoreRhs<NR> mr) {
+    extern __shared__ __attribute__((aligned(16))) double lsh[];      // per rhs: w [n][TP], then t [n][TP]
     const LeafWork lw = f.leaf_desc[blockIdx.x];
     const int sh = g.sh, TP = g.TP, tid = threadIdx.x;
     const int shv = VEC == 2 ? sh - 1 : sh;
     const int a = (tid & ((1 << shv) - 1)) * VEC, grp = tid >> shv, NG = NB >> shv;
     const int n = lw.n, b = lw.b, k0 = lw.k0;
     const bool live = a < g.ncol;
+    const int64_t rgn = (int64_t)2 * n * TP;
     double *wsh = lsh + a, *tsh = lsh + n * TP + a;
     const double *__restrict__ S = f.leafS + (lw.soff << sh) + a;
     Vd<VEC> srow[LEAF_PRE];
@@ -558,18 +636,31 @@ __global__ __launch_bounds__(NB) void k_front_leaf_fwd(FrontArgs g, FrontDev f, 
         eb1 = upd1 ? rowptr[vb1] : 0; ee1 = upd1 ? rowptr[vb1 + 1] : 0;
     }
     if (live)
-        for (int j = grp; j < n; j += NG) vstore<VEC>(wsh + j * TP, vload<VEC>(bhat + ((int64_t)(k0 + j) << sh) + a));
+        for (int j = grp; j < n; j += NG)
+#pragma unroll
+            for (int s = 0; s < NR; ++s) vstore<VEC>(wsh + s * rgn + j * TP, vload<VEC>(RHS_PICK(bhat, b, s) + ((int64_t)(k0 + j) << sh) + a));
     __syncthreads();
     if (live) {
-        if (grp < n) vstore<VEC>(tsh + grp * TP, leaf_row_dot<VEC>(srow, S, wsh, grp, n, TP, sh));
-        for (int i = grp + NG; i < n; i += NG) vstore<VEC>(tsh + i * TP, leaf_row<VEC>(S, wsh, i, n, TP, sh));
+        Vd<VEC> t[NR];
+        if (grp < n) {
+            leaf_row_dot<VEC, NR>(t, srow, S, wsh, rgn, grp, n, TP, sh);
+#pragma unroll
+            for (int s = 0; s < NR; ++s) vstore<VEC>(tsh + s * rgn + grp * TP, t[s]);
+        }
+        for (int i = grp + NG; i < n; i += NG) {
+            leaf_row<VEC, NR>(t, S, wsh, rgn, i, n, TP, sh);
+#pragma unroll
+            for (int s = 0; s < NR; ++s) vstore<VEC>(tsh + s * rgn + i * TP, t[s]);
+        }
     }
     __syncthreads();
     if (!live) return;
     for (int r = grp; r < b; r += NG) {
-        Vd<VEC> acc;
+        Vd<VEC> acc[NR];
 #pragma unroll
-        for (int c = 0; c < VEC; ++c) acc.v[c] = 0.0;
+        for (int s = 0; s < NR; ++s)
+#pragma unroll
+            for (int c = 0; c < VEC; ++c) acc[s].v[c] = 0.0;
         int cm;
         if (TAB) {      // (padded entries: value 0 at position 0 -- t is finite)
             cm = cm0;
@@ -579,11 +670,13 @@ __global__ __launch_bounds__(NB) void k_front_leaf_fwd(FrontArgs g, FrontDev f, 
                 for (int k = 0; k < LEAF_KC; ++k) { ru0[k] = br[r].u[k]; rv0[k] = br[r].v[k]; }
             }
 #pragma unroll
-            for (int k = 0; k < LEAF_KC; ++k) {
-                const Vd<VEC> t = vload<VEC>(tsh + ru0[k] * TP);
+            for (int k = 0; k < LEAF_KC; ++k)
 #pragma unroll
-                for (int c = 0; c < VEC; ++c) acc.v[c] += rv0[k] * t.v[c];
-            }
+                for (int s = 0; s < NR; ++s) {
+                    const Vd<VEC> t = vload<VEC>(tsh + s * rgn + ru0[k] * TP);
+#pragma unroll
+                    for (int c = 0; c < VEC; ++c) acc[s].v[c] += rv0[k] * t.v[c];
+                }
         } else {
             const bool p0 = r == grp, p1 = r == grp + NG;
             const int vb = p0 ? vb0 : (p1 ? vb1 : f.bd_vertex[lw.bdoff + r]);
@@ -593,26 +686,31 @@ __global__ __launch_bounds__(NB) void k_front_leaf_fwd(FrontArgs g, FrontDev f, 
                 const unsigned u = (unsigned)(col[e] - k0);
                 if (u < (unsigned)n) {
                     const double kv = val[e];
-                    const Vd<VEC> t = vload<VEC>(tsh + (int)u * TP);
 #pragma unroll
-                    for (int c = 0; c < VEC; ++c) acc.v[c] += kv * t.v[c];
+                    for (int s = 0; s < NR; ++s) {
+                        const Vd<VEC> t = vload<VEC>(tsh + s * rgn + (int)u * TP);
+#pragma unroll
+                        for (int c = 0; c < VEC; ++c) acc[s].v[c] += kv * t.v[c];
+                    }
                 }
             }
         }
-        vstore<VEC>(f.W + ((lw.parent_w + cm) << sh) + a, acc);
+#pragma unroll
+        for (int s = 0; s < NR; ++s) vstore<VEC>(RHS_PICK(f.W, W, s) + ((lw.parent_w + cm) << sh) + a, acc[s]);
     }
 }
 
-template <int VEC, int NB, bool TAB>
+template <int VEC, int NB, bool TAB, int NR = 1>
 __global__ __launch_bounds__(NB) void k_front_leaf_bwd(FrontArgs g, FrontDev f, const int *__restrict__ rowptr, const int *__restrict__ col,
-                                                       const double *__restrict__ val, const double *__restrict__ bhat, double *X) {
-    extern __shared__ __attribute__((aligned(16))) double lsh[];      // b[sep] - g  [n][TP]
+                                                       const double *__restrict__ val, const double *__restrict__ bhat, double *X, MoreRhs<NR> mr) {
+    extern __shared__ __attribute__((aligned(16))) double lsh[];      // per rhs: b[sep] - g  [n][TP]
     const LeafWork lw = f.leaf_desc[blockIdx.x];
     const int sh = g.sh, TP = g.TP, tid = threadIdx.x;
     const int shv = VEC == 2 ? sh - 1 : sh;
     const int a = (tid & ((1 << shv) - 1)) * VEC, grp = tid >> shv, NG = NB >> shv;
     const int n = lw.n, k0 = lw.k0;
     const bool live = a < g.ncol;
+    const int64_t rgn = (int64_t)n * TP;
     double *rsh = lsh + a;
     const double *__restrict__ S = f.leafS + (lw.soff << sh) + a;
     Vd<VEC> srow[LEAF_PRE];
@@ -620,15 +718,21 @@ __global__ __launch_bounds__(NB) void k_front_leaf_bwd(FrontArgs g, FrontDev f, 
     if (live)
         for (int j = grp; j < n; j += NG) {
             const int v = k0 + j;
-            Vd<VEC> acc = vload<VEC>(bhat + ((int64_t)v << sh) + a);
+            Vd<VEC> acc[NR];
+#pragma unroll
+            for (int s = 0; s < NR; ++s) acc[s] = vload<VEC>(RHS_PICK(bhat, b, s) + ((int64_t)v << sh) + a);
             if (TAB) {
                 const LeafSepRow &R = f.leaf_sep[v];
                 const int cnt = R.cnt;
                 for (int k = 0; k < cnt; ++k) {
                     const double kv = R.v[k];
-                    const Vd<VEC> x = vload<VEC>(X + ((int64_t)R.u[k] << sh) + a);
+                    const int64_t uo = (int64_t)R.u[k] << sh;
 #pragma unroll
-                    for (int c = 0; c < VEC; ++c) acc.v[c] -= kv * x.v[c];
+                    for (int s = 0; s < NR; ++s) {
+                        const Vd<VEC> x = vload<VEC>(RHS_PICK(X, x, s) + uo + a);
+#pragma unroll
+                        for (int c = 0; c < VEC; ++c) acc[s].v[c] -= kv * x.v[c];
+                    }
                 }
             } else {
                 const int e1 = rowptr[v + 1];
@@ -636,18 +740,31 @@ __global__ __launch_bounds__(NB) void k_front_leaf_bwd(FrontArgs g, FrontDev f, 
                     const int u = col[e];
                     if ((unsigned)(u - k0) >= (unsigned)n) {      // outside the leaf: a boundary vertex, solved by a launch of the bands above
                         const double kv = val[e];
-                        const Vd<VEC> x = vload<VEC>(X + ((int64_t)u << sh) + a);
 #pragma unroll
-                        for (int c = 0; c < VEC; ++c) acc.v[c] -= kv * x.v[c];
+                        for (int s = 0; s < NR; ++s) {
+                            const Vd<VEC> x = vload<VEC>(RHS_PICK(X, x, s) + ((int64_t)u << sh) + a);
+#pragma unroll
+                            for (int c = 0; c < VEC; ++c) acc[s].v[c] -= kv * x.v[c];
+                        }
                     }
                 }
             }
-            vstore<VEC>(rsh + j * TP, acc);
+#pragma unroll
+            for (int s = 0; s < NR; ++s) vstore<VEC>(rsh + s * rgn + j * TP, acc[s]);
         }
     __syncthreads();
     if (!live) return;
-    if (grp < n) vstore<VEC>(X + ((int64_t)(k0 + grp) << sh) + a, leaf_row_dot<VEC>(srow, S, rsh, grp, n, TP, sh));
-    for (int i = grp + NG; i < n; i += NG) vstore<VEC>(X + ((int64_t)(k0 + i) << sh) + a, leaf_row<VEC>(S, rsh, i, n, TP, sh));
+    Vd<VEC> xo[NR];
+    if (grp < n) {
+        leaf_row_dot<VEC, NR>(xo, srow, S, rsh, rgn, grp, n, TP, sh);
+#pragma unroll
+        for (int s = 0; s < NR; ++s) vstore<VEC>(RHS_PICK(X, x, s) + ((int64_t)(k0 + grp) << sh) + a, xo[s]);
+    }
+    for (int i = grp + NG; i < n; i += NG) {
+        leaf_row<VEC, NR>(xo, S, rsh, rgn, i, n, TP, sh);
+#pragma unroll
+        for (int s = 0; s < NR; ++s) vstore<VEC>(RHS_PICK(X, x, s) + ((int64_t)(k0 + i) << sh) + a, xo[s]);
+    }
 }
 
 // the coupling records of every leaf from the CSR (once per factorisation); *overflow is set when a row holds more entries than a record
@@ -788,19 +905,23 @@ static bool front_two_modes(const Ctx *c) {
     return c->front_vec2 != 3 || d.TP >= 64 || c->front_bytes > 1.0e9;
 }
 
-// one band of the forward sweep: n workgroups of nbt threads, blk rows each, kp update planes per node
-static void front_launch_fwd(Ctx *c, const FrontDev &f, const FrontWork *ptr, int n, int nbt, int blk, int kp, const double *bhat, double *y) {
+// right-hand sides a workgroup of 1024 threads (128 VGPRs) takes without spilling: forward fold kernel / the others (front_solve_many splits)
+constexpr int FRONT_NR_1024_FWD = 2, FRONT_NR_1024 = 4;
+
+// one band of the forward sweep: n workgroups of nbt threads, blk rows each, kp update planes per node (NR right-hand sides: mr their vectors 1 ..)
+template <int NR>
+static void front_launch_fwd(Ctx *c, const FrontDev &f, const FrontWork *ptr, int n, int nbt, int blk, int kp, const double *bhat, double *y, const MoreRhs<NR> &mr) {
     const Dev &d = c->dcg;
     const FrontArgs g{d.tp_shift, d.TP, d.cg_ncol};
     const bool vm = f.vmap != nullptr, v2 = front_two_modes(c);
 #define FRONT_FWD4(NBV, RBV, KPV)                                                                                                  \
     do {                                                                                                                           \
         if (v2) {                                                                                                                  \
-            if (vm) hipLaunchKernelGGL((k_front_fwd<NBV, RBV, true, KPV, 2>), dim3(n), dim3(NBV), 0, c->stream, g, f, ptr, blk, bhat, y);  \
-            else hipLaunchKernelGGL((k_front_fwd<NBV, RBV, false, KPV, 2>), dim3(n), dim3(NBV), 0, c->stream, g, f, ptr, blk, bhat, y);    \
+            if (vm) hipLaunchKernelGGL((k_front_fwd<NBV, RBV, true, KPV, 2, NR>), dim3(n), dim3(NBV), 0, c->stream, g, f, ptr, blk, bhat, y, mr);  \
+            else hipLaunchKernelGGL((k_front_fwd<NBV, RBV, false, KPV, 2, NR>), dim3(n), dim3(NBV), 0, c->stream, g, f, ptr, blk, bhat, y, mr);    \
         } else {                                                                                                                   \
-            if (vm) hipLaunchKernelGGL((k_front_fwd<NBV, RBV, true, KPV, 1>), dim3(n), dim3(NBV), 0, c->stream, g, f, ptr, blk, bhat, y);  \
-            else hipLaunchKernelGGL((k_front_fwd<NBV, RBV, false, KPV, 1>), dim3(n), dim3(NBV), 0, c->stream, g, f, ptr, blk, bhat, y);    \
+            if (vm) hipLaunchKernelGGL((k_front_fwd<NBV, RBV, true, KPV, 1, NR>), dim3(n), dim3(NBV), 0, c->stream, g, f, ptr, blk, bhat, y, mr);  \
+            else hipLaunchKernelGGL((k_front_fwd<NBV, RBV, false, KPV, 1, NR>), dim3(n), dim3(NBV), 0, c->stream, g, f, ptr, blk, bhat, y, mr);    \
         }                                                                                                                          \
     } while (0)
 #define FRONT_FWD(NBV, RBV)                                                                                                        \
@@ -810,26 +931,30 @@ static void front_launch_fwd(Ctx *c, const FrontDev &f, const FrontWork *ptr, in
         else if (kp == 4) FRONT_FWD4(NBV, RBV, 4);                                                                                 \
         else FRONT_FWD4(NBV, RBV, 8);                                                                                              \
     } while (0)
-    if (nbt == 1024) { if (blk == 1) FRONT_FWD(1024, 1); else if (blk == 2) FRONT_FWD(1024, 2); else FRONT_FWD(1024, 4); }
-    else { if (blk == 1) FRONT_FWD(256, 1); else if (blk == 2) FRONT_FWD(256, 2); else FRONT_FWD(256, 4); }
+    if (nbt == 1024) {
+        if constexpr (NR <= FRONT_NR_1024_FWD) { if (blk == 1) FRONT_FWD(1024, 1); else if (blk == 2) FRONT_FWD(1024, 2); else FRONT_FWD(1024, 4); }
+        else c->front_cap_fault = 1;      // (front_solve_many splits such launches: never reached)
+    } else { if (blk == 1) FRONT_FWD(256, 1); else if (blk == 2) FRONT_FWD(256, 2); else FRONT_FWD(256, 4); }
 #undef FRONT_FWD
 #undef FRONT_FWD4
 }
 
 // one band of the forward sweep with the row kernel: n workgroups of 256 threads, 2^qw_shift lane groups per row
-static void front_launch_fwd_rows(Ctx *c, const FrontDev &f, const FrontWork *ptr, int n, int qw_shift, int kp, int lds_cols, const double *bhat, double *y) {
+template <int NR>
+static void front_launch_fwd_rows(Ctx *c, const FrontDev &f, const FrontWork *ptr, int n, int qw_shift, int kp, int lds_cols, const double *bhat, double *y,
+                                  const MoreRhs<NR> &mr) {
     const Dev &d = c->dcg;
     const FrontArgs g{d.tp_shift, d.TP, d.cg_ncol};
     const bool vm = f.vmap != nullptr, v2 = front_two_modes(c);
-    const size_t lds = sizeof(double) * (size_t)std::max(lds_cols, 1) * (size_t)(d.TP + FWD_ROWS_PAD);
+    const size_t lds = NR * sizeof(double) * (size_t)std::max(lds_cols, 1) * (size_t)(d.TP + FWD_ROWS_PAD);
 #define FRONT_ROWS4(KPV)                                                                                                           \
     do {                                                                                                                           \
         if (v2) {                                                                                                                  \
-            if (vm) hipLaunchKernelGGL((k_front_fwd_rows<true, KPV, 2>), dim3(n), dim3(256), lds, c->stream, g, f, ptr, qw_shift, bhat, y);  \
-            else hipLaunchKernelGGL((k_front_fwd_rows<false, KPV, 2>), dim3(n), dim3(256), lds, c->stream, g, f, ptr, qw_shift, bhat, y);    \
+            if (vm) hipLaunchKernelGGL((k_front_fwd_rows<true, KPV, 2, NR>), dim3(n), dim3(256), lds, c->stream, g, f, ptr, qw_shift, bhat, y, mr);  \
+            else hipLaunchKernelGGL((k_front_fwd_rows<false, KPV, 2, NR>), dim3(n), dim3(256), lds, c->stream, g, f, ptr, qw_shift, bhat, y, mr);    \
         } else {                                                                                                                   \
-            if (vm) hipLaunchKernelGGL((k_front_fwd_rows<true, KPV, 1>), dim3(n), dim3(256), lds, c->stream, g, f, ptr, qw_shift, bhat, y);  \
-            else hipLaunchKernelGGL((k_front_fwd_rows<false, KPV, 1>), dim3(n), dim3(256), lds, c->stream, g, f, ptr, qw_shift, bhat, y);    \
+            if (vm) hipLaunchKernelGGL((k_front_fwd_rows<true, KPV, 1, NR>), dim3(n), dim3(256), lds, c->stream, g, f, ptr, qw_shift, bhat, y, mr);  \
+            else hipLaunchKernelGGL((k_front_fwd_rows<false, KPV, 1, NR>), dim3(n), dim3(256), lds, c->stream, g, f, ptr, qw_shift, bhat, y, mr);    \
         }                                                                                                                          \
     } while (0)
     if (kp == 0) FRONT_ROWS4(0);
@@ -839,28 +964,33 @@ static void front_launch_fwd_rows(Ctx *c, const FrontDev &f, const FrontWork *pt
 #undef FRONT_ROWS4
 }
 
-static void front_launch_bwd(Ctx *c, const FrontDev &f, const FrontWork *ptr, int n, int nbt, int blk, const double *y, double *x) {
+template <int NR>
+static void front_launch_bwd(Ctx *c, const FrontDev &f, const FrontWork *ptr, int n, int nbt, int blk, const double *y, double *x, const MoreRhs<NR> &mr) {
     const Dev &d = c->dcg;
     const FrontArgs g{d.tp_shift, d.TP, d.cg_ncol};
     const bool vm = f.vmap != nullptr, v2 = front_two_modes(c);
 #define FRONT_BWD(NBV, RBV)                                                                                                        \
     do {                                                                                                                           \
         if (v2) {                                                                                                                  \
-            if (vm) hipLaunchKernelGGL((k_front_bwd<NBV, RBV, true, 2>), dim3(n), dim3(NBV), 0, c->stream, g, f, ptr, blk, y, x);  \
-            else hipLaunchKernelGGL((k_front_bwd<NBV, RBV, false, 2>), dim3(n), dim3(NBV), 0, c->stream, g, f, ptr, blk, y, x);    \
+            if (vm) hipLaunchKernelGGL((k_front_bwd<NBV, RBV, true, 2, NR>), dim3(n), dim3(NBV), 0, c->stream, g, f, ptr, blk, y, x, mr);  \
+            else hipLaunchKernelGGL((k_front_bwd<NBV, RBV, false, 2, NR>), dim3(n), dim3(NBV), 0, c->stream, g, f, ptr, blk, y, x, mr);    \
         } else {                                                                                                                   \
-            if (vm) hipLaunchKernelGGL((k_front_bwd<NBV, RBV, true, 1>), dim3(n), dim3(NBV), 0, c->stream, g, f, ptr, blk, y, x);  \
-            else hipLaunchKernelGGL((k_front_bwd<NBV, RBV, false, 1>), dim3(n), dim3(NBV), 0, c->stream, g, f, ptr, blk, y, x);    \
+            if (vm) hipLaunchKernelGGL((k_front_bwd<NBV, RBV, true, 1, NR>), dim3(n), dim3(NBV), 0, c->stream, g, f, ptr, blk, y, x, mr);  \
+            else hipLaunchKernelGGL((k_front_bwd<NBV, RBV, false, 1, NR>), dim3(n), dim3(NBV), 0, c->stream, g, f, ptr, blk, y, x, mr);    \
         }                                                                                                                          \
     } while (0)
-    if (nbt == 1024) { if (blk == 1) FRONT_BWD(1024, 1); else if (blk == 2) FRONT_BWD(1024, 2); else FRONT_BWD(1024, 4); }
-    else { if (blk == 1) FRONT_BWD(256, 1); else if (blk == 2) FRONT_BWD(256, 2); else FRONT_BWD(256, 4); }
+    if (nbt == 1024) {
+        if constexpr (NR <= FRONT_NR_1024) { if (blk == 1) FRONT_BWD(1024, 1); else if (blk == 2) FRONT_BWD(1024, 2); else FRONT_BWD(1024, 4); }
+        else c->front_cap_fault = 1;
+    } else { if (blk == 1) FRONT_BWD(256, 1); else if (blk == 2) FRONT_BWD(256, 2); else FRONT_BWD(256, 4); }
 #undef FRONT_BWD
 }
 
 void front_release(Ctx *c) {
     for (int i = 0; i < c->n_front_allocs; ++i) (void)hipFree(c->front_allocs[i]);
     c->n_front_allocs = 0;
+    c->front_store.reset();      // (a shared factor: freed with its last holder)
+    c->front_w_rows = 0;
     c->front = FrontDev{};
     c->use_front = 0;
     c->front_bytes = c->front_bytes_unmerged = 0.0;
@@ -1536,6 +1666,7 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
     const double *w = nullptr;
     if ((rc = front_upload<double>(c, &w, nullptr, std::max<int64_t>(wrows, 1) << d.tp_shift))) { front_release(c); return rc; }
     f.W = const_cast<double *>(w);
+    c->front_w_rows = std::max<int64_t>(wrows, 1);
     // ---- the leaves as explicit local inverses (leaf_inv above; w and t of the largest leaf must fit the LDS a workgroup may take)
     if (leaf_inv) {
         std::vector<LeafWork> leaves;
@@ -1731,8 +1862,8 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
                         if (hipMalloc(&dl, sizeof(FrontWork) * list.size()) != hipSuccess) { ok = false; break; }
                         (void)hipMemcpyAsync(dl, list.data(), sizeof(FrontWork) * list.size(), hipMemcpyHostToDevice, c->stream);
                         const double us = time_us([&]() {
-                            if (sweep == 0) front_launch_fwd(c, f, (const FrontWork *)dl, (int)list.size(), tnb, trb, c->front_planes[k], vec[0], vec[1]);
-                            else front_launch_bwd(c, f, (const FrontWork *)dl, (int)list.size(), tnb, trb, vec[1], vec[2]);
+                            if (sweep == 0) front_launch_fwd(c, f, (const FrontWork *)dl, (int)list.size(), tnb, trb, c->front_planes[k], vec[0], vec[1], MoreRhs<1>{});
+                            else front_launch_bwd(c, f, (const FrontWork *)dl, (int)list.size(), tnb, trb, vec[1], vec[2], MoreRhs<1>{});
                         });
                         (void)hipFree(dl);
                         const bool cur = tnb == (sweep == 0 ? c->front_fwd_nb : c->front_bwd_nb)[k] && trb == (sweep == 0 ? c->front_fwd_rb : c->front_bwd_cb)[k] &&
@@ -1750,7 +1881,7 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
                         void *dl = nullptr;
                         if (hipMalloc(&dl, sizeof(FrontWork) * list.size()) != hipSuccess) { ok = false; break; }
                         (void)hipMemcpyAsync(dl, list.data(), sizeof(FrontWork) * list.size(), hipMemcpyHostToDevice, c->stream);
-                        const double us = time_us([&]() { front_launch_fwd_rows(c, f, (const FrontWork *)dl, (int)list.size(), qs, c->front_planes[k], lds_cols, vec[0], vec[1]); });
+                        const double us = time_us([&]() { front_launch_fwd_rows(c, f, (const FrontWork *)dl, (int)list.size(), qs, c->front_planes[k], lds_cols, vec[0], vec[1], MoreRhs<1>{}); });
                         (void)hipFree(dl);
                         fprintf(stderr, " r%d %.2f%s", 1 << qs, us, c->front_fwd_qw[k] == qs ? "*" : "");
                         if (us < best) { best = us; bqs = qs; }
@@ -1797,53 +1928,164 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
 #undef FUP
     c->front = f;
     c->use_front = 1;
+    c->front_eps = c->prm.eps;
     c->front_heights = h->n_levels;
     c->front_top_inverse = top_inv ? 1 : 0;
     return 0;
 }
 
 // the leaves' band as explicit local inverses: one workgroup per leaf
-static void front_launch_leaves(Ctx *c, const FrontDev &f, bool forward, const double *bhat, double *x) {
-    const Dev &d = c->dcg;
-    const FrontArgs g{d.tp_shift, d.TP, d.cg_ncol};
-    const size_t lds = sizeof(double) * (forward ? 2 : 1) * (size_t)f.leaf_nmax * (size_t)d.TP;
-    const bool v2 = front_two_modes(c);
-    const int lanes = d.TP / (v2 ? 2 : 1);
+static int front_leaf_threads(const Ctx *c) {
+    const int lanes = c->dcg.TP / (front_two_modes(c) ? 2 : 1);
     // (sixteen rows in flight per workgroup at every pitch -- 1024 threads at a pitch of 128 -- lose: torus65k_T127 110 / 87 -> 115 / 110 us per launch,
     // one workgroup per CU instead of four; workgroups grow only where a row of modes needs more than 256 lanes)
 #ifdef DOTS_LEAF_NB      // (A/B)
-    const int nbt = DOTS_LEAF_NB;
+    (void)lanes;
+    return DOTS_LEAF_NB;
 #else
-    const int nbt = lanes <= 256 ? 256 : (lanes <= 512 ? 512 : 1024);
+    return lanes <= 256 ? 256 : (lanes <= 512 ? 512 : 1024);
 #endif
+}
+template <int NR>
+static void front_launch_leaves(Ctx *c, const FrontDev &f, bool forward, const double *bhat, double *x, const MoreRhs<NR> &mr) {
+    const Dev &d = c->dcg;
+    const FrontArgs g{d.tp_shift, d.TP, d.cg_ncol};
+    const size_t lds = NR * sizeof(double) * (forward ? 2 : 1) * (size_t)f.leaf_nmax * (size_t)d.TP;
+    const bool v2 = front_two_modes(c);
+    const int nbt = front_leaf_threads(c);
     const bool tab = f.leaf_bd != nullptr;
 #define LEAF_LAUNCH2(VECV, NBV, TABV)                                                                                                                \
     do {                                                                                                                                             \
-        if (forward) hipLaunchKernelGGL((k_front_leaf_fwd<VECV, NBV, TABV>), dim3(f.n_leaves), dim3(NBV), lds, c->stream, g, f, d.rowptr, d.col, d.val, bhat);      \
-        else hipLaunchKernelGGL((k_front_leaf_bwd<VECV, NBV, TABV>), dim3(f.n_leaves), dim3(NBV), lds, c->stream, g, f, d.rowptr, d.col, d.val, bhat, x);           \
+        if (forward) hipLaunchKernelGGL((k_front_leaf_fwd<VECV, NBV, TABV, NR>), dim3(f.n_leaves), dim3(NBV), lds, c->stream, g, f, d.rowptr, d.col, d.val, bhat, mr);  \
+        else hipLaunchKernelGGL((k_front_leaf_bwd<VECV, NBV, TABV, NR>), dim3(f.n_leaves), dim3(NBV), lds, c->stream, g, f, d.rowptr, d.col, d.val, bhat, x, mr);       \
     } while (0)
 #define LEAF_LAUNCH(VECV, NBV) do { if (tab) LEAF_LAUNCH2(VECV, NBV, true); else LEAF_LAUNCH2(VECV, NBV, false); } while (0)
-    if (v2) { if (nbt == 256) LEAF_LAUNCH(2, 256); else if (nbt == 512) LEAF_LAUNCH(2, 512); else LEAF_LAUNCH(2, 1024); }
-    else { if (nbt == 256) LEAF_LAUNCH(1, 256); else if (nbt == 512) LEAF_LAUNCH(1, 512); else LEAF_LAUNCH(1, 1024); }
+    if (nbt == 1024) {
+        if constexpr (NR <= FRONT_NR_1024) { if (v2) LEAF_LAUNCH(2, 1024); else LEAF_LAUNCH(1, 1024); }
+        else c->front_cap_fault = 1;
+    } else if (v2) { if (nbt == 256) LEAF_LAUNCH(2, 256); else LEAF_LAUNCH(2, 512); }
+    else { if (nbt == 256) LEAF_LAUNCH(1, 256); else LEAF_LAUNCH(1, 512); }
 #undef LEAF_LAUNCH
 #undef LEAF_LAUNCH2
 }
 
-int front_solve(Ctx *c, const double *bhat, double *y, double *x) {
-    const FrontDev &f = c->front;
-    if (f.n_nodes == 0) { set_error("front_solve: no factor installed"); return DOTS_ERR_STATE; }
+// the sweeps of one problem with the factor and update planes of `f`, launched on c's stream
+static void front_solve_with(Ctx *c, const FrontDev &f, const double *bhat, double *y, double *x) {
+    const MoreRhs<1> mr{};
     for (int l = 0; l < f.n_levels; ++l) {
-        if (l == 0 && f.n_leaves > 0) { front_launch_leaves(c, f, true, bhat, x); continue; }
+        if (l == 0 && f.n_leaves > 0) { front_launch_leaves(c, f, true, bhat, x, mr); continue; }
         const int n = c->front_fwd_ptr[l + 1] - c->front_fwd_ptr[l];
         // (a top band of explicit inverses writes the solution itself)
         double *out = (c->front_top_inverse && l == f.n_levels - 1) ? x : y;
-        if (n > 0 && c->front_fwd_qw[l] >= 0) front_launch_fwd_rows(c, f, f.fwd_desc + c->front_fwd_ptr[l], n, c->front_fwd_qw[l], c->front_planes[l], c->front_fwd_lds[l], bhat, out);
-        else if (n > 0) front_launch_fwd(c, f, f.fwd_desc + c->front_fwd_ptr[l], n, c->front_fwd_nb[l], c->front_fwd_rb[l], c->front_planes[l], bhat, out);
+        if (n > 0 && c->front_fwd_qw[l] >= 0) front_launch_fwd_rows(c, f, f.fwd_desc + c->front_fwd_ptr[l], n, c->front_fwd_qw[l], c->front_planes[l], c->front_fwd_lds[l], bhat, out, mr);
+        else if (n > 0) front_launch_fwd(c, f, f.fwd_desc + c->front_fwd_ptr[l], n, c->front_fwd_nb[l], c->front_fwd_rb[l], c->front_planes[l], bhat, out, mr);
     }
     for (int l = f.n_levels - 1 - (c->front_top_inverse ? 1 : 0); l >= 0; --l) {
-        if (l == 0 && f.n_leaves > 0) { front_launch_leaves(c, f, false, bhat, x); continue; }
+        if (l == 0 && f.n_leaves > 0) { front_launch_leaves(c, f, false, bhat, x, mr); continue; }
         const int n = c->front_bwd_ptr[l + 1] - c->front_bwd_ptr[l];
-        if (n > 0) front_launch_bwd(c, f, f.bwd_desc + c->front_bwd_ptr[l], n, c->front_bwd_nb[l], c->front_bwd_cb[l], y, x);
+        if (n > 0) front_launch_bwd(c, f, f.bwd_desc + c->front_bwd_ptr[l], n, c->front_bwd_nb[l], c->front_bwd_cb[l], y, x, mr);
+    }
+}
+
+int front_solve(Ctx *c, const double *bhat, double *y, double *x) {
+    if (c->front.n_nodes == 0) { set_error("front_solve: no factor installed"); return DOTS_ERR_STATE; }
+    front_solve_with(c, c->front, bhat, y, x);
+    DOTS_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- several problems on one factor (front_solve_many) --------------------------------------------------------------------
+// One launch of a sweep for up to NR of the problems: problem k's vectors are (b[k], y[k], x[k]) and its own update planes (the W of its
+// context); the factor, the descriptors and the maps are the first context's (all share them: dots_front_share).  A launch whose LDS
+// holds one region per rhs is split where NR regions would exceed FRONT_MANY_LDS; a chunk of fewer than NR problems repeats its last
+// problem (the copy writes the same values to the same addresses from the same thread: harmless, and cheaper than a second launch).
+constexpr size_t FRONT_MANY_LDS = 64 * 1024;
+struct ManyView {
+    Ctx *const *cs;
+    const double *const *b;
+    double *const *y, *const *x;
+    int n;      // problems in the chunk (<= NR); rhs k >= n repeats problem n - 1
+};
+template <int NR>
+static MoreRhs<NR> many_rhs(const ManyView &v, int k0) {
+    MoreRhs<NR> mr{};
+    for (int k = 1; k < NR; ++k) {
+        const int p = std::min(k0 + k, v.n - 1);
+        mr.b[k - 1] = v.b[p];
+        mr.y[k - 1] = v.y[p];
+        mr.x[k - 1] = v.x[p];
+        mr.W[k - 1] = v.cs[p]->front.W;
+    }
+    return mr;
+}
+// one launch kind for the problems [k0, v.n) of the chunk, NR at a time (fewer where the LDS of NR would not fit)
+// (and at most `cap` per launch: the workgroups of 1024 threads have 128 VGPRs, more right-hand sides would spill)
+template <int NR, typename L>
+static void many_launch(const ManyView &v, size_t lds_per_rhs, int cap, const L &launch) {
+    if (NR > 1 && (NR > cap || NR * lds_per_rhs > FRONT_MANY_LDS)) {
+        for (int k0 = 0; k0 < v.n; k0 += NR / 2) {
+            ManyView s{v.cs + k0, v.b + k0, v.y + k0, v.x + k0, std::min(NR / 2, v.n - k0)};
+            many_launch<(NR > 1 ? NR / 2 : 1)>(s, lds_per_rhs, cap, launch);
+        }
+        return;
+    }
+    FrontDev f = v.cs[0]->front;
+    launch(f, v.b[0], v.y[0], v.x[0], many_rhs<NR>(v, 0));
+}
+
+template <int NR>
+static void front_solve_chunk(Ctx *c, const ManyView &v) {
+    const FrontDev &f0 = c->front;
+    const Dev &d = c->dcg;
+    const size_t leaf_fwd = sizeof(double) * 2 * (size_t)f0.leaf_nmax * (size_t)d.TP, leaf_bwd = leaf_fwd / 2;
+    const int leaf_cap = front_leaf_threads(c) == 1024 ? FRONT_NR_1024 : NR;
+#define MANY_CAP(BYTES, CAP, CALL) many_launch<NR>(v, (BYTES), (CAP), [&](const FrontDev &f, const double *bh, double *yy, double *xx, const auto &mr) { CALL; })
+#define MANY(BYTES, CALL) MANY_CAP(BYTES, NR, CALL)
+    for (int l = 0; l < f0.n_levels; ++l) {
+        if (l == 0 && f0.n_leaves > 0) { MANY_CAP(leaf_fwd, leaf_cap, front_launch_leaves(c, f, true, bh, xx, mr)); continue; }
+        const int n = c->front_fwd_ptr[l + 1] - c->front_fwd_ptr[l];
+        const bool top = c->front_top_inverse && l == f0.n_levels - 1;      // (a top band of explicit inverses writes the solution itself)
+        const FrontWork *ptr = f0.fwd_desc + c->front_fwd_ptr[l];
+        if (n > 0 && c->front_fwd_qw[l] >= 0) {
+            const size_t rows = sizeof(double) * (size_t)std::max(c->front_fwd_lds[l], 1) * (size_t)(d.TP + FWD_ROWS_PAD);
+            if (top) MANY(rows, { auto m = mr; for (int k = 0; k < (int)(sizeof m.y / sizeof m.y[0]); ++k) m.y[k] = m.x[k];
+                                  front_launch_fwd_rows(c, f, ptr, n, c->front_fwd_qw[l], c->front_planes[l], c->front_fwd_lds[l], bh, xx, m); });
+            else MANY(rows, front_launch_fwd_rows(c, f, ptr, n, c->front_fwd_qw[l], c->front_planes[l], c->front_fwd_lds[l], bh, yy, mr));
+        } else if (n > 0) {
+            const int cap = c->front_fwd_nb[l] == 1024 ? FRONT_NR_1024_FWD : NR;
+            if (top) MANY_CAP(0, cap, { auto m = mr; for (int k = 0; k < (int)(sizeof m.y / sizeof m.y[0]); ++k) m.y[k] = m.x[k];
+                               front_launch_fwd(c, f, ptr, n, c->front_fwd_nb[l], c->front_fwd_rb[l], c->front_planes[l], bh, xx, m); });
+            else MANY_CAP(0, cap, front_launch_fwd(c, f, ptr, n, c->front_fwd_nb[l], c->front_fwd_rb[l], c->front_planes[l], bh, yy, mr));
+        }
+    }
+    for (int l = f0.n_levels - 1 - (c->front_top_inverse ? 1 : 0); l >= 0; --l) {
+        if (l == 0 && f0.n_leaves > 0) { MANY_CAP(leaf_bwd, leaf_cap, front_launch_leaves(c, f, false, bh, xx, mr)); continue; }
+        const int n = c->front_bwd_ptr[l + 1] - c->front_bwd_ptr[l];
+        if (n > 0) MANY_CAP(0, c->front_bwd_nb[l] == 1024 ? FRONT_NR_1024 : NR,
+                            front_launch_bwd(c, f, f0.bwd_desc + c->front_bwd_ptr[l], n, c->front_bwd_nb[l], c->front_bwd_cb[l], yy, xx, mr));
+    }
+#undef MANY
+#undef MANY_CAP
+}
+
+int front_solve_many(Ctx *const *cs, int n, const double *const *b, double *const *y, double *const *x) {
+    if (n <= 0) return 0;
+    Ctx *c = cs[0];
+    if (c->front.n_nodes == 0) { set_error("front_solve_many: no factor installed"); return DOTS_ERR_STATE; }
+    if (n == 1) return front_solve(c, b[0], y[0], x[0]);
+    const int cap = c->front_nr_max;
+    for (int k0 = 0; k0 < n; k0 += cap) {
+        const int m = std::min(cap, n - k0);
+        const ManyView v{cs + k0, b + k0, y + k0, x + k0, m};
+        if (m == 1) front_solve_with(c, cs[k0]->front, b[k0], y[k0], x[k0]);      // (its own update planes, on the batch's stream)
+        else if (m == 2) front_solve_chunk<2>(c, v);
+        else if (m <= 4) front_solve_chunk<4>(c, v);
+        else front_solve_chunk<8>(c, v);
+    }
+    if (c->front_cap_fault) {
+        c->front_cap_fault = 0;
+        set_error("front_solve_many: a launch was asked for more right-hand sides than its workgroup shape takes (a band was not solved)");
+        return DOTS_ERR_STATE;
     }
     DOTS_HIP(hipGetLastError());
     return 0;

@@ -455,6 +455,14 @@ class DeviceProblem:
                                   bytes_per_solve_as_installed=float(info[1]), leaf_inverse=self.debug_counter(4) > 0)
         return self.front_summary
 
+    def share_frontal(self, owner: "DeviceProblem"):
+        """Install the factor of ``owner`` (a context with ``setup_frontal`` done) in this context (dots_front_share): the factor is
+        shared, reference-counted, this context allocates only the vectors one solve writes.  Same mesh in the same numbering (build
+        the context on ``owner.plan`` or on ``geometry.plan_with_densities(owner.plan, ...)``) and the same eps in ``params``."""
+        _lib.check(self.lib.dots_front_share(self._h, owner._h), "dots_front_share")
+        self.front_summary = getattr(owner, "front_summary", None)
+        return self.front_summary
+
     def front_launches(self):
         return int(self.lib.dots_front_launches(self._h))
 
@@ -474,3 +482,51 @@ class DeviceProblem:
 
     def device_bytes(self):
         return int(self.lib.dots_device_bytes(self._h))
+
+
+def laplacian_solve_many(problems, arrays):
+    """Step 1's operator inverse of ``arrays[k]`` ([T+1, V], reference layout) on ``problems[k]``, for problems that share one factor
+    (``DeviceProblem.share_frontal``): ONE batched pair of sweeps for all of them (dots_laplacian_solve_many).  Returns the solutions,
+    each bit for bit what the call on that problem alone returns."""
+    problems = list(problems)
+    if len(problems) != len(arrays) or not problems:
+        raise ValueError("laplacian_solve_many: one array per problem, at least one problem")
+    lib = problems[0].lib
+    ins = []
+    for p, a in zip(problems, arrays):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.shape != p.shape("phi"):
+            raise ValueError(f"laplacian_solve_many: expected shape {p.shape('phi')}, got {a.shape}")
+        ins.append(a)
+    outs = [np.empty(p.shape("phi"), dtype=np.float64) for p in problems]
+    n = len(problems)
+    hs = (C.c_void_p * n)(*[p._h.value for p in problems])
+    pin = (C.POINTER(C.c_double) * n)(*[_ptr(a, C.c_double) for a in ins])
+    pout = (C.POINTER(C.c_double) * n)(*[_ptr(a, C.c_double) for a in outs])
+    _lib.check(lib.dots_laplacian_solve_many(hs, n, pin, pout), "dots_laplacian_solve_many")
+    return outs
+
+
+def _handles(problems):
+    problems = list(problems)
+    if not problems:
+        raise ValueError("at least one problem")
+    return problems, (C.c_void_p * len(problems))(*[p._h.value for p in problems])
+
+
+def step_many(problems, stats=False):
+    """One ALM iteration of every problem (they share one factor), each under its own step flags, with ONE batched pair of sweeps
+    (dots_step_many).  ``stats``: the host waits and the batch's phase times come back as a ``StepStats``; otherwise the iteration is only
+    enqueued and None is returned."""
+    problems, hs = _handles(problems)
+    st = _lib.StepStats() if stats else None
+    _lib.check(problems[0].lib.dots_step_many(hs, len(problems), C.byref(st) if stats else None), "dots_step_many")
+    return st
+
+
+def bench_many(problems, reps=20):
+    """Device-timed batched sweeps alone (dots_bench_many): milliseconds per batched solve of all the problems."""
+    problems, hs = _handles(problems)
+    ms = C.c_double()
+    _lib.check(problems[0].lib.dots_bench_many(hs, len(problems), int(reps), C.byref(ms)), "dots_bench_many")
+    return ms.value

@@ -12,6 +12,7 @@ graph) so that neighbouring rows sit in neighbouring tiles / the same XCD's L2.
 """
 from __future__ import annotations
 
+import dataclasses
 from dataclasses import dataclass
 
 import numpy as np
@@ -204,6 +205,21 @@ def assemble_reference(vertices, triangles):
     mass = np.zeros(V)
     np.add.at(mass, triangles.reshape(-1), np.repeat(area, 3) / 3.0)
     return area, hat, mass, cptr.astype(np.int32), cidx.astype(np.int32), stiffness_matrix(V, triangles, area, hat)
+
+
+def plan_with_densities(plan: DevicePlan, mu0, mu1) -> DevicePlan:
+    """``plan`` with other densities ``mu0`` / ``mu1`` (caller's numbering): the mesh arrays, the permutation and the dissection are
+    shared, the densities are permuted into device numbering exactly as ``build_plan`` does -- the plan ``build_plan`` returns for the same
+    mesh with these densities."""
+    mu0 = np.asarray(mu0, dtype=np.float64)
+    mu1 = np.asarray(mu1, dtype=np.float64)
+    V = plan.n_vertices
+    if mu0.shape != (V,) or mu1.shape != (V,):
+        raise ValueError("mu0/mu1 must have one entry per vertex")
+    if plan.perm_vert is not None:
+        mu0, mu1 = mu0[plan.perm_vert], mu1[plan.perm_vert]
+    c = np.ascontiguousarray
+    return dataclasses.replace(plan, mu0=c(mu0), mu1=c(mu1))
 
 
 def build_plan(n_time, geometry, reorder=True, nd_leaf=16, native=True) -> DevicePlan:

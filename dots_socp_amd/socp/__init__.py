@@ -2,15 +2,16 @@
 
 ``solver_raw``  SOCP solver + conversion to DOT units          (socp/solver_decorator.py:10-27, utils/type.py:48-65)
 ``solver``      ``solver_raw`` on the time-centred grid          (socp/solver_decorator.py:29-54)
+``solver_raw_many`` / ``solver_many``   the same for several problems on one surface with one shared factor (solver_socp_many)
 
 Both take ``(n_time, geometry, **kwargs)`` and return ``(solution, run_history)``; they can be
 passed as ``solver=`` to the reference's ``run_dot_surface`` (interface.py:106-134).
 """
 import numpy as np
 
-from .solver_socp import solver_socp
+from .solver_socp import solver_socp, solver_socp_many
 
-__all__ = ["solver_socp", "solver_raw", "solver"]
+__all__ = ["solver_socp", "solver_raw", "solver", "solver_socp_many", "solver_raw_many", "solver_many"]
 
 
 def _socp_to_dot(solution_socp, geom):
@@ -70,3 +71,21 @@ def solver(n_time, geometry, **kwargs):
 
 
 solver.__name__ = "dot_solver_socp_center"
+
+
+def solver_raw_many(n_time, geometry, problems, **kwargs):
+    """``solver_raw`` for several problems on one surface (``solver_socp_many``): a list of ``(solution, run_history)``."""
+    g = _geometry_with_areas(geometry)
+    return [(_socp_to_dot(sol, g), hist) for sol, hist in solver_socp_many(n_time, geometry, problems, **kwargs)]
+
+
+def solver_many(n_time, geometry, problems, **kwargs):
+    """``solver`` for several problems on one surface: each density on the time-centred grid with its own mu0 / mu1 as end points."""
+    out = solver_raw_many(n_time, geometry, problems, **kwargs)
+    for p, (solution_dot, _) in zip(problems, out):
+        mu0 = np.asarray(p.get("mu0", geometry.get("mu0")), dtype=np.float64)
+        mu1 = np.asarray(p.get("mu1", geometry.get("mu1")), dtype=np.float64)
+        _to_time_centered(solution_dot, mu0, mu1)
+        for cp in solution_dot.get("checkpoints") or []:
+            _to_time_centered(cp, mu0, mu1)
+    return out

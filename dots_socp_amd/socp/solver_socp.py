@@ -69,7 +69,10 @@ class AlmSolver:
     def __init__(self, n_time, geometry, congestion=0.0, nit=1000, eps=0.0, tol=1e-4, tau=1.90, is_z_scaling=True,
                  is_constant_scaling=False, check_kkt_step_by_step=False, init_solution=None, tol_checkpoints=None,
                  time_limit=1000, is_palm=False, lap_solver="modal_direct", cg_tol=DEFAULT_CG_TOL, cg_max_iter=20000, device=0, reorder=True,
-                 preconditioner="multigrid", mg_coarsest=256, time_slab=None, nd_leaf=16):
+                 preconditioner="multigrid", mg_coarsest=256, time_slab=None, nd_leaf=16, plan=None, front_owner=None):
+        """``plan``: the device plan to use (geometry.plan_with_densities) instead of building one; ``front_owner``: a DeviceProblem
+        whose factor this solver shares (dots_front_share) instead of building its own -- a member of a batch (solver_socp_many), stepped
+        by ``step_batch``; the launch ahead of the right-hand side and of the penalty decision are off then."""
         self.tol_checkpoints = _validate_checkpoints(tol_checkpoints, tol)
         self.checkpoint_solutions = []
         self.n_time, self.nit, self.tol, self.time_limit = int(n_time), int(nit), tol, time_limit
@@ -85,8 +88,9 @@ class AlmSolver:
         # the projection now rides in the launch ahead, its results in alternate buffers until the step takes them: the same launch
         # the iteration would start with, only earlier -- on for every size
         ahead = env_choice("DOTS_RHS_AHEAD", ("0", "1", "2"), "1")
+        self.batched = front_owner is not None or plan is not None
         self._rhs_ahead_ok = (direct and time_slab is None and not self.is_palm and not check_kkt_step_by_step
-                              and not is_constant_scaling and ahead != "0")
+                              and not is_constant_scaling and ahead != "0" and not self.batched)
         self._rhs_ahead = False
         self._carry = False             # DOTS_STEP_CARRY for the next device step (iterate())
         # ... which pays where the iteration is bandwidth-bound: below DOTS_CARRY_MIN space-time nodes (V (T + 1)) the launches are
@@ -98,7 +102,7 @@ class AlmSolver:
         if direct and reorder is True:
             reorder = "nd"      # the elimination order of the factor doubles as the locality numbering
         self.dev = dev = DeviceProblem(n_time, geometry, lap_solver="modal_pcg" if direct else lap_solver, device=device,
-                                       reorder=reorder, time_slab=time_slab, nd_leaf=nd_leaf)
+                                       reorder=reorder, time_slab=time_slab, nd_leaf=nd_leaf, plan=plan)
 
         p = dev.params
         self.r = 1.0
@@ -114,7 +118,9 @@ class AlmSolver:
             raise ValueError("preconditioner must be 'multigrid' or 'jacobi'")
         self.mg_summary = self.front_summary = None
         self.lap_solver_fallback = None      # why the direct solve was not used although it was asked for
-        if direct:
+        if direct and front_owner is not None:
+            self.front_summary = dev.share_frontal(front_owner)      # (no fall-back: a batch shares the factor or fails)
+        elif direct:
             # Memory regime: the factor holds ~70 entries per vertex and time mode (8.9 GB at 500k vertices x 32 modes).  When it
             # does not fit beside the state, step 1 runs the batched multigrid-PCG on the same modes instead -- the reference has
             # no counterpart (laplacian_inverse_socp.py:34-41 just factorises); the choice is logged and reported in solver_stats.
@@ -354,6 +360,17 @@ class AlmSolver:
             self.dev.step_flags(skip_z_mid=quiet and not self.is_palm, palm=self.is_palm)
             self._account(self.dev.step(1), kind)
 
+    def batch_step_prepare(self, quiet):
+        """A batch member's share of ``_device_step``: its step flags (the batch enqueues the step itself, step_batch); returns
+        (kind, sampled)."""
+        kind = "quiet" if quiet else "read-back"
+        sample = self.step_timers.begin(kind)
+        if quiet:
+            self.quiet_steps += 1
+        self.dev.step_flags(skip_z_mid=quiet and not self.is_palm, palm=self.is_palm, carry=self._carry, kkt_sums=not quiet)
+        self._fused_kkt = not quiet
+        return kind, sample
+
     def _collect_step_times(self, wait=False):
         """Phase times of the timed iterations that have finished (at a read-back: all of them), into the history."""
         fresh = False
@@ -382,8 +399,17 @@ class AlmSolver:
 
     # ---- one pass of the main loop (:656-823); returns True when the loop must stop ------------
     def iterate(self):
-        if self.finished:
+        quiet = self.iterate_begin()
+        if quiet is None:
             return True
+        self._device_step(quiet)                                                # steps 1-3 (:674-722)
+        return self.iterate_end()
+
+    def iterate_begin(self):
+        """The part of ``iterate()`` before the device step: returns whether the step is quiet (nothing read back after it), or
+        None when the solver has finished."""
+        if self.finished:
+            return None
         self.counter_main += 1
         it, dev, hist, params = self.counter_main, self.dev, self.run_history, self.adjust_params
         if self.is_constant_scaling and params.is_to_scale(it):
@@ -411,8 +437,13 @@ class AlmSolver:
         # a z rescaling or a stop simply drop what was carried): steps 2+3 then also store the per-corner sums that iteration's
         # right-hand side and cone projection would gather from B, E and beta_mid (DOTS_STEP_CARRY: one pass over beta_mid less).
         self._carry = self._carry_ok and it + 1 < self.nit and not params.peek_adjust(it)
-        self._device_step(quiet)                                                # steps 1-3 (:674-722)
+        self._pass = (it, is_time_used_up, quiet)
+        return quiet
 
+    def iterate_end(self):
+        """The part of ``iterate()`` after the device step; returns True when the loop must stop."""
+        (it, is_time_used_up, quiet), self._pass = self._pass, None
+        hist, params = self.run_history, self.adjust_params
         adjust = params.is_to_adjust(it) or is_time_used_up
         required = KKT_PRIM + KKT_DUAL if adjust else None
         validator = self.kkt_validator
@@ -544,3 +575,144 @@ def solver_socp(
         return alm.finalize()
     finally:
         alm.close()
+
+
+# ---- several problems on one surface, one factor ---------------------------------------------------------------------------
+PER_PROBLEM_KEYS = ("mu0", "mu1", "congestion", "nit", "tol", "tau", "is_palm", "is_z_scaling", "is_constant_scaling", "check_kkt_step_by_step",
+                    "init_solution", "tol_checkpoints", "time_limit")
+COMMON_KEYS = ("eps", "lap_solver", "reorder", "nd_leaf", "device", "cg_tol", "cg_max_iter", "is_multi_threads")
+BATCH_TIME_NOTE = ("phase times of a batched iteration are the batch's, booked to each active member as 1/n of them "
+                   "(n = members in that iteration)")
+
+
+def _batch_problems(geometry, problems, common):
+    """The checks of solver_socp_many, before any device is touched."""
+    unknown = set(common) - set(COMMON_KEYS)
+    if unknown:
+        raise ValueError(f"solver_socp_many: unknown option(s) {sorted(unknown)}")
+    if common.get("lap_solver", "modal_direct") != "modal_direct":
+        raise ValueError("solver_socp_many: the batch shares the factor of the direct solver: lap_solver must be 'modal_direct'")
+    if not problems:
+        raise ValueError("solver_socp_many: no problems")
+    verts, tris = np.asarray(geometry["vertices"]), np.asarray(geometry["triangles"])
+    out = []
+    for i, p in enumerate(problems):
+        p = dict(p)
+        for k in ("vertices", "triangles"):
+            if k in p:
+                if not np.array_equal(np.asarray(p.pop(k)), verts if k == "vertices" else tris):
+                    raise ValueError(f"solver_socp_many: problem {i} is on another mesh: a batch shares one surface")
+        for k in p:
+            if k in COMMON_KEYS:
+                raise ValueError(f"solver_socp_many: '{k}' shapes the factor or the solver: give it once for the batch, not per problem ({i})")
+            if k not in PER_PROBLEM_KEYS:
+                raise ValueError(f"solver_socp_many: unknown per-problem option '{k}' (problem {i})")
+        for k in ("mu0", "mu1"):
+            if p.get(k) is None:
+                if k not in geometry:
+                    raise ValueError(f"solver_socp_many: problem {i} has no {k}")
+                p[k] = geometry[k]
+            if np.asarray(p[k]).shape != (verts.shape[0],):
+                raise ValueError(f"solver_socp_many: problem {i}: {k} must have one entry per vertex")
+        _validate_checkpoints(p.get("tol_checkpoints"), p.get("tol", 1e-4))
+        out.append(p)
+    return out
+
+
+def solver_socp_many(n_time, geometry, problems, *, max_batch=4, **common):
+    """Solve several transport problems on ONE surface with one factor of the direct solver.
+
+    ``geometry`` holds the mesh (``vertices``, ``triangles``; ``mu0`` / ``mu1`` are defaults for problems without their own);
+    ``problems`` is a list of dicts with ``mu0``, ``mu1`` and any of the per-problem options of ``solver_socp`` (congestion, nit, tol,
+    tau, is_palm, is_z_scaling, is_constant_scaling, check_kkt_step_by_step, init_solution, tol_checkpoints, time_limit).  The options that
+    shape the factor or the solver (eps, lap_solver -- only "modal_direct" --, reorder, nd_leaf, device, cg_tol, cg_max_iter) are given
+    once, as keywords.  At most ``max_batch`` problems are active at a time and advance in lockstep, one ALM iteration each with ONE batched
+    pair of sweeps (dots_step_many); when one stops the next pending problem takes its slot, sharing the same factor (built once).
+
+    Returns ``[(solution, run_history), ...]`` in input order, each what ``solver_socp(n_time, {**geometry, "mu0": ..., "mu1": ...},
+    **common, **problem)`` returns, bit for bit; ``run_history.solver_stats["batch"]`` = {"size", "index", "max_batch", "steps_time_note"}.
+    Each problem's running time and time limit start when it is admitted.  A factor that does not fit raises the library's memory error
+    (there is no batched PCG)."""
+    from .. import geometry as geo
+    from ..device import step_many
+
+    probs = _batch_problems(geometry, problems, common)
+    if int(max_batch) < 1:
+        raise ValueError("solver_socp_many: max_batch >= 1")
+    reorder = common.get("reorder", True)
+    reorder = "nd" if reorder is True else reorder
+    nd_leaf = common.get("nd_leaf", 16)
+    solver_kw = dict(eps=common.get("eps", 0.0), lap_solver="modal_direct", device=common.get("device", 0), reorder=reorder,
+                     cg_tol=common.get("cg_tol", DEFAULT_CG_TOL), cg_max_iter=common.get("cg_max_iter", 20000), nd_leaf=nd_leaf)
+    mesh = {k: v for k, v in geometry.items() if k not in ("mu0", "mu1")}
+    base = geo.build_plan(n_time, {**mesh, "mu0": probs[0]["mu0"], "mu1": probs[0]["mu1"]}, reorder=reorder, nd_leaf=nd_leaf)
+    results = [None] * len(probs)
+    pending = list(range(len(probs)))
+    active, done = [], []          # (index, AlmSolver)
+
+    def admit(owner_dev):
+        i = pending.pop(0)
+        p = probs[i]
+        opts = {k: v for k, v in p.items() if k not in ("mu0", "mu1")}
+        alm = AlmSolver(n_time, {**mesh, "mu0": p["mu0"], "mu1": p["mu1"]}, plan=geo.plan_with_densities(base, p["mu0"], p["mu1"]),
+                        front_owner=owner_dev, **solver_kw, **opts)
+        if owner_dev is None and not alm.direct:      # (the direct solver could not be installed)
+            reason = alm.lap_solver_fallback
+            alm.close()
+            err = _lib.HipLibraryError(f"solver_socp_many: the shared factor does not fit (no batched PCG): {reason}")
+            err.status = _lib.ERR_MEMORY
+            raise err
+        active.append((i, alm))
+
+    try:
+        while pending or active:
+            holder = next((a.dev for _, a in active + done), None)
+            while pending and len(active) < int(max_batch):
+                admit(holder)
+                holder = holder or active[-1][1].dev
+            for i, alm in done:
+                alm.close()
+            done = []
+            members = []
+            for i, alm in active:
+                quiet = alm.iterate_begin()
+                if quiet is not None:
+                    members.append((i, alm, quiet))
+            if members:
+                booked = [(alm, alm.batch_step_prepare(quiet)) for _, alm, quiet in members]
+                sampled = any(s for _, (_, s) in booked)
+                st = step_many([alm.dev for _, alm, _ in members], stats=sampled)
+                n = len(members)
+                for alm, (kind, sample) in booked:
+                    if sample and st is not None:
+                        alm._account(_BatchShare(st, n), kind)
+                    else:
+                        alm.untimed_steps += 1
+                for _, alm, _ in members:
+                    alm.iterate_end()
+            still = []
+            for i, alm in active:
+                if alm.finished:
+                    sol, hist = alm.finalize()
+                    hist.solver_stats["batch"] = {"size": len(probs), "index": i, "max_batch": int(max_batch), "steps_time_note": BATCH_TIME_NOTE}
+                    results[i] = (sol, hist)
+                    done.append((i, alm))
+                else:
+                    still.append((i, alm))
+            active = still
+    finally:
+        for _, alm in active + done:
+            alm.close()
+    return results
+
+
+class _BatchShare:
+    """1/n of a batch's phase times, in the form AlmSolver._account reads"""
+
+    def __init__(self, st, n):
+        self.cg_iterations = self.cg_not_converged = 0
+        self.alm_iterations = 1
+        self.ms_rhs = st.ms_rhs / n
+        self.ms_laplacian = st.ms_laplacian / n
+        self.ms_soc = st.ms_soc / n
+        self.ms_q_lambda_multiplier = st.ms_q_lambda_multiplier / n

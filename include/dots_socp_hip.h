@@ -469,6 +469,31 @@ int64_t dots_symbolic_front_rows(const dots_symbolic *sym);
 int dots_symbolic_copy(const dots_symbolic *sym, int32_t *node_b, int32_t *front_idx, int32_t *pull0, int32_t *pull1);
 void dots_symbolic_free(dots_symbolic *sym);
 int dots_front_enable(dots_ctx *ctx, int on);
+/* Several problems on one surface, one factor.  dots_front_share installs the factor of `owner` in `ctx`: the factor, its descriptors and
+ * maps are shared (reference-counted: they are freed with the last context that holds them, so the owner may be destroyed first);
+ * `ctx` allocates only what one solve writes (its update planes and the carried gathers of DOTS_STEP_CARRY).  DOTS_ERR_ARGUMENT unless
+ * both contexts are on one device with the same V, F, T, Laplacian entries, mode pitch and the eps the factor was built with (the
+ * caller guarantees the same mesh in the same vertex numbering); DOTS_ERR_STATE when the owner has no factor or either is a time slab.
+ * dots_laplacian_solve_many: step 1's operator inverse (the transforms to and from the time modes and the two sweeps) of host_in[k]
+ * into host_out[k], both [T+1][V] in the reference layout, for the n contexts cs[k] that share one factor; the sweeps of all of them
+ * run as ONE sequence of launches that reads each factor entry once for up to 4 right-hand sides (DOTS_FRONT_NR = 2 / 4 / 8 overrides),
+ * every result bit for bit what a call with n = 1 on that context computes.  Uses the solve's scratch of every context (waits for each
+ * context's stream; returns when the results are on the host).  DOTS_ERR_STATE for a context without an installed or shared factor,
+ * a time slab or a PCG context. */
+int dots_front_share(dots_ctx *ctx, dots_ctx *owner);
+int dots_laplacian_solve_many(dots_ctx *const *ctxs, int n, const double *const *host_in, double *const *host_out);
+/* One ALM iteration of each of the n contexts ctxs[k] that share one factor, each under the step flags set on it (dots_step_flags:
+ * DOTS_STEP_SKIP_Z_MID, _PALM, _CARRY, _KKT_SUMS; DOTS_STEP_RHS_AHEAD and DOTS_STEP_TIMED are ignored in a batch): each member's launches before
+ * the solve on its own stream, ONE batched pair of sweeps for all of them (on the stream of ctxs[0], ordered by events), each member's
+ * launches after the solve on its own stream again.  Every member ends bit for bit where dots_step(ctx, 1, NULL) would have left it, and
+ * calls on its own stream afterwards (KKT read-back, download, scaling) see its results.  stats != NULL: the host waits, and the batch's
+ * phases as a whole are returned (ms_rhs: first halves and forward transforms, ms_laplacian: the sweeps, ms_q_lambda_multiplier: the rest
+ * with the projections; alm_iterations = n).  dots_penalty_ahead on a context stepped in a batch returns DOTS_ERR_STATE until its next
+ * dots_step.  DOTS_ERR_STATE for a context without an installed or shared factor, a time slab or a PCG context.
+ * dots_bench_many: the batched sweeps alone, `reps` times on whatever the contexts' solve buffers hold, timed by events on ctxs[0]'s
+ * stream (milliseconds per batched solve). */
+int dots_step_many(dots_ctx *const *ctxs, int n, dots_step_stats *stats);
+int dots_bench_many(dots_ctx *const *ctxs, int n, int reps, double *ms_per_solve);
 /* launches one direct solve takes: 2 x bands of tree heights (one per band and sweep; a band is one height unless
  * dots_front_desc.band_ptr merges heights), minus one with dots_front_desc.top_inverse */
 int dots_front_launches(dots_ctx *ctx);
