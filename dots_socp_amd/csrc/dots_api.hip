@@ -1476,6 +1476,8 @@ int64_t dots_debug_counter(dots_ctx *c, int which) {
         case 4: return c->front.n_leaves;      // leaves the sweeps handle as explicit local inverses (0: band kernels)
         case 5: return c->front.leaf_bd ? 1 : 0;      // ... with their coupling in per-row records (0: read from the CSR)
         case 6: return c->bm_nt;                      // beta_mid streamed around the caches by steps 2+3 (the rule of dots_front_setup, or DOTS_BM_NT)
+        case 7: return c->front_many_launches;        // sweep launches the last front_solve_many on this (first) context enqueued
+        case 8: return c->front_many_split;           // ... of those, launches with fewer rhs than their chunk (many_launch halved: LDS or 1024-thread cap)
         default: return -1;
     }
 }

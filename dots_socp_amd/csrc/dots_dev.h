@@ -434,6 +434,7 @@ struct Ctx {
     int front_nr_max = 4;         // right-hand sides per launch of front_solve_many (DOTS_FRONT_NR: 2, 4 or 8)
     hipEvent_t ev_batch = nullptr;   // orders this context's stream against the others of a batched solve (created on first use)
     int front_cap_fault = 0;      // a multi-rhs launch was asked for more right-hand sides than its workgroup shape takes (front_solve_many reports it)
+    int64_t front_many_launches = 0, front_many_split = 0;   // sweep launches of the last front_solve_many, those split below their chunk (dots_debug_counter 7, 8)
     uint64_t lap_hash = 0;        // FNV-1a of the Laplacian (rowptr, col, val) and the vertex masses: dots_front_share compares it with the owner's
     int batched = 0;              // stepped by dots_step_many since its last dots_step: dots_penalty_ahead is refused
     void *mg_allocs[160]{};

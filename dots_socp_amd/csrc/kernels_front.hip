@@ -1969,22 +1969,26 @@ static void front_launch_leaves(Ctx *c, const FrontDev &f, bool forward, const d
 #undef LEAF_LAUNCH2
 }
 
-// the sweeps of one problem with the factor and update planes of `f`, launched on c's stream
-static void front_solve_with(Ctx *c, const FrontDev &f, const double *bhat, double *y, double *x) {
+// the sweeps of one problem with the factor and update planes of `f`, launched on c's stream; returns the launches enqueued
+static int front_solve_with(Ctx *c, const FrontDev &f, const double *bhat, double *y, double *x) {
     const MoreRhs<1> mr{};
+    int launches = 0;
     for (int l = 0; l < f.n_levels; ++l) {
-        if (l == 0 && f.n_leaves > 0) { front_launch_leaves(c, f, true, bhat, x, mr); continue; }
+        if (l == 0 && f.n_leaves > 0) { front_launch_leaves(c, f, true, bhat, x, mr); ++launches; continue; }
         const int n = c->front_fwd_ptr[l + 1] - c->front_fwd_ptr[l];
         // (a top band of explicit inverses writes the solution itself)
         double *out = (c->front_top_inverse && l == f.n_levels - 1) ? x : y;
         if (n > 0 && c->front_fwd_qw[l] >= 0) front_launch_fwd_rows(c, f, f.fwd_desc + c->front_fwd_ptr[l], n, c->front_fwd_qw[l], c->front_planes[l], c->front_fwd_lds[l], bhat, out, mr);
         else if (n > 0) front_launch_fwd(c, f, f.fwd_desc + c->front_fwd_ptr[l], n, c->front_fwd_nb[l], c->front_fwd_rb[l], c->front_planes[l], bhat, out, mr);
+        launches += n > 0;
     }
     for (int l = f.n_levels - 1 - (c->front_top_inverse ? 1 : 0); l >= 0; --l) {
-        if (l == 0 && f.n_leaves > 0) { front_launch_leaves(c, f, false, bhat, x, mr); continue; }
+        if (l == 0 && f.n_leaves > 0) { front_launch_leaves(c, f, false, bhat, x, mr); ++launches; continue; }
         const int n = c->front_bwd_ptr[l + 1] - c->front_bwd_ptr[l];
         if (n > 0) front_launch_bwd(c, f, f.bwd_desc + c->front_bwd_ptr[l], n, c->front_bwd_nb[l], c->front_bwd_cb[l], y, x, mr);
+        launches += n > 0;
     }
+    return launches;
 }
 
 int front_solve(Ctx *c, const double *bhat, double *y, double *x) {
@@ -2020,17 +2024,20 @@ static MoreRhs<NR> many_rhs(const ManyView &v, int k0) {
 }
 // one launch kind for the problems [k0, v.n) of the chunk, NR at a time (fewer where the LDS of NR would not fit)
 // (and at most `cap` per launch: the workgroups of 1024 threads have 128 VGPRs, more right-hand sides would spill)
+// c: the batch's first context, which counts the launches (dots_debug_counter 7) and those of a split chunk (8)
 template <int NR, typename L>
-static void many_launch(const ManyView &v, size_t lds_per_rhs, int cap, const L &launch) {
+static void many_launch(Ctx *c, const ManyView &v, size_t lds_per_rhs, int cap, const L &launch, bool split = false) {
     if (NR > 1 && (NR > cap || NR * lds_per_rhs > FRONT_MANY_LDS)) {
         for (int k0 = 0; k0 < v.n; k0 += NR / 2) {
             ManyView s{v.cs + k0, v.b + k0, v.y + k0, v.x + k0, std::min(NR / 2, v.n - k0)};
-            many_launch<(NR > 1 ? NR / 2 : 1)>(s, lds_per_rhs, cap, launch);
+            many_launch<(NR > 1 ? NR / 2 : 1)>(c, s, lds_per_rhs, cap, launch, true);
         }
         return;
     }
     FrontDev f = v.cs[0]->front;
     launch(f, v.b[0], v.y[0], v.x[0], many_rhs<NR>(v, 0));
+    ++c->front_many_launches;
+    c->front_many_split += split;
 }
 
 template <int NR>
@@ -2039,7 +2046,7 @@ static void front_solve_chunk(Ctx *c, const ManyView &v) {
     const Dev &d = c->dcg;
     const size_t leaf_fwd = sizeof(double) * 2 * (size_t)f0.leaf_nmax * (size_t)d.TP, leaf_bwd = leaf_fwd / 2;
     const int leaf_cap = front_leaf_threads(c) == 1024 ? FRONT_NR_1024 : NR;
-#define MANY_CAP(BYTES, CAP, CALL) many_launch<NR>(v, (BYTES), (CAP), [&](const FrontDev &f, const double *bh, double *yy, double *xx, const auto &mr) { CALL; })
+#define MANY_CAP(BYTES, CAP, CALL) many_launch<NR>(c, v, (BYTES), (CAP), [&](const FrontDev &f, const double *bh, double *yy, double *xx, const auto &mr) { CALL; })
 #define MANY(BYTES, CALL) MANY_CAP(BYTES, NR, CALL)
     for (int l = 0; l < f0.n_levels; ++l) {
         if (l == 0 && f0.n_leaves > 0) { MANY_CAP(leaf_fwd, leaf_cap, front_launch_leaves(c, f, true, bh, xx, mr)); continue; }
@@ -2072,12 +2079,17 @@ int front_solve_many(Ctx *const *cs, int n, const double *const *b, double *cons
     if (n <= 0) return 0;
     Ctx *c = cs[0];
     if (c->front.n_nodes == 0) { set_error("front_solve_many: no factor installed"); return DOTS_ERR_STATE; }
-    if (n == 1) return front_solve(c, b[0], y[0], x[0]);
+    c->front_many_launches = c->front_many_split = 0;
+    if (n == 1) {
+        c->front_many_launches = front_solve_with(c, c->front, b[0], y[0], x[0]);
+        DOTS_HIP(hipGetLastError());
+        return 0;
+    }
     const int cap = c->front_nr_max;
     for (int k0 = 0; k0 < n; k0 += cap) {
         const int m = std::min(cap, n - k0);
         const ManyView v{cs + k0, b + k0, y + k0, x + k0, m};
-        if (m == 1) front_solve_with(c, cs[k0]->front, b[k0], y[k0], x[k0]);      // (its own update planes, on the batch's stream)
+        if (m == 1) c->front_many_launches += front_solve_with(c, cs[k0]->front, b[k0], y[k0], x[k0]);      // (its own update planes, on the batch's stream)
         else if (m == 2) front_solve_chunk<2>(c, v);
         else if (m <= 4) front_solve_chunk<4>(c, v);
         else front_solve_chunk<8>(c, v);

@@ -517,7 +517,10 @@ int dots_bench_kernel(dots_ctx *ctx, int which, int reps, double *ms_per_launch,
  * caller's own decision then confirmed, 4 tree leaves the sweeps of the direct solve handle as explicit local inverses
  * (0: the leaves' band runs in the band kernels), 5 whether those leaves take their coupling from per-row
  * records (1) or from the CSR of K (0: a row holds more entries than a record, or DOTS_FRONT_LEAFINV=2), 6 whether steps 2+3 stream
- * beta_mid with the non-temporal hint (decided by dots_front_setup from the sizes of factor and state); -1 for an unknown counter */
+ * beta_mid with the non-temporal hint (decided by dots_front_setup from the sizes of factor and state), 7 sweep launches the last
+ * batched solve (dots_laplacian_solve_many, dots_step_many, dots_bench_many) enqueued, read on the batch's first context, 8 of those, the
+ * launches that took fewer right-hand sides than their chunk of DOTS_FRONT_NR problems held because NR regions of LDS would not fit or
+ * a workgroup of 1024 threads takes fewer (the launch was split); -1 for an unknown counter */
 int64_t dots_debug_counter(dots_ctx *ctx, int which);
 
 /* device memory in use by the context, bytes */
