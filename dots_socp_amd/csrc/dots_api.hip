@@ -215,40 +215,6 @@ static int build(Ctx *c, const dots_problem_desc *p) {
         for (int i = 0; i <= d.T; ++i) sig[i] = p->time_eigs[i];
         UP(sigma, sig.data(), tpg);
     }
-    // patch tiles of the right-hand-side / projection launch (k_rhs_soc_tiles: one GPU, T + 1 < 64)
-    if (p->patch_order && !sharded && p->lap_solver == DOTS_LAP_MODAL_PCG && tpg >= 4 && tpg <= 32) {
-        TileDev &tl = c->tiles;
-        tl.VTL = 512 / tpg;
-        tl.n_tiles = (V + tl.VTL - 1) / tl.VTL;
-        std::vector<int> tv((size_t)std::max(tl.n_tiles * tl.VTL, d.n_vtiles * d.VT), -1), tptr((size_t)tl.n_tiles + 1, 0), ttri, cloc((size_t)nC, 0), stamp((size_t)F, -1), pos((size_t)F, 0);
-        std::vector<char> seen((size_t)V, 0);
-        for (int i = 0; i < V; ++i) {
-            const int v = p->patch_order[i];
-            if (v < 0 || v >= V || seen[(size_t)v]) { set_error("patch_order is not a permutation of the vertices"); return DOTS_ERR_ARGUMENT; }
-            seen[(size_t)v] = 1;
-            tv[(size_t)i] = v;
-        }
-        for (int t = 0; t < tl.n_tiles; ++t) {
-            int count = 0;
-            for (int k = 0; k < tl.VTL; ++k) {
-                const int v = tv[(size_t)t * tl.VTL + k];
-                if (v < 0) continue;
-                for (int j = p->corner_ptr[v]; j < p->corner_ptr[v + 1]; ++j) {
-                    const int f = p->corner_idx[j] / 3;
-                    if (stamp[(size_t)f] != t) { stamp[(size_t)f] = t; pos[(size_t)f] = count++; ttri.push_back(f); }
-                    cloc[(size_t)j] = pos[(size_t)f];
-                }
-            }
-            tptr[(size_t)t + 1] = (int)ttri.size();
-            tl.ntri_max = std::max(tl.ntri_max, count);
-        }
-        if (ttri.empty()) ttri.push_back(0);
-        UP(tiles_vertex, tv.data(), tv.size());
-        UP(tiles_tri_ptr, tptr.data(), tptr.size());
-        UP(tiles_tri, ttri.data(), ttri.size());
-        UP(tiles_c_loc, cloc.data(), cloc.size());
-        tl.vertex = d.tiles_vertex; tl.tri_ptr = d.tiles_tri_ptr; tl.tri = d.tiles_tri; tl.c_loc = d.tiles_c_loc;
-    }
 #undef UP
 
     double **state[12] = {&d.phi, &d.A, &d.B, &d.lam, &d.zf, &d.zm, &d.ze, &d.mu, &d.E, &d.bf, &d.bm, &d.be};
@@ -448,7 +414,7 @@ static int iteration_before(Ctx *c, bool timed, IterPlan &p, hipEvent_t *tv) {
         if (!timed && !c->step_palm && c->rhs_ahead == 2 && c->ahead_div == c->pending_div && ql_divides(c, p.zmode)) {
             p.dv = c->pending_div;      // the launch ahead (penalty_decision_ahead) divided as it read: steps 2+3 do the same and write back divided
             c->pending_div = 0.0;
-        } else if (!timed && !c->step_palm && !c->rhs_ahead && rhs_takes_soc(c) && rhs_divides(c) && ql_divides(c, p.zmode)) {
+        } else if (!timed && !c->step_palm && !c->rhs_ahead && rhs_divides(c) && ql_divides(c, p.zmode)) {
             p.dv = c->pending_div;
             c->pending_div = 0.0;
         } else if ((rc = flush_division(c))) return rc;      // (a launch ahead that divided as it read saw the values the arrays now hold)
@@ -470,7 +436,7 @@ static int iteration_before(Ctx *c, bool timed, IterPlan &p, hipEvent_t *tv) {
     }
     if (timed) return 0;      // (the timed path of run_iteration_body goes on itself)
     c->zmid_stale = c->step_skip_zmid;
-    p.fused_rhs = rhs_takes_soc(c) && !ahead;      // [right-hand side + projection] -> sweeps -> inverse transform -> steps 2+3
+    p.fused_rhs = rhs_writes_modes(c) && !ahead;      // [right-hand side + projection] -> sweeps -> inverse transform -> steps 2+3
     p.fuse = !p.fused_rhs && soc_takes_inverse(c) && p.ahead_kind != 2;
     if (p.fused_rhs) { if ((rc = launch_rhs(c, true, p.dv))) return rc; }
     else if (!ahead && (rc = launch_rhs(c))) return rc;
@@ -597,21 +563,11 @@ int dots_create(const dots_problem_desc *desc, dots_ctx **out) {
     // measurement switches: every value is validated -- a typo must not silently select the default
     {
         bool ok = true;
-        ok &= env_int("DOTS_CG_STAGE_LDS", 0, 1, &c->cg_stage_lds);
-        ok &= env_int("DOTS_MG_TAIL_ROWS", 0, 1 << 20, &c->mg_tail_rows);
-        ok &= env_int("DOTS_SOC_WITH_RHS", 0, 1, &c->soc_with_rhs);
-        ok &= env_int("DOTS_QL_TWO", 0, 1, &c->ql_two);
         ok &= env_int("DOTS_KKT_TWO", 0, 1, &c->kkt_two);
-        ok &= env_int("DOTS_RHS_TWO", 0, 1, &c->rhs_two);
-        ok &= env_int("DOTS_RHS_TILES", 0, 2, &c->rhs_tiles);
         ok &= env_int("DOTS_ZMID_DEFER", 0, 1, &c->zmid_defer);    // 0: read-back iterations store z_mid as before
         ok &= env_int("DOTS_LAZY_DIV", 0, 1, &c->lazy_div);        // 0: a penalty update divides the dual arrays at once
-        ok &= env_int("DOTS_CARRY", 0, 1, &c->carry_arrays);       // 0: never allocate the carried gathers (DOTS_STEP_CARRY is then ignored)
-        ok &= env_int("DOTS_SPIN_FETCH", 0, 1, &c->spin_fetch);
-        ok &= env_int("DOTS_FRONT_VEC2", 0, 3, &c->front_vec2);      // 0 never, 1 / 2 wherever the pitch allows (default), 3 only where bandwidth-bound
-        ok &= env_int("DOTS_FRONT_RB", 1, 4, &c->front_rb_max);
+        ok &= env_int("DOTS_FRONT_VEC2", 0, 1, &c->front_vec2);      // 0: one mode per lane in the sweeps everywhere
         ok &= env_int("DOTS_FRONT_ROWS", 0, 2, &c->front_rows);      // 0: the fold kernels everywhere, 1: row kernels where the rules say (default), 2: wherever they fit
-        ok &= env_int("DOTS_FRONT_XCD", 0, 1, &c->front_xcd);
         ok &= env_int("DOTS_FRONT_LEAFINV", 0, 2, &c->front_leafinv);
         ok &= env_int("DOTS_FRONT_TUNE", 0, 2, &c->front_tune);
         ok &= env_int("DOTS_FRONT_NR", 2, 8, &c->front_nr_max);      // right-hand sides per launch of a batched solve (2, 4 or 8; A/B measurements)
@@ -1178,7 +1134,7 @@ int dots_mg_enable(dots_ctx *c, int on) {
 // they belong to the direct solver's iteration and are released with the factor (per context: a sharer of a factor has its own)
 static int front_carry_alloc(Ctx *c) {
     int rc;
-    if (c->d.TP <= 128 && c->carry_arrays && c->d.nl > 0) {      // (one GPU or a time slab with nodes)
+    if (c->d.TP <= 128 && c->d.nl > 0) {      // (one GPU or a time slab with nodes)
         const int64_t rows = (int64_t)3 * c->d.F;
         const double *sq = nullptr, *g = nullptr, *lo = nullptr, *e = nullptr;
         if ((rc = front_upload<double>(c, &sq, nullptr, (2 * rows) << c->d.tp_shift)) || (rc = front_upload<double>(c, &g, nullptr, rows << c->d.tp_shift)) ||

@@ -71,7 +71,6 @@ struct Dev {
     const double *kdiag;     // [V] diagonal of K
     const double *mu0, *mu1; // [V]
     const int *perm_v, *perm_f;
-    const int *tiles_vertex, *tiles_tri_ptr, *tiles_tri, *tiles_c_loc;   // owned arrays behind Ctx::tiles
     const double *Q;         // [(T+1)^2] or null
     const double *Qpad, *QpadT;  // [TP][TP] Q and its transpose, zero padded (operands of the MFMA transform)
     const double *sigma;     // [T+1] or null
@@ -193,16 +192,6 @@ struct MergeMember {
     int ch[2];                // its children inside the band by pull map (index of the member record, -1: none or below the band)
     int pad;
 };
-// Vertex tiles of the right-hand-side / projection launch cut from dots_problem_desc.patch_order (compact patches of the surface)
-// with the distinct triangles each tile touches (k_rhs_soc_tiles stages their rows of B, E in LDS).
-struct TileDev {
-    int n_tiles = 0, VTL = 0, ntri_max = 0;
-    const int *vertex = nullptr;     // [n_tiles][VTL] device vertices, -1 = padding
-    const int *tri_ptr = nullptr;    // [n_tiles + 1]
-    const int *tri = nullptr;        // the distinct triangles of every tile
-    const int *c_loc = nullptr;      // [3F] per corner-list entry: position of its triangle in its vertex's tile
-};
-
 struct FrontDev {
     int n_nodes = 0, n_levels = 0;        // original nodes; launches per sweep (= bands of tree heights)
     const FrontNode *nodes = nullptr;     // original tree (factorisation)
@@ -256,14 +245,12 @@ struct KktFused {
 constexpr uint32_t KKT_FUSED_MASK = 1u | 2u | 8u | 64u;
 
 struct Ctx;
-bool rhs_on_tiles(const Ctx *c);    // the right-hand-side / projection launch runs on patch tiles (k_rhs_soc_tiles)
-
 // ---- launch wrappers implemented in the kernel files (all asynchronous on ctx stream) ----
 int launch_soc_projection(Ctx *c, int zmid_mode = 0, bool with_inverse = false);   // 0: write z_mid; 1: write only the cone multiplier; with_inverse: extra workgroups do the modes -> time transform of phi
 void preload_alm_kernels();
 void preload_kkt_kernels();
 void preload_transform_kernels();
-int launch_rhs(Ctx *c, bool with_soc = false, double dv = 0.0);   // with_soc (only when rhs_takes_soc): the cone projection rides in the same launch; dv != 0 (only when rhs_divides): a pending penalty division is applied to what is read
+int launch_rhs(Ctx *c, bool with_soc = false, double dv = 0.0);   // with_soc (only when rhs_writes_modes): the cone projection rides in the same launch; dv != 0 (only when rhs_divides): a pending penalty division is applied to what is read
 bool rhs_divides(const Ctx *c);
 bool ql_divides(const Ctx *c, int zmid_mode);
 int launch_q_lambda_mult(Ctx *c, int zmid_mode = 0, double dv = 0.0);    // 0: read z_mid; 1: rebuild it from the multiplier and store it; 2: rebuild, do not store; dv != 0 (only when ql_divides): the dual arrays are divided as they are read and written back divided
@@ -346,29 +333,19 @@ struct Ctx {
     double *h_mail = nullptr;     // coherent pinned host memory the device writes itself: [0, MAX_SUMS) sums, [MAX_SUMS] sequence number (fetch_sums)
     uint64_t mail_seq = 0;
     int *kkt_counter = nullptr;   // device counter of k_reduce_mail (last workgroup publishes)
-    int spin_fetch = 1;           // DOTS_SPIN_FETCH=0: copy + stream synchronise instead of the device-written mailbox (A/B measurements)
     int64_t mail_spins = 20000000;   // host spins on the mailbox before it blocks on the stream (DOTS_MAIL_SPINS)
     int64_t mail_fallbacks = 0;   // evaluations whose sequence number never arrived: sums copied from the device scalars instead
     int mail_test_drop = 0;       // DOTS_MAIL_TEST_DROP=n (tests): every n-th evaluation publishes a wrong sequence number
     int front_rows = 1;           // row-per-lane-group sweep kernels on bands of short rows (DOTS_FRONT_ROWS: 0 never, 1 by rule, 2 wherever they fit)
-    int front_xcd = 1;            // DOTS_FRONT_XCD=0: plain work-list order in the sweeps
     int front_leafinv = 1;        // DOTS_FRONT_LEAFINV=0: the leaves keep [L^-1 ; G] blocks like every other node; 2: local inverses, coupling read from the CSR (no records)
     int front_tune = 0;           // DOTS_FRONT_TUNE=1 print the per-band timing table, 2 also apply the fastest choice
     int *h_flags = nullptr;
     int n_partial_blocks = 0;
     int last_cg_iters = 0;
-    int cg_stage_lds = 1;         // stage CSR row blocks in LDS (DOTS_CG_STAGE_LDS=0 disables, for A/B measurements)
     MgDev mg{};                   // multigrid preconditioner (nlev == 0: Jacobi only)
     int use_mg = 1;
-    int mg_tail_rows = 256;       // levels with at most this many rows run inside the single tail launch (DOTS_MG_TAIL_ROWS)
     int cg_graph_mg = -1;
-    int soc_with_rhs = 1;         // DOTS_SOC_WITH_RHS=0: keep the projection after the solve (A/B measurements)
     int kkt_two = 1;              // KKT sums with two nodes per lane (one GPU; DOTS_KKT_TWO=0: one)
-    int ql_two = 1;               // steps 2+3 with two nodes per lane (DOTS_QL_TWO=0: one, for A/B measurements)
-    int rhs_two = 1;              // right-hand side + projection with two time columns per lane (DOTS_RHS_TWO=0: one)
-    int carry_arrays = 1;         // DOTS_CARRY=0: no carried gathers (A/B measurements; dots_front_setup then allocates nothing for them)
-    int rhs_tiles = 0;            // DOTS_RHS_TILES: 1 patch tiles with the triangle rows staged in LDS (measured slower), 2 the plain launch on patch tiles (no difference); default 0
-    TileDev tiles{};
     // DOTS_STEP_TIMED: phase events of enqueue-only steps, collected later by dots_step_times (no host wait in the loop)
     static constexpr int TIME_SLOTS = 64;
     hipEvent_t tev[TIME_SLOTS][6]{};  // created on first use
@@ -406,7 +383,7 @@ struct Ctx {
     int front_fwd_qw[65]{};       // forward launch of a band: -1 the fold kernel (k_front_fwd), >= 0 the row kernel with 2^qw lane groups per row
     int front_fwd_lds[65]{};      // row kernel: columns of w a workgroup stages in LDS (the band's longest block)
     int front_planes[65]{};       // update planes the forward launch of a band reads per node (0, 2, 4 or 8)
-    int front_vec2 = 1;           // two modes per lane in the sweeps (DOTS_FRONT_VEC2: 0 never, 1 / 2 wherever the pitch allows, 3 only where bandwidth-bound)
+    int front_vec2 = 1;           // two modes per lane in the sweeps wherever the pitch allows (DOTS_FRONT_VEC2=0: never)
     int rhs_ahead_armed = 0;      // DOTS_STEP_RHS_AHEAD: the next KKT launch is followed by the next iteration's right-hand side
     int rhs_ahead = 0;            // ... which is on the stream and still valid (any call that changes state or parameters clears it); 2: with the
                                   // cone projection, whose results (z_fst, z_end, the cone multiplier) wait in the alternate buffers below
@@ -418,7 +395,6 @@ struct Ctx {
     int64_t penalty_ahead_started = 0, penalty_ahead_confirmed = 0;   // diagnostics (dots_debug_counter 2, 3)
     double ahead_div = 0.0;       // rhs_ahead == 2: the division the launch ahead applied as it read (steps 2+3 of the step that takes it must apply the same)
     double *zf_alt = nullptr, *ze_alt = nullptr, *lamc_alt = nullptr;   // [V][TP] each (one GPU): written ahead, swapped in by the step that takes them
-    int front_rb_max = 4;         // most rows (columns) of a node per workgroup (DOTS_FRONT_RB: 1, 2 or 4, for A/B measurements)
     double front_bytes = 0.0;     // factor bytes one solve reads (both sweeps, merged blocks as stored)
     double front_bytes_unmerged = 0.0;   // the same for one launch per tree height (no merged bands)
     int front_heights = 0;        // tree heights of the installed factor
@@ -491,15 +467,13 @@ inline bool soc_takes_inverse(const Ctx *c) { return rhs_writes_modes(c) && !tim
 // steps 2+3 can form the next iteration's per-corner gathers (k_q_lambda_mult_carry: whole triangles per 192-lane workgroup)
 // (one GPU or a time slab; the direct solver's iteration)
 inline bool carry_possible(const Ctx *c) {
-    return c->d.cn_sq && c->ql_two && c->d.TP >= 4 && c->d.TP <= 128 && c->use_front && c->front.n_nodes > 0 && c->lap_solver == DOTS_LAP_MODAL_PCG &&
+    return c->d.cn_sq && c->d.TP >= 4 && c->d.TP <= 128 && c->use_front && c->front.n_nodes > 0 && c->lap_solver == DOTS_LAP_MODAL_PCG &&
            (rhs_writes_modes(c) || c->d.slab);
 }
-// ... or the projection itself rides in the right-hand-side launch (enqueue-only iterations; TILE_ELEMS threads per tile)
-inline bool rhs_takes_soc(const Ctx *c) { return c->soc_with_rhs && rhs_writes_modes(c); }
 
 // a KKT evaluation of the conditions in `mask` reduces the sums the last steps-2+3 launch left (kernels_kkt.hip: kkt_sums) and reads no z_mid
 inline bool kkt_takes_fused(const Ctx *c, uint32_t mask) {
-    return c->kkt_fused_valid && !(mask & ~(KKT_FUSED_MASK | 4u)) && c->spin_fetch && c->h_mail && c->kkt_counter;
+    return c->kkt_fused_valid && !(mask & ~(KKT_FUSED_MASK | 4u)) && c->h_mail && c->kkt_counter;
 }
 
 int64_t array_count_host(const Dev &d, int array_id);    // elements in the reference layout
@@ -520,36 +494,19 @@ __device__ __forceinline__ D2 ld2(const double *p) { const double2 t = *reinterp
 __device__ __forceinline__ void st2(double *p, const D2 &x) { *reinterpret_cast<double2 *>(p) = make_double2(x.v[0], x.v[1]); }
 // the same with a streaming hint (non-temporal): data written once and read once by the next launch (the carried per-corner sums)
 // or not read at all in the loop (z_mid on read-back iterations) should not displace the factor and beta_mid from the caches.
-// A/B on one box (-DDOTS_CARRY_NT=0 against the default): knot 9 720-10 020 -> 10 160-10 210 it/s, sphere10k 4 795-4 813 -> 4 936-4 983,
-// torus100k 619 -> 631-646, knot63 unchanged (profiles/studies/r04_nontemporal.txt)
-#ifndef DOTS_CARRY_NT
-#define DOTS_CARRY_NT 1
-#endif
+// (Measured in round 4, plain loads and stores against these: knot 9 720-10 020 -> 10 160-10 210 it/s, sphere10k 4 795-4 813 ->
+// 4 936-4 983, torus100k 619 -> 631-646, knot63 unchanged; profiles/studies/r04_nontemporal.txt)
 typedef double dots_d2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ D2 ld2_nt(const double *p) {
-#if DOTS_CARRY_NT
     const dots_d2v t = __builtin_nontemporal_load(reinterpret_cast<const dots_d2v *>(p));
     return D2{{t.x, t.y}};
-#else
-    return ld2(p);
-#endif
 }
-__device__ __forceinline__ double ld1_nt(const double *p) {
-#if DOTS_CARRY_NT
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
-}
+__device__ __forceinline__ double ld1_nt(const double *p) { return __builtin_nontemporal_load(p); }
 __device__ __forceinline__ void st2_nt(double *p, const D2 &x) {
-#if DOTS_CARRY_NT
     dots_d2v t;
     t.x = x.v[0];
     t.y = x.v[1];
     __builtin_nontemporal_store(t, reinterpret_cast<dots_d2v *>(p));
-#else
-    st2(p, x);
-#endif
 }
 // slab predicates for local column t
 __device__ __forceinline__ bool first_node(const Dev &d, int t) { return d.t0 + t == 0; }       // global node 0
@@ -636,7 +593,7 @@ __device__ __forceinline__ void stage_q_chunk(const Dev &d, const double *Q, dou
 }
 template <bool FWD, int NB = BLOCK>
 __device__ __forceinline__ void modes_from_tile(const Dev &d, const double *Q, const double *xs, double *Qs, int IC, int v0, double *__restrict__ y,
-                                                int out_shift = -1, int j0 = 0, int jn = 1 << 30, bool staged0 = false, const int *__restrict__ vids = nullptr) {
+                                                int out_shift = -1, int j0 = 0, int jn = 1 << 30, bool staged0 = false) {
     if (out_shift < 0) out_shift = d.tp_shift;
     const int n = d.T + 1, TP = d.TP, TPp = TP + 1, tid = threadIdx.x;
     const int j = tid & (TP - 1), g = tid >> d.tp_shift, G = NB >> d.tp_shift;
@@ -663,7 +620,7 @@ __device__ __forceinline__ void modes_from_tile(const Dev &d, const double *Q, c
         for (int r = 0; r < 4; ++r) {
             const int vl = g + r * G;
             if (vl >= d.VT) continue;
-            const int vv = vids ? vids[vl] : v0 + vl;       // (vids: the tile's own vertex list, -1 = padding)
+            const int vv = v0 + vl;
             if (vv >= 0 && vv < d.V) y[((int64_t)vv << out_shift) + (j - j0)] = acc[r];
         }
     }

@@ -29,10 +29,7 @@ namespace dots {
 // kernels that gather these terms from memory and the steps-2+3 kernel that forms them from its registers for the next
 // iteration (DOTS_STEP_CARRY: cn_sq, cn_g below) then produce the same sums bit for bit (-ffp-contract=off: no fused multiply-adds).
 __device__ __forceinline__ double sum3(double x, double y, double z) { return (x + y) + z; }
-#ifndef DOTS_CARRY_BATCH
-#define DOTS_CARRY_BATCH 2
-#endif
-constexpr int CARRY_BATCH = DOTS_CARRY_BATCH;      // corners whose carried rows a lane loads before it adds them (closed surfaces: valence ~ 6)
+constexpr int CARRY_BATCH = 2;      // corners whose carried rows a lane loads before it adds them (closed surfaces: valence ~ 6)
 // one pre-image entry of the cone's middle block squared: (D (sB B - beta_mid))^2, sBB = sB * B already rounded
 __device__ __forceinline__ double soc_w2(double D, double sBB, double bm) {
     const double w = D * (sBB - bm);
@@ -130,12 +127,9 @@ __device__ __forceinline__ void soc_element(const Dev &d, int v, int t, double s
 // The projection of the intervals t and t + 1 (t even) of a vertex by ONE lane, multiplier only (one GPU: every node is held
 // here): B and the s = 0 entries of both intervals sit in one aligned 16-byte word per row, 15 loads per corner instead of 24;
 // half the waves for the same bytes (see k_q_lambda_mult_triangle2).  Interval for interval the arithmetic of soc_element.
-// STAGED: the rows of B come from LDS (`rows`: the tile's distinct triangles, [position][c][ldr]; `c_loc`: the position of a
-// corner-list entry's triangle) instead of from memory (k_rhs_soc_tiles): the same values, the same arithmetic.
 // CARRIED: see soc_element -- one 16-byte load per corner and half (the s = 1 shares are stored in the column of their INTERVAL).
-template <bool STAGED, bool CARRIED = false, bool DIV = false>
-__device__ __forceinline__ void soc_element2(const Dev &d, int v, int t, double sz, double cd, const double *rows = nullptr, int ldr = 0,
-                                             const int *__restrict__ c_loc = nullptr, double dv = 1.0) {
+template <bool CARRIED = false, bool DIV = false>
+__device__ __forceinline__ void soc_element2(const Dev &d, int v, int t, double sz, double cd, double dv = 1.0) {
     const double sB = sz * INV_SQRT3;
     const int iv = idxV(d, v, t);
     const bool two = t + 1 < d.ni;                 // the second interval exists (T odd: not for the last pair)
@@ -169,14 +163,8 @@ __device__ __forceinline__ void soc_element2(const Dev &d, int v, int t, double 
         double b2[3], m1a[3], m1b[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            if (STAGED) {
-                const double *rw = rows + (c_loc[j] * 3 + c) * ldr + t;
-                bt[c] = ld2(rw);
-                b2[c] = two ? rw[2] : 0.0;
-            } else {
-                bt[c] = ld2(d.B + idxF(d, f, c, t));
-                b2[c] = two ? d.B[idxF(d, f, c, t + 2)] : 0.0;
-            }
+            bt[c] = ld2(d.B + idxF(d, f, c, t));
+            b2[c] = two ? d.B[idxF(d, f, c, t + 2)] : 0.0;
             m0[c] = ld2(d.bm + idxM(d, fk, 0, c, t));
             m1a[c] = d.bm[idxM(d, fk, 1, c, t)];
             m1b[c] = two ? d.bm[idxM(d, fk, 1, c, t + 1)] : 0.0;
@@ -432,10 +420,8 @@ __global__ __launch_bounds__(RHS_NB) void k_rhs_modes(Dev d, double r, double ep
 
 // The right-hand side at the nodes t and t + 1 (t even) of a vertex by one lane (one GPU), node for node the arithmetic of
 // rhs_value: B and E of both nodes in one 16-byte word per row.
-// STAGED: B - E of the tile's distinct triangles comes from LDS (see soc_element2).
-template <bool STAGED, bool CARRIED = false, bool DIV = false>
-__device__ __forceinline__ void rhs_value2(const Dev &d, int v, int t, double r, double eps, double (&out)[2], const double *rows = nullptr, int ldr = 0,
-                                           const int *__restrict__ c_loc = nullptr, double dv = 1.0) {
+template <bool CARRIED = false, bool DIV = false>
+__device__ __forceinline__ void rhs_value2(const Dev &d, int v, int t, double r, double eps, double (&out)[2], double dv = 1.0) {
     const int iv = idxV(d, v, t);
     const double m = d.mass_v[v];
     const double ih = 1.0 / d.h;
@@ -473,20 +459,16 @@ __device__ __forceinline__ void rhs_value2(const Dev &d, int v, int t, double r,
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             ga[c] = d.c_gA[j * 3 + c];
-            if (STAGED) {
-                b[c] = ld2(rows + (c_loc[j] * 3 + c) * ldr + t);      // B - E, subtracted when it was staged
-            } else {
-                const int64_t i = idxF(d, f, c, t);
-                b[c] = ld2(d.B + i);
-                e[c] = ld2(d.E + i);
-                if (DIV) { e[c].v[0] /= dv; e[c].v[1] /= dv; }
-            }
+            const int64_t i = idxF(d, f, c, t);
+            b[c] = ld2(d.B + i);
+            e[c] = ld2(d.E + i);
+            if (DIV) { e[c].v[0] /= dv; e[c].v[1] /= dv; }
         }
         double g0[3], g1[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            g0[c] = ga[c] * (STAGED ? b[c].v[0] : b[c].v[0] - e[c].v[0]);
-            g1[c] = ga[c] * (STAGED ? b[c].v[1] : b[c].v[1] - e[c].v[1]);
+            g0[c] = ga[c] * (b[c].v[0] - e[c].v[0]);
+            g1[c] = ga[c] * (b[c].v[1] - e[c].v[1]);
         }
         ds[0] += sum3(g0[0], g0[1], g0[2]);
         ds[1] += sum3(g1[0], g1[1], g1[2]);
@@ -504,15 +486,13 @@ __device__ __forceinline__ void rhs_value2(const Dev &d, int v, int t, double r,
 // k_rhs_modes with two time columns per lane (one GPU, direct solver): 512 threads per tile.
 constexpr int RHS_NB2 = RHS_NB / 2;
 template <bool CARRIED, bool DIV = false>
-__global__ __launch_bounds__(RHS_NB2) void k_rhs_modes2(Dev d, double r, double eps, double *__restrict__ bhat, int IC, int n_rhs, double sz, double cd,
-                                                        const int *__restrict__ tile_vertex, double dv) {
-    // tile_vertex (or null): the tiles' vertices taken from dots_problem_desc.patch_order instead of from the numbering
+__global__ __launch_bounds__(RHS_NB2) void k_rhs_modes2(Dev d, double r, double eps, double *__restrict__ bhat, int IC, int n_rhs, double sz, double cd, double dv) {
     const int e = 2 * threadIdx.x, vl = e >> d.tp_shift, t = e & (d.TP - 1);
     if ((int)blockIdx.x >= n_rhs) {
         const int st = xcd_tile(blockIdx.x - n_rhs, d.n_vtiles);
         if (st >= d.n_vtiles) return;
-        const int v = tile_vertex ? tile_vertex[st * d.VT + vl] : (st * d.VT + vl < d.V ? st * d.VT + vl : -1);
-        if (v >= 0 && t < d.ni) soc_element2<false, CARRIED, DIV>(d, v, t, sz, cd, nullptr, 0, nullptr, dv);
+        const int v = st * d.VT + vl;
+        if (v < d.V && t < d.ni) soc_element2<CARRIED, DIV>(d, v, t, sz, cd, dv);
         return;
     }
     extern __shared__ double tm_lds[];
@@ -522,75 +502,16 @@ __global__ __launch_bounds__(RHS_NB2) void k_rhs_modes2(Dev d, double r, double 
     const int tile = xcd_tile(blockIdx.x, d.n_vtiles);
     if (tile >= d.n_vtiles) return;
     const int v0 = tile * d.VT;
-    const int *__restrict__ tv = tile_vertex ? tile_vertex + v0 : nullptr;
     stage_q_chunk<true, RHS_NB2>(d, d.Q, Qs, 0, min(IC, n));      // in flight while the corner walks run
     for (int ee = e; ee < TILE_ELEMS; ee += 2 * RHS_NB2) {       // (one pass: TILE_ELEMS = 2 * RHS_NB2)
         const int vv = ee >> d.tp_shift, tt = ee & (TP - 1);
-        const int v = tv ? tv[vv] : (v0 + vv < d.V ? v0 + vv : -1);
+        const int v = v0 + vv;
         double b[2] = {0.0, 0.0};
-        if (v >= 0 && tt < n) rhs_value2<false, CARRIED, DIV>(d, v, tt, r, eps, b, nullptr, 0, nullptr, dv);
+        if (v < d.V && tt < n) rhs_value2<CARRIED, DIV>(d, v, tt, r, eps, b, dv);
         xs[vv * TPp + tt] = b[0];
         xs[vv * TPp + tt + 1] = tt + 1 < n ? b[1] : 0.0;
     }
-    modes_from_tile<true, RHS_NB2>(d, d.Q, xs, Qs, IC, v0, bhat, -1, 0, 1 << 30, true, tv);
-}
-
-// The right-hand side + projection launch on PATCH tiles (dots_problem_desc.patch_order): a workgroup of 256 threads takes
-// TILE2 / TP vertices of a compact patch of the surface (two time columns per lane) and stages the rows of B of the patch's
-// DISTINCT triangles in LDS once; the projection walks its corner lists against them (beta_mid streams from memory, each
-// entry once); then E is subtracted in place and the right-hand side walks the same lists against B - E, followed at once by
-// the time-mode transform of the tile.  The corner walks of k_rhs_modes2 fetch the three rows of B (and of E) of a triangle
-// once per corner VERTEX; the caches catch little of that beside the beta_mid stream (PMC at torus100k: 2.25 GB read for
-// 1.50 GB algorithmic).  Here a triangle's rows are read once per tile that touches it (~1.6 tiles), and B serves both halves.
-// Vertex for vertex and corner for corner the arithmetic of rhs_value2 / soc_element2: results are bit-identical.
-constexpr int TILE2_NB = 256;      // (a tile of k_rhs_soc_tiles: 512 (vertex, time) elements, two per lane)
-template <bool WITH_SOC>
-__global__ __launch_bounds__(TILE2_NB) void k_rhs_soc_tiles(Dev d, TileDev tl, double r, double eps, double *__restrict__ bhat, int IC, double sz, double cd) {
-    extern __shared__ double tm_lds[];
-    const int n = d.T + 1, TP = d.TP, TPp = TP + 1, ldr = TP + 2;
-    double *Qs = tm_lds;                          // [IC][TP]
-    double *xs = tm_lds + IC * TP;                // [VTL][TPp]
-    double *rows = xs + tl.VTL * TPp + (((tl.VTL * TPp) & 1) ? 1 : 0);      // [distinct triangles][3][ldr], 16-byte aligned
-    const int tile = xcd_tile(blockIdx.x, tl.n_tiles);
-    if (tile >= tl.n_tiles) return;
-    const int *__restrict__ tv = tl.vertex + tile * tl.VTL;
-    const int t0 = tl.tri_ptr[tile], nrow = 3 * (tl.tri_ptr[tile + 1] - t0);
-    const int lr = TP >> 1, tid = threadIdx.x;    // lanes per row (two columns each)
-    const int ra = (tid & (lr - 1)) * 2, r0 = tid / lr, rstep = TILE2_NB / lr;
-    for (int row = r0; row < nrow; row += rstep) {
-        const int f = tl.tri[t0 + row / 3], c = row - 3 * (row / 3);
-        D2 b = ld2(d.B + idxF(d, f, c, ra));
-        if (!WITH_SOC) {
-            const D2 e = ld2(d.E + idxF(d, f, c, ra));
-            b.v[0] -= e.v[0];
-            b.v[1] -= e.v[1];
-        }
-        st2(rows + row * ldr + ra, b);
-    }
-    stage_q_chunk<true, TILE2_NB>(d, d.Q, Qs, 0, min(IC, n));
-    __syncthreads();
-    const int e2 = 2 * tid, vl = e2 >> d.tp_shift, t = e2 & (TP - 1);
-    const int v = tv[vl];
-    if (WITH_SOC) {
-        if (v >= 0 && t < d.ni) soc_element2<true>(d, v, t, sz, cd, rows, ldr, tl.c_loc);
-        __syncthreads();
-        for (int row = r0; row < nrow; row += rstep) {      // (every thread updates the entries it staged itself)
-            const int f = tl.tri[t0 + row / 3], c = row - 3 * (row / 3);
-            const D2 e = ld2(d.E + idxF(d, f, c, ra));
-            D2 b = ld2(rows + row * ldr + ra);
-            b.v[0] -= e.v[0];
-            b.v[1] -= e.v[1];
-            st2(rows + row * ldr + ra, b);
-        }
-        __syncthreads();
-    }
-    double b[2] = {0.0, 0.0};
-    if (v >= 0 && t < n) rhs_value2<true>(d, v, t, r, eps, b, rows, ldr, tl.c_loc);
-    xs[vl * TPp + t] = b[0];
-    xs[vl * TPp + t + 1] = t + 1 < n ? b[1] : 0.0;
-    Dev dt = d;
-    dt.VT = tl.VTL;
-    modes_from_tile<true, TILE2_NB>(dt, d.Q, xs, Qs, IC, 0, bhat, -1, 0, 1 << 30, true, tv);
+    modes_from_tile<true, RHS_NB2>(d, d.Q, xs, Qs, IC, v0, bhat, -1, 0, 1 << 30, true);
 }
 
 // T + 1 >= 64: 32 vertices per workgroup, the transform on the matrix cores.
@@ -616,26 +537,11 @@ __global__ __launch_bounds__(RHS_NB) void k_rhs_modes_mfma(Dev d, double r, doub
     modes_from_tile_mfma<RHS_NB / 64>(d, d.Qpad, xs_m, v0, bhat);
 }
 
-constexpr size_t RHS_TILES_LDS_MAX = 80 * 1024;      // two workgroups per CU stay resident
-// LDS of k_rhs_soc_tiles: Q chunk + the tile of right-hand-side values + the staged triangle rows
-static size_t rhs_tiles_lds(const Dev &d, const TileDev &tl) {
-    const size_t xs = (size_t)tl.VTL * (d.TP + 1);
-    return sizeof(double) * ((size_t)time_modes_chunk(d) * d.TP + xs + (xs & 1) + (size_t)tl.ntri_max * 3 * (d.TP + 2));
-}
-// DOTS_RHS_TILES=1 (default 0).  Measured in round 3 (profiles/studies/r03_rhs_tiles.txt): the staged launch reads what it was
-// built to read (a triangle's rows once per tile) and gives the same iterates bit for bit, but 170 B of LDS per thread leave
-// 8 of 32 waves per CU resident, and the launch it replaces runs at 5.9 TB/s of traffic BECAUSE it is at full occupancy:
-// torus100k 556 -> 500 it/s, sphere10k 4 960 -> 4 330, knot 10 350 -> 9 100.  Kept as an alternative, off by default.
-bool rhs_on_tiles(const Ctx *c) {
-    const TileDev &tl = c->tiles;
-    return c->rhs_tiles == 1 && tl.n_tiles > 0 && rhs_tiles_lds(c->d, tl) <= RHS_TILES_LDS_MAX;
-}
-
 // the right-hand-side (+ projection) launch that launch_rhs would pick can divide the dual arrays as it reads them
 bool rhs_divides(const Ctx *c) {
     if (!rhs_writes_modes(c) || c->carry_valid) return false;
     if (time_modes_mfma_ok(c->d)) return true;
-    return c->rhs_two && c->d.TP >= 4 && !rhs_on_tiles(c);
+    return c->d.TP >= 4;
 }
 
 int launch_rhs(Ctx *c, bool with_soc, double dv) {
@@ -652,31 +558,15 @@ int launch_rhs(Ctx *c, bool with_soc, double dv) {
             hipLaunchKernelGGL(k_rhs_modes_mfma<false>, dim3(n_rhs + (with_soc ? g : 0)), dim3(RHS_NB), sizeof(double) * TM_ROWS * (c->d.TP + 1), c->stream, c->d,
                                c->prm.r / c->prm.boundary_scale, c->prm.eps, c->d.cg_p0, n_rhs, n_tiles, c->prm.scale_z, c->prm.const_d, 1.0);
     }
-    else if (rhs_writes_modes(c) && c->rhs_two && c->d.TP >= 4 && c->carry_valid)      // the corners' shares come from the last steps-2+3 launch
+    else if (rhs_writes_modes(c) && c->d.TP >= 4 && c->carry_valid)      // the corners' shares come from the last steps-2+3 launch
         hipLaunchKernelGGL(k_rhs_modes2<true>, dim3(with_soc ? 2 * g : g), dim3(RHS_NB2), time_modes_tile_lds(c->d), c->stream, c->d, c->prm.r / c->prm.boundary_scale,
-                           c->prm.eps, c->d.cg_p0, time_modes_chunk(c->d), g, c->prm.scale_z, c->prm.const_d, (const int *)nullptr, 1.0);
+                           c->prm.eps, c->d.cg_p0, time_modes_chunk(c->d), g, c->prm.scale_z, c->prm.const_d, 1.0);
     else if (dv != 0.0)      // a penalty update is pending: the dual arrays are divided as they are read (rhs_divides told the caller this launch can)
         hipLaunchKernelGGL((k_rhs_modes2<false, true>), dim3(with_soc ? 2 * g : g), dim3(RHS_NB2), time_modes_tile_lds(c->d), c->stream, c->d, c->prm.r / c->prm.boundary_scale,
-                           c->prm.eps, c->d.cg_p0, time_modes_chunk(c->d), g, c->prm.scale_z, c->prm.const_d, (const int *)nullptr, dv);
-    else if (rhs_writes_modes(c) && c->rhs_two && rhs_on_tiles(c)) {     // patch tiles, triangle rows staged in LDS (large meshes)
-        const TileDev &tl = c->tiles;
-        const int IC = time_modes_chunk(c->d), gt = xcd_grid(tl.n_tiles);
-        const size_t lds = rhs_tiles_lds(c->d, tl);
-        static bool raised = false;      // more than the default 64 KB of dynamic LDS needs the attribute (once per process)
-        if (!raised) {
-            DOTS_HIP(hipFuncSetAttribute((const void *)k_rhs_soc_tiles<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RHS_TILES_LDS_MAX));
-            DOTS_HIP(hipFuncSetAttribute((const void *)k_rhs_soc_tiles<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RHS_TILES_LDS_MAX));
-            raised = true;
-        }
-        if (with_soc) hipLaunchKernelGGL((k_rhs_soc_tiles<true>), dim3(gt), dim3(TILE2_NB), lds, c->stream, c->d, tl, c->prm.r / c->prm.boundary_scale, c->prm.eps, c->d.cg_p0,
-                                         IC, c->prm.scale_z, c->prm.const_d);
-        else hipLaunchKernelGGL((k_rhs_soc_tiles<false>), dim3(gt), dim3(TILE2_NB), lds, c->stream, c->d, tl, c->prm.r / c->prm.boundary_scale, c->prm.eps, c->d.cg_p0,
-                                IC, c->prm.scale_z, c->prm.const_d);
-    }
-    else if (rhs_writes_modes(c) && c->rhs_two && c->d.TP >= 4)      // two time columns per lane (16-byte accesses)
+                           c->prm.eps, c->d.cg_p0, time_modes_chunk(c->d), g, c->prm.scale_z, c->prm.const_d, dv);
+    else if (rhs_writes_modes(c) && c->d.TP >= 4)      // two time columns per lane (16-byte accesses)
         hipLaunchKernelGGL(k_rhs_modes2<false>, dim3(with_soc ? 2 * g : g), dim3(RHS_NB2), time_modes_tile_lds(c->d), c->stream, c->d, c->prm.r / c->prm.boundary_scale,
-                           c->prm.eps, c->d.cg_p0, time_modes_chunk(c->d), g, c->prm.scale_z, c->prm.const_d,
-                           (c->rhs_tiles == 2 && c->tiles.n_tiles > 0) ? c->tiles.vertex : (const int *)nullptr, 1.0);
+                           c->prm.eps, c->d.cg_p0, time_modes_chunk(c->d), g, c->prm.scale_z, c->prm.const_d, 1.0);
     else if (rhs_writes_modes(c))
         hipLaunchKernelGGL(k_rhs_modes, dim3(with_soc ? 2 * g : g), dim3(RHS_NB), time_modes_tile_lds(c->d), c->stream, c->d, c->prm.r / c->prm.boundary_scale,
                            c->prm.eps, c->d.cg_p0, time_modes_chunk(c->d), g, c->prm.scale_z, c->prm.const_d);
@@ -1156,11 +1046,8 @@ __global__ __launch_bounds__(BLOCK) void k_q_lambda_mult_triangle2(Dev d, double
 // them (soc_element2 / rhs_value2 <CARRIED>) instead of walking index lists into B, E and beta_mid.
 // Replaces one of the three passes over beta_mid per iteration (solver_socp.py:997-1017 reads what :716-722 just wrote).
 // 148-152 VGPRs = 3 waves per SIMD by themselves; the instantiation with the KKT sums is held there (170 otherwise).
-// (A/B: -DDOTS_CARRY_WAVES=4 caps the registers at 128, 20 spilled: knot 10 900 -> 9 500 it/s, torus100k 630 -> 585)
-#ifndef DOTS_CARRY_WAVES
-#define DOTS_CARRY_WAVES 3
-#endif
-#define CARRY_OCCUPANCY __attribute__((amdgpu_waves_per_eu(DOTS_CARRY_WAVES)))
+// (Measured: 4 waves per SIMD capped the registers at 128 and spilled 20: knot 10 900 -> 9 500 it/s, torus100k 630 -> 585)
+#define CARRY_OCCUPANCY __attribute__((amdgpu_waves_per_eu(3)))
 // this workgroup's partial sums (thread 0 holds the totals) into the fused-KKT buffers: slot SLOT[i] of block `bid` of `nblk`
 template <int N>
 __device__ __forceinline__ void store_fused(const double (&v)[N], const int (&slot)[N], int first, double *__restrict__ part, int nblk, int bid) {
@@ -1188,9 +1075,7 @@ __global__ __launch_bounds__(CARRY_NB) CARRY_OCCUPANCY void k_q_lambda_mult_carr
     const int e = 2 * tid, lr = e >> d.tp_shift, t = e & (d.TP - 1);      // local row (3 per triangle), first node
     const int f = wg * tri_per_wg + lr / 3, c = lr - 3 * (lr / 3);
     const bool active = f < d.F && t < d.nl;      // (a whole triangle is active or not; so is a column over its three rows)
-#ifndef DOTS_CARRY_CPOS_LATE
     const int j = active ? d.cpos[f * 3 + c] : 0; // row of this lane's corner k = c in the carried arrays (loaded with the lane's other constants)
-#endif
     double kt[KF_N] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (active) ql2_lane<ZMODE, false, true, KKT, DIV, BMNT>(d, f, c, t, sz * INV_SQRT3, 1.0 + 2.0 * sz * sz, 1.0 + sz * sz, tau, xs + tid, sz, kt, dv);
     __syncthreads();
@@ -1206,9 +1091,6 @@ __global__ __launch_bounds__(CARRY_NB) CARRY_OCCUPANCY void k_q_lambda_mult_carr
     // the row's last lane (t = TP - 2) would need interval TP - 1 >= T, which does not exist.
     const double nxt = __shfl_down(q[2], 1, 64);
     if (active) {
-#ifdef DOTS_CARRY_CPOS_LATE
-        const int j = d.cpos[f * 3 + c];
-#endif
         if (emit & 1) {
             st2_nt(d.cn_sq + ((int64_t)(2 * j) << d.tp_shift) + t, D2{{q[0], q[1]}});
             st2_nt(d.cn_sq + ((int64_t)(2 * j + 1) << d.tp_shift) + t, D2{{q[3], t + 2 < d.TP ? nxt : 0.0}});
@@ -1334,7 +1216,7 @@ int launch_q_lambda_mult(Ctx *c, int zmid_mode, double dv) {
         if (k) { c->kkt_fused = kf; c->kkt_fused_valid = 1; }
         return 0;
     }
-    if (c->ql_two && c->d.TP >= 4) {      // two nodes per lane (16-byte accesses): k_q_lambda_mult_triangle2
+    if (c->d.TP >= 4) {      // two nodes per lane (16-byte accesses): k_q_lambda_mult_triangle2
         const dim3 g2(nf8 * (TILE_ELEMS / (2 * BLOCK)) + nv8);
         if (zmid_mode == 2) hipLaunchKernelGGL((k_q_lambda_mult_triangle2<2>), g2, dim3(BLOCK), 0, c->stream, c->d, p.scale_z, p.tau, nf8, cd, cr);
         else if (zmid_mode == 1) hipLaunchKernelGGL((k_q_lambda_mult_triangle2<1>), g2, dim3(BLOCK), 0, c->stream, c->d, p.scale_z, p.tau, nf8, cd, cr);

@@ -167,7 +167,6 @@ struct CgArgs {
     int G;                 // workgroups (= tiles, padded to a multiple of 8)
     int nc;                // scalar columns
     int pstride;           // doubles per partial array = G * TP (MODAL) or G
-    int stage;             // 1: stage the CSR row block in LDS, 0: read it through L1
     int mg;                // 1: z comes from the multigrid V-cycle (r.z and the stopping norm are separate sums)
     int collapse;          // 1: a small kernel sums the G partial rows once and consumers read that single row
     int Gr;                // rows a consumer re-reduces: G, or 1 when collapsed
@@ -231,17 +230,15 @@ __global__ __launch_bounds__(CG_NB) void k_cg_apply(Dev d, CgArgs a) {
         const int v0 = tile * a.vt;
         const int nrows = min(a.vt, d.V - v0);
         const int rp0 = d.rowptr[v0];
-        const int cap = a.stage ? a.cap : 0;
-        if (a.stage) {
-            for (int i = tid; i <= nrows; i += a.nb) l.rp[i] = d.rowptr[v0 + i] - rp0;
-            __syncthreads();
-            const int nloc = min(l.rp[nrows], cap);
-            for (int i = tid; i < nloc; i += a.nb) {
-                l.col[i] = d.col[rp0 + i];
-                l.val[i] = d.val[rp0 + i];
-            }
-            __syncthreads();
+        const int cap = a.cap;
+        for (int i = tid; i <= nrows; i += a.nb) l.rp[i] = d.rowptr[v0 + i] - rp0;
+        __syncthreads();
+        const int nloc = min(l.rp[nrows], cap);
+        for (int i = tid; i < nloc; i += a.nb) {
+            l.col[i] = d.col[rp0 + i];
+            l.val[i] = d.val[rp0 + i];
         }
+        __syncthreads();
 
         const bool use_p = FUSE_P && (beta != 0.0);
         for (int q = 0; q < a.ept; ++q) {
@@ -256,8 +253,8 @@ __global__ __launch_bounds__(CG_NB) void k_cg_apply(Dev d, CgArgs a) {
                 return x;
             };
             double sum = 0.0;
-            int j = a.stage ? l.rp[vl] : d.rowptr[v] - rp0;
-            const int jend = a.stage ? l.rp[vl + 1] : d.rowptr[v + 1] - rp0;
+            int j = l.rp[vl];
+            const int jend = l.rp[vl + 1];
             // gathers in batches of four independent loads (rows have ~7 entries)
             for (; j + 4 <= jend && j + 4 <= cap; j += 4) {
                 const int u0 = l.col[j], u1 = l.col[j + 1], u2 = l.col[j + 2], u3 = l.col[j + 3];
@@ -517,7 +514,6 @@ static CgArgs make_args(Ctx *c, bool modal) {
     a.prow = modal ? d.TP : 1;
     a.pstride = a.G * a.prow;
     a.Gr = a.collapse ? 1 : a.G;
-    a.stage = c->cg_stage_lds;
     a.mg = (modal && c->mg.nlev > 1 && c->use_mg) ? 1 : 0;
     a.eps = c->prm.eps;
     a.tol2 = c->prm.cg_tol * c->prm.cg_tol;

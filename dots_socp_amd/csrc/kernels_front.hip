@@ -548,11 +548,8 @@ __global__ __launch_bounds__(NB) void k_front_bwd(FrontArgs g, FrontDev f, const
 // it are column i of the rows below (every entry is one run of modes: the lanes of a group still load 16 consecutive bytes each).  The first
 // LEAF_PRE entries of the row are loaded into registers BEFORE the vector they multiply is staged (leaf_row_load: the factor streams from memory while
 // the workgroup gathers its right-hand side), the rest -- leaves of more than LEAF_PRE vertices: degenerate cuts only -- behind it.
-// (A/B on one box, -DDOTS_LEAF_PRE=16 / 8 / 4: torus100k solve 671 / 660 / 660 us -- 94 VGPRs and 5 waves per SIMD against ~60 and 8 --, torus65k_T127 1 422 / 1 426 / 1 424)
-#ifndef DOTS_LEAF_PRE
-#define DOTS_LEAF_PRE 8
-#endif
-constexpr int LEAF_PRE = DOTS_LEAF_PRE;
+// (Measured on one box with 16 / 8 / 4 entries: torus100k solve 671 / 660 / 660 us -- 94 VGPRs and 5 waves per SIMD against ~60 and 8 --, torus65k_T127 1 422 / 1 426 / 1 424)
+constexpr int LEAF_PRE = 8;
 __device__ __forceinline__ int64_t leaf_entry(int i, int j) { return j <= i ? (int64_t)i * (i + 1) / 2 + j : (int64_t)j * (j + 1) / 2 + i; }
 template <int VEC>
 __device__ __forceinline__ void leaf_row_load(Vd<VEC> (&s)[LEAF_PRE], const double *__restrict__ P, int i, int n, int sh) {
@@ -898,11 +895,10 @@ __global__ __launch_bounds__(256) void k_flush_read(const double *__restrict__ x
 
 // two modes per lane (16-byte loads, half the waves).  Round 1 (one launch per tree height): +6 % at torus100k, +13 % at T = 127,
 // -2 % on the latency-bound sphere10k; with merged bands it pays there too (knot solve 53.6 -> 51.9 us, sphere10k 97 -> 95.5 us):
-// on wherever the pitch allows.  DOTS_FRONT_VEC2=0 turns it off, =3 restores the round-1 rule (pitch >= 64 or a factor > 1 GB).
+// on wherever the pitch allows (DOTS_FRONT_VEC2=0 turns it off).
 static bool front_two_modes(const Ctx *c) {
     const Dev &d = c->dcg;
-    if (!c->front_vec2 || d.TP < 4 || d.TP > 128) return false;
-    return c->front_vec2 != 3 || d.TP >= 64 || c->front_bytes > 1.0e9;
+    return c->front_vec2 && d.TP >= 4 && d.TP <= 128;
 }
 
 // right-hand sides a workgroup of 1024 threads (128 VGPRs) takes without spilling: forward fold kernel / the others (front_solve_many splits)
@@ -1475,8 +1471,8 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
         // 128 a 256-thread workgroup splits a dot product only 4 ways: 1024 threads up to 3000 columns)
         if (cols >= (d.TP >= 128 ? 3000 : (two_modes ? 1024 : 1536)) || !big_ok) { bnb = 256; bcb = cols >= 4096 ? 4 : (cols >= 2048 ? 2 : 1); }
         else { bnb = 1024; bcb = (d.TP >= 128 && cols >= 600) ? 4 : (cols >= 250 ? 2 : 1); }
-        c->front_fwd_rb[k] = std::min(frb, c->front_rb_max);
-        c->front_bwd_cb[k] = std::min(bcb, c->front_rb_max);
+        c->front_fwd_rb[k] = frb;      // (1, 2 or 4)
+        c->front_bwd_cb[k] = bcb;
         c->front_fwd_nb[k] = fnb;
         c->front_bwd_nb[k] = bnb;
         // Bands of short rows take the row kernel (k_front_fwd_rows): QW lane groups per row by the band's mean row length
@@ -1529,7 +1525,7 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
         if (leaf_inv)
             for (int gi : by_band[0]) leaf_entries += 0.5 * (double)groups[(size_t)gi].n * (groups[(size_t)gi].n + 1.0);
         const double factor_b = per * ((double)all_entries + leaf_entries), work_b = h->values ? 0.0 : per * (double)(h->n_entries + srows);
-        const double carry_b = (c->d.TP <= 128 && c->carry_arrays) ? 8.0 * (c->shard_stride == 0 ? 12.0 : 9.0) * (double)c->d.F * (double)c->d.TP : 0.0;
+        const double carry_b = c->d.TP <= 128 ? 8.0 * (c->shard_stride == 0 ? 12.0 : 9.0) * (double)c->d.F * (double)c->d.TP : 0.0;
         size_t free_b = 0, total_b = 0;
         DOTS_HIP(hipMemGetInfo(&free_b, &total_b));
         double budget = 0.97 * (double)free_b;
@@ -1781,11 +1777,9 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
     // that the row blocks of a node, which read the same right-hand-side and plane rows, share an L2.  Measured (solve, us):
     // knot 49.3 -> 44.0, sphere10k 97.4 -> 89.5, knot63 80.0 -> 74.0; launches of few large nodes (>= 100 workgroups per node:
     // the top of torus100k) lose 4 % with it and keep the plain order; the large launches below them do not care.
-    // DOTS_FRONT_XCD=0: plain order everywhere.
-    const bool xcd_deal = c->front_xcd != 0;
     auto deal = [&](std::vector<FrontWork> &list, size_t from, size_t n_nodes) {
         const size_t n = list.size() - from;
-        if (!xcd_deal || n_nodes < 8 || n < 16 || n > 80 * n_nodes) return;
+        if (n_nodes < 8 || n < 16 || n > 80 * n_nodes) return;
         const size_t per = (n + 7) / 8;
         std::vector<FrontWork> out;
         out.reserve(n);
@@ -1939,12 +1933,7 @@ static int front_leaf_threads(const Ctx *c) {
     const int lanes = c->dcg.TP / (front_two_modes(c) ? 2 : 1);
     // (sixteen rows in flight per workgroup at every pitch -- 1024 threads at a pitch of 128 -- lose: torus65k_T127 110 / 87 -> 115 / 110 us per launch,
     // one workgroup per CU instead of four; workgroups grow only where a row of modes needs more than 256 lanes)
-#ifdef DOTS_LEAF_NB      // (A/B)
-    (void)lanes;
-    return DOTS_LEAF_NB;
-#else
     return lanes <= 256 ? 256 : (lanes <= 512 ? 512 : 1024);
-#endif
 }
 template <int NR>
 static void front_launch_leaves(Ctx *c, const FrontDev &f, bool forward, const double *bhat, double *x, const MoreRhs<NR> &mr) {

@@ -568,7 +568,7 @@ static int wait_mail(Ctx *c, double seq, int n) {
 }
 
 static int fetch_sums(Ctx *c, int n) {
-    if (c->spin_fetch && c->h_mail && n <= MAX_SUMS && n <= 64) {
+    if (c->h_mail && n <= MAX_SUMS && n <= 64) {
         const double seq = (double)(++c->mail_seq);
         const bool drop = c->mail_test_drop > 0 && c->mail_seq % (uint64_t)c->mail_test_drop == 0;      // tests: this publish goes astray
         hipLaunchKernelGGL(k_mail_sums, dim3(1), dim3(64), 0, c->stream, c->d.scal + S::SUMS, n, c->h_mail, drop ? -seq : seq);
@@ -649,7 +649,7 @@ int kkt_sums(Ctx *c, uint32_t mask, double *sums) {
         else hipLaunchKernelGGL(k_kkt_sums<false>, dim3(nv + nf), dim3(BLOCK), 0, c->stream, d, a, nv, d.partials, part_f);
     }
     int rc;
-    if (c->spin_fetch && c->h_mail && c->kkt_counter) {
+    if (c->h_mail && c->kkt_counter) {
         const double seq = (double)(++c->mail_seq);
         const bool drop = c->mail_test_drop > 0 && c->mail_seq % (uint64_t)c->mail_test_drop == 0;      // tests: this publish goes astray
         hipLaunchKernelGGL(k_reduce_mail, dim3(N_SUMS), dim3(BLOCK), 0, c->stream, src, c->d.scal + S::SUMS, c->h_mail, drop ? -seq : seq, c->kkt_counter);
@@ -658,7 +658,7 @@ int kkt_sums(Ctx *c, uint32_t mask, double *sums) {
         // right-hand side (it reads only what the next dots_step would read; dots_api.hip: check() drops it if anything changes)
         if (c->rhs_ahead_armed) {
             c->rhs_ahead_armed = 0;
-            if (rhs_takes_soc(c) && c->zf_alt) {      // ... and its cone projection, into the alternate buffers (a dropped launch leaves the state as it is)
+            if (rhs_writes_modes(c) && c->zf_alt) {      // ... and its cone projection, into the alternate buffers (a dropped launch leaves the state as it is)
                 Dev keep = c->d;
                 c->d.zf = c->zf_alt;
                 c->d.ze = c->ze_alt;
@@ -693,8 +693,8 @@ int kkt_sums(Ctx *c, uint32_t mask, double *sums) {
 // arrived, so that the next iteration's first launch is on the stream before the host has even returned to its own (identical) decision.
 int penalty_decision_ahead(Ctx *c, uint32_t mask, const double *sums) {
     const dots_penalty_policy &pp = c->penalty_policy;
-    if ((mask & 15u) != 15u || c->d.slab || c->step_palm || !c->lazy_div || !c->zf_alt || c->rhs_ahead || c->carry_valid || !rhs_takes_soc(c) ||
-        !rhs_divides(c) || c->pending_div != 0.0 || !carry_possible(c))      // (carry_possible: dots_adjust_penalty will leave the division pending)
+    if ((mask & 15u) != 15u || c->d.slab || c->step_palm || !c->lazy_div || !c->zf_alt || c->rhs_ahead || c->carry_valid || !rhs_divides(c) ||
+        c->pending_div != 0.0 || !carry_possible(c))      // (carry_possible: dots_adjust_penalty will leave the division pending)
         return 0;
     double o[2 * DOTS_N_KKT];
     int rc = kkt_combine(c, 15u, sums, o);

@@ -17,7 +17,7 @@
 // vector and otherwise reads only its own entries of bt and r: z may overwrite bt in place.
 // On the finest level post also emits the r.z partial sums that the next PCG kernel re-reduces.
 //
-// The coarse tail.  The smallest levels (at most Ctx::mg_tail_rows rows, default 256) are pure launch
+// The coarse tail.  The smallest levels (at most MG_TAIL_ROWS = 256 rows) are pure launch
 // latency.  The time-mode columns are independent of each other, so ONE kernel (k_mg_tail) walks those
 // levels -- down, restrict, ..., dense coarsest solve, ..., post -- with one workgroup per column and
 // workgroup barriers between the phases.  Measured on MI355X (us per V-cycle, sphere10k / torus100k):
@@ -28,6 +28,8 @@
 #include "dots_dev.h"
 
 namespace dots {
+
+constexpr int MG_TAIL_ROWS = 256;      // levels with at most this many rows run inside the single tail launch
 
 constexpr int MG_NB = 256;
 constexpr int MG_TAIL_NB = 1024;
@@ -293,7 +295,7 @@ int mg_vcycle(Ctx *c, const double *r, double *z, double *t0, double *rz_part, i
     // first level of the tail: the first level >= 1 with few enough rows (always at least the coarsest)
     int first_tail = nl - 1;
     for (int l = 1; l < nl; ++l)
-        if (m.lv[l].n <= c->mg_tail_rows && nl - l <= 8) { first_tail = l; break; }
+        if (m.lv[l].n <= MG_TAIL_ROWS && nl - l <= 8) { first_tail = l; break; }
     // down sweep above the tail
     for (int l = 0; l < first_tail; ++l) {
         const MgLevelDev &L = m.lv[l];

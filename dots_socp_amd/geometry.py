@@ -19,8 +19,6 @@ import numpy as np
 import scipy.sparse as sp
 from scipy.sparse.csgraph import reverse_cuthill_mckee
 
-from ._lib import env_choice
-
 
 @dataclass
 class DevicePlan:
@@ -44,7 +42,6 @@ class DevicePlan:
     time_eigs: np.ndarray     # (T+1,) sigma_a >= 0
     area_mesh: float
     vertices: np.ndarray | None = None    # (V,3) device numbering (used by the nested dissection of frontal.py)
-    patch_order: np.ndarray | None = None  # (V,) int32: device vertices as compact patches (geometry.patch_order)
     dissection: object | None = None      # frontal.Dissection in device numbering when reorder == "nd"
 
 
@@ -177,26 +174,6 @@ def dissection_order(K, vertices, triangles, leaf=16, pitch=32):
     return perm_v, perm_f, diss
 
 
-def patch_order(vertices, unit=16):
-    """A sequence of all vertices in which every aligned run of ``unit * 2^k`` entries is a compact patch of the surface:
-    recursive coordinate bisection (longest side of the bounding box, cut at a multiple of ``unit``), leaves of <= ``unit``
-    vertices, siblings next to each other (host code of the library: ``dots_patch_order``).  The element-wise kernels that walk
-    the corner lists of a tile of vertices (right-hand side, cone projection) take their tiles from this sequence instead of
-    from the numbering: the triangles of a compact patch are shared by its own vertices (~1.6 distinct triangle fetches per
-    triangle and 16-vertex tile instead of ~2.0 for 16 consecutive vertices of the sweep order, whose separators are
-    lines), while the rows of a vertex are contiguous in memory whatever the order the vertices are visited in."""
-    import ctypes as C
-
-    from . import _lib
-
-    v = np.ascontiguousarray(vertices, dtype=np.float64)
-    out = np.empty(v.shape[0], dtype=np.int32)
-    lib = _lib.load(host_only=True)
-    _lib.check(lib.dots_patch_order(v.shape[0], v.ctypes.data_as(C.POINTER(C.c_double)), int(unit), out.ctypes.data_as(C.POINTER(C.c_int32))),
-               "dots_patch_order")
-    return out
-
-
 def assemble_reference(vertices, triangles):
     """The same six results from the numpy reference functions of this module (no library needed: host-only tools and tests)."""
     V = vertices.shape[0]
@@ -265,5 +242,4 @@ def build_plan(n_time, geometry, reorder=True, nd_leaf=16, native=True) -> Devic
         perm_vert=None if perm_v is None else c(perm_v.astype(np.int32)),
         perm_tri=None if perm_f is None else c(perm_f.astype(np.int32)),
         time_modes=c(Q), time_eigs=c(sigma), area_mesh=float(area.sum()), vertices=c(vertices), dissection=diss,
-        patch_order=c(patch_order(vertices)) if env_choice("DOTS_RHS_TILES", ("0", "1", "2"), "0") != "0" else None,
     )

@@ -39,7 +39,6 @@ PRIMAL = ("phi", "A", "B", "lambda_c")
 Z_VARS = ("z_fst", "z_mid", "z_end")
 DUAL_QE = ("mu", "E")
 BETAS = ("beta_fst", "beta_mid", "beta_end")
-CARRY_MIN_NODES = 0       # space-time nodes from which quiet iterations carry the next iteration's gathers (DOTS_CARRY_MIN)
 DEFAULT_CG_TOL = 1e-8     # parity study: profiles/studies/cg_tol_parity.txt (cost within 1e-9 of the reference, budget 1e-6)
 
 
@@ -93,11 +92,9 @@ class AlmSolver:
                               and not is_constant_scaling and ahead != "0" and not self.batched)
         self._rhs_ahead = False
         self._carry = False             # DOTS_STEP_CARRY for the next device step (iterate())
-        # ... which pays where the iteration is bandwidth-bound: below DOTS_CARRY_MIN space-time nodes (V (T + 1)) the launches are
-        # latency-bound and the bytes saved in the right-hand side / projection only balance what the exchange through LDS costs
-        # steps 2+3 (A/B of the round: DESIGN.md section 5)
-        nodes = int(np.asarray(geometry["vertices"]).shape[0]) * (int(n_time) + 1)
-        self._carry_ok = direct and not self.is_palm and nodes >= int(env_choice("DOTS_CARRY_MIN", None, str(CARRY_MIN_NODES), integer=(0, 1 << 40)))
+        # (on at every size: where the launches are latency-bound the bytes saved in the right-hand side / projection only balance
+        # what the exchange through LDS costs steps 2+3)
+        self._carry_ok = direct and not self.is_palm
         self._fused_kkt = False         # the last device step formed the KKT sums it holds in registers (DOTS_STEP_KKT_SUMS)
         if direct and reorder is True:
             reorder = "nd"      # the elimination order of the factor doubles as the locality numbering

@@ -111,11 +111,7 @@ typedef struct dots_problem_desc {
     int32_t slab_count;
     int32_t slab_stride;
     int32_t reserved;
-    /* Optional (NULL: off): a sequence of all device vertices in which every aligned run of 16 * 2^k entries is a compact
-     * patch of the surface (dots_patch_order).  The right-hand-side / cone-projection launch then takes its vertex tiles
-     * from this sequence and stages the B, E rows of a tile's distinct triangles through LDS once, instead of gathering
-     * them per corner (solver_socp.py:909-921, :997-1017: the two SpMVs with incidence matrices).  Results do not change. */
-    const int32_t *patch_order;  /* [V] */
+    const int32_t *patch_order;  /* ignored (kept for the layout of ABI version 7; pass NULL) */
 } dots_problem_desc;
 
 /* Scalars the host control logic owns (solver_socp.py:97,318-321 and the kwargs of :25-41). */

@@ -397,6 +397,42 @@ def test_environment_switches_are_validated(monkeypatch):
         frontal.plan_bands(None, None, None, 32) if False else _lib.env_choice("DOTS_FRONT_TOPINV", ("auto", "0", "1"), "auto")
 
 
+ENV_READ = re.compile(r"""(?:env_int|getenv|env_choice|os\.environ\.get)\(\s*"(DOTS_[A-Z0-9_]+)"|os\.environ\["(DOTS_[A-Z0-9_]+)"\]""")
+
+
+def test_known_switches_are_the_ones_the_code_reads_and_the_ones_documented():
+    """_lib.KNOWN_ENV is exactly the set of DOTS_* switches the package (Python and native code) and bench.py read, and every
+    one of them has exactly one row in INTEGRATION.md's switch table."""
+    import glob
+
+    from dots_socp_amd import _lib
+
+    pkg = os.path.join(ROOT, "dots_socp_amd")
+    files = glob.glob(os.path.join(pkg, "**", "*.py"), recursive=True) + glob.glob(os.path.join(pkg, "csrc", "*"))
+    files = [f for f in files if os.path.splitext(f)[1] in (".py", ".hip", ".h")] + [os.path.join(ROOT, "bench.py")]
+    read = set()
+    for f in files:
+        with open(f) as fh:
+            read |= {a or b for a, b in ENV_READ.findall(fh.read())}
+    assert read == _lib.KNOWN_ENV
+    text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    table = text[text.index("| variable | default |"):]
+    rows = [line for line in table.splitlines() if line.startswith("| `DOTS_")]
+    for name in _lib.KNOWN_ENV:
+        assert sum(line.startswith(f"| `{name}`") for line in rows) == 1, name
+    assert len(rows) == len(_lib.KNOWN_ENV)
+
+
+@pytest.mark.parametrize("name, value", [("DOTS_RHS_TILES", "0"), ("DOTS_QL_TWO", "1"), ("DOTS_CARRY", "1"), ("DOTS_CARRY_MIN", "0")])
+def test_retired_switches_are_refused(monkeypatch, name, value):
+    """A retired A/B switch is an unknown name: a script that still sets it fails instead of quietly measuring the default."""
+    from dots_socp_amd import _lib
+
+    monkeypatch.setenv(name, value)
+    with pytest.raises(_lib.HipLibraryError, match=name):
+        _lib.check_environment()
+
+
 def test_plan_from_the_numpy_reference_functions_equals_the_native_one():
     """geometry.build_plan(native=False) (what host-only tools and the fake device of the gloo tests use: no library needed)
     gives the arrays of the library's dots_assemble."""
