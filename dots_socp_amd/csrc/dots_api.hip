@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 
 struct dots_ctx : dots::Ctx {};
@@ -99,8 +100,10 @@ static int build(Ctx *c, const dots_problem_desc *p) {
     int tpg = 8, shg = 3;                     // global pitch: power of two >= T + 1
     while (tpg < d.T + 1) { tpg <<= 1; ++shg; }
     if (tpg > TILE_ELEMS) { set_error("n_time too large: T+1 must be <= 1024"); return DOTS_ERR_ARGUMENT; }
-    if (p->lap_solver == DOTS_LAP_MODAL_PCG && tpg > BLOCK) { set_error("modal solver needs T+1 <= 256"); return DOTS_ERR_ARGUMENT; }
     const bool sharded = p->slab_count > 0 || p->slab_stride > 0;
+    // the modal context takes T + 1 <= 1024 on one GPU; above 256 only the direct solver steps it (modal_needs_factor), and time
+    // slabs keep T + 1 <= 256 (their scalar and halo layouts)
+    if (p->lap_solver == DOTS_LAP_MODAL_PCG && sharded && tpg > BLOCK) { set_error("time slabs need T + 1 <= 256"); return DOTS_ERR_ARGUMENT; }
     d.t0 = 0; d.nl = d.T + 1; d.ni = d.T; d.slab = 0;
     int tp = tpg, sh = shg;
     if (sharded) {
@@ -310,6 +313,14 @@ static int flush_division(Ctx *c) {
     const double f = c->pending_div;
     c->pending_div = 0.0;
     return launch_adjust_penalty(c, f);
+}
+
+// The modal PCG keeps per-mode scalars for NC <= CgScalOffsets::NCMAX = 256 modes: a modal context of T + 1 > 256 steps with the
+// direct solver only (a factor installed or shared, and enabled).
+static int modal_needs_factor(const Ctx *c, const char *what) {
+    if (c->lap_solver != DOTS_LAP_MODAL_PCG || c->dcg.cg_ncol <= CgScalOffsets::NCMAX || (c->use_front && c->front.n_nodes > 0)) return 0;
+    set_error(std::string(what) + ": T + 1 > 256 needs the direct solver (dots_front_setup); the modal PCG takes T + 1 <= 256");
+    return DOTS_ERR_STATE;
 }
 
 // `keeps_division`: the entry point neither reads nor writes the dual arrays (or, dots_step, applies a pending division itself).
@@ -791,6 +802,7 @@ int dots_step(dots_ctx *c, int n_iters, dots_step_stats *stats) {
     c->batched = 0;
     if (n_iters < 0) { set_error("n_iters < 0"); return DOTS_ERR_ARGUMENT; }
     if (c->shard_stride != 0) { set_error("dots_step on a time slab: use dots_slab_stage"); return DOTS_ERR_STATE; }
+    if ((rc = modal_needs_factor(c, "dots_step"))) return rc;
     dots_step_stats local;
     memset(&local, 0, sizeof local);
     for (int i = 0; i < n_iters; ++i)
@@ -880,6 +892,7 @@ int dots_run_phase(dots_ctx *c, int phase, dots_step_stats *stats) {
     if ((rc = materialise_zmid(c))) return rc;
     switch (phase) {
         case DOTS_PHASE_LAPLACIAN:
+            if ((rc = modal_needs_factor(c, "run_phase(LAPLACIAN)"))) return rc;
             if ((rc = launch_rhs(c))) return rc;
             if ((rc = cg_solve(c, &local))) return rc;
             break;
@@ -1058,6 +1071,7 @@ int dots_mg_setup(dots_ctx *c, const dots_mg_desc *m) {
     if (rc) return rc;
     if (!m || m->n_levels < 2 || m->n_levels > 10 || !m->levels || !m->coarse_inverse) { set_error("mg_setup: bad description"); return DOTS_ERR_ARGUMENT; }
     if (c->lap_solver != DOTS_LAP_MODAL_PCG) { set_error("multigrid needs the modal solver"); return DOTS_ERR_ARGUMENT; }
+    if (c->dcg.cg_ncol > CgScalOffsets::NCMAX) { set_error("mg_setup: the modal PCG takes T + 1 <= 256; above, use the direct solver (dots_front_setup)"); return DOTS_ERR_STATE; }
     if (m->levels[0].n != c->d.V || m->n_cols != c->dcg.cg_ncol) { set_error("mg_setup: level 0 / mode count mismatch"); return DOTS_ERR_ARGUMENT; }
     DOTS_HIP(hipStreamSynchronize(c->stream));
     if (c->cg_graph) { (void)hipGraphExecDestroy(c->cg_graph); c->cg_graph = nullptr; }

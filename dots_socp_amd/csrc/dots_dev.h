@@ -453,6 +453,8 @@ inline int front_upload(Ctx *c, const T **out, const T *host, int64_t count) {
 // T + 1 >= 64: the transforms are [V x (T+1)] x [(T+1) x (T+1)] fp64 GEMMs worth the matrix cores (k_time_modes_mfma)
 inline bool time_modes_mfma_ok(const Dev &d) { return d.TP >= 64 && d.TP <= 256 && d.Qpad != nullptr; }
 inline bool time_modes_tile_ok(const Dev &d) { return d.TP <= BLOCK && d.VT >= 1; }
+// T + 1 in (256, 1024] (pitch 512 / 1024, one GPU, direct solver): k_time_modes_wide, Q staged in LDS one k-slice at a time
+inline bool time_modes_wide_ok(const Dev &d) { return (d.TP == 512 || d.TP == 1024) && d.Qpad != nullptr && d.QpadT != nullptr; }
 inline int time_modes_chunk(const Dev &d) { return (4096 / d.TP) < (d.T + 1) ? (4096 / d.TP) : (d.T + 1); }    // rows of Q per chunk
 inline size_t time_modes_tile_lds(const Dev &d) { return sizeof(double) * ((size_t)time_modes_chunk(d) * d.TP + (size_t)d.VT * (d.TP + 1)); }
 // direct solver on one GPU, T + 1 < 64: the inverse time transform of phi rides in the cone-projection launch (the

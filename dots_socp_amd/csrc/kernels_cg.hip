@@ -457,6 +457,71 @@ __global__ __launch_bounds__(BLOCK) void k_time_modes_mfma(Dev d, const double *
     modes_from_tile_mfma<BLOCK / 64>(d, Qe, xs_m, v0, y);
 }
 
+// The transform at pitch 512 / 1024 (T + 1 in (256, 1024]): Q of 2 / 8 MB does not fit in LDS, nor does a tile of rows with
+// all their columns beside it.  A workgroup of TPC threads owns TM_ROWS = 32 vertices and ALL their TPC outputs; wavefront w
+// owns the columns [64 w, 64 w + 64): 2 row tiles x 4 column tiles of 16 x 16, 8 accumulators of v_mfma_f64_16x16x4_f64
+// (operand layout of modes_from_tile_mfma).  The k axis runs in slices of KS: per slice the workgroup stages KS rows of the
+// zero-padded Qe and the KS columns of its 32 rows (zero past T + 1) in LDS (36 KB), then every wavefront multiplies.  Each Qe entry
+// staged serves 32 vertices; x is read once.  Fixed order of the k steps: deterministic.
+template <int TPC>
+__global__ __launch_bounds__(TPC) void k_time_modes_wide(Dev d, const double *__restrict__ Qe, const double *__restrict__ x, double *__restrict__ y) {
+    constexpr int KS = 4096 / TPC;              // rows of Qe per slice: 32 KB of LDS (with x: < 64 KB, no opt-in needed)
+    constexpr int QLD = TPC + 16;               // (16 doubles of padding: the four k rows an instruction reads sit in different banks)
+    constexpr int XLD = KS + 1;
+    extern __shared__ double tw_lds[];
+    double *Qs = tw_lds;                        // [KS][QLD]
+    double *xs = tw_lds + KS * QLD;             // [TM_ROWS][XLD]
+    const int n = d.T + 1, tid = threadIdx.x;
+    const int lane = tid & 63, w = tid >> 6, li = lane & 15, lk = lane >> 4;
+    const int v0 = blockIdx.x * TM_ROWS;
+    mfma_f64x4 acc[2][4];
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = mfma_f64x4{0.0, 0.0, 0.0, 0.0};
+    for (int k0 = 0; k0 < n; k0 += KS) {
+        if (k0 > 0) __syncthreads();            // every wavefront is done with the slice before
+#pragma unroll
+        for (int i = 0; i < KS; ++i) Qs[i * QLD + tid] = Qe[(int64_t)(k0 + i) * TPC + tid];      // rows past T + 1 are zero
+        for (int e = tid; e < TM_ROWS * KS; e += TPC) {
+            const int vl = e / KS, kk = e % KS, v = v0 + vl;
+            xs[vl * XLD + kk] = (v < d.V && k0 + kk < n) ? x[idxV(d, v, k0 + kk)] : 0.0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < KS; kk += 4) {
+            const double a0 = xs[li * XLD + kk + lk], a1 = xs[(16 + li) * XLD + kk + lk];
+            const double *bq = Qs + (kk + lk) * QLD + w * 64 + li;
+#pragma unroll
+            for (int ct = 0; ct < 4; ++ct) {
+                const double b = bq[ct * 16];
+                acc[0][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b, acc[0][ct], 0, 0, 0);
+                acc[1][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b, acc[1][ct], 0, 0, 0);
+            }
+        }
+    }
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) {
+        const int j = w * 64 + ct * 16 + li;
+        if (j >= n) continue;
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int v = v0 + rt * 16 + lk + 4 * r;
+                if (v < d.V) y[idxV(d, v, j)] = acc[rt][ct][r];
+            }
+    }
+}
+template <int TPC>
+static size_t time_modes_wide_lds() { return sizeof(double) * ((size_t)(4096 / TPC) * (TPC + 16) + (size_t)TM_ROWS * (4096 / TPC + 1)); }
+static void launch_time_modes_wide(Ctx *c, const double *Qe, const double *x, double *y) {
+    const Dev &d = c->d;
+    const dim3 grid((d.V + TM_ROWS - 1) / TM_ROWS);
+    if (d.TP == 512) hipLaunchKernelGGL(k_time_modes_wide<512>, grid, dim3(512), time_modes_wide_lds<512>(), c->stream, d, Qe, x, y);
+    else hipLaunchKernelGGL(k_time_modes_wide<1024>, grid, dim3(1024), time_modes_wide_lds<1024>(), c->stream, d, Qe, x, y);
+}
+
 // ------------------------------------------------------------------------------------------
 // host driver
 // ------------------------------------------------------------------------------------------
@@ -723,7 +788,9 @@ __global__ __launch_bounds__(BLOCK) void k_time_modes_inv_gathered_tile(Dev dt, 
 void modes_forward(Ctx *c, const double *in, double *out, bool direct) {
     const Dev &d = c->d;
     const int gt = xcd_grid(d.n_vtiles);
-    if (direct && time_modes_tile_ok(d))
+    if (direct && time_modes_wide_ok(d))
+        launch_time_modes_wide(c, d.Qpad, in, out);
+    else if (direct && time_modes_tile_ok(d))
         hipLaunchKernelGGL((k_time_modes_tile<true>), dim3(gt), dim3(BLOCK), time_modes_tile_lds(d), c->stream, d, in, out, time_modes_chunk(d));
     else
         hipLaunchKernelGGL((k_time_modes<true>), dim3(gt), dim3(BLOCK), 0, c->stream, d, in, out, 1);
@@ -731,7 +798,9 @@ void modes_forward(Ctx *c, const double *in, double *out, bool direct) {
 void modes_inverse(Ctx *c, const double *x, double *phi, bool direct) {
     const Dev &d = c->d;
     const int gt = xcd_grid(d.n_vtiles);
-    if (time_modes_mfma_ok(d))
+    if (direct && time_modes_wide_ok(d))
+        launch_time_modes_wide(c, d.QpadT, x, phi);
+    else if (time_modes_mfma_ok(d))
         hipLaunchKernelGGL(k_time_modes_mfma, dim3((d.V + TM_ROWS - 1) / TM_ROWS), dim3(BLOCK), sizeof(double) * TM_ROWS * (d.TP + 1), c->stream, d, d.QpadT,
                            x, phi);
     else if (time_modes_tile_ok(d) && direct && d.n_vtiles <= 512)      // small meshes, behind the sweeps: latency-bound, one output per thread (knot: 9.5 -> 6 us; no gain at 10^5 vertices)
@@ -756,6 +825,10 @@ static int cg_solve_impl(Ctx *c, dots_step_stats *stats, bool defer_inverse) {
     const bool owns_mode0 = !sharded || c->shard_begin == 0;
     if (MODAL && g.cg_ncol == 0) return 0;   // a rank without modes has nothing to solve
     const bool direct = MODAL && c->use_front && c->front.n_nodes > 0;   // no warm start, no mean removal needed
+    if (MODAL && !direct && g.cg_ncol > S::NCMAX) {      // (the entry points refuse first: modal_needs_factor) nothing is launched
+        set_error("laplacian solve: T + 1 > 256 needs the direct solver (dots_front_setup); the modal PCG takes T + 1 <= 256");
+        return DOTS_ERR_STATE;
+    }
     if (sharded) {
         // time-slab context: the right-hand side of ALL nodes was all-gathered into slab.b_recv; this rank transforms the
         // modes it solves.  The PCG warm start is its own mode-space solution of the previous iteration (g.cg_x).
@@ -855,6 +928,10 @@ int cg_bench(Ctx *c, int which, int reps, double *ms, double *bytes) {
         *bytes = c->front_bytes_unmerged + 8.0 * (double)d.V * d.cg_ncol * 4.0;   // factor twice (one block per tree node: merged bands read more, dots_front_info); b read, y written + read, x written
         return 0;
     }
+    if (modal && d.cg_ncol > S::NCMAX) {      // the PCG's scalar block and flags hold NCMAX modes (T + 1 > 256: the direct solver only)
+        set_error("bench: the PCG kernels take T + 1 <= 256 modes; above, only the direct solve (which = 3) runs");
+        return DOTS_ERR_STATE;
+    }
     if (which == 2 && !a.mg) {
         set_error("bench: no multigrid hierarchy on this context");
         return DOTS_ERR_STATE;
@@ -922,7 +999,8 @@ int cg_bench(Ctx *c, int which, int reps, double *ms, double *bytes) {
 void preload_transform_kernels() {      // (see preload_alm_kernels)
     const void *fns[] = {(const void *)k_time_modes_tile<true, BLOCK>, (const void *)k_time_modes_tile<false, BLOCK>,
                          (const void *)k_time_modes_tile<false, 1024>, (const void *)k_time_modes_mfma,
-                         (const void *)k_time_modes<true>, (const void *)k_time_modes<false>};
+                         (const void *)k_time_modes<true>, (const void *)k_time_modes<false>,
+                         (const void *)k_time_modes_wide<512>, (const void *)k_time_modes_wide<1024>};
     hipFuncAttributes a;
     for (const void *f : fns) (void)hipFuncGetAttributes(&a, f);
     (void)hipGetLastError();

@@ -3,6 +3,9 @@
 // utils/laplacian_inverse_socp.py:40-44).  One elimination tree for all time modes; every kernel handles all
 // modes at once with the mode index fastest, so the work of the T+1 factorisations is one batched pass.
 //
+// Pitches above 256 (T + 1 <= 1024): a workgroup still holds at most 256 modes; the mode axis is cut into chunks of 256
+// (blockIdx.z), the layout [entry][TP] unchanged.  The modes are independent problems: every chunk does exactly what the
+// whole row would.
 // Per tree height (leaves first), all nodes of the height in each launch:
 //   assemble   C_p = A[front_p, sep_p] (entries of K + shift * mass, looked up in the CSR) + the children's
 //              Schur complements, S_p = the children's Schur complements on bd_p x bd_p        (pull form)
@@ -21,7 +24,9 @@
 namespace dots {
 
 struct FactArgs {
-    int sh, TP, ncol;
+    int sh, TP, ncol;           // row stride of the mode axis (log2, value) and live modes
+    int wsh;                    // log2 of the modes of one workgroup row: min(sh, 8); a pitch above 256 is cut into chunks of 256
+                                // modes (blockIdx.z), each its own workgroups, the row stride staying TP
     const double *sigma;        // shifts of the context's modes (without eps)
     double eps;
     const int *grounded;        // [TP] 1: the mode's operator is singular, its last root pivot is grounded
@@ -40,8 +45,8 @@ __device__ __forceinline__ int front_vertex(const FrontDev &f, const FrontNode &
 // ---- assemble -------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_fact_assemble(FactArgs g, FrontDev f) {
     const FrontNode nd = f.nodes[g.level_nodes[blockIdx.y]];
-    const int sh = g.sh, tid = threadIdx.x;
-    const int a = tid & (g.TP - 1), q = tid >> sh, Q = 256 >> sh;
+    const int sh = g.sh, wsh = g.wsh, tid = threadIdx.x;
+    const int a = (tid & ((1 << wsh) - 1)) + (blockIdx.z << wsh), q = tid >> wsh, Q = 256 >> wsh;
     if (a >= g.ncol) return;
     const int n = nd.n, b = nd.b, m = n + b;
     const int64_t nC = (int64_t)m * n, total = nC + (int64_t)b * b;
@@ -79,18 +84,18 @@ __global__ __launch_bounds__(256) void k_fact_assemble(FactArgs g, FrontDev f) {
 // Two launches, so that no workgroup can read a diagonal block another one is overwriting.
 template <bool FACTOR>
 __global__ __launch_bounds__(256) void k_fact_panel(FactArgs g, FrontDev f, int k0, int w, int rows_per_wg) {
-    extern __shared__ double D[];      // [w][w][TP]
+    extern __shared__ double D[];      // [w][w][modes of the workgroup]
     const FrontNode nd = f.nodes[g.level_nodes[blockIdx.y]];
     const int n = nd.n, m = n + nd.b;
     if (k0 >= n) return;
     const int we = min(w, n - k0);
     const int first = k0 + we + blockIdx.x * rows_per_wg;     // first row of this workgroup below the diagonal block
     if (!FACTOR && first >= m) return;
-    const int sh = g.sh, tid = threadIdx.x;
-    const int a = tid & (g.TP - 1), q = tid >> sh, Q = 256 >> sh;
+    const int sh = g.sh, wsh = g.wsh, tid = threadIdx.x;
+    const int al = tid & ((1 << wsh) - 1), a = al + (blockIdx.z << wsh), q = tid >> wsh, Q = 256 >> wsh;
     const bool live = a < g.ncol;
     double *__restrict__ Cp = g.C + (nd.foff << sh) + a;
-    auto Dd = [&](int i, int j) -> double & { return D[((i * w + j) << sh) + a]; };
+    auto Dd = [&](int i, int j) -> double & { return D[((i * w + j) << wsh) + al]; };
     if (live)
         for (int e = q; e < we * we; e += Q) {
             const int i = e / we, j = e % we;
@@ -156,13 +161,13 @@ __global__ __launch_bounds__(256) void k_fact_update(FactArgs g, FrontDev f, int
     if (j0 + 16 <= jlo) return;
     if (j0 < n) { if (i0 + 16 <= j0) return; }  // strictly above the diagonal of the L part
     else if (i0 + 16 <= n) return;              // S columns only take S rows
-    const int sh = g.sh, tid = threadIdx.x;
-    const int a = tid & (g.TP - 1);
+    const int sh = g.sh, wsh = g.wsh, tid = threadIdx.x;
+    const int a = (tid & ((1 << wsh) - 1)) + (blockIdx.z << wsh);
     if (a >= g.ncol) return;
-    const int Q = 256 >> sh;                    // threads per mode
+    const int Q = 256 >> wsh;                   // threads per mode
     const double *__restrict__ Cp = g.C + (nd.foff << sh) + a;
     // sub-tiles of 4 rows x 8 columns: 8 per tile, dealt to the mode's threads
-    for (int st = tid >> sh; st < 8; st += Q) {
+    for (int st = tid >> wsh; st < 8; st += Q) {
         const int ib = i0 + (st >> 1) * 4, jb = j0 + (st & 1) * 8;
         double acc[4][8];
 #pragma unroll
@@ -204,9 +209,9 @@ __global__ __launch_bounds__(256) void k_fact_update(FactArgs g, FrontDev f, int
 __global__ __launch_bounds__(256) void k_fact_linv(FactArgs g, FrontDev f) {
     const FrontNode nd = f.nodes[g.level_nodes[blockIdx.y]];
     const int n = nd.n;
-    const int sh = g.sh, tid = threadIdx.x;
-    const int a = tid & (g.TP - 1), Q = 256 >> sh;
-    const int j = blockIdx.x * Q + (tid >> sh);
+    const int sh = g.sh, wsh = g.wsh, tid = threadIdx.x;
+    const int a = (tid & ((1 << wsh) - 1)) + (blockIdx.z << wsh), Q = 256 >> wsh;
+    const int j = blockIdx.x * Q + (tid >> wsh);
     if (j >= n || a >= g.ncol) return;
     const double *__restrict__ L = g.C + (nd.foff << sh) + a;
     double *__restrict__ X = g.T + (nd.foff << sh) + a;
@@ -231,8 +236,8 @@ __global__ __launch_bounds__(256) void k_fact_linv(FactArgs g, FrontDev f) {
 __global__ __launch_bounds__(256) void k_fact_gmat(FactArgs g, FrontDev f) {
     const FrontNode nd = f.nodes[g.level_nodes[blockIdx.y]];
     const int n = nd.n, b = nd.b;
-    const int sh = g.sh, tid = threadIdx.x;
-    const int a = tid & (g.TP - 1), q = tid >> sh, Q = 256 >> sh;
+    const int sh = g.sh, wsh = g.wsh, tid = threadIdx.x;
+    const int a = (tid & ((1 << wsh) - 1)) + (blockIdx.z << wsh), q = tid >> wsh, Q = 256 >> wsh;
     if (a >= g.ncol) return;
     const double *__restrict__ L = g.C + (nd.foff << sh) + a;
     double *__restrict__ X = g.T + (nd.foff << sh) + a;
@@ -281,15 +286,18 @@ int front_factorize(Ctx *c, const dots_front_desc *h, FrontDev &f, const std::ve
     }
     FactArgs g{};
     g.sh = sh; g.TP = d.TP; g.ncol = d.cg_ncol;
+    g.wsh = std::min(sh, 8);
+    const unsigned nch = 1u << (sh - g.wsh);      // chunks of 256 modes (1 up to a pitch of 256)
+    const int WP = 1 << g.wsh;
     g.sigma = d.sigma; g.eps = c->prm.eps; g.grounded = (const int *)gr;
     g.rowptr = d.rowptr; g.col = d.col; g.val = d.val; g.mass = d.mass_v;
     g.pull0 = (const int *)p0; g.pull1 = (const int *)p1;
     g.C = (double *)C; g.T = T; g.S = (double *)S;
     g.bad_pivot = (int *)bp;
-    // panel width: the diagonal block of all modes must fit in LDS (w * w * TP doubles <= 64 KB)
+    // panel width: the diagonal block of the workgroup's modes must fit in LDS (w * w * WP doubles <= 64 KB)
     int w = 16;
-    while ((size_t)w * w * d.TP * sizeof(double) > 65536 && w > 1) w /= 2;
-    const int Q = 256 >> sh;
+    while ((size_t)w * w * WP * sizeof(double) > 65536 && w > 1) w /= 2;
+    const int Q = 256 >> g.wsh;
     for (int l = 0; l < h->n_levels && !rc; ++l) {
         const int cnt = h->level_ptr[l + 1] - h->level_ptr[l];
         if (cnt <= 0) continue;
@@ -304,19 +312,19 @@ int front_factorize(Ctx *c, const dots_front_desc *h, FrontDev &f, const std::ve
         }
         g.level_nodes = (const int *)ln + h->level_ptr[l];
         auto blocks = [&](int64_t items) { return (unsigned)std::min<int64_t>(std::max<int64_t>((items + Q - 1) / Q, 1), 4096); };
-        hipLaunchKernelGGL(k_fact_assemble, dim3(blocks(max_e), cnt), dim3(256), 0, c->stream, g, f);
+        hipLaunchKernelGGL(k_fact_assemble, dim3(blocks(max_e), cnt, nch), dim3(256), 0, c->stream, g, f);
         const int rows_per_wg = 8 * Q;
         const int tiles = (max_m + 15) / 16;
         for (int k0 = 0; k0 < max_n; k0 += w) {
             const int below = std::max(max_m - (k0 + 1), 0);
-            const size_t lds = sizeof(double) * (size_t)w * w * d.TP;
-            hipLaunchKernelGGL((k_fact_panel<true>), dim3(1, cnt), dim3(256), lds, c->stream, g, f, k0, w, rows_per_wg);
+            const size_t lds = sizeof(double) * (size_t)w * w * WP;
+            hipLaunchKernelGGL((k_fact_panel<true>), dim3(1, cnt, nch), dim3(256), lds, c->stream, g, f, k0, w, rows_per_wg);
             if (below > 0)
-                hipLaunchKernelGGL((k_fact_panel<false>), dim3((below + rows_per_wg - 1) / rows_per_wg, cnt), dim3(256), lds, c->stream, g, f, k0, w, rows_per_wg);
-            hipLaunchKernelGGL(k_fact_update, dim3(tiles * tiles, cnt), dim3(256), 0, c->stream, g, f, k0, w, tiles);
+                hipLaunchKernelGGL((k_fact_panel<false>), dim3((below + rows_per_wg - 1) / rows_per_wg, cnt, nch), dim3(256), lds, c->stream, g, f, k0, w, rows_per_wg);
+            hipLaunchKernelGGL(k_fact_update, dim3(tiles * tiles, cnt, nch), dim3(256), 0, c->stream, g, f, k0, w, tiles);
         }
-        if (max_n > 0) hipLaunchKernelGGL(k_fact_linv, dim3((max_n + Q - 1) / Q, cnt), dim3(256), 0, c->stream, g, f);
-        if (max_b > 0 && max_n > 0) hipLaunchKernelGGL(k_fact_gmat, dim3(blocks((int64_t)max_b * max_n), cnt), dim3(256), 0, c->stream, g, f);
+        if (max_n > 0) hipLaunchKernelGGL(k_fact_linv, dim3((max_n + Q - 1) / Q, cnt, nch), dim3(256), 0, c->stream, g, f);
+        if (max_b > 0 && max_n > 0) hipLaunchKernelGGL(k_fact_gmat, dim3(blocks((int64_t)max_b * max_n), cnt, nch), dim3(256), 0, c->stream, g, f);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) rc = hip_fail(e, "factorisation launch", __FILE__, __LINE__);
     }

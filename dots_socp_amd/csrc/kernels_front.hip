@@ -53,9 +53,18 @@
 
 namespace dots {
 
+// Pitches above 256 (T + 1 <= 1024): a workgroup row holds at most 256 modes (WP); the mode axis is cut into TP / WP chunks,
+// blockIdx.y, each with its own workgroups.  The row stride of the factor, W, y and x stays TP.  The modes are independent:
+// a chunk does what the whole row would, and at pitches up to 256 (one chunk) nothing changes.
 struct FrontArgs {
-    int sh, TP, ncol;          // mode pitch (log2, value) and live modes
+    int sh, TP, ncol;          // row stride of the mode axis (log2, value) and live modes
+    int wsh, WP;               // modes of one workgroup row (log2, value): min(TP, 256)
 };
+static inline FrontArgs front_args(const Dev &d) {
+    const int wsh = d.tp_shift < 8 ? d.tp_shift : 8;
+    return FrontArgs{d.tp_shift, d.TP, d.cg_ncol, wsh, 1 << wsh};
+}
+static inline unsigned front_chunks(const Dev &d) { return 1u << (d.tp_shift - front_args(d).wsh); }
 
 __device__ __forceinline__ int64_t front_row(const FrontDev &f, int k) { return f.vmap ? f.vmap[k] : k; }
 
@@ -151,9 +160,9 @@ __global__ __launch_bounds__(NB) void k_front_fwd(FrontArgs g, FrontDev f, const
     const SweepNode &nd = wk.nd;
     const int row0 = wk.first;
     const int sh = g.sh, tid = threadIdx.x;
-    const int shv = VEC == 2 ? sh - 1 : sh;                      // log2 of the lanes per row part
-    const int a = (tid & ((g.TP / VEC) - 1)) * VEC, q = tid >> shv, Q = NB >> shv;
-    const bool wide = (g.TP / VEC) > 64;                         // only with VEC == 1
+    const int shv = VEC == 2 ? g.wsh - 1 : g.wsh;                // log2 of the lanes per row part
+    const int al = (tid & ((g.WP / VEC) - 1)) * VEC, a = al + (blockIdx.y << g.wsh), q = tid >> shv, Q = NB >> shv;
+    const bool wide = (g.WP / VEC) > 64;                         // only with VEC == 1
     const int n = nd.n, m = n + nd.b;
     const double *__restrict__ Fp = f.F + (nd.foff << sh) + a;
     const int64_t plane = (int64_t)m << sh;
@@ -237,14 +246,14 @@ __global__ __launch_bounds__(NB) void k_front_fwd(FrontArgs g, FrontDev f, const
 #pragma unroll
         for (int r = 0; r < RB; ++r) as[r] = acc[r][s];
         if (VEC == 1 && wide) front_fold_wide<NB, RB>(reinterpret_cast<Vd<1>(&)[RB]>(as), red, tid);
-        else front_fold<NB, RB, VEC>(as, red, g.TP, a, tid);
+        else front_fold<NB, RB, VEC>(as, red, g.WP, al, tid);
         double *__restrict__ Ys = RHS_PICK(Y, y, s);
         double *__restrict__ Ws = RHS_PICK(f.W, W, s);
         const double *__restrict__ W0 = Ws + (nd.woff << sh) + a;
         for (int r = q; r < nr && live; r += Q) {
             Vd<VEC> sm;
-            if (VEC == 1 && wide) sm.v[0] = front_folded_wide<NB>(red, r, sh, a).v[0];
-            else sm = front_folded<NB, VEC>(red, r, g.TP, a);
+            if (VEC == 1 && wide) sm.v[0] = front_folded_wide<NB>(red, r, g.wsh, al).v[0];
+            else sm = front_folded<NB, VEC>(red, r, g.WP, al);
             const int i = row0 + r;
             if (i < n) {
                 vstore<VEC>(Ys + (front_row(f, nd.k0 + i) << sh) + a, sm);
@@ -278,6 +287,7 @@ __global__ __launch_bounds__(NB) void k_front_fwd(FrontArgs g, FrontDev f, const
 // log2(QW) xor-shuffles; the right-hand side w = b - (planes) of the block's columns is formed ONCE per workgroup, in LDS.
 // A block never spans two members of a merged node (FrontWork.pad = its rows), so wk.lo is the first column of ALL its rows.
 // Sums are formed per part in column order, parts folded pairwise: the order depends on QW only, not on the mode pitch.
+// Only chosen where a row of modes fits a wavefront (pitch <= 128): one chunk of modes, TP = WP.
 constexpr size_t FWD_ROWS_LDS_MAX = 40 * 1024;      // LDS a workgroup of the row kernel may take for w (4 workgroups per CU stay resident)
 constexpr double FWD_ROWS_MEAN_MAX = 30.0;          // bands whose rows are longer on average keep the fold kernel unless they read 4+ planes (DOTS_FRONT_ROWS=2: no limit)
 constexpr int FWD_ROWS_PAD = 2;      // doubles of padding per staged row of w (rows of exactly TP doubles would share their banks)
@@ -430,9 +440,9 @@ __global__ __launch_bounds__(NB) void k_front_bwd(FrontArgs g, FrontDev f, const
     const SweepNode &nd = wk.nd;
     const int col0 = wk.first;
     const int sh = g.sh, tid = threadIdx.x;
-    const int shv = VEC == 2 ? sh - 1 : sh;
-    const int a = (tid & ((g.TP / VEC) - 1)) * VEC, q = tid >> shv, Q = NB >> shv;
-    const bool wide = (g.TP / VEC) > 64;
+    const int shv = VEC == 2 ? g.wsh - 1 : g.wsh;
+    const int al = (tid & ((g.WP / VEC) - 1)) * VEC, a = al + (blockIdx.y << g.wsh), q = tid >> shv, Q = NB >> shv;
+    const bool wide = (g.WP / VEC) > 64;
     const int n = nd.n, m = n + nd.b;
     const double *__restrict__ Fp = f.F + (nd.foff << sh) + a;
     const int *__restrict__ bdv = f.bd_vertex + nd.bdoff;
@@ -521,12 +531,12 @@ __global__ __launch_bounds__(NB) void k_front_bwd(FrontArgs g, FrontDev f, const
 #pragma unroll
         for (int r = 0; r < RB; ++r) as[r] = acc[r][s];
         if (VEC == 1 && wide) front_fold_wide<NB, RB>(reinterpret_cast<Vd<1>(&)[RB]>(as), red, tid);
-        else front_fold<NB, RB, VEC>(as, red, g.TP, a, tid);
+        else front_fold<NB, RB, VEC>(as, red, g.WP, al, tid);
         double *Xs = RHS_PICK(X, x, s);
         for (int r = q; r < nc && live; r += Q) {
             Vd<VEC> sm;
-            if (VEC == 1 && wide) sm.v[0] = front_folded_wide<NB>(red, r, sh, a).v[0];
-            else sm = front_folded<NB, VEC>(red, r, g.TP, a);
+            if (VEC == 1 && wide) sm.v[0] = front_folded_wide<NB>(red, r, g.wsh, al).v[0];
+            else sm = front_folded<NB, VEC>(red, r, g.WP, al);
             vstore<VEC>(Xs + (front_row(f, nd.k0 + col0 + r) << sh) + a, sm);
         }
     }
@@ -805,6 +815,7 @@ __global__ __launch_bounds__(64) void k_leaf_tables(FrontDev f, const int *__res
 // ---- merged bands: F' of a merged node from its members' blocks (see the header comment) ---------------------
 struct MergeArgs {
     int sh, TP, ncol;
+    int wsh;                    // modes per workgroup (log2): chunks of 256 modes in blockIdx.z above a pitch of 256
     double *F;                  // original blocks, then the merged ones
     double *scratch;            // U_s of the members that are neither at the bottom nor at the top of their band
     const int *pull0, *pull1;   // front position -> row in the child's boundary, or -1
@@ -816,8 +827,8 @@ struct MergeArgs {
 // subtree in the merged node]); the members' children inside the band were handled by the launches before.
 __global__ __launch_bounds__(256) void k_merge_member(MergeArgs g) {
     const MergeMember s = g.mem[g.list[blockIdx.y]];
-    const int sh = g.sh, tid = threadIdx.x;
-    const int a = tid & (g.TP - 1), q = tid >> sh, Q = 256 >> sh;
+    const int sh = g.sh, wsh = g.wsh, tid = threadIdx.x;
+    const int a = (tid & ((1 << wsh) - 1)) + (blockIdx.z << wsh), q = tid >> wsh, Q = 256 >> wsh;
     if (a >= g.ncol) return;
     const int n = s.n, m = n + s.b, w = s.o + n - s.c0;
     const double *__restrict__ Fs = g.F + (s.foff << sh) + a;                 // entry (i, t): ((i * n + t) << sh)
@@ -858,6 +869,7 @@ __global__ __launch_bounds__(256) void k_merge_member(MergeArgs g) {
 // grid (blocks of entries, nodes); thread = (mode, entry (i, j)); L = the node's merged block, row stride n
 struct TopInvArgs {
     int sh, TP, ncol;
+    int wsh;                    // modes per workgroup (log2): chunks of 256 modes in blockIdx.z above a pitch of 256
     const double *F;
     double *out;                // S^-1 of every node of the list, one after the other
     const int64_t *foff, *ooff; // per node: its block in F, its block in out
@@ -866,8 +878,8 @@ struct TopInvArgs {
 };
 __global__ __launch_bounds__(256) void k_top_inverse(TopInvArgs g) {
     const int nd = blockIdx.y, n = g.n[nd];
-    const int sh = g.sh, tid = threadIdx.x;
-    const int a = tid & (g.TP - 1), q = tid >> sh, Q = 256 >> sh;
+    const int sh = g.sh, wsh = g.wsh, tid = threadIdx.x;
+    const int a = (tid & ((1 << wsh) - 1)) + (blockIdx.z << wsh), q = tid >> wsh, Q = 256 >> wsh;
     if (a >= g.ncol) return;
     const double *__restrict__ L = g.F + (g.foff[nd] << sh) + a;
     double *__restrict__ S = g.out + (g.ooff[nd] << sh) + a;
@@ -908,16 +920,17 @@ constexpr int FRONT_NR_1024_FWD = 2, FRONT_NR_1024 = 4;
 template <int NR>
 static void front_launch_fwd(Ctx *c, const FrontDev &f, const FrontWork *ptr, int n, int nbt, int blk, int kp, const double *bhat, double *y, const MoreRhs<NR> &mr) {
     const Dev &d = c->dcg;
-    const FrontArgs g{d.tp_shift, d.TP, d.cg_ncol};
+    const FrontArgs g = front_args(d);
+    const dim3 grid(n, front_chunks(d));
     const bool vm = f.vmap != nullptr, v2 = front_two_modes(c);
 #define FRONT_FWD4(NBV, RBV, KPV)                                                                                                  \
     do {                                                                                                                           \
         if (v2) {                                                                                                                  \
-            if (vm) hipLaunchKernelGGL((k_front_fwd<NBV, RBV, true, KPV, 2, NR>), dim3(n), dim3(NBV), 0, c->stream, g, f, ptr, blk, bhat, y, mr);  \
-            else hipLaunchKernelGGL((k_front_fwd<NBV, RBV, false, KPV, 2, NR>), dim3(n), dim3(NBV), 0, c->stream, g, f, ptr, blk, bhat, y, mr);    \
+            if (vm) hipLaunchKernelGGL((k_front_fwd<NBV, RBV, true, KPV, 2, NR>), grid, dim3(NBV), 0, c->stream, g, f, ptr, blk, bhat, y, mr);  \
+            else hipLaunchKernelGGL((k_front_fwd<NBV, RBV, false, KPV, 2, NR>), grid, dim3(NBV), 0, c->stream, g, f, ptr, blk, bhat, y, mr);    \
         } else {                                                                                                                   \
-            if (vm) hipLaunchKernelGGL((k_front_fwd<NBV, RBV, true, KPV, 1, NR>), dim3(n), dim3(NBV), 0, c->stream, g, f, ptr, blk, bhat, y, mr);  \
-            else hipLaunchKernelGGL((k_front_fwd<NBV, RBV, false, KPV, 1, NR>), dim3(n), dim3(NBV), 0, c->stream, g, f, ptr, blk, bhat, y, mr);    \
+            if (vm) hipLaunchKernelGGL((k_front_fwd<NBV, RBV, true, KPV, 1, NR>), grid, dim3(NBV), 0, c->stream, g, f, ptr, blk, bhat, y, mr);  \
+            else hipLaunchKernelGGL((k_front_fwd<NBV, RBV, false, KPV, 1, NR>), grid, dim3(NBV), 0, c->stream, g, f, ptr, blk, bhat, y, mr);    \
         }                                                                                                                          \
     } while (0)
 #define FRONT_FWD(NBV, RBV)                                                                                                        \
@@ -940,7 +953,7 @@ template <int NR>
 static void front_launch_fwd_rows(Ctx *c, const FrontDev &f, const FrontWork *ptr, int n, int qw_shift, int kp, int lds_cols, const double *bhat, double *y,
                                   const MoreRhs<NR> &mr) {
     const Dev &d = c->dcg;
-    const FrontArgs g{d.tp_shift, d.TP, d.cg_ncol};
+    const FrontArgs g = front_args(d);      // (a row of modes within a wavefront: one chunk)
     const bool vm = f.vmap != nullptr, v2 = front_two_modes(c);
     const size_t lds = NR * sizeof(double) * (size_t)std::max(lds_cols, 1) * (size_t)(d.TP + FWD_ROWS_PAD);
 #define FRONT_ROWS4(KPV)                                                                                                           \
@@ -963,16 +976,17 @@ static void front_launch_fwd_rows(Ctx *c, const FrontDev &f, const FrontWork *pt
 template <int NR>
 static void front_launch_bwd(Ctx *c, const FrontDev &f, const FrontWork *ptr, int n, int nbt, int blk, const double *y, double *x, const MoreRhs<NR> &mr) {
     const Dev &d = c->dcg;
-    const FrontArgs g{d.tp_shift, d.TP, d.cg_ncol};
+    const FrontArgs g = front_args(d);
+    const dim3 grid(n, front_chunks(d));
     const bool vm = f.vmap != nullptr, v2 = front_two_modes(c);
 #define FRONT_BWD(NBV, RBV)                                                                                                        \
     do {                                                                                                                           \
         if (v2) {                                                                                                                  \
-            if (vm) hipLaunchKernelGGL((k_front_bwd<NBV, RBV, true, 2, NR>), dim3(n), dim3(NBV), 0, c->stream, g, f, ptr, blk, y, x, mr);  \
-            else hipLaunchKernelGGL((k_front_bwd<NBV, RBV, false, 2, NR>), dim3(n), dim3(NBV), 0, c->stream, g, f, ptr, blk, y, x, mr);    \
+            if (vm) hipLaunchKernelGGL((k_front_bwd<NBV, RBV, true, 2, NR>), grid, dim3(NBV), 0, c->stream, g, f, ptr, blk, y, x, mr);  \
+            else hipLaunchKernelGGL((k_front_bwd<NBV, RBV, false, 2, NR>), grid, dim3(NBV), 0, c->stream, g, f, ptr, blk, y, x, mr);    \
         } else {                                                                                                                   \
-            if (vm) hipLaunchKernelGGL((k_front_bwd<NBV, RBV, true, 1, NR>), dim3(n), dim3(NBV), 0, c->stream, g, f, ptr, blk, y, x, mr);  \
-            else hipLaunchKernelGGL((k_front_bwd<NBV, RBV, false, 1, NR>), dim3(n), dim3(NBV), 0, c->stream, g, f, ptr, blk, y, x, mr);    \
+            if (vm) hipLaunchKernelGGL((k_front_bwd<NBV, RBV, true, 1, NR>), grid, dim3(NBV), 0, c->stream, g, f, ptr, blk, y, x, mr);  \
+            else hipLaunchKernelGGL((k_front_bwd<NBV, RBV, false, 1, NR>), grid, dim3(NBV), 0, c->stream, g, f, ptr, blk, y, x, mr);    \
         }                                                                                                                          \
     } while (0)
     if (nbt == 1024) {
@@ -1322,8 +1336,10 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
     // The leaves as explicit local inverses (k_front_leaf_fwd / _bwd): an un-merged band of leaves below at least one other band; every leaf's
     // vertices numbered as the sweeps walk them (device vertex = sweep-order index: the plan's own numbering, or any that keeps the leaves in place);
     // a row of modes within a workgroup.  DOTS_FRONT_CFG / DOTS_FRONT_TUNE choose among the BAND kernels, also for band 0: the leaves then stay with them.
+    // Above a pitch of 256 the band kernels keep the leaves (the leaf kernels take no chunks of modes; their LDS rule below would
+    // refuse all but leaves of a few vertices anyway).
     bool leaf_inv = c->front_leafinv && !getenv("DOTS_FRONT_CFG") && !c->front_tune && nb >= 2 && cuts[1] == 1 && d.rowptr && d.col && d.val &&
-                    (d.TP / (front_two_modes(c) ? 2 : 1)) <= 1024;
+                    d.TP <= 256;
     for (size_t gi = 0; gi < groups.size() && leaf_inv; ++gi) {
         const Group &G = groups[gi];
         if (G.band != 0) continue;
@@ -1455,21 +1471,22 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
             band_cols[(size_t)k] += groups[(size_t)gi].n;
         }
         const int64_t rows = band_rows[(size_t)k], cols = band_cols[(size_t)k];
-        const bool big_ok = d.TP <= 256;      // 1024-thread workgroups need a row of modes to fit
+        // (a workgroup row holds at most 256 modes, the rest of a wider pitch in chunks of their own: 1024-thread workgroups
+        // fit at every pitch, and above 256 each chunk takes the shapes of a pitch of 256)
         int fnb, frb, bnb, bcb;
-        if (top_inv && k == nb - 1 && big_ok) {      // full rows of S^-1: every workgroup reads the whole right-hand side and all planes
+        if (top_inv && k == nb - 1) {      // full rows of S^-1: every workgroup reads the whole right-hand side and all planes
             fnb = 1024;
             frb = rows >= 480 ? 4 : (rows >= 64 ? 2 : 1);
         } else if (band_planes[(size_t)k] >= 4) {
-            if (rows >= 600 || !big_ok) { fnb = 256; frb = 4; }
+            if (rows >= 600) { fnb = 256; frb = 4; }
             else { fnb = 1024; frb = rows >= 300 ? 2 : 1; }
         } else {      // (thresholds from the tables of profiles/studies/shape_tuner.txt)
-            fnb = (rows < 1024 && big_ok) ? 1024 : 256;
+            fnb = rows < 1024 ? 1024 : 256;
             frb = fnb == 1024 ? (rows >= 512 ? 2 : 1) : (rows >= 2048 ? 4 : 2);
         }
         // (two-mode lanes split a dot product over twice as many parts per workgroup: 256 threads reach further down; at a pitch of
         // 128 a 256-thread workgroup splits a dot product only 4 ways: 1024 threads up to 3000 columns)
-        if (cols >= (d.TP >= 128 ? 3000 : (two_modes ? 1024 : 1536)) || !big_ok) { bnb = 256; bcb = cols >= 4096 ? 4 : (cols >= 2048 ? 2 : 1); }
+        if (cols >= (d.TP >= 128 ? 3000 : (two_modes ? 1024 : 1536))) { bnb = 256; bcb = cols >= 4096 ? 4 : (cols >= 2048 ? 2 : 1); }
         else { bnb = 1024; bcb = (d.TP >= 128 && cols >= 600) ? 4 : (cols >= 250 ? 2 : 1); }
         c->front_fwd_rb[k] = frb;      // (1, 2 or 4)
         c->front_bwd_cb[k] = bcb;
@@ -1591,16 +1608,16 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
         if (e == hipSuccess) e = dalloc(&sc, sizeof(double) * ((size_t)std::max<int64_t>(scratch_entries, 1) << d.tp_shift), nullptr);
         if (e == hipSuccess) {
             MergeArgs g{};
-            g.sh = d.tp_shift; g.TP = d.TP; g.ncol = d.cg_ncol;
+            g.sh = d.tp_shift; g.TP = d.TP; g.ncol = d.cg_ncol; g.wsh = front_args(d).wsh;
             g.F = const_cast<double *>(Fall);
             g.scratch = (double *)sc;
             g.pull0 = (const int *)p0; g.pull1 = (const int *)p1;
             g.mem = (const MergeMember *)dm;
-            const int Q = 256 >> d.tp_shift;
+            const int Q = 256 >> g.wsh;
             for (size_t k = 0; k + 1 < launch_ptr.size(); ++k) {
                 g.list = (const int *)dl + launch_ptr[k];
                 const unsigned bx = (unsigned)std::min<int64_t>(std::max<int64_t>((launch_items[k] + Q - 1) / Q, 1), 2048);
-                hipLaunchKernelGGL(k_merge_member, dim3(bx, (unsigned)(launch_ptr[k + 1] - launch_ptr[k])), dim3(256), 0, c->stream, g);
+                hipLaunchKernelGGL(k_merge_member, dim3(bx, (unsigned)(launch_ptr[k + 1] - launch_ptr[k]), front_chunks(d)), dim3(256), 0, c->stream, g);
             }
             e = hipGetLastError();
         }
@@ -1634,12 +1651,12 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
             if (e == hipSuccess) e = hipMemcpyAsync(dn, ns.data(), sizeof(int) * ns.size(), hipMemcpyHostToDevice, c->stream);
             if (e == hipSuccess) {
                 TopInvArgs g{};
-                g.sh = d.tp_shift; g.TP = d.TP; g.ncol = d.cg_ncol;
+                g.sh = d.tp_shift; g.TP = d.TP; g.ncol = d.cg_ncol; g.wsh = front_args(d).wsh;
                 g.F = Fall; g.out = (double *)dS;
                 g.foff = (const int64_t *)dfo; g.ooff = (const int64_t *)doo; g.n = (const int *)dn;
-                const int Q = 256 >> d.tp_shift;
+                const int Q = 256 >> g.wsh;
                 const unsigned bx = (unsigned)std::min<int64_t>(std::max<int64_t>((biggest + Q - 1) / Q, 1), 4096);
-                hipLaunchKernelGGL(k_top_inverse, dim3(bx, (unsigned)ns.size()), dim3(256), 0, c->stream, g);
+                hipLaunchKernelGGL(k_top_inverse, dim3(bx, (unsigned)ns.size(), front_chunks(d)), dim3(256), 0, c->stream, g);
                 e = hipGetLastError();
                 for (size_t k = 0; k < ns.size() && e == hipSuccess; ++k)
                     e = hipMemcpyAsync(const_cast<double *>(Fall) + (foffs[k] << d.tp_shift), (const double *)dS + (ooffs[k] << d.tp_shift),
@@ -1709,7 +1726,7 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
                 const unsigned bx = (unsigned)std::min<int64_t>(std::max<int64_t>((biggest + std::max(Q, 1) - 1) / std::max(Q, 1), 1), 4096);
                 for (size_t at = 0; at < ns.size() && e == hipSuccess; at += 32768) {      // (grid.y is limited to 65535)
                     TopInvArgs g{};
-                    g.sh = d.tp_shift; g.TP = d.TP; g.ncol = d.cg_ncol;
+                    g.sh = d.tp_shift; g.TP = d.TP; g.ncol = d.cg_ncol; g.wsh = d.tp_shift;      // (leaf inverses: pitch <= 256)
                     g.F = Fall; g.out = const_cast<double *>(dS);
                     g.foff = (const int64_t *)dfo + at; g.ooff = (const int64_t *)doo + at; g.n = (const int *)dn + at;
                     g.packed = 1;
@@ -1847,7 +1864,6 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
                         (long long)(sweep == 0 ? band_rows[(size_t)k] : band_cols[(size_t)k]), sweep == 0 ? "rows" : "cols", c->front_planes[k]);
                 for (int tnb : {256, 1024})
                     for (int trb : {1, 2, 4}) {
-                        if (tnb == 1024 && d.TP > 256) continue;
                         std::vector<FrontWork> list;
                         if (sweep == 0) make_fwd(k, trb, list); else make_bwd(k, trb, list);
                         deal(list, 0, by_band[(size_t)k].size());
@@ -1938,7 +1954,7 @@ static int front_leaf_threads(const Ctx *c) {
 template <int NR>
 static void front_launch_leaves(Ctx *c, const FrontDev &f, bool forward, const double *bhat, double *x, const MoreRhs<NR> &mr) {
     const Dev &d = c->dcg;
-    const FrontArgs g{d.tp_shift, d.TP, d.cg_ncol};
+    const FrontArgs g = front_args(d);      // (pitch <= 256: one chunk)
     const size_t lds = NR * sizeof(double) * (forward ? 2 : 1) * (size_t)f.leaf_nmax * (size_t)d.TP;
     const bool v2 = front_two_modes(c);
     const int nbt = front_leaf_threads(c);

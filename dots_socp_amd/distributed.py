@@ -40,7 +40,7 @@ import numpy as np
 
 from ._lib import KKT_N_SUMS
 from .device import STATE_NAMES, place_slab
-from .socp.solver_socp import AlmSolver, DEFAULT_CG_TOL
+from .socp.solver_socp import AlmSolver, DEFAULT_CG_TOL, check_time_nodes
 
 
 def slab_partition(n_nodes: int, n_ranks: int):
@@ -290,6 +290,7 @@ class ShardedAlmSolver(AlmSolver):
     def __init__(self, n_time, geometry, comm=None, device=0, buffer_device=None, **kw):
         import torch
 
+        check_time_nodes(n_time, kw.get("lap_solver", "modal_direct"), time_slab=True)      # (before the communicator touches a device)
         if comm is None:
             comm = TorchComm()
         self.comm = comm

@@ -40,6 +40,21 @@ Z_VARS = ("z_fst", "z_mid", "z_end")
 DUAL_QE = ("mu", "E")
 BETAS = ("beta_fst", "beta_mid", "beta_end")
 DEFAULT_CG_TOL = 1e-8     # parity study: profiles/studies/cg_tol_parity.txt (cost within 1e-9 of the reference, budget 1e-6)
+MODAL_PCG_MAX_NODES = 256     # T + 1 the modal PCG and time slabs take (per-mode scalar block, slab layouts)
+MAX_TIME_NODES = 1024         # T + 1 the library takes at all (modal_direct and spacetime_pcg on one GPU)
+
+
+def check_time_nodes(n_time, lap_solver="modal_direct", time_slab=None):
+    """Refuse, before any device call, what the library cannot run at ``n_time + 1`` time nodes: above 256 only the direct
+    solver on one GPU (or spacetime_pcg) runs; above 1024 nothing does."""
+    nodes = int(n_time) + 1
+    if nodes > MAX_TIME_NODES:
+        raise ValueError(f"n_time + 1 = {nodes} time nodes: at most {MAX_TIME_NODES} are supported")
+    if nodes > MODAL_PCG_MAX_NODES:
+        if time_slab is not None:
+            raise ValueError(f"time slabs need n_time + 1 <= {MODAL_PCG_MAX_NODES} (got {nodes}); run on one GPU with lap_solver='modal_direct'")
+        if lap_solver == "modal_pcg":
+            raise ValueError(f"lap_solver='modal_pcg' needs n_time + 1 <= {MODAL_PCG_MAX_NODES} (got {nodes}); use lap_solver='modal_direct'")
 
 
 def _validate_checkpoints(tol_checkpoints, tol):
@@ -72,6 +87,7 @@ class AlmSolver:
         """``plan``: the device plan to use (geometry.plan_with_densities) instead of building one; ``front_owner``: a DeviceProblem
         whose factor this solver shares (dots_front_share) instead of building its own -- a member of a batch (solver_socp_many), stepped
         by ``step_batch``; the launch ahead of the right-hand side and of the penalty decision are off then."""
+        check_time_nodes(n_time, lap_solver, time_slab)
         self.tol_checkpoints = _validate_checkpoints(tol_checkpoints, tol)
         self.checkpoint_solutions = []
         self.n_time, self.nit, self.tol, self.time_limit = int(n_time), int(nit), tol, time_limit
@@ -124,8 +140,8 @@ class AlmSolver:
             try:
                 self.front_summary = dev.setup_frontal(eps=self.eps)
             except _lib.HipLibraryError as exc:
-                if exc.status != _lib.ERR_MEMORY or time_slab is not None:
-                    raise
+                if exc.status != _lib.ERR_MEMORY or time_slab is not None or int(n_time) + 1 > MODAL_PCG_MAX_NODES:
+                    raise      # (above 256 time nodes there is no PCG to fall back to: the error names the sizes)
                 self.lap_solver_fallback = str(exc)
                 logger.warning("modal_direct -> modal_pcg with the multigrid preconditioner: %s", exc)
                 self.direct = direct = False

@@ -69,7 +69,9 @@ enum dots_lap_solver {
     DOTS_LAP_SPACETIME_PCG = 0, /* Jacobi-PCG on the assembled space-time operator            */
     DOTS_LAP_MODAL_PCG = 1      /* time eigen-modes decoupled (DCT): batched shifted-surface PCG, or -- once a factor is
                                    installed with dots_front_setup -- the direct multifrontal sweeps (the default of
-                                   the Python driver: lap_solver="modal_direct")                  */
+                                   the Python driver: lap_solver="modal_direct").  T+1 <= 1024 on one GPU; above 256
+                                   only the direct sweeps step (dots_step, dots_run_phase(LAPLACIAN) and dots_mg_setup
+                                   return DOTS_ERR_STATE without a factor); time slabs need T+1 <= 256 */
 };
 
 /*
@@ -80,7 +82,7 @@ enum dots_lap_solver {
 typedef struct dots_problem_desc {
     int32_t abi_version;     /* DOTS_ABI_VERSION */
     int32_t device;          /* HIP device ordinal */
-    int32_t n_time;          /* T: number of time intervals (T+1 nodes) */
+    int32_t n_time;          /* T: number of time intervals (T+1 nodes, T+1 <= 1024; see dots_lap_solver) */
     int32_t n_vertices;      /* V */
     int32_t n_triangles;     /* F */
     int32_t n_corners;       /* = 3 F, length of the vertex->corner lists */
@@ -505,7 +507,7 @@ int dots_front_pitch(dots_ctx *ctx);
  * one launch moves (DESIGN.md section "roofline"). */
 /* which: 0 PCG operator application, 1 PCG vector update, 2 one multigrid V-cycle, 3 both sweeps of the direct
  * solve, 4 one calibration launch (k_calib_stream: reads and writes *bytes_per_launch bytes each, 8 B per lane)
- * for the PMC traffic counters */
+ * for the PMC traffic counters.  DOTS_ERR_STATE for 0, 1 and 2 on a modal context of T+1 > 256 (the PCG takes 256 modes) */
 int dots_bench_kernel(dots_ctx *ctx, int which, int reps, double *ms_per_launch, double *bytes_per_launch);
 
 /* diagnostics: which = 0 KKT read-backs whose mailbox sequence number never arrived (the sums were then copied from the
