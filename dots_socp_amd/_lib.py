@@ -31,7 +31,7 @@ EXPORTS = [
     "dots_slab_elems", "dots_slab_set_buffers", "dots_slab_stage", "dots_kkt_sums", "dots_kkt_sums_device", "dots_debug_counter", "dots_kkt_combine", "dots_objective_sums",
     "dots_objective_combine", "dots_front_launches", "dots_front_info", "dots_front_setup", "dots_front_enable", "dots_front_pitch", "dots_penalty_ahead", "dots_step_flags", "dots_step_times", "dots_stream_wait", "dots_tree_build", "dots_tree_nodes", "dots_tree_copy", "dots_tree_free",
     "dots_patch_order", "dots_assemble", "dots_assemble_nnz", "dots_assemble_copy", "dots_assemble_free", "dots_symbolic_build", "dots_symbolic_front_rows", "dots_symbolic_copy", "dots_symbolic_free",
-    "dots_front_share", "dots_laplacian_solve_many", "dots_step_many", "dots_bench_many",
+    "dots_front_share", "dots_laplacian_solve_many", "dots_step_many", "dots_bench_many", "dots_prolong_time",
 ]
 
 
@@ -100,6 +100,13 @@ class FrontDesc(C.Structure):
         ("node_uoff", C.POINTER(C.c_int64)), ("node_child", _i32p), ("front_idx", _i32p), ("pull0", _i32p), ("pull1", _i32p),
         ("level_ptr", _i32p), ("level_nodes", _i32p), ("values", _f64p), ("grounded", _i32p),
         ("band_ptr", _i32p), ("n_bands", C.c_int32), ("top_inverse", C.c_int32),
+    ]
+
+
+class ProlongDesc(C.Structure):      # dots_prolong_desc
+    _fields_ = [
+        ("node_j", _i32p), ("node_w", _f64p), ("interval_j", _i32p), ("interval_w", _f64p), ("vmap", _i32p), ("fmap", _i32p),
+        ("factor", C.c_double * 4), ("ms", _f64p),
     ]
 
 
@@ -288,6 +295,7 @@ def load(host_only=False):
     lib.dots_laplacian_solve_many.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(_f64p), C.POINTER(_f64p)]
     lib.dots_step_many.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(StepStats)]
     lib.dots_bench_many.argtypes = [C.POINTER(vp), C.c_int, C.c_int, _f64p]
+    lib.dots_prolong_time.argtypes = [vp, vp, C.POINTER(ProlongDesc)]
     lib.dots_device_bytes.argtypes = [vp]
     lib.dots_device_bytes.restype = C.c_int64
     for n in EXPORTS:

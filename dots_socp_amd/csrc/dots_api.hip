@@ -1407,6 +1407,84 @@ int dots_bench_many(dots_ctx *const *cs, int n, int reps, double *ms) {
     return 0;
 }
 
+int dots_prolong_time(dots_ctx *dst, dots_ctx *src, const dots_prolong_desc *desc) {
+    if (!dst || !src || !desc) { set_error("prolong_time: null argument"); return DOTS_ERR_ARGUMENT; }
+    if (dst == src) { set_error("prolong_time: source and destination are one context"); return DOTS_ERR_ARGUMENT; }
+    if (dst->shard_stride != 0 || src->shard_stride != 0) { set_error("prolong_time: not available on time slabs"); return DOTS_ERR_STATE; }
+    if (dst->device != src->device) { set_error("prolong_time: the contexts are on different devices"); return DOTS_ERR_STATE; }
+    const Dev &dd = dst->d, &ds = src->d;
+    if (dd.V != ds.V || dd.F != ds.F) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "prolong_time: V, F = %d, %d, the source's %d, %d: another mesh", dd.V, dd.F, ds.V, ds.F);
+        set_error(buf);
+        return DOTS_ERR_ARGUMENT;
+    }
+    if (!desc->node_j || !desc->node_w || !desc->interval_j || !desc->interval_w) { set_error("prolong_time: null table"); return DOTS_ERR_ARGUMENT; }
+    // every table entry names two source time points of the row it reads; every map entry a row of the source
+    const int nn = dd.T + 1, ni = dd.T;
+    for (int t = 0; t < nn + ni; ++t) {
+        const bool node = t < nn;
+        const int j = node ? desc->node_j[t] : desc->interval_j[t - nn];
+        const double w = node ? desc->node_w[t] : desc->interval_w[t - nn];
+        const int top = std::max((node ? ds.T + 1 : ds.T) - 2, 0);
+        if (j < 0 || j > top || !(w >= 0.0 && w <= 1.0)) {
+            char buf[200];
+            snprintf(buf, sizeof buf, "prolong_time: %s table entry %d (j = %d, w = %g) out of range (0 <= j <= %d, 0 <= w <= 1)", node ? "node" : "interval",
+                     node ? t : t - nn, j, w, top);
+            set_error(buf);
+            return DOTS_ERR_ARGUMENT;
+        }
+    }
+    for (int pass = 0; pass < 2; ++pass) {
+        const int32_t *m = pass ? desc->fmap : desc->vmap;
+        const int n = pass ? dd.F : dd.V;
+        for (int i = 0; m && i < n; ++i)
+            if (m[i] < 0 || m[i] >= n) { set_error(pass ? "prolong_time: fmap entry out of range" : "prolong_time: vmap entry out of range"); return DOTS_ERR_ARGUMENT; }
+    }
+    int rc = check(src, true);      // (a pending penalty division is carried out, as for a download)
+    if (rc) return rc;
+    if (src->zmid_stale) { set_error("prolong_time: the source's z_mid was not materialised by its last step (dots_step_flags)"); return DOTS_ERR_STATE; }
+    if ((rc = materialise_zmid(src))) return rc;
+    if ((rc = check(dst, false, true))) return rc;
+    dst->pending_div = 0.0;      // (every array a pending division would have touched is replaced)
+    // tables and maps in one device buffer: [node w | interval w | node j | interval j | vmap | fmap]
+    const size_t nv = desc->vmap ? (size_t)dd.V : 0, nf = desc->fmap ? (size_t)dd.F : 0;
+    const size_t bytes = sizeof(double) * (size_t)(nn + ni) + sizeof(int32_t) * ((size_t)(nn + ni) + nv + nf);
+    char *buf = nullptr;
+    DOTS_HIP(hipMalloc((void **)&buf, bytes));
+    double *wn = (double *)buf, *wi = wn + nn;
+    int *jn = (int *)(wi + ni), *ji = jn + nn, *vm = ji + ni, *fm = vm + nv;
+    hipError_t e = hipMemcpyAsync(wn, desc->node_w, sizeof(double) * (size_t)nn, hipMemcpyHostToDevice, dst->stream);
+    if (e == hipSuccess && ni) e = hipMemcpyAsync(wi, desc->interval_w, sizeof(double) * (size_t)ni, hipMemcpyHostToDevice, dst->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(jn, desc->node_j, sizeof(int32_t) * (size_t)nn, hipMemcpyHostToDevice, dst->stream);
+    if (e == hipSuccess && ni) e = hipMemcpyAsync(ji, desc->interval_j, sizeof(int32_t) * (size_t)ni, hipMemcpyHostToDevice, dst->stream);
+    if (e == hipSuccess && nv) e = hipMemcpyAsync(vm, desc->vmap, sizeof(int32_t) * nv, hipMemcpyHostToDevice, dst->stream);
+    if (e == hipSuccess && nf) e = hipMemcpyAsync(fm, desc->fmap, sizeof(int32_t) * nf, hipMemcpyHostToDevice, dst->stream);
+    if (e != hipSuccess) rc = hip_fail(e, "prolong_time: tables", __FILE__, __LINE__);
+    // the destination's stream waits for what the source has enqueued (its last step, the division, z_mid)
+    if (!rc) rc = batch_wait(dst, src);
+    if (!rc && (e = hipEventRecord(dst->ev[0], dst->stream)) != hipSuccess) rc = hip_fail(e, "hipEventRecord", __FILE__, __LINE__);
+    const int group[DOTS_N_ARRAYS] = {0, 0, 0, 0, 1, 1, 1, 2, 2, 3, 3, 3};      // recorver_scaled_solution (solver_socp.py:397-405)
+    for (int id = 0; id < DOTS_N_ARRAYS && !rc; ++id) {
+        const bool node = array_kind(id) == 0 || array_kind(id) == 2;
+        rc = launch_prolong(dst, src, id, node ? jn : ji, node ? wn : wi, nv ? vm : nullptr, nf ? fm : nullptr, desc->factor[group[id]]);
+    }
+    if (!rc && (e = hipEventRecord(dst->ev[1], dst->stream)) != hipSuccess) rc = hip_fail(e, "hipEventRecord", __FILE__, __LINE__);
+    if (!rc) rc = batch_wait(src, dst);      // (whatever the source does next -- its release included -- comes after the reads)
+    e = hipStreamSynchronize(dst->stream);
+    if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__);
+    (void)hipFree(buf);
+    if (rc) return rc;
+    dst->zmid_stale = dst->zmid_deferred = 0;      // (z_mid's storage holds the prolonged z_mid)
+    dst->kkt_halo_fresh = 0;
+    if (desc->ms) {
+        float t = 0.f;
+        DOTS_HIP(hipEventElapsedTime(&t, dst->ev[0], dst->ev[1]));
+        *desc->ms = t;
+    }
+    return 0;
+}
+
 int dots_front_enable(dots_ctx *c, int on) {
     int rc = check(c);
     if (rc) return rc;

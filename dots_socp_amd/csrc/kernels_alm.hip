@@ -1404,6 +1404,105 @@ int launch_from_device_layout(Ctx *c, int id, double *staged) {
 }
 
 // ------------------------------------------------------------------------------------------
+// time prolongation (dots_prolong_time): one state array of a context on the time grid of another, device layout to device layout
+// ------------------------------------------------------------------------------------------
+// A destination row is formed from ONE source row (the same vertex / triangle row in the source's numbering): time point t takes
+// (1 - w[t]) * (f * a[j[t]]) + w[t] * (f * a[j[t] + 1]) -- the operations of cascade.prolong_time on the recovered solution, in that
+// order (the build has -ffp-contract=off), so that the result is what an upload of the host's interpolation leaves, bit for bit.
+// A workgroup stages the tables once, then walks passes of R rows: the source rows go through LDS (read once, non-temporal: they
+// are never read again), a lane forms two neighbouring destination columns and stores them as one 16-byte word.  Corner arrays
+// hold interval i of half s in column i + s on both sides: interpolated along the interval index, placed at t + s, the slots whose
+// interval does not exist and the padding columns written as zero (as k_convert writes them).
+struct ProlongArgs {
+    const double *src;
+    double *dst;
+    const int *jt;           // [nd] source time point of every destination time point
+    const double *wt;        // [nd] weight of source point j + 1
+    const int *map;          // destination vertex / triangle -> the source's, or null (same numbering)
+    int64_t rows;            // destination rows
+    int rpe;                 // rows per vertex / triangle: 1, 3 (B, E) or 18 (corner arrays)
+    int corner;              // 1: row = ((f * 3 + k) * 2 + s) * 3 + c, column = interval + s
+    int nd, ns;              // destination / source time points of this array's grid
+    int sh_d, sh_s;          // log2 of the destination / source pitch
+    int R;                   // rows per pass
+    double f;
+};
+constexpr int PROLONG_XS = 4096, PROLONG_RMAX = 64, PROLONG_NT = 1024;      // doubles of source rows per pass, rows per pass, table entries
+
+__global__ __launch_bounds__(BLOCK) void k_prolong(ProlongArgs a) {
+    __shared__ __attribute__((aligned(16))) double xs[PROLONG_XS + 2 * PROLONG_RMAX];
+    __shared__ double ws[PROLONG_NT];
+    __shared__ int js[PROLONG_NT];
+    const int tid = threadIdx.x;
+    const int TPs = 1 << a.sh_s, SP = TPs + 2;      // (rows two columns apart in LDS: lane groups of neighbouring rows read other banks)
+    const int hs = a.sh_s - 1, hd = a.sh_d - 1;     // log2 of the column pairs per source / destination row
+    for (int t = tid; t < a.nd; t += BLOCK) {
+        js[t] = a.jt[t];
+        ws[t] = a.wt[t];
+    }
+    const int64_t n_pass = (a.rows + a.R - 1) / a.R;
+    for (int64_t pass = blockIdx.x; pass < n_pass; pass += gridDim.x) {
+        const int64_t r0 = pass * a.R;
+        __syncthreads();      // the tables are staged / the previous pass has read its rows
+        for (int e = tid; e < (a.R << hs); e += BLOCK) {
+            const int rr = e >> hs, p = e & ((1 << hs) - 1);
+            const int64_t r = r0 + rr;
+            if (r >= a.rows) continue;
+            const int64_t ent = r / a.rpe;
+            const int64_t sr = (a.map ? (int64_t)a.map[ent] : ent) * a.rpe + (r - ent * a.rpe);
+            st2(xs + rr * SP + 2 * p, ld2_nt(a.src + (sr << a.sh_s) + 2 * p));
+        }
+        __syncthreads();
+        for (int e = tid; e < (a.R << hd); e += BLOCK) {
+            const int rr = e >> hd, p = e & ((1 << hd) - 1);
+            const int64_t r = r0 + rr;
+            if (r >= a.rows) continue;
+            const int s = a.corner ? (int)((r / 3) & 1) : 0;
+            const double *x = xs + rr * SP + s;
+            D2 y;
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int t = 2 * p + q - s;      // time point of this column
+                double v = 0.0;
+                if (t >= 0 && t < a.nd) {
+                    const int j = js[t], j1 = min(j + 1, a.ns - 1);
+                    const double w = ws[t];
+                    v = (1.0 - w) * (a.f * x[j]) + w * (a.f * x[j1]);
+                }
+                y.v[q] = v;
+            }
+            st2(a.dst + (r << a.sh_d) + 2 * p, y);
+        }
+    }
+}
+
+int launch_prolong(Ctx *dst, Ctx *src, int id, const int *jt, const double *wt, const int *vmap, const int *fmap, double f) {
+    const Dev &dd = dst->d, &ds = src->d;
+    const int kind = array_kind(id);
+    ProlongArgs a{};
+    a.src = src->arr(id);
+    a.dst = dst->arr(id);
+    a.jt = jt;
+    a.wt = wt;
+    a.map = kind <= 1 ? vmap : fmap;
+    a.rpe = kind <= 1 ? 1 : (kind == 2 ? 3 : 18);
+    a.rows = (int64_t)a.rpe * (kind <= 1 ? dd.V : dd.F);
+    a.corner = kind == 3;
+    const int node = kind == 0 || kind == 2;
+    a.nd = dd.T + node;
+    a.ns = ds.T + node;
+    a.sh_d = dd.tp_shift;
+    a.sh_s = ds.tp_shift;
+    a.f = f;
+    a.R = std::max(1, std::min(std::min(PROLONG_RMAX, (4 * BLOCK) >> (a.sh_d - 1)), PROLONG_XS >> a.sh_s));
+    if (a.nd > PROLONG_NT || (1 << a.sh_s) > PROLONG_XS || a.sh_d < 1 || a.sh_s < 1) { set_error("prolong: time pitch out of range"); return DOTS_ERR_STATE; }
+    const int64_t n_pass = (a.rows + a.R - 1) / a.R;
+    hipLaunchKernelGGL(k_prolong, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(n_pass, 1024))), dim3(BLOCK), 0, dst->stream, a);
+    DOTS_HIP(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
 // standalone operators (rows a4-a6): same index arithmetic as the fused kernels, exposed so each
 // reference function has a one-to-one parity test.  in/out are device-layout scratch arrays.
 // ------------------------------------------------------------------------------------------

@@ -160,6 +160,31 @@ class DeviceProblem:
     def download_all(self):
         return {n: self.download(n) for n in STATE_NAMES}
 
+    def prolong_from(self, src: "DeviceProblem", factors=(1.0, 1.0, 1.0, 1.0)):
+        """Fill this context's twelve state arrays with those of ``src`` (the same mesh on the same device, another ``n_time``,
+        possibly another device numbering) interpolated linearly in time on the device (dots_prolong_time; cascade.prolong_time is
+        the specification).  ``factors``: what the source values of (phi, A, B, lambda_c), the z arrays, (mu, E) and the beta arrays
+        are multiplied with first -- the four factors of ``AlmSolver.recovered``.  Returns the milliseconds of the launches."""
+        from . import cascade
+
+        if self.slab or src.slab:
+            raise ValueError("prolong_from: not available on time slabs")
+        if (self.V, self.F) != (src.V, src.F):
+            raise ValueError(f"prolong_from: another mesh (V, F = {self.V}, {self.F}, the source's {src.V}, {src.F})")
+        nj, nw = cascade.time_weights(src.T, self.T, node=True)
+        ij, iw = cascade.time_weights(src.T, self.T, node=False)
+        vmap = cascade.row_map(self.plan.perm_vert, src.plan.perm_vert, self.V)
+        fmap = cascade.row_map(self.plan.perm_tri, src.plan.perm_tri, self.F)
+        ms = C.c_double()
+        d = _lib.ProlongDesc()
+        d.node_j, d.node_w, d.interval_j, d.interval_w = _ptr(nj, C.c_int32), _ptr(nw, C.c_double), _ptr(ij, C.c_int32), _ptr(iw, C.c_double)
+        d.vmap, d.fmap = _ptr(vmap, C.c_int32), _ptr(fmap, C.c_int32)
+        for i, f in enumerate(factors):
+            d.factor[i] = float(f)
+        d.ms = C.pointer(ms)
+        _lib.check(self.lib.dots_prolong_time(self._h, src._h, C.byref(d)), "dots_prolong_time")
+        return ms.value
+
     # ---- the hot loop
     def step(self, n_iters=1, wait=True):
         """``wait=False``: only enqueue (direct solver); returns None, nothing is timed."""

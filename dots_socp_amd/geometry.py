@@ -156,14 +156,24 @@ def locality_order(K, triangles):
     return perm_v, perm_f
 
 
-def dissection_order(K, vertices, triangles, leaf=16, pitch=32):
-    """Nested-dissection numbering (the order in which the sweeps of the direct solver walk the vertices, frontal.py:
-    the elimination order, with the separators of merged tree heights pulled together): leaves are compact patches of
-    the surface, so it is also a locality-preserving numbering for the gathers."""
+def dissection_tree(K, vertices, leaf=16):
+    """The part of ``dissection_order`` that does not depend on the time pitch: the elimination tree of the mesh and the boundary
+    sizes of its nodes."""
     from . import frontal
 
     diss = frontal.nested_dissection(K.indptr, K.indices, vertices, leaf=leaf)
-    node_b = frontal.symbolic_native(diss, K.indptr, K.indices)[0]
+    return diss, frontal.symbolic_native(diss, K.indptr, K.indices)[0]
+
+
+def dissection_order(K, vertices, triangles, leaf=16, pitch=32, tree=None):
+    """Nested-dissection numbering (the order in which the sweeps of the direct solver walk the vertices, frontal.py:
+    the elimination order, with the separators of merged tree heights pulled together): leaves are compact patches of
+    the surface, so it is also a locality-preserving numbering for the gathers.
+    ``tree``: the result of ``dissection_tree`` for this mesh (shared by plans of several time pitches; left untouched)."""
+    from . import frontal
+
+    diss, node_b = tree if tree is not None else dissection_tree(K, vertices, leaf=leaf)
+    diss = dataclasses.replace(diss)      # (bands and order below belong to this pitch)
     diss.bands, diss.top_inverse = frontal.plan_bands(diss, np.diff(diss.sep_ptr), node_b, pitch)
     perm_v = frontal.sweep_order(diss, diss.bands).astype(np.int64)
     inv = np.empty_like(perm_v)
@@ -199,9 +209,43 @@ def plan_with_densities(plan: DevicePlan, mu0, mu1) -> DevicePlan:
     return dataclasses.replace(plan, mu0=c(mu0), mu1=c(mu1))
 
 
-def build_plan(n_time, geometry, reorder=True, nd_leaf=16, native=True) -> DevicePlan:
+def plan_with_time(plan: DevicePlan, n_time) -> DevicePlan:
+    """``plan`` on another time grid: the mesh arrays, the permutation and the dissection are shared, only the time modes are new.
+    Valid when ``build_plan`` would number the mesh the same way at ``n_time`` (always without reordering and with "rcm"; with "nd"
+    when the bands planned for the two mode pitches agree -- ``build_level_plans`` checks that)."""
+    Q, sigma = time_modes(n_time)
+    c = np.ascontiguousarray
+    return dataclasses.replace(plan, n_time=int(n_time), time_modes=c(Q), time_eigs=c(sigma))
+
+
+def build_level_plans(levels, geometry, reorder=True, nd_leaf=16, native=True):
+    """The plans of ``build_plan(T, geometry, ...)`` for every ``T`` of ``levels`` (a time cascade on one mesh), each equal to what
+    ``build_plan`` returns on its own, with the mesh part built once where the numbering allows: the adjacency and the elimination
+    tree are computed once; a level whose numbering equals an earlier level's shares that plan's mesh arrays (``plan_with_time``).
+    With ``reorder="nd"`` the numbering follows the bands planned for the level's mode pitch, so levels of different pitch may be
+    numbered differently: their operators are then assembled in their own numbering (the assembly sums in the order of the
+    numbering, and a level must be the problem ``build_plan`` describes, bit for bit)."""
+    shared = {}
+    plans = []
+    for T in levels:
+        plans.append(build_plan(T, geometry, reorder=reorder, nd_leaf=nd_leaf, native=native, _shared=shared, _earlier=tuple(plans)))
+    return plans
+
+
+def _same_numbering(plan, perm_v, perm_f, diss):
+    if (plan.perm_vert is None) != (perm_v is None):
+        return False
+    if perm_v is not None and not (np.array_equal(plan.perm_vert, perm_v) and np.array_equal(plan.perm_tri, perm_f)):
+        return False
+    if (plan.dissection is None) != (diss is None):
+        return False
+    return diss is None or (np.array_equal(plan.dissection.bands, diss.bands) and plan.dissection.top_inverse == diss.top_inverse)
+
+
+def build_plan(n_time, geometry, reorder=True, nd_leaf=16, native=True, _shared=None, _earlier=()) -> DevicePlan:
     """``reorder``: True / "rcm" reverse Cuthill-McKee, "nd" nested dissection (direct solver), False none.
-    ``native``: the library's host assembly (dots_assemble; the product path) or the numpy reference functions."""
+    ``native``: the library's host assembly (dots_assemble; the product path) or the numpy reference functions.
+    ``_shared`` / ``_earlier``: what ``build_level_plans`` carries from level to level (mesh graph and elimination tree; the plans so far)."""
     vertices = np.asarray(geometry["vertices"], dtype=np.float64)
     triangles = np.asarray(geometry["triangles"]).astype(np.int64)
     mu0 = np.asarray(geometry["mu0"], dtype=np.float64)
@@ -214,12 +258,23 @@ def build_plan(n_time, geometry, reorder=True, nd_leaf=16, native=True) -> Devic
 
     perm_v = perm_f = diss = None
     if reorder:
-        K0 = mesh_adjacency(V, triangles)
+        shared = {} if _shared is None else _shared
+        if "K0" not in shared:
+            shared["K0"] = mesh_adjacency(V, triangles)
+        K0 = shared["K0"]
         if reorder == "nd":
             pitch = max(8, 1 << int(np.ceil(np.log2(n_time + 1))))
-            perm_v, perm_f, diss = dissection_order(K0, vertices, triangles, leaf=nd_leaf, pitch=pitch)
+            if "tree" not in shared:
+                shared["tree"] = dissection_tree(K0, vertices, leaf=nd_leaf)
+            perm_v, perm_f, diss = dissection_order(K0, vertices, triangles, leaf=nd_leaf, pitch=pitch, tree=shared["tree"])
         else:
-            perm_v, perm_f = locality_order(K0, triangles)
+            if "rcm" not in shared:
+                shared["rcm"] = locality_order(K0, triangles)
+            perm_v, perm_f = shared["rcm"]
+    for q in _earlier:
+        if _same_numbering(q, None if perm_v is None else perm_v.astype(np.int32), None if perm_f is None else perm_f.astype(np.int32), diss):
+            return plan_with_time(q, n_time)
+    if reorder:
         inv = np.empty_like(perm_v)
         inv[perm_v] = np.arange(V)
         vertices = vertices[perm_v]

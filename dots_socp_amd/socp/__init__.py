@@ -3,15 +3,17 @@
 ``solver_raw``  SOCP solver + conversion to DOT units          (socp/solver_decorator.py:10-27, utils/type.py:48-65)
 ``solver``      ``solver_raw`` on the time-centred grid          (socp/solver_decorator.py:29-54)
 ``solver_raw_many`` / ``solver_many``   the same for several problems on one surface with one shared factor (solver_socp_many)
+``solver_raw_cascade`` / ``solver_cascade``   the same through a coarse-to-fine cascade in time (solver_socp_cascade)
 
 Both take ``(n_time, geometry, **kwargs)`` and return ``(solution, run_history)``; they can be
 passed as ``solver=`` to the reference's ``run_dot_surface`` (interface.py:106-134).
 """
 import numpy as np
 
-from .solver_socp import solver_socp, solver_socp_many
+from .solver_socp import solver_socp, solver_socp_cascade, solver_socp_many
 
-__all__ = ["solver_socp", "solver_raw", "solver", "solver_socp_many", "solver_raw_many", "solver_many"]
+__all__ = ["solver_socp", "solver_raw", "solver", "solver_socp_many", "solver_raw_many", "solver_many",
+           "solver_socp_cascade", "solver_raw_cascade", "solver_cascade"]
 
 
 def _socp_to_dot(solution_socp, geom):
@@ -71,6 +73,29 @@ def solver(n_time, geometry, **kwargs):
 
 
 solver.__name__ = "dot_solver_socp_center"
+
+
+def solver_raw_cascade(n_time, geometry, **kwargs):
+    """``solver_raw`` through the time cascade (``solver_socp_cascade``: ``levels``, ``level_tol`` and the keywords of ``solver_socp``)."""
+    solution_socp, run_history = solver_socp_cascade(n_time, geometry, **kwargs)
+    return _socp_to_dot(solution_socp, _geometry_with_areas(geometry)), run_history
+
+
+solver_raw_cascade.__name__ = "dot_solver_socp_cascade"
+
+
+def solver_cascade(n_time, geometry, **kwargs):
+    """``solver`` through the time cascade: the density on the time-centred grid with mu0 / mu1 as end points."""
+    mu0 = np.asarray(geometry["mu0"], dtype=np.float64)
+    mu1 = np.asarray(geometry["mu1"], dtype=np.float64)
+    solution_dot, run_history = solver_raw_cascade(n_time, geometry, **kwargs)
+    _to_time_centered(solution_dot, mu0, mu1)
+    for cp in solution_dot.get("checkpoints") or []:
+        _to_time_centered(cp, mu0, mu1)
+    return solution_dot, run_history
+
+
+solver_cascade.__name__ = "dot_solver_socp_cascade_center"
 
 
 def solver_raw_many(n_time, geometry, problems, **kwargs):

@@ -83,11 +83,25 @@ class AlmSolver:
     def __init__(self, n_time, geometry, congestion=0.0, nit=1000, eps=0.0, tol=1e-4, tau=1.90, is_z_scaling=True,
                  is_constant_scaling=False, check_kkt_step_by_step=False, init_solution=None, tol_checkpoints=None,
                  time_limit=1000, is_palm=False, lap_solver="modal_direct", cg_tol=DEFAULT_CG_TOL, cg_max_iter=20000, device=0, reorder=True,
-                 preconditioner="multigrid", mg_coarsest=256, time_slab=None, nd_leaf=16, plan=None, front_owner=None):
+                 preconditioner="multigrid", mg_coarsest=256, time_slab=None, nd_leaf=16, plan=None, front_owner=None, init_from=None,
+                 release_init_from=False, batched=None):
         """``plan``: the device plan to use (geometry.plan_with_densities) instead of building one; ``front_owner``: a DeviceProblem
         whose factor this solver shares (dots_front_share) instead of building its own -- a member of a batch (solver_socp_many), stepped
-        by ``step_batch``; the launch ahead of the right-hand side and of the penalty decision are off then."""
+        by ``step_batch``; the launch ahead of the right-hand side and of the penalty decision are off then.
+        ``init_from``: a finalised AlmSolver of the same mesh on the same device at another ``n_time`` (a coarser level of a cascade):
+        its recovered solution, interpolated linearly in time on the device (DeviceProblem.prolong_from), is the warm start -- what
+        ``init_solution=cascade.prolong_solution(<its solution>, ...)`` does over the host, bit for bit.  The state is transferred before
+        this solver's factor is built; ``release_init_from`` closes the coarse solver right after the transfer, so that the two factors
+        are never on the device together.  ``batched``: whether the solver is stepped by a batch (default: whenever ``plan`` or
+        ``front_owner`` is given)."""
         check_time_nodes(n_time, lap_solver, time_slab)
+        if init_from is not None:
+            if init_solution:
+                raise ValueError("init_from and init_solution are mutually exclusive: the warm start comes from one of them")
+            if time_slab is not None:
+                raise ValueError("init_from is not available on time slabs")
+            if not getattr(init_from, "finalized", False):
+                raise ValueError("init_from must have been finalised (finalize(download=False) is enough)")
         self.tol_checkpoints = _validate_checkpoints(tol_checkpoints, tol)
         self.checkpoint_solutions = []
         self.n_time, self.nit, self.tol, self.time_limit = int(n_time), int(nit), tol, time_limit
@@ -103,7 +117,7 @@ class AlmSolver:
         # the projection now rides in the launch ahead, its results in alternate buffers until the step takes them: the same launch
         # the iteration would start with, only earlier -- on for every size
         ahead = env_choice("DOTS_RHS_AHEAD", ("0", "1", "2"), "1")
-        self.batched = front_owner is not None or plan is not None
+        self.batched = (front_owner is not None or plan is not None) if batched is None else bool(batched)
         self._rhs_ahead_ok = (direct and time_slab is None and not self.is_palm and not check_kkt_step_by_step
                               and not is_constant_scaling and ahead != "0" and not self.batched)
         self._rhs_ahead = False
@@ -129,6 +143,11 @@ class AlmSolver:
         self._push()
         if preconditioner not in ("multigrid", "jacobi"):
             raise ValueError("preconditioner must be 'multigrid' or 'jacobi'")
+        self.prolong_ms = None          # device milliseconds of the transfer from ``init_from``
+        if init_from is not None:
+            self.prolong_ms = dev.prolong_from(init_from.dev, init_from.recovery_factors())
+            if release_init_from:
+                init_from.close()
         self.mg_summary = self.front_summary = None
         self.lap_solver_fallback = None      # why the direct solve was not used although it was asked for
         if direct and front_owner is not None:
@@ -151,7 +170,10 @@ class AlmSolver:
         elif preconditioner == "multigrid" and lap_solver == "modal_pcg":
             self.mg_summary = dev.setup_multigrid(eps=self.eps, coarsest=mg_coarsest)
         init_solution = init_solution or {}
-        self._upload_initial_state(init_solution)
+        if init_from is None:
+            self._upload_initial_state(init_solution)
+        elif is_constant_scaling:
+            init_solution = {"phi": dev.download("phi")}      # (_initial_constant_scaling borrows phi's storage and puts this back)
 
         self.run_history = RunningHistory(max_record_numbers=self.nit, kkt_labels=KKT_LABELS,
                                           kkt_short_labels=KKT_SHORT_LABELS, name="SOCP")
@@ -165,6 +187,7 @@ class AlmSolver:
         self.cg_total = self.cg_fail = 0
         self.counter_main = -1
         self.finished = False
+        self.finalized = False
 
         self.run_history.start()
         self.prim_gap = 1.0 + 1.0 * math.exp(-100 * congestion)      # :568
@@ -289,6 +312,10 @@ class AlmSolver:
     def _norm_squares(self, requests):
         """norm_square_* (:875-878) of the listed (array, part) pairs; the multi-GPU solver adds the slabs' shares."""
         return [self.dev.norm_square(name, part) for name, part in requests]
+
+    def recovery_factors(self):
+        """The four factors of ``recovered``: (phi, A, B, lambda_c), the z arrays, (mu, E), the beta arrays."""
+        return (self.prim_scale, self.prim_scale / self.scale_z, self.r * self.dual_scale, self.r * self.scale_z * self.dual_scale)
 
     def recovered(self, name, arr):
         """recorver_scaled_solution (:397-405)."""
@@ -524,6 +551,7 @@ class AlmSolver:
                     history={"Transportation cost": cost, "Objective value": lagr})
         self._collect_step_times(wait=True)
         hist.end()
+        self.finalized = True
         hist.solver_stats = {
             "cg_iterations": int(self.cg_total), "cg_not_converged": int(self.cg_fail), "lap_solver": dev.lap_solver,
             "device_bytes": dev.device_bytes(), "final_r": self.r, "final_scale_z": self.scale_z,
@@ -729,3 +757,98 @@ class _BatchShare:
         self.ms_laplacian = st.ms_laplacian / n
         self.ms_soc = st.ms_soc / n
         self.ms_q_lambda_multiplier = st.ms_q_lambda_multiplier / n
+
+
+# ---- coarse-to-fine time cascade ---------------------------------------------------------------------------------------------
+CASCADE_KEYS = ("congestion", "nit", "eps", "tol", "tau", "is_palm", "is_multi_threads", "is_z_scaling", "is_constant_scaling",
+                "check_kkt_step_by_step", "init_solution", "tol_checkpoints", "time_limit", "lap_solver", "cg_tol", "cg_max_iter", "device",
+                "reorder", "preconditioner", "mg_coarsest", "nd_leaf")
+
+
+def _cascade_options(n_time, levels, level_tol, kwargs):
+    """The checks of solver_socp_cascade, before any device is touched: (levels, level_tol, options)."""
+    from .. import cascade
+
+    if "time_slab" in kwargs:
+        raise ValueError("solver_socp_cascade: time slabs are not supported (a cascade runs on one GPU)")
+    if "init_from" in kwargs:
+        raise ValueError("solver_socp_cascade: init_from belongs to the levels of the cascade; start the coarsest level with init_solution")
+    unknown = set(kwargs) - set(CASCADE_KEYS)
+    if unknown:
+        raise ValueError(f"solver_socp_cascade: unknown option(s) {sorted(unknown)}")
+    levels = cascade.check_levels(levels, n_time)
+    lap_solver = kwargs.get("lap_solver", "modal_direct")
+    if lap_solver != "modal_direct" and lap_solver not in _lib.LAP_SOLVERS:
+        raise ValueError(f"lap_solver must be one of {['modal_direct'] + list(_lib.LAP_SOLVERS)}")
+    for T in levels:
+        check_time_nodes(T, lap_solver)
+    tol = kwargs.get("tol", 1e-4)
+    if level_tol is None:
+        level_tol = tol
+    if not (isinstance(level_tol, (int, float)) and level_tol > 0):
+        raise ValueError("level_tol must be a positive number")
+    _validate_checkpoints(kwargs.get("tol_checkpoints"), tol)
+    if kwargs.get("preconditioner", "multigrid") not in ("multigrid", "jacobi"):
+        raise ValueError("preconditioner must be 'multigrid' or 'jacobi'")
+    if int(kwargs.get("nit", 1000)) < 1:
+        raise ValueError("nit must be at least 1")
+    opts = dict(kwargs)
+    opts.pop("is_multi_threads", None)
+    return levels, level_tol, opts
+
+
+def solver_socp_cascade(n_time, geometry, levels=None, level_tol=None, **kwargs):
+    """``solver_socp`` through a coarse-to-fine cascade in time: the problem is solved on the time grids ``levels`` (``n_time`` values,
+    increasing, the last one ``n_time``) one after the other, each level warm-started from the recovered solution of the one before,
+    interpolated linearly in time on the device (AlmSolver ``init_from``; cascade.prolong_time is the specification).  The number of
+    iterations hardly depends on the time grid and an iteration on half the grid moves half the bytes, so most of the way to the
+    solution is covered where iterations are cheap.
+
+    ``levels=None``: ``n_time + 1`` halved while it is even and stays >= 16 nodes (1023 -> 15, 31, ..., 1023; 31 -> 15, 31; 20 -> 20
+    alone).  ``level_tol``: the tolerance of the levels below the finest (default ``tol``).  The other keywords are ``solver_socp``'s:
+    ``nit`` holds per level, ``time_limit`` for the whole cascade (a level gets the time that is left), ``init_solution`` starts the
+    coarsest level, ``tol_checkpoints`` belong to the finest level.  Every level starts as a warm start through ``init_solution`` does
+    (r = 1, the initial z scaling, a fresh penalty schedule, validator and history).
+
+    Returns ``(solution, run_history)`` of the finest level; ``run_history.running_time`` is that level's own, and
+    ``run_history.solver_stats["cascade"]`` = {"levels": [one record per level: n_time, tol, iterations, running_time, setup_seconds,
+    prolong_ms (device events; None on the coarsest level), cost, kkt_max], "total_seconds"} has the whole cascade."""
+    from .. import geometry as geo
+
+    levels, level_tol, opts = _cascade_options(n_time, levels, level_tol, kwargs)
+    tol, nit = opts.pop("tol", 1e-4), int(opts.pop("nit", 1000))
+    time_limit = opts.pop("time_limit", 1000)
+    init_solution, checkpoints = opts.pop("init_solution", None), opts.pop("tol_checkpoints", None)
+    direct = opts.get("lap_solver", "modal_direct") == "modal_direct"
+    reorder = opts.pop("reorder", True)
+    if direct and reorder is True:
+        reorder = "nd"      # (as AlmSolver chooses it)
+    nd_leaf = opts.get("nd_leaf", 16)
+    t_start = time.perf_counter()
+    shared, plans, records = {}, [], []
+    coarse = alm = None
+    try:
+        for i, T in enumerate(levels):
+            last = i + 1 == len(levels)
+            t0 = time.perf_counter()
+            plans.append(geo.build_plan(T, geometry, reorder=reorder, nd_leaf=nd_leaf, _shared=shared, _earlier=tuple(plans)))
+            alm = AlmSolver(T, geometry, nit=nit, tol=tol if last else level_tol, tol_checkpoints=checkpoints if last else None,
+                            init_solution=init_solution if i == 0 else None, init_from=coarse, release_init_from=True,
+                            time_limit=max(time_limit - (t0 - t_start), 0.0), plan=plans[-1], batched=False, reorder=reorder, **opts)
+            coarse = None      # (closed by the constructor as soon as the finer state was filled)
+            setup = time.perf_counter() - t0
+            for _ in range(nit):
+                if alm.iterate():
+                    break
+            solution, hist = alm.finalize(download=last)
+            records.append({"n_time": int(T), "tol": float(alm.tol), "iterations": int(alm.counter_main) + 1, "running_time": float(hist.running_time),
+                            "setup_seconds": float(setup), "prolong_ms": alm.prolong_ms, "cost": float(hist.history["Transportation cost"][-1]),
+                            "kkt_max": float(np.nanmax(np.asarray(hist.kkt_errors[-1], dtype=np.float64)))})
+            coarse, alm = alm, None
+        coarse.dev.sync()
+        hist.solver_stats["cascade"] = {"levels": records, "total_seconds": time.perf_counter() - t_start}
+        return solution, hist
+    finally:
+        for a in (alm, coarse):
+            if a is not None:
+                a.close()

@@ -492,6 +492,35 @@ int dots_laplacian_solve_many(dots_ctx *const *ctxs, int n, const double *const 
  * stream (milliseconds per batched solve). */
 int dots_step_many(dots_ctx *const *ctxs, int n, dots_step_stats *stats);
 int dots_bench_many(dots_ctx *const *ctxs, int n, int reps, double *ms_per_solve);
+/* ---- coarse-to-fine time cascade: the state of one context on the time grid of another (init_solution, solver_socp.py:38,70-71,
+ * 239-250, without the round trip over the host) -----------------------------------------------------------------------------
+ * dots_prolong_time fills the twelve state arrays of `dst` with those of `src` interpolated linearly in time: destination
+ * time point t of an array takes (1 - w[t]) * (f * a[j[t]]) + w[t] * (f * a[j[t] + 1]) of the same row of `src` (a[j + 1] reads a[j]
+ * where the source has one point only), with f the array's factor below (the source's scaled iterate -> the recovered solution,
+ * solver_socp.py:397-405; pass 1 to copy the iterate as it is).  Node arrays (phi, B, E) use the node tables, every other array the
+ * interval tables; the corner arrays are interpolated along the interval index.  The tables come from the caller
+ * (dots_socp_amd/cascade.py: time_weights), so that the result is bit for bit what dots_upload of the same interpolation done on
+ * the host in these operations leaves.  Both contexts hold the same mesh on one device, possibly in different device numberings:
+ * vmap / fmap give the source row of every destination vertex / triangle (NULL = the same numbering; corner k of a triangle is the
+ * same in both).
+ * On `src` a pending penalty division is carried out and z_mid is materialised first (DOTS_ERR_STATE if z_mid is stale: the last
+ * step ran with DOTS_STEP_SKIP_Z_MID); `dst` is left as twelve dots_upload calls leave it (carried sums, fused KKT sums and a launch
+ * ahead dropped), ready for dots_step.  The two streams are ordered by events; the call returns when the destination is filled.
+ * DOTS_ERR_ARGUMENT: different V or F, dst == src, a NULL table, a table or map entry out of range; DOTS_ERR_STATE: a time slab,
+ * contexts on different devices. */
+typedef struct dots_prolong_desc {
+    const int32_t *node_j;       /* [T_dst + 1] source node j of every destination node, 0 <= j <= max(T_src - 1, 0)      */
+    const double *node_w;        /* [T_dst + 1] weight of source node j + 1, in [0, 1]                                    */
+    const int32_t *interval_j;   /* [T_dst]     source interval j of every destination interval, 0 <= j <= max(T_src - 2, 0) */
+    const double *interval_w;    /* [T_dst]                                                                               */
+    const int32_t *vmap;         /* [V] destination vertex row -> source vertex row, or NULL                              */
+    const int32_t *fmap;         /* [F] destination triangle row -> source triangle row, or NULL                          */
+    double factor[4];            /* applied to the source values of: phi, A, B, lambda_c / z_fst, z_mid, z_end / mu, E /
+                                    beta_fst, beta_mid, beta_end                                                          */
+    double *ms;                  /* NULL, or out: milliseconds of the launches on the device (events on dst's stream)     */
+} dots_prolong_desc;
+int dots_prolong_time(dots_ctx *dst, dots_ctx *src, const dots_prolong_desc *desc);
+
 /* launches one direct solve takes: 2 x bands of tree heights (one per band and sweep; a band is one height unless
  * dots_front_desc.band_ptr merges heights), minus one with dots_front_desc.top_inverse */
 int dots_front_launches(dots_ctx *ctx);
