@@ -31,7 +31,7 @@ EXPORTS = [
     "dots_slab_elems", "dots_slab_set_buffers", "dots_slab_stage", "dots_kkt_sums", "dots_kkt_sums_device", "dots_debug_counter", "dots_kkt_combine", "dots_objective_sums",
     "dots_objective_combine", "dots_front_launches", "dots_front_info", "dots_front_setup", "dots_front_enable", "dots_front_pitch", "dots_penalty_ahead", "dots_step_flags", "dots_step_times", "dots_stream_wait", "dots_tree_build", "dots_tree_nodes", "dots_tree_copy", "dots_tree_free",
     "dots_patch_order", "dots_assemble", "dots_assemble_nnz", "dots_assemble_copy", "dots_assemble_free", "dots_symbolic_build", "dots_symbolic_front_rows", "dots_symbolic_copy", "dots_symbolic_free",
-    "dots_front_share", "dots_laplacian_solve_many", "dots_step_many", "dots_bench_many", "dots_prolong_time",
+    "dots_front_share", "dots_laplacian_solve_many", "dots_step_many", "dots_bench_many", "dots_prolong_time", "dots_readout",
 ]
 
 
@@ -110,6 +110,13 @@ class ProlongDesc(C.Structure):      # dots_prolong_desc
     ]
 
 
+class ReadoutDesc(C.Structure):      # dots_readout_desc
+    _fields_ = [
+        ("factor", C.c_double), ("w_vertex", _f64p), ("w_triangle", _f64p), ("centred", C.c_int32), ("reserved", C.c_int32),
+        ("mu0", _f64p), ("mu1", _f64p), ("mu", _f64p), ("E", _f64p), ("layer_mass", _f64p), ("layer_negative", _f64p), ("ms", _f64p),
+    ]
+
+
 class StepStats(C.Structure):
     _fields_ = [
         ("alm_iterations", C.c_int32), ("cg_iterations", C.c_int32), ("cg_last_iterations", C.c_int32),
@@ -140,7 +147,7 @@ SLAB_SIZES = {"vertex_halo": 0, "b_chunk": 1, "x_chunk": 2, "triangle_halo": 3}
 KNOWN_ENV = {
     # read by the library (csrc/dots_api.hip: env_int)
     "DOTS_KKT_TWO", "DOTS_BM_NT", "DOTS_LAZY_DIV", "DOTS_ZMID_DEFER", "DOTS_MEM_BUDGET", "DOTS_FRONT_VEC2", "DOTS_FRONT_ROWS",
-    "DOTS_FRONT_LEAFINV", "DOTS_FRONT_TUNE", "DOTS_FRONT_CFG", "DOTS_FRONT_NR", "DOTS_MAIL_TEST_DROP", "DOTS_MAIL_SPINS", "DOTS_ND_PCA_MIN",
+    "DOTS_FRONT_LEAFINV", "DOTS_FRONT_TUNE", "DOTS_FRONT_CFG", "DOTS_FRONT_NR", "DOTS_MAIL_TEST_DROP", "DOTS_MAIL_SPINS", "DOTS_ND_PCA_MIN", "DOTS_READOUT_PINNED",
     # read by the host side
     "DOTS_RHS_AHEAD", "DOTS_TIME_EVERY", "DOTS_FRONT_BANDS", "DOTS_FRONT_TOPINV", "DOTS_TORCH_FIRST", "DOTS_DIST_BACKEND", "DOTS_HIPCC_FLAGS",
 }
@@ -296,6 +303,7 @@ def load(host_only=False):
     lib.dots_step_many.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(StepStats)]
     lib.dots_bench_many.argtypes = [C.POINTER(vp), C.c_int, C.c_int, _f64p]
     lib.dots_prolong_time.argtypes = [vp, vp, C.POINTER(ProlongDesc)]
+    lib.dots_readout.argtypes = [vp, C.POINTER(ReadoutDesc)]
     lib.dots_device_bytes.argtypes = [vp]
     lib.dots_device_bytes.restype = C.c_int64
     for n in EXPORTS:

@@ -584,6 +584,7 @@ int dots_create(const dots_problem_desc *desc, dots_ctx **out) {
         ok &= env_int("DOTS_FRONT_NR", 2, 8, &c->front_nr_max);      // right-hand sides per launch of a batched solve (2, 4 or 8; A/B measurements)
         if (c->front_nr_max != 2 && c->front_nr_max != 4 && c->front_nr_max != 8) { set_error("DOTS_FRONT_NR must be 2, 4 or 8"); ok = false; }
         ok &= env_int("DOTS_MAIL_TEST_DROP", 0, 1 << 20, &c->mail_test_drop);
+        ok &= env_int("DOTS_READOUT_PINNED", 0, 1 << 20, &c->readout_pinned);      // n > 0: dots_readout copies through two pinned slots of n KB (A/B measurements)
         int spins = -1;
         ok &= env_int("DOTS_MAIL_SPINS", 0, 2000000000, &spins);
         if (spins >= 0) c->mail_spins = spins;
@@ -597,6 +598,7 @@ int dots_create(const dots_problem_desc *desc, dots_ctx **out) {
     preload_alm_kernels();
     preload_kkt_kernels();
     preload_transform_kernels();
+    preload_readout_kernels();
     *out = c;
     return 0;
 }
@@ -612,6 +614,11 @@ int dots_destroy(dots_ctx *c) {
     if (c->h_pinned) (void)hipHostFree(c->h_pinned);
     if (c->h_flags) (void)hipHostFree(c->h_flags);
     if (c->h_mail) (void)hipHostFree(c->h_mail);
+    if (c->h_ro_sums) (void)hipHostFree(c->h_ro_sums);
+    if (c->h_ring) (void)hipHostFree(c->h_ring);
+    for (auto &ev : c->ro_ev) if (ev) (void)hipEventDestroy(ev);
+    for (auto &ev : c->ring_ev) if (ev) (void)hipEventDestroy(ev);
+    if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
     for (auto &ev : c->ev) if (ev) (void)hipEventDestroy(ev);
     if (c->ev_batch) (void)hipEventDestroy(c->ev_batch);
     c->front_store.reset();      // (a shared factor: freed with its last holder)
@@ -689,6 +696,7 @@ int dots_download(dots_ctx *c, int id, double *host, int64_t count) {
     if ((rc = launch_from_device_layout(c, id, c->stage))) return rc;
     DOTS_HIP(hipMemcpyAsync(host, c->stage, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, c->stream));
     DOTS_HIP(hipStreamSynchronize(c->stream));
+    c->d2h_bytes += (int64_t)sizeof(double) * count;
     return 0;
 }
 
@@ -1485,6 +1493,151 @@ int dots_prolong_time(dots_ctx *dst, dots_ctx *src, const dots_prolong_desc *des
     return 0;
 }
 
+// ---- dots_readout ---------------------------------------------------------------------------------------------------------
+// the inverse of the device numbering, the copy stream, the chunk events and the host memory of the layer sums: once per context
+static int readout_prepare(Ctx *c) {
+    if (c->readout_ready) return 0;
+    const Dev &d = c->d;
+    for (int pass = 0; pass < 2; ++pass) {
+        const int *perm = pass ? d.perm_f : d.perm_v;
+        const int n = pass ? d.F : d.V;
+        if (!perm) continue;
+        std::vector<int> p((size_t)n), inv((size_t)n);
+        DOTS_HIP(hipMemcpyAsync(p.data(), perm, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+        DOTS_HIP(hipStreamSynchronize(c->stream));
+        for (int i = 0; i < n; ++i) {
+            if (p[i] < 0 || p[i] >= n) { set_error("readout: the device numbering is not a permutation"); return DOTS_ERR_STATE; }
+            inv[p[i]] = i;
+        }
+        const int *dev = nullptr;
+        int rc = dev_upload(c, &dev, inv.data(), n);
+        if (rc) return rc;
+        (pass ? c->inv_perm_f : c->inv_perm_v) = const_cast<int *>(dev);
+    }
+    if (!c->copy_stream) DOTS_HIP(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+    for (auto &ev : c->ro_ev) if (!ev) DOTS_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    for (auto &ev : c->ring_ev) if (!ev) DOTS_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    if (!c->h_ro_sums) DOTS_HIP(hipHostMalloc((void **)&c->h_ro_sums, sizeof(double) * 2 * 1024, hipHostMallocCoherent | hipHostMallocMapped));
+    c->readout_ready = 1;
+    return 0;
+}
+
+// Device -> host copies of dots_readout on the copy stream, each behind the event of the launch that formed its layers: straight into the
+// caller's memory, or (DOTS_READOUT_PINNED=<KB per slot>) through two pinned slots that the host empties while the next piece is on its way
+struct ReadoutCopier {
+    Ctx *c;
+    size_t SLOT;                 // bytes per slot
+    char *pend_host[2] = {nullptr, nullptr};
+    size_t pend_n[2] = {0, 0};
+    int k = 0;
+    int drain(int slot) {
+        if (!pend_host[slot]) return 0;
+        DOTS_HIP(hipEventSynchronize(c->ring_ev[slot]));
+        memcpy(pend_host[slot], c->h_ring + slot * SLOT, pend_n[slot]);
+        pend_host[slot] = nullptr;
+        return 0;
+    }
+    int copy(double *host, const double *dev, size_t bytes, hipEvent_t after) {
+        DOTS_HIP(hipStreamWaitEvent(c->copy_stream, after, 0));
+        c->d2h_bytes += (int64_t)bytes;
+        if (!c->readout_pinned) {
+            DOTS_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->copy_stream));
+            return 0;
+        }
+        for (size_t off = 0; off < bytes; off += SLOT, ++k) {
+            const int slot = k & 1;
+            const size_t n = std::min(SLOT, bytes - off);
+            int rc = drain(slot);
+            if (rc) return rc;
+            DOTS_HIP(hipMemcpyAsync(c->h_ring + slot * SLOT, (const char *)dev + off, n, hipMemcpyDeviceToHost, c->copy_stream));
+            DOTS_HIP(hipEventRecord(c->ring_ev[slot], c->copy_stream));
+            pend_host[slot] = (char *)host + off;
+            pend_n[slot] = n;
+        }
+        return 0;
+    }
+    int finish() {
+        int rc = drain(k & 1);      // (the older of the two slots first)
+        if (!rc) rc = drain((k + 1) & 1);
+        if (rc) return rc;
+        return 0;
+    }
+};
+
+int dots_readout(dots_ctx *c, const dots_readout_desc *desc) {
+    if (!c) { set_error("null context"); return DOTS_ERR_ARGUMENT; }
+    if (!desc) { set_error("readout: null description"); return DOTS_ERR_ARGUMENT; }
+    if (c->shard_stride != 0) { set_error("readout: not available on time slabs"); return DOTS_ERR_STATE; }
+    const Dev &d = c->d;
+    const bool sums = desc->layer_mass || desc->layer_negative;
+    const bool want_mu = desc->mu || sums;
+    if (!want_mu && !desc->E) { set_error("readout: nothing requested (mu, E and the layer sums are all NULL)"); return DOTS_ERR_ARGUMENT; }
+    const int centred = desc->centred ? 1 : 0;
+    if (centred && (!desc->mu0 || !desc->mu1)) { set_error("readout: the centred output needs mu0 and mu1"); return DOTS_ERR_ARGUMENT; }
+    if (centred && d.T < 1) { set_error("readout: no layers to centre"); return DOTS_ERR_ARGUMENT; }
+    int rc = check(c, true);      // (a pending penalty division is carried out, as for a download; z_mid is not needed)
+    if (rc) return rc;
+    if ((rc = readout_prepare(c))) return rc;
+    const size_t slot = (size_t)c->readout_pinned << 10;
+    if (slot && !c->h_ring) DOTS_HIP(hipHostMalloc((void **)&c->h_ring, 2 * slot, hipHostMallocDefault));
+    // the staging buffer: [E | mu | w_vertex | mu0 | mu1 | w_triangle | partial sums], every part on a 16-byte boundary
+    const int layers = d.T + centred, n_wg = readout_workgroups(c);
+    auto even = [](int64_t n) { return (n + 1) & ~(int64_t)1; };
+    const int64_t V = d.V, F = d.F;
+    const int64_t n_E = desc->E ? (int64_t)(d.T + 1) * 3 * F : 0, n_mu = want_mu ? (int64_t)layers * V : 0;
+    const int64_t o_mu = even(n_E), o_wv = o_mu + even(n_mu), o_m0 = o_wv + even(V), o_m1 = o_m0 + even(V), o_wt = o_m1 + even(V);
+    const int64_t o_part = o_wt + even(F), total = o_part + (sums ? (int64_t)layers * 2 * n_wg : 0);
+    if (total > c->stage_count) {      // (18 F pitch doubles: reached only by a mesh with more than ~ 14 vertices per triangle)
+        set_error("readout: mu, E and their weights do not fit the staging buffer (sized for z_mid) on this mesh; use dots_download");
+        return DOTS_ERR_STATE;
+    }
+    double *st = c->stage;
+    // what is enqueued; every path out of the call waits for both streams first (the uploads read the caller's arrays)
+    auto enqueue = [&]() -> int {
+        const double *wv = nullptr, *wt = nullptr, *m0 = nullptr, *m1 = nullptr;
+        if (want_mu && desc->w_vertex) { DOTS_HIP(hipMemcpyAsync(st + o_wv, desc->w_vertex, sizeof(double) * (size_t)V, hipMemcpyHostToDevice, c->stream)); wv = st + o_wv; }
+        if (want_mu && centred) {
+            DOTS_HIP(hipMemcpyAsync(st + o_m0, desc->mu0, sizeof(double) * (size_t)V, hipMemcpyHostToDevice, c->stream));
+            DOTS_HIP(hipMemcpyAsync(st + o_m1, desc->mu1, sizeof(double) * (size_t)V, hipMemcpyHostToDevice, c->stream));
+            m0 = st + o_m0;
+            m1 = st + o_m1;
+        }
+        if (desc->E && desc->w_triangle) { DOTS_HIP(hipMemcpyAsync(st + o_wt, desc->w_triangle, sizeof(double) * (size_t)F, hipMemcpyHostToDevice, c->stream)); wt = st + o_wt; }
+        int n_ch_mu = 0, n_ch_E = 0, r = 0;
+        DOTS_HIP(hipEventRecord(c->ev[0], c->stream));
+        if (want_mu && (r = launch_readout(c, false, st + o_mu, c->inv_perm_v, wv, m0, m1, centred, desc->factor, sums ? st + o_part : nullptr, c->ro_ev, &n_ch_mu))) return r;
+        if (desc->E && (r = launch_readout(c, true, st, c->inv_perm_f, wt, nullptr, nullptr, 0, desc->factor, nullptr, c->ro_ev + 4, &n_ch_E))) return r;
+        if (sums && (r = launch_readout_fold(c, st + o_part, layers, n_wg, c->h_ro_sums))) return r;
+        DOTS_HIP(hipEventRecord(c->ev[1], c->stream));
+        // every chunk of layers is copied as soon as its launch has finished, while the later launches run
+        ReadoutCopier cp{c, slot};
+        for (int k = 0; k < n_ch_mu && desc->mu; ++k) {
+            const int64_t l0 = (int64_t)k * 256, l1 = std::min<int64_t>(l0 + 256, layers);
+            if ((r = cp.copy(desc->mu + l0 * V, st + o_mu + l0 * V, sizeof(double) * (size_t)((l1 - l0) * V), c->ro_ev[k]))) return r;
+        }
+        for (int k = 0; k < n_ch_E; ++k) {
+            const int64_t l0 = (int64_t)k * 256, l1 = std::min<int64_t>(l0 + 256, d.T + 1);
+            if ((r = cp.copy(desc->E + l0 * 3 * F, st + l0 * 3 * F, sizeof(double) * (size_t)((l1 - l0) * 3 * F), c->ro_ev[4 + k]))) return r;
+        }
+        return cp.finish();
+    };
+    rc = enqueue();
+    const hipError_t e1 = hipStreamSynchronize(c->copy_stream), e2 = hipStreamSynchronize(c->stream);
+    if (!rc && e1 != hipSuccess) rc = hip_fail(e1, "hipStreamSynchronize", __FILE__, __LINE__);
+    if (!rc && e2 != hipSuccess) rc = hip_fail(e2, "hipStreamSynchronize", __FILE__, __LINE__);
+    if (rc) return rc;
+    for (int l = 0; l < layers && sums; ++l) {      // (written by the fold kernel itself: no copy)
+        if (desc->layer_mass) desc->layer_mass[l] = c->h_ro_sums[2 * l];
+        if (desc->layer_negative) desc->layer_negative[l] = c->h_ro_sums[2 * l + 1];
+    }
+    if (desc->ms) {
+        float t = 0.f;
+        DOTS_HIP(hipEventElapsedTime(&t, c->ev[0], c->ev[1]));
+        *desc->ms = t;
+    }
+    return 0;
+}
+
 int dots_front_enable(dots_ctx *c, int on) {
     int rc = check(c);
     if (rc) return rc;
@@ -1526,6 +1679,7 @@ int64_t dots_debug_counter(dots_ctx *c, int which) {
         case 6: return c->bm_nt;                      // beta_mid streamed around the caches by steps 2+3 (the rule of dots_front_setup, or DOTS_BM_NT)
         case 7: return c->front_many_launches;        // sweep launches the last front_solve_many on this (first) context enqueued
         case 8: return c->front_many_split;           // ... of those, launches with fewer rhs than their chunk (many_launch halved: LDS or 1024-thread cap)
+        case 9: return c->d2h_bytes;                  // bytes dots_download and dots_readout have copied device -> host
         default: return -1;
     }
 }

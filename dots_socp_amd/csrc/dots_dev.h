@@ -293,6 +293,13 @@ int objective_sums(Ctx *c, double *sums);
 int objective_combine(Ctx *c, const double *sums, double *out);
 int norm_square(Ctx *c, int array_id, int part, double *out);
 int reduce_partials(Ctx *c, const double *partials, int n_slots, int n_blocks, int first_slot);  // -> scal[SUMS+first_slot+slot]
+// dots_readout (kernels_readout.hip): mu (or E) in the caller's numbering and the reference layout, scaled, into `out`; one launch per chunk of
+// 256 layers, each followed by ev[k]; part != null (mu): per-workgroup layer sums [layers][2][readout_workgroups], folded by launch_readout_fold
+int launch_readout(Ctx *c, bool is_E, double *out, const int *inv, const double *w, const double *m0, const double *m1, int centred, double factor,
+                   double *part, hipEvent_t *ev, int *n_chunks);
+int readout_workgroups(const Ctx *c);
+int launch_readout_fold(Ctx *c, const double *part, int layers, int n_wg, double *out);      // out[2 l], out[2 l + 1]: sum / negative sum of layer l
+void preload_readout_kernels();
 
 // device allocations of a factor shared by several contexts (Ctx::front_store)
 struct FrontStore {
@@ -415,6 +422,16 @@ struct Ctx {
     int64_t front_many_launches = 0, front_many_split = 0;   // sweep launches of the last front_solve_many, those split below their chunk (dots_debug_counter 7, 8)
     uint64_t lap_hash = 0;        // FNV-1a of the Laplacian (rowptr, col, val) and the vertex masses: dots_front_share compares it with the owner's
     int batched = 0;              // stepped by dots_step_many since its last dots_step: dots_penalty_ahead is refused
+    // dots_readout: built on first use
+    int *inv_perm_v = nullptr, *inv_perm_f = nullptr;   // caller vertex / triangle -> device row (null with the identity numbering)
+    int readout_ready = 0;
+    hipStream_t copy_stream = nullptr;   // device -> host copies of finished layer ranges, beside the launches of the next
+    hipEvent_t ro_ev[8]{};        // one per chunk of 256 layers of mu (0-3) and E (4-7)
+    double *h_ro_sums = nullptr;  // coherent pinned host memory the fold kernel writes: [layers][2]
+    char *h_ring = nullptr;       // DOTS_READOUT_PINNED=<KB>: two pinned slots of that size the copies go through (A/B measurements)
+    hipEvent_t ring_ev[2]{};
+    int readout_pinned = 0;       // KB per slot; 0: copies go straight into the caller's memory
+    int64_t d2h_bytes = 0;        // bytes copied device -> host by dots_download and dots_readout (dots_debug_counter 9)
     void *mg_allocs[160]{};
     int n_mg_allocs = 0;
     // constants of the KKT normalisation (solver_socp.py:303-313)

@@ -160,6 +160,34 @@ class DeviceProblem:
     def download_all(self):
         return {n: self.download(n) for n in STATE_NAMES}
 
+    def readout(self, factor=1.0, w_vertex=None, w_triangle=None, centred=False, mu0=None, mu1=None, mu=True, E=True, sums=True):
+        """``(mu, E, layer_mass, layer_negative)`` formed on the device (dots_readout; readout.read_out_host is the specification):
+        ``mu`` (T, V) -- (T + 1, V) when ``centred`` -- and ``E`` (T + 1, F, 3), every value times ``factor``, then times its
+        vertex's / triangle's weight where given; the sum of every layer of ``mu`` and of its negative entries.  ``mu`` / ``E`` /
+        ``sums`` = False leave that part out (None).  ``self.readout_ms`` / ``self.readout_bytes``: device milliseconds of the
+        launches and the bytes copied to the host by the last call."""
+        if self.slab:
+            raise ValueError("readout: not available on time slabs")
+        f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)      # noqa: E731
+        wv, wt, m0, m1 = f64(w_vertex), f64(w_triangle), f64(mu0), f64(mu1)
+        for a, n, what in ((wv, self.V, "w_vertex"), (m0, self.V, "mu0"), (m1, self.V, "mu1"), (wt, self.F, "w_triangle")):
+            if a is not None and a.shape != (n,):
+                raise ValueError(f"readout: {what} must have shape ({n},), got {a.shape}")
+        layers = self.T + (1 if centred else 0)
+        out_mu = np.empty((layers, self.V)) if mu else None
+        out_E = np.empty((self.T + 1, self.F, 3)) if E else None
+        mass, neg = (np.empty(layers), np.empty(layers)) if sums else (None, None)
+        ms = C.c_double()
+        d = _lib.ReadoutDesc()
+        d.factor, d.centred = float(factor), int(bool(centred))
+        d.w_vertex, d.w_triangle, d.mu0, d.mu1 = _ptr(wv, C.c_double), _ptr(wt, C.c_double), _ptr(m0, C.c_double), _ptr(m1, C.c_double)
+        d.mu, d.E, d.layer_mass, d.layer_negative = _ptr(out_mu, C.c_double), _ptr(out_E, C.c_double), _ptr(mass, C.c_double), _ptr(neg, C.c_double)
+        d.ms = C.pointer(ms)
+        before = self.debug_counter(9)
+        _lib.check(self.lib.dots_readout(self._h, C.byref(d)), "dots_readout")
+        self.readout_ms, self.readout_bytes = ms.value, self.debug_counter(9) - before
+        return out_mu, out_E, mass, neg
+
     def prolong_from(self, src: "DeviceProblem", factors=(1.0, 1.0, 1.0, 1.0)):
         """Fill this context's twelve state arrays with those of ``src`` (the same mesh on the same device, another ``n_time``,
         possibly another device numbering) interpolated linearly in time on the device (dots_prolong_time; cascade.prolong_time is

@@ -524,6 +524,15 @@ class ShardedAlmSolver(AlmSolver):
                 place_slab(name, gathered[begin // stride], full, begin, count, max(0, min(count, self.n_time - begin)))
         return full
 
+    def _read_out(self, factor, w_vertex=None, w_triangle=None, centred=False, mu0=None, mu1=None, sums=False):
+        """The read-out on the host (the device read-out works on whole arrays: not on time slabs): the gathered ``mu`` and ``E``
+        through readout.read_out_host."""
+        from .readout import layer_sums_host, read_out_host
+
+        mu, E = read_out_host({"mu": self._download("mu"), "E": self._download("E")}, factor, w_vertex, w_triangle, centred, mu0, mu1)
+        mass, neg = layer_sums_host(mu) if sums else (None, None)
+        return mu, E, {"layer_mass": mass, "layer_negative": neg, "ms": None, "bytes": None}
+
     def _time_is_up(self, reads_back=True):
         """Every rank must leave the loop on the same iteration, so the clock decision is shared (one flag
         all-reduce) -- but only on iterations that synchronise with the host anyway (KKT evaluation or penalty

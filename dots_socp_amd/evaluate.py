@@ -42,6 +42,24 @@ def check_negative_mass(mu, verbose=False):
     return err, neg
 
 
+def mass_conservation_from_layers(layer_mass, verbose=False):
+    """``check_mass_conservation`` from the per-layer sums of ``mu`` (``run_history.solver_stats["readout"]["layer_mass"]``)."""
+    mass = np.asarray(layer_mass, dtype=np.float64)
+    err = float(np.linalg.norm(mass - 1.0) / np.sqrt(mass.shape[0]))
+    if verbose:
+        logger.info("Mass Conservation Violation: %.2e", err)
+    return err
+
+
+def negative_mass_from_layers(layer_negative, verbose=False):
+    """``check_negative_mass`` from the per-layer sums of the negative entries of ``mu`` (``solver_stats["readout"]["layer_negative"]``)."""
+    neg = np.asarray(layer_negative, dtype=np.float64)
+    err = float(np.linalg.norm(neg) / np.sqrt(neg.shape[0]))
+    if verbose:
+        logger.info("Non-Negative Mass Violation: %.2e", err)
+    return err, neg
+
+
 def compare_with_exact_transportation(mu, mu_exact, geometry, verbose=False):
     """Relative L1 / L2 / Linf distance between the densities mu / (area_v / 3) of two mass arrays
     (evaluate_solution.py:47-58 with the norms of utils/util.py:32-67: each norm is divided by 1 + the norm of the

@@ -7,6 +7,11 @@
 
 Both take ``(n_time, geometry, **kwargs)`` and return ``(solution, run_history)``; they can be
 passed as ``solver=`` to the reference's ``run_dot_surface`` (interface.py:106-134).
+
+``readout="device"`` (the default) forms what they return -- ``mu`` and ``E`` in DOT units, ``mu`` on its final grid -- on the
+device (``dots_readout``): two arrays cross to the host instead of twelve, and ``run_history.solver_stats["readout"]`` holds the
+layer sums of ``mu`` (``evaluate.mass_conservation_from_layers`` / ``negative_mass_from_layers``).  ``readout="host"`` downloads
+the whole solution and converts it in numpy: the same values bit for bit, kept as the baseline of measurements.
 """
 import numpy as np
 
@@ -25,15 +30,21 @@ def _socp_to_dot(solution_socp, geom):
         "E": solution_socp["E"] * area_t[np.newaxis, :, np.newaxis],
     }
     if solution_socp.get("checkpoints"):
-        out["checkpoints"] = [
-            {
-                "mu": cp["mu"] * (area_v[np.newaxis, :] / 3.0),
-                "E": cp["E"] * area_t[np.newaxis, :, np.newaxis],
-                "iteration": cp["iteration"], "time": cp["time"], "kkt": cp["kkt"],
-            }
-            for cp in solution_socp["checkpoints"]
-        ]
+        out["checkpoints"] = _checkpoints_to_dot(solution_socp["checkpoints"], geom)
     return out
+
+
+def _checkpoints_to_dot(checkpoints, geom):
+    area_v = np.asarray(geom["area_vertices"], dtype=np.float64)
+    area_t = np.asarray(geom["area_triangles"], dtype=np.float64)
+    return [
+        {
+            "mu": cp["mu"] * (area_v[np.newaxis, :] / 3.0),
+            "E": cp["E"] * area_t[np.newaxis, :, np.newaxis],
+            "iteration": cp["iteration"], "time": cp["time"], "kkt": cp["kkt"],
+        }
+        for cp in checkpoints
+    ]
 
 
 def _geometry_with_areas(geometry):
@@ -47,10 +58,44 @@ def _geometry_with_areas(geometry):
     return g
 
 
-def solver_raw(n_time, geometry, **kwargs):
+def _read_out_spec(readout, centred):
+    if readout not in ("device", "host"):
+        raise ValueError("readout must be 'device' or 'host'")
+    return {"dot_units": True, "centred": centred} if readout == "device" else None
+
+
+def _from_device(solution, geom):
+    """The plug-in's dict from a solution that was read out on the device: ``mu`` and ``E`` are final, the checkpoints (in the
+    solver's units) are converted as ever."""
+    out = {"mu": solution["mu"], "E": solution["E"]}
+    if solution.get("checkpoints"):
+        out["checkpoints"] = _checkpoints_to_dot(solution["checkpoints"], geom)
+    return out
+
+
+def _finish(solution, geometry, mu0, mu1, readout, centred):
+    """What a plug-in returns from what its solver returned."""
+    g = _geometry_with_areas(geometry)
+    if readout == "device":
+        solution_dot = _from_device(solution, g)
+    else:
+        solution_dot = _socp_to_dot(solution, g)
+        if centred:
+            _to_time_centered(solution_dot, mu0, mu1)
+    if centred:
+        for cp in solution_dot.get("checkpoints") or []:
+            _to_time_centered(cp, mu0, mu1)
+    return solution_dot
+
+
+def _end_points(geometry):
+    return np.asarray(geometry["mu0"], dtype=np.float64), np.asarray(geometry["mu1"], dtype=np.float64)
+
+
+def solver_raw(n_time, geometry, readout="device", **kwargs):
     """Solve the DOT problem with the GPU SOCP solver; solution on the time-staggered grid."""
-    solution_socp, run_history = solver_socp(n_time, geometry, **kwargs)
-    return _socp_to_dot(solution_socp, _geometry_with_areas(geometry)), run_history
+    solution_socp, run_history = solver_socp(n_time, geometry, read_out=_read_out_spec(readout, False), **kwargs)
+    return _finish(solution_socp, geometry, None, None, readout, False), run_history
 
 
 solver_raw.__name__ = "dot_solver_socp"
@@ -61,56 +106,47 @@ def _to_time_centered(solution_dot, mu0, mu1):
     solution_dot["mu"] = np.concatenate([mu0[None, :], mid, mu1[None, :]], axis=0)
 
 
-def solver(n_time, geometry, **kwargs):
+def solver(n_time, geometry, readout="device", **kwargs):
     """``solver_raw`` with the density moved to the time-centred grid and mu0 / mu1 as end points."""
-    mu0 = np.asarray(geometry["mu0"], dtype=np.float64)
-    mu1 = np.asarray(geometry["mu1"], dtype=np.float64)
-    solution_dot, run_history = solver_raw(n_time, geometry, **kwargs)
-    _to_time_centered(solution_dot, mu0, mu1)
-    for cp in solution_dot.get("checkpoints") or []:
-        _to_time_centered(cp, mu0, mu1)
-    return solution_dot, run_history
+    mu0, mu1 = _end_points(geometry)
+    solution_socp, run_history = solver_socp(n_time, geometry, read_out=_read_out_spec(readout, True), **kwargs)
+    return _finish(solution_socp, geometry, mu0, mu1, readout, True), run_history
 
 
 solver.__name__ = "dot_solver_socp_center"
 
 
-def solver_raw_cascade(n_time, geometry, **kwargs):
+def solver_raw_cascade(n_time, geometry, readout="device", **kwargs):
     """``solver_raw`` through the time cascade (``solver_socp_cascade``: ``levels``, ``level_tol`` and the keywords of ``solver_socp``)."""
-    solution_socp, run_history = solver_socp_cascade(n_time, geometry, **kwargs)
-    return _socp_to_dot(solution_socp, _geometry_with_areas(geometry)), run_history
+    solution_socp, run_history = solver_socp_cascade(n_time, geometry, read_out=_read_out_spec(readout, False), **kwargs)
+    return _finish(solution_socp, geometry, None, None, readout, False), run_history
 
 
 solver_raw_cascade.__name__ = "dot_solver_socp_cascade"
 
 
-def solver_cascade(n_time, geometry, **kwargs):
+def solver_cascade(n_time, geometry, readout="device", **kwargs):
     """``solver`` through the time cascade: the density on the time-centred grid with mu0 / mu1 as end points."""
-    mu0 = np.asarray(geometry["mu0"], dtype=np.float64)
-    mu1 = np.asarray(geometry["mu1"], dtype=np.float64)
-    solution_dot, run_history = solver_raw_cascade(n_time, geometry, **kwargs)
-    _to_time_centered(solution_dot, mu0, mu1)
-    for cp in solution_dot.get("checkpoints") or []:
-        _to_time_centered(cp, mu0, mu1)
-    return solution_dot, run_history
+    mu0, mu1 = _end_points(geometry)
+    solution_socp, run_history = solver_socp_cascade(n_time, geometry, read_out=_read_out_spec(readout, True), **kwargs)
+    return _finish(solution_socp, geometry, mu0, mu1, readout, True), run_history
 
 
 solver_cascade.__name__ = "dot_solver_socp_cascade_center"
 
 
-def solver_raw_many(n_time, geometry, problems, **kwargs):
+def solver_raw_many(n_time, geometry, problems, readout="device", **kwargs):
     """``solver_raw`` for several problems on one surface (``solver_socp_many``): a list of ``(solution, run_history)``."""
-    g = _geometry_with_areas(geometry)
-    return [(_socp_to_dot(sol, g), hist) for sol, hist in solver_socp_many(n_time, geometry, problems, **kwargs)]
+    results = solver_socp_many(n_time, geometry, problems, read_out=_read_out_spec(readout, False), **kwargs)
+    return [(_finish(sol, geometry, None, None, readout, False), hist) for sol, hist in results]
 
 
-def solver_many(n_time, geometry, problems, **kwargs):
+def solver_many(n_time, geometry, problems, readout="device", **kwargs):
     """``solver`` for several problems on one surface: each density on the time-centred grid with its own mu0 / mu1 as end points."""
-    out = solver_raw_many(n_time, geometry, problems, **kwargs)
-    for p, (solution_dot, _) in zip(problems, out):
+    results = solver_socp_many(n_time, geometry, problems, read_out=_read_out_spec(readout, True), **kwargs)
+    out = []
+    for p, (sol, hist) in zip(problems, results):
         mu0 = np.asarray(p.get("mu0", geometry.get("mu0")), dtype=np.float64)
         mu1 = np.asarray(p.get("mu1", geometry.get("mu1")), dtype=np.float64)
-        _to_time_centered(solution_dot, mu0, mu1)
-        for cp in solution_dot.get("checkpoints") or []:
-            _to_time_centered(cp, mu0, mu1)
+        out.append((_finish(sol, geometry, mu0, mu1, readout, True), hist))
     return out

@@ -103,6 +103,7 @@ class AlmSolver:
             if not getattr(init_from, "finalized", False):
                 raise ValueError("init_from must have been finalised (finalize(download=False) is enough)")
         self.tol_checkpoints = _validate_checkpoints(tol_checkpoints, tol)
+        self.geometry = geometry        # (read_out takes the area weights and mu0 / mu1 from it)
         self.checkpoint_solutions = []
         self.n_time, self.nit, self.tol, self.time_limit = int(n_time), int(nit), tol, time_limit
         self.is_z_scaling, self.is_constant_scaling = is_z_scaling, is_constant_scaling
@@ -366,6 +367,13 @@ class AlmSolver:
         """The whole array ``name`` in the reference layout."""
         return self.dev.download(name)
 
+    def _read_out(self, factor, w_vertex=None, w_triangle=None, centred=False, mu0=None, mu1=None, sums=False):
+        """``(mu, E, info)`` of the current iterate, formed on the device (DeviceProblem.readout; readout.read_out_host is the
+        specification) -- one call, and only these two arrays cross to the host; ``info``: layer sums, device ms and bytes."""
+        dev = self.dev
+        mu, E, mass, neg = dev.readout(factor, w_vertex, w_triangle, centred, mu0, mu1, sums=sums)
+        return mu, E, {"layer_mass": mass, "layer_negative": neg, "ms": dev.readout_ms, "bytes": dev.readout_bytes}
+
     def _device_step(self, quiet=False):
         """Steps 1-3 on the device; the multi-GPU solver overrides this with begin / all-gather / end.
 
@@ -512,9 +520,10 @@ class AlmSolver:
 
         cps = self.tol_checkpoints
         if cps and error is not None and error <= cps[0]:                      # :790-801
+            cp_mu, cp_E, _ = self._read_out(self.r * self.dual_scale)
             self.checkpoint_solutions.append({
-                "mu": (self.r * self.dual_scale) * self._download("mu"),
-                "E": (self.r * self.dual_scale) * self._download("E"),
+                "mu": cp_mu,
+                "E": cp_E,
                 "iteration": it, "time": hist.get_running_time(), "kkt": np.array(org, dtype=object),
             })
             cps.pop(0)
@@ -541,7 +550,30 @@ class AlmSolver:
         return self.finished
 
     # ---- final record and solution (:826-871) ------------------------------------------------
-    def finalize(self, download=True):
+    def read_out(self, dot_units=True, centred=True):
+        """``({"mu", "E"}, info)``: the recovered ``mu`` and ``E`` (solver_socp.py:397-405) through the read-out --
+        ``dot_units``: as masses and fluxes (times area_v / 3 and area_t of ``geometry``: socp._socp_to_dot); ``centred``: ``mu`` on
+        the time-centred grid with ``geometry``'s mu0 / mu1 as end points (socp._to_time_centered).  ``info``: the sum of every
+        layer of that ``mu`` and of its negative entries, device milliseconds and bytes copied."""
+        w_vertex = w_triangle = mu0 = mu1 = None
+        if dot_units:
+            from . import _geometry_with_areas
+
+            g = _geometry_with_areas(self.geometry)
+            w_vertex = np.asarray(g["area_vertices"], dtype=np.float64) / 3.0
+            w_triangle = np.asarray(g["area_triangles"], dtype=np.float64)
+        if centred:
+            mu0 = np.asarray(self.geometry["mu0"], dtype=np.float64)
+            mu1 = np.asarray(self.geometry["mu1"], dtype=np.float64)
+        mu, E, info = self._read_out(self.r * self.dual_scale, w_vertex, w_triangle, centred, mu0, mu1, sums=True)
+        return {"mu": mu, "E": E}, info
+
+    def finalize(self, download=True, outputs=None, read_out=None):
+        """``outputs``: None = the twelve arrays, or a tuple of names: only those are downloaded.  ``read_out``: None, or the
+        keywords of ``read_out`` (dot_units, centred): the solution is then its ``{"mu", "E"}`` -- nothing else is downloaded --
+        and ``run_history.solver_stats["readout"]`` its info."""
+        if read_out is not None and outputs is not None:
+            raise ValueError("finalize: outputs and read_out are mutually exclusive (read_out returns mu and E only)")
         dev, hist, validator = self.dev, self.run_history, self.kkt_validator
         self._kkt_prefetch(range(7))
         validator.validator.validate(list(range(7)))
@@ -561,8 +593,14 @@ class AlmSolver:
         if self.cg_fail:
             logger.warning("PCG hit its iteration cap in %d solves", self.cg_fail)
         solution = {}
-        if download:
-            solution = {name: self.recovered(name, self._download(name)) for name in STATE_NAMES}
+        if read_out is not None:
+            solution, hist.solver_stats["readout"] = self.read_out(**read_out)
+        elif download:
+            names = STATE_NAMES if outputs is None else tuple(outputs)
+            unknown = set(names) - set(STATE_NAMES)
+            if unknown:
+                raise ValueError(f"finalize: unknown outputs {sorted(unknown)}")
+            solution = {name: self.recovered(name, self._download(name)) for name in names}
         solution["checkpoints"] = self.checkpoint_solutions if self.checkpoint_solutions else None
         logger.info("Number of iterations: %d   Iteration time: %.2f", self.counter_main, hist.running_time)
         return solution, hist
@@ -596,6 +634,8 @@ def solver_socp(
         preconditioner="multigrid",
         mg_coarsest=256,
         nd_leaf=16,
+        outputs=None,
+        read_out=None,
 ):
     """SOCP for dynamical optimal transport on a discrete surface, on the GPU.
 
@@ -603,7 +643,12 @@ def solver_socp(
     ``SolutionSocpData`` (reference layouts, un-scaled as at solver_socp.py:397-405) plus
     ``checkpoints``; ``run_history`` is a :class:`RunningHistory`.
     ``is_multi_threads`` is accepted and ignored (the GPU path has no host threads to split).
+    ``outputs``: a tuple of array names: ``solution`` holds only those (and ``checkpoints``), and only those are downloaded.
+    ``read_out``: the keywords of ``AlmSolver.read_out`` (dot_units, centred): ``solution`` is ``mu`` and ``E`` as the solver
+    plug-ins return them, formed on the device (``checkpoints`` stay in the solver's units).
     """
+    if read_out is not None and outputs is not None:
+        raise ValueError("solver_socp: outputs and read_out are mutually exclusive (read_out returns mu and E only)")
     alm = AlmSolver(n_time, geometry, congestion=congestion, nit=nit, eps=eps, tol=tol, tau=tau, is_z_scaling=is_z_scaling,
                     is_constant_scaling=is_constant_scaling, check_kkt_step_by_step=check_kkt_step_by_step,
                     init_solution=init_solution, tol_checkpoints=tol_checkpoints, time_limit=time_limit, is_palm=is_palm,
@@ -613,7 +658,7 @@ def solver_socp(
         for _ in range(nit):
             if alm.iterate():
                 break
-        return alm.finalize()
+        return alm.finalize(outputs=outputs, read_out=read_out)
     finally:
         alm.close()
 
@@ -660,7 +705,7 @@ def _batch_problems(geometry, problems, common):
     return out
 
 
-def solver_socp_many(n_time, geometry, problems, *, max_batch=4, **common):
+def solver_socp_many(n_time, geometry, problems, *, max_batch=4, read_out=None, **common):
     """Solve several transport problems on ONE surface with one factor of the direct solver.
 
     ``geometry`` holds the mesh (``vertices``, ``triangles``; ``mu0`` / ``mu1`` are defaults for problems without their own);
@@ -673,7 +718,7 @@ def solver_socp_many(n_time, geometry, problems, *, max_batch=4, **common):
     Returns ``[(solution, run_history), ...]`` in input order, each what ``solver_socp(n_time, {**geometry, "mu0": ..., "mu1": ...},
     **common, **problem)`` returns, bit for bit; ``run_history.solver_stats["batch"]`` = {"size", "index", "max_batch", "steps_time_note"}.
     Each problem's running time and time limit start when it is admitted.  A factor that does not fit raises the library's memory error
-    (there is no batched PCG)."""
+    (there is no batched PCG).  ``read_out``: as for ``solver_socp``, for every problem (with its own mu0 / mu1)."""
     from .. import geometry as geo
     from ..device import step_many
 
@@ -734,7 +779,7 @@ def solver_socp_many(n_time, geometry, problems, *, max_batch=4, **common):
             still = []
             for i, alm in active:
                 if alm.finished:
-                    sol, hist = alm.finalize()
+                    sol, hist = alm.finalize(read_out=read_out)
                     hist.solver_stats["batch"] = {"size": len(probs), "index": i, "max_batch": int(max_batch), "steps_time_note": BATCH_TIME_NOTE}
                     results[i] = (sol, hist)
                     done.append((i, alm))
@@ -797,7 +842,7 @@ def _cascade_options(n_time, levels, level_tol, kwargs):
     return levels, level_tol, opts
 
 
-def solver_socp_cascade(n_time, geometry, levels=None, level_tol=None, **kwargs):
+def solver_socp_cascade(n_time, geometry, levels=None, level_tol=None, read_out=None, **kwargs):
     """``solver_socp`` through a coarse-to-fine cascade in time: the problem is solved on the time grids ``levels`` (``n_time`` values,
     increasing, the last one ``n_time``) one after the other, each level warm-started from the recovered solution of the one before,
     interpolated linearly in time on the device (AlmSolver ``init_from``; cascade.prolong_time is the specification).  The number of
@@ -812,7 +857,8 @@ def solver_socp_cascade(n_time, geometry, levels=None, level_tol=None, **kwargs)
 
     Returns ``(solution, run_history)`` of the finest level; ``run_history.running_time`` is that level's own, and
     ``run_history.solver_stats["cascade"]`` = {"levels": [one record per level: n_time, tol, iterations, running_time, setup_seconds,
-    prolong_ms (device events; None on the coarsest level), cost, kkt_max], "total_seconds"} has the whole cascade."""
+    prolong_ms (device events; None on the coarsest level), cost, kkt_max], "total_seconds"} has the whole cascade.
+    ``read_out``: as for ``solver_socp``, for the finest level."""
     from .. import geometry as geo
 
     levels, level_tol, opts = _cascade_options(n_time, levels, level_tol, kwargs)
@@ -840,7 +886,7 @@ def solver_socp_cascade(n_time, geometry, levels=None, level_tol=None, **kwargs)
             for _ in range(nit):
                 if alm.iterate():
                     break
-            solution, hist = alm.finalize(download=last)
+            solution, hist = alm.finalize(download=last, read_out=read_out if last else None)
             records.append({"n_time": int(T), "tol": float(alm.tol), "iterations": int(alm.counter_main) + 1, "running_time": float(hist.running_time),
                             "setup_seconds": float(setup), "prolong_ms": alm.prolong_ms, "cost": float(hist.history["Transportation cost"][-1]),
                             "kkt_max": float(np.nanmax(np.asarray(hist.kkt_errors[-1], dtype=np.float64)))})

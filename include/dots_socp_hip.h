@@ -521,6 +521,38 @@ typedef struct dots_prolong_desc {
 } dots_prolong_desc;
 int dots_prolong_time(dots_ctx *dst, dots_ctx *src, const dots_prolong_desc *desc);
 
+/* ---- read-out of the transport: what the solver plug-ins return (mu, E), formed on the device ---------------------------------
+ * dots_readout delivers mu and / or E as dots_download would (reference layouts, the caller's numbering), every value multiplied
+ * first by `factor` (the recovered solution, solver_socp.py:397-405: r * dual_scale; 1 = the iterate) and then, where weights are
+ * given, by the weight of its vertex / triangle (translate_solution_socp_to_dot, utils/type.py:48-65: area_v / 3 and area_t) --
+ * these operations in this order, so that the result equals the host's bit for bit (dots_socp_amd/readout.py: read_out_host).
+ * centred: mu on the time-centred grid (socp/solver_decorator.py:29-54): T + 1 layers, mu0, 0.5 * (a_l-1 + a_l) for l = 1 .. T - 1
+ * of the T weighted layers a, mu1.  layer_mass / layer_negative: the sum over the vertices of every layer of mu as written, and of
+ * its negative entries (utils/evaluate_solution.py:7-45), formed on the device in a fixed order (the same run to run); they may be
+ * asked for without mu.  Only what is asked for crosses to the host.
+ * A pending penalty division is carried out first, as for a download; z_mid is neither needed nor produced (the call succeeds after
+ * a DOTS_STEP_SKIP_Z_MID step); the state, carried sums, fused KKT sums and a launch ahead are left as they are.  Works on contexts
+ * of every Laplacian solver and on members of a batch (on their own stream).
+ * The outputs are formed in the context's staging buffer (18 F pitch doubles, the size of z_mid) together with the weights, end
+ * points and partial sums: (T + 1) 3 F + (T + 1) V + 3 V + F + 2 (T + 1) V / 30 doubles must fit, which holds for every mesh with
+ * fewer than about 14 vertices per triangle (a closed surface has 1 / 2).
+ * DOTS_ERR_ARGUMENT: NULL desc, centred without mu0 / mu1 (whatever is asked for), nothing asked for; DOTS_ERR_STATE: a time slab,
+ * a mesh whose outputs do not fit the staging buffer (dots_download still works). */
+typedef struct dots_readout_desc {
+    double factor;              /* first multiplier of every value (r * dual_scale for the recovered mu, E; 1 = the iterate) */
+    const double *w_vertex;     /* host [V], caller numbering, or NULL: second multiplier of mu (area_v / 3) */
+    const double *w_triangle;   /* host [F] or NULL: second multiplier of E (area_t) */
+    int32_t centred;            /* 0: mu as stored, T layers; 1: T + 1 layers mu0, 0.5 (a_l + a_l+1), mu1 */
+    int32_t reserved;
+    const double *mu0, *mu1;    /* host [V], caller numbering; required when centred */
+    double *mu;                 /* host out [layers][V], or NULL */
+    double *E;                  /* host out [T+1][F][3], or NULL */
+    double *layer_mass;         /* host out [layers] or NULL: sum over v of the layer as written */
+    double *layer_negative;     /* host out [layers] or NULL: sum of its negative entries */
+    double *ms;                 /* NULL, or out: device milliseconds of the launches */
+} dots_readout_desc;
+int dots_readout(dots_ctx *ctx, const dots_readout_desc *desc);
+
 /* launches one direct solve takes: 2 x bands of tree heights (one per band and sweep; a band is one height unless
  * dots_front_desc.band_ptr merges heights), minus one with dots_front_desc.top_inverse */
 int dots_front_launches(dots_ctx *ctx);
@@ -547,7 +579,9 @@ int dots_bench_kernel(dots_ctx *ctx, int which, int reps, double *ms_per_launch,
  * beta_mid with the non-temporal hint (decided by dots_front_setup from the sizes of factor and state), 7 sweep launches the last
  * batched solve (dots_laplacian_solve_many, dots_step_many, dots_bench_many) enqueued, read on the batch's first context, 8 of those, the
  * launches that took fewer right-hand sides than their chunk of DOTS_FRONT_NR problems held because NR regions of LDS would not fit or
- * a workgroup of 1024 threads takes fewer (the launch was split); -1 for an unknown counter */
+ * a workgroup of 1024 threads takes fewer (the launch was split), 9 bytes this context has copied device -> host through dots_download
+ * and dots_readout since it was created (the layer sums of dots_readout are written by the device itself and not copied); -1 for an
+ * unknown counter */
 int64_t dots_debug_counter(dots_ctx *ctx, int which);
 
 /* device memory in use by the context, bytes */
