@@ -577,7 +577,7 @@ int dots_create(const dots_problem_desc *desc, dots_ctx **out) {
         ok &= env_int("DOTS_KKT_TWO", 0, 1, &c->kkt_two);
         ok &= env_int("DOTS_ZMID_DEFER", 0, 1, &c->zmid_defer);    // 0: read-back iterations store z_mid as before
         ok &= env_int("DOTS_LAZY_DIV", 0, 1, &c->lazy_div);        // 0: a penalty update divides the dual arrays at once
-        ok &= env_int("DOTS_FRONT_VEC2", 0, 1, &c->front_vec2);      // 0: one mode per lane in the sweeps everywhere
+        ok &= env_int("DOTS_FRONT_VEC2", 0, 1, &c->sched.vec2);      // 0: one mode per lane in the sweeps everywhere
         ok &= env_int("DOTS_FRONT_ROWS", 0, 2, &c->front_rows);      // 0: the fold kernels everywhere, 1: row kernels where the rules say (default), 2: wherever they fit
         ok &= env_int("DOTS_FRONT_LEAFINV", 0, 2, &c->front_leafinv);
         ok &= env_int("DOTS_FRONT_TUNE", 0, 2, &c->front_tune);
@@ -1203,8 +1203,8 @@ int dots_front_setup(dots_ctx *c, const dots_front_desc *desc) {
         const double touched = 33.0 * F8 + 12.0 * V8;      // beta_mid, B, E, the carried sums; the vertex arrays
         int nt = -1;
         if (!env_int("DOTS_BM_NT", 0, 1, &nt)) { front_release(c); return DOTS_ERR_ARGUMENT; }
-        const double factor = 0.5 * c->front_bytes;      // what the sweeps touch: every block is read by both sweeps (the zero blocks of merged nodes are never read)
-        c->bm_nt = nt >= 0 ? nt : (factor < 0.9e9 && factor + touched > mall ? 1 : 0);
+        const double factor = 0.5 * c->sched.bytes;      // what the sweeps touch: every block is read by both sweeps (the zero blocks of merged nodes are never read)
+        c->sched.bm_nt = nt >= 0 ? nt : (factor < 0.9e9 && factor + touched > mall ? 1 : 0);
     }
     return front_carry_alloc(c);
 }
@@ -1222,7 +1222,7 @@ int dots_front_share(dots_ctx *c, dots_ctx *owner) {
     if (c->device != owner->device) snprintf(buf, sizeof buf, "device %d, the owner's %d", c->device, owner->device);
     else if (a.V != b.V || a.F != b.F || a.T != b.T) snprintf(buf, sizeof buf, "V, F, T = %d, %d, %d, the owner's %d, %d, %d", a.V, a.F, a.T, b.V, b.F, b.T);
     else if (c->nnz != owner->nnz) snprintf(buf, sizeof buf, "%d Laplacian entries, the owner's %d", c->nnz, owner->nnz);
-    else if (c->prm.eps != owner->front_eps) snprintf(buf, sizeof buf, "eps %.17g, the owner's factor was built with %.17g", c->prm.eps, owner->front_eps);
+    else if (c->prm.eps != owner->sched.eps) snprintf(buf, sizeof buf, "eps %.17g, the owner's factor was built with %.17g", c->prm.eps, owner->sched.eps);
     else if (c->dcg.TP != owner->dcg.TP || c->dcg.cg_ncol != owner->dcg.cg_ncol) snprintf(buf, sizeof buf, "mode pitch %d, the owner's %d", c->dcg.TP, owner->dcg.TP);
     else if (c->lap_hash != owner->lap_hash) snprintf(buf, sizeof buf, "another mesh or vertex numbering (the Laplacian or the vertex masses differ)");
     if (buf[0]) { set_error(std::string("front_share: the factor does not fit this context: ") + buf); return DOTS_ERR_ARGUMENT; }
@@ -1244,26 +1244,10 @@ int dots_front_share(dots_ctx *c, dots_ctx *owner) {
     front_release(c);
     c->front = owner->front;
     c->front.W = nullptr;
-    std::copy(std::begin(owner->front_fwd_ptr), std::end(owner->front_fwd_ptr), std::begin(c->front_fwd_ptr));
-    std::copy(std::begin(owner->front_bwd_ptr), std::end(owner->front_bwd_ptr), std::begin(c->front_bwd_ptr));
-    std::copy(std::begin(owner->front_fwd_rb), std::end(owner->front_fwd_rb), std::begin(c->front_fwd_rb));
-    std::copy(std::begin(owner->front_bwd_cb), std::end(owner->front_bwd_cb), std::begin(c->front_bwd_cb));
-    std::copy(std::begin(owner->front_fwd_nb), std::end(owner->front_fwd_nb), std::begin(c->front_fwd_nb));
-    std::copy(std::begin(owner->front_bwd_nb), std::end(owner->front_bwd_nb), std::begin(c->front_bwd_nb));
-    std::copy(std::begin(owner->front_fwd_qw), std::end(owner->front_fwd_qw), std::begin(c->front_fwd_qw));
-    std::copy(std::begin(owner->front_fwd_lds), std::end(owner->front_fwd_lds), std::begin(c->front_fwd_lds));
-    std::copy(std::begin(owner->front_planes), std::end(owner->front_planes), std::begin(c->front_planes));
-    c->front_vec2 = owner->front_vec2;
-    c->front_bytes = owner->front_bytes;
-    c->front_bytes_unmerged = owner->front_bytes_unmerged;
-    c->front_heights = owner->front_heights;
-    c->front_top_inverse = owner->front_top_inverse;
-    c->front_eps = owner->front_eps;
-    c->bm_nt = owner->bm_nt;
+    c->sched = owner->sched;
     const double *w = nullptr;
-    if ((rc = front_upload<double>(c, &w, nullptr, owner->front_w_rows << c->dcg.tp_shift))) { front_release(c); return rc; }
+    if ((rc = front_upload<double>(c, &w, nullptr, owner->sched.w_rows << c->dcg.tp_shift))) { front_release(c); return rc; }
     c->front.W = const_cast<double *>(w);
-    c->front_w_rows = owner->front_w_rows;
     c->front_store = owner->front_store;
     c->use_front = 1;
     return front_carry_alloc(c);
@@ -1648,17 +1632,17 @@ int dots_front_enable(dots_ctx *c, int on) {
 
 int dots_front_launches(dots_ctx *c) {
     if (check(c) || c->front.n_nodes == 0) return -1;
-    return 2 * c->front.n_levels - (c->front_top_inverse ? 1 : 0);
+    return 2 * c->sched.n_bands - (c->sched.top_inverse ? 1 : 0);
 }
 
 int dots_front_info(dots_ctx *c, double *out) {
     int rc = check(c);
     if (rc) return rc;
     if (!out || c->front.n_nodes == 0) { set_error("front_info: no factor installed"); return DOTS_ERR_STATE; }
-    out[0] = c->front_bytes_unmerged;
-    out[1] = c->front_bytes;
-    out[2] = (double)c->front_heights;
-    out[3] = (double)c->front.n_levels;
+    out[0] = c->sched.bytes_unmerged;
+    out[1] = c->sched.bytes;
+    out[2] = (double)c->sched.heights;
+    out[3] = (double)c->sched.n_bands;
     return 0;
 }
 
@@ -1676,7 +1660,7 @@ int64_t dots_debug_counter(dots_ctx *c, int which) {
         case 3: return c->penalty_ahead_confirmed;
         case 4: return c->front.n_leaves;      // leaves the sweeps handle as explicit local inverses (0: band kernels)
         case 5: return c->front.leaf_bd ? 1 : 0;      // ... with their coupling in per-row records (0: read from the CSR)
-        case 6: return c->bm_nt;                      // beta_mid streamed around the caches by steps 2+3 (the rule of dots_front_setup, or DOTS_BM_NT)
+        case 6: return c->sched.bm_nt;                      // beta_mid streamed around the caches by steps 2+3 (the rule of dots_front_setup, or DOTS_BM_NT)
         case 7: return c->front_many_launches;        // sweep launches the last front_solve_many on this (first) context enqueued
         case 8: return c->front_many_split;           // ... of those, launches with fewer rhs than their chunk (many_launch halved: LDS or 1024-thread cap)
         case 9: return c->d2h_bytes;                  // bytes dots_download and dots_readout have copied device -> host

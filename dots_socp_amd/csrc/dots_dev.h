@@ -21,6 +21,7 @@
 #include <stdint.h>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/dots_socp_hip.h"
@@ -41,6 +42,15 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line);
         hipError_t e__ = (call);                                              \
         if (e__ != hipSuccess) return ::dots::hip_fail(e__, #call, __FILE__, __LINE__); \
     } while (0)
+
+// A run-time choice as a template argument: fn(std::integral_constant<T, V>{}) for the listed V that equals v (the last one when none does)
+template <auto V, auto... Vs, typename Fn>
+inline void with_constant(decltype(V) v, Fn &&fn) {
+    if constexpr (sizeof...(Vs) > 0) {
+        if (v != V) return with_constant<Vs...>(v, fn);
+    }
+    fn(std::integral_constant<decltype(V), V>{});
+}
 
 // Everything a kernel needs, passed by value.
 struct Dev {
@@ -208,6 +218,31 @@ struct FrontDev {
     int n_leaves = 0, leaf_nmax = 0;      // leaves handled by the leaf kernels (0: the band kernels take band 0), their largest n
 };
 
+// What installing a factor decided about the sweeps (front_setup; dots_front_share copies it whole): one record per band = launch of a sweep
+struct FrontBand {
+    int fwd_first, fwd_n;     // its workgroups in fwd_desc
+    int bwd_first, bwd_n;     // ... in bwd_desc
+    int fwd_rb, bwd_cb;       // rows / columns per workgroup
+    int fwd_nb, bwd_nb;       // threads per workgroup (256, or 1024 where a band has few rows)
+    int fwd_qw;               // forward launch: -1 the fold kernel (k_front_fwd), >= 0 the row kernel with 2^qw lane groups per row
+    int fwd_lds;              // row kernel: columns of w a workgroup stages in LDS (the band's longest block)
+    int planes;               // update planes the forward launch reads per node (0, 2, 4 or 8)
+};
+struct FrontSchedule {
+    static constexpr int MAX_BANDS = 64;
+    int vec2 = 1;             // two modes per lane in the sweeps wherever the pitch allows (DOTS_FRONT_VEC2=0: never); the one field front_release keeps
+    int n_bands = 0;          // launches per sweep (= FrontDev::n_levels)
+    int top_inverse = 0;      // the top band holds explicit inverses: its forward launch writes x, the backward sweep skips it
+    int heights = 0;          // tree heights of the installed factor
+    int bm_nt = 0;            // steps 2+3 stream beta_mid with the non-temporal hint (decided by dots_front_setup: see ql2_lane; DOTS_BM_NT = 0 / 1 overrides)
+    int64_t w_rows = 0;       // rows of W (the sharers allocate as many)
+    double bytes = 0.0;       // factor bytes one solve reads (both sweeps, merged blocks as stored)
+    double bytes_unmerged = 0.0;   // the same for one launch per tree height (no merged bands)
+    double eps = 0.0;         // eps the installed factor was built with
+    FrontBand band[MAX_BANDS]{};
+};
+static_assert(std::is_trivially_copyable<FrontSchedule>::value, "Ctx is copied by value (dots_apply_operator, dots_laplacian_solve_many)");
+
 // Layout of the device scalar block used by the PCG (all arrays have NC entries, NC <= 256).
 struct CgScalOffsets {
     static constexpr int NCMAX = 256;
@@ -368,7 +403,6 @@ struct Ctx {
     // reference).  Every other entry point that reads or writes those arrays first carries the division out (flush_division).
     double pending_div = 0.0;     // 0: none
     int lazy_div = 1;             // DOTS_LAZY_DIV=0: divide at once (A/B measurements)
-    int bm_nt = 0;                // steps 2+3 stream beta_mid with the non-temporal hint (decided by dots_front_setup: see ql2_lane; DOTS_BM_NT = 0 / 1 overrides)
     int step_kkt = 0;             // dots_step_flags: steps 2+3 also form the KKT sums they hold in registers (kkt_fused)
     KktFused kkt_fused{};         // their per-workgroup partial sums (own buffer: d.partials serves the other reductions)
     int64_t kkt_fused_cap_v = 0, kkt_fused_cap_f = 0;   // workgroups the buffers hold per slot
@@ -386,13 +420,7 @@ struct Ctx {
     int zmid_defer = 1;           // DOTS_ZMID_DEFER=0: store z_mid on those iterations as before (A/B measurements)
     FrontDev front{};             // multifrontal factor (n_nodes == 0: none)
     int use_front = 0;
-    int front_fwd_ptr[66]{}, front_bwd_ptr[66]{};   // workgroup ranges of the tree levels in fwd_desc / bwd_desc
-    int front_fwd_rb[65]{}, front_bwd_cb[65]{};     // rows / columns per workgroup on each level
-    int front_fwd_nb[65]{}, front_bwd_nb[65]{};     // threads per workgroup on each level (256, or 1024 where a level has few rows)
-    int front_fwd_qw[65]{};       // forward launch of a band: -1 the fold kernel (k_front_fwd), >= 0 the row kernel with 2^qw lane groups per row
-    int front_fwd_lds[65]{};      // row kernel: columns of w a workgroup stages in LDS (the band's longest block)
-    int front_planes[65]{};       // update planes the forward launch of a band reads per node (0, 2, 4 or 8)
-    int front_vec2 = 1;           // two modes per lane in the sweeps wherever the pitch allows (DOTS_FRONT_VEC2=0: never)
+    FrontSchedule sched{};        // what its installation decided about the sweeps
     int rhs_ahead_armed = 0;      // DOTS_STEP_RHS_AHEAD: the next KKT launch is followed by the next iteration's right-hand side
     int rhs_ahead = 0;            // ... which is on the stream and still valid (any call that changes state or parameters clears it); 2: with the
                                   // cone projection, whose results (z_fst, z_end, the cone multiplier) wait in the alternate buffers below
@@ -404,18 +432,12 @@ struct Ctx {
     int64_t penalty_ahead_started = 0, penalty_ahead_confirmed = 0;   // diagnostics (dots_debug_counter 2, 3)
     double ahead_div = 0.0;       // rhs_ahead == 2: the division the launch ahead applied as it read (steps 2+3 of the step that takes it must apply the same)
     double *zf_alt = nullptr, *ze_alt = nullptr, *lamc_alt = nullptr;   // [V][TP] each (one GPU): written ahead, swapped in by the step that takes them
-    double front_bytes = 0.0;     // factor bytes one solve reads (both sweeps, merged blocks as stored)
-    double front_bytes_unmerged = 0.0;   // the same for one launch per tree height (no merged bands)
-    int front_heights = 0;        // tree heights of the installed factor
-    int front_top_inverse = 0;    // the top band holds explicit inverses: its forward launch writes x, the backward sweep skips it
     void *front_allocs[48]{};
     int n_front_allocs = 0;
     // Factor shared by several contexts (dots_front_share): the allocations every sharer reads (factor, descriptors, maps, leaf records)
     // move from front_allocs into one reference-counted store, freed with its last holder; W (update planes) and the carried gathers stay
     // per context, in front_allocs
     std::shared_ptr<FrontStore> front_store;
-    int64_t front_w_rows = 0;     // rows of W (the sharers allocate as many)
-    double front_eps = 0.0;       // eps the installed factor was built with
     int front_nr_max = 4;         // right-hand sides per launch of front_solve_many (DOTS_FRONT_NR: 2, 4 or 8)
     hipEvent_t ev_batch = nullptr;   // orders this context's stream against the others of a batched solve (created on first use)
     int front_cap_fault = 0;      // a multi-rhs launch was asked for more right-hand sides than its workgroup shape takes (front_solve_many reports it)

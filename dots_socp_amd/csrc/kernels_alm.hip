@@ -545,37 +545,34 @@ bool rhs_divides(const Ctx *c) {
 }
 
 int launch_rhs(Ctx *c, bool with_soc, double dv) {
-    const int g = xcd_grid(c->d.n_vtiles);
-    if (rhs_writes_modes(c) && time_modes_mfma_ok(c->d)) {      // (two time columns per lane measured here too: knot63 -1.5 %, torus65k_T127 +1.5 %: not kept)
-        const int n_tiles = (c->d.V + TM_ROWS - 1) / TM_ROWS, n_rhs = xcd_grid(n_tiles);
-        if (c->carry_valid)
-            hipLaunchKernelGGL(k_rhs_modes_mfma<true>, dim3(n_rhs + (with_soc ? g : 0)), dim3(RHS_NB), sizeof(double) * TM_ROWS * (c->d.TP + 1), c->stream, c->d,
-                               c->prm.r / c->prm.boundary_scale, c->prm.eps, c->d.cg_p0, n_rhs, n_tiles, c->prm.scale_z, c->prm.const_d, 1.0);
-        else if (dv != 0.0)
-            hipLaunchKernelGGL((k_rhs_modes_mfma<false, true>), dim3(n_rhs + (with_soc ? g : 0)), dim3(RHS_NB), sizeof(double) * TM_ROWS * (c->d.TP + 1), c->stream, c->d,
-                               c->prm.r / c->prm.boundary_scale, c->prm.eps, c->d.cg_p0, n_rhs, n_tiles, c->prm.scale_z, c->prm.const_d, dv);
-        else
-            hipLaunchKernelGGL(k_rhs_modes_mfma<false>, dim3(n_rhs + (with_soc ? g : 0)), dim3(RHS_NB), sizeof(double) * TM_ROWS * (c->d.TP + 1), c->stream, c->d,
-                               c->prm.r / c->prm.boundary_scale, c->prm.eps, c->d.cg_p0, n_rhs, n_tiles, c->prm.scale_z, c->prm.const_d, 1.0);
+    const Dev &d = c->d;
+    const int g = xcd_grid(d.n_vtiles);
+    const double r = c->prm.r / c->prm.boundary_scale, eps = c->prm.eps, sz = c->prm.scale_z, cd = c->prm.const_d;
+    const bool modes = rhs_writes_modes(c), carried = c->carry_valid != 0;
+    // the mode kernels' variants: 0 CARRIED (the corners' shares come from the last steps-2+3 launch), 1 DIV (a penalty update is pending: the dual
+    // arrays are divided as they are read; rhs_divides told the caller this launch can), 2 neither
+    auto modes2 = [&](int variant) {      // two time columns per lane (16-byte accesses)
+        with_constant<0, 1, 2>(variant, [&](auto V) {
+            hipLaunchKernelGGL((k_rhs_modes2<V == 0, V == 1>), dim3(with_soc ? 2 * g : g), dim3(RHS_NB2), time_modes_tile_lds(d), c->stream, d, r, eps, d.cg_p0,
+                               time_modes_chunk(d), g, sz, cd, V == 1 ? dv : 1.0);
+        });
+    };
+    if (modes && time_modes_mfma_ok(d)) {      // (two time columns per lane measured here too: knot63 -1.5 %, torus65k_T127 +1.5 %: not kept)
+        const int n_tiles = (d.V + TM_ROWS - 1) / TM_ROWS, n_rhs = xcd_grid(n_tiles);
+        with_constant<0, 1, 2>(carried ? 0 : (dv != 0.0 ? 1 : 2), [&](auto V) {
+            hipLaunchKernelGGL((k_rhs_modes_mfma<V == 0, V == 1>), dim3(n_rhs + (with_soc ? g : 0)), dim3(RHS_NB), sizeof(double) * TM_ROWS * (d.TP + 1), c->stream, d, r, eps,
+                               d.cg_p0, n_rhs, n_tiles, sz, cd, V == 1 ? dv : 1.0);
+        });
     }
-    else if (rhs_writes_modes(c) && c->d.TP >= 4 && c->carry_valid)      // the corners' shares come from the last steps-2+3 launch
-        hipLaunchKernelGGL(k_rhs_modes2<true>, dim3(with_soc ? 2 * g : g), dim3(RHS_NB2), time_modes_tile_lds(c->d), c->stream, c->d, c->prm.r / c->prm.boundary_scale,
-                           c->prm.eps, c->d.cg_p0, time_modes_chunk(c->d), g, c->prm.scale_z, c->prm.const_d, 1.0);
-    else if (dv != 0.0)      // a penalty update is pending: the dual arrays are divided as they are read (rhs_divides told the caller this launch can)
-        hipLaunchKernelGGL((k_rhs_modes2<false, true>), dim3(with_soc ? 2 * g : g), dim3(RHS_NB2), time_modes_tile_lds(c->d), c->stream, c->d, c->prm.r / c->prm.boundary_scale,
-                           c->prm.eps, c->d.cg_p0, time_modes_chunk(c->d), g, c->prm.scale_z, c->prm.const_d, dv);
-    else if (rhs_writes_modes(c) && c->d.TP >= 4)      // two time columns per lane (16-byte accesses)
-        hipLaunchKernelGGL(k_rhs_modes2<false>, dim3(with_soc ? 2 * g : g), dim3(RHS_NB2), time_modes_tile_lds(c->d), c->stream, c->d, c->prm.r / c->prm.boundary_scale,
-                           c->prm.eps, c->d.cg_p0, time_modes_chunk(c->d), g, c->prm.scale_z, c->prm.const_d, 1.0);
-    else if (rhs_writes_modes(c))
-        hipLaunchKernelGGL(k_rhs_modes, dim3(with_soc ? 2 * g : g), dim3(RHS_NB), time_modes_tile_lds(c->d), c->stream, c->d, c->prm.r / c->prm.boundary_scale,
-                           c->prm.eps, c->d.cg_p0, time_modes_chunk(c->d), g, c->prm.scale_z, c->prm.const_d);
-    else if (c->carry_valid)      // (a time slab of the direct solver's iteration)
-        hipLaunchKernelGGL(k_rhs<true>, dim3(with_soc ? g + g * (TILE_ELEMS / BLOCK) : g), dim3(BLOCK), 0, c->stream, c->d, c->prm.r / c->prm.boundary_scale,
-                           c->prm.eps, g, c->prm.scale_z, c->prm.const_d);
-    else
-        hipLaunchKernelGGL(k_rhs<false>, dim3(with_soc ? g + g * (TILE_ELEMS / BLOCK) : g), dim3(BLOCK), 0, c->stream, c->d, c->prm.r / c->prm.boundary_scale,
-                           c->prm.eps, g, c->prm.scale_z, c->prm.const_d);
+    else if (modes && d.TP >= 4 && carried) modes2(0);
+    else if (dv != 0.0) modes2(1);
+    else if (modes && d.TP >= 4) modes2(2);
+    else if (modes)
+        hipLaunchKernelGGL(k_rhs_modes, dim3(with_soc ? 2 * g : g), dim3(RHS_NB), time_modes_tile_lds(d), c->stream, d, r, eps, d.cg_p0, time_modes_chunk(d), g, sz, cd);
+    else      // (carried: a time slab of the direct solver's iteration)
+        with_constant<true, false>(carried, [&](auto CARRIED) {
+            hipLaunchKernelGGL(k_rhs<CARRIED>, dim3(with_soc ? g + g * (TILE_ELEMS / BLOCK) : g), dim3(BLOCK), 0, c->stream, d, r, eps, g, sz, cd);
+        });
     DOTS_HIP(hipGetLastError());
     return 0;
 }
@@ -747,7 +744,7 @@ __global__ __launch_bounds__(BLOCK) void k_q_lambda_mult_triangle(Dev d, double 
 constexpr int CARRY_NB = 192;         // 3 wavefronts: 2 * 192 / TP rows = whole triangles for every pitch <= 128
 constexpr int CARRY_VALUES = 18;      // per lane: 3 corners x (2 halves + 1 divergence share) x 2 nodes
 // KKT: the lane also accumulates the sums of kkt_triangle_body2 that need no gather (ks[KF_N]; sz = scale_factor_z).
-// BMNT: beta_mid is loaded and stored with the non-temporal hint (Ctx::bm_nt: where the factor can live in the 256 MB Infinity Cache if the
+// BMNT: beta_mid is loaded and stored with the non-temporal hint (FrontSchedule::bm_nt: where the factor can live in the 256 MB Infinity Cache if the
 // 36 T F values of beta_mid that stream through every iteration do not displace it -- sphere10k: 5 130-5 190 -> 5 490-5 500 it/s; where
 // everything fits (knot) the hint costs 2 %, where nothing does (torus100k) it changes nothing: profiles/studies/r04_nontemporal.txt)
 template <int ZMODE, bool QONLY, bool CARRY, bool KKT = false, bool DIV = false, bool BMNT = false>
@@ -1184,22 +1181,17 @@ int launch_q_lambda_mult(Ctx *c, int zmid_mode, double dv) {
         const bool defer = zmid_mode == 1 && c->zmid_defer && c->B_alt && !c->d.slab && !c->step_palm;
         Dev dk = c->d;
         if (defer) { dk.B_st = c->B_alt; dk.bm_st = c->d.zm; }
-#define CARRY_LAUNCH(Z, K)                                                                                                                                     \
-    do {                                                                                                                                                     \
-        if (c->bm_nt) {                                                                                                                                      \
-            if (dv != 0.0) hipLaunchKernelGGL((k_q_lambda_mult_carry<Z, K, true, true>), g, dim3(CARRY_NB), 0, c->stream, dk, p.scale_z, p.tau, n_fwg, tw, cd, cr, ka, kf, dv, emit); \
-            else hipLaunchKernelGGL((k_q_lambda_mult_carry<Z, K, false, true>), g, dim3(CARRY_NB), 0, c->stream, dk, p.scale_z, p.tau, n_fwg, tw, cd, cr, ka, kf, 1.0, emit);        \
-        } else {                                                                                                                                             \
-            if (dv != 0.0) hipLaunchKernelGGL((k_q_lambda_mult_carry<Z, K, true, false>), g, dim3(CARRY_NB), 0, c->stream, dk, p.scale_z, p.tau, n_fwg, tw, cd, cr, ka, kf, dv, emit); \
-            else hipLaunchKernelGGL((k_q_lambda_mult_carry<Z, K, false, false>), g, dim3(CARRY_NB), 0, c->stream, dk, p.scale_z, p.tau, n_fwg, tw, cd, cr, ka, kf, 1.0, emit);        \
-        }                                                                                                                                                    \
-    } while (0)
-        if (zmid_mode == 2) CARRY_LAUNCH(2, false);
-        else if (defer && k) CARRY_LAUNCH(2, true);
-        else if (defer) CARRY_LAUNCH(2, false);
-        else if (k) CARRY_LAUNCH(1, true);
-        else CARRY_LAUNCH(1, false);
-#undef CARRY_LAUNCH
+        auto carry_launch = [&](int zmode, bool with_kkt) {
+            with_constant<1, 2>(zmode, [&](auto Z) { with_constant<true, false>(with_kkt, [&](auto K) { with_constant<true, false>(dv != 0.0, [&](auto DIV) {
+                with_constant<true, false>(c->sched.bm_nt != 0, [&](auto BMNT) {
+                    hipLaunchKernelGGL((k_q_lambda_mult_carry<Z, K, DIV, BMNT>), g, dim3(CARRY_NB), 0, c->stream, dk, p.scale_z, p.tau, n_fwg, tw, cd, cr, ka, kf, DIV ? dv : 1.0, emit);
+                }); }); }); });
+        };
+        if (zmid_mode == 2) carry_launch(2, false);
+        else if (defer && k) carry_launch(2, true);
+        else if (defer) carry_launch(2, false);
+        else if (k) carry_launch(1, true);
+        else carry_launch(1, false);
         DOTS_HIP(hipGetLastError());
         if (defer) {
             std::swap(c->d.B, c->B_alt);          // B_alt: the B the projection read

@@ -910,7 +910,7 @@ __global__ __launch_bounds__(256) void k_flush_read(const double *__restrict__ x
 // on wherever the pitch allows (DOTS_FRONT_VEC2=0 turns it off).
 static bool front_two_modes(const Ctx *c) {
     const Dev &d = c->dcg;
-    return c->front_vec2 && d.TP >= 4 && d.TP <= 128;
+    return c->sched.vec2 && d.TP >= 4 && d.TP <= 128;
 }
 
 // right-hand sides a workgroup of 1024 threads (128 VGPRs) takes without spilling: forward fold kernel / the others (front_solve_many splits)
@@ -922,30 +922,13 @@ static void front_launch_fwd(Ctx *c, const FrontDev &f, const FrontWork *ptr, in
     const Dev &d = c->dcg;
     const FrontArgs g = front_args(d);
     const dim3 grid(n, front_chunks(d));
-    const bool vm = f.vmap != nullptr, v2 = front_two_modes(c);
-#define FRONT_FWD4(NBV, RBV, KPV)                                                                                                  \
-    do {                                                                                                                           \
-        if (v2) {                                                                                                                  \
-            if (vm) hipLaunchKernelGGL((k_front_fwd<NBV, RBV, true, KPV, 2, NR>), grid, dim3(NBV), 0, c->stream, g, f, ptr, blk, bhat, y, mr);  \
-            else hipLaunchKernelGGL((k_front_fwd<NBV, RBV, false, KPV, 2, NR>), grid, dim3(NBV), 0, c->stream, g, f, ptr, blk, bhat, y, mr);    \
-        } else {                                                                                                                   \
-            if (vm) hipLaunchKernelGGL((k_front_fwd<NBV, RBV, true, KPV, 1, NR>), grid, dim3(NBV), 0, c->stream, g, f, ptr, blk, bhat, y, mr);  \
-            else hipLaunchKernelGGL((k_front_fwd<NBV, RBV, false, KPV, 1, NR>), grid, dim3(NBV), 0, c->stream, g, f, ptr, blk, bhat, y, mr);    \
-        }                                                                                                                          \
-    } while (0)
-#define FRONT_FWD(NBV, RBV)                                                                                                        \
-    do {                                                                                                                           \
-        if (kp == 0) FRONT_FWD4(NBV, RBV, 0);                                                                                      \
-        else if (kp == 2) FRONT_FWD4(NBV, RBV, 2);                                                                                 \
-        else if (kp == 4) FRONT_FWD4(NBV, RBV, 4);                                                                                 \
-        else FRONT_FWD4(NBV, RBV, 8);                                                                                              \
-    } while (0)
-    if (nbt == 1024) {
-        if constexpr (NR <= FRONT_NR_1024_FWD) { if (blk == 1) FRONT_FWD(1024, 1); else if (blk == 2) FRONT_FWD(1024, 2); else FRONT_FWD(1024, 4); }
-        else c->front_cap_fault = 1;      // (front_solve_many splits such launches: never reached)
-    } else { if (blk == 1) FRONT_FWD(256, 1); else if (blk == 2) FRONT_FWD(256, 2); else FRONT_FWD(256, 4); }
-#undef FRONT_FWD
-#undef FRONT_FWD4
+    with_constant<1024, 256>(nbt, [&](auto NB) {
+        if constexpr (NB == 1024 && NR > FRONT_NR_1024_FWD) c->front_cap_fault = 1;      // (front_solve_many splits such launches: never reached)
+        else with_constant<1, 2, 4>(blk, [&](auto RB) { with_constant<0, 2, 4, 8>(kp, [&](auto KP) { with_constant<true, false>(f.vmap != nullptr, [&](auto VM) {
+            with_constant<2, 1>(front_two_modes(c) ? 2 : 1, [&](auto VEC) {
+                hipLaunchKernelGGL((k_front_fwd<NB, RB, VM, KP, VEC, NR>), grid, dim3(NB), 0, c->stream, g, f, ptr, blk, bhat, y, mr);
+            }); }); }); });
+    });
 }
 
 // one band of the forward sweep with the row kernel: n workgroups of 256 threads, 2^qw_shift lane groups per row
@@ -954,23 +937,10 @@ static void front_launch_fwd_rows(Ctx *c, const FrontDev &f, const FrontWork *pt
                                   const MoreRhs<NR> &mr) {
     const Dev &d = c->dcg;
     const FrontArgs g = front_args(d);      // (a row of modes within a wavefront: one chunk)
-    const bool vm = f.vmap != nullptr, v2 = front_two_modes(c);
     const size_t lds = NR * sizeof(double) * (size_t)std::max(lds_cols, 1) * (size_t)(d.TP + FWD_ROWS_PAD);
-#define FRONT_ROWS4(KPV)                                                                                                           \
-    do {                                                                                                                           \
-        if (v2) {                                                                                                                  \
-            if (vm) hipLaunchKernelGGL((k_front_fwd_rows<true, KPV, 2, NR>), dim3(n), dim3(256), lds, c->stream, g, f, ptr, qw_shift, bhat, y, mr);  \
-            else hipLaunchKernelGGL((k_front_fwd_rows<false, KPV, 2, NR>), dim3(n), dim3(256), lds, c->stream, g, f, ptr, qw_shift, bhat, y, mr);    \
-        } else {                                                                                                                   \
-            if (vm) hipLaunchKernelGGL((k_front_fwd_rows<true, KPV, 1, NR>), dim3(n), dim3(256), lds, c->stream, g, f, ptr, qw_shift, bhat, y, mr);  \
-            else hipLaunchKernelGGL((k_front_fwd_rows<false, KPV, 1, NR>), dim3(n), dim3(256), lds, c->stream, g, f, ptr, qw_shift, bhat, y, mr);    \
-        }                                                                                                                          \
-    } while (0)
-    if (kp == 0) FRONT_ROWS4(0);
-    else if (kp == 2) FRONT_ROWS4(2);
-    else if (kp == 4) FRONT_ROWS4(4);
-    else FRONT_ROWS4(8);
-#undef FRONT_ROWS4
+    with_constant<0, 2, 4, 8>(kp, [&](auto KP) { with_constant<true, false>(f.vmap != nullptr, [&](auto VM) { with_constant<2, 1>(front_two_modes(c) ? 2 : 1, [&](auto VEC) {
+        hipLaunchKernelGGL((k_front_fwd_rows<VM, KP, VEC, NR>), dim3(n), dim3(256), lds, c->stream, g, f, ptr, qw_shift, bhat, y, mr);
+    }); }); });
 }
 
 template <int NR>
@@ -978,34 +948,21 @@ static void front_launch_bwd(Ctx *c, const FrontDev &f, const FrontWork *ptr, in
     const Dev &d = c->dcg;
     const FrontArgs g = front_args(d);
     const dim3 grid(n, front_chunks(d));
-    const bool vm = f.vmap != nullptr, v2 = front_two_modes(c);
-#define FRONT_BWD(NBV, RBV)                                                                                                        \
-    do {                                                                                                                           \
-        if (v2) {                                                                                                                  \
-            if (vm) hipLaunchKernelGGL((k_front_bwd<NBV, RBV, true, 2, NR>), grid, dim3(NBV), 0, c->stream, g, f, ptr, blk, y, x, mr);  \
-            else hipLaunchKernelGGL((k_front_bwd<NBV, RBV, false, 2, NR>), grid, dim3(NBV), 0, c->stream, g, f, ptr, blk, y, x, mr);    \
-        } else {                                                                                                                   \
-            if (vm) hipLaunchKernelGGL((k_front_bwd<NBV, RBV, true, 1, NR>), grid, dim3(NBV), 0, c->stream, g, f, ptr, blk, y, x, mr);  \
-            else hipLaunchKernelGGL((k_front_bwd<NBV, RBV, false, 1, NR>), grid, dim3(NBV), 0, c->stream, g, f, ptr, blk, y, x, mr);    \
-        }                                                                                                                          \
-    } while (0)
-    if (nbt == 1024) {
-        if constexpr (NR <= FRONT_NR_1024) { if (blk == 1) FRONT_BWD(1024, 1); else if (blk == 2) FRONT_BWD(1024, 2); else FRONT_BWD(1024, 4); }
-        else c->front_cap_fault = 1;
-    } else { if (blk == 1) FRONT_BWD(256, 1); else if (blk == 2) FRONT_BWD(256, 2); else FRONT_BWD(256, 4); }
-#undef FRONT_BWD
+    with_constant<1024, 256>(nbt, [&](auto NB) {
+        if constexpr (NB == 1024 && NR > FRONT_NR_1024) c->front_cap_fault = 1;
+        else with_constant<1, 2, 4>(blk, [&](auto RB) { with_constant<true, false>(f.vmap != nullptr, [&](auto VM) { with_constant<2, 1>(front_two_modes(c) ? 2 : 1, [&](auto VEC) {
+            hipLaunchKernelGGL((k_front_bwd<NB, RB, VM, VEC, NR>), grid, dim3(NB), 0, c->stream, g, f, ptr, blk, y, x, mr);
+        }); }); });
+    });
 }
 
 void front_release(Ctx *c) {
     for (int i = 0; i < c->n_front_allocs; ++i) (void)hipFree(c->front_allocs[i]);
     c->n_front_allocs = 0;
     c->front_store.reset();      // (a shared factor: freed with its last holder)
-    c->front_w_rows = 0;
     c->front = FrontDev{};
     c->use_front = 0;
-    c->front_bytes = c->front_bytes_unmerged = 0.0;
-    c->front_heights = 0;
-    c->front_top_inverse = 0;
+    c->sched = FrontSchedule{c->sched.vec2};      // (the switch is the context's own)
 }
 
 namespace {
@@ -1329,6 +1286,8 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
         cuts.swap(split);
     }
     const int nb = (int)cuts.size() - 1;
+    if (nb > FrontSchedule::MAX_BANDS) return bad("more bands than a schedule holds");      // (cannot happen: a band holds a height, n_levels <= 64)
+    FrontBand *const band = c->sched.band;
     bool identity = true;
     for (int k = 0; k < d.V && identity; ++k) identity = vmap[(size_t)k] == k;
     bool identity0 = true;
@@ -1351,7 +1310,7 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
     for (int k = 0; k < nb; ++k) {
         int &bp = band_planes[(size_t)k];
         bp = bp == 0 ? 0 : (bp <= 2 ? 2 : (bp <= 4 ? 4 : 8));
-        c->front_planes[k] = bp;
+        band[k].planes = bp;
     }
     for (Group &G : groups) {
         G.woff = wrows;
@@ -1488,14 +1447,14 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
         // 128 a 256-thread workgroup splits a dot product only 4 ways: 1024 threads up to 3000 columns)
         if (cols >= (d.TP >= 128 ? 3000 : (two_modes ? 1024 : 1536))) { bnb = 256; bcb = cols >= 4096 ? 4 : (cols >= 2048 ? 2 : 1); }
         else { bnb = 1024; bcb = (d.TP >= 128 && cols >= 600) ? 4 : (cols >= 250 ? 2 : 1); }
-        c->front_fwd_rb[k] = frb;      // (1, 2 or 4)
-        c->front_bwd_cb[k] = bcb;
-        c->front_fwd_nb[k] = fnb;
-        c->front_bwd_nb[k] = bnb;
+        band[k].fwd_rb = frb;      // (1, 2 or 4)
+        band[k].bwd_cb = bcb;
+        band[k].fwd_nb = fnb;
+        band[k].bwd_nb = bnb;
         // Bands of short rows take the row kernel (k_front_fwd_rows): QW lane groups per row by the band's mean row length
         // (rules from the DOTS_FRONT_TUNE tables of profiles/studies/shape_tuner.txt, round 3)
-        c->front_fwd_qw[k] = -1;
-        c->front_fwd_lds[k] = 0;
+        band[k].fwd_qw = -1;
+        band[k].fwd_lds = 0;
         if (c->front_rows && rows_groups >= 1) {
             double len = 0.0;      // columns a row of the band reads, summed
             int longest = 1;
@@ -1517,7 +1476,7 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
             // the fold kernels keep the longer rows)
             int qs = mean <= FWD_ROWS_MEAN_MAX ? 0 : 2;
             while ((1 << qs) > rows_groups) --qs;
-            if (fits && (c->front_rows >= 2 || mean <= FWD_ROWS_MEAN_MAX || (band_planes[(size_t)k] >= 4 && rows_groups >= 4))) c->front_fwd_qw[k] = qs;
+            if (fits && (c->front_rows >= 2 || mean <= FWD_ROWS_MEAN_MAX || (band_planes[(size_t)k] >= 4 && rows_groups >= 4))) band[k].fwd_qw = qs;
         }
     }
 
@@ -1679,7 +1638,7 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
     const double *w = nullptr;
     if ((rc = front_upload<double>(c, &w, nullptr, std::max<int64_t>(wrows, 1) << d.tp_shift))) { front_release(c); return rc; }
     f.W = const_cast<double *>(w);
-    c->front_w_rows = std::max<int64_t>(wrows, 1);
+    c->sched.w_rows = std::max<int64_t>(wrows, 1);
     // ---- the leaves as explicit local inverses (leaf_inv above; w and t of the largest leaf must fit the LDS a workgroup may take)
     if (leaf_inv) {
         std::vector<LeafWork> leaves;
@@ -1760,8 +1719,8 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
             entries_unmerged -= saved_alg;       // the coupling is the mode-independent CSR
         }
     }
-    c->front_bytes = 2.0 * entries_read * d.cg_ncol * sizeof(double);
-    c->front_bytes_unmerged = 2.0 * entries_unmerged * d.cg_ncol * sizeof(double);
+    c->sched.bytes = 2.0 * entries_read * d.cg_ncol * sizeof(double);
+    c->sched.bytes_unmerged = 2.0 * entries_unmerged * d.cg_ncol * sizeof(double);
     if (const char *e = getenv("DOTS_FRONT_CFG")) {      // "fwd:1024x2,256x4,r1,...;bwd:..." one entry per band (A/B measurements); rQ = row kernel, Q lane groups per row
         const std::string spec(e);
         bool ok = spec.find("fwd:") != std::string::npos || spec.find("bwd:") != std::string::npos;
@@ -1774,11 +1733,11 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
                 if (sweep == 0 && sscanf(spec.c_str() + pos, "r%d", &q) == 1 && q >= 1 && q <= rows_groups && (q & (q - 1)) == 0) {
                     int qs = 0;
                     while ((1 << qs) < q) ++qs;
-                    c->front_fwd_qw[k] = qs;
+                    band[k].fwd_qw = qs;
                 } else if (sscanf(spec.c_str() + pos, "%dx%d", &tnb, &trb) == 2 && (tnb == 256 || tnb == 1024) && (trb == 1 || trb == 2 || trb == 4)) {
-                    (sweep == 0 ? c->front_fwd_nb : c->front_bwd_nb)[k] = tnb;
-                    (sweep == 0 ? c->front_fwd_rb : c->front_bwd_cb)[k] = trb;
-                    if (sweep == 0) c->front_fwd_qw[k] = -1;
+                    (sweep == 0 ? band[k].fwd_nb : band[k].bwd_nb) = tnb;
+                    (sweep == 0 ? band[k].fwd_rb : band[k].bwd_cb) = trb;
+                    if (sweep == 0) band[k].fwd_qw = -1;
                 } else if (spec[pos] != '-') {      // "-" keeps the rule's choice for the band
                     ok = false;
                     break;
@@ -1820,7 +1779,7 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
         // A factor larger than the Infinity Cache streams from HBM in the real solve; a launch repeated back to back would find its
         // band (60-130 MB) in the cache.  There every timed launch is preceded by a read sweep over 512 MB (cold caches, no dirty lines, one event pair per
         // launch); small factors ARE cache-resident in the real solve and are timed back to back.
-        const bool cold = c->front_bytes > 400.0e6;
+        const bool cold = c->sched.bytes > 400.0e6;
         void *flushbuf = nullptr;
         const size_t flush_bytes = (size_t)512 << 20;
         if (cold && ok) {
@@ -1861,7 +1820,7 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
                 double best = 1e30;
                 int bnb = 0, brb = 0;
                 fprintf(stderr, "[front tune] band %d (heights %d-%d, %s, %lld %s, planes %d):", k, cuts[(size_t)k], cuts[(size_t)k + 1] - 1, sweep == 0 ? "fwd" : "bwd",
-                        (long long)(sweep == 0 ? band_rows[(size_t)k] : band_cols[(size_t)k]), sweep == 0 ? "rows" : "cols", c->front_planes[k]);
+                        (long long)(sweep == 0 ? band_rows[(size_t)k] : band_cols[(size_t)k]), sweep == 0 ? "rows" : "cols", band[k].planes);
                 for (int tnb : {256, 1024})
                     for (int trb : {1, 2, 4}) {
                         std::vector<FrontWork> list;
@@ -1872,12 +1831,12 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
                         if (hipMalloc(&dl, sizeof(FrontWork) * list.size()) != hipSuccess) { ok = false; break; }
                         (void)hipMemcpyAsync(dl, list.data(), sizeof(FrontWork) * list.size(), hipMemcpyHostToDevice, c->stream);
                         const double us = time_us([&]() {
-                            if (sweep == 0) front_launch_fwd(c, f, (const FrontWork *)dl, (int)list.size(), tnb, trb, c->front_planes[k], vec[0], vec[1], MoreRhs<1>{});
+                            if (sweep == 0) front_launch_fwd(c, f, (const FrontWork *)dl, (int)list.size(), tnb, trb, band[k].planes, vec[0], vec[1], MoreRhs<1>{});
                             else front_launch_bwd(c, f, (const FrontWork *)dl, (int)list.size(), tnb, trb, vec[1], vec[2], MoreRhs<1>{});
                         });
                         (void)hipFree(dl);
-                        const bool cur = tnb == (sweep == 0 ? c->front_fwd_nb : c->front_bwd_nb)[k] && trb == (sweep == 0 ? c->front_fwd_rb : c->front_bwd_cb)[k] &&
-                                         !(sweep == 0 && c->front_fwd_qw[k] >= 0);
+                        const bool cur = tnb == (sweep == 0 ? band[k].fwd_nb : band[k].bwd_nb) && trb == (sweep == 0 ? band[k].fwd_rb : band[k].bwd_cb) &&
+                                         !(sweep == 0 && band[k].fwd_qw >= 0);
                         fprintf(stderr, " %dx%d %.2f%s", tnb, trb, us, cur ? "*" : "");
                         if (us < best) { best = us; bnb = tnb; brb = trb; }
                     }
@@ -1891,18 +1850,18 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
                         void *dl = nullptr;
                         if (hipMalloc(&dl, sizeof(FrontWork) * list.size()) != hipSuccess) { ok = false; break; }
                         (void)hipMemcpyAsync(dl, list.data(), sizeof(FrontWork) * list.size(), hipMemcpyHostToDevice, c->stream);
-                        const double us = time_us([&]() { front_launch_fwd_rows(c, f, (const FrontWork *)dl, (int)list.size(), qs, c->front_planes[k], lds_cols, vec[0], vec[1], MoreRhs<1>{}); });
+                        const double us = time_us([&]() { front_launch_fwd_rows(c, f, (const FrontWork *)dl, (int)list.size(), qs, band[k].planes, lds_cols, vec[0], vec[1], MoreRhs<1>{}); });
                         (void)hipFree(dl);
-                        fprintf(stderr, " r%d %.2f%s", 1 << qs, us, c->front_fwd_qw[k] == qs ? "*" : "");
+                        fprintf(stderr, " r%d %.2f%s", 1 << qs, us, band[k].fwd_qw == qs ? "*" : "");
                         if (us < best) { best = us; bqs = qs; }
                     }
                 }
                 if (bqs >= 0) fprintf(stderr, "  -> r%d\n", 1 << bqs);
                 else fprintf(stderr, "  -> %dx%d\n", bnb, brb);
                 if (apply > 1 && bnb) {
-                    (sweep == 0 ? c->front_fwd_nb : c->front_bwd_nb)[k] = bnb;
-                    (sweep == 0 ? c->front_fwd_rb : c->front_bwd_cb)[k] = brb;
-                    if (sweep == 0) c->front_fwd_qw[k] = bqs;
+                    (sweep == 0 ? band[k].fwd_nb : band[k].bwd_nb) = bnb;
+                    (sweep == 0 ? band[k].fwd_rb : band[k].bwd_cb) = brb;
+                    if (sweep == 0) band[k].fwd_qw = bqs;
                 }
             }
         if (e0) (void)hipEventDestroy(e0);
@@ -1917,30 +1876,32 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
     // ~10 us more: sphere10k solve 85 -> 169 -> 272 us, torus100k 753 -> 804 -> 1061 us; profiles/studies/r03_lanes_experiment.txt)
     std::vector<FrontWork> fwd, bwd;
     for (int k = 0; k < nb; ++k) {
-        c->front_fwd_ptr[k] = (int)fwd.size();
-        c->front_bwd_ptr[k] = (int)bwd.size();
-        if (c->front_fwd_qw[k] >= 0) {
-            c->front_fwd_lds[k] = make_fwd_rows(k, rows_per_wg(c->front_fwd_qw[k]), fwd);
-            if ((size_t)c->front_fwd_lds[k] * (size_t)(d.TP + FWD_ROWS_PAD) * sizeof(double) > FWD_ROWS_LDS_MAX) {
+        FrontBand &bd = band[k];
+        bd.fwd_first = (int)fwd.size();
+        bd.bwd_first = (int)bwd.size();
+        if (bd.fwd_qw >= 0) {
+            bd.fwd_lds = make_fwd_rows(k, rows_per_wg(bd.fwd_qw), fwd);
+            if ((size_t)bd.fwd_lds * (size_t)(d.TP + FWD_ROWS_PAD) * sizeof(double) > FWD_ROWS_LDS_MAX) {
                 front_release(c);
                 return bad("DOTS_FRONT_CFG: the row kernel does not fit a band it was forced on (its right-hand side exceeds the LDS budget)");
             }
         } else {
-            make_fwd(k, c->front_fwd_rb[k], fwd);
+            make_fwd(k, bd.fwd_rb, fwd);
         }
-        make_bwd(k, c->front_bwd_cb[k], bwd);
-        deal(fwd, (size_t)c->front_fwd_ptr[k], by_band[(size_t)k].size());
-        deal(bwd, (size_t)c->front_bwd_ptr[k], by_band[(size_t)k].size());
+        make_bwd(k, bd.bwd_cb, bwd);
+        bd.fwd_n = (int)fwd.size() - bd.fwd_first;
+        bd.bwd_n = (int)bwd.size() - bd.bwd_first;
+        deal(fwd, (size_t)bd.fwd_first, by_band[(size_t)k].size());
+        deal(bwd, (size_t)bd.bwd_first, by_band[(size_t)k].size());
     }
-    c->front_fwd_ptr[nb] = (int)fwd.size();
-    c->front_bwd_ptr[nb] = (int)bwd.size();
     FUP(f, fwd_desc, fwd.data(), std::max<size_t>(fwd.size(), 1)); FUP(f, bwd_desc, bwd.data(), std::max<size_t>(bwd.size(), 1));
 #undef FUP
     c->front = f;
     c->use_front = 1;
-    c->front_eps = c->prm.eps;
-    c->front_heights = h->n_levels;
-    c->front_top_inverse = top_inv ? 1 : 0;
+    c->sched.n_bands = nb;
+    c->sched.eps = c->prm.eps;
+    c->sched.heights = h->n_levels;
+    c->sched.top_inverse = top_inv ? 1 : 0;
     return 0;
 }
 
@@ -1956,56 +1917,18 @@ static void front_launch_leaves(Ctx *c, const FrontDev &f, bool forward, const d
     const Dev &d = c->dcg;
     const FrontArgs g = front_args(d);      // (pitch <= 256: one chunk)
     const size_t lds = NR * sizeof(double) * (forward ? 2 : 1) * (size_t)f.leaf_nmax * (size_t)d.TP;
-    const bool v2 = front_two_modes(c);
-    const int nbt = front_leaf_threads(c);
-    const bool tab = f.leaf_bd != nullptr;
-#define LEAF_LAUNCH2(VECV, NBV, TABV)                                                                                                                \
-    do {                                                                                                                                             \
-        if (forward) hipLaunchKernelGGL((k_front_leaf_fwd<VECV, NBV, TABV, NR>), dim3(f.n_leaves), dim3(NBV), lds, c->stream, g, f, d.rowptr, d.col, d.val, bhat, mr);  \
-        else hipLaunchKernelGGL((k_front_leaf_bwd<VECV, NBV, TABV, NR>), dim3(f.n_leaves), dim3(NBV), lds, c->stream, g, f, d.rowptr, d.col, d.val, bhat, x, mr);       \
-    } while (0)
-#define LEAF_LAUNCH(VECV, NBV) do { if (tab) LEAF_LAUNCH2(VECV, NBV, true); else LEAF_LAUNCH2(VECV, NBV, false); } while (0)
-    if (nbt == 1024) {
-        if constexpr (NR <= FRONT_NR_1024) { if (v2) LEAF_LAUNCH(2, 1024); else LEAF_LAUNCH(1, 1024); }
-        else c->front_cap_fault = 1;
-    } else if (v2) { if (nbt == 256) LEAF_LAUNCH(2, 256); else LEAF_LAUNCH(2, 512); }
-    else { if (nbt == 256) LEAF_LAUNCH(1, 256); else LEAF_LAUNCH(1, 512); }
-#undef LEAF_LAUNCH
-#undef LEAF_LAUNCH2
+    with_constant<1024, 512, 256>(front_leaf_threads(c), [&](auto NB) {
+        if constexpr (NB == 1024 && NR > FRONT_NR_1024) c->front_cap_fault = 1;
+        else with_constant<2, 1>(front_two_modes(c) ? 2 : 1, [&](auto VEC) { with_constant<true, false>(f.leaf_bd != nullptr, [&](auto TAB) {
+            if (forward) hipLaunchKernelGGL((k_front_leaf_fwd<VEC, NB, TAB, NR>), dim3(f.n_leaves), dim3(NB), lds, c->stream, g, f, d.rowptr, d.col, d.val, bhat, mr);
+            else hipLaunchKernelGGL((k_front_leaf_bwd<VEC, NB, TAB, NR>), dim3(f.n_leaves), dim3(NB), lds, c->stream, g, f, d.rowptr, d.col, d.val, bhat, x, mr);
+        }); });
+    });
 }
 
-// the sweeps of one problem with the factor and update planes of `f`, launched on c's stream; returns the launches enqueued
-static int front_solve_with(Ctx *c, const FrontDev &f, const double *bhat, double *y, double *x) {
-    const MoreRhs<1> mr{};
-    int launches = 0;
-    for (int l = 0; l < f.n_levels; ++l) {
-        if (l == 0 && f.n_leaves > 0) { front_launch_leaves(c, f, true, bhat, x, mr); ++launches; continue; }
-        const int n = c->front_fwd_ptr[l + 1] - c->front_fwd_ptr[l];
-        // (a top band of explicit inverses writes the solution itself)
-        double *out = (c->front_top_inverse && l == f.n_levels - 1) ? x : y;
-        if (n > 0 && c->front_fwd_qw[l] >= 0) front_launch_fwd_rows(c, f, f.fwd_desc + c->front_fwd_ptr[l], n, c->front_fwd_qw[l], c->front_planes[l], c->front_fwd_lds[l], bhat, out, mr);
-        else if (n > 0) front_launch_fwd(c, f, f.fwd_desc + c->front_fwd_ptr[l], n, c->front_fwd_nb[l], c->front_fwd_rb[l], c->front_planes[l], bhat, out, mr);
-        launches += n > 0;
-    }
-    for (int l = f.n_levels - 1 - (c->front_top_inverse ? 1 : 0); l >= 0; --l) {
-        if (l == 0 && f.n_leaves > 0) { front_launch_leaves(c, f, false, bhat, x, mr); ++launches; continue; }
-        const int n = c->front_bwd_ptr[l + 1] - c->front_bwd_ptr[l];
-        if (n > 0) front_launch_bwd(c, f, f.bwd_desc + c->front_bwd_ptr[l], n, c->front_bwd_nb[l], c->front_bwd_cb[l], y, x, mr);
-        launches += n > 0;
-    }
-    return launches;
-}
-
-int front_solve(Ctx *c, const double *bhat, double *y, double *x) {
-    if (c->front.n_nodes == 0) { set_error("front_solve: no factor installed"); return DOTS_ERR_STATE; }
-    front_solve_with(c, c->front, bhat, y, x);
-    DOTS_HIP(hipGetLastError());
-    return 0;
-}
-
-// ---- several problems on one factor (front_solve_many) --------------------------------------------------------------------
+// ---- the sweeps of up to NR problems on one factor (front_solve: one; front_solve_many: several, dots_front_share) -------------------
 // One launch of a sweep for up to NR of the problems: problem k's vectors are (b[k], y[k], x[k]) and its own update planes (the W of its
-// context); the factor, the descriptors and the maps are the first context's (all share them: dots_front_share).  A launch whose LDS
+// context); the factor, the descriptors and the maps are the first context's (all share them).  A launch whose LDS
 // holds one region per rhs is split where NR regions would exceed FRONT_MANY_LDS; a chunk of fewer than NR problems repeats its last
 // problem (the copy writes the same values to the same addresses from the same thread: harmless, and cheaper than a second launch).
 constexpr size_t FRONT_MANY_LDS = 64 * 1024;
@@ -2013,71 +1936,72 @@ struct ManyView {
     Ctx *const *cs;
     const double *const *b;
     double *const *y, *const *x;
-    int n;      // problems in the chunk (<= NR); rhs k >= n repeats problem n - 1
+    int n;          // problems in the chunk (<= NR); rhs k >= n repeats problem n - 1
+    bool counted;   // the launches go into the batch's counters (front_solve_many; front_solve leaves them alone)
 };
-template <int NR>
-static MoreRhs<NR> many_rhs(const ManyView &v, int k0) {
-    MoreRhs<NR> mr{};
-    for (int k = 1; k < NR; ++k) {
-        const int p = std::min(k0 + k, v.n - 1);
-        mr.b[k - 1] = v.b[p];
-        mr.y[k - 1] = v.y[p];
-        mr.x[k - 1] = v.x[p];
-        mr.W[k - 1] = v.cs[p]->front.W;
-    }
-    return mr;
-}
-// one launch kind for the problems [k0, v.n) of the chunk, NR at a time (fewer where the LDS of NR would not fit)
+// one launch kind for the problems [0, v.n) of the chunk, NR at a time (fewer where the LDS of NR would not fit)
 // (and at most `cap` per launch: the workgroups of 1024 threads have 128 VGPRs, more right-hand sides would spill)
+// into_x: the launch writes the solution where it would write y (the forward launch of a top band of explicit inverses)
 // c: the batch's first context, which counts the launches (dots_debug_counter 7) and those of a split chunk (8)
 template <int NR, typename L>
-static void many_launch(Ctx *c, const ManyView &v, size_t lds_per_rhs, int cap, const L &launch, bool split = false) {
+static void many_launch(Ctx *c, const ManyView &v, size_t lds_per_rhs, int cap, bool into_x, const L &launch, bool split = false) {
     if (NR > 1 && (NR > cap || NR * lds_per_rhs > FRONT_MANY_LDS)) {
         for (int k0 = 0; k0 < v.n; k0 += NR / 2) {
-            ManyView s{v.cs + k0, v.b + k0, v.y + k0, v.x + k0, std::min(NR / 2, v.n - k0)};
-            many_launch<(NR > 1 ? NR / 2 : 1)>(c, s, lds_per_rhs, cap, launch, true);
+            ManyView s{v.cs + k0, v.b + k0, v.y + k0, v.x + k0, std::min(NR / 2, v.n - k0), v.counted};
+            many_launch<(NR > 1 ? NR / 2 : 1)>(c, s, lds_per_rhs, cap, into_x, launch, true);
         }
         return;
     }
-    FrontDev f = v.cs[0]->front;
-    launch(f, v.b[0], v.y[0], v.x[0], many_rhs<NR>(v, 0));
-    ++c->front_many_launches;
-    c->front_many_split += split;
+    double *const *out = into_x ? v.x : v.y;
+    MoreRhs<NR> mr{};
+    for (int k = 1; k < NR; ++k) {
+        const int p = std::min(k, v.n - 1);
+        mr.b[k - 1] = v.b[p];
+        mr.y[k - 1] = out[p];
+        mr.x[k - 1] = v.x[p];
+        mr.W[k - 1] = v.cs[p]->front.W;
+    }
+    launch(v.cs[0]->front, v.b[0], out[0], v.x[0], mr);
+    if (v.counted) {
+        ++c->front_many_launches;
+        c->front_many_split += split;
+    }
 }
 
+// both sweeps of the chunk on c's stream, band by band as the schedule says
 template <int NR>
-static void front_solve_chunk(Ctx *c, const ManyView &v) {
-    const FrontDev &f0 = c->front;
+static void front_sweeps(Ctx *c, const FrontSchedule &s, const ManyView &v) {
     const Dev &d = c->dcg;
-    const size_t leaf_fwd = sizeof(double) * 2 * (size_t)f0.leaf_nmax * (size_t)d.TP, leaf_bwd = leaf_fwd / 2;
+    const int n_leaves = v.cs[0]->front.n_leaves;
+    const size_t leaf_fwd = sizeof(double) * 2 * (size_t)v.cs[0]->front.leaf_nmax * (size_t)d.TP, leaf_bwd = leaf_fwd / 2;
     const int leaf_cap = front_leaf_threads(c) == 1024 ? FRONT_NR_1024 : NR;
-#define MANY_CAP(BYTES, CAP, CALL) many_launch<NR>(c, v, (BYTES), (CAP), [&](const FrontDev &f, const double *bh, double *yy, double *xx, const auto &mr) { CALL; })
-#define MANY(BYTES, CALL) MANY_CAP(BYTES, NR, CALL)
-    for (int l = 0; l < f0.n_levels; ++l) {
-        if (l == 0 && f0.n_leaves > 0) { MANY_CAP(leaf_fwd, leaf_cap, front_launch_leaves(c, f, true, bh, xx, mr)); continue; }
-        const int n = c->front_fwd_ptr[l + 1] - c->front_fwd_ptr[l];
-        const bool top = c->front_top_inverse && l == f0.n_levels - 1;      // (a top band of explicit inverses writes the solution itself)
-        const FrontWork *ptr = f0.fwd_desc + c->front_fwd_ptr[l];
-        if (n > 0 && c->front_fwd_qw[l] >= 0) {
-            const size_t rows = sizeof(double) * (size_t)std::max(c->front_fwd_lds[l], 1) * (size_t)(d.TP + FWD_ROWS_PAD);
-            if (top) MANY(rows, { auto m = mr; for (int k = 0; k < (int)(sizeof m.y / sizeof m.y[0]); ++k) m.y[k] = m.x[k];
-                                  front_launch_fwd_rows(c, f, ptr, n, c->front_fwd_qw[l], c->front_planes[l], c->front_fwd_lds[l], bh, xx, m); });
-            else MANY(rows, front_launch_fwd_rows(c, f, ptr, n, c->front_fwd_qw[l], c->front_planes[l], c->front_fwd_lds[l], bh, yy, mr));
-        } else if (n > 0) {
-            const int cap = c->front_fwd_nb[l] == 1024 ? FRONT_NR_1024_FWD : NR;
-            if (top) MANY_CAP(0, cap, { auto m = mr; for (int k = 0; k < (int)(sizeof m.y / sizeof m.y[0]); ++k) m.y[k] = m.x[k];
-                               front_launch_fwd(c, f, ptr, n, c->front_fwd_nb[l], c->front_fwd_rb[l], c->front_planes[l], bh, xx, m); });
-            else MANY_CAP(0, cap, front_launch_fwd(c, f, ptr, n, c->front_fwd_nb[l], c->front_fwd_rb[l], c->front_planes[l], bh, yy, mr));
-        }
+    for (int l = 0; l < s.n_bands; ++l) {
+        const FrontBand &bd = s.band[l];
+        const bool top = s.top_inverse && l == s.n_bands - 1;
+        if (l == 0 && n_leaves > 0)
+            many_launch<NR>(c, v, leaf_fwd, leaf_cap, false, [&](const FrontDev &f, const double *bh, double *, double *x, const auto &mr) { front_launch_leaves(c, f, true, bh, x, mr); });
+        else if (bd.fwd_n > 0 && bd.fwd_qw >= 0)
+            many_launch<NR>(c, v, sizeof(double) * (size_t)std::max(bd.fwd_lds, 1) * (size_t)(d.TP + FWD_ROWS_PAD), NR, top, [&](const FrontDev &f, const double *bh, double *y, double *, const auto &mr) {
+                front_launch_fwd_rows(c, f, f.fwd_desc + bd.fwd_first, bd.fwd_n, bd.fwd_qw, bd.planes, bd.fwd_lds, bh, y, mr); });
+        else if (bd.fwd_n > 0)
+            many_launch<NR>(c, v, 0, bd.fwd_nb == 1024 ? FRONT_NR_1024_FWD : NR, top, [&](const FrontDev &f, const double *bh, double *y, double *, const auto &mr) {
+                front_launch_fwd(c, f, f.fwd_desc + bd.fwd_first, bd.fwd_n, bd.fwd_nb, bd.fwd_rb, bd.planes, bh, y, mr); });
     }
-    for (int l = f0.n_levels - 1 - (c->front_top_inverse ? 1 : 0); l >= 0; --l) {
-        if (l == 0 && f0.n_leaves > 0) { MANY_CAP(leaf_bwd, leaf_cap, front_launch_leaves(c, f, false, bh, xx, mr)); continue; }
-        const int n = c->front_bwd_ptr[l + 1] - c->front_bwd_ptr[l];
-        if (n > 0) MANY_CAP(0, c->front_bwd_nb[l] == 1024 ? FRONT_NR_1024 : NR,
-                            front_launch_bwd(c, f, f0.bwd_desc + c->front_bwd_ptr[l], n, c->front_bwd_nb[l], c->front_bwd_cb[l], yy, xx, mr));
+    for (int l = s.n_bands - 1 - (s.top_inverse ? 1 : 0); l >= 0; --l) {
+        const FrontBand &bd = s.band[l];
+        if (l == 0 && n_leaves > 0)
+            many_launch<NR>(c, v, leaf_bwd, leaf_cap, false, [&](const FrontDev &f, const double *bh, double *, double *x, const auto &mr) { front_launch_leaves(c, f, false, bh, x, mr); });
+        else if (bd.bwd_n > 0)
+            many_launch<NR>(c, v, 0, bd.bwd_nb == 1024 ? FRONT_NR_1024 : NR, false, [&](const FrontDev &f, const double *, double *y, double *x, const auto &mr) {
+                front_launch_bwd(c, f, f.bwd_desc + bd.bwd_first, bd.bwd_n, bd.bwd_nb, bd.bwd_cb, y, x, mr); });
     }
-#undef MANY
-#undef MANY_CAP
+}
+
+int front_solve(Ctx *c, const double *bhat, double *y, double *x) {
+    if (c->front.n_nodes == 0) { set_error("front_solve: no factor installed"); return DOTS_ERR_STATE; }
+    front_sweeps<1>(c, c->sched, ManyView{&c, &bhat, &y, &x, 1, false});
+    DOTS_HIP(hipGetLastError());
+    return 0;
 }
 
 int front_solve_many(Ctx *const *cs, int n, const double *const *b, double *const *y, double *const *x) {
@@ -2085,19 +2009,14 @@ int front_solve_many(Ctx *const *cs, int n, const double *const *b, double *cons
     Ctx *c = cs[0];
     if (c->front.n_nodes == 0) { set_error("front_solve_many: no factor installed"); return DOTS_ERR_STATE; }
     c->front_many_launches = c->front_many_split = 0;
-    if (n == 1) {
-        c->front_many_launches = front_solve_with(c, c->front, b[0], y[0], x[0]);
-        DOTS_HIP(hipGetLastError());
-        return 0;
-    }
     const int cap = c->front_nr_max;
     for (int k0 = 0; k0 < n; k0 += cap) {
         const int m = std::min(cap, n - k0);
-        const ManyView v{cs + k0, b + k0, y + k0, x + k0, m};
-        if (m == 1) c->front_many_launches += front_solve_with(c, cs[k0]->front, b[k0], y[k0], x[k0]);      // (its own update planes, on the batch's stream)
-        else if (m == 2) front_solve_chunk<2>(c, v);
-        else if (m <= 4) front_solve_chunk<4>(c, v);
-        else front_solve_chunk<8>(c, v);
+        const ManyView v{cs + k0, b + k0, y + k0, x + k0, m, true};
+        if (m == 1) front_sweeps<1>(c, c->sched, v);      // (its own update planes, on the batch's stream)
+        else if (m == 2) front_sweeps<2>(c, c->sched, v);
+        else if (m <= 4) front_sweeps<4>(c, c->sched, v);
+        else front_sweeps<8>(c, c->sched, v);
     }
     if (c->front_cap_fault) {
         c->front_cap_fault = 0;
