@@ -1,4 +1,5 @@
-"""Coarse-to-fine time cascade: the transfer of a solution between two time grids, as a specification on the host.
+"""Coarse-to-fine cascades: the transfer of a solution between two time grids, or between two nested meshes, as a specification on
+the host.
 
 A solution on a coarse time grid is a good starting point for a finer one (``init_solution``, solver_socp.py:38,70-71).  This
 module is the single definition of the interpolation that the device kernel (``dots_prolong_time``, csrc/kernels_alm.hip), the
@@ -15,6 +16,10 @@ tests and the oracle-side checks share:
 
 ``time_weights`` computes the tables ``j`` and ``w`` once, on the host; the device reads the same tables, so both sides perform the
 same operations on the same numbers.
+
+The transfer in space (``prolong_space``; ``dots_prolong_space``, k_prolong_space in csrc/kernels_alm.hip) goes from a mesh to its
+nested refinement (``meshes.subdivide``: ``parents``) on one time grid; ``space_row_maps`` turns ``parents`` and the two device
+numberings into the row maps the kernel reads.
 """
 from __future__ import annotations
 
@@ -107,3 +112,90 @@ def row_map(perm_dst, perm_src, n):
     inv_src = np.empty(n, dtype=np.int64)
     inv_src[ps] = np.arange(n)
     return np.ascontiguousarray(inv_src[pd], dtype=np.int32)
+
+
+# ---- coarse-to-fine in space: a mesh to its nested refinement --------------------------------------------------------------------
+VERTEX_ARRAYS = ("phi", "A", "lambda_c", "z_fst", "z_end", "mu", "beta_fst", "beta_end")
+TRIANGLE_ARRAYS = ("B", "E")
+CORNER_ARRAYS = ("z_mid", "beta_mid")
+DEFAULT_COARSE_LEVELS = 2      # coarse levels below the finest mesh that paid on the 100k torus; small meshes: solve cold
+
+
+def check_parents(parents, n_vertices=None, n_triangles=None):
+    """``(vertex_parents (Vf, 2), triangle_parent (Ff,))`` of ``parents`` (``meshes.subdivide``) as int64 arrays; ``n_vertices`` /
+    ``n_triangles``: the size of the coarse mesh they must refer to (every coarse vertex and triangle has a child)."""
+    try:
+        vp = np.asarray(parents["vertex_parents"])
+        tp = np.asarray(parents["triangle_parent"])
+    except (KeyError, TypeError, IndexError):
+        raise ValueError("parents must hold 'vertex_parents' and 'triangle_parent' (meshes.subdivide)") from None
+    if vp.ndim != 2 or vp.shape[1] != 2 or tp.ndim != 1 or vp.shape[0] < 1 or tp.shape[0] < 1:
+        raise ValueError("parents: vertex_parents must be (Vf, 2) and triangle_parent (Ff,)")
+    if not (np.issubdtype(vp.dtype, np.integer) and np.issubdtype(tp.dtype, np.integer)):
+        raise ValueError("parents: integer arrays expected")
+    vp, tp = vp.astype(np.int64), tp.astype(np.int64)
+    if vp.min() < 0 or tp.min() < 0:
+        raise ValueError("parents: negative index")
+    if n_vertices is not None and int(vp.max()) + 1 != int(n_vertices):
+        raise ValueError(f"parents: vertex_parents refer to a mesh of {int(vp.max()) + 1} vertices, not {int(n_vertices)}")
+    if n_triangles is not None and int(tp.max()) + 1 != int(n_triangles):
+        raise ValueError(f"parents: triangle_parent refers to a mesh of {int(tp.max()) + 1} triangles, not {int(n_triangles)}")
+    return vp, tp
+
+
+def prolong_space(array, name, parents):
+    """``array`` (the state array ``name`` on the coarse mesh, reference layout) on the refinement that ``parents`` describes; the
+    time axis is untouched.
+
+    * vertex arrays (``phi``, ``A``, ``lambda_c``, ``z_fst``, ``z_end``, ``mu``, ``beta_fst``, ``beta_end``): a kept vertex
+      (``p0 == p1``) takes ``x[..., p0]``, an exact copy; a midpoint ``(x[..., p0] + x[..., p1]) * 0.5``, in this order of operations;
+    * triangle arrays (``B``, ``E``): a child takes the three components of its parent unchanged.  They are NOT projected into the
+      child's plane: on a curved surface a child is tilted against its parent, and the small normal component is left to the
+      first iterations on the fine mesh;
+    * corner arrays (``z_mid``, ``beta_mid``): child ``(f', k)`` takes parent ``(triangle_parent[f'], k)`` for both interval ends
+      and every component."""
+    a = np.asarray(array, dtype=np.float64)
+    if name in VERTEX_ARRAYS:
+        if a.ndim != 2:
+            raise ValueError(f"{name}: expected (time, V), got shape {a.shape}")
+        vp, _ = check_parents(parents, n_vertices=a.shape[-1])
+        p0, p1 = vp[:, 0], vp[:, 1]
+        return np.where(p0 == p1, a[..., p0], (a[..., p0] + a[..., p1]) * 0.5)
+    if name in TRIANGLE_ARRAYS or name in CORNER_ARRAYS:
+        if a.ndim != (3 if name in TRIANGLE_ARRAYS else 5) or a.shape[-1] != 3:
+            raise ValueError(f"{name}: expected (time, {'' if name in TRIANGLE_ARRAYS else '2, 3, '}F, 3), got shape {a.shape}")
+        _, tp = check_parents(parents, n_triangles=a.shape[-2])
+        return np.ascontiguousarray(a[..., tp, :])
+    raise ValueError(f"unknown state array {name!r}")
+
+
+def prolong_space_solution(solution, parents):
+    """Every state array of ``solution`` (a dict as ``solver_socp`` returns it) on the refinement: an ``init_solution``."""
+    names = VERTEX_ARRAYS + TRIANGLE_ARRAYS + CORNER_ARRAYS
+    return {k: prolong_space(v, k, parents) for k, v in solution.items() if k in names and v is not None}
+
+
+def space_row_maps(parents, n_src_vertices, n_src_triangles, perm_vert_dst=None, perm_tri_dst=None, perm_vert_src=None, perm_tri_src=None):
+    """The row maps of ``dots_prolong_space``: ``vmap`` (Vf, 2) int32, the two source device rows of every destination device vertex
+    row (equal for a kept vertex), and ``fmap`` (Ff,) int32, the source device triangle of every destination device triangle.
+    ``perm[i]`` = caller index of device row i (None = identity), as in ``row_map``: the two meshes are numbered independently."""
+    vp, tp = check_parents(parents, n_vertices=n_src_vertices, n_triangles=n_src_triangles)
+
+    def inverse(perm, n):
+        if perm is None:
+            return np.arange(n, dtype=np.int64)
+        perm = np.asarray(perm, dtype=np.int64)
+        if perm.shape != (n,):
+            raise ValueError("space_row_maps: a permutation of the wrong size")
+        inv = np.empty(n, dtype=np.int64)
+        inv[perm] = np.arange(n)
+        return inv
+
+    for perm, n in ((perm_vert_dst, vp.shape[0]), (perm_tri_dst, tp.shape[0])):
+        if perm is not None and np.asarray(perm).shape != (n,):
+            raise ValueError("space_row_maps: a permutation of the wrong size")
+    vd = vp if perm_vert_dst is None else vp[np.asarray(perm_vert_dst, dtype=np.int64)]
+    td = tp if perm_tri_dst is None else tp[np.asarray(perm_tri_dst, dtype=np.int64)]
+    vmap = inverse(perm_vert_src, int(n_src_vertices))[vd]
+    fmap = inverse(perm_tri_src, int(n_src_triangles))[td]
+    return np.ascontiguousarray(vmap, dtype=np.int32), np.ascontiguousarray(fmap, dtype=np.int32)

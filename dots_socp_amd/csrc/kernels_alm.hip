@@ -1495,6 +1495,101 @@ int launch_prolong(Ctx *dst, Ctx *src, int id, const int *jt, const double *wt, 
 }
 
 // ------------------------------------------------------------------------------------------
+// space prolongation (dots_prolong_space): one state array of a context on the nested refinement of its mesh, same time grid
+// ------------------------------------------------------------------------------------------
+// Both contexts have one time pitch, so a destination row is one source row (triangle and corner rows: the parent's row of the same
+// component / corner / interval end) or the half-sum of two (a midpoint vertex): f * a where the two source rows are one, else
+// (f * a + f * b) * 0.5 -- the operations of cascade.prolong_space on the recovered solution, in that order (-ffp-contract=off), so
+// that the result is what an upload of the host's prolongation leaves, bit for bit.  A lane forms two neighbouring columns (one
+// 16-byte word in, one out); a row wider than 256 columns is walked in chunks of 256.  Columns outside the array's time points
+// (padding, and the slot of a corner row whose interval does not exist) are written as zero, as k_convert writes them.
+// A workgroup takes runs of consecutive destination rows, a run a whole number of groups of four vertices / triangles: the four
+// children of a triangle, which read the same 3 or 18 source rows, are numbered together by the subdivision (and stay close under a
+// locality renumbering), so the source rows come from HBM once and from the cache for the siblings.
+struct ProlongSpaceArgs {
+    const double *src;
+    double *dst;
+    const int *map;          // VERT: [entities][2] source vertex rows; else [entities] source triangle
+    int64_t rows;            // destination rows
+    int64_t run;             // rows per run
+    int sh;                  // log2 of the time pitch (both sides)
+    int n_valid;             // time points of the array: T + 1 (node arrays) or T
+    double f;
+};
+
+template <int RPE>      // rows per vertex / triangle: 1, 3 (B, E), 18 (corner arrays: row = ((f * 3 + k) * 2 + s) * 3 + c, column = interval + s)
+__global__ __launch_bounds__(BLOCK) void k_prolong_space(ProlongSpaceArgs a) {
+    const int tid = threadIdx.x;
+    const int hp = a.sh - 1;                      // log2 of the column pairs per row
+    const int hl = min(hp, 7);                    // log2 of the lanes per row: at most 128 pairs = 256 columns per chunk
+    const int rpp = BLOCK >> hl;                  // rows per pass
+    const int rr = tid >> hl, p0 = tid & ((1 << hl) - 1);
+    const int64_t n_runs = (a.rows + a.run - 1) / a.run;
+    for (int64_t run = blockIdx.x; run < n_runs; run += gridDim.x) {
+        const int64_t r_end = min(a.rows, (run + 1) * a.run);
+        for (int64_t r = run * a.run + rr; r < r_end; r += rpp) {
+            const int64_t ent = r / RPE;
+            const int sub = (int)(r - ent * RPE);
+            int64_t ra, rb;
+            if (RPE == 1) {
+                ra = a.map[2 * ent];
+                rb = a.map[2 * ent + 1];
+            } else {
+                ra = rb = (int64_t)a.map[ent] * RPE + sub;
+            }
+            const int s = RPE == 18 ? (sub / 3) & 1 : 0;
+            const double *xa = a.src + (ra << a.sh), *xb = a.src + (rb << a.sh);
+            double *y = a.dst + (r << a.sh);
+            for (int p = p0; p < (1 << hp); p += 1 << hl) {
+                D2 va = ld2(xa + 2 * p), out;
+                if (ra != rb) {
+                    const D2 vb = ld2(xb + 2 * p);
+#pragma unroll
+                    for (int q = 0; q < 2; ++q) out.v[q] = (a.f * va.v[q] + a.f * vb.v[q]) * 0.5;
+                } else {
+#pragma unroll
+                    for (int q = 0; q < 2; ++q) out.v[q] = a.f * va.v[q];
+                }
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    const int t = 2 * p + q - s;
+                    if (t < 0 || t >= a.n_valid) out.v[q] = 0.0;
+                }
+                st2(y + 2 * p, out);
+            }
+        }
+    }
+}
+
+int launch_prolong_space(Ctx *dst, Ctx *src, int id, const int *vmap, const int *fmap, double f) {
+    const Dev &dd = dst->d;
+    const int kind = array_kind(id);
+    ProlongSpaceArgs a{};
+    a.src = src->arr(id);
+    a.dst = dst->arr(id);
+    a.map = kind <= 1 ? vmap : fmap;
+    const int rpe = kind <= 1 ? 1 : (kind == 2 ? 3 : 18);
+    a.rows = (int64_t)rpe * (kind <= 1 ? dd.V : dd.F);
+    a.sh = dd.tp_shift;
+    a.n_valid = dd.T + ((kind == 0 || kind == 2) ? 1 : 0);
+    a.f = f;
+    if (a.sh < 1 || dd.TP > TILE_ELEMS || a.sh != src->d.tp_shift) { set_error("prolong_space: time pitch out of range"); return DOTS_ERR_STATE; }
+    // a run: whole groups of four vertices / triangles, whole passes of the workgroup, about 32 KB of destination
+    const int rpp = BLOCK >> std::min(a.sh - 1, 7);
+    int64_t unit = 4 * rpe;
+    while (unit % rpp) unit *= 2;
+    const int64_t row_bytes = (int64_t)sizeof(double) << a.sh;
+    a.run = unit * std::max<int64_t>(1, (32768 + unit * row_bytes - 1) / (unit * row_bytes));
+    const int64_t n_runs = (a.rows + a.run - 1) / a.run;
+    const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(n_runs, 4096)));
+    if (rpe == 1) hipLaunchKernelGGL(k_prolong_space<1>, grid, dim3(BLOCK), 0, dst->stream, a);
+    else if (rpe == 3) hipLaunchKernelGGL(k_prolong_space<3>, grid, dim3(BLOCK), 0, dst->stream, a);
+    else hipLaunchKernelGGL(k_prolong_space<18>, grid, dim3(BLOCK), 0, dst->stream, a);
+    DOTS_HIP(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
 // standalone operators (rows a4-a6): same index arithmetic as the fused kernels, exposed so each
 // reference function has a one-to-one parity test.  in/out are device-layout scratch arrays.
 // ------------------------------------------------------------------------------------------

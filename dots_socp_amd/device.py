@@ -213,6 +213,32 @@ class DeviceProblem:
         _lib.check(self.lib.dots_prolong_time(self._h, src._h, C.byref(d)), "dots_prolong_time")
         return ms.value
 
+    def prolong_space_from(self, src: "DeviceProblem", parents, factors=(1.0, 1.0, 1.0, 1.0)):
+        """Fill this context's twelve state arrays from those of ``src``, a context on the parent mesh of this one (``parents``:
+        ``meshes.subdivide``) with the same ``n_time`` on the same device (dots_prolong_space; cascade.prolong_space is the
+        specification).  ``factors``: as for ``prolong_from``.  Returns the milliseconds of the launches; ``self.prolong_bytes``: the
+        bytes the transfer reads and writes when every source row is read once."""
+        from . import cascade
+
+        if self.slab or src.slab:
+            raise ValueError("prolong_space_from: not available on time slabs")
+        if self.T != src.T:
+            raise ValueError(f"prolong_space_from: n_time = {self.T}, the source's {src.T}: both levels have one time grid")
+        vp, tp = cascade.check_parents(parents, n_vertices=src.V, n_triangles=src.F)
+        if (vp.shape[0], tp.shape[0]) != (self.V, self.F):
+            raise ValueError(f"prolong_space_from: parents of a mesh with V, F = {vp.shape[0]}, {tp.shape[0]}, this one has {self.V}, {self.F}")
+        vmap, fmap = cascade.space_row_maps(parents, src.V, src.F, self.plan.perm_vert, self.plan.perm_tri, src.plan.perm_vert, src.plan.perm_tri)
+        ms = C.c_double()
+        d = _lib.ProlongSpaceDesc()
+        d.vmap, d.fmap, d.n_vertices, d.n_triangles = _ptr(vmap, C.c_int32), _ptr(fmap, C.c_int32), self.V, self.F
+        for i, f in enumerate(factors):
+            d.factor[i] = float(f)
+        d.ms = C.pointer(ms)
+        _lib.check(self.lib.dots_prolong_space(self._h, src._h, C.byref(d)), "dots_prolong_space")
+        pitch = max(8, 1 << int(np.ceil(np.log2(self.T + 1))))
+        self.prolong_bytes = 8 * pitch * (8 * (self.V + src.V) + (2 * 3 + 2 * 18) * (self.F + src.F))
+        return ms.value
+
     # ---- the hot loop
     def step(self, n_iters=1, wait=True):
         """``wait=False``: only enqueue (direct solver); returns None, nothing is timed."""

@@ -139,6 +139,95 @@ def plane(n: int = 20):
 
 
 # --------------------------------------------------------------------------- #
+# nested refinement (the levels of a cascade in space, cascade.prolong_space)
+# --------------------------------------------------------------------------- #
+def subdivide(vertices, triangles, project=None):
+    """One 1 -> 4 midpoint subdivision: ``(vertices_f, triangles_f, parents)``.
+
+    The coarse vertices keep their indices ``0 .. Vc - 1``; the edge midpoints follow in the order of ``_unique_edges``.  ``project``
+    (optional) is applied to the new vertices only, e.g. to put them back on a sphere or torus.  A parent ``(a, b, c)`` with the
+    midpoints ``ab, bc, ca`` has the children ``4f + 0 = (a, ab, ca)``, ``4f + 1 = (ab, b, bc)``, ``4f + 2 = (ca, bc, c)``,
+    ``4f + 3 = (ab, bc, ca)``: corner k of child k is corner k of the parent.  ``parents`` = {"vertex_parents": (Vf, 2) int32 -- both
+    entries of a kept vertex are the vertex itself, those of a midpoint the ends of its edge --, "triangle_parent": (Ff,) int32, here
+    ``f' // 4`` (stored, so that a hierarchy need not be 1 -> 4)}."""
+    v = np.asarray(vertices, dtype=np.float64)
+    t = np.asarray(triangles).astype(np.int64)
+    Vc, Fc = v.shape[0], t.shape[0]
+    e = np.concatenate([t[:, [0, 1]], t[:, [1, 2]], t[:, [2, 0]]], axis=0)
+    e.sort(axis=1)
+    ue, inv = np.unique(e, axis=0, return_inverse=True)
+    inv = np.asarray(inv).reshape(-1)
+    mid = (v[ue[:, 0]] + v[ue[:, 1]]) * 0.5
+    if project is not None:
+        mid = np.asarray(project(mid), dtype=np.float64)
+        if mid.shape != (ue.shape[0], 3):
+            raise ValueError("subdivide: project must return one point per new vertex")
+    ab, bc, ca = Vc + inv[:Fc], Vc + inv[Fc:2 * Fc], Vc + inv[2 * Fc:]
+    a, b, c = t[:, 0], t[:, 1], t[:, 2]
+    children = np.stack([np.stack([a, ab, ca], axis=1), np.stack([ab, b, bc], axis=1), np.stack([ca, bc, c], axis=1),
+                         np.stack([ab, bc, ca], axis=1)], axis=1)      # [f][child][corner]
+    kept = np.arange(Vc, dtype=np.int64)
+    parents = {"vertex_parents": np.ascontiguousarray(np.concatenate([np.stack([kept, kept], axis=1), ue], axis=0), dtype=np.int32),
+               "triangle_parent": np.ascontiguousarray(np.arange(4 * Fc) // 4, dtype=np.int32)}
+    return np.concatenate([v, mid], axis=0), children.reshape(-1, 3), parents
+
+
+def snap_projection(points):
+    """A ``project`` for ``subdivide`` that moves every new vertex to the nearest of ``points`` (the vertices of the surface at the
+    finer resolution, e.g. ``torus(2 * nu, 2 * nv)[0]`` above ``torus(nu, nv)``): the refined mesh then lies on the generator's own
+    grid.  Two new vertices that take the same point raise ``ValueError``."""
+    from scipy.spatial import cKDTree
+
+    pts = np.asarray(points, dtype=np.float64)
+    tree = cKDTree(pts)
+
+    def project(mid):
+        idx = tree.query(mid)[1]
+        if np.unique(idx).size != idx.size:
+            raise ValueError("snap_projection: two new vertices snap to the same point")
+        return pts[idx]
+
+    return project
+
+
+def refine_levels(geometry, n_levels, project=None, densities=None):
+    """``n_levels`` geometries from coarse to fine: ``geometry`` itself, then ``n_levels - 1`` subdivisions (``subdivide``), every
+    refined level with its ``parents`` (the map to the level below) under the key "parents".
+
+    ``project``: None, one callable for every step, or a list of one callable (or None) per step.  ``densities(vertices,
+    area_vertices) -> (mu0, mu1)`` gives a refined level its end points; without it the densities per unit area (``mu / area_vertices``)
+    of the level below are carried up by the vertex rule of ``cascade.prolong_space`` (copy at a kept vertex, half-sum of the two
+    parents at a midpoint) and weighted with the level's own ``area_vertices``.  Either way ``mu0`` / ``mu1`` are scaled to unit mass.
+    The coordinates are taken as they are (``make_geometry(..., normalize=False)``): a kept vertex is the same point on every level,
+    so normalise the coarsest geometry, not the levels."""
+    n_levels = int(n_levels)
+    if n_levels < 1:
+        raise ValueError("refine_levels: at least one level")
+    steps = list(project) if isinstance(project, (list, tuple)) else [project] * (n_levels - 1)
+    if len(steps) != n_levels - 1:
+        raise ValueError("refine_levels: one projection per refinement step")
+    levels = [geometry]
+    for proj in steps:
+        g = levels[-1]
+        v, t, parents = subdivide(g["vertices"], g["triangles"], proj)
+        fine, _ = make_geometry(v, t, normalize=False)
+        if densities is not None:
+            mu0, mu1 = densities(fine["vertices"], fine["area_vertices"])
+        else:
+            area_c = g["area_vertices"] if "area_vertices" in g else vertex_areas(
+                np.asarray(g["vertices"]).shape[0], g["triangles"], triangle_areas(g["vertices"], g["triangles"]))
+            p0, p1 = parents["vertex_parents"][:, 0], parents["vertex_parents"][:, 1]
+            rho0, rho1 = np.asarray(g["mu0"], dtype=np.float64) / area_c, np.asarray(g["mu1"], dtype=np.float64) / area_c
+            mu0 = np.where(p0 == p1, rho0[p0], (rho0[p0] + rho0[p1]) * 0.5) * fine["area_vertices"]
+            mu1 = np.where(p0 == p1, rho1[p0], (rho1[p0] + rho1[p1]) * 0.5) * fine["area_vertices"]
+        mu0, mu1 = np.asarray(mu0, dtype=np.float64), np.asarray(mu1, dtype=np.float64)
+        fine["mu0"], fine["mu1"] = mu0 / mu0.sum(), mu1 / mu1.sum()
+        fine["parents"] = parents
+        levels.append(fine)
+    return levels
+
+
+# --------------------------------------------------------------------------- #
 # geometry dict (GeometryData of the reference, utils/type.py:6-13)
 # --------------------------------------------------------------------------- #
 def triangle_areas(vertices, triangles):

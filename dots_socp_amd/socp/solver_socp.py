@@ -84,7 +84,7 @@ class AlmSolver:
                  is_constant_scaling=False, check_kkt_step_by_step=False, init_solution=None, tol_checkpoints=None,
                  time_limit=1000, is_palm=False, lap_solver="modal_direct", cg_tol=DEFAULT_CG_TOL, cg_max_iter=20000, device=0, reorder=True,
                  preconditioner="multigrid", mg_coarsest=256, time_slab=None, nd_leaf=16, plan=None, front_owner=None, init_from=None,
-                 release_init_from=False, batched=None):
+                 release_init_from=False, batched=None, init_parents=None):
         """``plan``: the device plan to use (geometry.plan_with_densities) instead of building one; ``front_owner``: a DeviceProblem
         whose factor this solver shares (dots_front_share) instead of building its own -- a member of a batch (solver_socp_many), stepped
         by ``step_batch``; the launch ahead of the right-hand side and of the penalty decision are off then.
@@ -92,7 +92,10 @@ class AlmSolver:
         its recovered solution, interpolated linearly in time on the device (DeviceProblem.prolong_from), is the warm start -- what
         ``init_solution=cascade.prolong_solution(<its solution>, ...)`` does over the host, bit for bit.  The state is transferred before
         this solver's factor is built; ``release_init_from`` closes the coarse solver right after the transfer, so that the two factors
-        are never on the device together.  ``batched``: whether the solver is stepped by a batch (default: whenever ``plan`` or
+        are never on the device together.  ``init_parents``: ``init_from`` is a solver on the PARENT mesh of this one (``meshes.subdivide``'s
+        ``parents``) at the same ``n_time``: its recovered solution is carried to the refinement on the device
+        (DeviceProblem.prolong_space_from; ``init_solution=cascade.prolong_space_solution(<its solution>, parents)`` bit for bit).  One call
+        changes the mesh or the time grid, not both.  ``batched``: whether the solver is stepped by a batch (default: whenever ``plan`` or
         ``front_owner`` is given)."""
         check_time_nodes(n_time, lap_solver, time_slab)
         if init_from is not None:
@@ -102,6 +105,11 @@ class AlmSolver:
                 raise ValueError("init_from is not available on time slabs")
             if not getattr(init_from, "finalized", False):
                 raise ValueError("init_from must have been finalised (finalize(download=False) is enough)")
+            if init_parents is not None and int(init_from.n_time) != int(n_time):
+                raise ValueError(f"init_parents: the parent mesh's solver has n_time = {int(init_from.n_time)}, this one {int(n_time)}: "
+                                 "one call changes the mesh or the time grid, not both")
+        elif init_parents is not None:
+            raise ValueError("init_parents needs init_from (the solver on the parent mesh)")
         self.tol_checkpoints = _validate_checkpoints(tol_checkpoints, tol)
         self.geometry = geometry        # (read_out takes the area weights and mu0 / mu1 from it)
         self.checkpoint_solutions = []
@@ -146,7 +154,10 @@ class AlmSolver:
             raise ValueError("preconditioner must be 'multigrid' or 'jacobi'")
         self.prolong_ms = None          # device milliseconds of the transfer from ``init_from``
         if init_from is not None:
-            self.prolong_ms = dev.prolong_from(init_from.dev, init_from.recovery_factors())
+            if init_parents is not None:
+                self.prolong_ms = dev.prolong_space_from(init_from.dev, init_parents, init_from.recovery_factors())
+            else:
+                self.prolong_ms = dev.prolong_from(init_from.dev, init_from.recovery_factors())
             if release_init_from:
                 init_from.close()
         self.mg_summary = self.front_summary = None
@@ -893,6 +904,96 @@ def solver_socp_cascade(n_time, geometry, levels=None, level_tol=None, read_out=
             coarse, alm = alm, None
         coarse.dev.sync()
         hist.solver_stats["cascade"] = {"levels": records, "total_seconds": time.perf_counter() - t_start}
+        return solution, hist
+    finally:
+        for a in (alm, coarse):
+            if a is not None:
+                a.close()
+
+
+# ---- coarse-to-fine cascade in space ---------------------------------------------------------------------------------------------
+def _mesh_cascade_options(geometries, level_tol, kwargs):
+    """The checks of solver_socp_mesh_cascade, before any device is touched: (geometries, level_tol, options)."""
+    from .. import cascade
+
+    try:
+        geometries = list(geometries)
+    except TypeError:
+        raise ValueError("solver_socp_mesh_cascade: geometries must be a list of geometries, coarse to fine") from None
+    if len(geometries) < 2:
+        raise ValueError("solver_socp_mesh_cascade: at least two geometries (a coarse level and its refinement); one level is solver_socp")
+    for key in ("time_slab", "init_from", "init_parents", "levels"):
+        if key in kwargs:
+            raise ValueError(f"solver_socp_mesh_cascade: {key} is not an option of the cascade in space" +
+                             (" (a cascade in time and in space in one call is not supported)" if key == "levels" else ""))
+    unknown = set(kwargs) - set(CASCADE_KEYS)
+    if unknown:
+        raise ValueError(f"solver_socp_mesh_cascade: unknown option(s) {sorted(unknown)}")
+    for i, (coarse, fine) in enumerate(zip(geometries, geometries[1:])):
+        if not isinstance(fine, dict) or fine.get("parents") is None:
+            raise ValueError(f"solver_socp_mesh_cascade: geometry {i + 1} has no 'parents' (meshes.refine_levels / meshes.subdivide)")
+        vp, tp = cascade.check_parents(fine["parents"], n_vertices=np.asarray(coarse["vertices"]).shape[0],
+                                       n_triangles=np.asarray(coarse["triangles"]).shape[0])
+        if (vp.shape[0], tp.shape[0]) != (np.asarray(fine["vertices"]).shape[0], np.asarray(fine["triangles"]).shape[0]):
+            raise ValueError(f"solver_socp_mesh_cascade: the parents of geometry {i + 1} do not have its size")
+    tol = kwargs.get("tol", 1e-4)
+    if level_tol is None:
+        level_tol = tol
+    if not (isinstance(level_tol, (int, float)) and level_tol > 0):
+        raise ValueError("level_tol must be a positive number")
+    _validate_checkpoints(kwargs.get("tol_checkpoints"), tol)
+    if int(kwargs.get("nit", 1000)) < 1:
+        raise ValueError("nit must be at least 1")
+    opts = dict(kwargs)
+    opts.pop("is_multi_threads", None)
+    return geometries, level_tol, opts
+
+
+def solver_socp_mesh_cascade(n_time, geometries, level_tol=None, read_out=None, **kwargs):
+    """``solver_socp`` through a coarse-to-fine cascade in space: the problem is solved on the meshes ``geometries`` (coarse to fine,
+    every one after the first the nested refinement of the one before with its ``parents``: ``meshes.refine_levels``), all at
+    ``n_time``, each level warm-started from the recovered solution of the one before, carried to the refinement on the device
+    (AlmSolver ``init_from`` with ``init_parents``; cascade.prolong_space is the specification).  A level down has a quarter of the
+    vertices and triangles: state, factor, set-up and every launch shrink with them.
+
+    ``level_tol``: the tolerance of the levels below the finest (default ``tol``).  The other keywords are ``solver_socp``'s: ``nit``
+    holds per level, ``time_limit`` for the whole call (a level gets the time that is left), ``init_solution`` starts the coarsest
+    level, ``tol_checkpoints`` belong to the finest level.  Every level starts as a warm start through ``init_solution`` does (r = 1,
+    the initial z scaling, a fresh penalty schedule, validator and history); the coarse solver is released before the finer factor
+    is built.  A cascade in time and in space in one call is not supported: run the levels of ``solver_socp_cascade`` on one mesh,
+    or these on one time grid.
+
+    Returns ``(solution, run_history)`` of the finest level; ``run_history.solver_stats["mesh_cascade"]`` = {"levels": [one record
+    per level: n_vertices, n_triangles, tol, iterations, running_time, setup_seconds, prolong_ms and prolong_bytes (None on the coarsest
+    level), cost, kkt_max, device_bytes], "total_seconds"}.  ``read_out``: as for ``solver_socp``, for the finest level."""
+    geometries, level_tol, opts = _mesh_cascade_options(geometries, level_tol, kwargs)
+    tol, nit = opts.pop("tol", 1e-4), int(opts.pop("nit", 1000))
+    time_limit = opts.pop("time_limit", 1000)
+    init_solution, checkpoints = opts.pop("init_solution", None), opts.pop("tol_checkpoints", None)
+    t_start = time.perf_counter()
+    records = []
+    coarse = alm = None
+    try:
+        for i, geom in enumerate(geometries):
+            last = i + 1 == len(geometries)
+            t0 = time.perf_counter()
+            alm = AlmSolver(n_time, geom, nit=nit, tol=tol if last else level_tol, tol_checkpoints=checkpoints if last else None,
+                            init_solution=init_solution if i == 0 else None, init_from=coarse, init_parents=geom["parents"] if i else None,
+                            release_init_from=True, time_limit=max(time_limit - (t0 - t_start), 0.0), **opts)
+            coarse = None      # (closed by the constructor as soon as the finer state was filled)
+            setup = time.perf_counter() - t0
+            for _ in range(nit):
+                if alm.iterate():
+                    break
+            solution, hist = alm.finalize(download=last, read_out=read_out if last else None)
+            records.append({"n_vertices": int(alm.dev.V), "n_triangles": int(alm.dev.F), "tol": float(alm.tol), "iterations": int(alm.counter_main) + 1,
+                            "running_time": float(hist.running_time), "setup_seconds": float(setup), "prolong_ms": alm.prolong_ms,
+                            "prolong_bytes": getattr(alm.dev, "prolong_bytes", None), "cost": float(hist.history["Transportation cost"][-1]),
+                            "kkt_max": float(np.nanmax(np.asarray(hist.kkt_errors[-1], dtype=np.float64))),
+                            "device_bytes": int(hist.solver_stats["device_bytes"])})
+            coarse, alm = alm, None
+        coarse.dev.sync()
+        hist.solver_stats["mesh_cascade"] = {"levels": records, "total_seconds": time.perf_counter() - t_start}
         return solution, hist
     finally:
         for a in (alm, coarse):

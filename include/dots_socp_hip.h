@@ -521,6 +521,29 @@ typedef struct dots_prolong_desc {
 } dots_prolong_desc;
 int dots_prolong_time(dots_ctx *dst, dots_ctx *src, const dots_prolong_desc *desc);
 
+/* ---- coarse-to-fine cascade in space: the state of a context on the nested refinement of its mesh -----------------------------
+ * dots_prolong_space fills the twelve state arrays of `dst` (the refined mesh) from those of `src` (its parent mesh), both on one
+ * time grid and one device: a vertex row of `dst` takes f * a where its two source rows are one (a kept vertex: a copy of the
+ * recovered value), else (f * a + f * b) * 0.5 (an edge midpoint); a row of a triangle array (B, E) takes f times the row of the same
+ * component of the parent triangle (not projected into the child's plane); a row of a corner array (z_mid, beta_mid) f times the
+ * parent's row of the same corner, interval end and component.  f is the array's factor, as for dots_prolong_time.  The row maps
+ * come from the caller (dots_socp_amd/cascade.py: space_row_maps, from meshes.subdivide's parents and the device numberings of the
+ * two contexts), so that the result is bit for bit what dots_upload of the host's prolongation (cascade.prolong_space) leaves.
+ * `src` and `dst` are treated as by dots_prolong_time (pending division, z_mid, what `dst` carried; stream order; the call returns
+ * when the destination is filled).
+ * DOTS_ERR_ARGUMENT: different n_time, dst == src, a NULL map, n_vertices / n_triangles that are not the destination's V / F, a map
+ * entry that is no row of the source; DOTS_ERR_STATE: a time slab, contexts on different devices, a stale z_mid.  After an error
+ * both contexts are as they were. */
+typedef struct dots_prolong_space_desc {
+    const int32_t *vmap;         /* [n_vertices][2] destination vertex row -> its two source vertex rows (equal: a copy)  */
+    const int32_t *fmap;         /* [n_triangles]   destination triangle -> source triangle (corner k stays corner k)       */
+    int32_t n_vertices;          /* entries of the maps: V and F of `dst`                                                  */
+    int32_t n_triangles;
+    double factor[4];            /* as dots_prolong_desc.factor                                                            */
+    double *ms;                  /* NULL, or out: milliseconds of the launches on the device (events on dst's stream)     */
+} dots_prolong_space_desc;
+int dots_prolong_space(dots_ctx *dst, dots_ctx *src, const dots_prolong_space_desc *desc);
+
 /* ---- read-out of the transport: what the solver plug-ins return (mu, E), formed on the device ---------------------------------
  * dots_readout delivers mu and / or E as dots_download would (reference layouts, the caller's numbering), every value multiplied
  * first by `factor` (the recovered solution, solver_socp.py:397-405: r * dual_scale; 1 = the iterate) and then, where weights are

@@ -1,0 +1,120 @@
+"""Coarse-to-fine cascade in space against the cold solve: for a workload and n_time, ``solver_socp`` on the finest mesh and
+``solver_socp_mesh_cascade`` with one, two and three coarse levels below it in one process, alternating, the host clock around each
+WHOLE call (plans, factorisations of every level, transfers, iterations, download of the solution) ending in a device synchronise;
+per level the stopping iteration and seconds, and the transfer's device milliseconds and bytes.
+
+    python profiles/tools/mesh_cascade_bench.py --mesh torus100k --T 31 [--depths 1,2,3] [--tol 1e-4] [--reps 2] [--level-tol 1e-3]
+
+The meshes are nested by construction: the generator's grid at (nu, nv) / 2^d is the coarsest level, and every refinement step snaps
+the edge midpoints to the generator's grid at twice the resolution (meshes.snap_projection), so the finest level is the generator's
+own mesh at (nu, nv), triangulated as ``_periodic_grid_triangles`` does, numbered by the subdivision.  ``torus100k`` is the torus at
+400 x 256 (102 400 vertices): the 400 x 250 of bench.py has a single nested level below it (250 / 4 is not an integer).  The knot is
+bench.py's 216 x 20 tube: two nested levels exist below it (108 x 10, 54 x 5), so a depth of three is refused.  All levels are
+normalised with the finest mesh's bounding box; the densities are the recipe of ``meshes.example`` around three vertices of the
+coarsest level (present on every level).  Building the levels on the host is not part of the timed calls: they are the input.
+
+Prints one JSON line per call (kind = "cold" / "cascade") and a summary line.  The transfer's device milliseconds are set against the
+bytes it moves (every source and destination array once) at 6.3 TB/s, the copy rate DESIGN.md quotes.  bench.py is unchanged."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+
+COPY_BPS = 6.3e12
+GRIDS = {"torus100k": ("torus", 400, 256), "knot": ("knot", 216, 20), "torus6k": ("torus", 96, 64)}
+
+
+def generator(kind, nu, nv):
+    from dots_socp_amd import meshes
+
+    return meshes.torus(nu, nv) if kind == "torus" else meshes.torus_knot_tube(2, 5, nu, nv)
+
+
+def build_levels(mesh, depth):
+    """``depth + 1`` nested geometries, coarse to fine, the last one the generator's mesh at its full resolution."""
+    import numpy as np
+
+    from dots_socp_amd import meshes
+
+    kind, nu, nv = GRIDS[mesh]
+    if nu % (1 << depth) or nv % (1 << depth) or (nv >> depth) < 3:
+        raise SystemExit(f"{mesh}: {nu} x {nv} has no nested level {depth} steps down")
+    fine_v = generator(kind, nu, nv)[0]
+    lo, scale = fine_v.min(axis=0), 1.0 / (fine_v.max(axis=0) - fine_v.min(axis=0)).max()
+    norm = lambda v: (v - lo) * scale      # noqa: E731
+    v0, t0 = generator(kind, nu >> depth, nv >> depth)
+    coarse, _ = meshes.make_geometry(norm(v0), t0, normalize=False)
+    c = meshes.farthest_vertices(coarse["vertices"], 0, 3)
+    dens = lambda v, a: (meshes.bump_density(v, a, [c[0]], 0.35, 0.05), meshes.bump_density(v, a, [c[1], c[2]], 0.35, 0.05))      # noqa: E731
+    coarse["mu0"], coarse["mu1"] = dens(coarse["vertices"], coarse["area_vertices"])
+    steps = [meshes.snap_projection(norm(generator(kind, nu >> d, nv >> d)[0])) for d in range(depth - 1, -1, -1)]
+    levels = meshes.refine_levels(coarse, depth + 1, project=steps, densities=dens)
+    assert np.asarray(levels[-1]["vertices"]).shape[0] == nu * nv
+    return levels
+
+
+def sync():
+    import torch
+
+    torch.cuda.synchronize()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mesh", default="knot", choices=sorted(GRIDS))
+    ap.add_argument("--T", type=int, default=31)
+    ap.add_argument("--tol", type=float, default=1e-4)
+    ap.add_argument("--nit", type=int, default=20000)
+    ap.add_argument("--reps", type=int, default=2)
+    ap.add_argument("--depths", default="1,2,3", help="comma-separated numbers of coarse levels")
+    ap.add_argument("--level-tol", type=float, default=None)
+    ap.add_argument("--congestion", type=float, default=0.0)
+    a = ap.parse_args()
+
+    import numpy as np
+
+    from dots_socp_amd.socp import solver_socp, solver_socp_mesh_cascade
+
+    depths = [int(x) for x in a.depths.split(",")]
+    deepest = build_levels(a.mesh, max(depths))
+    fine = deepest[-1]
+    V = int(np.asarray(fine["vertices"]).shape[0])
+    common = dict(tol=a.tol, nit=a.nit, congestion=a.congestion, time_limit=1e9)
+    base = dict(mesh=a.mesh, n_time=a.T, vertices=V, tol=a.tol, congestion=a.congestion)
+    best = {}
+    for rep in range(a.reps):
+        for depth in [0] + depths:
+            kind = "cold" if depth == 0 else "cascade"
+            sync()
+            t0 = time.perf_counter()
+            if depth == 0:
+                sol, hist = solver_socp(a.T, fine, **common)
+            else:
+                sol, hist = solver_socp_mesh_cascade(a.T, deepest[-depth - 1:], level_tol=a.level_tol, **common)
+            sync()
+            wall = time.perf_counter() - t0
+            out = dict(base, kind=kind, depth=depth, rep=rep, wall_s=round(wall, 4), iterations=int(hist.kkt_iteration[-1]) + 1,
+                       running_time=round(float(hist.running_time), 4), cost=float(hist.history["Transportation cost"][-1]),
+                       kkt_max=float(np.nanmax(np.asarray(hist.kkt_errors[-1], dtype=np.float64))))
+            if depth:
+                rec = hist.solver_stats["mesh_cascade"]["levels"]
+                for r in rec:
+                    if r["prolong_ms"]:
+                        r["prolong_floor_ms"] = round(1e3 * r["prolong_bytes"] / COPY_BPS, 4)
+                        r["prolong_tb_per_s"] = round(r["prolong_bytes"] / (1e-3 * r["prolong_ms"]) / 1e12, 3)
+                out["levels"] = rec
+                out["level_tol"] = a.level_tol
+            best[depth] = min(best.get(depth, wall), wall)
+            del sol, hist
+            print(json.dumps(out), flush=True)
+    print(json.dumps(dict(base, kind="summary", level_tol=a.level_tol, cold_wall_s=round(best[0], 4),
+                          cascade_wall_s={str(d): round(best[d], 4) for d in depths},
+                          cold_over_cascade={str(d): round(best[0] / best[d], 3) for d in depths})), flush=True)
+
+
+if __name__ == "__main__":
+    main()
