@@ -20,6 +20,10 @@ same operations on the same numbers.
 The transfer in space (``prolong_space``; ``dots_prolong_space``, k_prolong_space in csrc/kernels_alm.hip) goes from a mesh to its
 nested refinement (``meshes.subdivide``: ``parents``) on one time grid; ``space_row_maps`` turns ``parents`` and the two device
 numberings into the row maps the kernel reads.
+
+Between two independent triangulations of one surface (no ``parents``) the transfer is barycentric (``transfer_space``;
+``dots_transfer_space``, k_transfer_space): ``locate`` finds the closest point of the coarse mesh to every fine vertex and triangle
+centroid, ``mesh_transfer`` turns that into the tables of the transfer, ``transfer_row_maps`` puts them into the two device numberings.
 """
 from __future__ import annotations
 
@@ -199,3 +203,222 @@ def space_row_maps(parents, n_src_vertices, n_src_triangles, perm_vert_dst=None,
     vmap = inverse(perm_vert_src, int(n_src_vertices))[vd]
     fmap = inverse(perm_tri_src, int(n_src_triangles))[td]
     return np.ascontiguousarray(vmap, dtype=np.int32), np.ascontiguousarray(fmap, dtype=np.int32)
+
+
+# ---- coarse-to-fine in space between two independent triangulations of one surface -----------------------------------------------
+LOCATE_CHUNK = 1 << 16      # points per pass of locate (bounds the candidate arrays)
+
+
+def closest_on_triangles(p, a, b, c):
+    """The closest point to ``p[i]`` on the triangle ``(a[i], b[i], c[i])``, all (N, 3): ``(weights (N, 3), distance (N,))`` with the
+    clamped barycentric weights of the corners, all >= 0 and summing to 1.  The region test of Ericson's closest-point-on-triangle
+    (Real-Time Collision Detection, 5.1.5), vectorised: vertex regions, edge regions, then the interior."""
+    ab, ac, ap = b - a, c - a, p - a
+    dot = lambda x, y: np.einsum("ij,ij->i", x, y)      # noqa: E731
+    d1, d2 = dot(ab, ap), dot(ac, ap)
+    bp = p - b
+    d3, d4 = dot(ab, bp), dot(ac, bp)
+    cp = p - c
+    d5, d6 = dot(ab, cp), dot(ac, cp)
+    vc, vb, va = d1 * d4 - d3 * d2, d5 * d2 - d1 * d6, d3 * d6 - d5 * d4
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t_ab, t_ac = d1 / (d1 - d3), d2 / (d2 - d6)
+        t_bc = (d4 - d3) / ((d4 - d3) + (d5 - d6))
+        denom = 1.0 / (va + vb + vc)
+    v_in, w_in = vb * denom, vc * denom
+    zero, one = np.zeros_like(d1), np.ones_like(d1)
+    conds = [(d1 <= 0) & (d2 <= 0), (d3 >= 0) & (d4 <= d3), (vc <= 0) & (d1 >= 0) & (d3 <= 0), (d6 >= 0) & (d5 <= d6),
+             (vb <= 0) & (d2 >= 0) & (d6 <= 0), (va <= 0) & (d4 - d3 >= 0) & (d5 - d6 >= 0)]
+    w1 = np.select(conds, [zero, one, t_ab, zero, zero, 1.0 - t_bc], default=v_in)
+    w2 = np.select(conds, [zero, zero, zero, one, t_ac, t_bc], default=w_in)
+    w1, w2 = np.clip(w1, 0.0, 1.0), np.clip(w2, 0.0, 1.0)
+    w0 = np.maximum(1.0 - w1 - w2, 0.0)
+    w = np.stack([w0, w1, w2], axis=1)
+    q = w0[:, None] * a + w1[:, None] * b + w2[:, None] * c
+    return w, np.linalg.norm(p - q, axis=1)
+
+
+def locate(points, vertices, triangles, k=3):
+    """The closest point of the mesh ``(vertices, triangles)`` to every one of ``points``: ``(triangle (N,) int64, weights (N, 3),
+    distance (N,))``.  The candidates of a point are the triangles incident to its ``k`` nearest mesh vertices; of these the one with
+    the smallest distance (``closest_on_triangles``) is kept, on a tie the one with the smallest index.  This rule is the definition
+    of the result (deterministic; no claim beyond the candidate set).  A triangle of zero area raises ``ValueError``."""
+    from scipy.spatial import cKDTree
+
+    p = np.ascontiguousarray(points, dtype=np.float64)
+    v = np.ascontiguousarray(vertices, dtype=np.float64)
+    t = np.asarray(triangles).astype(np.int64)
+    if p.ndim != 2 or p.shape[1] != 3 or v.ndim != 2 or v.shape[1] != 3 or t.ndim != 2 or t.shape[1] != 3 or t.shape[0] < 1:
+        raise ValueError("locate: points (N, 3), vertices (V, 3) and triangles (F, 3) expected")
+    if t.min() < 0 or t.max() >= v.shape[0]:
+        raise ValueError("locate: a triangle names a vertex the mesh does not have")
+    if not np.all(np.linalg.norm(np.cross(v[t[:, 1]] - v[t[:, 0]], v[t[:, 2]] - v[t[:, 0]]), axis=1) > 0.0):
+        raise ValueError("locate: the mesh has a triangle of zero area")
+    k = max(1, min(int(k), v.shape[0]))
+    # the triangles around every vertex as a padded table (V, max degree), -1 where a vertex has fewer
+    corner_vertex = t.reshape(-1)
+    order = np.argsort(corner_vertex, kind="stable")
+    degree = np.bincount(corner_vertex, minlength=v.shape[0])
+    start = np.concatenate([[0], np.cumsum(degree)])
+    around = np.full((v.shape[0], max(int(degree.max()), 1)), -1, dtype=np.int64)
+    sorted_vertex = corner_vertex[order]
+    around[sorted_vertex, np.arange(order.size) - start[sorted_vertex]] = order // 3
+    tree = cKDTree(v)
+    tri = np.empty(p.shape[0], dtype=np.int64)
+    weights = np.empty((p.shape[0], 3))
+    distance = np.empty(p.shape[0])
+    for lo in range(0, p.shape[0], LOCATE_CHUNK):
+        pc = p[lo:lo + LOCATE_CHUNK]
+        near = tree.query(pc, k=k)[1].reshape(pc.shape[0], k)
+        cand = np.sort(around[near].reshape(pc.shape[0], -1), axis=1)      # (ascending: the first minimum is the smallest index)
+        n_c = cand.shape[1]
+        f = np.maximum(cand, 0).reshape(-1)
+        w, d = closest_on_triangles(np.repeat(pc, n_c, axis=0), v[t[f, 0]], v[t[f, 1]], v[t[f, 2]])
+        d = np.where(cand >= 0, d.reshape(pc.shape[0], n_c), np.inf)
+        if not np.all(np.isfinite(d.min(axis=1))):
+            raise ValueError("locate: a nearest vertex belongs to no triangle")
+        best = np.argmin(d, axis=1)
+        rows = np.arange(pc.shape[0])
+        tri[lo:lo + pc.shape[0]] = cand[rows, best]
+        weights[lo:lo + pc.shape[0]] = w.reshape(pc.shape[0], n_c, 3)[rows, best]
+        distance[lo:lo + pc.shape[0]] = d[rows, best]
+    return tri, weights, distance
+
+
+def mesh_transfer(coarse_geometry, fine_geometry):
+    """The transfer from the mesh of ``coarse_geometry`` to that of ``fine_geometry``, two independent triangulations of one surface
+    in the same coordinates (normalise them together): a dict with
+
+    * ``vertex_sources`` (Vf, 3) int32, ``vertex_weights`` (Vf, 3) float64: the three coarse vertices of the triangle ``locate``
+      finds for every fine vertex, in that triangle's corner order, and their clamped barycentric weights;
+    * ``triangle_source`` (Ff,) int32: the coarse triangle located for the centroid of every fine triangle;
+    * ``corner_source`` (Ff, 3) int32: for the fine corner ``(f', k)`` the corner of ``triangle_source[f']`` with the largest clamped
+      barycentric weight of the fine vertex ``triangles_f[f', k]`` with respect to that one triangle (a tie: the smallest corner);
+    * ``max_distance``: the largest distance of a fine vertex or centroid from the coarse mesh; ``n_source_vertices``,
+      ``n_source_triangles``.
+
+    ``ValueError`` when ``max_distance`` exceeds the longest edge of the coarse mesh: not the same surface, or not the same scaling."""
+    vc = np.asarray(coarse_geometry["vertices"], dtype=np.float64)
+    tc = np.asarray(coarse_geometry["triangles"]).astype(np.int64)
+    vf = np.asarray(fine_geometry["vertices"], dtype=np.float64)
+    tf = np.asarray(fine_geometry["triangles"]).astype(np.int64)
+    tri_v, w_v, d_v = locate(vf, vc, tc)
+    centroid = (vf[tf[:, 0]] + vf[tf[:, 1]] + vf[tf[:, 2]]) / 3.0
+    tri_f, _, d_f = locate(centroid, vc, tc)
+    corner = np.empty((tf.shape[0], 3), dtype=np.int32)
+    for k in range(3):
+        w, _ = closest_on_triangles(vf[tf[:, k]], vc[tc[tri_f, 0]], vc[tc[tri_f, 1]], vc[tc[tri_f, 2]])
+        corner[:, k] = np.argmax(w, axis=1)      # (the first maximum: the smallest corner index on a tie)
+    max_distance = float(max(d_v.max(), d_f.max()))
+    edges = np.concatenate([vc[tc[:, 1]] - vc[tc[:, 0]], vc[tc[:, 2]] - vc[tc[:, 1]], vc[tc[:, 0]] - vc[tc[:, 2]]], axis=0)
+    longest = float(np.linalg.norm(edges, axis=1).max())
+    if not max_distance <= longest:
+        raise ValueError(f"mesh_transfer: the fine mesh is up to {max_distance:.3g} away from the coarse one, whose longest edge is "
+                         f"{longest:.3g}: not the same surface, or not the same scaling (normalise the geometries together)")
+    return {"vertex_sources": np.ascontiguousarray(tc[tri_v], dtype=np.int32), "vertex_weights": np.ascontiguousarray(w_v),
+            "triangle_source": np.ascontiguousarray(tri_f, dtype=np.int32), "corner_source": corner, "max_distance": max_distance,
+            "n_source_vertices": int(vc.shape[0]), "n_source_triangles": int(tc.shape[0])}
+
+
+def check_transfer(transfer, n_vertices=None, n_triangles=None):
+    """``(vertex_sources (Vf, 3), vertex_weights (Vf, 3), triangle_source (Ff,), corner_source (Ff, 3))`` of ``transfer``
+    (``mesh_transfer``), the index arrays as int64; ``n_vertices`` / ``n_triangles``: the size of the source mesh it must refer to."""
+    try:
+        vs, vw = np.asarray(transfer["vertex_sources"]), np.asarray(transfer["vertex_weights"])
+        ts, cs = np.asarray(transfer["triangle_source"]), np.asarray(transfer["corner_source"])
+        nv, nt = int(transfer["n_source_vertices"]), int(transfer["n_source_triangles"])
+    except (KeyError, TypeError, IndexError, ValueError):
+        raise ValueError("transfer must hold 'vertex_sources', 'vertex_weights', 'triangle_source', 'corner_source', 'n_source_vertices' "
+                         "and 'n_source_triangles' (cascade.mesh_transfer)") from None
+    if vs.ndim != 2 or vs.shape[1] != 3 or vs.shape[0] < 1 or vw.shape != vs.shape:
+        raise ValueError("transfer: vertex_sources and vertex_weights must be (Vf, 3)")
+    if ts.ndim != 1 or ts.shape[0] < 1 or cs.shape != (ts.shape[0], 3):
+        raise ValueError("transfer: triangle_source must be (Ff,) and corner_source (Ff, 3)")
+    if not all(np.issubdtype(a.dtype, np.integer) for a in (vs, ts, cs)):
+        raise ValueError("transfer: integer index arrays expected")
+    if not np.issubdtype(vw.dtype, np.floating):
+        raise ValueError("transfer: floating-point weights expected")
+    vs, ts, cs, vw = vs.astype(np.int64), ts.astype(np.int64), cs.astype(np.int64), vw.astype(np.float64)
+    if vs.min() < 0 or vs.max() >= nv or ts.min() < 0 or ts.max() >= nt:
+        raise ValueError("transfer: an index outside the source mesh")
+    if cs.min() < 0 or cs.max() > 2:
+        raise ValueError("transfer: corner_source must be 0, 1 or 2")
+    if not (np.all(np.isfinite(vw)) and np.all(vw >= 0.0)):
+        raise ValueError("transfer: the weights must be finite and >= 0")
+    if n_vertices is not None and nv != int(n_vertices):
+        raise ValueError(f"transfer: from a mesh of {nv} vertices, not {int(n_vertices)}")
+    if n_triangles is not None and nt != int(n_triangles):
+        raise ValueError(f"transfer: from a mesh of {nt} triangles, not {int(n_triangles)}")
+    return vs, vw, ts, cs
+
+
+def transfer_space(array, name, transfer):
+    """``array`` (the state array ``name`` on the source mesh of ``transfer``, reference layout) on the destination mesh; the time axis
+    is untouched.
+
+    * vertex arrays: ``(w0 * x[..., s0] + w1 * x[..., s1]) + w2 * x[..., s2]`` with the three sources and weights of the vertex, in
+      exactly this order of operations and with no special case for a weight of 0 or 1;
+    * triangle arrays (``B``, ``E``): a triangle takes the three components of ``triangle_source`` unchanged.  As in
+      ``prolong_space`` they are NOT re-projected into the destination triangle's plane: the small normal component is left to the
+      first iterations on the destination mesh;
+    * corner arrays (``z_mid``, ``beta_mid``): corner ``(f', k)`` takes corner ``(triangle_source[f'], corner_source[f', k])`` for
+      both interval ends and every component."""
+    a = np.asarray(array, dtype=np.float64)
+    if name in VERTEX_ARRAYS:
+        if a.ndim != 2:
+            raise ValueError(f"{name}: expected (time, V), got shape {a.shape}")
+        vs, vw, _, _ = check_transfer(transfer, n_vertices=a.shape[-1])
+        return (vw[:, 0] * a[..., vs[:, 0]] + vw[:, 1] * a[..., vs[:, 1]]) + vw[:, 2] * a[..., vs[:, 2]]
+    if name in TRIANGLE_ARRAYS:
+        if a.ndim != 3 or a.shape[-1] != 3:
+            raise ValueError(f"{name}: expected (time, F, 3), got shape {a.shape}")
+        _, _, ts, _ = check_transfer(transfer, n_triangles=a.shape[-2])
+        return np.ascontiguousarray(a[..., ts, :])
+    if name in CORNER_ARRAYS:
+        if a.ndim != 5 or a.shape[1:3] != (2, 3) or a.shape[-1] != 3:
+            raise ValueError(f"{name}: expected (time, 2, 3, F, 3), got shape {a.shape}")
+        _, _, ts, cs = check_transfer(transfer, n_triangles=a.shape[-2])
+        return np.ascontiguousarray(a[:, :, cs.T, ts[None, :], :])      # [t][s][k][f'][c] = a[t][s][cs[f'][k]][ts[f']][c]
+    raise ValueError(f"unknown state array {name!r}")
+
+
+def transfer_space_solution(solution, transfer):
+    """Every state array of ``solution`` (a dict as ``solver_socp`` returns it) on the destination mesh of ``transfer``: an
+    ``init_solution``."""
+    names = VERTEX_ARRAYS + TRIANGLE_ARRAYS + CORNER_ARRAYS
+    return {k: transfer_space(v, k, transfer) for k, v in solution.items() if k in names and v is not None}
+
+
+def transfer_row_maps(transfer, perm_vert_dst=None, perm_tri_dst=None, perm_vert_src=None, perm_tri_src=None):
+    """The tables of ``dots_transfer_space``: ``vsrc`` (Vf, 3) int32, the three source device rows of every destination device vertex
+    row, ``vw`` (Vf, 3) their weights, ``fsrc`` (Ff,) int32, the source device triangle of every destination device triangle, and
+    ``csrc`` (Ff, 3) int32.  ``perm[i]`` = caller index of device row i (None = identity), as in ``space_row_maps``.  A renumbering
+    permutes the rows of the tables and renames the sources; the order of a vertex's three sources is never changed, so the sums do
+    not depend on the numberings.  The plans keep the corner order inside a triangle (as ``space_row_maps`` relies on), so
+    ``corner_source`` is carried over as it is."""
+    vs, vw, ts, cs = check_transfer(transfer)
+    n_src_v, n_src_t = int(transfer["n_source_vertices"]), int(transfer["n_source_triangles"])
+
+    def inverse(perm, n):
+        if perm is None:
+            return np.arange(n, dtype=np.int64)
+        perm = np.asarray(perm, dtype=np.int64)
+        if perm.shape != (n,):
+            raise ValueError("transfer_row_maps: a permutation of the wrong size")
+        inv = np.empty(n, dtype=np.int64)
+        inv[perm] = np.arange(n)
+        return inv
+
+    for perm, n in ((perm_vert_dst, vs.shape[0]), (perm_tri_dst, ts.shape[0])):
+        if perm is not None and np.asarray(perm).shape != (n,):
+            raise ValueError("transfer_row_maps: a permutation of the wrong size")
+    if perm_vert_dst is not None:
+        pv = np.asarray(perm_vert_dst, dtype=np.int64)
+        vs, vw = vs[pv], vw[pv]
+    if perm_tri_dst is not None:
+        pt = np.asarray(perm_tri_dst, dtype=np.int64)
+        ts, cs = ts[pt], cs[pt]
+    vsrc = inverse(perm_vert_src, n_src_v)[vs]
+    fsrc = inverse(perm_tri_src, n_src_t)[ts]
+    return (np.ascontiguousarray(vsrc, dtype=np.int32), np.ascontiguousarray(vw, dtype=np.float64),
+            np.ascontiguousarray(fsrc, dtype=np.int32), np.ascontiguousarray(cs, dtype=np.int32))

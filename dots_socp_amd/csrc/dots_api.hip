@@ -1536,6 +1536,73 @@ int dots_prolong_space(dots_ctx *dst, dots_ctx *src, const dots_prolong_space_de
     return 0;
 }
 
+int dots_transfer_space(dots_ctx *dst, dots_ctx *src, const dots_transfer_space_desc *desc) {
+    if (!dst || !src || !desc) { set_error("transfer_space: null argument"); return DOTS_ERR_ARGUMENT; }
+    if (dst == src) { set_error("transfer_space: source and destination are one context"); return DOTS_ERR_ARGUMENT; }
+    if (dst->shard_stride != 0 || src->shard_stride != 0) { set_error("transfer_space: not available on time slabs"); return DOTS_ERR_STATE; }
+    if (dst->device != src->device) { set_error("transfer_space: the contexts are on different devices"); return DOTS_ERR_STATE; }
+    const Dev &dd = dst->d, &ds = src->d;
+    if (dd.T != ds.T) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "transfer_space: n_time = %d, the source's %d: both levels have one time grid", dd.T, ds.T);
+        set_error(buf);
+        return DOTS_ERR_ARGUMENT;
+    }
+    if (!desc->vsrc || !desc->vw || !desc->fsrc || !desc->csrc) { set_error("transfer_space: null table"); return DOTS_ERR_ARGUMENT; }
+    if (desc->n_vertices != dd.V || desc->n_triangles != dd.F) {
+        char buf[200];
+        snprintf(buf, sizeof buf, "transfer_space: tables of %d vertices and %d triangles, the destination has %d and %d", desc->n_vertices,
+                 desc->n_triangles, dd.V, dd.F);
+        set_error(buf);
+        return DOTS_ERR_ARGUMENT;
+    }
+    // every index names a row / a corner of the source; every weight is a finite number >= 0
+    const size_t nv = 3 * (size_t)dd.V, nf = (size_t)dd.F;
+    for (size_t i = 0; i < nv; ++i) {
+        if (desc->vsrc[i] < 0 || desc->vsrc[i] >= ds.V) { set_error("transfer_space: vsrc entry out of range"); return DOTS_ERR_ARGUMENT; }
+        if (!(desc->vw[i] >= 0.0 && std::isfinite(desc->vw[i]))) { set_error("transfer_space: a weight that is negative or not finite"); return DOTS_ERR_ARGUMENT; }
+    }
+    for (size_t i = 0; i < nf; ++i)
+        if (desc->fsrc[i] < 0 || desc->fsrc[i] >= ds.F) { set_error("transfer_space: fsrc entry out of range"); return DOTS_ERR_ARGUMENT; }
+    for (size_t i = 0; i < 3 * nf; ++i)
+        if (desc->csrc[i] < 0 || desc->csrc[i] > 2) { set_error("transfer_space: csrc entry outside 0 .. 2"); return DOTS_ERR_ARGUMENT; }
+    int rc = check(src, true);      // (a pending penalty division is carried out, as for a download)
+    if (rc) return rc;
+    if (src->zmid_stale) { set_error("transfer_space: the source's z_mid was not materialised by its last step (dots_step_flags)"); return DOTS_ERR_STATE; }
+    if ((rc = materialise_zmid(src))) return rc;
+    if ((rc = check(dst, false, true))) return rc;
+    dst->pending_div = 0.0;      // (every array a pending division would have touched is replaced)
+    // the tables in one device buffer: [vw | vsrc | fsrc | csrc]
+    char *buf = nullptr;
+    DOTS_HIP(hipMalloc((void **)&buf, sizeof(double) * nv + sizeof(int32_t) * (nv + 4 * nf)));
+    double *vw = (double *)buf;
+    int *vs = (int *)(vw + nv), *fs = vs + nv, *cs = fs + nf;
+    hipError_t e = hipMemcpyAsync(vw, desc->vw, sizeof(double) * nv, hipMemcpyHostToDevice, dst->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(vs, desc->vsrc, sizeof(int32_t) * nv, hipMemcpyHostToDevice, dst->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(fs, desc->fsrc, sizeof(int32_t) * nf, hipMemcpyHostToDevice, dst->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(cs, desc->csrc, sizeof(int32_t) * 3 * nf, hipMemcpyHostToDevice, dst->stream);
+    if (e != hipSuccess) rc = hip_fail(e, "transfer_space: tables", __FILE__, __LINE__);
+    // the destination's stream waits for what the source has enqueued (its last step, the division, z_mid)
+    if (!rc) rc = batch_wait(dst, src);
+    if (!rc && (e = hipEventRecord(dst->ev[0], dst->stream)) != hipSuccess) rc = hip_fail(e, "hipEventRecord", __FILE__, __LINE__);
+    const int group[DOTS_N_ARRAYS] = {0, 0, 0, 0, 1, 1, 1, 2, 2, 3, 3, 3};      // recorver_scaled_solution (solver_socp.py:397-405)
+    for (int id = 0; id < DOTS_N_ARRAYS && !rc; ++id) rc = launch_transfer_space(dst, src, id, vs, vw, fs, cs, desc->factor[group[id]]);
+    if (!rc && (e = hipEventRecord(dst->ev[1], dst->stream)) != hipSuccess) rc = hip_fail(e, "hipEventRecord", __FILE__, __LINE__);
+    if (!rc) rc = batch_wait(src, dst);      // (whatever the source does next -- its release included -- comes after the reads)
+    e = hipStreamSynchronize(dst->stream);
+    if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__);
+    (void)hipFree(buf);
+    if (rc) return rc;
+    dst->zmid_stale = dst->zmid_deferred = 0;      // (z_mid's storage holds the transferred z_mid)
+    dst->kkt_halo_fresh = 0;
+    if (desc->ms) {
+        float t = 0.f;
+        DOTS_HIP(hipEventElapsedTime(&t, dst->ev[0], dst->ev[1]));
+        *desc->ms = t;
+    }
+    return 0;
+}
+
 // ---- dots_readout ---------------------------------------------------------------------------------------------------------
 // the inverse of the device numbering, the copy stream, the chunk events and the host memory of the layer sums: once per context
 static int readout_prepare(Ctx *c) {

@@ -1590,6 +1590,117 @@ int launch_prolong_space(Ctx *dst, Ctx *src, int id, const int *vmap, const int 
 }
 
 // ------------------------------------------------------------------------------------------
+// space transfer (dots_transfer_space): one state array of a context on another triangulation of the same surface, same time grid
+// ------------------------------------------------------------------------------------------
+// A destination vertex row is the barycentric combination of three source vertex rows, (w0 * (f * a0) + w1 * (f * a1)) + w2 * (f * a2)
+// -- the operations of cascade.transfer_space on the recovered solution, in that order and with no special case for a weight of 0 or
+// 1 (-ffp-contract=off) --; a triangle row f times the row of the same component of the located source triangle, a corner row f times
+// the row of the located corner, same interval end and component.  The shape is k_prolong_space's: a lane forms two neighbouring
+// columns (16-byte words in, one out), a row's indices and weights are read once per row, a row wider than 256 columns is walked in
+// chunks of 256, columns outside the array's time points are written as zero, and a workgroup takes runs of consecutive destination
+// rows: neighbouring destination vertices / triangles under a locality numbering lie in the same or in neighbouring source triangles,
+// so most of the 3 source rows per vertex row come from the cache.
+struct TransferSpaceArgs {
+    const double *src;
+    double *dst;
+    const int *vsrc;         // VERT: [entities][3] source vertex rows
+    const double *vw;        // VERT: [entities][3] weights
+    const int *fsrc;         // else: [entities] source triangle
+    const int *csrc;         // corner arrays: [entities][3] source corner of every destination corner
+    int64_t rows;            // destination rows
+    int64_t run;             // rows per run
+    int sh;                  // log2 of the time pitch (both sides)
+    int n_valid;             // time points of the array: T + 1 (node arrays) or T
+    double f;
+};
+
+template <int RPE>      // rows per vertex / triangle: 1, 3 (B, E), 18 (corner arrays: row = ((f * 3 + k) * 2 + s) * 3 + c, column = interval + s)
+__global__ __launch_bounds__(BLOCK) void k_transfer_space(TransferSpaceArgs a) {
+    const int tid = threadIdx.x;
+    const int hp = a.sh - 1;                      // log2 of the column pairs per row
+    const int hl = min(hp, 7);                    // log2 of the lanes per row: at most 128 pairs = 256 columns per chunk
+    const int rpp = BLOCK >> hl;                  // rows per pass
+    const int rr = tid >> hl, p0 = tid & ((1 << hl) - 1);
+    const int64_t n_runs = (a.rows + a.run - 1) / a.run;
+    for (int64_t run = blockIdx.x; run < n_runs; run += gridDim.x) {
+        const int64_t r_end = min(a.rows, (run + 1) * a.run);
+        for (int64_t r = run * a.run + rr; r < r_end; r += rpp) {
+            double *y = a.dst + (r << a.sh);
+            if (RPE == 1) {
+                const int *s = a.vsrc + 3 * r;
+                const double *w = a.vw + 3 * r;
+                const double w0 = w[0], w1 = w[1], w2 = w[2];
+                const double *x0 = a.src + ((int64_t)s[0] << a.sh), *x1 = a.src + ((int64_t)s[1] << a.sh), *x2 = a.src + ((int64_t)s[2] << a.sh);
+                for (int p = p0; p < (1 << hp); p += 1 << hl) {
+                    const D2 v0 = ld2(x0 + 2 * p), v1 = ld2(x1 + 2 * p), v2 = ld2(x2 + 2 * p);
+                    D2 out;
+#pragma unroll
+                    for (int q = 0; q < 2; ++q) {
+                        out.v[q] = (w0 * (a.f * v0.v[q]) + w1 * (a.f * v1.v[q])) + w2 * (a.f * v2.v[q]);
+                        if (2 * p + q >= a.n_valid) out.v[q] = 0.0;
+                    }
+                    st2(y + 2 * p, out);
+                }
+            } else {
+                const int64_t ent = r / RPE;
+                const int sub = (int)(r - ent * RPE);
+                int64_t rs = a.fsrc[ent];
+                int s = 0;
+                if (RPE == 18) {      // sub = (k * 2 + s) * 3 + c
+                    const int k = sub / 6, rest = sub - 6 * k;
+                    s = rest / 3;
+                    rs = (rs * 3 + a.csrc[3 * ent + k]) * 6 + rest;
+                } else {
+                    rs = rs * 3 + sub;
+                }
+                const double *x = a.src + (rs << a.sh);
+                for (int p = p0; p < (1 << hp); p += 1 << hl) {
+                    const D2 v = ld2(x + 2 * p);
+                    D2 out;
+#pragma unroll
+                    for (int q = 0; q < 2; ++q) {
+                        const int t = 2 * p + q - s;
+                        out.v[q] = (t < 0 || t >= a.n_valid) ? 0.0 : a.f * v.v[q];
+                    }
+                    st2(y + 2 * p, out);
+                }
+            }
+        }
+    }
+}
+
+int launch_transfer_space(Ctx *dst, Ctx *src, int id, const int *vsrc, const double *vw, const int *fsrc, const int *csrc, double f) {
+    const Dev &dd = dst->d;
+    const int kind = array_kind(id);
+    TransferSpaceArgs a{};
+    a.src = src->arr(id);
+    a.dst = dst->arr(id);
+    a.vsrc = vsrc;
+    a.vw = vw;
+    a.fsrc = fsrc;
+    a.csrc = csrc;
+    const int rpe = kind <= 1 ? 1 : (kind == 2 ? 3 : 18);
+    a.rows = (int64_t)rpe * (kind <= 1 ? dd.V : dd.F);
+    a.sh = dd.tp_shift;
+    a.n_valid = dd.T + ((kind == 0 || kind == 2) ? 1 : 0);
+    a.f = f;
+    if (a.sh < 1 || dd.TP > TILE_ELEMS || a.sh != src->d.tp_shift) { set_error("transfer_space: time pitch out of range"); return DOTS_ERR_STATE; }
+    // a run: whole vertices / triangles, whole passes of the workgroup, about 32 KB of destination
+    const int rpp = BLOCK >> std::min(a.sh - 1, 7);
+    int64_t unit = rpe;
+    while (unit % rpp) unit *= 2;
+    const int64_t row_bytes = (int64_t)sizeof(double) << a.sh;
+    a.run = unit * std::max<int64_t>(1, (32768 + unit * row_bytes - 1) / (unit * row_bytes));
+    const int64_t n_runs = (a.rows + a.run - 1) / a.run;
+    const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(n_runs, 4096)));
+    if (rpe == 1) hipLaunchKernelGGL(k_transfer_space<1>, grid, dim3(BLOCK), 0, dst->stream, a);
+    else if (rpe == 3) hipLaunchKernelGGL(k_transfer_space<3>, grid, dim3(BLOCK), 0, dst->stream, a);
+    else hipLaunchKernelGGL(k_transfer_space<18>, grid, dim3(BLOCK), 0, dst->stream, a);
+    DOTS_HIP(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
 // standalone operators (rows a4-a6): same index arithmetic as the fused kernels, exposed so each
 // reference function has a one-to-one parity test.  in/out are device-layout scratch arrays.
 // ------------------------------------------------------------------------------------------

@@ -239,6 +239,36 @@ class DeviceProblem:
         self.prolong_bytes = 8 * pitch * (8 * (self.V + src.V) + (2 * 3 + 2 * 18) * (self.F + src.F))
         return ms.value
 
+    def transfer_space_from(self, src: "DeviceProblem", transfer, factors=(1.0, 1.0, 1.0, 1.0)):
+        """Fill this context's twelve state arrays from those of ``src``, a context on another triangulation of the same surface
+        (``transfer``: ``cascade.mesh_transfer`` from its mesh to this one) with the same ``n_time`` on the same device
+        (dots_transfer_space; cascade.transfer_space is the specification).  ``factors``: as for ``prolong_from``.  Returns the
+        milliseconds of the launches; ``self.prolong_bytes``: one pass over this context's state (8 vertex arrays of V rows, 2 x 3 F
+        triangle rows, 2 x 18 F corner rows, ``pitch`` doubles each), plus three source rows per vertex row, plus one source row per
+        triangle / corner row: ``8 * pitch * (8 * V * (1 + 3) + 42 * F * (1 + 1))`` -- every source read counted, also those that
+        come from the cache."""
+        from . import cascade
+
+        if self.slab or src.slab:
+            raise ValueError("transfer_space_from: not available on time slabs")
+        if self.T != src.T:
+            raise ValueError(f"transfer_space_from: n_time = {self.T}, the source's {src.T}: both levels have one time grid")
+        vs, _, ts, _ = cascade.check_transfer(transfer, n_vertices=src.V, n_triangles=src.F)
+        if (vs.shape[0], ts.shape[0]) != (self.V, self.F):
+            raise ValueError(f"transfer_space_from: a transfer to a mesh with V, F = {vs.shape[0]}, {ts.shape[0]}, this one has {self.V}, {self.F}")
+        vsrc, vw, fsrc, csrc = cascade.transfer_row_maps(transfer, self.plan.perm_vert, self.plan.perm_tri, src.plan.perm_vert, src.plan.perm_tri)
+        ms = C.c_double()
+        d = _lib.TransferSpaceDesc()
+        d.vsrc, d.vw, d.fsrc, d.csrc = _ptr(vsrc, C.c_int32), _ptr(vw, C.c_double), _ptr(fsrc, C.c_int32), _ptr(csrc, C.c_int32)
+        d.n_vertices, d.n_triangles = self.V, self.F
+        for i, f in enumerate(factors):
+            d.factor[i] = float(f)
+        d.ms = C.pointer(ms)
+        _lib.check(self.lib.dots_transfer_space(self._h, src._h, C.byref(d)), "dots_transfer_space")
+        pitch = max(8, 1 << int(np.ceil(np.log2(self.T + 1))))
+        self.prolong_bytes = 8 * pitch * (8 * 4 * self.V + (2 * 3 + 2 * 18) * 2 * self.F)
+        return ms.value
+
     # ---- the hot loop
     def step(self, n_iters=1, wait=True):
         """``wait=False``: only enqueue (direct solver); returns None, nothing is timed."""

@@ -227,6 +227,50 @@ def refine_levels(geometry, n_levels, project=None, densities=None):
     return levels
 
 
+def link_levels(geometries, densities=None):
+    """The counterpart of ``refine_levels`` for meshes that already exist: ``geometries`` (coarse to fine) are independent
+    triangulations of one surface in the same coordinates (normalised together); every level after the first gets the map to the level
+    below under the key "transfer" (``cascade.mesh_transfer``).  A level that already has "parents" is left as it is, so nested and
+    located levels may be mixed.  The levels are returned as new dicts; the arrays are shared with the input.
+
+    ``mu0`` / ``mu1`` of a level that lacks them: ``densities(vertices, area_vertices) -> (mu0, mu1)``, or without it the densities per
+    unit area of the level below carried up by the vertex rule of ``cascade.transfer_space`` (of ``cascade.prolong_space`` on a level
+    with "parents") and weighted with the level's own ``area_vertices``; either way scaled to unit mass."""
+    from . import cascade
+
+    levels = [dict(g) for g in geometries]
+    if not levels:
+        raise ValueError("link_levels: at least one geometry")
+
+    def areas(g):
+        if "area_vertices" not in g:
+            g["area_triangles"] = triangle_areas(g["vertices"], g["triangles"])
+            g["area_vertices"] = vertex_areas(np.asarray(g["vertices"]).shape[0], g["triangles"], g["area_triangles"])
+        return np.asarray(g["area_vertices"], dtype=np.float64)
+
+    for coarse, fine in zip(levels, levels[1:]):
+        if fine.get("parents") is None:
+            fine["transfer"] = cascade.mesh_transfer(coarse, fine)
+        if fine.get("mu0") is not None and fine.get("mu1") is not None:
+            continue
+        area_f = areas(fine)
+        if densities is not None:
+            mu0, mu1 = densities(np.asarray(fine["vertices"], dtype=np.float64), area_f)
+        else:
+            if coarse.get("mu0") is None or coarse.get("mu1") is None:
+                raise ValueError("link_levels: the level below has no mu0 / mu1 to carry up")
+            area_c = areas(coarse)
+            if fine.get("parents") is not None:
+                up = lambda rho: cascade.prolong_space(rho[None, :], "mu", fine["parents"])[0]      # noqa: E731
+            else:
+                up = lambda rho: cascade.transfer_space(rho[None, :], "mu", fine["transfer"])[0]      # noqa: E731
+            mu0 = up(np.asarray(coarse["mu0"], dtype=np.float64) / area_c) * area_f
+            mu1 = up(np.asarray(coarse["mu1"], dtype=np.float64) / area_c) * area_f
+        mu0, mu1 = np.asarray(mu0, dtype=np.float64), np.asarray(mu1, dtype=np.float64)
+        fine["mu0"], fine["mu1"] = mu0 / mu0.sum(), mu1 / mu1.sum()
+    return levels
+
+
 # --------------------------------------------------------------------------- #
 # geometry dict (GeometryData of the reference, utils/type.py:6-13)
 # --------------------------------------------------------------------------- #

@@ -84,7 +84,7 @@ class AlmSolver:
                  is_constant_scaling=False, check_kkt_step_by_step=False, init_solution=None, tol_checkpoints=None,
                  time_limit=1000, is_palm=False, lap_solver="modal_direct", cg_tol=DEFAULT_CG_TOL, cg_max_iter=20000, device=0, reorder=True,
                  preconditioner="multigrid", mg_coarsest=256, time_slab=None, nd_leaf=16, plan=None, front_owner=None, init_from=None,
-                 release_init_from=False, batched=None, init_parents=None):
+                 release_init_from=False, batched=None, init_parents=None, init_transfer=None):
         """``plan``: the device plan to use (geometry.plan_with_densities) instead of building one; ``front_owner``: a DeviceProblem
         whose factor this solver shares (dots_front_share) instead of building its own -- a member of a batch (solver_socp_many), stepped
         by ``step_batch``; the launch ahead of the right-hand side and of the penalty decision are off then.
@@ -95,9 +95,15 @@ class AlmSolver:
         are never on the device together.  ``init_parents``: ``init_from`` is a solver on the PARENT mesh of this one (``meshes.subdivide``'s
         ``parents``) at the same ``n_time``: its recovered solution is carried to the refinement on the device
         (DeviceProblem.prolong_space_from; ``init_solution=cascade.prolong_space_solution(<its solution>, parents)`` bit for bit).  One call
-        changes the mesh or the time grid, not both.  ``batched``: whether the solver is stepped by a batch (default: whenever ``plan`` or
+        changes the mesh or the time grid, not both.  ``init_transfer`` (exclusive with ``init_parents``): ``init_from`` is a solver on ANOTHER
+        triangulation of the same surface at the same ``n_time`` and this is ``cascade.mesh_transfer`` from its mesh to this one: its
+        recovered solution is carried over barycentrically on the device (DeviceProblem.transfer_space_from;
+        ``init_solution=cascade.transfer_space_solution(<its solution>, transfer)`` bit for bit), in the same order: transfer, release,
+        factor.  ``batched``: whether the solver is stepped by a batch (default: whenever ``plan`` or
         ``front_owner`` is given)."""
         check_time_nodes(n_time, lap_solver, time_slab)
+        if init_transfer is not None and init_parents is not None:
+            raise ValueError("init_transfer and init_parents are mutually exclusive: the level below is a located mesh or the parent mesh")
         if init_from is not None:
             if init_solution:
                 raise ValueError("init_from and init_solution are mutually exclusive: the warm start comes from one of them")
@@ -108,8 +114,13 @@ class AlmSolver:
             if init_parents is not None and int(init_from.n_time) != int(n_time):
                 raise ValueError(f"init_parents: the parent mesh's solver has n_time = {int(init_from.n_time)}, this one {int(n_time)}: "
                                  "one call changes the mesh or the time grid, not both")
+            if init_transfer is not None and int(init_from.n_time) != int(n_time):
+                raise ValueError(f"init_transfer: the coarse mesh's solver has n_time = {int(init_from.n_time)}, this one {int(n_time)}: "
+                                 "one call changes the mesh or the time grid, not both")
         elif init_parents is not None:
             raise ValueError("init_parents needs init_from (the solver on the parent mesh)")
+        elif init_transfer is not None:
+            raise ValueError("init_transfer needs init_from (the solver on the coarse mesh)")
         self.tol_checkpoints = _validate_checkpoints(tol_checkpoints, tol)
         self.geometry = geometry        # (read_out takes the area weights and mu0 / mu1 from it)
         self.checkpoint_solutions = []
@@ -156,6 +167,8 @@ class AlmSolver:
         if init_from is not None:
             if init_parents is not None:
                 self.prolong_ms = dev.prolong_space_from(init_from.dev, init_parents, init_from.recovery_factors())
+            elif init_transfer is not None:
+                self.prolong_ms = dev.transfer_space_from(init_from.dev, init_transfer, init_from.recovery_factors())
             else:
                 self.prolong_ms = dev.prolong_from(init_from.dev, init_from.recovery_factors())
             if release_init_from:
@@ -922,7 +935,7 @@ def _mesh_cascade_options(geometries, level_tol, kwargs):
         raise ValueError("solver_socp_mesh_cascade: geometries must be a list of geometries, coarse to fine") from None
     if len(geometries) < 2:
         raise ValueError("solver_socp_mesh_cascade: at least two geometries (a coarse level and its refinement); one level is solver_socp")
-    for key in ("time_slab", "init_from", "init_parents", "levels"):
+    for key in ("time_slab", "init_from", "init_parents", "init_transfer", "levels"):
         if key in kwargs:
             raise ValueError(f"solver_socp_mesh_cascade: {key} is not an option of the cascade in space" +
                              (" (a cascade in time and in space in one call is not supported)" if key == "levels" else ""))
@@ -930,12 +943,23 @@ def _mesh_cascade_options(geometries, level_tol, kwargs):
     if unknown:
         raise ValueError(f"solver_socp_mesh_cascade: unknown option(s) {sorted(unknown)}")
     for i, (coarse, fine) in enumerate(zip(geometries, geometries[1:])):
-        if not isinstance(fine, dict) or fine.get("parents") is None:
-            raise ValueError(f"solver_socp_mesh_cascade: geometry {i + 1} has no 'parents' (meshes.refine_levels / meshes.subdivide)")
-        vp, tp = cascade.check_parents(fine["parents"], n_vertices=np.asarray(coarse["vertices"]).shape[0],
-                                       n_triangles=np.asarray(coarse["triangles"]).shape[0])
-        if (vp.shape[0], tp.shape[0]) != (np.asarray(fine["vertices"]).shape[0], np.asarray(fine["triangles"]).shape[0]):
-            raise ValueError(f"solver_socp_mesh_cascade: the parents of geometry {i + 1} do not have its size")
+        nested, located = isinstance(fine, dict) and fine.get("parents") is not None, isinstance(fine, dict) and fine.get("transfer") is not None
+        if nested and located:
+            raise ValueError(f"solver_socp_mesh_cascade: geometry {i + 1} has both 'parents' and 'transfer': the level below is its parent mesh "
+                             "or a located mesh, not both")
+        if not nested and not located:
+            raise ValueError(f"solver_socp_mesh_cascade: geometry {i + 1} has neither 'parents' (meshes.refine_levels / meshes.subdivide) nor "
+                             "'transfer' (meshes.link_levels / cascade.mesh_transfer)")
+        size_c = dict(n_vertices=np.asarray(coarse["vertices"]).shape[0], n_triangles=np.asarray(coarse["triangles"]).shape[0])
+        size_f = (np.asarray(fine["vertices"]).shape[0], np.asarray(fine["triangles"]).shape[0])
+        if nested:
+            vp, tp = cascade.check_parents(fine["parents"], **size_c)
+            if (vp.shape[0], tp.shape[0]) != size_f:
+                raise ValueError(f"solver_socp_mesh_cascade: the parents of geometry {i + 1} do not have its size")
+        else:
+            vs, _, ts, _ = cascade.check_transfer(fine["transfer"], **size_c)
+            if (vs.shape[0], ts.shape[0]) != size_f:
+                raise ValueError(f"solver_socp_mesh_cascade: the transfer of geometry {i + 1} does not have its size")
     tol = kwargs.get("tol", 1e-4)
     if level_tol is None:
         level_tol = tol
@@ -949,12 +973,20 @@ def _mesh_cascade_options(geometries, level_tol, kwargs):
     return geometries, level_tol, opts
 
 
+def _max_distance(geom):
+    d = (geom.get("transfer") or {}).get("max_distance")
+    return None if d is None else float(d)
+
+
 def solver_socp_mesh_cascade(n_time, geometries, level_tol=None, read_out=None, **kwargs):
     """``solver_socp`` through a coarse-to-fine cascade in space: the problem is solved on the meshes ``geometries`` (coarse to fine,
     every one after the first the nested refinement of the one before with its ``parents``: ``meshes.refine_levels``), all at
     ``n_time``, each level warm-started from the recovered solution of the one before, carried to the refinement on the device
     (AlmSolver ``init_from`` with ``init_parents``; cascade.prolong_space is the specification).  A level down has a quarter of the
-    vertices and triangles: state, factor, set-up and every launch shrink with them.
+    vertices and triangles: state, factor, set-up and every launch shrink with them.  A level may instead carry ``transfer``
+    (``meshes.link_levels`` / ``cascade.mesh_transfer``): the level below is then an independent triangulation of the same surface and
+    the state is carried over barycentrically (``init_transfer``; cascade.transfer_space is the specification).  Nested and located
+    levels may be mixed; a level with both keys or with neither raises ``ValueError``.
 
     ``level_tol``: the tolerance of the levels below the finest (default ``tol``).  The other keywords are ``solver_socp``'s: ``nit``
     holds per level, ``time_limit`` for the whole call (a level gets the time that is left), ``init_solution`` starts the coarsest
@@ -965,7 +997,8 @@ def solver_socp_mesh_cascade(n_time, geometries, level_tol=None, read_out=None, 
 
     Returns ``(solution, run_history)`` of the finest level; ``run_history.solver_stats["mesh_cascade"]`` = {"levels": [one record
     per level: n_vertices, n_triangles, tol, iterations, running_time, setup_seconds, prolong_ms and prolong_bytes (None on the coarsest
-    level), cost, kkt_max, device_bytes], "total_seconds"}.  ``read_out``: as for ``solver_socp``, for the finest level."""
+    level), cost, kkt_max, device_bytes, transfer ("nested" | "located", None on the coarsest level), max_distance (of a located
+    level, else None)], "total_seconds"}.  ``read_out``: as for ``solver_socp``, for the finest level."""
     geometries, level_tol, opts = _mesh_cascade_options(geometries, level_tol, kwargs)
     tol, nit = opts.pop("tol", 1e-4), int(opts.pop("nit", 1000))
     time_limit = opts.pop("time_limit", 1000)
@@ -978,7 +1011,8 @@ def solver_socp_mesh_cascade(n_time, geometries, level_tol=None, read_out=None, 
             last = i + 1 == len(geometries)
             t0 = time.perf_counter()
             alm = AlmSolver(n_time, geom, nit=nit, tol=tol if last else level_tol, tol_checkpoints=checkpoints if last else None,
-                            init_solution=init_solution if i == 0 else None, init_from=coarse, init_parents=geom["parents"] if i else None,
+                            init_solution=init_solution if i == 0 else None, init_from=coarse, init_parents=geom.get("parents") if i else None,
+                            init_transfer=geom.get("transfer") if i else None,
                             release_init_from=True, time_limit=max(time_limit - (t0 - t_start), 0.0), **opts)
             coarse = None      # (closed by the constructor as soon as the finer state was filled)
             setup = time.perf_counter() - t0
@@ -990,7 +1024,9 @@ def solver_socp_mesh_cascade(n_time, geometries, level_tol=None, read_out=None, 
                             "running_time": float(hist.running_time), "setup_seconds": float(setup), "prolong_ms": alm.prolong_ms,
                             "prolong_bytes": getattr(alm.dev, "prolong_bytes", None), "cost": float(hist.history["Transportation cost"][-1]),
                             "kkt_max": float(np.nanmax(np.asarray(hist.kkt_errors[-1], dtype=np.float64))),
-                            "device_bytes": int(hist.solver_stats["device_bytes"])})
+                            "device_bytes": int(hist.solver_stats["device_bytes"]),
+                            "transfer": None if i == 0 else ("nested" if geom.get("parents") is not None else "located"),
+                            "max_distance": _max_distance(geom) if i else None})
             coarse, alm = alm, None
         coarse.dev.sync()
         hist.solver_stats["mesh_cascade"] = {"levels": records, "total_seconds": time.perf_counter() - t_start}

@@ -544,6 +544,34 @@ typedef struct dots_prolong_space_desc {
 } dots_prolong_space_desc;
 int dots_prolong_space(dots_ctx *dst, dots_ctx *src, const dots_prolong_space_desc *desc);
 
+/* ---- cascade in space between two independent triangulations of one surface: barycentric transfer -----------------------------
+ * dots_transfer_space fills the twelve state arrays of `dst` from those of `src`, a context on ANOTHER triangulation of the same
+ * surface (no nesting, no `parents`), both on one time grid and one device.  It replaces the round trip over the host of a warm
+ * start on a mesh that is not a subdivision of the coarse one (init_solution, solver_socp.py:38,70-71, 239-250, filled from
+ * cascade.transfer_space_solution): a vertex row of `dst` takes (w0 * (f * a0) + w1 * (f * a1)) + w2 * (f * a2) of its three source
+ * vertex rows, in this order of operations and with no special case for weights 0 or 1; a row of a triangle array (B, E) f times
+ * the row of the same component of the source triangle fsrc[f'] (not projected into the destination triangle's plane); a row of a
+ * corner array (z_mid, beta_mid) f times the row of corner csrc[f'][k] of that triangle, same interval end and component.  f is the
+ * array's factor, as for dots_prolong_time.  The tables come from the caller (dots_socp_amd/cascade.py: mesh_transfer locates every
+ * destination vertex and triangle centroid on the source mesh, transfer_row_maps puts the result into the device numberings of the
+ * two contexts), so that the result is bit for bit what dots_upload of the host's transfer (cascade.transfer_space) leaves.
+ * `src` and `dst` are treated as by dots_prolong_time (pending division, z_mid, what `dst` carried; stream order; the call returns
+ * when the destination is filled).
+ * DOTS_ERR_ARGUMENT: different n_time, dst == src, a NULL table, n_vertices / n_triangles that are not the destination's V / F, a
+ * vsrc / fsrc entry that is no row of the source, a csrc entry outside 0 .. 2, a weight that is negative or not finite;
+ * DOTS_ERR_STATE: a time slab, contexts on different devices, a stale z_mid.  After an error both contexts are as they were. */
+typedef struct dots_transfer_space_desc {
+    const int32_t *vsrc;         /* [n_vertices][3] destination vertex row -> its three source vertex rows                 */
+    const double *vw;            /* [n_vertices][3] their weights: finite, >= 0                                            */
+    const int32_t *fsrc;         /* [n_triangles]   destination triangle -> source triangle                                */
+    const int32_t *csrc;         /* [n_triangles][3] corner k of the destination triangle -> corner 0 .. 2 of fsrc         */
+    int32_t n_vertices;          /* entries of the tables: V and F of `dst`                                                */
+    int32_t n_triangles;
+    double factor[4];            /* as dots_prolong_desc.factor                                                            */
+    double *ms;                  /* NULL, or out: milliseconds of the launches on the device (events on dst's stream)     */
+} dots_transfer_space_desc;
+int dots_transfer_space(dots_ctx *dst, dots_ctx *src, const dots_transfer_space_desc *desc);
+
 /* ---- read-out of the transport: what the solver plug-ins return (mu, E), formed on the device ---------------------------------
  * dots_readout delivers mu and / or E as dots_download would (reference layouts, the caller's numbering), every value multiplied
  * first by `factor` (the recovered solution, solver_socp.py:397-405: r * dual_scale; 1 = the iterate) and then, where weights are

@@ -13,6 +13,13 @@ bench.py's 216 x 20 tube: two nested levels exist below it (108 x 10, 54 x 5), s
 normalised with the finest mesh's bounding box; the densities are the recipe of ``meshes.example`` around three vertices of the
 coarsest level (present on every level).  Building the levels on the host is not part of the timed calls: they are the input.
 
+``--grids 100x63,200x125,400x250`` (coarse to fine) gives the hierarchy as generator grids of the workload's surface instead: the levels
+are then independent triangulations, none nested in another, linked by ``meshes.link_levels`` (every level located on the one below,
+the state carried over barycentrically by ``dots_transfer_space``), the finest grid is the workload (400x250 is bench.py's own
+torus100k), and ``--depths`` counts coarse levels from the finest grid down (default: every depth the list allows).  The densities are
+the same bumps around the points of three vertices of the coarsest grid.  The seconds the hierarchy took to build (``hierarchy_s``:
+meshes, location, densities) are printed in every line; they are not part of the timed calls either.
+
 Prints one JSON line per call (kind = "cold" / "cascade") and a summary line.  The transfer's device milliseconds are set against the
 bytes it moves (every source and destination array once) at 6.3 TB/s, the copy rate DESIGN.md quotes.  bench.py is unchanged."""
 import argparse
@@ -57,6 +64,28 @@ def build_levels(mesh, depth):
     return levels
 
 
+def build_grid_levels(mesh, grids):
+    """The generator's meshes at ``grids`` = [(nu, nv), ...] (coarse to fine), normalised with the finest mesh's bounding box and linked
+    by ``meshes.link_levels``: independent triangulations of one surface."""
+    import numpy as np
+
+    from dots_socp_amd import meshes
+
+    kind = GRIDS[mesh][0]
+    raw = [generator(kind, nu, nv) for nu, nv in grids]
+    fine_v = raw[-1][0]
+    lo, scale = fine_v.min(axis=0), 1.0 / (fine_v.max(axis=0) - fine_v.min(axis=0)).max()
+    geoms = [meshes.make_geometry((v - lo) * scale, t, normalize=False)[0] for v, t in raw]
+    centres = geoms[0]["vertices"][meshes.farthest_vertices(geoms[0]["vertices"], 0, 3)]
+
+    def dens(v, a):      # the recipe of meshes.example around the vertex of this level nearest to each centre
+        c = [int(np.argmin(np.linalg.norm(v - p, axis=1))) for p in centres]
+        return meshes.bump_density(v, a, [c[0]], 0.35, 0.05), meshes.bump_density(v, a, [c[1], c[2]], 0.35, 0.05)
+
+    geoms[0]["mu0"], geoms[0]["mu1"] = dens(geoms[0]["vertices"], geoms[0]["area_vertices"])
+    return meshes.link_levels(geoms, densities=dens)
+
+
 def sync():
     import torch
 
@@ -70,7 +99,8 @@ def main():
     ap.add_argument("--tol", type=float, default=1e-4)
     ap.add_argument("--nit", type=int, default=20000)
     ap.add_argument("--reps", type=int, default=2)
-    ap.add_argument("--depths", default="1,2,3", help="comma-separated numbers of coarse levels")
+    ap.add_argument("--depths", default=None, help="comma-separated numbers of coarse levels (default 1,2,3; with --grids every depth the list allows)")
+    ap.add_argument("--grids", default=None, help="the hierarchy as generator grids, coarse to fine, e.g. 100x63,200x125,400x250 (located levels)")
     ap.add_argument("--level-tol", type=float, default=None)
     ap.add_argument("--congestion", type=float, default=0.0)
     a = ap.parse_args()
@@ -79,12 +109,25 @@ def main():
 
     from dots_socp_amd.socp import solver_socp, solver_socp_mesh_cascade
 
-    depths = [int(x) for x in a.depths.split(",")]
-    deepest = build_levels(a.mesh, max(depths))
+    t_build = time.perf_counter()
+    if a.grids:
+        grids = [tuple(int(n) for n in g.split("x")) for g in a.grids.split(",")]
+        if len(grids) < 2 or any(len(g) != 2 for g in grids):
+            raise SystemExit("--grids: at least two grids NUxNV, coarse to fine")
+        depths = [int(x) for x in a.depths.split(",")] if a.depths else list(range(1, len(grids)))
+        if max(depths) > len(grids) - 1 or min(depths) < 1:
+            raise SystemExit(f"--depths: {len(grids)} grids give 1 .. {len(grids) - 1} coarse levels")
+        deepest = build_grid_levels(a.mesh, grids)
+    else:
+        depths = [int(x) for x in (a.depths or "1,2,3").split(",")]
+        deepest = build_levels(a.mesh, max(depths))
+    hierarchy_s = round(time.perf_counter() - t_build, 3)
     fine = deepest[-1]
     V = int(np.asarray(fine["vertices"]).shape[0])
     common = dict(tol=a.tol, nit=a.nit, congestion=a.congestion, time_limit=1e9)
-    base = dict(mesh=a.mesh, n_time=a.T, vertices=V, tol=a.tol, congestion=a.congestion)
+    base = dict(mesh=a.mesh, n_time=a.T, vertices=V, tol=a.tol, congestion=a.congestion, hierarchy_s=hierarchy_s)
+    if a.grids:
+        base["grids"] = a.grids
     best = {}
     for rep in range(a.reps):
         for depth in [0] + depths:
