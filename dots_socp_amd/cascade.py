@@ -17,12 +17,12 @@ tests and the oracle-side checks share:
 ``time_weights`` computes the tables ``j`` and ``w`` once, on the host; the device reads the same tables, so both sides perform the
 same operations on the same numbers.
 
-The transfer in space (``prolong_space``; ``dots_prolong_space``, k_prolong_space in csrc/kernels_alm.hip) goes from a mesh to its
+The transfer in space (``prolong_space``; ``dots_prolong_space``, k_carry_space in csrc/kernels_alm.hip) goes from a mesh to its
 nested refinement (``meshes.subdivide``: ``parents``) on one time grid; ``space_row_maps`` turns ``parents`` and the two device
 numberings into the row maps the kernel reads.
 
 Between two independent triangulations of one surface (no ``parents``) the transfer is barycentric (``transfer_space``;
-``dots_transfer_space``, k_transfer_space): ``locate`` finds the closest point of the coarse mesh to every fine vertex and triangle
+``dots_transfer_space``, k_carry_space): ``locate`` finds the closest point of the coarse mesh to every fine vertex and triangle
 centroid, ``mesh_transfer`` turns that into the tables of the transfer, ``transfer_row_maps`` puts them into the two device numberings.
 """
 from __future__ import annotations
@@ -104,6 +104,19 @@ def check_levels(levels, n_time):
     return out
 
 
+def inverse_numbering(perm, n, who):
+    """Caller index -> device row for the device numbering ``perm`` of ``n`` rows (``perm[i]`` = caller index of device row i, None =
+    identity), int64; ``who`` names the caller in the error for a ``perm`` of another size."""
+    if perm is None:
+        return np.arange(n, dtype=np.int64)
+    perm = np.asarray(perm, dtype=np.int64)
+    if perm.shape != (n,):
+        raise ValueError(f"{who}: a permutation of the wrong size")
+    inv = np.empty(n, dtype=np.int64)
+    inv[perm] = np.arange(n)
+    return inv
+
+
 def row_map(perm_dst, perm_src, n):
     """Destination device row -> source device row for two plans of one mesh (``perm[i]`` = caller index of device row i, None =
     identity); None when both numberings agree."""
@@ -113,9 +126,7 @@ def row_map(perm_dst, perm_src, n):
     ps = np.arange(n, dtype=np.int64) if perm_src is None else np.asarray(perm_src, dtype=np.int64)
     if np.array_equal(pd, ps):
         return None
-    inv_src = np.empty(n, dtype=np.int64)
-    inv_src[ps] = np.arange(n)
-    return np.ascontiguousarray(inv_src[pd], dtype=np.int32)
+    return np.ascontiguousarray(inverse_numbering(perm_src, n, "row_map")[pd], dtype=np.int32)
 
 
 # ---- coarse-to-fine in space: a mesh to its nested refinement --------------------------------------------------------------------
@@ -185,23 +196,13 @@ def space_row_maps(parents, n_src_vertices, n_src_triangles, perm_vert_dst=None,
     ``perm[i]`` = caller index of device row i (None = identity), as in ``row_map``: the two meshes are numbered independently."""
     vp, tp = check_parents(parents, n_vertices=n_src_vertices, n_triangles=n_src_triangles)
 
-    def inverse(perm, n):
-        if perm is None:
-            return np.arange(n, dtype=np.int64)
-        perm = np.asarray(perm, dtype=np.int64)
-        if perm.shape != (n,):
-            raise ValueError("space_row_maps: a permutation of the wrong size")
-        inv = np.empty(n, dtype=np.int64)
-        inv[perm] = np.arange(n)
-        return inv
-
     for perm, n in ((perm_vert_dst, vp.shape[0]), (perm_tri_dst, tp.shape[0])):
         if perm is not None and np.asarray(perm).shape != (n,):
             raise ValueError("space_row_maps: a permutation of the wrong size")
     vd = vp if perm_vert_dst is None else vp[np.asarray(perm_vert_dst, dtype=np.int64)]
     td = tp if perm_tri_dst is None else tp[np.asarray(perm_tri_dst, dtype=np.int64)]
-    vmap = inverse(perm_vert_src, int(n_src_vertices))[vd]
-    fmap = inverse(perm_tri_src, int(n_src_triangles))[td]
+    vmap = inverse_numbering(perm_vert_src, int(n_src_vertices), "space_row_maps")[vd]
+    fmap = inverse_numbering(perm_tri_src, int(n_src_triangles), "space_row_maps")[td]
     return np.ascontiguousarray(vmap, dtype=np.int32), np.ascontiguousarray(fmap, dtype=np.int32)
 
 
@@ -399,16 +400,6 @@ def transfer_row_maps(transfer, perm_vert_dst=None, perm_tri_dst=None, perm_vert
     vs, vw, ts, cs = check_transfer(transfer)
     n_src_v, n_src_t = int(transfer["n_source_vertices"]), int(transfer["n_source_triangles"])
 
-    def inverse(perm, n):
-        if perm is None:
-            return np.arange(n, dtype=np.int64)
-        perm = np.asarray(perm, dtype=np.int64)
-        if perm.shape != (n,):
-            raise ValueError("transfer_row_maps: a permutation of the wrong size")
-        inv = np.empty(n, dtype=np.int64)
-        inv[perm] = np.arange(n)
-        return inv
-
     for perm, n in ((perm_vert_dst, vs.shape[0]), (perm_tri_dst, ts.shape[0])):
         if perm is not None and np.asarray(perm).shape != (n,):
             raise ValueError("transfer_row_maps: a permutation of the wrong size")
@@ -418,7 +409,7 @@ def transfer_row_maps(transfer, perm_vert_dst=None, perm_tri_dst=None, perm_vert
     if perm_tri_dst is not None:
         pt = np.asarray(perm_tri_dst, dtype=np.int64)
         ts, cs = ts[pt], cs[pt]
-    vsrc = inverse(perm_vert_src, n_src_v)[vs]
-    fsrc = inverse(perm_tri_src, n_src_t)[ts]
+    vsrc = inverse_numbering(perm_vert_src, n_src_v, "transfer_row_maps")[vs]
+    fsrc = inverse_numbering(perm_tri_src, n_src_t, "transfer_row_maps")[ts]
     return (np.ascontiguousarray(vsrc, dtype=np.int32), np.ascontiguousarray(vw, dtype=np.float64),
             np.ascontiguousarray(fsrc, dtype=np.int32), np.ascontiguousarray(cs, dtype=np.int32))

@@ -1399,11 +1399,90 @@ int dots_bench_many(dots_ctx *const *cs, int n, int reps, double *ms) {
     return 0;
 }
 
+// ---- carrying the state from one context to another (dots_prolong_time, dots_prolong_space, dots_transfer_space) ------------------
+// What the three entry points share.  An entry point calls carry_guard, validates its descriptor -- a bad argument leaves both contexts
+// untouched --, lists its tables and calls carry_state with a callable that launches one array.  carry_state brings the source up to
+// date, prepares the destination, puts the tables one after another into one device buffer (doubles first keeps them aligned) and,
+// with both streams ordered, calls launch(array id, factor) for each of the twelve arrays.  The order is the protocol: the destination's
+// stream waits for what the source has enqueued, whatever the source does next -- its release included -- comes after the reads, and
+// the buffer is freed after the synchronise, also when a launch failed.  `what`: the tables' noun in the messages.
+extern "C++" {      // (a template)
+
+struct CarryTable {
+    const void *host;      // the caller's table (null with 0 bytes: not passed)
+    size_t bytes;
+    char *dev;             // where carry_state put it
+    template <class T>
+    const T *at() const { return bytes ? (const T *)dev : nullptr; }
+};
+
+static int carry_guard(const std::string &who, const dots_ctx *dst, const dots_ctx *src, const void *desc) {
+    if (!dst || !src || !desc) { set_error(who + ": null argument"); return DOTS_ERR_ARGUMENT; }
+    if (dst == src) { set_error(who + ": source and destination are one context"); return DOTS_ERR_ARGUMENT; }
+    if (dst->shard_stride != 0 || src->shard_stride != 0) { set_error(who + ": not available on time slabs"); return DOTS_ERR_STATE; }
+    if (dst->device != src->device) { set_error(who + ": the contexts are on different devices"); return DOTS_ERR_STATE; }
+    return 0;
+}
+
+// the two carriers in space: both levels have one time grid, no table is missing, and the tables are those of the destination's mesh
+static int carry_space_shapes(const char *who, const char *what, const Dev &dd, const Dev &ds, bool null_table, int n_vertices, int n_triangles) {
+    char buf[200];
+    if (dd.T != ds.T) snprintf(buf, sizeof buf, "%s: n_time = %d, the source's %d: both levels have one time grid", who, dd.T, ds.T);
+    else if (null_table) snprintf(buf, sizeof buf, "%s: null %s", who, what);
+    else if (n_vertices != dd.V || n_triangles != dd.F)
+        snprintf(buf, sizeof buf, "%s: %ss of %d vertices and %d triangles, the destination has %d and %d", who, what, n_vertices, n_triangles, dd.V, dd.F);
+    else return 0;
+    set_error(buf);
+    return DOTS_ERR_ARGUMENT;
+}
+
+template <size_t N, class Launch>
+static int carry_state(const std::string &who, const char *what, dots_ctx *dst, dots_ctx *src, const double *factor, double *ms, CarryTable (&tab)[N],
+                       Launch launch) {
+    int rc = check(src, true);      // (a pending penalty division is carried out, as for a download)
+    if (rc) return rc;
+    if (src->zmid_stale) { set_error(who + ": the source's z_mid was not materialised by its last step (dots_step_flags)"); return DOTS_ERR_STATE; }
+    if ((rc = materialise_zmid(src))) return rc;
+    if ((rc = check(dst, false, true))) return rc;
+    dst->pending_div = 0.0;      // (every array a pending division would have touched is replaced)
+    size_t bytes = 0;
+    for (const CarryTable &t : tab) bytes += t.bytes;
+    char *buf = nullptr;
+    DOTS_HIP(hipMalloc((void **)&buf, bytes));
+    hipError_t e = hipSuccess;
+    bytes = 0;
+    for (CarryTable &t : tab) {
+        t.dev = buf + bytes;
+        if (e == hipSuccess && t.bytes) e = hipMemcpyAsync(t.dev, t.host, t.bytes, hipMemcpyHostToDevice, dst->stream);
+        bytes += t.bytes;
+    }
+    if (e != hipSuccess) rc = hip_fail(e, (who + ": " + what + "s").c_str(), __FILE__, __LINE__);
+    // the destination's stream waits for what the source has enqueued (its last step, the division, z_mid)
+    if (!rc) rc = batch_wait(dst, src);
+    if (!rc && (e = hipEventRecord(dst->ev[0], dst->stream)) != hipSuccess) rc = hip_fail(e, "hipEventRecord", __FILE__, __LINE__);
+    const int group[DOTS_N_ARRAYS] = {0, 0, 0, 0, 1, 1, 1, 2, 2, 3, 3, 3};      // recorver_scaled_solution (solver_socp.py:397-405)
+    for (int id = 0; id < DOTS_N_ARRAYS && !rc; ++id) rc = launch(id, factor[group[id]]);
+    if (!rc && (e = hipEventRecord(dst->ev[1], dst->stream)) != hipSuccess) rc = hip_fail(e, "hipEventRecord", __FILE__, __LINE__);
+    if (!rc) rc = batch_wait(src, dst);      // (whatever the source does next -- its release included -- comes after the reads)
+    e = hipStreamSynchronize(dst->stream);
+    if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__);
+    (void)hipFree(buf);
+    if (rc) return rc;
+    dst->zmid_stale = dst->zmid_deferred = 0;      // (z_mid's storage holds the carried z_mid)
+    dst->kkt_halo_fresh = 0;
+    if (ms) {
+        float t = 0.f;
+        DOTS_HIP(hipEventElapsedTime(&t, dst->ev[0], dst->ev[1]));
+        *ms = t;
+    }
+    return 0;
+}
+
+}  // extern "C++"
+
 int dots_prolong_time(dots_ctx *dst, dots_ctx *src, const dots_prolong_desc *desc) {
-    if (!dst || !src || !desc) { set_error("prolong_time: null argument"); return DOTS_ERR_ARGUMENT; }
-    if (dst == src) { set_error("prolong_time: source and destination are one context"); return DOTS_ERR_ARGUMENT; }
-    if (dst->shard_stride != 0 || src->shard_stride != 0) { set_error("prolong_time: not available on time slabs"); return DOTS_ERR_STATE; }
-    if (dst->device != src->device) { set_error("prolong_time: the contexts are on different devices"); return DOTS_ERR_STATE; }
+    int rc = carry_guard("prolong_time", dst, src, desc);
+    if (rc) return rc;
     const Dev &dd = dst->d, &ds = src->d;
     if (dd.V != ds.V || dd.F != ds.F) {
         char buf[160];
@@ -1433,129 +1512,39 @@ int dots_prolong_time(dots_ctx *dst, dots_ctx *src, const dots_prolong_desc *des
         for (int i = 0; m && i < n; ++i)
             if (m[i] < 0 || m[i] >= n) { set_error(pass ? "prolong_time: fmap entry out of range" : "prolong_time: vmap entry out of range"); return DOTS_ERR_ARGUMENT; }
     }
-    int rc = check(src, true);      // (a pending penalty division is carried out, as for a download)
-    if (rc) return rc;
-    if (src->zmid_stale) { set_error("prolong_time: the source's z_mid was not materialised by its last step (dots_step_flags)"); return DOTS_ERR_STATE; }
-    if ((rc = materialise_zmid(src))) return rc;
-    if ((rc = check(dst, false, true))) return rc;
-    dst->pending_div = 0.0;      // (every array a pending division would have touched is replaced)
-    // tables and maps in one device buffer: [node w | interval w | node j | interval j | vmap | fmap]
     const size_t nv = desc->vmap ? (size_t)dd.V : 0, nf = desc->fmap ? (size_t)dd.F : 0;
-    const size_t bytes = sizeof(double) * (size_t)(nn + ni) + sizeof(int32_t) * ((size_t)(nn + ni) + nv + nf);
-    char *buf = nullptr;
-    DOTS_HIP(hipMalloc((void **)&buf, bytes));
-    double *wn = (double *)buf, *wi = wn + nn;
-    int *jn = (int *)(wi + ni), *ji = jn + nn, *vm = ji + ni, *fm = vm + nv;
-    hipError_t e = hipMemcpyAsync(wn, desc->node_w, sizeof(double) * (size_t)nn, hipMemcpyHostToDevice, dst->stream);
-    if (e == hipSuccess && ni) e = hipMemcpyAsync(wi, desc->interval_w, sizeof(double) * (size_t)ni, hipMemcpyHostToDevice, dst->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(jn, desc->node_j, sizeof(int32_t) * (size_t)nn, hipMemcpyHostToDevice, dst->stream);
-    if (e == hipSuccess && ni) e = hipMemcpyAsync(ji, desc->interval_j, sizeof(int32_t) * (size_t)ni, hipMemcpyHostToDevice, dst->stream);
-    if (e == hipSuccess && nv) e = hipMemcpyAsync(vm, desc->vmap, sizeof(int32_t) * nv, hipMemcpyHostToDevice, dst->stream);
-    if (e == hipSuccess && nf) e = hipMemcpyAsync(fm, desc->fmap, sizeof(int32_t) * nf, hipMemcpyHostToDevice, dst->stream);
-    if (e != hipSuccess) rc = hip_fail(e, "prolong_time: tables", __FILE__, __LINE__);
-    // the destination's stream waits for what the source has enqueued (its last step, the division, z_mid)
-    if (!rc) rc = batch_wait(dst, src);
-    if (!rc && (e = hipEventRecord(dst->ev[0], dst->stream)) != hipSuccess) rc = hip_fail(e, "hipEventRecord", __FILE__, __LINE__);
-    const int group[DOTS_N_ARRAYS] = {0, 0, 0, 0, 1, 1, 1, 2, 2, 3, 3, 3};      // recorver_scaled_solution (solver_socp.py:397-405)
-    for (int id = 0; id < DOTS_N_ARRAYS && !rc; ++id) {
-        const bool node = array_kind(id) == 0 || array_kind(id) == 2;
-        rc = launch_prolong(dst, src, id, node ? jn : ji, node ? wn : wi, nv ? vm : nullptr, nf ? fm : nullptr, desc->factor[group[id]]);
-    }
-    if (!rc && (e = hipEventRecord(dst->ev[1], dst->stream)) != hipSuccess) rc = hip_fail(e, "hipEventRecord", __FILE__, __LINE__);
-    if (!rc) rc = batch_wait(src, dst);      // (whatever the source does next -- its release included -- comes after the reads)
-    e = hipStreamSynchronize(dst->stream);
-    if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__);
-    (void)hipFree(buf);
-    if (rc) return rc;
-    dst->zmid_stale = dst->zmid_deferred = 0;      // (z_mid's storage holds the prolonged z_mid)
-    dst->kkt_halo_fresh = 0;
-    if (desc->ms) {
-        float t = 0.f;
-        DOTS_HIP(hipEventElapsedTime(&t, dst->ev[0], dst->ev[1]));
-        *desc->ms = t;
-    }
-    return 0;
+    CarryTable tab[] = {{desc->node_w, sizeof(double) * (size_t)nn}, {desc->interval_w, sizeof(double) * (size_t)ni}, {desc->node_j, sizeof(int32_t) * (size_t)nn},
+                        {desc->interval_j, sizeof(int32_t) * (size_t)ni}, {desc->vmap, sizeof(int32_t) * nv}, {desc->fmap, sizeof(int32_t) * nf}};
+    return carry_state("prolong_time", "table", dst, src, desc->factor, desc->ms, tab, [&](int id, double f) {
+        const int i = (array_kind(id) == 0 || array_kind(id) == 2) ? 0 : 1;      // the node tables, or the interval tables
+        return launch_prolong(dst, src, id, tab[2 + i].at<int>(), tab[i].at<double>(), tab[4].at<int>(), tab[5].at<int>(), f);
+    });
 }
 
 int dots_prolong_space(dots_ctx *dst, dots_ctx *src, const dots_prolong_space_desc *desc) {
-    if (!dst || !src || !desc) { set_error("prolong_space: null argument"); return DOTS_ERR_ARGUMENT; }
-    if (dst == src) { set_error("prolong_space: source and destination are one context"); return DOTS_ERR_ARGUMENT; }
-    if (dst->shard_stride != 0 || src->shard_stride != 0) { set_error("prolong_space: not available on time slabs"); return DOTS_ERR_STATE; }
-    if (dst->device != src->device) { set_error("prolong_space: the contexts are on different devices"); return DOTS_ERR_STATE; }
+    const char *who = "prolong_space";
+    int rc = carry_guard(who, dst, src, desc);
+    if (rc) return rc;
     const Dev &dd = dst->d, &ds = src->d;
-    if (dd.T != ds.T) {
-        char buf[160];
-        snprintf(buf, sizeof buf, "prolong_space: n_time = %d, the source's %d: both levels have one time grid", dd.T, ds.T);
-        set_error(buf);
-        return DOTS_ERR_ARGUMENT;
-    }
-    if (!desc->vmap || !desc->fmap) { set_error("prolong_space: null row map"); return DOTS_ERR_ARGUMENT; }
-    if (desc->n_vertices != dd.V || desc->n_triangles != dd.F) {
-        char buf[200];
-        snprintf(buf, sizeof buf, "prolong_space: row maps of %d vertices and %d triangles, the destination has %d and %d", desc->n_vertices,
-                 desc->n_triangles, dd.V, dd.F);
-        set_error(buf);
-        return DOTS_ERR_ARGUMENT;
-    }
+    if ((rc = carry_space_shapes(who, "row map", dd, ds, !desc->vmap || !desc->fmap, desc->n_vertices, desc->n_triangles))) return rc;
     // every map entry names a row of the source
-    for (int64_t i = 0; i < 2 * (int64_t)dd.V; ++i)
-        if (desc->vmap[i] < 0 || desc->vmap[i] >= ds.V) { set_error("prolong_space: vmap entry out of range"); return DOTS_ERR_ARGUMENT; }
-    for (int i = 0; i < dd.F; ++i)
-        if (desc->fmap[i] < 0 || desc->fmap[i] >= ds.F) { set_error("prolong_space: fmap entry out of range"); return DOTS_ERR_ARGUMENT; }
-    int rc = check(src, true);      // (a pending penalty division is carried out, as for a download)
-    if (rc) return rc;
-    if (src->zmid_stale) { set_error("prolong_space: the source's z_mid was not materialised by its last step (dots_step_flags)"); return DOTS_ERR_STATE; }
-    if ((rc = materialise_zmid(src))) return rc;
-    if ((rc = check(dst, false, true))) return rc;
-    dst->pending_div = 0.0;      // (every array a pending division would have touched is replaced)
     const size_t nv = 2 * (size_t)dd.V, nf = (size_t)dd.F;
-    int *vm = nullptr;
-    DOTS_HIP(hipMalloc((void **)&vm, sizeof(int32_t) * (nv + nf)));
-    int *fm = vm + nv;
-    hipError_t e = hipMemcpyAsync(vm, desc->vmap, sizeof(int32_t) * nv, hipMemcpyHostToDevice, dst->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(fm, desc->fmap, sizeof(int32_t) * nf, hipMemcpyHostToDevice, dst->stream);
-    if (e != hipSuccess) rc = hip_fail(e, "prolong_space: row maps", __FILE__, __LINE__);
-    // the destination's stream waits for what the source has enqueued (its last step, the division, z_mid)
-    if (!rc) rc = batch_wait(dst, src);
-    if (!rc && (e = hipEventRecord(dst->ev[0], dst->stream)) != hipSuccess) rc = hip_fail(e, "hipEventRecord", __FILE__, __LINE__);
-    const int group[DOTS_N_ARRAYS] = {0, 0, 0, 0, 1, 1, 1, 2, 2, 3, 3, 3};      // recorver_scaled_solution (solver_socp.py:397-405)
-    for (int id = 0; id < DOTS_N_ARRAYS && !rc; ++id) rc = launch_prolong_space(dst, src, id, vm, fm, desc->factor[group[id]]);
-    if (!rc && (e = hipEventRecord(dst->ev[1], dst->stream)) != hipSuccess) rc = hip_fail(e, "hipEventRecord", __FILE__, __LINE__);
-    if (!rc) rc = batch_wait(src, dst);      // (whatever the source does next -- its release included -- comes after the reads)
-    e = hipStreamSynchronize(dst->stream);
-    if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__);
-    (void)hipFree(vm);
-    if (rc) return rc;
-    dst->zmid_stale = dst->zmid_deferred = 0;      // (z_mid's storage holds the prolonged z_mid)
-    dst->kkt_halo_fresh = 0;
-    if (desc->ms) {
-        float t = 0.f;
-        DOTS_HIP(hipEventElapsedTime(&t, dst->ev[0], dst->ev[1]));
-        *desc->ms = t;
-    }
-    return 0;
+    for (size_t i = 0; i < nv; ++i)
+        if (desc->vmap[i] < 0 || desc->vmap[i] >= ds.V) { set_error("prolong_space: vmap entry out of range"); return DOTS_ERR_ARGUMENT; }
+    for (size_t i = 0; i < nf; ++i)
+        if (desc->fmap[i] < 0 || desc->fmap[i] >= ds.F) { set_error("prolong_space: fmap entry out of range"); return DOTS_ERR_ARGUMENT; }
+    CarryTable tab[] = {{desc->vmap, sizeof(int32_t) * nv}, {desc->fmap, sizeof(int32_t) * nf}};
+    return carry_state(who, "row map", dst, src, desc->factor, desc->ms, tab, [&](int id, double f) {      // (4: siblings share source rows)
+        return launch_carry_space(dst, src, id, tab[0].at<int>(), nullptr, tab[1].at<int>(), nullptr, 4, f, who);
+    });
 }
 
 int dots_transfer_space(dots_ctx *dst, dots_ctx *src, const dots_transfer_space_desc *desc) {
-    if (!dst || !src || !desc) { set_error("transfer_space: null argument"); return DOTS_ERR_ARGUMENT; }
-    if (dst == src) { set_error("transfer_space: source and destination are one context"); return DOTS_ERR_ARGUMENT; }
-    if (dst->shard_stride != 0 || src->shard_stride != 0) { set_error("transfer_space: not available on time slabs"); return DOTS_ERR_STATE; }
-    if (dst->device != src->device) { set_error("transfer_space: the contexts are on different devices"); return DOTS_ERR_STATE; }
+    const char *who = "transfer_space";
+    int rc = carry_guard(who, dst, src, desc);
+    if (rc) return rc;
     const Dev &dd = dst->d, &ds = src->d;
-    if (dd.T != ds.T) {
-        char buf[160];
-        snprintf(buf, sizeof buf, "transfer_space: n_time = %d, the source's %d: both levels have one time grid", dd.T, ds.T);
-        set_error(buf);
-        return DOTS_ERR_ARGUMENT;
-    }
-    if (!desc->vsrc || !desc->vw || !desc->fsrc || !desc->csrc) { set_error("transfer_space: null table"); return DOTS_ERR_ARGUMENT; }
-    if (desc->n_vertices != dd.V || desc->n_triangles != dd.F) {
-        char buf[200];
-        snprintf(buf, sizeof buf, "transfer_space: tables of %d vertices and %d triangles, the destination has %d and %d", desc->n_vertices,
-                 desc->n_triangles, dd.V, dd.F);
-        set_error(buf);
-        return DOTS_ERR_ARGUMENT;
-    }
+    if ((rc = carry_space_shapes(who, "table", dd, ds, !desc->vsrc || !desc->vw || !desc->fsrc || !desc->csrc, desc->n_vertices, desc->n_triangles))) return rc;
     // every index names a row / a corner of the source; every weight is a finite number >= 0
     const size_t nv = 3 * (size_t)dd.V, nf = (size_t)dd.F;
     for (size_t i = 0; i < nv; ++i) {
@@ -1566,41 +1555,10 @@ int dots_transfer_space(dots_ctx *dst, dots_ctx *src, const dots_transfer_space_
         if (desc->fsrc[i] < 0 || desc->fsrc[i] >= ds.F) { set_error("transfer_space: fsrc entry out of range"); return DOTS_ERR_ARGUMENT; }
     for (size_t i = 0; i < 3 * nf; ++i)
         if (desc->csrc[i] < 0 || desc->csrc[i] > 2) { set_error("transfer_space: csrc entry outside 0 .. 2"); return DOTS_ERR_ARGUMENT; }
-    int rc = check(src, true);      // (a pending penalty division is carried out, as for a download)
-    if (rc) return rc;
-    if (src->zmid_stale) { set_error("transfer_space: the source's z_mid was not materialised by its last step (dots_step_flags)"); return DOTS_ERR_STATE; }
-    if ((rc = materialise_zmid(src))) return rc;
-    if ((rc = check(dst, false, true))) return rc;
-    dst->pending_div = 0.0;      // (every array a pending division would have touched is replaced)
-    // the tables in one device buffer: [vw | vsrc | fsrc | csrc]
-    char *buf = nullptr;
-    DOTS_HIP(hipMalloc((void **)&buf, sizeof(double) * nv + sizeof(int32_t) * (nv + 4 * nf)));
-    double *vw = (double *)buf;
-    int *vs = (int *)(vw + nv), *fs = vs + nv, *cs = fs + nf;
-    hipError_t e = hipMemcpyAsync(vw, desc->vw, sizeof(double) * nv, hipMemcpyHostToDevice, dst->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(vs, desc->vsrc, sizeof(int32_t) * nv, hipMemcpyHostToDevice, dst->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(fs, desc->fsrc, sizeof(int32_t) * nf, hipMemcpyHostToDevice, dst->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(cs, desc->csrc, sizeof(int32_t) * 3 * nf, hipMemcpyHostToDevice, dst->stream);
-    if (e != hipSuccess) rc = hip_fail(e, "transfer_space: tables", __FILE__, __LINE__);
-    // the destination's stream waits for what the source has enqueued (its last step, the division, z_mid)
-    if (!rc) rc = batch_wait(dst, src);
-    if (!rc && (e = hipEventRecord(dst->ev[0], dst->stream)) != hipSuccess) rc = hip_fail(e, "hipEventRecord", __FILE__, __LINE__);
-    const int group[DOTS_N_ARRAYS] = {0, 0, 0, 0, 1, 1, 1, 2, 2, 3, 3, 3};      // recorver_scaled_solution (solver_socp.py:397-405)
-    for (int id = 0; id < DOTS_N_ARRAYS && !rc; ++id) rc = launch_transfer_space(dst, src, id, vs, vw, fs, cs, desc->factor[group[id]]);
-    if (!rc && (e = hipEventRecord(dst->ev[1], dst->stream)) != hipSuccess) rc = hip_fail(e, "hipEventRecord", __FILE__, __LINE__);
-    if (!rc) rc = batch_wait(src, dst);      // (whatever the source does next -- its release included -- comes after the reads)
-    e = hipStreamSynchronize(dst->stream);
-    if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__);
-    (void)hipFree(buf);
-    if (rc) return rc;
-    dst->zmid_stale = dst->zmid_deferred = 0;      // (z_mid's storage holds the transferred z_mid)
-    dst->kkt_halo_fresh = 0;
-    if (desc->ms) {
-        float t = 0.f;
-        DOTS_HIP(hipEventElapsedTime(&t, dst->ev[0], dst->ev[1]));
-        *desc->ms = t;
-    }
-    return 0;
+    CarryTable tab[] = {{desc->vw, sizeof(double) * nv}, {desc->vsrc, sizeof(int32_t) * nv}, {desc->fsrc, sizeof(int32_t) * nf}, {desc->csrc, sizeof(int32_t) * 3 * nf}};
+    return carry_state(who, "table", dst, src, desc->factor, desc->ms, tab, [&](int id, double f) {
+        return launch_carry_space(dst, src, id, tab[1].at<int>(), tab[0].at<double>(), tab[2].at<int>(), tab[3].at<int>(), 1, f, who);
+    });
 }
 
 // ---- dots_readout ---------------------------------------------------------------------------------------------------------

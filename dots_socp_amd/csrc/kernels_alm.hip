@@ -1495,21 +1495,30 @@ int launch_prolong(Ctx *dst, Ctx *src, int id, const int *jt, const double *wt, 
 }
 
 // ------------------------------------------------------------------------------------------
-// space prolongation (dots_prolong_space): one state array of a context on the nested refinement of its mesh, same time grid
+// state carry in space (dots_prolong_space, dots_transfer_space): one state array of a context on another mesh, same time grid
 // ------------------------------------------------------------------------------------------
-// Both contexts have one time pitch, so a destination row is one source row (triangle and corner rows: the parent's row of the same
-// component / corner / interval end) or the half-sum of two (a midpoint vertex): f * a where the two source rows are one, else
-// (f * a + f * b) * 0.5 -- the operations of cascade.prolong_space on the recovered solution, in that order (-ffp-contract=off), so
-// that the result is what an upload of the host's prolongation leaves, bit for bit.  A lane forms two neighbouring columns (one
-// 16-byte word in, one out); a row wider than 256 columns is walked in chunks of 256.  Columns outside the array's time points
-// (padding, and the slot of a corner row whose interval does not exist) are written as zero, as k_convert writes them.
-// A workgroup takes runs of consecutive destination rows, a run a whole number of groups of four vertices / triangles: the four
-// children of a triangle, which read the same 3 or 18 source rows, are numbered together by the subdivision (and stay close under a
-// locality renumbering), so the source rows come from HBM once and from the cache for the siblings.
-struct ProlongSpaceArgs {
+// Both contexts have one time pitch, so a destination row is formed from whole source rows.  A triangle row is f times the row of the
+// same component of its source triangle, a corner row f times the row of its source corner (same interval end and component): the
+// corner csrc names, or the same corner where csrc is null (a child triangle keeps its parent's corner order).  A vertex row is one
+// of two formulas, chosen at compile time because they differ in the sign of zero and in the subnormal range:
+//   nested  (a mesh to its refinement): f * a where the two source rows are one (a kept vertex), else (f * a + f * b) * 0.5;
+//   located (another triangulation):    (w0 * (f * a0) + w1 * (f * a1)) + w2 * (f * a2), no special case for a weight of 0 or 1.
+// These are the operations of cascade.prolong_space / cascade.transfer_space on the recovered solution, in that order
+// (-ffp-contract=off), so that the result is what an upload of the host's transfer leaves, bit for bit.  A lane forms two neighbouring
+// columns (16-byte words in, one out); a row's indices and weights are read once per row; a row wider than 256 columns is walked in
+// chunks of 256.  Columns outside the array's time points (padding, and the slot of a corner row whose interval does not exist) are
+// written as zero, as k_convert writes them.  A workgroup takes runs of consecutive destination rows.  Nested, a run is a whole number
+// of groups of four vertices / triangles: the four children of a triangle, which read the same 3 or 18 source rows, are numbered
+// together by the subdivision (and stay close under a locality renumbering), so the source rows come from HBM once and from the cache
+// for the siblings.  Located, neighbouring destination vertices / triangles under a locality numbering lie in the same or in
+// neighbouring source triangles, so most of the 3 source rows per vertex row come from the cache.
+struct CarrySpaceArgs {
     const double *src;
     double *dst;
-    const int *map;          // VERT: [entities][2] source vertex rows; else [entities] source triangle
+    const int *vsrc;         // vertex rows: [entities][2] (nested) or [entities][3] (located) source vertex rows
+    const double *vw;        // located vertex rows: [entities][3] weights
+    const int *fsrc;         // triangle and corner rows: [entities] source triangle
+    const int *csrc;         // corner rows: [entities][3] source corner of every destination corner, or null: the same corner
     int64_t rows;            // destination rows
     int64_t run;             // rows per run
     int sh;                  // log2 of the time pitch (both sides)
@@ -1517,8 +1526,10 @@ struct ProlongSpaceArgs {
     double f;
 };
 
-template <int RPE>      // rows per vertex / triangle: 1, 3 (B, E), 18 (corner arrays: row = ((f * 3 + k) * 2 + s) * 3 + c, column = interval + s)
-__global__ __launch_bounds__(BLOCK) void k_prolong_space(ProlongSpaceArgs a) {
+// RPE: rows per vertex / triangle: 1, 3 (B, E), 18 (corner arrays: row = ((f * 3 + k) * 2 + s) * 3 + c, column = interval + s);
+// LOCATED: the vertex formula (RPE = 1 only)
+template <int RPE, bool LOCATED = false>
+__global__ __launch_bounds__(BLOCK) void k_carry_space(CarrySpaceArgs a) {
     const int tid = threadIdx.x;
     const int hp = a.sh - 1;                      // log2 of the column pairs per row
     const int hl = min(hp, 7);                    // log2 of the lanes per row: at most 128 pairs = 256 columns per chunk
@@ -1528,27 +1539,45 @@ __global__ __launch_bounds__(BLOCK) void k_prolong_space(ProlongSpaceArgs a) {
     for (int64_t run = blockIdx.x; run < n_runs; run += gridDim.x) {
         const int64_t r_end = min(a.rows, (run + 1) * a.run);
         for (int64_t r = run * a.run + rr; r < r_end; r += rpp) {
-            const int64_t ent = r / RPE;
-            const int sub = (int)(r - ent * RPE);
-            int64_t ra, rb;
-            if (RPE == 1) {
-                ra = a.map[2 * ent];
-                rb = a.map[2 * ent + 1];
+            int64_t r0, r1 = 0, r2 = 0;             // source rows: one, or the 2 / 3 of a vertex row
+            double w0 = 0.0, w1 = 0.0, w2 = 0.0;
+            int s = 0;                              // interval end of a corner row: its columns are shifted by one
+            if (RPE == 1 && LOCATED) {
+                const int *v = a.vsrc + 3 * r;
+                const double *w = a.vw + 3 * r;
+                r0 = v[0], r1 = v[1], r2 = v[2];
+                w0 = w[0], w1 = w[1], w2 = w[2];
+            } else if (RPE == 1) {
+                r0 = a.vsrc[2 * r];
+                r1 = a.vsrc[2 * r + 1];
             } else {
-                ra = rb = (int64_t)a.map[ent] * RPE + sub;
+                const int64_t ent = r / RPE;
+                const int sub = (int)(r - ent * RPE);
+                r0 = a.fsrc[ent];
+                if (RPE == 18) {      // sub = (k * 2 + s) * 3 + c
+                    const int k = sub / 6, rest = sub - 6 * k;
+                    s = rest / 3;
+                    r0 = (r0 * 3 + (a.csrc ? a.csrc[3 * ent + k] : k)) * 6 + rest;
+                } else {
+                    r0 = r0 * 3 + sub;
+                }
             }
-            const int s = RPE == 18 ? (sub / 3) & 1 : 0;
-            const double *xa = a.src + (ra << a.sh), *xb = a.src + (rb << a.sh);
+            const double *x0 = a.src + (r0 << a.sh), *x1 = a.src + (r1 << a.sh), *x2 = a.src + (r2 << a.sh);
             double *y = a.dst + (r << a.sh);
             for (int p = p0; p < (1 << hp); p += 1 << hl) {
-                D2 va = ld2(xa + 2 * p), out;
-                if (ra != rb) {
-                    const D2 vb = ld2(xb + 2 * p);
+                const D2 v0 = ld2(x0 + 2 * p);
+                D2 out;
+                if (RPE == 1 && LOCATED) {
+                    const D2 v1 = ld2(x1 + 2 * p), v2 = ld2(x2 + 2 * p);
 #pragma unroll
-                    for (int q = 0; q < 2; ++q) out.v[q] = (a.f * va.v[q] + a.f * vb.v[q]) * 0.5;
+                    for (int q = 0; q < 2; ++q) out.v[q] = (w0 * (a.f * v0.v[q]) + w1 * (a.f * v1.v[q])) + w2 * (a.f * v2.v[q]);
+                } else if (RPE == 1 && r0 != r1) {
+                    const D2 v1 = ld2(x1 + 2 * p);
+#pragma unroll
+                    for (int q = 0; q < 2; ++q) out.v[q] = (a.f * v0.v[q] + a.f * v1.v[q]) * 0.5;
                 } else {
 #pragma unroll
-                    for (int q = 0; q < 2; ++q) out.v[q] = a.f * va.v[q];
+                    for (int q = 0; q < 2; ++q) out.v[q] = a.f * v0.v[q];
                 }
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
@@ -1561,118 +1590,13 @@ __global__ __launch_bounds__(BLOCK) void k_prolong_space(ProlongSpaceArgs a) {
     }
 }
 
-int launch_prolong_space(Ctx *dst, Ctx *src, int id, const int *vmap, const int *fmap, double f) {
+// vw null: the nested vertex formula (vsrc [V][2]), else the located one (vsrc, vw [V][3]); group: the vertices / triangles that share
+// source rows and stay in one run (4 siblings of a subdivision, or 1); who: the entry point, for the message
+int launch_carry_space(Ctx *dst, Ctx *src, int id, const int *vsrc, const double *vw, const int *fsrc, const int *csrc, int group, double f,
+                       const char *who) {
     const Dev &dd = dst->d;
     const int kind = array_kind(id);
-    ProlongSpaceArgs a{};
-    a.src = src->arr(id);
-    a.dst = dst->arr(id);
-    a.map = kind <= 1 ? vmap : fmap;
-    const int rpe = kind <= 1 ? 1 : (kind == 2 ? 3 : 18);
-    a.rows = (int64_t)rpe * (kind <= 1 ? dd.V : dd.F);
-    a.sh = dd.tp_shift;
-    a.n_valid = dd.T + ((kind == 0 || kind == 2) ? 1 : 0);
-    a.f = f;
-    if (a.sh < 1 || dd.TP > TILE_ELEMS || a.sh != src->d.tp_shift) { set_error("prolong_space: time pitch out of range"); return DOTS_ERR_STATE; }
-    // a run: whole groups of four vertices / triangles, whole passes of the workgroup, about 32 KB of destination
-    const int rpp = BLOCK >> std::min(a.sh - 1, 7);
-    int64_t unit = 4 * rpe;
-    while (unit % rpp) unit *= 2;
-    const int64_t row_bytes = (int64_t)sizeof(double) << a.sh;
-    a.run = unit * std::max<int64_t>(1, (32768 + unit * row_bytes - 1) / (unit * row_bytes));
-    const int64_t n_runs = (a.rows + a.run - 1) / a.run;
-    const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(n_runs, 4096)));
-    if (rpe == 1) hipLaunchKernelGGL(k_prolong_space<1>, grid, dim3(BLOCK), 0, dst->stream, a);
-    else if (rpe == 3) hipLaunchKernelGGL(k_prolong_space<3>, grid, dim3(BLOCK), 0, dst->stream, a);
-    else hipLaunchKernelGGL(k_prolong_space<18>, grid, dim3(BLOCK), 0, dst->stream, a);
-    DOTS_HIP(hipGetLastError());
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------
-// space transfer (dots_transfer_space): one state array of a context on another triangulation of the same surface, same time grid
-// ------------------------------------------------------------------------------------------
-// A destination vertex row is the barycentric combination of three source vertex rows, (w0 * (f * a0) + w1 * (f * a1)) + w2 * (f * a2)
-// -- the operations of cascade.transfer_space on the recovered solution, in that order and with no special case for a weight of 0 or
-// 1 (-ffp-contract=off) --; a triangle row f times the row of the same component of the located source triangle, a corner row f times
-// the row of the located corner, same interval end and component.  The shape is k_prolong_space's: a lane forms two neighbouring
-// columns (16-byte words in, one out), a row's indices and weights are read once per row, a row wider than 256 columns is walked in
-// chunks of 256, columns outside the array's time points are written as zero, and a workgroup takes runs of consecutive destination
-// rows: neighbouring destination vertices / triangles under a locality numbering lie in the same or in neighbouring source triangles,
-// so most of the 3 source rows per vertex row come from the cache.
-struct TransferSpaceArgs {
-    const double *src;
-    double *dst;
-    const int *vsrc;         // VERT: [entities][3] source vertex rows
-    const double *vw;        // VERT: [entities][3] weights
-    const int *fsrc;         // else: [entities] source triangle
-    const int *csrc;         // corner arrays: [entities][3] source corner of every destination corner
-    int64_t rows;            // destination rows
-    int64_t run;             // rows per run
-    int sh;                  // log2 of the time pitch (both sides)
-    int n_valid;             // time points of the array: T + 1 (node arrays) or T
-    double f;
-};
-
-template <int RPE>      // rows per vertex / triangle: 1, 3 (B, E), 18 (corner arrays: row = ((f * 3 + k) * 2 + s) * 3 + c, column = interval + s)
-__global__ __launch_bounds__(BLOCK) void k_transfer_space(TransferSpaceArgs a) {
-    const int tid = threadIdx.x;
-    const int hp = a.sh - 1;                      // log2 of the column pairs per row
-    const int hl = min(hp, 7);                    // log2 of the lanes per row: at most 128 pairs = 256 columns per chunk
-    const int rpp = BLOCK >> hl;                  // rows per pass
-    const int rr = tid >> hl, p0 = tid & ((1 << hl) - 1);
-    const int64_t n_runs = (a.rows + a.run - 1) / a.run;
-    for (int64_t run = blockIdx.x; run < n_runs; run += gridDim.x) {
-        const int64_t r_end = min(a.rows, (run + 1) * a.run);
-        for (int64_t r = run * a.run + rr; r < r_end; r += rpp) {
-            double *y = a.dst + (r << a.sh);
-            if (RPE == 1) {
-                const int *s = a.vsrc + 3 * r;
-                const double *w = a.vw + 3 * r;
-                const double w0 = w[0], w1 = w[1], w2 = w[2];
-                const double *x0 = a.src + ((int64_t)s[0] << a.sh), *x1 = a.src + ((int64_t)s[1] << a.sh), *x2 = a.src + ((int64_t)s[2] << a.sh);
-                for (int p = p0; p < (1 << hp); p += 1 << hl) {
-                    const D2 v0 = ld2(x0 + 2 * p), v1 = ld2(x1 + 2 * p), v2 = ld2(x2 + 2 * p);
-                    D2 out;
-#pragma unroll
-                    for (int q = 0; q < 2; ++q) {
-                        out.v[q] = (w0 * (a.f * v0.v[q]) + w1 * (a.f * v1.v[q])) + w2 * (a.f * v2.v[q]);
-                        if (2 * p + q >= a.n_valid) out.v[q] = 0.0;
-                    }
-                    st2(y + 2 * p, out);
-                }
-            } else {
-                const int64_t ent = r / RPE;
-                const int sub = (int)(r - ent * RPE);
-                int64_t rs = a.fsrc[ent];
-                int s = 0;
-                if (RPE == 18) {      // sub = (k * 2 + s) * 3 + c
-                    const int k = sub / 6, rest = sub - 6 * k;
-                    s = rest / 3;
-                    rs = (rs * 3 + a.csrc[3 * ent + k]) * 6 + rest;
-                } else {
-                    rs = rs * 3 + sub;
-                }
-                const double *x = a.src + (rs << a.sh);
-                for (int p = p0; p < (1 << hp); p += 1 << hl) {
-                    const D2 v = ld2(x + 2 * p);
-                    D2 out;
-#pragma unroll
-                    for (int q = 0; q < 2; ++q) {
-                        const int t = 2 * p + q - s;
-                        out.v[q] = (t < 0 || t >= a.n_valid) ? 0.0 : a.f * v.v[q];
-                    }
-                    st2(y + 2 * p, out);
-                }
-            }
-        }
-    }
-}
-
-int launch_transfer_space(Ctx *dst, Ctx *src, int id, const int *vsrc, const double *vw, const int *fsrc, const int *csrc, double f) {
-    const Dev &dd = dst->d;
-    const int kind = array_kind(id);
-    TransferSpaceArgs a{};
+    CarrySpaceArgs a{};
     a.src = src->arr(id);
     a.dst = dst->arr(id);
     a.vsrc = vsrc;
@@ -1684,18 +1608,19 @@ int launch_transfer_space(Ctx *dst, Ctx *src, int id, const int *vsrc, const dou
     a.sh = dd.tp_shift;
     a.n_valid = dd.T + ((kind == 0 || kind == 2) ? 1 : 0);
     a.f = f;
-    if (a.sh < 1 || dd.TP > TILE_ELEMS || a.sh != src->d.tp_shift) { set_error("transfer_space: time pitch out of range"); return DOTS_ERR_STATE; }
-    // a run: whole vertices / triangles, whole passes of the workgroup, about 32 KB of destination
+    if (a.sh < 1 || dd.TP > TILE_ELEMS || a.sh != src->d.tp_shift) { set_error(std::string(who) + ": time pitch out of range"); return DOTS_ERR_STATE; }
+    // a run: whole groups of vertices / triangles, whole passes of the workgroup, about 32 KB of destination
     const int rpp = BLOCK >> std::min(a.sh - 1, 7);
-    int64_t unit = rpe;
+    int64_t unit = (int64_t)group * rpe;
     while (unit % rpp) unit *= 2;
     const int64_t row_bytes = (int64_t)sizeof(double) << a.sh;
     a.run = unit * std::max<int64_t>(1, (32768 + unit * row_bytes - 1) / (unit * row_bytes));
     const int64_t n_runs = (a.rows + a.run - 1) / a.run;
     const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(n_runs, 4096)));
-    if (rpe == 1) hipLaunchKernelGGL(k_transfer_space<1>, grid, dim3(BLOCK), 0, dst->stream, a);
-    else if (rpe == 3) hipLaunchKernelGGL(k_transfer_space<3>, grid, dim3(BLOCK), 0, dst->stream, a);
-    else hipLaunchKernelGGL(k_transfer_space<18>, grid, dim3(BLOCK), 0, dst->stream, a);
+    if (rpe == 1 && vw) hipLaunchKernelGGL((k_carry_space<1, true>), grid, dim3(BLOCK), 0, dst->stream, a);
+    else if (rpe == 1) hipLaunchKernelGGL(k_carry_space<1>, grid, dim3(BLOCK), 0, dst->stream, a);
+    else if (rpe == 3) hipLaunchKernelGGL(k_carry_space<3>, grid, dim3(BLOCK), 0, dst->stream, a);
+    else hipLaunchKernelGGL(k_carry_space<18>, grid, dim3(BLOCK), 0, dst->stream, a);
     DOTS_HIP(hipGetLastError());
     return 0;
 }

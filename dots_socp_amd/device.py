@@ -188,6 +188,24 @@ class DeviceProblem:
         self.readout_ms, self.readout_bytes = ms.value, self.debug_counter(9) - before
         return out_mu, out_E, mass, neg
 
+    def _carry_from(self, who, src, entry, describe, factors, same_grid):
+        """What the three carriers share: the guards (``same_grid``: one ``n_time``), ``describe()`` -- the method's own validation, giving
+        its descriptor and the arrays it points to --, the factors, the call of ``entry`` and its check.  Returns the launches' milliseconds."""
+        if self.slab or src.slab:
+            raise ValueError(f"{who}: not available on time slabs")
+        if same_grid and self.T != src.T:
+            raise ValueError(f"{who}: n_time = {self.T}, the source's {src.T}: both levels have one time grid")
+        d, _arrays = describe()      # (_arrays: alive until the call has returned)
+        for i, f in enumerate(factors):
+            d.factor[i] = float(f)
+        ms = C.c_double()
+        d.ms = C.pointer(ms)
+        _lib.check(getattr(self.lib, entry)(self._h, src._h, C.byref(d)), entry)
+        return ms.value
+
+    def _state_pitch(self):
+        return max(8, 1 << int(np.ceil(np.log2(self.T + 1))))
+
     def prolong_from(self, src: "DeviceProblem", factors=(1.0, 1.0, 1.0, 1.0)):
         """Fill this context's twelve state arrays with those of ``src`` (the same mesh on the same device, another ``n_time``,
         possibly another device numbering) interpolated linearly in time on the device (dots_prolong_time; cascade.prolong_time is
@@ -195,23 +213,19 @@ class DeviceProblem:
         are multiplied with first -- the four factors of ``AlmSolver.recovered``.  Returns the milliseconds of the launches."""
         from . import cascade
 
-        if self.slab or src.slab:
-            raise ValueError("prolong_from: not available on time slabs")
-        if (self.V, self.F) != (src.V, src.F):
-            raise ValueError(f"prolong_from: another mesh (V, F = {self.V}, {self.F}, the source's {src.V}, {src.F})")
-        nj, nw = cascade.time_weights(src.T, self.T, node=True)
-        ij, iw = cascade.time_weights(src.T, self.T, node=False)
-        vmap = cascade.row_map(self.plan.perm_vert, src.plan.perm_vert, self.V)
-        fmap = cascade.row_map(self.plan.perm_tri, src.plan.perm_tri, self.F)
-        ms = C.c_double()
-        d = _lib.ProlongDesc()
-        d.node_j, d.node_w, d.interval_j, d.interval_w = _ptr(nj, C.c_int32), _ptr(nw, C.c_double), _ptr(ij, C.c_int32), _ptr(iw, C.c_double)
-        d.vmap, d.fmap = _ptr(vmap, C.c_int32), _ptr(fmap, C.c_int32)
-        for i, f in enumerate(factors):
-            d.factor[i] = float(f)
-        d.ms = C.pointer(ms)
-        _lib.check(self.lib.dots_prolong_time(self._h, src._h, C.byref(d)), "dots_prolong_time")
-        return ms.value
+        def describe():
+            if (self.V, self.F) != (src.V, src.F):
+                raise ValueError(f"prolong_from: another mesh (V, F = {self.V}, {self.F}, the source's {src.V}, {src.F})")
+            nj, nw = cascade.time_weights(src.T, self.T, node=True)
+            ij, iw = cascade.time_weights(src.T, self.T, node=False)
+            vmap = cascade.row_map(self.plan.perm_vert, src.plan.perm_vert, self.V)
+            fmap = cascade.row_map(self.plan.perm_tri, src.plan.perm_tri, self.F)
+            d = _lib.ProlongDesc()
+            d.node_j, d.node_w, d.interval_j, d.interval_w = _ptr(nj, C.c_int32), _ptr(nw, C.c_double), _ptr(ij, C.c_int32), _ptr(iw, C.c_double)
+            d.vmap, d.fmap = _ptr(vmap, C.c_int32), _ptr(fmap, C.c_int32)
+            return d, (nj, nw, ij, iw, vmap, fmap)
+
+        return self._carry_from("prolong_from", src, "dots_prolong_time", describe, factors, same_grid=False)
 
     def prolong_space_from(self, src: "DeviceProblem", parents, factors=(1.0, 1.0, 1.0, 1.0)):
         """Fill this context's twelve state arrays from those of ``src``, a context on the parent mesh of this one (``parents``:
@@ -220,24 +234,18 @@ class DeviceProblem:
         bytes the transfer reads and writes when every source row is read once."""
         from . import cascade
 
-        if self.slab or src.slab:
-            raise ValueError("prolong_space_from: not available on time slabs")
-        if self.T != src.T:
-            raise ValueError(f"prolong_space_from: n_time = {self.T}, the source's {src.T}: both levels have one time grid")
-        vp, tp = cascade.check_parents(parents, n_vertices=src.V, n_triangles=src.F)
-        if (vp.shape[0], tp.shape[0]) != (self.V, self.F):
-            raise ValueError(f"prolong_space_from: parents of a mesh with V, F = {vp.shape[0]}, {tp.shape[0]}, this one has {self.V}, {self.F}")
-        vmap, fmap = cascade.space_row_maps(parents, src.V, src.F, self.plan.perm_vert, self.plan.perm_tri, src.plan.perm_vert, src.plan.perm_tri)
-        ms = C.c_double()
-        d = _lib.ProlongSpaceDesc()
-        d.vmap, d.fmap, d.n_vertices, d.n_triangles = _ptr(vmap, C.c_int32), _ptr(fmap, C.c_int32), self.V, self.F
-        for i, f in enumerate(factors):
-            d.factor[i] = float(f)
-        d.ms = C.pointer(ms)
-        _lib.check(self.lib.dots_prolong_space(self._h, src._h, C.byref(d)), "dots_prolong_space")
-        pitch = max(8, 1 << int(np.ceil(np.log2(self.T + 1))))
-        self.prolong_bytes = 8 * pitch * (8 * (self.V + src.V) + (2 * 3 + 2 * 18) * (self.F + src.F))
-        return ms.value
+        def describe():
+            vp, tp = cascade.check_parents(parents, n_vertices=src.V, n_triangles=src.F)
+            if (vp.shape[0], tp.shape[0]) != (self.V, self.F):
+                raise ValueError(f"prolong_space_from: parents of a mesh with V, F = {vp.shape[0]}, {tp.shape[0]}, this one has {self.V}, {self.F}")
+            vmap, fmap = cascade.space_row_maps(parents, src.V, src.F, self.plan.perm_vert, self.plan.perm_tri, src.plan.perm_vert, src.plan.perm_tri)
+            d = _lib.ProlongSpaceDesc()
+            d.vmap, d.fmap, d.n_vertices, d.n_triangles = _ptr(vmap, C.c_int32), _ptr(fmap, C.c_int32), self.V, self.F
+            return d, (vmap, fmap)
+
+        ms = self._carry_from("prolong_space_from", src, "dots_prolong_space", describe, factors, same_grid=True)
+        self.prolong_bytes = 8 * self._state_pitch() * (8 * (self.V + src.V) + (2 * 3 + 2 * 18) * (self.F + src.F))
+        return ms
 
     def transfer_space_from(self, src: "DeviceProblem", transfer, factors=(1.0, 1.0, 1.0, 1.0)):
         """Fill this context's twelve state arrays from those of ``src``, a context on another triangulation of the same surface
@@ -249,25 +257,19 @@ class DeviceProblem:
         come from the cache."""
         from . import cascade
 
-        if self.slab or src.slab:
-            raise ValueError("transfer_space_from: not available on time slabs")
-        if self.T != src.T:
-            raise ValueError(f"transfer_space_from: n_time = {self.T}, the source's {src.T}: both levels have one time grid")
-        vs, _, ts, _ = cascade.check_transfer(transfer, n_vertices=src.V, n_triangles=src.F)
-        if (vs.shape[0], ts.shape[0]) != (self.V, self.F):
-            raise ValueError(f"transfer_space_from: a transfer to a mesh with V, F = {vs.shape[0]}, {ts.shape[0]}, this one has {self.V}, {self.F}")
-        vsrc, vw, fsrc, csrc = cascade.transfer_row_maps(transfer, self.plan.perm_vert, self.plan.perm_tri, src.plan.perm_vert, src.plan.perm_tri)
-        ms = C.c_double()
-        d = _lib.TransferSpaceDesc()
-        d.vsrc, d.vw, d.fsrc, d.csrc = _ptr(vsrc, C.c_int32), _ptr(vw, C.c_double), _ptr(fsrc, C.c_int32), _ptr(csrc, C.c_int32)
-        d.n_vertices, d.n_triangles = self.V, self.F
-        for i, f in enumerate(factors):
-            d.factor[i] = float(f)
-        d.ms = C.pointer(ms)
-        _lib.check(self.lib.dots_transfer_space(self._h, src._h, C.byref(d)), "dots_transfer_space")
-        pitch = max(8, 1 << int(np.ceil(np.log2(self.T + 1))))
-        self.prolong_bytes = 8 * pitch * (8 * 4 * self.V + (2 * 3 + 2 * 18) * 2 * self.F)
-        return ms.value
+        def describe():
+            vs, _, ts, _ = cascade.check_transfer(transfer, n_vertices=src.V, n_triangles=src.F)
+            if (vs.shape[0], ts.shape[0]) != (self.V, self.F):
+                raise ValueError(f"transfer_space_from: a transfer to a mesh with V, F = {vs.shape[0]}, {ts.shape[0]}, this one has {self.V}, {self.F}")
+            vsrc, vw, fsrc, csrc = cascade.transfer_row_maps(transfer, self.plan.perm_vert, self.plan.perm_tri, src.plan.perm_vert, src.plan.perm_tri)
+            d = _lib.TransferSpaceDesc()
+            d.vsrc, d.vw, d.fsrc, d.csrc = _ptr(vsrc, C.c_int32), _ptr(vw, C.c_double), _ptr(fsrc, C.c_int32), _ptr(csrc, C.c_int32)
+            d.n_vertices, d.n_triangles = self.V, self.F
+            return d, (vsrc, vw, fsrc, csrc)
+
+        ms = self._carry_from("transfer_space_from", src, "dots_transfer_space", describe, factors, same_grid=True)
+        self.prolong_bytes = 8 * self._state_pitch() * (8 * 4 * self.V + (2 * 3 + 2 * 18) * 2 * self.F)
+        return ms
 
     # ---- the hot loop
     def step(self, n_iters=1, wait=True):

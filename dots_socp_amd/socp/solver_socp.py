@@ -71,6 +71,35 @@ def _validate_checkpoints(tol_checkpoints, tol):
     return sorted(tol_checkpoints, reverse=True)
 
 
+def _state_carrier(n_time, init_from, init_solution, time_slab, init_parents, init_transfer):
+    """How a solver's state comes from ``init_from``, validated before any device call: None without ``init_from``, else ``carry(dev)``,
+    which fills the DeviceProblem ``dev`` and returns the milliseconds -- in space over ``init_parents`` / ``init_transfer``, else in time."""
+    if init_transfer is not None and init_parents is not None:
+        raise ValueError("init_transfer and init_parents are mutually exclusive: the level below is a located mesh or the parent mesh")
+    space = None      # (option, which mesh init_from is on, the DeviceProblem method, its map)
+    if init_parents is not None:
+        space = ("init_parents", "parent", "prolong_space_from", init_parents)
+    elif init_transfer is not None:
+        space = ("init_transfer", "coarse", "transfer_space_from", init_transfer)
+    if init_from is None:
+        if space:
+            raise ValueError(f"{space[0]} needs init_from (the solver on the {space[1]} mesh)")
+        return None
+    if init_solution:
+        raise ValueError("init_from and init_solution are mutually exclusive: the warm start comes from one of them")
+    if time_slab is not None:
+        raise ValueError("init_from is not available on time slabs")
+    if not getattr(init_from, "finalized", False):
+        raise ValueError("init_from must have been finalised (finalize(download=False) is enough)")
+    if space is None:
+        return lambda dev: dev.prolong_from(init_from.dev, init_from.recovery_factors())
+    option, mesh, method, table = space
+    if int(init_from.n_time) != int(n_time):
+        raise ValueError(f"{option}: the {mesh} mesh's solver has n_time = {int(init_from.n_time)}, this one {int(n_time)}: "
+                         "one call changes the mesh or the time grid, not both")
+    return lambda dev: getattr(dev, method)(init_from.dev, table, init_from.recovery_factors())
+
+
 class AlmSolver:
     """The reference's solver as an object: ``__init__`` = setup (solver_socp.py:96-652),
     ``iterate()`` = one pass of the main loop (:656-823), ``finalize()`` = :826-871.
@@ -102,25 +131,7 @@ class AlmSolver:
         factor.  ``batched``: whether the solver is stepped by a batch (default: whenever ``plan`` or
         ``front_owner`` is given)."""
         check_time_nodes(n_time, lap_solver, time_slab)
-        if init_transfer is not None and init_parents is not None:
-            raise ValueError("init_transfer and init_parents are mutually exclusive: the level below is a located mesh or the parent mesh")
-        if init_from is not None:
-            if init_solution:
-                raise ValueError("init_from and init_solution are mutually exclusive: the warm start comes from one of them")
-            if time_slab is not None:
-                raise ValueError("init_from is not available on time slabs")
-            if not getattr(init_from, "finalized", False):
-                raise ValueError("init_from must have been finalised (finalize(download=False) is enough)")
-            if init_parents is not None and int(init_from.n_time) != int(n_time):
-                raise ValueError(f"init_parents: the parent mesh's solver has n_time = {int(init_from.n_time)}, this one {int(n_time)}: "
-                                 "one call changes the mesh or the time grid, not both")
-            if init_transfer is not None and int(init_from.n_time) != int(n_time):
-                raise ValueError(f"init_transfer: the coarse mesh's solver has n_time = {int(init_from.n_time)}, this one {int(n_time)}: "
-                                 "one call changes the mesh or the time grid, not both")
-        elif init_parents is not None:
-            raise ValueError("init_parents needs init_from (the solver on the parent mesh)")
-        elif init_transfer is not None:
-            raise ValueError("init_transfer needs init_from (the solver on the coarse mesh)")
+        carry = _state_carrier(n_time, init_from, init_solution, time_slab, init_parents, init_transfer)
         self.tol_checkpoints = _validate_checkpoints(tol_checkpoints, tol)
         self.geometry = geometry        # (read_out takes the area weights and mu0 / mu1 from it)
         self.checkpoint_solutions = []
@@ -164,13 +175,8 @@ class AlmSolver:
         if preconditioner not in ("multigrid", "jacobi"):
             raise ValueError("preconditioner must be 'multigrid' or 'jacobi'")
         self.prolong_ms = None          # device milliseconds of the transfer from ``init_from``
-        if init_from is not None:
-            if init_parents is not None:
-                self.prolong_ms = dev.prolong_space_from(init_from.dev, init_parents, init_from.recovery_factors())
-            elif init_transfer is not None:
-                self.prolong_ms = dev.transfer_space_from(init_from.dev, init_transfer, init_from.recovery_factors())
-            else:
-                self.prolong_ms = dev.prolong_from(init_from.dev, init_from.recovery_factors())
+        if carry is not None:
+            self.prolong_ms = carry(dev)
             if release_init_from:
                 init_from.close()
         self.mg_summary = self.front_summary = None

@@ -136,6 +136,25 @@ def test_row_map_composes_two_numberings():
     assert np.array_equal(np.arange(9)[cascade.row_map(pd, None, 9)], pd)
 
 
+@pytest.mark.parametrize("who", ["row_map", "space_row_maps", "transfer_row_maps"])
+def test_inverse_numbering_rejects_a_permutation_of_the_wrong_size(who):
+    """The one inverse the three row-map builders share, under the name of each"""
+    perm = np.random.default_rng(6).permutation(9)
+    inv = cascade.inverse_numbering(perm, 9, who)
+    assert inv.dtype == np.int64 and np.array_equal(inv[perm], np.arange(9)) and np.array_equal(perm[inv], np.arange(9))
+    assert np.array_equal(cascade.inverse_numbering(None, 9, who), np.arange(9))
+    for n in (8, 10):
+        with pytest.raises(ValueError, match=f"^{who}: a permutation of the wrong size$"):
+            cascade.inverse_numbering(perm, n, who)
+    with pytest.raises(ValueError, match=f"^{who}: a permutation of the wrong size$"):
+        cascade.inverse_numbering(perm.reshape(3, 3), 9, who)
+
+
+def test_row_map_rejects_a_source_numbering_of_the_wrong_size():
+    with pytest.raises(ValueError, match="^row_map: a permutation of the wrong size$"):
+        cascade.row_map(np.arange(9)[::-1], np.arange(8), 9)
+
+
 # ---------------------------------------------------------------------------- the driver's argument checks
 def test_cascade_checks_its_arguments_before_any_device(monkeypatch):
     import importlib

@@ -8,12 +8,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from carry_checks import STATE, bits, check_carry, with_bumps
 from conftest import has_gpu
 from dots_socp_amd import _lib, cascade, meshes
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not has_gpu(), reason="needs a GPU")]
 
-STATE = ("phi", "A", "B", "lambda_c", "z_fst", "z_mid", "z_end", "mu", "E", "beta_fst", "beta_mid", "beta_end")
 CONVERGENCE_TOL = 1e-5
 
 
@@ -27,14 +27,6 @@ def rotation(az, ax):
 def rotated_icosphere(level, az, ax):
     v, t = meshes.icosphere(level)
     return v @ rotation(az, ax).T, t
-
-
-def with_bumps(v, t):
-    geom, _ = meshes.make_geometry(v, t, normalize=False)
-    c = meshes.farthest_vertices(geom["vertices"], 0, 3)
-    geom["mu0"] = meshes.bump_density(geom["vertices"], geom["area_vertices"], [c[0]], 1.0, 0.4)
-    geom["mu1"] = meshes.bump_density(geom["vertices"], geom["area_vertices"], [c[1], c[2]], 1.0, 0.4)
-    return geom
 
 
 _pairs = {}
@@ -104,60 +96,11 @@ def carry_up(solution, fine):
     return cascade.transfer_space_solution(solution, fine["transfer"])
 
 
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
-
-
-def scaled_source(geom, n_time, reorder, seed):
-    """A finalised solver on the coarse mesh whose recovery factors all differ from 1 (a few iterations with penalty updates, a primal /
-    dual rescaling, a z rescale), its twelve arrays then filled with random values: every entry of every array is exercised."""
-    from dots_socp_amd.socp.solver_socp import AlmSolver
-
-    alm = AlmSolver(n_time, geom, nit=40, tol=1e-12, check_kkt_step_by_step=True, reorder=reorder)
-    for _ in range(6):
-        alm.iterate()
-    alm.adjust_penalty(1.3)
-    alm.scale_prim_dual(scale_factor=(5.0, 0.7))
-    alm.scale_variable_z(1.5)
-    alm.iterate()
-    alm.finalize(download=False)
-    assert all(f != 1.0 for f in alm.recovery_factors())
-    rng = np.random.default_rng(seed)
-    for k in STATE:
-        alm.dev.upload(k, rng.standard_normal(alm.dev.shape(k)))
-    return alm
-
-
-def check_pair(name, n_time, src_orders=(True, False), dst_orders=("nd", False)):
-    from dots_socp_amd.device import DeviceProblem
-
+def check_pair(name, n_time, **orders):
     coarse, fine, transfer = pair(name)
-    for src_order in src_orders:
-        alm = scaled_source(coarse, n_time, src_order, seed=n_time)
-        try:
-            assert (alm.dev.plan.perm_vert is not None) == bool(src_order)
-            want = cascade.transfer_space_solution({k: alm.recovered(k, alm.dev.download(k)) for k in STATE}, transfer)
-            for dst_order in dst_orders:
-                with DeviceProblem(n_time, fine, lap_solver="modal_pcg", reorder=dst_order) as dst, \
-                        DeviceProblem(n_time, fine, lap_solver="modal_pcg", reorder=dst_order) as ref:
-                    ms = dst.transfer_space_from(alm.dev, transfer, alm.recovery_factors())
-                    pitch = max(8, 1 << int(np.ceil(np.log2(n_time + 1))))
-                    assert ms >= 0.0 and dst.prolong_bytes == 8 * pitch * (32 * dst.V + 84 * dst.F)
-                    for k in STATE:
-                        ref.upload(k, want[k])
-                    for k in STATE:
-                        got, up = dst.download(k), ref.download(k)
-                        assert got.shape == want[k].shape
-                        assert np.array_equal(bits(got), bits(up)), (k, src_order, dst_order, float(np.max(np.abs(got - up))))
-                        assert np.array_equal(bits(got), bits(want[k])), (k, src_order, dst_order)
-                    # the columns beyond the arrays' time points are as an upload leaves them: one step from either gives the same iterate
-                    if n_time + 1 <= 256:      # (above, only a context with a factor steps)
-                        for dev in (dst, ref):
-                            dev.step(1)
-                        for k in STATE:
-                            assert np.array_equal(bits(dst.download(k)), bits(ref.download(k))), (k, "after a step", src_order, dst_order)
-        finally:
-            alm.close()
+    check_carry(coarse, fine, n_time, carry=lambda dst, src, factors: dst.transfer_space_from(src, transfer, factors),
+                host=lambda solution: cascade.transfer_space_solution(solution, transfer),
+                bytes_ok=lambda dst, pitch: dst.prolong_bytes == 8 * pitch * (32 * dst.V + 84 * dst.F), **orders)
 
 
 @pytest.mark.parametrize("name", ["plane", "icosphere", "torus"])
