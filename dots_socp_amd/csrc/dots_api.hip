@@ -1748,6 +1748,7 @@ int64_t dots_debug_counter(dots_ctx *c, int which) {
         case 7: return c->front_many_launches;        // sweep launches the last front_solve_many on this (first) context enqueued
         case 8: return c->front_many_split;           // ... of those, launches with fewer rhs than their chunk (many_launch halved: LDS or 1024-thread cap)
         case 9: return c->d2h_bytes;                  // bytes dots_download and dots_readout have copied device -> host
+        case 10: return c->n_front_allocs;            // device allocations the installed factor holds (0 after front_release: also after a failed dots_front_setup)
         default: return -1;
     }
 }

@@ -37,7 +37,6 @@
 #include <array>
 #include <cstdio>
 #include <cstdlib>
-#include <functional>
 #include <string>
 #include <vector>
 
@@ -972,23 +971,90 @@ struct Group {                 // one node of the sweeps
     int n = 0, b = 0, k0 = 0, planes = 0, colour = -1, parent = -1;
     int64_t foff = 0, woff = 0;
 };
-}  // namespace
 
-int front_setup(Ctx *c, const dots_front_desc *h) {
-    const Dev &d = c->dcg;
-    auto bad = [&](const char *what) {
-        set_error(std::string("front_setup: ") + what);
-        return (int)DOTS_ERR_ARGUMENT;
-    };
+// What the phases of front_setup share.  Each block is written by the phase its comment names and only read by the later ones.
+struct FrontPlan {
+    int nn = 0, nb = 0;                                   // original nodes (check_desc); bands = cuts.size() - 1 (group_bands)
+    // check_desc
+    std::vector<int> level_of, parent, cuts;              // (group_bands splits a band of more than 8 update planes: cuts)
+    double entries_unmerged = 0.0;                        // (install_leaves takes off what the leaf kernels do not read)
+    bool top_inv = false;                                 // the top band stores explicit inverses (its nodes have no boundary rows)
+    // build_tree
+    std::vector<FrontNode> nodes;
+    std::vector<int> vmap0, bd_vertex;
+    bool identity0 = true;                                // vmap0 is the identity
+    // group_bands
+    std::vector<Group> groups;
+    std::vector<int> root_of, gidx, off_in, c0_in;        // per original node: its group's root, its group (roots only), first column, first column of its subtree
+    std::vector<int> vmap, cmap, band_planes;             // (choose_shapes rounds band_planes up to the kernels' buckets)
+    std::vector<MergeMember> members;
+    std::vector<int> member_of;
+    int64_t merged_entries = 0, scratch_entries = 0;
+    double entries_read = 0.0;                            // (install_leaves, as entries_unmerged)
+    bool identity = true;                                 // vmap is the identity
+    // choose_shapes
+    bool leaf_inv = false;
+    int64_t wrows = 8;
+    std::vector<std::vector<int>> by_band;                // group indices per band
+    std::vector<int64_t> band_rows, band_cols;
+    int lanes_row = 1;                                    // lanes that hold one row of modes (half the pitch with two-mode lanes)
+
+    // lane groups of a wavefront in the row kernel: 64 / (lanes per row of modes); 0 = a row of modes is wider than a wavefront
+    int rows_groups() const { return lanes_row <= 64 ? 64 / lanes_row : 0; }
+    int rows_per_wg(int qs) const { return std::max(1, ((256 / lanes_row) >> qs)); }
+    bool inverse_band(int k) const { return top_inv && k == nb - 1; }      // full rows of S^-1
+    int64_t plane_in_parent(const Group &G) const {       // G's plane in its parent's rows of W (G.parent >= 0)
+        const Group &A = groups[(size_t)G.parent];
+        return A.woff + (int64_t)G.colour * (A.n + A.b);
+    }
+};
+
+int bad(const char *what) {
+    set_error(std::string("front_setup: ") + what);
+    return (int)DOTS_ERR_ARGUMENT;
+}
+
+// front_setup fails from here on: whatever it has installed so far goes, the context is left as front_release leaves it
+// (runs AFTER the failing phase has set its error text: front_release must set none)
+struct ReleaseUnlessDone {
+    Ctx *c;
+    bool done = false;
+    ~ReleaseUnlessDone() { if (!done) front_release(c); }
+};
+
+// Temporary device buffers of one phase, freed when it ends (every phase synchronises the stream before it returns)
+struct DevTemps {
+    hipStream_t stream;
+    std::vector<void *> held;
+    explicit DevTemps(hipStream_t s) : stream(s) {}
+    DevTemps(const DevTemps &) = delete;
+    DevTemps &operator=(const DevTemps &) = delete;
+    ~DevTemps() { for (void *p : held) (void)hipFree(p); }
+    // `bytes` of device memory (at least 8), filled from `host` where given
+    hipError_t get(void **out, size_t bytes, const void *host = nullptr) {
+        void *p = nullptr;
+        hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 8));
+        if (e != hipSuccess) return e;
+        held.push_back(p);
+        *out = p;
+        return host ? hipMemcpyAsync(p, host, bytes, hipMemcpyHostToDevice, stream) : hipSuccess;
+    }
+    template <typename T> hipError_t copy(const T **out, const T *host, size_t count) { return get((void **)out, sizeof(T) * count, host); }
+    template <typename T> hipError_t copy(const T **out, const std::vector<T> &v) { return copy(out, v.data(), v.size()); }
+};
+
+// the right-hand side a workgroup of the row kernel (k_front_fwd_rows) stages, `cols` columns, fits its LDS
+bool rows_fit_lds(const Dev &d, int cols) { return (size_t)cols * (size_t)(d.TP + FWD_ROWS_PAD) * sizeof(double) <= FWD_ROWS_LDS_MAX; }
+
+// ---- check_desc: the arguments and every index (a wrong index would fault on the device); no HIP call --------------------------
+int check_desc(const Dev &d, const dots_front_desc *h, FrontPlan &P) {
     if (!h || h->n_nodes < 1 || h->n_levels < 1 || h->n_levels > 64) return bad("bad description");
     if (!h->node_n || !h->node_b || !h->node_foff || !h->node_ioff || !h->node_uoff || !h->node_child || !h->front_idx || !h->pull0 ||
         !h->pull1 || !h->level_ptr || !h->level_nodes || (!h->values && !h->grounded))
         return bad("null array");
     if (h->pitch != d.TP || h->n_modes != d.cg_ncol) return bad("pitch / mode count does not match the context");
-    // ---- index sanity: a wrong index would fault on the device -------------------------------------
-    const int nn = h->n_nodes;
+    const int nn = P.nn = h->n_nodes;
     int64_t fo = 0, io = 0, uo = 0, eliminated = 0;
-    double entries_unmerged = 0.0;
     for (int p = 0; p < nn; ++p) {
         const int64_t n = h->node_n[p], b = h->node_b[p];
         if (n < 0 || b < 0) return bad("node size");      // (n + b = 0: the empty top separator of a mesh of several components)
@@ -1009,31 +1075,32 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
         io += n + b;
         uo += b;
         eliminated += n;
-        entries_unmerged += 0.5 * n * (n + 1) + (double)b * n;
+        P.entries_unmerged += 0.5 * n * (n + 1) + (double)b * n;
     }
     if (fo != h->n_entries || io != h->n_front_rows || uo != h->update_rows || eliminated != d.V) return bad("totals do not match");
     if (h->level_ptr[0] != 0 || h->level_ptr[h->n_levels] != nn) return bad("level_ptr");
-    std::vector<int> level_of(nn, -1), parent(nn, -1);
+    P.level_of.assign((size_t)nn, -1);
+    P.parent.assign((size_t)nn, -1);
     for (int l = 0; l < h->n_levels; ++l) {
         if (h->level_ptr[l + 1] < h->level_ptr[l]) return bad("level_ptr not monotone");
         for (int k = h->level_ptr[l]; k < h->level_ptr[l + 1]; ++k) {
             const int p = h->level_nodes[k];
-            if (p < 0 || p >= nn || level_of[p] != -1) return bad("level_nodes is not a permutation");
-            level_of[p] = l;
+            if (p < 0 || p >= nn || P.level_of[p] != -1) return bad("level_nodes is not a permutation");
+            P.level_of[p] = l;
         }
     }
     for (int p = 0; p < nn; ++p)
         for (int k = 0; k < 2; ++k) {
             const int ch = h->node_child[2 * p + k];
             if (ch < 0) continue;
-            if (level_of[ch] >= level_of[p]) return bad("a child is not on a lower level than its parent");
-            if (parent[ch] != -1) return bad("a node has two parents");
-            parent[ch] = p;
+            if (P.level_of[ch] >= P.level_of[p]) return bad("a child is not on a lower level than its parent");
+            if (P.parent[ch] != -1) return bad("a node has two parents");
+            P.parent[ch] = p;
         }
     for (int p = 0; p < nn; ++p)
-        if (parent[p] == -1 && h->node_b[p] != 0) return bad("a node without parent has boundary rows");
+        if (P.parent[p] == -1 && h->node_b[p] != 0) return bad("a node without parent has boundary rows");
     // ---- bands of tree heights that one launch handles (default: one height each) --------------------
-    std::vector<int> cuts;
+    std::vector<int> &cuts = P.cuts;
     if (h->band_ptr) {
         if (h->n_bands < 1 || h->n_bands > h->n_levels) return bad("n_bands");
         for (int k = 0; k <= h->n_bands; ++k) cuts.push_back(h->band_ptr[k]);
@@ -1043,237 +1110,261 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
     } else {
         for (int l = 0; l <= h->n_levels; ++l) cuts.push_back(l);
     }
+    P.top_inv = h->top_inverse != 0;
+    return 0;
+}
 
-    const bool top_inv = h->top_inverse != 0;      // the top band stores explicit inverses (its nodes have no boundary rows)
-
-    DOTS_HIP(hipStreamSynchronize(c->stream));
-    front_release(c);
-    // ---- the original tree: node records of the factorisation, elimination order --------------------
-    std::vector<FrontNode> nodes((size_t)nn);
-    std::vector<int> vmap0((size_t)d.V), bd_vertex((size_t)std::max<int64_t>(h->update_rows, 1));
-    {
-        std::vector<char> seen((size_t)d.V, 0);
-        int k0 = 0;
-        int64_t soff = 0;
-        for (int p = 0; p < nn; ++p) {
-            FrontNode &nd = nodes[(size_t)p];
-            nd.n = h->node_n[p];
-            nd.b = h->node_b[p];
-            nd.k0 = k0;
-            nd.foff = h->node_foff[p];
-            nd.bdoff = h->node_uoff[p];
-            nd.parent = parent[p];
-            nd.c0 = h->node_child[2 * p];
-            nd.c1 = h->node_child[2 * p + 1];
-            nd.ioff = h->node_ioff[p];
-            nd.soff = soff;
-            soff += (int64_t)nd.b * nd.b;
-            const int64_t io2 = h->node_ioff[p];
-            for (int i = 0; i < nd.n; ++i) {
-                const int v = h->front_idx[io2 + i];
-                if (seen[(size_t)v]) return bad("a vertex is eliminated twice");
-                seen[(size_t)v] = 1;
-                vmap0[(size_t)(k0 + i)] = v;
-            }
-            for (int i = 0; i < nd.b; ++i) bd_vertex[(size_t)(nd.bdoff + i)] = h->front_idx[io2 + nd.n + i];
-            k0 += nd.n;
+// ---- build_tree: the original tree -- node records of the factorisation, elimination order ---------------------------------------
+int build_tree(const Dev &d, const dots_front_desc *h, FrontPlan &P) {
+    const int nn = P.nn;
+    P.nodes.resize((size_t)nn);
+    P.vmap0.resize((size_t)d.V);
+    P.bd_vertex.resize((size_t)std::max<int64_t>(h->update_rows, 1));
+    std::vector<char> seen((size_t)d.V, 0);
+    int k0 = 0;
+    int64_t soff = 0;
+    for (int p = 0; p < nn; ++p) {
+        FrontNode &nd = P.nodes[(size_t)p];
+        nd.n = h->node_n[p];
+        nd.b = h->node_b[p];
+        nd.k0 = k0;
+        nd.foff = h->node_foff[p];
+        nd.bdoff = h->node_uoff[p];
+        nd.parent = P.parent[p];
+        nd.c0 = h->node_child[2 * p];
+        nd.c1 = h->node_child[2 * p + 1];
+        nd.ioff = h->node_ioff[p];
+        nd.soff = soff;
+        soff += (int64_t)nd.b * nd.b;
+        const int64_t io2 = h->node_ioff[p];
+        for (int i = 0; i < nd.n; ++i) {
+            const int v = h->front_idx[io2 + i];
+            if (seen[(size_t)v]) return bad("a vertex is eliminated twice");
+            seen[(size_t)v] = 1;
+            P.vmap0[(size_t)(k0 + i)] = v;
         }
-        for (int p = 0; p < nn; ++p)       // every boundary row of a child must be pulled exactly once by its parent
-            for (int k = 0; k < 2; ++k) {
-                const int ch = h->node_child[2 * p + k];
-                if (ch < 0) continue;
-                const int32_t *pull = k == 0 ? h->pull0 : h->pull1;
-                std::vector<char> got((size_t)h->node_b[ch], 0);
-                for (int fpos = 0; fpos < h->node_n[p] + h->node_b[p]; ++fpos) {
-                    const int r = pull[h->node_ioff[p] + fpos];
-                    if (r < 0) continue;
-                    if (got[(size_t)r]) return bad("a child boundary row is pulled twice");
-                    got[(size_t)r] = 1;
-                }
-                for (int r = 0; r < h->node_b[ch]; ++r)
-                    if (!got[(size_t)r]) return bad("a child boundary row is not pulled by its parent");
-            }
+        for (int i = 0; i < nd.b; ++i) P.bd_vertex[(size_t)(nd.bdoff + i)] = h->front_idx[io2 + nd.n + i];
+        k0 += nd.n;
     }
+    for (int p = 0; p < nn; ++p)       // every boundary row of a child must be pulled exactly once by its parent
+        for (int k = 0; k < 2; ++k) {
+            const int ch = h->node_child[2 * p + k];
+            if (ch < 0) continue;
+            const int32_t *pull = k == 0 ? h->pull0 : h->pull1;
+            std::vector<char> got((size_t)h->node_b[ch], 0);
+            for (int fpos = 0; fpos < h->node_n[p] + h->node_b[p]; ++fpos) {
+                const int r = pull[h->node_ioff[p] + fpos];
+                if (r < 0) continue;
+                if (got[(size_t)r]) return bad("a child boundary row is pulled twice");
+                got[(size_t)r] = 1;
+            }
+            for (int r = 0; r < h->node_b[ch]; ++r)
+                if (!got[(size_t)r]) return bad("a child boundary row is not pulled by its parent");
+        }
+    for (int k = 0; k < d.V && P.identity0; ++k) P.identity0 = P.vmap0[(size_t)k] == k;
+    return 0;
+}
 
-    // ---- the nodes of the sweeps: the members of a band that hang together ----------------------------
-    std::vector<Group> groups;
-    std::vector<int> band_of_level, root_of((size_t)nn), gidx((size_t)nn, -1), off_in((size_t)nn, 0), c0_in((size_t)nn, 0);
-    std::vector<int> vmap, cmap, band_planes;
-    std::vector<MergeMember> members;
-    std::vector<int> member_of((size_t)nn, -1);
-    int64_t merged_entries = 0, scratch_entries = 0;
-    double entries_read = 0.0;
-    for (int attempt = 0;; ++attempt) {
-        const int nb = (int)cuts.size() - 1;
-        band_of_level.assign((size_t)h->n_levels, 0);
-        for (int k = 0; k < nb; ++k)
-            for (int l = cuts[k]; l < cuts[k + 1]; ++l) band_of_level[(size_t)l] = k;
-        auto band = [&](int p) { return band_of_level[(size_t)level_of[p]]; };
-        for (int p = nn - 1; p >= 0; --p) root_of[(size_t)p] = (parent[p] >= 0 && band(parent[p]) == band(p)) ? root_of[(size_t)parent[p]] : p;
-        groups.clear();
-        std::fill(gidx.begin(), gidx.end(), -1);
-        for (int p = 0; p < nn; ++p)
-            if (root_of[(size_t)p] == p) {
-                gidx[(size_t)p] = (int)groups.size();
-                Group G;
-                G.root = p;
-                G.band = band(p);
-                G.b = h->node_b[p];
-                groups.push_back(G);
+// ---- group_bands: the nodes of the sweeps -- the members of a band that hang together ------------------------------------------
+// the groups of the current cuts, their member records for the merge kernel, and the entries a sweep reads
+void form_groups(const dots_front_desc *h, FrontPlan &P) {
+    const int nn = P.nn, nb = P.nb = (int)P.cuts.size() - 1;
+    std::vector<int> band_of_level((size_t)h->n_levels, 0);
+    for (int k = 0; k < nb; ++k)
+        for (int l = P.cuts[k]; l < P.cuts[k + 1]; ++l) band_of_level[(size_t)l] = k;
+    auto band = [&](int p) { return band_of_level[(size_t)P.level_of[p]]; };
+    std::vector<Group> &groups = P.groups;
+    std::vector<int> &root_of = P.root_of, &off_in = P.off_in, &c0_in = P.c0_in;
+    root_of.resize((size_t)nn);
+    off_in.assign((size_t)nn, 0);
+    c0_in.assign((size_t)nn, 0);
+    for (int p = nn - 1; p >= 0; --p) root_of[(size_t)p] = (P.parent[p] >= 0 && band(P.parent[p]) == band(p)) ? root_of[(size_t)P.parent[p]] : p;
+    groups.clear();
+    P.gidx.assign((size_t)nn, -1);
+    for (int p = 0; p < nn; ++p)
+        if (root_of[(size_t)p] == p) {
+            P.gidx[(size_t)p] = (int)groups.size();
+            Group G;
+            G.root = p;
+            G.band = band(p);
+            G.b = h->node_b[p];
+            groups.push_back(G);
+        }
+    for (int p = 0; p < nn; ++p) groups[(size_t)P.gidx[(size_t)root_of[(size_t)p]]].members.push_back(p);
+    P.merged_entries = P.scratch_entries = 0;
+    P.entries_read = 0.0;
+    int k0 = 0;
+    P.members.clear();
+    P.member_of.assign((size_t)nn, -1);
+    for (Group &G : groups) {
+        for (int s : G.members) {
+            off_in[(size_t)s] = G.n;
+            int c0 = G.n;
+            for (int k = 0; k < 2; ++k) {
+                const int ch = h->node_child[2 * s + k];
+                if (ch >= 0 && root_of[(size_t)ch] == G.root) c0 = std::min(c0, c0_in[(size_t)ch]);
             }
-        for (int p = 0; p < nn; ++p) groups[(size_t)gidx[(size_t)root_of[(size_t)p]]].members.push_back(p);
-        merged_entries = scratch_entries = 0;
-        entries_read = 0.0;
-        int k0 = 0;
-        members.clear();
-        std::fill(member_of.begin(), member_of.end(), -1);
-        for (Group &G : groups) {
-            for (int s : G.members) {
-                off_in[(size_t)s] = G.n;
-                int c0 = G.n;
-                for (int k = 0; k < 2; ++k) {
-                    const int ch = h->node_child[2 * s + k];
-                    if (ch >= 0 && root_of[(size_t)ch] == G.root) c0 = std::min(c0, c0_in[(size_t)ch]);
-                }
-                c0_in[(size_t)s] = c0;
-                const double ns = h->node_n[s];
-                entries_read += 0.5 * ns * (ns + 1) + ns * (double)(G.n - c0);
-                G.n += h->node_n[s];
+            c0_in[(size_t)s] = c0;
+            const double ns = h->node_n[s];
+            P.entries_read += 0.5 * ns * (ns + 1) + ns * (double)(G.n - c0);
+            G.n += h->node_n[s];
+        }
+        P.entries_read += (double)G.b * G.n;
+        if (P.inverse_band(G.band)) {     // S^-1: n x n entries read ONCE per solve = n * n / 2 per sweep in this count
+            double tri = 0.0;
+            for (int s : G.members) tri += 0.5 * h->node_n[s] * (h->node_n[s] + 1.0) + (double)h->node_n[s] * (off_in[(size_t)s] - c0_in[(size_t)s]);
+            P.entries_read += 0.5 * (double)G.n * G.n - tri;
+        }
+        G.k0 = k0;
+        k0 += G.n;
+        if (G.members.size() == 1) {
+            G.foff = h->node_foff[G.root];
+            continue;
+        }
+        G.foff = h->n_entries + P.merged_entries;
+        P.merged_entries += (int64_t)(G.n + G.b) * G.n;
+        for (int s : G.members) {          // member records of the merge kernel
+            MergeMember mm{};
+            mm.n = h->node_n[s];
+            mm.b = h->node_b[s];
+            mm.o = off_in[(size_t)s];
+            mm.c0 = c0_in[(size_t)s];
+            mm.foff = h->node_foff[s];
+            mm.ioff = h->node_ioff[s];
+            mm.dst = G.foff;
+            mm.ns = G.n;
+            mm.ch[0] = mm.ch[1] = -1;
+            bool inner = false;
+            for (int k = 0; k < 2; ++k) {
+                const int ch = h->node_child[2 * s + k];
+                if (ch >= 0 && root_of[(size_t)ch] == G.root) { mm.ch[k] = P.member_of[(size_t)ch]; inner = true; }
             }
-            entries_read += (double)G.b * G.n;
-            if (top_inv && G.band == nb - 1) {     // S^-1: n x n entries read ONCE per solve = n * n / 2 per sweep in this count
-                double tri = 0.0;
-                for (int s : G.members) tri += 0.5 * h->node_n[s] * (h->node_n[s] + 1.0) + (double)h->node_n[s] * (off_in[(size_t)s] - c0_in[(size_t)s]);
-                entries_read += 0.5 * (double)G.n * G.n - tri;
-            }
-            G.k0 = k0;
-            k0 += G.n;
-            if (G.members.size() == 1) {
-                G.foff = h->node_foff[G.root];
+            if (s == G.root) {
+                mm.uin = 2;
+                mm.uoff = G.foff + (int64_t)G.n * G.n;
+                mm.ustride = G.n;
+            } else if (!inner) {
+                mm.uin = 0;
+                mm.uoff = mm.foff + (int64_t)mm.n * mm.n;
+                mm.ustride = mm.n;
             } else {
-                G.foff = h->n_entries + merged_entries;
-                merged_entries += (int64_t)(G.n + G.b) * G.n;
-                for (int s : G.members) {          // member records of the merge kernel
-                    MergeMember mm{};
-                    mm.n = h->node_n[s];
-                    mm.b = h->node_b[s];
-                    mm.o = off_in[(size_t)s];
-                    mm.c0 = c0_in[(size_t)s];
-                    mm.foff = h->node_foff[s];
-                    mm.ioff = h->node_ioff[s];
-                    mm.dst = G.foff;
-                    mm.ns = G.n;
-                    mm.ch[0] = mm.ch[1] = -1;
-                    bool inner = false;
-                    for (int k = 0; k < 2; ++k) {
-                        const int ch = h->node_child[2 * s + k];
-                        if (ch >= 0 && root_of[(size_t)ch] == G.root) { mm.ch[k] = member_of[(size_t)ch]; inner = true; }
-                    }
-                    if (s == G.root) {
-                        mm.uin = 2;
-                        mm.uoff = G.foff + (int64_t)G.n * G.n;
-                        mm.ustride = G.n;
-                    } else if (!inner) {
-                        mm.uin = 0;
-                        mm.uoff = mm.foff + (int64_t)mm.n * mm.n;
-                        mm.ustride = mm.n;
-                    } else {
-                        mm.uin = 1;
-                        mm.uoff = scratch_entries;
-                        mm.ustride = mm.o + mm.n - mm.c0;
-                        scratch_entries += (int64_t)mm.b * mm.ustride;
-                    }
-                    member_of[(size_t)s] = (int)members.size();
-                    members.push_back(mm);
-                }
+                mm.uin = 1;
+                mm.uoff = P.scratch_entries;
+                mm.ustride = mm.o + mm.n - mm.c0;
+                P.scratch_entries += (int64_t)mm.b * mm.ustride;
             }
+            P.member_of[(size_t)s] = (int)P.members.size();
+            P.members.push_back(mm);
         }
-        // sweep order, positions of the update rows in the parents' fronts, planes
-        vmap.assign((size_t)d.V, 0);
-        cmap.assign((size_t)std::max<int64_t>(h->update_rows, 1), 0);
-        std::vector<int> rowpos((size_t)d.V, -1);
-        band_planes.assign((size_t)nb, 0);
-        int over = -1;
-        for (size_t gi = 0; gi < groups.size(); ++gi) {
-            Group &G = groups[gi];
-            for (int s : G.members)
-                for (int i = 0; i < h->node_n[s]; ++i) {
-                    const int v = h->front_idx[h->node_ioff[s] + i];
-                    vmap[(size_t)(G.k0 + off_in[(size_t)s] + i)] = v;
-                    rowpos[(size_t)v] = off_in[(size_t)s] + i;
-                }
-            const int64_t iop = h->node_ioff[G.root] + h->node_n[G.root];
-            for (int i = 0; i < G.b; ++i) rowpos[(size_t)h->front_idx[iop + i]] = G.n + i;
-            // nodes below the band that hang from this one: where their update rows land, and a plane for each such
-            // that no two writers of a plane share a row -- the fewest planes (the forward kernel reads every plane of
-            // every column): exact colouring of the conflict graph (at most 16 nodes)
-            std::vector<int> ext;                          // the children's group indices
-            for (int s : G.members)
-                for (int k = 0; k < 2; ++k) {
-                    const int ch = h->node_child[2 * s + k];
-                    if (ch < 0 || root_of[(size_t)ch] == G.root) continue;
-                    const int32_t *pull = k == 0 ? h->pull0 : h->pull1;
-                    const int64_t ios = h->node_ioff[s], uoc = h->node_uoff[ch];
-                    for (int fpos = 0; fpos < h->node_n[s] + h->node_b[s]; ++fpos) {
-                        const int r = pull[ios + fpos];
-                        if (r >= 0) cmap[(size_t)(uoc + r)] = rowpos[(size_t)h->front_idx[ios + fpos]];
-                    }
-                    groups[(size_t)gidx[(size_t)ch]].parent = (int)gi;
-                    ext.push_back(gidx[(size_t)ch]);
-                }
-            const int ne = (int)ext.size();
-            std::vector<uint32_t> clash((size_t)ne, 0);    // bit j: child i and child j write a common row
-            {
-                std::vector<uint32_t> who((size_t)(G.n + G.b), 0);
-                for (int i = 0; i < ne && i < 32; ++i) {
-                    const int ch = groups[(size_t)ext[(size_t)i]].root;
-                    for (int r = 0; r < h->node_b[ch]; ++r) who[(size_t)cmap[(size_t)(h->node_uoff[ch] + r)]] |= 1u << i;
-                }
-                for (uint32_t m2 : who)
-                    for (int i = 0; i < ne && i < 32; ++i)
-                        if (m2 >> i & 1u) clash[(size_t)i] |= m2 & ~(1u << i);
+    }
+}
+
+// backtracking step: the nodes order[at ..] into `planes` colours, within `budget` steps (beyond: the caller takes the next larger count)
+bool place_colours(const std::vector<uint32_t> &clash, const std::vector<int> &order, int planes, int at, std::vector<int> &colour, int64_t &budget) {
+    const int ne = (int)order.size();
+    if (at == ne) return true;
+    if (--budget < 0) return false;
+    const int v = order[(size_t)at];
+    for (int col = 0; col < planes && col <= at; ++col) {     // col <= at: planes are interchangeable
+        bool free = true;
+        for (int j = 0; j < ne && free; ++j)
+            free = !((clash[(size_t)v] >> j & 1u) && colour[(size_t)j] == col);
+        if (!free) continue;
+        colour[(size_t)v] = col;
+        if (place_colours(clash, order, planes, at + 1, colour, budget)) return true;
+        colour[(size_t)v] = -1;
+    }
+    return false;
+}
+// The fewest planes such that no two writers of a plane share a row (the forward kernel reads every plane of every column): exact
+// colouring of the conflict graph of `ne` nodes (at most 16; bit j of clash[i]: i and j write a common row).  Returns the number of
+// planes, colour[i] = node i's.
+int colour_planes(const std::vector<uint32_t> &clash, int ne, std::vector<int> &colour) {
+    colour.assign((size_t)ne, -1);
+    if (ne == 0) return 0;
+    if (ne > 20) {                                 // (not reachable with bands of at most 4 heights) one plane each
+        for (int i = 0; i < ne; ++i) colour[(size_t)i] = i;
+        return ne;
+    }
+    std::vector<int> order((size_t)ne);
+    for (int i = 0; i < ne; ++i) order[(size_t)i] = i;
+    std::sort(order.begin(), order.end(), [&](int x, int y) {
+        const int dx = __builtin_popcount(clash[(size_t)x]), dy = __builtin_popcount(clash[(size_t)y]);
+        return dx != dy ? dx > dy : x < y;
+    });
+    int planes = 1;
+    for (; planes <= ne; ++planes) {
+        std::fill(colour.begin(), colour.end(), -1);
+        int64_t budget = 200000;
+        if (place_colours(clash, order, planes, 0, colour, budget)) break;
+    }
+    return planes;
+}
+
+// sweep order, positions of the update rows in the parents' fronts, planes; returns a band with a node of more than 8 planes, or -1
+int place_updates(const Dev &d, const dots_front_desc *h, FrontPlan &P) {
+    std::vector<Group> &groups = P.groups;
+    const std::vector<int> &root_of = P.root_of, &off_in = P.off_in;
+    std::vector<int> &cmap = P.cmap;
+    P.vmap.assign((size_t)d.V, 0);
+    cmap.assign((size_t)std::max<int64_t>(h->update_rows, 1), 0);
+    std::vector<int> rowpos((size_t)d.V, -1);
+    P.band_planes.assign((size_t)P.nb, 0);
+    int over = -1;
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+        Group &G = groups[gi];
+        for (int s : G.members)
+            for (int i = 0; i < h->node_n[s]; ++i) {
+                const int v = h->front_idx[h->node_ioff[s] + i];
+                P.vmap[(size_t)(G.k0 + off_in[(size_t)s] + i)] = v;
+                rowpos[(size_t)v] = off_in[(size_t)s] + i;
             }
-            std::vector<int> colour((size_t)ne, -1);
-            int planes = 0;
-            if (ne > 0 && ne <= 20) {
-                std::vector<int> order((size_t)ne);
-                for (int i = 0; i < ne; ++i) order[(size_t)i] = i;
-                std::sort(order.begin(), order.end(), [&](int x, int y) {
-                    const int dx = __builtin_popcount(clash[(size_t)x]), dy = __builtin_popcount(clash[(size_t)y]);
-                    return dx != dy ? dx > dy : x < y;
-                });
-                for (planes = 1; planes <= ne; ++planes) {
-                    std::fill(colour.begin(), colour.end(), -1);
-                    int64_t budget = 200000;      // backtracking steps; beyond: take the next larger count
-                    std::function<bool(int)> place = [&](int at) -> bool {
-                        if (at == ne) return true;
-                        if (--budget < 0) return false;
-                        const int v = order[(size_t)at];
-                        for (int col = 0; col < planes && col <= at; ++col) {     // col <= at: planes are interchangeable
-                            bool free = true;
-                            for (int j = 0; j < ne && free; ++j)
-                                free = !((clash[(size_t)v] >> j & 1u) && colour[(size_t)j] == col);
-                            if (!free) continue;
-                            colour[(size_t)v] = col;
-                            if (place(at + 1)) return true;
-                            colour[(size_t)v] = -1;
-                        }
-                        return false;
-                    };
-                    if (place(0)) break;
+        const int64_t iop = h->node_ioff[G.root] + h->node_n[G.root];
+        for (int i = 0; i < G.b; ++i) rowpos[(size_t)h->front_idx[iop + i]] = G.n + i;
+        // nodes below the band that hang from this one: where their update rows land, and a plane for each (colour_planes)
+        std::vector<int> ext;                          // the children's group indices
+        for (int s : G.members)
+            for (int k = 0; k < 2; ++k) {
+                const int ch = h->node_child[2 * s + k];
+                if (ch < 0 || root_of[(size_t)ch] == G.root) continue;
+                const int32_t *pull = k == 0 ? h->pull0 : h->pull1;
+                const int64_t ios = h->node_ioff[s], uoc = h->node_uoff[ch];
+                for (int fpos = 0; fpos < h->node_n[s] + h->node_b[s]; ++fpos) {
+                    const int r = pull[ios + fpos];
+                    if (r >= 0) cmap[(size_t)(uoc + r)] = rowpos[(size_t)h->front_idx[ios + fpos]];
                 }
-            } else {                                       // (not reachable with bands of at most 4 heights) one plane each
-                for (int i = 0; i < ne; ++i) colour[(size_t)i] = i;
-                planes = ne;
+                groups[(size_t)P.gidx[(size_t)ch]].parent = (int)gi;
+                ext.push_back(P.gidx[(size_t)ch]);
             }
-            for (int i = 0; i < ne; ++i) groups[(size_t)ext[(size_t)i]].colour = colour[(size_t)i];
-            G.planes = planes;
-            band_planes[(size_t)G.band] = std::max(band_planes[(size_t)G.band], G.planes);
-            if (G.planes > 8 && over < 0) over = G.band;
-            for (int s : G.members)
-                for (int i = 0; i < h->node_n[s]; ++i) rowpos[(size_t)h->front_idx[h->node_ioff[s] + i]] = -1;
-            for (int i = 0; i < G.b; ++i) rowpos[(size_t)h->front_idx[iop + i]] = -1;
+        const int ne = (int)ext.size();
+        std::vector<uint32_t> clash((size_t)ne, 0);    // bit j: child i and child j write a common row
+        {
+            std::vector<uint32_t> who((size_t)(G.n + G.b), 0);
+            for (int i = 0; i < ne && i < 32; ++i) {
+                const int ch = groups[(size_t)ext[(size_t)i]].root;
+                for (int r = 0; r < h->node_b[ch]; ++r) who[(size_t)cmap[(size_t)(h->node_uoff[ch] + r)]] |= 1u << i;
+            }
+            for (uint32_t m2 : who)
+                for (int i = 0; i < ne && i < 32; ++i)
+                    if (m2 >> i & 1u) clash[(size_t)i] |= m2 & ~(1u << i);
         }
+        std::vector<int> colour;
+        G.planes = colour_planes(clash, ne, colour);
+        for (int i = 0; i < ne; ++i) groups[(size_t)ext[(size_t)i]].colour = colour[(size_t)i];
+        P.band_planes[(size_t)G.band] = std::max(P.band_planes[(size_t)G.band], G.planes);
+        if (G.planes > 8 && over < 0) over = G.band;
+        for (int s : G.members)
+            for (int i = 0; i < h->node_n[s]; ++i) rowpos[(size_t)h->front_idx[h->node_ioff[s] + i]] = -1;
+        for (int i = 0; i < G.b; ++i) rowpos[(size_t)h->front_idx[iop + i]] = -1;
+    }
+    return over;
+}
+
+int group_bands(const Dev &d, const dots_front_desc *h, FrontPlan &P) {
+    std::vector<int> &cuts = P.cuts;
+    for (int attempt = 0;; ++attempt) {
+        form_groups(h, P);
+        const int over = place_updates(d, h, P);
         if (over < 0) break;
         // more than 8 planes on a merged node (cannot happen with one height per band: two children): split that band
         if (attempt > 64 || cuts[(size_t)over + 1] - cuts[(size_t)over] < 2) return bad("update planes");
@@ -1285,158 +1376,64 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
         }
         cuts.swap(split);
     }
-    const int nb = (int)cuts.size() - 1;
-    if (nb > FrontSchedule::MAX_BANDS) return bad("more bands than a schedule holds");      // (cannot happen: a band holds a height, n_levels <= 64)
+    if (P.nb > FrontSchedule::MAX_BANDS) return bad("more bands than a schedule holds");      // (cannot happen: a band holds a height, n_levels <= 64)
+    for (int k = 0; k < d.V && P.identity; ++k) P.identity = P.vmap[(size_t)k] == k;
+    return 0;
+}
+
+// ---- choose_shapes: the leaf-inverse precondition, the planes' buckets and W, threads and rows per workgroup of each band ------
+void choose_shapes(Ctx *c, const dots_front_desc *h, FrontPlan &P) {
+    const Dev &d = c->dcg;
+    const int nb = P.nb;
+    const std::vector<Group> &groups = P.groups;
     FrontBand *const band = c->sched.band;
-    bool identity = true;
-    for (int k = 0; k < d.V && identity; ++k) identity = vmap[(size_t)k] == k;
-    bool identity0 = true;
-    for (int k = 0; k < d.V && identity0; ++k) identity0 = vmap0[(size_t)k] == k;
     // The leaves as explicit local inverses (k_front_leaf_fwd / _bwd): an un-merged band of leaves below at least one other band; every leaf's
     // vertices numbered as the sweeps walk them (device vertex = sweep-order index: the plan's own numbering, or any that keeps the leaves in place);
     // a row of modes within a workgroup.  DOTS_FRONT_CFG / DOTS_FRONT_TUNE choose among the BAND kernels, also for band 0: the leaves then stay with them.
     // Above a pitch of 256 the band kernels keep the leaves (the leaf kernels take no chunks of modes; their LDS rule below would
     // refuse all but leaves of a few vertices anyway).
-    bool leaf_inv = c->front_leafinv && !getenv("DOTS_FRONT_CFG") && !c->front_tune && nb >= 2 && cuts[1] == 1 && d.rowptr && d.col && d.val &&
-                    d.TP <= 256;
-    for (size_t gi = 0; gi < groups.size() && leaf_inv; ++gi) {
+    P.leaf_inv = c->front_leafinv && !getenv("DOTS_FRONT_CFG") && !c->front_tune && nb >= 2 && P.cuts[1] == 1 && d.rowptr && d.col && d.val && d.TP <= 256;
+    for (size_t gi = 0; gi < groups.size() && P.leaf_inv; ++gi) {
         const Group &G = groups[gi];
         if (G.band != 0) continue;
-        if (G.n == 0 && G.b > 0) leaf_inv = false;      // (cannot happen: a leaf's boundary comes from its own vertices)
-        for (int j = 0; j < G.n && leaf_inv; ++j) leaf_inv = vmap[(size_t)(G.k0 + j)] == G.k0 + j;
+        if (G.n == 0 && G.b > 0) P.leaf_inv = false;      // (cannot happen: a leaf's boundary comes from its own vertices)
+        for (int j = 0; j < G.n && P.leaf_inv; ++j) P.leaf_inv = P.vmap[(size_t)(G.k0 + j)] == G.k0 + j;
     }
     // planes: the band's bucket (0, 2, 4, 8) of m rows each per node; W starts with a few zero rows (woff = 0 is never read)
-    int64_t wrows = 8;
+    P.wrows = 8;
     for (int k = 0; k < nb; ++k) {
-        int &bp = band_planes[(size_t)k];
+        int &bp = P.band_planes[(size_t)k];
         bp = bp == 0 ? 0 : (bp <= 2 ? 2 : (bp <= 4 ? 4 : 8));
         band[k].planes = bp;
     }
-    for (Group &G : groups) {
-        G.woff = wrows;
-        wrows += (int64_t)band_planes[(size_t)G.band] * (G.n + G.b);
+    for (Group &G : P.groups) {
+        G.woff = P.wrows;
+        P.wrows += (int64_t)P.band_planes[(size_t)G.band] * (G.n + G.b);
     }
-
-    // ---- workgroup lists per band: (node, first row) for the forward sweep, (node, first column, row ranges)
-    // backward
-    std::vector<std::vector<int>> by_band((size_t)nb);
-    for (size_t gi = 0; gi < groups.size(); ++gi) by_band[(size_t)groups[gi].band].push_back((int)gi);
-    auto sweep_node = [&](const Group &G) {
-        SweepNode sn{};
-        sn.n = G.n;
-        sn.b = G.b;
-        sn.k0 = G.k0;
-        sn.planes = G.planes;
-        sn.foff = G.foff;
-        sn.woff = G.woff;
-        sn.parent_w = G.parent < 0 ? -1 : groups[(size_t)G.parent].woff + (int64_t)G.colour * (groups[(size_t)G.parent].n + groups[(size_t)G.parent].b);
-        sn.bdoff = h->node_uoff[G.root];
-        return sn;
-    };
-    auto make_fwd = [&](int k, int rb, std::vector<FrontWork> &out) {
-        for (int gi : by_band[(size_t)k]) {
-            const Group &G = groups[(size_t)gi];
-            const SweepNode sn = sweep_node(G);
-            std::vector<int> first_col((size_t)G.n, 0);     // first column of its member's subtree, per separator row
-            for (int s : G.members)
-                for (int i = 0; i < h->node_n[s]; ++i) first_col[(size_t)(off_in[(size_t)s] + i)] = c0_in[(size_t)s];
-            for (int r = 0; r < G.n + G.b; r += rb) {
-                FrontWork w{};
-                w.nd = sn;
-                w.first = r;
-                int lo = r < G.n ? first_col[(size_t)r] : 0;
-                for (int i = r; i < std::min(r + rb, G.n + G.b); ++i) lo = std::min(lo, i < G.n ? first_col[(size_t)i] : 0);
-                w.lo = lo;
-                if (top_inv && k == nb - 1) { w.lo = 0; w.end = G.n; }     // full rows of S^-1
-                out.push_back(w);
-            }
-        }
-    };
-    // row kernel (k_front_fwd_rows): blocks of up to rows_wg rows that never span two members of a merged node (so that wk.lo is
-    // the first column of every row of the block) nor the separator / boundary rows; returns the longest column range a block stages
-    auto make_fwd_rows = [&](int k, int rows_wg, std::vector<FrontWork> &out) {
-        int lds_cols = 1;
-        for (int gi : by_band[(size_t)k]) {
-            const Group &G = groups[(size_t)gi];
-            const SweepNode sn = sweep_node(G);
-            const bool full = top_inv && k == nb - 1;
-            std::vector<std::array<int, 3>> segs;      // (first row, one past the last, first column)
-            if (full) segs.push_back({0, G.n, 0});
-            else {
-                for (int s : G.members)
-                    if (h->node_n[s] > 0) segs.push_back({off_in[(size_t)s], off_in[(size_t)s] + h->node_n[s], c0_in[(size_t)s]});
-                if (G.b > 0) segs.push_back({G.n, G.n + G.b, 0});
-            }
-            for (const auto &sg : segs)
-                for (int r = sg[0]; r < sg[1]; r += rows_wg) {
-                    FrontWork w{};
-                    w.nd = sn;
-                    w.first = r;
-                    w.pad = std::min(rows_wg, sg[1] - r);
-                    w.lo = sg[2];
-                    const int last = r + w.pad - 1;
-                    int jmax = last < G.n ? last + 1 : G.n;
-                    if (full) { w.end = G.n; jmax = G.n; }
-                    lds_cols = std::max(lds_cols, jmax - w.lo);
-                    out.push_back(w);
-                }
-        }
-        return lds_cols;
-    };
-    auto make_bwd = [&](int k, int cb, std::vector<FrontWork> &out) {
-        for (int gi : by_band[(size_t)k]) {
-            const Group &G = groups[(size_t)gi];
-            const SweepNode sn = sweep_node(G);
-            for (int s : G.members) {
-                const int o = off_in[(size_t)s], e = o + h->node_n[s];
-                for (int col = o; col < e; col += cb) {
-                    FrontWork w{};
-                    w.nd = sn;
-                    w.first = col;
-                    w.end = e;
-                    int nr = 0;
-                    w.rs[nr] = col;
-                    w.re[nr] = e;
-                    ++nr;
-                    for (int a2 = parent[s]; a2 >= 0 && root_of[(size_t)a2] == G.root; a2 = parent[a2]) {
-                        const int ao = off_in[(size_t)a2], ae = ao + h->node_n[a2];
-                        if (ae == ao) continue;
-                        if (w.re[nr - 1] == ao) w.re[nr - 1] = ae;          // adjacent: one range
-                        else if (nr < 4) {
-                            w.rs[nr] = ao;
-                            w.re[nr] = ae;
-                            ++nr;
-                        }
-                    }
-                    w.lo = nr;
-                    out.push_back(w);
-                }
-            }
-        }
-    };
+    P.by_band.assign((size_t)nb, {});
+    for (size_t gi = 0; gi < groups.size(); ++gi) P.by_band[(size_t)groups[gi].band].push_back((int)gi);
     // Threads and rows (columns) per workgroup of each band (measured per band with DOTS_FRONT_TUNE, profiles/studies/
     // band_cuts.txt).  Many rows: 256-thread workgroups of up to 4 rows; few rows (the large nodes near the root): 1024-thread
     // workgroups, so that the long dot products are split 4x finer.  Forward bands whose nodes read 4 or 8 update planes take
     // 4 rows per workgroup earlier (the planes are read once per workgroup, not per row).
-    std::vector<int64_t> band_rows((size_t)nb, 0), band_cols((size_t)nb, 0);
+    P.band_rows.assign((size_t)nb, 0);
+    P.band_cols.assign((size_t)nb, 0);
     const bool two_modes = front_two_modes(c);
-    // lane groups of a wavefront in the row kernel: 64 / (lanes per row of modes); 0 = a row of modes is wider than a wavefront
-    const int lanes_row = two_modes ? d.TP / 2 : d.TP;
-    const int rows_groups = lanes_row <= 64 ? 64 / lanes_row : 0;
-    auto rows_per_wg = [&](int qs) { return std::max(1, ((256 / lanes_row) >> qs)); };
+    P.lanes_row = two_modes ? d.TP / 2 : d.TP;
+    const int groups_row = P.rows_groups();
     for (int k = 0; k < nb; ++k) {
-        for (int gi : by_band[(size_t)k]) {
-            band_rows[(size_t)k] += groups[(size_t)gi].n + groups[(size_t)gi].b;
-            band_cols[(size_t)k] += groups[(size_t)gi].n;
+        for (int gi : P.by_band[(size_t)k]) {
+            P.band_rows[(size_t)k] += groups[(size_t)gi].n + groups[(size_t)gi].b;
+            P.band_cols[(size_t)k] += groups[(size_t)gi].n;
         }
-        const int64_t rows = band_rows[(size_t)k], cols = band_cols[(size_t)k];
+        const int64_t rows = P.band_rows[(size_t)k], cols = P.band_cols[(size_t)k];
         // (a workgroup row holds at most 256 modes, the rest of a wider pitch in chunks of their own: 1024-thread workgroups
         // fit at every pitch, and above 256 each chunk takes the shapes of a pitch of 256)
         int fnb, frb, bnb, bcb;
-        if (top_inv && k == nb - 1) {      // full rows of S^-1: every workgroup reads the whole right-hand side and all planes
+        if (P.inverse_band(k)) {      // full rows of S^-1: every workgroup reads the whole right-hand side and all planes
             fnb = 1024;
             frb = rows >= 480 ? 4 : (rows >= 64 ? 2 : 1);
-        } else if (band_planes[(size_t)k] >= 4) {
+        } else if (P.band_planes[(size_t)k] >= 4) {
             if (rows >= 600) { fnb = 256; frb = 4; }
             else { fnb = 1024; frb = rows >= 300 ? 2 : 1; }
         } else {      // (thresholds from the tables of profiles/studies/shape_tuner.txt)
@@ -1455,453 +1452,582 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
         // (rules from the DOTS_FRONT_TUNE tables of profiles/studies/shape_tuner.txt, round 3)
         band[k].fwd_qw = -1;
         band[k].fwd_lds = 0;
-        if (c->front_rows && rows_groups >= 1) {
+        if (c->front_rows && groups_row >= 1) {
             double len = 0.0;      // columns a row of the band reads, summed
             int longest = 1;
-            for (int gi : by_band[(size_t)k]) {
+            for (int gi : P.by_band[(size_t)k]) {
                 const Group &G = groups[(size_t)gi];
-                if (top_inv && k == nb - 1) { len += (double)G.n * G.n; longest = std::max(longest, G.n); continue; }
+                if (P.inverse_band(k)) { len += (double)G.n * G.n; longest = std::max(longest, G.n); continue; }
                 for (int s : G.members) {
-                    const double ns = h->node_n[s], w0 = off_in[(size_t)s] - c0_in[(size_t)s];
+                    const double ns = h->node_n[s], w0 = P.off_in[(size_t)s] - P.c0_in[(size_t)s];
                     len += ns * w0 + 0.5 * ns * (ns + 1);
-                    longest = std::max(longest, off_in[(size_t)s] + h->node_n[s] - c0_in[(size_t)s]);
+                    longest = std::max(longest, P.off_in[(size_t)s] + h->node_n[s] - P.c0_in[(size_t)s]);
                 }
                 len += (double)G.b * G.n;
                 if (G.b > 0) longest = std::max(longest, G.n);
             }
             const double mean = rows > 0 ? len / (double)rows : 0.0;
-            const bool fits = (size_t)longest * (size_t)(d.TP + FWD_ROWS_PAD) * sizeof(double) <= FWD_ROWS_LDS_MAX;
             // (round-3 tables: with rows of <= ~30 columns one lane group per row wins by 10-60 %; on merged bands of 4+ planes the
             // sixteen rows of a workgroup share ONE staged right-hand side: four groups per row draw level or win; elsewhere
             // the fold kernels keep the longer rows)
             int qs = mean <= FWD_ROWS_MEAN_MAX ? 0 : 2;
-            while ((1 << qs) > rows_groups) --qs;
-            if (fits && (c->front_rows >= 2 || mean <= FWD_ROWS_MEAN_MAX || (band_planes[(size_t)k] >= 4 && rows_groups >= 4))) band[k].fwd_qw = qs;
+            while ((1 << qs) > groups_row) --qs;
+            if (rows_fit_lds(d, longest) && (c->front_rows >= 2 || mean <= FWD_ROWS_MEAN_MAX || (P.band_planes[(size_t)k] >= 4 && groups_row >= 4))) band[k].fwd_qw = qs;
         }
     }
+}
 
-    // ---- device: the original tree, the factor, the merged blocks ----------------------------------------
-    FrontDev f0{};      // the original tree as the factorisation sees it
-    f0.n_nodes = nn;
-    f0.n_levels = h->n_levels;
-    int rc;
-#define FUP(dev, field, src, n) if ((rc = front_upload(c, &dev.field, src, (int64_t)(n)))) { front_release(c); return rc; }
-    FUP(f0, nodes, nodes.data(), nn);
-    if (!identity0) FUP(f0, vmap, vmap0.data(), d.V);
-    FUP(f0, bd_vertex, bd_vertex.data(), bd_vertex.size());
-    const int64_t all_entries = h->n_entries + merged_entries;
-    {   // Does it fit?  The factor (with the merged blocks) stays; the numeric factorisation needs a copy of the fronts and the
-        // Schur complements beside it; the iteration's carried gathers are allocated behind it (dots_front_setup).  The
-        // reference just factorises (laplacian_inverse_socp.py:34-41); here the caller gets a status it can act on
-        // (the Python driver falls back to the multigrid-PCG) instead of a failed allocation halfway through.
-        int64_t srows = 0;
-        for (const FrontNode &nd : nodes) srows += (int64_t)nd.b * nd.b;
-        const double per = 8.0 * (double)d.TP;
-        double leaf_entries = 0.0;      // the leaves' explicit inverses, stored beside their blocks (see below)
-        if (leaf_inv)
-            for (int gi : by_band[0]) leaf_entries += 0.5 * (double)groups[(size_t)gi].n * (groups[(size_t)gi].n + 1.0);
-        const double factor_b = per * ((double)all_entries + leaf_entries), work_b = h->values ? 0.0 : per * (double)(h->n_entries + srows);
-        const double carry_b = c->d.TP <= 128 ? 8.0 * (c->shard_stride == 0 ? 12.0 : 9.0) * (double)c->d.F * (double)c->d.TP : 0.0;
-        size_t free_b = 0, total_b = 0;
-        DOTS_HIP(hipMemGetInfo(&free_b, &total_b));
-        double budget = 0.97 * (double)free_b;
-        int mb = -1;
-        if (!env_int("DOTS_MEM_BUDGET", 0, 1 << 30, &mb)) return DOTS_ERR_ARGUMENT;      // MB the factor may take, whatever is free (tests)
-        if (mb >= 0) budget = 1048576.0 * mb;
-        if (factor_b + work_b + carry_b > budget) {
-            char buf[512];
-            snprintf(buf, sizeof buf, "front_setup: the factor does not fit: %.3f GB (factor %.3f GB for %d modes of %d vertices, %.3f GB while it is "
-                     "computed, %.3f GB of per-corner sums) against %.3f GB available", (factor_b + work_b + carry_b) * 1e-9, factor_b * 1e-9, h->n_modes, d.V,
-                     work_b * 1e-9, carry_b * 1e-9, budget * 1e-9);
-            front_release(c);
-            set_error(buf);
-            return DOTS_ERR_MEMORY;
+// ---- workgroup lists of a band: (node, first row) for the forward sweep, (node, first column, row ranges) backward -------------
+SweepNode sweep_node(const dots_front_desc *h, const FrontPlan &P, const Group &G) {
+    SweepNode sn{};
+    sn.n = G.n;
+    sn.b = G.b;
+    sn.k0 = G.k0;
+    sn.planes = G.planes;
+    sn.foff = G.foff;
+    sn.woff = G.woff;
+    sn.parent_w = G.parent < 0 ? -1 : P.plane_in_parent(G);
+    sn.bdoff = h->node_uoff[G.root];
+    return sn;
+}
+void make_fwd(const dots_front_desc *h, const FrontPlan &P, int k, int rb, std::vector<FrontWork> &out) {
+    for (int gi : P.by_band[(size_t)k]) {
+        const Group &G = P.groups[(size_t)gi];
+        const SweepNode sn = sweep_node(h, P, G);
+        std::vector<int> first_col((size_t)G.n, 0);     // first column of its member's subtree, per separator row
+        for (int s : G.members)
+            for (int i = 0; i < h->node_n[s]; ++i) first_col[(size_t)(P.off_in[(size_t)s] + i)] = P.c0_in[(size_t)s];
+        for (int r = 0; r < G.n + G.b; r += rb) {
+            FrontWork w{};
+            w.nd = sn;
+            w.first = r;
+            int lo = r < G.n ? first_col[(size_t)r] : 0;
+            for (int i = r; i < std::min(r + rb, G.n + G.b); ++i) lo = std::min(lo, i < G.n ? first_col[(size_t)i] : 0);
+            w.lo = lo;
+            if (P.inverse_band(k)) { w.lo = 0; w.end = G.n; }     // full rows of S^-1
+            out.push_back(w);
         }
     }
-    const double *Fall = nullptr;
-    if ((rc = front_upload<double>(c, &Fall, nullptr, all_entries << d.tp_shift))) { front_release(c); return rc; }
-    if (h->values) {
-        hipError_t e = hipMemcpyAsync(const_cast<double *>(Fall), h->values, sizeof(double) * ((size_t)h->n_entries << d.tp_shift), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) { front_release(c); return hip_fail(e, "factor upload", __FILE__, __LINE__); }
-    } else {   // numeric factorisation on the device (kernels_factor.hip)
-        std::vector<int> grounded((size_t)d.TP, 0);
-        for (int a = 0; a < h->n_modes; ++a) grounded[(size_t)a] = h->grounded[a] ? 1 : 0;
-        if ((rc = front_factorize(c, h, f0, nodes, const_cast<double *>(Fall), grounded.data()))) { front_release(c); return rc; }
+}
+// row kernel (k_front_fwd_rows): blocks of up to rows_wg rows that never span two members of a merged node (so that wk.lo is
+// the first column of every row of the block) nor the separator / boundary rows; returns the longest column range a block stages
+int make_fwd_rows(const dots_front_desc *h, const FrontPlan &P, int k, int rows_wg, std::vector<FrontWork> &out) {
+    int lds_cols = 1;
+    for (int gi : P.by_band[(size_t)k]) {
+        const Group &G = P.groups[(size_t)gi];
+        const SweepNode sn = sweep_node(h, P, G);
+        const bool full = P.inverse_band(k);
+        std::vector<std::array<int, 3>> segs;      // (first row, one past the last, first column)
+        if (full) segs.push_back({0, G.n, 0});
+        else {
+            for (int s : G.members)
+                if (h->node_n[s] > 0) segs.push_back({P.off_in[(size_t)s], P.off_in[(size_t)s] + h->node_n[s], P.c0_in[(size_t)s]});
+            if (G.b > 0) segs.push_back({G.n, G.n + G.b, 0});
+        }
+        for (const auto &sg : segs)
+            for (int r = sg[0]; r < sg[1]; r += rows_wg) {
+                FrontWork w{};
+                w.nd = sn;
+                w.first = r;
+                w.pad = std::min(rows_wg, sg[1] - r);
+                w.lo = sg[2];
+                const int last = r + w.pad - 1;
+                int jmax = last < G.n ? last + 1 : G.n;
+                if (full) { w.end = G.n; jmax = G.n; }
+                lds_cols = std::max(lds_cols, jmax - w.lo);
+                out.push_back(w);
+            }
     }
-    if (!members.empty()) {      // merged bands: one launch per tree height inside a band, children first
-        std::vector<void *> tmp;
-        auto release_tmp = [&]() { for (void *p : tmp) (void)hipFree(p); };
-        auto dalloc = [&](void **out, size_t bytes, const void *host) -> hipError_t {
-            void *p = nullptr;
-            hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 8));
-            if (e != hipSuccess) return e;
-            tmp.push_back(p);
-            *out = p;
-            return host ? hipMemcpyAsync(p, host, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess;
-        };
-        std::vector<int> order;                      // member records sorted by (band, tree height)
-        std::vector<int> launch_ptr{0};
-        std::vector<int64_t> launch_items;
-        std::vector<int> node_of_member(members.size());
-        for (int p = 0; p < nn; ++p)
-            if (member_of[(size_t)p] >= 0) node_of_member[(size_t)member_of[(size_t)p]] = p;
-        for (int l = 0; l < h->n_levels; ++l) {
-            int64_t items = 0;
-            for (size_t mi = 0; mi < members.size(); ++mi)
-                if (level_of[node_of_member[mi]] == l) {
-                    order.push_back((int)mi);
-                    const MergeMember &mm = members[mi];
-                    items = std::max(items, (int64_t)(mm.n + mm.b) * (mm.o + mm.n - mm.c0));
+    return lds_cols;
+}
+void make_bwd(const dots_front_desc *h, const FrontPlan &P, int k, int cb, std::vector<FrontWork> &out) {
+    for (int gi : P.by_band[(size_t)k]) {
+        const Group &G = P.groups[(size_t)gi];
+        const SweepNode sn = sweep_node(h, P, G);
+        for (int s : G.members) {
+            const int o = P.off_in[(size_t)s], e = o + h->node_n[s];
+            for (int col = o; col < e; col += cb) {
+                FrontWork w{};
+                w.nd = sn;
+                w.first = col;
+                w.end = e;
+                int nr = 0;
+                w.rs[nr] = col;
+                w.re[nr] = e;
+                ++nr;
+                for (int a2 = P.parent[s]; a2 >= 0 && P.root_of[(size_t)a2] == G.root; a2 = P.parent[a2]) {
+                    const int ao = P.off_in[(size_t)a2], ae = ao + h->node_n[a2];
+                    if (ae == ao) continue;
+                    if (w.re[nr - 1] == ao) w.re[nr - 1] = ae;          // adjacent: one range
+                    else if (nr < 4) {
+                        w.rs[nr] = ao;
+                        w.re[nr] = ae;
+                        ++nr;
+                    }
                 }
-            if ((int)order.size() > launch_ptr.back()) {
-                launch_ptr.push_back((int)order.size());
-                launch_items.push_back(items);
+                w.lo = nr;
+                out.push_back(w);
             }
         }
-        void *dm = nullptr, *dl = nullptr, *p0 = nullptr, *p1 = nullptr, *sc = nullptr;
-        hipError_t e = dalloc(&dm, sizeof(MergeMember) * members.size(), members.data());
-        if (e == hipSuccess) e = dalloc(&dl, sizeof(int) * order.size(), order.data());
-        if (e == hipSuccess) e = dalloc(&p0, sizeof(int) * (size_t)h->n_front_rows, h->pull0);
-        if (e == hipSuccess) e = dalloc(&p1, sizeof(int) * (size_t)h->n_front_rows, h->pull1);
-        if (e == hipSuccess) e = dalloc(&sc, sizeof(double) * ((size_t)std::max<int64_t>(scratch_entries, 1) << d.tp_shift), nullptr);
-        if (e == hipSuccess) {
-            MergeArgs g{};
-            g.sh = d.tp_shift; g.TP = d.TP; g.ncol = d.cg_ncol; g.wsh = front_args(d).wsh;
-            g.F = const_cast<double *>(Fall);
-            g.scratch = (double *)sc;
-            g.pull0 = (const int *)p0; g.pull1 = (const int *)p1;
-            g.mem = (const MergeMember *)dm;
-            const int Q = 256 >> g.wsh;
-            for (size_t k = 0; k + 1 < launch_ptr.size(); ++k) {
-                g.list = (const int *)dl + launch_ptr[k];
-                const unsigned bx = (unsigned)std::min<int64_t>(std::max<int64_t>((launch_items[k] + Q - 1) / Q, 1), 2048);
-                hipLaunchKernelGGL(k_merge_member, dim3(bx, (unsigned)(launch_ptr[k + 1] - launch_ptr[k]), front_chunks(d)), dim3(256), 0, c->stream, g);
+    }
+}
+// Workgroups are dealt round-robin over the 8 XCDs (blockIdx mod 8): every XCD gets one contiguous run of a launch's list, so
+// that the row blocks of a node, which read the same right-hand-side and plane rows, share an L2.  Measured (solve, us):
+// knot 49.3 -> 44.0, sphere10k 97.4 -> 89.5, knot63 80.0 -> 74.0; launches of few large nodes (>= 100 workgroups per node:
+// the top of torus100k) lose 4 % with it and keep the plain order; the large launches below them do not care.
+void deal(std::vector<FrontWork> &list, size_t from, size_t n_nodes) {
+    const size_t n = list.size() - from;
+    if (n_nodes < 8 || n < 16 || n > 80 * n_nodes) return;
+    const size_t per = (n + 7) / 8;
+    std::vector<FrontWork> out;
+    out.reserve(n);
+    for (size_t s2 = 0; s2 < per; ++s2)
+        for (size_t x = 0; x < 8; ++x)
+            if (x * per + s2 < n) out.push_back(list[from + x * per + s2]);
+    std::copy(out.begin(), out.end(), list.begin() + (std::ptrdiff_t)from);
+}
+
+// ---- device: the original tree, the factor, the merged blocks -----------------------------------------------------------------
+int upload_tree(Ctx *c, const FrontPlan &P, FrontDev &f0) {      // the original tree as the factorisation sees it
+    int rc;
+    if ((rc = front_upload(c, &f0.nodes, P.nodes.data(), (int64_t)P.nn))) return rc;
+    if (!P.identity0 && (rc = front_upload(c, &f0.vmap, P.vmap0.data(), (int64_t)c->dcg.V))) return rc;
+    return front_upload(c, &f0.bd_vertex, P.bd_vertex.data(), (int64_t)P.bd_vertex.size());
+}
+
+// Does it fit?  The factor (with the merged blocks) stays; the numeric factorisation needs a copy of the fronts and the
+// Schur complements beside it; the iteration's carried gathers are allocated behind it (dots_front_setup).  The
+// reference just factorises (laplacian_inverse_socp.py:34-41); here the caller gets a status it can act on
+// (the Python driver falls back to the multigrid-PCG) instead of a failed allocation halfway through.
+int check_memory(Ctx *c, const dots_front_desc *h, const FrontPlan &P) {
+    const Dev &d = c->dcg;
+    int64_t srows = 0;
+    for (const FrontNode &nd : P.nodes) srows += (int64_t)nd.b * nd.b;
+    const double per = 8.0 * (double)d.TP;
+    double leaf_entries = 0.0;      // the leaves' explicit inverses, stored beside their blocks (install_leaves)
+    if (P.leaf_inv)
+        for (int gi : P.by_band[0]) leaf_entries += 0.5 * (double)P.groups[(size_t)gi].n * (P.groups[(size_t)gi].n + 1.0);
+    const double factor_b = per * ((double)(h->n_entries + P.merged_entries) + leaf_entries), work_b = h->values ? 0.0 : per * (double)(h->n_entries + srows);
+    const double carry_b = c->d.TP <= 128 ? 8.0 * (c->shard_stride == 0 ? 12.0 : 9.0) * (double)c->d.F * (double)c->d.TP : 0.0;
+    size_t free_b = 0, total_b = 0;
+    DOTS_HIP(hipMemGetInfo(&free_b, &total_b));
+    double budget = 0.97 * (double)free_b;
+    int mb = -1;
+    if (!env_int("DOTS_MEM_BUDGET", 0, 1 << 30, &mb)) return DOTS_ERR_ARGUMENT;      // MB the factor may take, whatever is free (tests)
+    if (mb >= 0) budget = 1048576.0 * mb;
+    if (factor_b + work_b + carry_b > budget) {
+        char buf[512];
+        snprintf(buf, sizeof buf, "front_setup: the factor does not fit: %.3f GB (factor %.3f GB for %d modes of %d vertices, %.3f GB while it is "
+                 "computed, %.3f GB of per-corner sums) against %.3f GB available", (factor_b + work_b + carry_b) * 1e-9, factor_b * 1e-9, h->n_modes, d.V,
+                 work_b * 1e-9, carry_b * 1e-9, budget * 1e-9);
+        set_error(buf);
+        return DOTS_ERR_MEMORY;
+    }
+    return 0;
+}
+
+// the factor's blocks (room for the merged ones behind them): the caller's values, or the numeric factorisation on the device (kernels_factor.hip)
+int install_factor(Ctx *c, const dots_front_desc *h, const FrontPlan &P, FrontDev &f0, const double **F) {
+    const Dev &d = c->dcg;
+    int rc;
+    if ((rc = front_upload<double>(c, F, nullptr, (h->n_entries + P.merged_entries) << d.tp_shift))) return rc;
+    if (h->values) {
+        hipError_t e = hipMemcpyAsync(const_cast<double *>(*F), h->values, sizeof(double) * ((size_t)h->n_entries << d.tp_shift), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) return hip_fail(e, "factor upload", __FILE__, __LINE__);
+        return 0;
+    }
+    std::vector<int> grounded((size_t)d.TP, 0);
+    for (int a = 0; a < h->n_modes; ++a) grounded[(size_t)a] = h->grounded[a] ? 1 : 0;
+    return front_factorize(c, h, f0, P.nodes, const_cast<double *>(*F), grounded.data());
+}
+
+// merged bands: one launch per tree height inside a band, children first
+int merge_bands(Ctx *c, const dots_front_desc *h, const FrontPlan &P, const double *F) {
+    const Dev &d = c->dcg;
+    const std::vector<MergeMember> &members = P.members;
+    if (members.empty()) return 0;
+    std::vector<int> order;                      // member records sorted by (band, tree height)
+    std::vector<int> launch_ptr{0};
+    std::vector<int64_t> launch_items;
+    std::vector<int> node_of_member(members.size());
+    for (int p = 0; p < P.nn; ++p)
+        if (P.member_of[(size_t)p] >= 0) node_of_member[(size_t)P.member_of[(size_t)p]] = p;
+    for (int l = 0; l < h->n_levels; ++l) {
+        int64_t items = 0;
+        for (size_t mi = 0; mi < members.size(); ++mi)
+            if (P.level_of[node_of_member[mi]] == l) {
+                order.push_back((int)mi);
+                const MergeMember &mm = members[mi];
+                items = std::max(items, (int64_t)(mm.n + mm.b) * (mm.o + mm.n - mm.c0));
             }
+        if ((int)order.size() > launch_ptr.back()) {
+            launch_ptr.push_back((int)order.size());
+            launch_items.push_back(items);
+        }
+    }
+    DevTemps tmp(c->stream);
+    MergeArgs g{};
+    g.sh = d.tp_shift; g.TP = d.TP; g.ncol = d.cg_ncol; g.wsh = front_args(d).wsh;
+    g.F = const_cast<double *>(F);
+    const int *dl = nullptr;
+    hipError_t e = tmp.copy(&g.mem, members);
+    if (e == hipSuccess) e = tmp.copy(&dl, order);
+    if (e == hipSuccess) e = tmp.copy(&g.pull0, h->pull0, (size_t)h->n_front_rows);
+    if (e == hipSuccess) e = tmp.copy(&g.pull1, h->pull1, (size_t)h->n_front_rows);
+    if (e == hipSuccess) e = tmp.get((void **)&g.scratch, sizeof(double) * ((size_t)std::max<int64_t>(P.scratch_entries, 1) << d.tp_shift));
+    if (e == hipSuccess) {
+        const int Q = 256 >> g.wsh;
+        for (size_t k = 0; k + 1 < launch_ptr.size(); ++k) {
+            g.list = dl + launch_ptr[k];
+            const unsigned bx = (unsigned)std::min<int64_t>(std::max<int64_t>((launch_items[k] + Q - 1) / Q, 1), 2048);
+            hipLaunchKernelGGL(k_merge_member, dim3(bx, (unsigned)(launch_ptr[k + 1] - launch_ptr[k]), front_chunks(d)), dim3(256), 0, c->stream, g);
+        }
+        e = hipGetLastError();
+    }
+    const hipError_t e2 = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess || e2 != hipSuccess) return hip_fail(e != hipSuccess ? e : e2, "merged bands", __FILE__, __LINE__);
+    return 0;
+}
+
+// S^-1 = L^-T L^-1 (k_top_inverse) of the n[k] x n[k] blocks at foff[k] of F, one after the other into `out`: full squares, or with
+// `packed` their lower triangles packed by rows.  out = null (full squares only): in place -- into a temporary, then copied over the blocks in F.
+int explicit_inverses(Ctx *c, const double *F, const std::vector<int64_t> &foff, const std::vector<int> &n, bool packed, double *out, const char *what) {
+    const Dev &d = c->dcg;
+    if (n.empty()) return 0;
+    std::vector<int64_t> ooff;
+    int64_t total = 0, biggest = 1;
+    for (int nk : n) {
+        ooff.push_back(total);
+        total += packed ? (int64_t)nk * (nk + 1) / 2 : (int64_t)nk * nk;
+        biggest = std::max<int64_t>(biggest, (int64_t)nk * nk);
+    }
+    const bool in_place = out == nullptr;
+    DevTemps tmp(c->stream);
+    const int64_t *dfo = nullptr, *doo = nullptr;
+    const int *dn = nullptr;
+    hipError_t e = in_place ? tmp.get((void **)&out, sizeof(double) * ((size_t)total << d.tp_shift)) : hipSuccess;
+    if (e == hipSuccess) e = tmp.copy(&dfo, foff);
+    if (e == hipSuccess) e = tmp.copy(&doo, ooff);
+    if (e == hipSuccess) e = tmp.copy(&dn, n);
+    if (e == hipSuccess) {
+        TopInvArgs g{};
+        g.sh = d.tp_shift; g.TP = d.TP; g.ncol = d.cg_ncol; g.wsh = front_args(d).wsh;
+        g.F = F; g.out = out;
+        g.packed = packed ? 1 : 0;
+        const int Q = 256 >> g.wsh;
+        const unsigned bx = (unsigned)std::min<int64_t>(std::max<int64_t>((biggest + Q - 1) / Q, 1), 4096);
+        for (size_t at = 0; at < n.size() && e == hipSuccess; at += 32768) {      // (grid.y is limited to 65535)
+            g.foff = dfo + at; g.ooff = doo + at; g.n = dn + at;
+            hipLaunchKernelGGL(k_top_inverse, dim3(bx, (unsigned)std::min<size_t>(n.size() - at, 32768), front_chunks(d)), dim3(256), 0, c->stream, g);
             e = hipGetLastError();
         }
-        hipError_t e2 = hipStreamSynchronize(c->stream);
-        release_tmp();
-        if (e != hipSuccess || e2 != hipSuccess) { front_release(c); return hip_fail(e != hipSuccess ? e : e2, "merged bands", __FILE__, __LINE__); }
+        for (size_t k = 0; k < n.size() && e == hipSuccess && in_place; ++k)
+            e = hipMemcpyAsync(const_cast<double *>(F) + (foff[k] << d.tp_shift), out + (ooff[k] << d.tp_shift),
+                               sizeof(double) * ((size_t)n[k] * n[k] << d.tp_shift), hipMemcpyDeviceToDevice, c->stream);
     }
+    const hipError_t e2 = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess || e2 != hipSuccess) return hip_fail(e != hipSuccess ? e : e2, what, __FILE__, __LINE__);
+    return 0;
+}
 
-    if (top_inv) {      // the top band's blocks L'^-1 (n x n, no boundary rows) become S^-1 = L'^-T L'^-1, in place
-        std::vector<int64_t> foffs, ooffs;
-        std::vector<int> ns;
-        int64_t total = 0, biggest = 0;
-        for (int gi : by_band[(size_t)(nb - 1)]) {
-            const Group &G = groups[(size_t)gi];
-            if (G.b != 0) { front_release(c); return bad("top_inverse: a node of the top band has boundary rows"); }
-            if (G.n == 0) continue;
-            foffs.push_back(G.foff);
-            ooffs.push_back(total);
-            ns.push_back(G.n);
-            total += (int64_t)G.n * G.n;
-            biggest = std::max<int64_t>(biggest, (int64_t)G.n * G.n);
-        }
-        if (!ns.empty()) {
-            void *dS = nullptr, *dfo = nullptr, *doo = nullptr, *dn = nullptr;
-            hipError_t e = hipMalloc(&dS, sizeof(double) * ((size_t)total << d.tp_shift));
-            if (e == hipSuccess) e = hipMalloc(&dfo, sizeof(int64_t) * foffs.size());
-            if (e == hipSuccess) e = hipMalloc(&doo, sizeof(int64_t) * ooffs.size());
-            if (e == hipSuccess) e = hipMalloc(&dn, sizeof(int) * ns.size());
-            if (e == hipSuccess) e = hipMemcpyAsync(dfo, foffs.data(), sizeof(int64_t) * foffs.size(), hipMemcpyHostToDevice, c->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(doo, ooffs.data(), sizeof(int64_t) * ooffs.size(), hipMemcpyHostToDevice, c->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(dn, ns.data(), sizeof(int) * ns.size(), hipMemcpyHostToDevice, c->stream);
-            if (e == hipSuccess) {
-                TopInvArgs g{};
-                g.sh = d.tp_shift; g.TP = d.TP; g.ncol = d.cg_ncol; g.wsh = front_args(d).wsh;
-                g.F = Fall; g.out = (double *)dS;
-                g.foff = (const int64_t *)dfo; g.ooff = (const int64_t *)doo; g.n = (const int *)dn;
-                const int Q = 256 >> g.wsh;
-                const unsigned bx = (unsigned)std::min<int64_t>(std::max<int64_t>((biggest + Q - 1) / Q, 1), 4096);
-                hipLaunchKernelGGL(k_top_inverse, dim3(bx, (unsigned)ns.size(), front_chunks(d)), dim3(256), 0, c->stream, g);
-                e = hipGetLastError();
-                for (size_t k = 0; k < ns.size() && e == hipSuccess; ++k)
-                    e = hipMemcpyAsync(const_cast<double *>(Fall) + (foffs[k] << d.tp_shift), (const double *)dS + (ooffs[k] << d.tp_shift),
-                                       sizeof(double) * ((size_t)ns[k] * ns[k] << d.tp_shift), hipMemcpyDeviceToDevice, c->stream);
-            }
-            hipError_t e2 = hipStreamSynchronize(c->stream);
-            for (void *p2 : {dS, dfo, doo, dn}) if (p2) (void)hipFree(p2);
-            if (e != hipSuccess || e2 != hipSuccess) { front_release(c); return hip_fail(e != hipSuccess ? e : e2, "top inverse", __FILE__, __LINE__); }
-        }
+// the top band's blocks L'^-1 (n x n, no boundary rows) become S^-1 = L'^-T L'^-1, in place
+int invert_top_band(Ctx *c, const FrontPlan &P, const double *F) {
+    std::vector<int64_t> foff;
+    std::vector<int> n;
+    for (int gi : P.by_band[(size_t)(P.nb - 1)]) {
+        const Group &G = P.groups[(size_t)gi];
+        if (G.b != 0) return bad("top_inverse: a node of the top band has boundary rows");
+        if (G.n == 0) continue;
+        foff.push_back(G.foff);
+        n.push_back(G.n);
     }
+    return explicit_inverses(c, F, foff, n, false, nullptr, "top inverse");
+}
 
-    FrontDev f{};
-    f.n_nodes = nn;
-    f.n_levels = nb;
-    f.nodes = f0.nodes;
-    f.bd_vertex = f0.bd_vertex;
-    f.F = Fall;
-    if (!identity) FUP(f, vmap, vmap.data(), d.V);
-    FUP(f, cmap, cmap.data(), cmap.size());
+// the sweeps' own tables: the order of the merged tree, where the update rows land, the update planes W
+int upload_sweep_maps(Ctx *c, const FrontPlan &P, FrontDev &f) {
+    const Dev &d = c->dcg;
+    int rc;
+    if (!P.identity && (rc = front_upload(c, &f.vmap, P.vmap.data(), (int64_t)d.V))) return rc;
+    if ((rc = front_upload(c, &f.cmap, P.cmap.data(), (int64_t)P.cmap.size()))) return rc;
     const double *w = nullptr;
-    if ((rc = front_upload<double>(c, &w, nullptr, std::max<int64_t>(wrows, 1) << d.tp_shift))) { front_release(c); return rc; }
+    if ((rc = front_upload<double>(c, &w, nullptr, std::max<int64_t>(P.wrows, 1) << d.tp_shift))) return rc;
     f.W = const_cast<double *>(w);
-    c->sched.w_rows = std::max<int64_t>(wrows, 1);
-    // ---- the leaves as explicit local inverses (leaf_inv above; w and t of the largest leaf must fit the LDS a workgroup may take)
-    if (leaf_inv) {
-        std::vector<LeafWork> leaves;
-        std::vector<int64_t> foffs, ooffs;
-        std::vector<int> ns;
-        int64_t total = 0, biggest = 1, bd_rows = 0;
-        int nmax = 0;
-        double saved_read = 0.0, saved_alg = 0.0;
-        for (int gi : by_band[0]) {
-            const Group &G = groups[(size_t)gi];
-            if (G.n == 0) continue;      // (nothing to eliminate: nothing to send either -- its plane stays zero)
-            LeafWork lw{};
-            lw.k0 = G.k0; lw.n = G.n; lw.b = G.b;
-            lw.soff = total;
-            lw.bdoff = h->node_uoff[G.root];
-            lw.rowoff = bd_rows;
-            lw.parent_w = G.parent < 0 ? 0 : groups[(size_t)G.parent].woff + (int64_t)G.colour * (groups[(size_t)G.parent].n + groups[(size_t)G.parent].b);
-            if (G.parent < 0) lw.b = 0;
-            bd_rows += lw.b;
-            leaves.push_back(lw);
-            foffs.push_back(G.foff);
-            ooffs.push_back(total);
-            ns.push_back(G.n);
-            total += (int64_t)G.n * (G.n + 1) / 2;      // S is symmetric: its lower triangle, packed by rows
-            biggest = std::max<int64_t>(biggest, (int64_t)G.n * G.n);
-            nmax = std::max(nmax, G.n);
-            saved_read += (double)G.b * G.n;
-            saved_alg += (double)G.b * G.n;
-        }
-        const size_t lds = sizeof(double) * 2 * (size_t)nmax * (size_t)d.TP;
-        if (!leaves.empty() && lds <= 48 * 1024) {
-            const double *dS = nullptr;
-            const LeafWork *dl = nullptr;
-            if ((rc = front_upload<double>(c, &dS, nullptr, total << d.tp_shift)) || (rc = front_upload(c, &dl, leaves.data(), (int64_t)leaves.size()))) { front_release(c); return rc; }
-            void *dfo = nullptr, *doo = nullptr, *dn = nullptr;
-            hipError_t e = hipMalloc(&dfo, sizeof(int64_t) * foffs.size());
-            if (e == hipSuccess) e = hipMalloc(&doo, sizeof(int64_t) * ooffs.size());
-            if (e == hipSuccess) e = hipMalloc(&dn, sizeof(int) * ns.size());
-            if (e == hipSuccess) e = hipMemcpyAsync(dfo, foffs.data(), sizeof(int64_t) * foffs.size(), hipMemcpyHostToDevice, c->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(doo, ooffs.data(), sizeof(int64_t) * ooffs.size(), hipMemcpyHostToDevice, c->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(dn, ns.data(), sizeof(int) * ns.size(), hipMemcpyHostToDevice, c->stream);
-            if (e == hipSuccess) {
-                const int Q = 256 >> d.tp_shift;
-                const unsigned bx = (unsigned)std::min<int64_t>(std::max<int64_t>((biggest + std::max(Q, 1) - 1) / std::max(Q, 1), 1), 4096);
-                for (size_t at = 0; at < ns.size() && e == hipSuccess; at += 32768) {      // (grid.y is limited to 65535)
-                    TopInvArgs g{};
-                    g.sh = d.tp_shift; g.TP = d.TP; g.ncol = d.cg_ncol; g.wsh = d.tp_shift;      // (leaf inverses: pitch <= 256)
-                    g.F = Fall; g.out = const_cast<double *>(dS);
-                    g.foff = (const int64_t *)dfo + at; g.ooff = (const int64_t *)doo + at; g.n = (const int *)dn + at;
-                    g.packed = 1;
-                    hipLaunchKernelGGL(k_top_inverse, dim3(bx, (unsigned)std::min<size_t>(ns.size() - at, 32768)), dim3(256), 0, c->stream, g);
-                    e = hipGetLastError();
-                }
+    c->sched.w_rows = std::max<int64_t>(P.wrows, 1);
+    return 0;
+}
+
+// coupling records of the leaves (a row with more entries than a record holds: the kernels walk the CSR instead)
+int leaf_tables(Ctx *c, FrontDev &f, int64_t bd_rows) {
+    const Dev &d = c->dcg;
+    const LeafBdRow *dbt = nullptr;
+    const LeafSepRow *dst = nullptr;
+    const int *dov = nullptr;
+    int rc;
+    if ((rc = front_upload<LeafBdRow>(c, &dbt, nullptr, std::max<int64_t>(bd_rows, 1))) || (rc = front_upload<LeafSepRow>(c, &dst, nullptr, d.V)) ||
+        (rc = front_upload<int>(c, &dov, nullptr, 1))) return rc;
+    hipLaunchKernelGGL(k_leaf_tables, dim3(f.n_leaves), dim3(64), 0, c->stream, f, d.rowptr, d.col, d.val, const_cast<LeafBdRow *>(dbt),
+                       const_cast<LeafSepRow *>(dst), const_cast<int *>(dov));
+    int over = 0;
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(&over, dov, sizeof(int), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return hip_fail(e, "leaf coupling records", __FILE__, __LINE__);
+    if (!over) { f.leaf_bd = dbt; f.leaf_sep = dst; }
+    return 0;
+}
+
+// ---- the leaves as explicit local inverses (P.leaf_inv; w and t of the largest leaf must fit the LDS a workgroup may take)
+int install_leaves(Ctx *c, const dots_front_desc *h, FrontPlan &P, FrontDev &f) {
+    const Dev &d = c->dcg;
+    std::vector<LeafWork> leaves;
+    std::vector<int64_t> foff;
+    std::vector<int> n;
+    int64_t total = 0, bd_rows = 0;
+    int nmax = 0;
+    double saved = 0.0;
+    for (int gi : P.by_band[0]) {
+        const Group &G = P.groups[(size_t)gi];
+        if (G.n == 0) continue;      // (nothing to eliminate: nothing to send either -- its plane stays zero)
+        LeafWork lw{};
+        lw.k0 = G.k0; lw.n = G.n; lw.b = G.b;
+        lw.soff = total;
+        lw.bdoff = h->node_uoff[G.root];
+        lw.rowoff = bd_rows;
+        lw.parent_w = G.parent < 0 ? 0 : P.plane_in_parent(G);
+        if (G.parent < 0) lw.b = 0;
+        bd_rows += lw.b;
+        leaves.push_back(lw);
+        foff.push_back(G.foff);
+        n.push_back(G.n);
+        total += (int64_t)G.n * (G.n + 1) / 2;      // S is symmetric: its lower triangle, packed by rows
+        nmax = std::max(nmax, G.n);
+        saved += (double)G.b * G.n;
+    }
+    const size_t lds = sizeof(double) * 2 * (size_t)nmax * (size_t)d.TP;
+    if (leaves.empty() || lds > 48 * 1024) return 0;
+    const double *dS = nullptr;
+    const LeafWork *dl = nullptr;
+    int rc;
+    if ((rc = front_upload<double>(c, &dS, nullptr, total << d.tp_shift)) || (rc = front_upload(c, &dl, leaves.data(), (int64_t)leaves.size()))) return rc;
+    if ((rc = explicit_inverses(c, f.F, foff, n, true, const_cast<double *>(dS), "leaf inverses"))) return rc;
+    f.leafS = dS;
+    f.leaf_desc = dl;
+    f.n_leaves = (int)leaves.size();
+    f.leaf_nmax = nmax;
+    if (c->front_leafinv == 1 && (rc = leaf_tables(c, f, bd_rows))) return rc;
+    P.entries_read -= saved;          // n (n + 1) / 2 per leaf and sweep (the packed triangle of S) instead of n (n + 1) / 2 + b n;
+    P.entries_unmerged -= saved;      // the coupling is the mode-independent CSR
+    return 0;
+}
+
+// DOTS_FRONT_CFG: "fwd:1024x2,256x4,r1,...;bwd:..." one entry per band (A/B measurements); rQ = row kernel, Q lane groups per row
+int apply_cfg(Ctx *c, const FrontPlan &P) {
+    const char *env = getenv("DOTS_FRONT_CFG");
+    if (!env) return 0;
+    FrontBand *const band = c->sched.band;
+    const std::string spec(env);
+    bool ok = spec.find("fwd:") != std::string::npos || spec.find("bwd:") != std::string::npos;
+    for (int sweep = 0; sweep < 2 && ok; ++sweep) {
+        size_t pos = spec.find(sweep == 0 ? "fwd:" : "bwd:");
+        if (pos == std::string::npos) continue;
+        pos += 4;
+        for (int k = 0; k < P.nb && pos < spec.size() && spec[pos] != ';'; ++k) {
+            int tnb = 0, trb = 0, q = 0;
+            if (sweep == 0 && sscanf(spec.c_str() + pos, "r%d", &q) == 1 && q >= 1 && q <= P.rows_groups() && (q & (q - 1)) == 0) {
+                int qs = 0;
+                while ((1 << qs) < q) ++qs;
+                band[k].fwd_qw = qs;
+            } else if (sscanf(spec.c_str() + pos, "%dx%d", &tnb, &trb) == 2 && (tnb == 256 || tnb == 1024) && (trb == 1 || trb == 2 || trb == 4)) {
+                (sweep == 0 ? band[k].fwd_nb : band[k].bwd_nb) = tnb;
+                (sweep == 0 ? band[k].fwd_rb : band[k].bwd_cb) = trb;
+                if (sweep == 0) band[k].fwd_qw = -1;
+            } else if (spec[pos] != '-') {      // "-" keeps the rule's choice for the band
+                ok = false;
+                break;
             }
-            hipError_t e2 = hipStreamSynchronize(c->stream);
-            for (void *p2 : {dfo, doo, dn}) if (p2) (void)hipFree(p2);
-            if (e != hipSuccess || e2 != hipSuccess) { front_release(c); return hip_fail(e != hipSuccess ? e : e2, "leaf inverses", __FILE__, __LINE__); }
-            f.leafS = dS;
-            f.leaf_desc = dl;
-            f.n_leaves = (int)leaves.size();
-            f.leaf_nmax = nmax;
-            if (c->front_leafinv == 1) {      // coupling records (a row with more entries than a record holds: the kernels walk the CSR instead)
-                const LeafBdRow *dbt = nullptr;
-                const LeafSepRow *dst = nullptr;
-                const int *dov = nullptr;
-                if ((rc = front_upload<LeafBdRow>(c, &dbt, nullptr, std::max<int64_t>(bd_rows, 1))) || (rc = front_upload<LeafSepRow>(c, &dst, nullptr, d.V)) ||
-                    (rc = front_upload<int>(c, &dov, nullptr, 1))) { front_release(c); return rc; }
-                hipLaunchKernelGGL(k_leaf_tables, dim3(f.n_leaves), dim3(64), 0, c->stream, f, d.rowptr, d.col, d.val, const_cast<LeafBdRow *>(dbt),
-                                   const_cast<LeafSepRow *>(dst), const_cast<int *>(dov));
-                int over = 0;
-                hipError_t e3 = hipGetLastError();
-                if (e3 == hipSuccess) e3 = hipMemcpyAsync(&over, dov, sizeof(int), hipMemcpyDeviceToHost, c->stream);
-                if (e3 == hipSuccess) e3 = hipStreamSynchronize(c->stream);
-                if (e3 != hipSuccess) { front_release(c); return hip_fail(e3, "leaf coupling records", __FILE__, __LINE__); }
-                if (!over) { f.leaf_bd = dbt; f.leaf_sep = dst; }
-            }
-            entries_read -= saved_read;          // n (n + 1) / 2 per leaf and sweep (the packed triangle of S) instead of n (n + 1) / 2 + b n;
-            entries_unmerged -= saved_alg;       // the coupling is the mode-independent CSR
+            pos = spec.find_first_of(",;", pos);
+            if (pos == std::string::npos || spec[pos] == ';') break;
+            ++pos;
         }
     }
-    c->sched.bytes = 2.0 * entries_read * d.cg_ncol * sizeof(double);
-    c->sched.bytes_unmerged = 2.0 * entries_unmerged * d.cg_ncol * sizeof(double);
-    if (const char *e = getenv("DOTS_FRONT_CFG")) {      // "fwd:1024x2,256x4,r1,...;bwd:..." one entry per band (A/B measurements); rQ = row kernel, Q lane groups per row
-        const std::string spec(e);
-        bool ok = spec.find("fwd:") != std::string::npos || spec.find("bwd:") != std::string::npos;
-        for (int sweep = 0; sweep < 2 && ok; ++sweep) {
-            size_t pos = spec.find(sweep == 0 ? "fwd:" : "bwd:");
-            if (pos == std::string::npos) continue;
-            pos += 4;
-            for (int k = 0; k < nb && pos < spec.size() && spec[pos] != ';'; ++k) {
-                int tnb = 0, trb = 0, q = 0;
-                if (sweep == 0 && sscanf(spec.c_str() + pos, "r%d", &q) == 1 && q >= 1 && q <= rows_groups && (q & (q - 1)) == 0) {
-                    int qs = 0;
-                    while ((1 << qs) < q) ++qs;
-                    band[k].fwd_qw = qs;
-                } else if (sscanf(spec.c_str() + pos, "%dx%d", &tnb, &trb) == 2 && (tnb == 256 || tnb == 1024) && (trb == 1 || trb == 2 || trb == 4)) {
-                    (sweep == 0 ? band[k].fwd_nb : band[k].bwd_nb) = tnb;
-                    (sweep == 0 ? band[k].fwd_rb : band[k].bwd_cb) = trb;
-                    if (sweep == 0) band[k].fwd_qw = -1;
-                } else if (spec[pos] != '-') {      // "-" keeps the rule's choice for the band
-                    ok = false;
-                    break;
-                }
-                pos = spec.find_first_of(",;", pos);
-                if (pos == std::string::npos || spec[pos] == ';') break;
-                ++pos;
+    if (!ok) return bad("DOTS_FRONT_CFG: expected 'fwd:<entry>,...;bwd:<entry>,...' with entries 256xR, 1024xR (R = 1, 2, 4), rQ (forward: row kernel) or -");
+    return 0;
+}
+
+// DOTS_FRONT_TUNE: time every (threads, rows) choice per band and sweep on this device; prints the table (2: also applies the fastest)
+void tune_bands(Ctx *c, const dots_front_desc *h, const FrontPlan &P, const FrontDev &f) {
+    const Dev &d = c->dcg;
+    FrontBand *const band = c->sched.band;
+    DevTemps tmp(c->stream);
+    double *vec[3] = {nullptr, nullptr, nullptr};
+    const size_t vec_bytes = sizeof(double) * ((size_t)d.V << d.tp_shift);
+    bool ok = true;
+    for (int i = 0; i < 3 && ok; ++i) ok = tmp.get((void **)&vec[i], vec_bytes) == hipSuccess && hipMemsetAsync(vec[i], 0, vec_bytes, c->stream) == hipSuccess;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ok = ok && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
+    // A factor larger than the Infinity Cache streams from HBM in the real solve; a launch repeated back to back would find its
+    // band (60-130 MB) in the cache.  There every timed launch is preceded by a read sweep over 512 MB (cold caches, no dirty lines, one event pair per
+    // launch); small factors ARE cache-resident in the real solve and are timed back to back.
+    const bool cold = c->sched.bytes > 400.0e6;
+    double *flushbuf = nullptr;
+    const size_t flush_bytes = (size_t)512 << 20;
+    if (cold && ok) ok = tmp.get((void **)&flushbuf, flush_bytes) == hipSuccess && hipMemsetAsync(flushbuf, 0, flush_bytes, c->stream) == hipSuccess;
+    // one work list on the device, timed: microseconds per launch, or a negative number where the list found no room
+    auto time_us = [&](const std::vector<FrontWork> &list, auto &&launch) -> double {
+        DevTemps one(c->stream);      // (freed after the event wait below)
+        const FrontWork *dl = nullptr;
+        if (one.copy(&dl, list) != hipSuccess) return -1.0;
+        if (!cold) {
+            const int reps = 20;
+            for (int rep = -3; rep < reps; ++rep) {
+                if (rep == 0) (void)hipEventRecord(e0, c->stream);
+                launch(dl);
             }
+            (void)hipEventRecord(e1, c->stream);
+            (void)hipEventSynchronize(e1);
+            float ms = 0.f;
+            (void)hipEventElapsedTime(&ms, e0, e1);
+            return 1e3 * ms / reps;
         }
-        if (!ok) { front_release(c); return bad("DOTS_FRONT_CFG: expected 'fwd:<entry>,...;bwd:<entry>,...' with entries 256xR, 1024xR (R = 1, 2, 4), rQ (forward: row kernel) or -"); }
-    }
-    // Workgroups are dealt round-robin over the 8 XCDs (blockIdx mod 8): every XCD gets one contiguous run of a launch's list, so
-    // that the row blocks of a node, which read the same right-hand-side and plane rows, share an L2.  Measured (solve, us):
-    // knot 49.3 -> 44.0, sphere10k 97.4 -> 89.5, knot63 80.0 -> 74.0; launches of few large nodes (>= 100 workgroups per node:
-    // the top of torus100k) lose 4 % with it and keep the plain order; the large launches below them do not care.
-    auto deal = [&](std::vector<FrontWork> &list, size_t from, size_t n_nodes) {
-        const size_t n = list.size() - from;
-        if (n_nodes < 8 || n < 16 || n > 80 * n_nodes) return;
-        const size_t per = (n + 7) / 8;
-        std::vector<FrontWork> out;
-        out.reserve(n);
-        for (size_t s2 = 0; s2 < per; ++s2)
-            for (size_t x = 0; x < 8; ++x)
-                if (x * per + s2 < n) out.push_back(list[from + x * per + s2]);
-        std::copy(out.begin(), out.end(), list.begin() + (std::ptrdiff_t)from);
+        const int reps = 6;
+        double total = 0.0;
+        for (int rep = -1; rep < reps; ++rep) {
+            hipLaunchKernelGGL(k_flush_read, dim3(4096), dim3(256), 0, c->stream, (const double *)flushbuf, (int64_t)(flush_bytes / sizeof(double)), flushbuf);
+            (void)hipEventRecord(e0, c->stream);
+            launch(dl);
+            (void)hipEventRecord(e1, c->stream);
+            (void)hipEventSynchronize(e1);
+            float ms = 0.f;
+            (void)hipEventElapsedTime(&ms, e0, e1);
+            if (rep >= 0) total += ms;
+        }
+        return 1e3 * total / reps;
     };
-    if (c->front_tune) {     // DOTS_FRONT_TUNE: time every (threads, rows) choice per band and sweep on this device; prints the table
-        std::vector<void *> tmp;
-        double *vec[3] = {nullptr, nullptr, nullptr};
-        bool ok = true;
-        for (int i = 0; i < 3 && ok; ++i) {
-            void *p2 = nullptr;
-            ok = hipMalloc(&p2, sizeof(double) * ((size_t)d.V << d.tp_shift)) == hipSuccess;
-            if (ok) { tmp.push_back(p2); vec[i] = (double *)p2; ok = hipMemsetAsync(p2, 0, sizeof(double) * ((size_t)d.V << d.tp_shift), c->stream) == hipSuccess; }
+    if (cold) fprintf(stderr, "[front tune] cold caches: every timed launch follows a read sweep over 512 MB\n");
+    for (int k = 0; k < P.nb && ok; ++k)
+        for (int sweep = 0; sweep < 2 && ok; ++sweep) {
+            if (sweep == 1 && P.inverse_band(k)) continue;      // no backward launch there
+            const size_t n_nodes = P.by_band[(size_t)k].size();
+            double best = 1e30;
+            int bnb = 0, brb = 0;
+            fprintf(stderr, "[front tune] band %d (heights %d-%d, %s, %lld %s, planes %d):", k, P.cuts[(size_t)k], P.cuts[(size_t)k + 1] - 1, sweep == 0 ? "fwd" : "bwd",
+                    (long long)(sweep == 0 ? P.band_rows[(size_t)k] : P.band_cols[(size_t)k]), sweep == 0 ? "rows" : "cols", band[k].planes);
+            for (int tnb : {256, 1024})
+                for (int trb : {1, 2, 4}) {
+                    std::vector<FrontWork> list;
+                    if (sweep == 0) make_fwd(h, P, k, trb, list); else make_bwd(h, P, k, trb, list);
+                    deal(list, 0, n_nodes);
+                    if (list.empty()) continue;
+                    const double us = time_us(list, [&](const FrontWork *dl) {
+                        if (sweep == 0) front_launch_fwd(c, f, dl, (int)list.size(), tnb, trb, band[k].planes, vec[0], vec[1], MoreRhs<1>{});
+                        else front_launch_bwd(c, f, dl, (int)list.size(), tnb, trb, vec[1], vec[2], MoreRhs<1>{});
+                    });
+                    if (us < 0.0) { ok = false; break; }
+                    const bool cur = tnb == (sweep == 0 ? band[k].fwd_nb : band[k].bwd_nb) && trb == (sweep == 0 ? band[k].fwd_rb : band[k].bwd_cb) &&
+                                     !(sweep == 0 && band[k].fwd_qw >= 0);
+                    fprintf(stderr, " %dx%d %.2f%s", tnb, trb, us, cur ? "*" : "");
+                    if (us < best) { best = us; bnb = tnb; brb = trb; }
+                }
+            int bqs = -1;
+            for (int qs = 0; sweep == 0 && (1 << qs) <= P.rows_groups() && qs <= 4; ++qs) {
+                std::vector<FrontWork> list;
+                const int lds_cols = make_fwd_rows(h, P, k, P.rows_per_wg(qs), list);
+                if (!rows_fit_lds(d, lds_cols) || list.empty()) continue;
+                deal(list, 0, n_nodes);
+                const double us = time_us(list, [&](const FrontWork *dl) { front_launch_fwd_rows(c, f, dl, (int)list.size(), qs, band[k].planes, lds_cols, vec[0], vec[1], MoreRhs<1>{}); });
+                if (us < 0.0) { ok = false; break; }
+                fprintf(stderr, " r%d %.2f%s", 1 << qs, us, band[k].fwd_qw == qs ? "*" : "");
+                if (us < best) { best = us; bqs = qs; }
+            }
+            if (bqs >= 0) fprintf(stderr, "  -> r%d\n", 1 << bqs);
+            else fprintf(stderr, "  -> %dx%d\n", bnb, brb);
+            if (c->front_tune > 1 && bnb) {
+                (sweep == 0 ? band[k].fwd_nb : band[k].bwd_nb) = bnb;
+                (sweep == 0 ? band[k].fwd_rb : band[k].bwd_cb) = brb;
+                if (sweep == 0) band[k].fwd_qw = bqs;
+            }
         }
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ok = ok && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
-        const int apply = c->front_tune;
-        // A factor larger than the Infinity Cache streams from HBM in the real solve; a launch repeated back to back would find its
-        // band (60-130 MB) in the cache.  There every timed launch is preceded by a read sweep over 512 MB (cold caches, no dirty lines, one event pair per
-        // launch); small factors ARE cache-resident in the real solve and are timed back to back.
-        const bool cold = c->sched.bytes > 400.0e6;
-        void *flushbuf = nullptr;
-        const size_t flush_bytes = (size_t)512 << 20;
-        if (cold && ok) {
-            ok = hipMalloc(&flushbuf, flush_bytes) == hipSuccess;
-            if (ok) { tmp.push_back(flushbuf); ok = hipMemsetAsync(flushbuf, 0, flush_bytes, c->stream) == hipSuccess; }
-        }
-        auto time_us = [&](const std::function<void()> &launch) -> double {
-            if (!cold) {
-                const int reps = 20;
-                for (int rep = -3; rep < reps; ++rep) {
-                    if (rep == 0) (void)hipEventRecord(e0, c->stream);
-                    launch();
-                }
-                (void)hipEventRecord(e1, c->stream);
-                (void)hipEventSynchronize(e1);
-                float ms = 0.f;
-                (void)hipEventElapsedTime(&ms, e0, e1);
-                return 1e3 * ms / reps;
-            }
-            const int reps = 6;
-            double total = 0.0;
-            for (int rep = -1; rep < reps; ++rep) {
-                hipLaunchKernelGGL(k_flush_read, dim3(4096), dim3(256), 0, c->stream, (const double *)flushbuf, (int64_t)(flush_bytes / sizeof(double)), (double *)flushbuf);
-                (void)hipEventRecord(e0, c->stream);
-                launch();
-                (void)hipEventRecord(e1, c->stream);
-                (void)hipEventSynchronize(e1);
-                float ms = 0.f;
-                (void)hipEventElapsedTime(&ms, e0, e1);
-                if (rep >= 0) total += ms;
-            }
-            return 1e3 * total / reps;
-        };
-        if (cold) fprintf(stderr, "[front tune] cold caches: every timed launch follows a read sweep over 512 MB\n");
-        for (int k = 0; k < nb && ok; ++k)
-            for (int sweep = 0; sweep < 2 && ok; ++sweep) {
-                if (sweep == 1 && top_inv && k == nb - 1) continue;      // no backward launch there
-                double best = 1e30;
-                int bnb = 0, brb = 0;
-                fprintf(stderr, "[front tune] band %d (heights %d-%d, %s, %lld %s, planes %d):", k, cuts[(size_t)k], cuts[(size_t)k + 1] - 1, sweep == 0 ? "fwd" : "bwd",
-                        (long long)(sweep == 0 ? band_rows[(size_t)k] : band_cols[(size_t)k]), sweep == 0 ? "rows" : "cols", band[k].planes);
-                for (int tnb : {256, 1024})
-                    for (int trb : {1, 2, 4}) {
-                        std::vector<FrontWork> list;
-                        if (sweep == 0) make_fwd(k, trb, list); else make_bwd(k, trb, list);
-                        deal(list, 0, by_band[(size_t)k].size());
-                        if (list.empty()) continue;
-                        void *dl = nullptr;
-                        if (hipMalloc(&dl, sizeof(FrontWork) * list.size()) != hipSuccess) { ok = false; break; }
-                        (void)hipMemcpyAsync(dl, list.data(), sizeof(FrontWork) * list.size(), hipMemcpyHostToDevice, c->stream);
-                        const double us = time_us([&]() {
-                            if (sweep == 0) front_launch_fwd(c, f, (const FrontWork *)dl, (int)list.size(), tnb, trb, band[k].planes, vec[0], vec[1], MoreRhs<1>{});
-                            else front_launch_bwd(c, f, (const FrontWork *)dl, (int)list.size(), tnb, trb, vec[1], vec[2], MoreRhs<1>{});
-                        });
-                        (void)hipFree(dl);
-                        const bool cur = tnb == (sweep == 0 ? band[k].fwd_nb : band[k].bwd_nb) && trb == (sweep == 0 ? band[k].fwd_rb : band[k].bwd_cb) &&
-                                         !(sweep == 0 && band[k].fwd_qw >= 0);
-                        fprintf(stderr, " %dx%d %.2f%s", tnb, trb, us, cur ? "*" : "");
-                        if (us < best) { best = us; bnb = tnb; brb = trb; }
-                    }
-                int bqs = -1;
-                if (sweep == 0) {
-                    for (int qs = 0; (1 << qs) <= rows_groups && qs <= 4; ++qs) {
-                        std::vector<FrontWork> list;
-                        const int lds_cols = make_fwd_rows(k, rows_per_wg(qs), list);
-                        if ((size_t)lds_cols * (size_t)(d.TP + FWD_ROWS_PAD) * sizeof(double) > FWD_ROWS_LDS_MAX || list.empty()) continue;
-                        deal(list, 0, by_band[(size_t)k].size());
-                        void *dl = nullptr;
-                        if (hipMalloc(&dl, sizeof(FrontWork) * list.size()) != hipSuccess) { ok = false; break; }
-                        (void)hipMemcpyAsync(dl, list.data(), sizeof(FrontWork) * list.size(), hipMemcpyHostToDevice, c->stream);
-                        const double us = time_us([&]() { front_launch_fwd_rows(c, f, (const FrontWork *)dl, (int)list.size(), qs, band[k].planes, lds_cols, vec[0], vec[1], MoreRhs<1>{}); });
-                        (void)hipFree(dl);
-                        fprintf(stderr, " r%d %.2f%s", 1 << qs, us, band[k].fwd_qw == qs ? "*" : "");
-                        if (us < best) { best = us; bqs = qs; }
-                    }
-                }
-                if (bqs >= 0) fprintf(stderr, "  -> r%d\n", 1 << bqs);
-                else fprintf(stderr, "  -> %dx%d\n", bnb, brb);
-                if (apply > 1 && bnb) {
-                    (sweep == 0 ? band[k].fwd_nb : band[k].bwd_nb) = bnb;
-                    (sweep == 0 ? band[k].fwd_rb : band[k].bwd_cb) = brb;
-                    if (sweep == 0) band[k].fwd_qw = bqs;
-                }
-            }
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        (void)hipStreamSynchronize(c->stream);
-        (void)hipMemsetAsync(f.W, 0, sizeof(double) * ((size_t)std::max<int64_t>(wrows, 1) << d.tp_shift), c->stream);
-        (void)hipStreamSynchronize(c->stream);
-        for (void *p2 : tmp) (void)hipFree(p2);
-    }
-    // (Tried in round 3 and rejected: the independent subtrees below the top of the tree on 2 or 4 streams, so that one stream's
-    // ramp-up and drain overlap another's streaming -- launches from several streams do not overlap here, every launch costs
-    // ~10 us more: sphere10k solve 85 -> 169 -> 272 us, torus100k 753 -> 804 -> 1061 us; profiles/studies/r03_lanes_experiment.txt)
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipMemsetAsync(f.W, 0, sizeof(double) * ((size_t)std::max<int64_t>(P.wrows, 1) << d.tp_shift), c->stream);
+    (void)hipStreamSynchronize(c->stream);
+}
+
+// the work lists of both sweeps, band after band, as the schedule's shapes say; the factor goes live
+// (Tried in round 3 and rejected: the independent subtrees below the top of the tree on 2 or 4 streams, so that one stream's
+// ramp-up and drain overlap another's streaming -- launches from several streams do not overlap here, every launch costs
+// ~10 us more: sphere10k solve 85 -> 169 -> 272 us, torus100k 753 -> 804 -> 1061 us; profiles/studies/r03_lanes_experiment.txt)
+int install_schedule(Ctx *c, const dots_front_desc *h, const FrontPlan &P, FrontDev &f) {
     std::vector<FrontWork> fwd, bwd;
-    for (int k = 0; k < nb; ++k) {
-        FrontBand &bd = band[k];
+    for (int k = 0; k < P.nb; ++k) {
+        FrontBand &bd = c->sched.band[k];
+        const size_t n_nodes = P.by_band[(size_t)k].size();
         bd.fwd_first = (int)fwd.size();
         bd.bwd_first = (int)bwd.size();
         if (bd.fwd_qw >= 0) {
-            bd.fwd_lds = make_fwd_rows(k, rows_per_wg(bd.fwd_qw), fwd);
-            if ((size_t)bd.fwd_lds * (size_t)(d.TP + FWD_ROWS_PAD) * sizeof(double) > FWD_ROWS_LDS_MAX) {
-                front_release(c);
-                return bad("DOTS_FRONT_CFG: the row kernel does not fit a band it was forced on (its right-hand side exceeds the LDS budget)");
-            }
+            bd.fwd_lds = make_fwd_rows(h, P, k, P.rows_per_wg(bd.fwd_qw), fwd);
+            if (!rows_fit_lds(c->dcg, bd.fwd_lds)) return bad("DOTS_FRONT_CFG: the row kernel does not fit a band it was forced on (its right-hand side exceeds the LDS budget)");
         } else {
-            make_fwd(k, bd.fwd_rb, fwd);
+            make_fwd(h, P, k, bd.fwd_rb, fwd);
         }
-        make_bwd(k, bd.bwd_cb, bwd);
+        make_bwd(h, P, k, bd.bwd_cb, bwd);
         bd.fwd_n = (int)fwd.size() - bd.fwd_first;
         bd.bwd_n = (int)bwd.size() - bd.bwd_first;
-        deal(fwd, (size_t)bd.fwd_first, by_band[(size_t)k].size());
-        deal(bwd, (size_t)bd.bwd_first, by_band[(size_t)k].size());
+        deal(fwd, (size_t)bd.fwd_first, n_nodes);
+        deal(bwd, (size_t)bd.bwd_first, n_nodes);
     }
-    FUP(f, fwd_desc, fwd.data(), std::max<size_t>(fwd.size(), 1)); FUP(f, bwd_desc, bwd.data(), std::max<size_t>(bwd.size(), 1));
-#undef FUP
+    int rc;
+    if ((rc = front_upload(c, &f.fwd_desc, fwd.data(), (int64_t)std::max<size_t>(fwd.size(), 1)))) return rc;
+    if ((rc = front_upload(c, &f.bwd_desc, bwd.data(), (int64_t)std::max<size_t>(bwd.size(), 1)))) return rc;
     c->front = f;
     c->use_front = 1;
-    c->sched.n_bands = nb;
+    c->sched.n_bands = P.nb;
     c->sched.eps = c->prm.eps;
     c->sched.heights = h->n_levels;
-    c->sched.top_inverse = top_inv ? 1 : 0;
+    c->sched.top_inverse = P.top_inv ? 1 : 0;
+    return 0;
+}
+}  // namespace
+
+// The direct solver's setup: a host plan (FrontPlan) filled phase by phase, then the device work in a fixed order -- allocate, factorise,
+// merge, top inverse, W, leaf inverses, leaf tables, tuner, lists (dots_front_share picks through front_allocs by position).
+int front_setup(Ctx *c, const dots_front_desc *h) {
+    const Dev &d = c->dcg;
+    FrontPlan P;
+    int rc;
+    if ((rc = check_desc(d, h, P))) return rc;
+    DOTS_HIP(hipStreamSynchronize(c->stream));
+    front_release(c);
+    ReleaseUnlessDone guard{c};      // every failing exit below releases what it installed
+    if ((rc = build_tree(d, h, P))) return rc;
+    if ((rc = group_bands(d, h, P))) return rc;
+    choose_shapes(c, h, P);
+    FrontDev f0{};
+    f0.n_nodes = P.nn;
+    f0.n_levels = h->n_levels;
+    if ((rc = upload_tree(c, P, f0))) return rc;
+    if ((rc = check_memory(c, h, P))) return rc;
+    const double *F = nullptr;
+    if ((rc = install_factor(c, h, P, f0, &F))) return rc;
+    if ((rc = merge_bands(c, h, P, F))) return rc;
+    if (P.top_inv && (rc = invert_top_band(c, P, F))) return rc;
+    FrontDev f{};
+    f.n_nodes = P.nn;
+    f.n_levels = P.nb;
+    f.nodes = f0.nodes;
+    f.bd_vertex = f0.bd_vertex;
+    f.F = F;
+    if ((rc = upload_sweep_maps(c, P, f))) return rc;
+    if (P.leaf_inv && (rc = install_leaves(c, h, P, f))) return rc;
+    c->sched.bytes = 2.0 * P.entries_read * d.cg_ncol * sizeof(double);
+    c->sched.bytes_unmerged = 2.0 * P.entries_unmerged * d.cg_ncol * sizeof(double);
+    if ((rc = apply_cfg(c, P))) return rc;
+    if (c->front_tune) tune_bands(c, h, P, f);
+    if ((rc = install_schedule(c, h, P, f))) return rc;
+    guard.done = true;
     return 0;
 }
 

@@ -631,8 +631,8 @@ int dots_bench_kernel(dots_ctx *ctx, int which, int reps, double *ms_per_launch,
  * batched solve (dots_laplacian_solve_many, dots_step_many, dots_bench_many) enqueued, read on the batch's first context, 8 of those, the
  * launches that took fewer right-hand sides than their chunk of DOTS_FRONT_NR problems held because NR regions of LDS would not fit or
  * a workgroup of 1024 threads takes fewer (the launch was split), 9 bytes this context has copied device -> host through dots_download
- * and dots_readout since it was created (the layer sums of dots_readout are written by the device itself and not copied); -1 for an
- * unknown counter */
+ * and dots_readout since it was created (the layer sums of dots_readout are written by the device itself and not copied), 10 device
+ * allocations this context holds for its factor (0 without one, also after a dots_front_setup that failed); -1 for an unknown counter */
 int64_t dots_debug_counter(dots_ctx *ctx, int which);
 
 /* device memory in use by the context, bytes */

@@ -348,6 +348,43 @@ def test_leaf_coupling_falls_back_to_the_csr_on_high_degree_vertices(monkeypatch
     assert np.all(np.isfinite(out["1"])) and rel(out["1"], out["0"]) < 1e-11
 
 
+def test_failed_setup_leaves_the_context_as_new(monkeypatch):
+    """Setups that fail at different depths of dots_front_setup -- a bad DOTS_FRONT_CFG (after the factor, the merged blocks and the
+    leaf tables are on the device), a budget the factor does not fit and a budget that is no number (both after the tree's tables are)
+    -- release everything they installed: debug counter 10, the device allocations the context holds for its factor, is 0 after each
+    (it is not 0 after the good setup), and the good setup that follows on the same context solves bit for bit like a fresh context's.
+    device_bytes() is compared too, but cannot see any of this: it counts what dots_create allocated and is fixed from then on."""
+    from dots_socp_amd import _lib
+
+    geom, _ = meshes.example("sphere", level=3)
+
+    def solve(dev):
+        dev.setup_frontal(eps=1e-3)
+        assert dev.debug_counter(10) > 0
+        assert dev.run_phase("laplacian").cg_not_converged == 0
+        return dev.download("phi"), dev.device_bytes()
+
+    fresh = make(geom, 15, 1e-3, "nd")
+    want, want_bytes = solve(fresh)
+    fresh.close()
+    dev = make(geom, 15, 1e-3, "nd")
+    assert dev.debug_counter(10) == 0
+    for name, value, match, status in (("DOTS_FRONT_CFG", "fwd:r3", "DOTS_FRONT_CFG", _lib.ERR_ARGUMENT), ("DOTS_MEM_BUDGET", "1", "does not fit", _lib.ERR_MEMORY),
+                                       ("DOTS_MEM_BUDGET", "plenty", "DOTS_MEM_BUDGET", _lib.ERR_ARGUMENT)):
+        monkeypatch.setenv(name, value)
+        with pytest.raises(_lib.HipLibraryError, match=match) as err:
+            dev.setup_frontal(eps=1e-3)
+        assert err.value.status == status
+        monkeypatch.delenv(name)
+        assert dev.debug_counter(10) == 0, (name, value)
+        with pytest.raises(_lib.HipLibraryError, match="no factor"):
+            dev.enable_frontal(True)
+    got, got_bytes = solve(dev)
+    dev.close()
+    assert np.all(np.isfinite(want)) and np.array_equal(got, want)
+    assert got_bytes == want_bytes
+
+
 @pytest.mark.parametrize("mesh,kw,T,want", [("knot", {}, 31, 0), ("knot", {}, 63, 1), ("sphere", dict(level=5), 31, 1), ("torus", dict(nu=250, nv=160), 31, 1),
                                             ("torus", dict(nu=400, nv=250), 31, 0)])
 def test_beta_mid_streaming_rule(mesh, kw, T, want, monkeypatch):
