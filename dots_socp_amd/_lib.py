@@ -32,7 +32,7 @@ EXPORTS = [
     "dots_objective_combine", "dots_front_launches", "dots_front_info", "dots_front_setup", "dots_front_enable", "dots_front_pitch", "dots_penalty_ahead", "dots_step_flags", "dots_step_times", "dots_stream_wait", "dots_tree_build", "dots_tree_nodes", "dots_tree_copy", "dots_tree_free",
     "dots_patch_order", "dots_assemble", "dots_assemble_nnz", "dots_assemble_copy", "dots_assemble_free", "dots_symbolic_build", "dots_symbolic_front_rows", "dots_symbolic_copy", "dots_symbolic_free",
     "dots_front_share", "dots_laplacian_solve_many", "dots_step_many", "dots_bench_many", "dots_prolong_time", "dots_readout",
-    "dots_prolong_space", "dots_transfer_space",
+    "dots_prolong_space", "dots_transfer_space", "dots_carry_spacetime",
 ]
 
 
@@ -118,6 +118,11 @@ class ProlongSpaceDesc(C.Structure):      # dots_prolong_space_desc
 class TransferSpaceDesc(C.Structure):      # dots_transfer_space_desc
     _fields_ = [("vsrc", _i32p), ("vw", _f64p), ("fsrc", _i32p), ("csrc", _i32p), ("n_vertices", C.c_int32), ("n_triangles", C.c_int32),
                 ("factor", C.c_double * 4), ("ms", _f64p)]
+
+
+class CarrySpacetimeDesc(C.Structure):      # dots_carry_spacetime_desc
+    _fields_ = [("node_j", _i32p), ("node_w", _f64p), ("interval_j", _i32p), ("interval_w", _f64p), ("vsrc", _i32p), ("vw", _f64p), ("fsrc", _i32p),
+                ("csrc", _i32p), ("n_vertices", C.c_int32), ("n_triangles", C.c_int32), ("factor", C.c_double * 4), ("ms", _f64p)]
 
 
 class ReadoutDesc(C.Structure):      # dots_readout_desc
@@ -316,6 +321,7 @@ def load(host_only=False):
     lib.dots_readout.argtypes = [vp, C.POINTER(ReadoutDesc)]
     lib.dots_prolong_space.argtypes = [vp, vp, C.POINTER(ProlongSpaceDesc)]
     lib.dots_transfer_space.argtypes = [vp, vp, C.POINTER(TransferSpaceDesc)]
+    lib.dots_carry_spacetime.argtypes = [vp, vp, C.POINTER(CarrySpacetimeDesc)]
     lib.dots_device_bytes.argtypes = [vp]
     lib.dots_device_bytes.restype = C.c_int64
     for n in EXPORTS:

@@ -24,6 +24,9 @@ numberings into the row maps the kernel reads.
 Between two independent triangulations of one surface (no ``parents``) the transfer is barycentric (``transfer_space``;
 ``dots_transfer_space``, k_carry_space): ``locate`` finds the closest point of the coarse mesh to every fine vertex and triangle
 centroid, ``mesh_transfer`` turns that into the tables of the transfer, ``transfer_row_maps`` puts them into the two device numberings.
+
+A step that changes the mesh AND the time grid (``carry_spacetime``; ``dots_carry_spacetime``, k_carry_spacetime) is the composition
+of the two: the transfer in space first, then the interpolation in time, with the functions above unchanged.
 """
 from __future__ import annotations
 
@@ -413,3 +416,66 @@ def transfer_row_maps(transfer, perm_vert_dst=None, perm_tri_dst=None, perm_vert
     fsrc = inverse_numbering(perm_tri_src, n_src_t, "transfer_row_maps")[ts]
     return (np.ascontiguousarray(vsrc, dtype=np.int32), np.ascontiguousarray(vw, dtype=np.float64),
             np.ascontiguousarray(fsrc, dtype=np.int32), np.ascontiguousarray(cs, dtype=np.int32))
+
+
+# ---- coarse-to-fine in space and time at once ------------------------------------------------------------------------------------
+def _one_map(who, parents, transfer):
+    if (parents is None) == (transfer is None):
+        raise ValueError(f"{who}: exactly one of parents (the source is the parent mesh) and transfer (a located mesh) is needed")
+
+
+def carry_spacetime(array, name, n_src, n_dst, parents=None, transfer=None):
+    """``array`` (the state array ``name`` on the source mesh and the grid of ``n_src`` intervals, reference layout) on the destination
+    mesh of ``parents`` (``prolong_space``) or of ``transfer`` (``transfer_space``) -- exactly one of them -- and on the grid of ``n_dst``
+    intervals.  Space first, then time: ``prolong_time(prolong_space(array, name, parents), name, n_src, n_dst)``, or the same with
+    ``transfer_space``; this order of operations is the definition.  Only for ``n_src != n_dst``: on equal grids ``prolong_time`` is
+    ``(1 - w) * a[j] + w * a[j1]`` at ``w = 0``, which differs from a plain carry in the sign of zero and next to non-finite values, so
+    equal grids stay with ``prolong_space`` / ``transfer_space`` alone (``ValueError``)."""
+    _one_map("carry_spacetime", parents, transfer)
+    if int(n_src) == int(n_dst):
+        raise ValueError(f"carry_spacetime: both grids have {int(n_dst)} intervals: on one time grid the carriers in space "
+                         "(prolong_space / transfer_space) are the definition")
+    in_space = prolong_space(array, name, parents) if parents is not None else transfer_space(array, name, transfer)
+    return prolong_time(in_space, name, n_src, n_dst)
+
+
+def carry_spacetime_solution(solution, n_src, n_dst, parents=None, transfer=None):
+    """Every state array of ``solution`` (a dict as ``solver_socp`` returns it) on the destination mesh and the grid of ``n_dst``
+    intervals: an ``init_solution``."""
+    _one_map("carry_spacetime_solution", parents, transfer)
+    names = VERTEX_ARRAYS + TRIANGLE_ARRAYS + CORNER_ARRAYS
+    return {k: carry_spacetime(v, k, n_src, n_dst, parents=parents, transfer=transfer) for k, v in solution.items() if k in names and v is not None}
+
+
+def default_spacetime_levels(n_time, n_geometries):
+    """The ``n_time`` of every mesh level (coarse to fine) of a cascade in space and time that ends at ``n_time``: from the finest level
+    downward ``n_time + 1`` is halved per mesh level while it is even and the half stays >= ``MIN_LEVEL_NODES``, then held
+    (127, 3 levels -> 31, 63, 127; 31 -> 15, 15, 31; 20 -> 20, 20)."""
+    nodes = int(n_time) + 1
+    levels = [nodes - 1]
+    for _ in range(int(n_geometries) - 1):
+        if nodes % 2 == 0 and nodes // 2 >= MIN_LEVEL_NODES:
+            nodes //= 2
+        levels.append(nodes - 1)
+    return levels[::-1]
+
+
+def check_spacetime_levels(levels, n_time, n_geometries):
+    """The levels as a list of ints: one per geometry, at least one interval each, never decreasing, ending in ``n_time``."""
+    if levels is None:
+        return default_spacetime_levels(n_time, n_geometries)
+    try:
+        out = [int(x) for x in levels]
+    except (TypeError, ValueError):
+        raise ValueError("levels must be a list of n_time values, one per geometry") from None
+    if any(int(a) != a for a in levels):
+        raise ValueError("levels must be a list of integers")
+    if len(out) != int(n_geometries):
+        raise ValueError(f"levels: one n_time per geometry ({int(n_geometries)}), got {len(out)}")
+    if out[0] < 1:
+        raise ValueError("levels: every level needs n_time >= 1")
+    if any(b < a for a, b in zip(out, out[1:])):
+        raise ValueError(f"levels must not decrease (got {out})")
+    if out[-1] != int(n_time):
+        raise ValueError(f"the last level must be n_time = {int(n_time)} (got {out[-1]})")
+    return out

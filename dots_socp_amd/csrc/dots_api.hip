@@ -1399,8 +1399,8 @@ int dots_bench_many(dots_ctx *const *cs, int n, int reps, double *ms) {
     return 0;
 }
 
-// ---- carrying the state from one context to another (dots_prolong_time, dots_prolong_space, dots_transfer_space) ------------------
-// What the three entry points share.  An entry point calls carry_guard, validates its descriptor -- a bad argument leaves both contexts
+// ---- carrying the state from one context to another (dots_prolong_time, dots_prolong_space, dots_transfer_space, dots_carry_spacetime) --
+// What the four entry points share.  An entry point calls carry_guard, validates its descriptor -- a bad argument leaves both contexts
 // untouched --, lists its tables and calls carry_state with a callable that launches one array.  carry_state brings the source up to
 // date, prepares the destination, puts the tables one after another into one device buffer (doubles first keeps them aligned) and,
 // with both streams ordered, calls launch(array id, factor) for each of the twelve arrays.  The order is the protocol: the destination's
@@ -1558,6 +1558,58 @@ int dots_transfer_space(dots_ctx *dst, dots_ctx *src, const dots_transfer_space_
     CarryTable tab[] = {{desc->vw, sizeof(double) * nv}, {desc->vsrc, sizeof(int32_t) * nv}, {desc->fsrc, sizeof(int32_t) * nf}, {desc->csrc, sizeof(int32_t) * 3 * nf}};
     return carry_state(who, "table", dst, src, desc->factor, desc->ms, tab, [&](int id, double f) {
         return launch_carry_space(dst, src, id, tab[1].at<int>(), tab[0].at<double>(), tab[2].at<int>(), tab[3].at<int>(), 1, f, who);
+    });
+}
+
+int dots_carry_spacetime(dots_ctx *dst, dots_ctx *src, const dots_carry_spacetime_desc *desc) {
+    const char *who = "carry_spacetime";
+    int rc = carry_guard(who, dst, src, desc);
+    if (rc) return rc;
+    const Dev &dd = dst->d, &ds = src->d;
+    char buf[240];
+    if (dd.T == ds.T) {
+        snprintf(buf, sizeof buf, "carry_spacetime: both contexts have n_time = %d: on one time grid the carriers in space (dots_prolong_space, "
+                                  "dots_transfer_space) are the definition", dd.T);
+        set_error(buf);
+        return DOTS_ERR_ARGUMENT;
+    }
+    if (!desc->node_j || !desc->node_w || !desc->interval_j || !desc->interval_w || !desc->vsrc || !desc->fsrc) { set_error("carry_spacetime: null table"); return DOTS_ERR_ARGUMENT; }
+    if (desc->n_vertices != dd.V || desc->n_triangles != dd.F) {
+        snprintf(buf, sizeof buf, "carry_spacetime: tables of %d vertices and %d triangles, the destination has %d and %d", desc->n_vertices, desc->n_triangles, dd.V, dd.F);
+        set_error(buf);
+        return DOTS_ERR_ARGUMENT;
+    }
+    // every time-table entry names two source time points of the row it reads (as dots_prolong_time checks them)
+    const int nn = dd.T + 1, ni = dd.T;
+    for (int t = 0; t < nn + ni; ++t) {
+        const bool node = t < nn;
+        const int j = node ? desc->node_j[t] : desc->interval_j[t - nn];
+        const double w = node ? desc->node_w[t] : desc->interval_w[t - nn];
+        const int top = std::max((node ? ds.T + 1 : ds.T) - 2, 0);
+        if (j < 0 || j > top || !(w >= 0.0 && w <= 1.0)) {
+            snprintf(buf, sizeof buf, "carry_spacetime: %s table entry %d (j = %d, w = %g) out of range (0 <= j <= %d, 0 <= w <= 1)", node ? "node" : "interval",
+                     node ? t : t - nn, j, w, top);
+            set_error(buf);
+            return DOTS_ERR_ARGUMENT;
+        }
+    }
+    // every index names a row / a corner of the source; every weight is a finite number >= 0 (as the carriers in space check them)
+    const size_t per = desc->vw ? 3 : 2, nv = per * (size_t)dd.V, nf = (size_t)dd.F;
+    for (size_t i = 0; i < nv; ++i) {
+        if (desc->vsrc[i] < 0 || desc->vsrc[i] >= ds.V) { set_error("carry_spacetime: vsrc entry out of range"); return DOTS_ERR_ARGUMENT; }
+        if (desc->vw && !(desc->vw[i] >= 0.0 && std::isfinite(desc->vw[i]))) { set_error("carry_spacetime: a weight that is negative or not finite"); return DOTS_ERR_ARGUMENT; }
+    }
+    for (size_t i = 0; i < nf; ++i)
+        if (desc->fsrc[i] < 0 || desc->fsrc[i] >= ds.F) { set_error("carry_spacetime: fsrc entry out of range"); return DOTS_ERR_ARGUMENT; }
+    for (size_t i = 0; desc->csrc && i < 3 * nf; ++i)
+        if (desc->csrc[i] < 0 || desc->csrc[i] > 2) { set_error("carry_spacetime: csrc entry outside 0 .. 2"); return DOTS_ERR_ARGUMENT; }
+    CarryTable tab[] = {{desc->node_w, sizeof(double) * (size_t)nn}, {desc->interval_w, sizeof(double) * (size_t)ni}, {desc->vw, desc->vw ? sizeof(double) * nv : 0},
+                        {desc->node_j, sizeof(int32_t) * (size_t)nn}, {desc->interval_j, sizeof(int32_t) * (size_t)ni}, {desc->vsrc, sizeof(int32_t) * nv},
+                        {desc->fsrc, sizeof(int32_t) * nf}, {desc->csrc, desc->csrc ? sizeof(int32_t) * 3 * nf : 0}};
+    return carry_state(who, "table", dst, src, desc->factor, desc->ms, tab, [&](int id, double f) {
+        const int i = (array_kind(id) == 0 || array_kind(id) == 2) ? 0 : 1;      // the node tables, or the interval tables
+        return launch_carry_spacetime(dst, src, id, tab[3 + i].at<int>(), tab[i].at<double>(), tab[5].at<int>(), tab[2].at<double>(), tab[6].at<int>(),
+                                      tab[7].at<int>(), f);
     });
 }
 

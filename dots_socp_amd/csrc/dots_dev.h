@@ -300,6 +300,8 @@ int launch_from_device_layout(Ctx *c, int array_id, double *staged);
 int launch_prolong(Ctx *dst, Ctx *src, int array_id, const int *jt, const double *wt, const int *vmap, const int *fmap, double factor);
 int launch_carry_space(Ctx *dst, Ctx *src, int array_id, const int *vsrc, const double *vw, const int *fsrc, const int *csrc, int group,
                        double factor, const char *who);
+int launch_carry_spacetime(Ctx *dst, Ctx *src, int array_id, const int *jt, const double *wt, const int *vsrc, const double *vw, const int *fsrc,
+                           const int *csrc, double factor);
 int launch_operator(Ctx *c, int op, double scale, const double *in_staged, double *out_staged);
 int launch_calibration(Ctx *c, double *bytes_each_way);
 int cg_solve(Ctx *c, dots_step_stats *stats, bool defer_inverse = false);   // defer_inverse: phi is produced by the caller (soc_takes_inverse)

@@ -1626,6 +1626,161 @@ int launch_carry_space(Ctx *dst, Ctx *src, int id, const int *vsrc, const double
 }
 
 // ------------------------------------------------------------------------------------------
+// state carry in space and time at once (dots_carry_spacetime): one state array of a context on another mesh AND another time grid
+// ------------------------------------------------------------------------------------------
+// The composition of the two carriers above without the context in between: space first, then time (cascade.carry_spacetime).  A
+// workgroup stages the two time tables once, as k_prolong does, then walks passes of R destination rows in two phases.  Phase 1 forms
+// each row of the pass ON THE SOURCE'S TIME GRID with the row arithmetic and the formulas of k_carry_space (the recovery factor f
+// first; the nested and the located vertex formulas are separate instantiations, as there) from 16-byte loads at the source pitch, and
+// writes it into the LDS row k_prolong would have staged: what the space carrier would have left in a context on the destination's mesh
+// at the source's n_time never reaches memory.  Phase 2 is k_prolong's second loop on those rows without f (it was applied in phase
+// 1): (1 - w[t]) * x[j[t]] + w[t] * x[min(j[t] + 1, ns - 1)], two destination columns per lane, one 16-byte store; a corner row is read
+// at offset s and placed at t + s; every column outside the array's time points is written as zero.  Only columns j < ns of an LDS row
+// are read, so what phase 1 leaves in the source's padding columns is never used.  LDS rows are TPs + 2 doubles apart as in k_prolong:
+// an even number, so that phase 1's 16-byte writes stay aligned and neighbouring lanes write neighbouring words (no bank is hit twice),
+// and not a power of two, so that in phase 2 lane groups on neighbouring rows read other banks.
+struct CarrySpacetimeArgs {
+    const double *src;
+    double *dst;
+    const int *jt;           // [nd] source time point of every destination time point
+    const double *wt;        // [nd] weight of source point j + 1
+    const int *vsrc;         // vertex rows: [entities][2] (nested) or [entities][3] (located) source vertex rows
+    const double *vw;        // located vertex rows: [entities][3] weights
+    const int *fsrc;         // triangle and corner rows: [entities] source triangle
+    const int *csrc;         // corner rows: [entities][3] source corner of every destination corner, or null: the same corner
+    int64_t rows;            // destination rows
+    int nd, ns;              // destination / source time points of this array's grid
+    int sh_d, sh_s;          // log2 of the destination / source pitch
+    int R;                   // rows per pass
+    double f;
+};
+
+// RPE, LOCATED: as for k_carry_space
+template <int RPE, bool LOCATED = false>
+__global__ __launch_bounds__(BLOCK) void k_carry_spacetime(CarrySpacetimeArgs a) {
+    __shared__ __attribute__((aligned(16))) double xs[PROLONG_XS + 2 * PROLONG_RMAX];
+    __shared__ double ws[PROLONG_NT];
+    __shared__ int js[PROLONG_NT];
+    const int tid = threadIdx.x;
+    const int TPs = 1 << a.sh_s, SP = TPs + 2;
+    const int hs = a.sh_s - 1, hd = a.sh_d - 1;     // log2 of the column pairs per source / destination row
+    for (int t = tid; t < a.nd; t += BLOCK) {
+        js[t] = a.jt[t];
+        ws[t] = a.wt[t];
+    }
+    const int64_t n_pass = (a.rows + a.R - 1) / a.R;
+    for (int64_t pass = blockIdx.x; pass < n_pass; pass += gridDim.x) {
+        const int64_t base = pass * a.R;
+        __syncthreads();      // the tables are staged / the previous pass has read its rows
+        // phase 1: space, source rows -> LDS
+        for (int e = tid; e < (a.R << hs); e += BLOCK) {
+            const int rr = e >> hs, p = e & ((1 << hs) - 1);
+            const int64_t r = base + rr;
+            if (r >= a.rows) continue;
+            int64_t r0, r1 = 0, r2 = 0;             // source rows: one, or the 2 / 3 of a vertex row
+            double w0 = 0.0, w1 = 0.0, w2 = 0.0;
+            if (RPE == 1 && LOCATED) {
+                const int *v = a.vsrc + 3 * r;
+                const double *w = a.vw + 3 * r;
+                r0 = v[0], r1 = v[1], r2 = v[2];
+                w0 = w[0], w1 = w[1], w2 = w[2];
+            } else if (RPE == 1) {
+                r0 = a.vsrc[2 * r];
+                r1 = a.vsrc[2 * r + 1];
+            } else {
+                const int64_t ent = r / RPE;
+                const int sub = (int)(r - ent * RPE);
+                r0 = a.fsrc[ent];
+                if (RPE == 18) {      // sub = (k * 2 + s) * 3 + c
+                    const int k = sub / 6, rest = sub - 6 * k;
+                    r0 = (r0 * 3 + (a.csrc ? a.csrc[3 * ent + k] : k)) * 6 + rest;
+                } else {
+                    r0 = r0 * 3 + sub;
+                }
+            }
+            const D2 v0 = ld2(a.src + (r0 << a.sh_s) + 2 * p);
+            D2 out;
+            if (RPE == 1 && LOCATED) {
+                const D2 v1 = ld2(a.src + (r1 << a.sh_s) + 2 * p), v2 = ld2(a.src + (r2 << a.sh_s) + 2 * p);
+#pragma unroll
+                for (int q = 0; q < 2; ++q) out.v[q] = (w0 * (a.f * v0.v[q]) + w1 * (a.f * v1.v[q])) + w2 * (a.f * v2.v[q]);
+            } else if (RPE == 1 && r0 != r1) {
+                const D2 v1 = ld2(a.src + (r1 << a.sh_s) + 2 * p);
+#pragma unroll
+                for (int q = 0; q < 2; ++q) out.v[q] = (a.f * v0.v[q] + a.f * v1.v[q]) * 0.5;
+            } else {
+#pragma unroll
+                for (int q = 0; q < 2; ++q) out.v[q] = a.f * v0.v[q];
+            }
+            st2(xs + rr * SP + 2 * p, out);
+        }
+        __syncthreads();
+        // phase 2: time, LDS -> destination rows
+        for (int e = tid; e < (a.R << hd); e += BLOCK) {
+            const int rr = e >> hd, p = e & ((1 << hd) - 1);
+            const int64_t r = base + rr;
+            if (r >= a.rows) continue;
+            const int s = RPE == 18 ? (int)((r / 3) & 1) : 0;
+            const double *x = xs + rr * SP + s;
+            D2 y;
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int t = 2 * p + q - s;      // time point of this column
+                double v = 0.0;
+                if (t >= 0 && t < a.nd) {
+                    const int j = js[t], j1 = min(j + 1, a.ns - 1);
+                    const double w = ws[t];
+                    v = (1.0 - w) * x[j] + w * x[j1];
+                }
+                y.v[q] = v;
+            }
+            st2(a.dst + (r << a.sh_d) + 2 * p, y);
+        }
+    }
+}
+
+// vw null: the nested vertex formula (vsrc [V][2]), else the located one (vsrc, vw [V][3])
+int launch_carry_spacetime(Ctx *dst, Ctx *src, int id, const int *jt, const double *wt, const int *vsrc, const double *vw, const int *fsrc,
+                           const int *csrc, double f) {
+    const Dev &dd = dst->d, &ds = src->d;
+    const int kind = array_kind(id);
+    CarrySpacetimeArgs a{};
+    a.src = src->arr(id);
+    a.dst = dst->arr(id);
+    a.jt = jt;
+    a.wt = wt;
+    a.vsrc = vsrc;
+    a.vw = vw;
+    a.fsrc = fsrc;
+    a.csrc = csrc;
+    const int rpe = kind <= 1 ? 1 : (kind == 2 ? 3 : 18);
+    a.rows = (int64_t)rpe * (kind <= 1 ? dd.V : dd.F);
+    const int node = kind == 0 || kind == 2;
+    a.nd = dd.T + node;
+    a.ns = ds.T + node;
+    a.sh_d = dd.tp_shift;
+    a.sh_s = ds.tp_shift;
+    a.f = f;
+    if (a.nd > PROLONG_NT || a.sh_s < 1 || a.sh_s > 12 || a.sh_d < 1 || a.sh_d > 12 || (1 << a.sh_s) > PROLONG_XS) {
+        set_error("carry_spacetime: time pitch out of range");
+        return DOTS_ERR_STATE;
+    }
+    a.R = std::max(1, std::min(std::min(PROLONG_RMAX, (4 * BLOCK) >> (a.sh_d - 1)), PROLONG_XS >> a.sh_s));      // (k_prolong's)
+    // nested: the four children of a triangle (and the vertices the subdivision numbers with them) read the same source rows: a pass
+    // takes whole groups of four where R holds one (the corner arrays' 72 rows never fit: their passes stay at R)
+    const int unit = 4 * rpe;
+    if (!vw && a.R >= unit) a.R -= a.R % unit;
+    const int64_t n_pass = (a.rows + a.R - 1) / a.R;
+    const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(n_pass, 1024)));
+    if (rpe == 1 && vw) hipLaunchKernelGGL((k_carry_spacetime<1, true>), grid, dim3(BLOCK), 0, dst->stream, a);
+    else if (rpe == 1) hipLaunchKernelGGL(k_carry_spacetime<1>, grid, dim3(BLOCK), 0, dst->stream, a);
+    else if (rpe == 3) hipLaunchKernelGGL(k_carry_spacetime<3>, grid, dim3(BLOCK), 0, dst->stream, a);
+    else hipLaunchKernelGGL(k_carry_spacetime<18>, grid, dim3(BLOCK), 0, dst->stream, a);
+    DOTS_HIP(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
 // standalone operators (rows a4-a6): same index arithmetic as the fused kernels, exposed so each
 // reference function has a one-to-one parity test.  in/out are device-layout scratch arrays.
 // ------------------------------------------------------------------------------------------

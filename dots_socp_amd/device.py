@@ -271,6 +271,46 @@ class DeviceProblem:
         self.prolong_bytes = 8 * self._state_pitch() * (8 * 4 * self.V + (2 * 3 + 2 * 18) * 2 * self.F)
         return ms
 
+    def carry_spacetime_from(self, src: "DeviceProblem", factors=(1.0, 1.0, 1.0, 1.0), parents=None, transfer=None):
+        """Fill this context's twelve state arrays from those of ``src``, a context on another mesh -- the parent mesh of this one
+        (``parents``: ``meshes.subdivide``) or another triangulation of the same surface (``transfer``: ``cascade.mesh_transfer``),
+        exactly one of the two -- AND at another ``n_time``, on the same device, in one pass (dots_carry_spacetime;
+        cascade.carry_spacetime is the specification: space first, then time).  ``factors``: as for ``prolong_from``.  Returns the
+        milliseconds of the launches; ``self.prolong_bytes``: one pass over this context's state at its own pitch, plus the source
+        rows at the source's pitch -- nested, the source's state once (siblings share their source rows); located, three source rows
+        per vertex row and one per triangle / corner row, every read counted."""
+        from . import cascade
+
+        def describe():
+            cascade._one_map("carry_spacetime_from", parents, transfer)
+            if self.T == src.T:
+                raise ValueError(f"carry_spacetime_from: both contexts have n_time = {self.T}: on one time grid prolong_space_from / "
+                                 "transfer_space_from are the definition")
+            if parents is not None:
+                vp, tp = cascade.check_parents(parents, n_vertices=src.V, n_triangles=src.F)
+                size = (vp.shape[0], tp.shape[0])
+                vsrc, fsrc = cascade.space_row_maps(parents, src.V, src.F, self.plan.perm_vert, self.plan.perm_tri, src.plan.perm_vert, src.plan.perm_tri)
+                vw = csrc = None
+            else:
+                vs, _, ts, _ = cascade.check_transfer(transfer, n_vertices=src.V, n_triangles=src.F)
+                size = (vs.shape[0], ts.shape[0])
+                vsrc, vw, fsrc, csrc = cascade.transfer_row_maps(transfer, self.plan.perm_vert, self.plan.perm_tri, src.plan.perm_vert, src.plan.perm_tri)
+            if size != (self.V, self.F):
+                raise ValueError(f"carry_spacetime_from: a map to a mesh with V, F = {size[0]}, {size[1]}, this one has {self.V}, {self.F}")
+            nj, nw = cascade.time_weights(src.T, self.T, node=True)
+            ij, iw = cascade.time_weights(src.T, self.T, node=False)
+            d = _lib.CarrySpacetimeDesc()
+            d.node_j, d.node_w, d.interval_j, d.interval_w = _ptr(nj, C.c_int32), _ptr(nw, C.c_double), _ptr(ij, C.c_int32), _ptr(iw, C.c_double)
+            d.vsrc, d.vw, d.fsrc, d.csrc = _ptr(vsrc, C.c_int32), _ptr(vw, C.c_double), _ptr(fsrc, C.c_int32), _ptr(csrc, C.c_int32)
+            d.n_vertices, d.n_triangles = self.V, self.F
+            return d, (nj, nw, ij, iw, vsrc, vw, fsrc, csrc)
+
+        ms = self._carry_from("carry_spacetime_from", src, "dots_carry_spacetime", describe, factors, same_grid=False)
+        rows = 8 * self.V + (2 * 3 + 2 * 18) * self.F
+        src_rows = 8 * src.V + (2 * 3 + 2 * 18) * src.F if parents is not None else 8 * 3 * self.V + (2 * 3 + 2 * 18) * self.F
+        self.prolong_bytes = 8 * (self._state_pitch() * rows + src._state_pitch() * src_rows)
+        return ms
+
     # ---- the hot loop
     def step(self, n_iters=1, wait=True):
         """``wait=False``: only enqueue (direct solver); returns None, nothing is timed."""

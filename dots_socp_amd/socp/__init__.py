@@ -5,6 +5,8 @@
 ``solver_raw_many`` / ``solver_many``   the same for several problems on one surface with one shared factor (solver_socp_many)
 ``solver_raw_cascade`` / ``solver_cascade``   the same through a coarse-to-fine cascade in time (solver_socp_cascade)
 ``solver_raw_mesh_cascade`` / ``solver_mesh_cascade``   the same through a coarse-to-fine cascade in space (solver_socp_mesh_cascade)
+``solver_raw_spacetime_cascade`` / ``solver_spacetime_cascade``   the same through a cascade in space and time at once
+                                                                  (solver_socp_spacetime_cascade)
 
 Both take ``(n_time, geometry, **kwargs)`` and return ``(solution, run_history)``; they can be
 passed as ``solver=`` to the reference's ``run_dot_surface`` (interface.py:106-134).
@@ -16,11 +18,12 @@ the whole solution and converts it in numpy: the same values bit for bit, kept a
 """
 import numpy as np
 
-from .solver_socp import solver_socp, solver_socp_cascade, solver_socp_many, solver_socp_mesh_cascade
+from .solver_socp import solver_socp, solver_socp_cascade, solver_socp_many, solver_socp_mesh_cascade, solver_socp_spacetime_cascade
 
 __all__ = ["solver_socp", "solver_raw", "solver", "solver_socp_many", "solver_raw_many", "solver_many",
            "solver_socp_cascade", "solver_raw_cascade", "solver_cascade",
-           "solver_socp_mesh_cascade", "solver_raw_mesh_cascade", "solver_mesh_cascade"]
+           "solver_socp_mesh_cascade", "solver_raw_mesh_cascade", "solver_mesh_cascade",
+           "solver_socp_spacetime_cascade", "solver_raw_spacetime_cascade", "solver_spacetime_cascade"]
 
 
 def _socp_to_dot(solution_socp, geom):
@@ -137,10 +140,10 @@ def solver_cascade(n_time, geometry, readout="device", **kwargs):
 solver_cascade.__name__ = "dot_solver_socp_cascade_center"
 
 
-def _finest(geometries):
+def _finest(geometries, who="solver_socp_mesh_cascade"):
     geometries = list(geometries)
     if not geometries:
-        raise ValueError("solver_socp_mesh_cascade: at least two geometries")
+        raise ValueError(f"{who}: at least two geometries")
     return geometries, geometries[-1]
 
 
@@ -165,6 +168,29 @@ def solver_mesh_cascade(n_time, geometries, readout="device", **kwargs):
 
 
 solver_mesh_cascade.__name__ = "dot_solver_socp_mesh_cascade_center"
+
+
+def solver_raw_spacetime_cascade(n_time, geometries, readout="device", **kwargs):
+    """``solver_raw`` on the finest of ``geometries`` through the cascade in space and time (``solver_socp_spacetime_cascade``: ``levels``,
+    ``level_tol`` and the keywords of ``solver_socp``)."""
+    geometries, fine = _finest(geometries, "solver_socp_spacetime_cascade")
+    solution_socp, run_history = solver_socp_spacetime_cascade(n_time, geometries, read_out=_read_out_spec(readout, False), **kwargs)
+    return _finish(solution_socp, fine, None, None, readout, False), run_history
+
+
+solver_raw_spacetime_cascade.__name__ = "dot_solver_socp_spacetime_cascade"
+
+
+def solver_spacetime_cascade(n_time, geometries, readout="device", **kwargs):
+    """``solver`` on the finest of ``geometries`` through the cascade in space and time: the density on the time-centred grid with the
+    finest level's mu0 / mu1 as end points."""
+    geometries, fine = _finest(geometries, "solver_socp_spacetime_cascade")
+    mu0, mu1 = _end_points(fine)
+    solution_socp, run_history = solver_socp_spacetime_cascade(n_time, geometries, read_out=_read_out_spec(readout, True), **kwargs)
+    return _finish(solution_socp, fine, mu0, mu1, readout, True), run_history
+
+
+solver_spacetime_cascade.__name__ = "dot_solver_socp_spacetime_cascade_center"
 
 
 def solver_raw_many(n_time, geometry, problems, readout="device", **kwargs):

@@ -71,9 +71,10 @@ def _validate_checkpoints(tol_checkpoints, tol):
     return sorted(tol_checkpoints, reverse=True)
 
 
-def _state_carrier(n_time, init_from, init_solution, time_slab, init_parents, init_transfer):
+def _state_carrier(n_time, init_from, init_solution, time_slab, init_parents, init_transfer, init_regrid=False):
     """How a solver's state comes from ``init_from``, validated before any device call: None without ``init_from``, else ``carry(dev)``,
-    which fills the DeviceProblem ``dev`` and returns the milliseconds -- in space over ``init_parents`` / ``init_transfer``, else in time."""
+    which fills the DeviceProblem ``dev`` and returns the milliseconds -- in space over ``init_parents`` / ``init_transfer`` (with
+    ``init_regrid`` also from another ``n_time``: space and time in one pass), else in time."""
     if init_transfer is not None and init_parents is not None:
         raise ValueError("init_transfer and init_parents are mutually exclusive: the level below is a located mesh or the parent mesh")
     space = None      # (option, which mesh init_from is on, the DeviceProblem method, its map)
@@ -81,6 +82,8 @@ def _state_carrier(n_time, init_from, init_solution, time_slab, init_parents, in
         space = ("init_parents", "parent", "prolong_space_from", init_parents)
     elif init_transfer is not None:
         space = ("init_transfer", "coarse", "transfer_space_from", init_transfer)
+    if init_regrid and space is None:
+        raise ValueError("init_regrid needs init_parents or init_transfer: on one mesh init_from alone changes the time grid")
     if init_from is None:
         if space:
             raise ValueError(f"{space[0]} needs init_from (the solver on the {space[1]} mesh)")
@@ -95,6 +98,9 @@ def _state_carrier(n_time, init_from, init_solution, time_slab, init_parents, in
         return lambda dev: dev.prolong_from(init_from.dev, init_from.recovery_factors())
     option, mesh, method, table = space
     if int(init_from.n_time) != int(n_time):
+        if init_regrid:      # (the fused carrier; on one time grid the carrier in space below is the definition)
+            maps = {"parents": table} if option == "init_parents" else {"transfer": table}
+            return lambda dev: dev.carry_spacetime_from(init_from.dev, init_from.recovery_factors(), **maps)
         raise ValueError(f"{option}: the {mesh} mesh's solver has n_time = {int(init_from.n_time)}, this one {int(n_time)}: "
                          "one call changes the mesh or the time grid, not both")
     return lambda dev: getattr(dev, method)(init_from.dev, table, init_from.recovery_factors())
@@ -113,7 +119,7 @@ class AlmSolver:
                  is_constant_scaling=False, check_kkt_step_by_step=False, init_solution=None, tol_checkpoints=None,
                  time_limit=1000, is_palm=False, lap_solver="modal_direct", cg_tol=DEFAULT_CG_TOL, cg_max_iter=20000, device=0, reorder=True,
                  preconditioner="multigrid", mg_coarsest=256, time_slab=None, nd_leaf=16, plan=None, front_owner=None, init_from=None,
-                 release_init_from=False, batched=None, init_parents=None, init_transfer=None):
+                 release_init_from=False, batched=None, init_parents=None, init_transfer=None, init_regrid=False):
         """``plan``: the device plan to use (geometry.plan_with_densities) instead of building one; ``front_owner``: a DeviceProblem
         whose factor this solver shares (dots_front_share) instead of building its own -- a member of a batch (solver_socp_many), stepped
         by ``step_batch``; the launch ahead of the right-hand side and of the penalty decision are off then.
@@ -128,10 +134,12 @@ class AlmSolver:
         triangulation of the same surface at the same ``n_time`` and this is ``cascade.mesh_transfer`` from its mesh to this one: its
         recovered solution is carried over barycentrically on the device (DeviceProblem.transfer_space_from;
         ``init_solution=cascade.transfer_space_solution(<its solution>, transfer)`` bit for bit), in the same order: transfer, release,
-        factor.  ``batched``: whether the solver is stepped by a batch (default: whenever ``plan`` or
+        factor.  ``init_regrid=True`` (with ``init_parents`` or ``init_transfer``) allows ``init_from`` at ANOTHER ``n_time``: mesh and time
+        grid change in one pass on the device (DeviceProblem.carry_spacetime_from; ``init_solution=cascade.carry_spacetime_solution(<its
+        solution>, ...)`` bit for bit: space first, then time); at the same ``n_time`` it changes nothing.  ``batched``: whether the solver is stepped by a batch (default: whenever ``plan`` or
         ``front_owner`` is given)."""
         check_time_nodes(n_time, lap_solver, time_slab)
-        carry = _state_carrier(n_time, init_from, init_solution, time_slab, init_parents, init_transfer)
+        carry = _state_carrier(n_time, init_from, init_solution, time_slab, init_parents, init_transfer, init_regrid)
         self.tol_checkpoints = _validate_checkpoints(tol_checkpoints, tol)
         self.geometry = geometry        # (read_out takes the area weights and mu0 / mu1 from it)
         self.checkpoint_solutions = []
@@ -888,7 +896,8 @@ def solver_socp_cascade(n_time, geometry, levels=None, level_tol=None, read_out=
     Returns ``(solution, run_history)`` of the finest level; ``run_history.running_time`` is that level's own, and
     ``run_history.solver_stats["cascade"]`` = {"levels": [one record per level: n_time, tol, iterations, running_time, setup_seconds,
     prolong_ms (device events; None on the coarsest level), cost, kkt_max], "total_seconds"} has the whole cascade.
-    ``read_out``: as for ``solver_socp``, for the finest level."""
+    ``read_out``: as for ``solver_socp``, for the finest level.  The mesh is the same on every level; ``solver_socp_spacetime_cascade``
+    coarsens the mesh along with the time grid."""
     from .. import geometry as geo
 
     levels, level_tol, opts = _cascade_options(n_time, levels, level_tol, kwargs)
@@ -998,8 +1007,7 @@ def solver_socp_mesh_cascade(n_time, geometries, level_tol=None, read_out=None, 
     holds per level, ``time_limit`` for the whole call (a level gets the time that is left), ``init_solution`` starts the coarsest
     level, ``tol_checkpoints`` belong to the finest level.  Every level starts as a warm start through ``init_solution`` does (r = 1,
     the initial z scaling, a fresh penalty schedule, validator and history); the coarse solver is released before the finer factor
-    is built.  A cascade in time and in space in one call is not supported: run the levels of ``solver_socp_cascade`` on one mesh,
-    or these on one time grid.
+    is built.  All levels have one time grid here; ``solver_socp_spacetime_cascade`` coarsens the time grid along with the mesh.
 
     Returns ``(solution, run_history)`` of the finest level; ``run_history.solver_stats["mesh_cascade"]`` = {"levels": [one record
     per level: n_vertices, n_triangles, tol, iterations, running_time, setup_seconds, prolong_ms and prolong_bytes (None on the coarsest
@@ -1036,6 +1044,82 @@ def solver_socp_mesh_cascade(n_time, geometries, level_tol=None, read_out=None, 
             coarse, alm = alm, None
         coarse.dev.sync()
         hist.solver_stats["mesh_cascade"] = {"levels": records, "total_seconds": time.perf_counter() - t_start}
+        return solution, hist
+    finally:
+        for a in (alm, coarse):
+            if a is not None:
+                a.close()
+
+
+# ---- coarse-to-fine cascade in space and time at once ----------------------------------------------------------------------------
+def _spacetime_cascade_options(n_time, geometries, levels, level_tol, kwargs):
+    """The checks of solver_socp_spacetime_cascade, before any device is touched: (geometries, levels, level_tol, options)."""
+    from .. import cascade
+
+    who = "solver_socp_spacetime_cascade"
+    try:
+        geometries, level_tol, opts = _mesh_cascade_options(geometries, level_tol, kwargs)
+    except ValueError as exc:
+        raise ValueError(str(exc).replace("solver_socp_mesh_cascade", who)) from None
+    levels = cascade.check_spacetime_levels(levels, n_time, len(geometries))
+    lap_solver = opts.get("lap_solver", "modal_direct")
+    if lap_solver != "modal_direct" and lap_solver not in _lib.LAP_SOLVERS:
+        raise ValueError(f"lap_solver must be one of {['modal_direct'] + list(_lib.LAP_SOLVERS)}")
+    for T in levels:
+        check_time_nodes(T, lap_solver)
+    if opts.get("preconditioner", "multigrid") not in ("multigrid", "jacobi"):
+        raise ValueError("preconditioner must be 'multigrid' or 'jacobi'")
+    return geometries, levels, level_tol, opts
+
+
+def solver_socp_spacetime_cascade(n_time, geometries, levels=None, level_tol=None, read_out=None, **kwargs):
+    """``solver_socp`` through a coarse-to-fine cascade in space AND time: the meshes ``geometries`` (coarse to fine, each level above the
+    first with ``parents`` or ``transfer``, as for ``solver_socp_mesh_cascade``) are solved on the time grids ``levels`` (one ``n_time`` per
+    geometry, never decreasing, the last one ``n_time``, each one valid for the Laplacian solver).  A level that is coarser in both
+    directions costs about an eighth of the one above it.  Where two neighbouring levels have one ``n_time`` the state is carried as
+    ``solver_socp_mesh_cascade`` carries it, so ``levels=[n_time] * len(geometries)`` is that driver bit for bit; where they differ,
+    mesh and time grid change in one pass on the device (AlmSolver ``init_regrid``; cascade.carry_spacetime is the specification: space
+    first, then time).  A step that changes the time grid alone, on one mesh, is ``solver_socp_cascade``'s.
+
+    ``levels=None``: from the finest level downward ``n_time + 1`` is halved per mesh level while it is even and the half stays >= 16
+    nodes, then held (127 with three meshes -> 31, 63, 127; 31 -> 15, 15, 31; 20 -> 20, 20).  Everything else is as for
+    ``solver_socp_mesh_cascade``: ``level_tol``, ``nit`` per level, ``time_limit`` for the whole call, ``init_solution`` for the coarsest
+    level, the coarse solver released before the finer factor is built.
+
+    Returns ``(solution, run_history)`` of the finest level; ``run_history.solver_stats["spacetime_cascade"]`` = {"levels": [the records of
+    ``solver_socp_mesh_cascade`` plus ``n_time``], "total_seconds"}.  ``read_out``: as for ``solver_socp``, for the finest level."""
+    geometries, levels, level_tol, opts = _spacetime_cascade_options(n_time, geometries, levels, level_tol, kwargs)
+    tol, nit = opts.pop("tol", 1e-4), int(opts.pop("nit", 1000))
+    time_limit = opts.pop("time_limit", 1000)
+    init_solution, checkpoints = opts.pop("init_solution", None), opts.pop("tol_checkpoints", None)
+    t_start = time.perf_counter()
+    records = []
+    coarse = alm = None
+    try:
+        for i, (T, geom) in enumerate(zip(levels, geometries)):
+            last = i + 1 == len(geometries)
+            t0 = time.perf_counter()
+            alm = AlmSolver(T, geom, nit=nit, tol=tol if last else level_tol, tol_checkpoints=checkpoints if last else None,
+                            init_solution=init_solution if i == 0 else None, init_from=coarse, init_parents=geom.get("parents") if i else None,
+                            init_transfer=geom.get("transfer") if i else None, init_regrid=bool(i) and T != levels[i - 1],
+                            release_init_from=True, time_limit=max(time_limit - (t0 - t_start), 0.0), **opts)
+            coarse = None      # (closed by the constructor as soon as the finer state was filled)
+            setup = time.perf_counter() - t0
+            for _ in range(nit):
+                if alm.iterate():
+                    break
+            solution, hist = alm.finalize(download=last, read_out=read_out if last else None)
+            records.append({"n_time": int(T), "n_vertices": int(alm.dev.V), "n_triangles": int(alm.dev.F), "tol": float(alm.tol),
+                            "iterations": int(alm.counter_main) + 1, "running_time": float(hist.running_time), "setup_seconds": float(setup),
+                            "prolong_ms": alm.prolong_ms, "prolong_bytes": getattr(alm.dev, "prolong_bytes", None),
+                            "cost": float(hist.history["Transportation cost"][-1]),
+                            "kkt_max": float(np.nanmax(np.asarray(hist.kkt_errors[-1], dtype=np.float64))),
+                            "device_bytes": int(hist.solver_stats["device_bytes"]),
+                            "transfer": None if i == 0 else ("nested" if geom.get("parents") is not None else "located"),
+                            "max_distance": _max_distance(geom) if i else None})
+            coarse, alm = alm, None
+        coarse.dev.sync()
+        hist.solver_stats["spacetime_cascade"] = {"levels": records, "total_seconds": time.perf_counter() - t_start}
         return solution, hist
     finally:
         for a in (alm, coarse):

@@ -572,6 +572,37 @@ typedef struct dots_transfer_space_desc {
 } dots_transfer_space_desc;
 int dots_transfer_space(dots_ctx *dst, dots_ctx *src, const dots_transfer_space_desc *desc);
 
+/* ---- cascade in space and time at once: the state of a context on another mesh AND another time grid ---------------------------
+ * dots_carry_spacetime fills the twelve state arrays of `dst` from those of `src`, a context on the parent mesh of `dst`'s (vw NULL:
+ * the formulas of dots_prolong_space) or on another triangulation of the same surface (vw given: those of dots_transfer_space), with
+ * ANOTHER n_time, on one device.  Space first, then time: every row of `dst` is formed on the source's time grid as the carrier in
+ * space forms it (f applied to the source values first), and that row is then interpolated linearly in time as dots_prolong_time
+ * does with a factor of 1: time point t takes (1 - w[t]) * x[j[t]] + w[t] * x[j[t] + 1].  The row on the source's time grid exists
+ * in on-chip memory only: no third context, one pass over the state.  The tables come from the caller (dots_socp_amd/cascade.py:
+ * time_weights, and space_row_maps or transfer_row_maps in the device numberings of the two contexts), so that the result is bit for
+ * bit what dots_upload of cascade.carry_spacetime leaves.  `src` and `dst` are treated as by dots_prolong_time (pending division,
+ * z_mid, what `dst` carried; stream order; the call returns when the destination is filled).
+ * DOTS_ERR_ARGUMENT: the SAME n_time (use dots_prolong_space / dots_transfer_space: on one grid they are the definition), dst == src,
+ * a NULL time table, vsrc or fsrc, n_vertices / n_triangles that are not the destination's V / F, a time-table entry out of range,
+ * a vsrc / fsrc entry that is no row of the source, a csrc entry outside 0 .. 2, a weight that is negative or not finite;
+ * DOTS_ERR_STATE: a time slab, contexts on different devices, a stale z_mid.  After an error both contexts are as they were. */
+typedef struct dots_carry_spacetime_desc {
+    const int32_t *node_j;       /* the four time tables, as in dots_prolong_desc                                          */
+    const double *node_w;
+    const int32_t *interval_j;
+    const double *interval_w;
+    const int32_t *vsrc;         /* vw NULL: [n_vertices][2] the two source vertex rows (equal: a copy), as dots_prolong_space_desc.vmap;
+                                    else [n_vertices][3] the three source vertex rows, as dots_transfer_space_desc.vsrc     */
+    const double *vw;            /* NULL (nested), or [n_vertices][3] the weights: finite, >= 0                            */
+    const int32_t *fsrc;         /* [n_triangles]   destination triangle -> source triangle                                */
+    const int32_t *csrc;         /* NULL (corner k stays corner k), or [n_triangles][3] corner k -> corner 0 .. 2 of fsrc  */
+    int32_t n_vertices;          /* entries of the tables in space: V and F of `dst`                                       */
+    int32_t n_triangles;
+    double factor[4];            /* as dots_prolong_desc.factor                                                            */
+    double *ms;                  /* NULL, or out: milliseconds of the launches on the device (events on dst's stream)     */
+} dots_carry_spacetime_desc;
+int dots_carry_spacetime(dots_ctx *dst, dots_ctx *src, const dots_carry_spacetime_desc *desc);
+
 /* ---- read-out of the transport: what the solver plug-ins return (mu, E), formed on the device ---------------------------------
  * dots_readout delivers mu and / or E as dots_download would (reference layouts, the caller's numbering), every value multiplied
  * first by `factor` (the recovered solution, solver_socp.py:397-405: r * dual_scale; 1 = the iterate) and then, where weights are
