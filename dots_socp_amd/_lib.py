@@ -27,7 +27,7 @@ EXPORTS = [
     "dots_abi_version", "dots_last_error", "dots_create", "dots_destroy", "dots_set_params", "dots_get_params",
     "dots_sync", "dots_upload", "dots_download", "dots_array_count", "dots_step", "dots_run_phase", "dots_kkt",
     "dots_objective", "dots_adjust_penalty", "dots_scale_z", "dots_scale_arrays", "dots_norm_square",
-    "dots_apply_operator", "dots_bench_kernel", "dots_device_bytes", "dots_mg_setup", "dots_mg_enable",
+    "dots_apply_operator", "dots_bench_kernel", "dots_device_bytes", "dots_mg_setup", "dots_mg_enable", "dots_mg_apply",
     "dots_slab_elems", "dots_slab_set_buffers", "dots_slab_stage", "dots_kkt_sums", "dots_kkt_sums_device", "dots_debug_counter", "dots_kkt_combine", "dots_objective_sums",
     "dots_objective_combine", "dots_front_launches", "dots_front_info", "dots_front_setup", "dots_front_enable", "dots_front_pitch", "dots_penalty_ahead", "dots_step_flags", "dots_step_times", "dots_stream_wait", "dots_tree_build", "dots_tree_nodes", "dots_tree_copy", "dots_tree_free",
     "dots_patch_order", "dots_assemble", "dots_assemble_nnz", "dots_assemble_copy", "dots_assemble_free", "dots_symbolic_build", "dots_symbolic_front_rows", "dots_symbolic_copy", "dots_symbolic_free",
@@ -48,6 +48,11 @@ class HipLibraryError(RuntimeError):
 ERR_ARGUMENT = -1
 ERR_STATE = -5
 ERR_MEMORY = -6
+
+# dots_debug_counter(11): the launches the last multigrid V-cycle took (include/dots_socp_hip.h)
+MG_PATH_COUNTER = 11
+MG_PATH = {"restrict_rows": 1, "restrict_flat": 2, "coarse_rows": 4, "coarse_flat": 8, "tail": 16, "post": 32, "down_above0": 64}
+MG_PATH_TAIL_LEVELS_SHIFT = 8
 
 
 _i32p = C.POINTER(C.c_int32)
@@ -284,6 +289,7 @@ def load(host_only=False):
     lib.dots_objective_combine.argtypes = [vp, _f64p, _f64p]
     lib.dots_mg_setup.argtypes = [vp, C.POINTER(MgDesc)]
     lib.dots_mg_enable.argtypes = [vp, C.c_int]
+    lib.dots_mg_apply.argtypes = [vp, _f64p, _f64p, _f64p, _i32p]
     lib.dots_front_setup.argtypes = [vp, C.POINTER(FrontDesc)]
     lib.dots_front_enable.argtypes = [vp, C.c_int]
     lib.dots_front_pitch.argtypes = [vp]

@@ -521,6 +521,7 @@ static void mg_release(Ctx *c) {
     for (int i = 0; i < c->n_mg_allocs; ++i) (void)hipFree(c->mg_allocs[i]);
     c->n_mg_allocs = 0;
     c->mg = MgDev{};
+    c->mg_path = 0;      // no cycle of this (or no) hierarchy yet
 }
 
 template <typename T>
@@ -1149,6 +1150,32 @@ int dots_mg_enable(dots_ctx *c, int on) {
     int rc = check(c);
     if (rc) return rc;
     c->use_mg = on ? 1 : 0;
+    if (!c->use_mg) c->mg_path = 0;      // Jacobi from here on: the last cycle's launches are no longer this context's
+    return 0;
+}
+
+// One V-cycle on a caller's residual (tests and diagnosis; the product path never calls it): the launches are cg_mg_apply's, i.e. mg_vcycle with
+// the PCG's own tiling.  The PCG vectors, partial rows and flags it writes are scratch between solves (kernels_cg.hip: cg_mg_apply).
+int dots_mg_apply(dots_ctx *c, const double *r, double *z, double *rz, const int32_t *frozen) {
+    int rc = check(c);
+    if (rc) return rc;
+    if (c->lap_solver != DOTS_LAP_MODAL_PCG) { set_error("mg_apply: the V-cycle belongs to the modal solver"); return DOTS_ERR_STATE; }
+    if (c->shard_stride != 0) { set_error("mg_apply: not on a time slab"); return DOTS_ERR_STATE; }
+    if (c->mg.nlev < 2) { set_error("mg_apply: no multigrid hierarchy on this context (dots_mg_setup)"); return DOTS_ERR_STATE; }
+    if (!r || !z || !rz) { set_error("mg_apply: null array"); return DOTS_ERR_ARGUMENT; }
+    const Dev &g = c->dcg;
+    const int64_t nh = array_count_host(c->d, DOTS_PHI);      // [n_modes][V], the layout of phi
+    for (int k = 0; k < FLAG_TOTAL; ++k) c->h_flags[k] = (k < g.cg_ncol && frozen && frozen[k]) ? 1 : 0;
+    DOTS_HIP(hipMemcpyAsync(g.flags, c->h_flags, sizeof(int) * FLAG_TOTAL, hipMemcpyHostToDevice, c->stream));
+    DOTS_HIP(hipMemcpyAsync(c->stage, r, sizeof(double) * (size_t)nh, hipMemcpyHostToDevice, c->stream));
+    Ctx tmp = *c;      // (the layout kernels write the array in the phi slot)
+    tmp.d.phi = g.cg_r;
+    if ((rc = launch_to_device_layout(&tmp, DOTS_PHI, c->stage))) return rc;
+    if ((rc = cg_mg_apply(c, rz))) return rc;
+    tmp.d.phi = g.cg_z;
+    if ((rc = launch_from_device_layout(&tmp, DOTS_PHI, c->stage))) return rc;
+    DOTS_HIP(hipMemcpyAsync(z, c->stage, sizeof(double) * (size_t)nh, hipMemcpyDeviceToHost, c->stream));
+    DOTS_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }
 
@@ -1801,6 +1828,7 @@ int64_t dots_debug_counter(dots_ctx *c, int which) {
         case 8: return c->front_many_split;           // ... of those, launches with fewer rhs than their chunk (many_launch halved: LDS or 1024-thread cap)
         case 9: return c->d2h_bytes;                  // bytes dots_download and dots_readout have copied device -> host
         case 10: return c->n_front_allocs;            // device allocations the installed factor holds (0 after front_release: also after a failed dots_front_setup)
+        case 11: return c->mg_path;                   // MG_PATH_* bits of the last V-cycle enqueued (dots_dev.h)
         default: return -1;
     }
 }

@@ -125,6 +125,13 @@ struct MgLevelDev {
     const double *ap_vK, *ap_vM, *ap_vP;     // ap_vP: P itself on the pattern of A P (zeros where absent)
     double *b, *bt, *t;                      // level vectors [n][TP]: rhs, D^-1 rhs / result, residual (level 0 borrows the PCG's r, z, Ap)
 };
+// Launches one V-cycle took (Ctx::mg_path, dots_debug_counter 11): a test pinned to one kernel asserts that it still runs there
+enum {
+    MG_PATH_RESTRICT_ROWS = 1, MG_PATH_RESTRICT_FLAT = 2, MG_PATH_COARSE_ROWS = 4, MG_PATH_COARSE_FLAT = 8, MG_PATH_TAIL = 16,
+    MG_PATH_POST = 32,           // k_mg_post: a level above the tail other than the finest
+    MG_PATH_DOWN_ABOVE0 = 64,    // k_mg_down on such a level (vM != nullptr)
+    MG_PATH_TAIL_LEVELS_SHIFT = 8      // levels inside k_mg_tail (1: the dense solve alone), bits 8-11
+};
 struct MgDev {
     int nlev = 0;
     MgLevelDev lv[10]{};
@@ -320,6 +327,7 @@ int front_solve_many(Ctx *const *cs, int n, const double *const *bhat, double *c
 void modes_forward(Ctx *c, const double *in, double *out, bool direct);   // the time transforms around step 1's solve (one GPU)
 void modes_inverse(Ctx *c, const double *x, double *phi, bool direct);
 int mg_vcycle(Ctx *c, const double *r, double *z, double *t0, double *rz_part, int nb, int ept, int vt, int G);  // enqueue z = MG(r); z holds D^-1 r on entry
+int cg_mg_apply(Ctx *c, double *rz);        // dots_mg_apply: one V-cycle on what dcg.cg_r holds, as the PCG launches it; rz[mode] = sum of the r.z partial rows
 int kkt_evaluate(Ctx *c, uint32_t mask, double *out);
 int kkt_sums(Ctx *c, uint32_t mask, double *sums);                          // the weighted sums of this context's time slab
 int kkt_sums_device(Ctx *c, uint32_t mask, double *device_sums);            // the same, left in the caller's device buffer (enqueue only)
@@ -392,6 +400,7 @@ struct Ctx {
     int last_cg_iters = 0;
     MgDev mg{};                   // multigrid preconditioner (nlev == 0: Jacobi only)
     int use_mg = 1;
+    int mg_path = 0;              // MG_PATH_* of the last mg_vcycle (0: none since mg_release / dots_mg_enable(0))
     int cg_graph_mg = -1;
     int kkt_two = 1;              // KKT sums with two nodes per lane (one GPU; DOTS_KKT_TWO=0: one)
     // DOTS_STEP_TIMED: phase events of enqueue-only steps, collected later by dots_step_times (no host wait in the loop)

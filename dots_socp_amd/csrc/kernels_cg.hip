@@ -45,6 +45,11 @@ __device__ __forceinline__ double shift_of(const Dev &d, int t) {
     if (MODAL) return d.sigma[t];
     return ((t == 0 || t == d.T) ? 1.0 : 2.0) / (d.h * d.h);
 }
+// 1 / D for vertex v and column t, D = diag K + (shift + eps) mass: the one Jacobi diagonal of k_cg_r0, k_cg_update and k_mg_entry
+template <bool MODAL>
+__device__ __forceinline__ double jacobi_dinv(const Dev &d, int v, int t, double eps) {
+    return 1.0 / (d.kdiag[v] + (shift_of<MODAL>(d, t) + eps) * d.mass_v[v]);
+}
 template <bool MODAL>
 __device__ __forceinline__ int n_cols(const Dev &d) { return MODAL ? d.cg_ncol : d.T + 1; }
 
@@ -314,7 +319,7 @@ __global__ __launch_bounds__(CG_NB) void k_cg_r0(Dev d, CgArgs a, const double *
             const int cidx = MODAL ? t : 0;
             const double bt = b[iv] - d.scal[S::BMEAN + cidx];
             const double r = bt - Kx[iv];
-            const double dinv = 1.0 / (d.kdiag[v] + (shift_of<MODAL>(d, t) + a.eps) * d.mass_v[v]);
+            const double dinv = jacobi_dinv<MODAL>(d, v, t, a.eps);
             const double z = dinv * r;
             d.cg_r[iv] = r;
             d.cg_z[iv] = z;   // Jacobi z; with multigrid it is the D^-1 r the V-cycle starts from
@@ -365,7 +370,7 @@ __global__ __launch_bounds__(CG_NB) void k_cg_update(Dev d, CgArgs a) {
             const int v = tile * a.vt + (e >> d.tp_shift), t = e & (d.TP - 1);
             if ((e >> d.tp_shift) >= a.vt || v >= d.V || t >= ncols) continue;
             const int iv = idxV(d, v, t);
-            const double dinv = 1.0 / (d.kdiag[v] + (shift_of<MODAL>(d, t) + a.eps) * d.mass_v[v]);
+            const double dinv = jacobi_dinv<MODAL>(d, v, t, a.eps);
             if (MODAL && frozen) {      // keep the frozen column's norm in the sum so its total stays put
                 const double r = d.cg_r[iv];
                 acc += r * dinv * r;
@@ -896,6 +901,40 @@ int cg_apply_operator(Ctx *c, const double *x, double *y) {
     a.out = y;
     hipLaunchKernelGGL((k_cg_apply<false, false>), dim3(a.G), dim3(a.nb), cg_lds_bytes(a.cap, a.vt, a.nb), c->stream, c->d, a);
     DOTS_HIP(hipGetLastError());
+    return 0;
+}
+
+// z = D^-1 r for every live column, D = diag K + (sigma + eps) mass: the state k_cg_update hands to the V-cycle
+__global__ __launch_bounds__(BLOCK) void k_mg_entry(Dev d, double eps) {
+    const int64_t n = (int64_t)d.V << d.tp_shift;
+    for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLOCK) {
+        const int v = (int)(i >> d.tp_shift), t = (int)(i & (d.TP - 1));
+        if (t >= d.cg_ncol) continue;
+        const double dinv = jacobi_dinv<true>(d, v, t, eps);
+        d.cg_z[i] = d.cg_r[i] * dinv;
+    }
+}
+
+// One V-cycle exactly as cg_core enqueues its first one (tests, diagnosis: dots_mg_apply; never on the product path): the caller left r in
+// dcg.cg_r and the frozen marks in dcg.flags.  z lands in dcg.cg_z; rz[mode] = the r.z partial rows the next k_cg_apply would re-reduce, summed.
+// Everything written here (cg_r, cg_z, cg_Ap, the parity-0 r.z rows, the level vectors, the flags) is rewritten by k_cg_r0 / k_cg_begin / the
+// first V-cycle of the next solve before it is read.
+int cg_mg_apply(Ctx *c, double *rz) {
+    const Dev &d = c->dcg;
+    const CgArgs a = make_args(c, true);
+    const int64_t n = (int64_t)d.V << d.tp_shift;
+    hipLaunchKernelGGL(k_mg_entry, dim3((unsigned)std::min<int64_t>((n + BLOCK - 1) / BLOCK, 4096)), dim3(BLOCK), 0, c->stream, d, a.eps);
+    int rc = mg_vcycle(c, d.cg_r, d.cg_z, d.cg_Ap, d.partials + part_rz(a, 0), a.nb, a.ept, a.vt, a.G);
+    if (rc) return rc;
+    collapse_if_needed(c, d, a, idx_rz(0));
+    std::vector<double> part((size_t)a.Gr * a.prow);
+    DOTS_HIP(hipMemcpyAsync(part.data(), d.partials + read_at(a, idx_rz(0)), sizeof(double) * part.size(), hipMemcpyDeviceToHost, c->stream));
+    DOTS_HIP(hipStreamSynchronize(c->stream));
+    for (int k = 0; k < a.nc; ++k) {
+        double s = 0.0;
+        for (int g = 0; g < a.Gr; ++g) s += part[(size_t)g * a.prow + k];
+        rz[k] = s;
+    }
     return 0;
 }
 

@@ -296,6 +296,7 @@ int mg_vcycle(Ctx *c, const double *r, double *z, double *t0, double *rz_part, i
     int first_tail = nl - 1;
     for (int l = 1; l < nl; ++l)
         if (m.lv[l].n <= MG_TAIL_ROWS && nl - l <= 8) { first_tail = l; break; }
+    int path = 0;   // which launches this cycle takes (MG_PATH_*, dots_debug_counter 11): host bookkeeping only
     // down sweep above the tail
     for (int l = 0; l < first_tail; ++l) {
         const MgLevelDev &L = m.lv[l];
@@ -304,15 +305,26 @@ int mg_vcycle(Ctx *c, const double *r, double *z, double *t0, double *rz_part, i
         const double *bt = (l == 0) ? z : L.bt;
         double *t = (l == 0) ? t0 : L.t;
         hipLaunchKernelGGL(k_mg_down, dim3(mg_grid(d, L.n)), dim3(MG_NB), 0, c->stream, d, L, a, b, bt, t);
-        if (L.nc <= 4096 && d.TP <= MG_NB / 2) hipLaunchKernelGGL(k_mg_restrict_rows, dim3(L.nc), dim3(MG_NB), 0, c->stream, d, L, a, t, C.dK, C.dM, C.b, C.bt);
-        else hipLaunchKernelGGL(k_mg_restrict, dim3(mg_grid(d, L.nc)), dim3(MG_NB), 0, c->stream, d, L, a, t, C.dK, C.dM, C.b, C.bt);
+        if (l > 0) path |= MG_PATH_DOWN_ABOVE0;
+        if (L.nc <= 4096 && d.TP <= MG_NB / 2) {
+            hipLaunchKernelGGL(k_mg_restrict_rows, dim3(L.nc), dim3(MG_NB), 0, c->stream, d, L, a, t, C.dK, C.dM, C.b, C.bt);
+            path |= MG_PATH_RESTRICT_ROWS;
+        } else {
+            hipLaunchKernelGGL(k_mg_restrict, dim3(mg_grid(d, L.nc)), dim3(MG_NB), 0, c->stream, d, L, a, t, C.dK, C.dM, C.b, C.bt);
+            path |= MG_PATH_RESTRICT_FLAT;
+        }
     }
     // the tail (at least the dense coarsest solve): one workgroup per column; a large coarsest level on
     // its own is solved by the flat kernel instead (one thread per entry, coalesced over the columns)
     if (first_tail == nl - 1 && m.lv[nl - 1].n > 64) {
         const MgLevelDev &L = m.lv[nl - 1];
-        if (d.TP <= MG_NB / 2) hipLaunchKernelGGL(k_mg_coarse_rows, dim3(L.n), dim3(MG_NB), 0, c->stream, d, a, L.n, m.coarse_inv, L.b, L.bt);
-        else hipLaunchKernelGGL(k_mg_coarse, dim3(mg_grid(d, L.n)), dim3(MG_NB), 0, c->stream, d, a, L.n, m.coarse_inv, L.b, L.bt);
+        if (d.TP <= MG_NB / 2) {
+            hipLaunchKernelGGL(k_mg_coarse_rows, dim3(L.n), dim3(MG_NB), 0, c->stream, d, a, L.n, m.coarse_inv, L.b, L.bt);
+            path |= MG_PATH_COARSE_ROWS;
+        } else {
+            hipLaunchKernelGGL(k_mg_coarse, dim3(mg_grid(d, L.n)), dim3(MG_NB), 0, c->stream, d, a, L.n, m.coarse_inv, L.b, L.bt);
+            path |= MG_PATH_COARSE_FLAT;
+        }
     } else {
         MgTail T{};
         T.first = first_tail;
@@ -320,6 +332,7 @@ int mg_vcycle(Ctx *c, const double *r, double *z, double *t0, double *rz_part, i
         for (int l = first_tail; l < nl; ++l) T.lv[l - first_tail] = m.lv[l];
         T.coarse_inv = m.coarse_inv;
         hipLaunchKernelGGL(k_mg_tail, dim3(d.cg_ncol), dim3(MG_TAIL_NB), 0, c->stream, d, T, a);
+        path |= MG_PATH_TAIL | ((nl - first_tail) << MG_PATH_TAIL_LEVELS_SHIFT);
     }
     // up sweep above the tail: level l's result is written over its bt
     for (int l = first_tail - 1; l >= 0; --l) {
@@ -327,9 +340,12 @@ int mg_vcycle(Ctx *c, const double *r, double *z, double *t0, double *rz_part, i
         const double *xc = m.lv[l + 1].bt;
         if (l == 0)
             hipLaunchKernelGGL(k_mg_post_fine, dim3(G), dim3(nb), 0, c->stream, d, L, a, r, z, t0, xc, z, rz_part, ept, vt);
-        else
+        else {
             hipLaunchKernelGGL(k_mg_post, dim3(mg_grid(d, L.n)), dim3(MG_NB), 0, c->stream, d, L, a, L.bt, L.t, xc, L.bt);
+            path |= MG_PATH_POST;
+        }
     }
+    c->mg_path = path;
     DOTS_HIP(hipGetLastError());
     return 0;
 }

@@ -541,8 +541,32 @@ class DeviceProblem:
         desc.levels = lv
         desc.coarse_inverse = _ptr(arr(inv, np.float64), C.c_double)
         _lib.check(self.lib.dots_mg_setup(self._h, C.byref(desc)), "dots_mg_setup")
+        self.mg_levels = levels      # exactly what was uploaded (the plan's vertex numbering): the host reference of mg_apply runs on these
         self.mg_summary = multigrid.hierarchy_summary(levels)
         return self.mg_summary
+
+    def mg_apply(self, r, frozen=None):
+        """ONE V-cycle of the installed hierarchy on the residual ``r`` (``(T+1, V)``: modes x vertices, the caller's numbering), with
+        the launches the PCG uses; ``frozen``: modes to skip (their ``z`` stays ``D^-1 r``).  Returns ``(z, rz)``, ``rz[a] = r[a] . z[a]``
+        summed from the per-workgroup partial sums.  For tests and diagnosis: the solver never calls it.  ``mg_path()`` then tells
+        which kernels ran."""
+        a = np.ascontiguousarray(r, dtype=np.float64)
+        if a.shape != (self.T + 1, self.V):
+            raise ValueError(f"mg_apply: expected r of shape {(self.T + 1, self.V)}, got {a.shape}")
+        fp = None
+        if frozen is not None:
+            f = np.ascontiguousarray(np.asarray(frozen) != 0, dtype=np.int32)
+            if f.shape != (self.T + 1,):
+                raise ValueError(f"mg_apply: expected {self.T + 1} frozen marks, got shape {f.shape}")
+            fp = _ptr(f, C.c_int32)
+        z, rz = np.empty_like(a), np.empty(self.T + 1)
+        _lib.check(self.lib.dots_mg_apply(self._h, _ptr(a, C.c_double), _ptr(z, C.c_double), _ptr(rz, C.c_double), fp), "dots_mg_apply")
+        return z, rz
+
+    def mg_path(self):
+        """Names of the launches the last V-cycle took and the number of levels inside its tail launch (``_lib.MG_PATH``)."""
+        mask = self.debug_counter(_lib.MG_PATH_COUNTER)
+        return {n for n, bit in _lib.MG_PATH.items() if mask & bit}, (mask >> _lib.MG_PATH_TAIL_LEVELS_SHIFT) & 15
 
     # ---- direct (multifrontal) solve of the modal problems
     def setup_frontal(self, eps=0.0, leaf=None, mode_slice=None, numeric="device", bands=None, top_inverse=None):

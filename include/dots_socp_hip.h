@@ -386,6 +386,16 @@ typedef struct dots_mg_desc {
 int dots_mg_setup(dots_ctx *ctx, const dots_mg_desc *desc);
 int dots_mg_enable(dots_ctx *ctx, int on);   /* switch between multigrid (1) and Jacobi (0) preconditioning */
 
+/* Test and diagnosis entry point; the product path never calls it.  Applies ONE V-cycle, with the launches and the tiling the PCG
+ * uses, to a residual given on the host: r and z are [n_modes][V] in the caller's vertex numbering (the layout of phi), rz is
+ * [n_modes], frozen is [n_modes] or NULL (non-zero: the mode counts as converged and is skipped; its z stays D^-1 r with
+ * D = diag K + (sigma_a + eps) M, the state every cycle starts from, and its rz is 0).  On return z = MG(r) and
+ * rz[a] = sum_i r[a][i] z[a][i] as the sum of the per-workgroup partial rows the next PCG kernel would re-reduce.  Uses the PCG's
+ * vectors as scratch: a later solve is unaffected.  dots_mg_enable does not bear on it: the cycle of the installed hierarchy runs
+ * also while the PCG is switched to Jacobi.  DOTS_ERR_STATE unless the context is DOTS_LAP_MODAL_PCG on one GPU (no time
+ * slab) with a hierarchy installed by dots_mg_setup. */
+int dots_mg_apply(dots_ctx *ctx, const double *r, double *z, double *rz, const int32_t *frozen);
+
 /* ---- direct solve of the modal problems (replaces the T+1 SuperLU factorisations of
  * laplacian_inverse_socp.py:40-61 and their per-iteration triangular solves, :46-60) ----------------
  * Multifrontal Cholesky factor on one nested-dissection tree shared by all modes, built on the host
@@ -663,7 +673,12 @@ int dots_bench_kernel(dots_ctx *ctx, int which, int reps, double *ms_per_launch,
  * launches that took fewer right-hand sides than their chunk of DOTS_FRONT_NR problems held because NR regions of LDS would not fit or
  * a workgroup of 1024 threads takes fewer (the launch was split), 9 bytes this context has copied device -> host through dots_download
  * and dots_readout since it was created (the layer sums of dots_readout are written by the device itself and not copied), 10 device
- * allocations this context holds for its factor (0 without one, also after a dots_front_setup that failed); -1 for an unknown counter */
+ * allocations this context holds for its factor (0 without one, also after a dots_front_setup that failed), 11 the launches the
+ * last multigrid V-cycle enqueued on this context took, as a bit mask: 1 restriction with a workgroup per coarse row, 2 restriction
+ * with a thread per entry, 4 coarsest solve with a workgroup per row, 8 coarsest solve with a thread per entry, 16 the one-launch
+ * coarse tail, 32 post-smoothing of a level between the finest and the tail, 64 the down kernel on such a level, bits 8-11 the
+ * number of levels inside the tail launch (0: no cycle since dots_mg_setup installed or released the hierarchy, or since
+ * dots_mg_enable(ctx, 0)); -1 for an unknown counter */
 int64_t dots_debug_counter(dots_ctx *ctx, int which);
 
 /* device memory in use by the context, bytes */

@@ -98,3 +98,76 @@ def test_multigrid_beats_jacobi(name, kw):
         it_j, _ = pcg_iterations(A, b, lambda r: dinv * r, dinv)
         assert it_mg <= 40 and (it_mg * 3 <= it_j or it_j <= 40), (shift, it_mg, it_j)
         assert np.max(np.abs(A @ x - b)) < 1e-7 * np.max(np.abs(b))
+
+
+# ---------------------------------------------------------------------------- what a converged solve cannot see
+class WrongPostWeight(multigrid.CpuVcycle):
+    """The plain cycle with post-smoothing weight 0.6 instead of 2/3: still symmetric positive enough for PCG, and wrong."""
+
+    def cycle(self, b, l=0):
+        if l == len(self.levels) - 1:
+            return self.coarse_inv @ b
+        A, dinv, lv = self.A[l], self.dinv[l], self.levels[l]
+        x = self.omega * dinv * b
+        x = x + lv.P @ self.cycle(lv.R @ (b - A @ x), l + 1)
+        return x + 0.6 * dinv * (b - A @ x)
+
+
+@pytest.mark.parametrize("shift", [0.0, 9.3])
+def test_wrong_smoother_weight_hides_in_a_converged_solve(shift):
+    """Why tests/test_hip_multigrid.py compares ONE cycle element by element: a V-cycle with a wrong coefficient is far outside
+    that file's 1e-12 bound, yet a PCG preconditioned with it converges to the same solution and every converged-solve test
+    passes."""
+    plan, K = problem("torus", nu=24, nv=16)
+    levels = multigrid.build_hierarchy(K, plan.mass_vert, coarsest=6)
+    assert len(levels) == 3 and levels[0].n == 384
+    right, wrong = multigrid.CpuVcycle(levels, shift), WrongPostWeight(levels, shift)
+    b = np.random.default_rng(3).standard_normal(plan.n_vertices)
+    if shift == 0.0:
+        b -= b.mean()
+    z, zw = right.cycle(b), wrong.cycle(b)
+    assert np.max(np.abs(zw - z)) > 1e-3 * np.max(np.abs(z))
+    A, dinv = right.A[0], right.dinv[0]
+    it, x = pcg_iterations(A, b, right.cycle, dinv)
+    itw, xw = pcg_iterations(A, b, wrong.cycle, dinv)
+    assert it < 100 and itw < 100
+    if shift == 0.0:
+        x, xw = x - x.mean(), xw - xw.mean()
+    assert np.max(np.abs(xw - x)) < 1e-7 * np.max(np.abs(x))
+
+
+def test_setup_multigrid_keeps_the_levels_it_uploads():
+    """DeviceProblem.setup_multigrid leaves on the instance the hierarchy it described to the library (plan numbering): the
+    reference of the device V-cycle tests runs on these levels.  (The library call is replaced: no GPU here.)"""
+    import ctypes
+
+    from dots_socp_amd import _lib
+    from dots_socp_amd.device import DeviceProblem
+
+    plan, K = problem("torus", nu=24, nv=16)
+    seen = {}
+
+    class Library:
+        @staticmethod
+        def dots_mg_setup(handle, desc_ref):
+            d = ctypes.cast(desc_ref, ctypes.POINTER(_lib.MgDesc)).contents
+            seen["sizes"] = [d.levels[l].n for l in range(d.n_levels)]
+            seen["p_val"] = [np.ctypeslib.as_array(d.levels[l].p_val, (d.levels[l].p_nnz,)).copy() for l in range(d.n_levels - 1)]
+            seen["n_cols"] = d.n_cols
+            return 0
+
+    dev = DeviceProblem.__new__(DeviceProblem)
+    dev.lib, dev._h, dev.plan, dev.lap_solver, dev.mode_slice = Library(), None, plan, "modal_pcg", None
+    summary = dev.setup_multigrid(eps=1e-2, coarsest=6)
+    fresh = multigrid.build_hierarchy(K, plan.mass_vert, coarsest=6)
+    assert summary["sizes"] == seen["sizes"] == [lv.n for lv in fresh] == [lv.n for lv in dev.mg_levels] and seen["n_cols"] == plan.n_time + 1
+    for kept, want, p_val in zip(dev.mg_levels, fresh, seen["p_val"] + [None]):
+        for name in ("K", "M", "P", "R", "KP", "MP", "PP"):
+            a, b = getattr(kept, name), getattr(want, name)
+            assert (a is None) == (b is None)
+            if a is not None:
+                assert np.array_equal(a.indptr, b.indptr) and np.array_equal(a.indices, b.indices) and np.array_equal(a.data, b.data)
+        assert np.array_equal(kept.dK, want.dK) and np.array_equal(kept.dM, want.dM)
+        if p_val is not None:
+            assert np.array_equal(p_val, kept.P.data)
+    dev._h = None      # (nothing to destroy)
