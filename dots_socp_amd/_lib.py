@@ -53,6 +53,11 @@ ERR_MEMORY = -6
 MG_PATH_COUNTER = 11
 MG_PATH = {"restrict_rows": 1, "restrict_flat": 2, "coarse_rows": 4, "coarse_flat": 8, "tail": 16, "post": 32, "down_above0": 64}
 MG_PATH_TAIL_LEVELS_SHIFT = 8
+# dots_debug_counter(12): the launches the last dots_step iteration took (include/dots_socp_hip.h)
+STEP_PATH_COUNTER = 12
+STEP_PATH = {"rhs": 1, "rhs_modes": 2, "rhs_modes2": 4, "rhs_mfma": 8, "rhs_carried": 16, "rhs_div": 32, "soc_rider": 64, "soc_alone": 128,
+             "ql_triangle": 256, "ql_triangle2": 512, "ql_carry": 1024, "ql_kkt": 1 << 13, "ql_div": 1 << 14, "ql_bmnt": 1 << 15, "ql_defer": 1 << 16}
+STEP_PATH_QL_Z_SHIFT = 11
 
 
 _i32p = C.POINTER(C.c_int32)

@@ -328,7 +328,7 @@ static int check(dots_ctx *ctx, bool reads_only = false, bool keeps_division = f
     if (!ctx) { set_error("null context"); return DOTS_ERR_ARGUMENT; }
     hipError_t e = hipSetDevice(ctx->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice", __FILE__, __LINE__);
-    if (!reads_only) ctx->rhs_ahead = ctx->rhs_ahead_armed = ctx->penalty_armed = ctx->carry_valid = ctx->kkt_fused_valid = 0;      // (the carried gathers / fused sums belong to the state steps 2+3 left)
+    if (!reads_only) ctx->rhs_ahead = ctx->rhs_ahead_armed = ctx->penalty_armed = ctx->carry_valid = ctx->kkt_fused_valid = ctx->step_path = 0;      // (the carried gathers / fused sums belong to the state steps 2+3 left)
     if (!keeps_division) return flush_division(ctx);
     return 0;
 }
@@ -337,7 +337,7 @@ static int check(dots_ctx *ctx, bool reads_only = false, bool keeps_division = f
 static int palm_step0(Ctx *c) {
     if (!c->step_palm) return 0;
     if (c->zmid_stale) { set_error("step: DOTS_STEP_PALM needs z_mid of the previous iteration in memory"); return DOTS_ERR_STATE; }
-    c->carry_valid = c->kkt_fused_valid = 0;      // step 0 moves A, B and lambda_c
+    c->carry_valid = c->kkt_fused_valid = c->step_path = 0;      // step 0 moves A, B and lambda_c
     return launch_q_lambda_only(c);
 }
 
@@ -1829,6 +1829,7 @@ int64_t dots_debug_counter(dots_ctx *c, int which) {
         case 9: return c->d2h_bytes;                  // bytes dots_download and dots_readout have copied device -> host
         case 10: return c->n_front_allocs;            // device allocations the installed factor holds (0 after front_release: also after a failed dots_front_setup)
         case 11: return c->mg_path;                   // MG_PATH_* bits of the last V-cycle enqueued (dots_dev.h)
+        case 12: return c->step_path;                 // STEP_PATH_* bits of the last iteration's launches (dots_dev.h)
         default: return -1;
     }
 }

@@ -132,6 +132,27 @@ enum {
     MG_PATH_DOWN_ABOVE0 = 64,    // k_mg_down on such a level (vM != nullptr)
     MG_PATH_TAIL_LEVELS_SHIFT = 8      // levels inside k_mg_tail (1: the dense solve alone), bits 8-11
 };
+// Launches the last iteration took (Ctx::step_path, dots_debug_counter 12), recorded where launch_rhs, launch_soc_projection and
+// launch_q_lambda_mult choose: a test of one kernel variant asserts that the step ran it.  Host bookkeeping only.
+enum {
+    STEP_PATH_RHS = 1,              // k_rhs
+    STEP_PATH_RHS_MODES = 2,        // k_rhs_modes
+    STEP_PATH_RHS_MODES2 = 4,       // k_rhs_modes2
+    STEP_PATH_RHS_MFMA = 8,         // k_rhs_modes_mfma
+    STEP_PATH_RHS_CARRIED = 16,     // ... its CARRIED argument
+    STEP_PATH_RHS_DIV = 32,         // ... its DIV argument
+    STEP_PATH_SOC_RIDER = 64,       // the cone projection rode in the right-hand-side launch
+    STEP_PATH_SOC_ALONE = 128,      // ... or ran as k_soc_projection
+    STEP_PATH_QL_TRIANGLE = 256,    // k_q_lambda_mult_triangle
+    STEP_PATH_QL_TRIANGLE2 = 512,   // k_q_lambda_mult_triangle2
+    STEP_PATH_QL_CARRY = 1024,      // k_q_lambda_mult_carry
+    STEP_PATH_QL_Z_SHIFT = 11,      // the Z mode of steps 2+3 (0 read z_mid, 1 rebuild and store, 2 rebuild only), bits 11-12
+    STEP_PATH_QL_KKT = 1 << 13,     // K: the fused KKT sums
+    STEP_PATH_QL_DIV = 1 << 14,     // DIV: a pending penalty division applied
+    STEP_PATH_QL_BMNT = 1 << 15,    // BMNT: beta_mid streamed around the caches
+    STEP_PATH_QL_DEFER = 1 << 16,   // z_mid deferred (Ctx::zmid_deferred)
+    STEP_PATH_RHS_MASK = 0xff, STEP_PATH_QL_MASK = 0x1ff00
+};
 struct MgDev {
     int nlev = 0;
     MgLevelDev lv[10]{};
@@ -422,6 +443,7 @@ struct Ctx {
     int kkt_fused_valid = 0;      // ... and they belong to the current iterate and parameters
     int step_carry = 0;           // dots_step_flags: steps 2+3 also store the next iteration's per-corner gathers (cn_sq, cn_g)
     int carry_valid = 0;          // ... and they belong to the current iterate (cleared by every call that changes state or parameters)
+    int step_path = 0;            // STEP_PATH_* of the last iteration's launches (cleared with carry_valid; a right-hand side starts a new record)
     int zmid_stale = 0;           // z_mid does not belong to the current iterate
     // z_mid on demand (one GPU, carry mapping): an iteration after which z_mid MAY be read (residuals read back, possibly the last one) does
     // not store it (18 T F values that are almost never read); instead steps 2+3 write the new beta_mid into z_mid's storage and the new B

@@ -309,6 +309,7 @@ int launch_soc_projection(Ctx *c, int zmid_mode, bool with_inverse) {
     else
         hipLaunchKernelGGL((k_soc_projection<false>), dim3(n_soc + n_inv), dim3(BLOCK), lds, c->stream, c->d, c->prm.scale_z, c->prm.const_d, n_soc, IC);
     DOTS_HIP(hipGetLastError());
+    c->step_path = (c->step_path & ~STEP_PATH_SOC_RIDER) | STEP_PATH_SOC_ALONE;
     return 0;
 }
 
@@ -549,9 +550,11 @@ int launch_rhs(Ctx *c, bool with_soc, double dv) {
     const int g = xcd_grid(d.n_vtiles);
     const double r = c->prm.r / c->prm.boundary_scale, eps = c->prm.eps, sz = c->prm.scale_z, cd = c->prm.const_d;
     const bool modes = rhs_writes_modes(c), carried = c->carry_valid != 0;
+    int path = with_soc ? STEP_PATH_SOC_RIDER : 0;      // (dots_debug_counter 12)
     // the mode kernels' variants: 0 CARRIED (the corners' shares come from the last steps-2+3 launch), 1 DIV (a penalty update is pending: the dual
     // arrays are divided as they are read; rhs_divides told the caller this launch can), 2 neither
     auto modes2 = [&](int variant) {      // two time columns per lane (16-byte accesses)
+        path |= STEP_PATH_RHS_MODES2 | (variant == 0 ? STEP_PATH_RHS_CARRIED : 0) | (variant == 1 ? STEP_PATH_RHS_DIV : 0);
         with_constant<0, 1, 2>(variant, [&](auto V) {
             hipLaunchKernelGGL((k_rhs_modes2<V == 0, V == 1>), dim3(with_soc ? 2 * g : g), dim3(RHS_NB2), time_modes_tile_lds(d), c->stream, d, r, eps, d.cg_p0,
                                time_modes_chunk(d), g, sz, cd, V == 1 ? dv : 1.0);
@@ -559,6 +562,7 @@ int launch_rhs(Ctx *c, bool with_soc, double dv) {
     };
     if (modes && time_modes_mfma_ok(d)) {      // (two time columns per lane measured here too: knot63 -1.5 %, torus65k_T127 +1.5 %: not kept)
         const int n_tiles = (d.V + TM_ROWS - 1) / TM_ROWS, n_rhs = xcd_grid(n_tiles);
+        path |= STEP_PATH_RHS_MFMA | (carried ? STEP_PATH_RHS_CARRIED : (dv != 0.0 ? STEP_PATH_RHS_DIV : 0));
         with_constant<0, 1, 2>(carried ? 0 : (dv != 0.0 ? 1 : 2), [&](auto V) {
             hipLaunchKernelGGL((k_rhs_modes_mfma<V == 0, V == 1>), dim3(n_rhs + (with_soc ? g : 0)), dim3(RHS_NB), sizeof(double) * TM_ROWS * (d.TP + 1), c->stream, d, r, eps,
                                d.cg_p0, n_rhs, n_tiles, sz, cd, V == 1 ? dv : 1.0);
@@ -567,13 +571,17 @@ int launch_rhs(Ctx *c, bool with_soc, double dv) {
     else if (modes && d.TP >= 4 && carried) modes2(0);
     else if (dv != 0.0) modes2(1);
     else if (modes && d.TP >= 4) modes2(2);
-    else if (modes)
+    else if (modes) {
+        path |= STEP_PATH_RHS_MODES;
         hipLaunchKernelGGL(k_rhs_modes, dim3(with_soc ? 2 * g : g), dim3(RHS_NB), time_modes_tile_lds(d), c->stream, d, r, eps, d.cg_p0, time_modes_chunk(d), g, sz, cd);
-    else      // (carried: a time slab of the direct solver's iteration)
+    } else {      // (carried: a time slab of the direct solver's iteration)
+        path |= STEP_PATH_RHS | (carried ? STEP_PATH_RHS_CARRIED : 0);
         with_constant<true, false>(carried, [&](auto CARRIED) {
             hipLaunchKernelGGL(k_rhs<CARRIED>, dim3(with_soc ? g + g * (TILE_ELEMS / BLOCK) : g), dim3(BLOCK), 0, c->stream, d, r, eps, g, sz, cd);
         });
+    }
     DOTS_HIP(hipGetLastError());
+    c->step_path = path;      // the first launch of an iteration: a new record
     return 0;
 }
 
@@ -1163,6 +1171,7 @@ int launch_q_lambda_mult(Ctx *c, int zmid_mode, double dv) {
     const int nf8 = xcd_grid(c->d.n_ftiles), nv8 = xcd_grid(c->d.n_vtiles);
     const double cd = p.const_d, cr = p.congestion * p.r;
     c->carry_valid = c->kkt_fused_valid = 0;
+    c->step_path &= ~STEP_PATH_QL_MASK;
     // DOTS_STEP_KKT_SUMS: the launch also leaves the sums of the KKT conditions it can form from its registers (kkt_fused) and the
     // per-corner gather of Dual(alpha) (cn_e); it takes the carry mapping (whole triangles per workgroup) whether or not the next
     // iteration's gathers are wanted (emit)
@@ -1182,6 +1191,8 @@ int launch_q_lambda_mult(Ctx *c, int zmid_mode, double dv) {
         Dev dk = c->d;
         if (defer) { dk.B_st = c->B_alt; dk.bm_st = c->d.zm; }
         auto carry_launch = [&](int zmode, bool with_kkt) {
+            c->step_path |= STEP_PATH_QL_CARRY | (zmode << STEP_PATH_QL_Z_SHIFT) | (with_kkt ? STEP_PATH_QL_KKT : 0) | (dv != 0.0 ? STEP_PATH_QL_DIV : 0) |
+                            (c->sched.bm_nt != 0 ? STEP_PATH_QL_BMNT : 0) | (defer ? STEP_PATH_QL_DEFER : 0);
             with_constant<1, 2>(zmode, [&](auto Z) { with_constant<true, false>(with_kkt, [&](auto K) { with_constant<true, false>(dv != 0.0, [&](auto DIV) {
                 with_constant<true, false>(c->sched.bm_nt != 0, [&](auto BMNT) {
                     hipLaunchKernelGGL((k_q_lambda_mult_carry<Z, K, DIV, BMNT>), g, dim3(CARRY_NB), 0, c->stream, dk, p.scale_z, p.tau, n_fwg, tw, cd, cr, ka, kf, DIV ? dv : 1.0, emit);
@@ -1210,6 +1221,7 @@ int launch_q_lambda_mult(Ctx *c, int zmid_mode, double dv) {
     }
     if (c->d.TP >= 4) {      // two nodes per lane (16-byte accesses): k_q_lambda_mult_triangle2
         const dim3 g2(nf8 * (TILE_ELEMS / (2 * BLOCK)) + nv8);
+        c->step_path |= STEP_PATH_QL_TRIANGLE2 | (zmid_mode << STEP_PATH_QL_Z_SHIFT);
         if (zmid_mode == 2) hipLaunchKernelGGL((k_q_lambda_mult_triangle2<2>), g2, dim3(BLOCK), 0, c->stream, c->d, p.scale_z, p.tau, nf8, cd, cr);
         else if (zmid_mode == 1) hipLaunchKernelGGL((k_q_lambda_mult_triangle2<1>), g2, dim3(BLOCK), 0, c->stream, c->d, p.scale_z, p.tau, nf8, cd, cr);
         else hipLaunchKernelGGL((k_q_lambda_mult_triangle2<0>), g2, dim3(BLOCK), 0, c->stream, c->d, p.scale_z, p.tau, nf8, cd, cr);
@@ -1217,6 +1229,7 @@ int launch_q_lambda_mult(Ctx *c, int zmid_mode, double dv) {
         return 0;
     }
     const dim3 gf(nf8 * (TILE_ELEMS / BLOCK) + nv8);
+    c->step_path |= STEP_PATH_QL_TRIANGLE | (zmid_mode << STEP_PATH_QL_Z_SHIFT);
     if (zmid_mode == 2) hipLaunchKernelGGL((k_q_lambda_mult_triangle<2>), gf, dim3(BLOCK), 0, c->stream, c->d, p.scale_z, p.tau, nf8, cd, cr);
     else if (zmid_mode == 1) hipLaunchKernelGGL((k_q_lambda_mult_triangle<1>), gf, dim3(BLOCK), 0, c->stream, c->d, p.scale_z, p.tau, nf8, cd, cr);
     else hipLaunchKernelGGL((k_q_lambda_mult_triangle<0>), gf, dim3(BLOCK), 0, c->stream, c->d, p.scale_z, p.tau, nf8, cd, cr);

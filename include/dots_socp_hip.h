@@ -678,7 +678,13 @@ int dots_bench_kernel(dots_ctx *ctx, int which, int reps, double *ms_per_launch,
  * with a thread per entry, 4 coarsest solve with a workgroup per row, 8 coarsest solve with a thread per entry, 16 the one-launch
  * coarse tail, 32 post-smoothing of a level between the finest and the tail, 64 the down kernel on such a level, bits 8-11 the
  * number of levels inside the tail launch (0: no cycle since dots_mg_setup installed or released the hierarchy, or since
- * dots_mg_enable(ctx, 0)); -1 for an unknown counter */
+ * dots_mg_enable(ctx, 0)), 12 the launches of the last dots_step iteration on this context, as a bit mask: the right-hand-side kernel
+ * (1 k_rhs, 2 k_rhs_modes, 4 k_rhs_modes2, 8 k_rhs_modes_mfma), 16 it streamed the carried per-corner sums (CARRIED), 32 it applied a
+ * pending penalty division (DIV), 64 the cone projection rode in that launch, 128 it ran as k_soc_projection; steps 2+3 (256
+ * k_q_lambda_mult_triangle, 512 ..._triangle2, 1024 ..._carry), bits 11-12 their z_mid mode (0 read, 1 rebuild and store, 2 rebuild
+ * only), 8192 with the fused KKT sums, 16384 with the division, 32768 beta_mid streamed with the non-temporal hint, 65536 z_mid
+ * deferred (0: no iteration since a call that changed state or parameters; a right-hand side enqueued ahead of its iteration by
+ * DOTS_STEP_RHS_AHEAD starts the record of that iteration); -1 for an unknown counter */
 int64_t dots_debug_counter(dots_ctx *ctx, int which);
 
 /* device memory in use by the context, bytes */
