@@ -58,6 +58,10 @@ STEP_PATH_COUNTER = 12
 STEP_PATH = {"rhs": 1, "rhs_modes": 2, "rhs_modes2": 4, "rhs_mfma": 8, "rhs_carried": 16, "rhs_div": 32, "soc_rider": 64, "soc_alone": 128,
              "ql_triangle": 256, "ql_triangle2": 512, "ql_carry": 1024, "ql_kkt": 1 << 13, "ql_div": 1 << 14, "ql_bmnt": 1 << 15, "ql_defer": 1 << 16}
 STEP_PATH_QL_Z_SHIFT = 11
+# dots_debug_counter(13): path and tiling of the last launches of the PCG kernels (include/dots_socp_hip.h)
+CG_PATH_COUNTER = 13
+CG_PATH = {"modal": 1, "collapse": 2, "small_wg": 4, "mg": 8}
+CG_PATH_VT_SHIFT, CG_PATH_CAP_SHIFT, CG_PATH_G_SHIFT = 8, 20, 32
 
 
 _i32p = C.POINTER(C.c_int32)

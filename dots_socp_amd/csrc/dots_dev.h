@@ -132,6 +132,17 @@ enum {
     MG_PATH_DOWN_ABOVE0 = 64,    // k_mg_down on such a level (vM != nullptr)
     MG_PATH_TAIL_LEVELS_SHIFT = 8      // levels inside k_mg_tail (1: the dense solve alone), bits 8-11
 };
+// Tiling and kernel family of the last PCG launches (Ctx::cg_path, dots_debug_counter 13), written by make_args: a test pinned to one
+// path of the PCG kernels asserts that the launcher still puts it there.  Host bookkeeping only.
+enum {
+    CG_PATH_MODAL = 1,           // the batched per-mode PCG (0: the coupled space-time operator)
+    CG_PATH_COLLAPSE = 2,        // k_collapse sums the partial rows behind every producer
+    CG_PATH_SMALL_WG = 4,        // workgroups of fewer than 1024 threads
+    CG_PATH_MG = 8,              // multigrid preconditioner
+    CG_PATH_VT_SHIFT = 8,        // vertices per tile, bits 8-19
+    CG_PATH_CAP_SHIFT = 20,      // staged CSR entries per tile, bits 20-31
+    CG_PATH_G_SHIFT = 32         // workgroups, from bit 32
+};
 // Launches the last iteration took (Ctx::step_path, dots_debug_counter 12), recorded where launch_rhs, launch_soc_projection and
 // launch_q_lambda_mult choose: a test of one kernel variant asserts that the step ran it.  Host bookkeeping only.
 enum {
@@ -423,6 +434,7 @@ struct Ctx {
     int use_mg = 1;
     int mg_path = 0;              // MG_PATH_* of the last mg_vcycle (0: none since mg_release / dots_mg_enable(0))
     int cg_graph_mg = -1;
+    int64_t cg_path = 0;          // CG_PATH_* of the last PCG tiling handed to a launch (make_args, kernels_cg.hip; 0: none yet)
     int kkt_two = 1;              // KKT sums with two nodes per lane (one GPU; DOTS_KKT_TWO=0: one)
     // DOTS_STEP_TIMED: phase events of enqueue-only steps, collected later by dots_step_times (no host wait in the loop)
     static constexpr int TIME_SLOTS = 64;

@@ -214,14 +214,17 @@ __global__ __launch_bounds__(CG_NB) void k_cg_apply(Dev d, CgArgs a) {
         const double crit = a.mg ? column_total<MODAL>(d, d.partials + read_at(a, idx_crit(a, a.parity)), a.Gr, l) : rz_new;
         const double rz_old = d.scal[(a.parity ? SC_RZ0 : SC_RZ1) + col_of_thread];
         const double bref = d.scal[S::BREF + col_of_thread];
-        frozen = (d.flags[col_of_thread] != 0) || (crit <= a.tol2 * bref);
+        const bool was_frozen = d.flags[col_of_thread] != 0;
+        frozen = was_frozen || (crit <= a.tol2 * bref);
         beta = (rz_old > 0.0) ? rz_new / rz_old : 0.0;
         const bool col_valid = !MODAL || col_of_thread < ncols;
         const int all = __syncthreads_and((!col_valid || frozen) ? 1 : 0);
         if (blockIdx.x == 0) {
             if (tid < a.nc) {   // tid == column for the first nc threads (MODAL: TP <= CG_NB; else nc == 1)
                 d.scal[(a.parity ? SC_RZ1 : SC_RZ0) + tid] = rz_new;
-                d.scal[S::ALPHA + tid] = crit;      // last stopping-norm value (diagnostics)
+                // last stopping-norm value (diagnostics).  A column flagged earlier keeps the value it froze with: once ALL columns are
+                // frozen k_cg_update returns before it emits, so the rows of this parity are those of two iterations ago
+                if (!was_frozen) d.scal[S::ALPHA + tid] = crit;
                 d.flags[tid] = frozen ? 1 : 0;
             }
             if (tid == 0 && !all) d.flags[FLAG_ITERS] += 1;
@@ -587,6 +590,8 @@ static CgArgs make_args(Ctx *c, bool modal) {
     a.mg = (modal && c->mg.nlev > 1 && c->use_mg) ? 1 : 0;
     a.eps = c->prm.eps;
     a.tol2 = c->prm.cg_tol * c->prm.cg_tol;
+    c->cg_path = (modal ? CG_PATH_MODAL : 0) | (a.collapse ? CG_PATH_COLLAPSE : 0) | (a.nb < CG_NB ? CG_PATH_SMALL_WG : 0) | (a.mg ? CG_PATH_MG : 0) |
+                 ((int64_t)a.vt << CG_PATH_VT_SHIFT) | ((int64_t)a.cap << CG_PATH_CAP_SHIFT) | ((int64_t)a.G << CG_PATH_G_SHIFT);
     return a;
 }
 

@@ -568,6 +568,13 @@ class DeviceProblem:
         mask = self.debug_counter(_lib.MG_PATH_COUNTER)
         return {n for n, bit in _lib.MG_PATH.items() if mask & bit}, (mask >> _lib.MG_PATH_TAIL_LEVELS_SHIFT) & 15
 
+    def cg_path(self):
+        """``(names, vt, cap, G)`` of the last launches of the PCG kernels (``_lib.CG_PATH``): the path bits that are set, the vertices
+        per tile, the CSR entries of a tile staged in LDS and the number of workgroups; ``(set(), 0, 0, 0)`` before the first."""
+        mask = self.debug_counter(_lib.CG_PATH_COUNTER)
+        return ({n for n, bit in _lib.CG_PATH.items() if mask & bit}, (mask >> _lib.CG_PATH_VT_SHIFT) & 0xfff,
+                (mask >> _lib.CG_PATH_CAP_SHIFT) & 0xfff, mask >> _lib.CG_PATH_G_SHIFT)
+
     # ---- direct (multifrontal) solve of the modal problems
     def setup_frontal(self, eps=0.0, leaf=None, mode_slice=None, numeric="device", bands=None, top_inverse=None):
         """Factorise K + (sigma_a + eps) M for this context's modes on one nested-dissection tree

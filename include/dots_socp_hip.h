@@ -684,7 +684,12 @@ int dots_bench_kernel(dots_ctx *ctx, int which, int reps, double *ms_per_launch,
  * k_q_lambda_mult_triangle, 512 ..._triangle2, 1024 ..._carry), bits 11-12 their z_mid mode (0 read, 1 rebuild and store, 2 rebuild
  * only), 8192 with the fused KKT sums, 16384 with the division, 32768 beta_mid streamed with the non-temporal hint, 65536 z_mid
  * deferred (0: no iteration since a call that changed state or parameters; a right-hand side enqueued ahead of its iteration by
- * DOTS_STEP_RHS_AHEAD starts the record of that iteration); -1 for an unknown counter */
+ * DOTS_STEP_RHS_AHEAD starts the record of that iteration), 13 the path of the last launches of the PCG kernels on this context (a
+ * solve of step 1 without the direct solver, dots_mg_apply, the laplacian_apply operator, dots_bench_kernel 0-2), as a bit mask with the
+ * tiling packed above it: 1 the batched per-mode PCG (clear: the coupled space-time operator), 2 the per-workgroup partial rows are
+ * summed by k_collapse behind every producer, 4 workgroups of fewer than 1024 threads, 8 multigrid preconditioner; bits 8-19 the
+ * vertices per tile, bits 20-31 the CSR entries of a tile staged in LDS (further entries are read from global memory), from bit 32 the
+ * number of workgroups (0: no such launch yet); -1 for an unknown counter */
 int64_t dots_debug_counter(dots_ctx *ctx, int which);
 
 /* device memory in use by the context, bytes */

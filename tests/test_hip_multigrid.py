@@ -6,8 +6,9 @@ iterations (tests/test_multigrid_cpu.py::test_wrong_smoother_weight_hides_in_a_c
 kernels by the path mask of the launcher (dots_debug_counter 11): a change of the launcher's thresholds moves the mask and fails
 the case instead of silently moving it onto other kernels.
 
-Not covered here: the collapse of more than 1024 partial rows (k_collapse behind the V-cycle) needs V > 4096 at these pitches
-and stays with the converged solves of the large meshes; time-slab contexts are refused by dots_mg_apply.
+Case F reaches the collapse of more than 1024 partial rows (V > 4096 at pitch 256): the fine-level kernels of the cycle run with the
+256-thread tiling of the large problems and k_collapse sums the r.z rows, which the PCG's own path record (dots_debug_counter 13)
+must show.  Time-slab contexts are refused by dots_mg_apply.
 
 Bounds.  z: max|z - z_ref| / max|z_ref| < 1e-12 per mode (FP_TOL of test_hip_phases; the plain and the fused host cycle, two
 orderings of the same arithmetic, differ by 2e-16 to 3e-16).  rz: |rz - sum r z_ref| < 1e-12 sum |r_i z_i| per mode.
@@ -42,6 +43,12 @@ CASES = {
     # 2400, 400, 44, 9 rows: level 1 sits between the finest level and the tail
     "D": dict(mesh=("knot", dict(nu=240, nv=10)), coarsest=12, T=(15, 127, 255), tail_levels=2,
               narrow={"restrict_rows", "tail", "post", "down_above0"}, wide={"restrict_flat", "tail", "post", "down_above0"}),
+    # 4176, 976, 101 rows with the default coarsest (a lone coarsest level above 64 rows, level 1 between it and the finest): more than
+    # 1024 workgroups at pitch 256, so the finest level runs with one vertex per 256-thread workgroup and the r.z rows are collapsed
+    # behind the cycle
+    "F": dict(mesh=("torus", dict(nu=72, nv=58)), coarsest=256, T=(255,), tail_levels=0,
+              narrow=None, wide={"restrict_flat", "coarse_flat", "post", "down_above0"},
+              cg_path=({"modal", "collapse", "small_wg", "mg"}, 1, 76, 4176)),
 }
 CASE_T = [(c, T) for c, spec in CASES.items() for T in spec["T"]]
 
@@ -104,6 +111,12 @@ def assert_path(dev, case, T):
     names, tail_levels = dev.mg_path()
     want = spec["narrow"] if T + 1 <= 128 else spec["wide"]
     assert names == want and tail_levels == spec["tail_levels"], (case, T, dev.mg_summary["sizes"], sorted(names), tail_levels)
+    # the tiling of the PCG kernels around the cycle: only case F is large enough for the collapse
+    cg = dev.cg_path()
+    if "cg_path" in spec:
+        assert cg == spec["cg_path"], (case, T, cg)
+    else:
+        assert "modal" in cg[0] and not cg[0] & {"collapse", "small_wg"}, (case, T, cg)
 
 
 @pytest.mark.parametrize("eps", [0.0, 1e-2])
