@@ -33,6 +33,7 @@ EXPORTS = [
     "dots_patch_order", "dots_assemble", "dots_assemble_nnz", "dots_assemble_copy", "dots_assemble_free", "dots_symbolic_build", "dots_symbolic_front_rows", "dots_symbolic_copy", "dots_symbolic_free",
     "dots_front_share", "dots_laplacian_solve_many", "dots_step_many", "dots_bench_many", "dots_prolong_time", "dots_readout",
     "dots_prolong_space", "dots_transfer_space", "dots_carry_spacetime",
+    "dots_coarsen", "dots_coarsen_vertices", "dots_coarsen_triangles", "dots_coarsen_copy", "dots_coarsen_free", "dots_mesh_locate",
 ]
 
 
@@ -139,6 +140,12 @@ class CarrySpacetimeDesc(C.Structure):      # dots_carry_spacetime_desc
                 ("csrc", _i32p), ("n_vertices", C.c_int32), ("n_triangles", C.c_int32), ("factor", C.c_double * 4), ("ms", _f64p)]
 
 
+class MeshLocateDesc(C.Structure):      # dots_mesh_locate_desc
+    _fields_ = [("n_points", C.c_int32), ("n_vertices", C.c_int32), ("n_triangles", C.c_int32), ("reserved", C.c_int32),
+                ("points", _f64p), ("vertices", _f64p), ("triangles", _i32p), ("corner_points", _f64p), ("triangle", _i32p),
+                ("weights", _f64p), ("distance", _f64p), ("corner", _i32p), ("ms", _f64p)]
+
+
 class ReadoutDesc(C.Structure):      # dots_readout_desc
     _fields_ = [
         ("factor", C.c_double), ("w_vertex", _f64p), ("w_triangle", _f64p), ("centred", C.c_int32), ("reserved", C.c_int32),
@@ -239,7 +246,7 @@ _runtime_ready = False
 
 def load(host_only=False):
     """Load the shared library (once) and declare the signatures.  ``host_only``: the caller uses host entry points only
-    (dots_assemble, dots_patch_order, dots_tree_*, dots_symbolic_*): torch is still imported first (one copy of the HIP runtime per
+    (dots_assemble, dots_coarsen, dots_patch_order, dots_tree_*, dots_symbolic_*): torch is still imported first (one copy of the HIP runtime per
     process, see _torch_runtime_first) but the GPU runtime is not initialised -- a process that only assembles operators, or a parent
     that is about to spawn ranks, stays clear of the device."""
     global _lib, _runtime_ready
@@ -337,12 +344,22 @@ def load(host_only=False):
     lib.dots_prolong_space.argtypes = [vp, vp, C.POINTER(ProlongSpaceDesc)]
     lib.dots_transfer_space.argtypes = [vp, vp, C.POINTER(TransferSpaceDesc)]
     lib.dots_carry_spacetime.argtypes = [vp, vp, C.POINTER(CarrySpacetimeDesc)]
+    lib.dots_coarsen.argtypes = [C.c_int32, C.c_int32, _f64p, _i32p, C.c_int32, C.POINTER(vp)]
+    lib.dots_coarsen_vertices.argtypes = [vp]
+    lib.dots_coarsen_vertices.restype = C.c_int64
+    lib.dots_coarsen_triangles.argtypes = [vp]
+    lib.dots_coarsen_triangles.restype = C.c_int64
+    lib.dots_coarsen_copy.argtypes = [vp, _i32p, _i32p]
+    lib.dots_coarsen_free.argtypes = [vp]
+    lib.dots_coarsen_free.restype = None
+    lib.dots_mesh_locate.argtypes = [C.POINTER(MeshLocateDesc), C.c_int]
     lib.dots_device_bytes.argtypes = [vp]
     lib.dots_device_bytes.restype = C.c_int64
     for n in EXPORTS:
         f = getattr(lib, n)
         if n not in ("dots_last_error", "dots_array_count", "dots_device_bytes", "dots_slab_elems", "dots_tree_nodes", "dots_tree_free", "dots_debug_counter",
-                     "dots_symbolic_front_rows", "dots_symbolic_free", "dots_assemble_nnz", "dots_assemble_free"):
+                     "dots_symbolic_front_rows", "dots_symbolic_free", "dots_assemble_nnz", "dots_assemble_free", "dots_coarsen_vertices",
+                     "dots_coarsen_triangles", "dots_coarsen_free"):
             f.restype = C.c_int
     if lib.dots_abi_version() != ABI_VERSION:
         raise HipLibraryError("libdotsocp_hip.so ABI version mismatch; rebuild it")

@@ -289,7 +289,135 @@ def locate(points, vertices, triangles, k=3):
     return tri, weights, distance
 
 
-def mesh_transfer(coarse_geometry, fine_geometry):
+_locate_kdtree = locate      # (mesh_transfer's keyword ``locate`` shadows the function)
+LOCATE_MODES = ("kdtree", "exact", "device")
+LOCATE_EXACT_PAIRS = 1 << 21      # point-triangle pairs per pass of locate_exact
+
+
+def check_locate(locate, who):
+    if locate not in LOCATE_MODES:
+        raise ValueError(f"{who}: locate must be one of {list(LOCATE_MODES)}")
+
+
+def closest_scalar_order(p, a, b, c):
+    """``closest_on_triangles`` restated in a fixed order of operations (arrays that broadcast against each other, last axis 3):
+    ``(w0, w1, w2, d2)``, the clamped weights and the SQUARED distance.  Every dot product is ``(x0*y0 + x1*y1) + x2*y2``, the closest
+    point ``q = (w0*a + w1*b) + w2*c``, ``d2 = (rx*rx + ry*ry) + rz*rz`` with ``r = p - q``; the six region conditions are those of
+    ``closest_on_triangles`` in the same order.  The device kernel (k_locate, csrc/kernels_locate.hip) performs these operations."""
+    def dot(x, y):
+        return (x[..., 0] * y[..., 0] + x[..., 1] * y[..., 1]) + x[..., 2] * y[..., 2]
+
+    ab, ac, ap = b - a, c - a, p - a
+    d1, d2 = dot(ab, ap), dot(ac, ap)
+    bp = p - b
+    d3, d4 = dot(ab, bp), dot(ac, bp)
+    cp = p - c
+    d5, d6 = dot(ab, cp), dot(ac, cp)
+    vc, vb, va = d1 * d4 - d3 * d2, d5 * d2 - d1 * d6, d3 * d6 - d5 * d4
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        t_ab, t_ac = d1 / (d1 - d3), d2 / (d2 - d6)
+        t_bc = (d4 - d3) / ((d4 - d3) + (d5 - d6))
+        denom = 1.0 / ((va + vb) + vc)
+        v_in, w_in = vb * denom, vc * denom
+    zero, one = np.zeros_like(d1), np.ones_like(d1)
+    conds = [(d1 <= 0) & (d2 <= 0), (d3 >= 0) & (d4 <= d3), (vc <= 0) & (d1 >= 0) & (d3 <= 0), (d6 >= 0) & (d5 <= d6),
+             (vb <= 0) & (d2 >= 0) & (d6 <= 0), (va <= 0) & (d4 - d3 >= 0) & (d5 - d6 >= 0)]
+    w1 = np.select(conds, [zero, one, t_ab, zero, zero, 1.0 - t_bc], default=v_in)
+    w2 = np.select(conds, [zero, zero, zero, one, t_ac, t_bc], default=w_in)
+    clamp = lambda x: np.where(x < 0.0, 0.0, np.where(x > 1.0, 1.0, x))      # noqa: E731  (as the kernel's two selects)
+    w1, w2 = clamp(w1), clamp(w2)
+    w0 = (1.0 - w1) - w2
+    w0 = np.where(w0 < 0.0, 0.0, w0)
+    r = p - ((w0[..., None] * a + w1[..., None] * b) + w2[..., None] * c)
+    return w0, w1, w2, dot(r, r)
+
+
+def _locate_arguments(points, vertices, triangles, who):
+    p = np.ascontiguousarray(points, dtype=np.float64)
+    v = np.ascontiguousarray(vertices, dtype=np.float64)
+    t = np.asarray(triangles).astype(np.int64)
+    if p.ndim != 2 or p.shape[1] != 3 or p.shape[0] < 1 or v.ndim != 2 or v.shape[1] != 3 or t.ndim != 2 or t.shape[1] != 3 or t.shape[0] < 1:
+        raise ValueError(f"{who}: points (N, 3), vertices (V, 3) and triangles (F, 3) expected")
+    return p, v, t
+
+
+def locate_exact(points, vertices, triangles):
+    """The closest point of the mesh ``(vertices, triangles)`` to every one of ``points`` over ALL triangles: ``(triangle (N,) int64,
+    weights (N, 3), distance (N,))``.  Per point and triangle ``closest_scalar_order``; the winner is the smallest ``(d2, triangle
+    index)``; ``distance = sqrt(d2)``.  Brute force in chunks: the specification of ``dots_mesh_locate``, which returns these arrays bit
+    for bit.  ``ValueError``: an index out of range, a triangle of zero area, non-finite coordinates or points."""
+    p, v, t = _locate_arguments(points, vertices, triangles, "locate_exact")
+    if t.min() < 0 or t.max() >= v.shape[0]:
+        raise ValueError("locate_exact: a triangle names a vertex the mesh does not have")
+    if not (np.all(np.isfinite(p)) and np.all(np.isfinite(v))):
+        raise ValueError("locate_exact: non-finite coordinates or points")
+    if not np.all(np.linalg.norm(np.cross(v[t[:, 1]] - v[t[:, 0]], v[t[:, 2]] - v[t[:, 0]]), axis=1) > 0.0):
+        raise ValueError("locate_exact: the mesh has a triangle of zero area")
+    a, b, c = v[t[:, 0]][None], v[t[:, 1]][None], v[t[:, 2]][None]
+    tri = np.empty(p.shape[0], dtype=np.int64)
+    weights = np.empty((p.shape[0], 3))
+    distance = np.empty(p.shape[0])
+    chunk = max(1, LOCATE_EXACT_PAIRS // t.shape[0])
+    for lo in range(0, p.shape[0], chunk):
+        pc = p[lo:lo + chunk]
+        w0, w1, w2, d2 = closest_scalar_order(pc[:, None, :], a, b, c)
+        best = np.argmin(d2, axis=1)      # (the first minimum: the smallest triangle index on a tie)
+        rows = np.arange(pc.shape[0])
+        tri[lo:lo + pc.shape[0]] = best
+        weights[lo:lo + pc.shape[0]] = np.stack([w0[rows, best], w1[rows, best], w2[rows, best]], axis=1)
+        distance[lo:lo + pc.shape[0]] = np.sqrt(d2[rows, best])
+    return tri, weights, distance
+
+
+def corner_exact(corner_points, vertices, triangles, triangle):
+    """For point i with the three corner points ``corner_points[i]`` (N, 3, 3): the corner of ``triangle[i]`` with the largest clamped
+    weight (``closest_scalar_order``) of each corner point with respect to that one triangle, the first maximum on a tie: (N, 3) int32."""
+    v, t = np.asarray(vertices, dtype=np.float64), np.asarray(triangles).astype(np.int64)
+    f = np.asarray(triangle).astype(np.int64)
+    a, b, c = v[t[f, 0]][:, None, :], v[t[f, 1]][:, None, :], v[t[f, 2]][:, None, :]
+    w0, w1, w2, _ = closest_scalar_order(np.asarray(corner_points, dtype=np.float64), a, b, c)
+    return np.argmax(np.stack([w0, w1, w2], axis=-1), axis=-1).astype(np.int32)
+
+
+def locate_device(points, vertices, triangles, corner_points=None, device=0, timing=None):
+    """``locate_exact`` (and ``corner_exact`` when ``corner_points`` (N, 3, 3) is given) on the device (``dots_mesh_locate``): the same
+    arrays bit for bit, ``(triangle, weights, distance)`` or ``(triangle, weights, distance, corner)``.  ``timing``: a dict that
+    receives "kernel_ms" (device events around the launches).  There is no host fall-back: without the library or a device it raises."""
+    import ctypes as C
+
+    from . import _lib
+
+    p, v, t = _locate_arguments(points, vertices, triangles, "locate_device")
+    if t.max() >= 2 ** 31 or t.min() < -2 ** 31 or max(p.shape[0], v.shape[0], t.shape[0]) >= 2 ** 31:
+        raise ValueError("locate_device: sizes and indices must fit 32 bits")
+    t32 = np.ascontiguousarray(t, dtype=np.int32)
+    n = p.shape[0]
+    tri, weights, distance = np.empty(n, dtype=np.int32), np.empty((n, 3)), np.empty(n)
+    corner = cp = None
+    if corner_points is not None:
+        cp = np.ascontiguousarray(corner_points, dtype=np.float64)
+        if cp.shape != (n, 3, 3):
+            raise ValueError("locate_device: corner_points must be (N, 3, 3)")
+        corner = np.empty((n, 3), dtype=np.int32)
+    ms = C.c_double(0.0)
+    desc = _lib.MeshLocateDesc(
+        n_points=n, n_vertices=v.shape[0], n_triangles=t32.shape[0], reserved=0, points=p.ctypes.data_as(_lib._f64p),
+        vertices=v.ctypes.data_as(_lib._f64p), triangles=t32.ctypes.data_as(_lib._i32p),
+        corner_points=None if cp is None else cp.ctypes.data_as(_lib._f64p), triangle=tri.ctypes.data_as(_lib._i32p),
+        weights=weights.ctypes.data_as(_lib._f64p), distance=distance.ctypes.data_as(_lib._f64p),
+        corner=None if corner is None else corner.ctypes.data_as(_lib._i32p), ms=C.pointer(ms))
+    lib = _lib.load()
+    rc = lib.dots_mesh_locate(C.byref(desc), int(device))
+    if rc == _lib.ERR_ARGUMENT:
+        raise ValueError("locate_device: " + lib.dots_last_error().decode("utf-8", "replace"))
+    _lib.check(rc, "dots_mesh_locate")
+    if timing is not None:
+        timing["kernel_ms"] = float(ms.value)
+    out = (tri.astype(np.int64), weights, distance)
+    return out if corner is None else out + (corner,)
+
+
+def mesh_transfer(coarse_geometry, fine_geometry, locate="kdtree", device=0):
     """The transfer from the mesh of ``coarse_geometry`` to that of ``fine_geometry``, two independent triangulations of one surface
     in the same coordinates (normalise them together): a dict with
 
@@ -301,18 +429,34 @@ def mesh_transfer(coarse_geometry, fine_geometry):
     * ``max_distance``: the largest distance of a fine vertex or centroid from the coarse mesh; ``n_source_vertices``,
       ``n_source_triangles``.
 
+    ``locate``: "kdtree" is ``locate`` (the candidates around the three nearest vertices); "exact" is ``locate_exact`` /
+    ``corner_exact`` (the closest point over all triangles: what a decimated pair needs, ``meshes.coarsen_levels``); "device" is
+    ``locate_device`` on GPU ``device`` and returns what "exact" returns.
+
     ``ValueError`` when ``max_distance`` exceeds the longest edge of the coarse mesh: not the same surface, or not the same scaling."""
+    check_locate(locate, "mesh_transfer")
     vc = np.asarray(coarse_geometry["vertices"], dtype=np.float64)
     tc = np.asarray(coarse_geometry["triangles"]).astype(np.int64)
     vf = np.asarray(fine_geometry["vertices"], dtype=np.float64)
     tf = np.asarray(fine_geometry["triangles"]).astype(np.int64)
-    tri_v, w_v, d_v = locate(vf, vc, tc)
     centroid = (vf[tf[:, 0]] + vf[tf[:, 1]] + vf[tf[:, 2]]) / 3.0
-    tri_f, _, d_f = locate(centroid, vc, tc)
-    corner = np.empty((tf.shape[0], 3), dtype=np.int32)
-    for k in range(3):
-        w, _ = closest_on_triangles(vf[tf[:, k]], vc[tc[tri_f, 0]], vc[tc[tri_f, 1]], vc[tc[tri_f, 2]])
-        corner[:, k] = np.argmax(w, axis=1)      # (the first maximum: the smallest corner index on a tie)
+    if locate == "kdtree":
+        tri_v, w_v, d_v = _locate_kdtree(vf, vc, tc)
+        tri_f, _, d_f = _locate_kdtree(centroid, vc, tc)
+        corner = np.empty((tf.shape[0], 3), dtype=np.int32)
+        for k in range(3):
+            w, _ = closest_on_triangles(vf[tf[:, k]], vc[tc[tri_f, 0]], vc[tc[tri_f, 1]], vc[tc[tri_f, 2]])
+            corner[:, k] = np.argmax(w, axis=1)      # (the first maximum: the smallest corner index on a tie)
+    elif locate == "exact":
+        tri_v, w_v, d_v = locate_exact(vf, vc, tc)
+        tri_f, _, d_f = locate_exact(centroid, vc, tc)
+        corner = corner_exact(vf[tf], vc, tc, tri_f)
+    else:      # one call: the vertices first, then the centroids with the corner points of their triangles
+        points = np.concatenate([vf, centroid], axis=0)
+        corner_points = np.concatenate([np.repeat(vf[:, None, :], 3, axis=1), vf[tf]], axis=0)
+        tri, w, d, cn = locate_device(points, vc, tc, corner_points=corner_points, device=device)
+        n = vf.shape[0]
+        tri_v, w_v, d_v, tri_f, d_f, corner = tri[:n], w[:n], d[:n], tri[n:], d[n:], np.ascontiguousarray(cn[n:])
     max_distance = float(max(d_v.max(), d_f.max()))
     edges = np.concatenate([vc[tc[:, 1]] - vc[tc[:, 0]], vc[tc[:, 2]] - vc[tc[:, 1]], vc[tc[:, 0]] - vc[tc[:, 2]]], axis=0)
     longest = float(np.linalg.norm(edges, axis=1).max())

@@ -227,7 +227,7 @@ def refine_levels(geometry, n_levels, project=None, densities=None):
     return levels
 
 
-def link_levels(geometries, densities=None):
+def link_levels(geometries, densities=None, locate="kdtree"):
     """The counterpart of ``refine_levels`` for meshes that already exist: ``geometries`` (coarse to fine) are independent
     triangulations of one surface in the same coordinates (normalised together); every level after the first gets the map to the level
     below under the key "transfer" (``cascade.mesh_transfer``).  A level that already has "parents" is left as it is, so nested and
@@ -235,7 +235,8 @@ def link_levels(geometries, densities=None):
 
     ``mu0`` / ``mu1`` of a level that lacks them: ``densities(vertices, area_vertices) -> (mu0, mu1)``, or without it the densities per
     unit area of the level below carried up by the vertex rule of ``cascade.transfer_space`` (of ``cascade.prolong_space`` on a level
-    with "parents") and weighted with the level's own ``area_vertices``; either way scaled to unit mass."""
+    with "parents") and weighted with the level's own ``area_vertices``; either way scaled to unit mass.  ``locate``: how
+    ``cascade.mesh_transfer`` locates ("kdtree" | "exact" | "device")."""
     from . import cascade
 
     levels = [dict(g) for g in geometries]
@@ -250,7 +251,7 @@ def link_levels(geometries, densities=None):
 
     for coarse, fine in zip(levels, levels[1:]):
         if fine.get("parents") is None:
-            fine["transfer"] = cascade.mesh_transfer(coarse, fine)
+            fine["transfer"] = cascade.mesh_transfer(coarse, fine, locate=locate)
         if fine.get("mu0") is not None and fine.get("mu1") is not None:
             continue
         area_f = areas(fine)
@@ -268,6 +269,271 @@ def link_levels(geometries, densities=None):
             mu1 = up(np.asarray(coarse["mu1"], dtype=np.float64) / area_c) * area_f
         mu0, mu1 = np.asarray(mu0, dtype=np.float64), np.asarray(mu1, dtype=np.float64)
         fine["mu0"], fine["mu1"] = mu0 / mu0.sum(), mu1 / mu1.sum()
+    return levels
+
+
+# --------------------------------------------------------------------------- #
+# coarsening (the levels of a cascade in space from ONE mesh)
+# --------------------------------------------------------------------------- #
+COS_BOUNDARY_TURN = 0.7071067811865476      # cos(pi / 4): the most a boundary may turn at a vertex that is removed
+MIN_NORMAL_COSINE = 0.2                     # a triangle that survives a collapse keeps its normal to this cosine
+
+
+def _coarsen_arguments(vertices, triangles, n_vertices, ratio):
+    v = np.ascontiguousarray(vertices, dtype=np.float64)
+    t = np.asarray(triangles)
+    if v.ndim != 2 or v.shape[1] != 3 or v.shape[0] < 1 or t.ndim != 2 or t.shape[1] != 3 or t.shape[0] < 1:
+        raise ValueError("coarsen: vertices (V, 3) and triangles (F, 3) expected")
+    if not np.issubdtype(t.dtype, np.integer):
+        raise ValueError("coarsen: integer triangles expected")
+    if n_vertices is None:
+        if not ratio > 1:
+            raise ValueError(f"coarsen: ratio must be > 1 (got {ratio})")
+        target = int(np.floor(v.shape[0] / float(ratio)))
+    else:
+        target = int(n_vertices)
+        if target != n_vertices or target < 1:
+            raise ValueError("coarsen: n_vertices must be a positive integer")
+    return v, np.ascontiguousarray(t, dtype=np.int64), target
+
+
+def _check_coarsen_mesh(v, t):
+    """The refusals of ``coarsen`` (the native version makes the same ones in the same order)."""
+    if t.min() < 0 or t.max() >= v.shape[0]:
+        raise ValueError("coarsen: triangle index out of range")
+    if not np.all(np.isfinite(v)):
+        raise ValueError("coarsen: non-finite coordinates")
+    n = np.cross(v[t[:, 1]] - v[t[:, 0]], v[t[:, 2]] - v[t[:, 0]])
+    if not np.all(np.sqrt((n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2]) > 0.0):
+        raise ValueError("coarsen: a triangle of zero area")
+    directed = np.concatenate([t[:, [0, 1]], t[:, [1, 2]], t[:, [2, 0]]], axis=0)
+    if np.unique(np.sort(directed, axis=1), axis=0, return_counts=True)[1].max() > 2:
+        raise ValueError("coarsen: an edge with more than two triangles")
+    if np.unique(directed, axis=0).shape[0] != directed.shape[0]:
+        raise ValueError("coarsen: two triangles cross an edge in the same direction")
+
+
+def _coarsen_python(v, t, target):
+    """The specification of ``coarsen`` in plain Python (the rules are in its docstring): ``(kept, triangles_c)``."""
+    import heapq
+    from math import sqrt
+
+    P, T = v.tolist(), t.tolist()
+    V = len(P)
+    inc = [[] for _ in range(V)]      # the live triangles around every vertex
+    for f, tri in enumerate(T):
+        for w in tri:
+            inc[w].append(f)
+    alive_v, alive_t = [True] * V, [True] * len(T)
+
+    def sub(a, b):
+        return (a[0] - b[0], a[1] - b[1], a[2] - b[2])
+
+    def dot(a, b):
+        return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
+
+    def norm(a):
+        return sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2])
+
+    def normal(p0, p1, p2):
+        e1, e2 = sub(P[p1], P[p0]), sub(P[p2], P[p0])
+        return (e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0])
+
+    def key(a, b):
+        a, b = (a, b) if a < b else (b, a)
+        return (norm(sub(P[a], P[b])), a, b)
+
+    def neighbours(x):
+        return {w for f in inc[x] for w in T[f] if w != x}
+
+    def allowed(u, v_):
+        edge_t = [f for f in inc[v_] if u in T[f]]
+        if not 1 <= len(edge_t) <= 2:
+            return False
+        nu, nv = neighbours(u), neighbours(v_)
+        if (nu & nv) != {w for f in edge_t for w in T[f] if w != u and w != v_}:
+            return False
+        count = {}
+        for f in inc[v_]:
+            for w in T[f]:
+                if w != v_:
+                    count[w] = count.get(w, 0) + 1
+        boundary = sorted(w for w, k in count.items() if k == 1)
+        if boundary:
+            if len(edge_t) != 1 or len(boundary) != 2:
+                return False
+            a, b = sub(P[v_], P[boundary[0]]), sub(P[boundary[1]], P[v_])
+            if not dot(a, b) >= (COS_BOUNDARY_TURN * norm(a)) * norm(b):
+                return False
+        elif len((nu | nv) - {u, v_}) < 3:
+            return False
+        for f in inc[v_]:
+            if f in edge_t:
+                continue
+            p = T[f]
+            q = [u if w == v_ else w for w in p]
+            n_old, n_new = normal(*p), normal(*q)
+            length = norm(n_new)
+            if not length > 0.0 or not dot(n_old, n_new) >= (MIN_NORMAL_COSINE * norm(n_old)) * length:
+                return False
+        return True
+
+    def collapse(u, v_):
+        for f in list(inc[v_]):
+            if u in T[f]:
+                alive_t[f] = False
+                for w in T[f]:
+                    inc[w].remove(f)
+        for f in inc[v_]:
+            T[f] = [u if w == v_ else w for w in T[f]]
+            inc[u].append(f)
+        inc[v_] = []
+        alive_v[v_] = False
+
+    def all_edges():
+        return [key(a, b) for a in range(V) if alive_v[a] for b in neighbours(a) if a < b]
+
+    heap = all_edges()
+    heapq.heapify(heap)
+    live, collapsed = V, False
+    while live > target:
+        if not heap:
+            if not collapsed:
+                break      # a whole refill without a collapse: what was reached is the result
+            heap = all_edges()
+            heapq.heapify(heap)
+            collapsed = False
+            continue
+        _, a, b = heapq.heappop(heap)
+        if not (alive_v[a] and alive_v[b]) or not any(b in T[f] for f in inc[a]):
+            continue
+        for u, v_ in ((a, b), (b, a)):
+            if allowed(u, v_):
+                collapse(u, v_)
+                live -= 1
+                collapsed = True
+                for w in neighbours(u):
+                    heapq.heappush(heap, key(u, w))
+                break
+    kept = np.flatnonzero(np.asarray(alive_v))
+    return kept, np.asarray([T[f] for f in range(len(T)) if alive_t[f]], dtype=np.int64).reshape(-1, 3)
+
+
+def _coarsen_native(v, t, target):
+    import ctypes as C
+
+    from . import _lib
+
+    lib = _lib.load(host_only=True)
+    if t.max() >= 2 ** 31 or t.min() < -2 ** 31:
+        raise ValueError("coarsen: triangle index out of range")
+    t32 = np.ascontiguousarray(t, dtype=np.int32)
+    handle = C.c_void_p()
+    rc = lib.dots_coarsen(v.shape[0], t32.shape[0], v.ctypes.data_as(_lib._f64p), t32.ctypes.data_as(_lib._i32p), target, C.byref(handle))
+    if rc == _lib.ERR_ARGUMENT:
+        raise ValueError("coarsen: " + lib.dots_last_error().decode("utf-8", "replace").split(": ", 1)[-1])
+    _lib.check(rc, "dots_coarsen")
+    try:
+        kept = np.empty(lib.dots_coarsen_vertices(handle), dtype=np.int32)
+        tri = np.empty((lib.dots_coarsen_triangles(handle), 3), dtype=np.int32)
+        _lib.check(lib.dots_coarsen_copy(handle, kept.ctypes.data_as(_lib._i32p), tri.ctypes.data_as(_lib._i32p)), "dots_coarsen_copy")
+    finally:
+        lib.dots_coarsen_free(handle)
+    return kept.astype(np.int64), tri.astype(np.int64)
+
+
+def coarsen(vertices, triangles, n_vertices=None, ratio=4.0, backend="native"):
+    """Half-edge-collapse decimation: ``(vertices_c, triangles_c, kept)``.  The coarse vertices are a subset of the fine ones and no
+    position moves: ``kept`` (ascending fine indices) with ``vertices_c == vertices[kept]`` bit for bit; ``triangles_c`` are the
+    surviving fine triangles in fine order and corner order, with the substituted, renumbered vertices.
+
+    ``backend="python"`` is the specification, ``"native"`` (``dots_coarsen``, host C++ of the library) returns identical arrays.
+    The rules are chosen so that nothing depends on an implementation's data structures:
+
+    * candidates: a multiset of undirected edges keyed ``(length, a, b)``, ``a < b``, ``length = sqrt((dx*dx + dy*dy) + dz*dz)``;
+      every edge once at the start; always the smallest key is popped, and skipped when an end point is dead or the two are no
+      longer adjacent;
+    * removing ``b`` (keeping ``a``) is tried first, then removing ``a``; if neither is allowed the entry is dropped;
+    * removing ``v``, keeping ``u``, is allowed if (1) the edge has one or two triangles, (2) the common neighbours of ``u`` and ``v``
+      are exactly the vertices opposite the edge in those triangles (the link condition), (3) for a boundary ``v``: the edge is a
+      boundary edge, ``v`` has exactly two boundary neighbours ``prev < next`` and ``dot(v - prev, next - v) >= (cos(pi/4) |v - prev|)
+      |next - v|``, (4) for an interior ``v``: ``u`` keeps at least three neighbours, (5) every other triangle around ``v``, with ``v``
+      replaced by ``u``, has a non-zero normal ``n'`` with ``n . n' >= (0.2 |n|) |n'|`` against its old normal ``n`` (normals are
+      ``cross(p1 - p0, p2 - p0)``, every dot product ``(x0*y0 + x1*y1) + x2*y2``);
+    * after a collapse every edge now around ``u`` is inserted again (duplicates are harmless);
+    * it stops when the live vertex count is <= the target: ``n_vertices``, else ``floor(V / ratio)``; when the candidates run out
+      first they are refilled with every current edge; a whole refill without a collapse returns what was reached (the caller sees
+      the count).
+
+    ``ValueError`` before any work: an edge with more than two triangles, two triangles crossing an edge in the same direction, a
+    zero-area triangle, an index out of range, non-finite coordinates, ``ratio <= 1``."""
+    if backend not in ("native", "python"):
+        raise ValueError("coarsen: backend must be 'native' or 'python'")
+    v, t, target = _coarsen_arguments(vertices, triangles, n_vertices, ratio)
+    if backend == "python":
+        _check_coarsen_mesh(v, t)
+        kept, tri = _coarsen_python(v, t, target)
+    else:
+        kept, tri = _coarsen_native(v, t, target)
+    renumber = np.full(v.shape[0], -1, dtype=np.int64)
+    renumber[kept] = np.arange(kept.size)
+    return v[kept], renumber[tri], kept
+
+
+def restrict_density(mu_fine, transfer):
+    """A density (mass per vertex) of the destination mesh of ``transfer`` (``cascade.mesh_transfer``) on its source mesh:
+    ``mu_c[s] += w * mu_f[v]`` over ``vertex_sources`` / ``vertex_weights`` (``np.add.at`` in row order), the transpose of the vertex
+    rule of ``cascade.transfer_space``.  The clamped weights of a vertex sum to 1 and are >= 0: mass and signs are kept."""
+    from . import cascade
+
+    vs, vw, _, _ = cascade.check_transfer(transfer)
+    mu = np.asarray(mu_fine, dtype=np.float64)
+    if mu.shape != (vs.shape[0],):
+        raise ValueError(f"restrict_density: expected {vs.shape[0]} values (one per vertex of the transfer's destination), got shape {mu.shape}")
+    out = np.zeros(int(transfer["n_source_vertices"]))
+    np.add.at(out, vs, vw * mu[:, None])
+    return out
+
+
+def coarsen_levels(geometry, n_levels=3, ratio=4.0, locate="device", device=0):
+    """``n_levels`` geometries from coarse to fine out of ONE: the finest is ``dict(geometry)``, every coarser level is
+    ``make_geometry(..., normalize=False)`` of ``coarsen(level above, ratio=ratio)`` with "kept" (its vertices as indices of the level
+    above), ``mu0`` / ``mu1`` restricted from the level above (``restrict_density``) and scaled to unit mass, and "build" =
+    {"coarsen_seconds", "locate_seconds", "locate"}.  Every level but the coarsest carries "transfer" (``cascade.mesh_transfer`` with
+    ``locate``, "device" | "exact" | "kdtree"; ``device``: the GPU of "device"), so the list is ready for
+    ``solver_socp_mesh_cascade`` / ``solver_socp_spacetime_cascade``.
+
+    ``ValueError`` when a level does not reach half the vertices of the one above (the mesh does not coarsen: too small, or all
+    boundary and creases), and where ``cascade.mesh_transfer`` raises."""
+    import time
+
+    from . import cascade
+
+    n_levels = int(n_levels)
+    if n_levels < 1:
+        raise ValueError("coarsen_levels: at least one level")
+    cascade.check_locate(locate, "coarsen_levels")
+    levels = [dict(geometry)]
+    for _ in range(n_levels - 1):
+        fine = levels[0]
+        t0 = time.perf_counter()
+        v, t, kept = coarsen(fine["vertices"], fine["triangles"], ratio=ratio)
+        t1 = time.perf_counter()
+        n_fine = np.asarray(fine["vertices"]).shape[0]
+        if 2 * v.shape[0] > n_fine:
+            raise ValueError(f"coarsen_levels: the mesh of {n_fine} vertices coarsens to {v.shape[0]} only, not to half: too few levels "
+                             "can be made of it")
+        coarse, _ = make_geometry(v, t, normalize=False)
+        coarse["kept"] = kept
+        t2 = time.perf_counter()
+        fine["transfer"] = cascade.mesh_transfer(coarse, fine, locate=locate, device=device)
+        t3 = time.perf_counter()
+        for k in ("mu0", "mu1"):
+            if fine.get(k) is not None:
+                mu = restrict_density(fine[k], fine["transfer"])
+                coarse[k] = mu / mu.sum()
+        coarse["build"] = {"coarsen_seconds": t1 - t0, "locate_seconds": t3 - t2, "locate": locate}
+        levels.insert(0, coarse)
     return levels
 
 

@@ -7,6 +7,8 @@
 ``solver_raw_mesh_cascade`` / ``solver_mesh_cascade``   the same through a coarse-to-fine cascade in space (solver_socp_mesh_cascade)
 ``solver_raw_spacetime_cascade`` / ``solver_spacetime_cascade``   the same through a cascade in space and time at once
                                                                   (solver_socp_spacetime_cascade)
+``solver_raw_auto_cascade`` / ``solver_auto_cascade``   the same through a cascade in space whose coarse meshes are made of the ONE
+                                                        geometry the plug-in receives (solver_socp_auto_cascade)
 
 Both take ``(n_time, geometry, **kwargs)`` and return ``(solution, run_history)``; they can be
 passed as ``solver=`` to the reference's ``run_dot_surface`` (interface.py:106-134).
@@ -18,12 +20,14 @@ the whole solution and converts it in numpy: the same values bit for bit, kept a
 """
 import numpy as np
 
-from .solver_socp import solver_socp, solver_socp_cascade, solver_socp_many, solver_socp_mesh_cascade, solver_socp_spacetime_cascade
+from .solver_socp import (solver_socp, solver_socp_auto_cascade, solver_socp_cascade, solver_socp_many, solver_socp_mesh_cascade,
+                          solver_socp_spacetime_cascade)
 
 __all__ = ["solver_socp", "solver_raw", "solver", "solver_socp_many", "solver_raw_many", "solver_many",
            "solver_socp_cascade", "solver_raw_cascade", "solver_cascade",
            "solver_socp_mesh_cascade", "solver_raw_mesh_cascade", "solver_mesh_cascade",
-           "solver_socp_spacetime_cascade", "solver_raw_spacetime_cascade", "solver_spacetime_cascade"]
+           "solver_socp_spacetime_cascade", "solver_raw_spacetime_cascade", "solver_spacetime_cascade",
+           "solver_socp_auto_cascade", "solver_raw_auto_cascade", "solver_auto_cascade"]
 
 
 def _socp_to_dot(solution_socp, geom):
@@ -191,6 +195,28 @@ def solver_spacetime_cascade(n_time, geometries, readout="device", **kwargs):
 
 
 solver_spacetime_cascade.__name__ = "dot_solver_socp_spacetime_cascade_center"
+
+
+def solver_raw_auto_cascade(n_time, geometry, readout="device", **kwargs):
+    """``solver_raw`` through a cascade in space made of ``geometry`` alone (``solver_socp_auto_cascade``: ``coarse_levels``, ``ratio``,
+    ``locate``, ``spacetime``, ``levels``, ``level_tol`` and the keywords of ``solver_socp``): the signature of ``solver_raw``, so it can be
+    passed as ``solver=`` where one geometry is handed over."""
+    solution_socp, run_history = solver_socp_auto_cascade(n_time, geometry, read_out=_read_out_spec(readout, False), **kwargs)
+    return _finish(solution_socp, geometry, None, None, readout, False), run_history
+
+
+solver_raw_auto_cascade.__name__ = "dot_solver_socp_auto_cascade"
+
+
+def solver_auto_cascade(n_time, geometry, readout="device", **kwargs):
+    """``solver`` through a cascade in space made of ``geometry`` alone: the density on the time-centred grid with mu0 / mu1 as end
+    points."""
+    mu0, mu1 = _end_points(geometry)
+    solution_socp, run_history = solver_socp_auto_cascade(n_time, geometry, read_out=_read_out_spec(readout, True), **kwargs)
+    return _finish(solution_socp, geometry, mu0, mu1, readout, True), run_history
+
+
+solver_auto_cascade.__name__ = "dot_solver_socp_auto_cascade_center"
 
 
 def solver_raw_many(n_time, geometry, problems, readout="device", **kwargs):

@@ -1125,3 +1125,72 @@ def solver_socp_spacetime_cascade(n_time, geometries, levels=None, level_tol=Non
         for a in (alm, coarse):
             if a is not None:
                 a.close()
+
+
+# ---- a cascade in space from ONE geometry: the levels are made here ----------------------------------------------------------------
+def _auto_cascade_options(n_time, coarse_levels, ratio, locate, spacetime, levels, level_tol, kwargs):
+    """The checks of solver_socp_auto_cascade, before the levels are built and any device is touched: the number of coarse levels."""
+    from .. import cascade
+
+    who = "solver_socp_auto_cascade"
+    if isinstance(coarse_levels, bool) or not isinstance(coarse_levels, (int, np.integer)) or coarse_levels < 0:
+        raise ValueError(f"{who}: coarse_levels must be an integer >= 0")
+    if not (isinstance(ratio, (int, float)) and ratio > 1):
+        raise ValueError(f"{who}: ratio must be a number > 1")
+    cascade.check_locate(locate, who)
+    for key in ("time_slab", "init_from", "init_parents", "init_transfer"):
+        if key in kwargs:
+            raise ValueError(f"{who}: {key} is not an option of the cascade in space")
+    unknown = set(kwargs) - set(CASCADE_KEYS)
+    if unknown:
+        raise ValueError(f"{who}: unknown option(s) {sorted(unknown)}")
+    if levels is not None and not spacetime:
+        raise ValueError(f"{who}: levels (one n_time per mesh level) needs spacetime=True")
+    lap_solver = kwargs.get("lap_solver", "modal_direct")
+    if lap_solver != "modal_direct" and lap_solver not in _lib.LAP_SOLVERS:
+        raise ValueError(f"lap_solver must be one of {['modal_direct'] + list(_lib.LAP_SOLVERS)}")
+    time_grids = cascade.check_spacetime_levels(levels, n_time, int(coarse_levels) + 1) if spacetime else [n_time]
+    for T in time_grids:
+        check_time_nodes(T, lap_solver)
+    tol = kwargs.get("tol", 1e-4)
+    if level_tol is not None and not (isinstance(level_tol, (int, float)) and level_tol > 0):
+        raise ValueError("level_tol must be a positive number")
+    _validate_checkpoints(kwargs.get("tol_checkpoints"), tol)
+    if kwargs.get("preconditioner", "multigrid") not in ("multigrid", "jacobi"):
+        raise ValueError("preconditioner must be 'multigrid' or 'jacobi'")
+    if int(kwargs.get("nit", 1000)) < 1:
+        raise ValueError("nit must be at least 1")
+    return int(coarse_levels)
+
+
+def solver_socp_auto_cascade(n_time, geometry, coarse_levels=2, ratio=4.0, locate="device", spacetime=False, levels=None, level_tol=None,
+                             read_out=None, **kwargs):
+    """``solver_socp`` through a cascade in space for a caller with ONE geometry: ``coarse_levels`` coarser meshes are made of it
+    (``meshes.coarsen_levels``: half-edge-collapse decimation by ``ratio`` per level on the host, every level located on the one below
+    with ``locate`` -- "device": ``dots_mesh_locate`` on the solver's GPU --, ``mu0`` / ``mu1`` restricted), then the levels are handed
+    to ``solver_socp_mesh_cascade``, or with ``spacetime=True`` to ``solver_socp_spacetime_cascade`` (``levels``: its ``n_time`` per mesh
+    level).  ``coarse_levels=0`` is ``solver_socp``.  The other keywords are those drivers'; ``time_limit`` covers the build (the
+    cascade gets the time that is left).
+
+    Returns ``(solution, run_history)`` of ``geometry``; ``run_history.solver_stats["auto_cascade"]`` = {"levels": [one record per
+    coarse level, coarse to fine: n_vertices, n_triangles, coarsen_seconds, locate_seconds, locate, max_distance (of the level above
+    from it)], "build_seconds"} next to the record of the driver that ran.  ``ValueError`` where ``meshes.coarsen_levels`` raises (a
+    mesh that does not coarsen); every option is checked before the levels are built."""
+    from .. import meshes
+
+    n_coarse = _auto_cascade_options(n_time, coarse_levels, ratio, locate, spacetime, levels, level_tol, kwargs)
+    if n_coarse == 0:
+        return solver_socp(n_time, geometry, read_out=read_out, **kwargs)
+    t_start = time.perf_counter()
+    geometries = meshes.coarsen_levels(geometry, n_coarse + 1, ratio=ratio, locate=locate, device=kwargs.get("device", 0))
+    build = time.perf_counter() - t_start
+    records = [dict(g["build"], n_vertices=int(np.asarray(g["vertices"]).shape[0]), n_triangles=int(np.asarray(g["triangles"]).shape[0]),
+                    max_distance=_max_distance(above)) for g, above in zip(geometries, geometries[1:])]
+    opts = dict(kwargs)
+    opts["time_limit"] = max(opts.get("time_limit", 1000) - build, 0.0)
+    if spacetime:
+        solution, hist = solver_socp_spacetime_cascade(n_time, geometries, levels=levels, level_tol=level_tol, read_out=read_out, **opts)
+    else:
+        solution, hist = solver_socp_mesh_cascade(n_time, geometries, level_tol=level_tol, read_out=read_out, **opts)
+    hist.solver_stats["auto_cascade"] = {"levels": records, "build_seconds": build}
+    return solution, hist

@@ -645,6 +645,44 @@ typedef struct dots_readout_desc {
 } dots_readout_desc;
 int dots_readout(dots_ctx *ctx, const dots_readout_desc *desc);
 
+/* ---- levels of a cascade in space from ONE mesh: coarsen on the host, locate on the device ------------------------------------
+ * dots_coarsen: half-edge-collapse decimation of the mesh (xyz [V][3], tri [F][3]) towards `n_target` vertices, host only (no
+ * device work; dots_socp_amd/meshes.py: coarsen(backend="python") is the specification and states the rules; both return the same
+ * arrays).  Coarse vertices are a subset of the fine ones.  Copy out with dots_coarsen_copy: kept [dots_coarsen_vertices] (ascending
+ * fine indices), tri [dots_coarsen_triangles][3] (the surviving triangles in fine order and corner order, in FINE vertex indices).
+ * The target may not be reached (nothing collapsible is left): the caller sees the count.
+ * DOTS_ERR_ARGUMENT before any work: NULL pointers, sizes < 1, n_target < 1, an index out of range, non-finite coordinates, a
+ * zero-area triangle, an edge with more than two triangles, two triangles crossing an edge in the same direction. */
+typedef struct dots_coarse_mesh dots_coarse_mesh;
+int dots_coarsen(int32_t n_vertices, int32_t n_triangles, const double *xyz, const int32_t *tri, int32_t n_target, dots_coarse_mesh **out);
+int64_t dots_coarsen_vertices(const dots_coarse_mesh *mesh);
+int64_t dots_coarsen_triangles(const dots_coarse_mesh *mesh);
+int dots_coarsen_copy(const dots_coarse_mesh *mesh, int32_t *kept, int32_t *tri);
+void dots_coarsen_free(dots_coarse_mesh *mesh);
+
+/* dots_mesh_locate: the closest point of the mesh (vertices, triangles) to every one of `points`, over ALL triangles, on device
+ * `device` (no context: it runs once per pair of levels).  Per point and triangle the region test of Ericson's closest point on a
+ * triangle in a fixed order of operations (dots_socp_amd/cascade.py: closest_scalar_order); the winner is the smallest (squared
+ * distance, triangle index).  The outputs equal cascade.locate_exact bit for bit.  With corner_points: for point i the corner of
+ * triangle[i] with the largest clamped weight of each of its three corner points with respect to that one triangle, the first
+ * maximum on a tie (cascade.corner_exact).  A uniform grid over the mesh is built on the host; one lane per point walks rings of
+ * cells until the best distance certifies the result or the ring covers the grid.
+ * DOTS_ERR_ARGUMENT (nothing launched): NULL desc or a NULL required pointer, sizes < 1, corner without corner_points, an index out of
+ * range, a zero-area triangle, non-finite coordinates or points; DOTS_ERR_NO_DEVICE without a HIP device. */
+typedef struct dots_mesh_locate_desc {
+    int32_t n_points, n_vertices, n_triangles, reserved;
+    const double *points;          /* host [n_points][3]                                                              */
+    const double *vertices;        /* host [n_vertices][3]                                                            */
+    const int32_t *triangles;      /* host [n_triangles][3]                                                           */
+    const double *corner_points;   /* NULL, or host [n_points][3][3]: three points per point, for `corner`           */
+    int32_t *triangle;             /* host out [n_points]                                                             */
+    double *weights;               /* host out [n_points][3]: clamped barycentric weights, >= 0, summing to 1         */
+    double *distance;              /* host out [n_points]                                                             */
+    int32_t *corner;               /* NULL, or host out [n_points][3] (needs corner_points)                           */
+    double *ms;                    /* NULL, or out: milliseconds of the launches on the device                        */
+} dots_mesh_locate_desc;
+int dots_mesh_locate(const dots_mesh_locate_desc *desc, int device);
+
 /* launches one direct solve takes: 2 x bands of tree heights (one per band and sweep; a band is one height unless
  * dots_front_desc.band_ptr merges heights), minus one with dots_front_desc.top_inverse */
 int dots_front_launches(dots_ctx *ctx);

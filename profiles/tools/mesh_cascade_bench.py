@@ -20,7 +20,13 @@ torus100k), and ``--depths`` counts coarse levels from the finest grid down (def
 the same bumps around the points of three vertices of the coarsest grid.  The seconds the hierarchy took to build (``hierarchy_s``:
 meshes, location, densities) are printed in every line; they are not part of the timed calls either.
 
-Prints one JSON line per call (kind = "cold" / "cascade") and a summary line.  The transfer's device milliseconds are set against the
+``--coarsen K`` adds ``solver_socp_auto_cascade`` with K coarse levels to the alternation (kind = "auto"): the caller has the finest
+mesh only, the coarse levels are decimated from it (``meshes.coarsen_levels``) and located on the device INSIDE the timed call.  Before
+the alternation one line (kind = "levels") gives, per pair of decimated levels, the seconds of the coarsening and of
+``cascade.mesh_transfer`` with ``locate="kdtree"`` and ``locate="device"`` (entry to return, and the kernels' own milliseconds).
+``torus400x250`` is bench.py's own torus: one nested level exists below it (``--depths 1``).
+
+Prints one JSON line per call (kind = "cold" / "cascade" / "auto") and a summary line.  The transfer's device milliseconds are set against the
 bytes it moves (every source and destination array once) at 6.3 TB/s, the copy rate DESIGN.md quotes.  bench.py is unchanged."""
 import argparse
 import json
@@ -32,7 +38,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 
 COPY_BPS = 6.3e12
-GRIDS = {"torus100k": ("torus", 400, 256), "knot": ("knot", 216, 20), "torus6k": ("torus", 96, 64)}
+GRIDS = {"torus100k": ("torus", 400, 256), "torus400x250": ("torus", 400, 250), "knot": ("knot", 216, 20), "torus6k": ("torus", 96, 64)}
 
 
 def generator(kind, nu, nv):
@@ -86,6 +92,34 @@ def build_grid_levels(mesh, grids):
     return meshes.link_levels(geoms, densities=dens)
 
 
+def level_pair_times(fine, n_coarse):
+    """Per pair of decimated levels below ``fine`` (fine to coarse): the seconds of the coarsening, of mesh_transfer with the kd-tree
+    candidates on the host and with the exact location on the device, and the device milliseconds of the location kernels."""
+    import numpy as np
+
+    from dots_socp_amd import cascade, meshes
+
+    pairs, above = [], fine
+    for _ in range(n_coarse):
+        t0 = time.perf_counter()
+        v, t, _ = meshes.coarsen(above["vertices"], above["triangles"])
+        t1 = time.perf_counter()
+        below, _ = meshes.make_geometry(v, t, normalize=False)
+        t2 = time.perf_counter()
+        cascade.mesh_transfer(below, above, locate="kdtree")
+        t3 = time.perf_counter()
+        cascade.mesh_transfer(below, above, locate="device")
+        t4 = time.perf_counter()
+        tf = np.asarray(above["triangles"])
+        vf = np.asarray(above["vertices"], dtype=np.float64)
+        timing = {}
+        cascade.locate_device(np.concatenate([vf, (vf[tf[:, 0]] + vf[tf[:, 1]] + vf[tf[:, 2]]) / 3.0]), v, t, timing=timing)
+        pairs.append({"fine_vertices": int(vf.shape[0]), "coarse_vertices": int(v.shape[0]), "coarsen_s": round(t1 - t0, 4),
+                      "locate_kdtree_s": round(t3 - t2, 4), "locate_device_s": round(t4 - t3, 4), "locate_kernel_ms": round(timing["kernel_ms"], 3)})
+        above = below
+    return pairs
+
+
 def sync():
     import torch
 
@@ -102,12 +136,13 @@ def main():
     ap.add_argument("--depths", default=None, help="comma-separated numbers of coarse levels (default 1,2,3; with --grids every depth the list allows)")
     ap.add_argument("--grids", default=None, help="the hierarchy as generator grids, coarse to fine, e.g. 100x63,200x125,400x250 (located levels)")
     ap.add_argument("--level-tol", type=float, default=None)
+    ap.add_argument("--coarsen", type=int, default=0, help="add the auto cascade with this many decimated coarse levels (built inside the timed call)")
     ap.add_argument("--congestion", type=float, default=0.0)
     a = ap.parse_args()
 
     import numpy as np
 
-    from dots_socp_amd.socp import solver_socp, solver_socp_mesh_cascade
+    from dots_socp_amd.socp import solver_socp, solver_socp_auto_cascade, solver_socp_mesh_cascade
 
     t_build = time.perf_counter()
     if a.grids:
@@ -129,13 +164,18 @@ def main():
     if a.grids:
         base["grids"] = a.grids
     best = {}
+    plain = {k: v for k, v in fine.items() if k not in ("parents", "transfer")}      # what a caller with one mesh has
+    if a.coarsen:
+        print(json.dumps(dict(base, kind="levels", pairs=level_pair_times(plain, a.coarsen))), flush=True)
     for rep in range(a.reps):
-        for depth in [0] + depths:
-            kind = "cold" if depth == 0 else "cascade"
+        for depth in [0] + depths + (["auto"] if a.coarsen else []):
+            kind = "cold" if depth == 0 else "auto" if depth == "auto" else "cascade"
             sync()
             t0 = time.perf_counter()
             if depth == 0:
                 sol, hist = solver_socp(a.T, fine, **common)
+            elif depth == "auto":
+                sol, hist = solver_socp_auto_cascade(a.T, plain, coarse_levels=a.coarsen, level_tol=a.level_tol, **common)
             else:
                 sol, hist = solver_socp_mesh_cascade(a.T, deepest[-depth - 1:], level_tol=a.level_tol, **common)
             sync()
@@ -143,6 +183,9 @@ def main():
             out = dict(base, kind=kind, depth=depth, rep=rep, wall_s=round(wall, 4), iterations=int(hist.kkt_iteration[-1]) + 1,
                        running_time=round(float(hist.running_time), 4), cost=float(hist.history["Transportation cost"][-1]),
                        kkt_max=float(np.nanmax(np.asarray(hist.kkt_errors[-1], dtype=np.float64))))
+            if depth == "auto":
+                out["coarse_levels"] = a.coarsen
+                out["build"] = hist.solver_stats["auto_cascade"]
             if depth:
                 rec = hist.solver_stats["mesh_cascade"]["levels"]
                 for r in rec:
@@ -155,7 +198,7 @@ def main():
             del sol, hist
             print(json.dumps(out), flush=True)
     print(json.dumps(dict(base, kind="summary", level_tol=a.level_tol, cold_wall_s=round(best[0], 4),
-                          cascade_wall_s={str(d): round(best[d], 4) for d in depths},
+                          cascade_wall_s={str(d): round(best[d], 4) for d in depths}, auto_wall_s=round(best["auto"], 4) if a.coarsen else None,
                           cold_over_cascade={str(d): round(best[0] / best[d], 3) for d in depths})), flush=True)
 
 
