@@ -33,6 +33,7 @@ EXPORTS = [
     "dots_patch_order", "dots_assemble", "dots_assemble_nnz", "dots_assemble_copy", "dots_assemble_free", "dots_symbolic_build", "dots_symbolic_front_rows", "dots_symbolic_copy", "dots_symbolic_free",
     "dots_front_share", "dots_laplacian_solve_many", "dots_step_many", "dots_bench_many", "dots_prolong_time", "dots_readout",
     "dots_prolong_space", "dots_transfer_space", "dots_carry_spacetime",
+    "dots_pcg_windows",
     "dots_coarsen", "dots_coarsen_vertices", "dots_coarsen_triangles", "dots_coarsen_copy", "dots_coarsen_free", "dots_mesh_locate",
 ]
 
@@ -63,6 +64,9 @@ STEP_PATH_QL_Z_SHIFT = 11
 CG_PATH_COUNTER = 13
 CG_PATH = {"modal": 1, "collapse": 2, "small_wg": 4, "mg": 8}
 CG_PATH_VT_SHIFT, CG_PATH_CAP_SHIFT, CG_PATH_G_SHIFT = 8, 20, 32
+# dots_debug_counter(14): windows of the last PCG solve (low byte) and whether the windowed transforms ran (dots_pcg_windows)
+PCG_WINDOWS_COUNTER = 14
+PCG_WINDOWS_TRANSFORMS = 256
 
 
 _i32p = C.POINTER(C.c_int32)
@@ -308,6 +312,7 @@ def load(host_only=False):
     lib.dots_mg_apply.argtypes = [vp, _f64p, _f64p, _f64p, _i32p]
     lib.dots_front_setup.argtypes = [vp, C.POINTER(FrontDesc)]
     lib.dots_front_enable.argtypes = [vp, C.c_int]
+    lib.dots_pcg_windows.argtypes = [vp, C.c_int]
     lib.dots_front_pitch.argtypes = [vp]
     lib.dots_front_launches.argtypes = [vp]
     lib.dots_front_info.argtypes = [vp, _f64p]

@@ -316,9 +316,10 @@ static int flush_division(Ctx *c) {
 }
 
 // The modal PCG keeps per-mode scalars for NC <= CgScalOffsets::NCMAX = 256 modes: a modal context of T + 1 > 256 steps with the
-// direct solver only (a factor installed or shared, and enabled).
+// direct solver only (a factor installed or shared, and enabled), unless the caller switched the windowed PCG on (dots_pcg_windows).
 static int modal_needs_factor(const Ctx *c, const char *what) {
     if (c->lap_solver != DOTS_LAP_MODAL_PCG || c->dcg.cg_ncol <= CgScalOffsets::NCMAX || (c->use_front && c->front.n_nodes > 0)) return 0;
+    if (pcg_windowed(c)) return 0;      // dots_pcg_windows: the PCG takes the modes in windows of 256
     set_error(std::string(what) + ": T + 1 > 256 needs the direct solver (dots_front_setup); the modal PCG takes T + 1 <= 256");
     return DOTS_ERR_STATE;
 }
@@ -608,7 +609,7 @@ int dots_destroy(dots_ctx *c) {
     if (!c) return 0;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->cg_graph) (void)hipGraphExecDestroy(c->cg_graph);
+    c->cg_graphs_release();
     for (int i = 0; i < c->n_mg_allocs; ++i) (void)hipFree(c->mg_allocs[i]);
     for (int i = 0; i < c->n_front_allocs; ++i) (void)hipFree(c->front_allocs[i]);
     for (int i = 0; i < c->n_allocs; ++i) (void)hipFree(c->allocs[i]);
@@ -1080,12 +1081,14 @@ int dots_mg_setup(dots_ctx *c, const dots_mg_desc *m) {
     if (rc) return rc;
     if (!m || m->n_levels < 2 || m->n_levels > 10 || !m->levels || !m->coarse_inverse) { set_error("mg_setup: bad description"); return DOTS_ERR_ARGUMENT; }
     if (c->lap_solver != DOTS_LAP_MODAL_PCG) { set_error("multigrid needs the modal solver"); return DOTS_ERR_ARGUMENT; }
-    if (c->dcg.cg_ncol > CgScalOffsets::NCMAX) { set_error("mg_setup: the modal PCG takes T + 1 <= 256; above, use the direct solver (dots_front_setup)"); return DOTS_ERR_STATE; }
+    const bool windowed = c->pcg_windows && c->shard_stride == 0 && c->dcg.cg_ncol > CgScalOffsets::NCMAX;      // one coarse inverse per window of 256 modes
+    if (c->dcg.cg_ncol > CgScalOffsets::NCMAX && !windowed) { set_error("mg_setup: the modal PCG takes T + 1 <= 256; above, use the direct solver (dots_front_setup)"); return DOTS_ERR_STATE; }
     if (m->levels[0].n != c->d.V || m->n_cols != c->dcg.cg_ncol) { set_error("mg_setup: level 0 / mode count mismatch"); return DOTS_ERR_ARGUMENT; }
     DOTS_HIP(hipStreamSynchronize(c->stream));
-    if (c->cg_graph) { (void)hipGraphExecDestroy(c->cg_graph); c->cg_graph = nullptr; }
+    c->cg_graphs_release();
     mg_release(c);
-    const Dev &d = c->dcg;   // level vectors and the coarse inverse use the PCG view's pitch
+    // level vectors and the coarse inverse use the PCG view's pitch; windowed: a window's (256 columns), the vectors reused by every window
+    const Dev d = windowed ? pcg_window_view(c->dcg, 0) : c->dcg;
     MgDev g{};
     g.nlev = m->n_levels;
     g.omega = m->omega;
@@ -1133,16 +1136,20 @@ int dots_mg_setup(dots_ctx *c, const dots_mg_desc *m) {
         }
     }
     // coarse inverse: host [nL][nL][n_cols] -> device [nL][nL][TP]
+    // (windowed: block w = the modes [256 w, 256 w + 256), [nL][nL][256] each, one after the other)
     const int nL = m->levels[m->n_levels - 1].n;
-    std::vector<double> inv((size_t)nL * nL * d.TP, 0.0);
+    const int n_win = windowed ? pcg_window_count(c->dcg) : 1;
+    const size_t block = (size_t)nL * nL * d.TP;
+    std::vector<double> inv(block * n_win, 0.0);
     for (int64_t ij = 0; ij < (int64_t)nL * nL; ++ij)
-        for (int k = 0; k < m->n_cols; ++k) inv[(size_t)ij * d.TP + k] = m->coarse_inverse[(size_t)ij * m->n_cols + k];
+        for (int k = 0; k < m->n_cols; ++k) inv[(size_t)(k / d.TP) * block + (size_t)ij * d.TP + k % d.TP] = m->coarse_inverse[(size_t)ij * m->n_cols + k];
     if ((rc = mg_upload(c, &g.coarse_inv, inv.data(), (int64_t)inv.size()))) { mg_release(c); return rc; }
     // mg_release() reset c->mg; the level pointers were written into the local copy
     for (int l = 0; l < g.nlev; ++l) c->mg.lv[l] = g.lv[l];
     c->mg.nlev = g.nlev;
     c->mg.omega = g.omega;
     c->mg.coarse_inv = g.coarse_inv;
+    c->mg.coarse_win_stride = windowed ? (int64_t)block : 0;
     return 0;
 }
 
@@ -1161,6 +1168,7 @@ int dots_mg_apply(dots_ctx *c, const double *r, double *z, double *rz, const int
     if (rc) return rc;
     if (c->lap_solver != DOTS_LAP_MODAL_PCG) { set_error("mg_apply: the V-cycle belongs to the modal solver"); return DOTS_ERR_STATE; }
     if (c->shard_stride != 0) { set_error("mg_apply: not on a time slab"); return DOTS_ERR_STATE; }
+    if (c->dcg.cg_ncol > CgScalOffsets::NCMAX) { set_error("mg_apply: one V-cycle on all modes takes T + 1 <= 256 (a windowed context cycles inside its solves only)"); return DOTS_ERR_STATE; }
     if (c->mg.nlev < 2) { set_error("mg_apply: no multigrid hierarchy on this context (dots_mg_setup)"); return DOTS_ERR_STATE; }
     if (!r || !z || !rz) { set_error("mg_apply: null array"); return DOTS_ERR_ARGUMENT; }
     const Dev &g = c->dcg;
@@ -1793,6 +1801,24 @@ int dots_front_enable(dots_ctx *c, int on) {
     return 0;
 }
 
+int dots_pcg_windows(dots_ctx *c, int on) {
+    int rc = check(c);
+    if (rc) return rc;
+    if (c->lap_solver != DOTS_LAP_MODAL_PCG) { set_error("pcg_windows: the windows belong to the modal solver (DOTS_LAP_MODAL_PCG)"); return DOTS_ERR_STATE; }
+    if (c->shard_stride != 0) { set_error("pcg_windows: not on a time slab"); return DOTS_ERR_STATE; }
+    on = on ? 1 : 0;
+    if (on == c->pcg_windows) return 0;
+    // a hierarchy installed under the other setting has the other layout (level vectors and coarse inverse per window): it goes, with the graphs
+    if (c->dcg.cg_ncol > CgScalOffsets::NCMAX) {
+        DOTS_HIP(hipStreamSynchronize(c->stream));
+        c->cg_graphs_release();
+        mg_release(c);
+    }
+    c->pcg_windows = on;
+    c->pcg_windows_ran = 0;
+    return 0;
+}
+
 int dots_front_launches(dots_ctx *c) {
     if (check(c) || c->front.n_nodes == 0) return -1;
     return 2 * c->sched.n_bands - (c->sched.top_inverse ? 1 : 0);
@@ -1831,6 +1857,7 @@ int64_t dots_debug_counter(dots_ctx *c, int which) {
         case 11: return c->mg_path;                   // MG_PATH_* bits of the last V-cycle enqueued (dots_dev.h)
         case 12: return c->step_path;                 // STEP_PATH_* bits of the last iteration's launches (dots_dev.h)
         case 13: return c->cg_path;                   // CG_PATH_* bits and tiling of the last PCG launches (dots_dev.h)
+        case 14: return c->pcg_windows_ran;           // low byte: windows the last PCG solve ran (0: none yet, or unwindowed); bit 8: the windowed transforms ran
         default: return -1;
     }
 }

@@ -167,7 +167,8 @@ enum {
 struct MgDev {
     int nlev = 0;
     MgLevelDev lv[10]{};
-    const double *coarse_inv = nullptr;      // [nL][nL][TP]
+    const double *coarse_inv = nullptr;      // [nL][nL][TP]; on a windowed context one block [nL][nL][256] per window, one after the other
+    int64_t coarse_win_stride = 0;           // doubles per window block (0: installed unwindowed)
     double omega = 2.0 / 3.0;
 };
 
@@ -318,6 +319,20 @@ struct KktFused {
 };
 constexpr uint32_t KKT_FUSED_MASK = 1u | 2u | 8u | 64u;
 
+// What the PCG keeps between solves per set of columns it iterates on: the instantiated hipGraph of `iters` iterations (Dev is captured by
+// value, so a window of modes has its own) and the iteration count that sizes the next solve's first burst
+struct CgCache {
+    hipGraphExec_t graph = nullptr;
+    int iters = 0;
+    double eps = -1.0, tol = -1.0;
+    int mg = -1;
+    int last_iters = 0;
+};
+constexpr int PCG_WINDOW = CgScalOffsets::NCMAX;      // modes per window of a windowed context (dots_pcg_windows)
+constexpr int PCG_WINDOW_SHIFT = 8;
+constexpr int PCG_MAX_WINDOWS = TILE_ELEMS / PCG_WINDOW;
+static_assert((1 << PCG_WINDOW_SHIFT) == PCG_WINDOW, "window pitch");
+
 struct Ctx;
 // ---- launch wrappers implemented in the kernel files (all asynchronous on ctx stream) ----
 int launch_soc_projection(Ctx *c, int zmid_mode = 0, bool with_inverse = false);   // 0: write z_mid; 1: write only the cone multiplier; with_inverse: extra workgroups do the modes -> time transform of phi
@@ -358,7 +373,8 @@ int front_solve(Ctx *c, const double *bhat, double *y, double *x);   // x = A^-1
 int front_solve_many(Ctx *const *cs, int n, const double *const *bhat, double *const *y, double *const *x);
 void modes_forward(Ctx *c, const double *in, double *out, bool direct);   // the time transforms around step 1's solve (one GPU)
 void modes_inverse(Ctx *c, const double *x, double *phi, bool direct);
-int mg_vcycle(Ctx *c, const double *r, double *z, double *t0, double *rz_part, int nb, int ept, int vt, int G);  // enqueue z = MG(r); z holds D^-1 r on entry
+// enqueue z = MG(r) on the PCG view d (the context's own, or one window of it) with that view's coarse inverse; z holds D^-1 r on entry
+int mg_vcycle(Ctx *c, const Dev &d, const double *coarse_inv, const double *r, double *z, double *t0, double *rz_part, int nb, int ept, int vt, int G);
 int cg_mg_apply(Ctx *c, double *rz);        // dots_mg_apply: one V-cycle on what dcg.cg_r holds, as the PCG launches it; rz[mode] = sum of the r.z partial rows
 int kkt_evaluate(Ctx *c, uint32_t mask, double *out);
 int kkt_sums(Ctx *c, uint32_t mask, double *sums);                          // the weighted sums of this context's time slab
@@ -429,11 +445,12 @@ struct Ctx {
     int front_tune = 0;           // DOTS_FRONT_TUNE=1 print the per-band timing table, 2 also apply the fastest choice
     int *h_flags = nullptr;
     int n_partial_blocks = 0;
-    int last_cg_iters = 0;
+    int last_cg_iters = 0;        // iterations of the last solve (windowed: of its slowest window)
+    int pcg_windows = 0;          // dots_pcg_windows: above 256 modes and without an enabled factor, step 1 solves the modes in windows of 256
+    int pcg_windows_ran = 0;      // dots_debug_counter 14: windows of the last PCG solve (0: unwindowed), bit 8: the windowed transforms ran
     MgDev mg{};                   // multigrid preconditioner (nlev == 0: Jacobi only)
     int use_mg = 1;
     int mg_path = 0;              // MG_PATH_* of the last mg_vcycle (0: none since mg_release / dots_mg_enable(0))
-    int cg_graph_mg = -1;
     int64_t cg_path = 0;          // CG_PATH_* of the last PCG tiling handed to a launch (make_args, kernels_cg.hip; 0: none yet)
     int kkt_two = 1;              // KKT sums with two nodes per lane (one GPU; DOTS_KKT_TWO=0: one)
     // DOTS_STEP_TIMED: phase events of enqueue-only steps, collected later by dots_step_times (no host wait in the loop)
@@ -507,11 +524,13 @@ struct Ctx {
     double c_prim_q = 0, c_prim_z = 0, c_dual_alpha = 0, c_dual_beta = 0, c_comp_rho = 0, c_comp_m = 0;
     void *allocs[64]{};
     int n_allocs = 0;
-    // hipGraph cache of the PCG iteration body
-    hipGraphExec_t cg_graph = nullptr;
-    int cg_graph_iters = 0;
-    double cg_graph_eps = -1.0;
-    double cg_graph_tol = -1.0;
+    // hipGraph cache of the PCG iteration body: the context's own columns, and one per window of a windowed context
+    CgCache cgc{};
+    CgCache cgw[PCG_MAX_WINDOWS]{};
+    void cg_graphs_release() {
+        for (CgCache *k : {&cgc, &cgw[0], &cgw[1], &cgw[2], &cgw[3]})
+            if (k->graph) { (void)hipGraphExecDestroy(k->graph); k->graph = nullptr; }
+    }
     double *arr(int id) {
         double *t[12] = {d.phi, d.A, d.B, d.lam, d.zf, d.zm, d.ze, d.mu, d.E, d.bf, d.bm, d.be};
         return t[id];
@@ -554,6 +573,27 @@ inline bool rhs_writes_modes(const Ctx *c) {
 }
 
 inline bool soc_takes_inverse(const Ctx *c) { return rhs_writes_modes(c) && !time_modes_mfma_ok(c->d); }
+// Windowed modal PCG (dots_pcg_windows): one GPU, more than 256 modes, no enabled factor.  Mode space is then COMPACT: window k = modes
+// [256 k, 256 k + 256) of a PCG vector is a [V][256] array at base + k V 256 (the windows of a pitch-512 / 1024 array fill it exactly).
+inline bool pcg_windowed(const Ctx *c) {
+    return c->pcg_windows && c->lap_solver == DOTS_LAP_MODAL_PCG && c->shard_stride == 0 && c->dcg.cg_ncol > PCG_WINDOW &&
+           !(c->use_front && c->front.n_nodes > 0);
+}
+inline int pcg_window_count(const Dev &g) { return (g.cg_ncol + PCG_WINDOW - 1) / PCG_WINDOW; }
+// the PCG kernels' view of window k: pitch 256, its own tiling, column count, sigma slice and vectors
+inline Dev pcg_window_view(const Dev &g, int k) {
+    Dev w = g;
+    w.TP = PCG_WINDOW;
+    w.tp_shift = PCG_WINDOW_SHIFT;
+    w.VT = w.FT = TILE_ELEMS / PCG_WINDOW;
+    w.n_vtiles = (g.V + w.VT - 1) / w.VT;
+    w.n_ftiles = (3 * g.F + w.FT - 1) / w.FT;
+    w.cg_ncol = g.cg_ncol - k * PCG_WINDOW < PCG_WINDOW ? g.cg_ncol - k * PCG_WINDOW : PCG_WINDOW;
+    w.sigma = g.sigma + k * PCG_WINDOW;
+    const int64_t off = (int64_t)k * g.V * PCG_WINDOW;
+    w.cg_r = g.cg_r + off; w.cg_z = g.cg_z + off; w.cg_p0 = g.cg_p0 + off; w.cg_p1 = g.cg_p1 + off; w.cg_Ap = g.cg_Ap + off; w.cg_x = g.cg_x + off;
+    return w;
+}
 // steps 2+3 can form the next iteration's per-corner gathers (k_q_lambda_mult_carry: whole triangles per 192-lane workgroup)
 // (one GPU or a time slab; the direct solver's iteration)
 inline bool carry_possible(const Ctx *c) {

@@ -15,7 +15,9 @@
 //   MODAL      the orthonormal time eigen-basis Q (DCT-II) block-diagonalises K into T+1 shifted
 //              surface problems K_space + (sigma_a + eps) M; they are solved as one batched PCG with
 //              per-column scalars; converged columns are frozen and skipped.  Preconditioner: Jacobi,
-//              or the multigrid V-cycle of kernels_mg.hip when a hierarchy has been uploaded.
+//              or the multigrid V-cycle of kernels_mg.hip when a hierarchy has been uploaded.  The kernels hold 256 columns;
+//              above, a context that opted in (dots_pcg_windows) runs them window by window of 256 modes through
+//              pitch-256 views (pcg_window_view), between the windowed time transforms (k_time_modes_windows).
 //
 // One Jacobi-PCG iteration is TWO kernels and no host round trip:
 //   k_cg_apply   beta from the r.z partial sums of the previous kernel; p = z + beta p_old formed on the
@@ -530,6 +532,99 @@ static void launch_time_modes_wide(Ctx *c, const double *Qe, const double *x, do
     else hipLaunchKernelGGL(k_time_modes_wide<1024>, grid, dim3(1024), time_modes_wide_lds<1024>(), c->stream, d, Qe, x, y);
 }
 
+// The transforms of a WINDOWED context (dots_pcg_windows: T + 1 in (256, 1024], no factor): k_time_modes_wide's tiling, k slices and
+// fixed order of the k steps, with the mode side compact -- mode a of vertex v lives at (a >> 8) V 256 + (v << 8) + (a & 255), so
+// that window k = modes [256 k, 256 k + 256) is the [V][256] array the PCG's pitch-256 view indexes.  A wavefront's 64 columns lie in one window.
+//   FWD   x: time space at the full pitch; y: windows.  Columns past T + 1 are not stored: a window without a live mode is never written.
+//         emit_col0: the workgroup's sum of mode 0 over its 32 vertices goes to d.partials[blockIdx.x], summed in vertex order (k_cg_bmean)
+//   !FWD  x: windows; y: time space at the full pitch (Qe = the transposed, zero-padded Q)
+template <int TPC, bool FWD>
+__global__ __launch_bounds__(TPC) void k_time_modes_windows(Dev d, const double *__restrict__ Qe, const double *__restrict__ x, double *__restrict__ y,
+                                                            int emit_col0) {
+    constexpr int KS = 4096 / TPC;
+    constexpr int QLD = TPC + 16;
+    constexpr int XLD = KS + 1;
+    extern __shared__ double tw_lds[];
+    double *Qs = tw_lds;                        // [KS][QLD]
+    double *xs = tw_lds + KS * QLD;             // [TM_ROWS][XLD]
+    const int n = d.T + 1, tid = threadIdx.x;
+    const int lane = tid & 63, w = tid >> 6, li = lane & 15, lk = lane >> 4;
+    const int v0 = blockIdx.x * TM_ROWS;
+    const int64_t wstride = (int64_t)d.V << PCG_WINDOW_SHIFT;      // doubles per window
+    const bool live = w * 64 < n;               // this wavefront stores at least one column (the others only help to stage)
+    mfma_f64x4 acc[2][4];
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = mfma_f64x4{0.0, 0.0, 0.0, 0.0};
+    for (int k0 = 0; k0 < n; k0 += KS) {
+        if (k0 > 0) __syncthreads();
+#pragma unroll
+        for (int i = 0; i < KS; ++i) Qs[i * QLD + tid] = Qe[(int64_t)(k0 + i) * TPC + tid];      // rows past T + 1 are zero
+        for (int e = tid; e < TM_ROWS * KS; e += TPC) {
+            const int vl = e / KS, kk = e % KS, v = v0 + vl, a = k0 + kk;
+            double xv = 0.0;
+            if (v < d.V && a < n)
+                xv = FWD ? x[idxV(d, v, a)] : x[(a >> PCG_WINDOW_SHIFT) * wstride + ((int64_t)v << PCG_WINDOW_SHIFT) + (a & (PCG_WINDOW - 1))];
+            xs[vl * XLD + kk] = xv;
+        }
+        __syncthreads();
+        if (live) {
+#pragma unroll
+            for (int kk = 0; kk < KS; kk += 4) {
+                const double a0 = xs[li * XLD + kk + lk], a1 = xs[(16 + li) * XLD + kk + lk];
+                const double *bq = Qs + (kk + lk) * QLD + w * 64 + li;
+#pragma unroll
+                for (int ct = 0; ct < 4; ++ct) {
+                    const double b = bq[ct * 16];
+                    acc[0][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b, acc[0][ct], 0, 0, 0);
+                    acc[1][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b, acc[1][ct], 0, 0, 0);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) {
+        const int j = w * 64 + ct * 16 + li;
+        if (j >= n) continue;
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int v = v0 + rt * 16 + lk + 4 * r;
+                if (v >= d.V) continue;
+                if (FWD) y[(j >> PCG_WINDOW_SHIFT) * wstride + ((int64_t)v << PCG_WINDOW_SHIFT) + (j & (PCG_WINDOW - 1))] = acc[rt][ct][r];
+                else y[idxV(d, v, j)] = acc[rt][ct][r];
+            }
+    }
+    if (FWD && emit_col0) {      // mode 0 of the 32 vertices sits in wavefront 0, column tile 0, lanes 0, 16, 32, 48 (rows past V are zero)
+        __syncthreads();         // every wavefront is done with the last slice: xs is free
+        if (w == 0 && li == 0) {
+#pragma unroll
+            for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) xs[rt * 16 + lk + 4 * r] = acc[rt][0][r];
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double s = 0.0;
+            for (int i = 0; i < TM_ROWS; ++i) s += xs[i];
+            d.partials[blockIdx.x] = s;
+        }
+    }
+}
+static int windows_transform_grid(const Dev &d) { return (d.V + TM_ROWS - 1) / TM_ROWS; }
+template <bool FWD>
+static void launch_time_modes_windows(Ctx *c, const double *x, double *y, int emit_col0) {
+    const Dev &d = c->d;
+    const double *Qe = FWD ? d.Qpad : d.QpadT;
+    const dim3 grid(windows_transform_grid(d));
+    if (d.TP == 512)
+        hipLaunchKernelGGL((k_time_modes_windows<512, FWD>), grid, dim3(512), time_modes_wide_lds<512>(), c->stream, d, Qe, x, y, emit_col0);
+    else
+        hipLaunchKernelGGL((k_time_modes_windows<1024, FWD>), grid, dim3(1024), time_modes_wide_lds<1024>(), c->stream, d, Qe, x, y, emit_col0);
+}
+
 // ------------------------------------------------------------------------------------------
 // host driver
 // ------------------------------------------------------------------------------------------
@@ -577,8 +672,7 @@ static void cg_tiling(const Dev &d, int *nb_out, int *ept_out, int *vt_out, int 
     *collapse_out = collapse;
 }
 
-static CgArgs make_args(Ctx *c, bool modal) {
-    const Dev &d = modal ? c->dcg : c->d;
+static CgArgs make_args(Ctx *c, const Dev &d, bool modal) {
     CgArgs a{};
     cg_tiling(d, &a.nb, &a.ept, &a.vt, &a.G, &a.collapse);
     a.cap = a.vt * 12 + 64;          // ~7 entries per row on a triangle mesh; entries beyond cap are read from global
@@ -594,12 +688,17 @@ static CgArgs make_args(Ctx *c, bool modal) {
                  ((int64_t)a.vt << CG_PATH_VT_SHIFT) | ((int64_t)a.cap << CG_PATH_CAP_SHIFT) | ((int64_t)a.G << CG_PATH_G_SHIFT);
     return a;
 }
+static CgArgs make_args(Ctx *c, bool modal) { return make_args(c, modal ? c->dcg : c->d, modal); }
 
 int64_t cg_partials_needed(const Dev &d) {
     int nb, ept, vt, G, collapse;
     cg_tiling(d, &nb, &ept, &vt, &G, &collapse);
     // G rows per array + one collapsed row each + the intermediate rows of the two-stage collapse
-    return N_PART_ARRAYS * (int64_t)d.TP * (G + 1) + (int64_t)COLLAPSE_STAGE * d.TP;
+    const int64_t own = N_PART_ARRAYS * (int64_t)d.TP * (G + 1) + (int64_t)COLLAPSE_STAGE * d.TP;
+    if (d.TP <= PCG_WINDOW) return own;
+    // a wide context may solve in windows (dots_pcg_windows): the pitch-256 view has its own tiling, and the windowed forward
+    // transform leaves one column-0 sum per workgroup in front
+    return std::max<int64_t>({own, cg_partials_needed(pcg_window_view(d, 0)), (int64_t)windows_transform_grid(d)});
 }
 
 // sum partial array k into its collapsed row (no-op for problems small enough to re-reduce in the consumers)
@@ -611,8 +710,7 @@ static void collapse_if_needed(Ctx *c, const Dev &d, const CgArgs &a, int k) {
 }
 
 template <bool MODAL>
-static int cg_iterations(Ctx *c, CgArgs a, double *x, int n_iter) {
-    const Dev &d = MODAL ? c->dcg : c->d;
+static int cg_iterations(Ctx *c, const Dev &d, const double *coarse_inv, CgArgs a, double *x, int n_iter) {
     const size_t lds = cg_lds_bytes(a.cap, a.vt, a.nb);
     for (int it = 0; it < n_iter; ++it) {
         const bool odd = (it & 1) != 0;
@@ -627,7 +725,7 @@ static int cg_iterations(Ctx *c, CgArgs a, double *x, int n_iter) {
         hipLaunchKernelGGL((k_cg_update<MODAL>), dim3(a.G), dim3(a.nb), lds, c->stream, d, a);
         collapse_if_needed(c, d, a, idx_crit(a, a.parity ^ 1));
         if (a.mg) {
-            int rc = mg_vcycle(c, d.cg_r, d.cg_z, d.cg_Ap, d.partials + part_rz(a, a.parity ^ 1), a.nb, a.ept, a.vt, a.G);
+            int rc = mg_vcycle(c, d, coarse_inv, d.cg_r, d.cg_z, d.cg_Ap, d.partials + part_rz(a, a.parity ^ 1), a.nb, a.ept, a.vt, a.G);
             if (rc) return rc;
             collapse_if_needed(c, d, a, idx_rz(a.parity ^ 1));
         }
@@ -638,34 +736,32 @@ static int cg_iterations(Ctx *c, CgArgs a, double *x, int n_iter) {
 
 // Instantiate (once per eps / tolerance / preconditioner) a hipGraph holding `unit` PCG iterations.
 template <bool MODAL>
-static int cg_graph_prepare(Ctx *c, const CgArgs &a, double *x, int unit) {
-    if (c->cg_graph && c->cg_graph_iters == unit && c->cg_graph_eps == c->prm.eps && c->cg_graph_tol == c->prm.cg_tol &&
-        c->cg_graph_mg == a.mg)
-        return 0;
-    if (c->cg_graph) {
-        (void)hipGraphExecDestroy(c->cg_graph);
-        c->cg_graph = nullptr;
+static int cg_graph_prepare(Ctx *c, CgCache &k, const Dev &d, const double *coarse_inv, const CgArgs &a, double *x, int unit) {
+    if (k.graph && k.iters == unit && k.eps == c->prm.eps && k.tol == c->prm.cg_tol && k.mg == a.mg) return 0;
+    if (k.graph) {
+        (void)hipGraphExecDestroy(k.graph);
+        k.graph = nullptr;
     }
     hipGraph_t graph = nullptr;
     DOTS_HIP(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    int rc = cg_iterations<MODAL>(c, a, x, unit);
+    int rc = cg_iterations<MODAL>(c, d, coarse_inv, a, x, unit);
     hipError_t e = hipStreamEndCapture(c->stream, &graph);
     if (rc != 0) return rc;
     DOTS_HIP(e);
-    DOTS_HIP(hipGraphInstantiate(&c->cg_graph, graph, nullptr, nullptr, 0));
+    DOTS_HIP(hipGraphInstantiate(&k.graph, graph, nullptr, nullptr, 0));
     (void)hipGraphDestroy(graph);
-    c->cg_graph_iters = unit;
-    c->cg_graph_eps = c->prm.eps;
-    c->cg_graph_tol = c->prm.cg_tol;
-    c->cg_graph_mg = a.mg;
+    k.iters = unit;
+    k.eps = c->prm.eps;
+    k.tol = c->prm.cg_tol;
+    k.mg = a.mg;
     return 0;
 }
 
-// PCG on the node-layout right-hand side b (already in mode space when MODAL), solution in x.
+// PCG on the node-layout right-hand side b (already in mode space when MODAL), solution in x, for the columns of the view d (the
+// context's own, or one window of it): its graph cache k, its coarse inverse, and the iteration count that sizes its first burst.
 template <bool MODAL>
-static int cg_core(Ctx *c, const double *b, double *x, dots_step_stats *stats) {
-    const Dev &d = MODAL ? c->dcg : c->d;
-    CgArgs a = make_args(c, MODAL);
+static int cg_core(Ctx *c, const Dev &d, CgCache &k, const double *coarse_inv, int *last_iters, const double *b, double *x, dots_step_stats *stats) {
+    CgArgs a = make_args(c, d, MODAL);
     const size_t lds = cg_lds_bytes(a.cap, a.vt, a.nb);
     a.zin = x;
     a.out = d.cg_Ap;
@@ -676,36 +772,36 @@ static int cg_core(Ctx *c, const double *b, double *x, dots_step_stats *stats) {
     hipLaunchKernelGGL((k_cg_begin<MODAL>), dim3(1), dim3(a.nb), lds, c->stream, d, a);
     DOTS_HIP(hipGetLastError());
     if (a.mg) {
-        int rc = mg_vcycle(c, d.cg_r, d.cg_z, d.cg_Ap, d.partials + part_rz(a, 0), a.nb, a.ept, a.vt, a.G);
+        int rc = mg_vcycle(c, d, coarse_inv, d.cg_r, d.cg_z, d.cg_Ap, d.partials + part_rz(a, 0), a.nb, a.ept, a.vt, a.G);
         if (rc) return rc;
         collapse_if_needed(c, d, a, idx_rz(0));
     }
 
     const int max_iter = c->prm.cg_max_iter > 0 ? c->prm.cg_max_iter : 10000;
     const int unit = a.mg ? 2 : 8;   // iterations per graph replay (even: the ping-pong parity is preserved)
-    int rc = cg_graph_prepare<MODAL>(c, a, x, unit);
+    int rc = cg_graph_prepare<MODAL>(c, k, d, coarse_inv, a, x, unit);
     if (rc != 0) return rc;
     int launched = 0, iters = 0;
     bool done = false;
     // first burst sized from the previous solve (iteration counts drift slowly along the ALM)
-    int burst = c->last_cg_iters > 2 * unit ? ((c->last_cg_iters - unit / 2) / unit) * unit : unit;
+    int burst = *last_iters > 2 * unit ? ((*last_iters - unit / 2) / unit) * unit : unit;
     while (!done && launched < max_iter) {
-        for (int k = 0; k < burst / unit; ++k) DOTS_HIP(hipGraphLaunch(c->cg_graph, c->stream));
+        for (int q = 0; q < burst / unit; ++q) DOTS_HIP(hipGraphLaunch(k.graph, c->stream));
         launched += burst;
         burst = unit;
         DOTS_HIP(hipMemcpyAsync(c->h_flags, d.flags, sizeof(int) * FLAG_TOTAL, hipMemcpyDeviceToHost, c->stream));
         DOTS_HIP(hipStreamSynchronize(c->stream));
         done = true;
-        for (int k = 0; k < a.nc; ++k) done = done && (c->h_flags[k] != 0);
+        for (int q = 0; q < a.nc; ++q) done = done && (c->h_flags[q] != 0);
         iters = c->h_flags[FLAG_ITERS];
     }
-    c->last_cg_iters = iters;
+    *last_iters = iters;
     if (stats) {
         DOTS_HIP(hipMemcpyAsync(c->h_pinned, d.scal, sizeof(double) * S::TOTAL, hipMemcpyDeviceToHost, c->stream));
         DOTS_HIP(hipStreamSynchronize(c->stream));
         double worst = 0.0;
-        for (int k = 0; k < a.nc; ++k) {
-            const double br = c->h_pinned[S::BREF + k], cr = c->h_pinned[S::ALPHA + k];
+        for (int q = 0; q < a.nc; ++q) {
+            const double br = c->h_pinned[S::BREF + q], cr = c->h_pinned[S::ALPHA + q];
             if (br > 0.0 && cr / br > worst) worst = cr / br;
         }
         stats->cg_last_rel_residual = sqrt(worst);
@@ -798,7 +894,9 @@ __global__ __launch_bounds__(BLOCK) void k_time_modes_inv_gathered_tile(Dev dt, 
 void modes_forward(Ctx *c, const double *in, double *out, bool direct) {
     const Dev &d = c->d;
     const int gt = xcd_grid(d.n_vtiles);
-    if (direct && time_modes_wide_ok(d))
+    if (!direct && pcg_windowed(c))
+        launch_time_modes_windows<true>(c, in, out, 1);      // `out` in compact windows, column-0 sums for k_cg_bmean
+    else if (direct && time_modes_wide_ok(d))
         launch_time_modes_wide(c, d.Qpad, in, out);
     else if (direct && time_modes_tile_ok(d))
         hipLaunchKernelGGL((k_time_modes_tile<true>), dim3(gt), dim3(BLOCK), time_modes_tile_lds(d), c->stream, d, in, out, time_modes_chunk(d));
@@ -808,7 +906,9 @@ void modes_forward(Ctx *c, const double *in, double *out, bool direct) {
 void modes_inverse(Ctx *c, const double *x, double *phi, bool direct) {
     const Dev &d = c->d;
     const int gt = xcd_grid(d.n_vtiles);
-    if (direct && time_modes_wide_ok(d))
+    if (!direct && pcg_windowed(c))
+        launch_time_modes_windows<false>(c, x, phi, 0);      // `x` in compact windows
+    else if (direct && time_modes_wide_ok(d))
         launch_time_modes_wide(c, d.QpadT, x, phi);
     else if (time_modes_mfma_ok(d))
         hipLaunchKernelGGL(k_time_modes_mfma, dim3((d.V + TM_ROWS - 1) / TM_ROWS), dim3(BLOCK), sizeof(double) * TM_ROWS * (d.TP + 1), c->stream, d, d.QpadT,
@@ -835,7 +935,8 @@ static int cg_solve_impl(Ctx *c, dots_step_stats *stats, bool defer_inverse) {
     const bool owns_mode0 = !sharded || c->shard_begin == 0;
     if (MODAL && g.cg_ncol == 0) return 0;   // a rank without modes has nothing to solve
     const bool direct = MODAL && c->use_front && c->front.n_nodes > 0;   // no warm start, no mean removal needed
-    if (MODAL && !direct && g.cg_ncol > S::NCMAX) {      // (the entry points refuse first: modal_needs_factor) nothing is launched
+    const bool windowed = MODAL && !direct && pcg_windowed(c);      // modes in windows of 256, one after the other on the stream
+    if (MODAL && !direct && !windowed && g.cg_ncol > S::NCMAX) {      // (the entry points refuse first: modal_needs_factor) nothing is launched
         set_error("laplacian solve: T + 1 > 256 needs the direct solver (dots_front_setup); the modal PCG takes T + 1 <= 256");
         return DOTS_ERR_STATE;
     }
@@ -859,11 +960,15 @@ static int cg_solve_impl(Ctx *c, dots_step_stats *stats, bool defer_inverse) {
             if (rhs_writes_modes(c)) {
                 // k_rhs_modes (kernels_alm.hip) already left the mode-space right-hand side in cg_p0
             } else modes_forward(c, d.cg_b, d.cg_p0, direct);
-            if (!direct) hipLaunchKernelGGL((k_time_modes<true>), dim3(gt), dim3(BLOCK), 0, c->stream, d, d.phi, d.cg_x, 0);
+            if (windowed) launch_time_modes_windows<true>(c, d.phi, d.cg_x, 0);
+            else if (!direct) hipLaunchKernelGGL((k_time_modes<true>), dim3(gt), dim3(BLOCK), 0, c->stream, d, d.phi, d.cg_x, 0);
             b = d.cg_p0;   // consumed by k_cg_r0 before iteration 0 (which reads no p_old: beta = 0) writes p1
         }
         const double mean_scale = !singular ? 0.0 : (MODAL ? 1.0 / d.V : 1.0 / ((double)d.V * (d.T + 1)));
-        if (!direct) hipLaunchKernelGGL(k_cg_bmean, dim3(1), dim3(BLOCK), 0, c->stream, d, gt, MODAL ? d.cg_ncol : 1, mean_scale);
+        // (windowed: the forward transform left one sum per workgroup; the scalar block holds one window's columns)
+        if (!direct)
+            hipLaunchKernelGGL(k_cg_bmean, dim3(1), dim3(BLOCK), 0, c->stream, d, windowed ? windows_transform_grid(d) : gt,
+                               windowed ? PCG_WINDOW : (MODAL ? d.cg_ncol : 1), mean_scale);
     }
     DOTS_HIP(hipGetLastError());
     int rc;
@@ -872,8 +977,33 @@ static int cg_solve_impl(Ctx *c, dots_step_stats *stats, bool defer_inverse) {
         rc = front_solve(c, b, g.cg_z, x);
         c->last_cg_iters = 0;
         if (stats) stats->cg_last_iterations = 0;
+    } else if (windowed) {
+        // each live window through its pitch-256 view on the PCG kernels as they are; the mean removal belongs to window 0 (mode 0)
+        const int nw = pcg_window_count(g);
+        int worst_iters = 0, any_open = 0;
+        double worst_res = 0.0;
+        rc = 0;
+        for (int k = 0; k < nw && !rc; ++k) {
+            const Dev w = pcg_window_view(g, k);
+            if (k > 0) hipLaunchKernelGGL(k_cg_bmean, dim3(1), dim3(BLOCK), 0, c->stream, d, 0, PCG_WINDOW, 0.0);
+            dots_step_stats ws{};
+            const double *inv = c->mg.coarse_inv ? c->mg.coarse_inv + k * c->mg.coarse_win_stride : nullptr;
+            rc = cg_core<MODAL>(c, w, c->cgw[k], inv, &c->cgw[k].last_iters, b + (int64_t)k * d.V * PCG_WINDOW, w.cg_x, stats ? &ws : nullptr);
+            worst_iters = std::max(worst_iters, c->cgw[k].last_iters);
+            any_open |= ws.cg_not_converged;
+            worst_res = std::max(worst_res, ws.cg_last_rel_residual);
+        }
+        c->last_cg_iters = worst_iters;
+        c->pcg_windows_ran = nw | 256;
+        if (stats && !rc) {
+            stats->cg_last_rel_residual = worst_res;
+            stats->cg_last_iterations = worst_iters;
+            stats->cg_iterations += worst_iters;
+            if (any_open) stats->cg_not_converged += 1;
+        }
     } else {
-        rc = cg_core<MODAL>(c, b, x, stats);
+        rc = cg_core<MODAL>(c, MODAL ? c->dcg : c->d, c->cgc, c->mg.coarse_inv, &c->last_cg_iters, b, x, stats);
+        if (MODAL) c->pcg_windows_ran = 0;
     }
     if (rc) return rc;
     if (MODAL && !sharded && !defer_inverse) {
@@ -929,7 +1059,7 @@ int cg_mg_apply(Ctx *c, double *rz) {
     const CgArgs a = make_args(c, true);
     const int64_t n = (int64_t)d.V << d.tp_shift;
     hipLaunchKernelGGL(k_mg_entry, dim3((unsigned)std::min<int64_t>((n + BLOCK - 1) / BLOCK, 4096)), dim3(BLOCK), 0, c->stream, d, a.eps);
-    int rc = mg_vcycle(c, d.cg_r, d.cg_z, d.cg_Ap, d.partials + part_rz(a, 0), a.nb, a.ept, a.vt, a.G);
+    int rc = mg_vcycle(c, d, c->mg.coarse_inv, d.cg_r, d.cg_z, d.cg_Ap, d.partials + part_rz(a, 0), a.nb, a.ept, a.vt, a.G);
     if (rc) return rc;
     collapse_if_needed(c, d, a, idx_rz(0));
     std::vector<double> part((size_t)a.Gr * a.prow);
@@ -1013,7 +1143,7 @@ int cg_bench(Ctx *c, int which, int reps, double *ms, double *bytes) {
         a.p_old = (i & 1) ? d.cg_p1 : d.cg_p0;
         a.p_new = (i & 1) ? d.cg_p0 : d.cg_p1;
         if (which == 2) {
-            rc_launch |= mg_vcycle(c, d.cg_r, d.cg_z, d.cg_Ap, d.partials + part_rz(a, 1), a.nb, a.ept, a.vt, a.G);
+            rc_launch |= mg_vcycle(c, d, c->mg.coarse_inv, d.cg_r, d.cg_z, d.cg_Ap, d.partials + part_rz(a, 1), a.nb, a.ept, a.vt, a.G);
         } else if (which == 1) {
             if (modal) hipLaunchKernelGGL((k_cg_update<true>), dim3(a.G), dim3(a.nb), lds, c->stream, d, a);
             else hipLaunchKernelGGL((k_cg_update<false>), dim3(a.G), dim3(a.nb), lds, c->stream, d, a);
@@ -1044,7 +1174,9 @@ void preload_transform_kernels() {      // (see preload_alm_kernels)
     const void *fns[] = {(const void *)k_time_modes_tile<true, BLOCK>, (const void *)k_time_modes_tile<false, BLOCK>,
                          (const void *)k_time_modes_tile<false, 1024>, (const void *)k_time_modes_mfma,
                          (const void *)k_time_modes<true>, (const void *)k_time_modes<false>,
-                         (const void *)k_time_modes_wide<512>, (const void *)k_time_modes_wide<1024>};
+                         (const void *)k_time_modes_wide<512>, (const void *)k_time_modes_wide<1024>,
+                         (const void *)k_time_modes_windows<512, true>, (const void *)k_time_modes_windows<512, false>,
+                         (const void *)k_time_modes_windows<1024, true>, (const void *)k_time_modes_windows<1024, false>};
     hipFuncAttributes a;
     for (const void *f : fns) (void)hipFuncGetAttributes(&a, f);
     (void)hipGetLastError();

@@ -287,8 +287,8 @@ static inline int mg_grid(const Dev &d, int rows) { return (int)((((int64_t)rows
 
 // Enqueue one V-cycle.  r: residual; z: holds D^-1 r on entry (written by the PCG update kernel) and the
 // preconditioned residual on exit; r.z partial sums go to `rz_part`.  Level 0 uses `t0` as scratch.
-int mg_vcycle(Ctx *c, const double *r, double *z, double *t0, double *rz_part, int nb, int ept, int vt, int G) {
-    const Dev &d = c->dcg;   // the PCG's view: its own column range, pitch and sigma
+int mg_vcycle(Ctx *c, const Dev &d, const double *coarse_inv, const double *r, double *z, double *t0, double *rz_part, int nb, int ept, int vt, int G) {
+    // d: the PCG's view (its own column range, pitch and sigma; on a windowed context one window), coarse_inv: that view's block
     const MgDev &m = c->mg;
     MgArgs a{c->prm.eps, m.omega, d.cg_ncol};
     const int nl = m.nlev;
@@ -319,10 +319,10 @@ int mg_vcycle(Ctx *c, const double *r, double *z, double *t0, double *rz_part, i
     if (first_tail == nl - 1 && m.lv[nl - 1].n > 64) {
         const MgLevelDev &L = m.lv[nl - 1];
         if (d.TP <= MG_NB / 2) {
-            hipLaunchKernelGGL(k_mg_coarse_rows, dim3(L.n), dim3(MG_NB), 0, c->stream, d, a, L.n, m.coarse_inv, L.b, L.bt);
+            hipLaunchKernelGGL(k_mg_coarse_rows, dim3(L.n), dim3(MG_NB), 0, c->stream, d, a, L.n, coarse_inv, L.b, L.bt);
             path |= MG_PATH_COARSE_ROWS;
         } else {
-            hipLaunchKernelGGL(k_mg_coarse, dim3(mg_grid(d, L.n)), dim3(MG_NB), 0, c->stream, d, a, L.n, m.coarse_inv, L.b, L.bt);
+            hipLaunchKernelGGL(k_mg_coarse, dim3(mg_grid(d, L.n)), dim3(MG_NB), 0, c->stream, d, a, L.n, coarse_inv, L.b, L.bt);
             path |= MG_PATH_COARSE_FLAT;
         }
     } else {
@@ -330,7 +330,7 @@ int mg_vcycle(Ctx *c, const double *r, double *z, double *t0, double *rz_part, i
         T.first = first_tail;
         T.nlev = nl;
         for (int l = first_tail; l < nl; ++l) T.lv[l - first_tail] = m.lv[l];
-        T.coarse_inv = m.coarse_inv;
+        T.coarse_inv = coarse_inv;
         hipLaunchKernelGGL(k_mg_tail, dim3(d.cg_ncol), dim3(MG_TAIL_NB), 0, c->stream, d, T, a);
         path |= MG_PATH_TAIL | ((nl - first_tail) << MG_PATH_TAIL_LEVELS_SHIFT);
     }

@@ -34,12 +34,26 @@ def place_slab(name, part, full, n0, nl, ni):
     return full
 
 
+PCG_WINDOW = 256          # time modes per window of the windowed modal PCG (dots_pcg_windows)
+MAX_TIME_NODES = 1024     # T + 1 one context takes
+
+
+def pcg_window_plan(n_time):
+    """``[(first_mode, live_columns), ...]``: the windows of 256 time modes the windowed modal PCG (dots_pcg_windows) solves one after
+    the other at ``n_time + 1`` nodes.  Up to 256 nodes that is the one window the PCG always had; a window without a live mode
+    (the fourth at 600 intervals, pitch 1024) is not listed: it is neither written nor solved."""
+    nodes = int(n_time) + 1
+    if nodes < 2 or nodes > MAX_TIME_NODES:
+        raise ValueError(f"pcg_window_plan: n_time + 1 = {nodes} time nodes, the library takes 2 to {MAX_TIME_NODES}")
+    return [(first, min(PCG_WINDOW, nodes - first)) for first in range(0, nodes, PCG_WINDOW)]
+
+
 class DeviceProblem:
     def __init__(self, n_time, geometry, lap_solver="spacetime_pcg", device=0, reorder=True, plan: DevicePlan | None = None,
-                 time_slab=None, nd_leaf=16):
+                 time_slab=None, nd_leaf=16, pcg_windows=False):
         """``time_slab = (rank, n_ranks)``: this context is one TIME SLAB of a multi-GPU solve (distributed.py): it holds
         the nodes [rank * stride, ...) of every state array and solves the time modes with the same indices; the caller
-        drives ``slab_stage`` around its exchanges."""
+        drives ``slab_stage`` around its exchanges.  ``pcg_windows``: ``enable_pcg_windows()`` right after creation."""
         self.lib = _lib.load()
         self.plan = plan if plan is not None else build_plan(n_time, geometry, reorder=reorder, nd_leaf=nd_leaf)
         p = self.plan
@@ -86,6 +100,13 @@ class DeviceProblem:
         _lib.check(self.lib.dots_create(C.byref(d), C.byref(self._h)), "dots_create")
         self.params = _lib.Params()
         _lib.check(self.lib.dots_get_params(self._h, C.byref(self.params)), "dots_get_params")
+        self.pcg_windows = False
+        if pcg_windows:
+            try:
+                self.enable_pcg_windows()
+            except Exception:
+                self.close()
+                raise
 
     # ---- lifecycle
     def close(self):
@@ -498,8 +519,12 @@ class DeviceProblem:
             return None      # a rank without modes solves nothing
         last = levels[-1]
         inv = np.empty((last.n, last.n, sigma.size))
-        for k, s in enumerate(sigma):
-            inv[:, :, k] = multigrid.coarse_inverse(last, float(s + eps))
+        # one block of modes per window of the PCG (one window up to 256 modes; a time slab's slice is one too): the library installs
+        # the coarse inverse window by window from this array
+        windows = pcg_window_plan(self.T) if (getattr(self, "pcg_windows", False) and mode_slice is None) else [(0, sigma.size)]
+        for first, live in windows:
+            for k in range(first, first + live):
+                inv[:, :, k] = multigrid.coarse_inverse(last, float(sigma[k] + eps))
         keep = []   # host arrays must stay alive until dots_mg_setup returns
 
         def arr(a, dtype):
@@ -649,6 +674,19 @@ class DeviceProblem:
 
     def enable_frontal(self, on=True):
         _lib.check(self.lib.dots_front_enable(self._h, 1 if on else 0), "dots_front_enable")
+
+    def enable_pcg_windows(self, on=True):
+        """dots_pcg_windows: above 256 time nodes and without an enabled factor, step 1 solves the time modes in windows of 256
+        (``pcg_window_plan``) with the modal PCG instead of refusing.  Changing the setting above 256 nodes drops an installed
+        multigrid hierarchy (``setup_multigrid`` again)."""
+        _lib.check(self.lib.dots_pcg_windows(self._h, 1 if on else 0), "dots_pcg_windows")
+        self.pcg_windows = bool(on)
+
+    def pcg_windows_ran(self):
+        """``(windows, transforms)``: the windows the last PCG solve ran (0: none yet, or it ran unwindowed) and whether the windowed
+        time transforms ran (dots_debug_counter 14)."""
+        mask = self.debug_counter(_lib.PCG_WINDOWS_COUNTER)
+        return mask & 0xff, bool(mask & _lib.PCG_WINDOWS_TRANSFORMS)
 
     def enable_multigrid(self, on=True):
         _lib.check(self.lib.dots_mg_enable(self._h, 1 if on else 0), "dots_mg_enable")

@@ -40,20 +40,27 @@ Z_VARS = ("z_fst", "z_mid", "z_end")
 DUAL_QE = ("mu", "E")
 BETAS = ("beta_fst", "beta_mid", "beta_end")
 DEFAULT_CG_TOL = 1e-8     # parity study: profiles/studies/cg_tol_parity.txt (cost within 1e-9 of the reference, budget 1e-6)
-MODAL_PCG_MAX_NODES = 256     # T + 1 the modal PCG and time slabs take (per-mode scalar block, slab layouts)
+MODAL_PCG_MAX_NODES = 256     # T + 1 the modal PCG takes in one window, and time slabs at all (per-mode scalar block, slab layouts)
 MAX_TIME_NODES = 1024         # T + 1 the library takes at all (modal_direct and spacetime_pcg on one GPU)
 
 
-def check_time_nodes(n_time, lap_solver="modal_direct", time_slab=None):
+PCG_WINDOWS_ONE_SOLVER = ("pcg_windows belongs to solver_socp / AlmSolver on one GPU: {who} does not take it "
+                          "(a batch shares the direct solver's factor, the levels of a cascade build theirs)")
+
+
+def check_time_nodes(n_time, lap_solver="modal_direct", time_slab=None, pcg_windows=False):
     """Refuse, before any device call, what the library cannot run at ``n_time + 1`` time nodes: above 256 only the direct
-    solver on one GPU (or spacetime_pcg) runs; above 1024 nothing does."""
+    solver on one GPU (or spacetime_pcg) runs -- and, with ``pcg_windows=True``, the modal PCG on one GPU, in windows of 256 modes;
+    above 1024 nothing does."""
     nodes = int(n_time) + 1
     if nodes > MAX_TIME_NODES:
         raise ValueError(f"n_time + 1 = {nodes} time nodes: at most {MAX_TIME_NODES} are supported")
+    if pcg_windows and time_slab is not None:
+        raise ValueError("pcg_windows is not available on time slabs: the windowed modal PCG runs on one GPU")
     if nodes > MODAL_PCG_MAX_NODES:
         if time_slab is not None:
             raise ValueError(f"time slabs need n_time + 1 <= {MODAL_PCG_MAX_NODES} (got {nodes}); run on one GPU with lap_solver='modal_direct'")
-        if lap_solver == "modal_pcg":
+        if lap_solver == "modal_pcg" and not pcg_windows:
             raise ValueError(f"lap_solver='modal_pcg' needs n_time + 1 <= {MODAL_PCG_MAX_NODES} (got {nodes}); use lap_solver='modal_direct'")
 
 
@@ -119,7 +126,7 @@ class AlmSolver:
                  is_constant_scaling=False, check_kkt_step_by_step=False, init_solution=None, tol_checkpoints=None,
                  time_limit=1000, is_palm=False, lap_solver="modal_direct", cg_tol=DEFAULT_CG_TOL, cg_max_iter=20000, device=0, reorder=True,
                  preconditioner="multigrid", mg_coarsest=256, time_slab=None, nd_leaf=16, plan=None, front_owner=None, init_from=None,
-                 release_init_from=False, batched=None, init_parents=None, init_transfer=None, init_regrid=False):
+                 release_init_from=False, batched=None, init_parents=None, init_transfer=None, init_regrid=False, pcg_windows=False):
         """``plan``: the device plan to use (geometry.plan_with_densities) instead of building one; ``front_owner``: a DeviceProblem
         whose factor this solver shares (dots_front_share) instead of building its own -- a member of a batch (solver_socp_many), stepped
         by ``step_batch``; the launch ahead of the right-hand side and of the penalty decision are off then.
@@ -137,8 +144,12 @@ class AlmSolver:
         factor.  ``init_regrid=True`` (with ``init_parents`` or ``init_transfer``) allows ``init_from`` at ANOTHER ``n_time``: mesh and time
         grid change in one pass on the device (DeviceProblem.carry_spacetime_from; ``init_solution=cascade.carry_spacetime_solution(<its
         solution>, ...)`` bit for bit: space first, then time); at the same ``n_time`` it changes nothing.  ``batched``: whether the solver is stepped by a batch (default: whenever ``plan`` or
-        ``front_owner`` is given)."""
-        check_time_nodes(n_time, lap_solver, time_slab)
+        ``front_owner`` is given).  ``pcg_windows``: above 256 time nodes the modal PCG solves the modes in windows of 256
+        (DeviceProblem.enable_pcg_windows): ``lap_solver="modal_pcg"`` then takes ``n_time + 1 <= 1024`` on one GPU, and ``modal_direct``
+        falls back to it there too when the factor does not fit."""
+        check_time_nodes(n_time, lap_solver, time_slab, pcg_windows)
+        if pcg_windows and (front_owner is not None or plan is not None):
+            raise ValueError(PCG_WINDOWS_ONE_SOLVER.format(who="a member of a batch"))
         carry = _state_carrier(n_time, init_from, init_solution, time_slab, init_parents, init_transfer, init_regrid)
         self.tol_checkpoints = _validate_checkpoints(tol_checkpoints, tol)
         self.geometry = geometry        # (read_out takes the area weights and mu0 / mu1 from it)
@@ -168,7 +179,7 @@ class AlmSolver:
         if direct and reorder is True:
             reorder = "nd"      # the elimination order of the factor doubles as the locality numbering
         self.dev = dev = DeviceProblem(n_time, geometry, lap_solver="modal_pcg" if direct else lap_solver, device=device,
-                                       reorder=reorder, time_slab=time_slab, nd_leaf=nd_leaf, plan=plan)
+                                       reorder=reorder, time_slab=time_slab, nd_leaf=nd_leaf, plan=plan, pcg_windows=bool(pcg_windows))
 
         p = dev.params
         self.r = 1.0
@@ -198,8 +209,8 @@ class AlmSolver:
             try:
                 self.front_summary = dev.setup_frontal(eps=self.eps)
             except _lib.HipLibraryError as exc:
-                if exc.status != _lib.ERR_MEMORY or time_slab is not None or int(n_time) + 1 > MODAL_PCG_MAX_NODES:
-                    raise      # (above 256 time nodes there is no PCG to fall back to: the error names the sizes)
+                if exc.status != _lib.ERR_MEMORY or time_slab is not None or (int(n_time) + 1 > MODAL_PCG_MAX_NODES and not pcg_windows):
+                    raise      # (above 256 time nodes only the windowed PCG is there to fall back to: without it the error names the sizes)
                 self.lap_solver_fallback = str(exc)
                 logger.warning("modal_direct -> modal_pcg with the multigrid preconditioner: %s", exc)
                 self.direct = direct = False
@@ -674,6 +685,7 @@ def solver_socp(
         nd_leaf=16,
         outputs=None,
         read_out=None,
+        pcg_windows=False,
 ):
     """SOCP for dynamical optimal transport on a discrete surface, on the GPU.
 
@@ -684,6 +696,8 @@ def solver_socp(
     ``outputs``: a tuple of array names: ``solution`` holds only those (and ``checkpoints``), and only those are downloaded.
     ``read_out``: the keywords of ``AlmSolver.read_out`` (dot_units, centred): ``solution`` is ``mu`` and ``E`` as the solver
     plug-ins return them, formed on the device (``checkpoints`` stay in the solver's units).
+    ``pcg_windows``: above 256 time nodes the modal PCG runs in windows of 256 modes: ``lap_solver="modal_pcg"`` takes
+    ``n_time + 1 <= 1024`` with either preconditioner, and ``modal_direct`` falls back to it when its factor does not fit.
     """
     if read_out is not None and outputs is not None:
         raise ValueError("solver_socp: outputs and read_out are mutually exclusive (read_out returns mu and E only)")
@@ -691,7 +705,7 @@ def solver_socp(
                     is_constant_scaling=is_constant_scaling, check_kkt_step_by_step=check_kkt_step_by_step,
                     init_solution=init_solution, tol_checkpoints=tol_checkpoints, time_limit=time_limit, is_palm=is_palm,
                     lap_solver=lap_solver, cg_tol=cg_tol, cg_max_iter=cg_max_iter, device=device, reorder=reorder,
-                    preconditioner=preconditioner, mg_coarsest=mg_coarsest, nd_leaf=nd_leaf)
+                    preconditioner=preconditioner, mg_coarsest=mg_coarsest, nd_leaf=nd_leaf, pcg_windows=pcg_windows)
     try:
         for _ in range(nit):
             if alm.iterate():
@@ -711,6 +725,8 @@ BATCH_TIME_NOTE = ("phase times of a batched iteration are the batch's, booked t
 
 def _batch_problems(geometry, problems, common):
     """The checks of solver_socp_many, before any device is touched."""
+    if "pcg_windows" in common:
+        raise ValueError(PCG_WINDOWS_ONE_SOLVER.format(who="solver_socp_many"))
     unknown = set(common) - set(COMMON_KEYS)
     if unknown:
         raise ValueError(f"solver_socp_many: unknown option(s) {sorted(unknown)}")
@@ -856,6 +872,8 @@ def _cascade_options(n_time, levels, level_tol, kwargs):
         raise ValueError("solver_socp_cascade: time slabs are not supported (a cascade runs on one GPU)")
     if "init_from" in kwargs:
         raise ValueError("solver_socp_cascade: init_from belongs to the levels of the cascade; start the coarsest level with init_solution")
+    if "pcg_windows" in kwargs:
+        raise ValueError(PCG_WINDOWS_ONE_SOLVER.format(who="solver_socp_cascade"))
     unknown = set(kwargs) - set(CASCADE_KEYS)
     if unknown:
         raise ValueError(f"solver_socp_cascade: unknown option(s) {sorted(unknown)}")
@@ -954,6 +972,8 @@ def _mesh_cascade_options(geometries, level_tol, kwargs):
         if key in kwargs:
             raise ValueError(f"solver_socp_mesh_cascade: {key} is not an option of the cascade in space" +
                              (" (a cascade in time and in space in one call is not supported)" if key == "levels" else ""))
+    if "pcg_windows" in kwargs:
+        raise ValueError(PCG_WINDOWS_ONE_SOLVER.format(who="solver_socp_mesh_cascade"))
     unknown = set(kwargs) - set(CASCADE_KEYS)
     if unknown:
         raise ValueError(f"solver_socp_mesh_cascade: unknown option(s) {sorted(unknown)}")
@@ -1141,6 +1161,8 @@ def _auto_cascade_options(n_time, coarse_levels, ratio, locate, spacetime, level
     for key in ("time_slab", "init_from", "init_parents", "init_transfer"):
         if key in kwargs:
             raise ValueError(f"{who}: {key} is not an option of the cascade in space")
+    if "pcg_windows" in kwargs:
+        raise ValueError(PCG_WINDOWS_ONE_SOLVER.format(who=who))
     unknown = set(kwargs) - set(CASCADE_KEYS)
     if unknown:
         raise ValueError(f"{who}: unknown option(s) {sorted(unknown)}")

@@ -396,6 +396,21 @@ int dots_mg_enable(dots_ctx *ctx, int on);   /* switch between multigrid (1) and
  * slab) with a hierarchy installed by dots_mg_setup. */
 int dots_mg_apply(dots_ctx *ctx, const double *r, double *z, double *rz, const int32_t *frozen);
 
+/* Windowed modal PCG: long horizons without a factor (opt-in; off when a context is created).  The PCG kernels keep their per-mode
+ * scalars for 256 modes, so a DOTS_LAP_MODAL_PCG context of T + 1 > 256 is refused by dots_step, dots_run_phase(LAPLACIAN) and
+ * dots_mg_setup unless a factor is installed and enabled.  With on = 1 such a context solves step 1 without a factor: the T + 1
+ * independent modal problems are taken in windows of 256 -- window k = modes [256 k, 256 k + 256) -- one after the other on the
+ * context's stream, each through the PCG kernels at pitch 256 with its own hipGraph, first-burst size and (with multigrid) block of
+ * the coarse inverse; the time transforms around them keep mode space compact (window k of a PCG vector is the [V][256] array at
+ * offset k * V * 256).  dots_mg_setup then takes n_cols = T + 1 and one coarse inverse [n_L][n_L][T + 1] as below 256.  In
+ * dots_step_stats cg_last_iterations is the maximum over the windows, cg_iterations adds that maximum, cg_not_converged counts a
+ * solve once if any window hit the cap and cg_last_rel_residual is the worst window's.  An installed and enabled factor keeps
+ * precedence: the sweeps run as without the switch, bit for bit.  At T + 1 <= 256 the switch changes nothing.  Changing the
+ * setting on a context of T + 1 > 256 releases an installed multigrid hierarchy (its layout belongs to the setting).  Refused
+ * above 256 as before: dots_mg_apply, dots_bench_kernel 0-2, time slabs, dots_step_many / dots_laplacian_solve_many without a
+ * factor.  DOTS_ERR_STATE on a time slab and on a context that is not DOTS_LAP_MODAL_PCG. */
+int dots_pcg_windows(dots_ctx *ctx, int on);
+
 /* ---- direct solve of the modal problems (replaces the T+1 SuperLU factorisations of
  * laplacian_inverse_socp.py:40-61 and their per-iteration triangular solves, :46-60) ----------------
  * Multifrontal Cholesky factor on one nested-dissection tree shared by all modes, built on the host
@@ -727,7 +742,9 @@ int dots_bench_kernel(dots_ctx *ctx, int which, int reps, double *ms_per_launch,
  * tiling packed above it: 1 the batched per-mode PCG (clear: the coupled space-time operator), 2 the per-workgroup partial rows are
  * summed by k_collapse behind every producer, 4 workgroups of fewer than 1024 threads, 8 multigrid preconditioner; bits 8-19 the
  * vertices per tile, bits 20-31 the CSR entries of a tile staged in LDS (further entries are read from global memory), from bit 32 the
- * number of workgroups (0: no such launch yet); -1 for an unknown counter */
+ * number of workgroups (0: no such launch yet; on a windowed context the last window's), 14 low byte: the windows the last PCG
+ * solve on this context ran (0: none yet, or it ran unwindowed), bit 8: the windowed time transforms ran (dots_pcg_windows);
+ * -1 for an unknown counter */
 int64_t dots_debug_counter(dots_ctx *ctx, int which);
 
 /* device memory in use by the context, bytes */
