@@ -35,6 +35,7 @@ EXPORTS = [
     "dots_prolong_space", "dots_transfer_space", "dots_carry_spacetime",
     "dots_pcg_windows",
     "dots_coarsen", "dots_coarsen_vertices", "dots_coarsen_triangles", "dots_coarsen_copy", "dots_coarsen_free", "dots_mesh_locate",
+    "dots_flow_map",
 ]
 
 
@@ -154,6 +155,14 @@ class ReadoutDesc(C.Structure):      # dots_readout_desc
     _fields_ = [
         ("factor", C.c_double), ("w_vertex", _f64p), ("w_triangle", _f64p), ("centred", C.c_int32), ("reserved", C.c_int32),
         ("mu0", _f64p), ("mu1", _f64p), ("mu", _f64p), ("E", _f64p), ("layer_mass", _f64p), ("layer_negative", _f64p), ("ms", _f64p),
+    ]
+
+
+class FlowMapDesc(C.Structure):      # dots_flow_map_desc
+    _fields_ = [
+        ("n_particles", C.c_int32), ("max_crossings", C.c_int32), ("start_triangle", _i32p), ("start_weights", _f64p), ("neighbours", _i32p),
+        ("floor", C.c_double), ("triangle", _i32p), ("weights", _f64p), ("status", _i32p), ("rested", _i32p), ("crossings", _i32p),
+        ("triangles_at", _i32p), ("weights_at", _f64p), ("ms", _f64p),
     ]
 
 
@@ -346,6 +355,7 @@ def load(host_only=False):
     lib.dots_bench_many.argtypes = [C.POINTER(vp), C.c_int, C.c_int, _f64p]
     lib.dots_prolong_time.argtypes = [vp, vp, C.POINTER(ProlongDesc)]
     lib.dots_readout.argtypes = [vp, C.POINTER(ReadoutDesc)]
+    lib.dots_flow_map.argtypes = [vp, C.POINTER(FlowMapDesc)]
     lib.dots_prolong_space.argtypes = [vp, vp, C.POINTER(ProlongSpaceDesc)]
     lib.dots_transfer_space.argtypes = [vp, vp, C.POINTER(TransferSpaceDesc)]
     lib.dots_carry_spacetime.argtypes = [vp, vp, C.POINTER(CarrySpacetimeDesc)]

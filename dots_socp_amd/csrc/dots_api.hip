@@ -1793,6 +1793,141 @@ int dots_readout(dots_ctx *c, const dots_readout_desc *desc) {
     return 0;
 }
 
+// ---- dots_flow_map --------------------------------------------------------------------------------------------------------
+// the context's triangles and the inverse of its triangle numbering on the host, once per context: what the caller's tables are
+// checked against and translated with
+static int flow_prepare(Ctx *c) {
+    if (c->flow) return 0;
+    const Dev &d = c->d;
+    auto fh = std::make_shared<FlowHost>();
+    fh->tri.resize((size_t)d.F * 3);
+    DOTS_HIP(hipMemcpyAsync(fh->tri.data(), d.tri, sizeof(int) * (size_t)d.F * 3, hipMemcpyDeviceToHost, c->stream));
+    std::vector<int> perm;
+    if (d.perm_f) {
+        perm.resize((size_t)d.F);
+        DOTS_HIP(hipMemcpyAsync(perm.data(), d.perm_f, sizeof(int) * (size_t)d.F, hipMemcpyDeviceToHost, c->stream));
+    }
+    DOTS_HIP(hipStreamSynchronize(c->stream));
+    if (d.perm_f) {
+        fh->inv_f.assign((size_t)d.F, -1);
+        for (int i = 0; i < d.F; ++i) {
+            if (perm[i] < 0 || perm[i] >= d.F || fh->inv_f[perm[i]] >= 0) { set_error("flow_map: the device numbering is not a permutation"); return DOTS_ERR_STATE; }
+            fh->inv_f[perm[i]] = i;
+        }
+    }
+    preload_flow_kernels();
+    c->flow = fh;
+    return 0;
+}
+
+int dots_flow_map(dots_ctx *c, const dots_flow_map_desc *desc) {
+    if (!c) { set_error("null context"); return DOTS_ERR_ARGUMENT; }
+    if (!desc) { set_error("flow_map: null description"); return DOTS_ERR_ARGUMENT; }
+    if (c->shard_stride != 0) { set_error("flow_map: not available on time slabs"); return DOTS_ERR_STATE; }
+    const Dev &d = c->d;
+    if (!desc->start_triangle || !desc->start_weights || !desc->neighbours || !desc->triangle || !desc->weights || !desc->status || !desc->rested ||
+        !desc->crossings) {
+        set_error("flow_map: null pointer (start_triangle, start_weights, neighbours and the five outputs are required)");
+        return DOTS_ERR_ARGUMENT;
+    }
+    if (desc->n_particles < 1) { set_error("flow_map: n_particles < 1"); return DOTS_ERR_ARGUMENT; }
+    if (desc->max_crossings < 1 || desc->max_crossings > 255) { set_error("flow_map: max_crossings outside 1 .. 255"); return DOTS_ERR_ARGUMENT; }
+    if (std::isnan(desc->floor)) { set_error("flow_map: the floor is not a number"); return DOTS_ERR_ARGUMENT; }
+    if (d.F >= FLOW_MAX_TRIANGLES) { set_error("flow_map: more than 2^27 triangles"); return DOTS_ERR_ARGUMENT; }
+    hipError_t e0 = hipSetDevice(c->device);
+    if (e0 != hipSuccess) return hip_fail(e0, "hipSetDevice", __FILE__, __LINE__);
+    int rc = flow_prepare(c);
+    if (rc) return rc;
+    const FlowHost &fh = *c->flow;
+    const int P = desc->n_particles, F = d.F, T = d.T;
+    auto to_dev = [&](int f) { return fh.inv_f.empty() ? f : fh.inv_f[f]; };
+    // the starts, in the device numbering
+    std::vector<int> h_start((size_t)P);
+    for (int p = 0; p < P; ++p) {
+        const int f = desc->start_triangle[p];
+        if (f < 0 || f >= F) { set_error("flow_map: a start triangle out of range"); return DOTS_ERR_ARGUMENT; }
+        h_start[p] = to_dev(f);
+    }
+    for (size_t i = 0; i < (size_t)P * 3; ++i)
+        if (!(desc->start_weights[i] >= 0.0 && std::isfinite(desc->start_weights[i]))) {
+            set_error("flow_map: a weight that is negative or not finite");
+            return DOTS_ERR_ARGUMENT;
+        }
+    // the neighbour table, in the device numbering, every entry with the corners of the neighbour that name the two shared vertices
+    std::vector<int> h_nbr((size_t)F * 3);
+    for (int f = 0; f < F; ++f) {
+        const int fd = to_dev(f);
+        for (int k = 0; k < 3; ++k) {
+            const int g = desc->neighbours[(size_t)f * 3 + k];
+            if (g < -1 || g >= F) { set_error("flow_map: a neighbour index out of range"); return DOTS_ERR_ARGUMENT; }
+            if (g < 0) { h_nbr[(size_t)fd * 3 + k] = -1; continue; }
+            const int gd = to_dev(g);
+            const int va = fh.tri[(size_t)fd * 3 + (k + 1) % 3], vb = fh.tri[(size_t)fd * 3 + (k + 2) % 3];
+            int ca = -1, cb = -1;
+            for (int m = 0; m < 3; ++m) {
+                if (fh.tri[(size_t)gd * 3 + m] == va) ca = m;
+                if (fh.tri[(size_t)gd * 3 + m] == vb) cb = m;
+            }
+            if (g == f || ca < 0 || cb < 0 || ca == cb) { set_error("flow_map: a neighbour entry that does not share the edge opposite its corner"); return DOTS_ERR_ARGUMENT; }
+            h_nbr[(size_t)fd * 3 + k] = flow_pack_neighbour(gd, ca, cb);
+        }
+    }
+    if ((rc = check(c, true))) return rc;      // (a pending penalty division is carried out, as for a download; z_mid is not needed)
+    // one allocation for the call: [start_w | o_w | w_at] doubles, then [start | nbr | o_tri | status | rested | crossings | tri_at] ints
+    const size_t layers = (size_t)T + 1;
+    const size_t n_wat = desc->weights_at ? layers * P * 3 : 0, n_tat = desc->triangles_at ? layers * P : 0;
+    const size_t n_dbl = (size_t)P * 3 * 2 + n_wat, n_int = (size_t)P * 5 + (size_t)F * 3 + n_tat;
+    void *buf = nullptr;
+    hipError_t ea = hipMalloc(&buf, sizeof(double) * n_dbl + sizeof(int) * n_int);
+    if (ea != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("flow_map: out of device memory for the particle tables");
+        return DOTS_ERR_MEMORY;
+    }
+    double *b_sw = (double *)buf, *b_ow = b_sw + (size_t)P * 3, *b_wat = b_ow + (size_t)P * 3;
+    int *b_start = (int *)(b_wat + n_wat), *b_nbr = b_start + P, *b_otri = b_nbr + (size_t)F * 3, *b_status = b_otri + P, *b_rested = b_status + P,
+        *b_cross = b_rested + P, *b_tat = b_cross + P;
+    auto enqueue = [&]() -> int {
+        DOTS_HIP(hipMemcpyAsync(b_sw, desc->start_weights, sizeof(double) * (size_t)P * 3, hipMemcpyHostToDevice, c->stream));
+        DOTS_HIP(hipMemcpyAsync(b_start, h_start.data(), sizeof(int) * (size_t)P, hipMemcpyHostToDevice, c->stream));
+        DOTS_HIP(hipMemcpyAsync(b_nbr, h_nbr.data(), sizeof(int) * (size_t)F * 3, hipMemcpyHostToDevice, c->stream));
+        FlowArgs a{};
+        a.mu = d.mu; a.E = d.E; a.tri = d.tri; a.hat = d.hat; a.nbr = b_nbr; a.perm_f = d.perm_f;
+        a.start_tri = b_start; a.start_w = b_sw;
+        a.o_tri = b_otri; a.o_status = b_status; a.o_rested = b_rested; a.o_cross = b_cross; a.o_w = b_ow;
+        a.tri_at = desc->triangles_at ? b_tat : nullptr;
+        a.w_at = desc->weights_at ? b_wat : nullptr;
+        a.floor = desc->floor;
+        a.h = 1.0 / (double)T;
+        a.P = P; a.T = T; a.tp_shift = d.tp_shift; a.max_crossings = desc->max_crossings;
+        DOTS_HIP(hipEventRecord(c->ev[0], c->stream));
+        int r = launch_flow_map(c, a);
+        if (r) return r;
+        DOTS_HIP(hipEventRecord(c->ev[1], c->stream));
+        // only the outputs cross to the host
+        DOTS_HIP(hipMemcpyAsync(desc->weights, b_ow, sizeof(double) * (size_t)P * 3, hipMemcpyDeviceToHost, c->stream));
+        int32_t *outs[4] = {desc->triangle, desc->status, desc->rested, desc->crossings};
+        const int *srcs[4] = {b_otri, b_status, b_rested, b_cross};
+        for (int i = 0; i < 4; ++i) DOTS_HIP(hipMemcpyAsync(outs[i], srcs[i], sizeof(int) * (size_t)P, hipMemcpyDeviceToHost, c->stream));
+        if (desc->weights_at) DOTS_HIP(hipMemcpyAsync(desc->weights_at, b_wat, sizeof(double) * n_wat, hipMemcpyDeviceToHost, c->stream));
+        if (desc->triangles_at) DOTS_HIP(hipMemcpyAsync(desc->triangles_at, b_tat, sizeof(int) * n_tat, hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    };
+    rc = enqueue();      // (every path out of the call waits for the stream first: the copies use the caller's and this call's arrays)
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (!rc && es != hipSuccess) rc = hip_fail(es, "hipStreamSynchronize", __FILE__, __LINE__);
+    if (!rc && desc->ms) {
+        float t = 0.f;
+        const hipError_t et = hipEventElapsedTime(&t, c->ev[0], c->ev[1]);
+        if (et != hipSuccess) rc = hip_fail(et, "hipEventElapsedTime", __FILE__, __LINE__);
+        *desc->ms = t;
+    }
+    (void)hipFree(buf);
+    if (rc) return rc;
+    c->d2h_bytes += (int64_t)(sizeof(double) * ((size_t)P * 3 + n_wat) + sizeof(int) * ((size_t)P * 4 + n_tat));
+    return 0;
+}
+
 int dots_front_enable(dots_ctx *c, int on) {
     int rc = check(c);
     if (rc) return rc;
@@ -1852,7 +1987,7 @@ int64_t dots_debug_counter(dots_ctx *c, int which) {
         case 6: return c->sched.bm_nt;                      // beta_mid streamed around the caches by steps 2+3 (the rule of dots_front_setup, or DOTS_BM_NT)
         case 7: return c->front_many_launches;        // sweep launches the last front_solve_many on this (first) context enqueued
         case 8: return c->front_many_split;           // ... of those, launches with fewer rhs than their chunk (many_launch halved: LDS or 1024-thread cap)
-        case 9: return c->d2h_bytes;                  // bytes dots_download and dots_readout have copied device -> host
+        case 9: return c->d2h_bytes;                  // bytes dots_download, dots_readout and dots_flow_map have copied device -> host
         case 10: return c->n_front_allocs;            // device allocations the installed factor holds (0 after front_release: also after a failed dots_front_setup)
         case 11: return c->mg_path;                   // MG_PATH_* bits of the last V-cycle enqueued (dots_dev.h)
         case 12: return c->step_path;                 // STEP_PATH_* bits of the last iteration's launches (dots_dev.h)

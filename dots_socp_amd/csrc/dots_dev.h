@@ -395,6 +395,33 @@ int launch_readout(Ctx *c, bool is_E, double *out, const int *inv, const double 
 int readout_workgroups(const Ctx *c);
 int launch_readout_fold(Ctx *c, const double *part, int layers, int n_wg, double *out);      // out[2 l], out[2 l + 1]: sum / negative sum of layer l
 void preload_readout_kernels();
+// dots_flow_map (kernels_flow.hip): one lane per particle, the loop over the intervals inside the kernel.  Everything in the DEVICE
+// numbering except the triangles written out, which perm_f takes back to the caller's.
+struct FlowArgs {
+    const double *mu, *E;        // the state where it lies: [V][TP], [F][3][TP]
+    const int *tri;              // [F][3]
+    const double *hat;           // [F][3][3]
+    const int *nbr;              // [F][3] the triangle across the edge opposite corner k, packed (flow_pack_neighbour); -1 on the boundary
+    const int *perm_f;           // device triangle -> caller triangle, or null
+    const int *start_tri;        // [P]
+    const double *start_w;       // [P][3]
+    int *o_tri, *o_status, *o_rested, *o_cross;      // [P]
+    double *o_w;                 // [P][3]
+    int *tri_at;                 // [T + 1][P], or null
+    double *w_at;                // [T + 1][P][3], or null
+    double floor, h;
+    int P, T, tp_shift, max_crossings;
+};
+// neighbour g, and the corners of g that name the vertices of corners (k + 1) % 3 and (k + 2) % 3 of the triangle the entry belongs to
+constexpr int FLOW_MAX_TRIANGLES = 1 << 27;
+inline int flow_pack_neighbour(int g, int ca, int cb) { return (g << 4) | (ca << 2) | cb; }
+int launch_flow_map(Ctx *c, const FlowArgs &a);
+void preload_flow_kernels();
+// what dots_flow_map checks the caller's tables against, downloaded once per context
+struct FlowHost {
+    std::vector<int> tri;        // [F][3] device numbering
+    std::vector<int> inv_f;      // caller triangle -> device triangle (empty: the same numbering)
+};
 
 // device allocations of a factor shared by several contexts (Ctx::front_store)
 struct FrontStore {
@@ -517,7 +544,8 @@ struct Ctx {
     char *h_ring = nullptr;       // DOTS_READOUT_PINNED=<KB>: two pinned slots of that size the copies go through (A/B measurements)
     hipEvent_t ring_ev[2]{};
     int readout_pinned = 0;       // KB per slot; 0: copies go straight into the caller's memory
-    int64_t d2h_bytes = 0;        // bytes copied device -> host by dots_download and dots_readout (dots_debug_counter 9)
+    int64_t d2h_bytes = 0;        // bytes copied device -> host by dots_download, dots_readout and dots_flow_map (dots_debug_counter 9)
+    std::shared_ptr<FlowHost> flow;      // dots_flow_map: built on first use
     void *mg_allocs[160]{};
     int n_mg_allocs = 0;
     // constants of the KKT normalisation (solver_socp.py:303-313)

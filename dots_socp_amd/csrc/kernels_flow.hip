@@ -1,0 +1,123 @@
+// Flow map (dots_flow_map): particles traced through the transport on the device -- where the mass at a point ends up, and where it
+// is after every interval.  dots_socp_amd/flow.py: flow_map_host is the specification; the operations below are its operations in
+// its order (the build has -ffp-contract=off, fp64 division is correctly rounded), so the outputs equal it bit for bit.  It extends
+// what the reference returns (solver_socp.py:855-869, mu and E) without moving the two arrays to the host.
+//
+// One lane per particle; the loop over the intervals is inside the kernel because a particle's steps depend on each other.  A lane
+// reads the state where it lies (rows of mu and E, time fastest): a particle that stays in its triangle reads neighbouring doubles in
+// successive intervals.  The triangle's vertices and hat gradients stay in registers until the particle crosses an edge.  The three
+// weights and rates live in named registers and are selected with conditions: an array indexed by the exit corner would go to scratch.
+// It runs once per solve: the yardstick is the download of mu and E it replaces, not a roofline.
+#include "dots_dev.h"
+
+namespace dots {
+
+// max(x, 0.0) as the specification forms it: a NaN stays a NaN
+__device__ __forceinline__ double flow_clamp0(double x) { return 0.0 > x ? 0.0 : x; }
+
+struct FlowTriangle {
+    int64_t r0, r1, r2;      // first element of the vertices' rows of mu
+    int64_t e;               // first element of the triangle's three rows of E
+    double g00, g01, g02, g10, g11, g12, g20, g21, g22;      // hat gradients, [corner][xyz]
+};
+__device__ __forceinline__ void flow_load_triangle(const FlowArgs &a, int f, FlowTriangle &t) {
+    const int *v = a.tri + (int64_t)f * 3;
+    t.r0 = (int64_t)v[0] << a.tp_shift;
+    t.r1 = (int64_t)v[1] << a.tp_shift;
+    t.r2 = (int64_t)v[2] << a.tp_shift;
+    t.e = ((int64_t)f * 3) << a.tp_shift;
+    const double *g = a.hat + (int64_t)f * 9;
+    t.g00 = g[0]; t.g01 = g[1]; t.g02 = g[2];
+    t.g10 = g[3]; t.g11 = g[4]; t.g12 = g[5];
+    t.g20 = g[6]; t.g21 = g[7]; t.g22 = g[8];
+}
+
+__device__ __forceinline__ void flow_store_layer(const FlowArgs &a, int layer, int p, int f, double l0, double l1, double l2) {
+    const int64_t at = (int64_t)layer * a.P + p;
+    if (a.tri_at) a.tri_at[at] = a.perm_f ? a.perm_f[f] : f;
+    if (a.w_at) {
+        double *w = a.w_at + at * 3;
+        w[0] = l0; w[1] = l1; w[2] = l2;
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_flow_map(FlowArgs a) {
+    const int p = blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= a.P) return;
+    int f = a.start_tri[p];
+    double l0 = a.start_w[(int64_t)p * 3], l1 = a.start_w[(int64_t)p * 3 + 1], l2 = a.start_w[(int64_t)p * 3 + 2];
+    int status = 0, rested = 0, total = 0;
+    FlowTriangle t;
+    flow_load_triangle(a, f, t);
+    flow_store_layer(a, 0, p, f, l0, l1, l2);
+    const int pitch = 1 << a.tp_shift;
+    for (int j = 0; j < a.T; ++j) {
+        if (status == 0) {
+            double rem = a.h;
+            int crossings = 0;
+            for (;;) {
+                // density of the interval on the triangle, velocity from the momentum of its two nodes
+                // (loading the momentum beside the density instead of behind the floor test changed nothing: 2.38 against 2.37 ms)
+                const double rho = ((a.mu[t.r0 + j] + a.mu[t.r1 + j]) + a.mu[t.r2 + j]) * (1.0 / 3.0);
+                double u0 = 0.0, u1 = 0.0, u2 = 0.0;
+                if (rho > a.floor) {
+                    const double *e = a.E + t.e + j;
+                    u0 = (0.5 * (e[0] + e[1])) / rho;
+                    u1 = (0.5 * (e[pitch] + e[pitch + 1])) / rho;
+                    u2 = (0.5 * (e[2 * pitch] + e[2 * pitch + 1])) / rho;
+                }
+                // time derivatives of the weights
+                const double q0 = (t.g00 * u0 + t.g01 * u1) + t.g02 * u2;
+                const double q1 = (t.g10 * u0 + t.g11 * u1) + t.g12 * u2;
+                const double q2 = (t.g20 * u0 + t.g21 * u1) + t.g22 * u2;
+                // the first weight to reach zero before the interval ends (strict comparisons: the first corner wins a tie)
+                double best = rem;
+                int kmin = -1;
+                if (q0 < 0.0) { const double s = l0 / (-q0); if (s < best) { best = s; kmin = 0; } }
+                if (q1 < 0.0) { const double s = l1 / (-q1); if (s < best) { best = s; kmin = 1; } }
+                if (q2 < 0.0) { const double s = l2 / (-q2); if (s < best) { best = s; kmin = 2; } }
+                const double n0 = flow_clamp0(l0 + best * q0), n1 = flow_clamp0(l1 + best * q1), n2 = flow_clamp0(l2 + best * q2);
+                l0 = kmin == 0 ? 0.0 : n0;
+                l1 = kmin == 1 ? 0.0 : n1;
+                l2 = kmin == 2 ? 0.0 : n2;
+                if (kmin < 0) break;
+                rem = rem - best;
+                const int packed = a.nbr[(int64_t)f * 3 + kmin];
+                if (packed < 0) { status = 1; break; }
+                if (crossings == a.max_crossings) { ++rested; break; }
+                ++crossings;
+                ++total;
+                // the two kept weights go to the corners of the neighbour that name the same vertices
+                const double wa = kmin == 0 ? l1 : (kmin == 1 ? l2 : l0);      // corner (kmin + 1) % 3
+                const double wb = kmin == 0 ? l2 : (kmin == 1 ? l0 : l1);      // corner (kmin + 2) % 3
+                const int ca = (packed >> 2) & 3, cb = packed & 3;
+                l0 = ca == 0 ? wa : (cb == 0 ? wb : 0.0);
+                l1 = ca == 1 ? wa : (cb == 1 ? wb : 0.0);
+                l2 = ca == 2 ? wa : (cb == 2 ? wb : 0.0);
+                f = packed >> 4;
+                flow_load_triangle(a, f, t);
+            }
+        }
+        flow_store_layer(a, j + 1, p, f, l0, l1, l2);
+    }
+    a.o_tri[p] = a.perm_f ? a.perm_f[f] : f;
+    a.o_w[(int64_t)p * 3] = l0;
+    a.o_w[(int64_t)p * 3 + 1] = l1;
+    a.o_w[(int64_t)p * 3 + 2] = l2;
+    a.o_status[p] = status;
+    a.o_rested[p] = rested;
+    a.o_cross[p] = total;
+}
+
+int launch_flow_map(Ctx *c, const FlowArgs &a) {
+    hipLaunchKernelGGL(k_flow_map, dim3((unsigned)((a.P + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, a);
+    DOTS_HIP(hipGetLastError());
+    return 0;
+}
+void preload_flow_kernels() {
+    hipFuncAttributes attr;
+    (void)hipFuncGetAttributes(&attr, (const void *)k_flow_map);
+    (void)hipGetLastError();
+}
+
+}  // namespace dots

@@ -209,6 +209,40 @@ class DeviceProblem:
         self.readout_ms, self.readout_bytes = ms.value, self.debug_counter(9) - before
         return out_mu, out_E, mass, neg
 
+    def flow_map(self, start_triangle, start_weights, neighbours, floor, max_crossings=16, trajectory=False):
+        """Trace particles through the transport the context holds, on the device (dots_flow_map; flow.flow_map_host on the downloaded
+        ``mu`` and ``E`` is the specification and returns the same bits).  ``start_triangle`` (P,), ``start_weights`` (P, 3) and
+        ``neighbours`` (F, 3) (``flow.triangle_neighbours``) in the caller's numbering; ``floor`` in the units of the iterate as stored.
+        Returns the dict of ``flow_map_host``.  ``self.flow_map_ms`` / ``self.flow_map_bytes``: device milliseconds of the launch and
+        the bytes copied to the host by the last call."""
+        if self.slab:
+            raise ValueError("flow_map: not available on time slabs")
+        tri = np.ascontiguousarray(start_triangle, dtype=np.int32)
+        w = np.ascontiguousarray(start_weights, dtype=np.float64)
+        nbr = np.ascontiguousarray(neighbours, dtype=np.int32)
+        if tri.ndim != 1 or w.shape != (tri.shape[0], 3):
+            raise ValueError(f"flow_map: start_triangle (P,) and start_weights (P, 3) expected, got {tri.shape} and {w.shape}")
+        if nbr.shape != (self.F, 3):
+            raise ValueError(f"flow_map: neighbours must have shape ({self.F}, 3), got {nbr.shape}")
+        P = tri.shape[0]
+        out = {"triangle": np.empty(P, dtype=np.int32), "weights": np.empty((P, 3)), "status": np.empty(P, dtype=np.int32),
+               "rested": np.empty(P, dtype=np.int32), "crossings": np.empty(P, dtype=np.int32)}
+        if trajectory:
+            out["triangles_at"] = np.empty((self.T + 1, P), dtype=np.int32)
+            out["weights_at"] = np.empty((self.T + 1, P, 3))
+        ms = C.c_double()
+        d = _lib.FlowMapDesc()
+        d.n_particles, d.max_crossings, d.floor = P, int(max_crossings), float(floor)
+        d.start_triangle, d.start_weights, d.neighbours = _ptr(tri, C.c_int32), _ptr(w, C.c_double), _ptr(nbr, C.c_int32)
+        d.triangle, d.weights = _ptr(out["triangle"], C.c_int32), _ptr(out["weights"], C.c_double)
+        d.status, d.rested, d.crossings = _ptr(out["status"], C.c_int32), _ptr(out["rested"], C.c_int32), _ptr(out["crossings"], C.c_int32)
+        d.triangles_at, d.weights_at = _ptr(out.get("triangles_at"), C.c_int32), _ptr(out.get("weights_at"), C.c_double)
+        d.ms = C.pointer(ms)
+        before = self.debug_counter(9)
+        _lib.check(self.lib.dots_flow_map(self._h, C.byref(d)), "dots_flow_map")
+        self.flow_map_ms, self.flow_map_bytes = ms.value, self.debug_counter(9) - before
+        return out
+
     def _carry_from(self, who, src, entry, describe, factors, same_grid):
         """What the three carriers share: the guards (``same_grid``: one ``n_time``), ``describe()`` -- the method's own validation, giving
         its descriptor and the arrays it points to --, the factors, the call of ``entry`` and its check.  Returns the launches' milliseconds."""

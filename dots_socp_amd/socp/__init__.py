@@ -17,10 +17,14 @@ passed as ``solver=`` to the reference's ``run_dot_surface`` (interface.py:106-1
 device (``dots_readout``): two arrays cross to the host instead of twelve, and ``run_history.solver_stats["readout"]`` holds the
 layer sums of ``mu`` (``evaluate.mass_conservation_from_layers`` / ``negative_mass_from_layers``).  ``readout="host"`` downloads
 the whole solution and converts it in numpy: the same values bit for bit, kept as the baseline of measurements.
+
+``flow_map={"starts": "vertices"}`` (the keywords of ``AlmSolver.flow_map``; default None: nothing changes) adds ``solution["flow_map"]``,
+the transport map of the solution traced on the device (``dots_flow_map``; ``dots_socp_amd.flow.flow_map_host`` is the
+specification): where every start point ends up and, with ``trajectory``, where it is after every interval.  Not on time slabs.
 """
 import numpy as np
 
-from .solver_socp import (solver_socp, solver_socp_auto_cascade, solver_socp_cascade, solver_socp_many, solver_socp_mesh_cascade,
+from .solver_socp import (check_flow_map, solver_socp, solver_socp_auto_cascade, solver_socp_cascade, solver_socp_many, solver_socp_mesh_cascade,
                           solver_socp_spacetime_cascade)
 
 __all__ = ["solver_socp", "solver_raw", "solver", "solver_socp_many", "solver_raw_many", "solver_many",
@@ -67,7 +71,11 @@ def _geometry_with_areas(geometry):
     return g
 
 
-def _read_out_spec(readout, centred):
+def _read_out_spec(readout, centred, kwargs=None):
+    """The ``read_out`` a plug-in hands its solver; with the plug-in's keywords, ``flow_map`` is checked first -- before the library
+    is loaded -- and refused together with ``time_slab``."""
+    if kwargs is not None:
+        check_flow_map(kwargs.get("flow_map"), kwargs.get("time_slab"))
     if readout not in ("device", "host"):
         raise ValueError("readout must be 'device' or 'host'")
     return {"dot_units": True, "centred": centred} if readout == "device" else None
@@ -94,6 +102,8 @@ def _finish(solution, geometry, mu0, mu1, readout, centred):
     if centred:
         for cp in solution_dot.get("checkpoints") or []:
             _to_time_centered(cp, mu0, mu1)
+    if "flow_map" in solution:      # (positions and barycentric weights: no units to convert)
+        solution_dot["flow_map"] = solution["flow_map"]
     return solution_dot
 
 
@@ -103,7 +113,7 @@ def _end_points(geometry):
 
 def solver_raw(n_time, geometry, readout="device", **kwargs):
     """Solve the DOT problem with the GPU SOCP solver; solution on the time-staggered grid."""
-    solution_socp, run_history = solver_socp(n_time, geometry, read_out=_read_out_spec(readout, False), **kwargs)
+    solution_socp, run_history = solver_socp(n_time, geometry, read_out=_read_out_spec(readout, False, kwargs), **kwargs)
     return _finish(solution_socp, geometry, None, None, readout, False), run_history
 
 
@@ -118,7 +128,7 @@ def _to_time_centered(solution_dot, mu0, mu1):
 def solver(n_time, geometry, readout="device", **kwargs):
     """``solver_raw`` with the density moved to the time-centred grid and mu0 / mu1 as end points."""
     mu0, mu1 = _end_points(geometry)
-    solution_socp, run_history = solver_socp(n_time, geometry, read_out=_read_out_spec(readout, True), **kwargs)
+    solution_socp, run_history = solver_socp(n_time, geometry, read_out=_read_out_spec(readout, True, kwargs), **kwargs)
     return _finish(solution_socp, geometry, mu0, mu1, readout, True), run_history
 
 
@@ -127,7 +137,7 @@ solver.__name__ = "dot_solver_socp_center"
 
 def solver_raw_cascade(n_time, geometry, readout="device", **kwargs):
     """``solver_raw`` through the time cascade (``solver_socp_cascade``: ``levels``, ``level_tol`` and the keywords of ``solver_socp``)."""
-    solution_socp, run_history = solver_socp_cascade(n_time, geometry, read_out=_read_out_spec(readout, False), **kwargs)
+    solution_socp, run_history = solver_socp_cascade(n_time, geometry, read_out=_read_out_spec(readout, False, kwargs), **kwargs)
     return _finish(solution_socp, geometry, None, None, readout, False), run_history
 
 
@@ -137,7 +147,7 @@ solver_raw_cascade.__name__ = "dot_solver_socp_cascade"
 def solver_cascade(n_time, geometry, readout="device", **kwargs):
     """``solver`` through the time cascade: the density on the time-centred grid with mu0 / mu1 as end points."""
     mu0, mu1 = _end_points(geometry)
-    solution_socp, run_history = solver_socp_cascade(n_time, geometry, read_out=_read_out_spec(readout, True), **kwargs)
+    solution_socp, run_history = solver_socp_cascade(n_time, geometry, read_out=_read_out_spec(readout, True, kwargs), **kwargs)
     return _finish(solution_socp, geometry, mu0, mu1, readout, True), run_history
 
 
@@ -155,7 +165,7 @@ def solver_raw_mesh_cascade(n_time, geometries, readout="device", **kwargs):
     """``solver_raw`` on the finest of ``geometries`` through the cascade in space (``solver_socp_mesh_cascade``: ``level_tol`` and the
     keywords of ``solver_socp``)."""
     geometries, fine = _finest(geometries)
-    solution_socp, run_history = solver_socp_mesh_cascade(n_time, geometries, read_out=_read_out_spec(readout, False), **kwargs)
+    solution_socp, run_history = solver_socp_mesh_cascade(n_time, geometries, read_out=_read_out_spec(readout, False, kwargs), **kwargs)
     return _finish(solution_socp, fine, None, None, readout, False), run_history
 
 
@@ -167,7 +177,7 @@ def solver_mesh_cascade(n_time, geometries, readout="device", **kwargs):
     level's mu0 / mu1 as end points."""
     geometries, fine = _finest(geometries)
     mu0, mu1 = _end_points(fine)
-    solution_socp, run_history = solver_socp_mesh_cascade(n_time, geometries, read_out=_read_out_spec(readout, True), **kwargs)
+    solution_socp, run_history = solver_socp_mesh_cascade(n_time, geometries, read_out=_read_out_spec(readout, True, kwargs), **kwargs)
     return _finish(solution_socp, fine, mu0, mu1, readout, True), run_history
 
 
@@ -178,7 +188,7 @@ def solver_raw_spacetime_cascade(n_time, geometries, readout="device", **kwargs)
     """``solver_raw`` on the finest of ``geometries`` through the cascade in space and time (``solver_socp_spacetime_cascade``: ``levels``,
     ``level_tol`` and the keywords of ``solver_socp``)."""
     geometries, fine = _finest(geometries, "solver_socp_spacetime_cascade")
-    solution_socp, run_history = solver_socp_spacetime_cascade(n_time, geometries, read_out=_read_out_spec(readout, False), **kwargs)
+    solution_socp, run_history = solver_socp_spacetime_cascade(n_time, geometries, read_out=_read_out_spec(readout, False, kwargs), **kwargs)
     return _finish(solution_socp, fine, None, None, readout, False), run_history
 
 
@@ -190,7 +200,7 @@ def solver_spacetime_cascade(n_time, geometries, readout="device", **kwargs):
     finest level's mu0 / mu1 as end points."""
     geometries, fine = _finest(geometries, "solver_socp_spacetime_cascade")
     mu0, mu1 = _end_points(fine)
-    solution_socp, run_history = solver_socp_spacetime_cascade(n_time, geometries, read_out=_read_out_spec(readout, True), **kwargs)
+    solution_socp, run_history = solver_socp_spacetime_cascade(n_time, geometries, read_out=_read_out_spec(readout, True, kwargs), **kwargs)
     return _finish(solution_socp, fine, mu0, mu1, readout, True), run_history
 
 
@@ -201,7 +211,7 @@ def solver_raw_auto_cascade(n_time, geometry, readout="device", **kwargs):
     """``solver_raw`` through a cascade in space made of ``geometry`` alone (``solver_socp_auto_cascade``: ``coarse_levels``, ``ratio``,
     ``locate``, ``spacetime``, ``levels``, ``level_tol`` and the keywords of ``solver_socp``): the signature of ``solver_raw``, so it can be
     passed as ``solver=`` where one geometry is handed over."""
-    solution_socp, run_history = solver_socp_auto_cascade(n_time, geometry, read_out=_read_out_spec(readout, False), **kwargs)
+    solution_socp, run_history = solver_socp_auto_cascade(n_time, geometry, read_out=_read_out_spec(readout, False, kwargs), **kwargs)
     return _finish(solution_socp, geometry, None, None, readout, False), run_history
 
 
@@ -212,7 +222,7 @@ def solver_auto_cascade(n_time, geometry, readout="device", **kwargs):
     """``solver`` through a cascade in space made of ``geometry`` alone: the density on the time-centred grid with mu0 / mu1 as end
     points."""
     mu0, mu1 = _end_points(geometry)
-    solution_socp, run_history = solver_socp_auto_cascade(n_time, geometry, read_out=_read_out_spec(readout, True), **kwargs)
+    solution_socp, run_history = solver_socp_auto_cascade(n_time, geometry, read_out=_read_out_spec(readout, True, kwargs), **kwargs)
     return _finish(solution_socp, geometry, mu0, mu1, readout, True), run_history
 
 
@@ -221,13 +231,13 @@ solver_auto_cascade.__name__ = "dot_solver_socp_auto_cascade_center"
 
 def solver_raw_many(n_time, geometry, problems, readout="device", **kwargs):
     """``solver_raw`` for several problems on one surface (``solver_socp_many``): a list of ``(solution, run_history)``."""
-    results = solver_socp_many(n_time, geometry, problems, read_out=_read_out_spec(readout, False), **kwargs)
+    results = solver_socp_many(n_time, geometry, problems, read_out=_read_out_spec(readout, False, kwargs), **kwargs)
     return [(_finish(sol, geometry, None, None, readout, False), hist) for sol, hist in results]
 
 
 def solver_many(n_time, geometry, problems, readout="device", **kwargs):
     """``solver`` for several problems on one surface: each density on the time-centred grid with its own mu0 / mu1 as end points."""
-    results = solver_socp_many(n_time, geometry, problems, read_out=_read_out_spec(readout, True), **kwargs)
+    results = solver_socp_many(n_time, geometry, problems, read_out=_read_out_spec(readout, True, kwargs), **kwargs)
     out = []
     for p, (sol, hist) in zip(problems, results):
         mu0 = np.asarray(p.get("mu0", geometry.get("mu0")), dtype=np.float64)

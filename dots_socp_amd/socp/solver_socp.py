@@ -64,6 +64,24 @@ def check_time_nodes(n_time, lap_solver="modal_direct", time_slab=None, pcg_wind
             raise ValueError(f"lap_solver='modal_pcg' needs n_time + 1 <= {MODAL_PCG_MAX_NODES} (got {nodes}); use lap_solver='modal_direct'")
 
 
+FLOW_MAP_KEYS = ("starts", "floor", "max_crossings", "trajectory")
+
+
+def check_flow_map(flow_map, time_slab=None):
+    """Refuse, before any device call, a ``flow_map`` request that cannot be served: ``None`` or the keywords of ``AlmSolver.flow_map``
+    as a dict; never on a time slab (the particles are traced by one context, which holds every time node)."""
+    if flow_map is None:
+        return None
+    if time_slab is not None:
+        raise ValueError("flow_map is not available on time slabs: the particles are traced on one GPU, which holds every time node")
+    if not isinstance(flow_map, dict):
+        raise ValueError(f"flow_map must be None or a dict with any of {list(FLOW_MAP_KEYS)}")
+    unknown = set(flow_map) - set(FLOW_MAP_KEYS)
+    if unknown:
+        raise ValueError(f"flow_map: unknown option(s) {sorted(unknown)}; known: {list(FLOW_MAP_KEYS)}")
+    return dict(flow_map)
+
+
 def _validate_checkpoints(tol_checkpoints, tol):
     """solver_socp.py:85-94."""
     if tol_checkpoints is None:
@@ -617,12 +635,50 @@ class AlmSolver:
         mu, E, info = self._read_out(self.r * self.dual_scale, w_vertex, w_triangle, centred, mu0, mu1, sums=True)
         return {"mu": mu, "E": E}, info
 
-    def finalize(self, download=True, outputs=None, read_out=None):
+    def flow_map(self, starts="vertices", floor=None, max_crossings=16, trajectory=False):
+        """The transport map of the current iterate, traced on the device (DeviceProblem.flow_map; flow.flow_map_host is the
+        specification): where the mass at a point ends up, and with ``trajectory`` where it is after every interval.
+        ``starts``: "vertices" (one particle on every vertex: flow.vertex_starts) or ``(triangle (P,), weights (P, 3))`` in the
+        numbering of ``geometry`` -- arbitrary points of the surface come from ``cascade.locate_device``, which returns exactly
+        these two arrays.  ``floor``: densities up to it carry no velocity, in the units of the recovered ``mu`` (default
+        ``1e-3 * max(mu0 / (area_vertices / 3))``); it is divided by the recovery factor before the call, since the device holds
+        the iterate.  Returns the dict of ``flow_map_host`` plus ``positions`` (P, 3), and with ``trajectory`` ``positions_at``
+        (T + 1, P, 3); ``ms`` and ``bytes``: device milliseconds of the launch and bytes copied to the host."""
+        from .. import flow
+
+        if self.dev.slab:
+            raise ValueError("flow_map is not available on time slabs: the particles are traced on one GPU, which holds every time node")
+        vertices, triangles = np.asarray(self.geometry["vertices"], dtype=np.float64), np.asarray(self.geometry["triangles"])
+        if isinstance(starts, str):
+            if starts != "vertices":
+                raise ValueError("flow_map: starts must be 'vertices' or (triangle, weights)")
+            start_triangle, start_weights = flow.vertex_starts(triangles, vertices.shape[0])
+        else:
+            start_triangle, start_weights = starts
+        if floor is None:
+            from . import _geometry_with_areas
+
+            g = _geometry_with_areas(self.geometry)
+            floor = 1e-3 * float(np.max(np.asarray(g["mu0"], dtype=np.float64) / (np.asarray(g["area_vertices"], dtype=np.float64) / 3.0)))
+        if getattr(self, "_neighbours", None) is None:
+            self._neighbours = flow.triangle_neighbours(triangles)
+        dev = self.dev
+        out = dev.flow_map(start_triangle, start_weights, self._neighbours, float(floor) / (self.r * self.dual_scale),
+                           max_crossings=max_crossings, trajectory=trajectory)
+        out["positions"] = flow.positions(vertices, triangles, out["triangle"], out["weights"])
+        if trajectory:
+            out["positions_at"] = flow.positions(vertices, triangles, out["triangles_at"], out["weights_at"])
+        out["ms"], out["bytes"] = dev.flow_map_ms, dev.flow_map_bytes
+        return out
+
+    def finalize(self, download=True, outputs=None, read_out=None, flow_map=None):
         """``outputs``: None = the twelve arrays, or a tuple of names: only those are downloaded.  ``read_out``: None, or the
         keywords of ``read_out`` (dot_units, centred): the solution is then its ``{"mu", "E"}`` -- nothing else is downloaded --
-        and ``run_history.solver_stats["readout"]`` its info."""
+        and ``run_history.solver_stats["readout"]`` its info.  ``flow_map``: None, or the keywords of ``flow_map`` as a dict:
+        ``solution["flow_map"]`` then holds what it returns."""
         if read_out is not None and outputs is not None:
             raise ValueError("finalize: outputs and read_out are mutually exclusive (read_out returns mu and E only)")
+        flow_map = check_flow_map(flow_map, getattr(self.dev, "slab", None))
         dev, hist, validator = self.dev, self.run_history, self.kkt_validator
         self._kkt_prefetch(range(7))
         validator.validator.validate(list(range(7)))
@@ -650,6 +706,8 @@ class AlmSolver:
             if unknown:
                 raise ValueError(f"finalize: unknown outputs {sorted(unknown)}")
             solution = {name: self.recovered(name, self._download(name)) for name in names}
+        if flow_map is not None:
+            solution["flow_map"] = self.flow_map(**flow_map)
         solution["checkpoints"] = self.checkpoint_solutions if self.checkpoint_solutions else None
         logger.info("Number of iterations: %d   Iteration time: %.2f", self.counter_main, hist.running_time)
         return solution, hist
@@ -686,6 +744,7 @@ def solver_socp(
         outputs=None,
         read_out=None,
         pcg_windows=False,
+        flow_map=None,
 ):
     """SOCP for dynamical optimal transport on a discrete surface, on the GPU.
 
@@ -698,9 +757,12 @@ def solver_socp(
     plug-ins return them, formed on the device (``checkpoints`` stay in the solver's units).
     ``pcg_windows``: above 256 time nodes the modal PCG runs in windows of 256 modes: ``lap_solver="modal_pcg"`` takes
     ``n_time + 1 <= 1024`` with either preconditioner, and ``modal_direct`` falls back to it when its factor does not fit.
+    ``flow_map``: the keywords of ``AlmSolver.flow_map`` as a dict (``{"starts": "vertices"}``): ``solution["flow_map"]`` is the
+    transport map of the solution, traced on the device; None (the default) changes nothing.
     """
     if read_out is not None and outputs is not None:
         raise ValueError("solver_socp: outputs and read_out are mutually exclusive (read_out returns mu and E only)")
+    flow_map = check_flow_map(flow_map)
     alm = AlmSolver(n_time, geometry, congestion=congestion, nit=nit, eps=eps, tol=tol, tau=tau, is_z_scaling=is_z_scaling,
                     is_constant_scaling=is_constant_scaling, check_kkt_step_by_step=check_kkt_step_by_step,
                     init_solution=init_solution, tol_checkpoints=tol_checkpoints, time_limit=time_limit, is_palm=is_palm,
@@ -710,7 +772,7 @@ def solver_socp(
         for _ in range(nit):
             if alm.iterate():
                 break
-        return alm.finalize(outputs=outputs, read_out=read_out)
+        return alm.finalize(outputs=outputs, read_out=read_out, flow_map=flow_map)
     finally:
         alm.close()
 
@@ -759,7 +821,7 @@ def _batch_problems(geometry, problems, common):
     return out
 
 
-def solver_socp_many(n_time, geometry, problems, *, max_batch=4, read_out=None, **common):
+def solver_socp_many(n_time, geometry, problems, *, max_batch=4, read_out=None, flow_map=None, **common):
     """Solve several transport problems on ONE surface with one factor of the direct solver.
 
     ``geometry`` holds the mesh (``vertices``, ``triangles``; ``mu0`` / ``mu1`` are defaults for problems without their own);
@@ -772,10 +834,11 @@ def solver_socp_many(n_time, geometry, problems, *, max_batch=4, read_out=None, 
     Returns ``[(solution, run_history), ...]`` in input order, each what ``solver_socp(n_time, {**geometry, "mu0": ..., "mu1": ...},
     **common, **problem)`` returns, bit for bit; ``run_history.solver_stats["batch"]`` = {"size", "index", "max_batch", "steps_time_note"}.
     Each problem's running time and time limit start when it is admitted.  A factor that does not fit raises the library's memory error
-    (there is no batched PCG).  ``read_out``: as for ``solver_socp``, for every problem (with its own mu0 / mu1)."""
+    (there is no batched PCG).  ``read_out`` and ``flow_map``: as for ``solver_socp``, for every problem (with its own mu0 / mu1)."""
     from .. import geometry as geo
     from ..device import step_many
 
+    flow_map = check_flow_map(flow_map)
     probs = _batch_problems(geometry, problems, common)
     if int(max_batch) < 1:
         raise ValueError("solver_socp_many: max_batch >= 1")
@@ -833,7 +896,7 @@ def solver_socp_many(n_time, geometry, problems, *, max_batch=4, read_out=None, 
             still = []
             for i, alm in active:
                 if alm.finished:
-                    sol, hist = alm.finalize(read_out=read_out)
+                    sol, hist = alm.finalize(read_out=read_out, flow_map=flow_map)
                     hist.solver_stats["batch"] = {"size": len(probs), "index": i, "max_batch": int(max_batch), "steps_time_note": BATCH_TIME_NOTE}
                     results[i] = (sol, hist)
                     done.append((i, alm))
@@ -898,7 +961,7 @@ def _cascade_options(n_time, levels, level_tol, kwargs):
     return levels, level_tol, opts
 
 
-def solver_socp_cascade(n_time, geometry, levels=None, level_tol=None, read_out=None, **kwargs):
+def solver_socp_cascade(n_time, geometry, levels=None, level_tol=None, read_out=None, flow_map=None, **kwargs):
     """``solver_socp`` through a coarse-to-fine cascade in time: the problem is solved on the time grids ``levels`` (``n_time`` values,
     increasing, the last one ``n_time``) one after the other, each level warm-started from the recovered solution of the one before,
     interpolated linearly in time on the device (AlmSolver ``init_from``; cascade.prolong_time is the specification).  The number of
@@ -914,10 +977,11 @@ def solver_socp_cascade(n_time, geometry, levels=None, level_tol=None, read_out=
     Returns ``(solution, run_history)`` of the finest level; ``run_history.running_time`` is that level's own, and
     ``run_history.solver_stats["cascade"]`` = {"levels": [one record per level: n_time, tol, iterations, running_time, setup_seconds,
     prolong_ms (device events; None on the coarsest level), cost, kkt_max], "total_seconds"} has the whole cascade.
-    ``read_out``: as for ``solver_socp``, for the finest level.  The mesh is the same on every level; ``solver_socp_spacetime_cascade``
-    coarsens the mesh along with the time grid."""
+    ``read_out`` and ``flow_map``: as for ``solver_socp``, for the finest level.  The mesh is the same on every level;
+    ``solver_socp_spacetime_cascade`` coarsens the mesh along with the time grid."""
     from .. import geometry as geo
 
+    flow_map = check_flow_map(flow_map, kwargs.get("time_slab"))
     levels, level_tol, opts = _cascade_options(n_time, levels, level_tol, kwargs)
     tol, nit = opts.pop("tol", 1e-4), int(opts.pop("nit", 1000))
     time_limit = opts.pop("time_limit", 1000)
@@ -943,7 +1007,7 @@ def solver_socp_cascade(n_time, geometry, levels=None, level_tol=None, read_out=
             for _ in range(nit):
                 if alm.iterate():
                     break
-            solution, hist = alm.finalize(download=last, read_out=read_out if last else None)
+            solution, hist = alm.finalize(download=last, read_out=read_out if last else None, flow_map=flow_map if last else None)
             records.append({"n_time": int(T), "tol": float(alm.tol), "iterations": int(alm.counter_main) + 1, "running_time": float(hist.running_time),
                             "setup_seconds": float(setup), "prolong_ms": alm.prolong_ms, "cost": float(hist.history["Transportation cost"][-1]),
                             "kkt_max": float(np.nanmax(np.asarray(hist.kkt_errors[-1], dtype=np.float64)))})
@@ -1013,7 +1077,7 @@ def _max_distance(geom):
     return None if d is None else float(d)
 
 
-def solver_socp_mesh_cascade(n_time, geometries, level_tol=None, read_out=None, **kwargs):
+def solver_socp_mesh_cascade(n_time, geometries, level_tol=None, read_out=None, flow_map=None, **kwargs):
     """``solver_socp`` through a coarse-to-fine cascade in space: the problem is solved on the meshes ``geometries`` (coarse to fine,
     every one after the first the nested refinement of the one before with its ``parents``: ``meshes.refine_levels``), all at
     ``n_time``, each level warm-started from the recovered solution of the one before, carried to the refinement on the device
@@ -1032,7 +1096,8 @@ def solver_socp_mesh_cascade(n_time, geometries, level_tol=None, read_out=None, 
     Returns ``(solution, run_history)`` of the finest level; ``run_history.solver_stats["mesh_cascade"]`` = {"levels": [one record
     per level: n_vertices, n_triangles, tol, iterations, running_time, setup_seconds, prolong_ms and prolong_bytes (None on the coarsest
     level), cost, kkt_max, device_bytes, transfer ("nested" | "located", None on the coarsest level), max_distance (of a located
-    level, else None)], "total_seconds"}.  ``read_out``: as for ``solver_socp``, for the finest level."""
+    level, else None)], "total_seconds"}.  ``read_out`` and ``flow_map``: as for ``solver_socp``, for the finest level."""
+    flow_map = check_flow_map(flow_map, kwargs.get("time_slab"))
     geometries, level_tol, opts = _mesh_cascade_options(geometries, level_tol, kwargs)
     tol, nit = opts.pop("tol", 1e-4), int(opts.pop("nit", 1000))
     time_limit = opts.pop("time_limit", 1000)
@@ -1053,7 +1118,7 @@ def solver_socp_mesh_cascade(n_time, geometries, level_tol=None, read_out=None, 
             for _ in range(nit):
                 if alm.iterate():
                     break
-            solution, hist = alm.finalize(download=last, read_out=read_out if last else None)
+            solution, hist = alm.finalize(download=last, read_out=read_out if last else None, flow_map=flow_map if last else None)
             records.append({"n_vertices": int(alm.dev.V), "n_triangles": int(alm.dev.F), "tol": float(alm.tol), "iterations": int(alm.counter_main) + 1,
                             "running_time": float(hist.running_time), "setup_seconds": float(setup), "prolong_ms": alm.prolong_ms,
                             "prolong_bytes": getattr(alm.dev, "prolong_bytes", None), "cost": float(hist.history["Transportation cost"][-1]),
@@ -1092,7 +1157,7 @@ def _spacetime_cascade_options(n_time, geometries, levels, level_tol, kwargs):
     return geometries, levels, level_tol, opts
 
 
-def solver_socp_spacetime_cascade(n_time, geometries, levels=None, level_tol=None, read_out=None, **kwargs):
+def solver_socp_spacetime_cascade(n_time, geometries, levels=None, level_tol=None, read_out=None, flow_map=None, **kwargs):
     """``solver_socp`` through a coarse-to-fine cascade in space AND time: the meshes ``geometries`` (coarse to fine, each level above the
     first with ``parents`` or ``transfer``, as for ``solver_socp_mesh_cascade``) are solved on the time grids ``levels`` (one ``n_time`` per
     geometry, never decreasing, the last one ``n_time``, each one valid for the Laplacian solver).  A level that is coarser in both
@@ -1107,7 +1172,9 @@ def solver_socp_spacetime_cascade(n_time, geometries, levels=None, level_tol=Non
     level, the coarse solver released before the finer factor is built.
 
     Returns ``(solution, run_history)`` of the finest level; ``run_history.solver_stats["spacetime_cascade"]`` = {"levels": [the records of
-    ``solver_socp_mesh_cascade`` plus ``n_time``], "total_seconds"}.  ``read_out``: as for ``solver_socp``, for the finest level."""
+    ``solver_socp_mesh_cascade`` plus ``n_time``], "total_seconds"}.  ``read_out`` and ``flow_map``: as for ``solver_socp``, for the
+    finest level."""
+    flow_map = check_flow_map(flow_map, kwargs.get("time_slab"))
     geometries, levels, level_tol, opts = _spacetime_cascade_options(n_time, geometries, levels, level_tol, kwargs)
     tol, nit = opts.pop("tol", 1e-4), int(opts.pop("nit", 1000))
     time_limit = opts.pop("time_limit", 1000)
@@ -1128,7 +1195,7 @@ def solver_socp_spacetime_cascade(n_time, geometries, levels=None, level_tol=Non
             for _ in range(nit):
                 if alm.iterate():
                     break
-            solution, hist = alm.finalize(download=last, read_out=read_out if last else None)
+            solution, hist = alm.finalize(download=last, read_out=read_out if last else None, flow_map=flow_map if last else None)
             records.append({"n_time": int(T), "n_vertices": int(alm.dev.V), "n_triangles": int(alm.dev.F), "tol": float(alm.tol),
                             "iterations": int(alm.counter_main) + 1, "running_time": float(hist.running_time), "setup_seconds": float(setup),
                             "prolong_ms": alm.prolong_ms, "prolong_bytes": getattr(alm.dev, "prolong_bytes", None),
@@ -1186,7 +1253,7 @@ def _auto_cascade_options(n_time, coarse_levels, ratio, locate, spacetime, level
 
 
 def solver_socp_auto_cascade(n_time, geometry, coarse_levels=2, ratio=4.0, locate="device", spacetime=False, levels=None, level_tol=None,
-                             read_out=None, **kwargs):
+                             read_out=None, flow_map=None, **kwargs):
     """``solver_socp`` through a cascade in space for a caller with ONE geometry: ``coarse_levels`` coarser meshes are made of it
     (``meshes.coarsen_levels``: half-edge-collapse decimation by ``ratio`` per level on the host, every level located on the one below
     with ``locate`` -- "device": ``dots_mesh_locate`` on the solver's GPU --, ``mu0`` / ``mu1`` restricted), then the levels are handed
@@ -1200,9 +1267,10 @@ def solver_socp_auto_cascade(n_time, geometry, coarse_levels=2, ratio=4.0, locat
     mesh that does not coarsen); every option is checked before the levels are built."""
     from .. import meshes
 
+    flow_map = check_flow_map(flow_map, kwargs.get("time_slab"))
     n_coarse = _auto_cascade_options(n_time, coarse_levels, ratio, locate, spacetime, levels, level_tol, kwargs)
     if n_coarse == 0:
-        return solver_socp(n_time, geometry, read_out=read_out, **kwargs)
+        return solver_socp(n_time, geometry, read_out=read_out, flow_map=flow_map, **kwargs)
     t_start = time.perf_counter()
     geometries = meshes.coarsen_levels(geometry, n_coarse + 1, ratio=ratio, locate=locate, device=kwargs.get("device", 0))
     build = time.perf_counter() - t_start
@@ -1211,8 +1279,8 @@ def solver_socp_auto_cascade(n_time, geometry, coarse_levels=2, ratio=4.0, locat
     opts = dict(kwargs)
     opts["time_limit"] = max(opts.get("time_limit", 1000) - build, 0.0)
     if spacetime:
-        solution, hist = solver_socp_spacetime_cascade(n_time, geometries, levels=levels, level_tol=level_tol, read_out=read_out, **opts)
+        solution, hist = solver_socp_spacetime_cascade(n_time, geometries, levels=levels, level_tol=level_tol, read_out=read_out, flow_map=flow_map, **opts)
     else:
-        solution, hist = solver_socp_mesh_cascade(n_time, geometries, level_tol=level_tol, read_out=read_out, **opts)
+        solution, hist = solver_socp_mesh_cascade(n_time, geometries, level_tol=level_tol, read_out=read_out, flow_map=flow_map, **opts)
     hist.solver_stats["auto_cascade"] = {"levels": records, "build_seconds": build}
     return solution, hist

@@ -660,6 +660,47 @@ typedef struct dots_readout_desc {
 } dots_readout_desc;
 int dots_readout(dots_ctx *ctx, const dots_readout_desc *desc);
 
+/* ---- flow map: particles traced through the transport on the device ------------------------------------------------------------
+ * dots_flow_map moves n_particles points of the surface along the velocity E / mu of the state the context holds, from time 0 to
+ * time 1, and returns where they end up (and, on request, where they are after every interval).  It extends what the reference
+ * returns at solver_socp.py:855-869 (mu and E): the transport map is formed from them where they lie, and only a few numbers per
+ * particle cross to the host instead of the two arrays.  dots_socp_amd/flow.py: flow_map_host is the specification, and the
+ * outputs equal it bit for bit on the downloaded mu and E.
+ * A particle is a triangle and three barycentric weights.  In interval j = 0 .. T - 1 (length h = 1 / T) it moves with the
+ * velocity u = 0.5 (E[j] + E[j + 1]) / rho of the triangle it is in -- E lives on the nodes, mu on the intervals; rho = the mean
+ * of mu[j] over the triangle's vertices, and u = 0 where rho <= floor (or is not a number) -- through the rates hat_grad . u of
+ * its weights (the hat gradients of dots_problem_desc; only the tangential part of u enters).  Where a weight reaches 0 before
+ * the interval ends the particle crosses the edge opposite that corner into `neighbours` and goes on with the time that is left.
+ * On a boundary edge (-1) it stops for good (status 1).  After max_crossings crossings in one interval it rests on the edge until
+ * the next interval (`rested` counts these; two triangles that push a particle at each other).  Weights are never renormalised.
+ * Particles are taken and returned in the CALLER's triangle numbering; corners keep their index in every numbering.
+ * `floor` is in the units of the iterate as stored: mu and E share one recovery factor and only their ratio is used.
+ * A pending penalty division is carried out first, as for a download; z_mid is neither needed nor produced (the call succeeds after
+ * a DOTS_STEP_SKIP_Z_MID step); the state, carried sums, fused KKT sums and a launch ahead are left as they are.  Works on contexts
+ * of every Laplacian solver, at every n_time + 1 <= 1024, and on members of a batch (on their own stream).  One launch of
+ * ceil(n_particles / 256) workgroups, one lane per particle; only the outputs cross to the host (counted in dots_debug_counter 9).
+ * DOTS_ERR_ARGUMENT (nothing launched): NULL desc or a NULL required pointer, n_particles < 1, a start triangle or a neighbour
+ * index out of range, a neighbour entry that does not share the edge opposite its corner, a weight that is negative or not finite,
+ * max_crossings outside 1 .. 255, a floor that is not a number; DOTS_ERR_STATE: a time slab. */
+typedef struct dots_flow_map_desc {
+    int32_t n_particles;
+    int32_t max_crossings;          /* 1 .. 255: crossings per interval before the particle rests                       */
+    const int32_t *start_triangle;  /* host [n_particles], caller numbering                                             */
+    const double *start_weights;    /* host [n_particles][3]: finite, >= 0                                              */
+    const int32_t *neighbours;      /* host [F][3], caller numbering: the triangle across the edge opposite corner k
+                                       (the edge between corners (k + 1) % 3 and (k + 2) % 3), -1 on a boundary edge    */
+    double floor;                   /* densities up to this one carry no velocity                                       */
+    int32_t *triangle;              /* host out [n_particles]                                                           */
+    double *weights;                /* host out [n_particles][3]                                                        */
+    int32_t *status;                /* host out [n_particles]: 0, or 1 stopped at a boundary edge                       */
+    int32_t *rested;                /* host out [n_particles]: intervals cut short at max_crossings                     */
+    int32_t *crossings;             /* host out [n_particles]: edges crossed in all                                     */
+    int32_t *triangles_at;          /* NULL, or host out [T + 1][n_particles]: layer 0 the start, layer l after l intervals */
+    double *weights_at;             /* NULL, or host out [T + 1][n_particles][3]                                        */
+    double *ms;                     /* NULL, or out: device milliseconds of the launch                                  */
+} dots_flow_map_desc;
+int dots_flow_map(dots_ctx *ctx, const dots_flow_map_desc *desc);
+
 /* ---- levels of a cascade in space from ONE mesh: coarsen on the host, locate on the device ------------------------------------
  * dots_coarsen: half-edge-collapse decimation of the mesh (xyz [V][3], tri [F][3]) towards `n_target` vertices, host only (no
  * device work; dots_socp_amd/meshes.py: coarsen(backend="python") is the specification and states the rules; both return the same
@@ -724,8 +765,8 @@ int dots_bench_kernel(dots_ctx *ctx, int which, int reps, double *ms_per_launch,
  * beta_mid with the non-temporal hint (decided by dots_front_setup from the sizes of factor and state), 7 sweep launches the last
  * batched solve (dots_laplacian_solve_many, dots_step_many, dots_bench_many) enqueued, read on the batch's first context, 8 of those, the
  * launches that took fewer right-hand sides than their chunk of DOTS_FRONT_NR problems held because NR regions of LDS would not fit or
- * a workgroup of 1024 threads takes fewer (the launch was split), 9 bytes this context has copied device -> host through dots_download
- * and dots_readout since it was created (the layer sums of dots_readout are written by the device itself and not copied), 10 device
+ * a workgroup of 1024 threads takes fewer (the launch was split), 9 bytes this context has copied device -> host through dots_download,
+ * dots_readout and dots_flow_map since it was created (the layer sums of dots_readout are written by the device itself and not copied), 10 device
  * allocations this context holds for its factor (0 without one, also after a dots_front_setup that failed), 11 the launches the
  * last multigrid V-cycle enqueued on this context took, as a bit mask: 1 restriction with a workgroup per coarse row, 2 restriction
  * with a thread per entry, 4 coarsest solve with a workgroup per row, 8 coarsest solve with a thread per entry, 16 the one-launch
