@@ -2,7 +2,7 @@
 the host.
 
 A solution on a coarse time grid is a good starting point for a finer one (``init_solution``, solver_socp.py:38,70-71).  This
-module is the single definition of the interpolation that the device kernel (``dots_prolong_time``, csrc/kernels_alm.hip), the
+module is the single definition of the interpolation that the device kernel (``dots_prolong_time``, csrc/kernels_carry.hip), the
 tests and the oracle-side checks share:
 
 * node arrays (``phi``, ``B``, ``E``; n + 1 entries along the time axis) live at ``t_i = i / n``; interval arrays (``A``,
@@ -17,7 +17,7 @@ tests and the oracle-side checks share:
 ``time_weights`` computes the tables ``j`` and ``w`` once, on the host; the device reads the same tables, so both sides perform the
 same operations on the same numbers.
 
-The transfer in space (``prolong_space``; ``dots_prolong_space``, k_carry_space in csrc/kernels_alm.hip) goes from a mesh to its
+The transfer in space (``prolong_space``; ``dots_prolong_space``, k_carry_space in csrc/kernels_carry.hip) goes from a mesh to its
 nested refinement (``meshes.subdivide``: ``parents``) on one time grid; ``space_row_maps`` turns ``parents`` and the two device
 numberings into the row maps the kernel reads.
 

@@ -1436,21 +1436,11 @@ int dots_bench_many(dots_ctx *const *cs, int n, int reps, double *ms) {
 
 // ---- carrying the state from one context to another (dots_prolong_time, dots_prolong_space, dots_transfer_space, dots_carry_spacetime) --
 // What the four entry points share.  An entry point calls carry_guard, validates its descriptor -- a bad argument leaves both contexts
-// untouched --, lists its tables and calls carry_state with a callable that launches one array.  carry_state brings the source up to
-// date, prepares the destination, puts the tables one after another into one device buffer (doubles first keeps them aligned) and,
-// with both streams ordered, calls launch(array id, factor) for each of the twelve arrays.  The order is the protocol: the destination's
-// stream waits for what the source has enqueued, whatever the source does next -- its release included -- comes after the reads, and
-// the buffer is freed after the synchronise, also when a launch failed.  `what`: the tables' noun in the messages.
-extern "C++" {      // (a template)
-
-struct CarryTable {
-    const void *host;      // the caller's table (null with 0 bytes: not passed)
-    size_t bytes;
-    char *dev;             // where carry_state put it
-    template <class T>
-    const T *at() const { return bytes ? (const T *)dev : nullptr; }
-};
-
+// untouched --, lists its tables in a CarryTables record and calls carry_state.  carry_state brings the source up to date, prepares the
+// destination, puts the tables one after another into one device buffer (doubles first keeps them aligned) and, with both streams
+// ordered, calls launch_carry with the device's copy of the record for each of the twelve arrays.  The order is the protocol: the
+// destination's stream waits for what the source has enqueued, whatever the source does next -- its release included -- comes after the
+// reads, and the buffer is freed after the synchronise, also when a launch failed.  `what`: the tables' noun in the messages.
 static int carry_guard(const std::string &who, const dots_ctx *dst, const dots_ctx *src, const void *desc) {
     if (!dst || !src || !desc) { set_error(who + ": null argument"); return DOTS_ERR_ARGUMENT; }
     if (dst == src) { set_error(who + ": source and destination are one context"); return DOTS_ERR_ARGUMENT; }
@@ -1471,32 +1461,72 @@ static int carry_space_shapes(const char *who, const char *what, const Dev &dd, 
     return DOTS_ERR_ARGUMENT;
 }
 
-template <size_t N, class Launch>
-static int carry_state(const std::string &who, const char *what, dots_ctx *dst, dots_ctx *src, const double *factor, double *ms, CarryTable (&tab)[N],
-                       Launch launch) {
+// every time-table entry names two source time points of the row it reads
+static int check_time_tables(const char *who, const CarryTables &t, const Dev &dd, const Dev &ds) {
+    const int nn = dd.T + 1, ni = dd.T;
+    for (int i = 0; i < nn + ni; ++i) {
+        const bool node = i < nn;
+        const int j = node ? t.node_j[i] : t.interval_j[i - nn];
+        const double w = node ? t.node_w[i] : t.interval_w[i - nn];
+        const int top = std::max((node ? ds.T + 1 : ds.T) - 2, 0);
+        if (j < 0 || j > top || !(w >= 0.0 && w <= 1.0)) {
+            char buf[240];
+            snprintf(buf, sizeof buf, "%s: %s table entry %d (j = %d, w = %g) out of range (0 <= j <= %d, 0 <= w <= 1)", who, node ? "node" : "interval",
+                     node ? i : i - nn, j, w, top);
+            set_error(buf);
+            return DOTS_ERR_ARGUMENT;
+        }
+    }
+    return 0;
+}
+
+static size_t carry_rows_per_vertex(int mode) { return mode == CARRY_SAME ? 1 : (mode == CARRY_NESTED ? 2 : 3); }
+
+// every index that was passed names a row / a corner of the source; every weight is a finite number >= 0.  vname, fname: what the
+// entry point's descriptor calls the vertex and the triangle table
+static int check_space_tables(const std::string &who, const char *vname, const char *fname, const CarryTables &t, const Dev &dd, const Dev &ds) {
+    const size_t nv = carry_rows_per_vertex(t.mode) * (size_t)dd.V, nf = (size_t)dd.F;
+    for (size_t i = 0; t.vsrc && i < nv; ++i) {
+        if (t.vsrc[i] < 0 || t.vsrc[i] >= ds.V) { set_error(who + ": " + vname + " entry out of range"); return DOTS_ERR_ARGUMENT; }
+        if (t.vw && !(t.vw[i] >= 0.0 && std::isfinite(t.vw[i]))) { set_error(who + ": a weight that is negative or not finite"); return DOTS_ERR_ARGUMENT; }
+    }
+    for (size_t i = 0; t.fsrc && i < nf; ++i)
+        if (t.fsrc[i] < 0 || t.fsrc[i] >= ds.F) { set_error(who + ": " + fname + " entry out of range"); return DOTS_ERR_ARGUMENT; }
+    for (size_t i = 0; t.csrc && i < 3 * nf; ++i)
+        if (t.csrc[i] < 0 || t.csrc[i] > 2) { set_error(who + ": csrc entry outside 0 .. 2"); return DOTS_ERR_ARGUMENT; }
+    return 0;
+}
+
+static int carry_state(const std::string &who, const char *what, dots_ctx *dst, dots_ctx *src, const double *factor, double *ms, const CarryTables &host) {
     int rc = check(src, true);      // (a pending penalty division is carried out, as for a download)
     if (rc) return rc;
     if (src->zmid_stale) { set_error(who + ": the source's z_mid was not materialised by its last step (dots_step_flags)"); return DOTS_ERR_STATE; }
     if ((rc = materialise_zmid(src))) return rc;
     if ((rc = check(dst, false, true))) return rc;
     dst->pending_div = 0.0;      // (every array a pending division would have touched is replaced)
+    const size_t nn = (size_t)dst->d.T + 1, ni = (size_t)dst->d.T, V = (size_t)dst->d.V, F = (size_t)dst->d.F, per = carry_rows_per_vertex(host.mode);
+    const void *from[8] = {host.node_w, host.interval_w, host.vw, host.node_j, host.interval_j, host.vsrc, host.fsrc, host.csrc};
+    const size_t size[8] = {sizeof(double) * nn, sizeof(double) * ni, sizeof(double) * 3 * V, sizeof(int32_t) * nn,
+                            sizeof(int32_t) * ni, sizeof(int32_t) * per * V, sizeof(int32_t) * F, sizeof(int32_t) * 3 * F};
     size_t bytes = 0;
-    for (const CarryTable &t : tab) bytes += t.bytes;
-    char *buf = nullptr;
+    for (int k = 0; k < 8; ++k) bytes += from[k] ? size[k] : 0;
+    char *buf = nullptr, *at[8];
     DOTS_HIP(hipMalloc((void **)&buf, bytes));
     hipError_t e = hipSuccess;
     bytes = 0;
-    for (CarryTable &t : tab) {
-        t.dev = buf + bytes;
-        if (e == hipSuccess && t.bytes) e = hipMemcpyAsync(t.dev, t.host, t.bytes, hipMemcpyHostToDevice, dst->stream);
-        bytes += t.bytes;
+    for (int k = 0; k < 8; ++k) {
+        at[k] = from[k] ? buf + bytes : nullptr;      // (a table that was not passed stays null)
+        if (e == hipSuccess && from[k]) e = hipMemcpyAsync(at[k], from[k], size[k], hipMemcpyHostToDevice, dst->stream);
+        bytes += from[k] ? size[k] : 0;
     }
+    const CarryTables dev{(const int32_t *)at[3], (const int32_t *)at[4], (const double *)at[0], (const double *)at[1], (const int32_t *)at[5],
+                          (const double *)at[2], (const int32_t *)at[6], (const int32_t *)at[7], host.mode};
     if (e != hipSuccess) rc = hip_fail(e, (who + ": " + what + "s").c_str(), __FILE__, __LINE__);
     // the destination's stream waits for what the source has enqueued (its last step, the division, z_mid)
     if (!rc) rc = batch_wait(dst, src);
     if (!rc && (e = hipEventRecord(dst->ev[0], dst->stream)) != hipSuccess) rc = hip_fail(e, "hipEventRecord", __FILE__, __LINE__);
     const int group[DOTS_N_ARRAYS] = {0, 0, 0, 0, 1, 1, 1, 2, 2, 3, 3, 3};      // recorver_scaled_solution (solver_socp.py:397-405)
-    for (int id = 0; id < DOTS_N_ARRAYS && !rc; ++id) rc = launch(id, factor[group[id]]);
+    for (int id = 0; id < DOTS_N_ARRAYS && !rc; ++id) rc = launch_carry(dst, src, id, dev, factor[group[id]], who.c_str());
     if (!rc && (e = hipEventRecord(dst->ev[1], dst->stream)) != hipSuccess) rc = hip_fail(e, "hipEventRecord", __FILE__, __LINE__);
     if (!rc) rc = batch_wait(src, dst);      // (whatever the source does next -- its release included -- comes after the reads)
     e = hipStreamSynchronize(dst->stream);
@@ -1513,10 +1543,9 @@ static int carry_state(const std::string &who, const char *what, dots_ctx *dst, 
     return 0;
 }
 
-}  // extern "C++"
-
 int dots_prolong_time(dots_ctx *dst, dots_ctx *src, const dots_prolong_desc *desc) {
-    int rc = carry_guard("prolong_time", dst, src, desc);
+    const char *who = "prolong_time";
+    int rc = carry_guard(who, dst, src, desc);
     if (rc) return rc;
     const Dev &dd = dst->d, &ds = src->d;
     if (dd.V != ds.V || dd.F != ds.F) {
@@ -1526,34 +1555,9 @@ int dots_prolong_time(dots_ctx *dst, dots_ctx *src, const dots_prolong_desc *des
         return DOTS_ERR_ARGUMENT;
     }
     if (!desc->node_j || !desc->node_w || !desc->interval_j || !desc->interval_w) { set_error("prolong_time: null table"); return DOTS_ERR_ARGUMENT; }
-    // every table entry names two source time points of the row it reads; every map entry a row of the source
-    const int nn = dd.T + 1, ni = dd.T;
-    for (int t = 0; t < nn + ni; ++t) {
-        const bool node = t < nn;
-        const int j = node ? desc->node_j[t] : desc->interval_j[t - nn];
-        const double w = node ? desc->node_w[t] : desc->interval_w[t - nn];
-        const int top = std::max((node ? ds.T + 1 : ds.T) - 2, 0);
-        if (j < 0 || j > top || !(w >= 0.0 && w <= 1.0)) {
-            char buf[200];
-            snprintf(buf, sizeof buf, "prolong_time: %s table entry %d (j = %d, w = %g) out of range (0 <= j <= %d, 0 <= w <= 1)", node ? "node" : "interval",
-                     node ? t : t - nn, j, w, top);
-            set_error(buf);
-            return DOTS_ERR_ARGUMENT;
-        }
-    }
-    for (int pass = 0; pass < 2; ++pass) {
-        const int32_t *m = pass ? desc->fmap : desc->vmap;
-        const int n = pass ? dd.F : dd.V;
-        for (int i = 0; m && i < n; ++i)
-            if (m[i] < 0 || m[i] >= n) { set_error(pass ? "prolong_time: fmap entry out of range" : "prolong_time: vmap entry out of range"); return DOTS_ERR_ARGUMENT; }
-    }
-    const size_t nv = desc->vmap ? (size_t)dd.V : 0, nf = desc->fmap ? (size_t)dd.F : 0;
-    CarryTable tab[] = {{desc->node_w, sizeof(double) * (size_t)nn}, {desc->interval_w, sizeof(double) * (size_t)ni}, {desc->node_j, sizeof(int32_t) * (size_t)nn},
-                        {desc->interval_j, sizeof(int32_t) * (size_t)ni}, {desc->vmap, sizeof(int32_t) * nv}, {desc->fmap, sizeof(int32_t) * nf}};
-    return carry_state("prolong_time", "table", dst, src, desc->factor, desc->ms, tab, [&](int id, double f) {
-        const int i = (array_kind(id) == 0 || array_kind(id) == 2) ? 0 : 1;      // the node tables, or the interval tables
-        return launch_prolong(dst, src, id, tab[2 + i].at<int>(), tab[i].at<double>(), tab[4].at<int>(), tab[5].at<int>(), f);
-    });
+    const CarryTables t{desc->node_j, desc->interval_j, desc->node_w, desc->interval_w, desc->vmap, nullptr, desc->fmap, nullptr, CARRY_SAME};
+    if ((rc = check_time_tables(who, t, dd, ds)) || (rc = check_space_tables(who, "vmap", "fmap", t, dd, ds))) return rc;
+    return carry_state(who, "table", dst, src, desc->factor, desc->ms, t);
 }
 
 int dots_prolong_space(dots_ctx *dst, dots_ctx *src, const dots_prolong_space_desc *desc) {
@@ -1562,16 +1566,9 @@ int dots_prolong_space(dots_ctx *dst, dots_ctx *src, const dots_prolong_space_de
     if (rc) return rc;
     const Dev &dd = dst->d, &ds = src->d;
     if ((rc = carry_space_shapes(who, "row map", dd, ds, !desc->vmap || !desc->fmap, desc->n_vertices, desc->n_triangles))) return rc;
-    // every map entry names a row of the source
-    const size_t nv = 2 * (size_t)dd.V, nf = (size_t)dd.F;
-    for (size_t i = 0; i < nv; ++i)
-        if (desc->vmap[i] < 0 || desc->vmap[i] >= ds.V) { set_error("prolong_space: vmap entry out of range"); return DOTS_ERR_ARGUMENT; }
-    for (size_t i = 0; i < nf; ++i)
-        if (desc->fmap[i] < 0 || desc->fmap[i] >= ds.F) { set_error("prolong_space: fmap entry out of range"); return DOTS_ERR_ARGUMENT; }
-    CarryTable tab[] = {{desc->vmap, sizeof(int32_t) * nv}, {desc->fmap, sizeof(int32_t) * nf}};
-    return carry_state(who, "row map", dst, src, desc->factor, desc->ms, tab, [&](int id, double f) {      // (4: siblings share source rows)
-        return launch_carry_space(dst, src, id, tab[0].at<int>(), nullptr, tab[1].at<int>(), nullptr, 4, f, who);
-    });
+    const CarryTables t{nullptr, nullptr, nullptr, nullptr, desc->vmap, nullptr, desc->fmap, nullptr, CARRY_NESTED};
+    if ((rc = check_space_tables(who, "vmap", "fmap", t, dd, ds))) return rc;
+    return carry_state(who, "row map", dst, src, desc->factor, desc->ms, t);
 }
 
 int dots_transfer_space(dots_ctx *dst, dots_ctx *src, const dots_transfer_space_desc *desc) {
@@ -1580,20 +1577,9 @@ int dots_transfer_space(dots_ctx *dst, dots_ctx *src, const dots_transfer_space_
     if (rc) return rc;
     const Dev &dd = dst->d, &ds = src->d;
     if ((rc = carry_space_shapes(who, "table", dd, ds, !desc->vsrc || !desc->vw || !desc->fsrc || !desc->csrc, desc->n_vertices, desc->n_triangles))) return rc;
-    // every index names a row / a corner of the source; every weight is a finite number >= 0
-    const size_t nv = 3 * (size_t)dd.V, nf = (size_t)dd.F;
-    for (size_t i = 0; i < nv; ++i) {
-        if (desc->vsrc[i] < 0 || desc->vsrc[i] >= ds.V) { set_error("transfer_space: vsrc entry out of range"); return DOTS_ERR_ARGUMENT; }
-        if (!(desc->vw[i] >= 0.0 && std::isfinite(desc->vw[i]))) { set_error("transfer_space: a weight that is negative or not finite"); return DOTS_ERR_ARGUMENT; }
-    }
-    for (size_t i = 0; i < nf; ++i)
-        if (desc->fsrc[i] < 0 || desc->fsrc[i] >= ds.F) { set_error("transfer_space: fsrc entry out of range"); return DOTS_ERR_ARGUMENT; }
-    for (size_t i = 0; i < 3 * nf; ++i)
-        if (desc->csrc[i] < 0 || desc->csrc[i] > 2) { set_error("transfer_space: csrc entry outside 0 .. 2"); return DOTS_ERR_ARGUMENT; }
-    CarryTable tab[] = {{desc->vw, sizeof(double) * nv}, {desc->vsrc, sizeof(int32_t) * nv}, {desc->fsrc, sizeof(int32_t) * nf}, {desc->csrc, sizeof(int32_t) * 3 * nf}};
-    return carry_state(who, "table", dst, src, desc->factor, desc->ms, tab, [&](int id, double f) {
-        return launch_carry_space(dst, src, id, tab[1].at<int>(), tab[0].at<double>(), tab[2].at<int>(), tab[3].at<int>(), 1, f, who);
-    });
+    const CarryTables t{nullptr, nullptr, nullptr, nullptr, desc->vsrc, desc->vw, desc->fsrc, desc->csrc, CARRY_LOCATED};
+    if ((rc = check_space_tables(who, "vsrc", "fsrc", t, dd, ds))) return rc;
+    return carry_state(who, "table", dst, src, desc->factor, desc->ms, t);
 }
 
 int dots_carry_spacetime(dots_ctx *dst, dots_ctx *src, const dots_carry_spacetime_desc *desc) {
@@ -1614,38 +1600,10 @@ int dots_carry_spacetime(dots_ctx *dst, dots_ctx *src, const dots_carry_spacetim
         set_error(buf);
         return DOTS_ERR_ARGUMENT;
     }
-    // every time-table entry names two source time points of the row it reads (as dots_prolong_time checks them)
-    const int nn = dd.T + 1, ni = dd.T;
-    for (int t = 0; t < nn + ni; ++t) {
-        const bool node = t < nn;
-        const int j = node ? desc->node_j[t] : desc->interval_j[t - nn];
-        const double w = node ? desc->node_w[t] : desc->interval_w[t - nn];
-        const int top = std::max((node ? ds.T + 1 : ds.T) - 2, 0);
-        if (j < 0 || j > top || !(w >= 0.0 && w <= 1.0)) {
-            snprintf(buf, sizeof buf, "carry_spacetime: %s table entry %d (j = %d, w = %g) out of range (0 <= j <= %d, 0 <= w <= 1)", node ? "node" : "interval",
-                     node ? t : t - nn, j, w, top);
-            set_error(buf);
-            return DOTS_ERR_ARGUMENT;
-        }
-    }
-    // every index names a row / a corner of the source; every weight is a finite number >= 0 (as the carriers in space check them)
-    const size_t per = desc->vw ? 3 : 2, nv = per * (size_t)dd.V, nf = (size_t)dd.F;
-    for (size_t i = 0; i < nv; ++i) {
-        if (desc->vsrc[i] < 0 || desc->vsrc[i] >= ds.V) { set_error("carry_spacetime: vsrc entry out of range"); return DOTS_ERR_ARGUMENT; }
-        if (desc->vw && !(desc->vw[i] >= 0.0 && std::isfinite(desc->vw[i]))) { set_error("carry_spacetime: a weight that is negative or not finite"); return DOTS_ERR_ARGUMENT; }
-    }
-    for (size_t i = 0; i < nf; ++i)
-        if (desc->fsrc[i] < 0 || desc->fsrc[i] >= ds.F) { set_error("carry_spacetime: fsrc entry out of range"); return DOTS_ERR_ARGUMENT; }
-    for (size_t i = 0; desc->csrc && i < 3 * nf; ++i)
-        if (desc->csrc[i] < 0 || desc->csrc[i] > 2) { set_error("carry_spacetime: csrc entry outside 0 .. 2"); return DOTS_ERR_ARGUMENT; }
-    CarryTable tab[] = {{desc->node_w, sizeof(double) * (size_t)nn}, {desc->interval_w, sizeof(double) * (size_t)ni}, {desc->vw, desc->vw ? sizeof(double) * nv : 0},
-                        {desc->node_j, sizeof(int32_t) * (size_t)nn}, {desc->interval_j, sizeof(int32_t) * (size_t)ni}, {desc->vsrc, sizeof(int32_t) * nv},
-                        {desc->fsrc, sizeof(int32_t) * nf}, {desc->csrc, desc->csrc ? sizeof(int32_t) * 3 * nf : 0}};
-    return carry_state(who, "table", dst, src, desc->factor, desc->ms, tab, [&](int id, double f) {
-        const int i = (array_kind(id) == 0 || array_kind(id) == 2) ? 0 : 1;      // the node tables, or the interval tables
-        return launch_carry_spacetime(dst, src, id, tab[3 + i].at<int>(), tab[i].at<double>(), tab[5].at<int>(), tab[2].at<double>(), tab[6].at<int>(),
-                                      tab[7].at<int>(), f);
-    });
+    const CarryTables t{desc->node_j, desc->interval_j, desc->node_w, desc->interval_w, desc->vsrc, desc->vw, desc->fsrc, desc->csrc,
+                        desc->vw ? CARRY_LOCATED : CARRY_NESTED};
+    if ((rc = check_time_tables(who, t, dd, ds)) || (rc = check_space_tables(who, "vsrc", "fsrc", t, dd, ds))) return rc;
+    return carry_state(who, "table", dst, src, desc->factor, desc->ms, t);
 }
 
 // ---- dots_readout ---------------------------------------------------------------------------------------------------------

@@ -350,12 +350,19 @@ int launch_scale_z(Ctx *c, double z_mul, double beta_mul, double sz_new);
 int launch_scale_array(Ctx *c, int array_id, double factor);
 int launch_to_device_layout(Ctx *c, int array_id, const double *staged);
 int launch_from_device_layout(Ctx *c, int array_id, double *staged);
-// array `array_id` of dst = the one of src interpolated in time (device tables jt / wt of that array's grid, row maps or null), on dst's stream
-int launch_prolong(Ctx *dst, Ctx *src, int array_id, const int *jt, const double *wt, const int *vmap, const int *fmap, double factor);
-int launch_carry_space(Ctx *dst, Ctx *src, int array_id, const int *vsrc, const double *vw, const int *fsrc, const int *csrc, int group,
-                       double factor, const char *who);
-int launch_carry_spacetime(Ctx *dst, Ctx *src, int array_id, const int *jt, const double *wt, const int *vsrc, const double *vw, const int *fsrc,
-                           const int *csrc, double factor);
+// The tables of a state carry (kernels_carry.hip), the caller's or their copies on the device.  mode: how a row is formed in space.
+enum { CARRY_NESTED = 0, CARRY_LOCATED = 1, CARRY_SAME = 2 };
+struct CarryTables {
+    const int32_t *node_j, *interval_j;      // [T + 1], [T] source time point of every destination time point; null: one time grid
+    const double *node_w, *interval_w;       // weight of source point j + 1
+    const int32_t *vsrc;                     // [V][2] nested, [V][3] located, [V] or null same: source vertex rows
+    const double *vw;                        // [V][3] located: weights
+    const int32_t *fsrc;                     // [F] source triangle; same: or null
+    const int32_t *csrc;                     // [F][3] source corner of every corner, or null: the same corner
+    int mode;
+};
+// array `array_id` of dst = the one of src carried over with the device tables t, times factor, on dst's stream
+int launch_carry(Ctx *dst, Ctx *src, int array_id, const CarryTables &t, double factor, const char *who);
 int launch_operator(Ctx *c, int op, double scale, const double *in_staged, double *out_staged);
 int launch_calibration(Ctx *c, double *bytes_each_way);
 int cg_solve(Ctx *c, dots_step_stats *stats, bool defer_inverse = false);   // defer_inverse: phi is produced by the caller (soc_takes_inverse)

@@ -1409,391 +1409,6 @@ int launch_from_device_layout(Ctx *c, int id, double *staged) {
 }
 
 // ------------------------------------------------------------------------------------------
-// time prolongation (dots_prolong_time): one state array of a context on the time grid of another, device layout to device layout
-// ------------------------------------------------------------------------------------------
-// A destination row is formed from ONE source row (the same vertex / triangle row in the source's numbering): time point t takes
-// (1 - w[t]) * (f * a[j[t]]) + w[t] * (f * a[j[t] + 1]) -- the operations of cascade.prolong_time on the recovered solution, in that
-// order (the build has -ffp-contract=off), so that the result is what an upload of the host's interpolation leaves, bit for bit.
-// A workgroup stages the tables once, then walks passes of R rows: the source rows go through LDS (read once, non-temporal: they
-// are never read again), a lane forms two neighbouring destination columns and stores them as one 16-byte word.  Corner arrays
-// hold interval i of half s in column i + s on both sides: interpolated along the interval index, placed at t + s, the slots whose
-// interval does not exist and the padding columns written as zero (as k_convert writes them).
-struct ProlongArgs {
-    const double *src;
-    double *dst;
-    const int *jt;           // [nd] source time point of every destination time point
-    const double *wt;        // [nd] weight of source point j + 1
-    const int *map;          // destination vertex / triangle -> the source's, or null (same numbering)
-    int64_t rows;            // destination rows
-    int rpe;                 // rows per vertex / triangle: 1, 3 (B, E) or 18 (corner arrays)
-    int corner;              // 1: row = ((f * 3 + k) * 2 + s) * 3 + c, column = interval + s
-    int nd, ns;              // destination / source time points of this array's grid
-    int sh_d, sh_s;          // log2 of the destination / source pitch
-    int R;                   // rows per pass
-    double f;
-};
-constexpr int PROLONG_XS = 4096, PROLONG_RMAX = 64, PROLONG_NT = 1024;      // doubles of source rows per pass, rows per pass, table entries
-
-__global__ __launch_bounds__(BLOCK) void k_prolong(ProlongArgs a) {
-    __shared__ __attribute__((aligned(16))) double xs[PROLONG_XS + 2 * PROLONG_RMAX];
-    __shared__ double ws[PROLONG_NT];
-    __shared__ int js[PROLONG_NT];
-    const int tid = threadIdx.x;
-    const int TPs = 1 << a.sh_s, SP = TPs + 2;      // (rows two columns apart in LDS: lane groups of neighbouring rows read other banks)
-    const int hs = a.sh_s - 1, hd = a.sh_d - 1;     // log2 of the column pairs per source / destination row
-    for (int t = tid; t < a.nd; t += BLOCK) {
-        js[t] = a.jt[t];
-        ws[t] = a.wt[t];
-    }
-    const int64_t n_pass = (a.rows + a.R - 1) / a.R;
-    for (int64_t pass = blockIdx.x; pass < n_pass; pass += gridDim.x) {
-        const int64_t r0 = pass * a.R;
-        __syncthreads();      // the tables are staged / the previous pass has read its rows
-        for (int e = tid; e < (a.R << hs); e += BLOCK) {
-            const int rr = e >> hs, p = e & ((1 << hs) - 1);
-            const int64_t r = r0 + rr;
-            if (r >= a.rows) continue;
-            const int64_t ent = r / a.rpe;
-            const int64_t sr = (a.map ? (int64_t)a.map[ent] : ent) * a.rpe + (r - ent * a.rpe);
-            st2(xs + rr * SP + 2 * p, ld2_nt(a.src + (sr << a.sh_s) + 2 * p));
-        }
-        __syncthreads();
-        for (int e = tid; e < (a.R << hd); e += BLOCK) {
-            const int rr = e >> hd, p = e & ((1 << hd) - 1);
-            const int64_t r = r0 + rr;
-            if (r >= a.rows) continue;
-            const int s = a.corner ? (int)((r / 3) & 1) : 0;
-            const double *x = xs + rr * SP + s;
-            D2 y;
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const int t = 2 * p + q - s;      // time point of this column
-                double v = 0.0;
-                if (t >= 0 && t < a.nd) {
-                    const int j = js[t], j1 = min(j + 1, a.ns - 1);
-                    const double w = ws[t];
-                    v = (1.0 - w) * (a.f * x[j]) + w * (a.f * x[j1]);
-                }
-                y.v[q] = v;
-            }
-            st2(a.dst + (r << a.sh_d) + 2 * p, y);
-        }
-    }
-}
-
-int launch_prolong(Ctx *dst, Ctx *src, int id, const int *jt, const double *wt, const int *vmap, const int *fmap, double f) {
-    const Dev &dd = dst->d, &ds = src->d;
-    const int kind = array_kind(id);
-    ProlongArgs a{};
-    a.src = src->arr(id);
-    a.dst = dst->arr(id);
-    a.jt = jt;
-    a.wt = wt;
-    a.map = kind <= 1 ? vmap : fmap;
-    a.rpe = kind <= 1 ? 1 : (kind == 2 ? 3 : 18);
-    a.rows = (int64_t)a.rpe * (kind <= 1 ? dd.V : dd.F);
-    a.corner = kind == 3;
-    const int node = kind == 0 || kind == 2;
-    a.nd = dd.T + node;
-    a.ns = ds.T + node;
-    a.sh_d = dd.tp_shift;
-    a.sh_s = ds.tp_shift;
-    a.f = f;
-    a.R = std::max(1, std::min(std::min(PROLONG_RMAX, (4 * BLOCK) >> (a.sh_d - 1)), PROLONG_XS >> a.sh_s));
-    if (a.nd > PROLONG_NT || (1 << a.sh_s) > PROLONG_XS || a.sh_d < 1 || a.sh_s < 1) { set_error("prolong: time pitch out of range"); return DOTS_ERR_STATE; }
-    const int64_t n_pass = (a.rows + a.R - 1) / a.R;
-    hipLaunchKernelGGL(k_prolong, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(n_pass, 1024))), dim3(BLOCK), 0, dst->stream, a);
-    DOTS_HIP(hipGetLastError());
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------
-// state carry in space (dots_prolong_space, dots_transfer_space): one state array of a context on another mesh, same time grid
-// ------------------------------------------------------------------------------------------
-// Both contexts have one time pitch, so a destination row is formed from whole source rows.  A triangle row is f times the row of the
-// same component of its source triangle, a corner row f times the row of its source corner (same interval end and component): the
-// corner csrc names, or the same corner where csrc is null (a child triangle keeps its parent's corner order).  A vertex row is one
-// of two formulas, chosen at compile time because they differ in the sign of zero and in the subnormal range:
-//   nested  (a mesh to its refinement): f * a where the two source rows are one (a kept vertex), else (f * a + f * b) * 0.5;
-//   located (another triangulation):    (w0 * (f * a0) + w1 * (f * a1)) + w2 * (f * a2), no special case for a weight of 0 or 1.
-// These are the operations of cascade.prolong_space / cascade.transfer_space on the recovered solution, in that order
-// (-ffp-contract=off), so that the result is what an upload of the host's transfer leaves, bit for bit.  A lane forms two neighbouring
-// columns (16-byte words in, one out); a row's indices and weights are read once per row; a row wider than 256 columns is walked in
-// chunks of 256.  Columns outside the array's time points (padding, and the slot of a corner row whose interval does not exist) are
-// written as zero, as k_convert writes them.  A workgroup takes runs of consecutive destination rows.  Nested, a run is a whole number
-// of groups of four vertices / triangles: the four children of a triangle, which read the same 3 or 18 source rows, are numbered
-// together by the subdivision (and stay close under a locality renumbering), so the source rows come from HBM once and from the cache
-// for the siblings.  Located, neighbouring destination vertices / triangles under a locality numbering lie in the same or in
-// neighbouring source triangles, so most of the 3 source rows per vertex row come from the cache.
-struct CarrySpaceArgs {
-    const double *src;
-    double *dst;
-    const int *vsrc;         // vertex rows: [entities][2] (nested) or [entities][3] (located) source vertex rows
-    const double *vw;        // located vertex rows: [entities][3] weights
-    const int *fsrc;         // triangle and corner rows: [entities] source triangle
-    const int *csrc;         // corner rows: [entities][3] source corner of every destination corner, or null: the same corner
-    int64_t rows;            // destination rows
-    int64_t run;             // rows per run
-    int sh;                  // log2 of the time pitch (both sides)
-    int n_valid;             // time points of the array: T + 1 (node arrays) or T
-    double f;
-};
-
-// RPE: rows per vertex / triangle: 1, 3 (B, E), 18 (corner arrays: row = ((f * 3 + k) * 2 + s) * 3 + c, column = interval + s);
-// LOCATED: the vertex formula (RPE = 1 only)
-template <int RPE, bool LOCATED = false>
-__global__ __launch_bounds__(BLOCK) void k_carry_space(CarrySpaceArgs a) {
-    const int tid = threadIdx.x;
-    const int hp = a.sh - 1;                      // log2 of the column pairs per row
-    const int hl = min(hp, 7);                    // log2 of the lanes per row: at most 128 pairs = 256 columns per chunk
-    const int rpp = BLOCK >> hl;                  // rows per pass
-    const int rr = tid >> hl, p0 = tid & ((1 << hl) - 1);
-    const int64_t n_runs = (a.rows + a.run - 1) / a.run;
-    for (int64_t run = blockIdx.x; run < n_runs; run += gridDim.x) {
-        const int64_t r_end = min(a.rows, (run + 1) * a.run);
-        for (int64_t r = run * a.run + rr; r < r_end; r += rpp) {
-            int64_t r0, r1 = 0, r2 = 0;             // source rows: one, or the 2 / 3 of a vertex row
-            double w0 = 0.0, w1 = 0.0, w2 = 0.0;
-            int s = 0;                              // interval end of a corner row: its columns are shifted by one
-            if (RPE == 1 && LOCATED) {
-                const int *v = a.vsrc + 3 * r;
-                const double *w = a.vw + 3 * r;
-                r0 = v[0], r1 = v[1], r2 = v[2];
-                w0 = w[0], w1 = w[1], w2 = w[2];
-            } else if (RPE == 1) {
-                r0 = a.vsrc[2 * r];
-                r1 = a.vsrc[2 * r + 1];
-            } else {
-                const int64_t ent = r / RPE;
-                const int sub = (int)(r - ent * RPE);
-                r0 = a.fsrc[ent];
-                if (RPE == 18) {      // sub = (k * 2 + s) * 3 + c
-                    const int k = sub / 6, rest = sub - 6 * k;
-                    s = rest / 3;
-                    r0 = (r0 * 3 + (a.csrc ? a.csrc[3 * ent + k] : k)) * 6 + rest;
-                } else {
-                    r0 = r0 * 3 + sub;
-                }
-            }
-            const double *x0 = a.src + (r0 << a.sh), *x1 = a.src + (r1 << a.sh), *x2 = a.src + (r2 << a.sh);
-            double *y = a.dst + (r << a.sh);
-            for (int p = p0; p < (1 << hp); p += 1 << hl) {
-                const D2 v0 = ld2(x0 + 2 * p);
-                D2 out;
-                if (RPE == 1 && LOCATED) {
-                    const D2 v1 = ld2(x1 + 2 * p), v2 = ld2(x2 + 2 * p);
-#pragma unroll
-                    for (int q = 0; q < 2; ++q) out.v[q] = (w0 * (a.f * v0.v[q]) + w1 * (a.f * v1.v[q])) + w2 * (a.f * v2.v[q]);
-                } else if (RPE == 1 && r0 != r1) {
-                    const D2 v1 = ld2(x1 + 2 * p);
-#pragma unroll
-                    for (int q = 0; q < 2; ++q) out.v[q] = (a.f * v0.v[q] + a.f * v1.v[q]) * 0.5;
-                } else {
-#pragma unroll
-                    for (int q = 0; q < 2; ++q) out.v[q] = a.f * v0.v[q];
-                }
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    const int t = 2 * p + q - s;
-                    if (t < 0 || t >= a.n_valid) out.v[q] = 0.0;
-                }
-                st2(y + 2 * p, out);
-            }
-        }
-    }
-}
-
-// vw null: the nested vertex formula (vsrc [V][2]), else the located one (vsrc, vw [V][3]); group: the vertices / triangles that share
-// source rows and stay in one run (4 siblings of a subdivision, or 1); who: the entry point, for the message
-int launch_carry_space(Ctx *dst, Ctx *src, int id, const int *vsrc, const double *vw, const int *fsrc, const int *csrc, int group, double f,
-                       const char *who) {
-    const Dev &dd = dst->d;
-    const int kind = array_kind(id);
-    CarrySpaceArgs a{};
-    a.src = src->arr(id);
-    a.dst = dst->arr(id);
-    a.vsrc = vsrc;
-    a.vw = vw;
-    a.fsrc = fsrc;
-    a.csrc = csrc;
-    const int rpe = kind <= 1 ? 1 : (kind == 2 ? 3 : 18);
-    a.rows = (int64_t)rpe * (kind <= 1 ? dd.V : dd.F);
-    a.sh = dd.tp_shift;
-    a.n_valid = dd.T + ((kind == 0 || kind == 2) ? 1 : 0);
-    a.f = f;
-    if (a.sh < 1 || dd.TP > TILE_ELEMS || a.sh != src->d.tp_shift) { set_error(std::string(who) + ": time pitch out of range"); return DOTS_ERR_STATE; }
-    // a run: whole groups of vertices / triangles, whole passes of the workgroup, about 32 KB of destination
-    const int rpp = BLOCK >> std::min(a.sh - 1, 7);
-    int64_t unit = (int64_t)group * rpe;
-    while (unit % rpp) unit *= 2;
-    const int64_t row_bytes = (int64_t)sizeof(double) << a.sh;
-    a.run = unit * std::max<int64_t>(1, (32768 + unit * row_bytes - 1) / (unit * row_bytes));
-    const int64_t n_runs = (a.rows + a.run - 1) / a.run;
-    const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(n_runs, 4096)));
-    if (rpe == 1 && vw) hipLaunchKernelGGL((k_carry_space<1, true>), grid, dim3(BLOCK), 0, dst->stream, a);
-    else if (rpe == 1) hipLaunchKernelGGL(k_carry_space<1>, grid, dim3(BLOCK), 0, dst->stream, a);
-    else if (rpe == 3) hipLaunchKernelGGL(k_carry_space<3>, grid, dim3(BLOCK), 0, dst->stream, a);
-    else hipLaunchKernelGGL(k_carry_space<18>, grid, dim3(BLOCK), 0, dst->stream, a);
-    DOTS_HIP(hipGetLastError());
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------
-// state carry in space and time at once (dots_carry_spacetime): one state array of a context on another mesh AND another time grid
-// ------------------------------------------------------------------------------------------
-// The composition of the two carriers above without the context in between: space first, then time (cascade.carry_spacetime).  A
-// workgroup stages the two time tables once, as k_prolong does, then walks passes of R destination rows in two phases.  Phase 1 forms
-// each row of the pass ON THE SOURCE'S TIME GRID with the row arithmetic and the formulas of k_carry_space (the recovery factor f
-// first; the nested and the located vertex formulas are separate instantiations, as there) from 16-byte loads at the source pitch, and
-// writes it into the LDS row k_prolong would have staged: what the space carrier would have left in a context on the destination's mesh
-// at the source's n_time never reaches memory.  Phase 2 is k_prolong's second loop on those rows without f (it was applied in phase
-// 1): (1 - w[t]) * x[j[t]] + w[t] * x[min(j[t] + 1, ns - 1)], two destination columns per lane, one 16-byte store; a corner row is read
-// at offset s and placed at t + s; every column outside the array's time points is written as zero.  Only columns j < ns of an LDS row
-// are read, so what phase 1 leaves in the source's padding columns is never used.  LDS rows are TPs + 2 doubles apart as in k_prolong:
-// an even number, so that phase 1's 16-byte writes stay aligned and neighbouring lanes write neighbouring words (no bank is hit twice),
-// and not a power of two, so that in phase 2 lane groups on neighbouring rows read other banks.
-struct CarrySpacetimeArgs {
-    const double *src;
-    double *dst;
-    const int *jt;           // [nd] source time point of every destination time point
-    const double *wt;        // [nd] weight of source point j + 1
-    const int *vsrc;         // vertex rows: [entities][2] (nested) or [entities][3] (located) source vertex rows
-    const double *vw;        // located vertex rows: [entities][3] weights
-    const int *fsrc;         // triangle and corner rows: [entities] source triangle
-    const int *csrc;         // corner rows: [entities][3] source corner of every destination corner, or null: the same corner
-    int64_t rows;            // destination rows
-    int nd, ns;              // destination / source time points of this array's grid
-    int sh_d, sh_s;          // log2 of the destination / source pitch
-    int R;                   // rows per pass
-    double f;
-};
-
-// RPE, LOCATED: as for k_carry_space
-template <int RPE, bool LOCATED = false>
-__global__ __launch_bounds__(BLOCK) void k_carry_spacetime(CarrySpacetimeArgs a) {
-    __shared__ __attribute__((aligned(16))) double xs[PROLONG_XS + 2 * PROLONG_RMAX];
-    __shared__ double ws[PROLONG_NT];
-    __shared__ int js[PROLONG_NT];
-    const int tid = threadIdx.x;
-    const int TPs = 1 << a.sh_s, SP = TPs + 2;
-    const int hs = a.sh_s - 1, hd = a.sh_d - 1;     // log2 of the column pairs per source / destination row
-    for (int t = tid; t < a.nd; t += BLOCK) {
-        js[t] = a.jt[t];
-        ws[t] = a.wt[t];
-    }
-    const int64_t n_pass = (a.rows + a.R - 1) / a.R;
-    for (int64_t pass = blockIdx.x; pass < n_pass; pass += gridDim.x) {
-        const int64_t base = pass * a.R;
-        __syncthreads();      // the tables are staged / the previous pass has read its rows
-        // phase 1: space, source rows -> LDS
-        for (int e = tid; e < (a.R << hs); e += BLOCK) {
-            const int rr = e >> hs, p = e & ((1 << hs) - 1);
-            const int64_t r = base + rr;
-            if (r >= a.rows) continue;
-            int64_t r0, r1 = 0, r2 = 0;             // source rows: one, or the 2 / 3 of a vertex row
-            double w0 = 0.0, w1 = 0.0, w2 = 0.0;
-            if (RPE == 1 && LOCATED) {
-                const int *v = a.vsrc + 3 * r;
-                const double *w = a.vw + 3 * r;
-                r0 = v[0], r1 = v[1], r2 = v[2];
-                w0 = w[0], w1 = w[1], w2 = w[2];
-            } else if (RPE == 1) {
-                r0 = a.vsrc[2 * r];
-                r1 = a.vsrc[2 * r + 1];
-            } else {
-                const int64_t ent = r / RPE;
-                const int sub = (int)(r - ent * RPE);
-                r0 = a.fsrc[ent];
-                if (RPE == 18) {      // sub = (k * 2 + s) * 3 + c
-                    const int k = sub / 6, rest = sub - 6 * k;
-                    r0 = (r0 * 3 + (a.csrc ? a.csrc[3 * ent + k] : k)) * 6 + rest;
-                } else {
-                    r0 = r0 * 3 + sub;
-                }
-            }
-            const D2 v0 = ld2(a.src + (r0 << a.sh_s) + 2 * p);
-            D2 out;
-            if (RPE == 1 && LOCATED) {
-                const D2 v1 = ld2(a.src + (r1 << a.sh_s) + 2 * p), v2 = ld2(a.src + (r2 << a.sh_s) + 2 * p);
-#pragma unroll
-                for (int q = 0; q < 2; ++q) out.v[q] = (w0 * (a.f * v0.v[q]) + w1 * (a.f * v1.v[q])) + w2 * (a.f * v2.v[q]);
-            } else if (RPE == 1 && r0 != r1) {
-                const D2 v1 = ld2(a.src + (r1 << a.sh_s) + 2 * p);
-#pragma unroll
-                for (int q = 0; q < 2; ++q) out.v[q] = (a.f * v0.v[q] + a.f * v1.v[q]) * 0.5;
-            } else {
-#pragma unroll
-                for (int q = 0; q < 2; ++q) out.v[q] = a.f * v0.v[q];
-            }
-            st2(xs + rr * SP + 2 * p, out);
-        }
-        __syncthreads();
-        // phase 2: time, LDS -> destination rows
-        for (int e = tid; e < (a.R << hd); e += BLOCK) {
-            const int rr = e >> hd, p = e & ((1 << hd) - 1);
-            const int64_t r = base + rr;
-            if (r >= a.rows) continue;
-            const int s = RPE == 18 ? (int)((r / 3) & 1) : 0;
-            const double *x = xs + rr * SP + s;
-            D2 y;
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const int t = 2 * p + q - s;      // time point of this column
-                double v = 0.0;
-                if (t >= 0 && t < a.nd) {
-                    const int j = js[t], j1 = min(j + 1, a.ns - 1);
-                    const double w = ws[t];
-                    v = (1.0 - w) * x[j] + w * x[j1];
-                }
-                y.v[q] = v;
-            }
-            st2(a.dst + (r << a.sh_d) + 2 * p, y);
-        }
-    }
-}
-
-// vw null: the nested vertex formula (vsrc [V][2]), else the located one (vsrc, vw [V][3])
-int launch_carry_spacetime(Ctx *dst, Ctx *src, int id, const int *jt, const double *wt, const int *vsrc, const double *vw, const int *fsrc,
-                           const int *csrc, double f) {
-    const Dev &dd = dst->d, &ds = src->d;
-    const int kind = array_kind(id);
-    CarrySpacetimeArgs a{};
-    a.src = src->arr(id);
-    a.dst = dst->arr(id);
-    a.jt = jt;
-    a.wt = wt;
-    a.vsrc = vsrc;
-    a.vw = vw;
-    a.fsrc = fsrc;
-    a.csrc = csrc;
-    const int rpe = kind <= 1 ? 1 : (kind == 2 ? 3 : 18);
-    a.rows = (int64_t)rpe * (kind <= 1 ? dd.V : dd.F);
-    const int node = kind == 0 || kind == 2;
-    a.nd = dd.T + node;
-    a.ns = ds.T + node;
-    a.sh_d = dd.tp_shift;
-    a.sh_s = ds.tp_shift;
-    a.f = f;
-    if (a.nd > PROLONG_NT || a.sh_s < 1 || a.sh_s > 12 || a.sh_d < 1 || a.sh_d > 12 || (1 << a.sh_s) > PROLONG_XS) {
-        set_error("carry_spacetime: time pitch out of range");
-        return DOTS_ERR_STATE;
-    }
-    a.R = std::max(1, std::min(std::min(PROLONG_RMAX, (4 * BLOCK) >> (a.sh_d - 1)), PROLONG_XS >> a.sh_s));      // (k_prolong's)
-    // nested: the four children of a triangle (and the vertices the subdivision numbers with them) read the same source rows: a pass
-    // takes whole groups of four where R holds one (the corner arrays' 72 rows never fit: their passes stay at R)
-    const int unit = 4 * rpe;
-    if (!vw && a.R >= unit) a.R -= a.R % unit;
-    const int64_t n_pass = (a.rows + a.R - 1) / a.R;
-    const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(n_pass, 1024)));
-    if (rpe == 1 && vw) hipLaunchKernelGGL((k_carry_spacetime<1, true>), grid, dim3(BLOCK), 0, dst->stream, a);
-    else if (rpe == 1) hipLaunchKernelGGL(k_carry_spacetime<1>, grid, dim3(BLOCK), 0, dst->stream, a);
-    else if (rpe == 3) hipLaunchKernelGGL(k_carry_spacetime<3>, grid, dim3(BLOCK), 0, dst->stream, a);
-    else hipLaunchKernelGGL(k_carry_spacetime<18>, grid, dim3(BLOCK), 0, dst->stream, a);
-    DOTS_HIP(hipGetLastError());
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------
 // standalone operators (rows a4-a6): same index arithmetic as the fused kernels, exposed so each
 // reference function has a one-to-one parity test.  in/out are device-layout scratch arrays.
 // ------------------------------------------------------------------------------------------

@@ -261,6 +261,37 @@ class DeviceProblem:
     def _state_pitch(self):
         return max(8, 1 << int(np.ceil(np.log2(self.T + 1))))
 
+    def _time_tables(self, src, d):
+        """The time tables of ``d`` from ``src``'s grid to this one's; returns the arrays ``d`` points to."""
+        from . import cascade
+
+        nj, nw = cascade.time_weights(src.T, self.T, node=True)
+        ij, iw = cascade.time_weights(src.T, self.T, node=False)
+        d.node_j, d.node_w, d.interval_j, d.interval_w = _ptr(nj, C.c_int32), _ptr(nw, C.c_double), _ptr(ij, C.c_int32), _ptr(iw, C.c_double)
+        return nj, nw, ij, iw
+
+    def _space_tables(self, who, src, parents, transfer, size_first=True):
+        """``(vsrc, vw, fsrc, csrc)`` in the two device numberings from ``parents`` (``vw`` and ``csrc`` None) or from ``transfer``.
+        ``who``: what the message says where the map is not one to this context's mesh; ``size_first``: before the tables are made."""
+        from . import cascade
+
+        perms = (self.plan.perm_vert, self.plan.perm_tri, src.plan.perm_vert, src.plan.perm_tri)
+        if parents is not None:
+            v, t = cascade.check_parents(parents, n_vertices=src.V, n_triangles=src.F)
+        else:
+            v, _, t, _ = cascade.check_transfer(transfer, n_vertices=src.V, n_triangles=src.F)
+        wrong = None if (v.shape[0], t.shape[0]) == (self.V, self.F) else f"{who} with V, F = {v.shape[0]}, {t.shape[0]}, this one has {self.V}, {self.F}"
+        if wrong and size_first:
+            raise ValueError(wrong)
+        tables = cascade.transfer_row_maps(transfer, *perms) if parents is None else cascade.space_row_maps(parents, src.V, src.F, *perms)
+        if wrong:
+            raise ValueError(wrong)
+        return tables if parents is None else (tables[0], None, tables[1], None)
+
+    def _state_rows(self, per_vertex=1, per_triangle=1):
+        """Rows of the twelve state arrays: 8 vertex arrays of V rows, 2 x 3 F triangle rows, 2 x 18 F corner rows."""
+        return 8 * per_vertex * self.V + (2 * 3 + 2 * 18) * per_triangle * self.F
+
     def prolong_from(self, src: "DeviceProblem", factors=(1.0, 1.0, 1.0, 1.0)):
         """Fill this context's twelve state arrays with those of ``src`` (the same mesh on the same device, another ``n_time``,
         possibly another device numbering) interpolated linearly in time on the device (dots_prolong_time; cascade.prolong_time is
@@ -271,14 +302,12 @@ class DeviceProblem:
         def describe():
             if (self.V, self.F) != (src.V, src.F):
                 raise ValueError(f"prolong_from: another mesh (V, F = {self.V}, {self.F}, the source's {src.V}, {src.F})")
-            nj, nw = cascade.time_weights(src.T, self.T, node=True)
-            ij, iw = cascade.time_weights(src.T, self.T, node=False)
+            d = _lib.ProlongDesc()
+            tables = self._time_tables(src, d)
             vmap = cascade.row_map(self.plan.perm_vert, src.plan.perm_vert, self.V)
             fmap = cascade.row_map(self.plan.perm_tri, src.plan.perm_tri, self.F)
-            d = _lib.ProlongDesc()
-            d.node_j, d.node_w, d.interval_j, d.interval_w = _ptr(nj, C.c_int32), _ptr(nw, C.c_double), _ptr(ij, C.c_int32), _ptr(iw, C.c_double)
             d.vmap, d.fmap = _ptr(vmap, C.c_int32), _ptr(fmap, C.c_int32)
-            return d, (nj, nw, ij, iw, vmap, fmap)
+            return d, (tables, vmap, fmap)
 
         return self._carry_from("prolong_from", src, "dots_prolong_time", describe, factors, same_grid=False)
 
@@ -287,19 +316,14 @@ class DeviceProblem:
         ``meshes.subdivide``) with the same ``n_time`` on the same device (dots_prolong_space; cascade.prolong_space is the
         specification).  ``factors``: as for ``prolong_from``.  Returns the milliseconds of the launches; ``self.prolong_bytes``: the
         bytes the transfer reads and writes when every source row is read once."""
-        from . import cascade
-
         def describe():
-            vp, tp = cascade.check_parents(parents, n_vertices=src.V, n_triangles=src.F)
-            if (vp.shape[0], tp.shape[0]) != (self.V, self.F):
-                raise ValueError(f"prolong_space_from: parents of a mesh with V, F = {vp.shape[0]}, {tp.shape[0]}, this one has {self.V}, {self.F}")
-            vmap, fmap = cascade.space_row_maps(parents, src.V, src.F, self.plan.perm_vert, self.plan.perm_tri, src.plan.perm_vert, src.plan.perm_tri)
+            vmap, _, fmap, _ = self._space_tables("prolong_space_from: parents of a mesh", src, parents, None)
             d = _lib.ProlongSpaceDesc()
             d.vmap, d.fmap, d.n_vertices, d.n_triangles = _ptr(vmap, C.c_int32), _ptr(fmap, C.c_int32), self.V, self.F
             return d, (vmap, fmap)
 
         ms = self._carry_from("prolong_space_from", src, "dots_prolong_space", describe, factors, same_grid=True)
-        self.prolong_bytes = 8 * self._state_pitch() * (8 * (self.V + src.V) + (2 * 3 + 2 * 18) * (self.F + src.F))
+        self.prolong_bytes = 8 * self._state_pitch() * (self._state_rows() + src._state_rows())
         return ms
 
     def transfer_space_from(self, src: "DeviceProblem", transfer, factors=(1.0, 1.0, 1.0, 1.0)):
@@ -310,20 +334,15 @@ class DeviceProblem:
         triangle rows, 2 x 18 F corner rows, ``pitch`` doubles each), plus three source rows per vertex row, plus one source row per
         triangle / corner row: ``8 * pitch * (8 * V * (1 + 3) + 42 * F * (1 + 1))`` -- every source read counted, also those that
         come from the cache."""
-        from . import cascade
-
         def describe():
-            vs, _, ts, _ = cascade.check_transfer(transfer, n_vertices=src.V, n_triangles=src.F)
-            if (vs.shape[0], ts.shape[0]) != (self.V, self.F):
-                raise ValueError(f"transfer_space_from: a transfer to a mesh with V, F = {vs.shape[0]}, {ts.shape[0]}, this one has {self.V}, {self.F}")
-            vsrc, vw, fsrc, csrc = cascade.transfer_row_maps(transfer, self.plan.perm_vert, self.plan.perm_tri, src.plan.perm_vert, src.plan.perm_tri)
+            tables = self._space_tables("transfer_space_from: a transfer to a mesh", src, None, transfer)
             d = _lib.TransferSpaceDesc()
-            d.vsrc, d.vw, d.fsrc, d.csrc = _ptr(vsrc, C.c_int32), _ptr(vw, C.c_double), _ptr(fsrc, C.c_int32), _ptr(csrc, C.c_int32)
+            d.vsrc, d.vw, d.fsrc, d.csrc = (_ptr(t, c) for t, c in zip(tables, (C.c_int32, C.c_double, C.c_int32, C.c_int32)))
             d.n_vertices, d.n_triangles = self.V, self.F
-            return d, (vsrc, vw, fsrc, csrc)
+            return d, tables
 
         ms = self._carry_from("transfer_space_from", src, "dots_transfer_space", describe, factors, same_grid=True)
-        self.prolong_bytes = 8 * self._state_pitch() * (8 * 4 * self.V + (2 * 3 + 2 * 18) * 2 * self.F)
+        self.prolong_bytes = 8 * self._state_pitch() * self._state_rows(1 + 3, 1 + 1)
         return ms
 
     def carry_spacetime_from(self, src: "DeviceProblem", factors=(1.0, 1.0, 1.0, 1.0), parents=None, transfer=None):
@@ -341,29 +360,16 @@ class DeviceProblem:
             if self.T == src.T:
                 raise ValueError(f"carry_spacetime_from: both contexts have n_time = {self.T}: on one time grid prolong_space_from / "
                                  "transfer_space_from are the definition")
-            if parents is not None:
-                vp, tp = cascade.check_parents(parents, n_vertices=src.V, n_triangles=src.F)
-                size = (vp.shape[0], tp.shape[0])
-                vsrc, fsrc = cascade.space_row_maps(parents, src.V, src.F, self.plan.perm_vert, self.plan.perm_tri, src.plan.perm_vert, src.plan.perm_tri)
-                vw = csrc = None
-            else:
-                vs, _, ts, _ = cascade.check_transfer(transfer, n_vertices=src.V, n_triangles=src.F)
-                size = (vs.shape[0], ts.shape[0])
-                vsrc, vw, fsrc, csrc = cascade.transfer_row_maps(transfer, self.plan.perm_vert, self.plan.perm_tri, src.plan.perm_vert, src.plan.perm_tri)
-            if size != (self.V, self.F):
-                raise ValueError(f"carry_spacetime_from: a map to a mesh with V, F = {size[0]}, {size[1]}, this one has {self.V}, {self.F}")
-            nj, nw = cascade.time_weights(src.T, self.T, node=True)
-            ij, iw = cascade.time_weights(src.T, self.T, node=False)
+            space = self._space_tables("carry_spacetime_from: a map to a mesh", src, parents, transfer, size_first=False)
             d = _lib.CarrySpacetimeDesc()
-            d.node_j, d.node_w, d.interval_j, d.interval_w = _ptr(nj, C.c_int32), _ptr(nw, C.c_double), _ptr(ij, C.c_int32), _ptr(iw, C.c_double)
-            d.vsrc, d.vw, d.fsrc, d.csrc = _ptr(vsrc, C.c_int32), _ptr(vw, C.c_double), _ptr(fsrc, C.c_int32), _ptr(csrc, C.c_int32)
+            time = self._time_tables(src, d)
+            d.vsrc, d.vw, d.fsrc, d.csrc = (_ptr(t, c) for t, c in zip(space, (C.c_int32, C.c_double, C.c_int32, C.c_int32)))
             d.n_vertices, d.n_triangles = self.V, self.F
-            return d, (nj, nw, ij, iw, vsrc, vw, fsrc, csrc)
+            return d, (time, space)
 
         ms = self._carry_from("carry_spacetime_from", src, "dots_carry_spacetime", describe, factors, same_grid=False)
-        rows = 8 * self.V + (2 * 3 + 2 * 18) * self.F
-        src_rows = 8 * src.V + (2 * 3 + 2 * 18) * src.F if parents is not None else 8 * 3 * self.V + (2 * 3 + 2 * 18) * self.F
-        self.prolong_bytes = 8 * (self._state_pitch() * rows + src._state_pitch() * src_rows)
+        src_rows = src._state_rows() if parents is not None else self._state_rows(3, 1)
+        self.prolong_bytes = 8 * (self._state_pitch() * self._state_rows() + src._state_pitch() * src_rows)
         return ms
 
     # ---- the hot loop

@@ -111,122 +111,66 @@ def _end_points(geometry):
     return np.asarray(geometry["mu0"], dtype=np.float64), np.asarray(geometry["mu1"], dtype=np.float64)
 
 
-def solver_raw(n_time, geometry, readout="device", **kwargs):
-    """Solve the DOT problem with the GPU SOCP solver; solution on the time-staggered grid."""
-    solution_socp, run_history = solver_socp(n_time, geometry, read_out=_read_out_spec(readout, False, kwargs), **kwargs)
-    return _finish(solution_socp, geometry, None, None, readout, False), run_history
-
-
-solver_raw.__name__ = "dot_solver_socp"
-
-
 def _to_time_centered(solution_dot, mu0, mu1):
     mid = 0.5 * (solution_dot["mu"][:-1] + solution_dot["mu"][1:])
     solution_dot["mu"] = np.concatenate([mu0[None, :], mid, mu1[None, :]], axis=0)
 
 
-def solver(n_time, geometry, readout="device", **kwargs):
-    """``solver_raw`` with the density moved to the time-centred grid and mu0 / mu1 as end points."""
-    mu0, mu1 = _end_points(geometry)
-    solution_socp, run_history = solver_socp(n_time, geometry, read_out=_read_out_spec(readout, True, kwargs), **kwargs)
-    return _finish(solution_socp, geometry, mu0, mu1, readout, True), run_history
-
-
-solver.__name__ = "dot_solver_socp_center"
-
-
-def solver_raw_cascade(n_time, geometry, readout="device", **kwargs):
-    """``solver_raw`` through the time cascade (``solver_socp_cascade``: ``levels``, ``level_tol`` and the keywords of ``solver_socp``)."""
-    solution_socp, run_history = solver_socp_cascade(n_time, geometry, read_out=_read_out_spec(readout, False, kwargs), **kwargs)
-    return _finish(solution_socp, geometry, None, None, readout, False), run_history
-
-
-solver_raw_cascade.__name__ = "dot_solver_socp_cascade"
-
-
-def solver_cascade(n_time, geometry, readout="device", **kwargs):
-    """``solver`` through the time cascade: the density on the time-centred grid with mu0 / mu1 as end points."""
-    mu0, mu1 = _end_points(geometry)
-    solution_socp, run_history = solver_socp_cascade(n_time, geometry, read_out=_read_out_spec(readout, True, kwargs), **kwargs)
-    return _finish(solution_socp, geometry, mu0, mu1, readout, True), run_history
-
-
-solver_cascade.__name__ = "dot_solver_socp_cascade_center"
-
-
-def _finest(geometries, who="solver_socp_mesh_cascade"):
+def _finest(geometries, who):
     geometries = list(geometries)
     if not geometries:
         raise ValueError(f"{who}: at least two geometries")
     return geometries, geometries[-1]
 
 
-def solver_raw_mesh_cascade(n_time, geometries, readout="device", **kwargs):
-    """``solver_raw`` on the finest of ``geometries`` through the cascade in space (``solver_socp_mesh_cascade``: ``level_tol`` and the
-    keywords of ``solver_socp``)."""
-    geometries, fine = _finest(geometries)
-    solution_socp, run_history = solver_socp_mesh_cascade(n_time, geometries, read_out=_read_out_spec(readout, False, kwargs), **kwargs)
-    return _finish(solution_socp, fine, None, None, readout, False), run_history
+def _plug_in(driver, name, centred, finest=False, who=None, doc=None):
+    """The plug-in ``name`` of ``driver``: its solution in DOT units on the time-staggered grid, or ``centred``: with the density on the
+    time-centred grid and mu0 / mu1 as end points.  ``finest``: the plug-in takes ``geometries`` (coarse to fine) and returns the
+    solution on the last one; ``who``: the driver in the message where there is none."""
+    def run(n_time, geometry, geom, readout, kwargs):
+        mu0, mu1 = _end_points(geom) if centred else (None, None)
+        solution_socp, run_history = driver(n_time, geometry, read_out=_read_out_spec(readout, centred, kwargs), **kwargs)
+        return _finish(solution_socp, geom, mu0, mu1, readout, centred), run_history
+
+    if finest:
+        def plug_in(n_time, geometries, readout="device", **kwargs):
+            return run(n_time, *_finest(geometries, who), readout, kwargs)
+    else:
+        def plug_in(n_time, geometry, readout="device", **kwargs):
+            return run(n_time, geometry, geometry, readout, kwargs)
+    plug_in.__name__, plug_in.__doc__ = name, doc
+    return plug_in
 
 
-solver_raw_mesh_cascade.__name__ = "dot_solver_socp_mesh_cascade"
-
-
-def solver_mesh_cascade(n_time, geometries, readout="device", **kwargs):
-    """``solver`` on the finest of ``geometries`` through the cascade in space: the density on the time-centred grid with the finest
-    level's mu0 / mu1 as end points."""
-    geometries, fine = _finest(geometries)
-    mu0, mu1 = _end_points(fine)
-    solution_socp, run_history = solver_socp_mesh_cascade(n_time, geometries, read_out=_read_out_spec(readout, True, kwargs), **kwargs)
-    return _finish(solution_socp, fine, mu0, mu1, readout, True), run_history
-
-
-solver_mesh_cascade.__name__ = "dot_solver_socp_mesh_cascade_center"
-
-
-def solver_raw_spacetime_cascade(n_time, geometries, readout="device", **kwargs):
-    """``solver_raw`` on the finest of ``geometries`` through the cascade in space and time (``solver_socp_spacetime_cascade``: ``levels``,
-    ``level_tol`` and the keywords of ``solver_socp``)."""
-    geometries, fine = _finest(geometries, "solver_socp_spacetime_cascade")
-    solution_socp, run_history = solver_socp_spacetime_cascade(n_time, geometries, read_out=_read_out_spec(readout, False, kwargs), **kwargs)
-    return _finish(solution_socp, fine, None, None, readout, False), run_history
-
-
-solver_raw_spacetime_cascade.__name__ = "dot_solver_socp_spacetime_cascade"
-
-
-def solver_spacetime_cascade(n_time, geometries, readout="device", **kwargs):
-    """``solver`` on the finest of ``geometries`` through the cascade in space and time: the density on the time-centred grid with the
-    finest level's mu0 / mu1 as end points."""
-    geometries, fine = _finest(geometries, "solver_socp_spacetime_cascade")
-    mu0, mu1 = _end_points(fine)
-    solution_socp, run_history = solver_socp_spacetime_cascade(n_time, geometries, read_out=_read_out_spec(readout, True, kwargs), **kwargs)
-    return _finish(solution_socp, fine, mu0, mu1, readout, True), run_history
-
-
-solver_spacetime_cascade.__name__ = "dot_solver_socp_spacetime_cascade_center"
-
-
-def solver_raw_auto_cascade(n_time, geometry, readout="device", **kwargs):
-    """``solver_raw`` through a cascade in space made of ``geometry`` alone (``solver_socp_auto_cascade``: ``coarse_levels``, ``ratio``,
-    ``locate``, ``spacetime``, ``levels``, ``level_tol`` and the keywords of ``solver_socp``): the signature of ``solver_raw``, so it can be
-    passed as ``solver=`` where one geometry is handed over."""
-    solution_socp, run_history = solver_socp_auto_cascade(n_time, geometry, read_out=_read_out_spec(readout, False, kwargs), **kwargs)
-    return _finish(solution_socp, geometry, None, None, readout, False), run_history
-
-
-solver_raw_auto_cascade.__name__ = "dot_solver_socp_auto_cascade"
-
-
-def solver_auto_cascade(n_time, geometry, readout="device", **kwargs):
-    """``solver`` through a cascade in space made of ``geometry`` alone: the density on the time-centred grid with mu0 / mu1 as end
-    points."""
-    mu0, mu1 = _end_points(geometry)
-    solution_socp, run_history = solver_socp_auto_cascade(n_time, geometry, read_out=_read_out_spec(readout, True, kwargs), **kwargs)
-    return _finish(solution_socp, geometry, mu0, mu1, readout, True), run_history
-
-
-solver_auto_cascade.__name__ = "dot_solver_socp_auto_cascade_center"
+solver_raw = _plug_in(solver_socp, "dot_solver_socp", False,
+                      doc="Solve the DOT problem with the GPU SOCP solver; solution on the time-staggered grid.")
+solver = _plug_in(solver_socp, "dot_solver_socp_center", True,
+                  doc="``solver_raw`` with the density moved to the time-centred grid and mu0 / mu1 as end points.")
+solver_raw_cascade = _plug_in(solver_socp_cascade, "dot_solver_socp_cascade", False,
+                              doc="``solver_raw`` through the time cascade (``solver_socp_cascade``: ``levels``, ``level_tol`` and the keywords of "
+                                  "``solver_socp``).")
+solver_cascade = _plug_in(solver_socp_cascade, "dot_solver_socp_cascade_center", True,
+                          doc="``solver`` through the time cascade: the density on the time-centred grid with mu0 / mu1 as end points.")
+solver_raw_mesh_cascade = _plug_in(solver_socp_mesh_cascade, "dot_solver_socp_mesh_cascade", False, True, "solver_socp_mesh_cascade",
+                                   doc="``solver_raw`` on the finest of ``geometries`` through the cascade in space (``solver_socp_mesh_cascade``: "
+                                       "``level_tol`` and the keywords of ``solver_socp``).")
+solver_mesh_cascade = _plug_in(solver_socp_mesh_cascade, "dot_solver_socp_mesh_cascade_center", True, True, "solver_socp_mesh_cascade",
+                               doc="``solver`` on the finest of ``geometries`` through the cascade in space: the density on the time-centred grid "
+                                   "with the finest level's mu0 / mu1 as end points.")
+solver_raw_spacetime_cascade = _plug_in(solver_socp_spacetime_cascade, "dot_solver_socp_spacetime_cascade", False, True, "solver_socp_spacetime_cascade",
+                                        doc="``solver_raw`` on the finest of ``geometries`` through the cascade in space and time "
+                                            "(``solver_socp_spacetime_cascade``: ``levels``, ``level_tol`` and the keywords of ``solver_socp``).")
+solver_spacetime_cascade = _plug_in(solver_socp_spacetime_cascade, "dot_solver_socp_spacetime_cascade_center", True, True, "solver_socp_spacetime_cascade",
+                                    doc="``solver`` on the finest of ``geometries`` through the cascade in space and time: the density on the "
+                                        "time-centred grid with the finest level's mu0 / mu1 as end points.")
+solver_raw_auto_cascade = _plug_in(solver_socp_auto_cascade, "dot_solver_socp_auto_cascade", False,
+                                   doc="``solver_raw`` through a cascade in space made of ``geometry`` alone (``solver_socp_auto_cascade``: "
+                                       "``coarse_levels``, ``ratio``, ``locate``, ``spacetime``, ``levels``, ``level_tol`` and the keywords of "
+                                       "``solver_socp``): the signature of ``solver_raw``, so it can be passed as ``solver=`` where one geometry is "
+                                       "handed over.")
+solver_auto_cascade = _plug_in(solver_socp_auto_cascade, "dot_solver_socp_auto_cascade_center", True,
+                               doc="``solver`` through a cascade in space made of ``geometry`` alone: the density on the time-centred grid with "
+                                   "mu0 / mu1 as end points.")
 
 
 def solver_raw_many(n_time, geometry, problems, readout="device", **kwargs):

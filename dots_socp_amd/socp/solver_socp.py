@@ -921,12 +921,119 @@ class _BatchShare:
         self.ms_q_lambda_multiplier = st.ms_q_lambda_multiplier / n
 
 
-# ---- coarse-to-fine time cascade ---------------------------------------------------------------------------------------------
+# ---- coarse-to-fine cascades: what the drivers share ---------------------------------------------------------------------------------
 CASCADE_KEYS = ("congestion", "nit", "eps", "tol", "tau", "is_palm", "is_multi_threads", "is_z_scaling", "is_constant_scaling",
                 "check_kkt_step_by_step", "init_solution", "tol_checkpoints", "time_limit", "lap_solver", "cg_tol", "cg_max_iter", "device",
                 "reorder", "preconditioner", "mg_coarsest", "nd_leaf")
 
 
+def _check_option_names(who, kwargs):
+    if "pcg_windows" in kwargs:
+        raise ValueError(PCG_WINDOWS_ONE_SOLVER.format(who=who))
+    unknown = set(kwargs) - set(CASCADE_KEYS)
+    if unknown:
+        raise ValueError(f"{who}: unknown option(s) {sorted(unknown)}")
+
+
+def _check_lap_solver(kwargs, time_grids):
+    """The solver's name, then every time grid against it.  ``time_grids``: a list, or a callable that makes it once the name is good."""
+    lap_solver = kwargs.get("lap_solver", "modal_direct")
+    if lap_solver != "modal_direct" and lap_solver not in _lib.LAP_SOLVERS:
+        raise ValueError(f"lap_solver must be one of {['modal_direct'] + list(_lib.LAP_SOLVERS)}")
+    time_grids = time_grids() if callable(time_grids) else time_grids
+    for T in time_grids:
+        check_time_nodes(T, lap_solver)
+    return time_grids
+
+
+def _check_preconditioner(kwargs):
+    if kwargs.get("preconditioner", "multigrid") not in ("multigrid", "jacobi"):
+        raise ValueError("preconditioner must be 'multigrid' or 'jacobi'")
+
+
+def _common_cascade_checks(kwargs, level_tol, time_grids=None, level_tol_optional=False):
+    """The option checks the cascade drivers repeat, in the order their callers see: with ``time_grids`` the Laplacian solver and the
+    preconditioner are checked here too (the cascade in space leaves them to AlmSolver).  ``level_tol``: None is ``tol``, or with
+    ``level_tol_optional`` left to the driver that will run.  Returns ``(level_tol, time_grids)``."""
+    if time_grids is not None:
+        time_grids = _check_lap_solver(kwargs, time_grids)
+    tol = kwargs.get("tol", 1e-4)
+    if level_tol is None and not level_tol_optional:
+        level_tol = tol
+    if (level_tol is not None or not level_tol_optional) and not (isinstance(level_tol, (int, float)) and level_tol > 0):
+        raise ValueError("level_tol must be a positive number")
+    _validate_checkpoints(kwargs.get("tol_checkpoints"), tol)
+    if time_grids is not None:
+        _check_preconditioner(kwargs)
+    if int(kwargs.get("nit", 1000)) < 1:
+        raise ValueError("nit must be at least 1")
+    return level_tol, time_grids
+
+
+def _max_distance(geom):
+    d = (geom.get("transfer") or {}).get("max_distance")
+    return None if d is None else float(d)
+
+
+def _time_record(alm, hist, setup, n_time):
+    return {"n_time": int(n_time), "tol": float(alm.tol), "iterations": int(alm.counter_main) + 1, "running_time": float(hist.running_time),
+            "setup_seconds": float(setup), "prolong_ms": alm.prolong_ms, "cost": float(hist.history["Transportation cost"][-1]),
+            "kkt_max": float(np.nanmax(np.asarray(hist.kkt_errors[-1], dtype=np.float64)))}
+
+
+def _mesh_record(alm, hist, setup, geom, first):
+    return {"n_vertices": int(alm.dev.V), "n_triangles": int(alm.dev.F), "tol": float(alm.tol), "iterations": int(alm.counter_main) + 1,
+            "running_time": float(hist.running_time), "setup_seconds": float(setup), "prolong_ms": alm.prolong_ms,
+            "prolong_bytes": getattr(alm.dev, "prolong_bytes", None), "cost": float(hist.history["Transportation cost"][-1]),
+            "kkt_max": float(np.nanmax(np.asarray(hist.kkt_errors[-1], dtype=np.float64))),
+            "device_bytes": int(hist.solver_stats["device_bytes"]),
+            "transfer": None if first else ("nested" if geom.get("parents") is not None else "located"),
+            "max_distance": None if first else _max_distance(geom)}
+
+
+def _carried(geom, i, **more):
+    """The AlmSolver keywords of mesh level ``i``: how the state of the level below reaches it."""
+    return dict(geometry=geom, init_parents=geom.get("parents") if i else None, init_transfer=geom.get("transfer") if i else None, **more)
+
+
+def _run_levels(levels, stats_key, record, level_tol, opts, read_out, flow_map):
+    """The level loop of the cascade drivers.  ``levels``: per level, the AlmSolver keywords that vary (``n_time``, ``geometry``, a ``plan``,
+    ``init_parents`` / ``init_transfer`` / ``init_regrid``, ...), or a callable that makes them when the level starts (its time is set-up
+    time).  Each level is warm-started from the one before (``init_from``, released before the finer factor is built), runs ``nit``
+    iterations at most within what is left of ``time_limit``, and adds ``record(alm, hist, setup, i)`` to ``solver_stats[stats_key]``;
+    only the last one is downloaded.  ``opts``: the driver's checked options."""
+    tol, nit = opts.pop("tol", 1e-4), int(opts.pop("nit", 1000))
+    time_limit = opts.pop("time_limit", 1000)
+    init_solution, checkpoints = opts.pop("init_solution", None), opts.pop("tol_checkpoints", None)
+    t_start = time.perf_counter()
+    records = []
+    coarse = alm = None
+    try:
+        for i, level in enumerate(levels):
+            last = i + 1 == len(levels)
+            t0 = time.perf_counter()
+            level = level() if callable(level) else level
+            alm = AlmSolver(nit=nit, tol=tol if last else level_tol, tol_checkpoints=checkpoints if last else None,
+                            init_solution=init_solution if i == 0 else None, init_from=coarse, release_init_from=True,
+                            time_limit=max(time_limit - (t0 - t_start), 0.0), **level, **opts)
+            coarse = None      # (closed by the constructor as soon as the finer state was filled)
+            setup = time.perf_counter() - t0
+            for _ in range(nit):
+                if alm.iterate():
+                    break
+            solution, hist = alm.finalize(download=last, read_out=read_out if last else None, flow_map=flow_map if last else None)
+            records.append(record(alm, hist, setup, i))
+            coarse, alm = alm, None
+        coarse.dev.sync()
+        hist.solver_stats[stats_key] = {"levels": records, "total_seconds": time.perf_counter() - t_start}
+        return solution, hist
+    finally:
+        for a in (alm, coarse):
+            if a is not None:
+                a.close()
+
+
+# ---- coarse-to-fine time cascade ---------------------------------------------------------------------------------------------
 def _cascade_options(n_time, levels, level_tol, kwargs):
     """The checks of solver_socp_cascade, before any device is touched: (levels, level_tol, options)."""
     from .. import cascade
@@ -935,27 +1042,8 @@ def _cascade_options(n_time, levels, level_tol, kwargs):
         raise ValueError("solver_socp_cascade: time slabs are not supported (a cascade runs on one GPU)")
     if "init_from" in kwargs:
         raise ValueError("solver_socp_cascade: init_from belongs to the levels of the cascade; start the coarsest level with init_solution")
-    if "pcg_windows" in kwargs:
-        raise ValueError(PCG_WINDOWS_ONE_SOLVER.format(who="solver_socp_cascade"))
-    unknown = set(kwargs) - set(CASCADE_KEYS)
-    if unknown:
-        raise ValueError(f"solver_socp_cascade: unknown option(s) {sorted(unknown)}")
-    levels = cascade.check_levels(levels, n_time)
-    lap_solver = kwargs.get("lap_solver", "modal_direct")
-    if lap_solver != "modal_direct" and lap_solver not in _lib.LAP_SOLVERS:
-        raise ValueError(f"lap_solver must be one of {['modal_direct'] + list(_lib.LAP_SOLVERS)}")
-    for T in levels:
-        check_time_nodes(T, lap_solver)
-    tol = kwargs.get("tol", 1e-4)
-    if level_tol is None:
-        level_tol = tol
-    if not (isinstance(level_tol, (int, float)) and level_tol > 0):
-        raise ValueError("level_tol must be a positive number")
-    _validate_checkpoints(kwargs.get("tol_checkpoints"), tol)
-    if kwargs.get("preconditioner", "multigrid") not in ("multigrid", "jacobi"):
-        raise ValueError("preconditioner must be 'multigrid' or 'jacobi'")
-    if int(kwargs.get("nit", 1000)) < 1:
-        raise ValueError("nit must be at least 1")
+    _check_option_names("solver_socp_cascade", kwargs)
+    level_tol, levels = _common_cascade_checks(kwargs, level_tol, cascade.check_levels(levels, n_time))
     opts = dict(kwargs)
     opts.pop("is_multi_threads", None)
     return levels, level_tol, opts
@@ -983,98 +1071,59 @@ def solver_socp_cascade(n_time, geometry, levels=None, level_tol=None, read_out=
 
     flow_map = check_flow_map(flow_map, kwargs.get("time_slab"))
     levels, level_tol, opts = _cascade_options(n_time, levels, level_tol, kwargs)
-    tol, nit = opts.pop("tol", 1e-4), int(opts.pop("nit", 1000))
-    time_limit = opts.pop("time_limit", 1000)
-    init_solution, checkpoints = opts.pop("init_solution", None), opts.pop("tol_checkpoints", None)
-    direct = opts.get("lap_solver", "modal_direct") == "modal_direct"
     reorder = opts.pop("reorder", True)
-    if direct and reorder is True:
+    if opts.get("lap_solver", "modal_direct") == "modal_direct" and reorder is True:
         reorder = "nd"      # (as AlmSolver chooses it)
     nd_leaf = opts.get("nd_leaf", 16)
-    t_start = time.perf_counter()
-    shared, plans, records = {}, [], []
-    coarse = alm = None
-    try:
-        for i, T in enumerate(levels):
-            last = i + 1 == len(levels)
-            t0 = time.perf_counter()
-            plans.append(geo.build_plan(T, geometry, reorder=reorder, nd_leaf=nd_leaf, _shared=shared, _earlier=tuple(plans)))
-            alm = AlmSolver(T, geometry, nit=nit, tol=tol if last else level_tol, tol_checkpoints=checkpoints if last else None,
-                            init_solution=init_solution if i == 0 else None, init_from=coarse, release_init_from=True,
-                            time_limit=max(time_limit - (t0 - t_start), 0.0), plan=plans[-1], batched=False, reorder=reorder, **opts)
-            coarse = None      # (closed by the constructor as soon as the finer state was filled)
-            setup = time.perf_counter() - t0
-            for _ in range(nit):
-                if alm.iterate():
-                    break
-            solution, hist = alm.finalize(download=last, read_out=read_out if last else None, flow_map=flow_map if last else None)
-            records.append({"n_time": int(T), "tol": float(alm.tol), "iterations": int(alm.counter_main) + 1, "running_time": float(hist.running_time),
-                            "setup_seconds": float(setup), "prolong_ms": alm.prolong_ms, "cost": float(hist.history["Transportation cost"][-1]),
-                            "kkt_max": float(np.nanmax(np.asarray(hist.kkt_errors[-1], dtype=np.float64)))})
-            coarse, alm = alm, None
-        coarse.dev.sync()
-        hist.solver_stats["cascade"] = {"levels": records, "total_seconds": time.perf_counter() - t_start}
-        return solution, hist
-    finally:
-        for a in (alm, coarse):
-            if a is not None:
-                a.close()
+    shared, plans = {}, []
+
+    def level(T):      # the levels' plans share what does not depend on the time grid
+        plans.append(geo.build_plan(T, geometry, reorder=reorder, nd_leaf=nd_leaf, _shared=shared, _earlier=tuple(plans)))
+        return dict(n_time=T, geometry=geometry, plan=plans[-1], batched=False, reorder=reorder)
+
+    return _run_levels([lambda T=T: level(T) for T in levels], "cascade", lambda alm, hist, setup, i: _time_record(alm, hist, setup, levels[i]),
+                       level_tol, opts, read_out, flow_map)
 
 
 # ---- coarse-to-fine cascade in space ---------------------------------------------------------------------------------------------
-def _mesh_cascade_options(geometries, level_tol, kwargs):
-    """The checks of solver_socp_mesh_cascade, before any device is touched: (geometries, level_tol, options)."""
+def _mesh_cascade_options(geometries, level_tol, kwargs, who="solver_socp_mesh_cascade"):
+    """The checks of solver_socp_mesh_cascade (and, as ``who``, of the cascade in space and time), before any device is touched:
+    (geometries, level_tol, options)."""
     from .. import cascade
 
     try:
         geometries = list(geometries)
     except TypeError:
-        raise ValueError("solver_socp_mesh_cascade: geometries must be a list of geometries, coarse to fine") from None
+        raise ValueError(f"{who}: geometries must be a list of geometries, coarse to fine") from None
     if len(geometries) < 2:
-        raise ValueError("solver_socp_mesh_cascade: at least two geometries (a coarse level and its refinement); one level is solver_socp")
+        raise ValueError(f"{who}: at least two geometries (a coarse level and its refinement); one level is solver_socp")
     for key in ("time_slab", "init_from", "init_parents", "init_transfer", "levels"):
         if key in kwargs:
-            raise ValueError(f"solver_socp_mesh_cascade: {key} is not an option of the cascade in space" +
+            raise ValueError(f"{who}: {key} is not an option of the cascade in space" +
                              (" (a cascade in time and in space in one call is not supported)" if key == "levels" else ""))
-    if "pcg_windows" in kwargs:
-        raise ValueError(PCG_WINDOWS_ONE_SOLVER.format(who="solver_socp_mesh_cascade"))
-    unknown = set(kwargs) - set(CASCADE_KEYS)
-    if unknown:
-        raise ValueError(f"solver_socp_mesh_cascade: unknown option(s) {sorted(unknown)}")
+    _check_option_names(who, kwargs)
     for i, (coarse, fine) in enumerate(zip(geometries, geometries[1:])):
         nested, located = isinstance(fine, dict) and fine.get("parents") is not None, isinstance(fine, dict) and fine.get("transfer") is not None
         if nested and located:
-            raise ValueError(f"solver_socp_mesh_cascade: geometry {i + 1} has both 'parents' and 'transfer': the level below is its parent mesh "
+            raise ValueError(f"{who}: geometry {i + 1} has both 'parents' and 'transfer': the level below is its parent mesh "
                              "or a located mesh, not both")
         if not nested and not located:
-            raise ValueError(f"solver_socp_mesh_cascade: geometry {i + 1} has neither 'parents' (meshes.refine_levels / meshes.subdivide) nor "
+            raise ValueError(f"{who}: geometry {i + 1} has neither 'parents' (meshes.refine_levels / meshes.subdivide) nor "
                              "'transfer' (meshes.link_levels / cascade.mesh_transfer)")
         size_c = dict(n_vertices=np.asarray(coarse["vertices"]).shape[0], n_triangles=np.asarray(coarse["triangles"]).shape[0])
         size_f = (np.asarray(fine["vertices"]).shape[0], np.asarray(fine["triangles"]).shape[0])
         if nested:
             vp, tp = cascade.check_parents(fine["parents"], **size_c)
             if (vp.shape[0], tp.shape[0]) != size_f:
-                raise ValueError(f"solver_socp_mesh_cascade: the parents of geometry {i + 1} do not have its size")
+                raise ValueError(f"{who}: the parents of geometry {i + 1} do not have its size")
         else:
             vs, _, ts, _ = cascade.check_transfer(fine["transfer"], **size_c)
             if (vs.shape[0], ts.shape[0]) != size_f:
-                raise ValueError(f"solver_socp_mesh_cascade: the transfer of geometry {i + 1} does not have its size")
-    tol = kwargs.get("tol", 1e-4)
-    if level_tol is None:
-        level_tol = tol
-    if not (isinstance(level_tol, (int, float)) and level_tol > 0):
-        raise ValueError("level_tol must be a positive number")
-    _validate_checkpoints(kwargs.get("tol_checkpoints"), tol)
-    if int(kwargs.get("nit", 1000)) < 1:
-        raise ValueError("nit must be at least 1")
+                raise ValueError(f"{who}: the transfer of geometry {i + 1} does not have its size")
+    level_tol, _ = _common_cascade_checks(kwargs, level_tol)
     opts = dict(kwargs)
     opts.pop("is_multi_threads", None)
     return geometries, level_tol, opts
-
-
-def _max_distance(geom):
-    d = (geom.get("transfer") or {}).get("max_distance")
-    return None if d is None else float(d)
 
 
 def solver_socp_mesh_cascade(n_time, geometries, level_tol=None, read_out=None, flow_map=None, **kwargs):
@@ -1099,41 +1148,8 @@ def solver_socp_mesh_cascade(n_time, geometries, level_tol=None, read_out=None, 
     level, else None)], "total_seconds"}.  ``read_out`` and ``flow_map``: as for ``solver_socp``, for the finest level."""
     flow_map = check_flow_map(flow_map, kwargs.get("time_slab"))
     geometries, level_tol, opts = _mesh_cascade_options(geometries, level_tol, kwargs)
-    tol, nit = opts.pop("tol", 1e-4), int(opts.pop("nit", 1000))
-    time_limit = opts.pop("time_limit", 1000)
-    init_solution, checkpoints = opts.pop("init_solution", None), opts.pop("tol_checkpoints", None)
-    t_start = time.perf_counter()
-    records = []
-    coarse = alm = None
-    try:
-        for i, geom in enumerate(geometries):
-            last = i + 1 == len(geometries)
-            t0 = time.perf_counter()
-            alm = AlmSolver(n_time, geom, nit=nit, tol=tol if last else level_tol, tol_checkpoints=checkpoints if last else None,
-                            init_solution=init_solution if i == 0 else None, init_from=coarse, init_parents=geom.get("parents") if i else None,
-                            init_transfer=geom.get("transfer") if i else None,
-                            release_init_from=True, time_limit=max(time_limit - (t0 - t_start), 0.0), **opts)
-            coarse = None      # (closed by the constructor as soon as the finer state was filled)
-            setup = time.perf_counter() - t0
-            for _ in range(nit):
-                if alm.iterate():
-                    break
-            solution, hist = alm.finalize(download=last, read_out=read_out if last else None, flow_map=flow_map if last else None)
-            records.append({"n_vertices": int(alm.dev.V), "n_triangles": int(alm.dev.F), "tol": float(alm.tol), "iterations": int(alm.counter_main) + 1,
-                            "running_time": float(hist.running_time), "setup_seconds": float(setup), "prolong_ms": alm.prolong_ms,
-                            "prolong_bytes": getattr(alm.dev, "prolong_bytes", None), "cost": float(hist.history["Transportation cost"][-1]),
-                            "kkt_max": float(np.nanmax(np.asarray(hist.kkt_errors[-1], dtype=np.float64))),
-                            "device_bytes": int(hist.solver_stats["device_bytes"]),
-                            "transfer": None if i == 0 else ("nested" if geom.get("parents") is not None else "located"),
-                            "max_distance": _max_distance(geom) if i else None})
-            coarse, alm = alm, None
-        coarse.dev.sync()
-        hist.solver_stats["mesh_cascade"] = {"levels": records, "total_seconds": time.perf_counter() - t_start}
-        return solution, hist
-    finally:
-        for a in (alm, coarse):
-            if a is not None:
-                a.close()
+    return _run_levels([_carried(geom, i, n_time=n_time) for i, geom in enumerate(geometries)], "mesh_cascade",
+                       lambda alm, hist, setup, i: _mesh_record(alm, hist, setup, geometries[i], i == 0), level_tol, opts, read_out, flow_map)
 
 
 # ---- coarse-to-fine cascade in space and time at once ----------------------------------------------------------------------------
@@ -1141,19 +1157,9 @@ def _spacetime_cascade_options(n_time, geometries, levels, level_tol, kwargs):
     """The checks of solver_socp_spacetime_cascade, before any device is touched: (geometries, levels, level_tol, options)."""
     from .. import cascade
 
-    who = "solver_socp_spacetime_cascade"
-    try:
-        geometries, level_tol, opts = _mesh_cascade_options(geometries, level_tol, kwargs)
-    except ValueError as exc:
-        raise ValueError(str(exc).replace("solver_socp_mesh_cascade", who)) from None
-    levels = cascade.check_spacetime_levels(levels, n_time, len(geometries))
-    lap_solver = opts.get("lap_solver", "modal_direct")
-    if lap_solver != "modal_direct" and lap_solver not in _lib.LAP_SOLVERS:
-        raise ValueError(f"lap_solver must be one of {['modal_direct'] + list(_lib.LAP_SOLVERS)}")
-    for T in levels:
-        check_time_nodes(T, lap_solver)
-    if opts.get("preconditioner", "multigrid") not in ("multigrid", "jacobi"):
-        raise ValueError("preconditioner must be 'multigrid' or 'jacobi'")
+    geometries, level_tol, opts = _mesh_cascade_options(geometries, level_tol, kwargs, who="solver_socp_spacetime_cascade")
+    levels = _check_lap_solver(opts, cascade.check_spacetime_levels(levels, n_time, len(geometries)))
+    _check_preconditioner(opts)
     return geometries, levels, level_tol, opts
 
 
@@ -1176,42 +1182,10 @@ def solver_socp_spacetime_cascade(n_time, geometries, levels=None, level_tol=Non
     finest level."""
     flow_map = check_flow_map(flow_map, kwargs.get("time_slab"))
     geometries, levels, level_tol, opts = _spacetime_cascade_options(n_time, geometries, levels, level_tol, kwargs)
-    tol, nit = opts.pop("tol", 1e-4), int(opts.pop("nit", 1000))
-    time_limit = opts.pop("time_limit", 1000)
-    init_solution, checkpoints = opts.pop("init_solution", None), opts.pop("tol_checkpoints", None)
-    t_start = time.perf_counter()
-    records = []
-    coarse = alm = None
-    try:
-        for i, (T, geom) in enumerate(zip(levels, geometries)):
-            last = i + 1 == len(geometries)
-            t0 = time.perf_counter()
-            alm = AlmSolver(T, geom, nit=nit, tol=tol if last else level_tol, tol_checkpoints=checkpoints if last else None,
-                            init_solution=init_solution if i == 0 else None, init_from=coarse, init_parents=geom.get("parents") if i else None,
-                            init_transfer=geom.get("transfer") if i else None, init_regrid=bool(i) and T != levels[i - 1],
-                            release_init_from=True, time_limit=max(time_limit - (t0 - t_start), 0.0), **opts)
-            coarse = None      # (closed by the constructor as soon as the finer state was filled)
-            setup = time.perf_counter() - t0
-            for _ in range(nit):
-                if alm.iterate():
-                    break
-            solution, hist = alm.finalize(download=last, read_out=read_out if last else None, flow_map=flow_map if last else None)
-            records.append({"n_time": int(T), "n_vertices": int(alm.dev.V), "n_triangles": int(alm.dev.F), "tol": float(alm.tol),
-                            "iterations": int(alm.counter_main) + 1, "running_time": float(hist.running_time), "setup_seconds": float(setup),
-                            "prolong_ms": alm.prolong_ms, "prolong_bytes": getattr(alm.dev, "prolong_bytes", None),
-                            "cost": float(hist.history["Transportation cost"][-1]),
-                            "kkt_max": float(np.nanmax(np.asarray(hist.kkt_errors[-1], dtype=np.float64))),
-                            "device_bytes": int(hist.solver_stats["device_bytes"]),
-                            "transfer": None if i == 0 else ("nested" if geom.get("parents") is not None else "located"),
-                            "max_distance": _max_distance(geom) if i else None})
-            coarse, alm = alm, None
-        coarse.dev.sync()
-        hist.solver_stats["spacetime_cascade"] = {"levels": records, "total_seconds": time.perf_counter() - t_start}
-        return solution, hist
-    finally:
-        for a in (alm, coarse):
-            if a is not None:
-                a.close()
+    return _run_levels([_carried(geom, i, n_time=T, init_regrid=bool(i) and T != levels[i - 1]) for i, (T, geom) in enumerate(zip(levels, geometries))],
+                       "spacetime_cascade",
+                       lambda alm, hist, setup, i: {"n_time": int(levels[i]), **_mesh_record(alm, hist, setup, geometries[i], i == 0)},
+                       level_tol, opts, read_out, flow_map)
 
 
 # ---- a cascade in space from ONE geometry: the levels are made here ----------------------------------------------------------------
@@ -1228,27 +1202,11 @@ def _auto_cascade_options(n_time, coarse_levels, ratio, locate, spacetime, level
     for key in ("time_slab", "init_from", "init_parents", "init_transfer"):
         if key in kwargs:
             raise ValueError(f"{who}: {key} is not an option of the cascade in space")
-    if "pcg_windows" in kwargs:
-        raise ValueError(PCG_WINDOWS_ONE_SOLVER.format(who=who))
-    unknown = set(kwargs) - set(CASCADE_KEYS)
-    if unknown:
-        raise ValueError(f"{who}: unknown option(s) {sorted(unknown)}")
+    _check_option_names(who, kwargs)
     if levels is not None and not spacetime:
         raise ValueError(f"{who}: levels (one n_time per mesh level) needs spacetime=True")
-    lap_solver = kwargs.get("lap_solver", "modal_direct")
-    if lap_solver != "modal_direct" and lap_solver not in _lib.LAP_SOLVERS:
-        raise ValueError(f"lap_solver must be one of {['modal_direct'] + list(_lib.LAP_SOLVERS)}")
-    time_grids = cascade.check_spacetime_levels(levels, n_time, int(coarse_levels) + 1) if spacetime else [n_time]
-    for T in time_grids:
-        check_time_nodes(T, lap_solver)
-    tol = kwargs.get("tol", 1e-4)
-    if level_tol is not None and not (isinstance(level_tol, (int, float)) and level_tol > 0):
-        raise ValueError("level_tol must be a positive number")
-    _validate_checkpoints(kwargs.get("tol_checkpoints"), tol)
-    if kwargs.get("preconditioner", "multigrid") not in ("multigrid", "jacobi"):
-        raise ValueError("preconditioner must be 'multigrid' or 'jacobi'")
-    if int(kwargs.get("nit", 1000)) < 1:
-        raise ValueError("nit must be at least 1")
+    _common_cascade_checks(kwargs, level_tol, lambda: cascade.check_spacetime_levels(levels, n_time, int(coarse_levels) + 1) if spacetime else [n_time],
+                           level_tol_optional=True)
     return int(coarse_levels)
 
 

@@ -12,7 +12,8 @@ from dots_socp_amd import _lib, cascade, meshes
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not has_gpu(), reason="needs a GPU")]
 
 STATE = ("phi", "A", "B", "lambda_c", "z_fst", "z_mid", "z_end", "mu", "E", "beta_fst", "beta_mid", "beta_end")
-GRIDS = [(7, 15), (15, 31), (31, 63), (20, 50), (31, 31), (63, 127), (255, 511), (300, 1023)]
+# (1, 3): one source interval, the clamp min(j + 1, ns - 1) acts on every interval column; (31, 7): coarsening, the source pitch is the larger
+GRIDS = [(7, 15), (15, 31), (31, 63), (20, 50), (31, 31), (63, 127), (255, 511), (300, 1023), (1, 3), (31, 7)]
 
 
 def delaunay_patch(seed=11, n=150):
@@ -107,6 +108,26 @@ def test_prolongation_matches_the_host_specification(name, n_src, n_dst):
                 got = dst.download(k)
                 assert got.shape == want[k].shape
                 assert np.array_equal(bits(got), bits(want[k])), (k, reorder, float(np.max(np.abs(got - want[k]))))
+
+
+def test_prolongation_with_and_without_row_maps():
+    """The one runtime branch of the carrier's space mode "same": both row maps null (neither side renumbered) and both passed (only the
+    destination renumbered), from one source, each against the host specification."""
+    from dots_socp_amd.device import DeviceProblem
+
+    geom = mesh("torus")
+    alm = scaled_source(geom, 7, reorder=False)
+    try:
+        want = host_prolongation(alm, 15)
+        for reorder in (False, "nd"):
+            with DeviceProblem(15, geom, lap_solver="modal_pcg", reorder=reorder) as dst:
+                maps = (cascade.row_map(dst.plan.perm_vert, alm.dev.plan.perm_vert, dst.V), cascade.row_map(dst.plan.perm_tri, alm.dev.plan.perm_tri, dst.F))
+                assert all((m is None) == (reorder is False) for m in maps)
+                dst.prolong_from(alm.dev, alm.recovery_factors())
+                for k in STATE:
+                    assert np.array_equal(bits(dst.download(k)), bits(want[k])), (k, reorder)
+    finally:
+        alm.close()
 
 
 def test_some_default_pair_has_different_numberings():

@@ -117,8 +117,8 @@ def test_carrier_at_the_largest_pitches():
 
 @pytest.mark.parametrize("name,grids", [("nested-icosphere", (7, 15)), ("located-torus", (6, 13))])
 def test_carrier_equals_the_two_existing_kernels(name, grids):
-    """The fused call against the carrier in space into a context on the fine mesh at the source's n_time, then dots_prolong_time with
-    factors of 1 from there"""
+    """The fused call against two calls into the same kernel family: the carrier in space (the run kernel) into a context on the fine mesh
+    at the source's n_time, then dots_prolong_time (the staged kernel with the same row as its space stage) with factors of 1 from there"""
     from dots_socp_amd.device import DeviceProblem
 
     n_src, n_dst = grids

@@ -4,6 +4,7 @@ driver's argument errors before any device call, and the entry point in the head
 import ctypes as C
 import os
 import subprocess
+import types
 
 import numpy as np
 import pytest
@@ -187,6 +188,69 @@ def test_argument_errors_before_any_device_call(monkeypatch):
 
     with pytest.raises(ValueError, match="levels"):
         solver_socp_mesh_cascade(7, levels, levels=[3, 7, 7])
+
+
+TIME_RECORD = ("n_time", "tol", "iterations", "running_time", "setup_seconds", "prolong_ms", "cost", "kkt_max")
+MESH_RECORD = ("n_vertices", "n_triangles", "tol", "iterations", "running_time", "setup_seconds", "prolong_ms", "prolong_bytes", "cost", "kkt_max",
+               "device_bytes", "transfer", "max_distance")
+SPACETIME_RECORD = ("n_time", "n_vertices", "n_triangles", "tol", "iterations", "running_time", "setup_seconds", "prolong_ms", "prolong_bytes", "cost",
+                    "kkt_max", "device_bytes", "transfer", "max_distance")
+PLUG_IN_NAMES = {"solver_raw": "dot_solver_socp", "solver": "dot_solver_socp_center",
+                 "solver_raw_cascade": "dot_solver_socp_cascade", "solver_cascade": "dot_solver_socp_cascade_center",
+                 "solver_raw_mesh_cascade": "dot_solver_socp_mesh_cascade", "solver_mesh_cascade": "dot_solver_socp_mesh_cascade_center",
+                 "solver_raw_spacetime_cascade": "dot_solver_socp_spacetime_cascade",
+                 "solver_spacetime_cascade": "dot_solver_socp_spacetime_cascade_center",
+                 "solver_raw_auto_cascade": "dot_solver_socp_auto_cascade", "solver_auto_cascade": "dot_solver_socp_auto_cascade_center"}
+
+
+class _Level:
+    """What a cascade driver touches of an AlmSolver, without a device: a level that stops after one iteration."""
+    open_levels = 0
+
+    def __init__(self, n_time, geometry, tol=1e-4, init_from=None, release_init_from=False, **kw):
+        self.n_time, self.tol, self.counter_main = n_time, tol, 0
+        self.prolong_ms = None if init_from is None else 0.25
+        self.dev = types.SimpleNamespace(V=np.asarray(geometry["vertices"]).shape[0], F=np.asarray(geometry["triangles"]).shape[0], sync=lambda: None)
+        if init_from is not None:
+            assert release_init_from
+            init_from.close()
+        _Level.open_levels += 1
+
+    def iterate(self):
+        return True
+
+    def finalize(self, **kw):
+        hist = types.SimpleNamespace(running_time=0.5, history={"Transportation cost": [2.0]}, kkt_errors=np.full((1, 7), 1e-5),
+                                     solver_stats={"device_bytes": 1024})
+        return {}, hist
+
+    def close(self):
+        _Level.open_levels -= 1
+
+
+def test_level_records_and_plug_in_names(monkeypatch):
+    """Every level's record of the three cascade drivers has exactly the driver's fields, in its order; one level is open at a time and
+    none is left open; the ten plug-ins keep the names the reference's runner prints."""
+    import importlib
+
+    from dots_socp_amd import socp
+
+    module = importlib.import_module("dots_socp_amd.socp.solver_socp")
+    monkeypatch.setattr(module, "AlmSolver", _Level)
+    levels = sphere_levels(3)
+    runs = [("cascade", TIME_RECORD, 2, lambda: module.solver_socp_cascade(31, levels[0], levels=[15, 31])),
+            ("mesh_cascade", MESH_RECORD, 3, lambda: module.solver_socp_mesh_cascade(7, levels)),
+            ("spacetime_cascade", SPACETIME_RECORD, 3, lambda: module.solver_socp_spacetime_cascade(15, levels, levels=[7, 7, 15]))]
+    for key, fields, n, run in runs:
+        _, hist = run()
+        stats = hist.solver_stats[key]
+        assert tuple(stats) == ("levels", "total_seconds") and len(stats["levels"]) == n
+        for i, rec in enumerate(stats["levels"]):
+            assert tuple(rec) == fields, (key, i, tuple(rec))
+            assert (rec["prolong_ms"] is None) == (i == 0)
+        assert _Level.open_levels == 0
+    for name, printed in PLUG_IN_NAMES.items():
+        assert getattr(socp, name).__name__ == printed
 
 
 def test_header_and_library_have_the_entry_point(tmp_path):
