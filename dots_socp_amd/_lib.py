@@ -35,7 +35,7 @@ EXPORTS = [
     "dots_prolong_space", "dots_transfer_space", "dots_carry_spacetime",
     "dots_pcg_windows",
     "dots_coarsen", "dots_coarsen_vertices", "dots_coarsen_triangles", "dots_coarsen_copy", "dots_coarsen_free", "dots_mesh_locate",
-    "dots_flow_map",
+    "dots_flow_map", "dots_flow_push",
 ]
 
 
@@ -163,6 +163,13 @@ class FlowMapDesc(C.Structure):      # dots_flow_map_desc
         ("n_particles", C.c_int32), ("max_crossings", C.c_int32), ("start_triangle", _i32p), ("start_weights", _f64p), ("neighbours", _i32p),
         ("floor", C.c_double), ("triangle", _i32p), ("weights", _f64p), ("status", _i32p), ("rested", _i32p), ("crossings", _i32p),
         ("triangles_at", _i32p), ("weights_at", _f64p), ("ms", _f64p),
+    ]
+
+
+class FlowPushDesc(C.Structure):      # dots_flow_push_desc
+    _fields_ = [
+        ("map", FlowMapDesc), ("mass", _f64p), ("n_attributes", C.c_int32), ("all_layers", C.c_int32), ("attributes", _f64p),
+        ("scale_exponent", _i32p), ("mass_at", _f64p), ("attr_at", _f64p), ("dropped", C.POINTER(C.c_int64)), ("ms", _f64p),
     ]
 
 
@@ -356,6 +363,7 @@ def load(host_only=False):
     lib.dots_prolong_time.argtypes = [vp, vp, C.POINTER(ProlongDesc)]
     lib.dots_readout.argtypes = [vp, C.POINTER(ReadoutDesc)]
     lib.dots_flow_map.argtypes = [vp, C.POINTER(FlowMapDesc)]
+    lib.dots_flow_push.argtypes = [vp, C.POINTER(FlowPushDesc)]
     lib.dots_prolong_space.argtypes = [vp, vp, C.POINTER(ProlongSpaceDesc)]
     lib.dots_transfer_space.argtypes = [vp, vp, C.POINTER(TransferSpaceDesc)]
     lib.dots_carry_spacetime.argtypes = [vp, vp, C.POINTER(CarrySpacetimeDesc)]

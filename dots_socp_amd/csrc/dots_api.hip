@@ -1778,20 +1778,30 @@ static int flow_prepare(Ctx *c) {
     return 0;
 }
 
-int dots_flow_map(dots_ctx *c, const dots_flow_map_desc *desc) {
-    if (!c) { set_error("null context"); return DOTS_ERR_ARGUMENT; }
-    if (!desc) { set_error("flow_map: null description"); return DOTS_ERR_ARGUMENT; }
-    if (c->shard_stride != 0) { set_error("flow_map: not available on time slabs"); return DOTS_ERR_STATE; }
+// What dots_flow_map and dots_flow_push share: the checks of the embedded description, the caller's starts and neighbour table in the
+// device numbering (host preparation), the allocation of the call, the launch and the copies back.  `push` null: dots_flow_map.
+static int flow_run(dots_ctx *c, const char *who, const dots_flow_map_desc *desc, const dots_flow_push_desc *push) {
+    const std::string w = std::string(who) + ": ";
+    if (c->shard_stride != 0) { set_error(w + "not available on time slabs"); return DOTS_ERR_STATE; }
     const Dev &d = c->d;
-    if (!desc->start_triangle || !desc->start_weights || !desc->neighbours || !desc->triangle || !desc->weights || !desc->status || !desc->rested ||
-        !desc->crossings) {
-        set_error("flow_map: null pointer (start_triangle, start_weights, neighbours and the five outputs are required)");
+    const bool outputs = desc->triangle && desc->weights && desc->status && desc->rested && desc->crossings;
+    if (!desc->start_triangle || !desc->start_weights || !desc->neighbours || (!push && !outputs)) {
+        set_error(w + (push ? "null pointer (start_triangle, start_weights and neighbours are required)"
+                            : "null pointer (start_triangle, start_weights, neighbours and the five outputs are required)"));
         return DOTS_ERR_ARGUMENT;
     }
-    if (desc->n_particles < 1) { set_error("flow_map: n_particles < 1"); return DOTS_ERR_ARGUMENT; }
-    if (desc->max_crossings < 1 || desc->max_crossings > 255) { set_error("flow_map: max_crossings outside 1 .. 255"); return DOTS_ERR_ARGUMENT; }
-    if (std::isnan(desc->floor)) { set_error("flow_map: the floor is not a number"); return DOTS_ERR_ARGUMENT; }
-    if (d.F >= FLOW_MAX_TRIANGLES) { set_error("flow_map: more than 2^27 triangles"); return DOTS_ERR_ARGUMENT; }
+    const int A = push ? push->n_attributes : 0;
+    if (push) {
+        if (!push->mass || !push->scale_exponent || !push->mass_at) { set_error(w + "null pointer (mass, scale_exponent and mass_at are required)"); return DOTS_ERR_ARGUMENT; }
+        if (A < 0 || A > FLOW_PUSH_CHANNELS - 1) { set_error(w + "n_attributes outside 0 .. 4"); return DOTS_ERR_ARGUMENT; }
+        if (A > 0 && (!push->attributes || !push->attr_at)) { set_error(w + "attributes and attr_at are required with n_attributes > 0"); return DOTS_ERR_ARGUMENT; }
+        for (int ch = 0; ch <= A; ++ch)
+            if (push->scale_exponent[ch] < -1000 || push->scale_exponent[ch] > 1000) { set_error(w + "a scale exponent outside -1000 .. 1000"); return DOTS_ERR_ARGUMENT; }
+    }
+    if (desc->n_particles < 1) { set_error(w + "n_particles < 1"); return DOTS_ERR_ARGUMENT; }
+    if (desc->max_crossings < 1 || desc->max_crossings > 255) { set_error(w + "max_crossings outside 1 .. 255"); return DOTS_ERR_ARGUMENT; }
+    if (std::isnan(desc->floor)) { set_error(w + "the floor is not a number"); return DOTS_ERR_ARGUMENT; }
+    if (d.F >= FLOW_MAX_TRIANGLES) { set_error(w + "more than 2^27 triangles"); return DOTS_ERR_ARGUMENT; }
     hipError_t e0 = hipSetDevice(c->device);
     if (e0 != hipSuccess) return hip_fail(e0, "hipSetDevice", __FILE__, __LINE__);
     int rc = flow_prepare(c);
@@ -1803,12 +1813,12 @@ int dots_flow_map(dots_ctx *c, const dots_flow_map_desc *desc) {
     std::vector<int> h_start((size_t)P);
     for (int p = 0; p < P; ++p) {
         const int f = desc->start_triangle[p];
-        if (f < 0 || f >= F) { set_error("flow_map: a start triangle out of range"); return DOTS_ERR_ARGUMENT; }
+        if (f < 0 || f >= F) { set_error(w + "a start triangle out of range"); return DOTS_ERR_ARGUMENT; }
         h_start[p] = to_dev(f);
     }
     for (size_t i = 0; i < (size_t)P * 3; ++i)
         if (!(desc->start_weights[i] >= 0.0 && std::isfinite(desc->start_weights[i]))) {
-            set_error("flow_map: a weight that is negative or not finite");
+            set_error(w + "a weight that is negative or not finite");
             return DOTS_ERR_ARGUMENT;
         }
     // the neighbour table, in the device numbering, every entry with the corners of the neighbour that name the two shared vertices
@@ -1817,7 +1827,7 @@ int dots_flow_map(dots_ctx *c, const dots_flow_map_desc *desc) {
         const int fd = to_dev(f);
         for (int k = 0; k < 3; ++k) {
             const int g = desc->neighbours[(size_t)f * 3 + k];
-            if (g < -1 || g >= F) { set_error("flow_map: a neighbour index out of range"); return DOTS_ERR_ARGUMENT; }
+            if (g < -1 || g >= F) { set_error(w + "a neighbour index out of range"); return DOTS_ERR_ARGUMENT; }
             if (g < 0) { h_nbr[(size_t)fd * 3 + k] = -1; continue; }
             const int gd = to_dev(g);
             const int va = fh.tri[(size_t)fd * 3 + (k + 1) % 3], vb = fh.tri[(size_t)fd * 3 + (k + 2) % 3];
@@ -1826,29 +1836,57 @@ int dots_flow_map(dots_ctx *c, const dots_flow_map_desc *desc) {
                 if (fh.tri[(size_t)gd * 3 + m] == va) ca = m;
                 if (fh.tri[(size_t)gd * 3 + m] == vb) cb = m;
             }
-            if (g == f || ca < 0 || cb < 0 || ca == cb) { set_error("flow_map: a neighbour entry that does not share the edge opposite its corner"); return DOTS_ERR_ARGUMENT; }
+            if (g == f || ca < 0 || cb < 0 || ca == cb) { set_error(w + "a neighbour entry that does not share the edge opposite its corner"); return DOTS_ERR_ARGUMENT; }
             h_nbr[(size_t)fd * 3 + k] = flow_pack_neighbour(gd, ca, cb);
         }
     }
+    // what the particles carry: finite, and small enough for the caller's exponents -- sum_p |g| max(1, (w0 + w1) + w2) 2^k_c <= 2^61
+    FlowPush q{};
+    FlowPushFinish fin{};
+    if (push) {
+        for (int ch = 0; ch <= A; ++ch) {
+            double sum = 0.0;
+            for (int p = 0; p < P; ++p) {
+                const double g = ch == 0 ? push->mass[p] : push->mass[p] * push->attributes[(size_t)(ch - 1) * P + p];
+                if (!std::isfinite(g)) { set_error(w + (ch == 0 ? "a mass that is not finite" : "a mass times an attribute that is not finite")); return DOTS_ERR_ARGUMENT; }
+                const double *sw = desc->start_weights + (size_t)p * 3;
+                const double wsum = (sw[0] + sw[1]) + sw[2];
+                sum += std::fabs(g) * (1.0 > wsum ? 1.0 : wsum);
+            }
+            q.k[ch] = push->scale_exponent[ch];
+            fin.unscale[ch] = std::ldexp(1.0, -push->scale_exponent[ch]);
+            if (!(sum * std::ldexp(1.0, q.k[ch]) <= 0x1p61)) { set_error(w + "a scale exponent too large for what the particles carry (flow.push_scales chooses one)"); return DOTS_ERR_ARGUMENT; }
+        }
+    }
     if ((rc = check(c, true))) return rc;      // (a pending penalty division is carried out, as for a download; z_mid is not needed)
-    // one allocation for the call: [start_w | o_w | w_at] doubles, then [start | nbr | o_tri | status | rested | crossings | tri_at] ints
+    if (push && (rc = readout_prepare(c))) return rc;      // (the inverse of the vertex numbering is the read-out's)
+    // one allocation for the call: [start_w | o_w | w_at | mass | attr | pushed] doubles, [acc | dropped] 64-bit words, then
+    // [start | nbr | o_tri | status | rested | crossings | tri_at] ints
     const size_t layers = (size_t)T + 1;
     const size_t n_wat = desc->weights_at ? layers * P * 3 : 0, n_tat = desc->triangles_at ? layers * P : 0;
-    const size_t n_dbl = (size_t)P * 3 * 2 + n_wat, n_int = (size_t)P * 5 + (size_t)F * 3 + n_tat;
+    const size_t L = push ? (push->all_layers ? layers : 1) : 0;
+    const size_t n_acc = push ? (size_t)(A + 1) * L * (size_t)d.V : 0, n_carry = push ? (size_t)(A + 1) * P : 0;
+    const size_t n_dbl = (size_t)P * 3 * 2 + n_wat + n_carry + n_acc, n_u64 = push ? n_acc + 1 : 0, n_int = (size_t)P * 5 + (size_t)F * 3 + n_tat;
     void *buf = nullptr;
-    hipError_t ea = hipMalloc(&buf, sizeof(double) * n_dbl + sizeof(int) * n_int);
+    hipError_t ea = hipMalloc(&buf, sizeof(double) * (n_dbl + n_u64) + sizeof(int) * n_int);
     if (ea != hipSuccess) {
         (void)hipGetLastError();
-        set_error("flow_map: out of device memory for the particle tables");
+        set_error(w + (push ? "out of device memory for the particle tables and the accumulators" : "out of device memory for the particle tables"));
         return DOTS_ERR_MEMORY;
     }
-    double *b_sw = (double *)buf, *b_ow = b_sw + (size_t)P * 3, *b_wat = b_ow + (size_t)P * 3;
-    int *b_start = (int *)(b_wat + n_wat), *b_nbr = b_start + P, *b_otri = b_nbr + (size_t)F * 3, *b_status = b_otri + P, *b_rested = b_status + P,
+    double *b_sw = (double *)buf, *b_ow = b_sw + (size_t)P * 3, *b_wat = b_ow + (size_t)P * 3, *b_mass = b_wat + n_wat, *b_attr = b_mass + (push ? P : 0),
+           *b_pushed = b_mass + n_carry;
+    unsigned long long *b_acc = (unsigned long long *)(b_pushed + n_acc);
+    int *b_start = (int *)(b_acc + n_u64), *b_nbr = b_start + P, *b_otri = b_nbr + (size_t)F * 3, *b_status = b_otri + P, *b_rested = b_status + P,
         *b_cross = b_rested + P, *b_tat = b_cross + P;
     auto enqueue = [&]() -> int {
         DOTS_HIP(hipMemcpyAsync(b_sw, desc->start_weights, sizeof(double) * (size_t)P * 3, hipMemcpyHostToDevice, c->stream));
         DOTS_HIP(hipMemcpyAsync(b_start, h_start.data(), sizeof(int) * (size_t)P, hipMemcpyHostToDevice, c->stream));
         DOTS_HIP(hipMemcpyAsync(b_nbr, h_nbr.data(), sizeof(int) * (size_t)F * 3, hipMemcpyHostToDevice, c->stream));
+        if (push) {
+            DOTS_HIP(hipMemcpyAsync(b_mass, push->mass, sizeof(double) * (size_t)P, hipMemcpyHostToDevice, c->stream));
+            if (A) DOTS_HIP(hipMemcpyAsync(b_attr, push->attributes, sizeof(double) * (size_t)A * P, hipMemcpyHostToDevice, c->stream));
+        }
         FlowArgs a{};
         a.mu = d.mu; a.E = d.E; a.tri = d.tri; a.hat = d.hat; a.nbr = b_nbr; a.perm_f = d.perm_f;
         a.start_tri = b_start; a.start_w = b_sw;
@@ -1859,31 +1897,60 @@ int dots_flow_map(dots_ctx *c, const dots_flow_map_desc *desc) {
         a.h = 1.0 / (double)T;
         a.P = P; a.T = T; a.tp_shift = d.tp_shift; a.max_crossings = desc->max_crossings;
         DOTS_HIP(hipEventRecord(c->ev[0], c->stream));
-        int r = launch_flow_map(c, a);
-        if (r) return r;
+        int r;
+        if (push) {      // (the milliseconds hold the zeroing, the trace with its deposits and the conversion)
+            q.acc = b_acc; q.mass = b_mass; q.attr = b_attr;
+            q.A = A; q.L = (int)L; q.V = d.V;
+            DOTS_HIP(hipMemsetAsync(b_acc, 0, sizeof(unsigned long long) * n_u64, c->stream));
+            fin.acc = b_acc; fin.inv = c->inv_perm_v; fin.out = b_pushed; fin.A = A; fin.L = (int)L; fin.V = d.V;
+            if ((r = launch_flow_push(c, a, q)) || (r = launch_flow_push_finish(c, fin))) return r;
+        } else if ((r = launch_flow_map(c, a))) return r;
         DOTS_HIP(hipEventRecord(c->ev[1], c->stream));
         // only the outputs cross to the host
-        DOTS_HIP(hipMemcpyAsync(desc->weights, b_ow, sizeof(double) * (size_t)P * 3, hipMemcpyDeviceToHost, c->stream));
+        if (desc->weights) DOTS_HIP(hipMemcpyAsync(desc->weights, b_ow, sizeof(double) * (size_t)P * 3, hipMemcpyDeviceToHost, c->stream));
         int32_t *outs[4] = {desc->triangle, desc->status, desc->rested, desc->crossings};
         const int *srcs[4] = {b_otri, b_status, b_rested, b_cross};
-        for (int i = 0; i < 4; ++i) DOTS_HIP(hipMemcpyAsync(outs[i], srcs[i], sizeof(int) * (size_t)P, hipMemcpyDeviceToHost, c->stream));
+        for (int i = 0; i < 4; ++i)
+            if (outs[i]) DOTS_HIP(hipMemcpyAsync(outs[i], srcs[i], sizeof(int) * (size_t)P, hipMemcpyDeviceToHost, c->stream));
         if (desc->weights_at) DOTS_HIP(hipMemcpyAsync(desc->weights_at, b_wat, sizeof(double) * n_wat, hipMemcpyDeviceToHost, c->stream));
         if (desc->triangles_at) DOTS_HIP(hipMemcpyAsync(desc->triangles_at, b_tat, sizeof(int) * n_tat, hipMemcpyDeviceToHost, c->stream));
+        if (push) {
+            const size_t n_layer = L * (size_t)d.V;
+            DOTS_HIP(hipMemcpyAsync(push->mass_at, b_pushed, sizeof(double) * n_layer, hipMemcpyDeviceToHost, c->stream));
+            if (A) DOTS_HIP(hipMemcpyAsync(push->attr_at, b_pushed + n_layer, sizeof(double) * n_layer * A, hipMemcpyDeviceToHost, c->stream));
+            if (push->dropped) DOTS_HIP(hipMemcpyAsync(push->dropped, b_acc + n_acc, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        }
         return 0;
     };
     rc = enqueue();      // (every path out of the call waits for the stream first: the copies use the caller's and this call's arrays)
     const hipError_t es = hipStreamSynchronize(c->stream);
     if (!rc && es != hipSuccess) rc = hip_fail(es, "hipStreamSynchronize", __FILE__, __LINE__);
-    if (!rc && desc->ms) {
+    if (!rc && (desc->ms || (push && push->ms))) {
         float t = 0.f;
         const hipError_t et = hipEventElapsedTime(&t, c->ev[0], c->ev[1]);
         if (et != hipSuccess) rc = hip_fail(et, "hipEventElapsedTime", __FILE__, __LINE__);
-        *desc->ms = t;
+        if (desc->ms) *desc->ms = t;
+        if (push && push->ms) *push->ms = t;
     }
     (void)hipFree(buf);
     if (rc) return rc;
-    c->d2h_bytes += (int64_t)(sizeof(double) * ((size_t)P * 3 + n_wat) + sizeof(int) * ((size_t)P * 4 + n_tat));
+    size_t bytes = sizeof(double) * n_wat + sizeof(int) * n_tat + (desc->weights ? sizeof(double) * (size_t)P * 3 : 0);
+    for (const int32_t *o : {desc->triangle, desc->status, desc->rested, desc->crossings}) bytes += o ? sizeof(int) * (size_t)P : 0;
+    if (push) bytes += sizeof(double) * n_acc + (push->dropped ? sizeof(int64_t) : 0);
+    c->d2h_bytes += (int64_t)bytes;
     return 0;
+}
+
+int dots_flow_map(dots_ctx *c, const dots_flow_map_desc *desc) {
+    if (!c) { set_error("null context"); return DOTS_ERR_ARGUMENT; }
+    if (!desc) { set_error("flow_map: null description"); return DOTS_ERR_ARGUMENT; }
+    return flow_run(c, "flow_map", desc, nullptr);
+}
+
+int dots_flow_push(dots_ctx *c, const dots_flow_push_desc *desc) {
+    if (!c) { set_error("null context"); return DOTS_ERR_ARGUMENT; }
+    if (!desc) { set_error("flow_push: null description"); return DOTS_ERR_ARGUMENT; }
+    return flow_run(c, "flow_push", &desc->map, desc);
 }
 
 int dots_front_enable(dots_ctx *c, int on) {
@@ -1945,7 +2012,7 @@ int64_t dots_debug_counter(dots_ctx *c, int which) {
         case 6: return c->sched.bm_nt;                      // beta_mid streamed around the caches by steps 2+3 (the rule of dots_front_setup, or DOTS_BM_NT)
         case 7: return c->front_many_launches;        // sweep launches the last front_solve_many on this (first) context enqueued
         case 8: return c->front_many_split;           // ... of those, launches with fewer rhs than their chunk (many_launch halved: LDS or 1024-thread cap)
-        case 9: return c->d2h_bytes;                  // bytes dots_download, dots_readout and dots_flow_map have copied device -> host
+        case 9: return c->d2h_bytes;                  // bytes dots_download, dots_readout, dots_flow_map and dots_flow_push have copied device -> host
         case 10: return c->n_front_allocs;            // device allocations the installed factor holds (0 after front_release: also after a failed dots_front_setup)
         case 11: return c->mg_path;                   // MG_PATH_* bits of the last V-cycle enqueued (dots_dev.h)
         case 12: return c->step_path;                 // STEP_PATH_* bits of the last iteration's launches (dots_dev.h)

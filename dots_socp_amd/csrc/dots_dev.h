@@ -423,6 +423,25 @@ struct FlowArgs {
 constexpr int FLOW_MAX_TRIANGLES = 1 << 27;
 inline int flow_pack_neighbour(int g, int ca, int cb) { return (g << 4) | (ca << 2) | cb; }
 int launch_flow_map(Ctx *c, const FlowArgs &a);
+// dots_flow_push: what the tracer deposits besides.  Channel 0 is the mass, channels 1 .. A the mass times an attribute.
+constexpr int FLOW_PUSH_CHANNELS = 5;
+struct FlowPush {
+    unsigned long long *acc;     // [A + 1][L][V] fixed-point sums, DEVICE vertex numbering, then one word: the contributions that
+                                 // did not fit (|y| < 2^62 false); zeroed by the call
+    const double *mass;          // [P]
+    const double *attr;          // [A][P]
+    int k[FLOW_PUSH_CHANNELS];             // the exponents k_c
+    int A, L, V;                 // L = T + 1 (all the layers), or 1 (the state after interval T)
+};
+struct FlowPushFinish {
+    const unsigned long long *acc;
+    const int *inv;              // caller vertex -> device vertex, or null
+    double *out;                 // [A + 1][L][V], caller numbering
+    double unscale[FLOW_PUSH_CHANNELS];    // 2^-k_c
+    int A, L, V;
+};
+int launch_flow_push(Ctx *c, const FlowArgs &a, const FlowPush &q);
+int launch_flow_push_finish(Ctx *c, const FlowPushFinish &q);
 void preload_flow_kernels();
 // what dots_flow_map checks the caller's tables against, downloaded once per context
 struct FlowHost {

@@ -8,6 +8,11 @@
 // successive intervals.  The triangle's vertices and hat gradients stay in registers until the particle crosses an edge.  The three
 // weights and rates live in named registers and are selected with conditions: an array indexed by the exit corner would go to scratch.
 // It runs once per solve: the yardstick is the download of mu and E it replaces, not a roofline.
+//
+// dots_flow_push is the same tracer (flow_body<PUSH = true>) which also deposits what the particle carries on the vertices of its
+// triangle at every layer, in 64-bit fixed point with integer atomics (flow.py: push_forward_host is the specification), and
+// k_flow_push_finish, which turns the sums into doubles in the caller's vertex numbering.  k_flow_map is the PUSH = false
+// instantiation: the code it had.
 #include "dots_dev.h"
 
 namespace dots {
@@ -41,7 +46,39 @@ __device__ __forceinline__ void flow_store_layer(const FlowArgs &a, int layer, i
     }
 }
 
-__global__ __launch_bounds__(BLOCK) void k_flow_map(FlowArgs a) {
+// The deposit of dots_flow_push (flow.py: push_forward_host is the specification): the particle's channels g[c] -- its mass, and its
+// mass times each attribute -- go to the three vertices of the triangle it is in, weighted with l0, l1, l2, as 64-bit integers
+// q = rint((g * l) * 2^k_c) added with integer atomics: integer addition is associative, so the sums are the same bits for every
+// arrival order.  |y| < 2^62 false (a NaN included) drops the contribution and counts it; a zero issues no atomic.
+__device__ __forceinline__ void flow_deposit_one(unsigned long long *row, double g, int k, double l, int &dropped) {
+    const double x = g * l;
+    const double y = ldexp(x, k);      // x * 2^k, correctly rounded: the product of the specification (2^k is a double for |k| <= 1000)
+    if (!(fabs(y) < 0x1p62)) { ++dropped; return; }
+    const long long q = __double2ll_rn(y);
+    if (q != 0) atomicAdd(row, (unsigned long long)q);
+}
+template <int A>
+__device__ __forceinline__ void flow_deposit(const FlowArgs &a, const FlowPush &q, int layer, const FlowTriangle &t, double l0, double l1, double l2,
+                                             const double (&g)[A + 1], int &dropped) {
+    int slot = layer;
+    if (q.L == 1) {      // (only the state after interval T; with all the layers L = T + 1 >= 2)
+        if (layer != a.T) return;
+        slot = 0;
+    }
+    const int64_t v0 = t.r0 >> a.tp_shift, v1 = t.r1 >> a.tp_shift, v2 = t.r2 >> a.tp_shift;
+#pragma unroll
+    for (int c = 0; c <= A; ++c) {
+        unsigned long long *row = q.acc + ((int64_t)c * q.L + slot) * q.V;
+        flow_deposit_one(row + v0, g[c], q.k[c], l0, dropped);
+        flow_deposit_one(row + v1, g[c], q.k[c], l1, dropped);
+        flow_deposit_one(row + v2, g[c], q.k[c], l2, dropped);
+    }
+}
+
+// the tracer; PUSH: it also deposits what the particle carries (A attributes: a template argument, so that the channels are
+// straight-line code on named registers) wherever it stores a layer
+template <bool PUSH, int A>
+__device__ __forceinline__ void flow_body(const FlowArgs &a, const FlowPush &q) {
     const int p = blockIdx.x * BLOCK + threadIdx.x;
     if (p >= a.P) return;
     int f = a.start_tri[p];
@@ -50,8 +87,20 @@ __global__ __launch_bounds__(BLOCK) void k_flow_map(FlowArgs a) {
     FlowTriangle t;
     flow_load_triangle(a, f, t);
     flow_store_layer(a, 0, p, f, l0, l1, l2);
+    double g[A + 1] = {};
+    int dropped = 0;
+    if (PUSH) {
+        g[0] = q.mass[p];
+#pragma unroll
+        for (int c = 1; c <= A; ++c) g[c] = g[0] * q.attr[(int64_t)(c - 1) * a.P + p];
+    }
     const int pitch = 1 << a.tp_shift;
-    for (int j = 0; j < a.T; ++j) {
+    // (PUSH: one more turn, which only deposits -- layer j at the head of turn j, so that the deposit is in the code once)
+    for (int j = 0; PUSH ? j <= a.T : j < a.T; ++j) {
+        if (PUSH) {
+            flow_deposit<A>(a, q, j, t, l0, l1, l2, g, dropped);
+            if (j == a.T) break;
+        }
         if (status == 0) {
             double rem = a.h;
             int crossings = 0;
@@ -107,6 +156,24 @@ __global__ __launch_bounds__(BLOCK) void k_flow_map(FlowArgs a) {
     a.o_status[p] = status;
     a.o_rested[p] = rested;
     a.o_cross[p] = total;
+    if (PUSH && dropped) atomicAdd(q.acc + (int64_t)(A + 1) * q.L * q.V, (unsigned long long)dropped);      // (the word behind the sums)
+}
+
+__global__ __launch_bounds__(BLOCK) void k_flow_map(FlowArgs a) { flow_body<false, 0>(a, FlowPush{}); }
+template <int A>
+__global__ __launch_bounds__(BLOCK) void k_flow_push(FlowArgs a, FlowPush q) { flow_body<true, A>(a, q); }
+
+// One lane per (channel, layer, caller vertex), the vertex fastest: the accumulator of the vertex's device row as a double, times
+// 2^-k_c; a layer of the output is one contiguous run in the caller's numbering, as in k_readout_mu.
+__global__ __launch_bounds__(BLOCK) void k_flow_push_finish(FlowPushFinish q) {
+    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const int64_t n_layer = (int64_t)q.L * q.V;
+    if (i >= n_layer * (q.A + 1)) return;
+    const int64_t cl = i / q.V;
+    const int v = (int)(i - cl * q.V);
+    const int c = (int)(i / n_layer);
+    const long long s = (long long)q.acc[cl * q.V + (q.inv ? q.inv[v] : v)];
+    q.out[i] = (double)s * q.unscale[c];
 }
 
 int launch_flow_map(Ctx *c, const FlowArgs &a) {
@@ -114,9 +181,24 @@ int launch_flow_map(Ctx *c, const FlowArgs &a) {
     DOTS_HIP(hipGetLastError());
     return 0;
 }
+int launch_flow_push(Ctx *c, const FlowArgs &a, const FlowPush &q) {
+    with_constant<0, 1, 2, 3, 4>(q.A, [&](auto A) {
+        hipLaunchKernelGGL(k_flow_push<A.value>, dim3((unsigned)((a.P + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, a, q);
+    });
+    DOTS_HIP(hipGetLastError());
+    return 0;
+}
+int launch_flow_push_finish(Ctx *c, const FlowPushFinish &q) {
+    const int64_t n = (int64_t)(q.A + 1) * q.L * q.V;
+    hipLaunchKernelGGL(k_flow_push_finish, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, q);
+    DOTS_HIP(hipGetLastError());
+    return 0;
+}
 void preload_flow_kernels() {
     hipFuncAttributes attr;
     (void)hipFuncGetAttributes(&attr, (const void *)k_flow_map);
+    (void)hipFuncGetAttributes(&attr, (const void *)k_flow_push<0>);
+    (void)hipFuncGetAttributes(&attr, (const void *)k_flow_push_finish);
     (void)hipGetLastError();
 }
 

@@ -8,7 +8,11 @@ and ``E``): where the mass at a point ends up, and where it is at time t.
 ``mu`` lives on the intervals and ``E`` on the nodes of the time grid (the staggering of the solver): in interval j a particle moves
 with ``0.5 * (E[j] + E[j + 1]) / rho``, ``rho`` the mean of ``mu[j]`` over the vertices of its triangle.  Starts at arbitrary points
 of the surface come from ``cascade.locate_device`` (triangle and weights of the closest point); ``vertex_starts`` puts one particle
-on every vertex.
+on every vertex, ``triangle_starts`` one on every sub-triangle of a regular subdivision.
+
+``push_forward_host`` is the specification of ``dots_flow_push``: what the particles carry (``start_masses``, attributes) summed onto
+the vertices in 64-bit fixed point with the exponents of ``push_scales`` -- integer sums, so the device returns the same bits in
+every order of arrival.
 """
 from __future__ import annotations
 
@@ -161,3 +165,144 @@ def flow_map_host(mu, E, triangles, hat, nbr, start_triangle, start_weights, flo
                 out["triangles_at"][j + 1, p], out["weights_at"][j + 1, p] = f, l
         out["triangle"][p], out["weights"][p], out["status"][p], out["rested"][p], out["crossings"][p] = f, l, status, rested, total
     return out
+
+
+# ---- push-forward: what the particles carry, summed onto the vertices ------------------------------------------------------------------
+
+PUSH_MAX_ATTRIBUTES = 4
+PUSH_EXPONENT_LIMIT = 1000
+
+
+def _carried(mass, attributes, n_particles):
+    """``g`` (1 + A, P): ``g[0] = m`` and ``g[c] = m * a[c - 1]``, one fp64 multiply each."""
+    m = np.asarray(mass, dtype=np.float64)
+    a = np.zeros((0, n_particles)) if attributes is None else np.asarray(attributes, dtype=np.float64)
+    if m.shape != (n_particles,) or a.ndim != 2 or a.shape[1] != n_particles or a.shape[0] > PUSH_MAX_ATTRIBUTES:
+        raise ValueError(f"push: mass ({n_particles},) and attributes (A <= {PUSH_MAX_ATTRIBUTES}, {n_particles}) expected, got {m.shape} and {a.shape}")
+    with np.errstate(over="ignore", invalid="ignore"):
+        g = np.concatenate([m[None, :], m[None, :] * a], axis=0)
+    if not np.all(np.isfinite(g)):
+        raise ValueError("push: a mass, or a mass times an attribute, that is not finite")
+    return g
+
+
+def push_scales(mass, attributes, start_weights):
+    """The exponents ``k_c`` (1 + A,) int32 of ``push_forward_host`` / ``dots_flow_push`` for these particles:
+    ``B_c = fsum_p |g[p][c]| * max(1.0, (w0 + w1) + w2)``, ``e_c`` the least integer with ``2^e_c >= B_c``,
+    ``k_c = clip(60 - e_c, -1000, 1000)``, and ``k_c = 0`` where ``B_c = 0``.  A vertex sum then stays below 2^60 as long as the weight
+    sums stay below 4 times their start (rates sum to zero and the clamps only lift rounding negatives: they do not grow past that
+    in practice)."""
+    import math
+
+    w = np.asarray(start_weights, dtype=np.float64)
+    g = _carried(mass, attributes, w.shape[0])
+    wsum = np.maximum(1.0, (w[:, 0] + w[:, 1]) + w[:, 2])
+    out = np.zeros(g.shape[0], dtype=np.int32)
+    for c in range(g.shape[0]):
+        B = math.fsum((np.abs(g[c]) * wsum).tolist())
+        if B == 0.0:
+            continue
+        if not math.isfinite(B):
+            raise ValueError("push_scales: the bound of a channel is not finite")
+        frac, e = math.frexp(B)      # B = frac * 2^e, 0.5 <= frac < 1
+        if frac == 0.5:
+            e -= 1
+        out[c] = min(max(60 - e, -PUSH_EXPONENT_LIMIT), PUSH_EXPONENT_LIMIT)
+    return out
+
+
+def push_forward_host(result_with_trajectory, triangles, n_vertices, mass, attributes, exponents, layers="end"):
+    """The specification of ``dots_flow_push``: what the particles of a traced map carry, summed onto the vertices.
+
+    Channels are ``c = 0`` (mass) and ``c = 1 .. A`` (attributes), with ``0 <= A <= 4``.
+
+    - Particle p carries ``g[p][0] = m[p]`` and ``g[p][c] = m[p] * a[p][c-1]``, one fp64 multiply each.
+    - Every ``g`` must be finite.  Signs are free.
+
+    Layers:
+
+    - ``layers="end"`` gives ``L = 1``: the state after interval T.
+    - ``layers="all"`` gives ``L = T + 1``: layer 0 the starts, layer l the state after l intervals.  These are the layers of
+      ``triangles_at``.
+
+    At each layer, for each corner ``k = 0, 1, 2`` of the triangle ``f`` the particle is in and each channel c, in this order of
+    operations:
+
+    1. ``x = g[p][c] * l_k`` and ``y = x * scale_c``, where ``scale_c = ldexp(1.0, k_c)`` and ``k_c`` is an int32 the caller passes.
+    2. If ``|y| < 2^62`` is false (this includes NaN), the contribution is dropped and counted in one ``dropped`` counter.
+    3. Otherwise ``q = rint(y)``, round to nearest even, as int64.  ``acc[c][layer][tri[f][k]] += q`` in two's complement.
+    4. A ``q`` of zero issues no atomic.  Vertex starts have two zero weights.
+
+    Stopped (``status 1``) and resting particles keep depositing where they are.  Mass is not lost.
+
+    The result is ``float(acc) * ldexp(1.0, -k_c)``, with int64 -> fp64 rounding to nearest even.  Output arrays are in the caller's
+    vertex numbering: ``mass_at [L][V]`` and ``attr_at [A][L][V]``.
+
+    ``result_with_trajectory``: the dict of ``flow_map_host(..., trajectory=True)`` (its ``triangles_at`` and ``weights_at`` are used);
+    ``attributes``: None or (A, P).  The sums are formed in Python integers from the two halves of every ``q`` (each half summed in
+    int64, which cannot overflow below 2^31 contributions), and ``|sum| < 2^63`` is asserted.  Returns ``{"mass" (L, V), "attributes"
+    (A, L, V) or None, "dropped", "integers" (1 + A, L, V) int64: the sums themselves, "issued": the non-zero q}``."""
+    import math
+
+    tri_at = np.asarray(result_with_trajectory["triangles_at"]).astype(np.int64)
+    w_at = np.asarray(result_with_trajectory["weights_at"], dtype=np.float64)
+    if layers not in ("end", "all"):
+        raise ValueError("push_forward_host: layers must be 'end' or 'all'")
+    if layers == "end":
+        tri_at, w_at = tri_at[-1:], w_at[-1:]
+    L, P = tri_at.shape
+    V = int(n_vertices)
+    g = _carried(mass, attributes, P)
+    C = g.shape[0]
+    k = np.asarray(exponents).astype(np.int64).reshape(-1)
+    if k.shape != (C,) or np.any(np.abs(k) > PUSH_EXPONENT_LIMIT):
+        raise ValueError(f"push_forward_host: {C} exponents within -{PUSH_EXPONENT_LIMIT} .. {PUSH_EXPONENT_LIMIT} expected")
+    vert = np.asarray(triangles).astype(np.int64)[tri_at]      # (L, P, 3)
+    hi_sum, lo_sum = np.zeros((C, L, V), dtype=np.int64), np.zeros((C, L, V), dtype=np.int64)
+    dropped = issued = 0
+    index = (np.arange(L, dtype=np.int64)[:, None, None] * V + vert).reshape(-1)
+    for c in range(C):
+        with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+            x = g[c][None, :, None] * w_at
+            y = x * math.ldexp(1.0, int(k[c]))
+            keep = np.abs(y) < 2.0 ** 62      # (False for a NaN)
+        dropped += int(keep.size - np.count_nonzero(keep))
+        q = np.rint(np.where(keep, y, 0.0)).astype(np.int64)      # (to nearest even; exact: |y| < 2^62)
+        issued += int(np.count_nonzero(q))
+        np.add.at(hi_sum[c].reshape(-1), index, (q >> 32).reshape(-1))
+        np.add.at(lo_sum[c].reshape(-1), index, (q & 0xFFFFFFFF).reshape(-1))
+    acc = hi_sum.astype(object) * (1 << 32) + lo_sum.astype(object)      # Python integers
+    assert all(abs(s) < 1 << 63 for s in acc.reshape(-1)), "push_forward_host: a sum left the 64-bit range"
+    out = np.empty((C, L, V))
+    for c in range(C):
+        out[c] = acc[c].astype(np.float64) * math.ldexp(1.0, -int(k[c]))      # (float(int) rounds to nearest even)
+    return {"mass": out[0], "attributes": out[1:] if C > 1 else None, "dropped": dropped, "integers": acc.astype(np.int64), "issued": issued}
+
+
+def triangle_starts(triangles, level=1):
+    """``(triangle (F * level^2,) int32, weights (F * level^2, 3))``: every triangle cut into ``level^2`` congruent sub-triangles, one
+    particle at the centroid of each (triangle by triangle; the upright sub-triangles of a triangle first, then the inverted ones)."""
+    n = int(level)
+    if n < 1:
+        raise ValueError("triangle_starts: level >= 1 expected")
+    F = np.asarray(triangles).shape[0]
+    up = [(3 * i + 1, 3 * j + 1) for i in range(n) for j in range(n - i)]
+    down = [(3 * i + 2, 3 * j + 2) for i in range(n - 1) for j in range(n - 1 - i)]
+    ab = np.array(up + down, dtype=np.int64)
+    w = np.stack([ab[:, 0], ab[:, 1], 3 * n - ab[:, 0] - ab[:, 1]], axis=1) / float(3 * n)
+    return np.repeat(np.arange(F, dtype=np.int32), n * n), np.ascontiguousarray(np.tile(w, (F, 1)))
+
+
+def start_masses(mu0, area_vertices, area_triangles, triangles, start_triangle, start_weights, level=None):
+    """The mass of ``mu0`` every start carries.  ``level`` (``triangle_starts``): ``m_p = (area_f / level^2) sum_k w_k mu0[v_k] /
+    (area_vertices[v_k] / 3)`` -- the density of ``mu0``, linear on the triangle, at the particle, times the area of its sub-triangle:
+    the centroid rule is exact for linear functions, so the masses sum to ``sum(mu0)``.  ``level=None`` (``vertex_starts``):
+    ``m_v = mu0[v]`` of the corner with the largest weight."""
+    m0 = np.asarray(mu0, dtype=np.float64)
+    t = np.asarray(triangles).astype(np.int64)[np.asarray(start_triangle).astype(np.int64)]      # (P, 3)
+    w = np.asarray(start_weights, dtype=np.float64)
+    if level is None:
+        return m0[t[np.arange(t.shape[0]), np.argmax(w, axis=1)]]
+    rho = m0 / (np.asarray(area_vertices, dtype=np.float64) / 3.0)
+    area = np.asarray(area_triangles, dtype=np.float64)[np.asarray(start_triangle).astype(np.int64)]
+    return (area / float(int(level) ** 2)) * ((w[:, 0] * rho[t[:, 0]] + w[:, 1] * rho[t[:, 1]]) + w[:, 2] * rho[t[:, 2]])

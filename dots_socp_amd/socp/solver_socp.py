@@ -64,7 +64,47 @@ def check_time_nodes(n_time, lap_solver="modal_direct", time_slab=None, pcg_wind
             raise ValueError(f"lap_solver='modal_pcg' needs n_time + 1 <= {MODAL_PCG_MAX_NODES} (got {nodes}); use lap_solver='modal_direct'")
 
 
-FLOW_MAP_KEYS = ("starts", "floor", "max_crossings", "trajectory")
+FLOW_MAP_KEYS = ("starts", "floor", "max_crossings", "trajectory", "push")
+FLOW_PUSH_KEYS = ("mass", "attributes", "layers")
+
+
+def _check_flow_starts(starts):
+    """``(kind, level)`` of a named choice of starts -- "vertices", "triangles", ("triangles", level) -- or None for ``(triangle, weights)``."""
+    if isinstance(starts, str):
+        if starts not in ("vertices", "triangles"):
+            raise ValueError("flow_map: starts must be 'vertices', 'triangles', ('triangles', level) or (triangle, weights)")
+        return starts, (1 if starts == "triangles" else None)
+    if not isinstance(starts, (tuple, list)) or len(starts) != 2:
+        raise ValueError("flow_map: starts must be 'vertices', 'triangles', ('triangles', level) or (triangle, weights)")
+    if isinstance(starts[0], str):
+        level = starts[1]
+        if starts[0] != "triangles" or isinstance(level, bool) or not isinstance(level, (int, np.integer)) or level < 1:
+            raise ValueError("flow_map: starts by name with a level must be ('triangles', level) with an integer level >= 1")
+        return "triangles", int(level)
+    return None
+
+
+def _check_flow_push(push, starts):
+    """``None``, or the request as a dict with all of FLOW_PUSH_KEYS (``True``: the masses of mu0 at the starts, the last layer)."""
+    if push is None or push is False:
+        return None
+    if push is True:
+        push = {}
+    if not isinstance(push, dict):
+        raise ValueError(f"flow_map: push must be None, True or a dict with any of {list(FLOW_PUSH_KEYS)}")
+    unknown = set(push) - set(FLOW_PUSH_KEYS)
+    if unknown:
+        raise ValueError(f"flow_map: push: unknown option(s) {sorted(unknown)}; known: {list(FLOW_PUSH_KEYS)}")
+    out = {"mass": push.get("mass"), "attributes": push.get("attributes"), "layers": push.get("layers", "end")}
+    if not isinstance(out["layers"], str) or out["layers"] not in ("end", "all"):
+        raise ValueError("flow_map: push: layers must be 'end' or 'all'")
+    if out["attributes"] is not None:
+        a = np.asarray(out["attributes"])
+        if a.ndim != 2 or not 0 <= a.shape[0] <= 4:
+            raise ValueError(f"flow_map: push: attributes (A, P) with A <= 4 expected, got {a.shape}")
+    if out["mass"] is None and _check_flow_starts(starts) is None:
+        raise ValueError("flow_map: push: starts given as (triangle, weights) need a mass per particle")
+    return out
 
 
 def check_flow_map(flow_map, time_slab=None):
@@ -79,6 +119,9 @@ def check_flow_map(flow_map, time_slab=None):
     unknown = set(flow_map) - set(FLOW_MAP_KEYS)
     if unknown:
         raise ValueError(f"flow_map: unknown option(s) {sorted(unknown)}; known: {list(FLOW_MAP_KEYS)}")
+    if "starts" in flow_map:
+        _check_flow_starts(flow_map["starts"])
+    _check_flow_push(flow_map.get("push"), flow_map.get("starts", "vertices"))
     return dict(flow_map)
 
 
@@ -635,40 +678,61 @@ class AlmSolver:
         mu, E, info = self._read_out(self.r * self.dual_scale, w_vertex, w_triangle, centred, mu0, mu1, sums=True)
         return {"mu": mu, "E": E}, info
 
-    def flow_map(self, starts="vertices", floor=None, max_crossings=16, trajectory=False):
+    def flow_map(self, starts="vertices", floor=None, max_crossings=16, trajectory=False, push=None):
         """The transport map of the current iterate, traced on the device (DeviceProblem.flow_map; flow.flow_map_host is the
         specification): where the mass at a point ends up, and with ``trajectory`` where it is after every interval.
-        ``starts``: "vertices" (one particle on every vertex: flow.vertex_starts) or ``(triangle (P,), weights (P, 3))`` in the
-        numbering of ``geometry`` -- arbitrary points of the surface come from ``cascade.locate_device``, which returns exactly
+        ``starts``: "vertices" (one particle on every vertex: flow.vertex_starts), "triangles" or ``("triangles", level)`` (one on
+        every one of the ``level^2`` sub-triangles of every triangle: flow.triangle_starts) or ``(triangle (P,), weights (P, 3))`` in
+        the numbering of ``geometry`` -- arbitrary points of the surface come from ``cascade.locate_device``, which returns exactly
         these two arrays.  ``floor``: densities up to it carry no velocity, in the units of the recovered ``mu`` (default
         ``1e-3 * max(mu0 / (area_vertices / 3))``); it is divided by the recovery factor before the call, since the device holds
         the iterate.  Returns the dict of ``flow_map_host`` plus ``positions`` (P, 3), and with ``trajectory`` ``positions_at``
-        (T + 1, P, 3); ``ms`` and ``bytes``: device milliseconds of the launch and bytes copied to the host."""
-        from .. import flow
+        (T + 1, P, 3); ``ms`` and ``bytes``: device milliseconds of the launch and bytes copied to the host.
+        ``push``: None, ``True`` or ``{"mass" (P,), "attributes" (A <= 4, P), "layers": "end" | "all"}``: what the particles carry is
+        summed onto the vertices on the device (DeviceProblem.flow_push; flow.push_forward_host is the specification).  The
+        default mass is that of ``mu0`` at the named starts (flow.start_masses), the default layer the last.  The result gains
+        ``pushed``: ``{"mass" (L, V), "attributes" (A, L, V) or None, "dropped", "exponents" (flow.push_scales), "rested_mass" and
+        "stopped_mass" (the mass of the particles that rested / stopped), "to_mu1":
+        evaluate.compare_with_exact_transportation(mass[-1], mu1, geometry)}``."""
+        from .. import evaluate, flow
+        from . import _geometry_with_areas
 
         if self.dev.slab:
             raise ValueError("flow_map is not available on time slabs: the particles are traced on one GPU, which holds every time node")
+        push = _check_flow_push(push, starts)
         vertices, triangles = np.asarray(self.geometry["vertices"], dtype=np.float64), np.asarray(self.geometry["triangles"])
-        if isinstance(starts, str):
-            if starts != "vertices":
-                raise ValueError("flow_map: starts must be 'vertices' or (triangle, weights)")
+        named = _check_flow_starts(starts)
+        if named is None:
+            start_triangle, start_weights = starts
+        elif named[0] == "vertices":
             start_triangle, start_weights = flow.vertex_starts(triangles, vertices.shape[0])
         else:
-            start_triangle, start_weights = starts
+            start_triangle, start_weights = flow.triangle_starts(triangles, named[1])
+        g = _geometry_with_areas(self.geometry) if floor is None or push is not None else None
         if floor is None:
-            from . import _geometry_with_areas
-
-            g = _geometry_with_areas(self.geometry)
             floor = 1e-3 * float(np.max(np.asarray(g["mu0"], dtype=np.float64) / (np.asarray(g["area_vertices"], dtype=np.float64) / 3.0)))
         if getattr(self, "_neighbours", None) is None:
             self._neighbours = flow.triangle_neighbours(triangles)
         dev = self.dev
-        out = dev.flow_map(start_triangle, start_weights, self._neighbours, float(floor) / (self.r * self.dual_scale),
-                           max_crossings=max_crossings, trajectory=trajectory)
+        if push is None:
+            out = dev.flow_map(start_triangle, start_weights, self._neighbours, float(floor) / (self.r * self.dual_scale),
+                               max_crossings=max_crossings, trajectory=trajectory)
+            out["ms"], out["bytes"] = dev.flow_map_ms, dev.flow_map_bytes
+        else:
+            mass = push["mass"]
+            if mass is None:
+                mass = flow.start_masses(g["mu0"], g["area_vertices"], g["area_triangles"], triangles, start_triangle, start_weights, named[1])
+            mass = np.asarray(mass, dtype=np.float64)
+            out = dev.flow_push(start_triangle, start_weights, self._neighbours, float(floor) / (self.r * self.dual_scale), mass,
+                                attributes=push["attributes"], layers=push["layers"], max_crossings=max_crossings, trajectory=trajectory)
+            out["ms"], out["bytes"] = dev.flow_push_ms, dev.flow_push_bytes
+            pushed = {"mass": out.pop("mass_at"), "attributes": out.pop("attr_at"), "dropped": out.pop("dropped"), "exponents": out.pop("exponents"),
+                      "rested_mass": float(np.sum(mass[out["rested"] > 0])), "stopped_mass": float(np.sum(mass[out["status"] == 1]))}
+            pushed["to_mu1"] = evaluate.compare_with_exact_transportation(pushed["mass"][-1], np.asarray(g["mu1"], dtype=np.float64), g)
+            out["pushed"] = pushed
         out["positions"] = flow.positions(vertices, triangles, out["triangle"], out["weights"])
         if trajectory:
             out["positions_at"] = flow.positions(vertices, triangles, out["triangles_at"], out["weights_at"])
-        out["ms"], out["bytes"] = dev.flow_map_ms, dev.flow_map_bytes
         return out
 
     def finalize(self, download=True, outputs=None, read_out=None, flow_map=None):

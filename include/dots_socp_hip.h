@@ -701,6 +701,41 @@ typedef struct dots_flow_map_desc {
 } dots_flow_map_desc;
 int dots_flow_map(dots_ctx *ctx, const dots_flow_map_desc *desc);
 
+/* dots_flow_push: the trace of dots_flow_map, and what the particles carry summed onto the vertices on the device -- the push-forward
+ * of a mass (compare its last layer with mu1), the Lagrangian interpolation at every time node, an attribute carried along.
+ * dots_socp_amd/flow.py: push_forward_host is the specification, and mass_at / attr_at / dropped equal it bit for bit.
+ * Channels: c = 0 the mass, c = 1 .. A the attributes.  Particle p carries g[p][0] = mass[p] and g[p][c] = mass[p] *
+ * attributes[c - 1][p]; every g must be finite.  Layers: all_layers = 0 gives L = 1, the state after interval T; otherwise
+ * L = T + 1, the layers of triangles_at.  At each layer, for each corner k of the triangle f the particle is in and each channel:
+ * x = g * l_k, y = x * 2^k_c with k_c = scale_exponent[c]; if |y| < 2^62 is false (a NaN included) the contribution is dropped and
+ * counted in `dropped`; otherwise q = rint(y) (to nearest even) is added to a 64-bit integer of (c, layer, vertex k of f) in two's
+ * complement -- integer addition is associative: the sums are the same bits for every order of arrival, order of the particles and
+ * launch shape; two calls with the same exponents add exactly.  Stopped and resting particles keep depositing where they are.  The
+ * result is (double)sum * 2^-k_c in the CALLER's vertex numbering.  The caller chooses the exponents (flow.push_scales:
+ * 2^(60 - k_c) >= B_c = sum over p of |g[p][c]| max(1, (w0 + w1) + w2) of the start weights); the call refuses an exponent outside
+ * -1000 .. 1000 and one with B_c 2^k_c > 2^61 in its own summation.
+ * `map` is checked as dots_flow_map checks it, except that its five per-particle outputs may be NULL (those given are filled, and
+ * equal dots_flow_map's); the contract of dots_flow_map holds (pending penalty division, z_mid, state left alone, every Laplacian
+ * solver and n_time + 1 <= 1024, batch members on their own stream).  The accumulators ((1 + A) L V 64-bit words) are allocated and
+ * zeroed per call: DOTS_ERR_MEMORY when they do not fit, the context stays usable.  Three launches: the zeroing, the trace with
+ * its deposits (one no-return 64-bit integer atomic per non-zero q), the conversion; `ms` (and map.ms) cover them.  The output
+ * bytes are counted in dots_debug_counter 9.
+ * DOTS_ERR_ARGUMENT (nothing launched): what dots_flow_map refuses; NULL mass, scale_exponent or mass_at; n_attributes outside
+ * 0 .. 4; NULL attributes or attr_at with n_attributes > 0; a g that is not finite; an exponent as above.  DOTS_ERR_STATE: a time slab. */
+typedef struct dots_flow_push_desc {
+    dots_flow_map_desc map;         /* the particles and the trace; triangle, weights, status, rested, crossings may be NULL */
+    const double *mass;             /* host [n_particles]                                                               */
+    int32_t n_attributes;           /* A, 0 .. 4                                                                        */
+    int32_t all_layers;             /* 0: L = 1, the state after interval T; else L = T + 1                             */
+    const double *attributes;       /* host [A][n_particles], NULL iff A = 0                                            */
+    const int32_t *scale_exponent;  /* host [1 + A]: k_c, -1000 .. 1000                                                 */
+    double *mass_at;                /* host out [L][V]                                                                  */
+    double *attr_at;                /* host out [A][L][V], NULL iff A = 0                                               */
+    int64_t *dropped;               /* NULL, or out: contributions that were dropped                                    */
+    double *ms;                     /* NULL, or out: device milliseconds of the three launches                          */
+} dots_flow_push_desc;
+int dots_flow_push(dots_ctx *ctx, const dots_flow_push_desc *desc);
+
 /* ---- levels of a cascade in space from ONE mesh: coarsen on the host, locate on the device ------------------------------------
  * dots_coarsen: half-edge-collapse decimation of the mesh (xyz [V][3], tri [F][3]) towards `n_target` vertices, host only (no
  * device work; dots_socp_amd/meshes.py: coarsen(backend="python") is the specification and states the rules; both return the same
@@ -766,7 +801,7 @@ int dots_bench_kernel(dots_ctx *ctx, int which, int reps, double *ms_per_launch,
  * batched solve (dots_laplacian_solve_many, dots_step_many, dots_bench_many) enqueued, read on the batch's first context, 8 of those, the
  * launches that took fewer right-hand sides than their chunk of DOTS_FRONT_NR problems held because NR regions of LDS would not fit or
  * a workgroup of 1024 threads takes fewer (the launch was split), 9 bytes this context has copied device -> host through dots_download,
- * dots_readout and dots_flow_map since it was created (the layer sums of dots_readout are written by the device itself and not copied), 10 device
+ * dots_readout, dots_flow_map and dots_flow_push since it was created (the layer sums of dots_readout are written by the device itself and not copied), 10 device
  * allocations this context holds for its factor (0 without one, also after a dots_front_setup that failed), 11 the launches the
  * last multigrid V-cycle enqueued on this context took, as a bit mask: 1 restriction with a workgroup per coarse row, 2 restriction
  * with a thread per entry, 4 coarsest solve with a workgroup per row, 8 coarsest solve with a thread per entry, 16 the one-launch
