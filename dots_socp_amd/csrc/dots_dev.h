@@ -417,7 +417,12 @@ struct FlowArgs {
     int *tri_at;                 // [T + 1][P], or null
     double *w_at;                // [T + 1][P][3], or null
     double floor, h;
-    int P, T, tp_shift, max_crossings;
+    int P, T, tp_shift, max_crossings;      // (dots_flow_trace: T is the number of intervals traversed, h still 1 / n_time)
+};
+// dots_flow_trace: turn i = 0 .. T - 1 takes the interval j0 + i dj; dj = -1 traces backward (the velocity negated)
+struct FlowSpan {
+    double *action;              // [P] sum of best |u|^2 over the steps, or null
+    int j0, dj;
 };
 // neighbour g, and the corners of g that name the vertices of corners (k + 1) % 3 and (k + 2) % 3 of the triangle the entry belongs to
 constexpr int FLOW_MAX_TRIANGLES = 1 << 27;
@@ -431,7 +436,7 @@ struct FlowPush {
     const double *mass;          // [P]
     const double *attr;          // [A][P]
     int k[FLOW_PUSH_CHANNELS];             // the exponents k_c
-    int A, L, V;                 // L = T + 1 (all the layers), or 1 (the state after interval T)
+    int A, L, V;                 // L = T + 1 (all the layers), or 1 (the state after the last interval)
 };
 struct FlowPushFinish {
     const unsigned long long *acc;
@@ -442,6 +447,8 @@ struct FlowPushFinish {
 };
 int launch_flow_push(Ctx *c, const FlowArgs &a, const FlowPush &q);
 int launch_flow_push_finish(Ctx *c, const FlowPushFinish &q);
+int launch_flow_trace(Ctx *c, const FlowArgs &a, const FlowSpan &s);
+int launch_flow_trace_push(Ctx *c, const FlowArgs &a, const FlowPush &q, const FlowSpan &s);
 void preload_flow_kernels();
 // what dots_flow_map checks the caller's tables against, downloaded once per context
 struct FlowHost {

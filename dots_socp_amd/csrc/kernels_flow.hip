@@ -13,6 +13,12 @@
 // triangle at every layer, in 64-bit fixed point with integer atomics (flow.py: push_forward_host is the specification), and
 // k_flow_push_finish, which turns the sums into doubles in the caller's vertex numbering.  k_flow_map is the PUSH = false
 // instantiation: the code it had.
+//
+// dots_flow_trace is the same tracer once more (flow_body<PUSH, A, SPAN = true>): the a.T intervals j = j0 + i dj, i = 0 .. a.T - 1,
+// between two time nodes, forward (dj = 1) or backward (dj = -1: the velocity negated), and the kinetic action sum of best |u|^2
+// along the path.  Direction and start are run-time values of FlowSpan: a sign flip and an add per turn beside six fp64 divisions;
+// a template flag would double the instantiations for nothing (registers: DESIGN.md section 9).  The SPAN = false instantiations
+// are the code they were.
 #include "dots_dev.h"
 
 namespace dots {
@@ -61,7 +67,7 @@ template <int A>
 __device__ __forceinline__ void flow_deposit(const FlowArgs &a, const FlowPush &q, int layer, const FlowTriangle &t, double l0, double l1, double l2,
                                              const double (&g)[A + 1], int &dropped) {
     int slot = layer;
-    if (q.L == 1) {      // (only the state after interval T; with all the layers L = T + 1 >= 2)
+    if (q.L == 1) {      // (only the state after the last turn, a.T; with all the layers L = a.T + 1 >= 2)
         if (layer != a.T) return;
         slot = 0;
     }
@@ -77,8 +83,8 @@ __device__ __forceinline__ void flow_deposit(const FlowArgs &a, const FlowPush &
 
 // the tracer; PUSH: it also deposits what the particle carries (A attributes: a template argument, so that the channels are
 // straight-line code on named registers) wherever it stores a layer
-template <bool PUSH, int A>
-__device__ __forceinline__ void flow_body(const FlowArgs &a, const FlowPush &q) {
+template <bool PUSH, int A, bool SPAN = false>
+__device__ __forceinline__ void flow_body(const FlowArgs &a, const FlowPush &q, const FlowSpan &span = FlowSpan{}) {
     const int p = blockIdx.x * BLOCK + threadIdx.x;
     if (p >= a.P) return;
     int f = a.start_tri[p];
@@ -95,12 +101,14 @@ __device__ __forceinline__ void flow_body(const FlowArgs &a, const FlowPush &q) 
         for (int c = 1; c <= A; ++c) g[c] = g[0] * q.attr[(int64_t)(c - 1) * a.P + p];
     }
     const int pitch = 1 << a.tp_shift;
-    // (PUSH: one more turn, which only deposits -- layer j at the head of turn j, so that the deposit is in the code once)
-    for (int j = 0; PUSH ? j <= a.T : j < a.T; ++j) {
+    double act = 0.0;      // (SPAN: the action so far)
+    // (PUSH: one more turn, which only deposits -- layer i at the head of turn i, so that the deposit is in the code once)
+    for (int i = 0; PUSH ? i <= a.T : i < a.T; ++i) {
         if (PUSH) {
-            flow_deposit<A>(a, q, j, t, l0, l1, l2, g, dropped);
-            if (j == a.T) break;
+            flow_deposit<A>(a, q, i, t, l0, l1, l2, g, dropped);
+            if (i == a.T) break;
         }
+        const int j = SPAN ? span.j0 + i * span.dj : i;      // the interval of turn i (SPAN: a.T is the number of intervals traversed)
         if (status == 0) {
             double rem = a.h;
             int crossings = 0;
@@ -114,6 +122,7 @@ __device__ __forceinline__ void flow_body(const FlowArgs &a, const FlowPush &q) 
                     u0 = (0.5 * (e[0] + e[1])) / rho;
                     u1 = (0.5 * (e[pitch] + e[pitch + 1])) / rho;
                     u2 = (0.5 * (e[2 * pitch] + e[2 * pitch + 1])) / rho;
+                    if (SPAN && span.dj < 0) { u0 = -u0; u1 = -u1; u2 = -u2; }      // (backward; a floored triangle keeps +0.0)
                 }
                 // time derivatives of the weights
                 const double q0 = (t.g00 * u0 + t.g01 * u1) + t.g02 * u2;
@@ -125,6 +134,7 @@ __device__ __forceinline__ void flow_body(const FlowArgs &a, const FlowPush &q) 
                 if (q0 < 0.0) { const double s = l0 / (-q0); if (s < best) { best = s; kmin = 0; } }
                 if (q1 < 0.0) { const double s = l1 / (-q1); if (s < best) { best = s; kmin = 1; } }
                 if (q2 < 0.0) { const double s = l2 / (-q2); if (s < best) { best = s; kmin = 2; } }
+                if (SPAN) act = act + best * ((u0 * u0 + u1 * u1) + u2 * u2);      // (a step that ends in a stop or a rest has spent best)
                 const double n0 = flow_clamp0(l0 + best * q0), n1 = flow_clamp0(l1 + best * q1), n2 = flow_clamp0(l2 + best * q2);
                 l0 = kmin == 0 ? 0.0 : n0;
                 l1 = kmin == 1 ? 0.0 : n1;
@@ -147,8 +157,9 @@ __device__ __forceinline__ void flow_body(const FlowArgs &a, const FlowPush &q) 
                 flow_load_triangle(a, f, t);
             }
         }
-        flow_store_layer(a, j + 1, p, f, l0, l1, l2);
+        flow_store_layer(a, i + 1, p, f, l0, l1, l2);
     }
+    if (SPAN && span.action) span.action[p] = act;
     a.o_tri[p] = a.perm_f ? a.perm_f[f] : f;
     a.o_w[(int64_t)p * 3] = l0;
     a.o_w[(int64_t)p * 3 + 1] = l1;
@@ -162,6 +173,9 @@ __device__ __forceinline__ void flow_body(const FlowArgs &a, const FlowPush &q) 
 __global__ __launch_bounds__(BLOCK) void k_flow_map(FlowArgs a) { flow_body<false, 0>(a, FlowPush{}); }
 template <int A>
 __global__ __launch_bounds__(BLOCK) void k_flow_push(FlowArgs a, FlowPush q) { flow_body<true, A>(a, q); }
+__global__ __launch_bounds__(BLOCK) void k_flow_trace(FlowArgs a, FlowSpan s) { flow_body<false, 0, true>(a, FlowPush{}, s); }
+template <int A>
+__global__ __launch_bounds__(BLOCK) void k_flow_trace_push(FlowArgs a, FlowPush q, FlowSpan s) { flow_body<true, A, true>(a, q, s); }
 
 // One lane per (channel, layer, caller vertex), the vertex fastest: the accumulator of the vertex's device row as a double, times
 // 2^-k_c; a layer of the output is one contiguous run in the caller's numbering, as in k_readout_mu.
@@ -188,6 +202,18 @@ int launch_flow_push(Ctx *c, const FlowArgs &a, const FlowPush &q) {
     DOTS_HIP(hipGetLastError());
     return 0;
 }
+int launch_flow_trace(Ctx *c, const FlowArgs &a, const FlowSpan &s) {
+    hipLaunchKernelGGL(k_flow_trace, dim3((unsigned)((a.P + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, a, s);
+    DOTS_HIP(hipGetLastError());
+    return 0;
+}
+int launch_flow_trace_push(Ctx *c, const FlowArgs &a, const FlowPush &q, const FlowSpan &s) {
+    with_constant<0, 1, 2, 3, 4>(q.A, [&](auto A) {
+        hipLaunchKernelGGL(k_flow_trace_push<A.value>, dim3((unsigned)((a.P + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, a, q, s);
+    });
+    DOTS_HIP(hipGetLastError());
+    return 0;
+}
 int launch_flow_push_finish(Ctx *c, const FlowPushFinish &q) {
     const int64_t n = (int64_t)(q.A + 1) * q.L * q.V;
     hipLaunchKernelGGL(k_flow_push_finish, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, q);
@@ -199,6 +225,8 @@ void preload_flow_kernels() {
     (void)hipFuncGetAttributes(&attr, (const void *)k_flow_map);
     (void)hipFuncGetAttributes(&attr, (const void *)k_flow_push<0>);
     (void)hipFuncGetAttributes(&attr, (const void *)k_flow_push_finish);
+    (void)hipFuncGetAttributes(&attr, (const void *)k_flow_trace);
+    (void)hipFuncGetAttributes(&attr, (const void *)k_flow_trace_push<0>);
     (void)hipGetLastError();
 }
 

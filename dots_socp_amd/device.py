@@ -298,6 +298,70 @@ class DeviceProblem:
         out["dropped"], out["exponents"] = int(dropped.value), k
         return out
 
+    def flow_trace(self, start_triangle, start_weights, neighbours, floor, span, action=False, mass=None, attributes=None, exponents=None,
+                   layers="end", max_crossings=16, trajectory=False):
+        """``flow_map`` between the time nodes ``span = (node_from, node_to)``, backward where ``node_to < node_from`` (dots_flow_trace;
+        ``flow.flow_map_host(..., span=span, action=action)`` on the downloaded ``mu`` and ``E`` is the specification and returns the
+        same bits).  ``action``: the result gains ``"action"`` (P,).  ``mass`` (P,): also the deposits of ``flow_push`` on the layers of
+        this trace (``attributes``, ``exponents``, ``layers`` as there; ``"end"`` is the state at ``node_to``), and the result gains what
+        ``flow_push`` adds.  The trajectory has ``|node_to - node_from| + 1`` layers.  ``self.flow_trace_ms`` / ``self.flow_trace_bytes``:
+        device milliseconds of the launches and the bytes copied to the host by the last call."""
+        from . import flow
+
+        if self.slab:
+            raise ValueError("flow_trace: not available on time slabs")
+        node_from, node_to = flow.check_span(span, self.T, "flow_trace")
+        if layers not in ("end", "all"):
+            raise ValueError("flow_trace: layers must be 'end' or 'all'")
+        tri = np.ascontiguousarray(start_triangle, dtype=np.int32)
+        w = np.ascontiguousarray(start_weights, dtype=np.float64)
+        nbr = np.ascontiguousarray(neighbours, dtype=np.int32)
+        if tri.ndim != 1 or w.shape != (tri.shape[0], 3):
+            raise ValueError(f"flow_trace: start_triangle (P,) and start_weights (P, 3) expected, got {tri.shape} and {w.shape}")
+        if nbr.shape != (self.F, 3):
+            raise ValueError(f"flow_trace: neighbours must have shape ({self.F}, 3), got {nbr.shape}")
+        P, n = tri.shape[0], abs(node_to - node_from)
+        out = {"triangle": np.empty(P, dtype=np.int32), "weights": np.empty((P, 3)), "status": np.empty(P, dtype=np.int32),
+               "rested": np.empty(P, dtype=np.int32), "crossings": np.empty(P, dtype=np.int32)}
+        if trajectory:
+            out["triangles_at"] = np.empty((n + 1, P), dtype=np.int32)
+            out["weights_at"] = np.empty((n + 1, P, 3))
+        if action:
+            out["action"] = np.empty(P)
+        ms, dropped = C.c_double(), C.c_int64()
+        d = _lib.FlowTraceDesc()
+        d.map.n_particles, d.map.max_crossings, d.map.floor = P, int(max_crossings), float(floor)
+        d.map.start_triangle, d.map.start_weights, d.map.neighbours = _ptr(tri, C.c_int32), _ptr(w, C.c_double), _ptr(nbr, C.c_int32)
+        d.map.triangle, d.map.weights = _ptr(out["triangle"], C.c_int32), _ptr(out["weights"], C.c_double)
+        d.map.status, d.map.rested, d.map.crossings = _ptr(out["status"], C.c_int32), _ptr(out["rested"], C.c_int32), _ptr(out["crossings"], C.c_int32)
+        d.map.triangles_at, d.map.weights_at = _ptr(out.get("triangles_at"), C.c_int32), _ptr(out.get("weights_at"), C.c_double)
+        d.node_from, d.node_to, d.action = node_from, node_to, _ptr(out.get("action"), C.c_double)
+        d.map.ms = C.pointer(ms)
+        if mass is not None:
+            m = np.ascontiguousarray(mass, dtype=np.float64)
+            a = None if attributes is None else np.ascontiguousarray(attributes, dtype=np.float64)
+            A = 0 if a is None else a.shape[0]
+            if m.shape != (P,) or (a is not None and (a.ndim != 2 or a.shape[1] != P)):
+                raise ValueError(f"flow_trace: mass ({P},) and attributes (A, {P}) expected")
+            k = np.ascontiguousarray(flow.push_scales(m, a, w) if exponents is None else exponents, dtype=np.int32)
+            if k.shape != (1 + A,):
+                raise ValueError(f"flow_trace: {1 + A} exponents expected, got {k.shape}")
+            L = n + 1 if layers == "all" else 1
+            out["mass_at"] = np.empty((L, self.V))
+            out["attr_at"] = np.empty((A, L, self.V)) if A else None
+            d.mass, d.n_attributes, d.all_layers = _ptr(m, C.c_double), A, int(layers == "all")
+            d.attributes, d.scale_exponent = _ptr(a, C.c_double), _ptr(k, C.c_int32)
+            d.mass_at, d.attr_at = _ptr(out["mass_at"], C.c_double), _ptr(out["attr_at"], C.c_double)
+            d.dropped = C.pointer(dropped)
+        elif attributes is not None or exponents is not None:
+            raise ValueError("flow_trace: attributes and exponents need a mass")
+        before = self.debug_counter(9)
+        _lib.check(self.lib.dots_flow_trace(self._h, C.byref(d)), "dots_flow_trace")
+        self.flow_trace_ms, self.flow_trace_bytes = ms.value, self.debug_counter(9) - before
+        if mass is not None:
+            out["dropped"], out["exponents"] = int(dropped.value), k
+        return out
+
     def _carry_from(self, who, src, entry, describe, factors, same_grid):
         """What the three carriers share: the guards (``same_grid``: one ``n_time``), ``describe()`` -- the method's own validation, giving
         its descriptor and the arrays it points to --, the factors, the call of ``entry`` and its check.  Returns the launches' milliseconds."""

@@ -10,6 +10,10 @@ with ``0.5 * (E[j] + E[j + 1]) / rho``, ``rho`` the mean of ``mu[j]`` over the v
 of the surface come from ``cascade.locate_device`` (triangle and weights of the closest point); ``vertex_starts`` puts one particle
 on every vertex, ``triangle_starts`` one on every sub-triangle of a regular subdivision.
 
+With ``span=(node_from, node_to)`` and ``action=True`` the same function is the specification of ``dots_flow_trace``: the trace between
+any two time nodes, backward with the velocity negated (the inverse map: a source point for every start on the target, which
+``pull_back`` turns into a texture pull), and the kinetic action of every particle.
+
 ``push_forward_host`` is the specification of ``dots_flow_push``: what the particles carry (``start_masses``, attributes) summed onto
 the vertices in 64-bit fixed point with the exponents of ``push_scales`` -- integer sums, so the device returns the same bits in
 every order of arrival.
@@ -67,7 +71,20 @@ def _clamp0(x):
     return 0.0 if 0.0 > x else x
 
 
-def flow_map_host(mu, E, triangles, hat, nbr, start_triangle, start_weights, floor, max_crossings=16, trajectory=False):
+def check_span(span, n_time=None, who="flow_map"):
+    """``(node_from, node_to)`` as two ints: two different integers >= 0, and <= ``n_time`` where it is known.  ``ValueError`` otherwise."""
+    ok = isinstance(span, (tuple, list)) and len(span) == 2 and all(isinstance(x, (int, np.integer)) and not isinstance(x, bool) for x in span)
+    if not ok:
+        raise ValueError(f"{who}: span must be None or (node_from, node_to), two integers")
+    a, b = int(span[0]), int(span[1])
+    if a == b:
+        raise ValueError(f"{who}: span: node_from equals node_to ({a}): no interval to trace")
+    if min(a, b) < 0 or (n_time is not None and max(a, b) > int(n_time)):
+        raise ValueError(f"{who}: span {(a, b)} outside the time nodes 0 .. {'n_time' if n_time is None else int(n_time)}")
+    return a, b
+
+
+def flow_map_host(mu, E, triangles, hat, nbr, start_triangle, start_weights, floor, max_crossings=16, trajectory=False, span=None, action=False):
     """Trace particles through the transport ``(mu (T, V) on the intervals, E (T + 1, F, 3) on the nodes)`` -- both in the same units,
     the raw iterate or the recovered solution: they share one recovery factor and only their ratio is used.  ``hat`` (F, 3, 3): the
     hat-function gradients of the plan (``DevicePlan.hat_grad`` in the numbering of ``triangles``; the ones the device holds, not
@@ -93,7 +110,18 @@ def flow_map_host(mu, E, triangles, hat, nbr, start_triangle, start_weights, flo
 
     The weights are never renormalised.  Returns ``{"triangle" (P,) int32, "weights" (P, 3), "status" (P,) int32, "rested" (P,) int32,
     "crossings" (P,) int32 (the total)}``, with ``trajectory=True`` also ``"triangles_at" (T + 1, P)`` and ``"weights_at" (T + 1, P, 3)``:
-    layer 0 is the start, layer l the state after l intervals."""
+    layer 0 is the start, layer l the state after l intervals.
+
+    ``span = (node_from, node_to)``, two different nodes of 0 .. T (the specification of ``dots_flow_trace``; None: the above, bit for
+    bit): n = |node_to - node_from| intervals are traversed, forward (node_to > node_from) ``j = node_from + i``, backward
+    ``j = node_from - 1 - i``, i = 0 .. n - 1.  The steps are the ones above in the interval j, except that backward step 2 negates the
+    quotient, ``u[c] = -((0.5 * (E[j][f][c] + E[j + 1][f][c])) / rho)`` (a floored triangle has ``u = +0.0`` in both directions).
+    Layer i is the state after i traversed intervals: n + 1 layers.
+
+    ``action=True``: every particle starts with ``act = 0.0``, and after step 4 has found ``best``, once per turn of the inner loop,
+    ``uu = (u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]`` and ``act = act + best * uu`` (a step that ends in a stop or a rest has still
+    spent ``best``; ``u`` as formed, nothing projected): the time integral of |u|^2 along the path, ``"action"`` (P,) of the result.
+    Its mass-weighted sum is twice the transport cost the particles account for."""
     mu_a, E_a = np.asarray(mu, dtype=np.float64), np.asarray(E, dtype=np.float64)
     tri_a = np.asarray(triangles).astype(np.int64)
     T, F = mu_a.shape[0], tri_a.shape[0]
@@ -114,16 +142,26 @@ def flow_map_host(mu, E, triangles, hat, nbr, start_triangle, start_weights, flo
     third = 1.0 / 3.0
     out = {"triangle": np.empty(P, dtype=np.int32), "weights": np.empty((P, 3)), "status": np.empty(P, dtype=np.int32),
            "rested": np.empty(P, dtype=np.int32), "crossings": np.empty(P, dtype=np.int32)}
+    if span is None:
+        intervals, backward = range(T), False
+    else:
+        node_from, node_to = check_span(span, T, "flow_map_host")
+        backward = node_to < node_from
+        intervals = range(node_from - 1, node_to - 1, -1) if backward else range(node_from, node_to)
+    n = len(intervals)
     if trajectory:
-        out["triangles_at"] = np.empty((T + 1, P), dtype=np.int32)
-        out["weights_at"] = np.empty((T + 1, P, 3))
+        out["triangles_at"] = np.empty((n + 1, P), dtype=np.int32)
+        out["weights_at"] = np.empty((n + 1, P, 3))
+    if action:
+        out["action"] = np.empty(P)
     for p in range(P):
         f = int(start_f[p])
         l = start_w[p].tolist()
         status = rested = total = 0
+        act = 0.0
         if trajectory:
             out["triangles_at"][0, p], out["weights_at"][0, p] = f, l
-        for j in range(T):
+        for i, j in enumerate(intervals):
             if status == 0:
                 rem, crossings = h, 0
                 mu_j, E_j, E_n = mu_l[j], E_l[j], E_l[j + 1]
@@ -133,6 +171,8 @@ def flow_map_host(mu, E, triangles, hat, nbr, start_triangle, start_weights, flo
                     if rho > floor:
                         e0, e1 = E_j[f], E_n[f]
                         u0, u1, u2 = (0.5 * (e0[0] + e1[0])) / rho, (0.5 * (e0[1] + e1[1])) / rho, (0.5 * (e0[2] + e1[2])) / rho
+                        if backward:
+                            u0, u1, u2 = -u0, -u1, -u2
                     else:
                         u0 = u1 = u2 = 0.0
                     g = hat_l[f]
@@ -143,6 +183,8 @@ def flow_map_host(mu, E, triangles, hat, nbr, start_triangle, start_weights, flo
                             s = l[k] / (-rate[k])
                             if s < best:
                                 best, kmin = s, k
+                    if action:
+                        act = act + best * ((u0 * u0 + u1 * u1) + u2 * u2)
                     if kmin < 0:
                         l = [_clamp0(l[k] + rem * rate[k]) for k in range(3)]
                         break
@@ -162,7 +204,9 @@ def flow_map_host(mu, E, triangles, hat, nbr, start_triangle, start_weights, flo
                         moved[tri_l[g].index(v[k])] = l[k]
                     f, l = g, moved
             if trajectory:
-                out["triangles_at"][j + 1, p], out["weights_at"][j + 1, p] = f, l
+                out["triangles_at"][i + 1, p], out["weights_at"][i + 1, p] = f, l
+        if action:
+            out["action"][p] = act
         out["triangle"][p], out["weights"][p], out["status"][p], out["rested"][p], out["crossings"][p] = f, l, status, rested, total
     return out
 
@@ -224,6 +268,8 @@ def push_forward_host(result_with_trajectory, triangles, n_vertices, mass, attri
     - ``layers="end"`` gives ``L = 1``: the state after interval T.
     - ``layers="all"`` gives ``L = T + 1``: layer 0 the starts, layer l the state after l intervals.  These are the layers of
       ``triangles_at``.
+    - A result traced over a ``span`` of n intervals (in either direction) has n + 1 layers: ``"all"`` gives ``L = n + 1``, ``"end"``
+      the state at ``node_to``.
 
     At each layer, for each corner ``k = 0, 1, 2`` of the triangle ``f`` the particle is in and each channel c, in this order of
     operations:
@@ -277,6 +323,20 @@ def push_forward_host(result_with_trajectory, triangles, n_vertices, mass, attri
     for c in range(C):
         out[c] = acc[c].astype(np.float64) * math.ldexp(1.0, -int(k[c]))      # (float(int) rounds to nearest even)
     return {"mass": out[0], "attributes": out[1:] if C > 1 else None, "dropped": dropped, "integers": acc.astype(np.int64), "issued": issued}
+
+
+def pull_back(fields, result, triangles):
+    """Vertex fields ``(V, A)`` or ``(V,)`` interpolated at the landing points of a traced map: ``(w0 * x[v0] + w1 * x[v1]) + w2 * x[v2]``
+    over the vertices of ``result["triangle"]`` with ``result["weights"]``: ``(P, A)`` or ``(P,)``.  With a backward trace from the
+    vertices of the target this pulls a texture or a labelling on the source onto every target vertex."""
+    x = np.asarray(fields, dtype=np.float64)
+    t = np.asarray(triangles).astype(np.int64)[np.asarray(result["triangle"]).astype(np.int64)]      # (P, 3)
+    w = np.asarray(result["weights"], dtype=np.float64)
+    if x.ndim not in (1, 2) or t.ndim != 2 or w.shape != (t.shape[0], 3):
+        raise ValueError("pull_back: fields (V, A) or (V,), and a result with triangle (P,) and weights (P, 3) expected")
+    if x.ndim == 1:
+        return (w[:, 0] * x[t[:, 0]] + w[:, 1] * x[t[:, 1]]) + w[:, 2] * x[t[:, 2]]
+    return (w[:, 0:1] * x[t[:, 0]] + w[:, 1:2] * x[t[:, 1]]) + w[:, 2:3] * x[t[:, 2]]
 
 
 def triangle_starts(triangles, level=1):

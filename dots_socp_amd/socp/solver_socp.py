@@ -64,7 +64,7 @@ def check_time_nodes(n_time, lap_solver="modal_direct", time_slab=None, pcg_wind
             raise ValueError(f"lap_solver='modal_pcg' needs n_time + 1 <= {MODAL_PCG_MAX_NODES} (got {nodes}); use lap_solver='modal_direct'")
 
 
-FLOW_MAP_KEYS = ("starts", "floor", "max_crossings", "trajectory", "push")
+FLOW_MAP_KEYS = ("starts", "floor", "max_crossings", "trajectory", "push", "span", "action")
 FLOW_PUSH_KEYS = ("mass", "attributes", "layers")
 
 
@@ -84,8 +84,21 @@ def _check_flow_starts(starts):
     return None
 
 
-def _check_flow_push(push, starts):
-    """``None``, or the request as a dict with all of FLOW_PUSH_KEYS (``True``: the masses of mu0 at the starts, the last layer)."""
+def _check_flow_span(span, action, n_time=None):
+    """``None`` (today's trace over the whole horizon, no action), or ``(node_from, node_to)`` of a request with a span or the action
+    (``action`` alone: ``(0, n_time)``, or ``(0, None)`` while ``n_time`` is not known)."""
+    from ..flow import check_span
+
+    if not isinstance(action, (bool, np.bool_)):
+        raise ValueError("flow_map: action must be True or False")
+    if span is None:
+        return (0, None if n_time is None else int(n_time)) if action else None
+    return check_span(span, n_time)
+
+
+def _check_flow_push(push, starts, span=None, n_time=None):
+    """``None``, or the request as a dict with all of FLOW_PUSH_KEYS (``True``: the masses of mu0 -- of mu1 where the span starts at the
+    last node -- at the starts, the last layer).  ``span``: what ``_check_flow_span`` returned."""
     if push is None or push is False:
         return None
     if push is True:
@@ -104,12 +117,18 @@ def _check_flow_push(push, starts):
             raise ValueError(f"flow_map: push: attributes (A, P) with A <= 4 expected, got {a.shape}")
     if out["mass"] is None and _check_flow_starts(starts) is None:
         raise ValueError("flow_map: push: starts given as (triangle, weights) need a mass per particle")
+    if out["mass"] is None and span is not None and span[0] != 0:
+        # (without n_time the start of a backward span cannot be told from the last node here: AlmSolver.flow_map checks again)
+        if span[0] != int(n_time) if n_time is not None else span[1] > span[0]:
+            raise ValueError(f"flow_map: push: a span from the interior node {span[0]} needs a mass per particle (the default is mu0 from "
+                             "node 0 and mu1 from node n_time)")
     return out
 
 
-def check_flow_map(flow_map, time_slab=None):
+def check_flow_map(flow_map, time_slab=None, n_time=None):
     """Refuse, before any device call, a ``flow_map`` request that cannot be served: ``None`` or the keywords of ``AlmSolver.flow_map``
-    as a dict; never on a time slab (the particles are traced by one context, which holds every time node)."""
+    as a dict; never on a time slab (the particles are traced by one context, which holds every time node).  ``n_time``: where it is
+    known the span is checked against it here, otherwise ``AlmSolver.flow_map`` does."""
     if flow_map is None:
         return None
     if time_slab is not None:
@@ -121,7 +140,8 @@ def check_flow_map(flow_map, time_slab=None):
         raise ValueError(f"flow_map: unknown option(s) {sorted(unknown)}; known: {list(FLOW_MAP_KEYS)}")
     if "starts" in flow_map:
         _check_flow_starts(flow_map["starts"])
-    _check_flow_push(flow_map.get("push"), flow_map.get("starts", "vertices"))
+    span = _check_flow_span(flow_map.get("span"), flow_map.get("action", False), n_time)
+    _check_flow_push(flow_map.get("push"), flow_map.get("starts", "vertices"), span, n_time)
     return dict(flow_map)
 
 
@@ -678,7 +698,7 @@ class AlmSolver:
         mu, E, info = self._read_out(self.r * self.dual_scale, w_vertex, w_triangle, centred, mu0, mu1, sums=True)
         return {"mu": mu, "E": E}, info
 
-    def flow_map(self, starts="vertices", floor=None, max_crossings=16, trajectory=False, push=None):
+    def flow_map(self, starts="vertices", floor=None, max_crossings=16, trajectory=False, push=None, span=None, action=False):
         """The transport map of the current iterate, traced on the device (DeviceProblem.flow_map; flow.flow_map_host is the
         specification): where the mass at a point ends up, and with ``trajectory`` where it is after every interval.
         ``starts``: "vertices" (one particle on every vertex: flow.vertex_starts), "triangles" or ``("triangles", level)`` (one on
@@ -693,13 +713,22 @@ class AlmSolver:
         default mass is that of ``mu0`` at the named starts (flow.start_masses), the default layer the last.  The result gains
         ``pushed``: ``{"mass" (L, V), "attributes" (A, L, V) or None, "dropped", "exponents" (flow.push_scales), "rested_mass" and
         "stopped_mass" (the mass of the particles that rested / stopped), "to_mu1":
-        evaluate.compare_with_exact_transportation(mass[-1], mu1, geometry)}``."""
+        evaluate.compare_with_exact_transportation(mass[-1], mu1, geometry)}``.
+        ``span = (node_from, node_to)`` and ``action``: the trace between two time nodes, backward where ``node_to < node_from`` (the
+        inverse map: ``flow.pull_back`` then pulls a vertex field onto the starts), and the kinetic action of every particle
+        (DeviceProblem.flow_trace; ``action`` alone means ``span=(0, n_time)``).  With neither, the call is the one above.  The result
+        gains ``"span"``, ``"nodes"`` (n + 1,): the time node of every layer, and ``"action"`` (P,) on request; the trajectory has
+        n + 1 layers.  The default mass of a push is that of ``mu0`` where ``node_from == 0`` and of ``mu1`` where
+        ``node_from == n_time`` (a ``ValueError`` asks for ``mass`` otherwise); ``pushed["to_mu1"]`` is given only where
+        ``node_to == n_time``, and ``pushed["to_mu0"]``, the same comparison against ``mu0``, where ``node_to == 0``."""
         from .. import evaluate, flow
         from . import _geometry_with_areas
 
         if self.dev.slab:
             raise ValueError("flow_map is not available on time slabs: the particles are traced on one GPU, which holds every time node")
-        push = _check_flow_push(push, starts)
+        n_time = self.dev.T
+        span = _check_flow_span(span, action, n_time)
+        push = _check_flow_push(push, starts, span, n_time)
         vertices, triangles = np.asarray(self.geometry["vertices"], dtype=np.float64), np.asarray(self.geometry["triangles"])
         named = _check_flow_starts(starts)
         if named is None:
@@ -714,7 +743,29 @@ class AlmSolver:
         if getattr(self, "_neighbours", None) is None:
             self._neighbours = flow.triangle_neighbours(triangles)
         dev = self.dev
-        if push is None:
+        if span is not None:
+            mass = None
+            if push is not None:
+                mass = push["mass"]
+                if mass is None:
+                    mass = flow.start_masses(g["mu0" if span[0] == 0 else "mu1"], g["area_vertices"], g["area_triangles"], triangles, start_triangle,
+                                             start_weights, named[1])
+                mass = np.asarray(mass, dtype=np.float64)
+            out = dev.flow_trace(start_triangle, start_weights, self._neighbours, float(floor) / (self.r * self.dual_scale), span, action=bool(action),
+                                 mass=mass, attributes=None if push is None else push["attributes"], layers="end" if push is None else push["layers"],
+                                 max_crossings=max_crossings, trajectory=trajectory)
+            out["ms"], out["bytes"] = dev.flow_trace_ms, dev.flow_trace_bytes
+            out["span"] = span
+            out["nodes"] = np.arange(span[0], span[1] + (1 if span[1] > span[0] else -1), 1 if span[1] > span[0] else -1)
+            if push is not None:
+                pushed = {"mass": out.pop("mass_at"), "attributes": out.pop("attr_at"), "dropped": out.pop("dropped"), "exponents": out.pop("exponents"),
+                          "rested_mass": float(np.sum(mass[out["rested"] > 0])), "stopped_mass": float(np.sum(mass[out["status"] == 1]))}
+                if span[1] == n_time:
+                    pushed["to_mu1"] = evaluate.compare_with_exact_transportation(pushed["mass"][-1], np.asarray(g["mu1"], dtype=np.float64), g)
+                if span[1] == 0:
+                    pushed["to_mu0"] = evaluate.compare_with_exact_transportation(pushed["mass"][-1], np.asarray(g["mu0"], dtype=np.float64), g)
+                out["pushed"] = pushed
+        elif push is None:
             out = dev.flow_map(start_triangle, start_weights, self._neighbours, float(floor) / (self.r * self.dual_scale),
                                max_crossings=max_crossings, trajectory=trajectory)
             out["ms"], out["bytes"] = dev.flow_map_ms, dev.flow_map_bytes
@@ -742,7 +793,7 @@ class AlmSolver:
         ``solution["flow_map"]`` then holds what it returns."""
         if read_out is not None and outputs is not None:
             raise ValueError("finalize: outputs and read_out are mutually exclusive (read_out returns mu and E only)")
-        flow_map = check_flow_map(flow_map, getattr(self.dev, "slab", None))
+        flow_map = check_flow_map(flow_map, getattr(self.dev, "slab", None), self.dev.T)
         dev, hist, validator = self.dev, self.run_history, self.kkt_validator
         self._kkt_prefetch(range(7))
         validator.validator.validate(list(range(7)))
@@ -826,7 +877,7 @@ def solver_socp(
     """
     if read_out is not None and outputs is not None:
         raise ValueError("solver_socp: outputs and read_out are mutually exclusive (read_out returns mu and E only)")
-    flow_map = check_flow_map(flow_map)
+    flow_map = check_flow_map(flow_map, n_time=n_time)
     alm = AlmSolver(n_time, geometry, congestion=congestion, nit=nit, eps=eps, tol=tol, tau=tau, is_z_scaling=is_z_scaling,
                     is_constant_scaling=is_constant_scaling, check_kkt_step_by_step=check_kkt_step_by_step,
                     init_solution=init_solution, tol_checkpoints=tol_checkpoints, time_limit=time_limit, is_palm=is_palm,
@@ -902,7 +953,7 @@ def solver_socp_many(n_time, geometry, problems, *, max_batch=4, read_out=None, 
     from .. import geometry as geo
     from ..device import step_many
 
-    flow_map = check_flow_map(flow_map)
+    flow_map = check_flow_map(flow_map, n_time=n_time)
     probs = _batch_problems(geometry, problems, common)
     if int(max_batch) < 1:
         raise ValueError("solver_socp_many: max_batch >= 1")
@@ -1133,7 +1184,7 @@ def solver_socp_cascade(n_time, geometry, levels=None, level_tol=None, read_out=
     ``solver_socp_spacetime_cascade`` coarsens the mesh along with the time grid."""
     from .. import geometry as geo
 
-    flow_map = check_flow_map(flow_map, kwargs.get("time_slab"))
+    flow_map = check_flow_map(flow_map, kwargs.get("time_slab"), n_time)
     levels, level_tol, opts = _cascade_options(n_time, levels, level_tol, kwargs)
     reorder = opts.pop("reorder", True)
     if opts.get("lap_solver", "modal_direct") == "modal_direct" and reorder is True:
@@ -1210,7 +1261,7 @@ def solver_socp_mesh_cascade(n_time, geometries, level_tol=None, read_out=None, 
     per level: n_vertices, n_triangles, tol, iterations, running_time, setup_seconds, prolong_ms and prolong_bytes (None on the coarsest
     level), cost, kkt_max, device_bytes, transfer ("nested" | "located", None on the coarsest level), max_distance (of a located
     level, else None)], "total_seconds"}.  ``read_out`` and ``flow_map``: as for ``solver_socp``, for the finest level."""
-    flow_map = check_flow_map(flow_map, kwargs.get("time_slab"))
+    flow_map = check_flow_map(flow_map, kwargs.get("time_slab"), n_time)
     geometries, level_tol, opts = _mesh_cascade_options(geometries, level_tol, kwargs)
     return _run_levels([_carried(geom, i, n_time=n_time) for i, geom in enumerate(geometries)], "mesh_cascade",
                        lambda alm, hist, setup, i: _mesh_record(alm, hist, setup, geometries[i], i == 0), level_tol, opts, read_out, flow_map)
@@ -1244,7 +1295,7 @@ def solver_socp_spacetime_cascade(n_time, geometries, levels=None, level_tol=Non
     Returns ``(solution, run_history)`` of the finest level; ``run_history.solver_stats["spacetime_cascade"]`` = {"levels": [the records of
     ``solver_socp_mesh_cascade`` plus ``n_time``], "total_seconds"}.  ``read_out`` and ``flow_map``: as for ``solver_socp``, for the
     finest level."""
-    flow_map = check_flow_map(flow_map, kwargs.get("time_slab"))
+    flow_map = check_flow_map(flow_map, kwargs.get("time_slab"), n_time)
     geometries, levels, level_tol, opts = _spacetime_cascade_options(n_time, geometries, levels, level_tol, kwargs)
     return _run_levels([_carried(geom, i, n_time=T, init_regrid=bool(i) and T != levels[i - 1]) for i, (T, geom) in enumerate(zip(levels, geometries))],
                        "spacetime_cascade",
@@ -1289,7 +1340,7 @@ def solver_socp_auto_cascade(n_time, geometry, coarse_levels=2, ratio=4.0, locat
     mesh that does not coarsen); every option is checked before the levels are built."""
     from .. import meshes
 
-    flow_map = check_flow_map(flow_map, kwargs.get("time_slab"))
+    flow_map = check_flow_map(flow_map, kwargs.get("time_slab"), n_time)
     n_coarse = _auto_cascade_options(n_time, coarse_levels, ratio, locate, spacetime, levels, level_tol, kwargs)
     if n_coarse == 0:
         return solver_socp(n_time, geometry, read_out=read_out, flow_map=flow_map, **kwargs)

@@ -736,6 +736,39 @@ typedef struct dots_flow_push_desc {
 } dots_flow_push_desc;
 int dots_flow_push(dots_ctx *ctx, const dots_flow_push_desc *desc);
 
+/* dots_flow_trace: the trace of dots_flow_map between any two time nodes, in either direction, with the kinetic action of every
+ * particle and, on request, the deposits of dots_flow_push.  dots_socp_amd/flow.py: flow_map_host(..., span, action) and
+ * push_forward_host are the specification, and every output equals them bit for bit.
+ * n = |node_to - node_from| intervals are traversed: forward (node_to > node_from) j = node_from + i, backward j = node_from - 1 - i,
+ * i = 0 .. n - 1.  The steps are those of dots_flow_map in the interval j; backward the velocity is negated, u = -(0.5 (E[j] +
+ * E[j + 1]) / rho) (a floored triangle has u = +0 in both directions), which gives the inverse map: a source point for every start
+ * on the target.  Every step of a particle adds best * ((u0 u0 + u1 u1) + u2 u2) to its action, `best` the time the step took (a
+ * step that ends in a stop or a rest has still spent it) and u as formed (nothing is projected): the time integral of |u|^2 along
+ * the path.  Layer i of triangles_at / weights_at is the state after i traversed intervals: n + 1 layers.  With (0, n_time) and a
+ * NULL action the outputs equal dots_flow_map's and dots_flow_push's.
+ * mass NULL: no deposits, the deposit fields are ignored and the five per-particle outputs of `map` are required.  Otherwise the
+ * deposits of dots_flow_push on the layers of this trace: all_layers = 0 gives L = 1, the state at node_to; else L = n + 1.
+ * The contract of dots_flow_map / dots_flow_push holds (pending penalty division, z_mid, state left alone, every Laplacian solver
+ * and n_time + 1 <= 1024, batch members on their own stream; output bytes in dots_debug_counter 9); one more kernel family
+ * (k_flow_trace, k_flow_trace_push<A>), the same launches.
+ * DOTS_ERR_ARGUMENT (nothing launched, the context stays usable): what dots_flow_map / dots_flow_push refuse; a node outside
+ * 0 .. n_time; node_from == node_to.  DOTS_ERR_STATE: a time slab. */
+typedef struct dots_flow_trace_desc {
+    dots_flow_map_desc map;         /* the particles and per-particle outputs; triangles_at / weights_at are [n + 1] layers   */
+    int32_t node_from, node_to;     /* 0 .. n_time, different                                                            */
+    double *action;                 /* NULL, or host out [n_particles]                                                   */
+    const double *mass;             /* NULL: no push; else host [n_particles] and the fields below as in dots_flow_push_desc */
+    int32_t n_attributes;
+    int32_t all_layers;             /* 0: L = 1, the state at node_to; else L = n + 1                                    */
+    const double *attributes;
+    const int32_t *scale_exponent;
+    double *mass_at;                /* host out [L][V]                                                                   */
+    double *attr_at;                /* host out [A][L][V], NULL iff A = 0                                                */
+    int64_t *dropped;
+    double *ms;                     /* NULL, or out: device milliseconds of the launches (map.ms is filled too)          */
+} dots_flow_trace_desc;
+int dots_flow_trace(dots_ctx *ctx, const dots_flow_trace_desc *desc);
+
 /* ---- levels of a cascade in space from ONE mesh: coarsen on the host, locate on the device ------------------------------------
  * dots_coarsen: half-edge-collapse decimation of the mesh (xyz [V][3], tri [F][3]) towards `n_target` vertices, host only (no
  * device work; dots_socp_amd/meshes.py: coarsen(backend="python") is the specification and states the rules; both return the same
@@ -801,7 +834,7 @@ int dots_bench_kernel(dots_ctx *ctx, int which, int reps, double *ms_per_launch,
  * batched solve (dots_laplacian_solve_many, dots_step_many, dots_bench_many) enqueued, read on the batch's first context, 8 of those, the
  * launches that took fewer right-hand sides than their chunk of DOTS_FRONT_NR problems held because NR regions of LDS would not fit or
  * a workgroup of 1024 threads takes fewer (the launch was split), 9 bytes this context has copied device -> host through dots_download,
- * dots_readout, dots_flow_map and dots_flow_push since it was created (the layer sums of dots_readout are written by the device itself and not copied), 10 device
+ * dots_readout, dots_flow_map, dots_flow_push and dots_flow_trace since it was created (the layer sums of dots_readout are written by the device itself and not copied), 10 device
  * allocations this context holds for its factor (0 without one, also after a dots_front_setup that failed), 11 the launches the
  * last multigrid V-cycle enqueued on this context took, as a bit mask: 1 restriction with a workgroup per coarse row, 2 restriction
  * with a thread per entry, 4 coarsest solve with a workgroup per row, 8 coarsest solve with a thread per entry, 16 the one-launch
