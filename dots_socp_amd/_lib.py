@@ -35,7 +35,7 @@ EXPORTS = [
     "dots_prolong_space", "dots_transfer_space", "dots_carry_spacetime",
     "dots_pcg_windows",
     "dots_coarsen", "dots_coarsen_vertices", "dots_coarsen_triangles", "dots_coarsen_copy", "dots_coarsen_free", "dots_mesh_locate",
-    "dots_flow_map", "dots_flow_push", "dots_flow_trace",
+    "dots_flow_map", "dots_flow_push", "dots_flow_trace", "dots_flow_slide",
 ]
 
 
@@ -179,6 +179,10 @@ class FlowTraceDesc(C.Structure):      # dots_flow_trace_desc
         ("n_attributes", C.c_int32), ("all_layers", C.c_int32), ("attributes", _f64p), ("scale_exponent", _i32p), ("mass_at", _f64p),
         ("attr_at", _f64p), ("dropped", C.POINTER(C.c_int64)), ("ms", _f64p),
     ]
+
+
+class FlowSlideDesc(C.Structure):      # dots_flow_slide_desc
+    _fields_ = [("trace", FlowTraceDesc), ("slides", _i32p), ("steps", _i32p)]
 
 
 class StepStats(C.Structure):
@@ -373,6 +377,7 @@ def load(host_only=False):
     lib.dots_flow_map.argtypes = [vp, C.POINTER(FlowMapDesc)]
     lib.dots_flow_push.argtypes = [vp, C.POINTER(FlowPushDesc)]
     lib.dots_flow_trace.argtypes = [vp, C.POINTER(FlowTraceDesc)]
+    lib.dots_flow_slide.argtypes = [vp, C.POINTER(FlowSlideDesc)]
     lib.dots_prolong_space.argtypes = [vp, vp, C.POINTER(ProlongSpaceDesc)]
     lib.dots_transfer_space.argtypes = [vp, vp, C.POINTER(TransferSpaceDesc)]
     lib.dots_carry_spacetime.argtypes = [vp, vp, C.POINTER(CarrySpacetimeDesc)]

@@ -1778,18 +1778,24 @@ static int flow_prepare(Ctx *c) {
     return 0;
 }
 
-// What dots_flow_map, dots_flow_push and dots_flow_trace share: the checks of the embedded description, the caller's starts and
+// What dots_flow_map, dots_flow_push, dots_flow_trace and dots_flow_slide share: the checks of the embedded description, the caller's starts and
 // neighbour table in the device numbering (host preparation), the allocation of the call, the launch and the copies back.  `push`
 // null: no deposits.  `span` null: the intervals 0 .. T - 1 with the kernels of dots_flow_map / dots_flow_push; else the intervals
-// between two nodes, in either direction, with the kernels of dots_flow_trace.
+// between two nodes, in either direction, with the kernels of dots_flow_trace.  `slide` (with a span): the kernels of dots_flow_slide.
 struct FlowSpanRequest {
     int node_from, node_to;
     double *action;      // host out [n_particles], or null
 };
-static int flow_run(dots_ctx *c, const char *who, const dots_flow_map_desc *desc, const dots_flow_push_desc *push, const FlowSpanRequest *span = nullptr) {
+struct FlowSlideRequest {
+    int32_t *slides;     // host out [n_particles]
+    int32_t *steps;      // host out [n_particles], or null
+};
+static int flow_run(dots_ctx *c, const char *who, const dots_flow_map_desc *desc, const dots_flow_push_desc *push, const FlowSpanRequest *span = nullptr,
+                    const FlowSlideRequest *slide = nullptr) {
     const std::string w = std::string(who) + ": ";
     if (c->shard_stride != 0) { set_error(w + "not available on time slabs"); return DOTS_ERR_STATE; }
     const Dev &d = c->d;
+    if (slide && (!span || !slide->slides)) { set_error(w + "null pointer (slides is required)"); return DOTS_ERR_ARGUMENT; }
     if (span) {
         if (span->node_from < 0 || span->node_from > d.T || span->node_to < 0 || span->node_to > d.T) { set_error(w + "a time node outside 0 .. n_time"); return DOTS_ERR_ARGUMENT; }
         if (span->node_from == span->node_to) { set_error(w + "node_from equals node_to: no interval to trace"); return DOTS_ERR_ARGUMENT; }
@@ -1872,13 +1878,15 @@ static int flow_run(dots_ctx *c, const char *who, const dots_flow_map_desc *desc
     if ((rc = check(c, true))) return rc;      // (a pending penalty division is carried out, as for a download; z_mid is not needed)
     if (push && (rc = readout_prepare(c))) return rc;      // (the inverse of the vertex numbering is the read-out's)
     // one allocation for the call: [start_w | o_w | w_at | mass | attr | pushed | action] doubles, [acc | dropped] 64-bit words, then
-    // [start | nbr | o_tri | status | rested | crossings | tri_at] ints
+    // [start | nbr | o_tri | status | rested | crossings | slides | steps | tri_at] ints (the five counters in a row: FlowSlide::o_counts)
     const size_t layers = (size_t)n_turns + 1;
     const size_t n_wat = desc->weights_at ? layers * P * 3 : 0, n_tat = desc->triangles_at ? layers * P : 0;
     const size_t L = push ? (push->all_layers ? layers : 1) : 0;
     const size_t n_acc = push ? (size_t)(A + 1) * L * (size_t)d.V : 0, n_carry = push ? (size_t)(A + 1) * P : 0;
     const size_t n_act = span && span->action ? (size_t)P : 0;
-    const size_t n_dbl = (size_t)P * 3 * 2 + n_wat + n_carry + n_acc + n_act, n_u64 = push ? n_acc + 1 : 0, n_int = (size_t)P * 5 + (size_t)F * 3 + n_tat;
+    const size_t n_slides = slide ? (size_t)P : 0, n_steps = n_slides;      // (the kernel counts the steps in any case; copied on request)
+    const size_t n_dbl = (size_t)P * 3 * 2 + n_wat + n_carry + n_acc + n_act, n_u64 = push ? n_acc + 1 : 0,
+                 n_int = (size_t)P * 5 + (size_t)F * 3 + n_tat + n_slides + n_steps;
     void *buf = nullptr;
     hipError_t ea = hipMalloc(&buf, sizeof(double) * (n_dbl + n_u64) + sizeof(int) * n_int);
     if (ea != hipSuccess) {
@@ -1890,7 +1898,7 @@ static int flow_run(dots_ctx *c, const char *who, const dots_flow_map_desc *desc
            *b_pushed = b_mass + n_carry, *b_act = b_pushed + n_acc;
     unsigned long long *b_acc = (unsigned long long *)(b_act + n_act);
     int *b_start = (int *)(b_acc + n_u64), *b_nbr = b_start + P, *b_otri = b_nbr + (size_t)F * 3, *b_status = b_otri + P, *b_rested = b_status + P,
-        *b_cross = b_rested + P, *b_tat = b_cross + P;
+        *b_cross = b_rested + P, *b_slides = b_cross + P, *b_steps = b_slides + n_slides, *b_tat = b_steps + n_steps;
     auto enqueue = [&]() -> int {
         DOTS_HIP(hipMemcpyAsync(b_sw, desc->start_weights, sizeof(double) * (size_t)P * 3, hipMemcpyHostToDevice, c->stream));
         DOTS_HIP(hipMemcpyAsync(b_start, h_start.data(), sizeof(int) * (size_t)P, hipMemcpyHostToDevice, c->stream));
@@ -1915,6 +1923,8 @@ static int flow_run(dots_ctx *c, const char *who, const dots_flow_map_desc *desc
             sp.dj = forward ? 1 : -1;
             sp.action = n_act ? b_act : nullptr;
         }
+        FlowSlide sl{};
+        if (slide) { sl.area_f = d.area_f; sl.o_counts = b_status; }
         DOTS_HIP(hipEventRecord(c->ev[0], c->stream));
         int r;
         if (push) {      // (the milliseconds hold the zeroing, the trace with its deposits and the conversion)
@@ -1922,8 +1932,10 @@ static int flow_run(dots_ctx *c, const char *who, const dots_flow_map_desc *desc
             q.A = A; q.L = (int)L; q.V = d.V;
             DOTS_HIP(hipMemsetAsync(b_acc, 0, sizeof(unsigned long long) * n_u64, c->stream));
             fin.acc = b_acc; fin.inv = c->inv_perm_v; fin.out = b_pushed; fin.A = A; fin.L = (int)L; fin.V = d.V;
-            if ((r = span ? launch_flow_trace_push(c, a, q, sp) : launch_flow_push(c, a, q)) || (r = launch_flow_push_finish(c, fin))) return r;
-        } else if ((r = span ? launch_flow_trace(c, a, sp) : launch_flow_map(c, a))) return r;
+            if ((r = slide ? launch_flow_slide_push(c, a, q, sp, sl) : span ? launch_flow_trace_push(c, a, q, sp) : launch_flow_push(c, a, q)) ||
+                (r = launch_flow_push_finish(c, fin)))
+                return r;
+        } else if ((r = slide ? launch_flow_slide(c, a, sp, sl) : span ? launch_flow_trace(c, a, sp) : launch_flow_map(c, a))) return r;
         DOTS_HIP(hipEventRecord(c->ev[1], c->stream));
         // only the outputs cross to the host
         if (desc->weights) DOTS_HIP(hipMemcpyAsync(desc->weights, b_ow, sizeof(double) * (size_t)P * 3, hipMemcpyDeviceToHost, c->stream));
@@ -1934,6 +1946,8 @@ static int flow_run(dots_ctx *c, const char *who, const dots_flow_map_desc *desc
         if (desc->weights_at) DOTS_HIP(hipMemcpyAsync(desc->weights_at, b_wat, sizeof(double) * n_wat, hipMemcpyDeviceToHost, c->stream));
         if (desc->triangles_at) DOTS_HIP(hipMemcpyAsync(desc->triangles_at, b_tat, sizeof(int) * n_tat, hipMemcpyDeviceToHost, c->stream));
         if (n_act) DOTS_HIP(hipMemcpyAsync(span->action, b_act, sizeof(double) * n_act, hipMemcpyDeviceToHost, c->stream));
+        if (n_slides) DOTS_HIP(hipMemcpyAsync(slide->slides, b_slides, sizeof(int) * n_slides, hipMemcpyDeviceToHost, c->stream));
+        if (slide && slide->steps) DOTS_HIP(hipMemcpyAsync(slide->steps, b_steps, sizeof(int) * n_steps, hipMemcpyDeviceToHost, c->stream));
         if (push) {
             const size_t n_layer = L * (size_t)d.V;
             DOTS_HIP(hipMemcpyAsync(push->mass_at, b_pushed, sizeof(double) * n_layer, hipMemcpyDeviceToHost, c->stream));
@@ -1954,7 +1968,7 @@ static int flow_run(dots_ctx *c, const char *who, const dots_flow_map_desc *desc
     }
     (void)hipFree(buf);
     if (rc) return rc;
-    size_t bytes = sizeof(double) * (n_wat + n_act) + sizeof(int) * n_tat + (desc->weights ? sizeof(double) * (size_t)P * 3 : 0);
+    size_t bytes = sizeof(double) * (n_wat + n_act) + sizeof(int) * (n_tat + n_slides + (slide && slide->steps ? n_steps : 0)) + (desc->weights ? sizeof(double) * (size_t)P * 3 : 0);
     for (const int32_t *o : {desc->triangle, desc->status, desc->rested, desc->crossings}) bytes += o ? sizeof(int) * (size_t)P : 0;
     if (push) bytes += sizeof(double) * n_acc + (push->dropped ? sizeof(int64_t) : 0);
     c->d2h_bytes += (int64_t)bytes;
@@ -1983,6 +1997,20 @@ int dots_flow_trace(dots_ctx *c, const dots_flow_trace_desc *desc) {
     push.scale_exponent = desc->scale_exponent; push.mass_at = desc->mass_at; push.attr_at = desc->attr_at; push.dropped = desc->dropped;
     push.ms = desc->ms;
     return flow_run(c, "flow_trace", &desc->map, &push, &span);
+}
+
+int dots_flow_slide(dots_ctx *c, const dots_flow_slide_desc *desc) {
+    if (!c) { set_error("null context"); return DOTS_ERR_ARGUMENT; }
+    if (!desc) { set_error("flow_slide: null description"); return DOTS_ERR_ARGUMENT; }
+    const dots_flow_trace_desc &t = desc->trace;
+    const FlowSpanRequest span{t.node_from, t.node_to, t.action};
+    const FlowSlideRequest slide{desc->slides, desc->steps};
+    if (!t.mass) return flow_run(c, "flow_slide", &t.map, nullptr, &span, &slide);
+    dots_flow_push_desc push{};      // (the deposit fields, as dots_flow_push takes them; `map` is passed beside it)
+    push.mass = t.mass; push.n_attributes = t.n_attributes; push.all_layers = t.all_layers; push.attributes = t.attributes;
+    push.scale_exponent = t.scale_exponent; push.mass_at = t.mass_at; push.attr_at = t.attr_at; push.dropped = t.dropped;
+    push.ms = t.ms;
+    return flow_run(c, "flow_slide", &t.map, &push, &span, &slide);
 }
 
 int dots_front_enable(dots_ctx *c, int on) {
@@ -2044,7 +2072,7 @@ int64_t dots_debug_counter(dots_ctx *c, int which) {
         case 6: return c->sched.bm_nt;                      // beta_mid streamed around the caches by steps 2+3 (the rule of dots_front_setup, or DOTS_BM_NT)
         case 7: return c->front_many_launches;        // sweep launches the last front_solve_many on this (first) context enqueued
         case 8: return c->front_many_split;           // ... of those, launches with fewer rhs than their chunk (many_launch halved: LDS or 1024-thread cap)
-        case 9: return c->d2h_bytes;                  // bytes dots_download, dots_readout, dots_flow_map, dots_flow_push and dots_flow_trace have copied device -> host
+        case 9: return c->d2h_bytes;                  // bytes dots_download, dots_readout, dots_flow_map, dots_flow_push, dots_flow_trace and dots_flow_slide have copied device -> host
         case 10: return c->n_front_allocs;            // device allocations the installed factor holds (0 after front_release: also after a failed dots_front_setup)
         case 11: return c->mg_path;                   // MG_PATH_* bits of the last V-cycle enqueued (dots_dev.h)
         case 12: return c->step_path;                 // STEP_PATH_* bits of the last iteration's launches (dots_dev.h)

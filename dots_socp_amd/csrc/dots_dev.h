@@ -449,6 +449,15 @@ int launch_flow_push(Ctx *c, const FlowArgs &a, const FlowPush &q);
 int launch_flow_push_finish(Ctx *c, const FlowPushFinish &q);
 int launch_flow_trace(Ctx *c, const FlowArgs &a, const FlowSpan &s);
 int launch_flow_trace_push(Ctx *c, const FlowArgs &a, const FlowPush &q, const FlowSpan &s);
+// dots_flow_slide: what the sliding mode reads and writes besides (a struct of its own: the arguments of the kernels before it stay)
+// The slide kernels write their five per-particle counters as the rows of ONE array and leave FlowArgs::o_status / o_rested /
+// o_cross alone: five output pointers held in scalar registers through the loop made k_flow_slide_push<A> spill 12 - 18 of them.
+struct FlowSlide {
+    const double *area_f;        // [F] Dev::area_f, device numbering
+    int *o_counts;               // [5][P]: status, rested, crossings, slides, steps (the turns of the inner loop)
+};
+int launch_flow_slide(Ctx *c, const FlowArgs &a, const FlowSpan &s, const FlowSlide &sl);
+int launch_flow_slide_push(Ctx *c, const FlowArgs &a, const FlowPush &q, const FlowSpan &s, const FlowSlide &sl);
 void preload_flow_kernels();
 // what dots_flow_map checks the caller's tables against, downloaded once per context
 struct FlowHost {

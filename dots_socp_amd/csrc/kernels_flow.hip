@@ -19,6 +19,15 @@
 // along the path.  Direction and start are run-time values of FlowSpan: a sign flip and an add per turn beside six fp64 divisions;
 // a template flag would double the instantiations for nothing (registers: DESIGN.md section 9).  The SPAN = false instantiations
 // are the code they were.
+//
+// dots_flow_slide is the tracer with the sliding mode of the discontinuous field (flow_body<PUSH, A, SPAN = true, SLIDE = true>;
+// flow.py: step 3a of flow_map_host): where the triangle just entered pushes the particle back across the edge it came through, it
+// moves along that edge with the combination of the two velocities whose normal part vanishes, instead of crossing back and forth
+// until the cap and resting.  What step 3a needs of the triangle left (two doubles and the two shared corners) is formed at the
+// crossing and stays in registers; the corner-indexed reads are selects on the named registers.  The end of a slide is selects,
+// not branches, and the five per-particle counters go to the rows of one array (FlowSlide::o_counts): with the branches and five
+// output pointers k_flow_slide_push<A> spilled 12 - 20 scalar registers.  The SLIDE = false instantiations are the code they were
+// (registers: DESIGN.md section 9).
 #include "dots_dev.h"
 
 namespace dots {
@@ -81,10 +90,18 @@ __device__ __forceinline__ void flow_deposit(const FlowArgs &a, const FlowPush &
     }
 }
 
+// element k of three named registers, as a select (an indexed array would go to scratch); k outside 0 .. 2 gives the last
+__device__ __forceinline__ double flow_pick(int k, double x0, double x1, double x2) { return k == 0 ? x0 : (k == 1 ? x1 : x2); }
+// element 3 - c - k of three named registers, c and k two different corners: the same two comparisons as flow_pick(c) and flow_pick(k)
+__device__ __forceinline__ double flow_pick_third(int c, int k, double x0, double x1, double x2) {
+    return c == 0 ? (k == 1 ? x2 : x1) : (c == 1 ? (k == 0 ? x2 : x0) : (k == 0 ? x1 : x0));
+}
+__device__ __forceinline__ double flow_dot(double a0, double a1, double a2, double b0, double b1, double b2) { return (a0 * b0 + a1 * b1) + a2 * b2; }
+
 // the tracer; PUSH: it also deposits what the particle carries (A attributes: a template argument, so that the channels are
 // straight-line code on named registers) wherever it stores a layer
-template <bool PUSH, int A, bool SPAN = false>
-__device__ __forceinline__ void flow_body(const FlowArgs &a, const FlowPush &q, const FlowSpan &span = FlowSpan{}) {
+template <bool PUSH, int A, bool SPAN = false, bool SLIDE = false>
+__device__ __forceinline__ void flow_body(const FlowArgs &a, const FlowPush &q, const FlowSpan &span = FlowSpan{}, const FlowSlide &sl = FlowSlide{}) {
     const int p = blockIdx.x * BLOCK + threadIdx.x;
     if (p >= a.P) return;
     int f = a.start_tri[p];
@@ -102,6 +119,7 @@ __device__ __forceinline__ void flow_body(const FlowArgs &a, const FlowPush &q, 
     }
     const int pitch = 1 << a.tp_shift;
     double act = 0.0;      // (SPAN: the action so far)
+    int slides = 0, steps = 0;      // (SLIDE)
     // (PUSH: one more turn, which only deposits -- layer i at the head of turn i, so that the deposit is in the code once)
     for (int i = 0; PUSH ? i <= a.T : i < a.T; ++i) {
         if (PUSH) {
@@ -112,6 +130,10 @@ __device__ __forceinline__ void flow_body(const FlowArgs &a, const FlowPush &q, 
         if (status == 0) {
             double rem = a.h;
             int crossings = 0;
+            // of the crossing of the turn before: the corners that name the vertices of the edge crossed, and (SLIDE) the corner opposite
+            // that edge (-1: none), the edge rate and the normal speed times the area of the triangle left
+            int ca = 0, cb = 0, ent = -1;
+            double sP = 0.0, mP = 0.0;
             for (;;) {
                 // density of the interval on the triangle, velocity from the momentum of its two nodes
                 // (loading the momentum beside the density instead of behind the floor test changed nothing: 2.38 against 2.37 ms)
@@ -128,12 +150,51 @@ __device__ __forceinline__ void flow_body(const FlowArgs &a, const FlowPush &q, 
                 const double q0 = (t.g00 * u0 + t.g01 * u1) + t.g02 * u2;
                 const double q1 = (t.g10 * u0 + t.g11 * u1) + t.g12 * u2;
                 const double q2 = (t.g20 * u0 + t.g21 * u1) + t.g22 * u2;
+                int left_out = -1;      // (SLIDE: the corner step 4 leaves out after a slide that reached a vertex)
+                if (SLIDE) {
+                    ++steps;
+                    const int c = ent;
+                    ent = -1;
+                    bool over = false;      // the slide ended the interval
+                    const double qc = flow_pick(c, q0, q1, q2);
+                    if (c >= 0 && qc < 0.0) {      // step 3a: this triangle pushes back across the edge just crossed
+                        const double hc0 = flow_pick(c, t.g00, t.g10, t.g20), hc1 = flow_pick(c, t.g01, t.g11, t.g21), hc2 = flow_pick(c, t.g02, t.g12, t.g22);
+                        const double ha0 = flow_pick(ca, t.g00, t.g10, t.g20), ha1 = flow_pick(ca, t.g01, t.g11, t.g21), ha2 = flow_pick(ca, t.g02, t.g12, t.g22);
+                        const double cc = flow_dot(hc0, hc1, hc2, hc0, hc1, hc2), ac = flow_dot(ha0, ha1, ha2, hc0, hc1, hc2);
+                        const double qa = flow_pick(ca, q0, q1, q2);
+                        const double sG = qa - (ac / cc) * qc;
+                        const double mG = (-qc) * sl.area_f[f];
+                        const double s = (mG * sP + mP * sG) / (mP + mG);      // each side weighted with the other side's normal speed
+                        const double la = flow_pick(ca, l0, l1, l2), lb = flow_pick_third(c, ca, l0, l1, l2);      // (cb = 3 - c - ca)
+                        // (one division for both signs of s: tau = l[cb] / s or l[ca] / (-s); s = 0 or NaN takes neither)
+                        const bool up = s > 0.0, moves = up || s < 0.0;
+                        const double tau = (up ? lb : la) / (up ? s : -s);
+                        const bool hits = moves && tau < rem;
+                        const double best = hits ? tau : rem;
+                        const double qh = up ? flow_pick_third(c, ca, q0, q1, q2) : qa;      // the rate of the corner hit: cb (up) or ca
+                        const double aa = flow_dot(ha0, ha1, ha2, ha0, ha1, ha2);
+                        act = act + best * ((s * s) * (cc / (aa * cc - ac * ac)));      // (|d|^2 of the edge from the hat gradients)
+                        const double na = hits && !up ? 0.0 : flow_clamp0(la + best * s), nb = hits && up ? 0.0 : flow_clamp0(lb - best * s);
+                        l0 = c == 0 ? l0 : (ca == 0 ? na : nb);      // (the weight of corner c keeps its 0.0)
+                        l1 = c == 1 ? l1 : (ca == 1 ? na : nb);
+                        l2 = c == 2 ? l2 : (ca == 2 ? na : nb);
+                        ++slides;
+                        // the interval ended; or at the cap, or at the vertex where this triangle does not pass the particle on: a rest
+                        const bool rest = hits && (crossings == a.max_crossings || !(qh < 0.0));
+                        over = !hits || rest;
+                        rem = hits ? rem - best : rem;
+                        rested += rest ? 1 : 0;
+                        crossings += over ? 0 : 1;      // (bounds the loop; a slide is not an edge crossed: `total` stays)
+                        left_out = over ? -1 : c;
+                    }
+                    if (over) break;
+                }
                 // the first weight to reach zero before the interval ends (strict comparisons: the first corner wins a tie)
                 double best = rem;
                 int kmin = -1;
-                if (q0 < 0.0) { const double s = l0 / (-q0); if (s < best) { best = s; kmin = 0; } }
-                if (q1 < 0.0) { const double s = l1 / (-q1); if (s < best) { best = s; kmin = 1; } }
-                if (q2 < 0.0) { const double s = l2 / (-q2); if (s < best) { best = s; kmin = 2; } }
+                if ((!SLIDE || left_out != 0) && q0 < 0.0) { const double s = l0 / (-q0); if (s < best) { best = s; kmin = 0; } }
+                if ((!SLIDE || left_out != 1) && q1 < 0.0) { const double s = l1 / (-q1); if (s < best) { best = s; kmin = 1; } }
+                if ((!SLIDE || left_out != 2) && q2 < 0.0) { const double s = l2 / (-q2); if (s < best) { best = s; kmin = 2; } }
                 if (SPAN) act = act + best * ((u0 * u0 + u1 * u1) + u2 * u2);      // (a step that ends in a stop or a rest has spent best)
                 const double n0 = flow_clamp0(l0 + best * q0), n1 = flow_clamp0(l1 + best * q1), n2 = flow_clamp0(l2 + best * q2);
                 l0 = kmin == 0 ? 0.0 : n0;
@@ -149,7 +210,17 @@ __device__ __forceinline__ void flow_body(const FlowArgs &a, const FlowPush &q, 
                 // the two kept weights go to the corners of the neighbour that name the same vertices
                 const double wa = kmin == 0 ? l1 : (kmin == 1 ? l2 : l0);      // corner (kmin + 1) % 3
                 const double wb = kmin == 0 ? l2 : (kmin == 1 ? l0 : l1);      // corner (kmin + 2) % 3
-                const int ca = (packed >> 2) & 3, cb = packed & 3;
+                if (SLIDE) {      // what step 3a of the next turn needs of the triangle left; ka = (kmin + 1) % 3
+                    const double hk0 = flow_pick(kmin, t.g00, t.g10, t.g20), hk1 = flow_pick(kmin, t.g01, t.g11, t.g21), hk2 = flow_pick(kmin, t.g02, t.g12, t.g22);
+                    const double ha0 = flow_pick(kmin, t.g10, t.g20, t.g00), ha1 = flow_pick(kmin, t.g11, t.g21, t.g01), ha2 = flow_pick(kmin, t.g12, t.g22, t.g02);
+                    const double hh = flow_dot(hk0, hk1, hk2, hk0, hk1, hk2), ah = flow_dot(ha0, ha1, ha2, hk0, hk1, hk2);
+                    const double qk = flow_pick(kmin, q0, q1, q2);
+                    sP = flow_pick(kmin, q1, q2, q0) - (ah / hh) * qk;
+                    mP = (-qk) * sl.area_f[f];
+                }
+                ca = (packed >> 2) & 3;
+                cb = packed & 3;
+                if (SLIDE) ent = 3 - ca - cb;      // the corner of the neighbour opposite the edge crossed
                 l0 = ca == 0 ? wa : (cb == 0 ? wb : 0.0);
                 l1 = ca == 1 ? wa : (cb == 1 ? wb : 0.0);
                 l2 = ca == 2 ? wa : (cb == 2 ? wb : 0.0);
@@ -164,9 +235,18 @@ __device__ __forceinline__ void flow_body(const FlowArgs &a, const FlowPush &q, 
     a.o_w[(int64_t)p * 3] = l0;
     a.o_w[(int64_t)p * 3 + 1] = l1;
     a.o_w[(int64_t)p * 3 + 2] = l2;
-    a.o_status[p] = status;
-    a.o_rested[p] = rested;
-    a.o_cross[p] = total;
+    if (SLIDE) {      // (the five counters are rows of one array: one base pointer held through the loop instead of five)
+        int *o = sl.o_counts + p;
+        o[0] = status;
+        o[(int64_t)a.P] = rested;
+        o[(int64_t)a.P * 2] = total;
+        o[(int64_t)a.P * 3] = slides;
+        o[(int64_t)a.P * 4] = steps;
+    } else {
+        a.o_status[p] = status;
+        a.o_rested[p] = rested;
+        a.o_cross[p] = total;
+    }
     if (PUSH && dropped) atomicAdd(q.acc + (int64_t)(A + 1) * q.L * q.V, (unsigned long long)dropped);      // (the word behind the sums)
 }
 
@@ -176,6 +256,9 @@ __global__ __launch_bounds__(BLOCK) void k_flow_push(FlowArgs a, FlowPush q) { f
 __global__ __launch_bounds__(BLOCK) void k_flow_trace(FlowArgs a, FlowSpan s) { flow_body<false, 0, true>(a, FlowPush{}, s); }
 template <int A>
 __global__ __launch_bounds__(BLOCK) void k_flow_trace_push(FlowArgs a, FlowPush q, FlowSpan s) { flow_body<true, A, true>(a, q, s); }
+__global__ __launch_bounds__(BLOCK) void k_flow_slide(FlowArgs a, FlowSpan s, FlowSlide sl) { flow_body<false, 0, true, true>(a, FlowPush{}, s, sl); }
+template <int A>
+__global__ __launch_bounds__(BLOCK) void k_flow_slide_push(FlowArgs a, FlowPush q, FlowSpan s, FlowSlide sl) { flow_body<true, A, true, true>(a, q, s, sl); }
 
 // One lane per (channel, layer, caller vertex), the vertex fastest: the accumulator of the vertex's device row as a double, times
 // 2^-k_c; a layer of the output is one contiguous run in the caller's numbering, as in k_readout_mu.
@@ -214,6 +297,18 @@ int launch_flow_trace_push(Ctx *c, const FlowArgs &a, const FlowPush &q, const F
     DOTS_HIP(hipGetLastError());
     return 0;
 }
+int launch_flow_slide(Ctx *c, const FlowArgs &a, const FlowSpan &s, const FlowSlide &sl) {
+    hipLaunchKernelGGL(k_flow_slide, dim3((unsigned)((a.P + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, a, s, sl);
+    DOTS_HIP(hipGetLastError());
+    return 0;
+}
+int launch_flow_slide_push(Ctx *c, const FlowArgs &a, const FlowPush &q, const FlowSpan &s, const FlowSlide &sl) {
+    with_constant<0, 1, 2, 3, 4>(q.A, [&](auto A) {
+        hipLaunchKernelGGL(k_flow_slide_push<A.value>, dim3((unsigned)((a.P + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, a, q, s, sl);
+    });
+    DOTS_HIP(hipGetLastError());
+    return 0;
+}
 int launch_flow_push_finish(Ctx *c, const FlowPushFinish &q) {
     const int64_t n = (int64_t)(q.A + 1) * q.L * q.V;
     hipLaunchKernelGGL(k_flow_push_finish, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, q);
@@ -227,6 +322,8 @@ void preload_flow_kernels() {
     (void)hipFuncGetAttributes(&attr, (const void *)k_flow_push_finish);
     (void)hipFuncGetAttributes(&attr, (const void *)k_flow_trace);
     (void)hipFuncGetAttributes(&attr, (const void *)k_flow_trace_push<0>);
+    (void)hipFuncGetAttributes(&attr, (const void *)k_flow_slide);
+    (void)hipFuncGetAttributes(&attr, (const void *)k_flow_slide_push<0>);
     (void)hipGetLastError();
 }
 

@@ -209,14 +209,21 @@ class DeviceProblem:
         self.readout_ms, self.readout_bytes = ms.value, self.debug_counter(9) - before
         return out_mu, out_E, mass, neg
 
-    def flow_map(self, start_triangle, start_weights, neighbours, floor, max_crossings=16, trajectory=False):
+    def flow_map(self, start_triangle, start_weights, neighbours, floor, max_crossings=16, trajectory=False, slide=False):
         """Trace particles through the transport the context holds, on the device (dots_flow_map; flow.flow_map_host on the downloaded
         ``mu`` and ``E`` is the specification and returns the same bits).  ``start_triangle`` (P,), ``start_weights`` (P, 3) and
         ``neighbours`` (F, 3) (``flow.triangle_neighbours``) in the caller's numbering; ``floor`` in the units of the iterate as stored.
         Returns the dict of ``flow_map_host``.  ``self.flow_map_ms`` / ``self.flow_map_bytes``: device milliseconds of the launch and
-        the bytes copied to the host by the last call."""
+        the bytes copied to the host by the last call.  ``slide``: the sliding mode on edges where two triangles push a particle at
+        each other (dots_flow_slide; ``flow_map_host(..., slide=True, areas=plan.area_tri)`` is the specification): the call is
+        ``flow_trace`` over ``(0, n_time)`` with ``slide=True``, and the result gains ``"slides"`` and ``"steps"``."""
         if self.slab:
             raise ValueError("flow_map: not available on time slabs")
+        if slide:
+            out = self.flow_trace(start_triangle, start_weights, neighbours, floor, (0, self.T), max_crossings=max_crossings, trajectory=trajectory,
+                                  slide=True)
+            self.flow_map_ms, self.flow_map_bytes = self.flow_trace_ms, self.flow_trace_bytes
+            return out
         tri = np.ascontiguousarray(start_triangle, dtype=np.int32)
         w = np.ascontiguousarray(start_weights, dtype=np.float64)
         nbr = np.ascontiguousarray(neighbours, dtype=np.int32)
@@ -299,13 +306,15 @@ class DeviceProblem:
         return out
 
     def flow_trace(self, start_triangle, start_weights, neighbours, floor, span, action=False, mass=None, attributes=None, exponents=None,
-                   layers="end", max_crossings=16, trajectory=False):
+                   layers="end", max_crossings=16, trajectory=False, slide=False):
         """``flow_map`` between the time nodes ``span = (node_from, node_to)``, backward where ``node_to < node_from`` (dots_flow_trace;
         ``flow.flow_map_host(..., span=span, action=action)`` on the downloaded ``mu`` and ``E`` is the specification and returns the
         same bits).  ``action``: the result gains ``"action"`` (P,).  ``mass`` (P,): also the deposits of ``flow_push`` on the layers of
         this trace (``attributes``, ``exponents``, ``layers`` as there; ``"end"`` is the state at ``node_to``), and the result gains what
         ``flow_push`` adds.  The trajectory has ``|node_to - node_from| + 1`` layers.  ``self.flow_trace_ms`` / ``self.flow_trace_bytes``:
-        device milliseconds of the launches and the bytes copied to the host by the last call."""
+        device milliseconds of the launches and the bytes copied to the host by the last call.  ``slide``: with the sliding mode
+        (dots_flow_slide; the specification takes ``slide=True, areas=plan.area_tri``, the areas in the caller's numbering): the result
+        gains ``"slides"`` and ``"steps"`` (P,) int32."""
         from . import flow
 
         if self.slab:
@@ -329,7 +338,11 @@ class DeviceProblem:
         if action:
             out["action"] = np.empty(P)
         ms, dropped = C.c_double(), C.c_int64()
-        d = _lib.FlowTraceDesc()
+        whole = _lib.FlowSlideDesc() if slide else None
+        d = whole.trace if slide else _lib.FlowTraceDesc()
+        if slide:
+            out["slides"], out["steps"] = np.empty(P, dtype=np.int32), np.empty(P, dtype=np.int32)
+            whole.slides, whole.steps = _ptr(out["slides"], C.c_int32), _ptr(out["steps"], C.c_int32)
         d.map.n_particles, d.map.max_crossings, d.map.floor = P, int(max_crossings), float(floor)
         d.map.start_triangle, d.map.start_weights, d.map.neighbours = _ptr(tri, C.c_int32), _ptr(w, C.c_double), _ptr(nbr, C.c_int32)
         d.map.triangle, d.map.weights = _ptr(out["triangle"], C.c_int32), _ptr(out["weights"], C.c_double)
@@ -356,7 +369,10 @@ class DeviceProblem:
         elif attributes is not None or exponents is not None:
             raise ValueError("flow_trace: attributes and exponents need a mass")
         before = self.debug_counter(9)
-        _lib.check(self.lib.dots_flow_trace(self._h, C.byref(d)), "dots_flow_trace")
+        if slide:
+            _lib.check(self.lib.dots_flow_slide(self._h, C.byref(whole)), "dots_flow_slide")
+        else:
+            _lib.check(self.lib.dots_flow_trace(self._h, C.byref(d)), "dots_flow_trace")
         self.flow_trace_ms, self.flow_trace_bytes = ms.value, self.debug_counter(9) - before
         if mass is not None:
             out["dropped"], out["exponents"] = int(dropped.value), k

@@ -14,6 +14,9 @@ With ``span=(node_from, node_to)`` and ``action=True`` the same function is the 
 any two time nodes, backward with the velocity negated (the inverse map: a source point for every start on the target, which
 ``pull_back`` turns into a texture pull), and the kinetic action of every particle.
 
+With ``slide=True`` and the triangle ``areas`` it is the specification of ``dots_flow_slide``: on an edge where two neighbouring
+triangles push a particle at each other it moves along the edge (the sliding mode of the discontinuous field) instead of resting.
+
 ``push_forward_host`` is the specification of ``dots_flow_push``: what the particles carry (``start_masses``, attributes) summed onto
 the vertices in 64-bit fixed point with the exponents of ``push_scales`` -- integer sums, so the device returns the same bits in
 every order of arrival.
@@ -84,7 +87,15 @@ def check_span(span, n_time=None, who="flow_map"):
     return a, b
 
 
-def flow_map_host(mu, E, triangles, hat, nbr, start_triangle, start_weights, floor, max_crossings=16, trajectory=False, span=None, action=False):
+def _dot(a, b):
+    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
+
+
+SLIDE_ENDS = ("done", "passed_on", "vertex_rest", "cap")      # how a slide ends (the keys of ``tally`` of flow_map_host)
+
+
+def flow_map_host(mu, E, triangles, hat, nbr, start_triangle, start_weights, floor, max_crossings=16, trajectory=False, span=None, action=False,
+                  slide=False, areas=None, tally=None):
     """Trace particles through the transport ``(mu (T, V) on the intervals, E (T + 1, F, 3) on the nodes)`` -- both in the same units,
     the raw iterate or the recovered solution: they share one recovery factor and only their ratio is used.  ``hat`` (F, 3, 3): the
     hat-function gradients of the plan (``DevicePlan.hat_grad`` in the numbering of ``triangles``; the ones the device holds, not
@@ -121,7 +132,41 @@ def flow_map_host(mu, E, triangles, hat, nbr, start_triangle, start_weights, flo
     ``action=True``: every particle starts with ``act = 0.0``, and after step 4 has found ``best``, once per turn of the inner loop,
     ``uu = (u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]`` and ``act = act + best * uu`` (a step that ends in a stop or a rest has still
     spent ``best``; ``u`` as formed, nothing projected): the time integral of |u|^2 along the path, ``"action"`` (P,) of the result.
-    Its mass-weighted sum is twice the transport cost the particles account for."""
+    Its mass-weighted sum is twice the transport cost the particles account for.
+
+    ``slide=True`` with ``areas`` (F,), the triangle areas of the plan (the specification of ``dots_flow_slide``; False: the above, bit
+    for bit): the sliding mode of the discontinuous velocity field.  Where the triangle a particle has just entered pushes it back
+    across the edge it came through, it moves ALONG that edge with the convex combination of the two velocities whose normal
+    component vanishes (Filippov), instead of crossing back and forth until the cap.  ``dot(a, b) = (a[0] * b[0] + a[1] * b[1]) +
+    a[2] * b[2]``.  Every interval starts with ``ent = -1``.  Step 9 saves, before ``f`` and ``l`` are replaced, with
+    ``ka = (kmin + 1) % 3``:
+
+    - ``hh = dot(hat[f][kmin], hat[f][kmin])``, ``ah = dot(hat[f][ka], hat[f][kmin])``,
+      ``sP = rate[ka] - (ah / hh) * rate[kmin]`` (the rate of the weight of the vertex at corner ka with u projected onto the edge),
+      ``mP = (-rate[kmin]) * areas[f]`` (proportional to the speed at which f pushes across the edge);
+    - ``ca``, ``cb``: the corners of g that name the vertices of corners ka and (kmin + 2) % 3 of f, and ``ent = 3 - ca - cb``, the
+      corner of g opposite the edge just crossed.
+
+    Step 3a, after the rates of a turn are formed, applies if ``ent >= 0 and rate[ent] < 0.0`` (g pushes back), with ``c = ent`` and
+    f now being g:
+
+    - ``cc = dot(hat[f][c], hat[f][c])``, ``ac = dot(hat[f][ca], hat[f][c])``, ``sG = rate[ca] - (ac / cc) * rate[c]``,
+      ``mG = (-rate[c]) * areas[f]``, ``s = (mG * sP + mP * sG) / (mP + mG)`` (each side weighted with the OTHER side's normal speed);
+    - ``best = rem``, ``hit = -1``; if ``s > 0.0``: ``tau = l[cb] / s``, taken with ``hit = cb`` if ``tau < best``; else if ``s < 0.0``:
+      ``tau = l[ca] / (-s)``, taken with ``hit = ca`` if ``tau < best``;
+    - with ``action``: ``aa = dot(hat[f][ca], hat[f][ca])`` and ``act = act + best * ((s * s) * (cc / (aa * cc - ac * ac)))`` (the
+      squared length of the edge from the hat gradients);
+    - ``l[ca] = max(l[ca] + best * s, 0.0)``, ``l[cb] = max(l[cb] - best * s, 0.0)``, ``l[hit] = 0.0`` if ``hit >= 0``; ``slides += 1``;
+    - ``hit < 0``: the interval is done.  Else ``rem = rem - best``; ``crossings == max_crossings``: ``rested += 1``, the interval is
+      done; ``rate[hit] < 0.0`` false: ``rested += 1``, the interval is done (the particle is at a vertex and this triangle does not
+      pass it on round the fan); else ``crossings += 1`` (it bounds the loop; the total ``"crossings"`` is not incremented: a slide is
+      not an edge crossed) and the turn goes on with step 4 with corner c left out of the candidates (it finds ``kmin = hit``,
+      ``best = 0.0``).
+
+    ``ent`` is -1 again after the test of step 3a in every turn, taken or not.  A floored triangle has ``rate = 0`` and never slides.
+    The result gains ``"slides"`` (P,) int32, the slides of every particle, and ``"steps"`` (P,) int32, the turns of its inner loop.
+    ``tally``: a dict which receives, under the keys ``SLIDE_ENDS``, how many slides ended with the interval done, with the vertex
+    passing the particle on, with a rest at the vertex and with a rest at the cap (for tests)."""
     mu_a, E_a = np.asarray(mu, dtype=np.float64), np.asarray(E, dtype=np.float64)
     tri_a = np.asarray(triangles).astype(np.int64)
     T, F = mu_a.shape[0], tri_a.shape[0]
@@ -138,6 +183,14 @@ def flow_map_host(mu, E, triangles, hat, nbr, start_triangle, start_weights, flo
     hat_l = np.asarray(hat, dtype=np.float64).tolist()
     nbr_l = np.asarray(nbr).astype(np.int64).tolist()
     floor, max_crossings = float(floor), int(max_crossings)
+    slide = bool(slide)
+    if slide:
+        if areas is None or np.asarray(areas).shape != (F,):
+            raise ValueError("flow_map_host: slide needs areas (F,), the triangle areas of the plan")
+        area_l = np.asarray(areas, dtype=np.float64).tolist()
+        if tally is not None:
+            for key in SLIDE_ENDS:
+                tally.setdefault(key, 0)
     h = 1.0 / T
     third = 1.0 / 3.0
     out = {"triangle": np.empty(P, dtype=np.int32), "weights": np.empty((P, 3)), "status": np.empty(P, dtype=np.int32),
@@ -154,16 +207,18 @@ def flow_map_host(mu, E, triangles, hat, nbr, start_triangle, start_weights, flo
         out["weights_at"] = np.empty((n + 1, P, 3))
     if action:
         out["action"] = np.empty(P)
+    if slide:
+        out["slides"], out["steps"] = np.empty(P, dtype=np.int32), np.empty(P, dtype=np.int32)
     for p in range(P):
         f = int(start_f[p])
         l = start_w[p].tolist()
-        status = rested = total = 0
+        status = rested = total = slides = steps = 0
         act = 0.0
         if trajectory:
             out["triangles_at"][0, p], out["weights_at"][0, p] = f, l
         for i, j in enumerate(intervals):
             if status == 0:
-                rem, crossings = h, 0
+                rem, crossings, ent = h, 0, -1
                 mu_j, E_j, E_n = mu_l[j], E_l[j], E_l[j + 1]
                 while True:
                     v = tri_l[f]
@@ -177,9 +232,52 @@ def flow_map_host(mu, E, triangles, hat, nbr, start_triangle, start_weights, flo
                         u0 = u1 = u2 = 0.0
                     g = hat_l[f]
                     rate = [(g[k][0] * u0 + g[k][1] * u1) + g[k][2] * u2 for k in range(3)]
+                    steps += 1
+                    left_out = -1
+                    if slide:
+                        c, ent = ent, -1
+                        if c >= 0 and rate[c] < 0.0:      # step 3a: g pushes back across the edge just crossed
+                            cc, ac = _dot(g[c], g[c]), _dot(g[ca], g[c])
+                            sG = rate[ca] - (ac / cc) * rate[c]
+                            mG = (-rate[c]) * area_l[f]
+                            s = (mG * sP + mP * sG) / (mP + mG)
+                            best, hit = rem, -1
+                            if s > 0.0:
+                                tau = l[cb] / s
+                                if tau < best:
+                                    best, hit = tau, cb
+                            elif s < 0.0:
+                                tau = l[ca] / (-s)
+                                if tau < best:
+                                    best, hit = tau, ca
+                            if action:
+                                aa = _dot(g[ca], g[ca])
+                                act = act + best * ((s * s) * (cc / (aa * cc - ac * ac)))
+                            l[ca], l[cb] = _clamp0(l[ca] + best * s), _clamp0(l[cb] - best * s)
+                            if hit >= 0:
+                                l[hit] = 0.0
+                            slides += 1
+                            if hit < 0:
+                                end = "done"
+                            else:
+                                rem = rem - best
+                                if crossings == max_crossings:
+                                    rested += 1
+                                    end = "cap"
+                                elif not rate[hit] < 0.0:
+                                    rested += 1
+                                    end = "vertex_rest"
+                                else:
+                                    crossings += 1
+                                    left_out = c
+                                    end = "passed_on"
+                            if tally is not None:
+                                tally[end] += 1
+                            if left_out < 0:
+                                break
                     best, kmin = rem, -1
                     for k in range(3):
-                        if rate[k] < 0.0:
+                        if k != left_out and rate[k] < 0.0:
                             s = l[k] / (-rate[k])
                             if s < best:
                                 best, kmin = s, k
@@ -202,11 +300,20 @@ def flow_map_host(mu, E, triangles, hat, nbr, start_triangle, start_weights, flo
                     moved = [0.0, 0.0, 0.0]
                     for k in ((kmin + 1) % 3, (kmin + 2) % 3):
                         moved[tri_l[g].index(v[k])] = l[k]
+                    if slide:      # what step 3a of the next turn needs of the triangle left
+                        ka, hf = (kmin + 1) % 3, hat_l[f]
+                        hh, ah = _dot(hf[kmin], hf[kmin]), _dot(hf[ka], hf[kmin])
+                        sP = rate[ka] - (ah / hh) * rate[kmin]
+                        mP = (-rate[kmin]) * area_l[f]
+                        ca, cb = tri_l[g].index(v[ka]), tri_l[g].index(v[(kmin + 2) % 3])
+                        ent = 3 - ca - cb
                     f, l = g, moved
             if trajectory:
                 out["triangles_at"][i + 1, p], out["weights_at"][i + 1, p] = f, l
         if action:
             out["action"][p] = act
+        if slide:
+            out["slides"][p], out["steps"][p] = slides, steps
         out["triangle"][p], out["weights"][p], out["status"][p], out["rested"][p], out["crossings"][p] = f, l, status, rested, total
     return out
 

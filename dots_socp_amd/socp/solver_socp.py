@@ -64,7 +64,7 @@ def check_time_nodes(n_time, lap_solver="modal_direct", time_slab=None, pcg_wind
             raise ValueError(f"lap_solver='modal_pcg' needs n_time + 1 <= {MODAL_PCG_MAX_NODES} (got {nodes}); use lap_solver='modal_direct'")
 
 
-FLOW_MAP_KEYS = ("starts", "floor", "max_crossings", "trajectory", "push", "span", "action")
+FLOW_MAP_KEYS = ("starts", "floor", "max_crossings", "trajectory", "push", "span", "action", "slide")
 FLOW_PUSH_KEYS = ("mass", "attributes", "layers")
 
 
@@ -140,6 +140,8 @@ def check_flow_map(flow_map, time_slab=None, n_time=None):
         raise ValueError(f"flow_map: unknown option(s) {sorted(unknown)}; known: {list(FLOW_MAP_KEYS)}")
     if "starts" in flow_map:
         _check_flow_starts(flow_map["starts"])
+    if not isinstance(flow_map.get("slide", False), (bool, np.bool_)):
+        raise ValueError("flow_map: slide must be True or False")
     span = _check_flow_span(flow_map.get("span"), flow_map.get("action", False), n_time)
     _check_flow_push(flow_map.get("push"), flow_map.get("starts", "vertices"), span, n_time)
     return dict(flow_map)
@@ -698,7 +700,7 @@ class AlmSolver:
         mu, E, info = self._read_out(self.r * self.dual_scale, w_vertex, w_triangle, centred, mu0, mu1, sums=True)
         return {"mu": mu, "E": E}, info
 
-    def flow_map(self, starts="vertices", floor=None, max_crossings=16, trajectory=False, push=None, span=None, action=False):
+    def flow_map(self, starts="vertices", floor=None, max_crossings=16, trajectory=False, push=None, span=None, action=False, slide=False):
         """The transport map of the current iterate, traced on the device (DeviceProblem.flow_map; flow.flow_map_host is the
         specification): where the mass at a point ends up, and with ``trajectory`` where it is after every interval.
         ``starts``: "vertices" (one particle on every vertex: flow.vertex_starts), "triangles" or ``("triangles", level)`` (one on
@@ -720,14 +722,23 @@ class AlmSolver:
         gains ``"span"``, ``"nodes"`` (n + 1,): the time node of every layer, and ``"action"`` (P,) on request; the trajectory has
         n + 1 layers.  The default mass of a push is that of ``mu0`` where ``node_from == 0`` and of ``mu1`` where
         ``node_from == n_time`` (a ``ValueError`` asks for ``mass`` otherwise); ``pushed["to_mu1"]`` is given only where
-        ``node_to == n_time``, and ``pushed["to_mu0"]``, the same comparison against ``mu0``, where ``node_to == 0``."""
+        ``node_to == n_time``, and ``pushed["to_mu0"]``, the same comparison against ``mu0``, where ``node_to == 0``.
+        ``slide``: the sliding mode (DeviceProblem.flow_trace with ``slide=True``: dots_flow_slide; ``flow_map_host(..., slide=True,
+        areas)`` is the specification): where two triangles push a particle at each other across their edge it moves along the edge
+        instead of resting there.  Without a span the trace is ``(0, n_time)``.  The result gains ``"slides"`` and ``"steps"`` (P,),
+        and ``pushed`` ``"slid_mass"``, the mass of the particles that slid at least once, beside the rested and the stopped mass.
+        With ``slide=False`` the calls are the ones above."""
         from .. import evaluate, flow
         from . import _geometry_with_areas
 
         if self.dev.slab:
             raise ValueError("flow_map is not available on time slabs: the particles are traced on one GPU, which holds every time node")
         n_time = self.dev.T
+        if not isinstance(slide, (bool, np.bool_)):
+            raise ValueError("flow_map: slide must be True or False")
         span = _check_flow_span(span, action, n_time)
+        if slide and span is None:
+            span = (0, n_time)
         push = _check_flow_push(push, starts, span, n_time)
         vertices, triangles = np.asarray(self.geometry["vertices"], dtype=np.float64), np.asarray(self.geometry["triangles"])
         named = _check_flow_starts(starts)
@@ -753,13 +764,15 @@ class AlmSolver:
                 mass = np.asarray(mass, dtype=np.float64)
             out = dev.flow_trace(start_triangle, start_weights, self._neighbours, float(floor) / (self.r * self.dual_scale), span, action=bool(action),
                                  mass=mass, attributes=None if push is None else push["attributes"], layers="end" if push is None else push["layers"],
-                                 max_crossings=max_crossings, trajectory=trajectory)
+                                 max_crossings=max_crossings, trajectory=trajectory, slide=bool(slide))
             out["ms"], out["bytes"] = dev.flow_trace_ms, dev.flow_trace_bytes
             out["span"] = span
             out["nodes"] = np.arange(span[0], span[1] + (1 if span[1] > span[0] else -1), 1 if span[1] > span[0] else -1)
             if push is not None:
                 pushed = {"mass": out.pop("mass_at"), "attributes": out.pop("attr_at"), "dropped": out.pop("dropped"), "exponents": out.pop("exponents"),
                           "rested_mass": float(np.sum(mass[out["rested"] > 0])), "stopped_mass": float(np.sum(mass[out["status"] == 1]))}
+                if slide:
+                    pushed["slid_mass"] = float(np.sum(mass[out["slides"] > 0]))
                 if span[1] == n_time:
                     pushed["to_mu1"] = evaluate.compare_with_exact_transportation(pushed["mass"][-1], np.asarray(g["mu1"], dtype=np.float64), g)
                 if span[1] == 0:

@@ -769,6 +769,32 @@ typedef struct dots_flow_trace_desc {
 } dots_flow_trace_desc;
 int dots_flow_trace(dots_ctx *ctx, const dots_flow_trace_desc *desc);
 
+/* dots_flow_slide: dots_flow_trace with the sliding mode of the discontinuous velocity field.  dots_socp_amd/flow.py:
+ * flow_map_host(..., span, action, slide=True, areas) and push_forward_host are the specification, and every output equals them
+ * bit for bit.
+ * Where the triangle a particle has just entered pushes it back across the edge it came through (the rate of the weight of the
+ * corner opposite that edge is negative), dots_flow_trace crosses back and forth in zero time until max_crossings and rests for
+ * what is left of the interval.  Here the particle moves ALONG the edge instead, with the convex combination of the two
+ * velocities whose normal component vanishes (Filippov): s = (mG sP + mP sG) / (mP + mG), sP and sG the two triangles' rates of
+ * the weight of one end of the edge with the velocity projected onto the edge, mP and mG their normal speeds times their areas
+ * (the context's triangle areas).  The slide lasts until the interval ends or a vertex is reached; there the triangle either
+ * passes the particle on round the fan (an ordinary exit with no time spent) or, if it does not, the particle rests at the
+ * vertex (`rested`).  A slide counts towards max_crossings within its interval but not in `crossings`; its action is the time
+ * spent times the squared speed along the edge.  flow.py states the steps in their order of operations.
+ * slides: the slides of every particle; steps: the turns of its inner loop (one per stretch of straight motion or slide).
+ * Everything else is dots_flow_trace: the span in either direction, the action, the deposits (trace.mass), the layers; the same
+ * contract (pending penalty division, z_mid, state left alone, every Laplacian solver and n_time + 1 <= 1024, batch members on
+ * their own stream; output bytes in dots_debug_counter 9: 4 more per particle, 8 with steps); one more kernel family
+ * (k_flow_slide, k_flow_slide_push<A>), the same launches.
+ * DOTS_ERR_ARGUMENT (nothing launched, the context stays usable): what dots_flow_trace refuses; a NULL slides.
+ * DOTS_ERR_STATE: a time slab. */
+typedef struct dots_flow_slide_desc {
+    dots_flow_trace_desc trace;     /* everything dots_flow_trace takes and returns                                      */
+    int32_t *slides;                /* host out [n_particles], required                                                  */
+    int32_t *steps;                 /* NULL, or host out [n_particles]: turns of the inner loop                          */
+} dots_flow_slide_desc;
+int dots_flow_slide(dots_ctx *ctx, const dots_flow_slide_desc *desc);
+
 /* ---- levels of a cascade in space from ONE mesh: coarsen on the host, locate on the device ------------------------------------
  * dots_coarsen: half-edge-collapse decimation of the mesh (xyz [V][3], tri [F][3]) towards `n_target` vertices, host only (no
  * device work; dots_socp_amd/meshes.py: coarsen(backend="python") is the specification and states the rules; both return the same
@@ -834,7 +860,7 @@ int dots_bench_kernel(dots_ctx *ctx, int which, int reps, double *ms_per_launch,
  * batched solve (dots_laplacian_solve_many, dots_step_many, dots_bench_many) enqueued, read on the batch's first context, 8 of those, the
  * launches that took fewer right-hand sides than their chunk of DOTS_FRONT_NR problems held because NR regions of LDS would not fit or
  * a workgroup of 1024 threads takes fewer (the launch was split), 9 bytes this context has copied device -> host through dots_download,
- * dots_readout, dots_flow_map, dots_flow_push and dots_flow_trace since it was created (the layer sums of dots_readout are written by the device itself and not copied), 10 device
+ * dots_readout, dots_flow_map, dots_flow_push, dots_flow_trace and dots_flow_slide since it was created (the layer sums of dots_readout are written by the device itself and not copied), 10 device
  * allocations this context holds for its factor (0 without one, also after a dots_front_setup that failed), 11 the launches the
  * last multigrid V-cycle enqueued on this context took, as a bit mask: 1 restriction with a workgroup per coarse row, 2 restriction
  * with a thread per entry, 4 coarsest solve with a workgroup per row, 8 coarsest solve with a thread per entry, 16 the one-launch
