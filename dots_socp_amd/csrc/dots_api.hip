@@ -1778,27 +1778,41 @@ static int flow_prepare(Ctx *c) {
     return 0;
 }
 
-// What dots_flow_map, dots_flow_push, dots_flow_trace and dots_flow_slide share: the checks of the embedded description, the caller's starts and
-// neighbour table in the device numbering (host preparation), the allocation of the call, the launch and the copies back.  `push`
-// null: no deposits.  `span` null: the intervals 0 .. T - 1 with the kernels of dots_flow_map / dots_flow_push; else the intervals
-// between two nodes, in either direction, with the kernels of dots_flow_trace.  `slide` (with a span): the kernels of dots_flow_slide.
-struct FlowSpanRequest {
-    int node_from, node_to;
-    double *action;      // host out [n_particles], or null
+// What dots_flow_map, dots_flow_push, dots_flow_trace and dots_flow_slide ask for, as one record: the embedded description, and what is
+// optional beside it.  Without nodes the trace is the whole horizon, node 0 to node n_time.
+struct FlowRequest {
+    const char *who;                                 // the entry point, for the messages
+    const dots_flow_map_desc *map;
+    const dots_flow_push_desc *push = nullptr;       // the deposit fields (its `map` is not read), or null: no deposits
+    bool nodes = false;                              // node_from and node_to are the caller's, and are checked
+    int node_from = 0, node_to = 0;
+    double *action = nullptr;                        // host out [n_particles], or null
+    bool slide = false;                              // the sliding mode; `slides` is then required
+    int32_t *slides = nullptr, *steps = nullptr;     // host out [n_particles]; steps may be null
 };
-struct FlowSlideRequest {
-    int32_t *slides;     // host out [n_particles]
-    int32_t *steps;      // host out [n_particles], or null
-};
-static int flow_run(dots_ctx *c, const char *who, const dots_flow_map_desc *desc, const dots_flow_push_desc *push, const FlowSpanRequest *span = nullptr,
-                    const FlowSlideRequest *slide = nullptr) {
-    const std::string w = std::string(who) + ": ";
+// The request of a trace description; `deposits` holds its deposit fields as dots_flow_push takes them.
+static FlowRequest flow_trace_request(const char *who, const dots_flow_trace_desc &t, dots_flow_push_desc &deposits) {
+    deposits = dots_flow_push_desc{};
+    deposits.mass = t.mass; deposits.n_attributes = t.n_attributes; deposits.all_layers = t.all_layers; deposits.attributes = t.attributes;
+    deposits.scale_exponent = t.scale_exponent; deposits.mass_at = t.mass_at; deposits.attr_at = t.attr_at; deposits.dropped = t.dropped;
+    deposits.ms = t.ms;
+    FlowRequest r{who, &t.map};
+    if (t.mass) r.push = &deposits;
+    r.nodes = true; r.node_from = t.node_from; r.node_to = t.node_to; r.action = t.action;
+    return r;
+}
+// The one call path of the four entry points: the checks of the request, the caller's starts and neighbour table in the device
+// numbering (host preparation), the allocation of the call, the launch and the copies back.
+static int flow_run(dots_ctx *c, const FlowRequest &req) {
+    const dots_flow_map_desc *desc = req.map;
+    const dots_flow_push_desc *push = req.push;
+    const std::string w = std::string(req.who) + ": ";
     if (c->shard_stride != 0) { set_error(w + "not available on time slabs"); return DOTS_ERR_STATE; }
     const Dev &d = c->d;
-    if (slide && (!span || !slide->slides)) { set_error(w + "null pointer (slides is required)"); return DOTS_ERR_ARGUMENT; }
-    if (span) {
-        if (span->node_from < 0 || span->node_from > d.T || span->node_to < 0 || span->node_to > d.T) { set_error(w + "a time node outside 0 .. n_time"); return DOTS_ERR_ARGUMENT; }
-        if (span->node_from == span->node_to) { set_error(w + "node_from equals node_to: no interval to trace"); return DOTS_ERR_ARGUMENT; }
+    if (req.slide && !req.slides) { set_error(w + "null pointer (slides is required)"); return DOTS_ERR_ARGUMENT; }
+    if (req.nodes) {
+        if (req.node_from < 0 || req.node_from > d.T || req.node_to < 0 || req.node_to > d.T) { set_error(w + "a time node outside 0 .. n_time"); return DOTS_ERR_ARGUMENT; }
+        if (req.node_from == req.node_to) { set_error(w + "node_from equals node_to: no interval to trace"); return DOTS_ERR_ARGUMENT; }
     }
     const bool outputs = desc->triangle && desc->weights && desc->status && desc->rested && desc->crossings;
     if (!desc->start_triangle || !desc->start_weights || !desc->neighbours || (!push && !outputs)) {
@@ -1824,7 +1838,8 @@ static int flow_run(dots_ctx *c, const char *who, const dots_flow_map_desc *desc
     if (rc) return rc;
     const FlowHost &fh = *c->flow;
     const int P = desc->n_particles, F = d.F, T = d.T;
-    const int n_turns = span ? std::abs(span->node_to - span->node_from) : T;      // intervals traversed
+    const int node_from = req.nodes ? req.node_from : 0, node_to = req.nodes ? req.node_to : T;
+    const int n_turns = std::abs(node_to - node_from);      // intervals traversed
     auto to_dev = [&](int f) { return fh.inv_f.empty() ? f : fh.inv_f[f]; };
     // the starts, in the device numbering
     std::vector<int> h_start((size_t)P);
@@ -1883,8 +1898,8 @@ static int flow_run(dots_ctx *c, const char *who, const dots_flow_map_desc *desc
     const size_t n_wat = desc->weights_at ? layers * P * 3 : 0, n_tat = desc->triangles_at ? layers * P : 0;
     const size_t L = push ? (push->all_layers ? layers : 1) : 0;
     const size_t n_acc = push ? (size_t)(A + 1) * L * (size_t)d.V : 0, n_carry = push ? (size_t)(A + 1) * P : 0;
-    const size_t n_act = span && span->action ? (size_t)P : 0;
-    const size_t n_slides = slide ? (size_t)P : 0, n_steps = n_slides;      // (the kernel counts the steps in any case; copied on request)
+    const size_t n_act = req.action ? (size_t)P : 0;
+    const size_t n_slides = req.slide ? (size_t)P : 0, n_steps = n_slides;      // (the kernel counts the steps in any case; copied on request)
     const size_t n_dbl = (size_t)P * 3 * 2 + n_wat + n_carry + n_acc + n_act, n_u64 = push ? n_acc + 1 : 0,
                  n_int = (size_t)P * 5 + (size_t)F * 3 + n_tat + n_slides + n_steps;
     void *buf = nullptr;
@@ -1916,26 +1931,19 @@ static int flow_run(dots_ctx *c, const char *who, const dots_flow_map_desc *desc
         a.floor = desc->floor;
         a.h = 1.0 / (double)T;
         a.P = P; a.T = n_turns; a.tp_shift = d.tp_shift; a.max_crossings = desc->max_crossings;
-        FlowSpan sp{};
-        if (span) {      // forward: the intervals node_from + i; backward: node_from - 1 - i
-            const bool forward = span->node_to > span->node_from;
-            sp.j0 = forward ? span->node_from : span->node_from - 1;
-            sp.dj = forward ? 1 : -1;
-            sp.action = n_act ? b_act : nullptr;
-        }
-        FlowSlide sl{};
-        if (slide) { sl.area_f = d.area_f; sl.o_counts = b_status; }
+        const bool forward = node_to > node_from;      // forward: the intervals node_from + i; backward: node_from - 1 - i
+        const FlowSpan sp{n_act ? b_act : nullptr, forward ? node_from : node_from - 1, forward ? 1 : -1};
+        const FlowSlide sl{d.area_f, b_status};
         DOTS_HIP(hipEventRecord(c->ev[0], c->stream));
-        int r;
         if (push) {      // (the milliseconds hold the zeroing, the trace with its deposits and the conversion)
             q.acc = b_acc; q.mass = b_mass; q.attr = b_attr;
             q.A = A; q.L = (int)L; q.V = d.V;
             DOTS_HIP(hipMemsetAsync(b_acc, 0, sizeof(unsigned long long) * n_u64, c->stream));
             fin.acc = b_acc; fin.inv = c->inv_perm_v; fin.out = b_pushed; fin.A = A; fin.L = (int)L; fin.V = d.V;
-            if ((r = slide ? launch_flow_slide_push(c, a, q, sp, sl) : span ? launch_flow_trace_push(c, a, q, sp) : launch_flow_push(c, a, q)) ||
-                (r = launch_flow_push_finish(c, fin)))
-                return r;
-        } else if ((r = slide ? launch_flow_slide(c, a, sp, sl) : span ? launch_flow_trace(c, a, sp) : launch_flow_map(c, a))) return r;
+        }
+        int r = launch_flow(c, a, sp, push ? &q : nullptr, req.slide ? &sl : nullptr);
+        if (!r && push) r = launch_flow_push_finish(c, fin);
+        if (r) return r;
         DOTS_HIP(hipEventRecord(c->ev[1], c->stream));
         // only the outputs cross to the host
         if (desc->weights) DOTS_HIP(hipMemcpyAsync(desc->weights, b_ow, sizeof(double) * (size_t)P * 3, hipMemcpyDeviceToHost, c->stream));
@@ -1945,9 +1953,9 @@ static int flow_run(dots_ctx *c, const char *who, const dots_flow_map_desc *desc
             if (outs[i]) DOTS_HIP(hipMemcpyAsync(outs[i], srcs[i], sizeof(int) * (size_t)P, hipMemcpyDeviceToHost, c->stream));
         if (desc->weights_at) DOTS_HIP(hipMemcpyAsync(desc->weights_at, b_wat, sizeof(double) * n_wat, hipMemcpyDeviceToHost, c->stream));
         if (desc->triangles_at) DOTS_HIP(hipMemcpyAsync(desc->triangles_at, b_tat, sizeof(int) * n_tat, hipMemcpyDeviceToHost, c->stream));
-        if (n_act) DOTS_HIP(hipMemcpyAsync(span->action, b_act, sizeof(double) * n_act, hipMemcpyDeviceToHost, c->stream));
-        if (n_slides) DOTS_HIP(hipMemcpyAsync(slide->slides, b_slides, sizeof(int) * n_slides, hipMemcpyDeviceToHost, c->stream));
-        if (slide && slide->steps) DOTS_HIP(hipMemcpyAsync(slide->steps, b_steps, sizeof(int) * n_steps, hipMemcpyDeviceToHost, c->stream));
+        if (n_act) DOTS_HIP(hipMemcpyAsync(req.action, b_act, sizeof(double) * n_act, hipMemcpyDeviceToHost, c->stream));
+        if (n_slides) DOTS_HIP(hipMemcpyAsync(req.slides, b_slides, sizeof(int) * n_slides, hipMemcpyDeviceToHost, c->stream));
+        if (req.slide && req.steps) DOTS_HIP(hipMemcpyAsync(req.steps, b_steps, sizeof(int) * n_steps, hipMemcpyDeviceToHost, c->stream));
         if (push) {
             const size_t n_layer = L * (size_t)d.V;
             DOTS_HIP(hipMemcpyAsync(push->mass_at, b_pushed, sizeof(double) * n_layer, hipMemcpyDeviceToHost, c->stream));
@@ -1968,7 +1976,7 @@ static int flow_run(dots_ctx *c, const char *who, const dots_flow_map_desc *desc
     }
     (void)hipFree(buf);
     if (rc) return rc;
-    size_t bytes = sizeof(double) * (n_wat + n_act) + sizeof(int) * (n_tat + n_slides + (slide && slide->steps ? n_steps : 0)) + (desc->weights ? sizeof(double) * (size_t)P * 3 : 0);
+    size_t bytes = sizeof(double) * (n_wat + n_act) + sizeof(int) * (n_tat + n_slides + (req.slide && req.steps ? n_steps : 0)) + (desc->weights ? sizeof(double) * (size_t)P * 3 : 0);
     for (const int32_t *o : {desc->triangle, desc->status, desc->rested, desc->crossings}) bytes += o ? sizeof(int) * (size_t)P : 0;
     if (push) bytes += sizeof(double) * n_acc + (push->dropped ? sizeof(int64_t) : 0);
     c->d2h_bytes += (int64_t)bytes;
@@ -1978,39 +1986,29 @@ static int flow_run(dots_ctx *c, const char *who, const dots_flow_map_desc *desc
 int dots_flow_map(dots_ctx *c, const dots_flow_map_desc *desc) {
     if (!c) { set_error("null context"); return DOTS_ERR_ARGUMENT; }
     if (!desc) { set_error("flow_map: null description"); return DOTS_ERR_ARGUMENT; }
-    return flow_run(c, "flow_map", desc, nullptr);
+    return flow_run(c, FlowRequest{"flow_map", desc});
 }
 
 int dots_flow_push(dots_ctx *c, const dots_flow_push_desc *desc) {
     if (!c) { set_error("null context"); return DOTS_ERR_ARGUMENT; }
     if (!desc) { set_error("flow_push: null description"); return DOTS_ERR_ARGUMENT; }
-    return flow_run(c, "flow_push", &desc->map, desc);
+    return flow_run(c, FlowRequest{"flow_push", &desc->map, desc});
 }
 
 int dots_flow_trace(dots_ctx *c, const dots_flow_trace_desc *desc) {
     if (!c) { set_error("null context"); return DOTS_ERR_ARGUMENT; }
     if (!desc) { set_error("flow_trace: null description"); return DOTS_ERR_ARGUMENT; }
-    const FlowSpanRequest span{desc->node_from, desc->node_to, desc->action};
-    if (!desc->mass) return flow_run(c, "flow_trace", &desc->map, nullptr, &span);
-    dots_flow_push_desc push{};      // (the deposit fields, as dots_flow_push takes them; `map` is passed beside it)
-    push.mass = desc->mass; push.n_attributes = desc->n_attributes; push.all_layers = desc->all_layers; push.attributes = desc->attributes;
-    push.scale_exponent = desc->scale_exponent; push.mass_at = desc->mass_at; push.attr_at = desc->attr_at; push.dropped = desc->dropped;
-    push.ms = desc->ms;
-    return flow_run(c, "flow_trace", &desc->map, &push, &span);
+    dots_flow_push_desc deposits;
+    return flow_run(c, flow_trace_request("flow_trace", *desc, deposits));
 }
 
 int dots_flow_slide(dots_ctx *c, const dots_flow_slide_desc *desc) {
     if (!c) { set_error("null context"); return DOTS_ERR_ARGUMENT; }
     if (!desc) { set_error("flow_slide: null description"); return DOTS_ERR_ARGUMENT; }
-    const dots_flow_trace_desc &t = desc->trace;
-    const FlowSpanRequest span{t.node_from, t.node_to, t.action};
-    const FlowSlideRequest slide{desc->slides, desc->steps};
-    if (!t.mass) return flow_run(c, "flow_slide", &t.map, nullptr, &span, &slide);
-    dots_flow_push_desc push{};      // (the deposit fields, as dots_flow_push takes them; `map` is passed beside it)
-    push.mass = t.mass; push.n_attributes = t.n_attributes; push.all_layers = t.all_layers; push.attributes = t.attributes;
-    push.scale_exponent = t.scale_exponent; push.mass_at = t.mass_at; push.attr_at = t.attr_at; push.dropped = t.dropped;
-    push.ms = t.ms;
-    return flow_run(c, "flow_slide", &t.map, &push, &span, &slide);
+    dots_flow_push_desc deposits;
+    FlowRequest req = flow_trace_request("flow_slide", desc->trace, deposits);
+    req.slide = true; req.slides = desc->slides; req.steps = desc->steps;
+    return flow_run(c, req);
 }
 
 int dots_front_enable(dots_ctx *c, int on) {

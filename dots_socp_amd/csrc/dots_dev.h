@@ -402,8 +402,9 @@ int launch_readout(Ctx *c, bool is_E, double *out, const int *inv, const double 
 int readout_workgroups(const Ctx *c);
 int launch_readout_fold(Ctx *c, const double *part, int layers, int n_wg, double *out);      // out[2 l], out[2 l + 1]: sum / negative sum of layer l
 void preload_readout_kernels();
-// dots_flow_map (kernels_flow.hip): one lane per particle, the loop over the intervals inside the kernel.  Everything in the DEVICE
-// numbering except the triangles written out, which perm_f takes back to the caller's.
+// The flow map (kernels_flow.hip): one lane per particle, the loop over the intervals inside the kernel.  Everything in the DEVICE
+// numbering except the triangles written out, which perm_f takes back to the caller's.  A launch takes FlowArgs and FlowSpan, with
+// deposits FlowPush, with the sliding mode FlowSlide: separate by-value kernel arguments, in the order args, push, span, slide.
 struct FlowArgs {
     const double *mu, *E;        // the state where it lies: [V][TP], [F][3][TP]
     const int *tri;              // [F][3]
@@ -417,9 +418,9 @@ struct FlowArgs {
     int *tri_at;                 // [T + 1][P], or null
     double *w_at;                // [T + 1][P][3], or null
     double floor, h;
-    int P, T, tp_shift, max_crossings;      // (dots_flow_trace: T is the number of intervals traversed, h still 1 / n_time)
+    int P, T, tp_shift, max_crossings;      // T is the number of intervals traversed, h is 1 / n_time
 };
-// dots_flow_trace: turn i = 0 .. T - 1 takes the interval j0 + i dj; dj = -1 traces backward (the velocity negated)
+// turn i = 0 .. T - 1 takes the interval j0 + i dj; dj = -1 traces backward (the velocity negated).  The whole horizon is j0 = 0, dj = 1.
 struct FlowSpan {
     double *action;              // [P] sum of best |u|^2 over the steps, or null
     int j0, dj;
@@ -427,8 +428,7 @@ struct FlowSpan {
 // neighbour g, and the corners of g that name the vertices of corners (k + 1) % 3 and (k + 2) % 3 of the triangle the entry belongs to
 constexpr int FLOW_MAX_TRIANGLES = 1 << 27;
 inline int flow_pack_neighbour(int g, int ca, int cb) { return (g << 4) | (ca << 2) | cb; }
-int launch_flow_map(Ctx *c, const FlowArgs &a);
-// dots_flow_push: what the tracer deposits besides.  Channel 0 is the mass, channels 1 .. A the mass times an attribute.
+// what the tracer deposits besides.  Channel 0 is the mass, channels 1 .. A the mass times an attribute.
 constexpr int FLOW_PUSH_CHANNELS = 5;
 struct FlowPush {
     unsigned long long *acc;     // [A + 1][L][V] fixed-point sums, DEVICE vertex numbering, then one word: the contributions that
@@ -445,19 +445,15 @@ struct FlowPushFinish {
     double unscale[FLOW_PUSH_CHANNELS];    // 2^-k_c
     int A, L, V;
 };
-int launch_flow_push(Ctx *c, const FlowArgs &a, const FlowPush &q);
-int launch_flow_push_finish(Ctx *c, const FlowPushFinish &q);
-int launch_flow_trace(Ctx *c, const FlowArgs &a, const FlowSpan &s);
-int launch_flow_trace_push(Ctx *c, const FlowArgs &a, const FlowPush &q, const FlowSpan &s);
-// dots_flow_slide: what the sliding mode reads and writes besides (a struct of its own: the arguments of the kernels before it stay)
-// The slide kernels write their five per-particle counters as the rows of ONE array and leave FlowArgs::o_status / o_rested /
-// o_cross alone: five output pointers held in scalar registers through the loop made k_flow_slide_push<A> spill 12 - 18 of them.
+// What the sliding mode reads and writes besides.  The slide kernels write their five per-particle counters as the rows of ONE array
+// and leave FlowArgs::o_status / o_rested / o_cross alone: five output pointers held in scalar registers through the loop made
+// k_flow_slide_push<A> spill 12 - 18 of them.
 struct FlowSlide {
     const double *area_f;        // [F] Dev::area_f, device numbering
     int *o_counts;               // [5][P]: status, rested, crossings, slides, steps (the turns of the inner loop)
 };
-int launch_flow_slide(Ctx *c, const FlowArgs &a, const FlowSpan &s, const FlowSlide &sl);
-int launch_flow_slide_push(Ctx *c, const FlowArgs &a, const FlowPush &q, const FlowSpan &s, const FlowSlide &sl);
+int launch_flow(Ctx *c, const FlowArgs &a, const FlowSpan &s, const FlowPush *push, const FlowSlide *slide);      // push / slide: null without
+int launch_flow_push_finish(Ctx *c, const FlowPushFinish &q);
 void preload_flow_kernels();
 // what dots_flow_map checks the caller's tables against, downloaded once per context
 struct FlowHost {

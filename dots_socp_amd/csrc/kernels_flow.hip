@@ -1,33 +1,32 @@
-// Flow map (dots_flow_map): particles traced through the transport on the device -- where the mass at a point ends up, and where it
-// is after every interval.  dots_socp_amd/flow.py: flow_map_host is the specification; the operations below are its operations in
-// its order (the build has -ffp-contract=off, fp64 division is correctly rounded), so the outputs equal it bit for bit.  It extends
-// what the reference returns (solver_socp.py:855-869, mu and E) without moving the two arrays to the host.
+// The flow map (dots_flow_map, dots_flow_push, dots_flow_trace, dots_flow_slide): particles traced through the transport on the device
+// -- where the mass at a point ends up, where it is after every interval, what it carries there, how far it moved.
+// dots_socp_amd/flow.py is the specification (flow_map_host, push_forward_host); the operations below are its operations in its order
+// (the build has -ffp-contract=off, fp64 division is correctly rounded), so the outputs equal it bit for bit.  It extends what the
+// reference returns (solver_socp.py:855-869, mu and E) without moving the two arrays to the host.
 //
-// One lane per particle; the loop over the intervals is inside the kernel because a particle's steps depend on each other.  A lane
-// reads the state where it lies (rows of mu and E, time fastest): a particle that stays in its triangle reads neighbouring doubles in
-// successive intervals.  The triangle's vertices and hat gradients stay in registers until the particle crosses an edge.  The three
-// weights and rates live in named registers and are selected with conditions: an array indexed by the exit corner would go to scratch.
-// It runs once per solve: the yardstick is the download of mu and E it replaces, not a roofline.
+// One tracer body, flow_body<PUSH, A, SLIDE>, one lane per particle; the loop over the intervals is inside the kernel because a
+// particle's steps depend on each other.  A lane reads the state where it lies (rows of mu and E, time fastest): a particle that stays
+// in its triangle reads neighbouring doubles in successive intervals.  The triangle's vertices and hat gradients stay in registers
+// until the particle crosses an edge.  The three weights and rates live in named registers and are selected with conditions: an array
+// indexed by the exit corner would go to scratch.  It runs once per solve: the yardstick is the download of mu and E it replaces,
+// not a roofline.
 //
-// dots_flow_push is the same tracer (flow_body<PUSH = true>) which also deposits what the particle carries on the vertices of its
-// triangle at every layer, in 64-bit fixed point with integer atomics (flow.py: push_forward_host is the specification), and
-// k_flow_push_finish, which turns the sums into doubles in the caller's vertex numbering.  k_flow_map is the PUSH = false
-// instantiation: the code it had.
+// Every trace is a span (FlowSpan): the a.T intervals j = j0 + i dj, i = 0 .. a.T - 1, between two time nodes, forward (dj = 1) or
+// backward (dj = -1: the velocity negated), with the kinetic action, the sum of best |u|^2 along the path, stored on request.  The
+// whole horizon of dots_flow_map / dots_flow_push is j0 = 0, dj = 1, a.T = n_time.  Direction and start are run-time values: a sign
+// flip and an add per turn beside six fp64 divisions, where a template flag would double the instantiations for nothing.
 //
-// dots_flow_trace is the same tracer once more (flow_body<PUSH, A, SPAN = true>): the a.T intervals j = j0 + i dj, i = 0 .. a.T - 1,
-// between two time nodes, forward (dj = 1) or backward (dj = -1: the velocity negated), and the kinetic action sum of best |u|^2
-// along the path.  Direction and start are run-time values of FlowSpan: a sign flip and an add per turn beside six fp64 divisions;
-// a template flag would double the instantiations for nothing (registers: DESIGN.md section 9).  The SPAN = false instantiations
-// are the code they were.
-//
-// dots_flow_slide is the tracer with the sliding mode of the discontinuous field (flow_body<PUSH, A, SPAN = true, SLIDE = true>;
-// flow.py: step 3a of flow_map_host): where the triangle just entered pushes the particle back across the edge it came through, it
-// moves along that edge with the combination of the two velocities whose normal part vanishes, instead of crossing back and forth
-// until the cap and resting.  What step 3a needs of the triangle left (two doubles and the two shared corners) is formed at the
-// crossing and stays in registers; the corner-indexed reads are selects on the named registers.  The end of a slide is selects,
-// not branches, and the five per-particle counters go to the rows of one array (FlowSlide::o_counts): with the branches and five
-// output pointers k_flow_slide_push<A> spilled 12 - 20 scalar registers.  The SLIDE = false instantiations are the code they were
-// (registers: DESIGN.md section 9).
+// The template flags are the two that change what a lane holds in registers (DESIGN.md section 9 has the table):
+// - PUSH, with the number of attributes A: the tracer also deposits what the particle carries on the vertices of its triangle at
+//   every layer, in 64-bit fixed point with integer atomics; k_flow_push_finish turns the sums into doubles in the caller's vertex
+//   numbering.  A is a template argument so that the channels are straight-line code on named registers.
+// - SLIDE: the sliding mode of the discontinuous field (flow.py: step 3a of flow_map_host): where the triangle just entered pushes the
+//   particle back across the edge it came through, it moves along that edge with the combination of the two velocities whose normal
+//   part vanishes, instead of crossing back and forth until the cap and resting.  What step 3a needs of the triangle left (two
+//   doubles and the two shared corners) is formed at the crossing and stays in registers; the corner-indexed reads are selects on the
+//   named registers.  The end of a slide is selects, not branches, and the five per-particle counters go to the rows of one array
+//   (FlowSlide::o_counts): one base pointer held through the loop.  With the branches and five output pointers
+//   k_flow_slide_push<A> spilled 12 - 20 scalar registers.
 #include "dots_dev.h"
 
 namespace dots {
@@ -100,8 +99,8 @@ __device__ __forceinline__ double flow_dot(double a0, double a1, double a2, doub
 
 // the tracer; PUSH: it also deposits what the particle carries (A attributes: a template argument, so that the channels are
 // straight-line code on named registers) wherever it stores a layer
-template <bool PUSH, int A, bool SPAN = false, bool SLIDE = false>
-__device__ __forceinline__ void flow_body(const FlowArgs &a, const FlowPush &q, const FlowSpan &span = FlowSpan{}, const FlowSlide &sl = FlowSlide{}) {
+template <bool PUSH, int A, bool SLIDE = false>
+__device__ __forceinline__ void flow_body(const FlowArgs &a, const FlowPush &q, const FlowSpan &span, const FlowSlide &sl = FlowSlide{}) {
     const int p = blockIdx.x * BLOCK + threadIdx.x;
     if (p >= a.P) return;
     int f = a.start_tri[p];
@@ -118,7 +117,7 @@ __device__ __forceinline__ void flow_body(const FlowArgs &a, const FlowPush &q, 
         for (int c = 1; c <= A; ++c) g[c] = g[0] * q.attr[(int64_t)(c - 1) * a.P + p];
     }
     const int pitch = 1 << a.tp_shift;
-    double act = 0.0;      // (SPAN: the action so far)
+    double act = 0.0;      // the action so far
     int slides = 0, steps = 0;      // (SLIDE)
     // (PUSH: one more turn, which only deposits -- layer i at the head of turn i, so that the deposit is in the code once)
     for (int i = 0; PUSH ? i <= a.T : i < a.T; ++i) {
@@ -126,7 +125,7 @@ __device__ __forceinline__ void flow_body(const FlowArgs &a, const FlowPush &q, 
             flow_deposit<A>(a, q, i, t, l0, l1, l2, g, dropped);
             if (i == a.T) break;
         }
-        const int j = SPAN ? span.j0 + i * span.dj : i;      // the interval of turn i (SPAN: a.T is the number of intervals traversed)
+        const int j = span.j0 + i * span.dj;      // the interval of turn i (a.T is the number of intervals traversed)
         if (status == 0) {
             double rem = a.h;
             int crossings = 0;
@@ -144,7 +143,7 @@ __device__ __forceinline__ void flow_body(const FlowArgs &a, const FlowPush &q, 
                     u0 = (0.5 * (e[0] + e[1])) / rho;
                     u1 = (0.5 * (e[pitch] + e[pitch + 1])) / rho;
                     u2 = (0.5 * (e[2 * pitch] + e[2 * pitch + 1])) / rho;
-                    if (SPAN && span.dj < 0) { u0 = -u0; u1 = -u1; u2 = -u2; }      // (backward; a floored triangle keeps +0.0)
+                    if (span.dj < 0) { u0 = -u0; u1 = -u1; u2 = -u2; }      // (backward; a floored triangle keeps +0.0)
                 }
                 // time derivatives of the weights
                 const double q0 = (t.g00 * u0 + t.g01 * u1) + t.g02 * u2;
@@ -195,7 +194,7 @@ __device__ __forceinline__ void flow_body(const FlowArgs &a, const FlowPush &q, 
                 if ((!SLIDE || left_out != 0) && q0 < 0.0) { const double s = l0 / (-q0); if (s < best) { best = s; kmin = 0; } }
                 if ((!SLIDE || left_out != 1) && q1 < 0.0) { const double s = l1 / (-q1); if (s < best) { best = s; kmin = 1; } }
                 if ((!SLIDE || left_out != 2) && q2 < 0.0) { const double s = l2 / (-q2); if (s < best) { best = s; kmin = 2; } }
-                if (SPAN) act = act + best * ((u0 * u0 + u1 * u1) + u2 * u2);      // (a step that ends in a stop or a rest has spent best)
+                act = act + best * ((u0 * u0 + u1 * u1) + u2 * u2);      // (a step that ends in a stop or a rest has spent best)
                 const double n0 = flow_clamp0(l0 + best * q0), n1 = flow_clamp0(l1 + best * q1), n2 = flow_clamp0(l2 + best * q2);
                 l0 = kmin == 0 ? 0.0 : n0;
                 l1 = kmin == 1 ? 0.0 : n1;
@@ -230,7 +229,7 @@ __device__ __forceinline__ void flow_body(const FlowArgs &a, const FlowPush &q, 
         }
         flow_store_layer(a, i + 1, p, f, l0, l1, l2);
     }
-    if (SPAN && span.action) span.action[p] = act;
+    if (span.action) span.action[p] = act;
     a.o_tri[p] = a.perm_f ? a.perm_f[f] : f;
     a.o_w[(int64_t)p * 3] = l0;
     a.o_w[(int64_t)p * 3 + 1] = l1;
@@ -250,15 +249,12 @@ __device__ __forceinline__ void flow_body(const FlowArgs &a, const FlowPush &q, 
     if (PUSH && dropped) atomicAdd(q.acc + (int64_t)(A + 1) * q.L * q.V, (unsigned long long)dropped);      // (the word behind the sums)
 }
 
-__global__ __launch_bounds__(BLOCK) void k_flow_map(FlowArgs a) { flow_body<false, 0>(a, FlowPush{}); }
+__global__ __launch_bounds__(BLOCK) void k_flow_trace(FlowArgs a, FlowSpan s) { flow_body<false, 0>(a, FlowPush{}, s); }
 template <int A>
-__global__ __launch_bounds__(BLOCK) void k_flow_push(FlowArgs a, FlowPush q) { flow_body<true, A>(a, q); }
-__global__ __launch_bounds__(BLOCK) void k_flow_trace(FlowArgs a, FlowSpan s) { flow_body<false, 0, true>(a, FlowPush{}, s); }
+__global__ __launch_bounds__(BLOCK) void k_flow_trace_push(FlowArgs a, FlowPush q, FlowSpan s) { flow_body<true, A>(a, q, s); }
+__global__ __launch_bounds__(BLOCK) void k_flow_slide(FlowArgs a, FlowSpan s, FlowSlide sl) { flow_body<false, 0, true>(a, FlowPush{}, s, sl); }
 template <int A>
-__global__ __launch_bounds__(BLOCK) void k_flow_trace_push(FlowArgs a, FlowPush q, FlowSpan s) { flow_body<true, A, true>(a, q, s); }
-__global__ __launch_bounds__(BLOCK) void k_flow_slide(FlowArgs a, FlowSpan s, FlowSlide sl) { flow_body<false, 0, true, true>(a, FlowPush{}, s, sl); }
-template <int A>
-__global__ __launch_bounds__(BLOCK) void k_flow_slide_push(FlowArgs a, FlowPush q, FlowSpan s, FlowSlide sl) { flow_body<true, A, true, true>(a, q, s, sl); }
+__global__ __launch_bounds__(BLOCK) void k_flow_slide_push(FlowArgs a, FlowPush q, FlowSpan s, FlowSlide sl) { flow_body<true, A, true>(a, q, s, sl); }
 
 // One lane per (channel, layer, caller vertex), the vertex fastest: the accumulator of the vertex's device row as a double, times
 // 2^-k_c; a layer of the output is one contiguous run in the caller's numbering, as in k_readout_mu.
@@ -273,39 +269,16 @@ __global__ __launch_bounds__(BLOCK) void k_flow_push_finish(FlowPushFinish q) {
     q.out[i] = (double)s * q.unscale[c];
 }
 
-int launch_flow_map(Ctx *c, const FlowArgs &a) {
-    hipLaunchKernelGGL(k_flow_map, dim3((unsigned)((a.P + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, a);
-    DOTS_HIP(hipGetLastError());
-    return 0;
-}
-int launch_flow_push(Ctx *c, const FlowArgs &a, const FlowPush &q) {
-    with_constant<0, 1, 2, 3, 4>(q.A, [&](auto A) {
-        hipLaunchKernelGGL(k_flow_push<A.value>, dim3((unsigned)((a.P + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, a, q);
-    });
-    DOTS_HIP(hipGetLastError());
-    return 0;
-}
-int launch_flow_trace(Ctx *c, const FlowArgs &a, const FlowSpan &s) {
-    hipLaunchKernelGGL(k_flow_trace, dim3((unsigned)((a.P + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, a, s);
-    DOTS_HIP(hipGetLastError());
-    return 0;
-}
-int launch_flow_trace_push(Ctx *c, const FlowArgs &a, const FlowPush &q, const FlowSpan &s) {
-    with_constant<0, 1, 2, 3, 4>(q.A, [&](auto A) {
-        hipLaunchKernelGGL(k_flow_trace_push<A.value>, dim3((unsigned)((a.P + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, a, q, s);
-    });
-    DOTS_HIP(hipGetLastError());
-    return 0;
-}
-int launch_flow_slide(Ctx *c, const FlowArgs &a, const FlowSpan &s, const FlowSlide &sl) {
-    hipLaunchKernelGGL(k_flow_slide, dim3((unsigned)((a.P + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, a, s, sl);
-    DOTS_HIP(hipGetLastError());
-    return 0;
-}
-int launch_flow_slide_push(Ctx *c, const FlowArgs &a, const FlowPush &q, const FlowSpan &s, const FlowSlide &sl) {
-    with_constant<0, 1, 2, 3, 4>(q.A, [&](auto A) {
-        hipLaunchKernelGGL(k_flow_slide_push<A.value>, dim3((unsigned)((a.P + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, a, q, s, sl);
-    });
+// the tracer of a request: `push` null: no deposits; `slide` null: without the sliding mode
+int launch_flow(Ctx *c, const FlowArgs &a, const FlowSpan &s, const FlowPush *push, const FlowSlide *slide) {
+    const dim3 grid((unsigned)((a.P + BLOCK - 1) / BLOCK)), block(BLOCK);
+    if (push)
+        with_constant<0, 1, 2, 3, 4>(push->A, [&](auto A) {
+            if (slide) hipLaunchKernelGGL(k_flow_slide_push<A.value>, grid, block, 0, c->stream, a, *push, s, *slide);
+            else hipLaunchKernelGGL(k_flow_trace_push<A.value>, grid, block, 0, c->stream, a, *push, s);
+        });
+    else if (slide) hipLaunchKernelGGL(k_flow_slide, grid, block, 0, c->stream, a, s, *slide);
+    else hipLaunchKernelGGL(k_flow_trace, grid, block, 0, c->stream, a, s);
     DOTS_HIP(hipGetLastError());
     return 0;
 }
@@ -317,8 +290,6 @@ int launch_flow_push_finish(Ctx *c, const FlowPushFinish &q) {
 }
 void preload_flow_kernels() {
     hipFuncAttributes attr;
-    (void)hipFuncGetAttributes(&attr, (const void *)k_flow_map);
-    (void)hipFuncGetAttributes(&attr, (const void *)k_flow_push<0>);
     (void)hipFuncGetAttributes(&attr, (const void *)k_flow_push_finish);
     (void)hipFuncGetAttributes(&attr, (const void *)k_flow_trace);
     (void)hipFuncGetAttributes(&attr, (const void *)k_flow_trace_push<0>);

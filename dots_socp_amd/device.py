@@ -224,31 +224,7 @@ class DeviceProblem:
                                   slide=True)
             self.flow_map_ms, self.flow_map_bytes = self.flow_trace_ms, self.flow_trace_bytes
             return out
-        tri = np.ascontiguousarray(start_triangle, dtype=np.int32)
-        w = np.ascontiguousarray(start_weights, dtype=np.float64)
-        nbr = np.ascontiguousarray(neighbours, dtype=np.int32)
-        if tri.ndim != 1 or w.shape != (tri.shape[0], 3):
-            raise ValueError(f"flow_map: start_triangle (P,) and start_weights (P, 3) expected, got {tri.shape} and {w.shape}")
-        if nbr.shape != (self.F, 3):
-            raise ValueError(f"flow_map: neighbours must have shape ({self.F}, 3), got {nbr.shape}")
-        P = tri.shape[0]
-        out = {"triangle": np.empty(P, dtype=np.int32), "weights": np.empty((P, 3)), "status": np.empty(P, dtype=np.int32),
-               "rested": np.empty(P, dtype=np.int32), "crossings": np.empty(P, dtype=np.int32)}
-        if trajectory:
-            out["triangles_at"] = np.empty((self.T + 1, P), dtype=np.int32)
-            out["weights_at"] = np.empty((self.T + 1, P, 3))
-        ms = C.c_double()
-        d = _lib.FlowMapDesc()
-        d.n_particles, d.max_crossings, d.floor = P, int(max_crossings), float(floor)
-        d.start_triangle, d.start_weights, d.neighbours = _ptr(tri, C.c_int32), _ptr(w, C.c_double), _ptr(nbr, C.c_int32)
-        d.triangle, d.weights = _ptr(out["triangle"], C.c_int32), _ptr(out["weights"], C.c_double)
-        d.status, d.rested, d.crossings = _ptr(out["status"], C.c_int32), _ptr(out["rested"], C.c_int32), _ptr(out["crossings"], C.c_int32)
-        d.triangles_at, d.weights_at = _ptr(out.get("triangles_at"), C.c_int32), _ptr(out.get("weights_at"), C.c_double)
-        d.ms = C.pointer(ms)
-        before = self.debug_counter(9)
-        _lib.check(self.lib.dots_flow_map(self._h, C.byref(d)), "dots_flow_map")
-        self.flow_map_ms, self.flow_map_bytes = ms.value, self.debug_counter(9) - before
-        return out
+        return self._flow("flow_map", start_triangle, start_weights, neighbours, floor, max_crossings, trajectory)
 
     def flow_push(self, start_triangle, start_weights, neighbours, floor, mass, attributes=None, exponents=None, layers="end",
                   max_crossings=16, trajectory=False):
@@ -258,52 +234,8 @@ class DeviceProblem:
         Returns the dict of ``flow_map`` plus ``"mass_at"`` (L, V), ``"attr_at"`` (A, L, V) or None, ``"dropped"`` and ``"exponents"``.
         ``self.flow_push_ms`` / ``self.flow_push_bytes``: device milliseconds (zeroing, trace with deposits, conversion) and the
         bytes copied to the host by the last call."""
-        from . import flow
-
-        if self.slab:
-            raise ValueError("flow_push: not available on time slabs")
-        if layers not in ("end", "all"):
-            raise ValueError("flow_push: layers must be 'end' or 'all'")
-        tri = np.ascontiguousarray(start_triangle, dtype=np.int32)
-        w = np.ascontiguousarray(start_weights, dtype=np.float64)
-        nbr = np.ascontiguousarray(neighbours, dtype=np.int32)
-        if tri.ndim != 1 or w.shape != (tri.shape[0], 3):
-            raise ValueError(f"flow_push: start_triangle (P,) and start_weights (P, 3) expected, got {tri.shape} and {w.shape}")
-        if nbr.shape != (self.F, 3):
-            raise ValueError(f"flow_push: neighbours must have shape ({self.F}, 3), got {nbr.shape}")
-        P = tri.shape[0]
-        m = np.ascontiguousarray(mass, dtype=np.float64)
-        a = None if attributes is None else np.ascontiguousarray(attributes, dtype=np.float64)
-        A = 0 if a is None else a.shape[0]
-        if m.shape != (P,) or (a is not None and (a.ndim != 2 or a.shape[1] != P)):
-            raise ValueError(f"flow_push: mass ({P},) and attributes (A, {P}) expected")
-        k = np.ascontiguousarray(flow.push_scales(m, a, w) if exponents is None else exponents, dtype=np.int32)
-        if k.shape != (1 + A,):
-            raise ValueError(f"flow_push: {1 + A} exponents expected, got {k.shape}")
-        L = self.T + 1 if layers == "all" else 1
-        out = {"triangle": np.empty(P, dtype=np.int32), "weights": np.empty((P, 3)), "status": np.empty(P, dtype=np.int32),
-               "rested": np.empty(P, dtype=np.int32), "crossings": np.empty(P, dtype=np.int32)}
-        if trajectory:
-            out["triangles_at"] = np.empty((self.T + 1, P), dtype=np.int32)
-            out["weights_at"] = np.empty((self.T + 1, P, 3))
-        out["mass_at"] = np.empty((L, self.V))
-        out["attr_at"] = np.empty((A, L, self.V)) if A else None
-        ms, dropped = C.c_double(), C.c_int64()
-        d = _lib.FlowPushDesc()
-        d.map.n_particles, d.map.max_crossings, d.map.floor = P, int(max_crossings), float(floor)
-        d.map.start_triangle, d.map.start_weights, d.map.neighbours = _ptr(tri, C.c_int32), _ptr(w, C.c_double), _ptr(nbr, C.c_int32)
-        d.map.triangle, d.map.weights = _ptr(out["triangle"], C.c_int32), _ptr(out["weights"], C.c_double)
-        d.map.status, d.map.rested, d.map.crossings = _ptr(out["status"], C.c_int32), _ptr(out["rested"], C.c_int32), _ptr(out["crossings"], C.c_int32)
-        d.map.triangles_at, d.map.weights_at = _ptr(out.get("triangles_at"), C.c_int32), _ptr(out.get("weights_at"), C.c_double)
-        d.mass, d.n_attributes, d.all_layers = _ptr(m, C.c_double), A, int(layers == "all")
-        d.attributes, d.scale_exponent = _ptr(a, C.c_double), _ptr(k, C.c_int32)
-        d.mass_at, d.attr_at = _ptr(out["mass_at"], C.c_double), _ptr(out["attr_at"], C.c_double)
-        d.dropped, d.ms = C.pointer(dropped), C.pointer(ms)
-        before = self.debug_counter(9)
-        _lib.check(self.lib.dots_flow_push(self._h, C.byref(d)), "dots_flow_push")
-        self.flow_push_ms, self.flow_push_bytes = ms.value, self.debug_counter(9) - before
-        out["dropped"], out["exponents"] = int(dropped.value), k
-        return out
+        return self._flow("flow_push", start_triangle, start_weights, neighbours, floor, max_crossings, trajectory, mass=mass, attributes=attributes,
+                          exponents=exponents, layers=layers)
 
     def flow_trace(self, start_triangle, start_weights, neighbours, floor, span, action=False, mass=None, attributes=None, exponents=None,
                    layers="end", max_crossings=16, trajectory=False, slide=False):
@@ -315,20 +247,29 @@ class DeviceProblem:
         device milliseconds of the launches and the bytes copied to the host by the last call.  ``slide``: with the sliding mode
         (dots_flow_slide; the specification takes ``slide=True, areas=plan.area_tri``, the areas in the caller's numbering): the result
         gains ``"slides"`` and ``"steps"`` (P,) int32."""
+        return self._flow("flow_trace", start_triangle, start_weights, neighbours, floor, max_crossings, trajectory, span=span, action=action,
+                          slide=slide, mass=mass, attributes=attributes, exponents=exponents, layers=layers)
+
+    def _flow(self, who, start_triangle, start_weights, neighbours, floor, max_crossings, trajectory, span=None, action=False, slide=False,
+              mass=None, attributes=None, exponents=None, layers="end"):
+        """What ``flow_map``, ``flow_push`` and ``flow_trace`` share; ``who`` names the method: it prefixes the messages, chooses the
+        description and the entry point (``dots_<who>``; ``dots_flow_slide`` with ``slide``) and the ``<who>_ms`` / ``<who>_bytes`` set.
+        Checks the arguments, allocates the result (``span`` None: the whole horizon), fills the embedded ``dots_flow_map_desc``
+        wherever it sits in the description and, with a mass, the deposit fields, and brackets the call with the byte counter."""
         from . import flow
 
         if self.slab:
-            raise ValueError("flow_trace: not available on time slabs")
-        node_from, node_to = flow.check_span(span, self.T, "flow_trace")
+            raise ValueError(f"{who}: not available on time slabs")
+        node_from, node_to = (0, self.T) if span is None else flow.check_span(span, self.T, who)
         if layers not in ("end", "all"):
-            raise ValueError("flow_trace: layers must be 'end' or 'all'")
+            raise ValueError(f"{who}: layers must be 'end' or 'all'")
         tri = np.ascontiguousarray(start_triangle, dtype=np.int32)
         w = np.ascontiguousarray(start_weights, dtype=np.float64)
         nbr = np.ascontiguousarray(neighbours, dtype=np.int32)
         if tri.ndim != 1 or w.shape != (tri.shape[0], 3):
-            raise ValueError(f"flow_trace: start_triangle (P,) and start_weights (P, 3) expected, got {tri.shape} and {w.shape}")
+            raise ValueError(f"{who}: start_triangle (P,) and start_weights (P, 3) expected, got {tri.shape} and {w.shape}")
         if nbr.shape != (self.F, 3):
-            raise ValueError(f"flow_trace: neighbours must have shape ({self.F}, 3), got {nbr.shape}")
+            raise ValueError(f"{who}: neighbours must have shape ({self.F}, 3), got {nbr.shape}")
         P, n = tri.shape[0], abs(node_to - node_from)
         out = {"triangle": np.empty(P, dtype=np.int32), "weights": np.empty((P, 3)), "status": np.empty(P, dtype=np.int32),
                "rested": np.empty(P, dtype=np.int32), "crossings": np.empty(P, dtype=np.int32)}
@@ -337,44 +278,53 @@ class DeviceProblem:
             out["weights_at"] = np.empty((n + 1, P, 3))
         if action:
             out["action"] = np.empty(P)
-        ms, dropped = C.c_double(), C.c_int64()
-        whole = _lib.FlowSlideDesc() if slide else None
-        d = whole.trace if slide else _lib.FlowTraceDesc()
         if slide:
             out["slides"], out["steps"] = np.empty(P, dtype=np.int32), np.empty(P, dtype=np.int32)
-            whole.slides, whole.steps = _ptr(out["slides"], C.c_int32), _ptr(out["steps"], C.c_int32)
-        d.map.n_particles, d.map.max_crossings, d.map.floor = P, int(max_crossings), float(floor)
-        d.map.start_triangle, d.map.start_weights, d.map.neighbours = _ptr(tri, C.c_int32), _ptr(w, C.c_double), _ptr(nbr, C.c_int32)
-        d.map.triangle, d.map.weights = _ptr(out["triangle"], C.c_int32), _ptr(out["weights"], C.c_double)
-        d.map.status, d.map.rested, d.map.crossings = _ptr(out["status"], C.c_int32), _ptr(out["rested"], C.c_int32), _ptr(out["crossings"], C.c_int32)
-        d.map.triangles_at, d.map.weights_at = _ptr(out.get("triangles_at"), C.c_int32), _ptr(out.get("weights_at"), C.c_double)
-        d.node_from, d.node_to, d.action = node_from, node_to, _ptr(out.get("action"), C.c_double)
-        d.map.ms = C.pointer(ms)
-        if mass is not None:
-            m = np.ascontiguousarray(mass, dtype=np.float64)
+        ms, dropped = C.c_double(), C.c_int64()
+        # the description of the entry point: `whole` is passed, `d` holds the deposit fields, `m` is the embedded map description
+        if who == "flow_map":
+            whole = d = m = _lib.FlowMapDesc()
+        elif who == "flow_push":
+            whole = d = _lib.FlowPushDesc()
+            m = d.map
+        else:
+            whole = _lib.FlowSlideDesc() if slide else _lib.FlowTraceDesc()
+            d = whole.trace if slide else whole
+            m = d.map
+            d.node_from, d.node_to, d.action = node_from, node_to, _ptr(out.get("action"), C.c_double)
+            if slide:
+                whole.slides, whole.steps = _ptr(out["slides"], C.c_int32), _ptr(out["steps"], C.c_int32)
+        m.n_particles, m.max_crossings, m.floor = P, int(max_crossings), float(floor)
+        m.start_triangle, m.start_weights, m.neighbours = _ptr(tri, C.c_int32), _ptr(w, C.c_double), _ptr(nbr, C.c_int32)
+        m.triangle, m.weights = _ptr(out["triangle"], C.c_int32), _ptr(out["weights"], C.c_double)
+        m.status, m.rested, m.crossings = _ptr(out["status"], C.c_int32), _ptr(out["rested"], C.c_int32), _ptr(out["crossings"], C.c_int32)
+        m.triangles_at, m.weights_at = _ptr(out.get("triangles_at"), C.c_int32), _ptr(out.get("weights_at"), C.c_double)
+        m.ms = C.pointer(ms)
+        push = who == "flow_push" or mass is not None
+        if push:
+            mass = np.ascontiguousarray(mass, dtype=np.float64)
             a = None if attributes is None else np.ascontiguousarray(attributes, dtype=np.float64)
             A = 0 if a is None else a.shape[0]
-            if m.shape != (P,) or (a is not None and (a.ndim != 2 or a.shape[1] != P)):
-                raise ValueError(f"flow_trace: mass ({P},) and attributes (A, {P}) expected")
-            k = np.ascontiguousarray(flow.push_scales(m, a, w) if exponents is None else exponents, dtype=np.int32)
+            if mass.shape != (P,) or (a is not None and (a.ndim != 2 or a.shape[1] != P)):
+                raise ValueError(f"{who}: mass ({P},) and attributes (A, {P}) expected")
+            k = np.ascontiguousarray(flow.push_scales(mass, a, w) if exponents is None else exponents, dtype=np.int32)
             if k.shape != (1 + A,):
-                raise ValueError(f"flow_trace: {1 + A} exponents expected, got {k.shape}")
+                raise ValueError(f"{who}: {1 + A} exponents expected, got {k.shape}")
             L = n + 1 if layers == "all" else 1
             out["mass_at"] = np.empty((L, self.V))
             out["attr_at"] = np.empty((A, L, self.V)) if A else None
-            d.mass, d.n_attributes, d.all_layers = _ptr(m, C.c_double), A, int(layers == "all")
+            d.mass, d.n_attributes, d.all_layers = _ptr(mass, C.c_double), A, int(layers == "all")
             d.attributes, d.scale_exponent = _ptr(a, C.c_double), _ptr(k, C.c_int32)
             d.mass_at, d.attr_at = _ptr(out["mass_at"], C.c_double), _ptr(out["attr_at"], C.c_double)
             d.dropped = C.pointer(dropped)
         elif attributes is not None or exponents is not None:
-            raise ValueError("flow_trace: attributes and exponents need a mass")
+            raise ValueError(f"{who}: attributes and exponents need a mass")
+        entry = "dots_flow_slide" if slide else "dots_" + who
         before = self.debug_counter(9)
-        if slide:
-            _lib.check(self.lib.dots_flow_slide(self._h, C.byref(whole)), "dots_flow_slide")
-        else:
-            _lib.check(self.lib.dots_flow_trace(self._h, C.byref(d)), "dots_flow_trace")
-        self.flow_trace_ms, self.flow_trace_bytes = ms.value, self.debug_counter(9) - before
-        if mass is not None:
+        _lib.check(getattr(self.lib, entry)(self._h, C.byref(whole)), entry)
+        setattr(self, who + "_ms", ms.value)
+        setattr(self, who + "_bytes", self.debug_counter(9) - before)
+        if push:
             out["dropped"], out["exponents"] = int(dropped.value), k
         return out
 

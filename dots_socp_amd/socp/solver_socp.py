@@ -753,46 +753,36 @@ class AlmSolver:
             floor = 1e-3 * float(np.max(np.asarray(g["mu0"], dtype=np.float64) / (np.asarray(g["area_vertices"], dtype=np.float64) / 3.0)))
         if getattr(self, "_neighbours", None) is None:
             self._neighbours = flow.triangle_neighbours(triangles)
-        dev = self.dev
-        if span is not None:
-            mass = None
-            if push is not None:
-                mass = push["mass"]
-                if mass is None:
-                    mass = flow.start_masses(g["mu0" if span[0] == 0 else "mu1"], g["area_vertices"], g["area_triangles"], triangles, start_triangle,
-                                             start_weights, named[1])
-                mass = np.asarray(mass, dtype=np.float64)
-            out = dev.flow_trace(start_triangle, start_weights, self._neighbours, float(floor) / (self.r * self.dual_scale), span, action=bool(action),
-                                 mass=mass, attributes=None if push is None else push["attributes"], layers="end" if push is None else push["layers"],
-                                 max_crossings=max_crossings, trajectory=trajectory, slide=bool(slide))
-            out["ms"], out["bytes"] = dev.flow_trace_ms, dev.flow_trace_bytes
-            out["span"] = span
-            out["nodes"] = np.arange(span[0], span[1] + (1 if span[1] > span[0] else -1), 1 if span[1] > span[0] else -1)
-            if push is not None:
-                pushed = {"mass": out.pop("mass_at"), "attributes": out.pop("attr_at"), "dropped": out.pop("dropped"), "exponents": out.pop("exponents"),
-                          "rested_mass": float(np.sum(mass[out["rested"] > 0])), "stopped_mass": float(np.sum(mass[out["status"] == 1]))}
-                if slide:
-                    pushed["slid_mass"] = float(np.sum(mass[out["slides"] > 0]))
-                if span[1] == n_time:
-                    pushed["to_mu1"] = evaluate.compare_with_exact_transportation(pushed["mass"][-1], np.asarray(g["mu1"], dtype=np.float64), g)
-                if span[1] == 0:
-                    pushed["to_mu0"] = evaluate.compare_with_exact_transportation(pushed["mass"][-1], np.asarray(g["mu0"], dtype=np.float64), g)
-                out["pushed"] = pushed
-        elif push is None:
-            out = dev.flow_map(start_triangle, start_weights, self._neighbours, float(floor) / (self.r * self.dual_scale),
-                               max_crossings=max_crossings, trajectory=trajectory)
-            out["ms"], out["bytes"] = dev.flow_map_ms, dev.flow_map_bytes
-        else:
+        dev, floor = self.dev, float(floor) / (self.r * self.dual_scale)
+        node_from, node_to = (0, n_time) if span is None else span
+        mass = None
+        if push is not None:      # (the default: mu0 from node 0, mu1 from node n_time; _check_flow_push refused an interior start)
             mass = push["mass"]
             if mass is None:
-                mass = flow.start_masses(g["mu0"], g["area_vertices"], g["area_triangles"], triangles, start_triangle, start_weights, named[1])
+                mass = flow.start_masses(g["mu0" if node_from == 0 else "mu1"], g["area_vertices"], g["area_triangles"], triangles, start_triangle,
+                                         start_weights, named[1])
             mass = np.asarray(mass, dtype=np.float64)
-            out = dev.flow_push(start_triangle, start_weights, self._neighbours, float(floor) / (self.r * self.dual_scale), mass,
-                                attributes=push["attributes"], layers=push["layers"], max_crossings=max_crossings, trajectory=trajectory)
-            out["ms"], out["bytes"] = dev.flow_push_ms, dev.flow_push_bytes
+        common = dict(max_crossings=max_crossings, trajectory=trajectory)
+        if span is not None:
+            call, who = dev.flow_trace, "flow_trace"
+            common.update(span=span, action=bool(action), slide=bool(slide))
+        else:
+            call, who = (dev.flow_map, "flow_map") if push is None else (dev.flow_push, "flow_push")
+        if push is not None:
+            common.update(mass=mass, attributes=push["attributes"], layers=push["layers"])
+        out = call(start_triangle, start_weights, self._neighbours, floor, **common)
+        out["ms"], out["bytes"] = getattr(dev, who + "_ms"), getattr(dev, who + "_bytes")
+        if span is not None:
+            step = 1 if node_to > node_from else -1
+            out["span"], out["nodes"] = span, np.arange(node_from, node_to + step, step)
+        if push is not None:
             pushed = {"mass": out.pop("mass_at"), "attributes": out.pop("attr_at"), "dropped": out.pop("dropped"), "exponents": out.pop("exponents"),
                       "rested_mass": float(np.sum(mass[out["rested"] > 0])), "stopped_mass": float(np.sum(mass[out["status"] == 1]))}
-            pushed["to_mu1"] = evaluate.compare_with_exact_transportation(pushed["mass"][-1], np.asarray(g["mu1"], dtype=np.float64), g)
+            if slide:
+                pushed["slid_mass"] = float(np.sum(mass[out["slides"] > 0]))
+            for end, key in ((n_time, "mu1"), (0, "mu0")):
+                if node_to == end:
+                    pushed["to_" + key] = evaluate.compare_with_exact_transportation(pushed["mass"][-1], np.asarray(g[key], dtype=np.float64), g)
             out["pushed"] = pushed
         out["positions"] = flow.positions(vertices, triangles, out["triangle"], out["weights"])
         if trajectory:

@@ -749,8 +749,8 @@ int dots_flow_push(dots_ctx *ctx, const dots_flow_push_desc *desc);
  * mass NULL: no deposits, the deposit fields are ignored and the five per-particle outputs of `map` are required.  Otherwise the
  * deposits of dots_flow_push on the layers of this trace: all_layers = 0 gives L = 1, the state at node_to; else L = n + 1.
  * The contract of dots_flow_map / dots_flow_push holds (pending penalty division, z_mid, state left alone, every Laplacian solver
- * and n_time + 1 <= 1024, batch members on their own stream; output bytes in dots_debug_counter 9); one more kernel family
- * (k_flow_trace, k_flow_trace_push<A>), the same launches.
+ * and n_time + 1 <= 1024, batch members on their own stream; output bytes in dots_debug_counter 9); the same launches, and the same
+ * kernels (k_flow_trace, k_flow_trace_push<A>): dots_flow_map and dots_flow_push are this trace over (0, n_time).
  * DOTS_ERR_ARGUMENT (nothing launched, the context stays usable): what dots_flow_map / dots_flow_push refuse; a node outside
  * 0 .. n_time; node_from == node_to.  DOTS_ERR_STATE: a time slab. */
 typedef struct dots_flow_trace_desc {
@@ -784,7 +784,7 @@ int dots_flow_trace(dots_ctx *ctx, const dots_flow_trace_desc *desc);
  * slides: the slides of every particle; steps: the turns of its inner loop (one per stretch of straight motion or slide).
  * Everything else is dots_flow_trace: the span in either direction, the action, the deposits (trace.mass), the layers; the same
  * contract (pending penalty division, z_mid, state left alone, every Laplacian solver and n_time + 1 <= 1024, batch members on
- * their own stream; output bytes in dots_debug_counter 9: 4 more per particle, 8 with steps); one more kernel family
+ * their own stream; output bytes in dots_debug_counter 9: 4 more per particle, 8 with steps); the tracer's other kernel family
  * (k_flow_slide, k_flow_slide_push<A>), the same launches.
  * DOTS_ERR_ARGUMENT (nothing launched, the context stays usable): what dots_flow_trace refuses; a NULL slides.
  * DOTS_ERR_STATE: a time slab. */

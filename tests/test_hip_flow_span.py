@@ -85,8 +85,9 @@ def test_kernel_equals_the_specification_bit_for_bit(name, span):
 
 
 def test_the_whole_horizon_equals_flow_map_and_flow_push():
-    """dots_flow_trace with (0, T) and no action against dots_flow_map and dots_flow_push on the same inputs: the other kernel family,
-    the same bits -- outputs, layers, mass_at, attr_at and dropped, with 0 and 3 attributes, the last layer and all of them."""
+    """dots_flow_map and dots_flow_push pinned to dots_flow_trace with (0, T) and no action on the same inputs, through the three entry
+    points: one kernel family behind them, the same bits -- outputs, layers, mass_at, attr_at and dropped, with 0 and 3 attributes,
+    the last layer and all of them -- and the same bytes to the host."""
     name = "torus"
     T, max_crossings = fc.CASES[name][1], fc.CASES[name][4]
     dev, t, V, mu, E, hat, nbr = uploaded(name)

@@ -133,3 +133,12 @@ def test_sweep_instantiations_match_the_right_hand_side_caps(kernels):
         want = {nr for nr in (1, 2, 4, 8) if nr <= cap}
         assert nr_by.get((base, True)) == want, (base, nr_by.get((base, True)), cap)
     assert ("k_front_fwd_rows", True) not in nr_by
+
+
+def test_flow_kernels_are_one_tracer_family(kernels):
+    """Every trace is a span: the tracer with and without the sliding mode, each bare and with the deposits of 0 .. 4 attributes, and
+    the conversion of the sums.  A family that comes back or an instantiation that drops out changes this set."""
+    want = ["k_flow_trace", "k_flow_slide", "k_flow_push_finish"]
+    want += [f"{base}<{a}>" for base in ("k_flow_trace_push", "k_flow_slide_push") for a in range(5)]
+    got = sorted(r["short"] for r in kernels if r["short"].startswith("k_flow"))
+    assert got == sorted(want)
