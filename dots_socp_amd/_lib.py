@@ -36,6 +36,7 @@ EXPORTS = [
     "dots_pcg_windows",
     "dots_coarsen", "dots_coarsen_vertices", "dots_coarsen_triangles", "dots_coarsen_copy", "dots_coarsen_free", "dots_mesh_locate",
     "dots_flow_map", "dots_flow_push", "dots_flow_trace", "dots_flow_slide",
+    "dots_sensitivity",
 ]
 
 
@@ -183,6 +184,13 @@ class FlowTraceDesc(C.Structure):      # dots_flow_trace_desc
 
 class FlowSlideDesc(C.Structure):      # dots_flow_slide_desc
     _fields_ = [("trace", FlowTraceDesc), ("slides", _i32p), ("steps", _i32p)]
+
+
+class SensitivityDesc(C.Structure):      # dots_sensitivity_desc
+    _fields_ = [
+        ("factor_phi", C.c_double), ("factor_mu", C.c_double), ("mass_vertex", _f64p), ("phi0", C.c_void_p), ("phiT", C.c_void_p),
+        ("stress", C.c_void_p), ("device_pointers", C.c_int32), ("reserved", C.c_int32), ("ms", _f64p),
+    ]
 
 
 class StepStats(C.Structure):
@@ -378,6 +386,7 @@ def load(host_only=False):
     lib.dots_flow_push.argtypes = [vp, C.POINTER(FlowPushDesc)]
     lib.dots_flow_trace.argtypes = [vp, C.POINTER(FlowTraceDesc)]
     lib.dots_flow_slide.argtypes = [vp, C.POINTER(FlowSlideDesc)]
+    lib.dots_sensitivity.argtypes = [vp, C.POINTER(SensitivityDesc)]
     lib.dots_prolong_space.argtypes = [vp, vp, C.POINTER(ProlongSpaceDesc)]
     lib.dots_transfer_space.argtypes = [vp, vp, C.POINTER(TransferSpaceDesc)]
     lib.dots_carry_spacetime.argtypes = [vp, vp, C.POINTER(CarrySpacetimeDesc)]

@@ -2011,6 +2011,64 @@ int dots_flow_slide(dots_ctx *c, const dots_flow_slide_desc *desc) {
     return flow_run(c, req);
 }
 
+// ---- dots_sensitivity -----------------------------------------------------------------------------------------------------
+int dots_sensitivity(dots_ctx *c, const dots_sensitivity_desc *desc) {
+    if (!c) { set_error("null context"); return DOTS_ERR_ARGUMENT; }
+    if (!desc) { set_error("sensitivity: null description"); return DOTS_ERR_ARGUMENT; }
+    if (c->shard_stride != 0) { set_error("sensitivity: not available on time slabs"); return DOTS_ERR_STATE; }
+    if (!desc->phi0 && !desc->phiT && !desc->stress) { set_error("sensitivity: nothing requested (phi0, phiT and stress are all NULL)"); return DOTS_ERR_ARGUMENT; }
+    if (!std::isfinite(desc->factor_phi) || !std::isfinite(desc->factor_mu)) { set_error("sensitivity: a factor that is not finite"); return DOTS_ERR_ARGUMENT; }
+    const bool on_device = desc->device_pointers != 0;
+    if (on_device && ((uintptr_t)desc->stress & 15)) { set_error("sensitivity: the device stress pointer is not on a 16-byte boundary"); return DOTS_ERR_ARGUMENT; }
+    const Dev &d = c->d;
+    int rc = check(c, true);      // (a pending penalty division is carried out, as for a download; z_mid is not needed)
+    if (rc) return rc;
+    if ((rc = readout_prepare(c))) return rc;      // (the inverses of the device numbering are the read-out's)
+    // the staging buffer: [stress | phi0 | phiT | mass], every part on a 16-byte boundary
+    auto even = [](int64_t n) { return (n + 1) & ~(int64_t)1; };
+    const int64_t V = d.V, F = d.F;
+    const int64_t n_s = desc->stress && !on_device ? 18 * F : 0, n_p = on_device ? 0 : even(V);
+    const int64_t o_p0 = n_s, o_pT = o_p0 + n_p, o_mass = o_pT + n_p, total = o_mass + (desc->mass_vertex ? V : 0);
+    if (total > c->stage_count) { set_error("sensitivity: the outputs do not fit the staging buffer on this mesh"); return DOTS_ERR_STATE; }
+    double *st = c->stage;
+    auto enqueue = [&]() -> int {
+        SensArgs a{};
+        a.phi = d.phi; a.mu = d.mu; a.tri = d.tri;
+        a.inv_v = c->inv_perm_v; a.inv_f = c->inv_perm_f; a.perm_v = d.perm_v;
+        a.mass_dev = d.mass_v;
+        if (desc->mass_vertex && desc->stress) {
+            DOTS_HIP(hipMemcpyAsync(st + o_mass, desc->mass_vertex, sizeof(double) * (size_t)V, hipMemcpyHostToDevice, c->stream));
+            a.mass = st + o_mass;
+        }
+        a.phi0 = !desc->phi0 ? nullptr : (on_device ? desc->phi0 : st + o_p0);
+        a.phiT = !desc->phiT ? nullptr : (on_device ? desc->phiT : st + o_pT);
+        a.stress = !desc->stress ? nullptr : (on_device ? desc->stress : st);
+        a.factor_phi = desc->factor_phi; a.factor_mu = desc->factor_mu;
+        a.V = d.V; a.F = d.F; a.T = d.T; a.tp_shift = d.tp_shift;
+        DOTS_HIP(hipEventRecord(c->ev[0], c->stream));
+        int r = launch_sensitivity(c, a);
+        if (r) return r;
+        DOTS_HIP(hipEventRecord(c->ev[1], c->stream));
+        if (!on_device) {      // only the outputs cross to the host
+            if (desc->phi0) DOTS_HIP(hipMemcpyAsync(desc->phi0, st + o_p0, sizeof(double) * (size_t)V, hipMemcpyDeviceToHost, c->stream));
+            if (desc->phiT) DOTS_HIP(hipMemcpyAsync(desc->phiT, st + o_pT, sizeof(double) * (size_t)V, hipMemcpyDeviceToHost, c->stream));
+            if (desc->stress) DOTS_HIP(hipMemcpyAsync(desc->stress, st, sizeof(double) * (size_t)(18 * F), hipMemcpyDeviceToHost, c->stream));
+        }
+        return 0;
+    };
+    rc = enqueue();      // (every path out of the call waits for the stream first: the copies use the caller's arrays)
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (!rc && es != hipSuccess) rc = hip_fail(es, "hipStreamSynchronize", __FILE__, __LINE__);
+    if (rc) return rc;
+    if (desc->ms) {
+        float t = 0.f;
+        DOTS_HIP(hipEventElapsedTime(&t, c->ev[0], c->ev[1]));
+        *desc->ms = t;
+    }
+    if (!on_device) c->d2h_bytes += (int64_t)sizeof(double) * ((desc->phi0 ? V : 0) + (desc->phiT ? V : 0) + (desc->stress ? 18 * F : 0));
+    return 0;
+}
+
 int dots_front_enable(dots_ctx *c, int on) {
     int rc = check(c);
     if (rc) return rc;
@@ -2070,7 +2128,7 @@ int64_t dots_debug_counter(dots_ctx *c, int which) {
         case 6: return c->sched.bm_nt;                      // beta_mid streamed around the caches by steps 2+3 (the rule of dots_front_setup, or DOTS_BM_NT)
         case 7: return c->front_many_launches;        // sweep launches the last front_solve_many on this (first) context enqueued
         case 8: return c->front_many_split;           // ... of those, launches with fewer rhs than their chunk (many_launch halved: LDS or 1024-thread cap)
-        case 9: return c->d2h_bytes;                  // bytes dots_download, dots_readout, dots_flow_map, dots_flow_push, dots_flow_trace and dots_flow_slide have copied device -> host
+        case 9: return c->d2h_bytes;                  // bytes dots_download, dots_readout, dots_flow_map, dots_flow_push, dots_flow_trace, dots_flow_slide and dots_sensitivity have copied device -> host
         case 10: return c->n_front_allocs;            // device allocations the installed factor holds (0 after front_release: also after a failed dots_front_setup)
         case 11: return c->mg_path;                   // MG_PATH_* bits of the last V-cycle enqueued (dots_dev.h)
         case 12: return c->step_path;                 // STEP_PATH_* bits of the last iteration's launches (dots_dev.h)

@@ -402,6 +402,21 @@ int launch_readout(Ctx *c, bool is_E, double *out, const int *inv, const double 
 int readout_workgroups(const Ctx *c);
 int launch_readout_fold(Ctx *c, const double *part, int layers, int n_wg, double *out);      // out[2 l], out[2 l + 1]: sum / negative sum of layer l
 void preload_readout_kernels();
+// dots_sensitivity (kernels_sensitivity.hip): the potentials at the two ends (one lane per caller vertex) and the stress (one lane per
+// caller triangle corner).  Inputs in the DEVICE numbering, outputs in the caller's; an output that is null is not formed.
+struct SensArgs {
+    const double *phi, *mu;      // the state where it lies: [V][TP]
+    const int *tri;              // [F][3]
+    const int *inv_v, *inv_f;    // caller vertex / triangle -> device row, or null (same numbering)
+    const int *perm_v;           // device vertex -> caller vertex, or null
+    const double *mass;          // [V] vertex masses in the CALLER's numbering, or null: mass_dev
+    const double *mass_dev;      // [V] Dev::mass_v
+    double *phi0, *phiT;         // [V]
+    double *stress;              // [F][3][6], on a 16-byte boundary
+    double factor_phi, factor_mu;
+    int V, F, T, tp_shift;
+};
+int launch_sensitivity(Ctx *c, const SensArgs &a);
 // The flow map (kernels_flow.hip): one lane per particle, the loop over the intervals inside the kernel.  Everything in the DEVICE
 // numbering except the triangles written out, which perm_f takes back to the caller's.  A launch takes FlowArgs and FlowSpan, with
 // deposits FlowPush, with the sliding mode FlowSlide: separate by-value kernel arguments, in the order args, push, span, slide.

@@ -63,7 +63,7 @@ class DeviceProblem:
         self.lap_solver = lap_solver
         d = _lib.ProblemDesc()
         d.abi_version = _lib.ABI_VERSION
-        d.device = int(device)
+        d.device = self.device = int(device)
         d.n_time, d.n_vertices, d.n_triangles = p.n_time, p.n_vertices, p.n_triangles
         d.n_corners = int(p.corner_idx.size)
         d.lap_nnz = int(p.lap_val.size)
@@ -208,6 +208,46 @@ class DeviceProblem:
         _lib.check(self.lib.dots_readout(self._h, C.byref(d)), "dots_readout")
         self.readout_ms, self.readout_bytes = ms.value, self.debug_counter(9) - before
         return out_mu, out_E, mass, neg
+
+    def sensitivity(self, factor_phi=1.0, factor_mu=1.0, mass_vertex=None, potentials=True, stress=True, to_device=False):
+        """``{"phi0", "phiT", "stress"}`` formed on the device (dots_sensitivity; sensitivity.potentials_host and stress_host on the
+        downloaded ``phi`` and ``mu`` are the specification and return the same bits): ``phi0`` / ``phiT`` (V,) the potential at the two
+        ends times ``factor_phi``, ``stress`` (F, 3, 6) of ``factor_mu * mu``, ``factor_phi * phi`` and the vertex masses
+        ``mass_vertex`` (V,) in the caller's numbering (None: the context's own).  ``potentials`` / ``stress`` = False leave that part
+        out.  ``to_device``: torch tensors on the context's device, written by the kernels themselves -- nothing crosses to the host.
+        ``self.sensitivity_ms`` / ``self.sensitivity_bytes``: device milliseconds of the launches and bytes copied to the host."""
+        if self.slab:
+            raise ValueError("sensitivity: not available on time slabs")
+        if not potentials and not stress:
+            raise ValueError("sensitivity: nothing asked for (potentials and stress are both False)")
+        mass = None if mass_vertex is None else np.ascontiguousarray(mass_vertex, dtype=np.float64)
+        if mass is not None and mass.shape != (self.V,):
+            raise ValueError(f"sensitivity: mass_vertex must have shape ({self.V},), got {mass.shape}")
+        shapes = {}
+        if potentials:
+            shapes["phi0"] = shapes["phiT"] = (self.V,)
+        if stress:
+            shapes["stress"] = (self.F, 3, 6)
+        if to_device:
+            import torch
+
+            where = torch.device("cuda", self.device)
+            out = {k: torch.empty(s, dtype=torch.float64, device=where) for k, s in shapes.items()}
+            torch.cuda.current_stream(where).synchronize()      # (the kernels write on the context's stream: nothing of torch's is pending on the memory)
+            address = {k: a.data_ptr() for k, a in out.items()}
+        else:
+            out = {k: np.empty(s) for k, s in shapes.items()}
+            address = {k: a.ctypes.data for k, a in out.items()}
+        ms = C.c_double()
+        d = _lib.SensitivityDesc()
+        d.factor_phi, d.factor_mu, d.mass_vertex = float(factor_phi), float(factor_mu), _ptr(mass, C.c_double)
+        d.phi0, d.phiT, d.stress = address.get("phi0"), address.get("phiT"), address.get("stress")
+        d.device_pointers = int(bool(to_device))
+        d.ms = C.pointer(ms)
+        before = self.debug_counter(9)
+        _lib.check(self.lib.dots_sensitivity(self._h, C.byref(d)), "dots_sensitivity")
+        self.sensitivity_ms, self.sensitivity_bytes = ms.value, self.debug_counter(9) - before
+        return out
 
     def flow_map(self, start_triangle, start_weights, neighbours, floor, max_crossings=16, trajectory=False, slide=False):
         """Trace particles through the transport the context holds, on the device (dots_flow_map; flow.flow_map_host on the downloaded

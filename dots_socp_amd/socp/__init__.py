@@ -21,9 +21,15 @@ the whole solution and converts it in numpy: the same values bit for bit, kept a
 ``flow_map={"starts": "vertices"}`` (the keywords of ``AlmSolver.flow_map``; default None: nothing changes) adds ``solution["flow_map"]``,
 the transport map of the solution traced on the device (``dots_flow_map``; ``dots_socp_amd.flow.flow_map_host`` is the
 specification): where every start point ends up and, with ``trajectory``, where it is after every interval.  Not on time slabs.
+
+``sensitivity=True`` (or the keywords of ``AlmSolver.sensitivity``; default None: nothing changes) adds ``solution["sensitivity"]``: the
+potentials at the two ends, the gradients of the cost in mu0 / mu1 and the stress of the kinetic energy, reduced on the device
+(``dots_sensitivity``; ``dots_socp_amd.sensitivity`` holds the specification and ``cost_gradients``).  Not on time slabs; the stress
+not with congestion.
 """
 import numpy as np
 
+from ..sensitivity import check_sensitivity
 from .solver_socp import (check_flow_map, solver_socp, solver_socp_auto_cascade, solver_socp_cascade, solver_socp_many, solver_socp_mesh_cascade,
                           solver_socp_spacetime_cascade)
 
@@ -73,9 +79,10 @@ def _geometry_with_areas(geometry):
 
 def _read_out_spec(readout, centred, kwargs=None):
     """The ``read_out`` a plug-in hands its solver; with the plug-in's keywords, ``flow_map`` is checked first -- before the library
-    is loaded -- and refused together with ``time_slab``."""
+    is loaded -- and refused together with ``time_slab``; so is ``sensitivity``."""
     if kwargs is not None:
         check_flow_map(kwargs.get("flow_map"), kwargs.get("time_slab"))
+        check_sensitivity(kwargs.get("sensitivity"), kwargs.get("time_slab"), kwargs.get("congestion", 0.0))
     if readout not in ("device", "host"):
         raise ValueError("readout must be 'device' or 'host'")
     return {"dot_units": True, "centred": centred} if readout == "device" else None
@@ -104,6 +111,8 @@ def _finish(solution, geometry, mu0, mu1, readout, centred):
             _to_time_centered(cp, mu0, mu1)
     if "flow_map" in solution:      # (positions and barycentric weights: no units to convert)
         solution_dot["flow_map"] = solution["flow_map"]
+    if "sensitivity" in solution:   # (in the units of geometry's mu0 / mu1 and vertices already)
+        solution_dot["sensitivity"] = solution["sensitivity"]
     return solution_dot
 
 

@@ -30,6 +30,7 @@ from ..control import (AdaptiveValidator, AdjustAdmmParam, ConditionValidator, E
 from .. import _lib
 from .._lib import env_choice
 from ..device import DeviceProblem, STATE_NAMES
+from ..sensitivity import check_sensitivity
 
 logger = logging.getLogger("dots_socp_amd")
 
@@ -789,14 +790,41 @@ class AlmSolver:
             out["positions_at"] = flow.positions(vertices, triangles, out["triangles_at"], out["weights_at"])
         return out
 
-    def finalize(self, download=True, outputs=None, read_out=None, flow_map=None):
+    def sensitivity(self, potentials=True, stress=True, to_device=False):
+        """What the derivative of the transport cost of the current iterate is made of, reduced on the device
+        (DeviceProblem.sensitivity: dots_sensitivity; sensitivity.potentials_host and stress_host on the recovered ``phi`` and ``mu``
+        are the specification and return the same bits).  ``potentials``: ``phi0`` and ``phiT`` (V,), the recovered potential at the
+        two ends as stored, and ``grad_mu0 = -(phi0 - mean)``, ``grad_mu1 = phiT - mean``, the derivative of the cost in the masses
+        ``mu0`` / ``mu1`` of ``geometry``.  ``stress`` (F, 3, 6): the tensor the kinetic energy is linear in, with the vertex masses
+        ``area_vertices / 3`` of ``geometry``; ``sensitivity.cost_gradients`` turns it into the derivative in the vertex positions.
+        Refused with congestion > 0 (a ``ValueError``; the potentials are still to be had with ``stress=False``).  ``to_device``:
+        torch tensors on the context's device instead of numpy arrays, nothing crosses to the host.  Also ``n_time``, and ``ms`` /
+        ``bytes``: device milliseconds of the launches and bytes copied to the host."""
+        from .. import sensitivity as sens
+        from . import _geometry_with_areas
+
+        spec = sens.check_sensitivity({"potentials": potentials, "stress": stress, "to_device": to_device}, getattr(self.dev, "slab", None),
+                                      self.congestion0)
+        mass = None
+        if spec["stress"]:
+            mass = np.asarray(_geometry_with_areas(self.geometry)["area_vertices"], dtype=np.float64) / 3.0
+        dev = self.dev
+        out = dev.sensitivity(self.prim_scale, self.r * self.dual_scale, mass, spec["potentials"], spec["stress"], spec["to_device"])
+        if spec["potentials"]:
+            out["grad_mu0"], out["grad_mu1"] = sens.potential_gradients(out["phi0"], out["phiT"])
+        out["n_time"], out["ms"], out["bytes"] = dev.T, dev.sensitivity_ms, dev.sensitivity_bytes
+        return out
+
+    def finalize(self, download=True, outputs=None, read_out=None, flow_map=None, sensitivity=None):
         """``outputs``: None = the twelve arrays, or a tuple of names: only those are downloaded.  ``read_out``: None, or the
         keywords of ``read_out`` (dot_units, centred): the solution is then its ``{"mu", "E"}`` -- nothing else is downloaded --
         and ``run_history.solver_stats["readout"]`` its info.  ``flow_map``: None, or the keywords of ``flow_map`` as a dict:
-        ``solution["flow_map"]`` then holds what it returns."""
+        ``solution["flow_map"]`` then holds what it returns.  ``sensitivity``: None, True or the keywords of ``sensitivity`` as a
+        dict: ``solution["sensitivity"]`` then holds what it returns."""
         if read_out is not None and outputs is not None:
             raise ValueError("finalize: outputs and read_out are mutually exclusive (read_out returns mu and E only)")
         flow_map = check_flow_map(flow_map, getattr(self.dev, "slab", None), self.dev.T)
+        sensitivity = check_sensitivity(sensitivity, getattr(self.dev, "slab", None), self.congestion0)
         dev, hist, validator = self.dev, self.run_history, self.kkt_validator
         self._kkt_prefetch(range(7))
         validator.validator.validate(list(range(7)))
@@ -826,6 +854,8 @@ class AlmSolver:
             solution = {name: self.recovered(name, self._download(name)) for name in names}
         if flow_map is not None:
             solution["flow_map"] = self.flow_map(**flow_map)
+        if sensitivity is not None:
+            solution["sensitivity"] = self.sensitivity(**sensitivity)
         solution["checkpoints"] = self.checkpoint_solutions if self.checkpoint_solutions else None
         logger.info("Number of iterations: %d   Iteration time: %.2f", self.counter_main, hist.running_time)
         return solution, hist
@@ -863,6 +893,7 @@ def solver_socp(
         read_out=None,
         pcg_windows=False,
         flow_map=None,
+        sensitivity=None,
 ):
     """SOCP for dynamical optimal transport on a discrete surface, on the GPU.
 
@@ -877,10 +908,14 @@ def solver_socp(
     ``n_time + 1 <= 1024`` with either preconditioner, and ``modal_direct`` falls back to it when its factor does not fit.
     ``flow_map``: the keywords of ``AlmSolver.flow_map`` as a dict (``{"starts": "vertices"}``): ``solution["flow_map"]`` is the
     transport map of the solution, traced on the device; None (the default) changes nothing.
+    ``sensitivity``: True, or the keywords of ``AlmSolver.sensitivity`` as a dict: ``solution["sensitivity"]`` holds the potentials at
+    the two ends and the stress of the kinetic energy, reduced on the device (``dots_socp_amd.sensitivity.cost_gradients`` makes the
+    derivatives of the cost in mu0, mu1 and the vertex positions of them); None (the default) changes nothing.
     """
     if read_out is not None and outputs is not None:
         raise ValueError("solver_socp: outputs and read_out are mutually exclusive (read_out returns mu and E only)")
     flow_map = check_flow_map(flow_map, n_time=n_time)
+    sensitivity = check_sensitivity(sensitivity, congestion=congestion)
     alm = AlmSolver(n_time, geometry, congestion=congestion, nit=nit, eps=eps, tol=tol, tau=tau, is_z_scaling=is_z_scaling,
                     is_constant_scaling=is_constant_scaling, check_kkt_step_by_step=check_kkt_step_by_step,
                     init_solution=init_solution, tol_checkpoints=tol_checkpoints, time_limit=time_limit, is_palm=is_palm,
@@ -890,7 +925,7 @@ def solver_socp(
         for _ in range(nit):
             if alm.iterate():
                 break
-        return alm.finalize(outputs=outputs, read_out=read_out, flow_map=flow_map)
+        return alm.finalize(outputs=outputs, read_out=read_out, flow_map=flow_map, sensitivity=sensitivity)
     finally:
         alm.close()
 
@@ -939,7 +974,7 @@ def _batch_problems(geometry, problems, common):
     return out
 
 
-def solver_socp_many(n_time, geometry, problems, *, max_batch=4, read_out=None, flow_map=None, **common):
+def solver_socp_many(n_time, geometry, problems, *, max_batch=4, read_out=None, flow_map=None, sensitivity=None, outputs=None, **common):
     """Solve several transport problems on ONE surface with one factor of the direct solver.
 
     ``geometry`` holds the mesh (``vertices``, ``triangles``; ``mu0`` / ``mu1`` are defaults for problems without their own);
@@ -952,12 +987,17 @@ def solver_socp_many(n_time, geometry, problems, *, max_batch=4, read_out=None, 
     Returns ``[(solution, run_history), ...]`` in input order, each what ``solver_socp(n_time, {**geometry, "mu0": ..., "mu1": ...},
     **common, **problem)`` returns, bit for bit; ``run_history.solver_stats["batch"]`` = {"size", "index", "max_batch", "steps_time_note"}.
     Each problem's running time and time limit start when it is admitted.  A factor that does not fit raises the library's memory error
-    (there is no batched PCG).  ``read_out`` and ``flow_map``: as for ``solver_socp``, for every problem (with its own mu0 / mu1)."""
+    (there is no batched PCG).  ``read_out``, ``flow_map`` and ``sensitivity``: as for ``solver_socp``, for every problem (with its own
+    mu0 / mu1 and congestion); so is ``outputs`` (the arrays that are downloaded; exclusive with ``read_out``)."""
     from .. import geometry as geo
     from ..device import step_many
 
+    if read_out is not None and outputs is not None:
+        raise ValueError("solver_socp_many: outputs and read_out are mutually exclusive (read_out returns mu and E only)")
     flow_map = check_flow_map(flow_map, n_time=n_time)
     probs = _batch_problems(geometry, problems, common)
+    for p in probs:
+        sensitivity = check_sensitivity(sensitivity, congestion=p.get("congestion", 0.0))
     if int(max_batch) < 1:
         raise ValueError("solver_socp_many: max_batch >= 1")
     reorder = common.get("reorder", True)
@@ -1014,7 +1054,7 @@ def solver_socp_many(n_time, geometry, problems, *, max_batch=4, read_out=None, 
             still = []
             for i, alm in active:
                 if alm.finished:
-                    sol, hist = alm.finalize(read_out=read_out, flow_map=flow_map)
+                    sol, hist = alm.finalize(outputs=outputs, read_out=read_out, flow_map=flow_map, sensitivity=sensitivity)
                     hist.solver_stats["batch"] = {"size": len(probs), "index": i, "max_batch": int(max_batch), "steps_time_note": BATCH_TIME_NOTE}
                     results[i] = (sol, hist)
                     done.append((i, alm))
@@ -1114,12 +1154,13 @@ def _carried(geom, i, **more):
     return dict(geometry=geom, init_parents=geom.get("parents") if i else None, init_transfer=geom.get("transfer") if i else None, **more)
 
 
-def _run_levels(levels, stats_key, record, level_tol, opts, read_out, flow_map):
+def _run_levels(levels, stats_key, record, level_tol, opts, read_out, flow_map, sensitivity=None):
     """The level loop of the cascade drivers.  ``levels``: per level, the AlmSolver keywords that vary (``n_time``, ``geometry``, a ``plan``,
     ``init_parents`` / ``init_transfer`` / ``init_regrid``, ...), or a callable that makes them when the level starts (its time is set-up
     time).  Each level is warm-started from the one before (``init_from``, released before the finer factor is built), runs ``nit``
     iterations at most within what is left of ``time_limit``, and adds ``record(alm, hist, setup, i)`` to ``solver_stats[stats_key]``;
-    only the last one is downloaded.  ``opts``: the driver's checked options."""
+    only the last one is downloaded, read out, traced (``flow_map``) and asked for its ``sensitivity``.  ``opts``: the driver's checked
+    options."""
     tol, nit = opts.pop("tol", 1e-4), int(opts.pop("nit", 1000))
     time_limit = opts.pop("time_limit", 1000)
     init_solution, checkpoints = opts.pop("init_solution", None), opts.pop("tol_checkpoints", None)
@@ -1139,7 +1180,8 @@ def _run_levels(levels, stats_key, record, level_tol, opts, read_out, flow_map):
             for _ in range(nit):
                 if alm.iterate():
                     break
-            solution, hist = alm.finalize(download=last, read_out=read_out if last else None, flow_map=flow_map if last else None)
+            solution, hist = alm.finalize(download=last, read_out=read_out if last else None, flow_map=flow_map if last else None,
+                                          sensitivity=sensitivity if last else None)
             records.append(record(alm, hist, setup, i))
             coarse, alm = alm, None
         coarse.dev.sync()
@@ -1167,7 +1209,7 @@ def _cascade_options(n_time, levels, level_tol, kwargs):
     return levels, level_tol, opts
 
 
-def solver_socp_cascade(n_time, geometry, levels=None, level_tol=None, read_out=None, flow_map=None, **kwargs):
+def solver_socp_cascade(n_time, geometry, levels=None, level_tol=None, read_out=None, flow_map=None, sensitivity=None, **kwargs):
     """``solver_socp`` through a coarse-to-fine cascade in time: the problem is solved on the time grids ``levels`` (``n_time`` values,
     increasing, the last one ``n_time``) one after the other, each level warm-started from the recovered solution of the one before,
     interpolated linearly in time on the device (AlmSolver ``init_from``; cascade.prolong_time is the specification).  The number of
@@ -1183,11 +1225,12 @@ def solver_socp_cascade(n_time, geometry, levels=None, level_tol=None, read_out=
     Returns ``(solution, run_history)`` of the finest level; ``run_history.running_time`` is that level's own, and
     ``run_history.solver_stats["cascade"]`` = {"levels": [one record per level: n_time, tol, iterations, running_time, setup_seconds,
     prolong_ms (device events; None on the coarsest level), cost, kkt_max], "total_seconds"} has the whole cascade.
-    ``read_out`` and ``flow_map``: as for ``solver_socp``, for the finest level.  The mesh is the same on every level;
+    ``read_out``, ``flow_map`` and ``sensitivity``: as for ``solver_socp``, for the finest level.  The mesh is the same on every level;
     ``solver_socp_spacetime_cascade`` coarsens the mesh along with the time grid."""
     from .. import geometry as geo
 
     flow_map = check_flow_map(flow_map, kwargs.get("time_slab"), n_time)
+    sensitivity = check_sensitivity(sensitivity, kwargs.get("time_slab"), kwargs.get("congestion", 0.0))
     levels, level_tol, opts = _cascade_options(n_time, levels, level_tol, kwargs)
     reorder = opts.pop("reorder", True)
     if opts.get("lap_solver", "modal_direct") == "modal_direct" and reorder is True:
@@ -1200,7 +1243,7 @@ def solver_socp_cascade(n_time, geometry, levels=None, level_tol=None, read_out=
         return dict(n_time=T, geometry=geometry, plan=plans[-1], batched=False, reorder=reorder)
 
     return _run_levels([lambda T=T: level(T) for T in levels], "cascade", lambda alm, hist, setup, i: _time_record(alm, hist, setup, levels[i]),
-                       level_tol, opts, read_out, flow_map)
+                       level_tol, opts, read_out, flow_map, sensitivity)
 
 
 # ---- coarse-to-fine cascade in space ---------------------------------------------------------------------------------------------
@@ -1244,7 +1287,7 @@ def _mesh_cascade_options(geometries, level_tol, kwargs, who="solver_socp_mesh_c
     return geometries, level_tol, opts
 
 
-def solver_socp_mesh_cascade(n_time, geometries, level_tol=None, read_out=None, flow_map=None, **kwargs):
+def solver_socp_mesh_cascade(n_time, geometries, level_tol=None, read_out=None, flow_map=None, sensitivity=None, **kwargs):
     """``solver_socp`` through a coarse-to-fine cascade in space: the problem is solved on the meshes ``geometries`` (coarse to fine,
     every one after the first the nested refinement of the one before with its ``parents``: ``meshes.refine_levels``), all at
     ``n_time``, each level warm-started from the recovered solution of the one before, carried to the refinement on the device
@@ -1263,11 +1306,12 @@ def solver_socp_mesh_cascade(n_time, geometries, level_tol=None, read_out=None, 
     Returns ``(solution, run_history)`` of the finest level; ``run_history.solver_stats["mesh_cascade"]`` = {"levels": [one record
     per level: n_vertices, n_triangles, tol, iterations, running_time, setup_seconds, prolong_ms and prolong_bytes (None on the coarsest
     level), cost, kkt_max, device_bytes, transfer ("nested" | "located", None on the coarsest level), max_distance (of a located
-    level, else None)], "total_seconds"}.  ``read_out`` and ``flow_map``: as for ``solver_socp``, for the finest level."""
+    level, else None)], "total_seconds"}.  ``read_out``, ``flow_map`` and ``sensitivity``: as for ``solver_socp``, for the finest level."""
     flow_map = check_flow_map(flow_map, kwargs.get("time_slab"), n_time)
+    sensitivity = check_sensitivity(sensitivity, kwargs.get("time_slab"), kwargs.get("congestion", 0.0))
     geometries, level_tol, opts = _mesh_cascade_options(geometries, level_tol, kwargs)
     return _run_levels([_carried(geom, i, n_time=n_time) for i, geom in enumerate(geometries)], "mesh_cascade",
-                       lambda alm, hist, setup, i: _mesh_record(alm, hist, setup, geometries[i], i == 0), level_tol, opts, read_out, flow_map)
+                       lambda alm, hist, setup, i: _mesh_record(alm, hist, setup, geometries[i], i == 0), level_tol, opts, read_out, flow_map, sensitivity)
 
 
 # ---- coarse-to-fine cascade in space and time at once ----------------------------------------------------------------------------
@@ -1281,7 +1325,7 @@ def _spacetime_cascade_options(n_time, geometries, levels, level_tol, kwargs):
     return geometries, levels, level_tol, opts
 
 
-def solver_socp_spacetime_cascade(n_time, geometries, levels=None, level_tol=None, read_out=None, flow_map=None, **kwargs):
+def solver_socp_spacetime_cascade(n_time, geometries, levels=None, level_tol=None, read_out=None, flow_map=None, sensitivity=None, **kwargs):
     """``solver_socp`` through a coarse-to-fine cascade in space AND time: the meshes ``geometries`` (coarse to fine, each level above the
     first with ``parents`` or ``transfer``, as for ``solver_socp_mesh_cascade``) are solved on the time grids ``levels`` (one ``n_time`` per
     geometry, never decreasing, the last one ``n_time``, each one valid for the Laplacian solver).  A level that is coarser in both
@@ -1296,14 +1340,15 @@ def solver_socp_spacetime_cascade(n_time, geometries, levels=None, level_tol=Non
     level, the coarse solver released before the finer factor is built.
 
     Returns ``(solution, run_history)`` of the finest level; ``run_history.solver_stats["spacetime_cascade"]`` = {"levels": [the records of
-    ``solver_socp_mesh_cascade`` plus ``n_time``], "total_seconds"}.  ``read_out`` and ``flow_map``: as for ``solver_socp``, for the
-    finest level."""
+    ``solver_socp_mesh_cascade`` plus ``n_time``], "total_seconds"}.  ``read_out``, ``flow_map`` and ``sensitivity``: as for
+    ``solver_socp``, for the finest level."""
     flow_map = check_flow_map(flow_map, kwargs.get("time_slab"), n_time)
+    sensitivity = check_sensitivity(sensitivity, kwargs.get("time_slab"), kwargs.get("congestion", 0.0))
     geometries, levels, level_tol, opts = _spacetime_cascade_options(n_time, geometries, levels, level_tol, kwargs)
     return _run_levels([_carried(geom, i, n_time=T, init_regrid=bool(i) and T != levels[i - 1]) for i, (T, geom) in enumerate(zip(levels, geometries))],
                        "spacetime_cascade",
                        lambda alm, hist, setup, i: {"n_time": int(levels[i]), **_mesh_record(alm, hist, setup, geometries[i], i == 0)},
-                       level_tol, opts, read_out, flow_map)
+                       level_tol, opts, read_out, flow_map, sensitivity)
 
 
 # ---- a cascade in space from ONE geometry: the levels are made here ----------------------------------------------------------------
@@ -1329,7 +1374,7 @@ def _auto_cascade_options(n_time, coarse_levels, ratio, locate, spacetime, level
 
 
 def solver_socp_auto_cascade(n_time, geometry, coarse_levels=2, ratio=4.0, locate="device", spacetime=False, levels=None, level_tol=None,
-                             read_out=None, flow_map=None, **kwargs):
+                             read_out=None, flow_map=None, sensitivity=None, **kwargs):
     """``solver_socp`` through a cascade in space for a caller with ONE geometry: ``coarse_levels`` coarser meshes are made of it
     (``meshes.coarsen_levels``: half-edge-collapse decimation by ``ratio`` per level on the host, every level located on the one below
     with ``locate`` -- "device": ``dots_mesh_locate`` on the solver's GPU --, ``mu0`` / ``mu1`` restricted), then the levels are handed
@@ -1344,9 +1389,10 @@ def solver_socp_auto_cascade(n_time, geometry, coarse_levels=2, ratio=4.0, locat
     from .. import meshes
 
     flow_map = check_flow_map(flow_map, kwargs.get("time_slab"), n_time)
+    sensitivity = check_sensitivity(sensitivity, kwargs.get("time_slab"), kwargs.get("congestion", 0.0))
     n_coarse = _auto_cascade_options(n_time, coarse_levels, ratio, locate, spacetime, levels, level_tol, kwargs)
     if n_coarse == 0:
-        return solver_socp(n_time, geometry, read_out=read_out, flow_map=flow_map, **kwargs)
+        return solver_socp(n_time, geometry, read_out=read_out, flow_map=flow_map, sensitivity=sensitivity, **kwargs)
     t_start = time.perf_counter()
     geometries = meshes.coarsen_levels(geometry, n_coarse + 1, ratio=ratio, locate=locate, device=kwargs.get("device", 0))
     build = time.perf_counter() - t_start
@@ -1355,8 +1401,8 @@ def solver_socp_auto_cascade(n_time, geometry, coarse_levels=2, ratio=4.0, locat
     opts = dict(kwargs)
     opts["time_limit"] = max(opts.get("time_limit", 1000) - build, 0.0)
     if spacetime:
-        solution, hist = solver_socp_spacetime_cascade(n_time, geometries, levels=levels, level_tol=level_tol, read_out=read_out, flow_map=flow_map, **opts)
+        solution, hist = solver_socp_spacetime_cascade(n_time, geometries, levels=levels, level_tol=level_tol, read_out=read_out, flow_map=flow_map, sensitivity=sensitivity, **opts)
     else:
-        solution, hist = solver_socp_mesh_cascade(n_time, geometries, level_tol=level_tol, read_out=read_out, flow_map=flow_map, **opts)
+        solution, hist = solver_socp_mesh_cascade(n_time, geometries, level_tol=level_tol, read_out=read_out, flow_map=flow_map, sensitivity=sensitivity, **opts)
     hist.solver_stats["auto_cascade"] = {"levels": records, "build_seconds": build}
     return solution, hist

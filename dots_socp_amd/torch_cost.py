@@ -1,0 +1,102 @@
+"""The transport cost as a differentiable torch function: a loss in the end densities and in the shape.
+
+``transport_cost`` solves one problem with ``solver_socp`` and returns its cost as a scalar tensor; the backward pass is
+``sensitivity.cost_gradients`` on what ``dots_sensitivity`` reduced on the device at the end of the solve: the mean-free Kantorovich
+potentials for ``mu0`` / ``mu1`` (the masses per vertex ``solver_socp`` takes) and minus the derivative of the kinetic energy at fixed
+stress for ``vertices`` (envelope theorem; without congestion only).  The gradients are those of the converged problem: their error
+is the solve's (``tol``) -- DESIGN.md section 9, "Cost gradients", has the measured finite differences.  ``transport_costs`` does
+the same for a batch of densities on one surface through ``solver_socp_many``: one factor for all of them.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import meshes, sensitivity
+from .socp.solver_socp import PER_PROBLEM_KEYS, solver_socp, solver_socp_many
+
+
+def _host(a):
+    return a.detach().cpu().numpy().astype(np.float64) if isinstance(a, torch.Tensor) else np.asarray(a, dtype=np.float64)
+
+
+def _request(needs):
+    """The ``sensitivity`` request for the inputs (mu0, mu1, vertices) that need a gradient, or None."""
+    if not any(needs[:3]):
+        return None
+    return {"potentials": bool(needs[0] or needs[1]), "stress": bool(needs[2])}
+
+
+def _like(array, ref):
+    return torch.as_tensor(np.ascontiguousarray(array), dtype=ref.dtype, device=ref.device)
+
+
+class _TransportCost(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mu0, mu1, vertices, triangles, n_time, options):
+        x, tri = _host(vertices), np.asarray(_host(triangles), dtype=np.int64)
+        geom, _ = meshes.make_geometry(x, tri, _host(mu0), _host(mu1), normalize=False)      # the geometry as given
+        solution, hist = solver_socp(int(n_time), geom, outputs=(), sensitivity=_request(ctx.needs_input_grad), **options)
+        ctx.sens, ctx.mesh = solution.get("sensitivity"), (x, tri)
+        ctx.like = (mu0, mu1, vertices)
+        return torch.tensor(float(hist.history["Transportation cost"][-1]), dtype=torch.float64, device=mu0.device)
+
+    @staticmethod
+    def backward(ctx, g):
+        g0, g1, gx = sensitivity.cost_gradients(ctx.sens, *ctx.mesh)
+        grads = [None if a is None or not need else g.to(ref.device, ref.dtype) * _like(a, ref)
+                 for a, need, ref in zip((g0, g1, gx), ctx.needs_input_grad[:3], ctx.like)]
+        return (*grads, None, None, None)
+
+
+def _tensor(a):
+    return a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, dtype=np.float64))
+
+
+def transport_cost(mu0, mu1, vertices, triangles, n_time, **solver_options):
+    """The transport cost between the masses ``mu0`` and ``mu1`` (V,) on the mesh (``vertices`` (V, 3), ``triangles`` (F, 3)) with
+    ``n_time`` intervals, as a scalar fp64 tensor on ``mu0``'s device, differentiable in ``mu0``, ``mu1`` and ``vertices``.  Forward:
+    one ``solver_socp`` call on the geometry as given (``meshes.make_geometry(..., normalize=False)``) with ``solver_options`` (tol,
+    nit, ...); only what an input that requires a gradient needs is reduced.  Backward: ``sensitivity.cost_gradients``.  The
+    gradients in the masses are mean-free (the cost is defined for equal total masses); the one in ``vertices`` needs congestion 0."""
+    for k in ("outputs", "read_out", "flow_map", "sensitivity"):
+        if k in solver_options:
+            raise ValueError(f"transport_cost: '{k}' is chosen by the function itself")
+    return _TransportCost.apply(_tensor(mu0), _tensor(mu1), _tensor(vertices), triangles, n_time, solver_options)
+
+
+class _TransportCosts(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mu0, mu1, vertices, triangles, n_time, options):
+        x, tri = _host(vertices), np.asarray(_host(triangles), dtype=np.int64)
+        m0, m1 = _host(mu0), _host(mu1)
+        geom, _ = meshes.make_geometry(x, tri, m0[0], m1[0], normalize=False)
+        each = {k: v for k, v in options.items() if k in PER_PROBLEM_KEYS}
+        common = {k: v for k, v in options.items() if k not in PER_PROBLEM_KEYS}
+        problems = [dict(each, mu0=a, mu1=b) for a, b in zip(m0, m1)]
+        results = solver_socp_many(int(n_time), geom, problems, outputs=(), sensitivity=_request(ctx.needs_input_grad), **common)
+        ctx.sens, ctx.mesh = [sol.get("sensitivity") for sol, _ in results], (x, tri)
+        ctx.like = (mu0, mu1, vertices)
+        return torch.tensor([float(hist.history["Transportation cost"][-1]) for _, hist in results], dtype=torch.float64, device=mu0.device)
+
+    @staticmethod
+    def backward(ctx, g):
+        parts = [sensitivity.cost_gradients(s, *ctx.mesh) for s in ctx.sens]
+        need, (r0, r1, rx) = ctx.needs_input_grad, ctx.like
+        g0 = g.to(r0.device, r0.dtype)[:, None] * _like(np.stack([p[0] for p in parts]), r0) if need[0] else None
+        g1 = g.to(r1.device, r1.dtype)[:, None] * _like(np.stack([p[1] for p in parts]), r1) if need[1] else None
+        gx = (g.to(rx.device, rx.dtype)[:, None, None] * _like(np.stack([p[2] for p in parts]), rx)).sum(0) if need[2] else None
+        return g0, g1, gx, None, None, None
+
+
+def transport_costs(mu0, mu1, vertices, triangles, n_time, **solver_options):
+    """``transport_cost`` for ``B`` pairs of masses on one surface: ``mu0`` and ``mu1`` (B, V); returns the costs (B,).  The problems
+    run through ``solver_socp_many``: one factor of the direct solver, batched sweeps.  ``solver_options``: the per-problem options of
+    ``solver_socp_many`` (tol, nit, congestion, ...) hold for every problem, the others (eps, device, max_batch, ...) for the batch."""
+    for k in ("outputs", "read_out", "flow_map", "sensitivity"):
+        if k in solver_options:
+            raise ValueError(f"transport_costs: '{k}' is chosen by the function itself")
+    mu0, mu1 = _tensor(mu0), _tensor(mu1)
+    if mu0.ndim != 2 or mu0.shape != mu1.shape or mu0.shape[0] < 1:
+        raise ValueError(f"transport_costs: mu0 and mu1 (B, V) expected, got {tuple(mu0.shape)} and {tuple(mu1.shape)}")
+    return _TransportCosts.apply(mu0, mu1, _tensor(vertices), triangles, n_time, solver_options)

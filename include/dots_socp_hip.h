@@ -795,6 +795,39 @@ typedef struct dots_flow_slide_desc {
 } dots_flow_slide_desc;
 int dots_flow_slide(dots_ctx *ctx, const dots_flow_slide_desc *desc);
 
+/* ---- cost gradients: the potentials at the two ends and the stress of the kinetic energy, reduced on the device ------------------
+ * dots_sensitivity returns what the derivative of the transport cost is made of, from the state the context holds, in the caller's
+ * numbering (dots_socp_amd/sensitivity.py: potentials_host and stress_host are the specification, and every output equals them bit for
+ * bit on the downloaded phi and mu):
+ *   phi0[v] = factor_phi * phi[0][v], phiT[v] = factor_phi * phi[n_time][v]: the Kantorovich potential at the two ends, as stored (the
+ *     caller fixes the gauge); the cost's derivative in the end masses is -(phi0 - mean) and phiT - mean.
+ *   stress[f][k][e], e over the entries (a, b) = 00, 01, 02, 11, 12, 22 of a symmetric 3 x 3 tensor per corner k of triangle f (vertex
+ *     v_k = tri[f][k]; corners keep their index in every numbering):
+ *       sum over t = 0 .. n_time - 1 of (mu[t][v_k] * mass[v_k]) * 0.5 * (p_t[a] p_t[b] + p_t+1[a] p_t+1[b]),  p_t[a] = phi[t][tri[f][a]],
+ *     with phi and mu multiplied by their factors first (one multiplication each; the recovered solution: prim_scale and
+ *     r * dual_scale), one accumulator per entry, t ascending, in the order of operations stress_host states.  The discrete kinetic
+ *     energy is linear in it, and minus its derivative in the vertex positions at fixed stress is the shape derivative of the cost
+ *     without congestion (sensitivity.py: kinetic_energy).
+ * One lane per caller vertex and one per caller triangle corner, plain loads and stores; 18 F + 2 V doubles leave the device instead
+ * of phi and mu.  Without device_pointers the outputs are formed in the context's staging buffer and copied to the host (counted in
+ * dots_debug_counter 9); with it they are written where the caller's device pointers say, and the call returns with the stream
+ * synchronised, so that they may be read right away from any stream.
+ * A pending penalty division is carried out first, as for a download; z_mid is neither needed nor produced; the state, carried sums,
+ * fused KKT sums and a launch ahead are left as they are.  Works on contexts of every Laplacian solver and on members of a batch.
+ * DOTS_ERR_ARGUMENT (nothing launched): NULL desc, nothing asked for (phi0, phiT and stress all NULL), a factor that is not finite,
+ * a device stress pointer off a 16-byte boundary; DOTS_ERR_STATE: a time slab. */
+typedef struct dots_sensitivity_desc {
+    double factor_phi;           /* multiplier of every phi (prim_scale for the recovered solution; 1 = the iterate)            */
+    double factor_mu;            /* multiplier of every mu (r * dual_scale; 1 = the iterate)                                    */
+    const double *mass_vertex;   /* HOST [V], caller numbering (area_vertices / 3), or NULL: the context's own vertex masses    */
+    double *phi0, *phiT;         /* out [V] each, or NULL                                                                       */
+    double *stress;              /* out [F][3][6], or NULL                                                                      */
+    int32_t device_pointers;     /* 0: phi0, phiT, stress are host addresses; 1: device addresses on the context's device      */
+    int32_t reserved;
+    double *ms;                  /* NULL, or HOST out: device milliseconds of the launches                                      */
+} dots_sensitivity_desc;
+int dots_sensitivity(dots_ctx *ctx, const dots_sensitivity_desc *desc);
+
 /* ---- levels of a cascade in space from ONE mesh: coarsen on the host, locate on the device ------------------------------------
  * dots_coarsen: half-edge-collapse decimation of the mesh (xyz [V][3], tri [F][3]) towards `n_target` vertices, host only (no
  * device work; dots_socp_amd/meshes.py: coarsen(backend="python") is the specification and states the rules; both return the same
