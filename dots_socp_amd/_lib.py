@@ -37,7 +37,10 @@ EXPORTS = [
     "dots_coarsen", "dots_coarsen_vertices", "dots_coarsen_triangles", "dots_coarsen_copy", "dots_coarsen_free", "dots_mesh_locate",
     "dots_flow_map", "dots_flow_push", "dots_flow_trace", "dots_flow_slide",
     "dots_sensitivity",
+    "dots_restart",
 ]
+RESTART_COLD, RESTART_WARM = 0, 1      # dots_restart_desc.mode
+BENCH_RESTART_SCALE = 5                # dots_bench_kernel: the in-place rescaling of dots_restart(WARM), every factor 1
 
 
 class PenaltyPolicy(C.Structure):      # dots_penalty_policy
@@ -191,6 +194,11 @@ class SensitivityDesc(C.Structure):      # dots_sensitivity_desc
         ("factor_phi", C.c_double), ("factor_mu", C.c_double), ("mass_vertex", _f64p), ("phi0", C.c_void_p), ("phiT", C.c_void_p),
         ("stress", C.c_void_p), ("device_pointers", C.c_int32), ("reserved", C.c_int32), ("ms", _f64p),
     ]
+
+
+class RestartDesc(C.Structure):      # dots_restart_desc
+    _fields_ = [("mu0", C.c_void_p), ("mu1", C.c_void_p), ("device_pointers", C.c_int32), ("mode", C.c_int32), ("factors", C.c_double * 4),
+                ("ms", _f64p)]
 
 
 class StepStats(C.Structure):
@@ -387,6 +395,7 @@ def load(host_only=False):
     lib.dots_flow_trace.argtypes = [vp, C.POINTER(FlowTraceDesc)]
     lib.dots_flow_slide.argtypes = [vp, C.POINTER(FlowSlideDesc)]
     lib.dots_sensitivity.argtypes = [vp, C.POINTER(SensitivityDesc)]
+    lib.dots_restart.argtypes = [vp, C.POINTER(RestartDesc)]
     lib.dots_prolong_space.argtypes = [vp, vp, C.POINTER(ProlongSpaceDesc)]
     lib.dots_transfer_space.argtypes = [vp, vp, C.POINTER(TransferSpaceDesc)]
     lib.dots_carry_spacetime.argtypes = [vp, vp, C.POINTER(CarrySpacetimeDesc)]

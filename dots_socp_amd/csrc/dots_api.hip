@@ -92,6 +92,15 @@ static int dev_upload(Ctx *c, const T **out, const T *host, int64_t count) {
     return 0;
 }
 
+// norm_boundary = r h sqrt(norm_square_center(boundary / mass)) at r = 1 (solver_socp.py:296) from the end masses: the sum in vertex
+// order on the host (dots_create, dots_restart with host arrays: one loop, the same bits), the norm from a sum however it was formed
+static double boundary_sum(const double *mu0, const double *mu1, const double *mass, int V) {
+    double nb = 0.0;
+    for (int v = 0; v < V; ++v) nb += (mu0[v] * mu0[v] + mu1[v] * mu1[v]) / mass[v];
+    return nb;
+}
+static double boundary_norm(double nb, int T) { return std::sqrt(nb / (T + 1)); }
+
 static int build(Ctx *c, const dots_problem_desc *p) {
     Dev &d = c->d;
     d.T = p->n_time;
@@ -295,10 +304,9 @@ static int build(Ctx *c, const dots_problem_desc *p) {
     c->c_comp_m = mean_f;
 
     dots_params &q = c->prm;
-    q.r = 1.0; q.scale_z = 1.0; q.const_d = 1.0; q.norm_d = std::sqrt(2.0 * sa);
-    double nb = 0.0;
-    for (int v = 0; v < V; ++v) nb += (p->mu0[v] * p->mu0[v] + p->mu1[v] * p->mu1[v]) / p->mass_vert[v];
-    q.norm_boundary = std::sqrt(nb / (d.T + 1));      // = r h sqrt(norm_square_center(boundary / mass)), :296
+    q.r = 1.0; q.scale_z = 1.0; q.const_d = 1.0; q.norm_d = c->norm_d0 = std::sqrt(2.0 * sa);
+    c->mass_host = std::make_shared<std::vector<double>>(p->mass_vert, p->mass_vert + V);      // (dots_restart forms norm_boundary again)
+    q.norm_boundary = boundary_norm(boundary_sum(p->mu0, p->mu1, p->mass_vert, V), d.T);
     q.congestion = 0.0; q.tau = 1.9; q.eps = 0.0; q.prim_scale = 1.0; q.dual_scale = 1.0; q.boundary_scale = 1.0;
     q.cg_tol = 1e-8; q.cg_max_iter = 20000;
     DOTS_HIP(hipStreamSynchronize(c->stream));
@@ -601,6 +609,7 @@ int dots_create(const dots_problem_desc *desc, dots_ctx **out) {
     preload_kkt_kernels();
     preload_transform_kernels();
     preload_readout_kernels();
+    preload_restart_kernels();
     *out = c;
     return 0;
 }
@@ -1606,6 +1615,77 @@ int dots_carry_spacetime(dots_ctx *dst, dots_ctx *src, const dots_carry_spacetim
     return carry_state(who, "table", dst, src, desc->factor, desc->ms, t);
 }
 
+// ---- dots_restart: new end masses on a live context (include/dots_socp_hip.h) ------------------------------------------------------
+int dots_restart(dots_ctx *c, const dots_restart_desc *desc) {
+    if (!c || !desc || !desc->mu0 || !desc->mu1) { set_error("restart: null argument"); return DOTS_ERR_ARGUMENT; }
+    if (desc->mode != DOTS_RESTART_COLD && desc->mode != DOTS_RESTART_WARM) { set_error("restart: unknown mode"); return DOTS_ERR_ARGUMENT; }
+    const bool warm = desc->mode == DOTS_RESTART_WARM, on_device = desc->device_pointers != 0;
+    if (c->shard_stride != 0) { set_error("restart: not available on a time slab"); return DOTS_ERR_STATE; }
+    const int V = c->d.V;
+    if (!on_device)
+        for (int v = 0; v < V; ++v)
+            if (!std::isfinite(desc->mu0[v]) || !std::isfinite(desc->mu1[v])) { set_error("restart: an end mass that is not finite"); return DOTS_ERR_ARGUMENT; }
+    if (warm) {
+        for (double f : desc->factors)
+            if (!(std::isfinite(f) && f > 0.0)) { set_error("restart: a factor that is not finite and positive"); return DOTS_ERR_ARGUMENT; }
+        if (c->zmid_stale) { set_error("restart: z_mid was not materialised by the last step (dots_step_flags): no warm start from this iterate"); return DOTS_ERR_STATE; }
+    }
+    // the launch ahead, an armed penalty decision, the carried gathers, the fused sums and the step path go (check); the division stays for below
+    int rc = check(c, false, true);
+    if (rc) return rc;
+    Dev &d = c->d;
+    DOTS_HIP(hipEventRecord(c->ev[0], c->stream));
+    if (warm) {      // what dots_download does before it reads, then the recovery factors in place
+        if ((rc = flush_division(c)) || (rc = materialise_zmid(c)) || (rc = launch_restart_scale(c, desc->factors, nullptr))) return rc;
+    } else {
+        c->pending_div = 0.0;      // (it would have divided arrays that are zero from here on)
+        c->zmid_deferred = 0;
+        if ((rc = launch_restart_scale(c, nullptr, nullptr))) return rc;      // (one launch: a memset per array costs the host milliseconds on the large ones)
+    }
+    // what is derived from the state or left over from the old run's launches, as a new context has it: zero
+    const size_t node_bytes = sizeof(double) * ((size_t)V << d.tp_shift);
+    double *const node_arrays[] = {d.lamc, c->zf_alt, c->ze_alt, c->lamc_alt, d.cg_b, d.cg_r, d.cg_z, d.cg_p0, d.cg_p1, d.cg_Ap, d.cg_x};
+    for (double *p : node_arrays)
+        if (p) DOTS_HIP(hipMemsetAsync(p, 0, node_bytes, c->stream));
+    // (B_alt keeps its bytes: it is read only while zmid_deferred is set, and the step that sets it has written all of it)
+    DOTS_HIP(hipMemsetAsync(d.scal, 0, sizeof(double) * CgScalOffsets::TOTAL, c->stream));
+    DOTS_HIP(hipMemsetAsync(d.flags, 0, sizeof(int) * FLAG_TOTAL, c->stream));
+    DOTS_HIP(hipMemsetAsync(c->kkt_counter, 0, 2 * sizeof(int), c->stream));
+    // boundary data: the masses where the kernels read them, norm_boundary as dots_create forms it
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    DOTS_HIP(hipMemcpyAsync(const_cast<double *>(d.mu0), desc->mu0, sizeof(double) * (size_t)V, kind, c->stream));
+    DOTS_HIP(hipMemcpyAsync(const_cast<double *>(d.mu1), desc->mu1, sizeof(double) * (size_t)V, kind, c->stream));
+    double nb = 0.0;
+    if (on_device) { if ((rc = restart_boundary_sum(c, d.mu0, d.mu1, &nb))) return rc; }
+    else nb = boundary_sum(desc->mu0, desc->mu1, c->mass_host->data(), V);
+    DOTS_HIP(hipEventRecord(c->ev[1], c->stream));
+    DOTS_HIP(hipStreamSynchronize(c->stream));      // (host arrays are borrowed for the call only; the ring's events and the mailbox are idle from here)
+    dots_params &q = c->prm;
+    q.r = 1.0; q.scale_z = 1.0; q.const_d = 1.0; q.norm_d = c->norm_d0;
+    q.norm_boundary = boundary_norm(nb, d.T);
+    q.congestion = 0.0; q.prim_scale = 1.0; q.dual_scale = 1.0; q.boundary_scale = 1.0;      // (tau, eps, cg_tol, cg_max_iter stay)
+    // host bookkeeping of the old run
+    c->zmid_stale = c->zmid_deferred = 0;
+    c->zmid_dv = c->zmid_sz = 0.0;
+    c->ahead_dv = c->ahead_r = c->ahead_div = 0.0;
+    c->kkt_halo_fresh = 0;
+    c->step_timed = c->step_skip_zmid = c->step_palm = c->step_kkt = c->step_carry = 0;
+    c->batched = 0;
+    c->t_head = c->t_count = 0;
+    c->last_cg_iters = 0;
+    c->cgc.last_iters = 0;
+    for (auto &k : c->cgw) k.last_iters = 0;
+    c->pcg_windows_ran = 0;
+    c->mail_seq = 0;
+    for (int i = 0; i < MAX_SUMS + 8; ++i) c->h_mail[i] = 0.0;
+    if (desc->ms) {
+        float t = 0.f;
+        DOTS_HIP(hipEventElapsedTime(&t, c->ev[0], c->ev[1]));
+        *desc->ms = t;
+    }
+    return 0;
+}
+
 // ---- dots_readout ---------------------------------------------------------------------------------------------------------
 // the inverse of the device numbering, the copy stream, the chunk events and the host memory of the layer sums: once per context
 static int readout_prepare(Ctx *c) {
@@ -2142,6 +2222,20 @@ int dots_bench_kernel(dots_ctx *c, int which, int reps, double *ms, double *byte
     int rc = check(c);
     if (rc) return rc;
     if (reps < 1 || !ms || !bytes) { set_error("bench: bad argument"); return DOTS_ERR_ARGUMENT; }
+    if (which == 5) {      // dots_restart's in-place rescaling with every factor 1: the state keeps its values
+        if (c->shard_stride != 0) { set_error("bench: the rescaling of dots_restart does not run on a time slab"); return DOTS_ERR_STATE; }
+        if ((rc = materialise_zmid(c))) return rc;
+        const double one[4] = {1.0, 1.0, 1.0, 1.0};
+        for (int i = 0; i < 2; ++i) if ((rc = launch_restart_scale(c, one, bytes))) return rc;
+        DOTS_HIP(hipEventRecord(c->ev[6], c->stream));
+        for (int i = 0; i < reps; ++i) if ((rc = launch_restart_scale(c, one, bytes))) return rc;
+        DOTS_HIP(hipEventRecord(c->ev[7], c->stream));
+        DOTS_HIP(hipEventSynchronize(c->ev[7]));
+        float t = 0.f;
+        DOTS_HIP(hipEventElapsedTime(&t, c->ev[6], c->ev[7]));
+        *ms = (double)t / reps;
+        return 0;
+    }
     return cg_bench(c, which, reps, ms, bytes);
 }
 

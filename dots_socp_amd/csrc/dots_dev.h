@@ -417,6 +417,13 @@ struct SensArgs {
     int V, F, T, tp_shift;
 };
 int launch_sensitivity(Ctx *c, const SensArgs &a);
+// dots_restart (kernels_restart.hip): every element of state array k times factor[group(k)] in place, ONE launch over the twelve
+// arrays (the padding columns are written as zeros), or with factor == null every element zeroed; *bytes (or null): what the launch
+// reads and writes
+int launch_restart_scale(Ctx *c, const double factor[4], double *bytes);
+// sum over v of (mu0[v]^2 + mu1[v]^2) / mass_v[v] of two DEVICE arrays in a fixed order, left in *out on the host (waits for the stream)
+int restart_boundary_sum(Ctx *c, const double *mu0, const double *mu1, double *out);
+void preload_restart_kernels();
 // The flow map (kernels_flow.hip): one lane per particle, the loop over the intervals inside the kernel.  Everything in the DEVICE
 // numbering except the triangles written out, which perm_f takes back to the caller's.  A launch takes FlowArgs and FlowSpan, with
 // deposits FlowPush, with the sliding mode FlowSlide: separate by-value kernel arguments, in the order args, push, span, slide.
@@ -599,6 +606,9 @@ struct Ctx {
     int readout_pinned = 0;       // KB per slot; 0: copies go straight into the caller's memory
     int64_t d2h_bytes = 0;        // bytes copied device -> host by dots_download, dots_readout and dots_flow_map (dots_debug_counter 9)
     std::shared_ptr<FlowHost> flow;      // dots_flow_map: built on first use
+    // dots_restart: what the parameters of a new context are formed from besides mu0 / mu1
+    std::shared_ptr<std::vector<double>> mass_host;      // [V] vertex masses, device numbering (norm_boundary's loop)
+    double norm_d0 = 0.0;         // norm_d as dots_create leaves it
     void *mg_allocs[160]{};
     int n_mg_allocs = 0;
     // constants of the KKT normalisation (solver_socp.py:303-313)

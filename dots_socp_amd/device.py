@@ -497,6 +497,57 @@ class DeviceProblem:
         self.prolong_bytes = 8 * (self._state_pitch() * self._state_rows() + src._state_pitch() * src_rows)
         return ms
 
+    # ---- solve session: the next problem on this context
+    def restart(self, mu0, mu1, mode="cold", factors=None, device_pointers=False):
+        """Take the end masses of another problem on the same surface and start over on the live context (dots_restart): the factor,
+        the hierarchy and every allocation are kept, the parameters go back to a new context's (``self.params`` is read again).
+        ``mode="cold"``: the state is zeroed; ``"warm"``: every state array is multiplied in place by its entry of ``factors``, the
+        four of ``AlmSolver.recovery_factors()`` -- the bits that downloading, ``recovered`` and ``init_solution=`` leave.  ``mu0`` /
+        ``mu1`` (V,) in the caller's numbering: arrays, or with ``device_pointers`` torch tensors on the context's device (permuted
+        there; nothing crosses to the host except that ``self.plan``'s copies are refreshed for ``_initial_constant_scaling``).
+        Returns the device milliseconds of the call."""
+        if self.slab:
+            raise ValueError("restart: not available on time slabs")
+        if mode not in ("cold", "warm"):
+            raise ValueError("restart: mode must be 'cold' or 'warm'")
+        if mode == "warm" and (factors is None or len(factors) != 4):
+            raise ValueError("restart: a warm restart needs the four recovery factors")
+        perm = self.plan.perm_vert
+        d = _lib.RestartDesc()
+        if device_pointers:
+            import torch
+
+            where = torch.device("cuda", self.device)
+            dev = []
+            for name, a in (("mu0", mu0), ("mu1", mu1)):
+                if not isinstance(a, torch.Tensor) or a.device != where or a.dtype != torch.float64 or tuple(a.shape) != (self.V,):
+                    raise ValueError(f"restart: {name} must be a float64 tensor of shape ({self.V},) on {where}")
+                a = a.detach()
+                dev.append((a if perm is None else a[torch.as_tensor(perm, device=where, dtype=torch.int64)]).contiguous())
+            torch.cuda.current_stream(where).synchronize()      # (the call reads them on the context's stream)
+            d.mu0, d.mu1 = dev[0].data_ptr(), dev[1].data_ptr()
+            host = [t.cpu().numpy() for t in dev]
+        else:
+            host = []
+            for name, a in (("mu0", mu0), ("mu1", mu1)):
+                a = np.asarray(a, dtype=np.float64)
+                if a.shape != (self.V,):
+                    raise ValueError(f"restart: {name} must have shape ({self.V},), got {a.shape}")
+                host.append(np.ascontiguousarray(a if perm is None else a[perm]))
+            d.mu0, d.mu1 = host[0].ctypes.data, host[1].ctypes.data
+        d.device_pointers, d.mode = int(bool(device_pointers)), _lib.RESTART_WARM if mode == "warm" else _lib.RESTART_COLD
+        for i in range(4):
+            d.factors[i] = float(factors[i]) if mode == "warm" else 1.0
+        ms = C.c_double()
+        d.ms = C.pointer(ms)
+        _lib.check(self.lib.dots_restart(self._h, C.byref(d)), "dots_restart")
+        import dataclasses
+
+        self.plan = dataclasses.replace(self.plan, mu0=host[0], mu1=host[1])      # (shared plans of other solvers keep theirs)
+        _lib.check(self.lib.dots_get_params(self._h, C.byref(self.params)), "dots_get_params")
+        self.restart_ms = ms.value
+        return ms.value
+
     # ---- the hot loop
     def step(self, n_iters=1, wait=True):
         """``wait=False``: only enqueue (direct solver); returns None, nothing is timed."""

@@ -10,6 +10,9 @@
 ``solver_raw_auto_cascade`` / ``solver_auto_cascade``   the same through a cascade in space whose coarse meshes are made of the ONE
                                                         geometry the plug-in receives (solver_socp_auto_cascade)
 
+``SolveSession``   one live context and one factor for a sequence of problems on one surface whose end masses change:
+                   ``with SolveSession(n_time, geometry, **options) as s: solution, hist = s.solve(mu0, mu1, warm=True)`` (dots_restart)
+
 Both take ``(n_time, geometry, **kwargs)`` and return ``(solution, run_history)``; they can be
 passed as ``solver=`` to the reference's ``run_dot_surface`` (interface.py:106-134).
 
@@ -30,10 +33,10 @@ not with congestion.
 import numpy as np
 
 from ..sensitivity import check_sensitivity
-from .solver_socp import (check_flow_map, solver_socp, solver_socp_auto_cascade, solver_socp_cascade, solver_socp_many, solver_socp_mesh_cascade,
-                          solver_socp_spacetime_cascade)
+from .solver_socp import (SolveSession, check_flow_map, solver_socp, solver_socp_auto_cascade, solver_socp_cascade, solver_socp_many,
+                          solver_socp_mesh_cascade, solver_socp_spacetime_cascade)
 
-__all__ = ["solver_socp", "solver_raw", "solver", "solver_socp_many", "solver_raw_many", "solver_many",
+__all__ = ["solver_socp", "solver_raw", "solver", "solver_socp_many", "solver_raw_many", "solver_many", "SolveSession",
            "solver_socp_cascade", "solver_raw_cascade", "solver_cascade",
            "solver_socp_mesh_cascade", "solver_raw_mesh_cascade", "solver_mesh_cascade",
            "solver_socp_spacetime_cascade", "solver_raw_spacetime_cascade", "solver_spacetime_cascade",

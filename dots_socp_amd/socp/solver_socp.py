@@ -265,6 +265,56 @@ class AlmSolver:
         self.dev = dev = DeviceProblem(n_time, geometry, lap_solver="modal_pcg" if direct else lap_solver, device=device,
                                        reorder=reorder, time_slab=time_slab, nd_leaf=nd_leaf, plan=plan, pcg_windows=bool(pcg_windows))
 
+        self.tau, self.eps = float(tau), float(eps)
+        self._init_from = init_from is not None      # (a level of a cascade: ``restart`` refuses it)
+
+        def install():
+            """What only a new solver does between the first push of the parameters and the start of the run: the state carried from
+            ``init_from``, the factor or the hierarchy, the initial state.  Returns the ``init_solution`` the constant scaling reads."""
+            nonlocal direct
+            if preconditioner not in ("multigrid", "jacobi"):
+                raise ValueError("preconditioner must be 'multigrid' or 'jacobi'")
+            self.prolong_ms = None          # device milliseconds of the transfer from ``init_from``
+            if carry is not None:
+                self.prolong_ms = carry(dev)
+                if release_init_from:
+                    init_from.close()
+            self.mg_summary = self.front_summary = None
+            self.lap_solver_fallback = None      # why the direct solve was not used although it was asked for
+            if direct and front_owner is not None:
+                self.front_summary = dev.share_frontal(front_owner)      # (no fall-back: a batch shares the factor or fails)
+            elif direct:
+                # Memory regime: the factor holds ~70 entries per vertex and time mode (8.9 GB at 500k vertices x 32 modes).  When it
+                # does not fit beside the state, step 1 runs the batched multigrid-PCG on the same modes instead -- the reference has
+                # no counterpart (laplacian_inverse_socp.py:34-41 just factorises); the choice is logged and reported in solver_stats.
+                try:
+                    self.front_summary = dev.setup_frontal(eps=self.eps)
+                except _lib.HipLibraryError as exc:
+                    if exc.status != _lib.ERR_MEMORY or time_slab is not None or (int(n_time) + 1 > MODAL_PCG_MAX_NODES and not pcg_windows):
+                        raise      # (above 256 time nodes only the windowed PCG is there to fall back to: without it the error names the sizes)
+                    self.lap_solver_fallback = str(exc)
+                    logger.warning("modal_direct -> modal_pcg with the multigrid preconditioner: %s", exc)
+                    self.direct = direct = False
+                    self._rhs_ahead_ok = False
+                    if preconditioner == "multigrid":
+                        self.mg_summary = dev.setup_multigrid(eps=self.eps, coarsest=mg_coarsest)
+            elif preconditioner == "multigrid" and lap_solver == "modal_pcg":
+                self.mg_summary = dev.setup_multigrid(eps=self.eps, coarsest=mg_coarsest)
+            init = init_solution or {}
+            if init_from is None:
+                self._upload_initial_state(init)
+            elif is_constant_scaling:
+                init = {"phi": dev.download("phi")}      # (_initial_constant_scaling borrows phi's storage and puts this back)
+            return init
+
+        self._start_run(congestion, cg=(cg_tol, int(cg_max_iter)), install=install)
+
+    def _start_run(self, congestion, cg=None, install=None, keep_phi=False):
+        """The start of a run on ``self.dev``, which holds its initial state or receives it from ``install()``: the host scalars of a
+        new context (``dev.params``), their push, the history, the timers, the validator, ``prim_gap``, the initial z scaling and the
+        constant scaling.  ``__init__`` runs it with ``cg`` (the PCG's tolerance and cap, set once) and ``install``; ``restart`` runs it
+        on the context ``dots_restart`` has reset, with ``keep_phi`` where the state is a warm start."""
+        dev, is_z_scaling, is_constant_scaling = self.dev, self.is_z_scaling, self.is_constant_scaling
         p = dev.params
         self.r = 1.0
         self.prim_scale = self.dual_scale = self.boundary_scale = 1.0
@@ -272,42 +322,13 @@ class AlmSolver:
         self.norm_d, self.norm_boundary = p.norm_d, p.norm_boundary
         self.congestion0 = float(congestion)
         self.congestion = float(congestion)
-        self.tau, self.eps = float(tau), float(eps)
-        dev.set_params(cg_tol=cg_tol, cg_max_iter=int(cg_max_iter))
+        if cg is not None:
+            dev.set_params(cg_tol=cg[0], cg_max_iter=cg[1])
         self._push()
-        if preconditioner not in ("multigrid", "jacobi"):
-            raise ValueError("preconditioner must be 'multigrid' or 'jacobi'")
-        self.prolong_ms = None          # device milliseconds of the transfer from ``init_from``
-        if carry is not None:
-            self.prolong_ms = carry(dev)
-            if release_init_from:
-                init_from.close()
-        self.mg_summary = self.front_summary = None
-        self.lap_solver_fallback = None      # why the direct solve was not used although it was asked for
-        if direct and front_owner is not None:
-            self.front_summary = dev.share_frontal(front_owner)      # (no fall-back: a batch shares the factor or fails)
-        elif direct:
-            # Memory regime: the factor holds ~70 entries per vertex and time mode (8.9 GB at 500k vertices x 32 modes).  When it
-            # does not fit beside the state, step 1 runs the batched multigrid-PCG on the same modes instead -- the reference has
-            # no counterpart (laplacian_inverse_socp.py:34-41 just factorises); the choice is logged and reported in solver_stats.
-            try:
-                self.front_summary = dev.setup_frontal(eps=self.eps)
-            except _lib.HipLibraryError as exc:
-                if exc.status != _lib.ERR_MEMORY or time_slab is not None or (int(n_time) + 1 > MODAL_PCG_MAX_NODES and not pcg_windows):
-                    raise      # (above 256 time nodes only the windowed PCG is there to fall back to: without it the error names the sizes)
-                self.lap_solver_fallback = str(exc)
-                logger.warning("modal_direct -> modal_pcg with the multigrid preconditioner: %s", exc)
-                self.direct = direct = False
-                self._rhs_ahead_ok = False
-                if preconditioner == "multigrid":
-                    self.mg_summary = dev.setup_multigrid(eps=self.eps, coarsest=mg_coarsest)
-        elif preconditioner == "multigrid" and lap_solver == "modal_pcg":
-            self.mg_summary = dev.setup_multigrid(eps=self.eps, coarsest=mg_coarsest)
-        init_solution = init_solution or {}
-        if init_from is None:
-            self._upload_initial_state(init_solution)
-        elif is_constant_scaling:
-            init_solution = {"phi": dev.download("phi")}      # (_initial_constant_scaling borrows phi's storage and puts this back)
+        if install is not None:
+            init_solution = install()
+        else:      # (a warm restart left the recovered iterate in place; the constant scaling borrows phi's storage and puts this back)
+            init_solution = {"phi": dev.download("phi")} if is_constant_scaling and keep_phi else {}
 
         self.run_history = RunningHistory(max_record_numbers=self.nit, kkt_labels=KKT_LABELS,
                                           kkt_short_labels=KKT_SHORT_LABELS, name="SOCP")
@@ -331,7 +352,7 @@ class AlmSolver:
             self._initial_constant_scaling(init_solution)                # :574-586
 
         self._kkt_cache = {}
-        conditions = [ErrorCondition((lambda i=i: self._kkt_value(i)), tol, KKT_SHORT_LABELS[i]) for i in range(7)]
+        conditions = [ErrorCondition((lambda i=i: self._kkt_value(i)), self.tol, KKT_SHORT_LABELS[i]) for i in range(7)]
         self.kkt_validator = AdaptiveValidator(ConditionValidator(conditions, KKT_QUEUE_ORDER))   # :589-645
         self.start_time = time.perf_counter()
 
@@ -619,6 +640,7 @@ class AlmSolver:
         # right-hand side and cone projection would gather from B, E and beta_mid (DOTS_STEP_CARRY: one pass over beta_mid less).
         self._carry = self._carry_ok and it + 1 < self.nit and not params.peek_adjust(it)
         self._pass = (it, is_time_used_up, quiet)
+        self._last_quiet = quiet        # (a quiet step stores no z_mid: ``restart(warm=True)`` needs the iterate of a read-back)
         return quiet
 
     def iterate_end(self):
@@ -861,7 +883,71 @@ class AlmSolver:
         return solution, hist
 
     def close(self):
+        self.closed = True
         self.dev.close()
+
+    def restart(self, mu0, mu1, warm=True, nit=None, tol=None, tol_checkpoints=None, time_limit=None, congestion=None):
+        """The next problem of a solve session on the live context: other end masses ``mu0`` / ``mu1`` (V,) on the same surface
+        (DeviceProblem.restart: dots_restart).  The factor, the hierarchy and the plan are kept; the run starts as a new solver's does
+        (r = 1, the initial z scaling, a fresh penalty schedule, validator and history).  ``warm=True``: from the recovered iterate
+        the solver holds, rescaled in place on the device -- the state a new solver with ``init_solution=`` all twelve arrays of
+        ``finalize()`` starts from, bit for bit, without the arrays crossing to the host; ``warm=False``: from zero, as a new solver.
+        May be called mid-run, after the run has finished or after ``finalize``, not after ``close``; the caller's arrays and
+        ``geometry`` dict are not written to (``self.geometry`` becomes a shallow copy with the new masses).  ``nit``, ``tol``,
+        ``tol_checkpoints``, ``time_limit``, ``congestion``: None keeps the solver's.  Torch tensors on the context's device are read
+        there (their finiteness is then the caller's business).  Returns the device milliseconds of the call."""
+        tol = self.tol if tol is None else tol
+        checkpoints = _validate_checkpoints(tol_checkpoints, tol)
+        if getattr(self, "closed", False):
+            raise ValueError("restart: the solver is closed")
+        if getattr(self.dev, "slab", None):
+            raise ValueError("restart: not available on time slabs")
+        if getattr(self, "_init_from", False):
+            raise ValueError("restart: the solver was started from init_from (a level of a cascade); sessions over the cascades are not supported")
+        if self.batched:
+            raise ValueError("restart: the solver is stepped by a batch (solver_socp_many); sessions over batches are not supported")
+        V = int(np.asarray(self.geometry["vertices"]).shape[0])
+        on_device = all(type(a).__module__.startswith("torch") and getattr(a, "is_cuda", False) for a in (mu0, mu1))
+        masses = []
+        for name, a in (("mu0", mu0), ("mu1", mu1)):
+            if not on_device:
+                a = np.asarray(a.detach().cpu().numpy() if type(a).__module__.startswith("torch") else a, dtype=np.float64)
+                if a.shape == (V,) and not np.all(np.isfinite(a)):
+                    raise ValueError(f"restart: {name} has entries that are not finite")
+            if tuple(a.shape) != (V,):
+                raise ValueError(f"restart: {name} must have shape ({V},), got {tuple(a.shape)}")
+            masses.append(a)
+        if warm and self.counter_main >= 0 and getattr(self, "_last_quiet", False) and not self.is_palm:
+            raise ValueError("restart: the last iteration stored no z_mid (nothing was read back after it): a warm restart needs the "
+                             "whole iterate; iterate to a read-back or restart cold")
+        factors = self.recovery_factors() if warm else None
+        ms = self.dev.restart(masses[0], masses[1], "warm" if warm else "cold", factors, device_pointers=on_device)
+        if on_device:      # (the plan's host copies, back in the caller's numbering: read_out and flow_map take the end masses from the geometry)
+            order = self._caller_order()
+            masses = [self.dev.plan.mu0[order], self.dev.plan.mu1[order]]
+        self.geometry = {**self.geometry, "mu0": np.array(masses[0]), "mu1": np.array(masses[1])}
+        if nit is not None:
+            self.nit = int(nit)
+        if time_limit is not None:
+            self.time_limit = time_limit
+        self.tol, self.tol_checkpoints = tol, checkpoints
+        self.checkpoint_solutions = []
+        self.untimed_steps = self.quiet_steps = 0
+        self._timed_in_flight = []      # (dots_restart emptied the library's ring)
+        self._rhs_ahead = self._carry = self._fused_kkt = False
+        self._pass, self._last_quiet = None, False
+        self._start_run(self.congestion0 if congestion is None else congestion, keep_phi=bool(warm))
+        self.restart_ms = ms
+        return ms
+
+    def _caller_order(self):
+        """Index array that takes a per-vertex array of the plan (device numbering) to the caller's numbering."""
+        perm = self.dev.plan.perm_vert
+        inv = np.arange(self.dev.V)
+        if perm is not None:
+            inv = np.empty(self.dev.V, dtype=np.int64)
+            inv[perm] = np.arange(self.dev.V)
+        return inv
 
 
 def solver_socp(
@@ -928,6 +1014,114 @@ def solver_socp(
         return alm.finalize(outputs=outputs, read_out=read_out, flow_map=flow_map, sensitivity=sensitivity)
     finally:
         alm.close()
+
+
+# ---- a sequence of problems on one surface, one live context -----------------------------------------------------------------
+SESSION_KEYS = ("congestion", "nit", "eps", "tol", "tau", "is_palm", "is_multi_threads", "is_z_scaling", "is_constant_scaling",
+                "check_kkt_step_by_step", "tol_checkpoints", "time_limit", "lap_solver", "cg_tol", "cg_max_iter", "device", "reorder",
+                "preconditioner", "mg_coarsest", "nd_leaf", "pcg_windows")
+SESSION_SOLVE_KEYS = ("nit", "tol", "tol_checkpoints", "time_limit", "congestion")      # what one solve of a session may change
+
+
+def _is_device_tensor(a):
+    return type(a).__module__.startswith("torch") and bool(getattr(a, "is_cuda", False))
+
+
+class SolveSession:
+    """One device context and one factor for a sequence of transport problems on one surface, whose end masses change from solve to
+    solve: ``with SolveSession(n_time, geometry, **solver_options) as s: solution, hist = s.solve(mu0, mu1)``.
+
+    ``geometry``: the mesh (``vertices``, ``triangles``; ``mu0`` / ``mu1`` in it are ignored); ``solver_options``: the keywords of
+    ``solver_socp`` that shape the solver (``SESSION_KEYS``; no ``init_solution``: a session starts from zero or from its own last
+    iterate).  The first ``solve`` builds the solver -- plan, factor, context --, every later one restarts it on the device
+    (``AlmSolver.restart``: dots_restart): nothing is rebuilt, and nothing but what the caller asks for crosses to the host.
+    ``close()`` (or leaving the ``with`` block) releases the context.  Not over ``solver_socp_many``, the cascades, time slabs or
+    moved vertices (a numeric re-factorisation is another call)."""
+
+    def __init__(self, n_time, geometry, **solver_options):
+        unknown = set(solver_options) - set(SESSION_KEYS)
+        if unknown:
+            raise ValueError(f"SolveSession: unknown option(s) {sorted(unknown)}; known: {list(SESSION_KEYS)}")
+        if not isinstance(geometry, dict) or "vertices" not in geometry or "triangles" not in geometry:
+            raise ValueError("SolveSession: geometry must be a dict with 'vertices' and 'triangles'")
+        options = dict(solver_options)
+        options.pop("is_multi_threads", None)
+        check_time_nodes(n_time, options.get("lap_solver", "modal_direct"), None, options.get("pcg_windows", False))
+        _validate_checkpoints(options.get("tol_checkpoints"), options.get("tol", 1e-4))
+        if int(options.get("nit", 1000)) < 1:
+            raise ValueError("SolveSession: nit must be at least 1")
+        self.n_time, self.options = int(n_time), options
+        self.geometry = {k: v for k, v in geometry.items() if k not in ("mu0", "mu1")}
+        self.n_vertices = int(np.asarray(geometry["vertices"]).shape[0])
+        self.alm = None
+        self.index = 0                  # solves so far
+        self.setup_seconds = None       # of the first solve: what every later one saves
+        self.closed = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        self.closed = True
+        if self.alm is not None:
+            self.alm.close()
+
+    def _masses(self, mu0, mu1, to_host):
+        out = []
+        for name, a in (("mu0", mu0), ("mu1", mu1)):
+            if not _is_device_tensor(a) or to_host:
+                a = np.asarray(a.detach().cpu().numpy() if type(a).__module__.startswith("torch") else a, dtype=np.float64)
+                if a.shape == (self.n_vertices,) and not np.all(np.isfinite(a)):
+                    raise ValueError(f"SolveSession.solve: {name} has entries that are not finite")
+            if tuple(a.shape) != (self.n_vertices,):
+                raise ValueError(f"SolveSession.solve: {name} must have shape ({self.n_vertices},), got {tuple(a.shape)}")
+            out.append(a)
+        return out
+
+    def solve(self, mu0, mu1, warm=True, outputs=None, read_out=None, flow_map=None, sensitivity=None, **per_solve):
+        """Solve the problem with the end masses ``mu0`` / ``mu1`` (V,): returns ``(solution, run_history)`` as ``solver_socp(n_time,
+        {**geometry, "mu0": mu0, "mu1": mu1}, **solver_options)`` does -- with ``warm=False`` bit for bit.  ``warm=True`` (the default)
+        starts from the session's last iterate, rescaled on the device: what ``init_solution=`` the whole previous solution does over
+        the host, bit for bit; on the first solve it is a cold start.  ``outputs``, ``read_out``, ``flow_map``, ``sensitivity``: as for
+        ``solver_socp``.  ``per_solve``: ``nit``, ``tol``, ``tol_checkpoints``, ``time_limit``, ``congestion`` for this and the later
+        solves.  The masses may be torch tensors on the context's device: from the second solve on they are read there.
+        ``run_history.solver_stats["session"]`` = {"index", "warm", "restart_ms" (device milliseconds of the restart; None on the first
+        solve), "setup_seconds" (wall time before the first iteration of this solve), "setup_seconds_saved" (the first solve's
+        set-up: what this one did not repeat; 0 on the first)}."""
+        if self.closed:
+            raise ValueError("SolveSession.solve: the session is closed")
+        unknown = set(per_solve) - set(SESSION_SOLVE_KEYS)
+        if unknown:
+            raise ValueError(f"SolveSession.solve: unknown option(s) {sorted(unknown)}; known: {list(SESSION_SOLVE_KEYS)}")
+        if read_out is not None and outputs is not None:
+            raise ValueError("SolveSession.solve: outputs and read_out are mutually exclusive (read_out returns mu and E only)")
+        flow_map = check_flow_map(flow_map, n_time=self.n_time)
+        congestion = per_solve.get("congestion", self.options.get("congestion", 0.0) if self.alm is None else self.alm.congestion0)
+        sensitivity = check_sensitivity(sensitivity, congestion=congestion)
+        first = self.alm is None
+        m0, m1 = self._masses(mu0, mu1, to_host=first)
+        t0 = time.perf_counter()
+        if first:
+            self.options.update(per_solve)
+            self.alm = AlmSolver(self.n_time, {**self.geometry, "mu0": m0.copy(), "mu1": m1.copy()}, **self.options)
+            warm, restart_ms = False, None
+        else:
+            restart_ms = self.alm.restart(m0, m1, warm=bool(warm), **per_solve)
+        setup = time.perf_counter() - t0
+        if first:
+            self.setup_seconds = setup
+        alm = self.alm
+        for _ in range(alm.nit):
+            if alm.iterate():
+                break
+        solution, hist = alm.finalize(outputs=outputs, read_out=read_out, flow_map=flow_map, sensitivity=sensitivity)
+        hist.solver_stats["session"] = {"index": self.index, "warm": bool(warm), "restart_ms": restart_ms, "setup_seconds": setup,
+                                        "setup_seconds_saved": 0.0 if first else self.setup_seconds}
+        self.index += 1
+        return solution, hist
 
 
 # ---- several problems on one surface, one factor ---------------------------------------------------------------------------

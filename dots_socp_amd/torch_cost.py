@@ -33,10 +33,19 @@ def _like(array, ref):
 
 class _TransportCost(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, mu0, mu1, vertices, triangles, n_time, options):
+    def forward(ctx, mu0, mu1, vertices, triangles, n_time, options, session=None):
         x, tri = _host(vertices), np.asarray(_host(triangles), dtype=np.int64)
-        geom, _ = meshes.make_geometry(x, tri, _host(mu0), _host(mu1), normalize=False)      # the geometry as given
-        solution, hist = solver_socp(int(n_time), geom, outputs=(), sensitivity=_request(ctx.needs_input_grad), **options)
+        if session is not None:      # the session's live context: the masses change, the mesh must be the session's
+            if int(n_time) != session.n_time:
+                raise ValueError(f"transport_cost: n_time = {int(n_time)}, the session's {session.n_time}")
+            if not (np.array_equal(x, np.asarray(session.geometry["vertices"], dtype=np.float64))
+                    and np.array_equal(tri, np.asarray(session.geometry["triangles"], dtype=np.int64))):
+                raise ValueError("transport_cost: vertices / triangles are not the session's (a session solves on one mesh; moved "
+                                 "vertices need a new session)")
+            solution, hist = session.solve(mu0.detach(), mu1.detach(), outputs=(), sensitivity=_request(ctx.needs_input_grad), **options)
+        else:
+            geom, _ = meshes.make_geometry(x, tri, _host(mu0), _host(mu1), normalize=False)      # the geometry as given
+            solution, hist = solver_socp(int(n_time), geom, outputs=(), sensitivity=_request(ctx.needs_input_grad), **options)
         ctx.sens, ctx.mesh = solution.get("sensitivity"), (x, tri)
         ctx.like = (mu0, mu1, vertices)
         return torch.tensor(float(hist.history["Transportation cost"][-1]), dtype=torch.float64, device=mu0.device)
@@ -46,23 +55,30 @@ class _TransportCost(torch.autograd.Function):
         g0, g1, gx = sensitivity.cost_gradients(ctx.sens, *ctx.mesh)
         grads = [None if a is None or not need else g.to(ref.device, ref.dtype) * _like(a, ref)
                  for a, need, ref in zip((g0, g1, gx), ctx.needs_input_grad[:3], ctx.like)]
-        return (*grads, None, None, None)
+        return (*grads, None, None, None, None)
 
 
 def _tensor(a):
     return a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, dtype=np.float64))
 
 
-def transport_cost(mu0, mu1, vertices, triangles, n_time, **solver_options):
+def transport_cost(mu0, mu1, vertices, triangles, n_time, session=None, **solver_options):
     """The transport cost between the masses ``mu0`` and ``mu1`` (V,) on the mesh (``vertices`` (V, 3), ``triangles`` (F, 3)) with
     ``n_time`` intervals, as a scalar fp64 tensor on ``mu0``'s device, differentiable in ``mu0``, ``mu1`` and ``vertices``.  Forward:
     one ``solver_socp`` call on the geometry as given (``meshes.make_geometry(..., normalize=False)``) with ``solver_options`` (tol,
     nit, ...); only what an input that requires a gradient needs is reduced.  Backward: ``sensitivity.cost_gradients``.  The
-    gradients in the masses are mean-free (the cost is defined for equal total masses); the one in ``vertices`` needs congestion 0."""
+    gradients in the masses are mean-free (the cost is defined for equal total masses); the one in ``vertices`` needs congestion 0.
+    ``session``: a ``socp.SolveSession`` on this mesh (``meshes.make_geometry(vertices, triangles, ..., normalize=False)``) and
+    ``n_time``: the forward pass is ``session.solve`` on its live context -- no plan, factor or context is built again -- and
+    ``solver_options`` are that call's (``warm``, ``tol``, ``nit``, ``time_limit``, ``congestion``); ``vertices`` / ``triangles`` must be
+    the session's, by value.  With ``warm=False`` cost and gradients are those of the call without a session, bit for bit; the
+    gradient in ``vertices`` is still the stress of the current geometry."""
     for k in ("outputs", "read_out", "flow_map", "sensitivity"):
         if k in solver_options:
             raise ValueError(f"transport_cost: '{k}' is chosen by the function itself")
-    return _TransportCost.apply(_tensor(mu0), _tensor(mu1), _tensor(vertices), triangles, n_time, solver_options)
+    if session is None and "warm" in solver_options:
+        raise ValueError("transport_cost: 'warm' needs a session (a call without one starts from zero)")
+    return _TransportCost.apply(_tensor(mu0), _tensor(mu1), _tensor(vertices), triangles, n_time, solver_options, session)
 
 
 class _TransportCosts(torch.autograd.Function):

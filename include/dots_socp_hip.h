@@ -828,6 +828,42 @@ typedef struct dots_sensitivity_desc {
 } dots_sensitivity_desc;
 int dots_sensitivity(dots_ctx *ctx, const dots_sensitivity_desc *desc);
 
+/* ---- solve session: new end masses on a live context ---------------------------------------------------------------------------
+ * dots_restart: the context takes the end masses mu0 / mu1 of another transport problem on the same surface and starts over, with
+ * everything that does not depend on them kept: the factor (its own or a shared one: only this context's state changes), the
+ * multigrid hierarchy, the PCG work arrays, the window setting (dots_pcg_windows), every allocation.  Nothing is rebuilt and nothing
+ * crosses to the host.
+ *   Boundary data: mu0 / mu1 replace the context's; norm_boundary is formed again.  From host arrays with the loop of dots_create: the
+ *     bits of a new context.  With device_pointers the sum is a two-stage reduction on the device in a fixed order (every lane of up
+ *     to 1024 workgroups adds its vertices in ascending order, the lanes of a workgroup fold in a fixed tree, one workgroup folds the
+ *     workgroups' sums the same way): reproducible from call to call, but not the host loop's bits (the two agree to V roundings).  The caller's device arrays must be complete before the call (it reads them on the context's
+ *     stream).
+ *   Parameters: dots_params as dots_create leaves them -- r = scale_z = const_d = 1, prim / dual / boundary scale 1, congestion 0,
+ *     norm_d as at creation --, except tau, eps, cg_tol and cg_max_iter, which are kept.
+ *   DOTS_RESTART_COLD: a pending penalty division is dropped without being applied, the twelve state arrays (one launch of the same
+ *     kernel family, stores only) and what is derived from them (the cone multiplier, the buffers written ahead, the PCG vectors and
+ *     scalars) are zeroed: a new context's state.
+ *   DOTS_RESTART_WARM: a pending penalty division is carried out and z_mid materialised, as for dots_download; then every element of
+ *     array k is multiplied once by factors[group(k)] -- groups (phi, A, B, lambda_c), the z arrays, (mu, E), the beta arrays: the
+ *     recovered solution (solver_socp.py:397-405) -- in place, in ONE launch (two time columns per lane, 16-byte accesses; the
+ *     padding columns are zero afterwards).  The state then holds the bits that downloading the twelve arrays, multiplying them on the
+ *     host and uploading them into a new context at r = 1 leaves.
+ *   Both modes drop what belongs to the old run: a right-hand side enqueued ahead, an armed penalty decision, the carried gathers,
+ *     the fused KKT sums, the step path, the step flags, the KKT halo flag, the mailbox sequence and the step-time ring (records not
+ *     yet collected by dots_step_times are lost).
+ * The call returns with the stream synchronised.  DOTS_ERR_ARGUMENT (the context is untouched): NULL desc or mass array, an unknown
+ * mode, a host mass that is not finite, a WARM factor that is not finite and positive; DOTS_ERR_STATE (untouched as well): a time slab,
+ * WARM when z_mid was not materialised by the last step (dots_step_flags).  dots_bench_kernel(which = 5) times the WARM launch alone. */
+enum { DOTS_RESTART_COLD = 0, DOTS_RESTART_WARM = 1 };
+typedef struct dots_restart_desc {
+    const double *mu0, *mu1;     /* [V] each, in the numbering of dots_problem_desc (the device numbering)                      */
+    int32_t device_pointers;     /* 0: mu0 / mu1 are host addresses; 1: device addresses on the context's device               */
+    int32_t mode;                /* DOTS_RESTART_COLD or DOTS_RESTART_WARM                                                     */
+    double factors[4];           /* WARM: multipliers of (phi, A, B, lambda_c), the z arrays, (mu, E), the beta arrays          */
+    double *ms;                  /* NULL, or HOST out: device milliseconds of the call's launches and memsets                  */
+} dots_restart_desc;
+int dots_restart(dots_ctx *ctx, const dots_restart_desc *desc);
+
 /* ---- levels of a cascade in space from ONE mesh: coarsen on the host, locate on the device ------------------------------------
  * dots_coarsen: half-edge-collapse decimation of the mesh (xyz [V][3], tri [F][3]) towards `n_target` vertices, host only (no
  * device work; dots_socp_amd/meshes.py: coarsen(backend="python") is the specification and states the rules; both return the same
@@ -881,7 +917,9 @@ int dots_front_pitch(dots_ctx *ctx);
  * one launch moves (DESIGN.md section "roofline"). */
 /* which: 0 PCG operator application, 1 PCG vector update, 2 one multigrid V-cycle, 3 both sweeps of the direct
  * solve, 4 one calibration launch (k_calib_stream: reads and writes *bytes_per_launch bytes each, 8 B per lane)
- * for the PMC traffic counters.  DOTS_ERR_STATE for 0, 1 and 2 on a modal context of T+1 > 256 (the PCG takes 256 modes) */
+ * for the PMC traffic counters, 5 the in-place rescaling launch of dots_restart(DOTS_RESTART_WARM) over the twelve state arrays with
+ * every factor 1 (the state keeps its values; not on a time slab).  DOTS_ERR_STATE for 0, 1 and 2 on a modal context of T+1 > 256
+ * (the PCG takes 256 modes) */
 int dots_bench_kernel(dots_ctx *ctx, int which, int reps, double *ms_per_launch, double *bytes_per_launch);
 
 /* diagnostics: which = 0 KKT read-backs whose mailbox sequence number never arrived (the sums were then copied from the
