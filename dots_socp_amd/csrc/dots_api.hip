@@ -357,6 +357,12 @@ __global__ __launch_bounds__(BLOCK) void k_slab_append_multiplier(Dev d, double 
     if (v < d.V) tail[v] = (d.ni == d.nl && d.nl > 0) ? d.lamc[idxV(d, v, d.nl - 1)] : 0.0;
 }
 
+// dots_upload of phi with the next slab's first node as one more row (reference layout: vertex v of the host is row perm_v^-1 here)
+__global__ __launch_bounds__(BLOCK) void k_slab_phi_hi(Dev d, const double *__restrict__ row, double *__restrict__ phi_hi) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i < d.V) phi_hi[i] = row[d.perm_v ? d.perm_v[i] : i];
+}
+
 static int slab_stage(Ctx *c, int stage) {
     int rc;
     const Dev &d = c->d;
@@ -689,10 +695,18 @@ int64_t dots_device_bytes(dots_ctx *c) { return c ? c->bytes : -1; }
 int dots_upload(dots_ctx *c, int id, const double *host, int64_t count) {
     int rc = check(c);
     if (rc) return rc;
-    if (id < 0 || id >= DOTS_N_ARRAYS || !host || count != array_count_host(c->d, id)) { set_error("upload: bad array id or element count"); return DOTS_ERR_ARGUMENT; }
+    // a time slab that has a next slab may bring phi at that slab's first node along, as one more row: it becomes phi_hi, which only
+    // this rank's inverse transform writes otherwise (step 0 of DOTS_STEP_PALM and the KKT kernels read it before the first solve)
+    const bool with_hi = id == DOTS_PHI && host && c->d.slab && c->d.phi_hi && c->d.nl > 0 && c->d.t0 + c->d.nl <= c->d.T &&
+                         count == array_count_host(c->d, id) + c->d.V && count <= c->stage_count;
+    if (id < 0 || id >= DOTS_N_ARRAYS || !host || (count != array_count_host(c->d, id) && !with_hi)) { set_error("upload: bad array id or element count"); return DOTS_ERR_ARGUMENT; }
     if (id != DOTS_Z_MID && (rc = materialise_zmid(c))) return rc;
     DOTS_HIP(hipMemcpyAsync(c->stage, host, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, c->stream));
     if ((rc = launch_to_device_layout(c, id, c->stage))) return rc;
+    if (with_hi) {
+        hipLaunchKernelGGL(k_slab_phi_hi, dim3((c->d.V + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, c->d, c->stage + (int64_t)c->d.nl * c->d.V, c->d.phi_hi);
+        DOTS_HIP(hipGetLastError());
+    }
     DOTS_HIP(hipStreamSynchronize(c->stream));
     if (id == DOTS_Z_MID) { c->zmid_stale = 0; c->zmid_deferred = 0; }      // (the upload is what z_mid's storage now holds)
     c->kkt_halo_fresh = 0;

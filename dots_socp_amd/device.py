@@ -141,9 +141,10 @@ class DeviceProblem:
         T, V, F = self.T, self.V, self.F
         return {"phi": (T + 1, V), "B": (T + 1, F, 3), "E": (T + 1, F, 3), "z_mid": (T, 2, 3, F, 3), "beta_mid": (T, 2, 3, F, 3)}.get(name, (T, V))
 
-    def to_slab(self, name, full):
-        """This slab's part of a whole array in the reference layout (see include/dots_socp_hip.h: the corner arrays
-        are indexed by the node an entry is compared with)."""
+    def to_slab(self, name, full, with_next_node=False):
+        """This slab's part of a whole array in the reference layout, of shape ``shape(name)`` (see include/dots_socp_hip.h: the
+        corner arrays are indexed by the node an entry is compared with).  ``with_next_node``: phi with the next slab's first
+        node as one more row, where a next slab exists -- the form in which ``upload`` also sets that node."""
         full = np.asarray(full, dtype=np.float64)
         n0, nl, ni = self.node0, self.nl, self.ni
         if name in ("z_mid", "beta_mid"):
@@ -152,6 +153,8 @@ class DeviceProblem:
             lo = 1 if n0 == 0 else 0                           # entry [j][1] is the reference's [n0 + j - 1][1]
             out[lo:nl, 1] = full[n0 + lo - 1:n0 + nl - 1, 1]
             return out
+        if with_next_node and name == "phi" and self.slab and nl and n0 + nl <= self.T:
+            return np.ascontiguousarray(full[n0:n0 + nl + 1])      # ... and the next slab's first node (``upload``)
         return np.ascontiguousarray(full[n0:n0 + (nl if name in ("phi", "B", "E") else ni)])
 
     def from_slab(self, name, part, full):
@@ -169,7 +172,10 @@ class DeviceProblem:
     # ---- state transfer
     def upload(self, name, array):
         a = np.ascontiguousarray(array, dtype=np.float64)
-        if a.shape != self.shape(name):
+        # a time slab's phi may come with the next slab's first node as one more row (``to_slab(..., with_next_node=True)``): only this rank's
+        # solves write that node otherwise, and step 0 of is_palm and the KKT residuals read it
+        with_next = name == "phi" and self.slab and self.nl and self.node0 + self.nl <= self.T and a.shape == (self.nl + 1, self.V)
+        if a.shape != self.shape(name) and not with_next:
             raise ValueError(f"{name}: expected shape {self.shape(name)}, got {a.shape}")
         _lib.check(self.lib.dots_upload(self._h, _lib.ARRAY_IDS[name], _ptr(a, C.c_double), a.size), f"upload {name}")
 

@@ -23,9 +23,9 @@ One iteration (``dots_slab_stage`` 0, 6, 5, 2, 3; include/dots_socp_hip.h) has t
 
 The KKT residuals and the objective are sums over space-time: each rank forms the sums of its slab (after one more halo
 exchange for the time stencils inside them) and ONE all-reduce of 24 doubles per evaluation adds them
-(``solver_socp.py:433-559``); every rank then takes the same control decisions.  Iterates are bit-identical for every
-number of ranks (wherever a value is computed, the same sum is formed in the same order); only those sums differ in
-rounding.
+(``solver_socp.py:433-559``); every rank then takes the same control decisions.  Iterates are bit-identical for rank
+counts of equal slab pitch (wherever a value is computed, the same sum is formed in the same order; the sweeps of the direct
+solver split their dot products by that pitch); only those sums differ in rounding.
 
 ``ShardedAlmSolver`` is ``AlmSolver`` with the device step and every read-back replaced.  Communicators: ``TorchComm``
 (torch.distributed; "nccl" = RCCL on ROCm with device tensors; with "gloo" the payload is staged through the host) and
@@ -346,7 +346,7 @@ class ShardedAlmSolver(AlmSolver):
         r, sz = self.r, self.scale_z
         for k in ("phi", "A", "B", "lambda_c"):
             if k in have:
-                dev.upload(k, dev.to_slab(k, have[k]))
+                dev.upload(k, dev.to_slab(k, have[k], with_next_node=k == "phi"))      # (step 0 of is_palm and the first KKT sums read that node)
         for k in ("z_fst", "z_mid", "z_end"):
             if k in have:
                 dev.upload(k, dev.to_slab(k, sz * have[k]))

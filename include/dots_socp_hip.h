@@ -21,6 +21,9 @@
  *       phi (n, V); interval arrays (m, V); B, E (n, F, 3) with n = slab_count nodes, m = min(n, T - slab_begin)
  *       intervals; z_mid, beta_mid (n, 2, 3, F, 3) indexed by the NODE an entry is compared with: entry [j][s] is the
  *       reference's [slab_begin + j - s][s] (entries whose interval does not exist: ignored on upload, zero on download).
+ *       dots_upload of phi also takes (n + 1, V) on a slab that has a next slab: the last row is phi at that slab's first node,
+ *       which stage 3 computes redundantly and step 0 of DOTS_STEP_PALM and the KKT sums read.  Without that row the node keeps
+ *       what the last stage 3 left (zero on a fresh context): upload it whenever one of the two follows before a stage 3.
  *   - no C++ exceptions, torch types or Python objects cross this boundary.
  */
 #ifndef DOTS_SOCP_HIP_H
@@ -194,7 +197,8 @@ int dots_step(dots_ctx *ctx, int n_iters, dots_step_stats *stats);
  * the finished slots later, oldest first (the reference's per-step timers, utils/admm_tools.py:244-251, without a host wait in
  * the loop).  A step that finds the ring full is simply not timed. */
 #define DOTS_STEP_TIMED 8u
-/* DOTS_STEP_CARRY (a hint: ignored without the direct solver, on a time slab, with DOTS_STEP_PALM or a time pitch above 128): the caller
+/* DOTS_STEP_CARRY (a hint: ignored without the direct solver, with DOTS_STEP_PALM or a time pitch above 128; a time slab with a factor
+ * carries too, at its own pitch: its stage 0 packs send_nsq from the carried sums, stages 1 / 6 and 5 stream them): the caller
  * expects the NEXT iteration to start from the state this step leaves.  Steps 2+3 then also store, per corner of every triangle,
  * what the next right-hand side (solver_socp.py:983-986: div_x((B - E) area)) and the next cone projection (:997-1017: the squared
  * norm of D (L B - beta_mid)) would gather from B, E and beta_mid -- they hold those values in registers when they write them
@@ -243,9 +247,10 @@ int dots_step_times(dots_ctx *ctx, dots_step_stats *out, int capacity, int wait,
  * Stages must be called in order 0,1,2,3 or 0,6,5,2,3 (DOTS_ERR_STATE otherwise).  With stats == NULL a stage is only enqueued on the
  * context's stream: the caller orders its exchanges against it with dots_stream_wait (no host wait anywhere).
  * All buffers are DEVICE memory owned by the caller (e.g. torch tensors handed to RCCL), registered once with
- * dots_slab_set_buffers; sizes from dots_slab_elems.  Results are bit-identical for every number of ranks, 1 included
- * (the same sums are formed in the same order wherever a value is computed); only the KKT / objective sums differ in
- * rounding (partial sums per slab). */
+ * dots_slab_set_buffers; sizes from dots_slab_elems.  Results are bit-identical for rank counts of equal slab pitch
+ * (max(4, slab_stride rounded up to a power of two): the element-wise steps form the same sums in the same order wherever a
+ * value is computed, the sweeps of the direct solver split their dot products by that pitch); only the KKT / objective sums
+ * differ in rounding (partial sums per slab). */
 typedef struct dots_slab_buffers {
     double *send_x, *send_nsq;      /* [V] each: stage 0 output                                              */
     double *recv_x, *recv_nsq;      /* [V] each: from the previous / next rank                               */

@@ -8,6 +8,11 @@ Every fake rank keeps the WHOLE state (the oracle's arrays) and advances it redu
 wiring: each stage writes exactly the payload a real slab would send, and every payload RECEIVED through the driver's
 exchanges is compared with the value this rank's own whole state says it must have (direction, neighbour, buffer
 layout, ordering).  The slab numerics themselves are the business of the GPU tests (tests/test_hip_sharded.py).
+
+``local=True`` creates a LOCAL rank (tests/slab_checks.py, test_slab_checks_cpu.py): it knows its own slab only -- every entry of another
+slab is NaN -- takes ``upload``, and each stage works from the slab and the payloads it RECEIVED, as a device slab does (the checks
+against the whole state are off: there is none).  A payload that is wrong, stale or ignored then shows in what the rank downloads.
+``defect`` names one deliberate defect of that kind (DEFECTS): the checks of slab_checks must catch every one of them.
 """
 import ctypes
 import types
@@ -32,8 +37,15 @@ def _stats(**kw):
     return types.SimpleNamespace(**base)
 
 
+# deliberate defects of a LOCAL rank (the s = 1 half of a corner array shifted in to_slab is the adapter's: slab_checks.SlabDevice)
+DEFECTS = ("recv_nsq_zero", "recv_x_zero", "stale_tail", "stale_phi_hi", "kkt_halos_missing")
+KKT_SUMS = 24
+
+
 class FakeDeviceProblem:
-    def __init__(self, n_time, geometry, lap_solver="modal_pcg", device=0, reorder=True, plan=None, time_slab=None, **_ignored):
+    defect = None
+
+    def __init__(self, n_time, geometry, lap_solver="modal_pcg", device=0, reorder=True, plan=None, time_slab=None, local=False, **_ignored):
         from dots_socp_amd.geometry import time_modes
 
         self.s = O.OracleSolver(n_time, geometry)
@@ -64,8 +76,18 @@ class FakeDeviceProblem:
                                           hat_grad=real.hat_grad, triangles=real.triangles)
         self.v2c = O.corner_maps(s.V, s.tri, s.area_f)[2]          # (3F, V) 0/1
         self.stage = 0
+        self.local = False
+        self.palm = False
         self.kkt_halo_fresh = False
         self.checked = {"recv_x": 0, "recv_nsq": 0, "lamc_lo": 0, "b": 0, "x": 0, "recv_mu": 0, "recv_b": 0}
+        if local:      # a fresh context: zero on its own slab; nothing is known of the others
+            self.local = True
+            for k in O.OracleSolver.STATE:
+                full = getattr(s, k)
+                own = self.to_slab(k, full)
+                full[...] = np.nan
+                self.from_slab(k, own, full)
+            self.phi_hi = np.zeros(self.V)
 
     # ---- bookkeeping
     def close(self):
@@ -90,8 +112,12 @@ class FakeDeviceProblem:
         s.bnd[0] = -p.boundary_scale * self.mu0 / (p.r * s.h)
         s.bnd[-1] = p.boundary_scale * self.mu1 / (p.r * s.h)
 
-    def step_flags(self, skip_z_mid=False, palm=False, timed=False, carry=False):
+    def step_flags(self, skip_z_mid=False, palm=False, timed=False, carry=False, **_hints):
         self.palm = palm
+        self.skip_z_mid = skip_z_mid
+
+    def debug_counter(self, which=0):
+        return 0       # (no kernels here: nothing is recorded)
 
     def step_times(self, wait=False, capacity=64):
         return []
@@ -111,10 +137,10 @@ class FakeDeviceProblem:
     def full_shape(self, name):
         return getattr(self.s, name).shape
 
-    def to_slab(self, name, full):
+    def to_slab(self, name, full, with_next_node=False):
         from dots_socp_amd.device import DeviceProblem
 
-        return DeviceProblem.to_slab(self, name, full)
+        return DeviceProblem.to_slab(self, name, full, with_next_node)
 
     def from_slab(self, name, part, full):
         from dots_socp_amd.device import DeviceProblem
@@ -122,10 +148,30 @@ class FakeDeviceProblem:
         return DeviceProblem.from_slab(self, name, part, full)
 
     def upload(self, name, arr):
-        raise NotImplementedError("the CPU stand-in starts from the zero state")
+        assert self.local, "the whole-state stand-in starts from the zero state"
+        arr = np.asarray(arr, dtype=np.float64)
+        rows = (self.nl + 1,) + self.shape(name)[1:]       # phi may bring the next slab's first node along (include/dots_socp_hip.h)
+        assert arr.shape == self.shape(name) or (name == "phi" and self.has_next and arr.shape == rows), (name, arr.shape, self.shape(name))
+        full = getattr(self.s, name)
+        if name == "phi":
+            full[...] = np.nan                             # (what the last solve left of the other slabs goes too)
+            if arr.shape == rows:
+                self.phi_hi = arr[self.nl].copy()
+        self.from_slab(name, arr, full)
+        self.kkt_halo_fresh = False
 
     def download(self, name):
+        if self.local and name == "z_mid":
+            assert not getattr(self, "zmid_stale", False), "download: z_mid was not materialised by the last step"
         return self.to_slab(name, getattr(self.s, name))
+
+    @property
+    def has_next(self):
+        return self.nl > 0 and self.node0 + self.nl <= self.T
+
+    @property
+    def has_prev(self):
+        return self.nl > 0 and self.node0 > 0
 
     # ---- exchange buffers
     def slab_elems(self, which):
@@ -171,6 +217,11 @@ class FakeDeviceProblem:
         s, b = self.s, self.buf
         n0, nl, ni, T = self.node0, self.nl, self.ni, self.T
         assert stage == 4 or stage == self.stage or (stage == 6 and self.stage == 1), "stages out of order"
+        assert stage != 4 or self.stage == 0, "the KKT halos are packed between iterations"
+        if self.local:
+            with np.errstate(all="ignore"):      # (the other slabs' entries are NaN and stay NaN)
+                self._local_stage(stage)
+            return self._stage_done(stage, wait)
         has_next, has_prev = n0 + nl <= T and nl > 0, n0 > 0 and nl > 0
         if stage == 0:
             if getattr(self, "palm", False):
@@ -234,6 +285,9 @@ class FakeDeviceProblem:
             if has_prev:
                 b["send_b"][:] = s.B[n0].reshape(-1)
             self.kkt_halo_fresh = True
+        return self._stage_done(stage, wait)
+
+    def _stage_done(self, stage, wait):
         if stage <= 3:
             self.stage = (stage + 1) & 3
         elif stage == 6:
@@ -242,8 +296,180 @@ class FakeDeviceProblem:
             self.stage = 2
         return _stats(alm_iterations=1 if stage == 3 else 0) if wait else None
 
+    # ---- LOCAL mode: the same stages from the rank's own slab and what it received (numpy on the oracle's arrays; NaN marks what is not here)
+    def _phi_and_gradients(self):
+        """dt_phi / dx_phi of the slab: phi at the next slab's first node is phi_hi (what this rank's last inverse transform, or an
+        upload, left)."""
+        s = self.s
+        phi = s.phi.copy()
+        if self.has_next:
+            phi[self.node0 + self.nl] = self.phi_hi
+        s.dt_phi = O.grad_time(s.h, phi)
+        s.dx_phi = O.grad_space(s.G, s.F, phi)
+
+    def _corner_sum(self, per_corner):
+        """(3, F) per-corner values -> (V,) sums over each vertex's corners."""
+        return self.v2c.T.dot(per_corner.reshape(-1))
+
+    def _local_stage(self, stage):
+        s, b = self.s, self.buf
+        n0, nl, ni, T, V = self.node0, self.nl, self.ni, self.T, self.V
+        has_next, has_prev, last = self.has_next, self.has_prev, n0 + nl - 1
+        if stage == 4:
+            self.kkt_halo_fresh = True
+        if nl == 0:
+            if stage in (1, 6):
+                b["b_send"][:] = 0.0
+            elif stage == 2:
+                b["x_send"][:V * self.pitch] = 0.0
+            return
+        if stage == 0:
+            if self.palm:      # step 0: the closed form with the gradients of the phi in memory
+                self._phi_and_gradients()
+                s.step_q_lambda(refresh_gradients=False)
+            if has_next:
+                b["send_x"][:] = self._X()[last]
+            if has_prev:
+                b["send_nsq"][:] = self._half_norms(n0 - 1)
+        if stage in (1, 6):
+            keep = (s.A[n0 - 1].copy(), s.lambda_c[n0 - 1].copy(), s.mu[n0 - 1].copy()) if has_prev else None
+            if has_prev:       # X of the previous slab's last interval, as received
+                s.A[n0 - 1] = 0.0 if self.defect == "recv_x_zero" else b["recv_x"]
+                s.lambda_c[n0 - 1] = s.mu[n0 - 1] = 0.0
+            self.rhs = s.laplacian_rhs()
+            if has_prev:
+                s.A[n0 - 1], s.lambda_c[n0 - 1], s.mu[n0 - 1] = keep
+            out = b["b_send"]
+            out[:] = 0.0
+            out.reshape(V, self.pitch)[:, :nl] = self.rhs[n0:n0 + nl].T
+        if stage in (1, 5):
+            w_fst = s.d - s.sz * s.A - s.beta_fst
+            w_mid = s.D[None, None, :, :, None] * (O.decouple(s.B, s.sz) - s.beta_mid)      # own: [t][0] of own intervals, [t][1] where node t + 1 is own
+            w_end = s.d + s.sz * s.A - s.beta_end
+            per_corner = (w_mid ** 2).sum(axis=4)                                             # (T, 2, 3, F)
+            lam = np.full((T, V), np.nan)
+            nrm = np.full((T, V), np.nan)
+            for t in range(n0, n0 + ni):
+                if t == last:      # ends at the next slab's first node: that half of the norm was received
+                    hi = np.zeros(V) if self.defect == "recv_nsq_zero" else np.array(b["recv_nsq"])
+                else:
+                    hi = self._corner_sum(per_corner[t, 1])
+                nrm[t] = np.sqrt(self._corner_sum(per_corner[t, 0]) + hi + w_end[t] ** 2)
+                lam[t] = np.clip(0.5 * (1.0 + w_fst[t] / nrm[t]), 0.0, 1.0)
+                corner = self.v2c.dot(lam[t]).reshape(3, s.F) / s.D
+                s.z_fst[t] = np.where(lam[t] >= 1.0, w_fst[t], lam[t] * nrm[t])
+                s.z_end[t] = lam[t] * w_end[t]
+                s.z_mid[t, 0] = corner[:, :, None] * w_mid[t, 0]
+                if t != last or not has_next:
+                    s.z_mid[t, 1] = corner[:, :, None] * w_mid[t, 1]
+            self.w_lo = w_mid[n0 - 1, 1].copy() if has_prev else None      # its multiplier arrives with the solution
+            if self.defect != "stale_tail":
+                b["x_send"][V * self.pitch:] = lam[last] if has_next else 0.0
+        elif stage == 2:
+            chunks = b["b_recv"].reshape(self.n_ranks, -1)
+            rhs = np.zeros((T + 1, V))
+            for t in range(T + 1):
+                p, j = divmod(t, self.stride)
+                rhs[t] = chunks[p].reshape(V, self.pitch)[:, j]
+            out = b["x_send"][:V * self.pitch].reshape(V, self.pitch)
+            out[:] = 0.0
+            for j, a in enumerate(range(n0, n0 + nl)):
+                hat = self.Q[:, a] @ rhs
+                if self.sigma[a] + self.params.eps == 0.0:
+                    hat = hat - hat.mean()
+                out[:, j] = self._solve_mode(a, hat)
+        elif stage == 3:
+            chunks = b["x_recv"].reshape(self.n_ranks, -1)
+            if has_prev:
+                corner = self.v2c.dot(chunks[self.rank - 1, V * self.pitch:]).reshape(3, s.F) / s.D
+                s.z_mid[n0 - 1, 1] = corner[:, :, None] * self.w_lo
+            g = chunks[:, :V * self.pitch].reshape(self.n_ranks, V, self.pitch)
+            xhat = np.zeros((T + 1, V))
+            for a in range(T + 1):
+                xhat[a] = g[a // self.stride, :, a % self.stride]
+            phi = self.Q @ xhat
+            s.phi[...] = np.nan
+            s.phi[n0:n0 + nl] = phi[n0:n0 + nl]
+            if has_next and self.defect != "stale_phi_hi":
+                self.phi_hi = phi[n0 + nl].copy()
+            self._phi_and_gradients()
+            s.step_q_lambda(refresh_gradients=False)
+            s.step_multipliers()
+            self.zmid_stale = bool(getattr(self, "skip_z_mid", False))
+            self.kkt_halo_fresh = False
+        elif stage == 4:
+            if has_next:
+                b["send_mu"][:] = s.mu[last]
+            if has_prev:
+                b["send_b"][:] = s.B[n0].reshape(-1)
+            self.kkt_halo_fresh = True
+
+    def _local_kkt_sums(self, conditions):
+        """The slab's share of every weighted sum of squares the seven residuals are made of (oracle: kkt_functions), 24 in all; the time
+        stencils of conditions 2, 4 and 5 reach into the neighbours through recv_mu (mu of the previous slab's last interval) and recv_b (B
+        of the next slab's first node)."""
+        s, b = self.s, self.buf
+        n0, nl, ni, T = self.node0, self.nl, self.ni, self.T
+        out = np.zeros(KKT_SUMS)
+        if nl == 0:
+            return out
+        missing = self.defect == "kkt_halos_missing"
+        I, N = slice(n0, n0 + ni), slice(n0, n0 + nl)
+        wv, wf, wd = s.mass_v[None, :], s.area_f[None, :, None], s.area_f[None, None, :, None]
+        wt = lambda a: float(np.sum(a[I] ** 2 * wv))                      # noqa: E731  interval arrays
+        wc = lambda a: float(np.sum(a[N] ** 2 * wv))                      # noqa: E731  node arrays on vertices
+        ws = lambda a: float(np.sum(a[N] ** 2 * wf))                      # noqa: E731  node arrays on triangles
+        lo = max(n0 - 1, 0)
+        wm = lambda a: float(np.sum(a[I, 0] ** 2 * wd)) + float(np.sum(a[lo:n0 + nl - 1, 1] ** 2 * wd))      # noqa: E731  corner arrays, by the node of an entry
+        mu, B = s.mu.copy(), s.B.copy()
+        if self.has_prev:
+            mu[n0 - 1] = 0.0 if missing else b["recv_mu"]
+        if self.has_next:
+            B[n0 + nl] = 0.0 if missing else np.array(b["recv_b"]).reshape(s.F, 3)
+        self._phi_and_gradients()
+        ps, ds, r, sz = s.prim_scale, s.dual_scale, s.r, s.sz
+        r_mu, r_e = s.dt_phi - s.A - s.lambda_c, s.dx_phi - s.B
+        out[0:7] = wt(s.dt_phi), ws(s.dx_phi), wt(s.A), ws(s.B), wt(s.lambda_c), wt(r_mu), ws(r_e)
+        if 1 in conditions:
+            out[7:10] = (wt(s.z_fst + sz * s.A - s.d), wt(s.z_end - sz * s.A - s.d), wm(sz * (s.z_mid - O.decouple(s.B, sz))))
+        aux = (r * s.h) * (s.bnd + O.div_time(s.h, np.nan_to_num(mu) * wv) + O.div_space(s.Dv, s.E * wf)) / wv
+        out[10] = wc(aux)
+        a1, a2 = sz * (s.beta_end - s.beta_fst), O.decouple_adjoint(s.beta_mid, sz)
+        out[11:17] = wt(s.mu), ws(s.E), wt(a1), ws(a2), wt(s.mu + a1), ws(s.E + a2)
+        rho = (ds * r) * mu
+        sq = np.sum(np.square(O.decouple(ps * B)), axis=(1, 4)).reshape(-1)
+        aux = ps * s.A + 0.25 * s.c2v_area_T.dot(sq).reshape(T, s.V) / wv
+        out[17:20] = wt(rho), wt(aux), wt(np.maximum(0.0, aux + rho) - rho)
+        m = (ds * r) * s.E
+        rho_f = s.v2f_third.dot(O.time_average_adjoint(np.nan_to_num(rho)).reshape(-1)).reshape(T + 1, s.F, 1)
+        aux = rho_f * (ps * s.B)
+        out[20:23] = ws(m), ws(aux), ws(aux - m)
+        out[23] = wt(s.congestion * rho - ps * s.lambda_c)
+        return out
+
+    def _local_kkt_combine(self, conditions, q):
+        s, T = self.s, self.T
+        sq = lambda *terms: float(np.sqrt(sum(terms)))                    # noqa: E731
+        nt, nn = 1.0 / T, 1.0 / (T + 1)                                   # nsq_time / nsq_center and nsq_space
+        ps, ds, r = s.prim_scale, s.dual_scale, s.r
+        pair = lambda num, const, rest, scale: [num / (const / sc + rest) for sc in (scale, 1.0)]      # noqa: E731
+        res = {
+            0: lambda: pair(sq(nt * q[5], nn * q[6]), s.c_prim_q, sq(nt * q[0], nn * q[1]) + sq(nt * q[2], nn * q[3]) + sq(nt * q[4]), ps),
+            1: lambda: pair(sq(nt * q[7], nt * q[8], nt * q[9]), s.c_prim_z, s.norm_d, ps),
+            2: lambda: pair(sq(nn * q[10]), s.c_dual_alpha, s.norm_boundary, ds),
+            3: lambda: pair(r * sq(nt * q[15], nn * q[16]), s.c_dual_beta, r * (sq(nt * q[11], nn * q[12]) + sq(nt * q[13], nn * q[14])), ds),
+            4: lambda: [sq(nt * q[19]) / (s.c_comp_rho + sq(nt * q[17]) + sq(nt * q[18])), None],
+            5: lambda: [sq(nn * q[22]) / (s.c_comp_m + sq(nn * q[20]) + sq(nn * q[21])), None],
+            6: lambda: [sq(nt * q[23]) / (s.c_comp_rho + sq(nt * q[17]) + sq(nt * (ps ** 2) * q[4])), None],
+        }
+        return {int(i): res[int(i)]() for i in conditions}
+
     # ---- scalars: every rank contributes (slot 0 counts the contributions), the residuals come from the whole state
     def kkt_sums(self, conditions):
+        if self.local:
+            assert self.kkt_halo_fresh or not set(conditions) & {2, 4, 5}, "KKT sums with time stencils before the halo exchange"
+            with np.errstate(all="ignore"):
+                return self._local_kkt_sums([int(i) for i in conditions])
         if set(conditions) & {2, 4, 5}:
             assert self.kkt_halo_fresh, "KKT sums with time stencils before the halo exchange"
             n0, nl = self.node0, self.nl
@@ -256,6 +482,8 @@ class FakeDeviceProblem:
         return out
 
     def kkt_combine(self, conditions, sums):
+        if self.local:
+            return self._local_kkt_combine(conditions, np.asarray(sums, dtype=np.float64))
         assert sums[0] == self.n_ranks, "the KKT sums were not added over all ranks"
         self.s.dt_phi = O.grad_time(self.s.h, self.s.phi)
         self.s.dx_phi = O.grad_space(self.s.G, self.s.F, self.s.phi)
@@ -264,9 +492,17 @@ class FakeDeviceProblem:
         return {int(i): list(fns[int(i)]()) for i in conditions}
 
     def objective_sums(self):
+        if self.local:      # the two ends of the cost, each from the rank that holds the node, and the slab's share of |lambda_c|^2
+            s, n0, nl = self.s, self.node0, self.nl
+            bnd = (s.dual_scale * s.r) * s.bnd
+            ends = [float(np.dot(s.prim_scale * s.phi[t], bnd[t])) for t in (0, self.T) if n0 <= t < n0 + nl]
+            return np.array([s.h * sum(ends), float(np.sum((s.prim_scale * s.lambda_c[n0:n0 + self.ni]) ** 2 * s.mass_v[None, :])) / self.T, 0.0])
         return np.array([1.0, 0.0, 0.0])
 
     def objective_combine(self, sums):
+        if self.local:
+            cong = self.s.congestion * self.s.prim_scale / self.s.dual_scale
+            return float(sums[0]), float(sums[0] - sums[1] / (2.0 * cong)) if cong > 1e-10 else float(sums[0])
         assert sums[0] == self.n_ranks
         return self.s.objective()
 
@@ -299,6 +535,7 @@ class FakeDeviceProblem:
             setattr(self.s, k, getattr(self.s, k) * factor)
 
     def adjust_penalty(self, factor):
+        """(r and the boundary term follow with set_params, as on the device)"""
         self.kkt_halo_fresh = False
         for k in ("mu", "E", "beta_fst", "beta_mid", "beta_end"):
             setattr(self.s, k, getattr(self.s, k) / factor)

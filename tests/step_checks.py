@@ -163,7 +163,13 @@ def _undivided(x, div):
     return None
 
 
-def edge_state(s, seed, zero_preimage=True, div=1.0):
+def default_cells(T):
+    """Where ``edge_state`` plants its special columns unless told otherwise: name -> interval (nan*: a zero pre-image, up* / lo*: exactly
+    on the upper / lower boundary of the cone)."""
+    return {"nan0": 0, "nan1": T - 1, "up0": 0, "up1": T - 1, "lo0": T // 2, "lo1": T - 1}
+
+
+def edge_state(s, seed, zero_preimage=True, div=1.0, cells=None):
     """Fill the twelve arrays of ``s`` by the recipe of random_state (test_hip_phases.py), then overwrite single (v, t) columns so that the
     oracle's own projection
       * takes each branch (lam clipped to 1, clipped to 0, in between) on about a third of all columns, chosen entry by entry;
@@ -173,6 +179,8 @@ def edge_state(s, seed, zero_preimage=True, div=1.0):
         interval (the lane without a second interval when T is odd).
     ``div`` != 1: the five dual arrays are left as they stand BEFORE a penalty division by ``div`` that is still to come
     (adjust_penalty(div) on ``s`` and on the device): the properties hold for the divided state.
+    ``cells``: name -> interval of the special columns (``default_cells`` when None; any number of names that start with nan, up or lo,
+    at most V - 1 of them): a time slab's tests put them next to the slab boundaries.
     Returns the masks of ``cone_masks`` for the state the iteration sees, plus ``planted``: the (t, v) of the special columns."""
     rng = np.random.default_rng(seed)
     for k in STATE:
@@ -182,10 +190,14 @@ def edge_state(s, seed, zero_preimage=True, div=1.0):
     T, V = s.T, s.V
     val = valence(s)
     v_odd = int(np.argmax(np.where(val % 2 == 1, val, -1)))          # the vertex of the largest odd valence stays an ordinary column
-    vs = [int(v) for v in rng.permutation(V) if v != v_odd][:6]
-    cells = {"nan0": (0, vs[0]), "nan1": (T - 1, vs[1]), "up0": (0, vs[2]), "up1": (T - 1, vs[3]), "lo0": (T // 2, vs[4]), "lo1": (T - 1, vs[5])}
+    where = default_cells(T) if cells is None else dict(cells)
+    assert len(where) <= V - 1 and all(k[:2] in ("na", "up", "lo") and 0 <= t < T for k, t in where.items()), where
+    vs = [int(v) for v in rng.permutation(V) if v != v_odd][:len(where)]
+    if cells is None:      # (the order the vertices were always dealt in)
+        where = {k: where[k] for k in ("nan0", "nan1", "up0", "up1", "lo0", "lo1")}
+    cells = {k: (int(t), v) for (k, t), v in zip(where.items(), vs)}
     if not zero_preimage:
-        del cells["nan0"], cells["nan1"]
+        cells = {k: tv for k, tv in cells.items() if not k.startswith("nan")}
     d_pre = _undivided(s.d, div)
     assert d_pre is not None, "no double divides back to const_d"
     vert = s.tri.T                                                  # (3, F): vertex of corner (k, f)
@@ -225,19 +237,39 @@ def edge_state(s, seed, zero_preimage=True, div=1.0):
     return masks
 
 
-def assert_edge_properties(masks, zero_preimage=True):
-    """Conditions on the INPUT (the oracle's own lam), not on the device."""
+def assert_edge_properties(masks, zero_preimage=True, cells=None, boundary=()):
+    """Conditions on the INPUT (the oracle's own lam), not on the device.  ``cells``: where the special columns were asked for, when not
+    at ``default_cells``; ``boundary``: intervals next to a slab boundary, where every branch must occur on at least one column."""
     n = masks["lam"].size
+    T = masks["lam"].shape[0]
+    cells = masks.get("cells") if cells is None else cells          # (what the side under test asked _upload for)
+    boundary = boundary or masks.get("boundary", ())
     for branch in ("one", "zero", "mid"):
         assert masks[branch].sum() >= 0.1 * n, (branch, int(masks[branch].sum()), n)
     assert (masks["on_upper"] & (masks["lam"] == 1.0)).sum() >= 2 and (masks["on_lower"] & (masks["lam"] == 0.0)).sum() >= 2
+    both = masks["nan"] & masks["zero_preimage"]
     if zero_preimage:
-        T = masks["lam"].shape[0]
-        both = masks["nan"] & masks["zero_preimage"]
-        assert both[0].any() and both[T - 1].any() and both.sum() >= 2
+        if cells is None:
+            assert both[0].any() and both[T - 1].any()
+        assert both.sum() >= 2
         assert np.array_equal(masks["nan"], masks["zero_preimage"])
     else:
         assert not masks["nan"].any()
+    # the planted columns are where they were asked for
+    want = default_cells(T) if cells is None else cells
+    want = {k: t for k, t in want.items() if zero_preimage or not k.startswith("nan")}
+    assert set(masks["planted"]) == set(want), (sorted(masks["planted"]), sorted(want))
+    for k, (t, v) in masks["planted"].items():
+        assert t == want[k], (k, t, want[k])
+        if k.startswith("nan"):
+            assert both[t, v], k
+        elif k.startswith("up"):
+            assert masks["on_upper"][t, v] and masks["lam"][t, v] == 1.0, k
+        else:
+            assert masks["on_lower"][t, v] and masks["lam"][t, v] == 0.0, k
+    for t in boundary:
+        for branch in ("one", "zero", "mid"):
+            assert masks[branch][t].any(), (branch, t)
 
 
 # ---- the comparison ---------------------------------------------------------------------------------------------------------
@@ -350,7 +382,10 @@ class OracleDevice:
 # Every scenario: (dev, s, T, seed, expect) -> None.  ``dev`` holds the parameters of ``s``; ``expect(dev, **bits)`` asserts on
 # dots_debug_counter 12 that the step just enqueued took the named launches (a no-op on the CPU).
 def _upload(dev, s, seed, **kw):
-    masks = edge_state(s, seed, **kw)
+    """``dev.cells`` / ``dev.boundary`` (a time slab's adapter has them): where the special columns go, and the intervals next to a slab
+    boundary that ``assert_edge_properties`` then looks at."""
+    masks = edge_state(s, seed, cells=getattr(dev, "cells", None), **kw)
+    masks["cells"], masks["boundary"] = getattr(dev, "cells", None), tuple(getattr(dev, "boundary", ()))
     before = snapshot(s)
     for k in STATE:
         dev.upload(k, before[k])

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN_DIR, load_oracle
+from slab_checks import SlabGroup
 
 pytestmark = pytest.mark.gpu
 O = load_oracle()
@@ -48,93 +49,6 @@ def run_ranks(n_ranks, fn):
         if e is not None:
             raise e
     return out
-
-
-class SlabGroup:
-    """n time-slab contexts on one GPU driven from ONE thread: the exchanges are plain tensor copies."""
-
-    def __init__(self, T, geom, n_ranks, **kw):
-        import torch
-
-        from dots_socp_amd.device import DeviceProblem
-
-        self.torch, self.n = torch, n_ranks
-        self.devs = [DeviceProblem(T, geom, lap_solver="modal_pcg", time_slab=(r, n_ranks), **kw) for r in range(n_ranks)]
-        self.bufs = []
-        for d in self.devs:
-            nv, nf, nb, nx = (d.slab_elems(k) for k in ("vertex_halo", "triangle_halo", "b_chunk", "x_chunk"))
-            z = lambda n: torch.zeros(n, dtype=torch.float64, device="cuda")       # noqa: E731
-            b = {"send_x": z(nv), "send_nsq": z(nv), "recv_x": z(nv), "recv_nsq": z(nv), "b_send": z(nb), "b_recv": z(nb * n_ranks),
-                 "x_send": z(nx), "x_recv": z(nx * n_ranks), "send_mu": z(nv), "send_b": z(nf), "recv_mu": z(nv), "recv_b": z(nf)}
-            d.slab_set_buffers(**{k: t.data_ptr() for k, t in b.items()})
-            self.bufs.append(b)
-        self.active = self.devs[0].active_ranks
-
-    def each(self, fn):
-        return [fn(d) for d in self.devs]
-
-    def upload(self, state):
-        for d in self.devs:
-            if d.nl:
-                for k, v in state.items():
-                    d.upload(k, d.to_slab(k, v))
-
-    def neighbours(self, fwd, bwd):
-        for d in self.devs:
-            d.sync()
-        for r in range(self.active):
-            if r > 0:
-                self.bufs[r][fwd[1]].copy_(self.bufs[r - 1][fwd[0]])
-            if r + 1 < self.active:
-                self.bufs[r][bwd[1]].copy_(self.bufs[r + 1][bwd[0]])
-        self.torch.cuda.synchronize()
-
-    def gather(self, send, recv):
-        for d in self.devs:
-            d.sync()
-        allv = self.torch.cat([b[send] for b in self.bufs])
-        for b in self.bufs:
-            b[recv].copy_(allv)
-        self.torch.cuda.synchronize()
-
-    def iterate(self, split=None):
-        """``split``: stage 1 in its two halves (6: right-hand side, 5: projection) around the all-gather of b; default: every other iteration."""
-        self.n_iterations = getattr(self, "n_iterations", 0) + 1
-        if split is None:
-            split = self.n_iterations % 2 == 0
-        self.each(lambda d: d.slab_stage(0))
-        self.neighbours(("send_x", "recv_x"), ("send_nsq", "recv_nsq"))
-        if split:
-            self.each(lambda d: d.slab_stage(6))
-            self.gather("b_send", "b_recv")
-            self.each(lambda d: d.slab_stage(5))
-            with pytest.raises(Exception, match="order"):
-                self.devs[0].slab_stage(5)
-        else:
-            self.each(lambda d: d.slab_stage(1))
-            self.gather("b_send", "b_recv")
-        self.each(lambda d: d.slab_stage(2))
-        self.gather("x_send", "x_recv")
-        self.each(lambda d: d.slab_stage(3))
-
-    def kkt(self, conditions):
-        self.each(lambda d: d.slab_stage(4))
-        self.neighbours(("send_mu", "recv_mu"), ("send_b", "recv_b"))
-        total = sum(d.kkt_sums(conditions) for d in self.devs)
-        return self.devs[0].kkt_combine(conditions, total)
-
-    def objective(self):
-        return self.devs[0].objective_combine(sum(d.objective_sums() for d in self.devs))
-
-    def download(self, name):
-        full = np.zeros(self.devs[0].full_shape(name))
-        for d in self.devs:
-            if d.nl:
-                d.from_slab(name, d.download(name), full)
-        return full
-
-    def close(self):
-        self.each(lambda d: d.close())
 
 
 @pytest.mark.parametrize("direct", [False, True])
