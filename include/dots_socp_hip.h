@@ -275,6 +275,11 @@ enum dots_phase {
     DOTS_PHASE_Q_LAMBDA_MULT = 2,    /* grad_time/grad_space + vanilla_solve_q_lambda :709-714,1044-1065 and the multiplier update :716-722 */
     DOTS_PHASE_Q_LAMBDA = 3          /* vanilla_solve_q_lambda alone (is_palm's step 0, :668-672): no multiplier moves */
 };
+/* A phase counts as a call that changes the state: a pending penalty division is carried out first, a z_mid left to be rebuilt is
+ * materialised, and the carried gathers, the fused KKT sums, a right-hand side ahead and an armed penalty decision are dropped --
+ * also by a phase that is then refused.  While z_mid is unspecified (DOTS_STEP_SKIP_Z_MID) DOTS_PHASE_Q_LAMBDA returns DOTS_ERR_STATE
+ * (the arrays are untouched); DOTS_PHASE_Q_LAMBDA_MULT is not refused and reads the unspecified z_mid: the caller runs
+ * DOTS_PHASE_SOC_PROJECTION (which makes z_mid valid again) or a step without the flag first. */
 int dots_run_phase(dots_ctx *ctx, int phase, dots_step_stats *stats);
 
 /* KKT residuals (closures of solver_socp.py:433-559 as wired at :589-643).  mask: bit i set =
@@ -331,7 +336,11 @@ int dots_scale_arrays(dots_ctx *ctx, uint32_t array_mask, double factor); /* x *
  * and of dt_phi / dx_phi when array_id is DOTS_PHI with part = 1 / 2.
  * On a time slab: the slab's SHARE of the norm (the sum over its own nodes / intervals / corner entries divided by the
  * GLOBAL averaging count); the caller adds the shares of all slabs (is_constant_scaling, solver_socp.py:324-365).  part = 1
- * reads phi at the next slab's first node as the last solve (dots_slab_stage 3) left it. */
+ * reads phi at the next slab's first node as the last solve (dots_slab_stage 3) left it.
+ * The state is left as it is, but the call is treated as one that changes it: a pending penalty division is carried out, and the
+ * carried gathers, the fused KKT sums, a right-hand side ahead and an armed penalty decision are dropped (dots_apply_operator does
+ * the same).  DOTS_Z_MID: a z_mid left to be rebuilt is materialised; DOTS_ERR_STATE while z_mid is
+ * unspecified (DOTS_STEP_SKIP_Z_MID). */
 int dots_norm_square(dots_ctx *ctx, int array_id, int part, double *out);
 
 /* ---- standalone operators (rows a4-a6 of SURVEY.md section 8a), host in / host out, for tests */

@@ -336,43 +336,213 @@ def compare_kkt(s, after, got, conditions=(0, 1, 2, 3, 6)):
 
 
 # ---- the CPU stand-in for the calls the scenarios make -------------------------------------------------------------------------
+def refused(status, what):
+    """The error a refused call raises, as ``_lib.check`` raises it."""
+    from dots_socp_amd import _lib
+
+    err = _lib.HipLibraryError(f"{what} failed with status {status}")
+    err.status = status
+    return err
+
+
+def trace_host(mu, E, triangles, n_vertices, tables, start_triangle, start_weights, neighbours, floor, span, action=False, mass=None,
+               max_crossings=16, slide=False):
+    """What ``DeviceProblem.flow_trace`` returns without a trajectory, from the host specifications (flow.flow_map_host and, with a
+    ``mass``, flow.push_forward_host on the last layer); ``tables``: ``(areas, hat)`` in the caller's triangle numbering."""
+    from dots_socp_amd import flow
+
+    areas, hat = tables
+    out = flow.flow_map_host(mu, E, triangles, hat, neighbours, start_triangle, start_weights, floor, max_crossings=max_crossings, trajectory=True,
+                             span=tuple(int(n) for n in span), action=action, slide=slide, areas=areas if slide else None)
+    if mass is not None:
+        k = flow.push_scales(mass, None, start_weights)
+        pushed = flow.push_forward_host(out, triangles, n_vertices, mass, None, k, "end")
+        out.update(mass_at=pushed["mass"], attr_at=None, dropped=pushed["dropped"], exponents=k)
+    return {k: v for k, v in out.items() if k not in ("triangles_at", "weights_at")}
+
+
 class OracleDevice:
-    """``DeviceProblem``'s calls used below, played by a second oracle (tests/fake_device.py plays time slabs only: no upload, no dots_step).
-    It knows nothing of kernels: counter 12 is not played."""
+    """``DeviceProblem``'s calls used below and by tests/sequence_checks.py, played by a second oracle (tests/fake_device.py plays time
+    slabs only: no upload, no dots_step).  It knows nothing of kernels: counter 12 is not played, and every hint of ``step_flags`` is
+    taken and ignored.  What the header documents about z_mid is played: after a step with ``skip_z_mid`` the calls that read it are
+    refused with DOTS_ERR_STATE until a step without the flag, an upload of it or the projection phase."""
 
-    def __init__(self, T, geom, congestion):
+    NORMS = {"phi": "nsq_center", "A": "nsq_time", "lambda_c": "nsq_time", "mu": "nsq_time", "z_fst": "nsq_time", "z_end": "nsq_time",
+             "beta_fst": "nsq_time", "beta_end": "nsq_time", "B": "nsq_space", "E": "nsq_space", "z_mid": "nsq_space_dec", "beta_mid": "nsq_space_dec"}
+    PARAMS = {"r": "r", "scale_z": "sz", "const_d": "d", "norm_d": "norm_d"}      # dots_params -> the oracle's attribute
+
+    def __init__(self, T, geom, congestion, strict=True):
         self.s = make_oracle(T, geom, congestion)
+        self.strict = strict
         self.palm = False
+        self.skip = False
+        self.stale = False      # z_mid unspecified (the last step ran with skip_z_mid)
+        self.geom = geom
+        self.norm_d0 = self.s.norm_d / 1.3      # (as a new context has it: make_oracle scaled it)
 
+    # ---- state transfer
     def upload(self, name, a):
         setattr(self.s, name, np.array(a, dtype=np.float64, copy=True))
+        if name == "z_mid":
+            self.stale = False
 
     def download(self, name):
+        if name == "z_mid" and self.stale:
+            raise refused(-5, "download z_mid")
         return getattr(self.s, name).copy()
 
     def download_all(self):
-        return snapshot(self.s)
+        return {k: self.download(k) for k in STATE}
 
+    # ---- parameters and scaling tools
     def set_params(self, **kw):
-        assert set(kw) == {"r"} and abs(kw["r"] - self.s.r) <= 1e-15 * self.s.r      # (adjust_penalty moved it already)
+        """The scenarios (``strict``) only ever bring the ``r`` that adjust_penalty moved already.  Otherwise the scalars are the
+        caller's, as on the device: ``r`` is the penalty the state is read with, and the boundary term follows it."""
+        s = self.s
+        if self.strict:
+            assert set(kw) == {"r"} and abs(kw["r"] - self.s.r) <= 1e-15 * self.s.r      # (adjust_penalty moved it already)
+            return
+        for k, v in kw.items():
+            if k == "r":
+                s.bnd *= s.r / v
+                s.r = float(v)
+            elif k in self.PARAMS:
+                setattr(s, self.PARAMS[k], float(v))
+            else:
+                assert k in ("congestion", "tau") or (k == "eps" and v == s.eps), k      # (eps is built into the oracle's solve)
+                setattr(s, k, float(v))
 
     def adjust_penalty(self, f):
         self.s.adjust_penalty(f)
 
-    def step_flags(self, palm=False, **_hints):
-        self.palm = palm
+    def scale_z(self, z_mul, beta_mul, scale_z_new):
+        """The arrays only, as the header states it (the caller brings scale_z, const_d and norm_d with set_params)."""
+        s = self.s
+        for k in ("z_fst", "z_mid", "z_end"):
+            setattr(s, k, getattr(s, k) * z_mul)
+        for k in ("beta_fst", "beta_mid", "beta_end"):
+            setattr(s, k, getattr(s, k) * beta_mul)
+        s.mu = scale_z_new * (s.beta_fst - s.beta_end)
+        s.E = -O.decouple_adjoint(s.beta_mid, scale_z_new)
+
+    def scale_arrays(self, names, factor):
+        for k in names:
+            setattr(self.s, k, getattr(self.s, k) * factor)
+
+    # ---- the iteration
+    def step_flags(self, palm=False, skip_z_mid=False, rhs_ahead=False, **_hints):
+        if palm and (skip_z_mid or rhs_ahead):
+            raise refused(-1, "dots_step_flags")
+        self.palm, self.skip = palm, skip_z_mid
 
     def step(self, n=1, wait=True):
         for _ in range(n):
             if self.palm:
+                if self.stale:
+                    raise refused(-5, "dots_step")
                 palm_step0(self.s)
             self.s.iterate()
+            self.stale = self.skip
 
+    def run_phase(self, phase):
+        s = self.s
+        if phase == "laplacian":
+            s.step_laplacian()
+        elif phase == "soc_projection":
+            s.step_soc_projection()
+            self.stale = False
+        elif phase == "q_lambda_mult":
+            s.step_q_lambda()
+            s.step_multipliers()
+        else:
+            assert phase == "q_lambda", phase
+            if self.stale:
+                raise refused(-5, "phase q_lambda")
+            palm_step0(s)
+
+    # ---- what is read
     def kkt(self, conditions):
         s = self.s
+        conditions = list(conditions)
+        if 1 in conditions and self.stale:
+            raise refused(-5, "dots_kkt")
+        s.dt_phi = O.grad_time(s.h, s.phi)      # (of the phi in memory, as the device forms them)
+        s.dx_phi = O.grad_space(s.G, s.F, s.phi)
         s.dec_B = O.decouple(s.B, s.sz)
         fns = s.kkt_functions()
         return {i: list(fns[i]()) for i in conditions}
+
+    def objective(self):
+        return self.s.objective()
+
+    def norm_square(self, name, part=0):
+        s = self.s
+        if name == "z_mid" and self.stale:
+            raise refused(-5, "dots_norm_square")
+        if name == "phi" and part == 1:
+            return s.nsq_time(O.grad_time(s.h, s.phi))
+        if name == "phi" and part == 2:
+            return s.nsq_space(O.grad_space(s.G, s.F, s.phi))
+        return getattr(s, self.NORMS[name])(getattr(s, name))
+
+    def apply_operator(self, op, x, scale=1.0):
+        s = self.s
+        x = np.asarray(x, dtype=np.float64)
+        return {"grad_time": lambda: O.grad_time(s.h, x), "div_time": lambda: O.div_time(s.h, x), "grad_space": lambda: O.grad_space(s.G, s.F, x),
+                "div_space": lambda: O.div_space(s.Dv, x), "decouple": lambda: O.decouple(x, scale), "decouple_adjoint": lambda: O.decouple_adjoint(x, scale),
+                "time_avg_adjoint": lambda: O.time_average_adjoint(x)}[op]()
+
+    def readout(self, factor=1.0, w_vertex=None, w_triangle=None, centred=False, mu0=None, mu1=None):
+        from dots_socp_amd import readout
+
+        mu, E = readout.read_out_host({"mu": self.s.mu, "E": self.s.E}, factor, w_vertex, w_triangle, centred, mu0, mu1)
+        return (mu, E) + tuple(readout.layer_sums_host(mu))
+
+    def sensitivity(self, factor_phi=1.0, factor_mu=1.0, mass_vertex=None):
+        from dots_socp_amd import sensitivity
+
+        s = self.s
+        phi0, phiT = sensitivity.potentials_host(s.phi, factor_phi)
+        mass = s.mass_v if mass_vertex is None else mass_vertex
+        return {"phi0": phi0, "phiT": phiT, "stress": sensitivity.stress_numpy(s.mu, s.phi, s.tri, mass, factor_mu, factor_phi)}
+
+    def flow_tables(self):
+        """``(areas, hat)`` of the host specification of the tracer: this stand-in's own (a device holds its plan's)."""
+        from dots_socp_amd.geometry import hat_gradients
+
+        return hat_gradients(self.geom["vertices"], self.geom["triangles"])
+
+    def flow_trace(self, start_triangle, start_weights, neighbours, floor, span, action=False, mass=None, max_crossings=16, slide=False):
+        s = self.s
+        return trace_host(s.mu, s.E, s.tri, s.V, self.flow_tables(), start_triangle, start_weights, neighbours, floor, span, action=action,
+                          mass=mass, max_crossings=max_crossings, slide=slide)
+
+    def flow_map(self, start_triangle, start_weights, neighbours, floor, max_crossings=16, slide=False):
+        return self.flow_trace(start_triangle, start_weights, neighbours, floor, (0, self.s.T), max_crossings=max_crossings, slide=slide)
+
+    def flow_push(self, start_triangle, start_weights, neighbours, floor, mass, max_crossings=16):
+        return self.flow_trace(start_triangle, start_weights, neighbours, floor, (0, self.s.T), mass=mass, max_crossings=max_crossings)
+
+    # ---- solve session
+    def restart(self, mu0, mu1, mode="cold", factors=None):
+        """dots_restart as the header states it: new end masses, the parameters of a new context (tau and eps kept), the state zeroed
+        (cold) or every array times the factor of its group (warm; refused while z_mid is unspecified)."""
+        s = self.s
+        if mode == "warm" and self.stale:
+            raise refused(-5, "dots_restart")
+        groups = (("phi", "A", "B", "lambda_c"), ("z_fst", "z_mid", "z_end"), ("mu", "E"), ("beta_fst", "beta_mid", "beta_end"))
+        for group, f in zip(groups, factors if mode == "warm" else (0.0,) * 4):
+            for k in group:
+                setattr(s, k, getattr(s, k) * f if mode == "warm" else np.zeros_like(getattr(s, k)))
+        s.r, s.sz, s.d, s.congestion, s.norm_d = 1.0, 1.0, 1.0, 0.0, self.norm_d0
+        s.bnd = np.zeros_like(s.bnd)
+        s.bnd[0] = -np.asarray(mu0, dtype=np.float64) / s.h
+        s.bnd[-1] = np.asarray(mu1, dtype=np.float64) / s.h
+        s.norm_boundary = s.h * float(np.sqrt(s.nsq_center(s.bnd / s.w_v)))
+        self.palm = self.skip = self.stale = False
+
+    def penalty_ahead(self, *policy):
+        pass      # (a hint)
 
     def close(self):
         pass
