@@ -72,6 +72,10 @@ CG_PATH_VT_SHIFT, CG_PATH_CAP_SHIFT, CG_PATH_G_SHIFT = 8, 20, 32
 # dots_debug_counter(14): windows of the last PCG solve (low byte) and whether the windowed transforms ran (dots_pcg_windows)
 PCG_WINDOWS_COUNTER = 14
 PCG_WINDOWS_TRANSFORMS = 256
+# dots_debug_counter(15): which of the launches around the direct solve last ran in their deep form (DOTS_RHS_DEEP; csrc/dots_dev.h)
+DEEP_PATH_COUNTER = 15
+DEEP_PATH = {"rhs": 1, "inverse": 2}
+DEEP_WGS_PER_CU = 16     # the rule: deep while a compute unit gets at most this many of the launch's workgroups
 
 
 _i32p = C.POINTER(C.c_int32)
@@ -232,6 +236,7 @@ KNOWN_ENV = {
     # read by the library (csrc/dots_api.hip: env_int)
     "DOTS_KKT_TWO", "DOTS_BM_NT", "DOTS_LAZY_DIV", "DOTS_ZMID_DEFER", "DOTS_MEM_BUDGET", "DOTS_FRONT_VEC2", "DOTS_FRONT_ROWS",
     "DOTS_FRONT_LEAFINV", "DOTS_FRONT_TUNE", "DOTS_FRONT_CFG", "DOTS_FRONT_NR", "DOTS_MAIL_TEST_DROP", "DOTS_MAIL_SPINS", "DOTS_ND_PCA_MIN", "DOTS_READOUT_PINNED",
+    "DOTS_RHS_DEEP",
     # read by the host side
     "DOTS_RHS_AHEAD", "DOTS_TIME_EVERY", "DOTS_FRONT_BANDS", "DOTS_FRONT_TOPINV", "DOTS_TORCH_FIRST", "DOTS_DIST_BACKEND", "DOTS_HIPCC_FLAGS",
 }

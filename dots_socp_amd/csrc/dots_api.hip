@@ -337,7 +337,7 @@ static int check(dots_ctx *ctx, bool reads_only = false, bool keeps_division = f
     if (!ctx) { set_error("null context"); return DOTS_ERR_ARGUMENT; }
     hipError_t e = hipSetDevice(ctx->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice", __FILE__, __LINE__);
-    if (!reads_only) ctx->rhs_ahead = ctx->rhs_ahead_armed = ctx->penalty_armed = ctx->carry_valid = ctx->kkt_fused_valid = ctx->step_path = 0;      // (the carried gathers / fused sums belong to the state steps 2+3 left)
+    if (!reads_only) ctx->rhs_ahead = ctx->rhs_ahead_armed = ctx->penalty_armed = ctx->carry_valid = ctx->kkt_fused_valid = ctx->step_path = ctx->deep_path = 0;      // (the carried gathers / fused sums belong to the state steps 2+3 left)
     if (!keeps_division) return flush_division(ctx);
     return 0;
 }
@@ -346,7 +346,7 @@ static int check(dots_ctx *ctx, bool reads_only = false, bool keeps_division = f
 static int palm_step0(Ctx *c) {
     if (!c->step_palm) return 0;
     if (c->zmid_stale) { set_error("step: DOTS_STEP_PALM needs z_mid of the previous iteration in memory"); return DOTS_ERR_STATE; }
-    c->carry_valid = c->kkt_fused_valid = c->step_path = 0;      // step 0 moves A, B and lambda_c
+    c->carry_valid = c->kkt_fused_valid = c->step_path = c->deep_path = 0;      // step 0 moves A, B and lambda_c
     return launch_q_lambda_only(c);
 }
 
@@ -587,12 +587,14 @@ int dots_create(const dots_problem_desc *desc, dots_ctx **out) {
     DOTS_HIP(hipSetDevice(desc->device));
     dots_ctx *c = new dots_ctx();
     c->device = desc->device;
+    if (hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, desc->device) != hipSuccess) c->n_cu = 0;      // (unknown: deep_launch_wins never)
     // measurement switches: every value is validated -- a typo must not silently select the default
     {
         bool ok = true;
         ok &= env_int("DOTS_KKT_TWO", 0, 1, &c->kkt_two);
         ok &= env_int("DOTS_ZMID_DEFER", 0, 1, &c->zmid_defer);    // 0: read-back iterations store z_mid as before
         ok &= env_int("DOTS_LAZY_DIV", 0, 1, &c->lazy_div);        // 0: a penalty update divides the dual arrays at once
+        ok &= env_int("DOTS_RHS_DEEP", 0, 1, &c->rhs_deep);        // 0: the right-hand side and inverse transform as they were, 1: their deep forms wherever the kernels exist (default: deep_launch_wins)
         ok &= env_int("DOTS_FRONT_VEC2", 0, 1, &c->sched.vec2);      // 0: one mode per lane in the sweeps everywhere
         ok &= env_int("DOTS_FRONT_ROWS", 0, 2, &c->front_rows);      // 0: the fold kernels everywhere, 1: row kernels where the rules say (default), 2: wherever they fit
         ok &= env_int("DOTS_FRONT_LEAFINV", 0, 2, &c->front_leafinv);
@@ -2228,6 +2230,7 @@ int64_t dots_debug_counter(dots_ctx *c, int which) {
         case 12: return c->step_path;                 // STEP_PATH_* bits of the last iteration's launches (dots_dev.h)
         case 13: return c->cg_path;                   // CG_PATH_* bits and tiling of the last PCG launches (dots_dev.h)
         case 14: return c->pcg_windows_ran;           // low byte: windows the last PCG solve ran (0: none yet, or unwindowed); bit 8: the windowed transforms ran
+        case 15: return c->deep_path;                 // DEEP_PATH_* of the last right-hand side and inverse transform (dots_dev.h)
         default: return -1;
     }
 }

@@ -162,7 +162,10 @@ enum {
     STEP_PATH_QL_DIV = 1 << 14,     // DIV: a pending penalty division applied
     STEP_PATH_QL_BMNT = 1 << 15,    // BMNT: beta_mid streamed around the caches
     STEP_PATH_QL_DEFER = 1 << 16,   // z_mid deferred (Ctx::zmid_deferred)
-    STEP_PATH_RHS_MASK = 0xff, STEP_PATH_QL_MASK = 0x1ff00
+    STEP_PATH_RHS_MASK = 0xff, STEP_PATH_QL_MASK = 0x1ff00,
+    // Ctx::deep_path, dots_debug_counter 15: which form of the launches around the direct solve ran last
+    DEEP_PATH_RHS = 1,              // k_rhs_modes2_deep took the right-hand side (and the projection riders)
+    DEEP_PATH_INVERSE = 2           // k_time_modes_tile_fast took the inverse time transform
 };
 struct MgDev {
     int nlev = 0;
@@ -560,6 +563,11 @@ struct Ctx {
     int step_carry = 0;           // dots_step_flags: steps 2+3 also store the next iteration's per-corner gathers (cn_sq, cn_g)
     int carry_valid = 0;          // ... and they belong to the current iterate (cleared by every call that changes state or parameters)
     int step_path = 0;            // STEP_PATH_* of the last iteration's launches (cleared with carry_valid; a right-hand side starts a new record)
+    // The launches around the direct solve at a pitch of 8, 16 or 32 have a form that keeps its loads in flight (k_rhs_modes2_deep: every
+    // carried row of a vertex at once; k_time_modes_tile_fast) at the price of registers: taken while a CU gets few of the launch's workgroups
+    int rhs_deep = -1;            // DOTS_RHS_DEEP: 0 never (the launches as they were), 1 wherever the kernels exist, -1 (default) the rule deep_launch_wins
+    int n_cu = 0;                 // compute units of the device
+    int deep_path = 0;            // DEEP_PATH_* of the last right-hand side and inverse transform (dots_debug_counter 15; cleared with step_path)
     int zmid_stale = 0;           // z_mid does not belong to the current iterate
     // z_mid on demand (one GPU, carry mapping): an iteration after which z_mid MAY be read (residuals read back, possibly the last one) does
     // not store it (18 T F values that are almost never read); instead steps 2+3 write the new beta_mid into z_mid's storage and the new B
@@ -655,6 +663,20 @@ inline bool time_modes_tile_ok(const Dev &d) { return d.TP <= BLOCK && d.VT >= 1
 inline bool time_modes_wide_ok(const Dev &d) { return (d.TP == 512 || d.TP == 1024) && d.Qpad != nullptr && d.QpadT != nullptr; }
 inline int time_modes_chunk(const Dev &d) { return (4096 / d.TP) < (d.T + 1) ? (4096 / d.TP) : (d.T + 1); }    // rows of Q per chunk
 inline size_t time_modes_tile_lds(const Dev &d) { return sizeof(double) * ((size_t)time_modes_chunk(d) * d.TP + (size_t)d.VT * (d.TP + 1)); }
+// pitch 8, 16 or 32 (all of Q is one chunk): the transforms' form with the pitch as a template argument (modes_from_tile_fast),
+// tile rows at an even pitch
+constexpr int fast_tile_pitch(int TPC) { return TPC + 2; }
+inline bool time_modes_fast_ok(const Dev &d) { return (d.TP == 8 || d.TP == 16 || d.TP == 32) && d.VT * d.TP == TILE_ELEMS; }
+inline size_t time_modes_fast_lds(const Dev &d) { return sizeof(double) * ((size_t)d.TP * d.TP + (size_t)d.VT * fast_tile_pitch(d.TP)); }
+// ... and whether a launch of `wgs` workgroups takes it (and the right-hand side its deep corner walk).  Side by side on tori at T = 31 the
+// deep right-hand side is shorter at every size measured, by 30 % at 2 workgroups per CU and still by 12 % at 16
+// (profiles/rhs_deep/threshold.txt); nothing was measured between 16 and torus100k's 24, where the launch moves its bytes at full
+// occupancy, so the rule ends where the measurement does
+constexpr int DEEP_WGS_PER_CU = 16;
+inline bool deep_launch_wins(const Ctx *c, int wgs) {
+    if (!time_modes_fast_ok(c->d) || c->rhs_deep == 0) return false;
+    return c->rhs_deep == 1 || wgs <= DEEP_WGS_PER_CU * c->n_cu;
+}
 // direct solver on one GPU, T + 1 < 64: the inverse time transform of phi rides in the cone-projection launch (the
 // projection reads neither phi nor anything the solve writes: steps 1-1 and 1-2 are a separable block)
 inline bool soc_takes_inverse(const Ctx *c);
@@ -844,6 +866,62 @@ __device__ __forceinline__ void modes_from_tile(const Dev &d, const double *Q, c
             const int vv = v0 + vl;
             if (vv >= 0 && vv < d.V) y[((int64_t)vv << out_shift) + (j - j0)] = acc[r];
         }
+    }
+}
+
+// The same product for a pitch known at compile time (TPC = 8, 16 or 32: all of Q is one chunk; whole tile, every output stored at
+// pitch TPC).  The loop above waits for one LDS read per term; here the loops are unrolled over a column of Q held in registers and
+// the rows of the tile read in 16-byte words, so that the reads go out well ahead of their use (as compiled: a dozen in flight before
+// the first counted wait): xs is [VT][TPC + 2] (an even pitch keeps the rows aligned; the rows one wavefront broadcasts still start in
+// different banks), Qs is [TPC][TPC], zero beyond T.
+// Output for output the arithmetic above: acc = acc + q * x for i = 0 .. T in that order, nothing added beyond T.
+// A thread's outputs g, g + G, ... (TILE_ELEMS / NB of them) are all rows of the tile: no bound on vl.
+// Q of the chunk as this thread stages it, loaded (addresses clamped, nothing branches) so that the caller's own loads join the
+// same round trip, and written to Qs once those are issued
+template <bool FWD, int NB, int TPC>
+struct QStage {
+    static constexpr int N = (TPC * TPC + NB - 1) / NB;
+    double v[N];
+    __device__ __forceinline__ void load(const Dev &d, const double *__restrict__ Q) {
+        const int n = d.T + 1;
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            const int e = threadIdx.x + k * NB, i = (e / TPC) & (TPC - 1), jj = e & (TPC - 1);
+            const int ic = min(i, n - 1), jc = min(jj, n - 1);
+            const double q = FWD ? Q[ic * n + jc] : Q[jc * n + ic];
+            v[k] = ((i < n) & (jj < n)) ? q : 0.0;      // (&, not &&: a branch here would put the load, and a wait for it, behind the branch)
+        }
+    }
+    __device__ __forceinline__ void store(double *Qs) const {
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            const int e = threadIdx.x + k * NB;
+            if (TPC * TPC % NB == 0 || e < TPC * TPC) Qs[e] = v[k];
+        }
+    }
+};
+template <int NB, int TPC>
+__device__ __forceinline__ void modes_from_tile_fast(const Dev &d, const double *xs, const double *Qs, int v0, double *__restrict__ y) {
+    constexpr int G = NB / TPC, R = TILE_ELEMS / NB, XP = fast_tile_pitch(TPC);
+    const int n = d.T + 1, j = threadIdx.x & (TPC - 1), g = threadIdx.x / TPC;
+    double q[TPC];
+#pragma unroll
+    for (int i = 0; i < TPC; ++i) q[i] = Qs[i * TPC + j];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int vl = g + r * G;
+        const dots_d2v *x2 = reinterpret_cast<const dots_d2v *>(xs + vl * XP);
+        double acc = 0.0;
+#pragma unroll
+        for (int i = 0; i < TPC; i += 2) {
+            const dots_d2v x = x2[i >> 1];
+            const double s0 = acc + q[i] * x.x;      // (T + 1 > TPC / 2 above a pitch of 8: the first half is always added)
+            acc = (TPC > 8 && i < TPC / 2) || i < n ? s0 : acc;
+            const double s1 = acc + q[i + 1] * x.y;
+            acc = (TPC > 8 && i + 1 < TPC / 2) || i + 1 < n ? s1 : acc;
+        }
+        const int vv = v0 + vl;
+        if (j < n && vv < d.V) y[((int64_t)vv << d.tp_shift) + j] = acc;
     }
 }
 

@@ -411,7 +411,7 @@ __global__ __launch_bounds__(RHS_NB) void k_rhs_modes(Dev d, double r, double ep
     const int tile = xcd_tile(blockIdx.x, d.n_vtiles);
     if (tile >= d.n_vtiles) return;
     const int v0 = tile * d.VT;
-    stage_q_chunk<true, RHS_NB>(d, d.Q, Qs, 0, min(IC, n));      // in flight while the corner walks run
+    stage_q_chunk<true, RHS_NB>(d, d.Q, Qs, 0, min(IC, n));      // ahead of the corner walks (as compiled not beside them: Q is waited for and written before the walks' loads are issued)
     for (int e = threadIdx.x; e < TILE_ELEMS; e += RHS_NB) {
         const int vl = e >> d.tp_shift, t = e & (TP - 1);
         xs[vl * TPp + t] = (v0 + vl < d.V && t < n) ? rhs_value(d, v0 + vl, t, r, eps) : 0.0;
@@ -503,7 +503,7 @@ __global__ __launch_bounds__(RHS_NB2) void k_rhs_modes2(Dev d, double r, double 
     const int tile = xcd_tile(blockIdx.x, d.n_vtiles);
     if (tile >= d.n_vtiles) return;
     const int v0 = tile * d.VT;
-    stage_q_chunk<true, RHS_NB2>(d, d.Q, Qs, 0, min(IC, n));      // in flight while the corner walks run
+    stage_q_chunk<true, RHS_NB2>(d, d.Q, Qs, 0, min(IC, n));      // ahead of the corner walks (as compiled not beside them: Q is waited for and written before the walks' loads are issued; k_rhs_modes2_deep overlaps them)
     for (int ee = e; ee < TILE_ELEMS; ee += 2 * RHS_NB2) {       // (one pass: TILE_ELEMS = 2 * RHS_NB2)
         const int vv = ee >> d.tp_shift, tt = ee & (TP - 1);
         const int v = v0 + vv;
@@ -513,6 +513,131 @@ __global__ __launch_bounds__(RHS_NB2) void k_rhs_modes2(Dev d, double r, double 
         xs[vv * TPp + tt + 1] = tt + 1 < n ? b[1] : 0.0;
     }
     modes_from_tile<true, RHS_NB2>(d, d.Q, xs, Qs, IC, v0, bhat, -1, 0, 1 << 30, true);
+}
+
+// ---- k_rhs_modes2<true> with its loads in flight (pitch 8, 16 or 32) ----------------------------------------------------------------
+// As compiled, the carried walks above wait for memory step after step: the vertex arrays, the values of interval t - 1 behind their
+// branch, cptr, the carried rows CARRY_BATCH at a time, mu0 / mu1 behind theirs -- and the workgroup's barrier waits for the slowest
+// lane.  Here a lane issues cptr together with everything that does not depend on it (addresses clamped instead of branches: every
+// load is unconditional, what it must not use is dropped by a select), then ALL carried rows of its vertex: DEEP_BATCH corners per
+// pass, rows clamped to the list, added in list order -- value for value the sums of rhs_value2<true> / soc_element2<true>.
+// The rows in flight cost registers (occupancy): launch_rhs takes this form while a CU gets few workgroups (deep_launch_wins).
+constexpr int DEEP_BATCH = 8;      // corners per pass (closed surfaces: valence ~ 6: one pass)
+__device__ __forceinline__ void rhs_value2_deep(const Dev &d, int v, int t, double r, double eps, double (&out)[2]) {
+    const int iv = idxV(d, v, t), ip = t > 0 ? iv - 1 : iv;
+    const int jc0 = d.cptr[v], jc1 = d.cptr[v + 1];
+    const double m = d.mass_v[v];
+    const D2 A = ld2(d.A + iv), L = ld2(d.lam + iv), P = ld2(d.phi + iv), M = ld2(d.mu + iv);
+    const double Ap = d.A[ip], Lp = d.lam[ip], Mp = d.mu[ip];
+    const double m0 = d.mu0[v], m1 = d.mu1[v];
+    const double *__restrict__ g = d.cn_g + t;
+    double ds[2] = {0.0, 0.0};
+    for (int j = jc0; j < jc1; j += DEEP_BATCH) {
+        D2 gj[DEEP_BATCH];
+#pragma unroll
+        for (int i = 0; i < DEEP_BATCH; ++i) gj[i] = ld2_nt(g + ((int64_t)min(j + i, jc1 - 1) << d.tp_shift));
+#pragma unroll
+        for (int i = 0; i < DEEP_BATCH; ++i) {
+            const double s0 = ds[0] + gj[i].v[0], s1 = ds[1] + gj[i].v[1];
+            ds[0] = j + i < jc1 ? s0 : ds[0];
+            ds[1] = j + i < jc1 ? s1 : ds[1];
+        }
+    }
+    const double ih = 1.0 / d.h;
+    const double xp = t > 0 ? (Ap + Lp - Mp) * m : 0.0;                                      // interval t - 1
+    const double x0 = t < d.ni ? (A.v[0] + L.v[0] - M.v[0]) * m : 0.0;                      // interval t
+    const double x1 = t + 1 < d.ni ? (A.v[1] + L.v[1] - M.v[1]) * m : 0.0;                  // interval t + 1
+    double rhs[2] = {(x0 - xp) * ih, (x1 - x0) * ih};
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        rhs[u] -= ds[u];
+        if (t + u == 0) rhs[u] += m0 / (r * d.h);
+        if (t + u == d.T) rhs[u] -= m1 / (r * d.h);
+        rhs[u] -= eps * m * P.v[u];
+        out[u] = -rhs[u];
+    }
+}
+__device__ __forceinline__ void soc_element2_deep(const Dev &d, int v, int t, double sz, double cd) {
+    const int iv = idxV(d, v, t);
+    const bool two = t + 1 < d.ni;                 // the second interval exists (T odd: not for the last pair)
+    const int j0 = d.cptr[v], j1 = d.cptr[v + 1];
+    const D2 A = ld2(d.A + iv), bf = ld2(d.bf + iv), be = ld2(d.be + iv);
+    double a0[2] = {0.0, 0.0}, a1[2] = {0.0, 0.0};
+    const double *__restrict__ q = d.cn_sq + t;
+    for (int j = j0; j < j1; j += DEEP_BATCH) {
+        D2 q0[DEEP_BATCH], q1[DEEP_BATCH];
+#pragma unroll
+        for (int i = 0; i < DEEP_BATCH; ++i) {
+            const int64_t row = (int64_t)(2 * min(j + i, j1 - 1)) << d.tp_shift;
+            q0[i] = ld2_nt(q + row);
+            q1[i] = ld2_nt(q + row + d.TP);
+        }
+#pragma unroll
+        for (int i = 0; i < DEEP_BATCH; ++i) {
+            const bool in = j + i < j1;
+            const double s00 = a0[0] + q0[i].v[0], s10 = a1[0] + q1[i].v[0], s01 = a0[1] + q0[i].v[1], s11 = a1[1] + q1[i].v[1];
+            a0[0] = in ? s00 : a0[0];
+            a1[0] = in ? s10 : a1[0];
+            a0[1] = in ? s01 : a0[1];
+            a1[1] = in ? s11 : a1[1];
+        }
+    }
+    D2 zf, ze, lm;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const double acc = a0[u] + a1[u];
+        const double a = A.v[u];
+        const double w_fst = cd - sz * a - bf.v[u];
+        const double w_end = cd + sz * a - be.v[u];
+        const double nrm = sqrt(acc + w_end * w_end);
+        double lam = 0.5 * (1.0 + w_fst / nrm);          // 0/0 -> NaN when the pre-image is 0, as in the reference (:1018)
+        if (lam == lam) lam = fmin(fmax(lam, 0.0), 1.0);  // np.clip keeps NaN; fmin/fmax would drop it
+        zf.v[u] = (lam >= 1.0) ? w_fst : lam * nrm;
+        ze.v[u] = lam * w_end;
+        lm.v[u] = lam;
+    }
+    if (two) {
+        st2(d.zf + iv, zf);
+        st2(d.ze + iv, ze);
+        st2(d.lamc + iv, lm);
+    } else {
+        d.zf[iv] = zf.v[0];
+        d.ze[iv] = ze.v[0];
+        d.lamc[iv] = lm.v[0];
+    }
+}
+
+// k_rhs_modes2<true> in that form: Q is loaded first and held in registers while the walk's loads are in flight, written to LDS with
+// the tile, and the transform is modes_from_tile_fast.  Same grid, same tiles, same riders.
+template <int TPC>
+__global__ __launch_bounds__(RHS_NB2) void k_rhs_modes2_deep(Dev d, double r, double eps, double *__restrict__ bhat, int n_rhs, double sz, double cd) {
+    const int e = 2 * threadIdx.x, vl = e / TPC, t = e & (TPC - 1);
+    if ((int)blockIdx.x >= n_rhs) {
+        const int st = xcd_tile(blockIdx.x - n_rhs, d.n_vtiles);
+        if (st >= d.n_vtiles) return;
+        const int v = st * d.VT + vl;
+        if (v < d.V && t < d.ni) soc_element2_deep(d, v, t, sz, cd);
+        return;
+    }
+    extern __shared__ dots_d2v tm_lds_deep[];
+    constexpr int XP = fast_tile_pitch(TPC);
+    double *Qs = reinterpret_cast<double *>(tm_lds_deep);      // [TPC][TPC]
+    double *xs = Qs + TPC * TPC;                                // [VT][XP]
+    const int n = d.T + 1;
+    const int tile = xcd_tile(blockIdx.x, d.n_vtiles);
+    if (tile >= d.n_vtiles) return;
+    const int v0 = tile * d.VT, v = v0 + vl;
+    QStage<true, RHS_NB2, TPC> qs;
+    qs.load(d, d.Q);
+    double b[2] = {0.0, 0.0};
+    if (v < d.V && t < n) rhs_value2_deep(d, v, t, r, eps, b);
+    qs.store(Qs);
+    dots_d2v bb;
+    bb.x = b[0];
+    bb.y = t + 1 < n ? b[1] : 0.0;
+    *reinterpret_cast<dots_d2v *>(xs + vl * XP + t) = bb;      // (t even, XP even: aligned)
+    __syncthreads();
+    modes_from_tile_fast<RHS_NB2, TPC>(d, xs, Qs, v0, bhat);
 }
 
 // T + 1 >= 64: 32 vertices per workgroup, the transform on the matrix cores.
@@ -551,6 +676,7 @@ int launch_rhs(Ctx *c, bool with_soc, double dv) {
     const double r = c->prm.r / c->prm.boundary_scale, eps = c->prm.eps, sz = c->prm.scale_z, cd = c->prm.const_d;
     const bool modes = rhs_writes_modes(c), carried = c->carry_valid != 0;
     int path = with_soc ? STEP_PATH_SOC_RIDER : 0;      // (dots_debug_counter 12)
+    int deep = 0;                                       // (dots_debug_counter 15)
     // the mode kernels' variants: 0 CARRIED (the corners' shares come from the last steps-2+3 launch), 1 DIV (a penalty update is pending: the dual
     // arrays are divided as they are read; rhs_divides told the caller this launch can), 2 neither
     auto modes2 = [&](int variant) {      // two time columns per lane (16-byte accesses)
@@ -568,6 +694,13 @@ int launch_rhs(Ctx *c, bool with_soc, double dv) {
                                d.cg_p0, n_rhs, n_tiles, sz, cd, V == 1 ? dv : 1.0);
         });
     }
+    else if (modes && carried && deep_launch_wins(c, with_soc ? 2 * g : g)) {      // the carried walks with every row in flight (pitch 8, 16, 32)
+        path |= STEP_PATH_RHS_MODES2 | STEP_PATH_RHS_CARRIED;
+        deep = DEEP_PATH_RHS;
+        with_constant<8, 16, 32>(d.TP, [&](auto TPC) {
+            hipLaunchKernelGGL((k_rhs_modes2_deep<TPC>), dim3(with_soc ? 2 * g : g), dim3(RHS_NB2), time_modes_fast_lds(d), c->stream, d, r, eps, d.cg_p0, g, sz, cd);
+        });
+    }
     else if (modes && d.TP >= 4 && carried) modes2(0);
     else if (dv != 0.0) modes2(1);
     else if (modes && d.TP >= 4) modes2(2);
@@ -582,6 +715,7 @@ int launch_rhs(Ctx *c, bool with_soc, double dv) {
     }
     DOTS_HIP(hipGetLastError());
     c->step_path = path;      // the first launch of an iteration: a new record
+    c->deep_path = deep;
     return 0;
 }
 
@@ -1492,6 +1626,7 @@ void preload_alm_kernels() {
     const void *fns[] = {
         (const void *)k_rhs<false>, (const void *)k_rhs<true>, (const void *)k_rhs_modes, (const void *)k_rhs_modes2<false>, (const void *)k_rhs_modes2<true>,
         (const void *)k_rhs_modes_mfma<false>, (const void *)k_rhs_modes_mfma<true>, (const void *)k_rhs_modes_mfma<false, true>, (const void *)k_rhs_modes2<false, true>,
+        (const void *)k_rhs_modes2_deep<8>, (const void *)k_rhs_modes2_deep<16>, (const void *)k_rhs_modes2_deep<32>,
         (const void *)k_soc_projection<true>, (const void *)k_soc_projection<false>, (const void *)k_soc_projection<true, true>,
         (const void *)k_q_lambda_mult_triangle<0>, (const void *)k_q_lambda_mult_triangle<1>, (const void *)k_q_lambda_mult_triangle<2>,
         (const void *)k_q_lambda_mult_triangle<0, true>,

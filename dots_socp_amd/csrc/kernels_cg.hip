@@ -445,12 +445,43 @@ __global__ __launch_bounds__(NB) void k_time_modes_tile(Dev d, const double *__r
     const int tile = xcd_tile(blockIdx.x, d.n_vtiles);
     if (tile >= d.n_vtiles) return;
     const int v0 = tile * d.VT;
-    stage_q_chunk<FWD, NB>(d, d.Q, Qs, 0, min(IC, n));      // together with the tile's loads: one round trip, one barrier
+    stage_q_chunk<FWD, NB>(d, d.Q, Qs, 0, min(IC, n));      // one barrier for Q and the tile (as compiled, two round trips: Q is waited for and written before the tile's loads are issued)
     for (int e = threadIdx.x; e < TILE_ELEMS; e += NB) {
         const int vl = e >> d.tp_shift, t = e & (TP - 1);
         xs[vl * TPp + t] = (v0 + vl < d.V && t < n) ? x[idxV(d, v0 + vl, t)] : 0.0;
     }
     modes_from_tile<FWD, NB>(d, d.Q, xs, Qs, IC, v0, y, -1, 0, 1 << 30, true);
+}
+
+// The same launch for a pitch of TPC = 8, 16 or 32 (modes_from_tile_fast in dots_dev.h): Q and the tile are loaded before either is
+// written to LDS -- one round trip -- and the transform waits once for its column of Q instead of once per term.
+template <bool FWD, int NB, int TPC>
+__global__ __launch_bounds__(NB) void k_time_modes_tile_fast(Dev d, const double *__restrict__ x, double *__restrict__ y) {
+    extern __shared__ dots_d2v tm_lds_fast[];
+    constexpr int R = TILE_ELEMS / NB, XP = fast_tile_pitch(TPC);
+    double *Qs = reinterpret_cast<double *>(tm_lds_fast);      // [TPC][TPC]
+    double *xs = Qs + TPC * TPC;                                // [VT][XP]
+    const int n = d.T + 1;
+    const int tile = xcd_tile(blockIdx.x, d.n_vtiles);
+    if (tile >= d.n_vtiles) return;
+    const int v0 = tile * d.VT;
+    QStage<FWD, NB, TPC> qs;
+    qs.load(d, d.Q);
+    double xv[R];
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+        const int e = threadIdx.x + k * NB, vl = e / TPC, t = e & (TPC - 1);
+        const double v = x[idxV(d, min(v0 + vl, d.V - 1), t)];
+        xv[k] = ((v0 + vl < d.V) & (t < n)) ? v : 0.0;
+    }
+    qs.store(Qs);
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+        const int e = threadIdx.x + k * NB;
+        xs[(e / TPC) * XP + (e & (TPC - 1))] = xv[k];
+    }
+    __syncthreads();
+    modes_from_tile_fast<NB, TPC>(d, xs, Qs, v0, y);
 }
 
 // The transform as a GEMM on the matrix cores (T + 1 >= 64; modes_from_tile_mfma in dots_dev.h): a workgroup
@@ -906,6 +937,7 @@ void modes_forward(Ctx *c, const double *in, double *out, bool direct) {
 void modes_inverse(Ctx *c, const double *x, double *phi, bool direct) {
     const Dev &d = c->d;
     const int gt = xcd_grid(d.n_vtiles);
+    c->deep_path &= ~DEEP_PATH_INVERSE;
     if (!direct && pcg_windowed(c))
         launch_time_modes_windows<false>(c, x, phi, 0);      // `x` in compact windows
     else if (direct && time_modes_wide_ok(d))
@@ -913,6 +945,12 @@ void modes_inverse(Ctx *c, const double *x, double *phi, bool direct) {
     else if (time_modes_mfma_ok(d))
         hipLaunchKernelGGL(k_time_modes_mfma, dim3((d.V + TM_ROWS - 1) / TM_ROWS), dim3(BLOCK), sizeof(double) * TM_ROWS * (d.TP + 1), c->stream, d, d.QpadT,
                            x, phi);
+    else if (time_modes_tile_ok(d) && direct && d.n_vtiles <= 512 && deep_launch_wins(c, gt)) {      // ... with its reads in flight (pitch 8, 16, 32)
+        with_constant<8, 16, 32>(d.TP, [&](auto TPC) {
+            hipLaunchKernelGGL((k_time_modes_tile_fast<false, 1024, TPC>), dim3(gt), dim3(1024), time_modes_fast_lds(d), c->stream, d, x, phi);
+        });
+        c->deep_path |= DEEP_PATH_INVERSE;
+    }
     else if (time_modes_tile_ok(d) && direct && d.n_vtiles <= 512)      // small meshes, behind the sweeps: latency-bound, one output per thread (knot: 9.5 -> 6 us; no gain at 10^5 vertices)
         hipLaunchKernelGGL((k_time_modes_tile<false, 1024>), dim3(gt), dim3(1024), time_modes_tile_lds(d), c->stream, d, x, phi, time_modes_chunk(d));
     else if (time_modes_tile_ok(d))
@@ -1173,6 +1211,8 @@ int cg_bench(Ctx *c, int which, int reps, double *ms, double *bytes) {
 void preload_transform_kernels() {      // (see preload_alm_kernels)
     const void *fns[] = {(const void *)k_time_modes_tile<true, BLOCK>, (const void *)k_time_modes_tile<false, BLOCK>,
                          (const void *)k_time_modes_tile<false, 1024>, (const void *)k_time_modes_mfma,
+                         (const void *)k_time_modes_tile_fast<false, 1024, 8>, (const void *)k_time_modes_tile_fast<false, 1024, 16>,
+                         (const void *)k_time_modes_tile_fast<false, 1024, 32>,
                          (const void *)k_time_modes<true>, (const void *)k_time_modes<false>,
                          (const void *)k_time_modes_wide<512>, (const void *)k_time_modes_wide<1024>,
                          (const void *)k_time_modes_windows<512, true>, (const void *)k_time_modes_windows<512, false>,

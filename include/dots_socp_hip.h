@@ -963,7 +963,11 @@ int dots_bench_kernel(dots_ctx *ctx, int which, int reps, double *ms_per_launch,
  * summed by k_collapse behind every producer, 4 workgroups of fewer than 1024 threads, 8 multigrid preconditioner; bits 8-19 the
  * vertices per tile, bits 20-31 the CSR entries of a tile staged in LDS (further entries are read from global memory), from bit 32 the
  * number of workgroups (0: no such launch yet; on a windowed context the last window's), 14 low byte: the windows the last PCG
- * solve on this context ran (0: none yet, or it ran unwindowed), bit 8: the windowed time transforms ran (dots_pcg_windows);
+ * solve on this context ran (0: none yet, or it ran unwindowed), bit 8: the windowed time transforms ran (dots_pcg_windows),
+ * 15 which of the launches around the direct solve last ran in the form that keeps its loads in flight (time pitch 8, 16 or 32; by
+ * rule where a compute unit gets few workgroups, DOTS_RHS_DEEP=0/1 forces either): 1 the right-hand side with the carried sums
+ * (k_rhs_modes2_deep; a right-hand side starts a new record), 2 the inverse time transform (k_time_modes_tile_fast); same results
+ * bit for bit either way;
  * -1 for an unknown counter */
 int64_t dots_debug_counter(dots_ctx *ctx, int which);
 
