@@ -7,10 +7,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
-struct dots_ctx : dots::Ctx {};
+struct dots_ctx : dots::Ctx { using Ctx::Ctx; };
 
 namespace dots {
 
@@ -65,32 +66,11 @@ int64_t array_count_device(const Dev &d, int id) {
     }
 }
 
+// the context's own arrays (Ctx::pool): zeroed, or the device copy of a host array
 template <typename T>
-static int dev_alloc(Ctx *c, T **out, int64_t count, bool zero = true) {
-    void *p = nullptr;
-    const size_t bytes = sizeof(T) * (size_t)std::max<int64_t>(count, 1);
-    DOTS_HIP(hipMalloc(&p, bytes));
-    if (zero) DOTS_HIP(hipMemsetAsync(p, 0, bytes, c->stream));
-    if (c->n_allocs >= (int)(sizeof(c->allocs) / sizeof(c->allocs[0]))) {
-        set_error("allocation table full");
-        return DOTS_ERR_STATE;
-    }
-    c->allocs[c->n_allocs++] = p;
-    c->bytes += (int64_t)bytes;
-    *out = (T *)p;
-    return 0;
-}
-
+static int dev_alloc(Ctx *c, T **out, int64_t count) { return c->pool.alloc(out, count, c->stream); }
 template <typename T>
-static int dev_upload(Ctx *c, const T **out, const T *host, int64_t count) {
-    T *p = nullptr;
-    int rc = dev_alloc(c, &p, count, false);
-    if (rc) return rc;
-    DOTS_HIP(hipMemcpyAsync(p, host, sizeof(T) * (size_t)count, hipMemcpyHostToDevice, c->stream));
-    DOTS_HIP(hipStreamSynchronize(c->stream));   // host buffers are borrowed for the call only
-    *out = p;
-    return 0;
-}
+static int dev_upload(Ctx *c, const T **out, const T *host, int64_t count) { return c->pool.upload(out, host, count, c->stream); }
 
 // norm_boundary = r h sqrt(norm_square_center(boundary / mass)) at r = 1 (solver_socp.py:296) from the end masses: the sum in vertex
 // order on the host (dots_create, dots_restart with host arrays: one loop, the same bits), the norm from a sum however it was formed
@@ -264,10 +244,10 @@ static int build(Ctx *c, const dots_problem_desc *p) {
     }
     c->stage_count = array_count_device(d, DOTS_Z_MID);
     if ((rc = dev_alloc(c, &c->stage, c->stage_count))) return rc;
-    DOTS_HIP(hipHostMalloc((void **)&c->h_pinned, sizeof(double) * CgScalOffsets::TOTAL, hipHostMallocDefault));
-    DOTS_HIP(hipHostMalloc((void **)&c->h_flags, sizeof(int) * FLAG_TOTAL, hipHostMallocDefault));
+    if ((rc = c->pinned.alloc(&c->h_pinned, CgScalOffsets::TOTAL, hipHostMallocDefault))) return rc;
+    if ((rc = c->pinned.alloc(&c->h_flags, FLAG_TOTAL, hipHostMallocDefault))) return rc;
     if ((rc = dev_alloc(c, &c->kkt_counter, 2))) return rc;
-    DOTS_HIP(hipHostMalloc((void **)&c->h_mail, sizeof(double) * (MAX_SUMS + 8), hipHostMallocCoherent | hipHostMallocMapped));
+    if ((rc = c->pinned.alloc(&c->h_mail, MAX_SUMS + 8, hipHostMallocCoherent | hipHostMallocMapped))) return rc;
     for (int i = 0; i < MAX_SUMS + 8; ++i) c->h_mail[i] = 0.0;
 
     // the PCG's view of the device data (see Ctx::dcg), and on a slab the global-time view of the transforms
@@ -533,30 +513,9 @@ static int run_iteration(Ctx *c, dots_step_stats *st) {
 }
 
 static void mg_release(Ctx *c) {
-    for (int i = 0; i < c->n_mg_allocs; ++i) (void)hipFree(c->mg_allocs[i]);
-    c->n_mg_allocs = 0;
+    c->mg_pool.release();
     c->mg = MgDev{};
     c->mg_path = 0;      // no cycle of this (or no) hierarchy yet
-}
-
-template <typename T>
-static int mg_upload(Ctx *c, const T **out, const T *host, int64_t count) {
-    void *p = nullptr;
-    const size_t bytes = sizeof(T) * (size_t)std::max<int64_t>(count, 1);
-    DOTS_HIP(hipMalloc(&p, bytes));
-    if (c->n_mg_allocs >= (int)(sizeof(c->mg_allocs) / sizeof(c->mg_allocs[0]))) {
-        (void)hipFree(p);
-        set_error("multigrid allocation table full");
-        return DOTS_ERR_STATE;
-    }
-    c->mg_allocs[c->n_mg_allocs++] = p;
-    // on the context's own (non-blocking) stream: never touch the legacy default stream, another
-    // context of this process may be capturing a graph
-    if (host) DOTS_HIP(hipMemcpyAsync(p, host, sizeof(T) * (size_t)count, hipMemcpyHostToDevice, c->stream));
-    else DOTS_HIP(hipMemsetAsync(p, 0, bytes, c->stream));
-    DOTS_HIP(hipStreamSynchronize(c->stream));
-    *out = (const T *)p;
-    return 0;
 }
 
 }  // namespace dots
@@ -585,8 +544,7 @@ int dots_create(const dots_problem_desc *desc, dots_ctx **out) {
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { set_error("no HIP device"); return DOTS_ERR_NO_DEVICE; }
     if (desc->device < 0 || desc->device >= ndev) { set_error("device ordinal out of range"); return DOTS_ERR_ARGUMENT; }
     DOTS_HIP(hipSetDevice(desc->device));
-    dots_ctx *c = new dots_ctx();
-    c->device = desc->device;
+    std::unique_ptr<dots_ctx> c(new dots_ctx(desc->device));      // (deleted on every failing exit)
     if (hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, desc->device) != hipSuccess) c->n_cu = 0;      // (unknown: deep_launch_wins never)
     // measurement switches: every value is validated -- a typo must not silently select the default
     {
@@ -606,45 +564,25 @@ int dots_create(const dots_problem_desc *desc, dots_ctx **out) {
         int spins = -1;
         ok &= env_int("DOTS_MAIL_SPINS", 0, 2000000000, &spins);
         if (spins >= 0) c->mail_spins = spins;
-        if (!ok) { delete c; return DOTS_ERR_ARGUMENT; }
+        if (!ok) return DOTS_ERR_ARGUMENT;
     }
-    hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { delete c; return hip_fail(e, "hipStreamCreate", __FILE__, __LINE__); }
+    DOTS_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     for (auto &ev : c->ev) (void)hipEventCreate(&ev);
-    int rc = build(c, desc);
-    if (rc) { dots_destroy(c); return rc; }
+    int rc = build(c.get(), desc);
+    if (rc) return rc;
     preload_alm_kernels();
     preload_kkt_kernels();
     preload_transform_kernels();
     preload_readout_kernels();
     preload_restart_kernels();
-    *out = c;
+    *out = c.release();
     return 0;
 }
 
 int dots_destroy(dots_ctx *c) {
     if (!c) return 0;
     (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    c->cg_graphs_release();
-    for (int i = 0; i < c->n_mg_allocs; ++i) (void)hipFree(c->mg_allocs[i]);
-    for (int i = 0; i < c->n_front_allocs; ++i) (void)hipFree(c->front_allocs[i]);
-    for (int i = 0; i < c->n_allocs; ++i) (void)hipFree(c->allocs[i]);
-    if (c->h_pinned) (void)hipHostFree(c->h_pinned);
-    if (c->h_flags) (void)hipHostFree(c->h_flags);
-    if (c->h_mail) (void)hipHostFree(c->h_mail);
-    if (c->h_ro_sums) (void)hipHostFree(c->h_ro_sums);
-    if (c->h_ring) (void)hipHostFree(c->h_ring);
-    for (auto &ev : c->ro_ev) if (ev) (void)hipEventDestroy(ev);
-    for (auto &ev : c->ring_ev) if (ev) (void)hipEventDestroy(ev);
-    if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
-    for (auto &ev : c->ev) if (ev) (void)hipEventDestroy(ev);
-    if (c->ev_batch) (void)hipEventDestroy(c->ev_batch);
-    c->front_store.reset();      // (a shared factor: freed with its last holder)
-    for (auto &slot : c->tev)
-        for (auto &ev : slot) if (ev) (void)hipEventDestroy(ev);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;      // (~Ctx lists what goes)
     return 0;
 }
 
@@ -692,7 +630,7 @@ int64_t dots_array_count(dots_ctx *c, int id) {
     if (!c || id < 0 || id >= DOTS_N_ARRAYS) return -1;
     return array_count_host(c->d, id);
 }
-int64_t dots_device_bytes(dots_ctx *c) { return c ? c->bytes : -1; }
+int64_t dots_device_bytes(dots_ctx *c) { return c ? c->pool.bytes() : -1; }
 
 int dots_upload(dots_ctx *c, int id, const double *host, int64_t count) {
     int rc = check(c);
@@ -704,7 +642,7 @@ int dots_upload(dots_ctx *c, int id, const double *host, int64_t count) {
     if (id < 0 || id >= DOTS_N_ARRAYS || !host || (count != array_count_host(c->d, id) && !with_hi)) { set_error("upload: bad array id or element count"); return DOTS_ERR_ARGUMENT; }
     if (id != DOTS_Z_MID && (rc = materialise_zmid(c))) return rc;
     DOTS_HIP(hipMemcpyAsync(c->stage, host, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, c->stream));
-    if ((rc = launch_to_device_layout(c, id, c->stage))) return rc;
+    if ((rc = launch_to_device_layout(c, id, c->arr(id), c->stage))) return rc;
     if (with_hi) {
         hipLaunchKernelGGL(k_slab_phi_hi, dim3((c->d.V + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, c->d, c->stage + (int64_t)c->d.nl * c->d.V, c->d.phi_hi);
         DOTS_HIP(hipGetLastError());
@@ -720,7 +658,7 @@ int dots_download(dots_ctx *c, int id, double *host, int64_t count) {
     if (id < 0 || id >= DOTS_N_ARRAYS || !host || count != array_count_host(c->d, id)) { set_error("download: bad array id or element count"); return DOTS_ERR_ARGUMENT; }
     if (id == DOTS_Z_MID && c->zmid_stale) { set_error("download: z_mid was not materialised by the last step (dots_step_flags)"); return DOTS_ERR_STATE; }
     if (id == DOTS_Z_MID && (rc = materialise_zmid(c))) return rc;
-    if ((rc = launch_from_device_layout(c, id, c->stage))) return rc;
+    if ((rc = launch_from_device_layout(c, id, c->arr(id), c->stage))) return rc;
     DOTS_HIP(hipMemcpyAsync(host, c->stage, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, c->stream));
     DOTS_HIP(hipStreamSynchronize(c->stream));
     c->d2h_bytes += (int64_t)sizeof(double) * count;
@@ -1070,34 +1008,23 @@ int dots_apply_operator(dots_ctx *c, int op, double scale, const double *in, int
         return DOTS_ERR_ARGUMENT;
     }
     // scratch: device-layout input and output live in two temporary buffers
+    DevicePool tmp(c->device);
     double *din = nullptr, *dout = nullptr;
-    const int64_t cin = array_count_device(c->d, in_id), cout = array_count_device(c->d, out_id);
-    DOTS_HIP(hipMalloc((void **)&din, sizeof(double) * (size_t)cin));
-    DOTS_HIP(hipMalloc((void **)&dout, sizeof(double) * (size_t)cout));
-    DOTS_HIP(hipMemsetAsync(dout, 0, sizeof(double) * (size_t)cout, c->stream));
-    DOTS_HIP(hipMemcpyAsync(c->stage, in, sizeof(double) * (size_t)n_in, hipMemcpyHostToDevice, c->stream));
-    // reuse the layout kernels by temporarily pointing the state slot at the scratch buffers
-    Ctx tmp = *c;
-    double **slot_in[12] = {&tmp.d.phi, &tmp.d.A, &tmp.d.B, &tmp.d.lam, &tmp.d.zf, &tmp.d.zm, &tmp.d.ze, &tmp.d.mu, &tmp.d.E, &tmp.d.bf, &tmp.d.bm, &tmp.d.be};
-    *slot_in[in_id] = din;
-    rc = launch_to_device_layout(&tmp, in_id, c->stage);
-    if (!rc) {
-        if (op == DOTS_OP_LAPLACIAN_APPLY) rc = cg_apply_operator(c, din, dout);
-        else rc = launch_operator(c, op, scale, din, dout);
-    }
-    if (!rc) {
-        Ctx tmp2 = *c;
-        double **slot_out[12] = {&tmp2.d.phi, &tmp2.d.A, &tmp2.d.B, &tmp2.d.lam, &tmp2.d.zf, &tmp2.d.zm, &tmp2.d.ze, &tmp2.d.mu, &tmp2.d.E, &tmp2.d.bf, &tmp2.d.bm, &tmp2.d.be};
-        *slot_out[out_id] = dout;
-        rc = launch_from_device_layout(&tmp2, out_id, c->stage);
-    }
-    hipError_t e1 = hipMemcpyAsync(out, c->stage, sizeof(double) * (size_t)n_out, hipMemcpyDeviceToHost, c->stream);
-    hipError_t e2 = hipStreamSynchronize(c->stream);
-    (void)hipFree(din);
-    (void)hipFree(dout);
+    auto enqueue = [&]() -> int {
+        int r;
+        if ((r = tmp.alloc(&din, array_count_device(c->d, in_id), c->stream, false))) return r;
+        if ((r = tmp.alloc(&dout, array_count_device(c->d, out_id), c->stream))) return r;
+        DOTS_HIP(hipMemcpyAsync(c->stage, in, sizeof(double) * (size_t)n_in, hipMemcpyHostToDevice, c->stream));
+        if ((r = launch_to_device_layout(c, in_id, din, c->stage))) return r;
+        if ((r = op == DOTS_OP_LAPLACIAN_APPLY ? cg_apply_operator(c, din, dout) : launch_operator(c, op, scale, din, dout))) return r;
+        if ((r = launch_from_device_layout(c, out_id, dout, c->stage))) return r;
+        DOTS_HIP(hipMemcpyAsync(out, c->stage, sizeof(double) * (size_t)n_out, hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    };
+    rc = enqueue();      // (every path out of the call waits for the stream before the buffers go)
+    const hipError_t es = hipStreamSynchronize(c->stream);
     if (rc) return rc;
-    DOTS_HIP(e1);
-    DOTS_HIP(e2);
+    DOTS_HIP(es);
     return 0;
 }
 
@@ -1134,7 +1061,7 @@ int dots_mg_setup(dots_ctx *c, const dots_mg_desc *m) {
             for (int j = 0; j < h.p_nnz; ++j)
                 if (h.p_col[j] < 0 || h.p_col[j] >= h.n_coarse || h.r_col[j] < 0 || h.r_col[j] >= h.n) { set_error("mg_setup: P/R index out of range"); mg_release(c); return DOTS_ERR_ARGUMENT; }
         }
-#define MUP(field, src, n) if ((rc = mg_upload(c, &L.field, src, (int64_t)(n)))) { mg_release(c); return rc; }
+#define MUP(field, src, n) if ((rc = c->mg_pool.upload(&L.field, src, (int64_t)(n), c->stream))) { mg_release(c); return rc; }
         if (l == 0) {
             L.rp = d.rowptr; L.col = d.col; L.vK = d.val; L.vM = nullptr; L.dK = d.kdiag; L.dM = d.mass_v;
         } else {
@@ -1155,7 +1082,7 @@ int dots_mg_setup(dots_ctx *c, const dots_mg_desc *m) {
             const double *tmp = nullptr;
             double **vecs[3] = {&L.b, &L.bt, &L.t};
             for (auto v : vecs) {
-                if ((rc = mg_upload<double>(c, &tmp, nullptr, nv))) { mg_release(c); return rc; }
+                if ((rc = c->mg_pool.upload<double>(&tmp, nullptr, nv, c->stream))) { mg_release(c); return rc; }
                 *v = const_cast<double *>(tmp);
             }
         }
@@ -1168,7 +1095,7 @@ int dots_mg_setup(dots_ctx *c, const dots_mg_desc *m) {
     std::vector<double> inv(block * n_win, 0.0);
     for (int64_t ij = 0; ij < (int64_t)nL * nL; ++ij)
         for (int k = 0; k < m->n_cols; ++k) inv[(size_t)(k / d.TP) * block + (size_t)ij * d.TP + k % d.TP] = m->coarse_inverse[(size_t)ij * m->n_cols + k];
-    if ((rc = mg_upload(c, &g.coarse_inv, inv.data(), (int64_t)inv.size()))) { mg_release(c); return rc; }
+    if ((rc = c->mg_pool.upload(&g.coarse_inv, inv, c->stream))) { mg_release(c); return rc; }
     // mg_release() reset c->mg; the level pointers were written into the local copy
     for (int l = 0; l < g.nlev; ++l) c->mg.lv[l] = g.lv[l];
     c->mg.nlev = g.nlev;
@@ -1201,12 +1128,9 @@ int dots_mg_apply(dots_ctx *c, const double *r, double *z, double *rz, const int
     for (int k = 0; k < FLAG_TOTAL; ++k) c->h_flags[k] = (k < g.cg_ncol && frozen && frozen[k]) ? 1 : 0;
     DOTS_HIP(hipMemcpyAsync(g.flags, c->h_flags, sizeof(int) * FLAG_TOTAL, hipMemcpyHostToDevice, c->stream));
     DOTS_HIP(hipMemcpyAsync(c->stage, r, sizeof(double) * (size_t)nh, hipMemcpyHostToDevice, c->stream));
-    Ctx tmp = *c;      // (the layout kernels write the array in the phi slot)
-    tmp.d.phi = g.cg_r;
-    if ((rc = launch_to_device_layout(&tmp, DOTS_PHI, c->stage))) return rc;
+    if ((rc = launch_to_device_layout(c, DOTS_PHI, g.cg_r, c->stage))) return rc;
     if ((rc = cg_mg_apply(c, rz))) return rc;
-    tmp.d.phi = g.cg_z;
-    if ((rc = launch_from_device_layout(&tmp, DOTS_PHI, c->stage))) return rc;
+    if ((rc = launch_from_device_layout(c, DOTS_PHI, g.cg_z, c->stage))) return rc;
     DOTS_HIP(hipMemcpyAsync(z, c->stage, sizeof(double) * (size_t)nh, hipMemcpyDeviceToHost, c->stream));
     DOTS_HIP(hipStreamSynchronize(c->stream));
     return 0;
@@ -1219,8 +1143,9 @@ static int front_carry_alloc(Ctx *c) {
     if (c->d.TP <= 128 && c->d.nl > 0) {      // (one GPU or a time slab with nodes)
         const int64_t rows = (int64_t)3 * c->d.F;
         const double *sq = nullptr, *g = nullptr, *lo = nullptr, *e = nullptr;
-        if ((rc = front_upload<double>(c, &sq, nullptr, (2 * rows) << c->d.tp_shift)) || (rc = front_upload<double>(c, &g, nullptr, rows << c->d.tp_shift)) ||
-            (rc = front_upload<double>(c, &lo, nullptr, rows)) || (c->shard_stride == 0 && (rc = front_upload<double>(c, &e, nullptr, rows << c->d.tp_shift)))) {
+        DevicePool &own = c->front_own;
+        if ((rc = own.upload<double>(&sq, nullptr, (2 * rows) << c->d.tp_shift, c->stream)) || (rc = own.upload<double>(&g, nullptr, rows << c->d.tp_shift, c->stream)) ||
+            (rc = own.upload<double>(&lo, nullptr, rows, c->stream)) || (c->shard_stride == 0 && (rc = own.upload<double>(&e, nullptr, rows << c->d.tp_shift, c->stream)))) {
             front_release(c);
             return rc;
         }
@@ -1286,27 +1211,14 @@ int dots_front_share(dots_ctx *c, dots_ctx *owner) {
     else if (c->dcg.TP != owner->dcg.TP || c->dcg.cg_ncol != owner->dcg.cg_ncol) snprintf(buf, sizeof buf, "mode pitch %d, the owner's %d", c->dcg.TP, owner->dcg.TP);
     else if (c->lap_hash != owner->lap_hash) snprintf(buf, sizeof buf, "another mesh or vertex numbering (the Laplacian or the vertex masses differ)");
     if (buf[0]) { set_error(std::string("front_share: the factor does not fit this context: ") + buf); return DOTS_ERR_ARGUMENT; }
-    // what every sharer reads moves into one store the first time the factor is shared; W and the carried gathers stay the owner's
-    if (!owner->front_store) {
-        auto st = std::make_shared<FrontStore>();
-        st->device = owner->device;
-        const void *own[5] = {owner->front.W, owner->d.cn_sq, owner->d.cn_g, owner->d.cn_lo, owner->d.cn_e};
-        int kept = 0;
-        for (int i = 0; i < owner->n_front_allocs; ++i) {
-            void *p = owner->front_allocs[i];
-            if (std::find(own, own + 5, p) != own + 5) owner->front_allocs[kept++] = p;
-            else st->allocs.push_back(p);
-        }
-        owner->n_front_allocs = kept;
-        owner->front_store = st;
-    }
+    // what every sharer reads is the owner's store; the update planes and the carried gathers are the sharer's own
     c->d.cn_sq = c->d.cn_g = c->d.cn_lo = c->d.cn_e = nullptr;
     front_release(c);
     c->front = owner->front;
     c->front.W = nullptr;
     c->sched = owner->sched;
     const double *w = nullptr;
-    if ((rc = front_upload<double>(c, &w, nullptr, owner->sched.w_rows << c->dcg.tp_shift))) { front_release(c); return rc; }
+    if ((rc = c->front_own.upload<double>(&w, nullptr, owner->sched.w_rows << c->dcg.tp_shift, c->stream))) { front_release(c); return rc; }
     c->front.W = const_cast<double *>(w);
     c->front_store = owner->front_store;
     c->use_front = 1;
@@ -1329,40 +1241,35 @@ int dots_laplacian_solve_many(dots_ctx *const *cs, int n, const double *const *h
     std::vector<const double *> bh((size_t)n);
     std::vector<double *> ys((size_t)n), xs((size_t)n);
     std::vector<Ctx *> cv(cs, cs + n);
-    auto release = [&]() {
-        for (int k = 0; k < n; ++k) (void)hipStreamSynchronize(cs[k]->stream);
-        for (auto p : din) if (p) (void)hipFree(p);
-        for (auto p : dout) if (p) (void)hipFree(p);
+    DevicePool tmp(cs[0]->device);
+    auto enqueue = [&]() -> int {
+        int r;
+        // per member, on its own stream: the input in device layout and its forward time transform (as step 1 forms them)
+        for (int k = 0; k < n; ++k) {
+            Ctx *c = cs[k];
+            if ((r = tmp.alloc(&din[k], cnt, c->stream, false)) || (r = tmp.alloc(&dout[k], cnt, c->stream, false))) return r;
+            DOTS_HIP(hipMemcpyAsync(c->stage, host_in[k], sizeof(double) * (size_t)nh, hipMemcpyHostToDevice, c->stream));
+            if ((r = launch_to_device_layout(c, DOTS_PHI, din[k], c->stage))) return r;
+            modes_forward(c, din[k], c->d.cg_p0, true);
+            bh[(size_t)k] = c->d.cg_p0;
+            ys[(size_t)k] = c->dcg.cg_z;
+            xs[(size_t)k] = c->dcg.cg_x;
+        }
+        // the sweeps of all members on the first member's stream, then each member's inverse transform on its own
+        for (int k = 1; k < n; ++k)
+            if ((r = batch_wait(cs[0], cs[k]))) return r;
+        if ((r = front_solve_many(cv.data(), n, bh.data(), ys.data(), xs.data()))) return r;
+        for (int k = 0; k < n; ++k) {
+            Ctx *c = cs[k];
+            if ((r = batch_wait(c, cs[0]))) return r;
+            modes_inverse(c, c->dcg.cg_x, dout[k], true);
+            if ((r = launch_from_device_layout(c, DOTS_PHI, dout[k], c->stage))) return r;
+            DOTS_HIP(hipMemcpyAsync(host_out[k], c->stage, sizeof(double) * (size_t)nh, hipMemcpyDeviceToHost, c->stream));
+        }
+        return 0;
     };
-    // per member, on its own stream: the input in device layout and its forward time transform (as step 1 forms them)
-    for (int k = 0; k < n && !rc; ++k) {
-        Ctx *c = cs[k];
-        hipError_t e = hipMalloc((void **)&din[k], sizeof(double) * (size_t)cnt);
-        if (e == hipSuccess) e = hipMalloc((void **)&dout[k], sizeof(double) * (size_t)cnt);
-        if (e == hipSuccess) e = hipMemcpyAsync(c->stage, host_in[k], sizeof(double) * (size_t)nh, hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) { rc = hip_fail(e, "laplacian_solve_many", __FILE__, __LINE__); break; }
-        Ctx tmp = *c;
-        tmp.d.phi = din[k];
-        if ((rc = launch_to_device_layout(&tmp, DOTS_PHI, c->stage))) break;
-        modes_forward(c, din[k], c->d.cg_p0, true);
-        bh[(size_t)k] = c->d.cg_p0;
-        ys[(size_t)k] = c->dcg.cg_z;
-        xs[(size_t)k] = c->dcg.cg_x;
-    }
-    // the sweeps of all members on the first member's stream, then each member's inverse transform on its own
-    for (int k = 1; k < n && !rc; ++k) rc = batch_wait(cs[0], cs[k]);
-    if (!rc) rc = front_solve_many(cv.data(), n, bh.data(), ys.data(), xs.data());
-    for (int k = 0; k < n && !rc; ++k) {
-        Ctx *c = cs[k];
-        if ((rc = batch_wait(c, cs[0]))) break;
-        modes_inverse(c, c->dcg.cg_x, dout[k], true);
-        Ctx tmp = *c;
-        tmp.d.phi = dout[k];
-        if ((rc = launch_from_device_layout(&tmp, DOTS_PHI, c->stage))) break;
-        hipError_t e = hipMemcpyAsync(host_out[k], c->stage, sizeof(double) * (size_t)nh, hipMemcpyDeviceToHost, c->stream);
-        if (e != hipSuccess) rc = hip_fail(e, "laplacian_solve_many", __FILE__, __LINE__);
-    }
-    release();
+    rc = enqueue();
+    for (int k = 0; k < n; ++k) (void)hipStreamSynchronize(cs[k]->stream);      // (every member's, before the buffers go)
     if (rc) return rc;
     DOTS_HIP(hipGetLastError());
     return 0;
@@ -1536,7 +1443,8 @@ static int carry_state(const std::string &who, const char *what, dots_ctx *dst, 
     size_t bytes = 0;
     for (int k = 0; k < 8; ++k) bytes += from[k] ? size[k] : 0;
     char *buf = nullptr, *at[8];
-    DOTS_HIP(hipMalloc((void **)&buf, bytes));
+    DevicePool tmp(dst->device);      // (freed behind the stream synchronisation below)
+    if ((rc = tmp.alloc(&buf, (int64_t)bytes, dst->stream, false))) return rc;
     hipError_t e = hipSuccess;
     bytes = 0;
     for (int k = 0; k < 8; ++k) {
@@ -1556,7 +1464,6 @@ static int carry_state(const std::string &who, const char *what, dots_ctx *dst, 
     if (!rc) rc = batch_wait(src, dst);      // (whatever the source does next -- its release included -- comes after the reads)
     e = hipStreamSynchronize(dst->stream);
     if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__);
-    (void)hipFree(buf);
     if (rc) return rc;
     dst->zmid_stale = dst->zmid_deferred = 0;      // (z_mid's storage holds the carried z_mid)
     dst->kkt_halo_fresh = 0;
@@ -1726,7 +1633,8 @@ static int readout_prepare(Ctx *c) {
     if (!c->copy_stream) DOTS_HIP(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
     for (auto &ev : c->ro_ev) if (!ev) DOTS_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     for (auto &ev : c->ring_ev) if (!ev) DOTS_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    if (!c->h_ro_sums) DOTS_HIP(hipHostMalloc((void **)&c->h_ro_sums, sizeof(double) * 2 * 1024, hipHostMallocCoherent | hipHostMallocMapped));
+    int rc = 0;
+    if (!c->h_ro_sums && (rc = c->pinned.alloc(&c->h_ro_sums, 2 * 1024, hipHostMallocCoherent | hipHostMallocMapped))) return rc;
     c->readout_ready = 1;
     return 0;
 }
@@ -1788,7 +1696,7 @@ int dots_readout(dots_ctx *c, const dots_readout_desc *desc) {
     if (rc) return rc;
     if ((rc = readout_prepare(c))) return rc;
     const size_t slot = (size_t)c->readout_pinned << 10;
-    if (slot && !c->h_ring) DOTS_HIP(hipHostMalloc((void **)&c->h_ring, 2 * slot, hipHostMallocDefault));
+    if (slot && !c->h_ring && (rc = c->pinned.alloc(&c->h_ring, 2 * slot, hipHostMallocDefault))) return rc;
     // the staging buffer: [E | mu | w_vertex | mu0 | mu1 | w_triangle | partial sums], every part on a 16-byte boundary
     const int layers = d.T + centred, n_wg = readout_workgroups(c);
     auto even = [](int64_t n) { return (n + 1) & ~(int64_t)1; };
@@ -1998,9 +1906,9 @@ static int flow_run(dots_ctx *c, const FlowRequest &req) {
     const size_t n_slides = req.slide ? (size_t)P : 0, n_steps = n_slides;      // (the kernel counts the steps in any case; copied on request)
     const size_t n_dbl = (size_t)P * 3 * 2 + n_wat + n_carry + n_acc + n_act, n_u64 = push ? n_acc + 1 : 0,
                  n_int = (size_t)P * 5 + (size_t)F * 3 + n_tat + n_slides + n_steps;
-    void *buf = nullptr;
-    hipError_t ea = hipMalloc(&buf, sizeof(double) * (n_dbl + n_u64) + sizeof(int) * n_int);
-    if (ea != hipSuccess) {
+    char *buf = nullptr;
+    DevicePool tmp(c->device);      // (every path out of the call below waits for the stream first)
+    if (tmp.alloc(&buf, (int64_t)(sizeof(double) * (n_dbl + n_u64) + sizeof(int) * n_int), c->stream, false)) {
         (void)hipGetLastError();
         set_error(w + (push ? "out of device memory for the particle tables and the accumulators" : "out of device memory for the particle tables"));
         return DOTS_ERR_MEMORY;
@@ -2070,7 +1978,6 @@ static int flow_run(dots_ctx *c, const FlowRequest &req) {
         if (desc->ms) *desc->ms = t;
         if (push && push->ms) *push->ms = t;
     }
-    (void)hipFree(buf);
     if (rc) return rc;
     size_t bytes = sizeof(double) * (n_wat + n_act) + sizeof(int) * (n_tat + n_slides + (req.slide && req.steps ? n_steps : 0)) + (desc->weights ? sizeof(double) * (size_t)P * 3 : 0);
     for (const int32_t *o : {desc->triangle, desc->status, desc->rested, desc->crossings}) bytes += o ? sizeof(int) * (size_t)P : 0;
@@ -2225,7 +2132,7 @@ int64_t dots_debug_counter(dots_ctx *c, int which) {
         case 7: return c->front_many_launches;        // sweep launches the last front_solve_many on this (first) context enqueued
         case 8: return c->front_many_split;           // ... of those, launches with fewer rhs than their chunk (many_launch halved: LDS or 1024-thread cap)
         case 9: return c->d2h_bytes;                  // bytes dots_download, dots_readout, dots_flow_map, dots_flow_push, dots_flow_trace, dots_flow_slide and dots_sensitivity have copied device -> host
-        case 10: return c->n_front_allocs;            // device allocations the installed factor holds (0 after front_release: also after a failed dots_front_setup)
+        case 10: return c->front_own.size() + (c->front_store ? c->front_store->size() : 0);      // device allocations of the factor this context holds, its own and the store it shares (0 after front_release: also after a failed dots_front_setup)
         case 11: return c->mg_path;                   // MG_PATH_* bits of the last V-cycle enqueued (dots_dev.h)
         case 12: return c->step_path;                 // STEP_PATH_* bits of the last iteration's launches (dots_dev.h)
         case 13: return c->cg_path;                   // CG_PATH_* bits and tiling of the last PCG launches (dots_dev.h)

@@ -351,8 +351,8 @@ int launch_q_lambda_only(Ctx *c);                       // the (q, lambda_c) clo
 int launch_adjust_penalty(Ctx *c, double factor);
 int launch_scale_z(Ctx *c, double z_mul, double beta_mul, double sz_new);
 int launch_scale_array(Ctx *c, int array_id, double factor);
-int launch_to_device_layout(Ctx *c, int array_id, const double *staged);
-int launch_from_device_layout(Ctx *c, int array_id, double *staged);
+int launch_to_device_layout(Ctx *c, int array_id, double *dev, const double *staged);      // dev: the array in device layout (the state's: c->arr(array_id))
+int launch_from_device_layout(Ctx *c, int array_id, const double *dev, double *staged);
 // The tables of a state carry (kernels_carry.hip), the caller's or their copies on the device.  mode: how a row is formed in space.
 enum { CARRY_NESTED = 0, CARRY_LOCATED = 1, CARRY_SAME = 2 };
 struct CarryTables {
@@ -486,15 +486,78 @@ struct FlowHost {
     std::vector<int> inv_f;      // caller triangle -> device triangle (empty: the same numbering)
 };
 
-// device allocations of a factor shared by several contexts (Ctx::front_store)
-struct FrontStore {
-    int device = 0;
-    std::vector<void *> allocs;
-    ~FrontStore() {
-        if (allocs.empty()) return;
-        (void)hipSetDevice(device);
-        for (void *p : allocs) (void)hipFree(p);
+// The one owner of device memory, and the one place that allocates and frees it: what a pool holds goes when it is released or
+// destroyed.  A call that fails leaves the pool holding what it held before, or the new allocation as well: never a pointer nobody frees.
+// Copies and fills go on the caller's stream (never the legacy default stream: another context of this process may be capturing a graph).
+struct DevicePool {
+    int device;
+    explicit DevicePool(int dev) : device(dev) {}
+    DevicePool(const DevicePool &) = delete;
+    DevicePool &operator=(const DevicePool &) = delete;
+    ~DevicePool() { release(); }
+    // `count` elements (room for at least one, 8 bytes), zeroed on `stream` unless told otherwise
+    template <typename T>
+    int alloc(T **out, int64_t count, hipStream_t stream, bool zero = true) {
+        const size_t n = sizeof(T) * (size_t)(count > 1 ? count : 1), bytes = n > 8 ? n : 8;
+        held.reserve(held.size() + 1);      // (nothing below can fail between the allocation and its record)
+        void *p = nullptr;
+        DOTS_HIP(hipMalloc(&p, bytes));
+        held.push_back(p);
+        held_bytes += (int64_t)bytes;
+        if (zero) DOTS_HIP(hipMemsetAsync(p, 0, bytes, stream));
+        *out = (T *)p;
+        return 0;
     }
+    // device copy of `count` elements of a host array (null: zeros); the stream is synchronised: host buffers are borrowed for the call only
+    template <typename T>
+    int upload(const T **out, const T *host, int64_t count, hipStream_t stream) {
+        T *p = nullptr;
+        const int rc = alloc(&p, count, stream, host == nullptr);
+        if (rc) return rc;
+        if (host) DOTS_HIP(hipMemcpyAsync(p, host, sizeof(T) * (size_t)count, hipMemcpyHostToDevice, stream));
+        DOTS_HIP(hipStreamSynchronize(stream));
+        *out = p;
+        return 0;
+    }
+    template <typename T>
+    int upload(const T **out, const std::vector<T> &v, hipStream_t stream) { return upload(out, v.data(), (int64_t)v.size(), stream); }
+    void release() {
+        if (held.empty()) return;
+        (void)hipSetDevice(device);
+        for (void *p : held) (void)hipFree(p);
+        held.clear();
+        held_bytes = 0;
+    }
+    int64_t size() const { return (int64_t)held.size(); }
+    int64_t bytes() const { return held_bytes; }
+
+private:
+    std::vector<void *> held;
+    int64_t held_bytes = 0;
+};
+
+// ... and of pinned host memory
+struct PinnedPool {
+    PinnedPool() = default;
+    PinnedPool(const PinnedPool &) = delete;
+    PinnedPool &operator=(const PinnedPool &) = delete;
+    ~PinnedPool() { release(); }
+    template <typename T>
+    int alloc(T **out, size_t count, unsigned flags) {
+        held.reserve(held.size() + 1);
+        void *p = nullptr;
+        DOTS_HIP(hipHostMalloc(&p, sizeof(T) * count, flags));
+        held.push_back(p);
+        *out = (T *)p;
+        return 0;
+    }
+    void release() {
+        for (void *p : held) (void)hipHostFree(p);
+        held.clear();
+    }
+
+private:
+    std::vector<void *> held;
 };
 
 struct Ctx {
@@ -515,10 +578,9 @@ struct Ctx {
     int slab_stage = 0;           // next stage dots_slab_stage expects
     int kkt_halo_fresh = 0;       // mu_lo / B_hi belong to the current iterate
     dots_params prm{};
-    int device = 0;
+    int device;
     int lap_solver = 0;
     int nnz = 0;
-    int64_t bytes = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev[12]{};
     double *stage = nullptr;      // device staging buffer (largest state array)
@@ -591,12 +653,11 @@ struct Ctx {
     int64_t penalty_ahead_started = 0, penalty_ahead_confirmed = 0;   // diagnostics (dots_debug_counter 2, 3)
     double ahead_div = 0.0;       // rhs_ahead == 2: the division the launch ahead applied as it read (steps 2+3 of the step that takes it must apply the same)
     double *zf_alt = nullptr, *ze_alt = nullptr, *lamc_alt = nullptr;   // [V][TP] each (one GPU): written ahead, swapped in by the step that takes them
-    void *front_allocs[48]{};
-    int n_front_allocs = 0;
-    // Factor shared by several contexts (dots_front_share): the allocations every sharer reads (factor, descriptors, maps, leaf records)
-    // move from front_allocs into one reference-counted store, freed with its last holder; W (update planes) and the carried gathers stay
-    // per context, in front_allocs
-    std::shared_ptr<FrontStore> front_store;
+    // The factor's device memory.  What every sharer of it reads (factor, node records, maps, leaf inverses and tables, work lists) is in one
+    // reference-counted store, created by front_setup and freed with its last holder (dots_front_share copies the pointer); W (update
+    // planes) and the carried gathers are this context's own
+    std::shared_ptr<DevicePool> front_store;
+    DevicePool front_own;
     int front_nr_max = 4;         // right-hand sides per launch of front_solve_many (DOTS_FRONT_NR: 2, 4 or 8)
     hipEvent_t ev_batch = nullptr;   // orders this context's stream against the others of a batched solve (created on first use)
     int front_cap_fault = 0;      // a multi-rhs launch was asked for more right-hand sides than its workgroup shape takes (front_solve_many reports it)
@@ -617,12 +678,11 @@ struct Ctx {
     // dots_restart: what the parameters of a new context are formed from besides mu0 / mu1
     std::shared_ptr<std::vector<double>> mass_host;      // [V] vertex masses, device numbering (norm_boundary's loop)
     double norm_d0 = 0.0;         // norm_d as dots_create leaves it
-    void *mg_allocs[160]{};
-    int n_mg_allocs = 0;
+    DevicePool mg_pool;           // the multigrid hierarchy (mg_release)
     // constants of the KKT normalisation (solver_socp.py:303-313)
     double c_prim_q = 0, c_prim_z = 0, c_dual_alpha = 0, c_dual_beta = 0, c_comp_rho = 0, c_comp_m = 0;
-    void *allocs[64]{};
-    int n_allocs = 0;
+    DevicePool pool;              // what dots_create allocated and what the read-out added on first use: dots_device_bytes
+    PinnedPool pinned;            // h_pinned, h_flags, h_mail, h_ro_sums, h_ring
     // hipGraph cache of the PCG iteration body: the context's own columns, and one per window of a windowed context
     CgCache cgc{};
     CgCache cgw[PCG_MAX_WINDOWS]{};
@@ -634,26 +694,28 @@ struct Ctx {
         double *t[12] = {d.phi, d.A, d.B, d.lam, d.zf, d.zm, d.ze, d.mu, d.E, d.bf, d.bm, d.be};
         return t[id];
     }
-};
-
-// device copy of a host array owned by the factor (released by front_release)
-template <typename T>
-inline int front_upload(Ctx *c, const T **out, const T *host, int64_t count) {
-    void *p = nullptr;
-    const size_t bytes = sizeof(T) * (size_t)(count > 1 ? count : 1);
-    DOTS_HIP(hipMalloc(&p, bytes));
-    if (c->n_front_allocs >= (int)(sizeof(c->front_allocs) / sizeof(c->front_allocs[0]))) {
-        (void)hipFree(p);
-        set_error("front allocation table full");
-        return DOTS_ERR_STATE;
+    explicit Ctx(int dev) : device(dev), front_own(dev), mg_pool(dev), pool(dev) {}
+    Ctx(const Ctx &) = delete;
+    Ctx &operator=(const Ctx &) = delete;
+    // the one list of what a context owns (the caller has set the device: dots_create, dots_destroy)
+    ~Ctx() {
+        if (stream) (void)hipStreamSynchronize(stream);
+        cg_graphs_release();
+        mg_pool.release();
+        front_own.release();
+        pool.release();
+        pinned.release();
+        for (auto &e : ro_ev) if (e) (void)hipEventDestroy(e);
+        for (auto &e : ring_ev) if (e) (void)hipEventDestroy(e);
+        if (copy_stream) { (void)hipStreamSynchronize(copy_stream); (void)hipStreamDestroy(copy_stream); }
+        for (auto &e : ev) if (e) (void)hipEventDestroy(e);
+        if (ev_batch) (void)hipEventDestroy(ev_batch);
+        front_store.reset();      // (a shared factor: freed with its last holder)
+        for (auto &slot : tev)
+            for (auto &e : slot) if (e) (void)hipEventDestroy(e);
+        if (stream) (void)hipStreamDestroy(stream);
     }
-    c->front_allocs[c->n_front_allocs++] = p;
-    if (host) DOTS_HIP(hipMemcpyAsync(p, host, sizeof(T) * (size_t)count, hipMemcpyHostToDevice, c->stream));
-    else DOTS_HIP(hipMemsetAsync(p, 0, bytes, c->stream));
-    DOTS_HIP(hipStreamSynchronize(c->stream));
-    *out = (const T *)p;
-    return 0;
-}
+};
 
 // The time-mode transforms stage a tile of rows and Q (in chunks of <= 32 KB) in LDS (k_time_modes_tile, k_rhs_modes)
 // T + 1 >= 64: the transforms are [V x (T+1)] x [(T+1) x (T+1)] fp64 GEMMs worth the matrix cores (k_time_modes_mfma)

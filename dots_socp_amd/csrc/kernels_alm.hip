@@ -1528,16 +1528,16 @@ __global__ __launch_bounds__(BLOCK) void k_convert(Dev d, int kind, double *dev,
     }
 }
 
-int launch_to_device_layout(Ctx *c, int id, const double *staged) {
+int launch_to_device_layout(Ctx *c, int id, double *dev, const double *staged) {
     const int64_t n = array_count_device(c->d, id);
-    hipLaunchKernelGGL(k_convert<true>, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, c->d, array_kind(id), c->arr(id),
+    hipLaunchKernelGGL(k_convert<true>, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, c->d, array_kind(id), dev,
                        const_cast<double *>(staged));
     DOTS_HIP(hipGetLastError());
     return 0;
 }
-int launch_from_device_layout(Ctx *c, int id, double *staged) {
+int launch_from_device_layout(Ctx *c, int id, const double *dev, double *staged) {
     const int64_t n = array_count_device(c->d, id);
-    hipLaunchKernelGGL(k_convert<false>, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, c->d, array_kind(id), c->arr(id), staged);
+    hipLaunchKernelGGL(k_convert<false>, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, c->d, array_kind(id), const_cast<double *>(dev), staged);
     DOTS_HIP(hipGetLastError());
     return 0;
 }

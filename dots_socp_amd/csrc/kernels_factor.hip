@@ -262,38 +262,22 @@ int front_factorize(Ctx *c, const dots_front_desc *h, FrontDev &f, const std::ve
     const Dev &d = c->dcg;
     const int sh = d.tp_shift;
     int rc = 0;
-    std::vector<void *> tmp;
-    auto release = [&]() { for (void *p : tmp) (void)hipFree(p); };
-    auto dalloc = [&](void **out, size_t bytes, const void *host) -> int {
-        void *p = nullptr;
-        DOTS_HIP(hipMalloc(&p, std::max<size_t>(bytes, 8)));
-        tmp.push_back(p);
-        if (host) DOTS_HIP(hipMemcpyAsync(p, host, bytes, hipMemcpyHostToDevice, c->stream));
-        else DOTS_HIP(hipMemsetAsync(p, 0, std::max<size_t>(bytes, 8), c->stream));
-        *out = p;
-        return 0;
-    };
+    DevicePool tmp(c->device);      // (freed behind the stream synchronisation that ends the function)
     int64_t srows = 0;
     for (const FrontNode &nd : nodes) srows = std::max(srows, nd.soff + (int64_t)nd.b * nd.b);
-    void *C = nullptr, *S = nullptr, *p0 = nullptr, *p1 = nullptr, *ln = nullptr, *gr = nullptr, *bp = nullptr;
-    if ((rc = dalloc(&C, sizeof(double) * ((size_t)h->n_entries << sh), nullptr)) ||
-        (rc = dalloc(&S, sizeof(double) * ((size_t)std::max<int64_t>(srows, 1) << sh), nullptr)) ||
-        (rc = dalloc(&p0, sizeof(int) * (size_t)h->n_front_rows, h->pull0)) || (rc = dalloc(&p1, sizeof(int) * (size_t)h->n_front_rows, h->pull1)) ||
-        (rc = dalloc(&ln, sizeof(int) * (size_t)h->n_nodes, h->level_nodes)) || (rc = dalloc(&gr, sizeof(int) * (size_t)d.TP, grounded_host)) ||
-        (rc = dalloc(&bp, sizeof(int), nullptr))) {
-        release();
-        return rc;
-    }
+    const int *ln = nullptr;
     FactArgs g{};
+    if ((rc = tmp.alloc(&g.C, (int64_t)h->n_entries << sh, c->stream)) || (rc = tmp.alloc(&g.S, std::max<int64_t>(srows, 1) << sh, c->stream)) ||
+        (rc = tmp.upload(&g.pull0, h->pull0, (int64_t)h->n_front_rows, c->stream)) || (rc = tmp.upload(&g.pull1, h->pull1, (int64_t)h->n_front_rows, c->stream)) ||
+        (rc = tmp.upload(&ln, h->level_nodes, (int64_t)h->n_nodes, c->stream)) || (rc = tmp.upload(&g.grounded, grounded_host, (int64_t)d.TP, c->stream)) ||
+        (rc = tmp.alloc(&g.bad_pivot, 1, c->stream))) return rc;
     g.sh = sh; g.TP = d.TP; g.ncol = d.cg_ncol;
     g.wsh = std::min(sh, 8);
     const unsigned nch = 1u << (sh - g.wsh);      // chunks of 256 modes (1 up to a pitch of 256)
     const int WP = 1 << g.wsh;
-    g.sigma = d.sigma; g.eps = c->prm.eps; g.grounded = (const int *)gr;
+    g.sigma = d.sigma; g.eps = c->prm.eps;
     g.rowptr = d.rowptr; g.col = d.col; g.val = d.val; g.mass = d.mass_v;
-    g.pull0 = (const int *)p0; g.pull1 = (const int *)p1;
-    g.C = (double *)C; g.T = T; g.S = (double *)S;
-    g.bad_pivot = (int *)bp;
+    g.T = T;
     // panel width: the diagonal block of the workgroup's modes must fit in LDS (w * w * WP doubles <= 64 KB)
     int w = 16;
     while ((size_t)w * w * WP * sizeof(double) > 65536 && w > 1) w /= 2;
@@ -310,7 +294,7 @@ int front_factorize(Ctx *c, const dots_front_desc *h, FrontDev &f, const std::ve
             max_m = std::max(max_m, nd.n + nd.b);
             max_e = std::max(max_e, (int64_t)(nd.n + nd.b) * nd.n + (int64_t)nd.b * nd.b);
         }
-        g.level_nodes = (const int *)ln + h->level_ptr[l];
+        g.level_nodes = ln + h->level_ptr[l];
         auto blocks = [&](int64_t items) { return (unsigned)std::min<int64_t>(std::max<int64_t>((items + Q - 1) / Q, 1), 4096); };
         hipLaunchKernelGGL(k_fact_assemble, dim3(blocks(max_e), cnt, nch), dim3(256), 0, c->stream, g, f);
         const int rows_per_wg = 8 * Q;
@@ -329,9 +313,8 @@ int front_factorize(Ctx *c, const dots_front_desc *h, FrontDev &f, const std::ve
         if (e != hipSuccess) rc = hip_fail(e, "factorisation launch", __FILE__, __LINE__);
     }
     int bad = 0;
-    hipError_t e = hipMemcpyAsync(&bad, bp, sizeof(int), hipMemcpyDeviceToHost, c->stream);
+    hipError_t e = hipMemcpyAsync(&bad, g.bad_pivot, sizeof(int), hipMemcpyDeviceToHost, c->stream);
     hipError_t e2 = hipStreamSynchronize(c->stream);
-    release();
     if (rc) return rc;
     DOTS_HIP(e);
     DOTS_HIP(e2);

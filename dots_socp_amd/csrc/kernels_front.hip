@@ -956,8 +956,7 @@ static void front_launch_bwd(Ctx *c, const FrontDev &f, const FrontWork *ptr, in
 }
 
 void front_release(Ctx *c) {
-    for (int i = 0; i < c->n_front_allocs; ++i) (void)hipFree(c->front_allocs[i]);
-    c->n_front_allocs = 0;
+    c->front_own.release();
     c->front_store.reset();      // (a shared factor: freed with its last holder)
     c->front = FrontDev{};
     c->use_front = 0;
@@ -1020,27 +1019,6 @@ struct ReleaseUnlessDone {
     Ctx *c;
     bool done = false;
     ~ReleaseUnlessDone() { if (!done) front_release(c); }
-};
-
-// Temporary device buffers of one phase, freed when it ends (every phase synchronises the stream before it returns)
-struct DevTemps {
-    hipStream_t stream;
-    std::vector<void *> held;
-    explicit DevTemps(hipStream_t s) : stream(s) {}
-    DevTemps(const DevTemps &) = delete;
-    DevTemps &operator=(const DevTemps &) = delete;
-    ~DevTemps() { for (void *p : held) (void)hipFree(p); }
-    // `bytes` of device memory (at least 8), filled from `host` where given
-    hipError_t get(void **out, size_t bytes, const void *host = nullptr) {
-        void *p = nullptr;
-        hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 8));
-        if (e != hipSuccess) return e;
-        held.push_back(p);
-        *out = p;
-        return host ? hipMemcpyAsync(p, host, bytes, hipMemcpyHostToDevice, stream) : hipSuccess;
-    }
-    template <typename T> hipError_t copy(const T **out, const T *host, size_t count) { return get((void **)out, sizeof(T) * count, host); }
-    template <typename T> hipError_t copy(const T **out, const std::vector<T> &v) { return copy(out, v.data(), v.size()); }
 };
 
 // the right-hand side a workgroup of the row kernel (k_front_fwd_rows) stages, `cols` columns, fits its LDS
@@ -1589,10 +1567,11 @@ void deal(std::vector<FrontWork> &list, size_t from, size_t n_nodes) {
 
 // ---- device: the original tree, the factor, the merged blocks -----------------------------------------------------------------
 int upload_tree(Ctx *c, const FrontPlan &P, FrontDev &f0) {      // the original tree as the factorisation sees it
+    DevicePool &store = *c->front_store;
     int rc;
-    if ((rc = front_upload(c, &f0.nodes, P.nodes.data(), (int64_t)P.nn))) return rc;
-    if (!P.identity0 && (rc = front_upload(c, &f0.vmap, P.vmap0.data(), (int64_t)c->dcg.V))) return rc;
-    return front_upload(c, &f0.bd_vertex, P.bd_vertex.data(), (int64_t)P.bd_vertex.size());
+    if ((rc = store.upload(&f0.nodes, P.nodes.data(), (int64_t)P.nn, c->stream))) return rc;
+    if (!P.identity0 && (rc = store.upload(&f0.vmap, P.vmap0.data(), (int64_t)c->dcg.V, c->stream))) return rc;
+    return store.upload(&f0.bd_vertex, P.bd_vertex, c->stream);
 }
 
 // Does it fit?  The factor (with the merged blocks) stays; the numeric factorisation needs a copy of the fronts and the
@@ -1630,7 +1609,7 @@ int check_memory(Ctx *c, const dots_front_desc *h, const FrontPlan &P) {
 int install_factor(Ctx *c, const dots_front_desc *h, const FrontPlan &P, FrontDev &f0, const double **F) {
     const Dev &d = c->dcg;
     int rc;
-    if ((rc = front_upload<double>(c, F, nullptr, (h->n_entries + P.merged_entries) << d.tp_shift))) return rc;
+    if ((rc = c->front_store->upload<double>(F, nullptr, (h->n_entries + P.merged_entries) << d.tp_shift, c->stream))) return rc;
     if (h->values) {
         hipError_t e = hipMemcpyAsync(const_cast<double *>(*F), h->values, sizeof(double) * ((size_t)h->n_entries << d.tp_shift), hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -1666,25 +1645,22 @@ int merge_bands(Ctx *c, const dots_front_desc *h, const FrontPlan &P, const doub
             launch_items.push_back(items);
         }
     }
-    DevTemps tmp(c->stream);
+    DevicePool tmp(c->device);      // (freed when the phase ends, behind its stream synchronisation)
     MergeArgs g{};
     g.sh = d.tp_shift; g.TP = d.TP; g.ncol = d.cg_ncol; g.wsh = front_args(d).wsh;
     g.F = const_cast<double *>(F);
     const int *dl = nullptr;
-    hipError_t e = tmp.copy(&g.mem, members);
-    if (e == hipSuccess) e = tmp.copy(&dl, order);
-    if (e == hipSuccess) e = tmp.copy(&g.pull0, h->pull0, (size_t)h->n_front_rows);
-    if (e == hipSuccess) e = tmp.copy(&g.pull1, h->pull1, (size_t)h->n_front_rows);
-    if (e == hipSuccess) e = tmp.get((void **)&g.scratch, sizeof(double) * ((size_t)std::max<int64_t>(P.scratch_entries, 1) << d.tp_shift));
-    if (e == hipSuccess) {
-        const int Q = 256 >> g.wsh;
-        for (size_t k = 0; k + 1 < launch_ptr.size(); ++k) {
-            g.list = dl + launch_ptr[k];
-            const unsigned bx = (unsigned)std::min<int64_t>(std::max<int64_t>((launch_items[k] + Q - 1) / Q, 1), 2048);
-            hipLaunchKernelGGL(k_merge_member, dim3(bx, (unsigned)(launch_ptr[k + 1] - launch_ptr[k]), front_chunks(d)), dim3(256), 0, c->stream, g);
-        }
-        e = hipGetLastError();
+    int rc;
+    if ((rc = tmp.upload(&g.mem, members, c->stream)) || (rc = tmp.upload(&dl, order, c->stream)) ||
+        (rc = tmp.upload(&g.pull0, h->pull0, (int64_t)h->n_front_rows, c->stream)) || (rc = tmp.upload(&g.pull1, h->pull1, (int64_t)h->n_front_rows, c->stream)) ||
+        (rc = tmp.alloc(&g.scratch, std::max<int64_t>(P.scratch_entries, 1) << d.tp_shift, c->stream, false))) return rc;
+    const int Q = 256 >> g.wsh;
+    for (size_t k = 0; k + 1 < launch_ptr.size(); ++k) {
+        g.list = dl + launch_ptr[k];
+        const unsigned bx = (unsigned)std::min<int64_t>(std::max<int64_t>((launch_items[k] + Q - 1) / Q, 1), 2048);
+        hipLaunchKernelGGL(k_merge_member, dim3(bx, (unsigned)(launch_ptr[k + 1] - launch_ptr[k]), front_chunks(d)), dim3(256), 0, c->stream, g);
     }
+    const hipError_t e = hipGetLastError();
     const hipError_t e2 = hipStreamSynchronize(c->stream);
     if (e != hipSuccess || e2 != hipSuccess) return hip_fail(e != hipSuccess ? e : e2, "merged bands", __FILE__, __LINE__);
     return 0;
@@ -1703,29 +1679,27 @@ int explicit_inverses(Ctx *c, const double *F, const std::vector<int64_t> &foff,
         biggest = std::max<int64_t>(biggest, (int64_t)nk * nk);
     }
     const bool in_place = out == nullptr;
-    DevTemps tmp(c->stream);
+    DevicePool tmp(c->device);      // (freed when the phase ends, behind its stream synchronisation)
     const int64_t *dfo = nullptr, *doo = nullptr;
     const int *dn = nullptr;
-    hipError_t e = in_place ? tmp.get((void **)&out, sizeof(double) * ((size_t)total << d.tp_shift)) : hipSuccess;
-    if (e == hipSuccess) e = tmp.copy(&dfo, foff);
-    if (e == hipSuccess) e = tmp.copy(&doo, ooff);
-    if (e == hipSuccess) e = tmp.copy(&dn, n);
-    if (e == hipSuccess) {
-        TopInvArgs g{};
-        g.sh = d.tp_shift; g.TP = d.TP; g.ncol = d.cg_ncol; g.wsh = front_args(d).wsh;
-        g.F = F; g.out = out;
-        g.packed = packed ? 1 : 0;
-        const int Q = 256 >> g.wsh;
-        const unsigned bx = (unsigned)std::min<int64_t>(std::max<int64_t>((biggest + Q - 1) / Q, 1), 4096);
-        for (size_t at = 0; at < n.size() && e == hipSuccess; at += 32768) {      // (grid.y is limited to 65535)
-            g.foff = dfo + at; g.ooff = doo + at; g.n = dn + at;
-            hipLaunchKernelGGL(k_top_inverse, dim3(bx, (unsigned)std::min<size_t>(n.size() - at, 32768), front_chunks(d)), dim3(256), 0, c->stream, g);
-            e = hipGetLastError();
-        }
-        for (size_t k = 0; k < n.size() && e == hipSuccess && in_place; ++k)
-            e = hipMemcpyAsync(const_cast<double *>(F) + (foff[k] << d.tp_shift), out + (ooff[k] << d.tp_shift),
-                               sizeof(double) * ((size_t)n[k] * n[k] << d.tp_shift), hipMemcpyDeviceToDevice, c->stream);
+    int rc;
+    if ((in_place && (rc = tmp.alloc(&out, total << d.tp_shift, c->stream, false))) || (rc = tmp.upload(&dfo, foff, c->stream)) ||
+        (rc = tmp.upload(&doo, ooff, c->stream)) || (rc = tmp.upload(&dn, n, c->stream))) return rc;
+    TopInvArgs g{};
+    g.sh = d.tp_shift; g.TP = d.TP; g.ncol = d.cg_ncol; g.wsh = front_args(d).wsh;
+    g.F = F; g.out = out;
+    g.packed = packed ? 1 : 0;
+    const int Q = 256 >> g.wsh;
+    const unsigned bx = (unsigned)std::min<int64_t>(std::max<int64_t>((biggest + Q - 1) / Q, 1), 4096);
+    hipError_t e = hipSuccess;
+    for (size_t at = 0; at < n.size() && e == hipSuccess; at += 32768) {      // (grid.y is limited to 65535)
+        g.foff = dfo + at; g.ooff = doo + at; g.n = dn + at;
+        hipLaunchKernelGGL(k_top_inverse, dim3(bx, (unsigned)std::min<size_t>(n.size() - at, 32768), front_chunks(d)), dim3(256), 0, c->stream, g);
+        e = hipGetLastError();
     }
+    for (size_t k = 0; k < n.size() && e == hipSuccess && in_place; ++k)
+        e = hipMemcpyAsync(const_cast<double *>(F) + (foff[k] << d.tp_shift), out + (ooff[k] << d.tp_shift),
+                           sizeof(double) * ((size_t)n[k] * n[k] << d.tp_shift), hipMemcpyDeviceToDevice, c->stream);
     const hipError_t e2 = hipStreamSynchronize(c->stream);
     if (e != hipSuccess || e2 != hipSuccess) return hip_fail(e != hipSuccess ? e : e2, what, __FILE__, __LINE__);
     return 0;
@@ -1749,10 +1723,10 @@ int invert_top_band(Ctx *c, const FrontPlan &P, const double *F) {
 int upload_sweep_maps(Ctx *c, const FrontPlan &P, FrontDev &f) {
     const Dev &d = c->dcg;
     int rc;
-    if (!P.identity && (rc = front_upload(c, &f.vmap, P.vmap.data(), (int64_t)d.V))) return rc;
-    if ((rc = front_upload(c, &f.cmap, P.cmap.data(), (int64_t)P.cmap.size()))) return rc;
-    const double *w = nullptr;
-    if ((rc = front_upload<double>(c, &w, nullptr, std::max<int64_t>(P.wrows, 1) << d.tp_shift))) return rc;
+    if (!P.identity && (rc = c->front_store->upload(&f.vmap, P.vmap.data(), (int64_t)d.V, c->stream))) return rc;
+    if ((rc = c->front_store->upload(&f.cmap, P.cmap, c->stream))) return rc;
+    const double *w = nullptr;      // (this context's own: a sharer has its own planes)
+    if ((rc = c->front_own.upload<double>(&w, nullptr, std::max<int64_t>(P.wrows, 1) << d.tp_shift, c->stream))) return rc;
     f.W = const_cast<double *>(w);
     c->sched.w_rows = std::max<int64_t>(P.wrows, 1);
     return 0;
@@ -1765,8 +1739,9 @@ int leaf_tables(Ctx *c, FrontDev &f, int64_t bd_rows) {
     const LeafSepRow *dst = nullptr;
     const int *dov = nullptr;
     int rc;
-    if ((rc = front_upload<LeafBdRow>(c, &dbt, nullptr, std::max<int64_t>(bd_rows, 1))) || (rc = front_upload<LeafSepRow>(c, &dst, nullptr, d.V)) ||
-        (rc = front_upload<int>(c, &dov, nullptr, 1))) return rc;
+    DevicePool &store = *c->front_store;
+    if ((rc = store.upload<LeafBdRow>(&dbt, nullptr, std::max<int64_t>(bd_rows, 1), c->stream)) || (rc = store.upload<LeafSepRow>(&dst, nullptr, d.V, c->stream)) ||
+        (rc = store.upload<int>(&dov, nullptr, 1, c->stream))) return rc;
     hipLaunchKernelGGL(k_leaf_tables, dim3(f.n_leaves), dim3(64), 0, c->stream, f, d.rowptr, d.col, d.val, const_cast<LeafBdRow *>(dbt),
                        const_cast<LeafSepRow *>(dst), const_cast<int *>(dov));
     int over = 0;
@@ -1810,7 +1785,7 @@ int install_leaves(Ctx *c, const dots_front_desc *h, FrontPlan &P, FrontDev &f) 
     const double *dS = nullptr;
     const LeafWork *dl = nullptr;
     int rc;
-    if ((rc = front_upload<double>(c, &dS, nullptr, total << d.tp_shift)) || (rc = front_upload(c, &dl, leaves.data(), (int64_t)leaves.size()))) return rc;
+    if ((rc = c->front_store->upload<double>(&dS, nullptr, total << d.tp_shift, c->stream)) || (rc = c->front_store->upload(&dl, leaves, c->stream))) return rc;
     if ((rc = explicit_inverses(c, f.F, foff, n, true, const_cast<double *>(dS), "leaf inverses"))) return rc;
     f.leafS = dS;
     f.leaf_desc = dl;
@@ -1860,11 +1835,10 @@ int apply_cfg(Ctx *c, const FrontPlan &P) {
 void tune_bands(Ctx *c, const dots_front_desc *h, const FrontPlan &P, const FrontDev &f) {
     const Dev &d = c->dcg;
     FrontBand *const band = c->sched.band;
-    DevTemps tmp(c->stream);
+    DevicePool tmp(c->device);      // (freed behind the stream synchronisation that ends the function)
     double *vec[3] = {nullptr, nullptr, nullptr};
-    const size_t vec_bytes = sizeof(double) * ((size_t)d.V << d.tp_shift);
     bool ok = true;
-    for (int i = 0; i < 3 && ok; ++i) ok = tmp.get((void **)&vec[i], vec_bytes) == hipSuccess && hipMemsetAsync(vec[i], 0, vec_bytes, c->stream) == hipSuccess;
+    for (int i = 0; i < 3 && ok; ++i) ok = tmp.alloc(&vec[i], (int64_t)d.V << d.tp_shift, c->stream) == 0;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     ok = ok && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
     // A factor larger than the Infinity Cache streams from HBM in the real solve; a launch repeated back to back would find its
@@ -1873,12 +1847,12 @@ void tune_bands(Ctx *c, const dots_front_desc *h, const FrontPlan &P, const Fron
     const bool cold = c->sched.bytes > 400.0e6;
     double *flushbuf = nullptr;
     const size_t flush_bytes = (size_t)512 << 20;
-    if (cold && ok) ok = tmp.get((void **)&flushbuf, flush_bytes) == hipSuccess && hipMemsetAsync(flushbuf, 0, flush_bytes, c->stream) == hipSuccess;
+    if (cold && ok) ok = tmp.alloc(&flushbuf, (int64_t)(flush_bytes / sizeof(double)), c->stream) == 0;
     // one work list on the device, timed: microseconds per launch, or a negative number where the list found no room
     auto time_us = [&](const std::vector<FrontWork> &list, auto &&launch) -> double {
-        DevTemps one(c->stream);      // (freed after the event wait below)
+        DevicePool one(c->device);      // (freed after the event wait below)
         const FrontWork *dl = nullptr;
-        if (one.copy(&dl, list) != hipSuccess) return -1.0;
+        if (one.upload(&dl, list, c->stream)) return -1.0;
         if (!cold) {
             const int reps = 20;
             for (int rep = -3; rep < reps; ++rep) {
@@ -1980,8 +1954,8 @@ int install_schedule(Ctx *c, const dots_front_desc *h, const FrontPlan &P, Front
         deal(bwd, (size_t)bd.bwd_first, n_nodes);
     }
     int rc;
-    if ((rc = front_upload(c, &f.fwd_desc, fwd.data(), (int64_t)std::max<size_t>(fwd.size(), 1)))) return rc;
-    if ((rc = front_upload(c, &f.bwd_desc, bwd.data(), (int64_t)std::max<size_t>(bwd.size(), 1)))) return rc;
+    if ((rc = c->front_store->upload(&f.fwd_desc, fwd.data(), (int64_t)std::max<size_t>(fwd.size(), 1), c->stream))) return rc;
+    if ((rc = c->front_store->upload(&f.bwd_desc, bwd.data(), (int64_t)std::max<size_t>(bwd.size(), 1), c->stream))) return rc;
     c->front = f;
     c->use_front = 1;
     c->sched.n_bands = P.nb;
@@ -1993,7 +1967,7 @@ int install_schedule(Ctx *c, const dots_front_desc *h, const FrontPlan &P, Front
 }  // namespace
 
 // The direct solver's setup: a host plan (FrontPlan) filled phase by phase, then the device work in a fixed order -- allocate, factorise,
-// merge, top inverse, W, leaf inverses, leaf tables, tuner, lists (dots_front_share picks through front_allocs by position).
+// merge, top inverse, W, leaf inverses, leaf tables, tuner, lists.  What a sharer of the factor reads goes into the store, W into front_own.
 int front_setup(Ctx *c, const dots_front_desc *h) {
     const Dev &d = c->dcg;
     FrontPlan P;
@@ -2002,6 +1976,7 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
     DOTS_HIP(hipStreamSynchronize(c->stream));
     front_release(c);
     ReleaseUnlessDone guard{c};      // every failing exit below releases what it installed
+    c->front_store = std::make_shared<DevicePool>(c->device);
     if ((rc = build_tree(d, h, P))) return rc;
     if ((rc = group_bands(d, h, P))) return rc;
     choose_shapes(c, h, P);

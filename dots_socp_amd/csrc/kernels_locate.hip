@@ -135,19 +135,10 @@ int refuse(const char *what) {
     return DOTS_ERR_ARGUMENT;
 }
 
-struct DeviceBuffers {      // freed on every way out of the entry point
-    std::vector<void *> all;
+struct LocateScope {      // the call's events and the caller's device ordinal, put back on every way out of the entry point
     hipEvent_t ev[2] = {nullptr, nullptr};
     int previous_device = -1;
-    template <typename T>
-    hipError_t get(T **p, size_t count, const T *host) {
-        hipError_t e = hipMalloc((void **)p, std::max<size_t>(count, 1) * sizeof(T));
-        if (e != hipSuccess) return e;
-        all.push_back(*p);
-        return host ? hipMemcpy(*p, host, count * sizeof(T), hipMemcpyHostToDevice) : hipSuccess;
-    }
-    ~DeviceBuffers() {
-        for (void *p : all) (void)hipFree(p);
+    ~LocateScope() {
         for (hipEvent_t e : ev)
             if (e) (void)hipEventDestroy(e);
         if (previous_device >= 0) (void)hipSetDevice(previous_device);
@@ -280,26 +271,27 @@ extern "C" int dots_mesh_locate(const dots_mesh_locate_desc *d, int device) {
         }
     }
 
-    DeviceBuffers dev;
+    LocateScope dev;
     int previous = -1;
     DOTS_HIP(hipGetDevice(&previous));
     DOTS_HIP(hipSetDevice(device));
     dev.previous_device = previous;
     int *d_order, *d_cell_of, *d_cell_ptr, *d_cell_tri, *d_tri, *d_corner = nullptr;
     double *d_points, *d_corners, *d_w, *d_d2, *d_cpoints = nullptr;
-    DOTS_HIP(dev.get(&d_order, (size_t)N, order.data()));
-    DOTS_HIP(dev.get(&d_cell_of, (size_t)N, cell_of.data()));
-    DOTS_HIP(dev.get(&d_cell_ptr, cell_ptr.size(), cell_ptr.data()));
-    DOTS_HIP(dev.get(&d_cell_tri, cell_tri.size(), cell_tri.data()));
-    DOTS_HIP(dev.get(&d_points, (size_t)N * 3, d->points));
-    DOTS_HIP(dev.get(&d_corners, corners.size(), corners.data()));
-    DOTS_HIP(dev.get(&d_tri, (size_t)N, (const int *)nullptr));
-    DOTS_HIP(dev.get(&d_w, (size_t)N * 3, (const double *)nullptr));
-    DOTS_HIP(dev.get(&d_d2, (size_t)N, (const double *)nullptr));
-    if (d->corner) {
-        DOTS_HIP(dev.get(&d_cpoints, (size_t)N * 9, d->corner_points));
-        DOTS_HIP(dev.get(&d_corner, (size_t)N * 3, (const int *)nullptr));
-    }
+    DevicePool mem(device);      // (after `dev`: freed before the caller's device ordinal is put back)
+    auto get = [&](auto **p, size_t count, const auto *host) -> int {      // not zeroed; filled from `host` where given, with a synchronous copy
+        const int r = mem.alloc(p, (int64_t)count, nullptr, false);
+        if (r) return r;
+        if (host) DOTS_HIP(hipMemcpy(*p, host, count * sizeof(**p), hipMemcpyHostToDevice));
+        return 0;
+    };
+    int rc;
+    if ((rc = get(&d_order, (size_t)N, order.data())) || (rc = get(&d_cell_of, (size_t)N, cell_of.data())) ||
+        (rc = get(&d_cell_ptr, cell_ptr.size(), cell_ptr.data())) || (rc = get(&d_cell_tri, cell_tri.size(), cell_tri.data())) ||
+        (rc = get(&d_points, (size_t)N * 3, d->points)) || (rc = get(&d_corners, corners.size(), corners.data())) ||
+        (rc = get(&d_tri, (size_t)N, (const int *)nullptr)) || (rc = get(&d_w, (size_t)N * 3, (const double *)nullptr)) ||
+        (rc = get(&d_d2, (size_t)N, (const double *)nullptr))) return rc;
+    if (d->corner && ((rc = get(&d_cpoints, (size_t)N * 9, d->corner_points)) || (rc = get(&d_corner, (size_t)N * 3, (const int *)nullptr)))) return rc;
     DOTS_HIP(hipEventCreate(&dev.ev[0]));
     DOTS_HIP(hipEventCreate(&dev.ev[1]));
     DOTS_HIP(hipEventRecord(dev.ev[0], nullptr));

@@ -946,7 +946,8 @@ int dots_bench_kernel(dots_ctx *ctx, int which, int reps, double *ms_per_launch,
  * launches that took fewer right-hand sides than their chunk of DOTS_FRONT_NR problems held because NR regions of LDS would not fit or
  * a workgroup of 1024 threads takes fewer (the launch was split), 9 bytes this context has copied device -> host through dots_download,
  * dots_readout, dots_flow_map, dots_flow_push, dots_flow_trace and dots_flow_slide since it was created (the layer sums of dots_readout are written by the device itself and not copied), 10 device
- * allocations this context holds for its factor (0 without one, also after a dots_front_setup that failed), 11 the launches the
+ * allocations this context holds for its factor: its own (update planes, carried gathers) plus those of the store it holds with
+ * the factor's other sharers (0 without a factor, also after a dots_front_setup that failed), 11 the launches the
  * last multigrid V-cycle enqueued on this context took, as a bit mask: 1 restriction with a workgroup per coarse row, 2 restriction
  * with a thread per entry, 4 coarsest solve with a workgroup per row, 8 coarsest solve with a thread per entry, 16 the one-launch
  * coarse tail, 32 post-smoothing of a level between the finest and the tail, 64 the down kernel on such a level, bits 8-11 the

@@ -433,6 +433,37 @@ def test_retired_switches_are_refused(monkeypatch, name, value):
         _lib.check_environment()
 
 
+def test_device_and_pinned_memory_have_one_owner_each():
+    """Over csrc/*.hip and dots_dev.h: device memory is allocated and freed inside struct DevicePool only, pinned host memory inside
+    struct PinnedPool only, and the mechanisms they replaced (a context copied by value, the fixed allocation tables, the holders of
+    shared and temporary buffers) are gone."""
+    import glob
+
+    csrc = os.path.join(ROOT, "dots_socp_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*.hip"))) + [os.path.join(csrc, "dots_dev.h")]
+    assert len(files) > 10
+    text = {f: open(f).read() for f in files}
+
+    def cut_struct(source, name):      # (source without the struct's body, the body)
+        start = source.index(f"struct {name} {{")
+        at, depth = source.index("{", start), 0
+        for end in range(at, len(source)):
+            depth += {"{": 1, "}": -1}.get(source[end], 0)
+            if depth == 0:
+                return source[:at] + source[end + 1:], source[at:end + 1]
+        raise AssertionError(f"struct {name} does not close")
+
+    header = os.path.join(csrc, "dots_dev.h")
+    text[header], device_pool = cut_struct(text[header], "DevicePool")
+    text[header], pinned_pool = cut_struct(text[header], "PinnedPool")
+    assert device_pool.count("hipMalloc(") == 1 and device_pool.count("hipFree(") == 1
+    assert pinned_pool.count("hipHostMalloc(") == 1 and pinned_pool.count("hipHostFree(") == 1
+    assert "hipMalloc(" not in pinned_pool and "hipHostMalloc(" not in device_pool
+    for f, source in text.items():
+        for gone in ("hipMalloc(", "hipFree(", "hipHostMalloc(", "hipHostFree(", "Ctx tmp", "allocs[", "FrontStore", "DevTemps"):
+            assert gone not in source, (os.path.basename(f), gone)
+
+
 def test_plan_from_the_numpy_reference_functions_equals_the_native_one():
     """geometry.build_plan(native=False) (what host-only tools and the fake device of the gloo tests use: no library needed)
     gives the arrays of the library's dots_assemble."""
