@@ -38,6 +38,7 @@ EXPORTS = [
     "dots_flow_map", "dots_flow_push", "dots_flow_trace", "dots_flow_slide",
     "dots_sensitivity",
     "dots_restart",
+    "dots_move_vertices", "dots_geometry_copy",
 ]
 RESTART_COLD, RESTART_WARM = 0, 1      # dots_restart_desc.mode
 BENCH_RESTART_SCALE = 5                # dots_bench_kernel: the in-place rescaling of dots_restart(WARM), every factor 1
@@ -203,6 +204,15 @@ class SensitivityDesc(C.Structure):      # dots_sensitivity_desc
 class RestartDesc(C.Structure):      # dots_restart_desc
     _fields_ = [("mu0", C.c_void_p), ("mu1", C.c_void_p), ("device_pointers", C.c_int32), ("mode", C.c_int32), ("factors", C.c_double * 4),
                 ("ms", _f64p)]
+
+
+class MoveDesc(C.Structure):      # dots_move_desc
+    _fields_ = [("vertices", C.c_void_p), ("device_pointers", C.c_int32), ("reserved", C.c_int32), ("ms", _f64p)]
+
+
+class GeometryTables(C.Structure):      # dots_geometry_tables
+    NAMES = ("area_tri", "hat_grad", "mass_vert", "lap_val", "kdiag", "corner_scale", "corner_grad_area")
+    _fields_ = [(n, _f64p) for n in NAMES]
 
 
 class StepStats(C.Structure):
@@ -401,6 +411,8 @@ def load(host_only=False):
     lib.dots_flow_slide.argtypes = [vp, C.POINTER(FlowSlideDesc)]
     lib.dots_sensitivity.argtypes = [vp, C.POINTER(SensitivityDesc)]
     lib.dots_restart.argtypes = [vp, C.POINTER(RestartDesc)]
+    lib.dots_move_vertices.argtypes = [vp, C.POINTER(MoveDesc)]
+    lib.dots_geometry_copy.argtypes = [vp, C.POINTER(GeometryTables)]
     lib.dots_prolong_space.argtypes = [vp, vp, C.POINTER(ProlongSpaceDesc)]
     lib.dots_transfer_space.argtypes = [vp, vp, C.POINTER(TransferSpaceDesc)]
     lib.dots_carry_spacetime.argtypes = [vp, vp, C.POINTER(CarrySpacetimeDesc)]

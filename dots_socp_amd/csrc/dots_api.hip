@@ -132,6 +132,7 @@ static int build(Ctx *c, const dots_problem_desc *p) {
         };
         mix(p->lap_rowptr, sizeof(int32_t) * ((size_t)p->n_vertices + 1));
         mix(p->lap_col, sizeof(int32_t) * (size_t)p->lap_nnz);
+        c->lap_hash_graph = h;
         mix(p->lap_val, sizeof(double) * (size_t)p->lap_nnz);
         mix(p->mass_vert, sizeof(double) * (size_t)p->n_vertices);
         c->lap_hash = h;
@@ -309,6 +310,13 @@ static int modal_needs_factor(const Ctx *c, const char *what) {
     if (c->lap_solver != DOTS_LAP_MODAL_PCG || c->dcg.cg_ncol <= CgScalOffsets::NCMAX || (c->use_front && c->front.n_nodes > 0)) return 0;
     if (pcg_windowed(c)) return 0;      // dots_pcg_windows: the PCG takes the modes in windows of 256
     set_error(std::string(what) + ": T + 1 > 256 needs the direct solver (dots_front_setup); the modal PCG takes T + 1 <= 256");
+    return DOTS_ERR_STATE;
+}
+
+// dots_move_vertices changed the surface under the iterate: what steps it or measures it waits for dots_restart
+static int moved_needs_restart(const Ctx *c, const char *what) {
+    if (!c || !c->needs_restart) return 0;
+    set_error(std::string(what) + ": the vertices were moved (dots_move_vertices): the context needs a dots_restart (cold or warm) first");
     return DOTS_ERR_STATE;
 }
 
@@ -575,6 +583,7 @@ int dots_create(const dots_problem_desc *desc, dots_ctx **out) {
     preload_transform_kernels();
     preload_readout_kernels();
     preload_restart_kernels();
+    preload_geometry_kernels();
     *out = c.release();
     return 0;
 }
@@ -772,6 +781,7 @@ int dots_stream_wait(dots_ctx *c, void *other_stream, int ctx_waits) {
 int dots_step(dots_ctx *c, int n_iters, dots_step_stats *stats) {
     int rc = check(c, true, true);      // (run_iteration consumes the flags and a pending penalty division itself)
     if (rc) return rc;
+    if ((rc = moved_needs_restart(c, "dots_step"))) return rc;
     c->batched = 0;
     if (n_iters < 0) { set_error("n_iters < 0"); return DOTS_ERR_ARGUMENT; }
     if (c->shard_stride != 0) { set_error("dots_step on a time slab: use dots_slab_stage"); return DOTS_ERR_STATE; }
@@ -860,6 +870,7 @@ int dots_run_phase(dots_ctx *c, int phase, dots_step_stats *stats) {
     int rc = check(c);
     if (rc) return rc;
     if (c->shard_stride != 0) { set_error("run_phase works on whole arrays: not available on a time slab"); return DOTS_ERR_STATE; }
+    if ((rc = moved_needs_restart(c, "dots_run_phase"))) return rc;
     dots_step_stats local;
     memset(&local, 0, sizeof local);
     if ((rc = materialise_zmid(c))) return rc;
@@ -886,6 +897,7 @@ int dots_run_phase(dots_ctx *c, int phase, dots_step_stats *stats) {
 int dots_kkt(dots_ctx *c, uint32_t mask, double *out) {
     int rc = check(c, true);
     if (rc) return rc;
+    if ((rc = moved_needs_restart(c, "dots_kkt"))) return rc;
     if (!out || (mask >> DOTS_N_KKT)) { set_error("kkt: bad mask or null output"); return DOTS_ERR_ARGUMENT; }
     if (!mask) return 0;
     if (c->zmid_stale && (mask & (1u << DOTS_KKT_PRIM_Z))) { set_error("kkt: z_mid was not materialised by the last step (dots_step_flags)"); return DOTS_ERR_STATE; }
@@ -896,6 +908,7 @@ int dots_kkt(dots_ctx *c, uint32_t mask, double *out) {
 int dots_kkt_sums(dots_ctx *c, uint32_t mask, double *sums) {
     int rc = check(c, true);
     if (rc) return rc;
+    if ((rc = moved_needs_restart(c, "dots_kkt_sums"))) return rc;
     if (!sums || (mask >> DOTS_N_KKT)) { set_error("kkt_sums: bad mask or null output"); return DOTS_ERR_ARGUMENT; }
     static_assert(DOTS_KKT_N_SUMS == MAX_SUMS, "header and kernels disagree on the number of KKT sums");
     for (int i = 0; i < DOTS_KKT_N_SUMS; ++i) sums[i] = 0.0;
@@ -911,6 +924,7 @@ int dots_kkt_sums(dots_ctx *c, uint32_t mask, double *sums) {
 int dots_kkt_sums_device(dots_ctx *c, uint32_t mask, double *device_sums) {
     int rc = check(c, true);
     if (rc) return rc;
+    if ((rc = moved_needs_restart(c, "dots_kkt_sums_device"))) return rc;
     if (!device_sums || (mask >> DOTS_N_KKT)) { set_error("kkt_sums_device: bad mask or null output"); return DOTS_ERR_ARGUMENT; }
     if (c->zmid_stale && (mask & (1u << DOTS_KKT_PRIM_Z))) { set_error("kkt: z_mid was not materialised by the last step (dots_step_flags)"); return DOTS_ERR_STATE; }
     if (c->shard_stride != 0 && !c->kkt_halo_fresh && (mask & ((1u << DOTS_KKT_DUAL_ALPHA) | (1u << DOTS_KKT_COMP_RHO_FQ) | (1u << DOTS_KKT_COMP_M_RHO_B)))) {
@@ -928,6 +942,7 @@ int dots_kkt_combine(dots_ctx *c, uint32_t mask, const double *sums, double *out
 int dots_objective_sums(dots_ctx *c, double *sums) {
     int rc = check(c, true);
     if (rc) return rc;
+    if ((rc = moved_needs_restart(c, "dots_objective_sums"))) return rc;
     if (!sums) { set_error("null output"); return DOTS_ERR_ARGUMENT; }
     return objective_sums(c, sums);
 }
@@ -941,6 +956,7 @@ int dots_objective_combine(dots_ctx *c, const double *sums, double *out) {
 int dots_objective(dots_ctx *c, double *out) {
     int rc = check(c, true);
     if (rc) return rc;
+    if ((rc = moved_needs_restart(c, "dots_objective"))) return rc;
     if (!out) { set_error("null output"); return DOTS_ERR_ARGUMENT; }
     if (c->shard_stride != 0) { set_error("objective on a time slab: use dots_objective_sums / dots_objective_combine"); return DOTS_ERR_STATE; }
     return objective_evaluate(c, out);
@@ -1280,6 +1296,7 @@ int dots_step_many(dots_ctx *const *cs, int n, dots_step_stats *stats) {
     int rc;
     for (int k = 0; k < n; ++k) {
         if ((rc = check(cs[k], true, true))) return rc;      // (the iteration consumes the flags and a pending division itself)
+        if ((rc = moved_needs_restart(cs[k], "dots_step_many"))) return rc;
         if (!front_batchable(cs[k])) { set_error("step_many: every context needs an installed or shared factor on one GPU (no PCG, no time slab)"); return DOTS_ERR_STATE; }
         if (cs[k]->front.F != cs[0]->front.F) { set_error("step_many: the contexts do not share one factor (dots_front_share)"); return DOTS_ERR_ARGUMENT; }
         for (int j = 0; j < k; ++j)
@@ -1589,6 +1606,7 @@ int dots_restart(dots_ctx *c, const dots_restart_desc *desc) {
     q.congestion = 0.0; q.prim_scale = 1.0; q.dual_scale = 1.0; q.boundary_scale = 1.0;      // (tau, eps, cg_tol, cg_max_iter stay)
     // host bookkeeping of the old run
     c->zmid_stale = c->zmid_deferred = 0;
+    c->needs_restart = 0;      // (after dots_move_vertices: the run that starts here is one on the new surface)
     c->zmid_dv = c->zmid_sz = 0.0;
     c->ahead_dv = c->ahead_r = c->ahead_div = 0.0;
     c->kkt_halo_fresh = 0;
@@ -1606,6 +1624,129 @@ int dots_restart(dots_ctx *c, const dots_restart_desc *desc) {
         DOTS_HIP(hipEventElapsedTime(&t, c->ev[0], c->ev[1]));
         *desc->ms = t;
     }
+    return 0;
+}
+
+// ---- dots_move_vertices: other vertex positions on a live context (include/dots_socp_hip.h) ------------------------------------------
+int dots_move_vertices(dots_ctx *c, const dots_move_desc *desc) {
+    if (!c || !desc || !desc->vertices) { set_error("move_vertices: null argument"); return DOTS_ERR_ARGUMENT; }
+    if (c->shard_stride != 0) { set_error("move_vertices: not available on a time slab"); return DOTS_ERR_STATE; }
+    if (c->lap_solver != DOTS_LAP_MODAL_PCG) { set_error("move_vertices: the context is not modal (DOTS_LAP_MODAL_PCG)"); return DOTS_ERR_STATE; }
+    if (c->mg.nlev >= 2) { set_error("move_vertices: a multigrid hierarchy is installed (its coarse operators belong to the old surface)"); return DOTS_ERR_STATE; }
+    if (c->front_store && c->front_store.use_count() > 1) {
+        set_error("move_vertices: the factor store is shared (dots_front_share): a sharer cannot move it, and an owner not under its sharers");
+        return DOTS_ERR_STATE;
+    }
+    const bool on_device = desc->device_pointers != 0;
+    const int V = c->d.V, F = c->d.F, nnz = c->nnz;
+    if (!on_device)
+        for (int64_t i = 0; i < (int64_t)3 * V; ++i)
+            if (!std::isfinite(desc->vertices[i])) { set_error("move_vertices: a coordinate that is not finite"); return DOTS_ERR_ARGUMENT; }
+    hipError_t e0 = hipSetDevice(c->device);
+    if (e0 != hipSuccess) return hip_fail(e0, "hipSetDevice", __FILE__, __LINE__);
+    int rc = front_refresh_check(c);
+    if (rc) return rc;
+    // scratch in the staging buffer: [area F | hat 9 F | mass V | flag | xyz 3 V], every part on a 16-byte boundary
+    auto even = [](int64_t n) { return (n + 1) & ~(int64_t)1; };
+    const int64_t o_hat = even(F), o_mass = o_hat + even((int64_t)9 * F), o_flag = o_mass + even(V), o_xyz = o_flag + 2, total = o_xyz + (int64_t)3 * V;
+    if (total > c->stage_count) { set_error("move_vertices: the scratch tables do not fit the staging buffer on this mesh"); return DOTS_ERR_STATE; }
+    // what dots_download does before it reads, with the OLD geometry (z_mid is rebuilt from tables that are about to change); the launch
+    // ahead, an armed penalty decision, the carried gathers and the fused sums go (check)
+    if ((rc = check(c)) || (rc = materialise_zmid(c))) return rc;
+    Dev &d = c->d;
+    GeomScratch s{c->stage, c->stage + o_hat, c->stage + o_mass, reinterpret_cast<int *>(c->stage + o_flag)};
+    const double *xyz = desc->vertices;
+    if (!on_device) {
+        DOTS_HIP(hipMemcpyAsync(c->stage + o_xyz, desc->vertices, sizeof(double) * (size_t)3 * V, hipMemcpyHostToDevice, c->stream));
+        xyz = c->stage + o_xyz;
+    }
+    DOTS_HIP(hipEventRecord(c->ev[0], c->stream));
+    if ((rc = launch_geometry_validate(c, xyz, s))) return rc;
+    DOTS_HIP(hipEventRecord(c->ev[1], c->stream));
+    int flag = 0;
+    DOTS_HIP(hipMemcpyAsync(&flag, s.flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    DOTS_HIP(hipStreamSynchronize(c->stream));      // (host positions are borrowed for the call only)
+    if (flag) {
+        set_error("move_vertices: a coordinate that is not finite, a triangle whose area is not positive or a vertex whose mass is not positive; the context keeps its geometry");
+        return DOTS_ERR_ARGUMENT;
+    }
+    // from here on the context is on the new surface
+    DOTS_HIP(hipEventRecord(c->ev[2], c->stream));
+    if ((rc = launch_geometry_commit(c, s))) return rc;
+    DOTS_HIP(hipEventRecord(c->ev[3], c->stream));
+    c->needs_restart = 1;
+    c->kkt_halo_fresh = 0;
+    // the host constants of build(): its sequential sums over the tables, downloaded once
+    std::vector<double> area((size_t)F), val((size_t)nnz), mu0((size_t)V), mu1((size_t)V);
+    auto mass = std::make_shared<std::vector<double>>((size_t)V);
+    DOTS_HIP(hipMemcpyAsync(area.data(), d.area_f, sizeof(double) * (size_t)F, hipMemcpyDeviceToHost, c->stream));
+    DOTS_HIP(hipMemcpyAsync(mass->data(), d.mass_v, sizeof(double) * (size_t)V, hipMemcpyDeviceToHost, c->stream));
+    DOTS_HIP(hipMemcpyAsync(val.data(), d.val, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToHost, c->stream));
+    DOTS_HIP(hipMemcpyAsync(mu0.data(), d.mu0, sizeof(double) * (size_t)V, hipMemcpyDeviceToHost, c->stream));
+    DOTS_HIP(hipMemcpyAsync(mu1.data(), d.mu1, sizeof(double) * (size_t)V, hipMemcpyDeviceToHost, c->stream));
+    DOTS_HIP(hipStreamSynchronize(c->stream));
+    c->d2h_bytes += (int64_t)sizeof(double) * ((int64_t)F + 3 * (int64_t)V + nnz);
+    {
+        uint64_t h = c->lap_hash_graph;
+        auto mix = [&h](const void *data, size_t bytes) {
+            const unsigned char *b = static_cast<const unsigned char *>(data);
+            for (size_t i = 0; i < bytes; ++i) h = (h ^ b[i]) * 1099511628211ull;
+        };
+        mix(val.data(), sizeof(double) * (size_t)nnz);
+        mix(mass->data(), sizeof(double) * (size_t)V);
+        c->lap_hash = h;
+    }
+    double sm = 0.0, sa = 0.0;
+    for (int v = 0; v < V; ++v) sm += (*mass)[(size_t)v];
+    for (int f = 0; f < F; ++f) sa += area[(size_t)f];
+    const double mean_v = sm / V, mean_f = sa / F;
+    c->c_prim_q = 0.5 * (mean_v + mean_f);
+    c->c_prim_z = (mean_v + mean_f + mean_v) / 3.0;
+    c->c_dual_alpha = mean_v;
+    c->c_dual_beta = 0.5 * (mean_v + mean_f);
+    c->c_comp_rho = mean_v;
+    c->c_comp_m = mean_f;
+    c->prm.norm_d = c->norm_d0 = std::sqrt(2.0 * sa);
+    c->mass_host = mass;      // (a new vector: whoever shares the old one keeps it)
+    c->prm.norm_boundary = boundary_norm(boundary_sum(mu0.data(), mu1.data(), mass->data(), V), d.T);
+    // the factor the context owns, from K + (sigma_a + eps) M of the new tables, into the allocations it has
+    DOTS_HIP(hipEventRecord(c->ev[6], c->stream));
+    if (c->front.n_nodes > 0 && (rc = front_refresh(c))) {
+        (void)hipStreamSynchronize(c->stream);
+        const std::string why = g_last_error;
+        d.cn_sq = d.cn_g = d.cn_lo = d.cn_e = nullptr;
+        front_release(c);      // (a PCG context from here on, as after a failed dots_front_setup)
+        set_error(why);
+        return rc;
+    }
+    DOTS_HIP(hipEventRecord(c->ev[7], c->stream));
+    DOTS_HIP(hipStreamSynchronize(c->stream));
+    if (desc->ms) {
+        float a = 0.f, b = 0.f, f = 0.f, w = 0.f;
+        DOTS_HIP(hipEventElapsedTime(&a, c->ev[0], c->ev[1]));
+        DOTS_HIP(hipEventElapsedTime(&b, c->ev[2], c->ev[3]));
+        DOTS_HIP(hipEventElapsedTime(&f, c->ev[6], c->ev[7]));
+        DOTS_HIP(hipEventElapsedTime(&w, c->ev[0], c->ev[7]));
+        desc->ms[0] = (double)a + b;
+        desc->ms[1] = f;
+        desc->ms[2] = w;
+    }
+    return 0;
+}
+
+int dots_geometry_copy(dots_ctx *c, const dots_geometry_tables *out) {
+    int rc = check(c, true, true);      // (reads tables only: neither the state nor the parameters)
+    if (rc) return rc;
+    if (!out) { set_error("geometry_copy: null argument"); return DOTS_ERR_ARGUMENT; }
+    const Dev &d = c->d;
+    const int64_t V = d.V, F = d.F;
+    const struct { double *host; const double *dev; int64_t n; } parts[] = {
+        {out->area_tri, d.area_f, F}, {out->hat_grad, d.hat, 9 * F}, {out->mass_vert, d.mass_v, V}, {out->lap_val, d.val, (int64_t)c->nnz},
+        {out->kdiag, d.kdiag, V}, {out->corner_scale, d.c_D, 3 * F}, {out->corner_grad_area, d.c_gA, 9 * F}};
+    DOTS_HIP(hipStreamSynchronize(c->stream));
+    for (const auto &p : parts)
+        if (p.host) DOTS_HIP(hipMemcpyAsync(p.host, p.dev, sizeof(double) * (size_t)p.n, hipMemcpyDeviceToHost, c->stream));
+    DOTS_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }
 

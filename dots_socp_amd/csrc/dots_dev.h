@@ -337,6 +337,7 @@ constexpr int PCG_MAX_WINDOWS = TILE_ELEMS / PCG_WINDOW;
 static_assert((1 << PCG_WINDOW_SHIFT) == PCG_WINDOW, "window pitch");
 
 struct Ctx;
+struct FrontRecord;      // kernels_front.hip
 // ---- launch wrappers implemented in the kernel files (all asynchronous on ctx stream) ----
 int launch_soc_projection(Ctx *c, int zmid_mode = 0, bool with_inverse = false);   // 0: write z_mid; 1: write only the cone multiplier; with_inverse: extra workgroups do the modes -> time transform of phi
 void preload_alm_kernels();
@@ -377,7 +378,11 @@ int cg_bench(Ctx *c, int which, int reps, double *ms, double *bytes);
 int64_t cg_partials_needed(const Dev &d);   // doubles of Dev::partials the PCG uses
 int front_setup(Ctx *c, const dots_front_desc *desc);
 void front_release(Ctx *c);
-int front_factorize(Ctx *c, const dots_front_desc *desc, FrontDev &f, const std::vector<FrontNode> &nodes, double *T, const int *grounded_host);
+// `zero_entries` > 0: T holds an old factor; that many entries of it are zeroed once the temporaries are allocated (front_refresh)
+int front_factorize(Ctx *c, const dots_front_desc *desc, FrontDev &f, const std::vector<FrontNode> &nodes, double *T, const int *grounded_host, int64_t zero_entries = 0);
+// dots_move_vertices: the numeric phases of front_setup again, into the allocations of the installed factor (Ctx::front_record)
+int front_refresh_check(Ctx *c);      // DOTS_ERR_STATE / DOTS_ERR_MEMORY before anything is touched
+int front_refresh(Ctx *c);
 int front_solve(Ctx *c, const double *bhat, double *y, double *x);   // x = A^-1 bhat for every mode of the PCG view (y: scratch)
 // the same for n problems on one shared factor (dots_front_share), up to Ctx::front_nr_max per launch, on cs[0]'s stream; n = 1 is front_solve
 int front_solve_many(Ctx *const *cs, int n, const double *const *bhat, double *const *y, double *const *x);
@@ -427,6 +432,15 @@ int launch_restart_scale(Ctx *c, const double factor[4], double *bytes);
 // sum over v of (mu0[v]^2 + mu1[v]^2) / mass_v[v] of two DEVICE arrays in a fixed order, left in *out on the host (waits for the stream)
 int restart_boundary_sum(Ctx *c, const double *mu0, const double *mu1, double *out);
 void preload_restart_kernels();
+
+// ---- dots_move_vertices (kernels_geometry.hip): the geometry tables from vertex positions, dots_assemble's and dots_create's bits
+struct GeomScratch {
+    double *area, *hat, *mass;   // [F], [F][3][3], [V]
+    int *flag;                   // raised for a coordinate that is not finite, an area or a mass that is not positive
+};
+int launch_geometry_validate(Ctx *c, const double *xyz, const GeomScratch &s);      // triangle pass and the vertex masses, into scratch
+int launch_geometry_commit(Ctx *c, const GeomScratch &s);                           // every table of the context from the scratch
+void preload_geometry_kernels();
 // The flow map (kernels_flow.hip): one lane per particle, the loop over the intervals inside the kernel.  Everything in the DEVICE
 // numbering except the triangles written out, which perm_f takes back to the caller's.  A launch takes FlowArgs and FlowSpan, with
 // deposits FlowPush, with the sliding mode FlowSlide: separate by-value kernel arguments, in the order args, push, span, slide.
@@ -658,10 +672,13 @@ struct Ctx {
     // planes) and the carried gathers are this context's own
     std::shared_ptr<DevicePool> front_store;
     DevicePool front_own;
+    std::shared_ptr<FrontRecord> front_record;      // what front_setup planned, kept with the store: dots_move_vertices refreshes the factor from it
     int front_nr_max = 4;         // right-hand sides per launch of front_solve_many (DOTS_FRONT_NR: 2, 4 or 8)
     hipEvent_t ev_batch = nullptr;   // orders this context's stream against the others of a batched solve (created on first use)
     int front_cap_fault = 0;      // a multi-rhs launch was asked for more right-hand sides than its workgroup shape takes (front_solve_many reports it)
     int64_t front_many_launches = 0, front_many_split = 0;   // sweep launches of the last front_solve_many, those split below their chunk (dots_debug_counter 7, 8)
+    uint64_t lap_hash_graph = 0;  // ... its state after rowptr and col (dots_move_vertices goes on from there)
+    int needs_restart = 0;        // dots_move_vertices changed the surface under the iterate: dots_restart before the next step
     uint64_t lap_hash = 0;        // FNV-1a of the Laplacian (rowptr, col, val) and the vertex masses: dots_front_share compares it with the owner's
     int batched = 0;              // stepped by dots_step_many since its last dots_step: dots_penalty_ahead is refused
     // dots_readout: built on first use

@@ -257,8 +257,9 @@ __global__ __launch_bounds__(256) void k_fact_gmat(FactArgs g, FrontDev f) {
 }
 
 // Factorise on the device.  `f` holds the tree (nodes, vmap, bd_vertex already uploaded); T (zeroed,
-// n_entries << sh doubles) receives the factor.  Host arrays: per-level node lists and the pull maps.
-int front_factorize(Ctx *c, const dots_front_desc *h, FrontDev &f, const std::vector<FrontNode> &nodes, double *T, const int *grounded_host) {
+// n_entries << sh doubles) receives the factor; with `zero_entries` it holds an old factor and that many entries (the original and the
+// merged blocks) are zeroed here, once the temporaries are allocated.  Host arrays: per-level node lists and the pull maps.
+int front_factorize(Ctx *c, const dots_front_desc *h, FrontDev &f, const std::vector<FrontNode> &nodes, double *T, const int *grounded_host, int64_t zero_entries) {
     const Dev &d = c->dcg;
     const int sh = d.tp_shift;
     int rc = 0;
@@ -271,6 +272,8 @@ int front_factorize(Ctx *c, const dots_front_desc *h, FrontDev &f, const std::ve
         (rc = tmp.upload(&g.pull0, h->pull0, (int64_t)h->n_front_rows, c->stream)) || (rc = tmp.upload(&g.pull1, h->pull1, (int64_t)h->n_front_rows, c->stream)) ||
         (rc = tmp.upload(&ln, h->level_nodes, (int64_t)h->n_nodes, c->stream)) || (rc = tmp.upload(&g.grounded, grounded_host, (int64_t)d.TP, c->stream)) ||
         (rc = tmp.alloc(&g.bad_pivot, 1, c->stream))) return rc;
+    // (a refresh: the old factor was intact until here, whatever failed above)
+    if (zero_entries > 0) DOTS_HIP(hipMemsetAsync(T, 0, sizeof(double) * ((size_t)zero_entries << sh), c->stream));
     g.sh = sh; g.TP = d.TP; g.ncol = d.cg_ncol;
     g.wsh = std::min(sh, 8);
     const unsigned nch = 1u << (sh - g.wsh);      // chunks of 256 modes (1 up to a pitch of 256)

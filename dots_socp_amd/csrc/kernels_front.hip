@@ -958,6 +958,7 @@ static void front_launch_bwd(Ctx *c, const FrontDev &f, const FrontWork *ptr, in
 void front_release(Ctx *c) {
     c->front_own.release();
     c->front_store.reset();      // (a shared factor: freed with its last holder)
+    c->front_record.reset();
     c->front = FrontDev{};
     c->use_front = 0;
     c->sched = FrontSchedule{c->sched.vec2};      // (the switch is the context's own)
@@ -997,6 +998,9 @@ struct FrontPlan {
     std::vector<std::vector<int>> by_band;                // group indices per band
     std::vector<int64_t> band_rows, band_cols;
     int lanes_row = 1;                                    // lanes that hold one row of modes (half the pitch with two-mode lanes)
+    // install_leaves
+    std::vector<int64_t> leaf_foff;                       // the leaves' blocks in F and their sizes, in the order of FrontDev::leafS
+    std::vector<int> leaf_n;
 
     // lane groups of a wavefront in the row kernel: 64 / (lanes per row of modes); 0 = a row of modes is wider than a wavefront
     int rows_groups() const { return lanes_row <= 64 ? 64 / lanes_row : 0; }
@@ -1787,6 +1791,8 @@ int install_leaves(Ctx *c, const dots_front_desc *h, FrontPlan &P, FrontDev &f) 
     int rc;
     if ((rc = c->front_store->upload<double>(&dS, nullptr, total << d.tp_shift, c->stream)) || (rc = c->front_store->upload(&dl, leaves, c->stream))) return rc;
     if ((rc = explicit_inverses(c, f.F, foff, n, true, const_cast<double *>(dS), "leaf inverses"))) return rc;
+    P.leaf_foff = foff;
+    P.leaf_n = n;
     f.leafS = dS;
     f.leaf_desc = dl;
     f.n_leaves = (int)leaves.size();
@@ -1966,6 +1972,24 @@ int install_schedule(Ctx *c, const dots_front_desc *h, const FrontPlan &P, Front
 }
 }  // namespace
 
+// What front_setup planned, kept with the installed factor (Ctx::front_record, released with it): the host plan, the tree as the
+// factorisation sees it, and the arrays of the description the numeric phases read.  dots_move_vertices runs those phases again from
+// it (front_refresh) and needs nothing from the caller but the positions.
+struct FrontRecord {
+    FrontPlan P;
+    FrontDev f0{};                                        // nodes, vmap0, bd_vertex: in the store
+    std::vector<int> pull0, pull1, level_ptr, level_nodes, grounded;
+    int64_t n_entries = 0, n_front_rows = 0;
+    int n_nodes = 0, n_levels = 0;
+    bool from_values = false;                             // the factor was the caller's values: there is nothing to compute again
+    dots_front_desc desc() const {                        // the fields front_factorize and merge_bands read
+        dots_front_desc h{};
+        h.n_nodes = n_nodes; h.n_levels = n_levels; h.n_entries = n_entries; h.n_front_rows = n_front_rows;
+        h.pull0 = pull0.data(); h.pull1 = pull1.data(); h.level_ptr = level_ptr.data(); h.level_nodes = level_nodes.data();
+        return h;
+    }
+};
+
 // The direct solver's setup: a host plan (FrontPlan) filled phase by phase, then the device work in a fixed order -- allocate, factorise,
 // merge, top inverse, W, leaf inverses, leaf tables, tuner, lists.  What a sharer of the factor reads goes into the store, W into front_own.
 int front_setup(Ctx *c, const dots_front_desc *h) {
@@ -2002,7 +2026,87 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
     if ((rc = apply_cfg(c, P))) return rc;
     if (c->front_tune) tune_bands(c, h, P, f);
     if ((rc = install_schedule(c, h, P, f))) return rc;
+    {   // what a later front_refresh needs, kept with the store
+        auto rec = std::make_shared<FrontRecord>();
+        rec->f0 = f0;
+        rec->pull0.assign(h->pull0, h->pull0 + h->n_front_rows);
+        rec->pull1.assign(h->pull1, h->pull1 + h->n_front_rows);
+        rec->level_ptr.assign(h->level_ptr, h->level_ptr + h->n_levels + 1);
+        rec->level_nodes.assign(h->level_nodes, h->level_nodes + h->n_nodes);
+        rec->grounded.assign((size_t)d.TP, 0);
+        if (h->grounded)
+            for (int a = 0; a < h->n_modes; ++a) rec->grounded[(size_t)a] = h->grounded[a] ? 1 : 0;
+        rec->n_entries = h->n_entries; rec->n_front_rows = h->n_front_rows;
+        rec->n_nodes = h->n_nodes; rec->n_levels = h->n_levels;
+        rec->from_values = h->values != nullptr;
+        rec->P = std::move(P);
+        c->front_record = rec;
+    }
     guard.done = true;
+    return 0;
+}
+
+// What the factorisation allocates beside the factor while it runs (front_factorize: the copy of the fronts, the Schur complements)
+static double refresh_work_bytes(const Ctx *c, const FrontRecord &R) {
+    int64_t srows = 0;
+    for (const FrontNode &nd : R.P.nodes) srows = std::max(srows, nd.soff + (int64_t)nd.b * nd.b);
+    return 8.0 * (double)c->dcg.TP * (double)(R.n_entries + std::max<int64_t>(srows, 1));
+}
+
+int front_refresh_check(Ctx *c) {
+    if (c->front.n_nodes == 0) return 0;
+    if (!c->front_record || c->front_record->from_values) {
+        set_error("move_vertices: the factor was installed from the caller's values (dots_front_desc.values): there is no factorisation to run again");
+        return DOTS_ERR_STATE;
+    }
+    if (c->prm.eps != c->sched.eps) {
+        char buf[192];
+        snprintf(buf, sizeof buf, "move_vertices: eps %.17g, the factor was built with %.17g", c->prm.eps, c->sched.eps);
+        set_error(buf);
+        return DOTS_ERR_STATE;
+    }
+    size_t free_b = 0, total_b = 0;
+    DOTS_HIP(hipMemGetInfo(&free_b, &total_b));
+    double budget = 0.97 * (double)free_b;
+    int mb = -1;
+    if (!env_int("DOTS_MEM_BUDGET", 0, 1 << 30, &mb)) return DOTS_ERR_ARGUMENT;
+    if (mb >= 0) budget = 1048576.0 * mb;
+    const double work_b = refresh_work_bytes(c, *c->front_record);
+    if (work_b > budget) {
+        char buf[256];
+        snprintf(buf, sizeof buf, "move_vertices: the temporaries of the factorisation do not fit: %.3f GB against %.3f GB available", work_b * 1e-9, budget * 1e-9);
+        set_error(buf);
+        return DOTS_ERR_MEMORY;
+    }
+    return 0;
+}
+
+// The numeric phases of front_setup on the live store, from the geometry tables the context holds now: the factor (zeroed once the
+// temporaries are there), the merged blocks, the top band's inverse, the leaves' packed inverses and coupling records.  The tree, the
+// maps, W, the work lists and the schedule stay.  A failure leaves the store's numbers undefined: the caller releases the factor.
+int front_refresh(Ctx *c) {
+    const FrontRecord &R = *c->front_record;
+    const FrontPlan &P = R.P;
+    const dots_front_desc h = R.desc();
+    FrontDev f0 = R.f0;
+    double *F = const_cast<double *>(c->front.F);
+    int rc;
+    if ((rc = front_factorize(c, &h, f0, P.nodes, F, R.grounded.data(), R.n_entries + P.merged_entries))) return rc;
+    if ((rc = merge_bands(c, &h, P, F))) return rc;
+    if (P.top_inv && (rc = invert_top_band(c, P, F))) return rc;
+    const FrontDev &f = c->front;
+    if (f.n_leaves > 0 && (rc = explicit_inverses(c, F, P.leaf_foff, P.leaf_n, true, const_cast<double *>(f.leafS), "leaf inverses"))) return rc;
+    if (f.n_leaves > 0 && f.leaf_bd) {
+        const Dev &d = c->dcg;
+        DevicePool tmp(c->device);      // (freed behind the stream synchronisation below)
+        int *over = nullptr;
+        if ((rc = tmp.alloc(&over, 1, c->stream))) return rc;
+        hipLaunchKernelGGL(k_leaf_tables, dim3(f.n_leaves), dim3(64), 0, c->stream, f, d.rowptr, d.col, d.val, const_cast<LeafBdRow *>(f.leaf_bd),
+                           const_cast<LeafSepRow *>(f.leaf_sep), over);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) return hip_fail(e, "leaf coupling records", __FILE__, __LINE__);
+    }
     return 0;
 }
 

@@ -554,6 +554,59 @@ class DeviceProblem:
         self.restart_ms = ms.value
         return ms.value
 
+    def move_vertices(self, vertices, device_pointers=False):
+        """Move the vertices of the live context to ``vertices`` (V, 3), caller's numbering (dots_move_vertices): every geometry table
+        is assembled again on the device and a factor the context owns is computed again into its allocations; the tree, the plan of
+        the bands and the state stay.  The context then needs ``restart`` before it steps.  An array, or with ``device_pointers`` a
+        float64 torch tensor on the context's device (permuted there; the positions come down once, 24 V bytes, for the plan).
+        ``self.plan`` becomes ``geometry.plan_with_vertices(self.plan, vertices)`` and ``self.params`` is read again.  Returns the
+        device milliseconds of the assembly launches, of the factor refresh and of the whole call."""
+        from .geometry import plan_with_vertices
+
+        if self.slab:
+            raise ValueError("move_vertices: not available on time slabs")
+        perm = self.plan.perm_vert
+        d = _lib.MoveDesc()
+        if device_pointers:
+            import torch
+
+            where = torch.device("cuda", self.device)
+            a = vertices
+            if not isinstance(a, torch.Tensor) or a.device != where or a.dtype != torch.float64 or tuple(a.shape) != (self.V, 3):
+                raise ValueError(f"move_vertices: vertices must be a float64 tensor of shape ({self.V}, 3) on {where}")
+            a = a.detach()
+            keep = (a if perm is None else a[torch.as_tensor(perm, device=where, dtype=torch.int64)]).contiguous()
+            torch.cuda.current_stream(where).synchronize()      # (the call reads it on the context's stream)
+            d.vertices = keep.data_ptr()
+            host = a.cpu().numpy()
+        else:
+            host = np.asarray(vertices, dtype=np.float64)
+            if host.shape != (self.V, 3):
+                raise ValueError(f"move_vertices: vertices must have shape ({self.V}, 3), got {host.shape}")
+            keep = np.ascontiguousarray(host if perm is None else host[perm])
+            d.vertices = keep.ctypes.data
+        plan = plan_with_vertices(self.plan, host)      # (raises for what the library would refuse, before the context is touched)
+        d.device_pointers = int(bool(device_pointers))
+        ms = (C.c_double * 3)()
+        d.ms = C.cast(ms, C.POINTER(C.c_double))
+        _lib.check(self.lib.dots_move_vertices(self._h, C.byref(d)), "dots_move_vertices")
+        self.plan = plan
+        _lib.check(self.lib.dots_get_params(self._h, C.byref(self.params)), "dots_get_params")
+        self.move_ms = tuple(float(x) for x in ms)
+        return self.move_ms
+
+    def geometry_tables(self):
+        """The geometry tables the context holds (dots_geometry_copy), device numbering: a dict of arrays named as ``DevicePlan``'s,
+        plus ``kdiag`` (V,), ``corner_scale`` (3F,) and ``corner_grad_area`` (3F, 3) in corner-list order."""
+        V, F, nnz = self.V, self.F, int(self.plan.lap_val.size)
+        out = {"area_tri": np.empty(F), "hat_grad": np.empty((F, 3, 3)), "mass_vert": np.empty(V), "lap_val": np.empty(nnz), "kdiag": np.empty(V),
+               "corner_scale": np.empty(3 * F), "corner_grad_area": np.empty((3 * F, 3))}
+        t = _lib.GeometryTables()
+        for name, a in out.items():
+            setattr(t, name, _ptr(a, C.c_double))
+        _lib.check(self.lib.dots_geometry_copy(self._h, C.byref(t)), "dots_geometry_copy")
+        return out
+
     # ---- the hot loop
     def step(self, n_iters=1, wait=True):
         """``wait=False``: only enqueue (direct solver); returns None, nothing is timed."""

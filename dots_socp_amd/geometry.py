@@ -209,6 +209,33 @@ def plan_with_densities(plan: DevicePlan, mu0, mu1) -> DevicePlan:
     return dataclasses.replace(plan, mu0=c(mu0), mu1=c(mu1))
 
 
+def plan_with_vertices(plan: DevicePlan, vertices) -> DevicePlan:
+    """``plan`` with the vertices moved to ``vertices`` (V, 3), caller's numbering: the plan ``build_plan`` would return for the moved
+    mesh if it numbered it as ``plan`` does.  The permutations and the dissection are shared, the triangles and the corner lists are
+    unchanged (the connectivity is), the tables come from ``assemble_native`` on the permuted positions; ``area_mesh`` and
+    ``vertices`` are refreshed.  What ``dots_move_vertices`` leaves on a live context, bit for bit."""
+    v = np.asarray(vertices, dtype=np.float64)
+    V = plan.n_vertices
+    if v.shape != (V, 3):
+        raise ValueError(f"vertices must have shape ({V}, 3), got {v.shape}")
+    if not np.all(np.isfinite(v)):
+        raise ValueError("vertices has entries that are not finite")
+    if plan.perm_vert is not None:
+        v = v[plan.perm_vert]
+    area, hat, mass, cptr, cidx, K = assemble_native(v, plan.triangles)
+    if not np.all(area > 0):
+        raise ValueError("degenerate triangle (zero area)")
+    if not np.all(mass > 0):
+        raise ValueError("isolated vertex (no incident triangle)")
+    rowptr, col = K.indptr.astype(np.int32), K.indices.astype(np.int32)
+    if not (np.array_equal(cptr, plan.corner_ptr) and np.array_equal(cidx, plan.corner_idx) and np.array_equal(rowptr, plan.lap_rowptr)
+            and np.array_equal(col, plan.lap_col)):
+        raise ValueError("plan_with_vertices: the plan's corner lists or Laplacian pattern are not those of its triangles")
+    c = np.ascontiguousarray
+    return dataclasses.replace(plan, hat_grad=c(hat), area_tri=c(area), mass_vert=c(mass), lap_val=c(K.data.astype(np.float64)),
+                               area_mesh=float(area.sum()), vertices=c(v))
+
+
 def plan_with_time(plan: DevicePlan, n_time) -> DevicePlan:
     """``plan`` on another time grid: the mesh arrays, the permutation and the dissection are shared, only the time modes are new.
     Valid when ``build_plan`` would number the mesh the same way at ``n_time`` (always without reordering and with "rcm"; with "nd"

@@ -238,6 +238,7 @@ class AlmSolver:
         self.tol_checkpoints = _validate_checkpoints(tol_checkpoints, tol)
         self.geometry = geometry        # (read_out takes the area weights and mu0 / mu1 from it)
         self.checkpoint_solutions = []
+        self.move_ms = None             # device milliseconds of the last restart's move of the vertices (restart(vertices=)); None: it moved nothing
         self.n_time, self.nit, self.tol, self.time_limit = int(n_time), int(nit), tol, time_limit
         self.is_z_scaling, self.is_constant_scaling = is_z_scaling, is_constant_scaling
         self.check_kkt_step_by_step = check_kkt_step_by_step
@@ -886,7 +887,7 @@ class AlmSolver:
         self.closed = True
         self.dev.close()
 
-    def restart(self, mu0, mu1, warm=True, nit=None, tol=None, tol_checkpoints=None, time_limit=None, congestion=None):
+    def restart(self, mu0, mu1, warm=True, nit=None, tol=None, tol_checkpoints=None, time_limit=None, congestion=None, vertices=None):
         """The next problem of a solve session on the live context: other end masses ``mu0`` / ``mu1`` (V,) on the same surface
         (DeviceProblem.restart: dots_restart).  The factor, the hierarchy and the plan are kept; the run starts as a new solver's does
         (r = 1, the initial z scaling, a fresh penalty schedule, validator and history).  ``warm=True``: from the recovered iterate
@@ -895,7 +896,11 @@ class AlmSolver:
         May be called mid-run, after the run has finished or after ``finalize``, not after ``close``; the caller's arrays and
         ``geometry`` dict are not written to (``self.geometry`` becomes a shallow copy with the new masses).  ``nit``, ``tol``,
         ``tol_checkpoints``, ``time_limit``, ``congestion``: None keeps the solver's.  Torch tensors on the context's device are read
-        there (their finiteness is then the caller's business).  Returns the device milliseconds of the call."""
+        there (their finiteness is then the caller's business).  Returns the device milliseconds of the call.
+        ``vertices`` (V, 3): the surface moves first (DeviceProblem.move_vertices: dots_move_vertices) -- same triangles, other
+        positions; the geometry tables are assembled and the factor is computed again on the device, the tree and the plan stay --
+        and the run then starts on the moved surface: what a new solver on ``geometry.plan_with_vertices(plan, vertices)`` computes,
+        bit for bit.  ``self.geometry`` follows (vertices, areas); ``self.move_ms``: the three times of the move, or None."""
         tol = self.tol if tol is None else tol
         checkpoints = _validate_checkpoints(tol_checkpoints, tol)
         if getattr(self, "closed", False):
@@ -921,6 +926,18 @@ class AlmSolver:
             raise ValueError("restart: the last iteration stored no z_mid (nothing was read back after it): a warm restart needs the "
                              "whole iterate; iterate to a read-back or restart cold")
         factors = self.recovery_factors() if warm else None
+        self.move_ms = None
+        if vertices is not None:
+            moved_on_device = _is_device_tensor(vertices)
+            if not moved_on_device and type(vertices).__module__.startswith("torch"):
+                vertices = vertices.detach().cpu().numpy()
+            self.move_ms = self.dev.move_vertices(vertices, device_pointers=moved_on_device)
+            from .. import meshes
+
+            moved = np.array(vertices.detach().cpu().numpy() if moved_on_device else vertices, dtype=np.float64)
+            t = np.asarray(self.geometry["triangles"])
+            area_t = meshes.triangle_areas(moved, t)
+            self.geometry = {**self.geometry, "vertices": moved, "area_triangles": area_t, "area_vertices": meshes.vertex_areas(V, t, area_t)}
         ms = self.dev.restart(masses[0], masses[1], "warm" if warm else "cold", factors, device_pointers=on_device)
         if on_device:      # (the plan's host copies, back in the caller's numbering: read_out and flow_map take the end masses from the geometry)
             order = self._caller_order()
@@ -1035,8 +1052,9 @@ class SolveSession:
     ``solver_socp`` that shape the solver (``SESSION_KEYS``; no ``init_solution``: a session starts from zero or from its own last
     iterate).  The first ``solve`` builds the solver -- plan, factor, context --, every later one restarts it on the device
     (``AlmSolver.restart``: dots_restart): nothing is rebuilt, and nothing but what the caller asks for crosses to the host.
-    ``close()`` (or leaving the ``with`` block) releases the context.  Not over ``solver_socp_many``, the cascades, time slabs or
-    moved vertices (a numeric re-factorisation is another call)."""
+    ``close()`` (or leaving the ``with`` block) releases the context.  Moved vertices -- the same triangles at other positions -- are
+    taken by ``solve(..., vertices=)``: the geometry tables and the factor are refreshed on the live context (dots_move_vertices), the
+    tree and the plan stay.  Not over ``solver_socp_many``, the cascades, time slabs or changed connectivity."""
 
     def __init__(self, n_time, geometry, **solver_options):
         unknown = set(solver_options) - set(SESSION_KEYS)
@@ -1081,7 +1099,20 @@ class SolveSession:
             out.append(a)
         return out
 
-    def solve(self, mu0, mu1, warm=True, outputs=None, read_out=None, flow_map=None, sensitivity=None, **per_solve):
+    def _moved(self, vertices):
+        """``vertices`` as the session takes them: a device tensor as it is, anything else as a finite (V, 3) float64 array."""
+        if _is_device_tensor(vertices):
+            if tuple(vertices.shape) != (self.n_vertices, 3):
+                raise ValueError(f"SolveSession.solve: vertices must have shape ({self.n_vertices}, 3), got {tuple(vertices.shape)}")
+            return vertices
+        a = np.asarray(vertices.detach().cpu().numpy() if type(vertices).__module__.startswith("torch") else vertices, dtype=np.float64)
+        if a.shape != (self.n_vertices, 3):
+            raise ValueError(f"SolveSession.solve: vertices must have shape ({self.n_vertices}, 3), got {a.shape}")
+        if not np.all(np.isfinite(a)):
+            raise ValueError("SolveSession.solve: vertices has entries that are not finite")
+        return a
+
+    def solve(self, mu0, mu1, warm=True, outputs=None, read_out=None, flow_map=None, sensitivity=None, vertices=None, **per_solve):
         """Solve the problem with the end masses ``mu0`` / ``mu1`` (V,): returns ``(solution, run_history)`` as ``solver_socp(n_time,
         {**geometry, "mu0": mu0, "mu1": mu1}, **solver_options)`` does -- with ``warm=False`` bit for bit.  ``warm=True`` (the default)
         starts from the session's last iterate, rescaled on the device: what ``init_solution=`` the whole previous solution does over
@@ -1090,7 +1121,11 @@ class SolveSession:
         solves.  The masses may be torch tensors on the context's device: from the second solve on they are read there.
         ``run_history.solver_stats["session"]`` = {"index", "warm", "restart_ms" (device milliseconds of the restart; None on the first
         solve), "setup_seconds" (wall time before the first iteration of this solve), "setup_seconds_saved" (the first solve's
-        set-up: what this one did not repeat; 0 on the first)}."""
+        set-up: what this one did not repeat; 0 on the first), "moved", "move_ms"}.
+        ``vertices`` (V, 3): the surface moves before this solve (same triangles): on the first solve they replace the session's, later
+        the live context is moved (``AlmSolver.restart(vertices=)``: tables and factor are refreshed on the device, nothing is planned
+        again); ``session.geometry`` follows.  ``"moved"``: whether this solve moved the surface; ``"move_ms"``: the device
+        milliseconds of the assembly launches, the factor refresh and the whole move, or None."""
         if self.closed:
             raise ValueError("SolveSession.solve: the session is closed")
         unknown = set(per_solve) - set(SESSION_SOLVE_KEYS)
@@ -1103,13 +1138,26 @@ class SolveSession:
         sensitivity = check_sensitivity(sensitivity, congestion=congestion)
         first = self.alm is None
         m0, m1 = self._masses(mu0, mu1, to_host=first)
+        moved = None if vertices is None else self._moved(vertices)
         t0 = time.perf_counter()
+        move_ms = None
         if first:
             self.options.update(per_solve)
+            if moved is not None:
+                from .. import meshes
+
+                x = np.array(moved.detach().cpu().numpy() if _is_device_tensor(moved) else moved, dtype=np.float64)
+                t = np.asarray(self.geometry["triangles"])
+                area_t = meshes.triangle_areas(x, t)
+                self.geometry = {**self.geometry, "vertices": x, "area_triangles": area_t, "area_vertices": meshes.vertex_areas(self.n_vertices, t, area_t)}
             self.alm = AlmSolver(self.n_time, {**self.geometry, "mu0": m0.copy(), "mu1": m1.copy()}, **self.options)
             warm, restart_ms = False, None
         else:
-            restart_ms = self.alm.restart(m0, m1, warm=bool(warm), **per_solve)
+            more = {} if moved is None else {"vertices": moved}      # (without vertices the call is the one a session always made)
+            restart_ms = self.alm.restart(m0, m1, warm=bool(warm), **more, **per_solve)
+            if moved is not None:
+                move_ms = self.alm.move_ms
+                self.geometry = {k: v for k, v in self.alm.geometry.items() if k not in ("mu0", "mu1")}
         setup = time.perf_counter() - t0
         if first:
             self.setup_seconds = setup
@@ -1119,7 +1167,8 @@ class SolveSession:
                 break
         solution, hist = alm.finalize(outputs=outputs, read_out=read_out, flow_map=flow_map, sensitivity=sensitivity)
         hist.solver_stats["session"] = {"index": self.index, "warm": bool(warm), "restart_ms": restart_ms, "setup_seconds": setup,
-                                        "setup_seconds_saved": 0.0 if first else self.setup_seconds}
+                                        "setup_seconds_saved": 0.0 if first else self.setup_seconds,
+                                        "moved": moved is not None, "move_ms": move_ms}
         self.index += 1
         return solution, hist
 

@@ -33,16 +33,22 @@ def _like(array, ref):
 
 class _TransportCost(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, mu0, mu1, vertices, triangles, n_time, options, session=None):
+    def forward(ctx, mu0, mu1, vertices, triangles, n_time, options, session=None, move=False):
         x, tri = _host(vertices), np.asarray(_host(triangles), dtype=np.int64)
         if session is not None:      # the session's live context: the masses change, the mesh must be the session's
             if int(n_time) != session.n_time:
                 raise ValueError(f"transport_cost: n_time = {int(n_time)}, the session's {session.n_time}")
-            if not (np.array_equal(x, np.asarray(session.geometry["vertices"], dtype=np.float64))
-                    and np.array_equal(tri, np.asarray(session.geometry["triangles"], dtype=np.int64))):
+            same_tri = np.array_equal(tri, np.asarray(session.geometry["triangles"], dtype=np.int64))
+            same_x = np.array_equal(x, np.asarray(session.geometry["vertices"], dtype=np.float64))
+            moved = None
+            if move and same_tri and not same_x:      # the session's triangles at other positions: the live context moves
+                if x.shape != np.asarray(session.geometry["vertices"]).shape:
+                    raise ValueError(f"transport_cost: vertices must have the session's shape {np.asarray(session.geometry['vertices']).shape}, got {x.shape}")
+                moved = x
+            elif not (same_x and same_tri):
                 raise ValueError("transport_cost: vertices / triangles are not the session's (a session solves on one mesh; moved "
-                                 "vertices need a new session)")
-            solution, hist = session.solve(mu0.detach(), mu1.detach(), outputs=(), sensitivity=_request(ctx.needs_input_grad), **options)
+                                 "vertices need a new session)" + (": move=True moves the vertices, the triangles must be the session's" if move else ""))
+            solution, hist = session.solve(mu0.detach(), mu1.detach(), outputs=(), sensitivity=_request(ctx.needs_input_grad), vertices=moved, **options)
         else:
             geom, _ = meshes.make_geometry(x, tri, _host(mu0), _host(mu1), normalize=False)      # the geometry as given
             solution, hist = solver_socp(int(n_time), geom, outputs=(), sensitivity=_request(ctx.needs_input_grad), **options)
@@ -55,14 +61,14 @@ class _TransportCost(torch.autograd.Function):
         g0, g1, gx = sensitivity.cost_gradients(ctx.sens, *ctx.mesh)
         grads = [None if a is None or not need else g.to(ref.device, ref.dtype) * _like(a, ref)
                  for a, need, ref in zip((g0, g1, gx), ctx.needs_input_grad[:3], ctx.like)]
-        return (*grads, None, None, None, None)
+        return (*grads, None, None, None, None, None)
 
 
 def _tensor(a):
     return a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, dtype=np.float64))
 
 
-def transport_cost(mu0, mu1, vertices, triangles, n_time, session=None, **solver_options):
+def transport_cost(mu0, mu1, vertices, triangles, n_time, session=None, move=False, **solver_options):
     """The transport cost between the masses ``mu0`` and ``mu1`` (V,) on the mesh (``vertices`` (V, 3), ``triangles`` (F, 3)) with
     ``n_time`` intervals, as a scalar fp64 tensor on ``mu0``'s device, differentiable in ``mu0``, ``mu1`` and ``vertices``.  Forward:
     one ``solver_socp`` call on the geometry as given (``meshes.make_geometry(..., normalize=False)``) with ``solver_options`` (tol,
@@ -72,13 +78,19 @@ def transport_cost(mu0, mu1, vertices, triangles, n_time, session=None, **solver
     ``n_time``: the forward pass is ``session.solve`` on its live context -- no plan, factor or context is built again -- and
     ``solver_options`` are that call's (``warm``, ``tol``, ``nit``, ``time_limit``, ``congestion``); ``vertices`` / ``triangles`` must be
     the session's, by value.  With ``warm=False`` cost and gradients are those of the call without a session, bit for bit; the
-    gradient in ``vertices`` is still the stress of the current geometry."""
+    gradient in ``vertices`` is still the stress of the current geometry.
+    ``move=True`` (with a session): ``vertices`` that differ from the session's by value move its live context
+    (``SolveSession.solve(vertices=)``: tables and factor refreshed on the device; same shape, same triangles); equal positions do not
+    move it.  With ``warm=False`` cost and gradients are those of a new solver on ``geometry.plan_with_vertices`` of the session's
+    plan, bit for bit.  The default keeps the session on its mesh and refuses other positions."""
     for k in ("outputs", "read_out", "flow_map", "sensitivity"):
         if k in solver_options:
             raise ValueError(f"transport_cost: '{k}' is chosen by the function itself")
     if session is None and "warm" in solver_options:
         raise ValueError("transport_cost: 'warm' needs a session (a call without one starts from zero)")
-    return _TransportCost.apply(_tensor(mu0), _tensor(mu1), _tensor(vertices), triangles, n_time, solver_options, session)
+    if session is None and move:
+        raise ValueError("transport_cost: 'move' needs a session (a call without one builds its own solver on the mesh as given)")
+    return _TransportCost.apply(_tensor(mu0), _tensor(mu1), _tensor(vertices), triangles, n_time, solver_options, session, bool(move))
 
 
 class _TransportCosts(torch.autograd.Function):

@@ -878,6 +878,50 @@ typedef struct dots_restart_desc {
 } dots_restart_desc;
 int dots_restart(dots_ctx *ctx, const dots_restart_desc *desc);
 
+/* ---- solve session: moved vertices on a live context ----------------------------------------------------------------------------
+ * dots_move_vertices: the context takes other vertex positions of the SAME triangulation.  Everything that depends on the mesh graph
+ * only is kept (tri, the corner lists, the CSR pattern, the permutations, the time modes, the elimination tree, the band plan, the
+ * sweep schedule and every allocation); every table that depends on the positions is formed again on the device (kernels_geometry.hip:
+ * the formulas of dots_assemble and dots_create in their order of operations, the same bits): hat, area_f, mass_v, c_D, fk_D, c_gA,
+ * c_area, val, kdiag.  The host constants of dots_create (the KKT normalisation constants, norm_d, the vertex masses of norm_boundary's
+ * loop, the hash dots_front_share compares, norm_boundary from the masses the context holds) are formed again from area_f, mass_v and
+ * val downloaded once (about 10 V doubles) in dots_create's loops: a new context's bits for the moved mesh.
+ *   Before the geometry changes a pending penalty division is carried out and z_mid materialised with the OLD geometry, as for
+ *     dots_download; a launch ahead, an armed penalty decision, the carried gathers and the fused sums are dropped.
+ *   A factor the context owns is computed again from K + (sigma_a + eps) M into the allocations it has: the numeric factorisation,
+ *     the merged blocks, the top band's inverse, the leaves' packed inverses and coupling records.  Nothing of the schedule changes.
+ *   The state arrays are left as they are.  The iterate's derived quantities and the parameters belong to a run on the old surface:
+ *     the context requires a dots_restart (cold or warm) before it steps; until then dots_step, dots_step_many, dots_run_phase,
+ *     dots_kkt*, dots_objective* return DOTS_ERR_STATE.  dots_restart then forms norm_boundary from the new vertex masses.
+ *   ms (optional, HOST out [3]): device milliseconds of the assembly launches, of the factor refresh, of the whole call.
+ * DOTS_ERR_ARGUMENT, the context keeping its old geometry, factor and state, fully usable: NULL arguments, a coordinate that is not
+ * finite, a triangle whose area is not positive, a vertex whose mass is not positive (areas and hat gradients are formed in scratch
+ * first; host positions are checked for finiteness on the host).  DOTS_ERR_STATE (untouched as well): a time slab, a factor store that
+ * is shared (a sharer, or an owner with sharers), a multigrid hierarchy installed, a non-modal context, a factor installed from the
+ * caller's values, params.eps other than the factor's.  DOTS_ERR_MEMORY (untouched): the temporaries of the factorisation do not fit.
+ * A pivot that is not positive in the refresh (impossible for valid areas and eps >= 0) releases the factor and returns the
+ * factorisation's error: the context is then a PCG context, as after a failed dots_front_setup. */
+typedef struct dots_move_desc {
+    const double *vertices;      /* [V][3], in the numbering of dots_problem_desc (the device numbering)                        */
+    int32_t device_pointers;     /* 0: a host address; 1: a device address on the context's device                              */
+    int32_t reserved;
+    double *ms;                  /* NULL, or HOST out [3]                                                                       */
+} dots_move_desc;
+int dots_move_vertices(dots_ctx *ctx, const dots_move_desc *desc);
+
+/* dots_geometry_copy: the geometry tables of the context, copied device -> host behind a stream synchronisation (read-only; NULL
+ * members are skipped).  Device numbering; corner_scale and corner_grad_area in corner-list order. */
+typedef struct dots_geometry_tables {
+    double *area_tri;            /* [F]        */
+    double *hat_grad;            /* [F][3][3]  */
+    double *mass_vert;           /* [V]        */
+    double *lap_val;             /* [nnz]      */
+    double *kdiag;               /* [V]        */
+    double *corner_scale;        /* [3F] c_D = sqrt(area / mass) per corner-list entry */
+    double *corner_grad_area;    /* [3F][3] c_gA = hat gradient * area per corner-list entry */
+} dots_geometry_tables;
+int dots_geometry_copy(dots_ctx *ctx, const dots_geometry_tables *out);
+
 /* ---- levels of a cascade in space from ONE mesh: coarsen on the host, locate on the device ------------------------------------
  * dots_coarsen: half-edge-collapse decimation of the mesh (xyz [V][3], tri [F][3]) towards `n_target` vertices, host only (no
  * device work; dots_socp_amd/meshes.py: coarsen(backend="python") is the specification and states the rules; both return the same
