@@ -38,7 +38,7 @@ EXPORTS = [
     "dots_flow_map", "dots_flow_push", "dots_flow_trace", "dots_flow_slide",
     "dots_sensitivity",
     "dots_restart",
-    "dots_move_vertices", "dots_geometry_copy",
+    "dots_move_vertices", "dots_geometry_copy", "dots_move_vertices_many",
 ]
 RESTART_COLD, RESTART_WARM = 0, 1      # dots_restart_desc.mode
 BENCH_RESTART_SCALE = 5                # dots_bench_kernel: the in-place rescaling of dots_restart(WARM), every factor 1
@@ -413,6 +413,7 @@ def load(host_only=False):
     lib.dots_restart.argtypes = [vp, C.POINTER(RestartDesc)]
     lib.dots_move_vertices.argtypes = [vp, C.POINTER(MoveDesc)]
     lib.dots_geometry_copy.argtypes = [vp, C.POINTER(GeometryTables)]
+    lib.dots_move_vertices_many.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(MoveDesc)]
     lib.dots_prolong_space.argtypes = [vp, vp, C.POINTER(ProlongSpaceDesc)]
     lib.dots_transfer_space.argtypes = [vp, vp, C.POINTER(TransferSpaceDesc)]
     lib.dots_carry_spacetime.argtypes = [vp, vp, C.POINTER(CarrySpacetimeDesc)]

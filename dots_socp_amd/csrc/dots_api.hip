@@ -136,6 +136,11 @@ static int build(Ctx *c, const dots_problem_desc *p) {
         mix(p->lap_val, sizeof(double) * (size_t)p->lap_nnz);
         mix(p->mass_vert, sizeof(double) * (size_t)p->n_vertices);
         c->lap_hash = h;
+        h = 1469598103934665603ull;
+        mix(p->triangles, sizeof(int32_t) * 3 * (size_t)p->n_triangles);
+        mix(p->corner_ptr, sizeof(int32_t) * ((size_t)p->n_vertices + 1));
+        mix(p->corner_idx, sizeof(int32_t) * (size_t)p->n_corners);
+        c->tri_hash = h;
     }
     c->lap_solver = p->lap_solver;
 
@@ -1237,6 +1242,7 @@ int dots_front_share(dots_ctx *c, dots_ctx *owner) {
     if ((rc = c->front_own.upload<double>(&w, nullptr, owner->sched.w_rows << c->dcg.tp_shift, c->stream))) { front_release(c); return rc; }
     c->front.W = const_cast<double *>(w);
     c->front_store = owner->front_store;
+    c->front_record = owner->front_record;      // (dots_move_vertices_many refreshes the store from whichever holder is listed first)
     c->use_front = 1;
     return front_carry_alloc(c);
 }
@@ -1627,111 +1633,169 @@ int dots_restart(dots_ctx *c, const dots_restart_desc *desc) {
     return 0;
 }
 
-// ---- dots_move_vertices: other vertex positions on a live context (include/dots_socp_hip.h) ------------------------------------------
-int dots_move_vertices(dots_ctx *c, const dots_move_desc *desc) {
-    if (!c || !desc || !desc->vertices) { set_error("move_vertices: null argument"); return DOTS_ERR_ARGUMENT; }
-    if (c->shard_stride != 0) { set_error("move_vertices: not available on a time slab"); return DOTS_ERR_STATE; }
-    if (c->lap_solver != DOTS_LAP_MODAL_PCG) { set_error("move_vertices: the context is not modal (DOTS_LAP_MODAL_PCG)"); return DOTS_ERR_STATE; }
-    if (c->mg.nlev >= 2) { set_error("move_vertices: a multigrid hierarchy is installed (its coarse operators belong to the old surface)"); return DOTS_ERR_STATE; }
-    if (c->front_store && c->front_store.use_count() > 1) {
+// ---- dots_move_vertices, dots_move_vertices_many: other vertex positions on live contexts (include/dots_socp_hip.h) -----------------
+// cs[0 .. n) move together.  Every check runs for every member before any member changes; the positions are validated once, into the
+// scratch of cs[0]; then each member does on its own stream what a move does to one context, all take the host constants of one
+// download, and the factor they hold is refreshed once, on cs[0]'s stream, with every stream idle before and after.  `many`: the list
+// is the caller's (dots_move_vertices_many) and must be the whole set of holders of the store; otherwise cs is one context, which
+// must hold its store alone.
+static int move_holders(dots_ctx *const *cs, int n, const dots_move_desc *desc, bool many) {
+    dots_ctx *c0 = cs[0];
+    const int V = c0->d.V, F = c0->d.F, nnz = c0->nnz;
+    for (int k = 0; k < n; ++k) {
+        const Ctx *c = cs[k];
+        if (c->shard_stride != 0) { set_error("move_vertices: not available on a time slab"); return DOTS_ERR_STATE; }
+        if (c->lap_solver != DOTS_LAP_MODAL_PCG) { set_error("move_vertices: the context is not modal (DOTS_LAP_MODAL_PCG)"); return DOTS_ERR_STATE; }
+        if (c->mg.nlev >= 2) { set_error("move_vertices: a multigrid hierarchy is installed (its coarse operators belong to the old surface)"); return DOTS_ERR_STATE; }
+    }
+    if (!many && c0->front_store && c0->front_store.use_count() > 1) {
         set_error("move_vertices: the factor store is shared (dots_front_share): a sharer cannot move it, and an owner not under its sharers");
         return DOTS_ERR_STATE;
     }
+    if (many) {
+        bool whole = c0->front_store ? (long)n == c0->front_store.use_count() : n == 1;
+        for (int k = 1; k < n; ++k) {
+            whole = whole && cs[k]->front_store == c0->front_store;
+            for (int j = 0; j < k; ++j) whole = whole && cs[j] != cs[k];
+        }
+        if (!whole) {
+            set_error("move_vertices_many: the list is not the set of holders of one factor store (every context that shares it, each once)");
+            return DOTS_ERR_STATE;
+        }
+        // (one store: one mesh, Laplacian and vertex numbering, dots_front_share; the scratch of cs[0] also serves the triangle tables of all)
+        for (int k = 1; k < n; ++k)
+            if (cs[k]->tri_hash != c0->tri_hash || cs[k]->d.F != F) {
+                set_error("move_vertices_many: the members number their triangles or corner lists differently");
+                return DOTS_ERR_STATE;
+            }
+    }
     const bool on_device = desc->device_pointers != 0;
-    const int V = c->d.V, F = c->d.F, nnz = c->nnz;
     if (!on_device)
         for (int64_t i = 0; i < (int64_t)3 * V; ++i)
             if (!std::isfinite(desc->vertices[i])) { set_error("move_vertices: a coordinate that is not finite"); return DOTS_ERR_ARGUMENT; }
-    hipError_t e0 = hipSetDevice(c->device);
+    hipError_t e0 = hipSetDevice(c0->device);
     if (e0 != hipSuccess) return hip_fail(e0, "hipSetDevice", __FILE__, __LINE__);
-    int rc = front_refresh_check(c);
-    if (rc) return rc;
+    int rc;
     // scratch in the staging buffer: [area F | hat 9 F | mass V | flag | xyz 3 V], every part on a 16-byte boundary
     auto even = [](int64_t n) { return (n + 1) & ~(int64_t)1; };
     const int64_t o_hat = even(F), o_mass = o_hat + even((int64_t)9 * F), o_flag = o_mass + even(V), o_xyz = o_flag + 2, total = o_xyz + (int64_t)3 * V;
-    if (total > c->stage_count) { set_error("move_vertices: the scratch tables do not fit the staging buffer on this mesh"); return DOTS_ERR_STATE; }
+    for (int k = 0; k < n; ++k) {
+        if ((rc = front_refresh_check(cs[k]))) return rc;
+        if (total > cs[k]->stage_count) { set_error("move_vertices: the scratch tables do not fit the staging buffer on this mesh"); return DOTS_ERR_STATE; }
+    }
     // what dots_download does before it reads, with the OLD geometry (z_mid is rebuilt from tables that are about to change); the launch
     // ahead, an armed penalty decision, the carried gathers and the fused sums go (check)
-    if ((rc = check(c)) || (rc = materialise_zmid(c))) return rc;
-    Dev &d = c->d;
-    GeomScratch s{c->stage, c->stage + o_hat, c->stage + o_mass, reinterpret_cast<int *>(c->stage + o_flag)};
+    for (int k = 0; k < n; ++k)
+        if ((rc = check(cs[k])) || (rc = materialise_zmid(cs[k]))) return rc;
+    GeomScratch s{c0->stage, c0->stage + o_hat, c0->stage + o_mass, reinterpret_cast<int *>(c0->stage + o_flag)};
     const double *xyz = desc->vertices;
     if (!on_device) {
-        DOTS_HIP(hipMemcpyAsync(c->stage + o_xyz, desc->vertices, sizeof(double) * (size_t)3 * V, hipMemcpyHostToDevice, c->stream));
-        xyz = c->stage + o_xyz;
+        DOTS_HIP(hipMemcpyAsync(c0->stage + o_xyz, desc->vertices, sizeof(double) * (size_t)3 * V, hipMemcpyHostToDevice, c0->stream));
+        xyz = c0->stage + o_xyz;
     }
-    DOTS_HIP(hipEventRecord(c->ev[0], c->stream));
-    if ((rc = launch_geometry_validate(c, xyz, s))) return rc;
-    DOTS_HIP(hipEventRecord(c->ev[1], c->stream));
+    DOTS_HIP(hipEventRecord(c0->ev[0], c0->stream));
+    if ((rc = launch_geometry_validate(c0, xyz, s))) return rc;
+    DOTS_HIP(hipEventRecord(c0->ev[1], c0->stream));
     int flag = 0;
-    DOTS_HIP(hipMemcpyAsync(&flag, s.flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    DOTS_HIP(hipStreamSynchronize(c->stream));      // (host positions are borrowed for the call only)
+    DOTS_HIP(hipMemcpyAsync(&flag, s.flag, sizeof(int), hipMemcpyDeviceToHost, c0->stream));
+    DOTS_HIP(hipStreamSynchronize(c0->stream));      // (host positions are borrowed for the call only)
     if (flag) {
         set_error("move_vertices: a coordinate that is not finite, a triangle whose area is not positive or a vertex whose mass is not positive; the context keeps its geometry");
         return DOTS_ERR_ARGUMENT;
     }
-    // from here on the context is on the new surface
-    DOTS_HIP(hipEventRecord(c->ev[2], c->stream));
-    if ((rc = launch_geometry_commit(c, s))) return rc;
-    DOTS_HIP(hipEventRecord(c->ev[3], c->stream));
-    c->needs_restart = 1;
-    c->kkt_halo_fresh = 0;
-    // the host constants of build(): its sequential sums over the tables, downloaded once
-    std::vector<double> area((size_t)F), val((size_t)nnz), mu0((size_t)V), mu1((size_t)V);
-    auto mass = std::make_shared<std::vector<double>>((size_t)V);
-    DOTS_HIP(hipMemcpyAsync(area.data(), d.area_f, sizeof(double) * (size_t)F, hipMemcpyDeviceToHost, c->stream));
-    DOTS_HIP(hipMemcpyAsync(mass->data(), d.mass_v, sizeof(double) * (size_t)V, hipMemcpyDeviceToHost, c->stream));
-    DOTS_HIP(hipMemcpyAsync(val.data(), d.val, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToHost, c->stream));
-    DOTS_HIP(hipMemcpyAsync(mu0.data(), d.mu0, sizeof(double) * (size_t)V, hipMemcpyDeviceToHost, c->stream));
-    DOTS_HIP(hipMemcpyAsync(mu1.data(), d.mu1, sizeof(double) * (size_t)V, hipMemcpyDeviceToHost, c->stream));
-    DOTS_HIP(hipStreamSynchronize(c->stream));
-    c->d2h_bytes += (int64_t)sizeof(double) * ((int64_t)F + 3 * (int64_t)V + nnz);
+    // from here on the contexts are on the new surface: each member's tables from the one scratch (complete: the host has waited for
+    // it), behind the flush on its own stream; the host constants of build(), its sequential sums over the tables, from one download
+    std::vector<double> area((size_t)F), val((size_t)nnz);
+    std::vector<std::vector<double>> mu((size_t)2 * n, std::vector<double>((size_t)V));
+    auto mass = std::make_shared<std::vector<double>>((size_t)V);      // (a new vector: whoever shares the old one keeps it)
+    for (int k = 0; k < n; ++k) {
+        dots_ctx *c = cs[k];
+        const Dev &d = c->d;
+        DOTS_HIP(hipEventRecord(c->ev[2], c->stream));
+        if ((rc = launch_geometry_commit(c, s))) return rc;
+        DOTS_HIP(hipEventRecord(c->ev[3], c->stream));
+        c->needs_restart = 1;
+        c->kkt_halo_fresh = 0;
+        if (k == 0) {
+            DOTS_HIP(hipMemcpyAsync(area.data(), d.area_f, sizeof(double) * (size_t)F, hipMemcpyDeviceToHost, c->stream));
+            DOTS_HIP(hipMemcpyAsync(mass->data(), d.mass_v, sizeof(double) * (size_t)V, hipMemcpyDeviceToHost, c->stream));
+            DOTS_HIP(hipMemcpyAsync(val.data(), d.val, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToHost, c->stream));
+            c->d2h_bytes += (int64_t)sizeof(double) * ((int64_t)F + (int64_t)V + nnz);
+        }
+        DOTS_HIP(hipMemcpyAsync(mu[(size_t)2 * k].data(), d.mu0, sizeof(double) * (size_t)V, hipMemcpyDeviceToHost, c->stream));
+        DOTS_HIP(hipMemcpyAsync(mu[(size_t)2 * k + 1].data(), d.mu1, sizeof(double) * (size_t)V, hipMemcpyDeviceToHost, c->stream));
+        c->d2h_bytes += (int64_t)sizeof(double) * 2 * (int64_t)V;
+    }
+    for (int k = 0; k < n; ++k) DOTS_HIP(hipStreamSynchronize(cs[k]->stream));      // (no member has anything in flight when the refresh starts)
+    uint64_t h = c0->lap_hash_graph;
     {
-        uint64_t h = c->lap_hash_graph;
         auto mix = [&h](const void *data, size_t bytes) {
             const unsigned char *b = static_cast<const unsigned char *>(data);
             for (size_t i = 0; i < bytes; ++i) h = (h ^ b[i]) * 1099511628211ull;
         };
         mix(val.data(), sizeof(double) * (size_t)nnz);
         mix(mass->data(), sizeof(double) * (size_t)V);
-        c->lap_hash = h;
     }
     double sm = 0.0, sa = 0.0;
     for (int v = 0; v < V; ++v) sm += (*mass)[(size_t)v];
     for (int f = 0; f < F; ++f) sa += area[(size_t)f];
     const double mean_v = sm / V, mean_f = sa / F;
-    c->c_prim_q = 0.5 * (mean_v + mean_f);
-    c->c_prim_z = (mean_v + mean_f + mean_v) / 3.0;
-    c->c_dual_alpha = mean_v;
-    c->c_dual_beta = 0.5 * (mean_v + mean_f);
-    c->c_comp_rho = mean_v;
-    c->c_comp_m = mean_f;
-    c->prm.norm_d = c->norm_d0 = std::sqrt(2.0 * sa);
-    c->mass_host = mass;      // (a new vector: whoever shares the old one keeps it)
-    c->prm.norm_boundary = boundary_norm(boundary_sum(mu0.data(), mu1.data(), mass->data(), V), d.T);
-    // the factor the context owns, from K + (sigma_a + eps) M of the new tables, into the allocations it has
-    DOTS_HIP(hipEventRecord(c->ev[6], c->stream));
-    if (c->front.n_nodes > 0 && (rc = front_refresh(c))) {
-        (void)hipStreamSynchronize(c->stream);
+    for (int k = 0; k < n; ++k) {
+        dots_ctx *c = cs[k];
+        c->lap_hash = h;
+        c->c_prim_q = 0.5 * (mean_v + mean_f);
+        c->c_prim_z = (mean_v + mean_f + mean_v) / 3.0;
+        c->c_dual_alpha = mean_v;
+        c->c_dual_beta = 0.5 * (mean_v + mean_f);
+        c->c_comp_rho = mean_v;
+        c->c_comp_m = mean_f;
+        c->prm.norm_d = c->norm_d0 = std::sqrt(2.0 * sa);
+        c->mass_host = mass;
+        c->prm.norm_boundary = boundary_norm(boundary_sum(mu[(size_t)2 * k].data(), mu[(size_t)2 * k + 1].data(), mass->data(), V), c->d.T);
+    }
+    // the factor the members hold, from K + (sigma_a + eps) M of the new tables, into the allocations it has: once
+    DOTS_HIP(hipEventRecord(c0->ev[6], c0->stream));
+    if (c0->front.n_nodes > 0 && (rc = front_refresh(c0))) {
+        (void)hipStreamSynchronize(c0->stream);
         const std::string why = g_last_error;
-        d.cn_sq = d.cn_g = d.cn_lo = d.cn_e = nullptr;
-        front_release(c);      // (a PCG context from here on, as after a failed dots_front_setup)
+        for (int k = 0; k < n; ++k) {
+            dots_ctx *c = cs[k];
+            c->d.cn_sq = c->d.cn_g = c->d.cn_lo = c->d.cn_e = nullptr;
+            front_release(c);      // (a PCG context from here on, as after a failed dots_front_setup)
+        }
         set_error(why);
         return rc;
     }
-    DOTS_HIP(hipEventRecord(c->ev[7], c->stream));
-    DOTS_HIP(hipStreamSynchronize(c->stream));
+    DOTS_HIP(hipEventRecord(c0->ev[7], c0->stream));
+    for (int k = 0; k < n; ++k) DOTS_HIP(hipStreamSynchronize(cs[k]->stream));
     if (desc->ms) {
-        float a = 0.f, b = 0.f, f = 0.f, w = 0.f;
-        DOTS_HIP(hipEventElapsedTime(&a, c->ev[0], c->ev[1]));
-        DOTS_HIP(hipEventElapsedTime(&b, c->ev[2], c->ev[3]));
-        DOTS_HIP(hipEventElapsedTime(&f, c->ev[6], c->ev[7]));
-        DOTS_HIP(hipEventElapsedTime(&w, c->ev[0], c->ev[7]));
-        desc->ms[0] = (double)a + b;
+        float a = 0.f, f = 0.f, w = 0.f;
+        DOTS_HIP(hipEventElapsedTime(&a, c0->ev[0], c0->ev[1]));
+        DOTS_HIP(hipEventElapsedTime(&f, c0->ev[6], c0->ev[7]));
+        DOTS_HIP(hipEventElapsedTime(&w, c0->ev[0], c0->ev[7]));
+        double assembly = a;
+        for (int k = 0; k < n; ++k) {
+            float b = 0.f;
+            DOTS_HIP(hipEventElapsedTime(&b, cs[k]->ev[2], cs[k]->ev[3]));
+            assembly += b;
+        }
+        desc->ms[0] = assembly;
         desc->ms[1] = f;
         desc->ms[2] = w;
     }
     return 0;
+}
+
+int dots_move_vertices(dots_ctx *c, const dots_move_desc *desc) {
+    if (!c || !desc || !desc->vertices) { set_error("move_vertices: null argument"); return DOTS_ERR_ARGUMENT; }
+    return move_holders(&c, 1, desc, false);
+}
+
+int dots_move_vertices_many(dots_ctx *const *ctxs, int n, const dots_move_desc *desc) {
+    if (!ctxs || n < 1 || !desc || !desc->vertices) { set_error("move_vertices_many: null argument"); return DOTS_ERR_ARGUMENT; }
+    for (int k = 0; k < n; ++k)
+        if (!ctxs[k]) { set_error("move_vertices_many: null context"); return DOTS_ERR_ARGUMENT; }
+    return move_holders(ctxs, n, desc, true);
 }
 
 int dots_geometry_copy(dots_ctx *c, const dots_geometry_tables *out) {

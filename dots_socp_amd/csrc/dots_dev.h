@@ -678,6 +678,7 @@ struct Ctx {
     int front_cap_fault = 0;      // a multi-rhs launch was asked for more right-hand sides than its workgroup shape takes (front_solve_many reports it)
     int64_t front_many_launches = 0, front_many_split = 0;   // sweep launches of the last front_solve_many, those split below their chunk (dots_debug_counter 7, 8)
     uint64_t lap_hash_graph = 0;  // ... its state after rowptr and col (dots_move_vertices goes on from there)
+    uint64_t tri_hash = 0;        // FNV-1a of triangles, corner_ptr and corner_idx: dots_move_vertices_many forms the triangle tables of all members from one scratch
     int needs_restart = 0;        // dots_move_vertices changed the surface under the iterate: dots_restart before the next step
     uint64_t lap_hash = 0;        // FNV-1a of the Laplacian (rowptr, col, val) and the vertex masses: dots_front_share compares it with the owner's
     int batched = 0;              // stepped by dots_step_many since its last dots_step: dots_penalty_ahead is refused

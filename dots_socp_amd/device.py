@@ -561,6 +561,13 @@ class DeviceProblem:
         float64 torch tensor on the context's device (permuted there; the positions come down once, 24 V bytes, for the plan).
         ``self.plan`` becomes ``geometry.plan_with_vertices(self.plan, vertices)`` and ``self.params`` is read again.  Returns the
         device milliseconds of the assembly launches, of the factor refresh and of the whole call."""
+        d, ms, plan, keep = self._move_desc(vertices, device_pointers)
+        _lib.check(self.lib.dots_move_vertices(self._h, C.byref(d)), "dots_move_vertices")
+        return self._moved(plan, ms)
+
+    def _move_desc(self, vertices, device_pointers):
+        """The descriptor of a move to ``vertices`` (permuted into this context's numbering), its ``ms`` array, the moved plan and what
+        keeps the descriptor's memory alive: ``move_vertices`` and ``move_vertices_many``."""
         from .geometry import plan_with_vertices
 
         if self.slab:
@@ -589,7 +596,9 @@ class DeviceProblem:
         d.device_pointers = int(bool(device_pointers))
         ms = (C.c_double * 3)()
         d.ms = C.cast(ms, C.POINTER(C.c_double))
-        _lib.check(self.lib.dots_move_vertices(self._h, C.byref(d)), "dots_move_vertices")
+        return d, ms, plan, keep
+
+    def _moved(self, plan, ms):
         self.plan = plan
         _lib.check(self.lib.dots_get_params(self._h, C.byref(self.params)), "dots_get_params")
         self.move_ms = tuple(float(x) for x in ms)
@@ -1016,6 +1025,23 @@ def step_many(problems, stats=False):
     st = _lib.StepStats() if stats else None
     _lib.check(problems[0].lib.dots_step_many(hs, len(problems), C.byref(st) if stats else None), "dots_step_many")
     return st
+
+
+def move_vertices_many(problems, vertices, device_pointers=False):
+    """Move the vertices of every problem to ``vertices`` (V, 3), caller's numbering (dots_move_vertices_many).  ``problems`` are ALL
+    the holders of one factor (``DeviceProblem.share_frontal``), built on one plan up to the densities: every member's geometry tables
+    are assembled again, the factor is computed again ONCE into the allocations it has, and each member then needs ``restart``
+    before it steps.  ``vertices`` as for ``DeviceProblem.move_vertices``.  Every member's ``plan`` becomes the moved plan with its
+    own densities and its ``params`` are read again.  Returns the device milliseconds of the assembly launches (summed over the
+    members), of the one factor refresh and of the whole call, which is also every member's ``move_ms``."""
+    import dataclasses
+
+    problems, hs = _handles(problems)
+    d, ms, plan, keep = problems[0]._move_desc(vertices, device_pointers)
+    _lib.check(problems[0].lib.dots_move_vertices_many(hs, len(problems), C.byref(d)), "dots_move_vertices_many")
+    for p in problems:
+        out = p._moved(plan if p is problems[0] else dataclasses.replace(plan, mu0=p.plan.mu0, mu1=p.plan.mu1), ms)
+    return out
 
 
 def bench_many(problems, reps=20):

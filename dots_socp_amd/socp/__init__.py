@@ -33,10 +33,10 @@ not with congestion.
 import numpy as np
 
 from ..sensitivity import check_sensitivity
-from .solver_socp import (SolveSession, check_flow_map, solver_socp, solver_socp_auto_cascade, solver_socp_cascade, solver_socp_many,
+from .solver_socp import (BatchSession, SolveSession, check_flow_map, solver_socp, solver_socp_auto_cascade, solver_socp_cascade, solver_socp_many,
                           solver_socp_mesh_cascade, solver_socp_spacetime_cascade)
 
-__all__ = ["solver_socp", "solver_raw", "solver", "solver_socp_many", "solver_raw_many", "solver_many", "SolveSession",
+__all__ = ["solver_socp", "solver_raw", "solver", "solver_socp_many", "solver_raw_many", "solver_many", "SolveSession", "BatchSession",
            "solver_socp_cascade", "solver_raw_cascade", "solver_cascade",
            "solver_socp_mesh_cascade", "solver_raw_mesh_cascade", "solver_mesh_cascade",
            "solver_socp_spacetime_cascade", "solver_raw_spacetime_cascade", "solver_spacetime_cascade",

@@ -887,7 +887,24 @@ class AlmSolver:
         self.closed = True
         self.dev.close()
 
-    def restart(self, mu0, mu1, warm=True, nit=None, tol=None, tol_checkpoints=None, time_limit=None, congestion=None, vertices=None):
+    def _warm_refusal(self):
+        """Why this solver's iterate cannot be a warm start, or None."""
+        if self.counter_main >= 0 and getattr(self, "_last_quiet", False) and not self.is_palm:
+            return ("restart: the last iteration stored no z_mid (nothing was read back after it): a warm restart needs the "
+                    "whole iterate; iterate to a read-back or restart cold")
+        return None
+
+    def _geometry_moved(self, moved):
+        """``self.geometry`` after the context's vertices moved to ``moved`` (V, 3), a host array: positions and areas follow."""
+        from .. import meshes
+
+        t = np.asarray(self.geometry["triangles"])
+        area_t = meshes.triangle_areas(moved, t)
+        self.geometry = {**self.geometry, "vertices": moved, "area_triangles": area_t,
+                         "area_vertices": meshes.vertex_areas(moved.shape[0], t, area_t)}
+
+    def restart(self, mu0, mu1, warm=True, nit=None, tol=None, tol_checkpoints=None, time_limit=None, congestion=None, vertices=None, *,
+                batch_member=False):
         """The next problem of a solve session on the live context: other end masses ``mu0`` / ``mu1`` (V,) on the same surface
         (DeviceProblem.restart: dots_restart).  The factor, the hierarchy and the plan are kept; the run starts as a new solver's does
         (r = 1, the initial z scaling, a fresh penalty schedule, validator and history).  ``warm=True``: from the recovered iterate
@@ -900,7 +917,10 @@ class AlmSolver:
         ``vertices`` (V, 3): the surface moves first (DeviceProblem.move_vertices: dots_move_vertices) -- same triangles, other
         positions; the geometry tables are assembled and the factor is computed again on the device, the tree and the plan stay --
         and the run then starts on the moved surface: what a new solver on ``geometry.plan_with_vertices(plan, vertices)`` computes,
-        bit for bit.  ``self.geometry`` follows (vertices, areas); ``self.move_ms``: the three times of the move, or None."""
+        bit for bit.  ``self.geometry`` follows (vertices, areas); ``self.move_ms``: the three times of the move, or None.
+        ``batch_member``: the route of ``BatchSession`` to a solver that is stepped by a batch (dots_restart takes a sharer of a
+        factor: only this context's state changes); such a solver is moved by its session, with all holders of the factor
+        (``device.move_vertices_many``), never through ``vertices``."""
         tol = self.tol if tol is None else tol
         checkpoints = _validate_checkpoints(tol_checkpoints, tol)
         if getattr(self, "closed", False):
@@ -909,8 +929,10 @@ class AlmSolver:
             raise ValueError("restart: not available on time slabs")
         if getattr(self, "_init_from", False):
             raise ValueError("restart: the solver was started from init_from (a level of a cascade); sessions over the cascades are not supported")
-        if self.batched:
+        if self.batched and not batch_member:
             raise ValueError("restart: the solver is stepped by a batch (solver_socp_many); sessions over batches are not supported")
+        if batch_member and vertices is not None:
+            raise ValueError("restart: a member of a batch moves with all holders of its factor (BatchSession.solve_many(vertices=))")
         V = int(np.asarray(self.geometry["vertices"]).shape[0])
         on_device = all(type(a).__module__.startswith("torch") and getattr(a, "is_cuda", False) for a in (mu0, mu1))
         masses = []
@@ -922,22 +944,17 @@ class AlmSolver:
             if tuple(a.shape) != (V,):
                 raise ValueError(f"restart: {name} must have shape ({V},), got {tuple(a.shape)}")
             masses.append(a)
-        if warm and self.counter_main >= 0 and getattr(self, "_last_quiet", False) and not self.is_palm:
-            raise ValueError("restart: the last iteration stored no z_mid (nothing was read back after it): a warm restart needs the "
-                             "whole iterate; iterate to a read-back or restart cold")
+        if warm and self._warm_refusal():
+            raise ValueError(self._warm_refusal())
         factors = self.recovery_factors() if warm else None
-        self.move_ms = None
+        if not batch_member:      # (a member's session has moved it, or not, and booked the times)
+            self.move_ms = None
         if vertices is not None:
             moved_on_device = _is_device_tensor(vertices)
             if not moved_on_device and type(vertices).__module__.startswith("torch"):
                 vertices = vertices.detach().cpu().numpy()
             self.move_ms = self.dev.move_vertices(vertices, device_pointers=moved_on_device)
-            from .. import meshes
-
-            moved = np.array(vertices.detach().cpu().numpy() if moved_on_device else vertices, dtype=np.float64)
-            t = np.asarray(self.geometry["triangles"])
-            area_t = meshes.triangle_areas(moved, t)
-            self.geometry = {**self.geometry, "vertices": moved, "area_triangles": area_t, "area_vertices": meshes.vertex_areas(V, t, area_t)}
+            self._geometry_moved(np.array(vertices.detach().cpu().numpy() if moved_on_device else vertices, dtype=np.float64))
         ms = self.dev.restart(masses[0], masses[1], "warm" if warm else "cold", factors, device_pointers=on_device)
         if on_device:      # (the plan's host copies, back in the caller's numbering: read_out and flow_map take the end masses from the geometry)
             order = self._caller_order()
@@ -1054,7 +1071,8 @@ class SolveSession:
     (``AlmSolver.restart``: dots_restart): nothing is rebuilt, and nothing but what the caller asks for crosses to the host.
     ``close()`` (or leaving the ``with`` block) releases the context.  Moved vertices -- the same triangles at other positions -- are
     taken by ``solve(..., vertices=)``: the geometry tables and the factor are refreshed on the live context (dots_move_vertices), the
-    tree and the plan stay.  Not over ``solver_socp_many``, the cascades, time slabs or changed connectivity."""
+    tree and the plan stay.  Batches (``solver_socp_many``) have ``BatchSession``; not over the cascades, time slabs or changed
+    connectivity."""
 
     def __init__(self, n_time, geometry, **solver_options):
         unknown = set(solver_options) - set(SESSION_KEYS)
@@ -1181,6 +1199,24 @@ BATCH_TIME_NOTE = ("phase times of a batched iteration are the batch's, booked t
                    "(n = members in that iteration)")
 
 
+def _batch_solver_options(common):
+    """The keywords every solver of a batch is built with, from the options given once (``COMMON_KEYS``)."""
+    reorder = common.get("reorder", True)
+    return dict(eps=common.get("eps", 0.0), lap_solver="modal_direct", device=common.get("device", 0), reorder="nd" if reorder is True else reorder,
+                cg_tol=common.get("cg_tol", DEFAULT_CG_TOL), cg_max_iter=common.get("cg_max_iter", 20000), nd_leaf=common.get("nd_leaf", 16))
+
+
+def _needs_shared_factor(who, alm):
+    """The first solver of a batch must hold the direct solver's factor: one that fell back to the PCG is closed and the memory error raised."""
+    if alm.direct:
+        return
+    reason = alm.lap_solver_fallback
+    alm.close()
+    err = _lib.HipLibraryError(f"{who}: the shared factor does not fit (no batched PCG): {reason}")
+    err.status = _lib.ERR_MEMORY
+    raise err
+
+
 def _batch_problems(geometry, problems, common):
     """The checks of solver_socp_many, before any device is touched."""
     if "pcg_windows" in common:
@@ -1217,7 +1253,7 @@ def _batch_problems(geometry, problems, common):
     return out
 
 
-def solver_socp_many(n_time, geometry, problems, *, max_batch=4, read_out=None, flow_map=None, sensitivity=None, outputs=None, **common):
+def solver_socp_many(n_time, geometry, problems, *, max_batch=4, read_out=None, flow_map=None, sensitivity=None, outputs=None, plan=None, **common):
     """Solve several transport problems on ONE surface with one factor of the direct solver.
 
     ``geometry`` holds the mesh (``vertices``, ``triangles``; ``mu0`` / ``mu1`` are defaults for problems without their own);
@@ -1231,9 +1267,10 @@ def solver_socp_many(n_time, geometry, problems, *, max_batch=4, read_out=None, 
     **common, **problem)`` returns, bit for bit; ``run_history.solver_stats["batch"]`` = {"size", "index", "max_batch", "steps_time_note"}.
     Each problem's running time and time limit start when it is admitted.  A factor that does not fit raises the library's memory error
     (there is no batched PCG).  ``read_out``, ``flow_map`` and ``sensitivity``: as for ``solver_socp``, for every problem (with its own
-    mu0 / mu1 and congestion); so is ``outputs`` (the arrays that are downloaded; exclusive with ``read_out``)."""
+    mu0 / mu1 and congestion); so is ``outputs`` (the arrays that are downloaded; exclusive with ``read_out``).  ``plan``: the device
+    plan of this mesh to number it by (``geometry.build_plan``, ``geometry.plan_with_vertices``) instead of building one: the nested
+    dissection reads the positions, so a mesh that moved keeps the numbering of a live context only through its plan."""
     from .. import geometry as geo
-    from ..device import step_many
 
     if read_out is not None and outputs is not None:
         raise ValueError("solver_socp_many: outputs and read_out are mutually exclusive (read_out returns mu and E only)")
@@ -1243,13 +1280,13 @@ def solver_socp_many(n_time, geometry, problems, *, max_batch=4, read_out=None, 
         sensitivity = check_sensitivity(sensitivity, congestion=p.get("congestion", 0.0))
     if int(max_batch) < 1:
         raise ValueError("solver_socp_many: max_batch >= 1")
-    reorder = common.get("reorder", True)
-    reorder = "nd" if reorder is True else reorder
-    nd_leaf = common.get("nd_leaf", 16)
-    solver_kw = dict(eps=common.get("eps", 0.0), lap_solver="modal_direct", device=common.get("device", 0), reorder=reorder,
-                     cg_tol=common.get("cg_tol", DEFAULT_CG_TOL), cg_max_iter=common.get("cg_max_iter", 20000), nd_leaf=nd_leaf)
+    solver_kw = _batch_solver_options(common)
+    if plan is not None and (plan.n_time != int(n_time) or plan.n_vertices != np.asarray(geometry["vertices"]).shape[0]
+                             or plan.n_triangles != np.asarray(geometry["triangles"]).shape[0]):
+        raise ValueError("solver_socp_many: plan is not a plan of this mesh and n_time")
     mesh = {k: v for k, v in geometry.items() if k not in ("mu0", "mu1")}
-    base = geo.build_plan(n_time, {**mesh, "mu0": probs[0]["mu0"], "mu1": probs[0]["mu1"]}, reorder=reorder, nd_leaf=nd_leaf)
+    base = plan if plan is not None else geo.build_plan(n_time, {**mesh, "mu0": probs[0]["mu0"], "mu1": probs[0]["mu1"]},
+                                                        reorder=solver_kw["reorder"], nd_leaf=solver_kw["nd_leaf"])
     results = [None] * len(probs)
     pending = list(range(len(probs)))
     active, done = [], []          # (index, AlmSolver)
@@ -1260,12 +1297,8 @@ def solver_socp_many(n_time, geometry, problems, *, max_batch=4, read_out=None, 
         opts = {k: v for k, v in p.items() if k not in ("mu0", "mu1")}
         alm = AlmSolver(n_time, {**mesh, "mu0": p["mu0"], "mu1": p["mu1"]}, plan=geo.plan_with_densities(base, p["mu0"], p["mu1"]),
                         front_owner=owner_dev, **solver_kw, **opts)
-        if owner_dev is None and not alm.direct:      # (the direct solver could not be installed)
-            reason = alm.lap_solver_fallback
-            alm.close()
-            err = _lib.HipLibraryError(f"solver_socp_many: the shared factor does not fit (no batched PCG): {reason}")
-            err.status = _lib.ERR_MEMORY
-            raise err
+        if owner_dev is None:
+            _needs_shared_factor("solver_socp_many", alm)
         active.append((i, alm))
 
     try:
@@ -1277,23 +1310,7 @@ def solver_socp_many(n_time, geometry, problems, *, max_batch=4, read_out=None, 
             for i, alm in done:
                 alm.close()
             done = []
-            members = []
-            for i, alm in active:
-                quiet = alm.iterate_begin()
-                if quiet is not None:
-                    members.append((i, alm, quiet))
-            if members:
-                booked = [(alm, alm.batch_step_prepare(quiet)) for _, alm, quiet in members]
-                sampled = any(s for _, (_, s) in booked)
-                st = step_many([alm.dev for _, alm, _ in members], stats=sampled)
-                n = len(members)
-                for alm, (kind, sample) in booked:
-                    if sample and st is not None:
-                        alm._account(_BatchShare(st, n), kind)
-                    else:
-                        alm.untimed_steps += 1
-                for _, alm, _ in members:
-                    alm.iterate_end()
+            _lockstep([alm for _, alm in active], int(max_batch))
             still = []
             for i, alm in active:
                 if alm.finished:
@@ -1310,6 +1327,31 @@ def solver_socp_many(n_time, geometry, problems, *, max_batch=4, read_out=None, 
     return results
 
 
+def _lockstep(solvers, max_batch):
+    """One ALM iteration of every solver of ``solvers`` (holders of one factor) that still runs: those that step, in groups of at most
+    ``max_batch`` in the order given, each group with ONE batched pair of sweeps (device.step_many)."""
+    from ..device import step_many
+
+    members = []
+    for alm in solvers:
+        quiet = alm.iterate_begin()
+        if quiet is not None:
+            members.append((alm, quiet))
+    for at in range(0, len(members), max_batch):
+        group = members[at:at + max_batch]
+        booked = [(alm, alm.batch_step_prepare(quiet)) for alm, quiet in group]
+        sampled = any(s for _, (_, s) in booked)
+        st = step_many([alm.dev for alm, _ in group], stats=sampled)
+        n = len(group)
+        for alm, (kind, sample) in booked:
+            if sample and st is not None:
+                alm._account(_BatchShare(st, n), kind)
+            else:
+                alm.untimed_steps += 1
+        for alm, _ in group:
+            alm.iterate_end()
+
+
 class _BatchShare:
     """1/n of a batch's phase times, in the form AlmSolver._account reads"""
 
@@ -1320,6 +1362,223 @@ class _BatchShare:
         self.ms_laplacian = st.ms_laplacian / n
         self.ms_soc = st.ms_soc / n
         self.ms_q_lambda_multiplier = st.ms_q_lambda_multiplier / n
+
+
+# ---- a sequence of batches on one surface: live contexts on one shared factor ------------------------------------------------------
+BATCH_SESSION_FIXED = ("tau", "is_palm", "is_z_scaling", "is_constant_scaling", "check_kkt_step_by_step")      # per problem in solver_socp_many; a restart cannot change them
+BATCH_SOLVE_DEFAULTS = {"nit": 1000, "tol": 1e-4, "tol_checkpoints": None, "time_limit": 1000, "congestion": 0.0}      # SESSION_SOLVE_KEYS as a new AlmSolver has them
+
+
+class BatchSession:
+    """Live device contexts on ONE shared factor for a sequence of batches of transport problems on one surface, whose end masses --
+    and vertex positions -- change from call to call: ``with BatchSession(n_time, geometry, max_batch=4) as bs: results =
+    bs.solve_many(problems)``.  What ``solver_socp_many`` is to ``solver_socp``, this is to ``SolveSession``.
+
+    ``geometry``: the mesh (``vertices``, ``triangles``; ``mu0`` / ``mu1`` in it are defaults for problems without their own).
+    ``options``: the keywords ``solver_socp_many`` takes once (``COMMON_KEYS``) and the solver options a restart cannot change
+    (``BATCH_SESSION_FIXED``: tau, is_palm, is_z_scaling, is_constant_scaling, check_kkt_step_by_step), fixed for the session.
+    ``slots`` (default ``max_batch``, at least ``max_batch``): the live contexts the session keeps, created when first needed; each
+    holds the state of the problem it solved last.  At most ``max_batch`` of them share one ``device.step_many`` call; with more slots
+    the running members are stepped in groups of ``max_batch``, in slot order.  Memory: ``slots`` times the state of one context
+    plus ONE factor.  ``close()`` (or leaving the ``with`` block) releases every context; the factor goes with the last."""
+
+    def __init__(self, n_time, geometry, max_batch=4, slots=None, **options):
+        if "pcg_windows" in options:
+            raise ValueError(PCG_WINDOWS_ONE_SOLVER.format(who="BatchSession"))
+        unknown = set(options) - set(COMMON_KEYS) - set(BATCH_SESSION_FIXED)
+        if unknown:
+            raise ValueError(f"BatchSession: unknown option(s) {sorted(unknown)}; known: {list(COMMON_KEYS + BATCH_SESSION_FIXED)}")
+        if options.get("lap_solver", "modal_direct") != "modal_direct":
+            raise ValueError("BatchSession: the batch shares the factor of the direct solver: lap_solver must be 'modal_direct'")
+        if not isinstance(geometry, dict) or "vertices" not in geometry or "triangles" not in geometry:
+            raise ValueError("BatchSession: geometry must be a dict with 'vertices' and 'triangles'")
+        if int(max_batch) < 1:
+            raise ValueError("BatchSession: max_batch >= 1")
+        slots = int(max_batch) if slots is None else int(slots)
+        if slots < int(max_batch):
+            raise ValueError(f"BatchSession: slots = {slots} < max_batch = {int(max_batch)}: a lockstep group needs a context per member")
+        check_time_nodes(n_time, "modal_direct")
+        self.n_time, self.max_batch = int(n_time), int(max_batch)
+        self.solver_kw = {**_batch_solver_options(options), **{k: options[k] for k in BATCH_SESSION_FIXED if k in options}}
+        self.geometry = {k: v for k, v in geometry.items() if k not in ("mu0", "mu1")}
+        self.default_masses = {k: geometry[k] for k in ("mu0", "mu1") if k in geometry}
+        self.n_vertices = int(np.asarray(geometry["vertices"]).shape[0])
+        self.solvers = [None] * slots   # AlmSolver per slot, or None: not created yet
+        self.solved = [False] * slots   # the slot's context holds the iterate of a finished solve
+        self.base = None                # the plan every context is built on, up to the densities; follows the moves
+        self.index = 0                  # problems admitted so far
+        self.setup_seconds = None       # of the first context: plan, factor, context
+        self.closed = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        self.closed = True
+        for alm in self.solvers:
+            if alm is not None:
+                alm.close()
+
+    def _problems(self, problems):
+        """The checks of ``solve_many`` on its problems, before any device is touched: dicts with host masses and every key of
+        ``SESSION_SOLVE_KEYS`` (a problem describes its run completely: what it leaves out is a new solver's default)."""
+        if not problems:
+            raise ValueError("BatchSession.solve_many: no problems")
+        out = []
+        for i, p in enumerate(problems):
+            p = dict(p)
+            for k in p:
+                if k in BATCH_SESSION_FIXED or k in COMMON_KEYS:
+                    raise ValueError(f"BatchSession.solve_many: '{k}' is fixed for the session: give it to BatchSession, not per problem ({i})")
+                if k == "init_solution":
+                    raise ValueError(f"BatchSession.solve_many: problem {i}: no init_solution: a slot starts from zero or, with warm=True, from its own last iterate")
+                if k not in ("mu0", "mu1") + SESSION_SOLVE_KEYS:
+                    raise ValueError(f"BatchSession.solve_many: unknown per-problem option '{k}' (problem {i}); known: {list(('mu0', 'mu1') + SESSION_SOLVE_KEYS)}")
+            for k in ("mu0", "mu1"):
+                a = p.get(k)
+                if a is None:
+                    if k not in self.default_masses:
+                        raise ValueError(f"BatchSession.solve_many: problem {i} has no {k}")
+                    a = self.default_masses[k]
+                a = np.asarray(a.detach().cpu().numpy() if type(a).__module__.startswith("torch") else a, dtype=np.float64)
+                if a.shape != (self.n_vertices,):
+                    raise ValueError(f"BatchSession.solve_many: problem {i}: {k} must have shape ({self.n_vertices},), got {a.shape}")
+                if not np.all(np.isfinite(a)):
+                    raise ValueError(f"BatchSession.solve_many: problem {i}: {k} has entries that are not finite")
+                p[k] = a
+            p = {**BATCH_SOLVE_DEFAULTS, **p}
+            _validate_checkpoints(p["tol_checkpoints"], p["tol"])
+            if int(p["nit"]) < 1:
+                raise ValueError(f"BatchSession.solve_many: problem {i}: nit must be at least 1")
+            out.append(p)
+        return out
+
+    def _moved(self, vertices):
+        """``vertices`` as the session takes them: ``(what the device call reads, the host array)``."""
+        on_device = _is_device_tensor(vertices)
+        shape = tuple(vertices.shape) if on_device else None
+        host = np.asarray(vertices.detach().cpu().numpy() if type(vertices).__module__.startswith("torch") else vertices, dtype=np.float64)
+        if (shape or host.shape) != (self.n_vertices, 3):
+            raise ValueError(f"BatchSession.solve_many: vertices must have shape ({self.n_vertices}, 3), got {shape or host.shape}")
+        if not np.all(np.isfinite(host)):
+            raise ValueError("BatchSession.solve_many: vertices has entries that are not finite")
+        return (vertices if on_device else host), np.array(host)
+
+    def _move(self, moved):
+        """All live contexts to other positions with ONE refresh of the factor (device.move_vertices_many); the session's geometry and
+        plan, and every solver's geometry, follow.  Without a live context the positions replace the session's.  Returns the times."""
+        from ..device import move_vertices_many
+
+        given, host = moved
+        live = [alm for alm in self.solvers if alm is not None]
+        ms = move_vertices_many([alm.dev for alm in live], given, device_pointers=_is_device_tensor(given)) if live else None
+        for alm in live:
+            alm._geometry_moved(host)
+            alm.move_ms = ms
+        if live:
+            self.base = live[0].dev.plan
+            self.geometry = {k: v for k, v in live[0].geometry.items() if k not in ("mu0", "mu1")}
+        else:
+            from .. import meshes
+
+            t = np.asarray(self.geometry["triangles"])
+            area_t = meshes.triangle_areas(host, t)
+            self.geometry = {**self.geometry, "vertices": host, "area_triangles": area_t, "area_vertices": meshes.vertex_areas(self.n_vertices, t, area_t)}
+        return ms
+
+    def _admit(self, slot, p, warm):
+        """Problem ``p`` into ``slot``: a new solver on the session's plan where the slot has no context yet, else a restart of the
+        one it has.  Returns the record ``solver_stats["session"]`` starts from."""
+        from .. import geometry as geo
+
+        t0 = time.perf_counter()
+        run = {k: p[k] for k in SESSION_SOLVE_KEYS}
+        alm, restart_ms = self.solvers[slot], None
+        created = alm is None
+        if created:
+            if self.base is None:
+                self.base = geo.build_plan(self.n_time, {**self.geometry, "mu0": p["mu0"], "mu1": p["mu1"]}, reorder=self.solver_kw["reorder"],
+                                           nd_leaf=self.solver_kw["nd_leaf"])
+            owner = next((a.dev for a in self.solvers if a is not None), None)
+            alm = AlmSolver(self.n_time, {**self.geometry, "mu0": p["mu0"].copy(), "mu1": p["mu1"].copy()},
+                            plan=geo.plan_with_densities(self.base, p["mu0"], p["mu1"]), front_owner=owner, **self.solver_kw, **run)
+            if owner is None:
+                _needs_shared_factor("BatchSession", alm)
+            self.solvers[slot] = alm
+        else:
+            restart_ms = alm.restart(p["mu0"], p["mu1"], warm=warm, batch_member=True, **run)
+        self.solved[slot] = False
+        setup = time.perf_counter() - t0
+        if self.setup_seconds is None:
+            self.setup_seconds = setup
+        record = {"index": self.index, "warm": bool(warm) and not created, "restart_ms": restart_ms, "setup_seconds": setup,
+                  "setup_seconds_saved": 0.0 if created else self.setup_seconds}
+        self.index += 1
+        return record
+
+    def solve_many(self, problems, warm=False, vertices=None, outputs=None, read_out=None, flow_map=None, sensitivity=None):
+        """Solve ``problems`` -- dicts with ``mu0``, ``mu1`` (V,) and any of ``nit``, ``tol``, ``tol_checkpoints``, ``time_limit``,
+        ``congestion`` (what a problem leaves out is a new solver's default, not the slot's last value) -- on the session's contexts.
+        Returns ``[(solution, run_history), ...]`` in input order.
+        ``warm=False``: the problems are admitted into free slots in input order and a slot that finishes takes the next one, as
+        ``solver_socp_many`` does, and with its results bit for bit; a slot that holds a context takes its problem by a cold restart
+        on the device (``AlmSolver.restart``: dots_restart), so from the second call on nothing is built.
+        ``warm=True``: problem ``i`` runs in slot ``i`` from that slot's last iterate -- per problem what
+        ``SolveSession.solve(..., warm=True)`` computes, bit for bit, under ``AlmSolver.restart``'s rules; at most ``slots`` problems, each
+        on a slot that has solved before.
+        ``vertices`` (V, 3; an array or a tensor on the contexts' device): the surface moves before the solves, same triangles: every
+        live context takes the positions and the shared factor is refreshed once (``device.move_vertices_many``); contexts created
+        later are built on the moved plan; ``self.geometry`` follows.  On the first call they replace the session's positions.
+        ``outputs``, ``read_out``, ``flow_map``, ``sensitivity``: as for ``solver_socp_many``.
+        ``run_history.solver_stats["batch"]`` as ``solver_socp_many`` writes it; ``solver_stats["session"]`` = {"index" (problems the
+        session admitted before this one), "warm", "restart_ms" (None where the context was built for this problem), "setup_seconds",
+        "setup_seconds_saved" (the first context's set-up, 0 where one was built), "moved", "move_ms" (of this call's one move, the
+        same in every problem's record)}."""
+        if self.closed:
+            raise ValueError("BatchSession.solve_many: the session is closed")
+        if read_out is not None and outputs is not None:
+            raise ValueError("BatchSession.solve_many: outputs and read_out are mutually exclusive (read_out returns mu and E only)")
+        flow_map = check_flow_map(flow_map, n_time=self.n_time)
+        probs = self._problems(problems)
+        for p in probs:
+            sensitivity = check_sensitivity(sensitivity, congestion=p["congestion"])
+        slots = len(self.solvers)
+        if warm:
+            if len(probs) > slots:
+                raise ValueError(f"BatchSession.solve_many: warm=True runs problem i in slot i: {len(probs)} problems, {slots} slots (problem {slots} has none)")
+            for i in range(len(probs)):
+                if not self.solved[i]:
+                    raise ValueError(f"BatchSession.solve_many: warm=True: slot {i} has not solved a problem yet: problem {i} has no iterate to start from")
+                refusal = self.solvers[i]._warm_refusal()
+                if refusal:
+                    raise ValueError(f"BatchSession.solve_many: problem {i}: {refusal}")
+        moved = None if vertices is None else self._moved(vertices)
+        for alm in self.solvers:
+            if alm is not None:
+                alm.move_ms = None
+        move_ms = None if moved is None else self._move(moved)
+        results = [None] * len(probs)
+        pending = list(range(len(probs)))
+        active = {}         # slot -> (problem index, the start of its session record)
+        while pending or active:
+            for slot in range(slots):
+                if pending and slot not in active and (not warm or slot == pending[0]):
+                    i = pending.pop(0)
+                    active[slot] = (i, self._admit(slot, probs[i], bool(warm)))
+            _lockstep([self.solvers[slot] for slot in sorted(active)], self.max_batch)
+            for slot in sorted(active):
+                alm = self.solvers[slot]
+                if alm.finished:
+                    i, record = active.pop(slot)
+                    sol, hist = alm.finalize(outputs=outputs, read_out=read_out, flow_map=flow_map, sensitivity=sensitivity)
+                    hist.solver_stats["batch"] = {"size": len(probs), "index": i, "max_batch": self.max_batch, "steps_time_note": BATCH_TIME_NOTE}
+                    hist.solver_stats["session"] = {**record, "moved": moved is not None, "move_ms": move_ms}
+                    results[i] = (sol, hist)
+                    self.solved[slot] = True
+        return results
 
 
 # ---- coarse-to-fine cascades: what the drivers share ---------------------------------------------------------------------------------

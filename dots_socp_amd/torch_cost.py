@@ -27,6 +27,23 @@ def _request(needs):
     return {"potentials": bool(needs[0] or needs[1]), "stress": bool(needs[2])}
 
 
+def _session_mesh(who, session, n_time, x, tri, move):
+    """The refusals of a call on a session (``SolveSession``, ``BatchSession``): its time grid and its mesh, by value.  Returns the
+    positions its live contexts move to (``move`` and the session's triangles at other positions), or None."""
+    if int(n_time) != session.n_time:
+        raise ValueError(f"{who}: n_time = {int(n_time)}, the session's {session.n_time}")
+    same_tri = np.array_equal(tri, np.asarray(session.geometry["triangles"], dtype=np.int64))
+    same_x = np.array_equal(x, np.asarray(session.geometry["vertices"], dtype=np.float64))
+    if move and same_tri and not same_x:
+        if x.shape != np.asarray(session.geometry["vertices"]).shape:
+            raise ValueError(f"{who}: vertices must have the session's shape {np.asarray(session.geometry['vertices']).shape}, got {x.shape}")
+        return x
+    if not (same_x and same_tri):
+        raise ValueError(f"{who}: vertices / triangles are not the session's (a session solves on one mesh; moved "
+                         "vertices need a new session)" + (": move=True moves the vertices, the triangles must be the session's" if move else ""))
+    return None
+
+
 def _like(array, ref):
     return torch.as_tensor(np.ascontiguousarray(array), dtype=ref.dtype, device=ref.device)
 
@@ -36,18 +53,7 @@ class _TransportCost(torch.autograd.Function):
     def forward(ctx, mu0, mu1, vertices, triangles, n_time, options, session=None, move=False):
         x, tri = _host(vertices), np.asarray(_host(triangles), dtype=np.int64)
         if session is not None:      # the session's live context: the masses change, the mesh must be the session's
-            if int(n_time) != session.n_time:
-                raise ValueError(f"transport_cost: n_time = {int(n_time)}, the session's {session.n_time}")
-            same_tri = np.array_equal(tri, np.asarray(session.geometry["triangles"], dtype=np.int64))
-            same_x = np.array_equal(x, np.asarray(session.geometry["vertices"], dtype=np.float64))
-            moved = None
-            if move and same_tri and not same_x:      # the session's triangles at other positions: the live context moves
-                if x.shape != np.asarray(session.geometry["vertices"]).shape:
-                    raise ValueError(f"transport_cost: vertices must have the session's shape {np.asarray(session.geometry['vertices']).shape}, got {x.shape}")
-                moved = x
-            elif not (same_x and same_tri):
-                raise ValueError("transport_cost: vertices / triangles are not the session's (a session solves on one mesh; moved "
-                                 "vertices need a new session)" + (": move=True moves the vertices, the triangles must be the session's" if move else ""))
+            moved = _session_mesh("transport_cost", session, n_time, x, tri, move)
             solution, hist = session.solve(mu0.detach(), mu1.detach(), outputs=(), sensitivity=_request(ctx.needs_input_grad), vertices=moved, **options)
         else:
             geom, _ = meshes.make_geometry(x, tri, _host(mu0), _host(mu1), normalize=False)      # the geometry as given
@@ -95,14 +101,21 @@ def transport_cost(mu0, mu1, vertices, triangles, n_time, session=None, move=Fal
 
 class _TransportCosts(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, mu0, mu1, vertices, triangles, n_time, options):
+    def forward(ctx, mu0, mu1, vertices, triangles, n_time, options, session=None, move=False):
         x, tri = _host(vertices), np.asarray(_host(triangles), dtype=np.int64)
         m0, m1 = _host(mu0), _host(mu1)
-        geom, _ = meshes.make_geometry(x, tri, m0[0], m1[0], normalize=False)
-        each = {k: v for k, v in options.items() if k in PER_PROBLEM_KEYS}
-        common = {k: v for k, v in options.items() if k not in PER_PROBLEM_KEYS}
-        problems = [dict(each, mu0=a, mu1=b) for a, b in zip(m0, m1)]
-        results = solver_socp_many(int(n_time), geom, problems, outputs=(), sensitivity=_request(ctx.needs_input_grad), **common)
+        if session is not None:      # the session's live contexts: the masses change, the mesh must be the session's
+            moved = _session_mesh("transport_costs", session, n_time, x, tri, move)
+            options = dict(options)
+            warm = options.pop("warm", False)
+            problems = [dict(options, mu0=a, mu1=b) for a, b in zip(m0, m1)]
+            results = session.solve_many(problems, warm=warm, vertices=moved, outputs=(), sensitivity=_request(ctx.needs_input_grad))
+        else:
+            geom, _ = meshes.make_geometry(x, tri, m0[0], m1[0], normalize=False)
+            each = {k: v for k, v in options.items() if k in PER_PROBLEM_KEYS}
+            common = {k: v for k, v in options.items() if k not in PER_PROBLEM_KEYS}
+            problems = [dict(each, mu0=a, mu1=b) for a, b in zip(m0, m1)]
+            results = solver_socp_many(int(n_time), geom, problems, outputs=(), sensitivity=_request(ctx.needs_input_grad), **common)
         ctx.sens, ctx.mesh = [sol.get("sensitivity") for sol, _ in results], (x, tri)
         ctx.like = (mu0, mu1, vertices)
         return torch.tensor([float(hist.history["Transportation cost"][-1]) for _, hist in results], dtype=torch.float64, device=mu0.device)
@@ -114,17 +127,29 @@ class _TransportCosts(torch.autograd.Function):
         g0 = g.to(r0.device, r0.dtype)[:, None] * _like(np.stack([p[0] for p in parts]), r0) if need[0] else None
         g1 = g.to(r1.device, r1.dtype)[:, None] * _like(np.stack([p[1] for p in parts]), r1) if need[1] else None
         gx = (g.to(rx.device, rx.dtype)[:, None, None] * _like(np.stack([p[2] for p in parts]), rx)).sum(0) if need[2] else None
-        return g0, g1, gx, None, None, None
+        return g0, g1, gx, None, None, None, None, None
 
 
-def transport_costs(mu0, mu1, vertices, triangles, n_time, **solver_options):
+def transport_costs(mu0, mu1, vertices, triangles, n_time, session=None, move=False, **solver_options):
     """``transport_cost`` for ``B`` pairs of masses on one surface: ``mu0`` and ``mu1`` (B, V); returns the costs (B,).  The problems
     run through ``solver_socp_many``: one factor of the direct solver, batched sweeps.  ``solver_options``: the per-problem options of
-    ``solver_socp_many`` (tol, nit, congestion, ...) hold for every problem, the others (eps, device, max_batch, ...) for the batch."""
+    ``solver_socp_many`` (tol, nit, congestion, ...) hold for every problem, the others (eps, device, max_batch, ...) for the batch.
+    ``session``: a ``socp.BatchSession`` on this mesh (``meshes.make_geometry(vertices, triangles, ..., normalize=False)``) and
+    ``n_time``: the forward pass is ``session.solve_many`` on its live contexts -- no plan, factor or context is built again once
+    they exist -- and ``solver_options`` are ``warm`` and what one of its problems may hold (``tol``, ``nit``, ``tol_checkpoints``,
+    ``time_limit``, ``congestion``); ``vertices`` / ``triangles`` must be the session's, by value.  With ``warm=False`` (the default)
+    costs and gradients are those of the call without a session, bit for bit.  ``move=True`` (with a session): ``vertices`` that
+    differ from the session's by value move its live contexts with one refresh of the factor (``BatchSession.solve_many(vertices=)``);
+    costs and gradients are then those of the call on the moved mesh in the session's numbering.  The default keeps the session on
+    its mesh and refuses other positions."""
     for k in ("outputs", "read_out", "flow_map", "sensitivity"):
         if k in solver_options:
             raise ValueError(f"transport_costs: '{k}' is chosen by the function itself")
+    if session is None and "warm" in solver_options:
+        raise ValueError("transport_costs: 'warm' needs a session (a call without one starts from zero)")
+    if session is None and move:
+        raise ValueError("transport_costs: 'move' needs a session (a call without one builds its own solvers on the mesh as given)")
     mu0, mu1 = _tensor(mu0), _tensor(mu1)
     if mu0.ndim != 2 or mu0.shape != mu1.shape or mu0.shape[0] < 1:
         raise ValueError(f"transport_costs: mu0 and mu1 (B, V) expected, got {tuple(mu0.shape)} and {tuple(mu1.shape)}")
-    return _TransportCosts.apply(mu0, mu1, _tensor(vertices), triangles, n_time, solver_options)
+    return _TransportCosts.apply(mu0, mu1, _tensor(vertices), triangles, n_time, solver_options, session, bool(move))

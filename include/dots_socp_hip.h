@@ -909,6 +909,28 @@ typedef struct dots_move_desc {
 } dots_move_desc;
 int dots_move_vertices(dots_ctx *ctx, const dots_move_desc *desc);
 
+/* dots_move_vertices_many: every holder of ONE factor store (dots_front_share) takes the other vertex positions together -- a batch
+ * whose surface moves.  ctxs[0 .. n) are exactly the holders of the store: pairwise distinct, all with the same store, n its number
+ * of holders; one context that holds its store alone (or has no factor) is the case n = 1, which is dots_move_vertices bit for bit.
+ * dots_move_vertices itself keeps refusing a shared store.
+ *   Every check runs for every member before any member changes; the positions are validated once, on ctxs[0], in scratch.  After a
+ *     refusal all contexts keep geometry, factor and state and stay fully usable.  DOTS_ERR_ARGUMENT: NULL arguments, a coordinate
+ *     that is not finite, an area or a vertex mass that is not positive.  DOTS_ERR_STATE: what dots_move_vertices refuses a context
+ *     for (a time slab, a multigrid hierarchy, a non-modal context, a factor from the caller's values, another eps, scratch that does
+ *     not fit), a list that is not the whole set of holders, members whose triangle tables are numbered differently.
+ *     DOTS_ERR_MEMORY: the temporaries of the factorisation do not fit.
+ *   Then every member does on its own stream what dots_move_vertices does to its context: the pending division and z_mid with the OLD
+ *     geometry, the launch ahead and what goes with it dropped, the nine tables committed (from the one scratch), a dots_restart
+ *     required before it steps.  The host constants are formed once, from one download of area_f, mass_v and val, and every member
+ *     gets the same bits (and the same hash: a new context on the moved mesh can share, one on the old mesh cannot); norm_boundary
+ *     is formed per member from the masses that member holds.
+ *   The factor is refreshed ONCE into the store's allocations, after every member's stream has been synchronised (no sweep in flight
+ *     on the old factor), and every stream is synchronised again before the call returns: launches, events and stream
+ *     synchronisation only.  A pivot that is not positive releases the factor of EVERY member (all are PCG contexts then) and
+ *     returns the factorisation's error.
+ *   ms (HOST out [3]) as for dots_move_vertices: the assembly launches summed over the members, the one refresh, the whole call. */
+int dots_move_vertices_many(dots_ctx *const *ctxs, int n, const dots_move_desc *desc);
+
 /* dots_geometry_copy: the geometry tables of the context, copied device -> host behind a stream synchronisation (read-only; NULL
  * members are skipped).  Device numbering; corner_scale and corner_grad_area in corner-list order. */
 typedef struct dots_geometry_tables {
