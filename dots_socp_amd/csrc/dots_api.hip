@@ -81,6 +81,47 @@ static double boundary_sum(const double *mu0, const double *mu1, const double *m
 }
 static double boundary_norm(double nb, int T) { return std::sqrt(nb / (T + 1)); }
 
+// The host constants of a run on the geometry tables `mass` (V), `area` (F) and `val` (nnz), for the n contexts cs[0 .. n) that hold
+// them (dots_create: one; a move: every holder of the factor, the sums formed once): the hash of what the factor is built from,
+// continued from the graph's (dots_front_share); the KKT normalisation constants (solver_socp.py:303-313), means of the broadcast
+// weight arrays summed in index order; norm_d; the masses dots_restart forms norm_boundary from; norm_boundary of cs[k]'s end masses
+// ends[2 k], ends[2 k + 1].
+static void run_constants(Ctx *const *cs, int n, const std::shared_ptr<std::vector<double>> &mass, const double *area, const double *val,
+                          const double *const *ends) {
+    const int V = cs[0]->d.V, F = cs[0]->d.F;
+    uint64_t h = cs[0]->lap_hash_graph;
+    auto mix = [&h](const void *data, size_t bytes) {
+        const unsigned char *b = static_cast<const unsigned char *>(data);
+        for (size_t i = 0; i < bytes; ++i) h = (h ^ b[i]) * 1099511628211ull;
+    };
+    mix(val, sizeof(double) * (size_t)cs[0]->nnz);
+    mix(mass->data(), sizeof(double) * (size_t)V);
+    double sm = 0.0, sa = 0.0;
+    for (int v = 0; v < V; ++v) sm += (*mass)[(size_t)v];
+    for (int f = 0; f < F; ++f) sa += area[f];
+    const double mean_v = sm / V, mean_f = sa / F;
+    for (int k = 0; k < n; ++k) {
+        Ctx *c = cs[k];
+        c->lap_hash = h;
+        c->c_prim_q = 0.5 * (mean_v + mean_f);
+        c->c_prim_z = (mean_v + mean_f + mean_v) / 3.0;
+        c->c_dual_alpha = mean_v;
+        c->c_dual_beta = 0.5 * (mean_v + mean_f);
+        c->c_comp_rho = mean_v;
+        c->c_comp_m = mean_f;
+        c->prm.norm_d = c->norm_d0 = std::sqrt(2.0 * sa);
+        c->mass_host = mass;
+        c->prm.norm_boundary = boundary_norm(boundary_sum(ends[2 * k], ends[2 * k + 1], mass->data(), V), c->d.T);
+    }
+}
+
+// The parameters a run starts from, in dots_create and in dots_restart (tau, eps and the PCG's tolerance and cap are the caller's)
+static void fresh_run_params(Ctx *c) {
+    dots_params &q = c->prm;
+    q.r = 1.0; q.scale_z = 1.0; q.const_d = 1.0;
+    q.congestion = 0.0; q.prim_scale = 1.0; q.dual_scale = 1.0; q.boundary_scale = 1.0;
+}
+
 static int build(Ctx *c, const dots_problem_desc *p) {
     Dev &d = c->d;
     d.T = p->n_time;
@@ -132,10 +173,7 @@ static int build(Ctx *c, const dots_problem_desc *p) {
         };
         mix(p->lap_rowptr, sizeof(int32_t) * ((size_t)p->n_vertices + 1));
         mix(p->lap_col, sizeof(int32_t) * (size_t)p->lap_nnz);
-        c->lap_hash_graph = h;
-        mix(p->lap_val, sizeof(double) * (size_t)p->lap_nnz);
-        mix(p->mass_vert, sizeof(double) * (size_t)p->n_vertices);
-        c->lap_hash = h;
+        c->lap_hash_graph = h;      // (lap_hash continues it over the values: run_constants)
         h = 1469598103934665603ull;
         mix(p->triangles, sizeof(int32_t) * 3 * (size_t)p->n_triangles);
         mix(p->corner_ptr, sizeof(int32_t) * ((size_t)p->n_vertices + 1));
@@ -277,24 +315,10 @@ static int build(Ctx *c, const dots_problem_desc *p) {
         c->slab_x_chunk = nnode + V;
     }
 
-    // KKT normalisation constants (solver_socp.py:303-313): means of the broadcast weight arrays
-    double sm = 0.0, sa = 0.0;
-    for (int v = 0; v < V; ++v) sm += p->mass_vert[v];
-    for (int f = 0; f < F; ++f) sa += p->area_tri[f];
-    const double mean_v = sm / V, mean_f = sa / F;
-    c->c_prim_q = 0.5 * (mean_v + mean_f);
-    c->c_prim_z = (mean_v + mean_f + mean_v) / 3.0;
-    c->c_dual_alpha = mean_v;
-    c->c_dual_beta = 0.5 * (mean_v + mean_f);
-    c->c_comp_rho = mean_v;
-    c->c_comp_m = mean_f;
-
-    dots_params &q = c->prm;
-    q.r = 1.0; q.scale_z = 1.0; q.const_d = 1.0; q.norm_d = c->norm_d0 = std::sqrt(2.0 * sa);
-    c->mass_host = std::make_shared<std::vector<double>>(p->mass_vert, p->mass_vert + V);      // (dots_restart forms norm_boundary again)
-    q.norm_boundary = boundary_norm(boundary_sum(p->mu0, p->mu1, p->mass_vert, V), d.T);
-    q.congestion = 0.0; q.tau = 1.9; q.eps = 0.0; q.prim_scale = 1.0; q.dual_scale = 1.0; q.boundary_scale = 1.0;
-    q.cg_tol = 1e-8; q.cg_max_iter = 20000;
+    const double *const ends[2] = {p->mu0, p->mu1};
+    run_constants(&c, 1, std::make_shared<std::vector<double>>(p->mass_vert, p->mass_vert + V), p->area_tri, p->lap_val, ends);
+    fresh_run_params(c);
+    c->prm.tau = 1.9; c->prm.eps = 0.0; c->prm.cg_tol = 1e-8; c->prm.cg_max_iter = 20000;
     DOTS_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -1192,6 +1216,35 @@ static int batch_wait(Ctx *c, Ctx *other) {
     return 0;
 }
 
+// The members of a batched call and what front_solve_many reads and writes per member: right-hand side, intermediate, solution (modes)
+struct BatchMembers {
+    std::vector<Ctx *> cv;
+    std::vector<const double *> bh;
+    std::vector<double *> ys, xs;
+};
+
+// cs[0 .. n) as the members of `who`'s batch: each passes check(reads_only, keeps_division) -- with `needs_restart_check` it must
+// not be waiting for a dots_restart after a move --, holds a direct solver on one GPU and the factor of cs[0], and is listed once.
+// `one_message` (dots_bench_many): the two factor checks under one text and status, no search for a context listed twice.
+static int batch_members(const char *who, dots_ctx *const *cs, int n, bool reads_only, bool keeps_division, bool needs_restart_check, BatchMembers &out,
+                         bool one_message = false) {
+    const std::string w(who);
+    int rc;
+    for (int k = 0; k < n; ++k) {
+        if ((rc = check(cs[k], reads_only, keeps_division))) return rc;
+        if (needs_restart_check && (rc = moved_needs_restart(cs[k], ("dots_" + w).c_str()))) return rc;
+        const bool holds = front_batchable(cs[k]), shares = holds && cs[k]->front.F == cs[0]->front.F;
+        if (one_message && !shares) { set_error(w + ": the contexts do not share one factor"); return DOTS_ERR_STATE; }
+        if (!holds) { set_error(w + ": every context needs an installed or shared factor on one GPU (no PCG, no time slab)"); return DOTS_ERR_STATE; }
+        if (!shares) { set_error(w + ": the contexts do not share one factor (dots_front_share)"); return DOTS_ERR_ARGUMENT; }
+        for (int j = 0; j < k && !one_message; ++j)
+            if (cs[j] == cs[k]) { set_error(w + ": a context is listed twice"); return DOTS_ERR_ARGUMENT; }
+    }
+    out.cv.assign(cs, cs + n);
+    for (Ctx *c : out.cv) { out.bh.push_back(c->d.cg_p0); out.ys.push_back(c->dcg.cg_z); out.xs.push_back(c->dcg.cg_x); }
+    return 0;
+}
+
 int dots_front_setup(dots_ctx *c, const dots_front_desc *desc) {
     int rc = check(c);
     if (rc) return rc;
@@ -1249,20 +1302,13 @@ int dots_front_share(dots_ctx *c, dots_ctx *owner) {
 
 int dots_laplacian_solve_many(dots_ctx *const *cs, int n, const double *const *host_in, double *const *host_out) {
     if (!cs || n < 1 || !host_in || !host_out) { set_error("laplacian_solve_many: bad arguments"); return DOTS_ERR_ARGUMENT; }
-    int rc;
-    for (int k = 0; k < n; ++k) {
-        if ((rc = check(cs[k]))) return rc;
+    for (int k = 0; k < n; ++k)
         if (!host_in[k] || !host_out[k]) { set_error("laplacian_solve_many: null array"); return DOTS_ERR_ARGUMENT; }
-        if (!front_batchable(cs[k])) { set_error("laplacian_solve_many: every context needs an installed or shared factor on one GPU (no PCG, no time slab)"); return DOTS_ERR_STATE; }
-        if (cs[k]->front.F != cs[0]->front.F) { set_error("laplacian_solve_many: the contexts do not share one factor (dots_front_share)"); return DOTS_ERR_ARGUMENT; }
-        for (int j = 0; j < k; ++j)
-            if (cs[j] == cs[k]) { set_error("laplacian_solve_many: a context is listed twice"); return DOTS_ERR_ARGUMENT; }
-    }
+    BatchMembers m;
+    int rc = batch_members("laplacian_solve_many", cs, n, false, false, false, m);
+    if (rc) return rc;
     const int64_t cnt = array_count_device(cs[0]->d, DOTS_PHI), nh = array_count_host(cs[0]->d, DOTS_PHI);
     std::vector<double *> din((size_t)n, nullptr), dout((size_t)n, nullptr);
-    std::vector<const double *> bh((size_t)n);
-    std::vector<double *> ys((size_t)n), xs((size_t)n);
-    std::vector<Ctx *> cv(cs, cs + n);
     DevicePool tmp(cs[0]->device);
     auto enqueue = [&]() -> int {
         int r;
@@ -1273,14 +1319,11 @@ int dots_laplacian_solve_many(dots_ctx *const *cs, int n, const double *const *h
             DOTS_HIP(hipMemcpyAsync(c->stage, host_in[k], sizeof(double) * (size_t)nh, hipMemcpyHostToDevice, c->stream));
             if ((r = launch_to_device_layout(c, DOTS_PHI, din[k], c->stage))) return r;
             modes_forward(c, din[k], c->d.cg_p0, true);
-            bh[(size_t)k] = c->d.cg_p0;
-            ys[(size_t)k] = c->dcg.cg_z;
-            xs[(size_t)k] = c->dcg.cg_x;
         }
         // the sweeps of all members on the first member's stream, then each member's inverse transform on its own
         for (int k = 1; k < n; ++k)
             if ((r = batch_wait(cs[0], cs[k]))) return r;
-        if ((r = front_solve_many(cv.data(), n, bh.data(), ys.data(), xs.data()))) return r;
+        if ((r = front_solve_many(m.cv.data(), n, m.bh.data(), m.ys.data(), m.xs.data()))) return r;
         for (int k = 0; k < n; ++k) {
             Ctx *c = cs[k];
             if ((r = batch_wait(c, cs[0]))) return r;
@@ -1299,20 +1342,12 @@ int dots_laplacian_solve_many(dots_ctx *const *cs, int n, const double *const *h
 
 int dots_step_many(dots_ctx *const *cs, int n, dots_step_stats *stats) {
     if (!cs || n < 1) { set_error("step_many: bad arguments"); return DOTS_ERR_ARGUMENT; }
-    int rc;
-    for (int k = 0; k < n; ++k) {
-        if ((rc = check(cs[k], true, true))) return rc;      // (the iteration consumes the flags and a pending division itself)
-        if ((rc = moved_needs_restart(cs[k], "dots_step_many"))) return rc;
-        if (!front_batchable(cs[k])) { set_error("step_many: every context needs an installed or shared factor on one GPU (no PCG, no time slab)"); return DOTS_ERR_STATE; }
-        if (cs[k]->front.F != cs[0]->front.F) { set_error("step_many: the contexts do not share one factor (dots_front_share)"); return DOTS_ERR_ARGUMENT; }
-        for (int j = 0; j < k; ++j)
-            if (cs[j] == cs[k]) { set_error("step_many: a context is listed twice"); return DOTS_ERR_ARGUMENT; }
-    }
+    BatchMembers m;
+    int rc = batch_members("step_many", cs, n, true, true, true, m);      // (the iteration consumes the flags and a pending division itself)
+    if (rc) return rc;
     Ctx *c0 = cs[0];
-    std::vector<Ctx *> cv(cs, cs + n);
+    const std::vector<Ctx *> &cv = m.cv;
     std::vector<IterPlan> plan((size_t)n);
-    std::vector<const double *> bh((size_t)n);
-    std::vector<double *> ys((size_t)n), xs((size_t)n);
     const bool timed = stats != nullptr;
     hipEvent_t *ev = c0->ev;      // (stats: the batch's phases on the first member's stream)
     if (timed) {
@@ -1329,13 +1364,10 @@ int dots_step_many(dots_ctx *const *cs, int n, dots_step_stats *stats) {
         if ((rc = iteration_before(c, false, p, nullptr))) return rc;
         if (!rhs_writes_modes(c)) modes_forward(c, c->d.cg_b, c->d.cg_p0, true);
         c->last_cg_iters = 0;
-        bh[(size_t)k] = c->d.cg_p0;
-        ys[(size_t)k] = c->dcg.cg_z;
-        xs[(size_t)k] = c->dcg.cg_x;
     }
     for (int k = 1; k < n; ++k) if ((rc = batch_wait(c0, cv[k]))) return rc;
     if (timed) DOTS_HIP(hipEventRecord(ev[1], c0->stream));
-    if ((rc = front_solve_many(cv.data(), n, bh.data(), ys.data(), xs.data()))) return rc;
+    if ((rc = front_solve_many(m.cv.data(), n, m.bh.data(), m.ys.data(), m.xs.data()))) return rc;
     if (timed) DOTS_HIP(hipEventRecord(ev[2], c0->stream));
     // each member behind the sweeps: inverse transform (unless its projection takes it), projection, steps 2+3
     for (int k = 0; k < n; ++k) {
@@ -1362,24 +1394,15 @@ int dots_step_many(dots_ctx *const *cs, int n, dots_step_stats *stats) {
 
 int dots_bench_many(dots_ctx *const *cs, int n, int reps, double *ms) {
     if (!cs || n < 1 || reps < 1 || !ms) { set_error("bench_many: bad arguments"); return DOTS_ERR_ARGUMENT; }
-    int rc;
-    for (int k = 0; k < n; ++k) {
-        if ((rc = check(cs[k]))) return rc;
-        if (!front_batchable(cs[k]) || cs[k]->front.F != cs[0]->front.F) { set_error("bench_many: the contexts do not share one factor"); return DOTS_ERR_STATE; }
-    }
-    std::vector<Ctx *> cv(cs, cs + n);
-    std::vector<const double *> bh((size_t)n);
-    std::vector<double *> ys((size_t)n), xs((size_t)n);
-    for (int k = 0; k < n; ++k) {
-        bh[(size_t)k] = cv[k]->d.cg_p0;
-        ys[(size_t)k] = cv[k]->dcg.cg_z;
-        xs[(size_t)k] = cv[k]->dcg.cg_x;
-    }
+    BatchMembers m;
+    int rc = batch_members("bench_many", cs, n, false, false, false, m, true);
+    if (rc) return rc;
+    const std::vector<Ctx *> &cv = m.cv;
     Ctx *c0 = cv[0];
     for (int k = 1; k < n; ++k) if ((rc = batch_wait(c0, cv[k]))) return rc;
-    for (int i = 0; i < 2; ++i) if ((rc = front_solve_many(cv.data(), n, bh.data(), ys.data(), xs.data()))) return rc;
+    for (int i = 0; i < 2; ++i) if ((rc = front_solve_many(m.cv.data(), n, m.bh.data(), m.ys.data(), m.xs.data()))) return rc;
     DOTS_HIP(hipEventRecord(c0->ev[6], c0->stream));
-    for (int i = 0; i < reps; ++i) if ((rc = front_solve_many(cv.data(), n, bh.data(), ys.data(), xs.data()))) return rc;
+    for (int i = 0; i < reps; ++i) if ((rc = front_solve_many(m.cv.data(), n, m.bh.data(), m.ys.data(), m.xs.data()))) return rc;
     DOTS_HIP(hipEventRecord(c0->ev[7], c0->stream));
     DOTS_HIP(hipEventSynchronize(c0->ev[7]));
     float t;
@@ -1606,10 +1629,9 @@ int dots_restart(dots_ctx *c, const dots_restart_desc *desc) {
     else nb = boundary_sum(desc->mu0, desc->mu1, c->mass_host->data(), V);
     DOTS_HIP(hipEventRecord(c->ev[1], c->stream));
     DOTS_HIP(hipStreamSynchronize(c->stream));      // (host arrays are borrowed for the call only; the ring's events and the mailbox are idle from here)
-    dots_params &q = c->prm;
-    q.r = 1.0; q.scale_z = 1.0; q.const_d = 1.0; q.norm_d = c->norm_d0;
-    q.norm_boundary = boundary_norm(nb, d.T);
-    q.congestion = 0.0; q.prim_scale = 1.0; q.dual_scale = 1.0; q.boundary_scale = 1.0;      // (tau, eps, cg_tol, cg_max_iter stay)
+    fresh_run_params(c);      // (tau, eps, cg_tol, cg_max_iter stay)
+    c->prm.norm_d = c->norm_d0;
+    c->prm.norm_boundary = boundary_norm(nb, d.T);
     // host bookkeeping of the old run
     c->zmid_stale = c->zmid_deferred = 0;
     c->needs_restart = 0;      // (after dots_move_vertices: the run that starts here is one on the new surface)
@@ -1704,7 +1726,7 @@ static int move_holders(dots_ctx *const *cs, int n, const dots_move_desc *desc, 
         return DOTS_ERR_ARGUMENT;
     }
     // from here on the contexts are on the new surface: each member's tables from the one scratch (complete: the host has waited for
-    // it), behind the flush on its own stream; the host constants of build(), its sequential sums over the tables, from one download
+    // it), behind the flush on its own stream; the host constants of the run (run_constants: sequential sums over the tables) from one download
     std::vector<double> area((size_t)F), val((size_t)nnz);
     std::vector<std::vector<double>> mu((size_t)2 * n, std::vector<double>((size_t)V));
     auto mass = std::make_shared<std::vector<double>>((size_t)V);      // (a new vector: whoever shares the old one keeps it)
@@ -1727,32 +1749,10 @@ static int move_holders(dots_ctx *const *cs, int n, const dots_move_desc *desc, 
         c->d2h_bytes += (int64_t)sizeof(double) * 2 * (int64_t)V;
     }
     for (int k = 0; k < n; ++k) DOTS_HIP(hipStreamSynchronize(cs[k]->stream));      // (no member has anything in flight when the refresh starts)
-    uint64_t h = c0->lap_hash_graph;
-    {
-        auto mix = [&h](const void *data, size_t bytes) {
-            const unsigned char *b = static_cast<const unsigned char *>(data);
-            for (size_t i = 0; i < bytes; ++i) h = (h ^ b[i]) * 1099511628211ull;
-        };
-        mix(val.data(), sizeof(double) * (size_t)nnz);
-        mix(mass->data(), sizeof(double) * (size_t)V);
-    }
-    double sm = 0.0, sa = 0.0;
-    for (int v = 0; v < V; ++v) sm += (*mass)[(size_t)v];
-    for (int f = 0; f < F; ++f) sa += area[(size_t)f];
-    const double mean_v = sm / V, mean_f = sa / F;
-    for (int k = 0; k < n; ++k) {
-        dots_ctx *c = cs[k];
-        c->lap_hash = h;
-        c->c_prim_q = 0.5 * (mean_v + mean_f);
-        c->c_prim_z = (mean_v + mean_f + mean_v) / 3.0;
-        c->c_dual_alpha = mean_v;
-        c->c_dual_beta = 0.5 * (mean_v + mean_f);
-        c->c_comp_rho = mean_v;
-        c->c_comp_m = mean_f;
-        c->prm.norm_d = c->norm_d0 = std::sqrt(2.0 * sa);
-        c->mass_host = mass;
-        c->prm.norm_boundary = boundary_norm(boundary_sum(mu[(size_t)2 * k].data(), mu[(size_t)2 * k + 1].data(), mass->data(), V), c->d.T);
-    }
+    const std::vector<Ctx *> cv(cs, cs + n);
+    std::vector<const double *> ends;
+    for (const std::vector<double> &m : mu) ends.push_back(m.data());
+    run_constants(cv.data(), n, mass, area.data(), val.data(), ends.data());
     // the factor the members hold, from K + (sigma_a + eps) M of the new tables, into the allocations it has: once
     DOTS_HIP(hipEventRecord(c0->ev[6], c0->stream));
     if (c0->front.n_nodes > 0 && (rc = front_refresh(c0))) {

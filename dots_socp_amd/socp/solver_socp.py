@@ -896,12 +896,7 @@ class AlmSolver:
 
     def _geometry_moved(self, moved):
         """``self.geometry`` after the context's vertices moved to ``moved`` (V, 3), a host array: positions and areas follow."""
-        from .. import meshes
-
-        t = np.asarray(self.geometry["triangles"])
-        area_t = meshes.triangle_areas(moved, t)
-        self.geometry = {**self.geometry, "vertices": moved, "area_triangles": area_t,
-                         "area_vertices": meshes.vertex_areas(moved.shape[0], t, area_t)}
+        self.geometry = _moved_geometry(self.geometry, moved)
 
     def restart(self, mu0, mu1, warm=True, nit=None, tol=None, tol_checkpoints=None, time_limit=None, congestion=None, vertices=None, *,
                 batch_member=False):
@@ -934,27 +929,17 @@ class AlmSolver:
         if batch_member and vertices is not None:
             raise ValueError("restart: a member of a batch moves with all holders of its factor (BatchSession.solve_many(vertices=))")
         V = int(np.asarray(self.geometry["vertices"]).shape[0])
-        on_device = all(type(a).__module__.startswith("torch") and getattr(a, "is_cuda", False) for a in (mu0, mu1))
-        masses = []
-        for name, a in (("mu0", mu0), ("mu1", mu1)):
-            if not on_device:
-                a = np.asarray(a.detach().cpu().numpy() if type(a).__module__.startswith("torch") else a, dtype=np.float64)
-                if a.shape == (V,) and not np.all(np.isfinite(a)):
-                    raise ValueError(f"restart: {name} has entries that are not finite")
-            if tuple(a.shape) != (V,):
-                raise ValueError(f"restart: {name} must have shape ({V},), got {tuple(a.shape)}")
-            masses.append(a)
+        on_device = _is_device_tensor(mu0) and _is_device_tensor(mu1)      # (one of each: both are read on the host)
+        masses = _end_masses("restart", mu0, mu1, V, to_host=not on_device)
         if warm and self._warm_refusal():
             raise ValueError(self._warm_refusal())
         factors = self.recovery_factors() if warm else None
         if not batch_member:      # (a member's session has moved it, or not, and booked the times)
             self.move_ms = None
-        if vertices is not None:
-            moved_on_device = _is_device_tensor(vertices)
-            if not moved_on_device and type(vertices).__module__.startswith("torch"):
-                vertices = vertices.detach().cpu().numpy()
-            self.move_ms = self.dev.move_vertices(vertices, device_pointers=moved_on_device)
-            self._geometry_moved(np.array(vertices.detach().cpu().numpy() if moved_on_device else vertices, dtype=np.float64))
+            if vertices is not None:
+                given = vertices if _is_device_tensor(vertices) else _host_array(vertices)
+                self.move_ms = self.dev.move_vertices(given, device_pointers=_is_device_tensor(given))
+                self._geometry_moved(np.array(_host_array(given)))
         ms = self.dev.restart(masses[0], masses[1], "warm" if warm else "cold", factors, device_pointers=on_device)
         if on_device:      # (the plan's host copies, back in the caller's numbering: read_out and flow_map take the end masses from the geometry)
             order = self._caller_order()
@@ -1032,10 +1017,7 @@ def solver_socp(
     the two ends and the stress of the kinetic energy, reduced on the device (``dots_socp_amd.sensitivity.cost_gradients`` makes the
     derivatives of the cost in mu0, mu1 and the vertex positions of them); None (the default) changes nothing.
     """
-    if read_out is not None and outputs is not None:
-        raise ValueError("solver_socp: outputs and read_out are mutually exclusive (read_out returns mu and E only)")
-    flow_map = check_flow_map(flow_map, n_time=n_time)
-    sensitivity = check_sensitivity(sensitivity, congestion=congestion)
+    flow_map, sensitivity = _requests("solver_socp", n_time, outputs, read_out, flow_map, sensitivity, [congestion])
     alm = AlmSolver(n_time, geometry, congestion=congestion, nit=nit, eps=eps, tol=tol, tau=tau, is_z_scaling=is_z_scaling,
                     is_constant_scaling=is_constant_scaling, check_kkt_step_by_step=check_kkt_step_by_step,
                     init_solution=init_solution, tol_checkpoints=tol_checkpoints, time_limit=time_limit, is_palm=is_palm,
@@ -1061,7 +1043,96 @@ def _is_device_tensor(a):
     return type(a).__module__.startswith("torch") and bool(getattr(a, "is_cuda", False))
 
 
-class SolveSession:
+def _host_array(a):
+    """``a``, an array or a torch tensor wherever it lives, as a float64 array on the host"""
+    return np.asarray(a.detach().cpu().numpy() if type(a).__module__.startswith("torch") else a, dtype=np.float64)
+
+
+def _without_masses(geometry):
+    return {k: v for k, v in geometry.items() if k not in ("mu0", "mu1")}
+
+
+# ---- what the drivers over live contexts share: intake, admission, the slot loop ------------------------------------------------------
+def _end_masses(who, mu0, mu1, V, to_host):
+    """The end masses as a driver takes them: float64 host arrays of shape (V,) with finite entries; a tensor on a device passes as it
+    is, checked for its shape alone (its entries are the caller's business), unless ``to_host``.  ``who`` opens the messages."""
+    out = []
+    for name, a in (("mu0", mu0), ("mu1", mu1)):
+        if to_host or not _is_device_tensor(a):
+            a = _host_array(a)
+            if a.shape == (V,) and not np.all(np.isfinite(a)):
+                raise ValueError(f"{who}: {name} has entries that are not finite")
+        if tuple(a.shape) != (V,):
+            raise ValueError(f"{who}: {name} must have shape ({V},), got {tuple(a.shape)}")
+        out.append(a)
+    return out
+
+
+def _moved_vertices(who, vertices, V):
+    """Moved vertices as a session takes them: ``(what the device call reads, the host array)`` -- a tensor on a device as it is,
+    anything else as the host array; the host array is a finite (V, 3) float64 copy either way."""
+    on_device = _is_device_tensor(vertices)
+    host = _host_array(vertices)
+    if host.shape != (V, 3):
+        raise ValueError(f"{who}: vertices must have shape ({V}, 3), got {host.shape}")
+    if not np.all(np.isfinite(host)):
+        raise ValueError(f"{who}: vertices has entries that are not finite")
+    return (vertices if on_device else host), np.array(host)
+
+
+def _moved_geometry(geometry, host_vertices):
+    """``geometry`` with its vertices at ``host_vertices`` (V, 3): the same triangles, positions and areas follow."""
+    from .. import meshes
+
+    t = np.asarray(geometry["triangles"])
+    area_t = meshes.triangle_areas(host_vertices, t)
+    return {**geometry, "vertices": host_vertices, "area_triangles": area_t,
+            "area_vertices": meshes.vertex_areas(host_vertices.shape[0], t, area_t)}
+
+
+def _requests(who, n_time, outputs, read_out, flow_map, sensitivity, congestions):
+    """What every driver checks of the results it is asked for, before a device is touched; ``congestions``: of every problem.
+    Returns the checked ``flow_map`` and ``sensitivity``."""
+    if read_out is not None and outputs is not None:
+        raise ValueError(f"{who}: outputs and read_out are mutually exclusive (read_out returns mu and E only)")
+    flow_map = check_flow_map(flow_map, n_time=n_time)
+    for congestion in congestions:
+        sensitivity = check_sensitivity(sensitivity, congestion=congestion)
+    return flow_map, sensitivity
+
+
+class _Session:
+    """What the two sessions share: the mesh, the counters, the context manager and the record ``solver_stats["session"]``."""
+
+    def __init__(self, who, geometry):
+        if not isinstance(geometry, dict) or "vertices" not in geometry or "triangles" not in geometry:
+            raise ValueError(f"{who}: geometry must be a dict with 'vertices' and 'triangles'")
+        self.geometry = _without_masses(geometry)
+        self.n_vertices = int(np.asarray(geometry["vertices"]).shape[0])
+        self.index = 0                  # problems admitted (SolveSession: solved) so far
+        self.setup_seconds = None       # of the first context -- plan, factor, context --: what every later admission saves
+        self.closed = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        self.closed = True
+        for alm in self._live():
+            alm.close()
+
+    def _admitted(self, built, warm, restart_ms, setup, moved, move_ms):
+        """``solver_stats["session"]`` of the problem just admitted; ``built``: its context was built for it (else restarted)."""
+        if self.setup_seconds is None:
+            self.setup_seconds = setup
+        return {"index": self.index, "warm": bool(warm) and not built, "restart_ms": restart_ms, "setup_seconds": setup,
+                "setup_seconds_saved": 0.0 if built else self.setup_seconds, "moved": bool(moved), "move_ms": move_ms}
+
+
+class SolveSession(_Session):
     """One device context and one factor for a sequence of transport problems on one surface, whose end masses change from solve to
     solve: ``with SolveSession(n_time, geometry, **solver_options) as s: solution, hist = s.solve(mu0, mu1)``.
 
@@ -1078,8 +1149,7 @@ class SolveSession:
         unknown = set(solver_options) - set(SESSION_KEYS)
         if unknown:
             raise ValueError(f"SolveSession: unknown option(s) {sorted(unknown)}; known: {list(SESSION_KEYS)}")
-        if not isinstance(geometry, dict) or "vertices" not in geometry or "triangles" not in geometry:
-            raise ValueError("SolveSession: geometry must be a dict with 'vertices' and 'triangles'")
+        _Session.__init__(self, "SolveSession", geometry)
         options = dict(solver_options)
         options.pop("is_multi_threads", None)
         check_time_nodes(n_time, options.get("lap_solver", "modal_direct"), None, options.get("pcg_windows", False))
@@ -1087,48 +1157,10 @@ class SolveSession:
         if int(options.get("nit", 1000)) < 1:
             raise ValueError("SolveSession: nit must be at least 1")
         self.n_time, self.options = int(n_time), options
-        self.geometry = {k: v for k, v in geometry.items() if k not in ("mu0", "mu1")}
-        self.n_vertices = int(np.asarray(geometry["vertices"]).shape[0])
         self.alm = None
-        self.index = 0                  # solves so far
-        self.setup_seconds = None       # of the first solve: what every later one saves
-        self.closed = False
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def close(self):
-        self.closed = True
-        if self.alm is not None:
-            self.alm.close()
-
-    def _masses(self, mu0, mu1, to_host):
-        out = []
-        for name, a in (("mu0", mu0), ("mu1", mu1)):
-            if not _is_device_tensor(a) or to_host:
-                a = np.asarray(a.detach().cpu().numpy() if type(a).__module__.startswith("torch") else a, dtype=np.float64)
-                if a.shape == (self.n_vertices,) and not np.all(np.isfinite(a)):
-                    raise ValueError(f"SolveSession.solve: {name} has entries that are not finite")
-            if tuple(a.shape) != (self.n_vertices,):
-                raise ValueError(f"SolveSession.solve: {name} must have shape ({self.n_vertices},), got {tuple(a.shape)}")
-            out.append(a)
-        return out
-
-    def _moved(self, vertices):
-        """``vertices`` as the session takes them: a device tensor as it is, anything else as a finite (V, 3) float64 array."""
-        if _is_device_tensor(vertices):
-            if tuple(vertices.shape) != (self.n_vertices, 3):
-                raise ValueError(f"SolveSession.solve: vertices must have shape ({self.n_vertices}, 3), got {tuple(vertices.shape)}")
-            return vertices
-        a = np.asarray(vertices.detach().cpu().numpy() if type(vertices).__module__.startswith("torch") else vertices, dtype=np.float64)
-        if a.shape != (self.n_vertices, 3):
-            raise ValueError(f"SolveSession.solve: vertices must have shape ({self.n_vertices}, 3), got {a.shape}")
-        if not np.all(np.isfinite(a)):
-            raise ValueError("SolveSession.solve: vertices has entries that are not finite")
-        return a
+    def _live(self):
+        return [] if self.alm is None else [self.alm]
 
     def solve(self, mu0, mu1, warm=True, outputs=None, read_out=None, flow_map=None, sensitivity=None, vertices=None, **per_solve):
         """Solve the problem with the end masses ``mu0`` / ``mu1`` (V,): returns ``(solution, run_history)`` as ``solver_socp(n_time,
@@ -1149,46 +1181,35 @@ class SolveSession:
         unknown = set(per_solve) - set(SESSION_SOLVE_KEYS)
         if unknown:
             raise ValueError(f"SolveSession.solve: unknown option(s) {sorted(unknown)}; known: {list(SESSION_SOLVE_KEYS)}")
-        if read_out is not None and outputs is not None:
-            raise ValueError("SolveSession.solve: outputs and read_out are mutually exclusive (read_out returns mu and E only)")
-        flow_map = check_flow_map(flow_map, n_time=self.n_time)
-        congestion = per_solve.get("congestion", self.options.get("congestion", 0.0) if self.alm is None else self.alm.congestion0)
-        sensitivity = check_sensitivity(sensitivity, congestion=congestion)
+        who = "SolveSession.solve"
         first = self.alm is None
-        m0, m1 = self._masses(mu0, mu1, to_host=first)
-        moved = None if vertices is None else self._moved(vertices)
+        congestion = per_solve.get("congestion", self.options.get("congestion", 0.0) if first else self.alm.congestion0)
+        flow_map, sensitivity = _requests(who, self.n_time, outputs, read_out, flow_map, sensitivity, [congestion])
+        m0, m1 = _end_masses(who, mu0, mu1, self.n_vertices, to_host=first)
+        given, host = (None, None) if vertices is None else _moved_vertices(who, vertices, self.n_vertices)
         t0 = time.perf_counter()
-        move_ms = None
+        restart_ms = move_ms = None
         if first:
             self.options.update(per_solve)
-            if moved is not None:
-                from .. import meshes
-
-                x = np.array(moved.detach().cpu().numpy() if _is_device_tensor(moved) else moved, dtype=np.float64)
-                t = np.asarray(self.geometry["triangles"])
-                area_t = meshes.triangle_areas(x, t)
-                self.geometry = {**self.geometry, "vertices": x, "area_triangles": area_t, "area_vertices": meshes.vertex_areas(self.n_vertices, t, area_t)}
+            if host is not None:
+                self.geometry = _moved_geometry(self.geometry, host)
             self.alm = AlmSolver(self.n_time, {**self.geometry, "mu0": m0.copy(), "mu1": m1.copy()}, **self.options)
-            warm, restart_ms = False, None
         else:
-            more = {} if moved is None else {"vertices": moved}      # (without vertices the call is the one a session always made)
+            more = {} if given is None else {"vertices": given}      # (without vertices the call is the one a session always made)
             restart_ms = self.alm.restart(m0, m1, warm=bool(warm), **more, **per_solve)
-            if moved is not None:
+            if given is not None:
                 move_ms = self.alm.move_ms
-                self.geometry = {k: v for k, v in self.alm.geometry.items() if k not in ("mu0", "mu1")}
-        setup = time.perf_counter() - t0
-        if first:
-            self.setup_seconds = setup
+                self.geometry = _without_masses(self.alm.geometry)
+        record = self._admitted(first, warm, restart_ms, time.perf_counter() - t0, host is not None, move_ms)
         alm = self.alm
         for _ in range(alm.nit):
             if alm.iterate():
                 break
         solution, hist = alm.finalize(outputs=outputs, read_out=read_out, flow_map=flow_map, sensitivity=sensitivity)
-        hist.solver_stats["session"] = {"index": self.index, "warm": bool(warm), "restart_ms": restart_ms, "setup_seconds": setup,
-                                        "setup_seconds_saved": 0.0 if first else self.setup_seconds,
-                                        "moved": moved is not None, "move_ms": move_ms}
+        hist.solver_stats["session"] = record
         self.index += 1
         return solution, hist
+
 
 
 # ---- several problems on one surface, one factor ---------------------------------------------------------------------------
@@ -1270,61 +1291,90 @@ def solver_socp_many(n_time, geometry, problems, *, max_batch=4, read_out=None, 
     mu0 / mu1 and congestion); so is ``outputs`` (the arrays that are downloaded; exclusive with ``read_out``).  ``plan``: the device
     plan of this mesh to number it by (``geometry.build_plan``, ``geometry.plan_with_vertices``) instead of building one: the nested
     dissection reads the positions, so a mesh that moved keeps the numbering of a live context only through its plan."""
-    from .. import geometry as geo
-
-    if read_out is not None and outputs is not None:
-        raise ValueError("solver_socp_many: outputs and read_out are mutually exclusive (read_out returns mu and E only)")
-    flow_map = check_flow_map(flow_map, n_time=n_time)
+    who = "solver_socp_many"
     probs = _batch_problems(geometry, problems, common)
-    for p in probs:
-        sensitivity = check_sensitivity(sensitivity, congestion=p.get("congestion", 0.0))
+    flow_map, sensitivity = _requests(who, n_time, outputs, read_out, flow_map, sensitivity, [p.get("congestion", 0.0) for p in probs])
     if int(max_batch) < 1:
         raise ValueError("solver_socp_many: max_batch >= 1")
     solver_kw = _batch_solver_options(common)
     if plan is not None and (plan.n_time != int(n_time) or plan.n_vertices != np.asarray(geometry["vertices"]).shape[0]
                              or plan.n_triangles != np.asarray(geometry["triangles"]).shape[0]):
         raise ValueError("solver_socp_many: plan is not a plan of this mesh and n_time")
-    mesh = {k: v for k, v in geometry.items() if k not in ("mu0", "mu1")}
-    base = plan if plan is not None else geo.build_plan(n_time, {**mesh, "mu0": probs[0]["mu0"], "mu1": probs[0]["mu1"]},
-                                                        reorder=solver_kw["reorder"], nd_leaf=solver_kw["nd_leaf"])
-    results = [None] * len(probs)
-    pending = list(range(len(probs)))
-    active, done = [], []          # (index, AlmSolver)
+    mesh = _without_masses(geometry)
+    base = plan if plan is not None else _base_plan(n_time, mesh, probs[0], solver_kw)
 
-    def admit(owner_dev):
-        i = pending.pop(0)
+    def admit(slot, i, owner):
         p = probs[i]
-        opts = {k: v for k, v in p.items() if k not in ("mu0", "mu1")}
-        alm = AlmSolver(n_time, {**mesh, "mu0": p["mu0"], "mu1": p["mu1"]}, plan=geo.plan_with_densities(base, p["mu0"], p["mu1"]),
-                        front_owner=owner_dev, **solver_kw, **opts)
-        if owner_dev is None:
-            _needs_shared_factor("solver_socp_many", alm)
-        active.append((i, alm))
+        return _new_member(who, n_time, mesh, base, p["mu0"], p["mu1"], owner, solver_kw, **_without_masses(p))
 
+    # a slot per problem, at most max_batch of them running: the members step in the order they were admitted in
+    return _run_slots(len(probs), int(max_batch), lambda i, running: i if len(running) < int(max_batch) else None, admit,
+                      dict(outputs=outputs, read_out=read_out, flow_map=flow_map, sensitivity=sensitivity))
+
+
+def _base_plan(n_time, mesh, p, solver_kw):
+    """The plan every solver of a batch on ``mesh`` is built on, up to its densities (here those of problem ``p``)"""
+    from .. import geometry as geo
+
+    return geo.build_plan(n_time, {**mesh, "mu0": p["mu0"], "mu1": p["mu1"]}, reorder=solver_kw["reorder"], nd_leaf=solver_kw["nd_leaf"])
+
+
+def _new_member(who, n_time, mesh, base, mu0, mu1, owner, solver_kw, **run):
+    """A new solver of a batch on ``mesh`` with the end masses ``mu0`` / ``mu1``: ``base`` with these densities, and the factor of
+    ``owner``, a solver that holds it -- None: this one builds it, and must not fall back to the PCG."""
+    from .. import geometry as geo
+
+    alm = AlmSolver(n_time, {**mesh, "mu0": mu0, "mu1": mu1}, plan=geo.plan_with_densities(base, mu0, mu1),
+                    front_owner=None if owner is None else owner.dev, **solver_kw, **run)
+    if owner is None:
+        _needs_shared_factor(who, alm)
+    return alm
+
+
+def _run_slots(n_problems, max_batch, slot_for, admit, requests, harvested=None, keep=False, live=()):
+    """The loop of the batch drivers: while problems are pending or running, admit into free slots, step every running solver once
+    (``_lockstep``: in slot order, in groups of ``max_batch``), finalize those that finished and write their ``solver_stats["batch"]``.
+    Returns ``[(solution, run_history), ...]`` in input order.
+    ``slot_for(i, running)``: the slot the first pending problem ``i`` may take now (``running``: the slots in use), or None: it waits.
+    ``admit(slot, i, owner)``: returns the solver, new or restarted, that now runs problem ``i``; ``owner``: a live holder of the factor
+    -- the first that runs as the round begins, else that the last round harvested, else of ``live`` (the caller's idle solvers) --,
+    or None: the first admitted builds the factor and is the owner from then on.  ``requests``: the keywords of ``finalize``;
+    ``harvested(slot, i, run_history)``: the caller's hook after it.  ``keep``: the solvers stay the caller's; else a harvested one is
+    closed after the next admissions, so that a holder of the factor store is alive throughout, and all of them however the loop ends."""
+    results = [None] * n_problems
+    pending = list(range(n_problems))
+    running, retired = {}, []      # slot -> (problem, solver); the harvested solvers that are still to be closed
     try:
-        while pending or active:
-            holder = next((a.dev for _, a in active + done), None)
-            while pending and len(active) < int(max_batch):
-                admit(holder)
-                holder = holder or active[-1][1].dev
-            for i, alm in done:
+        while pending or running:
+            owner = next(iter([running[slot][1] for slot in sorted(running)] + retired + list(live)), None)      # (one for the whole round)
+            while pending:
+                slot = slot_for(pending[0], running)
+                if slot is None:
+                    break
+                i = pending.pop(0)
+                running[slot] = (i, admit(slot, i, owner))
+                owner = owner or running[slot][1]
+            for alm in retired:
                 alm.close()
-            done = []
-            _lockstep([alm for _, alm in active], int(max_batch))
-            still = []
-            for i, alm in active:
+            retired = []
+            _lockstep([running[slot][1] for slot in sorted(running)], max_batch)
+            for slot in sorted(running):
+                i, alm = running[slot]
                 if alm.finished:
-                    sol, hist = alm.finalize(outputs=outputs, read_out=read_out, flow_map=flow_map, sensitivity=sensitivity)
-                    hist.solver_stats["batch"] = {"size": len(probs), "index": i, "max_batch": int(max_batch), "steps_time_note": BATCH_TIME_NOTE}
+                    sol, hist = alm.finalize(**requests)
+                    hist.solver_stats["batch"] = {"size": n_problems, "index": i, "max_batch": max_batch, "steps_time_note": BATCH_TIME_NOTE}
+                    if harvested is not None:
+                        harvested(slot, i, hist)
                     results[i] = (sol, hist)
-                    done.append((i, alm))
-                else:
-                    still.append((i, alm))
-            active = still
+                    del running[slot]
+                    if not keep:
+                        retired.append(alm)
     finally:
-        for _, alm in active + done:
-            alm.close()
+        if not keep:
+            for alm in [alm for _, alm in running.values()] + retired:
+                alm.close()
     return results
+
 
 
 def _lockstep(solvers, max_batch):
@@ -1369,7 +1419,7 @@ BATCH_SESSION_FIXED = ("tau", "is_palm", "is_z_scaling", "is_constant_scaling", 
 BATCH_SOLVE_DEFAULTS = {"nit": 1000, "tol": 1e-4, "tol_checkpoints": None, "time_limit": 1000, "congestion": 0.0}      # SESSION_SOLVE_KEYS as a new AlmSolver has them
 
 
-class BatchSession:
+class BatchSession(_Session):
     """Live device contexts on ONE shared factor for a sequence of batches of transport problems on one surface, whose end masses --
     and vertex positions -- change from call to call: ``with BatchSession(n_time, geometry, max_batch=4) as bs: results =
     bs.solve_many(problems)``.  What ``solver_socp_many`` is to ``solver_socp``, this is to ``SolveSession``.
@@ -1390,8 +1440,7 @@ class BatchSession:
             raise ValueError(f"BatchSession: unknown option(s) {sorted(unknown)}; known: {list(COMMON_KEYS + BATCH_SESSION_FIXED)}")
         if options.get("lap_solver", "modal_direct") != "modal_direct":
             raise ValueError("BatchSession: the batch shares the factor of the direct solver: lap_solver must be 'modal_direct'")
-        if not isinstance(geometry, dict) or "vertices" not in geometry or "triangles" not in geometry:
-            raise ValueError("BatchSession: geometry must be a dict with 'vertices' and 'triangles'")
+        _Session.__init__(self, "BatchSession", geometry)
         if int(max_batch) < 1:
             raise ValueError("BatchSession: max_batch >= 1")
         slots = int(max_batch) if slots is None else int(slots)
@@ -1400,27 +1449,13 @@ class BatchSession:
         check_time_nodes(n_time, "modal_direct")
         self.n_time, self.max_batch = int(n_time), int(max_batch)
         self.solver_kw = {**_batch_solver_options(options), **{k: options[k] for k in BATCH_SESSION_FIXED if k in options}}
-        self.geometry = {k: v for k, v in geometry.items() if k not in ("mu0", "mu1")}
         self.default_masses = {k: geometry[k] for k in ("mu0", "mu1") if k in geometry}
-        self.n_vertices = int(np.asarray(geometry["vertices"]).shape[0])
         self.solvers = [None] * slots   # AlmSolver per slot, or None: not created yet
         self.solved = [False] * slots   # the slot's context holds the iterate of a finished solve
         self.base = None                # the plan every context is built on, up to the densities; follows the moves
-        self.index = 0                  # problems admitted so far
-        self.setup_seconds = None       # of the first context: plan, factor, context
-        self.closed = False
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def close(self):
-        self.closed = True
-        for alm in self.solvers:
-            if alm is not None:
-                alm.close()
+    def _live(self):
+        return [alm for alm in self.solvers if alm is not None]
 
     def _problems(self, problems):
         """The checks of ``solve_many`` on its problems, before any device is touched: dicts with host masses and every key of
@@ -1438,17 +1473,11 @@ class BatchSession:
                 if k not in ("mu0", "mu1") + SESSION_SOLVE_KEYS:
                     raise ValueError(f"BatchSession.solve_many: unknown per-problem option '{k}' (problem {i}); known: {list(('mu0', 'mu1') + SESSION_SOLVE_KEYS)}")
             for k in ("mu0", "mu1"):
-                a = p.get(k)
-                if a is None:
+                if p.get(k) is None:
                     if k not in self.default_masses:
                         raise ValueError(f"BatchSession.solve_many: problem {i} has no {k}")
-                    a = self.default_masses[k]
-                a = np.asarray(a.detach().cpu().numpy() if type(a).__module__.startswith("torch") else a, dtype=np.float64)
-                if a.shape != (self.n_vertices,):
-                    raise ValueError(f"BatchSession.solve_many: problem {i}: {k} must have shape ({self.n_vertices},), got {a.shape}")
-                if not np.all(np.isfinite(a)):
-                    raise ValueError(f"BatchSession.solve_many: problem {i}: {k} has entries that are not finite")
-                p[k] = a
+                    p[k] = self.default_masses[k]
+            p["mu0"], p["mu1"] = _end_masses(f"BatchSession.solve_many: problem {i}", p["mu0"], p["mu1"], self.n_vertices, to_host=True)
             p = {**BATCH_SOLVE_DEFAULTS, **p}
             _validate_checkpoints(p["tol_checkpoints"], p["tol"])
             if int(p["nit"]) < 1:
@@ -1456,68 +1485,41 @@ class BatchSession:
             out.append(p)
         return out
 
-    def _moved(self, vertices):
-        """``vertices`` as the session takes them: ``(what the device call reads, the host array)``."""
-        on_device = _is_device_tensor(vertices)
-        shape = tuple(vertices.shape) if on_device else None
-        host = np.asarray(vertices.detach().cpu().numpy() if type(vertices).__module__.startswith("torch") else vertices, dtype=np.float64)
-        if (shape or host.shape) != (self.n_vertices, 3):
-            raise ValueError(f"BatchSession.solve_many: vertices must have shape ({self.n_vertices}, 3), got {shape or host.shape}")
-        if not np.all(np.isfinite(host)):
-            raise ValueError("BatchSession.solve_many: vertices has entries that are not finite")
-        return (vertices if on_device else host), np.array(host)
-
-    def _move(self, moved):
+    def _move(self, given, host):
         """All live contexts to other positions with ONE refresh of the factor (device.move_vertices_many); the session's geometry and
         plan, and every solver's geometry, follow.  Without a live context the positions replace the session's.  Returns the times."""
         from ..device import move_vertices_many
 
-        given, host = moved
-        live = [alm for alm in self.solvers if alm is not None]
-        ms = move_vertices_many([alm.dev for alm in live], given, device_pointers=_is_device_tensor(given)) if live else None
+        live = self._live()
+        if not live:
+            self.geometry = _moved_geometry(self.geometry, host)
+            return None
+        ms = move_vertices_many([alm.dev for alm in live], given, device_pointers=_is_device_tensor(given))
         for alm in live:
             alm._geometry_moved(host)
             alm.move_ms = ms
-        if live:
-            self.base = live[0].dev.plan
-            self.geometry = {k: v for k, v in live[0].geometry.items() if k not in ("mu0", "mu1")}
-        else:
-            from .. import meshes
-
-            t = np.asarray(self.geometry["triangles"])
-            area_t = meshes.triangle_areas(host, t)
-            self.geometry = {**self.geometry, "vertices": host, "area_triangles": area_t, "area_vertices": meshes.vertex_areas(self.n_vertices, t, area_t)}
+        self.base = live[0].dev.plan
+        self.geometry = _without_masses(live[0].geometry)
         return ms
 
-    def _admit(self, slot, p, warm):
+    def _admit(self, slot, p, warm, owner, moved, move_ms):
         """Problem ``p`` into ``slot``: a new solver on the session's plan where the slot has no context yet, else a restart of the
-        one it has.  Returns the record ``solver_stats["session"]`` starts from."""
-        from .. import geometry as geo
-
+        one it has.  Returns the solver and its ``solver_stats["session"]`` (``moved``, ``move_ms``: this call's move, for the record)."""
         t0 = time.perf_counter()
         run = {k: p[k] for k in SESSION_SOLVE_KEYS}
         alm, restart_ms = self.solvers[slot], None
-        created = alm is None
-        if created:
+        built = alm is None
+        if built:
             if self.base is None:
-                self.base = geo.build_plan(self.n_time, {**self.geometry, "mu0": p["mu0"], "mu1": p["mu1"]}, reorder=self.solver_kw["reorder"],
-                                           nd_leaf=self.solver_kw["nd_leaf"])
-            owner = next((a.dev for a in self.solvers if a is not None), None)
-            alm = AlmSolver(self.n_time, {**self.geometry, "mu0": p["mu0"].copy(), "mu1": p["mu1"].copy()},
-                            plan=geo.plan_with_densities(self.base, p["mu0"], p["mu1"]), front_owner=owner, **self.solver_kw, **run)
-            if owner is None:
-                _needs_shared_factor("BatchSession", alm)
+                self.base = _base_plan(self.n_time, self.geometry, p, self.solver_kw)
+            alm = _new_member("BatchSession", self.n_time, self.geometry, self.base, p["mu0"].copy(), p["mu1"].copy(), owner, self.solver_kw, **run)
             self.solvers[slot] = alm
         else:
             restart_ms = alm.restart(p["mu0"], p["mu1"], warm=warm, batch_member=True, **run)
         self.solved[slot] = False
-        setup = time.perf_counter() - t0
-        if self.setup_seconds is None:
-            self.setup_seconds = setup
-        record = {"index": self.index, "warm": bool(warm) and not created, "restart_ms": restart_ms, "setup_seconds": setup,
-                  "setup_seconds_saved": 0.0 if created else self.setup_seconds}
+        record = self._admitted(built, warm, restart_ms, time.perf_counter() - t0, moved, move_ms)
         self.index += 1
-        return record
+        return alm, record
 
     def solve_many(self, problems, warm=False, vertices=None, outputs=None, read_out=None, flow_map=None, sensitivity=None):
         """Solve ``problems`` -- dicts with ``mu0``, ``mu1`` (V,) and any of ``nit``, ``tol``, ``tol_checkpoints``, ``time_limit``,
@@ -1539,12 +1541,9 @@ class BatchSession:
         same in every problem's record)}."""
         if self.closed:
             raise ValueError("BatchSession.solve_many: the session is closed")
-        if read_out is not None and outputs is not None:
-            raise ValueError("BatchSession.solve_many: outputs and read_out are mutually exclusive (read_out returns mu and E only)")
-        flow_map = check_flow_map(flow_map, n_time=self.n_time)
+        who = "BatchSession.solve_many"
         probs = self._problems(problems)
-        for p in probs:
-            sensitivity = check_sensitivity(sensitivity, congestion=p["congestion"])
+        flow_map, sensitivity = _requests(who, self.n_time, outputs, read_out, flow_map, sensitivity, [p["congestion"] for p in probs])
         slots = len(self.solvers)
         if warm:
             if len(probs) > slots:
@@ -1555,30 +1554,25 @@ class BatchSession:
                 refusal = self.solvers[i]._warm_refusal()
                 if refusal:
                     raise ValueError(f"BatchSession.solve_many: problem {i}: {refusal}")
-        moved = None if vertices is None else self._moved(vertices)
-        for alm in self.solvers:
-            if alm is not None:
-                alm.move_ms = None
-        move_ms = None if moved is None else self._move(moved)
-        results = [None] * len(probs)
-        pending = list(range(len(probs)))
-        active = {}         # slot -> (problem index, the start of its session record)
-        while pending or active:
-            for slot in range(slots):
-                if pending and slot not in active and (not warm or slot == pending[0]):
-                    i = pending.pop(0)
-                    active[slot] = (i, self._admit(slot, probs[i], bool(warm)))
-            _lockstep([self.solvers[slot] for slot in sorted(active)], self.max_batch)
-            for slot in sorted(active):
-                alm = self.solvers[slot]
-                if alm.finished:
-                    i, record = active.pop(slot)
-                    sol, hist = alm.finalize(outputs=outputs, read_out=read_out, flow_map=flow_map, sensitivity=sensitivity)
-                    hist.solver_stats["batch"] = {"size": len(probs), "index": i, "max_batch": self.max_batch, "steps_time_note": BATCH_TIME_NOTE}
-                    hist.solver_stats["session"] = {**record, "moved": moved is not None, "move_ms": move_ms}
-                    results[i] = (sol, hist)
-                    self.solved[slot] = True
-        return results
+        given, host = (None, None) if vertices is None else _moved_vertices(who, vertices, self.n_vertices)
+        for alm in self._live():
+            alm.move_ms = None
+        move_ms = None if host is None else self._move(given, host)
+        records = {}        # problem -> its session record
+
+        def slot_for(i, running):      # (warm: problem i runs in slot i; else the first free slot takes the first pending problem)
+            return next((slot for slot in ([i] if warm else range(slots)) if slot not in running), None)
+
+        def admit(slot, i, owner):
+            alm, records[i] = self._admit(slot, probs[i], bool(warm), owner, host is not None, move_ms)
+            return alm
+
+        def harvested(slot, i, hist):
+            hist.solver_stats["session"] = records[i]
+            self.solved[slot] = True
+
+        return _run_slots(len(probs), self.max_batch, slot_for, admit, dict(outputs=outputs, read_out=read_out, flow_map=flow_map, sensitivity=sensitivity),
+                          harvested, keep=True, live=self._live())
 
 
 # ---- coarse-to-fine cascades: what the drivers share ---------------------------------------------------------------------------------

@@ -208,6 +208,146 @@ def print_recorded_scalars():
     pprint.pprint(out, width=150, sort_dicts=False)
 
 
+# ---- the device calls of the four drivers, in order ------------------------------------------------------------------------------------
+def driver_calls(monkeypatch_setattr):
+    """One fixed script through solver_socp, solver_socp_many, SolveSession and BatchSession on the RecordingDevice: returns ``(log,
+    stats)``.  ``log``: the calls create, share_frontal, setup_frontal, upload, restart, move_vertices, move_vertices_many, step (one
+    solver's loop), step_many (a lockstep group), finalize and close in the order the drivers make them, each with the number of its
+    device (the order of creation within a driver: a session's slot) and, where it has one, the problem (the letter of its end masses
+    in ``named`` below) and cold / warm.  ``stats``: ``(driver, solver_stats)`` of every result in the order returned, times masked.
+    The lockstep iteration is replaced by one that runs every member for a scripted number of rounds, so that slots refill unevenly;
+    ``AlmSolver.iterate`` by one step that ends the run; ``finalize`` by an empty record that logs tau, nit and tol.
+    test_driver_calls_cpu.py holds what this returned before the drivers shared their intake, slot loop and admission:
+        python -c "import sys; sys.path[:0] = ['tests', '.']; import session_checks as s; s.print_driver_calls()"
+    """
+    import importlib
+
+    ss = importlib.import_module("dots_socp_amd.socp.solver_socp")
+    mesh, (mu0, mu1), (_, mu1b) = problems("plane")
+    n_time, V = CASES["plane"][0], mesh["vertices"].shape[0]
+    named = {"A": (mu0, mu1), "B": (mu0, mu1b), "C": (mu1, mu0), "D": (mu1b, mu0), "E": (mu1, mu1b)}
+    P = {k: dict(mu0=a, mu1=b) for k, (a, b) in named.items()}
+    moved = np.array(mesh["vertices"], dtype=np.float64)
+    moved[:, 2] += 0.02 * np.sin(2.0 * np.pi * moved[:, 0])
+    log, made, script = [], [], []
+
+    def letter(a, b):
+        return next((k for k, (x, y) in named.items() if np.array_equal(x, a) and np.array_equal(y, b)), "?")
+
+    class Calls(list):
+        def __init__(self, tag):
+            super().__init__()
+            self.tag = tag
+
+        def append(self, name):
+            super().append(name)
+            if name in ("setup_frontal", "upload"):
+                log.append((name, self.tag))
+
+    class Device(RecordingDevice):
+        def __init__(self, n_time, geometry, **kw):
+            super().__init__(n_time, geometry, **kw)
+            made.append(self)
+            self.tag = len(made) - 1
+            self.calls = Calls(self.tag)
+            log.append(("create", self.tag, letter(geometry["mu0"], geometry["mu1"])))
+
+        def share_frontal(self, owner):
+            log.append(("share_frontal", self.tag, owner.tag))
+
+        def restart(self, mu0, mu1, mode="cold", factors=None, device_pointers=False):
+            log.append(("restart", self.tag, letter(mu0, mu1), mode))
+            return super().restart(mu0, mu1, mode, factors, device_pointers)
+
+        def apply_operator(self, *a, **kw):      # (an init_solution of phi alone derives the other arrays from it)
+            return np.zeros(1)
+
+        def move_vertices(self, vertices, device_pointers=False):
+            log.append(("move_vertices", self.tag))
+            return (0.125, 0.25, 0.5)
+
+        def close(self):
+            log.append(("close", self.tag))
+            super().close()
+
+    def lockstep(solvers, max_batch):
+        running = [a for a in solvers if not a.finished]
+        for at in range(0, len(running), max_batch):
+            log.append(("step_many", tuple(a.dev.tag for a in running[at:at + max_batch])))
+        for a in running:
+            if a.counter_main < 0:      # (a run that has not stepped yet takes the next scripted length)
+                a.rounds_left = script.pop(0) if script else 1
+            a.counter_main, a._last_quiet = a.counter_main + 1, False
+            a.rounds_left -= 1
+            a.finished = a.rounds_left == 0
+
+    def iterate(self):
+        log.append(("step", self.dev.tag))
+        self.counter_main, self._last_quiet, self.finished = self.counter_main + 1, False, True
+        return True
+
+    def finalize(self, **kw):
+        log.append(("finalize", self.dev.tag, letter(self.geometry["mu0"], self.geometry["mu1"]), self.tau, self.nit, self.tol))
+        return {"checkpoints": None}, types.SimpleNamespace(solver_stats={})
+
+    def move_vertices_many(devices, vertices, device_pointers=False):
+        log.append(("move_vertices_many", tuple(d.tag for d in devices)))
+        return (0.125, 0.25, 0.5)
+
+    monkeypatch_setattr(ss, "DeviceProblem", Device)
+    monkeypatch_setattr(ss, "_lockstep", lockstep)
+    monkeypatch_setattr(ss.AlmSolver, "iterate", iterate)
+    monkeypatch_setattr(ss.AlmSolver, "finalize", finalize)
+    monkeypatch_setattr(importlib.import_module("dots_socp_amd.device"), "move_vertices_many", move_vertices_many)
+
+    stats = []
+
+    def masked(d):
+        return {k: ({kk: ("t" if kk.startswith("setup_seconds") and vv else vv) for kk, vv in v.items()} if isinstance(v, dict) else v)
+                for k, v in d.items()}
+
+    def run(driver, call, stops=()):
+        del made[:]
+        script[:] = list(stops)
+        log.append(("driver", driver))
+        results = call()
+        for _, hist in ([results] if isinstance(results, tuple) else results):
+            stats.append((driver, masked(hist.solver_stats)))
+
+    run("solver_socp", lambda: ss.solver_socp(n_time, {**mesh, **P["A"]}, tol=TOL, nit=9))
+    refill = dict(P["C"], tau=1.7, init_solution={"phi": np.ones((n_time + 1, V))})
+    run("solver_socp_many", lambda: ss.solver_socp_many(n_time, mesh, [P["A"], P["B"], refill, P["D"], dict(P["E"], nit=11)], max_batch=2),
+        stops=[3, 1, 2, 2, 1])
+    with ss.SolveSession(n_time, {**mesh, **P["E"]}, tol=TOL, nit=9) as s:
+        run("SolveSession first", lambda: s.solve(*named["A"]))
+        run("SolveSession warm", lambda: s.solve(*named["B"], nit=11))
+        run("SolveSession vertices", lambda: s.solve(*named["C"], vertices=moved))
+        run("SolveSession cold", lambda: s.solve(*named["D"], warm=False))
+    with ss.BatchSession(n_time, mesh, max_batch=2, slots=3, tau=1.8) as bs:
+        run("BatchSession cold", lambda: bs.solve_many([P["A"], P["B"], dict(P["C"], nit=11), P["D"]]), stops=[1, 2, 1, 1])
+        run("BatchSession warm", lambda: bs.solve_many([P["B"], dict(P["A"], tol=TOL)], warm=True), stops=[2, 1])
+        run("BatchSession vertices", lambda: bs.solve_many([P["E"], P["D"], P["C"], P["B"], P["A"]], vertices=moved), stops=[2, 1, 1, 1, 1])
+    with ss.BatchSession(n_time, {**mesh, **P["E"]}, max_batch=2, slots=3) as bs:
+        run("BatchSession first vertices", lambda: bs.solve_many([P["A"], dict(mu1=mu1b)], vertices=moved), stops=[1, 1])
+    log.append(("driver", "end"))
+    return log, stats
+
+
+def print_driver_calls():
+    import pprint
+
+    from dots_socp_amd.socp.solver_socp import BATCH_TIME_NOTE
+
+    log, stats = driver_calls(setattr)
+    print("NOTE = " + repr(BATCH_TIME_NOTE))
+    print("LOG = ", end="")
+    pprint.pprint(log, width=150, compact=True)
+    print("STATS = [")
+    for entry in stats:
+        print("    " + repr(entry).replace(repr(BATCH_TIME_NOTE), "NOTE") + ",")
+    print("]")
+
+
 # ---- the bar of the warm torch function ----------------------------------------------------------------------------------------------
 # |cost(fresh cold) - cost(fresh host-warm)| and the largest absolute difference of each gradient between the same two solves of P2
 # at TOL (host-warm: init_solution = the whole solution of P1), both of which exist without a session; measured by

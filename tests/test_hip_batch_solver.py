@@ -83,3 +83,24 @@ def test_knot_batch_refills_slots_bit_for_bit():
         assert out[i][1].solver_stats["batch"]["index"] == i
         stops.add(int(alone[1].kkt_iteration[-1]))
     assert len(stops) > 1      # uneven stops: the refill was exercised
+
+
+def test_a_refilled_slot_builds_a_solver_with_its_own_options():
+    """Three problems on the plane with max_batch=2: the third takes the slot the first to stop leaves and is built there with its own
+    tau, without the z scaling and from the whole solution of the first problem; each result is its own solver_socp call's, bit for bit."""
+    import session_checks as sc
+    from dots_socp_amd.socp import solver_socp, solver_socp_many
+
+    n_time, cap = sc.CASES["plane"]
+    mesh, p1, p2 = sc.problems("plane")
+    run = dict(tol=sc.TOL, nit=cap)
+    probs = [dict(mu0=p1[0], mu1=p1[1], **run), dict(mu0=p2[0], mu1=p2[1], **run), dict(mu0=p1[1], mu1=p1[0], **run)]
+    alone = [solver_socp(n_time, {**mesh, "mu0": p["mu0"], "mu1": p["mu1"]}, **run) for p in probs[:2]]
+    probs[2].update(tau=1.7, is_z_scaling=False, init_solution={k: alone[0][0][k] for k in STATE})
+    alone.append(solver_socp(n_time, {**mesh, "mu0": probs[2]["mu0"], "mu1": probs[2]["mu1"]},
+                             **{k: v for k, v in probs[2].items() if k not in ("mu0", "mu1")}))
+    out = solver_socp_many(n_time, mesh, probs, max_batch=2)
+    for i, (got, want) in enumerate(zip(out, alone)):
+        assert_same_run(got, want)
+        assert got[1].solver_stats["batch"] == {**got[1].solver_stats["batch"], "size": 3, "index": i, "max_batch": 2}
+    assert not np.array_equal(out[2][0]["phi"], out[0][0]["phi"])      # (the third ran: it did not just keep what it started from)
