@@ -323,15 +323,17 @@ static int build(Ctx *c, const dots_problem_desc *p) {
     return 0;
 }
 
-// `reads_only`: the entry point changes neither the state nor the parameters.  Every other one drops a right-hand side that was
-// enqueued ahead of its iteration (DOTS_STEP_RHS_AHEAD): the next dots_step then computes it again.
-// A pending penalty division (Ctx::pending_div) carried out now: the stand-alone pass over the five dual arrays.
-static int flush_division(Ctx *c) {
-    if (c->pending_div == 0.0) return 0;
-    const double f = c->pending_div;
-    c->pending_div = 0.0;
-    return launch_adjust_penalty(c, f);
-}
+// The runtime's side of admission.h: every entry point opens with admit(c, E_...); what reads z_mid from memory says need_zmid
+static const Runtime RUNTIME = {
+    [](void *ctx) -> int {
+        const hipError_t e = hipSetDevice(static_cast<Ctx *>(ctx)->device);
+        return e == hipSuccess ? 0 : hip_fail(e, "hipSetDevice", __FILE__, __LINE__);
+    },
+    [](void *ctx, double factor) -> int { return launch_adjust_penalty(static_cast<Ctx *>(ctx), factor); },
+    [](void *ctx) -> int { return launch_rebuild_zmid(static_cast<Ctx *>(ctx)); }};
+static int admit(Ctx *c, Entry e) { return admit(c ? &c->carried : nullptr, e, RUNTIME, c); }
+static int need_zmid(Ctx *c, Entry e, bool argument = true) { return need_zmid(c->carried, e, RUNTIME, c, argument); }
+static int flush_division(Ctx *c) { return flush_division(c->carried, RUNTIME, c); }
 
 // The modal PCG keeps per-mode scalars for NC <= CgScalOffsets::NCMAX = 256 modes: a modal context of T + 1 > 256 steps with the
 // direct solver only (a factor installed or shared, and enabled), unless the caller switched the windowed PCG on (dots_pcg_windows).
@@ -342,28 +344,11 @@ static int modal_needs_factor(const Ctx *c, const char *what) {
     return DOTS_ERR_STATE;
 }
 
-// dots_move_vertices changed the surface under the iterate: what steps it or measures it waits for dots_restart
-static int moved_needs_restart(const Ctx *c, const char *what) {
-    if (!c || !c->needs_restart) return 0;
-    set_error(std::string(what) + ": the vertices were moved (dots_move_vertices): the context needs a dots_restart (cold or warm) first");
-    return DOTS_ERR_STATE;
-}
-
-// `keeps_division`: the entry point neither reads nor writes the dual arrays (or, dots_step, applies a pending division itself).
-static int check(dots_ctx *ctx, bool reads_only = false, bool keeps_division = false) {
-    if (!ctx) { set_error("null context"); return DOTS_ERR_ARGUMENT; }
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice", __FILE__, __LINE__);
-    if (!reads_only) ctx->rhs_ahead = ctx->rhs_ahead_armed = ctx->penalty_armed = ctx->carry_valid = ctx->kkt_fused_valid = ctx->step_path = ctx->deep_path = 0;      // (the carried gathers / fused sums belong to the state steps 2+3 left)
-    if (!keeps_division) return flush_division(ctx);
-    return 0;
-}
-
 // first half of an iteration: right-hand side + solve (for this context's modes)
 static int palm_step0(Ctx *c) {
     if (!c->step_palm) return 0;
-    if (c->zmid_stale) { set_error("step: DOTS_STEP_PALM needs z_mid of the previous iteration in memory"); return DOTS_ERR_STATE; }
-    c->carry_valid = c->kkt_fused_valid = c->step_path = c->deep_path = 0;      // step 0 moves A, B and lambda_c
+    if (int rc = refuse_unspecified_zmid(c->carried, E_STEP)) return rc;
+    c->carried.drop_for_step0();
     return launch_q_lambda_only(c);
 }
 
@@ -405,12 +390,12 @@ static int slab_stage(Ctx *c, int stage) {
             return cg_solve(c, nullptr);
         case 3:       // inverse transform for this slab, steps 2 and 3
             if ((rc = cg_finish_sharded(c))) return rc;
-            c->zmid_stale = c->step_skip_zmid;
-            c->kkt_halo_fresh = 0;
+            c->carried.stepped(c->step_skip_zmid);
+            state_changed(c->carried);
             if (d.nl == 0) return 0;
             return launch_q_lambda_mult(c, c->step_skip_zmid ? 2 : 1);
         case 4:       // halos of the KKT kernels
-            c->kkt_halo_fresh = 1;
+            c->carried.kkt_halo_fresh = 1;
             return launch_slab_pack_kkt(c);
         default:
             set_error("slab_stage: unknown stage");
@@ -446,29 +431,30 @@ static int iteration_before(Ctx *c, bool timed, IterPlan &p, hipEvent_t *tv) {
     int rc;
 #define MARK(i) do { if (tv) DOTS_HIP(hipEventRecord(tv[i], c->stream)); } while (0)
     MARK(0);
-    if (c->zmid_deferred) {      // nobody asked for the last iterate's z_mid: its storage (holding the old beta_mid) is simply stale
-        if (c->step_palm) { if ((rc = materialise_zmid(c))) return rc; }      // (step 0 reads z_mid)
-        else { c->zmid_deferred = 0; c->zmid_stale = 1; }
+    Carried &k = c->carried;
+    if (k.zmid == ZMID_DEFERRED) {      // nobody asked for the last iterate's z_mid: its storage (holding the old beta_mid) is simply stale
+        if (c->step_palm) { if ((rc = rebuild_zmid(k, RUNTIME, c))) return rc; }      // (step 0 reads z_mid)
+        else k.zmid = ZMID_UNSPECIFIED;
     }
     // a pending penalty division rides in this iteration's kernels when both of them can apply it; otherwise it is carried out first
     p.zmode = c->step_skip_zmid ? 2 : 1;
     p.dv = 0.0;
-    if (c->pending_div != 0.0) {
-        if (!timed && !c->step_palm && c->rhs_ahead == 2 && c->ahead_div == c->pending_div && ql_divides(c, p.zmode)) {
-            p.dv = c->pending_div;      // the launch ahead (penalty_decision_ahead) divided as it read: steps 2+3 do the same and write back divided
-            c->pending_div = 0.0;
-        } else if (!timed && !c->step_palm && !c->rhs_ahead && rhs_divides(c) && ql_divides(c, p.zmode)) {
-            p.dv = c->pending_div;
-            c->pending_div = 0.0;
+    if (k.pending_div != 0.0) {
+        if (!timed && !c->step_palm && k.rhs_ahead == 2 && k.ahead_div == k.pending_div && ql_divides(c, p.zmode)) {
+            p.dv = k.pending_div;      // the launch ahead (penalty_decision_ahead) divided as it read: steps 2+3 do the same and write back divided
+            k.pending_div = 0.0;
+        } else if (!timed && !c->step_palm && !k.rhs_ahead && rhs_divides(c) && ql_divides(c, p.zmode)) {
+            p.dv = k.pending_div;
+            k.pending_div = 0.0;
         } else if ((rc = flush_division(c))) return rc;      // (a launch ahead that divided as it read saw the values the arrays now hold)
     }
-    c->ahead_div = 0.0;
+    k.ahead_div = 0.0;
     if ((rc = palm_step0(c))) return rc;
     // the right-hand side of this iteration was enqueued behind the KKT kernels of the last one (DOTS_STEP_RHS_AHEAD) and nothing
     // it reads has changed since: start at the solve; the projection then runs with the inverse transform
-    p.ahead_kind = (c->step_palm || c->rhs_ahead > 2) ? 0 : c->rhs_ahead;      // (3, 4: an anticipated penalty update the caller did not confirm)
+    p.ahead_kind = (c->step_palm || k.rhs_ahead > 2) ? 0 : k.rhs_ahead;      // (3, 4: an anticipated penalty update the caller did not confirm)
     const bool ahead = p.ahead_kind != 0;
-    c->rhs_ahead = 0;
+    k.rhs_ahead = 0;
     if (p.ahead_kind == 2) {      // the projection ran ahead too: its results become the current z_fst, z_end and cone multiplier
         std::swap(c->d.zf, c->zf_alt);
         std::swap(c->d.ze, c->ze_alt);
@@ -478,7 +464,7 @@ static int iteration_before(Ctx *c, bool timed, IterPlan &p, hipEvent_t *tv) {
         c->dcg.lamc = c->dgt.lamc = c->d.lamc;
     }
     if (timed) return 0;      // (the timed path of run_iteration_body goes on itself)
-    c->zmid_stale = c->step_skip_zmid;
+    k.stepped(c->step_skip_zmid);
     p.fused_rhs = rhs_writes_modes(c) && !ahead;      // [right-hand side + projection] -> sweeps -> inverse transform -> steps 2+3
     p.fuse = !p.fused_rhs && soc_takes_inverse(c) && p.ahead_kind != 2;
     if (p.fused_rhs) { if ((rc = launch_rhs(c, true, p.dv))) return rc; }
@@ -527,7 +513,7 @@ static int run_iteration_body(Ctx *c, dots_step_stats *st, hipEvent_t *tv) {
     if (ahead_kind != 2 && (rc = launch_soc_projection(c, 1, fuse))) return rc;
     DOTS_HIP(hipEventRecord(c->ev[3], c->stream));
     if ((rc = launch_q_lambda_mult(c, c->step_skip_zmid ? 2 : 1))) return rc;
-    c->zmid_stale = c->step_skip_zmid;
+    c->carried.stepped(c->step_skip_zmid);
     DOTS_HIP(hipEventRecord(c->ev[4], c->stream));
     DOTS_HIP(hipEventSynchronize(c->ev[4]));
     float t;
@@ -626,22 +612,22 @@ int dots_destroy(dots_ctx *c) {
 
 int dots_set_params(dots_ctx *c, const dots_params *p) {
     // the penalty update the library anticipated (penalty_decision_ahead): only r moves, to the anticipated value
-    const bool anticipated = c && p && c->rhs_ahead == 4 && p->r == c->ahead_r && p->scale_z == c->prm.scale_z && p->const_d == c->prm.const_d &&
+    const bool anticipated = c && p && c->carried.rhs_ahead == 4 && p->r == c->ahead_r && p->scale_z == c->prm.scale_z && p->const_d == c->prm.const_d &&
                              p->eps == c->prm.eps && p->boundary_scale == c->prm.boundary_scale && p->congestion == c->prm.congestion && p->tau == c->prm.tau;
-    int rc = check(c, false, true);
+    int rc = admit(c, E_SET_PARAMS);
     if (rc) return rc;
     if (!p || !(p->r > 0) || !(p->scale_z > 0) || !(p->cg_tol > 0) || p->eps < 0 || !(p->boundary_scale > 0)) { set_error("bad parameters"); return DOTS_ERR_ARGUMENT; }
     c->prm = *p;
-    if (anticipated && c->pending_div == c->ahead_dv) {
-        c->rhs_ahead = 2;
-        c->ahead_div = c->ahead_dv;
+    if (anticipated && c->carried.pending_div == c->ahead_dv) {
+        c->carried.rhs_ahead = 2;
+        c->carried.ahead_div = c->ahead_dv;
         c->penalty_ahead_confirmed += 1;
     }
     return 0;
 }
 
 int dots_penalty_ahead(dots_ctx *c, const dots_penalty_policy *policy) {
-    int rc = check(c, true, true);
+    int rc = admit(c, E_PENALTY_AHEAD);
     if (rc) return rc;
     if (c->batched) { set_error("penalty_ahead: the context is stepped in a batch (dots_step_many)"); return DOTS_ERR_STATE; }
     if (!policy || policy->n_steps < 0 || policy->n_steps > 16 || !(policy->tol > 0) || !(policy->r_lower > 0) || !(policy->r_upper >= policy->r_lower)) {
@@ -649,7 +635,7 @@ int dots_penalty_ahead(dots_ctx *c, const dots_penalty_policy *policy) {
         return DOTS_ERR_ARGUMENT;
     }
     c->penalty_policy = *policy;
-    c->penalty_armed = 1;
+    c->carried.penalty_armed = 1;
     return 0;
 }
 int dots_get_params(dots_ctx *c, dots_params *p) {
@@ -658,7 +644,7 @@ int dots_get_params(dots_ctx *c, dots_params *p) {
     return 0;
 }
 int dots_sync(dots_ctx *c) {
-    int rc = check(c, true, true);
+    int rc = admit(c, E_SYNC);
     if (rc) return rc;
     DOTS_HIP(hipStreamSynchronize(c->stream));
     return 0;
@@ -671,14 +657,14 @@ int64_t dots_array_count(dots_ctx *c, int id) {
 int64_t dots_device_bytes(dots_ctx *c) { return c ? c->pool.bytes() : -1; }
 
 int dots_upload(dots_ctx *c, int id, const double *host, int64_t count) {
-    int rc = check(c);
+    int rc = admit(c, E_UPLOAD);
     if (rc) return rc;
     // a time slab that has a next slab may bring phi at that slab's first node along, as one more row: it becomes phi_hi, which only
     // this rank's inverse transform writes otherwise (step 0 of DOTS_STEP_PALM and the KKT kernels read it before the first solve)
     const bool with_hi = id == DOTS_PHI && host && c->d.slab && c->d.phi_hi && c->d.nl > 0 && c->d.t0 + c->d.nl <= c->d.T &&
                          count == array_count_host(c->d, id) + c->d.V && count <= c->stage_count;
     if (id < 0 || id >= DOTS_N_ARRAYS || !host || (count != array_count_host(c->d, id) && !with_hi)) { set_error("upload: bad array id or element count"); return DOTS_ERR_ARGUMENT; }
-    if (id != DOTS_Z_MID && (rc = materialise_zmid(c))) return rc;
+    if ((rc = need_zmid(c, E_UPLOAD, id != DOTS_Z_MID))) return rc;
     DOTS_HIP(hipMemcpyAsync(c->stage, host, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, c->stream));
     if ((rc = launch_to_device_layout(c, id, c->arr(id), c->stage))) return rc;
     if (with_hi) {
@@ -686,16 +672,15 @@ int dots_upload(dots_ctx *c, int id, const double *host, int64_t count) {
         DOTS_HIP(hipGetLastError());
     }
     DOTS_HIP(hipStreamSynchronize(c->stream));
-    if (id == DOTS_Z_MID) { c->zmid_stale = 0; c->zmid_deferred = 0; }      // (the upload is what z_mid's storage now holds)
-    c->kkt_halo_fresh = 0;
+    if (id == DOTS_Z_MID) c->carried.zmid = ZMID_STORED;      // (the upload is what z_mid's storage now holds)
+    state_changed(c->carried);
     return 0;
 }
 int dots_download(dots_ctx *c, int id, double *host, int64_t count) {
-    int rc = check(c, true);
+    int rc = admit(c, E_DOWNLOAD);
     if (rc) return rc;
     if (id < 0 || id >= DOTS_N_ARRAYS || !host || count != array_count_host(c->d, id)) { set_error("download: bad array id or element count"); return DOTS_ERR_ARGUMENT; }
-    if (id == DOTS_Z_MID && c->zmid_stale) { set_error("download: z_mid was not materialised by the last step (dots_step_flags)"); return DOTS_ERR_STATE; }
-    if (id == DOTS_Z_MID && (rc = materialise_zmid(c))) return rc;
+    if ((rc = need_zmid(c, E_DOWNLOAD, id == DOTS_Z_MID))) return rc;
     if ((rc = launch_from_device_layout(c, id, c->arr(id), c->stage))) return rc;
     DOTS_HIP(hipMemcpyAsync(host, c->stage, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, c->stream));
     DOTS_HIP(hipStreamSynchronize(c->stream));
@@ -716,7 +701,7 @@ int64_t dots_slab_elems(dots_ctx *c, int which) {
 }
 
 int dots_slab_set_buffers(dots_ctx *c, const dots_slab_buffers *b) {
-    int rc = check(c);
+    int rc = admit(c, E_SLAB_SET_BUFFERS);
     if (rc) return rc;
     if (c->shard_stride == 0) { set_error("slab_set_buffers: context is not a time slab"); return DOTS_ERR_STATE; }
     if (!b || !b->send_x || !b->send_nsq || !b->recv_x || !b->recv_nsq || !b->b_send || !b->b_recv || !b->x_send || !b->x_recv ||
@@ -753,7 +738,7 @@ int dots_slab_set_buffers(dots_ctx *c, const dots_slab_buffers *b) {
 }
 
 int dots_slab_stage(dots_ctx *c, int stage, dots_step_stats *stats) {
-    int rc = check(c, true);      // (the stages say themselves what they invalidate: carried sums live from stage 3 to the next stages 0 and 1)
+    int rc = admit(c, E_SLAB_STAGE);
     if (rc) return rc;
     if (c->shard_stride == 0) { set_error("slab_stage: context is not a time slab"); return DOTS_ERR_STATE; }
     if (!c->slab.b_send) { set_error("slab_stage: no exchange buffers (dots_slab_set_buffers)"); return DOTS_ERR_STATE; }
@@ -794,7 +779,7 @@ int dots_slab_stage(dots_ctx *c, int stage, dots_step_stats *stats) {
 }
 
 int dots_stream_wait(dots_ctx *c, void *other_stream, int ctx_waits) {
-    int rc = check(c, true, true);      // (orders streams: changes neither state nor parameters)
+    int rc = admit(c, E_STREAM_WAIT);
     if (rc) return rc;
     hipStream_t other = (hipStream_t)other_stream;       // nullptr = the legacy default stream
     if (ctx_waits) {
@@ -808,9 +793,8 @@ int dots_stream_wait(dots_ctx *c, void *other_stream, int ctx_waits) {
 }
 
 int dots_step(dots_ctx *c, int n_iters, dots_step_stats *stats) {
-    int rc = check(c, true, true);      // (run_iteration consumes the flags and a pending penalty division itself)
+    int rc = admit(c, E_STEP);
     if (rc) return rc;
-    if ((rc = moved_needs_restart(c, "dots_step"))) return rc;
     c->batched = 0;
     if (n_iters < 0) { set_error("n_iters < 0"); return DOTS_ERR_ARGUMENT; }
     if (c->shard_stride != 0) { set_error("dots_step on a time slab: use dots_slab_stage"); return DOTS_ERR_STATE; }
@@ -824,11 +808,11 @@ int dots_step(dots_ctx *c, int n_iters, dots_step_stats *stats) {
 }
 
 int dots_step_flags(dots_ctx *c, uint32_t flags) {
-    int rc = check(c, true, true);
+    int rc = admit(c, E_STEP_FLAGS);
     if (rc) return rc;
     if (flags & ~(uint32_t)(DOTS_STEP_SKIP_Z_MID | DOTS_STEP_PALM | DOTS_STEP_RHS_AHEAD | DOTS_STEP_TIMED | DOTS_STEP_CARRY | DOTS_STEP_KKT_SUMS)) { set_error("step_flags: unknown flag"); return DOTS_ERR_ARGUMENT; }
     if ((flags & DOTS_STEP_RHS_AHEAD) && (flags & DOTS_STEP_PALM)) { set_error("step_flags: DOTS_STEP_RHS_AHEAD cannot be combined with DOTS_STEP_PALM (its step 0 changes what the right-hand side reads)"); return DOTS_ERR_ARGUMENT; }
-    c->rhs_ahead_armed = ((flags & DOTS_STEP_RHS_AHEAD) && rhs_writes_modes(c)) ? 1 : 0;      // (a hint: ignored without the direct solver / on a time slab)
+    c->carried.rhs_ahead_armed = ((flags & DOTS_STEP_RHS_AHEAD) && rhs_writes_modes(c)) ? 1 : 0;      // (a hint: ignored without the direct solver / on a time slab)
     if ((flags & DOTS_STEP_SKIP_Z_MID) && (flags & DOTS_STEP_PALM)) { set_error("step_flags: DOTS_STEP_PALM reads z_mid, it cannot be combined with DOTS_STEP_SKIP_Z_MID"); return DOTS_ERR_ARGUMENT; }
     c->step_skip_zmid = (flags & DOTS_STEP_SKIP_Z_MID) ? 1 : 0;
     c->step_palm = (flags & DOTS_STEP_PALM) ? 1 : 0;
@@ -839,7 +823,7 @@ int dots_step_flags(dots_ctx *c, uint32_t flags) {
 }
 
 int dots_step_times(dots_ctx *c, dots_step_stats *out, int capacity, int wait, int *n_out) {
-    int rc = check(c, true, true);
+    int rc = admit(c, E_STEP_TIMES);
     if (rc) return rc;
     if (!out || !n_out || capacity < 0) { set_error("step_times: bad argument"); return DOTS_ERR_ARGUMENT; }
     int n = 0;
@@ -896,25 +880,21 @@ int dots_step_times(dots_ctx *c, dots_step_stats *out, int capacity, int wait, i
 }
 
 int dots_run_phase(dots_ctx *c, int phase, dots_step_stats *stats) {
-    int rc = check(c);
+    int rc = admit(c, E_RUN_PHASE);
     if (rc) return rc;
     if (c->shard_stride != 0) { set_error("run_phase works on whole arrays: not available on a time slab"); return DOTS_ERR_STATE; }
-    if ((rc = moved_needs_restart(c, "dots_run_phase"))) return rc;
     dots_step_stats local;
     memset(&local, 0, sizeof local);
-    if ((rc = materialise_zmid(c))) return rc;
+    if ((rc = need_zmid(c, E_RUN_PHASE, phase == DOTS_PHASE_Q_LAMBDA))) return rc;
     switch (phase) {
         case DOTS_PHASE_LAPLACIAN:
             if ((rc = modal_needs_factor(c, "run_phase(LAPLACIAN)"))) return rc;
             if ((rc = launch_rhs(c))) return rc;
             if ((rc = cg_solve(c, &local))) return rc;
             break;
-        case DOTS_PHASE_SOC_PROJECTION: rc = launch_soc_projection(c); c->zmid_stale = 0; break;
+        case DOTS_PHASE_SOC_PROJECTION: rc = launch_soc_projection(c); c->carried.zmid = ZMID_STORED; break;
         case DOTS_PHASE_Q_LAMBDA_MULT: rc = launch_q_lambda_mult(c); break;
-        case DOTS_PHASE_Q_LAMBDA:
-            if (c->zmid_stale) { set_error("phase q_lambda: z_mid was not materialised by the last step (dots_step_flags)"); return DOTS_ERR_STATE; }
-            rc = launch_q_lambda_only(c);
-            break;
+        case DOTS_PHASE_Q_LAMBDA: rc = launch_q_lambda_only(c); break;
         default: set_error("unknown phase"); return DOTS_ERR_ARGUMENT;
     }
     if (rc) return rc;
@@ -923,118 +903,111 @@ int dots_run_phase(dots_ctx *c, int phase, dots_step_stats *stats) {
     return 0;
 }
 
-int dots_kkt(dots_ctx *c, uint32_t mask, double *out) {
-    int rc = check(c, true);
-    if (rc) return rc;
-    if ((rc = moved_needs_restart(c, "dots_kkt"))) return rc;
-    if (!out || (mask >> DOTS_N_KKT)) { set_error("kkt: bad mask or null output"); return DOTS_ERR_ARGUMENT; }
+// What the three KKT entry points share behind admit: the mask check, the refusal of an unspecified z_mid, on a time slab the refusal
+// of stale halos (dots_kkt: of the slab itself), and z_mid rebuilt where the stand-alone kernels read it.  An empty mask passes.
+static int kkt_prelude(Ctx *c, Entry e, uint32_t mask, const double *out) {
+    const char *who = ADMISSION[e].name;
+    if (!out || (mask >> DOTS_N_KKT)) { set_error(std::string(who) + ": bad mask or null output"); return DOTS_ERR_ARGUMENT; }
     if (!mask) return 0;
-    if (c->zmid_stale && (mask & (1u << DOTS_KKT_PRIM_Z))) { set_error("kkt: z_mid was not materialised by the last step (dots_step_flags)"); return DOTS_ERR_STATE; }
-    if (c->shard_stride != 0) { set_error("kkt on a time slab: use dots_kkt_sums / dots_kkt_combine around the caller's all-reduce"); return DOTS_ERR_STATE; }
-    if ((mask & (1u << DOTS_KKT_PRIM_Z)) && !kkt_takes_fused(c, mask) && (rc = materialise_zmid(c))) return rc;      // (the stand-alone kernels read z_mid)
+    const bool prim_z = mask & (1u << DOTS_KKT_PRIM_Z);
+    int rc;
+    if (prim_z && (rc = refuse_unspecified_zmid(c->carried, e))) return rc;
+    if (c->shard_stride != 0 && e == E_KKT) { set_error("kkt on a time slab: use dots_kkt_sums / dots_kkt_combine around the caller's all-reduce"); return DOTS_ERR_STATE; }
+    if (c->shard_stride != 0 && !c->carried.kkt_halo_fresh && (mask & ((1u << DOTS_KKT_DUAL_ALPHA) | (1u << DOTS_KKT_COMP_RHO_FQ) | (1u << DOTS_KKT_COMP_M_RHO_B)))) {
+        set_error(std::string(who) + ": the KKT halos are stale (dots_slab_stage 4 + exchange first)");
+        return DOTS_ERR_STATE;
+    }
+    return need_zmid(c, e, prim_z && !kkt_takes_fused(c, mask));
+}
+
+int dots_kkt(dots_ctx *c, uint32_t mask, double *out) {
+    int rc = admit(c, E_KKT);
+    if (rc || (rc = kkt_prelude(c, E_KKT, mask, out)) || !mask) return rc;
     return kkt_evaluate(c, mask, out);
 }
 int dots_kkt_sums(dots_ctx *c, uint32_t mask, double *sums) {
-    int rc = check(c, true);
+    int rc = admit(c, E_KKT_SUMS);
     if (rc) return rc;
-    if ((rc = moved_needs_restart(c, "dots_kkt_sums"))) return rc;
-    if (!sums || (mask >> DOTS_N_KKT)) { set_error("kkt_sums: bad mask or null output"); return DOTS_ERR_ARGUMENT; }
     static_assert(DOTS_KKT_N_SUMS == MAX_SUMS, "header and kernels disagree on the number of KKT sums");
-    for (int i = 0; i < DOTS_KKT_N_SUMS; ++i) sums[i] = 0.0;
-    if (!mask) return 0;
-    if (c->zmid_stale && (mask & (1u << DOTS_KKT_PRIM_Z))) { set_error("kkt: z_mid was not materialised by the last step (dots_step_flags)"); return DOTS_ERR_STATE; }
-    if (c->shard_stride != 0 && !c->kkt_halo_fresh && (mask & ((1u << DOTS_KKT_DUAL_ALPHA) | (1u << DOTS_KKT_COMP_RHO_FQ) | (1u << DOTS_KKT_COMP_M_RHO_B)))) {
-        set_error("kkt_sums: the KKT halos are stale (dots_slab_stage 4 + exchange first)");
-        return DOTS_ERR_STATE;
-    }
-    if ((mask & (1u << DOTS_KKT_PRIM_Z)) && !kkt_takes_fused(c, mask) && (rc = materialise_zmid(c))) return rc;
+    for (int i = 0; sums && !(mask >> DOTS_N_KKT) && i < DOTS_KKT_N_SUMS; ++i) sums[i] = 0.0;      // (also when the call is then refused)
+    if ((rc = kkt_prelude(c, E_KKT_SUMS, mask, sums)) || !mask) return rc;
     return kkt_sums(c, mask, sums);
 }
 int dots_kkt_sums_device(dots_ctx *c, uint32_t mask, double *device_sums) {
-    int rc = check(c, true);
-    if (rc) return rc;
-    if ((rc = moved_needs_restart(c, "dots_kkt_sums_device"))) return rc;
-    if (!device_sums || (mask >> DOTS_N_KKT)) { set_error("kkt_sums_device: bad mask or null output"); return DOTS_ERR_ARGUMENT; }
-    if (c->zmid_stale && (mask & (1u << DOTS_KKT_PRIM_Z))) { set_error("kkt: z_mid was not materialised by the last step (dots_step_flags)"); return DOTS_ERR_STATE; }
-    if (c->shard_stride != 0 && !c->kkt_halo_fresh && (mask & ((1u << DOTS_KKT_DUAL_ALPHA) | (1u << DOTS_KKT_COMP_RHO_FQ) | (1u << DOTS_KKT_COMP_M_RHO_B)))) {
-        set_error("kkt_sums_device: the KKT halos are stale (dots_slab_stage 4 + exchange first)");
-        return DOTS_ERR_STATE;
-    }
+    int rc = admit(c, E_KKT_SUMS_DEVICE);
+    if (rc || (rc = kkt_prelude(c, E_KKT_SUMS_DEVICE, mask, device_sums))) return rc;
     return kkt_sums_device(c, mask, device_sums);
 }
 int dots_kkt_combine(dots_ctx *c, uint32_t mask, const double *sums, double *out) {
-    int rc = check(c, true);
+    int rc = admit(c, E_KKT_COMBINE);
     if (rc) return rc;
     if (!sums || !out || (mask >> DOTS_N_KKT)) { set_error("kkt_combine: bad argument"); return DOTS_ERR_ARGUMENT; }
     return kkt_combine(c, mask, sums, out);
 }
 int dots_objective_sums(dots_ctx *c, double *sums) {
-    int rc = check(c, true);
+    int rc = admit(c, E_OBJECTIVE_SUMS);
     if (rc) return rc;
-    if ((rc = moved_needs_restart(c, "dots_objective_sums"))) return rc;
     if (!sums) { set_error("null output"); return DOTS_ERR_ARGUMENT; }
     return objective_sums(c, sums);
 }
 int dots_objective_combine(dots_ctx *c, const double *sums, double *out) {
-    int rc = check(c, true);
+    int rc = admit(c, E_OBJECTIVE_COMBINE);
     if (rc) return rc;
     if (!sums || !out) { set_error("null argument"); return DOTS_ERR_ARGUMENT; }
     return objective_combine(c, sums, out);
 }
 
 int dots_objective(dots_ctx *c, double *out) {
-    int rc = check(c, true);
+    int rc = admit(c, E_OBJECTIVE);
     if (rc) return rc;
-    if ((rc = moved_needs_restart(c, "dots_objective"))) return rc;
     if (!out) { set_error("null output"); return DOTS_ERR_ARGUMENT; }
     if (c->shard_stride != 0) { set_error("objective on a time slab: use dots_objective_sums / dots_objective_combine"); return DOTS_ERR_STATE; }
     return objective_evaluate(c, out);
 }
 
 int dots_adjust_penalty(dots_ctx *c, double factor) {
-    const bool anticipated = c && c->rhs_ahead == 3 && factor == c->ahead_dv;      // (penalty_decision_ahead; check() drops the launch ahead)
-    int rc = check(c);      // (carries out a division that is still pending)
+    const bool anticipated = c && c->carried.rhs_ahead == 3 && factor == c->ahead_dv;      // (penalty_decision_ahead; admission drops the launch ahead)
+    int rc = admit(c, E_ADJUST_PENALTY);      // (carries out a division that is still pending)
     if (rc) return rc;
     if (!(factor > 0)) { set_error("factor must be positive"); return DOTS_ERR_ARGUMENT; }
-    c->kkt_halo_fresh = 0;
+    state_changed(c->carried);
     // one GPU, direct solver: the next iteration's kernels apply the division as they read (run_iteration); any other access to
-    // the arrays carries it out first (check)
+    // the arrays carries it out first (admission.h: DUALS)
     if (c->lazy_div && c->shard_stride == 0 && carry_possible(c)) {
-        c->pending_div = factor;
-        if (anticipated) c->rhs_ahead = 4;      // ... kept if dots_set_params now brings the anticipated penalty
+        c->carried.pending_div = factor;
+        if (anticipated) c->carried.rhs_ahead = 4;      // ... kept if dots_set_params now brings the anticipated penalty
         return 0;
     }
     return launch_adjust_penalty(c, factor);
 }
 int dots_scale_z(dots_ctx *c, double z_mul, double beta_mul, double sz_new) {
-    int rc = check(c);
+    int rc = admit(c, E_SCALE_Z);
     if (rc) return rc;
-    c->kkt_halo_fresh = 0;
-    if ((rc = materialise_zmid(c))) return rc;
+    state_changed(c->carried);
+    if ((rc = need_zmid(c, E_SCALE_Z))) return rc;
     return launch_scale_z(c, z_mul, beta_mul, sz_new);
 }
 int dots_scale_arrays(dots_ctx *c, uint32_t mask, double factor) {
-    int rc = check(c);
+    int rc = admit(c, E_SCALE_ARRAYS);
     if (rc) return rc;
     if (mask >> DOTS_N_ARRAYS) { set_error("bad array mask"); return DOTS_ERR_ARGUMENT; }
-    c->kkt_halo_fresh = 0;
-    if ((rc = materialise_zmid(c))) return rc;
+    state_changed(c->carried);
+    if ((rc = need_zmid(c, E_SCALE_ARRAYS))) return rc;
     for (int id = 0; id < DOTS_N_ARRAYS; ++id)
         if ((mask >> id) & 1u)
             if ((rc = launch_scale_array(c, id, factor))) return rc;
     return 0;
 }
 int dots_norm_square(dots_ctx *c, int id, int part, double *out) {
-    int rc = check(c);
+    int rc = admit(c, E_NORM_SQUARE);
     if (rc) return rc;
     if (id < 0 || id >= DOTS_N_ARRAYS || !out || part < 0 || part > 2) { set_error("norm_square: bad argument"); return DOTS_ERR_ARGUMENT; }
-    if (id == DOTS_Z_MID && c->zmid_stale) { set_error("norm_square: z_mid was not materialised by the last step (dots_step_flags)"); return DOTS_ERR_STATE; }
-    if (id == DOTS_Z_MID && (rc = materialise_zmid(c))) return rc;
+    if ((rc = need_zmid(c, E_NORM_SQUARE, id == DOTS_Z_MID))) return rc;
     return norm_square(c, id, part, out);
 }
 
 int dots_apply_operator(dots_ctx *c, int op, double scale, const double *in, int64_t n_in, double *out, int64_t n_out) {
-    int rc = check(c);
+    int rc = admit(c, E_APPLY_OPERATOR);
     if (rc) return rc;
     // (input array class, output array class) per operator, expressed through state arrays of the same shape
     int in_id, out_id;
@@ -1074,7 +1047,7 @@ int dots_apply_operator(dots_ctx *c, int op, double scale, const double *in, int
 }
 
 int dots_mg_setup(dots_ctx *c, const dots_mg_desc *m) {
-    int rc = check(c);
+    int rc = admit(c, E_MG_SETUP);
     if (rc) return rc;
     if (!m || m->n_levels < 2 || m->n_levels > 10 || !m->levels || !m->coarse_inverse) { set_error("mg_setup: bad description"); return DOTS_ERR_ARGUMENT; }
     if (c->lap_solver != DOTS_LAP_MODAL_PCG) { set_error("multigrid needs the modal solver"); return DOTS_ERR_ARGUMENT; }
@@ -1151,7 +1124,7 @@ int dots_mg_setup(dots_ctx *c, const dots_mg_desc *m) {
 }
 
 int dots_mg_enable(dots_ctx *c, int on) {
-    int rc = check(c);
+    int rc = admit(c, E_MG_ENABLE);
     if (rc) return rc;
     c->use_mg = on ? 1 : 0;
     if (!c->use_mg) c->mg_path = 0;      // Jacobi from here on: the last cycle's launches are no longer this context's
@@ -1161,7 +1134,7 @@ int dots_mg_enable(dots_ctx *c, int on) {
 // One V-cycle on a caller's residual (tests and diagnosis; the product path never calls it): the launches are cg_mg_apply's, i.e. mg_vcycle with
 // the PCG's own tiling.  The PCG vectors, partial rows and flags it writes are scratch between solves (kernels_cg.hip: cg_mg_apply).
 int dots_mg_apply(dots_ctx *c, const double *r, double *z, double *rz, const int32_t *frozen) {
-    int rc = check(c);
+    int rc = admit(c, E_MG_APPLY);
     if (rc) return rc;
     if (c->lap_solver != DOTS_LAP_MODAL_PCG) { set_error("mg_apply: the V-cycle belongs to the modal solver"); return DOTS_ERR_STATE; }
     if (c->shard_stride != 0) { set_error("mg_apply: not on a time slab"); return DOTS_ERR_STATE; }
@@ -1223,16 +1196,14 @@ struct BatchMembers {
     std::vector<double *> ys, xs;
 };
 
-// cs[0 .. n) as the members of `who`'s batch: each passes check(reads_only, keeps_division) -- with `needs_restart_check` it must
-// not be waiting for a dots_restart after a move --, holds a direct solver on one GPU and the factor of cs[0], and is listed once.
+// cs[0 .. n) as the members of the batched call `e`: each is admitted as its row says, holds a direct solver on one GPU and the factor
+// of cs[0], and is listed once.
 // `one_message` (dots_bench_many): the two factor checks under one text and status, no search for a context listed twice.
-static int batch_members(const char *who, dots_ctx *const *cs, int n, bool reads_only, bool keeps_division, bool needs_restart_check, BatchMembers &out,
-                         bool one_message = false) {
-    const std::string w(who);
+static int batch_members(Entry e, dots_ctx *const *cs, int n, BatchMembers &out, bool one_message = false) {
+    const std::string w(ADMISSION[e].name);
     int rc;
     for (int k = 0; k < n; ++k) {
-        if ((rc = check(cs[k], reads_only, keeps_division))) return rc;
-        if (needs_restart_check && (rc = moved_needs_restart(cs[k], ("dots_" + w).c_str()))) return rc;
+        if ((rc = admit(cs[k], e))) return rc;
         const bool holds = front_batchable(cs[k]), shares = holds && cs[k]->front.F == cs[0]->front.F;
         if (one_message && !shares) { set_error(w + ": the contexts do not share one factor"); return DOTS_ERR_STATE; }
         if (!holds) { set_error(w + ": every context needs an installed or shared factor on one GPU (no PCG, no time slab)"); return DOTS_ERR_STATE; }
@@ -1246,7 +1217,7 @@ static int batch_members(const char *who, dots_ctx *const *cs, int n, bool reads
 }
 
 int dots_front_setup(dots_ctx *c, const dots_front_desc *desc) {
-    int rc = check(c);
+    int rc = admit(c, E_FRONT_SETUP);
     if (rc) return rc;
     if (c->lap_solver != DOTS_LAP_MODAL_PCG) { set_error("the direct solve needs the modal solver"); return DOTS_ERR_ARGUMENT; }
     c->d.cn_sq = c->d.cn_g = c->d.cn_lo = c->d.cn_e = nullptr;
@@ -1269,9 +1240,9 @@ int dots_front_setup(dots_ctx *c, const dots_front_desc *desc) {
 }
 
 int dots_front_share(dots_ctx *c, dots_ctx *owner) {
-    int rc = check(c);
+    int rc = admit(c, E_FRONT_SHARE);
     if (rc) return rc;
-    if ((rc = check(owner, true, true))) return rc;
+    if ((rc = admit(owner, E_FRONT_SHARE_OWNER))) return rc;
     if (owner == c) { set_error("front_share: a context cannot share its own factor"); return DOTS_ERR_ARGUMENT; }
     if (owner->front.n_nodes == 0) { set_error("front_share: the owner has no factor installed"); return DOTS_ERR_STATE; }
     if (owner->shard_stride != 0 || c->shard_stride != 0) { set_error("front_share: time slabs cannot share a factor"); return DOTS_ERR_STATE; }
@@ -1305,7 +1276,7 @@ int dots_laplacian_solve_many(dots_ctx *const *cs, int n, const double *const *h
     for (int k = 0; k < n; ++k)
         if (!host_in[k] || !host_out[k]) { set_error("laplacian_solve_many: null array"); return DOTS_ERR_ARGUMENT; }
     BatchMembers m;
-    int rc = batch_members("laplacian_solve_many", cs, n, false, false, false, m);
+    int rc = batch_members(E_LAPLACIAN_SOLVE_MANY, cs, n, m);
     if (rc) return rc;
     const int64_t cnt = array_count_device(cs[0]->d, DOTS_PHI), nh = array_count_host(cs[0]->d, DOTS_PHI);
     std::vector<double *> din((size_t)n, nullptr), dout((size_t)n, nullptr);
@@ -1343,7 +1314,7 @@ int dots_laplacian_solve_many(dots_ctx *const *cs, int n, const double *const *h
 int dots_step_many(dots_ctx *const *cs, int n, dots_step_stats *stats) {
     if (!cs || n < 1) { set_error("step_many: bad arguments"); return DOTS_ERR_ARGUMENT; }
     BatchMembers m;
-    int rc = batch_members("step_many", cs, n, true, true, true, m);      // (the iteration consumes the flags and a pending division itself)
+    int rc = batch_members(E_STEP_MANY, cs, n, m);      // (the iteration consumes the flags and a pending division itself)
     if (rc) return rc;
     Ctx *c0 = cs[0];
     const std::vector<Ctx *> &cv = m.cv;
@@ -1358,7 +1329,7 @@ int dots_step_many(dots_ctx *const *cs, int n, dots_step_stats *stats) {
     // each member on its own stream: the first half of its iteration and the forward time transform of its right-hand side
     for (int k = 0; k < n; ++k) {
         Ctx *c = cv[k];
-        c->rhs_ahead_armed = 0;      // (DOTS_STEP_RHS_AHEAD is ignored in a batch; a launch ahead already enqueued is still taken)
+        c->carried.rhs_ahead_armed = 0;      // (DOTS_STEP_RHS_AHEAD is ignored in a batch; a launch ahead already enqueued is still taken)
         c->batched = 1;
         IterPlan &p = plan[(size_t)k];
         if ((rc = iteration_before(c, false, p, nullptr))) return rc;
@@ -1395,7 +1366,7 @@ int dots_step_many(dots_ctx *const *cs, int n, dots_step_stats *stats) {
 int dots_bench_many(dots_ctx *const *cs, int n, int reps, double *ms) {
     if (!cs || n < 1 || reps < 1 || !ms) { set_error("bench_many: bad arguments"); return DOTS_ERR_ARGUMENT; }
     BatchMembers m;
-    int rc = batch_members("bench_many", cs, n, false, false, false, m, true);
+    int rc = batch_members(E_BENCH_MANY, cs, n, m, true);
     if (rc) return rc;
     const std::vector<Ctx *> &cv = m.cv;
     Ctx *c0 = cv[0];
@@ -1475,13 +1446,11 @@ static int check_space_tables(const std::string &who, const char *vname, const c
     return 0;
 }
 
-static int carry_state(const std::string &who, const char *what, dots_ctx *dst, dots_ctx *src, const double *factor, double *ms, const CarryTables &host) {
-    int rc = check(src, true);      // (a pending penalty division is carried out, as for a download)
-    if (rc) return rc;
-    if (src->zmid_stale) { set_error(who + ": the source's z_mid was not materialised by its last step (dots_step_flags)"); return DOTS_ERR_STATE; }
-    if ((rc = materialise_zmid(src))) return rc;
-    if ((rc = check(dst, false, true))) return rc;
-    dst->pending_div = 0.0;      // (every array a pending division would have touched is replaced)
+static int carry_state(Entry e_src, Entry e_dst, const char *what, dots_ctx *dst, dots_ctx *src, const double *factor, double *ms, const CarryTables &host) {
+    const std::string who = ADMISSION[e_dst].name;
+    int rc = admit(src, e_src);      // (a pending penalty division is carried out, as for a download)
+    if (rc || (rc = need_zmid(src, e_src)) || (rc = admit(dst, e_dst))) return rc;
+    dst->carried.pending_div = 0.0;      // (every array a pending division would have touched is replaced)
     const size_t nn = (size_t)dst->d.T + 1, ni = (size_t)dst->d.T, V = (size_t)dst->d.V, F = (size_t)dst->d.F, per = carry_rows_per_vertex(host.mode);
     const void *from[8] = {host.node_w, host.interval_w, host.vw, host.node_j, host.interval_j, host.vsrc, host.fsrc, host.csrc};
     const size_t size[8] = {sizeof(double) * nn, sizeof(double) * ni, sizeof(double) * 3 * V, sizeof(int32_t) * nn,
@@ -1511,8 +1480,8 @@ static int carry_state(const std::string &who, const char *what, dots_ctx *dst, 
     e = hipStreamSynchronize(dst->stream);
     if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__);
     if (rc) return rc;
-    dst->zmid_stale = dst->zmid_deferred = 0;      // (z_mid's storage holds the carried z_mid)
-    dst->kkt_halo_fresh = 0;
+    dst->carried.zmid = ZMID_STORED;      // (z_mid's storage holds the carried z_mid)
+    state_changed(dst->carried);
     if (ms) {
         float t = 0.f;
         DOTS_HIP(hipEventElapsedTime(&t, dst->ev[0], dst->ev[1]));
@@ -1535,7 +1504,7 @@ int dots_prolong_time(dots_ctx *dst, dots_ctx *src, const dots_prolong_desc *des
     if (!desc->node_j || !desc->node_w || !desc->interval_j || !desc->interval_w) { set_error("prolong_time: null table"); return DOTS_ERR_ARGUMENT; }
     const CarryTables t{desc->node_j, desc->interval_j, desc->node_w, desc->interval_w, desc->vmap, nullptr, desc->fmap, nullptr, CARRY_SAME};
     if ((rc = check_time_tables(who, t, dd, ds)) || (rc = check_space_tables(who, "vmap", "fmap", t, dd, ds))) return rc;
-    return carry_state(who, "table", dst, src, desc->factor, desc->ms, t);
+    return carry_state(E_PROLONG_TIME_SRC, E_PROLONG_TIME, "table", dst, src, desc->factor, desc->ms, t);
 }
 
 int dots_prolong_space(dots_ctx *dst, dots_ctx *src, const dots_prolong_space_desc *desc) {
@@ -1546,7 +1515,7 @@ int dots_prolong_space(dots_ctx *dst, dots_ctx *src, const dots_prolong_space_de
     if ((rc = carry_space_shapes(who, "row map", dd, ds, !desc->vmap || !desc->fmap, desc->n_vertices, desc->n_triangles))) return rc;
     const CarryTables t{nullptr, nullptr, nullptr, nullptr, desc->vmap, nullptr, desc->fmap, nullptr, CARRY_NESTED};
     if ((rc = check_space_tables(who, "vmap", "fmap", t, dd, ds))) return rc;
-    return carry_state(who, "row map", dst, src, desc->factor, desc->ms, t);
+    return carry_state(E_PROLONG_SPACE_SRC, E_PROLONG_SPACE, "row map", dst, src, desc->factor, desc->ms, t);
 }
 
 int dots_transfer_space(dots_ctx *dst, dots_ctx *src, const dots_transfer_space_desc *desc) {
@@ -1557,7 +1526,7 @@ int dots_transfer_space(dots_ctx *dst, dots_ctx *src, const dots_transfer_space_
     if ((rc = carry_space_shapes(who, "table", dd, ds, !desc->vsrc || !desc->vw || !desc->fsrc || !desc->csrc, desc->n_vertices, desc->n_triangles))) return rc;
     const CarryTables t{nullptr, nullptr, nullptr, nullptr, desc->vsrc, desc->vw, desc->fsrc, desc->csrc, CARRY_LOCATED};
     if ((rc = check_space_tables(who, "vsrc", "fsrc", t, dd, ds))) return rc;
-    return carry_state(who, "table", dst, src, desc->factor, desc->ms, t);
+    return carry_state(E_TRANSFER_SPACE_SRC, E_TRANSFER_SPACE, "table", dst, src, desc->factor, desc->ms, t);
 }
 
 int dots_carry_spacetime(dots_ctx *dst, dots_ctx *src, const dots_carry_spacetime_desc *desc) {
@@ -1581,7 +1550,7 @@ int dots_carry_spacetime(dots_ctx *dst, dots_ctx *src, const dots_carry_spacetim
     const CarryTables t{desc->node_j, desc->interval_j, desc->node_w, desc->interval_w, desc->vsrc, desc->vw, desc->fsrc, desc->csrc,
                         desc->vw ? CARRY_LOCATED : CARRY_NESTED};
     if ((rc = check_time_tables(who, t, dd, ds)) || (rc = check_space_tables(who, "vsrc", "fsrc", t, dd, ds))) return rc;
-    return carry_state(who, "table", dst, src, desc->factor, desc->ms, t);
+    return carry_state(E_CARRY_SPACETIME_SRC, E_CARRY_SPACETIME, "table", dst, src, desc->factor, desc->ms, t);
 }
 
 // ---- dots_restart: new end masses on a live context (include/dots_socp_hip.h) ------------------------------------------------------
@@ -1597,18 +1566,18 @@ int dots_restart(dots_ctx *c, const dots_restart_desc *desc) {
     if (warm) {
         for (double f : desc->factors)
             if (!(std::isfinite(f) && f > 0.0)) { set_error("restart: a factor that is not finite and positive"); return DOTS_ERR_ARGUMENT; }
-        if (c->zmid_stale) { set_error("restart: z_mid was not materialised by the last step (dots_step_flags): no warm start from this iterate"); return DOTS_ERR_STATE; }
+        if (int rc = refuse_unspecified_zmid(c->carried, E_RESTART)) return rc;
     }
-    // the launch ahead, an armed penalty decision, the carried gathers, the fused sums and the step path go (check); the division stays for below
-    int rc = check(c, false, true);
+    // the launch ahead, an armed penalty decision, the carried gathers, the fused sums and the step path go; the division stays for below
+    int rc = admit(c, E_RESTART);
     if (rc) return rc;
     Dev &d = c->d;
     DOTS_HIP(hipEventRecord(c->ev[0], c->stream));
     if (warm) {      // what dots_download does before it reads, then the recovery factors in place
-        if ((rc = flush_division(c)) || (rc = materialise_zmid(c)) || (rc = launch_restart_scale(c, desc->factors, nullptr))) return rc;
+        if ((rc = flush_division(c)) || (rc = need_zmid(c, E_RESTART)) || (rc = launch_restart_scale(c, desc->factors, nullptr))) return rc;
     } else {
-        c->pending_div = 0.0;      // (it would have divided arrays that are zero from here on)
-        c->zmid_deferred = 0;
+        c->carried.pending_div = 0.0;      // (it would have divided arrays that are zero from here on)
+        if (c->carried.zmid == ZMID_DEFERRED) c->carried.zmid = ZMID_STORED;      // (nothing to rebuild it for)
         if ((rc = launch_restart_scale(c, nullptr, nullptr))) return rc;      // (one launch: a memset per array costs the host milliseconds on the large ones)
     }
     // what is derived from the state or left over from the old run's launches, as a new context has it: zero
@@ -1616,7 +1585,7 @@ int dots_restart(dots_ctx *c, const dots_restart_desc *desc) {
     double *const node_arrays[] = {d.lamc, c->zf_alt, c->ze_alt, c->lamc_alt, d.cg_b, d.cg_r, d.cg_z, d.cg_p0, d.cg_p1, d.cg_Ap, d.cg_x};
     for (double *p : node_arrays)
         if (p) DOTS_HIP(hipMemsetAsync(p, 0, node_bytes, c->stream));
-    // (B_alt keeps its bytes: it is read only while zmid_deferred is set, and the step that sets it has written all of it)
+    // (B_alt keeps its bytes: it is read only while z_mid is deferred, and the step that sets it has written all of it)
     DOTS_HIP(hipMemsetAsync(d.scal, 0, sizeof(double) * CgScalOffsets::TOTAL, c->stream));
     DOTS_HIP(hipMemsetAsync(d.flags, 0, sizeof(int) * FLAG_TOTAL, c->stream));
     DOTS_HIP(hipMemsetAsync(c->kkt_counter, 0, 2 * sizeof(int), c->stream));
@@ -1633,11 +1602,11 @@ int dots_restart(dots_ctx *c, const dots_restart_desc *desc) {
     c->prm.norm_d = c->norm_d0;
     c->prm.norm_boundary = boundary_norm(nb, d.T);
     // host bookkeeping of the old run
-    c->zmid_stale = c->zmid_deferred = 0;
-    c->needs_restart = 0;      // (after dots_move_vertices: the run that starts here is one on the new surface)
+    c->carried.zmid = ZMID_STORED;
+    c->carried.needs_restart = 0;      // (after dots_move_vertices: the run that starts here is one on the new surface)
     c->zmid_dv = c->zmid_sz = 0.0;
-    c->ahead_dv = c->ahead_r = c->ahead_div = 0.0;
-    c->kkt_halo_fresh = 0;
+    c->ahead_dv = c->ahead_r = c->carried.ahead_div = 0.0;
+    state_changed(c->carried);
     c->step_timed = c->step_skip_zmid = c->step_palm = c->step_kkt = c->step_carry = 0;
     c->batched = 0;
     c->t_head = c->t_count = 0;
@@ -1706,9 +1675,10 @@ static int move_holders(dots_ctx *const *cs, int n, const dots_move_desc *desc, 
         if (total > cs[k]->stage_count) { set_error("move_vertices: the scratch tables do not fit the staging buffer on this mesh"); return DOTS_ERR_STATE; }
     }
     // what dots_download does before it reads, with the OLD geometry (z_mid is rebuilt from tables that are about to change); the launch
-    // ahead, an armed penalty decision, the carried gathers and the fused sums go (check)
+    // ahead, an armed penalty decision, the carried gathers and the fused sums go
+    const Entry e = many ? E_MOVE_VERTICES_MANY : E_MOVE_VERTICES;
     for (int k = 0; k < n; ++k)
-        if ((rc = check(cs[k])) || (rc = materialise_zmid(cs[k]))) return rc;
+        if ((rc = admit(cs[k], e)) || (rc = need_zmid(cs[k], e))) return rc;
     GeomScratch s{c0->stage, c0->stage + o_hat, c0->stage + o_mass, reinterpret_cast<int *>(c0->stage + o_flag)};
     const double *xyz = desc->vertices;
     if (!on_device) {
@@ -1736,8 +1706,8 @@ static int move_holders(dots_ctx *const *cs, int n, const dots_move_desc *desc, 
         DOTS_HIP(hipEventRecord(c->ev[2], c->stream));
         if ((rc = launch_geometry_commit(c, s))) return rc;
         DOTS_HIP(hipEventRecord(c->ev[3], c->stream));
-        c->needs_restart = 1;
-        c->kkt_halo_fresh = 0;
+        c->carried.needs_restart = 1;
+        state_changed(c->carried);
         if (k == 0) {
             DOTS_HIP(hipMemcpyAsync(area.data(), d.area_f, sizeof(double) * (size_t)F, hipMemcpyDeviceToHost, c->stream));
             DOTS_HIP(hipMemcpyAsync(mass->data(), d.mass_v, sizeof(double) * (size_t)V, hipMemcpyDeviceToHost, c->stream));
@@ -1799,7 +1769,7 @@ int dots_move_vertices_many(dots_ctx *const *ctxs, int n, const dots_move_desc *
 }
 
 int dots_geometry_copy(dots_ctx *c, const dots_geometry_tables *out) {
-    int rc = check(c, true, true);      // (reads tables only: neither the state nor the parameters)
+    int rc = admit(c, E_GEOMETRY_COPY);      // (reads tables only: neither the state nor the parameters)
     if (rc) return rc;
     if (!out) { set_error("geometry_copy: null argument"); return DOTS_ERR_ARGUMENT; }
     const Dev &d = c->d;
@@ -1897,7 +1867,7 @@ int dots_readout(dots_ctx *c, const dots_readout_desc *desc) {
     const int centred = desc->centred ? 1 : 0;
     if (centred && (!desc->mu0 || !desc->mu1)) { set_error("readout: the centred output needs mu0 and mu1"); return DOTS_ERR_ARGUMENT; }
     if (centred && d.T < 1) { set_error("readout: no layers to centre"); return DOTS_ERR_ARGUMENT; }
-    int rc = check(c, true);      // (a pending penalty division is carried out, as for a download; z_mid is not needed)
+    int rc = admit(c, E_READOUT);      // (a pending penalty division is carried out, as for a download; z_mid is not needed)
     if (rc) return rc;
     if ((rc = readout_prepare(c))) return rc;
     const size_t slot = (size_t)c->readout_pinned << 10;
@@ -1990,7 +1960,7 @@ static int flow_prepare(Ctx *c) {
 // What dots_flow_map, dots_flow_push, dots_flow_trace and dots_flow_slide ask for, as one record: the embedded description, and what is
 // optional beside it.  Without nodes the trace is the whole horizon, node 0 to node n_time.
 struct FlowRequest {
-    const char *who;                                 // the entry point, for the messages
+    Entry entry;                                     // the entry point: its admission row, its name in the messages
     const dots_flow_map_desc *map;
     const dots_flow_push_desc *push = nullptr;       // the deposit fields (its `map` is not read), or null: no deposits
     bool nodes = false;                              // node_from and node_to are the caller's, and are checked
@@ -2000,12 +1970,12 @@ struct FlowRequest {
     int32_t *slides = nullptr, *steps = nullptr;     // host out [n_particles]; steps may be null
 };
 // The request of a trace description; `deposits` holds its deposit fields as dots_flow_push takes them.
-static FlowRequest flow_trace_request(const char *who, const dots_flow_trace_desc &t, dots_flow_push_desc &deposits) {
+static FlowRequest flow_trace_request(Entry entry, const dots_flow_trace_desc &t, dots_flow_push_desc &deposits) {
     deposits = dots_flow_push_desc{};
     deposits.mass = t.mass; deposits.n_attributes = t.n_attributes; deposits.all_layers = t.all_layers; deposits.attributes = t.attributes;
     deposits.scale_exponent = t.scale_exponent; deposits.mass_at = t.mass_at; deposits.attr_at = t.attr_at; deposits.dropped = t.dropped;
     deposits.ms = t.ms;
-    FlowRequest r{who, &t.map};
+    FlowRequest r{entry, &t.map};
     if (t.mass) r.push = &deposits;
     r.nodes = true; r.node_from = t.node_from; r.node_to = t.node_to; r.action = t.action;
     return r;
@@ -2015,7 +1985,7 @@ static FlowRequest flow_trace_request(const char *who, const dots_flow_trace_des
 static int flow_run(dots_ctx *c, const FlowRequest &req) {
     const dots_flow_map_desc *desc = req.map;
     const dots_flow_push_desc *push = req.push;
-    const std::string w = std::string(req.who) + ": ";
+    const std::string w = std::string(ADMISSION[req.entry].name) + ": ";
     if (c->shard_stride != 0) { set_error(w + "not available on time slabs"); return DOTS_ERR_STATE; }
     const Dev &d = c->d;
     if (req.slide && !req.slides) { set_error(w + "null pointer (slides is required)"); return DOTS_ERR_ARGUMENT; }
@@ -2099,7 +2069,7 @@ static int flow_run(dots_ctx *c, const FlowRequest &req) {
             if (!(sum * std::ldexp(1.0, q.k[ch]) <= 0x1p61)) { set_error(w + "a scale exponent too large for what the particles carry (flow.push_scales chooses one)"); return DOTS_ERR_ARGUMENT; }
         }
     }
-    if ((rc = check(c, true))) return rc;      // (a pending penalty division is carried out, as for a download; z_mid is not needed)
+    if ((rc = admit(c, req.entry))) return rc;      // (a pending penalty division is carried out, as for a download; z_mid is not needed)
     if (push && (rc = readout_prepare(c))) return rc;      // (the inverse of the vertex numbering is the read-out's)
     // one allocation for the call: [start_w | o_w | w_at | mass | attr | pushed | action] doubles, [acc | dropped] 64-bit words, then
     // [start | nbr | o_tri | status | rested | crossings | slides | steps | tri_at] ints (the five counters in a row: FlowSlide::o_counts)
@@ -2194,27 +2164,27 @@ static int flow_run(dots_ctx *c, const FlowRequest &req) {
 int dots_flow_map(dots_ctx *c, const dots_flow_map_desc *desc) {
     if (!c) { set_error("null context"); return DOTS_ERR_ARGUMENT; }
     if (!desc) { set_error("flow_map: null description"); return DOTS_ERR_ARGUMENT; }
-    return flow_run(c, FlowRequest{"flow_map", desc});
+    return flow_run(c, FlowRequest{E_FLOW_MAP, desc});
 }
 
 int dots_flow_push(dots_ctx *c, const dots_flow_push_desc *desc) {
     if (!c) { set_error("null context"); return DOTS_ERR_ARGUMENT; }
     if (!desc) { set_error("flow_push: null description"); return DOTS_ERR_ARGUMENT; }
-    return flow_run(c, FlowRequest{"flow_push", &desc->map, desc});
+    return flow_run(c, FlowRequest{E_FLOW_PUSH, &desc->map, desc});
 }
 
 int dots_flow_trace(dots_ctx *c, const dots_flow_trace_desc *desc) {
     if (!c) { set_error("null context"); return DOTS_ERR_ARGUMENT; }
     if (!desc) { set_error("flow_trace: null description"); return DOTS_ERR_ARGUMENT; }
     dots_flow_push_desc deposits;
-    return flow_run(c, flow_trace_request("flow_trace", *desc, deposits));
+    return flow_run(c, flow_trace_request(E_FLOW_TRACE, *desc, deposits));
 }
 
 int dots_flow_slide(dots_ctx *c, const dots_flow_slide_desc *desc) {
     if (!c) { set_error("null context"); return DOTS_ERR_ARGUMENT; }
     if (!desc) { set_error("flow_slide: null description"); return DOTS_ERR_ARGUMENT; }
     dots_flow_push_desc deposits;
-    FlowRequest req = flow_trace_request("flow_slide", desc->trace, deposits);
+    FlowRequest req = flow_trace_request(E_FLOW_SLIDE, desc->trace, deposits);
     req.slide = true; req.slides = desc->slides; req.steps = desc->steps;
     return flow_run(c, req);
 }
@@ -2229,7 +2199,7 @@ int dots_sensitivity(dots_ctx *c, const dots_sensitivity_desc *desc) {
     const bool on_device = desc->device_pointers != 0;
     if (on_device && ((uintptr_t)desc->stress & 15)) { set_error("sensitivity: the device stress pointer is not on a 16-byte boundary"); return DOTS_ERR_ARGUMENT; }
     const Dev &d = c->d;
-    int rc = check(c, true);      // (a pending penalty division is carried out, as for a download; z_mid is not needed)
+    int rc = admit(c, E_SENSITIVITY);      // (a pending penalty division is carried out, as for a download; z_mid is not needed)
     if (rc) return rc;
     if ((rc = readout_prepare(c))) return rc;      // (the inverses of the device numbering are the read-out's)
     // the staging buffer: [stress | phi0 | phiT | mass], every part on a 16-byte boundary
@@ -2278,7 +2248,7 @@ int dots_sensitivity(dots_ctx *c, const dots_sensitivity_desc *desc) {
 }
 
 int dots_front_enable(dots_ctx *c, int on) {
-    int rc = check(c);
+    int rc = admit(c, E_FRONT_ENABLE);
     if (rc) return rc;
     if (on && c->front.n_nodes == 0) { set_error("front_enable: no factor installed"); return DOTS_ERR_STATE; }
     c->use_front = on ? 1 : 0;
@@ -2286,7 +2256,7 @@ int dots_front_enable(dots_ctx *c, int on) {
 }
 
 int dots_pcg_windows(dots_ctx *c, int on) {
-    int rc = check(c);
+    int rc = admit(c, E_PCG_WINDOWS);
     if (rc) return rc;
     if (c->lap_solver != DOTS_LAP_MODAL_PCG) { set_error("pcg_windows: the windows belong to the modal solver (DOTS_LAP_MODAL_PCG)"); return DOTS_ERR_STATE; }
     if (c->shard_stride != 0) { set_error("pcg_windows: not on a time slab"); return DOTS_ERR_STATE; }
@@ -2304,12 +2274,12 @@ int dots_pcg_windows(dots_ctx *c, int on) {
 }
 
 int dots_front_launches(dots_ctx *c) {
-    if (check(c) || c->front.n_nodes == 0) return -1;
+    if (admit(c, E_FRONT_LAUNCHES) || c->front.n_nodes == 0) return -1;
     return 2 * c->sched.n_bands - (c->sched.top_inverse ? 1 : 0);
 }
 
 int dots_front_info(dots_ctx *c, double *out) {
-    int rc = check(c);
+    int rc = admit(c, E_FRONT_INFO);
     if (rc) return rc;
     if (!out || c->front.n_nodes == 0) { set_error("front_info: no factor installed"); return DOTS_ERR_STATE; }
     out[0] = c->sched.bytes_unmerged;
@@ -2320,7 +2290,7 @@ int dots_front_info(dots_ctx *c, double *out) {
 }
 
 int dots_front_pitch(dots_ctx *c) {
-    if (check(c)) return -1;
+    if (admit(c, E_FRONT_PITCH)) return -1;
     return c->dcg.TP;
 }
 
@@ -2339,21 +2309,21 @@ int64_t dots_debug_counter(dots_ctx *c, int which) {
         case 9: return c->d2h_bytes;                  // bytes dots_download, dots_readout, dots_flow_map, dots_flow_push, dots_flow_trace, dots_flow_slide and dots_sensitivity have copied device -> host
         case 10: return c->front_own.size() + (c->front_store ? c->front_store->size() : 0);      // device allocations of the factor this context holds, its own and the store it shares (0 after front_release: also after a failed dots_front_setup)
         case 11: return c->mg_path;                   // MG_PATH_* bits of the last V-cycle enqueued (dots_dev.h)
-        case 12: return c->step_path;                 // STEP_PATH_* bits of the last iteration's launches (dots_dev.h)
+        case 12: return c->carried.step_path;                 // STEP_PATH_* bits of the last iteration's launches (dots_dev.h)
         case 13: return c->cg_path;                   // CG_PATH_* bits and tiling of the last PCG launches (dots_dev.h)
         case 14: return c->pcg_windows_ran;           // low byte: windows the last PCG solve ran (0: none yet, or unwindowed); bit 8: the windowed transforms ran
-        case 15: return c->deep_path;                 // DEEP_PATH_* of the last right-hand side and inverse transform (dots_dev.h)
+        case 15: return c->carried.deep_path;                 // DEEP_PATH_* of the last right-hand side and inverse transform (dots_dev.h)
         default: return -1;
     }
 }
 
 int dots_bench_kernel(dots_ctx *c, int which, int reps, double *ms, double *bytes) {
-    int rc = check(c);
+    int rc = admit(c, E_BENCH_KERNEL);
     if (rc) return rc;
     if (reps < 1 || !ms || !bytes) { set_error("bench: bad argument"); return DOTS_ERR_ARGUMENT; }
     if (which == 5) {      // dots_restart's in-place rescaling with every factor 1: the state keeps its values
         if (c->shard_stride != 0) { set_error("bench: the rescaling of dots_restart does not run on a time slab"); return DOTS_ERR_STATE; }
-        if ((rc = materialise_zmid(c))) return rc;
+        if ((rc = need_zmid(c, E_BENCH_KERNEL))) return rc;
         const double one[4] = {1.0, 1.0, 1.0, 1.0};
         for (int i = 0; i < 2; ++i) if ((rc = launch_restart_scale(c, one, bytes))) return rc;
         DOTS_HIP(hipEventRecord(c->ev[6], c->stream));

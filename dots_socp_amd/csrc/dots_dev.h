@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/dots_socp_hip.h"
+#include "admission.h"
 
 namespace dots {
 
@@ -87,7 +88,7 @@ struct Dev {
     // state
     double *phi, *A, *B, *lam, *zf, *zm, *ze, *mu, *E, *bf, *bm, *be;
     double *B_st, *bm_st;    // where steps 2+3 (k_q_lambda_mult_carry) STORE the new B and beta_mid: the arrays themselves, or -- on an iteration
-                             // whose z_mid may be asked for -- the alternate B buffer and z_mid's storage (Ctx::zmid_deferred)
+                             // whose z_mid may be asked for -- the alternate B buffer and z_mid's storage (Carried::zmid)
     double *lamc;            // [V][TP] cone multiplier of the last projection (z_mid = lamc/D * pre-image, rebuilt in steps 2+3)
     // DOTS_STEP_CARRY (one GPU, direct solver, pitch <= 128; null otherwise): what the right-hand side and the cone projection of the
     // NEXT iteration gather per corner, stored by steps 2+3 in corner-LIST order (row j = position in cidx; cpos: f*3+k -> j)
@@ -143,7 +144,7 @@ enum {
     CG_PATH_CAP_SHIFT = 20,      // staged CSR entries per tile, bits 20-31
     CG_PATH_G_SHIFT = 32         // workgroups, from bit 32
 };
-// Launches the last iteration took (Ctx::step_path, dots_debug_counter 12), recorded where launch_rhs, launch_soc_projection and
+// Launches the last iteration took (Carried::step_path, dots_debug_counter 12), recorded where launch_rhs, launch_soc_projection and
 // launch_q_lambda_mult choose: a test of one kernel variant asserts that the step ran it.  Host bookkeeping only.
 enum {
     STEP_PATH_RHS = 1,              // k_rhs
@@ -161,9 +162,9 @@ enum {
     STEP_PATH_QL_KKT = 1 << 13,     // K: the fused KKT sums
     STEP_PATH_QL_DIV = 1 << 14,     // DIV: a pending penalty division applied
     STEP_PATH_QL_BMNT = 1 << 15,    // BMNT: beta_mid streamed around the caches
-    STEP_PATH_QL_DEFER = 1 << 16,   // z_mid deferred (Ctx::zmid_deferred)
+    STEP_PATH_QL_DEFER = 1 << 16,   // z_mid deferred (Carried::zmid)
     STEP_PATH_RHS_MASK = 0xff, STEP_PATH_QL_MASK = 0x1ff00,
-    // Ctx::deep_path, dots_debug_counter 15: which form of the launches around the direct solve ran last
+    // Carried::deep_path, dots_debug_counter 15: which form of the launches around the direct solve ran last
     DEEP_PATH_RHS = 1,              // k_rhs_modes2_deep took the right-hand side (and the projection riders)
     DEEP_PATH_INVERSE = 2           // k_time_modes_tile_fast took the inverse time transform
 };
@@ -347,7 +348,7 @@ int launch_rhs(Ctx *c, bool with_soc = false, double dv = 0.0);   // with_soc (o
 bool rhs_divides(const Ctx *c);
 bool ql_divides(const Ctx *c, int zmid_mode);
 int launch_q_lambda_mult(Ctx *c, int zmid_mode = 0, double dv = 0.0);    // 0: read z_mid; 1: rebuild it from the multiplier and store it; 2: rebuild, do not store; dv != 0 (only when ql_divides): the dual arrays are divided as they are read and written back divided
-int materialise_zmid(Ctx *c);                            // z_mid rebuilt from the old B / beta_mid a deferred step kept (no-op otherwise)
+int launch_rebuild_zmid(Ctx *c);                         // z_mid rebuilt from the old B / beta_mid a deferred step kept (admission.h: rebuild_zmid)
 int launch_q_lambda_only(Ctx *c);                       // the (q, lambda_c) closed form alone (is_palm's step 0): z_mid is read from memory
 int launch_adjust_penalty(Ctx *c, double factor);
 int launch_scale_z(Ctx *c, double z_mul, double beta_mul, double sz_new);
@@ -590,7 +591,6 @@ struct Ctx {
     int64_t slab_b_chunk = 0;     // doubles one rank contributes to the right-hand-side all-gather: V * pitch
     int64_t slab_x_chunk = 0;     // ... to the all-gather of the mode-space solution: V * pitch + V (the last interval's cone multipliers)
     int slab_stage = 0;           // next stage dots_slab_stage expects
-    int kkt_halo_fresh = 0;       // mu_lo / B_hi belong to the current iterate
     dots_params prm{};
     int device;
     int lap_solver = 0;
@@ -627,45 +627,32 @@ struct Ctx {
     int step_timed = 0;           // dots_step_flags
     int step_skip_zmid = 0;       // dots_step_flags: steps leave z_mid unspecified (never written, rebuilt on the fly)
     int step_palm = 0;            // dots_step_flags: every iteration opens with the (q, lambda_c) closed form (is_palm = True)
-    // A penalty update (dots_adjust_penalty) is not carried out at once: the next iteration's kernels divide the five dual arrays as
-    // they read them and steps 2+3 write them back divided (one pass over beta_mid saved: solver_socp.py:367-371 is 5 passes in the
-    // reference).  Every other entry point that reads or writes those arrays first carries the division out (flush_division).
-    double pending_div = 0.0;     // 0: none
+    // What the context carries from one call to the next, and what each entry point does to it (admission.h).  A penalty update
+    // (dots_adjust_penalty) is not carried out at once: the next iteration's kernels divide the five dual arrays as they read them
+    // and steps 2+3 write them back divided (one pass over beta_mid saved: solver_socp.py:367-371 is 5 passes in the reference).
+    Carried carried;
     int lazy_div = 1;             // DOTS_LAZY_DIV=0: divide at once (A/B measurements)
     int step_kkt = 0;             // dots_step_flags: steps 2+3 also form the KKT sums they hold in registers (kkt_fused)
     KktFused kkt_fused{};         // their per-workgroup partial sums (own buffer: d.partials serves the other reductions)
     int64_t kkt_fused_cap_v = 0, kkt_fused_cap_f = 0;   // workgroups the buffers hold per slot
-    int kkt_fused_valid = 0;      // ... and they belong to the current iterate and parameters
     int step_carry = 0;           // dots_step_flags: steps 2+3 also store the next iteration's per-corner gathers (cn_sq, cn_g)
-    int carry_valid = 0;          // ... and they belong to the current iterate (cleared by every call that changes state or parameters)
-    int step_path = 0;            // STEP_PATH_* of the last iteration's launches (cleared with carry_valid; a right-hand side starts a new record)
     // The launches around the direct solve at a pitch of 8, 16 or 32 have a form that keeps its loads in flight (k_rhs_modes2_deep: every
     // carried row of a vertex at once; k_time_modes_tile_fast) at the price of registers: taken while a CU gets few of the launch's workgroups
     int rhs_deep = -1;            // DOTS_RHS_DEEP: 0 never (the launches as they were), 1 wherever the kernels exist, -1 (default) the rule deep_launch_wins
     int n_cu = 0;                 // compute units of the device
-    int deep_path = 0;            // DEEP_PATH_* of the last right-hand side and inverse transform (dots_debug_counter 15; cleared with step_path)
-    int zmid_stale = 0;           // z_mid does not belong to the current iterate
     // z_mid on demand (one GPU, carry mapping): an iteration after which z_mid MAY be read (residuals read back, possibly the last one) does
     // not store it (18 T F values that are almost never read); instead steps 2+3 write the new beta_mid into z_mid's storage and the new B
     // into an alternate buffer and the pointers are swapped, so that the old B and beta_mid -- the pre-image of the projection, from which
     // z_mid = (lambda / D) * D (s_z/sqrt3 B_old - beta_mid_old) is rebuilt bit for bit (k_rebuild_zmid) -- survive until the next iteration.
     double *B_alt = nullptr;      // [3F][TP]
-    int zmid_deferred = 0;        // z_mid's storage holds the OLD beta_mid, B_alt the OLD B: materialise_zmid() before anything reads z_mid
     double zmid_dv = 0.0, zmid_sz = 0.0;   // the penalty division that was pending during that step (0: none); scale_factor_z of that step
     int zmid_defer = 1;           // DOTS_ZMID_DEFER=0: store z_mid on those iterations as before (A/B measurements)
     FrontDev front{};             // multifrontal factor (n_nodes == 0: none)
     int use_front = 0;
     FrontSchedule sched{};        // what its installation decided about the sweeps
-    int rhs_ahead_armed = 0;      // DOTS_STEP_RHS_AHEAD: the next KKT launch is followed by the next iteration's right-hand side
-    int rhs_ahead = 0;            // ... which is on the stream and still valid (any call that changes state or parameters clears it); 2: with the
-                                  // cone projection, whose results (z_fst, z_end, the cone multiplier) wait in the alternate buffers below
-                                  // 3 / 4: started by the penalty decision ahead of the host (dots_penalty_ahead) with the division `ahead_dv` applied as it read and
-                                  // the penalty `ahead_r`; becomes 2 when dots_adjust_penalty (3 -> 4) and dots_set_params (4 -> 2) confirm both
-    int penalty_armed = 0;        // dots_penalty_ahead: the next evaluation of conditions 0-3 takes the penalty decision itself
     dots_penalty_policy penalty_policy{};
     double ahead_dv = 0.0, ahead_r = 0.0;   // what the launch ahead anticipated
     int64_t penalty_ahead_started = 0, penalty_ahead_confirmed = 0;   // diagnostics (dots_debug_counter 2, 3)
-    double ahead_div = 0.0;       // rhs_ahead == 2: the division the launch ahead applied as it read (steps 2+3 of the step that takes it must apply the same)
     double *zf_alt = nullptr, *ze_alt = nullptr, *lamc_alt = nullptr;   // [V][TP] each (one GPU): written ahead, swapped in by the step that takes them
     // The factor's device memory.  What every sharer of it reads (factor, node records, maps, leaf inverses and tables, work lists) is in one
     // reference-counted store, created by front_setup and freed with its last holder (dots_front_share copies the pointer); W (update
@@ -679,7 +666,6 @@ struct Ctx {
     int64_t front_many_launches = 0, front_many_split = 0;   // sweep launches of the last front_solve_many, those split below their chunk (dots_debug_counter 7, 8)
     uint64_t lap_hash_graph = 0;  // ... its state after rowptr and col (dots_move_vertices goes on from there)
     uint64_t tri_hash = 0;        // FNV-1a of triangles, corner_ptr and corner_idx: dots_move_vertices_many forms the triangle tables of all members from one scratch
-    int needs_restart = 0;        // dots_move_vertices changed the surface under the iterate: dots_restart before the next step
     uint64_t lap_hash = 0;        // FNV-1a of the Laplacian (rowptr, col, val) and the vertex masses: dots_front_share compares it with the owner's
     int batched = 0;              // stepped by dots_step_many since its last dots_step: dots_penalty_ahead is refused
     // dots_readout: built on first use
@@ -796,7 +782,7 @@ inline bool carry_possible(const Ctx *c) {
 
 // a KKT evaluation of the conditions in `mask` reduces the sums the last steps-2+3 launch left (kernels_kkt.hip: kkt_sums) and reads no z_mid
 inline bool kkt_takes_fused(const Ctx *c, uint32_t mask) {
-    return c->kkt_fused_valid && !(mask & ~(KKT_FUSED_MASK | 4u)) && c->h_mail && c->kkt_counter;
+    return c->carried.kkt_fused_valid && !(mask & ~(KKT_FUSED_MASK | 4u)) && c->h_mail && c->kkt_counter;
 }
 
 int64_t array_count_host(const Dev &d, int array_id);    // elements in the reference layout

@@ -52,7 +52,7 @@ __device__ __forceinline__ double soc_half(const Dev &d, int v, int t, int s, do
 
 // CARRIED: the corners' shares of both halves were stored by the last steps-2+3 launch (cn_sq[j][s][interval], in corner-LIST
 // order: a vertex's rows are contiguous): two loads per corner, no index chain, neither B nor beta_mid is touched.
-// DIV: a penalty update is pending (Ctx::pending_div): the five dual arrays still hold their values BEFORE the division by
+// DIV: a penalty update is pending (Carried::pending_div): the five dual arrays still hold their values BEFORE the division by
 // `dv` (admm_tools / solver_socp.py:367-371) and every entry is divided as it is read -- the same IEEE division the stand-alone
 // kernel (k_divide_five) performs, so nothing changes bit for bit; steps 2+3 of the same iteration write the arrays back divided.
 template <bool ONLY_MULTIPLIER, bool CARRIED = false, bool DIV = false>
@@ -284,7 +284,7 @@ __global__ __launch_bounds__(BLOCK) void k_slab_pack_kkt(Dev d, double *__restri
 }
 int launch_slab_pack_iteration(Ctx *c) {
     if (c->d.nl == 0) return 0;
-    if (c->carry_valid) hipLaunchKernelGGL(k_slab_pack_iteration<true>, dim3((c->d.V + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, c->d, c->prm.scale_z, c->slab.send_x, c->slab.send_nsq);
+    if (c->carried.carry_valid) hipLaunchKernelGGL(k_slab_pack_iteration<true>, dim3((c->d.V + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, c->d, c->prm.scale_z, c->slab.send_x, c->slab.send_nsq);
     else hipLaunchKernelGGL(k_slab_pack_iteration<false>, dim3((c->d.V + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, c->d, c->prm.scale_z, c->slab.send_x, c->slab.send_nsq);
     DOTS_HIP(hipGetLastError());
     return 0;
@@ -302,14 +302,14 @@ int launch_soc_projection(Ctx *c, int zmid_mode, bool with_inverse) {
     const int n_inv = with_inverse ? xcd_grid(c->d.n_vtiles) : 0;
     const size_t lds = with_inverse ? time_modes_tile_lds(c->d) : 0;
     const int IC = time_modes_chunk(c->d);
-    if (zmid_mode && c->carry_valid)
+    if (zmid_mode && c->carried.carry_valid)
         hipLaunchKernelGGL((k_soc_projection<true, true>), dim3(n_soc + n_inv), dim3(BLOCK), lds, c->stream, c->d, c->prm.scale_z, c->prm.const_d, n_soc, IC);
     else if (zmid_mode)
         hipLaunchKernelGGL((k_soc_projection<true>), dim3(n_soc + n_inv), dim3(BLOCK), lds, c->stream, c->d, c->prm.scale_z, c->prm.const_d, n_soc, IC);
     else
         hipLaunchKernelGGL((k_soc_projection<false>), dim3(n_soc + n_inv), dim3(BLOCK), lds, c->stream, c->d, c->prm.scale_z, c->prm.const_d, n_soc, IC);
     DOTS_HIP(hipGetLastError());
-    c->step_path = (c->step_path & ~STEP_PATH_SOC_RIDER) | STEP_PATH_SOC_ALONE;
+    c->carried.step_path = (c->carried.step_path & ~STEP_PATH_SOC_RIDER) | STEP_PATH_SOC_ALONE;
     return 0;
 }
 
@@ -665,7 +665,7 @@ __global__ __launch_bounds__(RHS_NB) void k_rhs_modes_mfma(Dev d, double r, doub
 
 // the right-hand-side (+ projection) launch that launch_rhs would pick can divide the dual arrays as it reads them
 bool rhs_divides(const Ctx *c) {
-    if (!rhs_writes_modes(c) || c->carry_valid) return false;
+    if (!rhs_writes_modes(c) || c->carried.carry_valid) return false;
     if (time_modes_mfma_ok(c->d)) return true;
     return c->d.TP >= 4;
 }
@@ -674,7 +674,7 @@ int launch_rhs(Ctx *c, bool with_soc, double dv) {
     const Dev &d = c->d;
     const int g = xcd_grid(d.n_vtiles);
     const double r = c->prm.r / c->prm.boundary_scale, eps = c->prm.eps, sz = c->prm.scale_z, cd = c->prm.const_d;
-    const bool modes = rhs_writes_modes(c), carried = c->carry_valid != 0;
+    const bool modes = rhs_writes_modes(c), carried = c->carried.carry_valid != 0;
     int path = with_soc ? STEP_PATH_SOC_RIDER : 0;      // (dots_debug_counter 12)
     int deep = 0;                                       // (dots_debug_counter 15)
     // the mode kernels' variants: 0 CARRIED (the corners' shares come from the last steps-2+3 launch), 1 DIV (a penalty update is pending: the dual
@@ -714,8 +714,8 @@ int launch_rhs(Ctx *c, bool with_soc, double dv) {
         });
     }
     DOTS_HIP(hipGetLastError());
-    c->step_path = path;      // the first launch of an iteration: a new record
-    c->deep_path = deep;
+    c->carried.step_path = path;      // the first launch of an iteration: a new record
+    c->carried.deep_path = deep;
     return 0;
 }
 
@@ -1248,7 +1248,7 @@ __global__ __launch_bounds__(CARRY_NB) CARRY_OCCUPANCY void k_q_lambda_mult_carr
     }
 }
 
-// z_mid on demand (Ctx::zmid_deferred): in place on z_mid's storage, which holds the beta_mid the last projection read;
+// z_mid on demand (Carried::zmid): in place on z_mid's storage, which holds the beta_mid the last projection read;
 // Bold: the B it read.  One node per lane; the expression of the steps-2+3 kernels (ZMODE 1), entry for entry.
 __global__ __launch_bounds__(BLOCK) void k_rebuild_zmid(Dev d, const double *__restrict__ Bold, double sz, double dv) {
     const int tile = xcd_tile(blockIdx.x, d.n_ftiles);
@@ -1277,9 +1277,7 @@ __global__ __launch_bounds__(BLOCK) void k_rebuild_zmid(Dev d, const double *__r
         }
     }
 }
-int materialise_zmid(Ctx *c) {
-    if (!c->zmid_deferred) return 0;
-    c->zmid_deferred = 0;
+int launch_rebuild_zmid(Ctx *c) {
     hipLaunchKernelGGL(k_rebuild_zmid, dim3(xcd_grid(c->d.n_ftiles)), dim3(BLOCK), 0, c->stream, c->d, c->B_alt, c->zmid_sz, c->zmid_dv);
     DOTS_HIP(hipGetLastError());
     return 0;
@@ -1304,8 +1302,8 @@ int launch_q_lambda_mult(Ctx *c, int zmid_mode, double dv) {
     const dots_params &p = c->prm;
     const int nf8 = xcd_grid(c->d.n_ftiles), nv8 = xcd_grid(c->d.n_vtiles);
     const double cd = p.const_d, cr = p.congestion * p.r;
-    c->carry_valid = c->kkt_fused_valid = 0;
-    c->step_path &= ~STEP_PATH_QL_MASK;
+    c->carried.drop_for_steps23();
+    c->carried.step_path &= ~STEP_PATH_QL_MASK;
     // DOTS_STEP_KKT_SUMS: the launch also leaves the sums of the KKT conditions it can form from its registers (kkt_fused) and the
     // per-corner gather of Dual(alpha) (cn_e); it takes the carry mapping (whole triangles per workgroup) whether or not the next
     // iteration's gathers are wanted (emit)
@@ -1320,12 +1318,12 @@ int launch_q_lambda_mult(Ctx *c, int zmid_mode, double dv) {
         kf.nf = n_fwg;
         const bool k = kkt && nv8 <= c->kkt_fused_cap_v && n_fwg <= c->kkt_fused_cap_f;
         const int emit = (carry ? 1 : 0) | (k ? 2 : 0);
-        // z_mid on demand: nothing of it is stored; the new B / beta_mid go to the alternate buffers, the old ones stay (Ctx::zmid_deferred)
+        // z_mid on demand: nothing of it is stored; the new B / beta_mid go to the alternate buffers, the old ones stay (Carried::zmid)
         const bool defer = zmid_mode == 1 && c->zmid_defer && c->B_alt && !c->d.slab && !c->step_palm;
         Dev dk = c->d;
         if (defer) { dk.B_st = c->B_alt; dk.bm_st = c->d.zm; }
         auto carry_launch = [&](int zmode, bool with_kkt) {
-            c->step_path |= STEP_PATH_QL_CARRY | (zmode << STEP_PATH_QL_Z_SHIFT) | (with_kkt ? STEP_PATH_QL_KKT : 0) | (dv != 0.0 ? STEP_PATH_QL_DIV : 0) |
+            c->carried.step_path |= STEP_PATH_QL_CARRY | (zmode << STEP_PATH_QL_Z_SHIFT) | (with_kkt ? STEP_PATH_QL_KKT : 0) | (dv != 0.0 ? STEP_PATH_QL_DIV : 0) |
                             (c->sched.bm_nt != 0 ? STEP_PATH_QL_BMNT : 0) | (defer ? STEP_PATH_QL_DEFER : 0);
             with_constant<1, 2>(zmode, [&](auto Z) { with_constant<true, false>(with_kkt, [&](auto K) { with_constant<true, false>(dv != 0.0, [&](auto DIV) {
                 with_constant<true, false>(c->sched.bm_nt != 0, [&](auto BMNT) {
@@ -1345,17 +1343,17 @@ int launch_q_lambda_mult(Ctx *c, int zmid_mode, double dv) {
             c->d.bm_st = c->d.bm;
             c->dcg.B = c->dgt.B = c->d.B; c->dcg.bm = c->dgt.bm = c->d.bm; c->dcg.zm = c->dgt.zm = c->d.zm;
             c->dcg.B_st = c->dgt.B_st = c->d.B; c->dcg.bm_st = c->dgt.bm_st = c->d.bm;
-            c->zmid_deferred = 1;
+            c->carried.zmid = ZMID_DEFERRED;
             c->zmid_dv = dv;
             c->zmid_sz = p.scale_z;
         }
-        c->carry_valid = carry ? 1 : 0;
-        if (k) { c->kkt_fused = kf; c->kkt_fused_valid = 1; }
+        c->carried.carry_valid = carry ? 1 : 0;
+        if (k) { c->kkt_fused = kf; c->carried.kkt_fused_valid = 1; }
         return 0;
     }
     if (c->d.TP >= 4) {      // two nodes per lane (16-byte accesses): k_q_lambda_mult_triangle2
         const dim3 g2(nf8 * (TILE_ELEMS / (2 * BLOCK)) + nv8);
-        c->step_path |= STEP_PATH_QL_TRIANGLE2 | (zmid_mode << STEP_PATH_QL_Z_SHIFT);
+        c->carried.step_path |= STEP_PATH_QL_TRIANGLE2 | (zmid_mode << STEP_PATH_QL_Z_SHIFT);
         if (zmid_mode == 2) hipLaunchKernelGGL((k_q_lambda_mult_triangle2<2>), g2, dim3(BLOCK), 0, c->stream, c->d, p.scale_z, p.tau, nf8, cd, cr);
         else if (zmid_mode == 1) hipLaunchKernelGGL((k_q_lambda_mult_triangle2<1>), g2, dim3(BLOCK), 0, c->stream, c->d, p.scale_z, p.tau, nf8, cd, cr);
         else hipLaunchKernelGGL((k_q_lambda_mult_triangle2<0>), g2, dim3(BLOCK), 0, c->stream, c->d, p.scale_z, p.tau, nf8, cd, cr);
@@ -1363,7 +1361,7 @@ int launch_q_lambda_mult(Ctx *c, int zmid_mode, double dv) {
         return 0;
     }
     const dim3 gf(nf8 * (TILE_ELEMS / BLOCK) + nv8);
-    c->step_path |= STEP_PATH_QL_TRIANGLE | (zmid_mode << STEP_PATH_QL_Z_SHIFT);
+    c->carried.step_path |= STEP_PATH_QL_TRIANGLE | (zmid_mode << STEP_PATH_QL_Z_SHIFT);
     if (zmid_mode == 2) hipLaunchKernelGGL((k_q_lambda_mult_triangle<2>), gf, dim3(BLOCK), 0, c->stream, c->d, p.scale_z, p.tau, nf8, cd, cr);
     else if (zmid_mode == 1) hipLaunchKernelGGL((k_q_lambda_mult_triangle<1>), gf, dim3(BLOCK), 0, c->stream, c->d, p.scale_z, p.tau, nf8, cd, cr);
     else hipLaunchKernelGGL((k_q_lambda_mult_triangle<0>), gf, dim3(BLOCK), 0, c->stream, c->d, p.scale_z, p.tau, nf8, cd, cr);

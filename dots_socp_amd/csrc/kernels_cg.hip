@@ -937,7 +937,7 @@ void modes_forward(Ctx *c, const double *in, double *out, bool direct) {
 void modes_inverse(Ctx *c, const double *x, double *phi, bool direct) {
     const Dev &d = c->d;
     const int gt = xcd_grid(d.n_vtiles);
-    c->deep_path &= ~DEEP_PATH_INVERSE;
+    c->carried.deep_path &= ~DEEP_PATH_INVERSE;
     if (!direct && pcg_windowed(c))
         launch_time_modes_windows<false>(c, x, phi, 0);      // `x` in compact windows
     else if (direct && time_modes_wide_ok(d))
@@ -949,7 +949,7 @@ void modes_inverse(Ctx *c, const double *x, double *phi, bool direct) {
         with_constant<8, 16, 32>(d.TP, [&](auto TPC) {
             hipLaunchKernelGGL((k_time_modes_tile_fast<false, 1024, TPC>), dim3(gt), dim3(1024), time_modes_fast_lds(d), c->stream, d, x, phi);
         });
-        c->deep_path |= DEEP_PATH_INVERSE;
+        c->carried.deep_path |= DEEP_PATH_INVERSE;
     }
     else if (time_modes_tile_ok(d) && direct && d.n_vtiles <= 512)      // small meshes, behind the sweeps: latency-bound, one output per thread (knot: 9.5 -> 6 us; no gain at 10^5 vertices)
         hipLaunchKernelGGL((k_time_modes_tile<false, 1024>), dim3(gt), dim3(1024), time_modes_tile_lds(d), c->stream, d, x, phi, time_modes_chunk(d));

@@ -656,8 +656,8 @@ int kkt_sums(Ctx *c, uint32_t mask, double *sums) {
         DOTS_HIP(hipGetLastError());
         // DOTS_STEP_RHS_AHEAD: while the host waits for these sums and decides, the device starts on the next iteration's
         // right-hand side (it reads only what the next dots_step would read; dots_api.hip: check() drops it if anything changes)
-        if (c->rhs_ahead_armed) {
-            c->rhs_ahead_armed = 0;
+        if (c->carried.rhs_ahead_armed) {
+            c->carried.rhs_ahead_armed = 0;
             if (rhs_writes_modes(c) && c->zf_alt) {      // ... and its cone projection, into the alternate buffers (a dropped launch leaves the state as it is)
                 Dev keep = c->d;
                 c->d.zf = c->zf_alt;
@@ -666,10 +666,10 @@ int kkt_sums(Ctx *c, uint32_t mask, double *sums) {
                 rc = launch_rhs(c, true);
                 c->d = keep;
                 if (rc) return rc;
-                c->rhs_ahead = 2;
+                c->carried.rhs_ahead = 2;
             } else {
                 if ((rc = launch_rhs(c))) return rc;
-                c->rhs_ahead = 1;
+                c->carried.rhs_ahead = 1;
             }
         }
         rc = wait_mail(c, seq, N_SUMS);
@@ -682,8 +682,8 @@ int kkt_sums(Ctx *c, uint32_t mask, double *sums) {
     if (rc) return rc;
     // slots of kernels that did not run hold leftovers of earlier calls: report zeros there
     for (int i = 0; i < N_SUMS; ++i) sums[i] = have[i] ? c->h_pinned[i] : 0.0;
-    if (c->penalty_armed) {
-        c->penalty_armed = 0;
+    if (c->carried.penalty_armed) {
+        c->carried.penalty_armed = 0;
         if ((rc = penalty_decision_ahead(c, mask, sums))) return rc;
     }
     return 0;
@@ -693,8 +693,8 @@ int kkt_sums(Ctx *c, uint32_t mask, double *sums) {
 // arrived, so that the next iteration's first launch is on the stream before the host has even returned to its own (identical) decision.
 int penalty_decision_ahead(Ctx *c, uint32_t mask, const double *sums) {
     const dots_penalty_policy &pp = c->penalty_policy;
-    if ((mask & 15u) != 15u || c->d.slab || c->step_palm || !c->lazy_div || !c->zf_alt || c->rhs_ahead || c->carry_valid || !rhs_divides(c) ||
-        c->pending_div != 0.0 || !carry_possible(c))      // (carry_possible: dots_adjust_penalty will leave the division pending)
+    if ((mask & 15u) != 15u || c->d.slab || c->step_palm || !c->lazy_div || !c->zf_alt || c->carried.rhs_ahead || c->carried.carry_valid || !rhs_divides(c) ||
+        c->carried.pending_div != 0.0 || !carry_possible(c))      // (carry_possible: dots_adjust_penalty will leave the division pending)
         return 0;
     double o[2 * DOTS_N_KKT];
     int rc = kkt_combine(c, 15u, sums, o);
@@ -734,7 +734,7 @@ int penalty_decision_ahead(Ctx *c, uint32_t mask, const double *sums) {
     c->prm.r = r;
     c->d = keep;
     if (rc) return rc;
-    c->rhs_ahead = 3;
+    c->carried.rhs_ahead = 3;
     c->penalty_ahead_started += 1;
     c->ahead_dv = dv;
     c->ahead_r = r_next;

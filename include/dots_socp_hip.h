@@ -24,6 +24,13 @@
  *       dots_upload of phi also takes (n + 1, V) on a slab that has a next slab: the last row is phi at that slab's first node,
  *       which stage 3 computes redundantly and step 0 of DOTS_STEP_PALM and the KKT sums read.  Without that row the node keeps
  *       what the last stage 3 left (zero on a fresh context): upload it whenever one of the two follows before a stage 3.
+ *   - a context carries deferred work from one call to the next (a penalty division not yet applied, sums and gathers the last
+ *     iteration left, a right-hand side launched ahead, a z_mid left to be rebuilt); results never depend on it.  What a call does
+ *     to that work follows from four properties, one table row per function (csrc/admission.h; DESIGN.md, "What a call does to
+ *     deferred work"): it DROPS what belongs to the old state or parameters; it uses the DUAL arrays, so a pending division is
+ *     carried out first; it changes the STATE, so a slab's KKT halos go stale; it steps or measures the iterate on its SURFACE,
+ *     so it is refused after dots_move_vertices until a dots_restart.  A call that reads z_mid from memory rebuilds one that
+ *     was left to be rebuilt, and where the row says so refuses one that is unspecified.
  *   - no C++ exceptions, torch types or Python objects cross this boundary.
  */
 #ifndef DOTS_SOCP_HIP_H
@@ -295,7 +302,8 @@ int dots_kkt_sums(dots_ctx *ctx, uint32_t mask, double *sums /* [DOTS_KKT_N_SUMS
 int dots_kkt_combine(dots_ctx *ctx, uint32_t mask, const double *sums, double *out /* [2*DOTS_N_KKT] */);
 /* dots_kkt_sums with the result left in DEVICE memory of the caller (DOTS_KKT_N_SUMS doubles, e.g. a torch tensor handed to
  * RCCL's all-reduce): only enqueued on the context's stream, no host wait, no copy -- order the consumer's stream with
- * dots_stream_wait.  Slots of sums the mask does not need (and every slot on a rank without nodes) are zero. */
+ * dots_stream_wait.  Slots of sums the mask does not need (and every slot on a rank without nodes) are zero.  z_mid is
+ * refused and rebuilt as by dots_kkt_sums. */
 int dots_kkt_sums_device(dots_ctx *ctx, uint32_t mask, double *device_sums /* [DOTS_KKT_N_SUMS], device memory */);
 
 /* The penalty decision ahead of the host (a hint; one GPU, direct solver).  On the iterations where the reference adapts the penalty
@@ -982,7 +990,9 @@ typedef struct dots_mesh_locate_desc {
 } dots_mesh_locate_desc;
 int dots_mesh_locate(const dots_mesh_locate_desc *desc, int device);
 
-/* launches one direct solve takes: 2 x bands of tree heights (one per band and sweep; a band is one height unless
+/* The three queries below are admitted as calls that change something: a pending penalty division is carried out and what the context
+ * carried is dropped (results do not depend on it).
+ * launches one direct solve takes: 2 x bands of tree heights (one per band and sweep; a band is one height unless
  * dots_front_desc.band_ptr merges heights), minus one with dots_front_desc.top_inverse */
 int dots_front_launches(dots_ctx *ctx);
 /* out[4]: factor bytes one solve reads with one block per tree node (both sweeps: the algorithmic bytes of the solve),

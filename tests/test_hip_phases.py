@@ -485,9 +485,13 @@ def test_penalty_division_left_to_the_next_iteration(fixture, T, monkeypatch):
 @pytest.mark.parametrize("fixture,T", [("ops_ico1.npz", None), ("ops_torus8x6.npz", 30), ("ops_refplane4.npz", 63)])
 def test_z_mid_on_demand_equals_the_stored_one(fixture, T, monkeypatch):
     """Iterations after which z_mid may be read do not store it: steps 2+3 write the new B / beta_mid into alternate buffers and z_mid is
-    rebuilt from the OLD ones when something asks for it (download, Prim(q, z) through the stand-alone kernels, norms, a rescaling,
+    rebuilt from the OLD ones when something asks for it (download, Prim(q, z) through the stand-alone kernels -- dots_kkt,
+    dots_kkt_sums and dots_kkt_sums_device, whose sums in a device buffer have the bits of dots_kkt_sums --, norms, a rescaling,
     is_palm's step 0, a single phase) -- with a penalty division pending during the step too.  DOTS_ZMID_DEFER=0 stores it as before:
     the same numbers bit for bit, whatever is asked for and in whatever order."""
+    import torch
+
+    from dots_socp_amd._lib import KKT_N_SUMS
     from dots_socp_amd.device import DeviceProblem
 
     g = golden(fixture)
@@ -521,8 +525,15 @@ def test_z_mid_on_demand_equals_the_stored_one(fixture, T, monkeypatch):
                 dev.scale_z(3.0, 1.0 / 3.0, 3.0)                           # scales z_mid: rebuilt first
                 dev.set_params(scale_z=3.0, const_d=3.0)
                 res.append(dev.download("z_mid").copy())
-            if k == 9:
-                res.append(dev.kkt([1, 3]))                                # no fused sums on this step: the stand-alone kernels
+            if k == 9:                                                     # no fused sums on this step: the stand-alone kernels
+                sums = torch.zeros(KKT_N_SUMS, dtype=torch.float64, device="cuda")
+                torch.cuda.synchronize()
+                dev.kkt_sums_device([1, 3], sums.data_ptr())               # issued first: this is the call that rebuilds z_mid
+                dev.sync()
+                res.append(sums.cpu().numpy())
+                host = dev.kkt_sums([1, 3])
+                assert np.array_equal(res[-1].view(np.uint64), host.view(np.uint64)), (defer, res[-1], host)
+                res.append(dev.kkt([1, 3]))
             if k == 11:
                 pass                                                       # nobody asks: the next step (is_palm: step 0 reads z_mid) must rebuild it
             if k == 13:
