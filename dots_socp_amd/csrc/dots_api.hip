@@ -1224,7 +1224,7 @@ int dots_front_setup(dots_ctx *c, const dots_front_desc *desc) {
     if ((rc = front_setup(c, desc))) return rc;
     // DOTS_STEP_CARRY: the per-corner gathers steps 2+3 leave for the next right-hand side / projection (one GPU, pitch <= 128);
     // they belong to the direct solver's iteration and are released with the factor
-    {   // beta_mid streamed around the caches (ql2_lane<BMNT>): where factor + the state an iteration touches do not fit the Infinity Cache but the
+    {   // beta_mid streamed around the caches (ql_lane<BMNT>): where factor + the state an iteration touches do not fit the Infinity Cache but the
         // factor is small enough for a good part of it to stay there between the sweeps once beta_mid no longer pushes it out.  Measured, hint against
         // none (profiles/studies/r04_nontemporal.txt): knot -2.5 % (everything fits), knot63 / sphere10k / a 10k torus +9 %, tori of 20k / 40k / 60k vertices
         // +3.3 / +3.7 / +5.0 %, 80k +0.3 %, 100k -0.5 %; T = 63: 20k +2.3 %, 40k +0.1...1.5 %; T = 127: 20k -0.2...+1.7 %, 65k -2 %

@@ -87,8 +87,10 @@ struct Dev {
     const double *sigma;     // [T+1] or null
     // state
     double *phi, *A, *B, *lam, *zf, *zm, *ze, *mu, *E, *bf, *bm, *be;
-    double *B_st, *bm_st;    // where steps 2+3 (k_q_lambda_mult_carry) STORE the new B and beta_mid: the arrays themselves, or -- on an iteration
-                             // whose z_mid may be asked for -- the alternate B buffer and z_mid's storage (Carried::zmid)
+    double *B_st, *bm_st;    // where steps 2+3 (ql_lane) STORE the new B and beta_mid: the arrays themselves, or -- on an iteration whose z_mid may
+                             // be asked for -- the alternate B buffer and z_mid's storage (Carried::zmid).  Every Dev a context keeps has
+                             // B_st == B and bm_st == bm; only the copy launch_q_lambda_mult hands to k_q_lambda_mult_carry ever differs, so
+                             // the tile kernels (k_q_lambda_mult_triangle, k_q_lambda_mult_triangle2) store to the arrays themselves.
     double *lamc;            // [V][TP] cone multiplier of the last projection (z_mid = lamc/D * pre-image, rebuilt in steps 2+3)
     // DOTS_STEP_CARRY (one GPU, direct solver, pitch <= 128; null otherwise): what the right-hand side and the cone projection of the
     // NEXT iteration gather per corner, stored by steps 2+3 in corner-LIST order (row j = position in cidx; cpos: f*3+k -> j)
@@ -278,7 +280,7 @@ struct FrontSchedule {
     int n_bands = 0;          // launches per sweep (= FrontDev::n_levels)
     int top_inverse = 0;      // the top band holds explicit inverses: its forward launch writes x, the backward sweep skips it
     int heights = 0;          // tree heights of the installed factor
-    int bm_nt = 0;            // steps 2+3 stream beta_mid with the non-temporal hint (decided by dots_front_setup: see ql2_lane; DOTS_BM_NT = 0 / 1 overrides)
+    int bm_nt = 0;            // steps 2+3 stream beta_mid with the non-temporal hint (decided by dots_front_setup: see ql_lane; DOTS_BM_NT = 0 / 1 overrides)
     int64_t w_rows = 0;       // rows of W (the sharers allocate as many)
     double bytes = 0.0;       // factor bytes one solve reads (both sweeps, merged blocks as stored)
     double bytes_unmerged = 0.0;   // the same for one launch per tree height (no merged bands)
@@ -798,7 +800,9 @@ __device__ __forceinline__ int64_t idxM(const Dev &d, int fk, int s, int c, int 
     return ((int64_t)((fk * 2 + s) * 3 + c) << d.tp_shift) + t + s;
 }
 // two consecutive time columns of a row in one aligned 16-byte word (even first column)
-struct D2 { double v[2]; };
+// (DN<N>: the N consecutive time columns a lane owns, N = 2 that word, N = 1 one double; ldn / stn and their _nt forms below)
+template <int N> struct DN { double v[N]; };
+using D2 = DN<2>;
 __device__ __forceinline__ D2 ld2(const double *p) { const double2 t = *reinterpret_cast<const double2 *>(p); return D2{{t.x, t.y}}; }
 __device__ __forceinline__ void st2(double *p, const D2 &x) { *reinterpret_cast<double2 *>(p) = make_double2(x.v[0], x.v[1]); }
 // the same with a streaming hint (non-temporal): data written once and read once by the next launch (the carried per-corner sums)
@@ -817,6 +821,11 @@ __device__ __forceinline__ void st2_nt(double *p, const D2 &x) {
     t.y = x.v[1];
     __builtin_nontemporal_store(t, reinterpret_cast<dots_d2v *>(p));
 }
+// a lane's N columns: 16-byte accesses for N = 2, 8-byte ones for N = 1
+template <int N> __device__ __forceinline__ DN<N> ldn(const double *p) { if constexpr (N == 2) return ld2(p); else return DN<1>{{*p}}; }
+template <int N> __device__ __forceinline__ DN<N> ldn_nt(const double *p) { if constexpr (N == 2) return ld2_nt(p); else return DN<1>{{ld1_nt(p)}}; }
+template <int N> __device__ __forceinline__ void stn(double *p, const DN<N> &x) { if constexpr (N == 2) st2(p, x); else *p = x.v[0]; }
+template <int N> __device__ __forceinline__ void stn_nt(double *p, const DN<N> &x) { if constexpr (N == 2) st2_nt(p, x); else __builtin_nontemporal_store(x.v[0], p); }
 // slab predicates for local column t
 __device__ __forceinline__ bool first_node(const Dev &d, int t) { return d.t0 + t == 0; }       // global node 0
 __device__ __forceinline__ bool last_node(const Dev &d, int t) { return d.t0 + t == d.T; }      // global node T

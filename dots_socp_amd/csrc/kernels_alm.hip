@@ -2,8 +2,10 @@
 // of the phi step, the fused (q, lambda_c) + multiplier update, scaling tools, layout conversion.
 // All HBM-bound fp64; one thread per (row, time) element, rows = vertices or (triangle, xyz).
 #include "dots_dev.h"
+#include "kkt_slots.h"
 
 #include <algorithm>
+#include <cassert>
 
 namespace dots {
 
@@ -35,6 +37,9 @@ __device__ __forceinline__ double soc_w2(double D, double sBB, double bm) {
     const double w = D * (sBB - bm);
     return w * w;
 }
+// z_mid from the cone multiplier: z = (lambda / D) * (D * (sz/sqrt3 * B - beta_mid)), sBB = sz/sqrt3 * B already rounded.  The one place where it is
+// written: the full projection stores it, steps 2+3 (ql_lane, ZMODE >= 1) and k_rebuild_zmid rebuild it from the stored multiplier.
+__device__ __forceinline__ double zmid_of(double lam, double D, double sBB, double bm) { return (lam / D) * (D * (sBB - bm)); }
 
 __device__ __forceinline__ double soc_half(const Dev &d, int v, int t, int s, double sB) {
     double acc = 0.0;
@@ -50,173 +55,135 @@ __device__ __forceinline__ double soc_half(const Dev &d, int v, int t, int s, do
     return acc;
 }
 
-// CARRIED: the corners' shares of both halves were stored by the last steps-2+3 launch (cn_sq[j][s][interval], in corner-LIST
-// order: a vertex's rows are contiguous): two loads per corner, no index chain, neither B nor beta_mid is touched.
-// DIV: a penalty update is pending (Carried::pending_div): the five dual arrays still hold their values BEFORE the division by
-// `dv` (admm_tools / solver_socp.py:367-371) and every entry is divided as it is read -- the same IEEE division the stand-alone
-// kernel (k_divide_five) performs, so nothing changes bit for bit; steps 2+3 of the same iteration write the arrays back divided.
-template <bool ONLY_MULTIPLIER, bool CARRIED = false, bool DIV = false>
-__device__ __forceinline__ void soc_element(const Dev &d, int v, int t, double sz, double cd, double dv = 1.0) {
-    const double sB = sz * INV_SQRT3;
-    const int iv = idxV(d, v, t);
-    const int j0 = d.cptr[v], j1 = d.cptr[v + 1];
-    const bool own1 = t + 1 < d.nl;      // node t + 1 is held here (always on one GPU)
-    double acc0 = 0.0, acc1 = 0.0;
-    if (CARRIED) {
-        for (int j = j0; j < j1; j += CARRY_BATCH) {
-            double q0[CARRY_BATCH], q1[CARRY_BATCH];
+// CARRIED: the corners' shares were stored by the last steps-2+3 launch in corner-LIST order (a vertex's rows are contiguous), ROWS rows per
+// corner, the column that of the lane's interval or node: no index chain, neither B, E nor beta_mid is touched.  The rows of the corners
+// j0 .. j1 - 1 at the N columns p points to, added in list order into acc[row][column]: BATCH corners' loads in flight, rows clamped to the list.
+// What lies past the list is dropped by a select, not a branch: behind a branch the compiler moved the later corners' loads too (k_rhs_modes2<true>: the
+// projection's four loads of a pass went out two and two, torus100k 691 -> 676 it/s).
+template <int N, int BATCH, int ROWS>
+__device__ __forceinline__ void carried_gather(const Dev &d, const double *__restrict__ p, int j0, int j1, double (&acc)[ROWS][N]) {
+    for (int j = j0; j < j1; j += BATCH) {
+        DN<N> q[BATCH][ROWS];
 #pragma unroll
-            for (int i = 0; i < CARRY_BATCH; ++i) {
-                const int64_t row = ((int64_t)(2 * min(j + i, j1 - 1)) << d.tp_shift) + t;
-                q0[i] = ld1_nt(d.cn_sq + row);
-                q1[i] = ld1_nt(d.cn_sq + row + d.TP);
-            }
+        for (int i = 0; i < BATCH; ++i) {
+            const int64_t row = (int64_t)(ROWS * min(j + i, j1 - 1)) << d.tp_shift;
 #pragma unroll
-            for (int i = 0; i < CARRY_BATCH; ++i) {
-                if (j + i >= j1) break;
-                acc0 += q0[i];
-                acc1 += q1[i];
-            }
+            for (int r = 0; r < ROWS; ++r) q[i][r] = ldn_nt<N>(p + row + r * d.TP);
         }
-        if (!own1) acc1 = d.nsq_hi[v];      // (time slab: node t + 1 belongs to the next slab, which formed this half)
-    } else {
-        for (int j = j0; j < j1; ++j) {
-            const int fk = d.cidx[j];
-            const int f = fk / 3;
-            const double D = d.c_D[j];
-            double q[3];
 #pragma unroll
-            for (int c = 0; c < 3; ++c) q[c] = soc_w2(D, sB * d.B[idxF(d, f, c, t)], DIV ? d.bm[idxM(d, fk, 0, c, t)] / dv : d.bm[idxM(d, fk, 0, c, t)]);
-            acc0 += sum3(q[0], q[1], q[2]);
-            if (own1) {
+        for (int i = 0; i < BATCH; ++i) {
+            const bool in = j + i < j1;
 #pragma unroll
-                for (int c = 0; c < 3; ++c) q[c] = soc_w2(D, sB * d.B[idxF(d, f, c, t + 1)], DIV ? d.bm[idxM(d, fk, 1, c, t)] / dv : d.bm[idxM(d, fk, 1, c, t)]);
-                acc1 += sum3(q[0], q[1], q[2]);
-            }
+            for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+                for (int u = 0; u < N; ++u) {
+                    const double sum = acc[r][u] + q[i][r].v[u];
+                    acc[r][u] = in ? sum : acc[r][u];
+                }
         }
-        if (!own1) acc1 = d.nsq_hi[v];
-    }
-    const double acc = acc0 + acc1;
-    const double a = d.A[iv];
-    const double w_fst = cd - sz * a - (DIV ? d.bf[iv] / dv : d.bf[iv]);
-    const double w_end = cd + sz * a - (DIV ? d.be[iv] / dv : d.be[iv]);
-    const double nrm = sqrt(acc + w_end * w_end);
-    double lam = 0.5 * (1.0 + w_fst / nrm);          // 0/0 -> NaN when the pre-image is 0, as in the reference (:1018)
-    if (lam == lam) lam = fmin(fmax(lam, 0.0), 1.0);  // np.clip keeps NaN; fmin/fmax would drop it
-    d.zf[iv] = (lam >= 1.0) ? w_fst : lam * nrm;
-    d.ze[iv] = lam * w_end;
-    if (ONLY_MULTIPLIER) {
-        d.lamc[iv] = lam;
-        return;
-    }
-    for (int j = j0; j < j1; ++j) {      // (not reached on a time slab: the full projection needs every node of the interval here)
-        const int fk = d.cidx[j];
-        const int f = fk / 3;
-        const double D = d.c_D[j];
-        const double lt = lam / D;
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const double w = D * (sB * d.B[idxF(d, f, c, t + s)] - d.bm[idxM(d, fk, s, c, t)]);
-                d.zm[idxM(d, fk, s, c, t)] = lt * w;
-            }
     }
 }
 
-// The projection of the intervals t and t + 1 (t even) of a vertex by ONE lane, multiplier only (one GPU: every node is held
-// here): B and the s = 0 entries of both intervals sit in one aligned 16-byte word per row, 15 loads per corner instead of 24;
-// half the waves for the same bytes (see k_q_lambda_mult_triangle2).  Interval for interval the arithmetic of soc_element.
-// CARRIED: see soc_element -- one 16-byte load per corner and half (the s = 1 shares are stored in the column of their INTERVAL).
-template <bool CARRIED = false, bool DIV = false>
-__device__ __forceinline__ void soc_element2(const Dev &d, int v, int t, double sz, double cd, double dv = 1.0) {
-    const double sB = sz * INV_SQRT3;
-    const int iv = idxV(d, v, t);
-    const bool two = t + 1 < d.ni;                 // the second interval exists (T odd: not for the last pair)
-    const int j0 = d.cptr[v], j1 = d.cptr[v + 1];
-    double a0[2] = {0.0, 0.0}, a1[2] = {0.0, 0.0};
-    if (CARRIED) {      // CARRY_BATCH corners' loads in flight (rows clamped to the list, sums in list order)
-        const double *__restrict__ q = d.cn_sq + t;
-        for (int j = j0; j < j1; j += CARRY_BATCH) {
-            D2 q0[CARRY_BATCH], q1[CARRY_BATCH];
+// The multiplier of the cone from the two halves of the middle block's squared norm and the values of A, beta_fst, beta_end at the lane's N
+// intervals; z_fst, z_end (and with ONLY_MULTIPLIER the multiplier) are stored -- as 16-byte words when both intervals of a pair exist.
+template <int N, bool ONLY_MULTIPLIER>
+__device__ __forceinline__ DN<N> soc_finish(const Dev &d, int iv, int t, double sz, double cd, const double (&acc)[2][N], const DN<N> &A, const DN<N> &bf, const DN<N> &be) {
+    DN<N> zf, ze, lm;
 #pragma unroll
-            for (int i = 0; i < CARRY_BATCH; ++i) {
-                const int64_t row = (int64_t)(2 * min(j + i, j1 - 1)) << d.tp_shift;
-                q0[i] = ld2_nt(q + row);
-                q1[i] = ld2_nt(q + row + d.TP);
-            }
-#pragma unroll
-            for (int i = 0; i < CARRY_BATCH; ++i) {
-                if (j + i >= j1) break;
-                a0[0] += q0[i].v[0];
-                a1[0] += q1[i].v[0];
-                a0[1] += q0[i].v[1];
-                a1[1] += q1[i].v[1];
-            }
-        }
-    }
-    for (int j = CARRIED ? j1 : j0; j < j1; ++j) {
-        const int fk = d.cidx[j];
-        const int f = fk / 3;
-        const double D = d.c_D[j];
-        D2 bt[3], m0[3];
-        double b2[3], m1a[3], m1b[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            bt[c] = ld2(d.B + idxF(d, f, c, t));
-            b2[c] = two ? d.B[idxF(d, f, c, t + 2)] : 0.0;
-            m0[c] = ld2(d.bm + idxM(d, fk, 0, c, t));
-            m1a[c] = d.bm[idxM(d, fk, 1, c, t)];
-            m1b[c] = two ? d.bm[idxM(d, fk, 1, c, t + 1)] : 0.0;
-            if (DIV) {
-                m0[c].v[0] /= dv;
-                m0[c].v[1] /= dv;
-                m1a[c] /= dv;
-                m1b[c] /= dv;
-            }
-        }
-        double q[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) q[c] = soc_w2(D, sB * bt[c].v[0], m0[c].v[0]);
-        a0[0] += sum3(q[0], q[1], q[2]);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) q[c] = soc_w2(D, sB * bt[c].v[1], m1a[c]);
-        a1[0] += sum3(q[0], q[1], q[2]);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) q[c] = soc_w2(D, sB * bt[c].v[1], m0[c].v[1]);
-        a0[1] += sum3(q[0], q[1], q[2]);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) q[c] = soc_w2(D, sB * b2[c], m1b[c]);
-        a1[1] += sum3(q[0], q[1], q[2]);
-    }
-    const D2 A = ld2(d.A + iv);
-    D2 bf = ld2(d.bf + iv), be = ld2(d.be + iv);
-    if (DIV) {
-        bf.v[0] /= dv; bf.v[1] /= dv;
-        be.v[0] /= dv; be.v[1] /= dv;
-    }
-    D2 zf, ze, lm;
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const double acc = a0[u] + a1[u];
+    for (int u = 0; u < N; ++u) {
         const double a = A.v[u];
         const double w_fst = cd - sz * a - bf.v[u];
         const double w_end = cd + sz * a - be.v[u];
-        const double nrm = sqrt(acc + w_end * w_end);
+        const double nrm = sqrt((acc[0][u] + acc[1][u]) + w_end * w_end);
         double lam = 0.5 * (1.0 + w_fst / nrm);          // 0/0 -> NaN when the pre-image is 0, as in the reference (:1018)
         if (lam == lam) lam = fmin(fmax(lam, 0.0), 1.0);  // np.clip keeps NaN; fmin/fmax would drop it
         zf.v[u] = (lam >= 1.0) ? w_fst : lam * nrm;
         ze.v[u] = lam * w_end;
         lm.v[u] = lam;
     }
-    if (two) {
-        st2(d.zf + iv, zf);
-        st2(d.ze + iv, ze);
-        st2(d.lamc + iv, lm);
+    if (N == 2 && t + 1 < d.ni) {      // the second interval exists (T odd: not for the last pair)
+        stn<N>(d.zf + iv, zf);
+        stn<N>(d.ze + iv, ze);
+        if (ONLY_MULTIPLIER) stn<N>(d.lamc + iv, lm);
     } else {
         d.zf[iv] = zf.v[0];
         d.ze[iv] = ze.v[0];
-        d.lamc[iv] = lm.v[0];
+        if (ONLY_MULTIPLIER) d.lamc[iv] = lm.v[0];
+    }
+    return lm;
+}
+
+// The projection of the N consecutive intervals t .. t + N - 1 of a vertex by one lane.
+// N = 1: 8-byte accesses; the only form of the full projection (z_mid stored) and on a time slab (the halo nsq_hi).
+// N = 2 (t even, one GPU: every node is held here, multiplier only): B and the s = 0 entries of both intervals sit in one aligned 16-byte
+// word per row, 15 loads per corner instead of 24; half the waves for the same bytes (see ql_lane).
+// CARRIED: carried_gather over cn_sq[j][s][interval] (the s = 1 shares are stored in the column of their INTERVAL).
+// DIV: a penalty update is pending (Carried::pending_div): the five dual arrays still hold their values BEFORE the division by
+// `dv` (admm_tools / solver_socp.py:367-371) and every entry is divided as it is read -- the same IEEE division the stand-alone
+// kernel (k_divide_five) performs, so nothing changes bit for bit; steps 2+3 of the same iteration write the arrays back divided.
+template <int N, bool ONLY_MULTIPLIER, bool CARRIED = false, bool DIV = false>
+__device__ __forceinline__ void soc_lane(const Dev &d, int v, int t, double sz, double cd, double dv = 1.0) {
+    static_assert(N == 1 || ONLY_MULTIPLIER, "the full projection takes one interval per lane");
+    const double sB = sz * INV_SQRT3;
+    const int iv = idxV(d, v, t);
+    const int j0 = d.cptr[v], j1 = d.cptr[v + 1];
+    bool ex[N];      // the end node of interval t + u is held here (N = 1: not at a slab's last interval) and the interval exists (N = 2: T odd)
+#pragma unroll
+    for (int u = 0; u < N; ++u) ex[u] = N == 1 ? t + 1 < d.nl : (u == 0 || t + 1 < d.ni);
+    double acc[2][N] = {};
+    if (CARRIED) carried_gather<N, CARRY_BATCH, 2>(d, d.cn_sq + t, j0, j1, acc);
+    for (int j = CARRIED ? j1 : j0; j < j1; ++j) {
+        const int fk = d.cidx[j];
+        const int f = fk / 3;
+        const double D = d.c_D[j];
+        double b[3][N + 1], m0[3][N], m1[3][N];      // B at the nodes t .. t + N; beta_mid's s = 0 and s = 1 entries of the lane's intervals
+        // N = 2: every load of the corner first, what does not exist dropped by a select.  N = 1: B at node t + 1 and the s = 1 entries behind their
+        // branch, after the s = 0 half: with a corner's twelve loads in flight k_rhs_modes_mfma<false, true> took 74 VGPRs instead of 72 (6 waves
+        // per SIMD instead of 7) and k_soc_projection<true> 58 instead of 50.
+        constexpr bool LATE = N == 1;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const DN<N> bt = ldn<N>(d.B + idxF(d, f, c, t)), mt = ldn<N>(d.bm + idxM(d, fk, 0, c, t));
+            if (!LATE) b[c][N] = ex[N - 1] ? d.B[idxF(d, f, c, t + N)] : 0.0;
+#pragma unroll
+            for (int u = 0; u < N; ++u) {
+                b[c][u] = bt.v[u];
+                m0[c][u] = mt.v[u];
+                if (!LATE) m1[c][u] = ex[u] ? d.bm[idxM(d, fk, 1, c, t + u)] : 0.0;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < N; ++u) {
+            double q[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) q[c] = soc_w2(D, sB * b[c][u], DIV ? m0[c][u] / dv : m0[c][u]);
+            acc[0][u] += sum3(q[0], q[1], q[2]);
+            if (!ex[u]) continue;
+            if (LATE) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) { b[c][u + 1] = d.B[idxF(d, f, c, t + u + 1)]; m1[c][u] = d.bm[idxM(d, fk, 1, c, t + u)]; }
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) q[c] = soc_w2(D, sB * b[c][u + 1], DIV ? m1[c][u] / dv : m1[c][u]);
+            acc[1][u] += sum3(q[0], q[1], q[2]);
+        }
+    }
+    if constexpr (N == 1) { if (!ex[0]) acc[1][0] = d.nsq_hi[v]; }      // (time slab: node t + 1 belongs to the next slab, which formed this half)
+    DN<N> bf = ldn<N>(d.bf + iv), be = ldn<N>(d.be + iv);
+    if (DIV) {
+#pragma unroll
+        for (int u = 0; u < N; ++u) { bf.v[u] /= dv; be.v[u] /= dv; }
+    }
+    const DN<N> lam = soc_finish<N, ONLY_MULTIPLIER>(d, iv, t, sz, cd, acc, ldn<N>(d.A + iv), bf, be);
+    if (ONLY_MULTIPLIER) return;
+    for (int j = j0; j < j1; ++j) {      // (not reached on a time slab: the full projection needs every node of the interval here)
+        const int fk = d.cidx[j];
+        const int f = fk / 3;
+        const double D = d.c_D[j];
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) d.zm[idxM(d, fk, s, c, t)] = zmid_of(lam.v[0], D, sB * d.B[idxF(d, f, c, t + s)], d.bm[idxM(d, fk, s, c, t)]);
     }
 }
 
@@ -247,7 +214,7 @@ __global__ __launch_bounds__(BLOCK) void k_soc_projection(Dev d, double sz, doub
     for (int e = (blockIdx.x / G8) * BLOCK + threadIdx.x; e < TILE_ELEMS; e += TILE_ELEMS) {
         const int v = v0 + (e >> d.tp_shift), t = e & (d.TP - 1);
         if (v >= d.V || t >= d.ni) continue;
-        soc_element<ONLY_MULTIPLIER, CARRIED>(d, v, t, sz, cd);
+        soc_lane<1, ONLY_MULTIPLIER, CARRIED>(d, v, t, sz, cd);
     }
 }
 
@@ -284,8 +251,9 @@ __global__ __launch_bounds__(BLOCK) void k_slab_pack_kkt(Dev d, double *__restri
 }
 int launch_slab_pack_iteration(Ctx *c) {
     if (c->d.nl == 0) return 0;
-    if (c->carried.carry_valid) hipLaunchKernelGGL(k_slab_pack_iteration<true>, dim3((c->d.V + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, c->d, c->prm.scale_z, c->slab.send_x, c->slab.send_nsq);
-    else hipLaunchKernelGGL(k_slab_pack_iteration<false>, dim3((c->d.V + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, c->d, c->prm.scale_z, c->slab.send_x, c->slab.send_nsq);
+    with_constant<true, false>(c->carried.carry_valid != 0, [&](auto CARRIED) {
+        hipLaunchKernelGGL(k_slab_pack_iteration<CARRIED>, dim3((c->d.V + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, c->d, c->prm.scale_z, c->slab.send_x, c->slab.send_nsq);
+    });
     DOTS_HIP(hipGetLastError());
     return 0;
 }
@@ -302,12 +270,10 @@ int launch_soc_projection(Ctx *c, int zmid_mode, bool with_inverse) {
     const int n_inv = with_inverse ? xcd_grid(c->d.n_vtiles) : 0;
     const size_t lds = with_inverse ? time_modes_tile_lds(c->d) : 0;
     const int IC = time_modes_chunk(c->d);
-    if (zmid_mode && c->carried.carry_valid)
-        hipLaunchKernelGGL((k_soc_projection<true, true>), dim3(n_soc + n_inv), dim3(BLOCK), lds, c->stream, c->d, c->prm.scale_z, c->prm.const_d, n_soc, IC);
-    else if (zmid_mode)
-        hipLaunchKernelGGL((k_soc_projection<true>), dim3(n_soc + n_inv), dim3(BLOCK), lds, c->stream, c->d, c->prm.scale_z, c->prm.const_d, n_soc, IC);
-    else
-        hipLaunchKernelGGL((k_soc_projection<false>), dim3(n_soc + n_inv), dim3(BLOCK), lds, c->stream, c->d, c->prm.scale_z, c->prm.const_d, n_soc, IC);
+    // 0: the full projection (z_mid stored), 1: the multiplier only, 2: the multiplier from the carried shares
+    with_constant<0, 1, 2>(!zmid_mode ? 0 : (c->carried.carry_valid ? 2 : 1), [&](auto V) {
+        hipLaunchKernelGGL((k_soc_projection<V != 0, V == 2>), dim3(n_soc + n_inv), dim3(BLOCK), lds, c->stream, c->d, c->prm.scale_z, c->prm.const_d, n_soc, IC);
+    });
     DOTS_HIP(hipGetLastError());
     c->carried.step_path = (c->carried.step_path & ~STEP_PATH_SOC_RIDER) | STEP_PATH_SOC_ALONE;
     return 0;
@@ -320,46 +286,93 @@ int launch_soc_projection(Ctx *c, int zmid_mode, bool with_inverse) {
 // div_x is a gather over the vertex's corner list (no scatter, no atomics).  Each workgroup also
 // emits the partial sum of b (mean removal for the singular eps = 0 operator).
 // ------------------------------------------------------------------------------------------
-template <bool CARRIED = false, bool DIV = false>
-__device__ __forceinline__ double rhs_value(const Dev &d, int v, int t, double r, double eps, double dv = 1.0) {
+// div_t((A + lambda_c - mu) mass) at the lane's N nodes: xp = that product of interval t - 1 (0 when there is none); A, L, M = A, lambda_c, mu of
+// the lane's intervals, in its columns
+template <int N>
+__device__ __forceinline__ void rhs_div_time(const Dev &d, int t, double m, double xp, const DN<N> &A, const DN<N> &L, const DN<N> &M, double (&dt)[N]) {
+    const double ih = 1.0 / d.h;
+    double x[N + 1];
+    x[0] = xp;
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+        x[u + 1] = t + u < d.ni ? (A.v[u] + L.v[u] - M.v[u]) * m : 0.0;
+        dt[u] = (x[u + 1] - x[u]) * ih;
+    }
+}
+// The right-hand side at the lane's N nodes t .. t + N - 1 from its parts: dt (rhs_div_time), P = phi in the lane's columns, ds = the nodes'
+// div_x((B - E) area), mu0[i] / mu1[i] = the vertex's boundary masses, read behind their branch, by the lanes of node 0 / T only (the deep form has
+// them in registers and passes their addresses; handing them over by value put the loads before the branch and ten instructions into k_rhs_modes2).
+template <int N>
+__device__ __forceinline__ void rhs_finish(const Dev &d, int t, double r, double eps, double m, const double (&dt)[N], const DN<N> &P, const double (&ds)[1][N],
+                                           const double *mu0, const double *mu1, int i, double (&out)[N]) {
+    const int t0 = N == 1 ? d.t0 : 0;      // (two nodes per lane run on one GPU; t is even then: its second node is never node 0)
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+        double rhs = dt[u];
+        rhs -= ds[0][u];
+        if (t0 + t + u == 0) rhs += mu0[i] / (r * d.h);       // first_node
+        if (t0 + t + u == d.T) rhs -= mu1[i] / (r * d.h);     // last_node
+        rhs -= eps * m * P.v[u];
+        out[u] = -rhs;
+    }
+}
+
+// The right-hand side at the N consecutive nodes t .. t + N - 1 of a vertex by one lane.  N = 1: 8-byte accesses; on a time slab interval t0 - 1
+// lives in the previous slab (the halo X_lo).  N = 2 (t even, one GPU): the vertex arrays, B and E of both nodes in one 16-byte word per row.
+// CARRIED: the corners' shares of div_x((B - E) area) were stored by the last steps-2+3 launch (cn_g[j][node]).  DIV: see soc_lane.
+template <int N, bool CARRIED = false, bool DIV = false>
+__device__ __forceinline__ void rhs_lane(const Dev &d, int v, int t, double r, double eps, double (&out)[N], double dv = 1.0) {
     const int iv = idxV(d, v, t);
     const double m = d.mass_v[v];
-    const double ih = 1.0 / d.h;
-    double xt = 0.0, xm = 0.0;
-    if (t < d.ni) xt = (d.A[iv] + d.lam[iv] - (DIV ? d.mu[iv] / dv : d.mu[iv])) * m;
-    if (t > 0) xm = (d.A[iv - 1] + d.lam[iv - 1] - (DIV ? d.mu[iv - 1] / dv : d.mu[iv - 1])) * m;
-    else if (has_prev_interval(d, t)) xm = d.X_lo[v] * m;      // interval t0 - 1 lives in the previous time slab
-    double rhs = (xt - xm) * ih;
-    double ds = 0.0;
-    if (CARRIED) {      // the corners' shares of div_x((B - E) area) were stored by the last steps-2+3 launch (cn_g[j][node])
-        const int jc0 = d.cptr[v], jc1 = d.cptr[v + 1];
-        for (int j = jc0; j < jc1; j += CARRY_BATCH) {
-            double gj[CARRY_BATCH];
-#pragma unroll
-            for (int i = 0; i < CARRY_BATCH; ++i) gj[i] = ld1_nt(d.cn_g + ((int64_t)min(j + i, jc1 - 1) << d.tp_shift) + t);
-#pragma unroll
-            for (int i = 0; i < CARRY_BATCH; ++i) {
-                if (j + i >= jc1) break;
-                ds += gj[i];
-            }
-        }
+    DN<N> P;
+    double dt[N], ds[1][N] = {};
+    if constexpr (N == 1) {
+        // One node per lane keeps its own head: the interval's loads behind `t < ni`, interval t first, then t - 1, phi loaded after the walk.  Through
+        // the two-node head below (every load first, interval t - 1 first) the one-node kernels held 2 to 6 VGPRs more -- k_rhs<true> 42 against 36,
+        // k_rhs<false> 52 / 48, k_rhs_modes 54 / 50, k_rhs_modes_mfma<false, true> 74 / 72 = 6 waves per SIMD against 7 -- and the slab iteration at
+        // torus100k ran at 517 it/s against 525-531 (profiles/elementwise_lanes).
+        const double ih = 1.0 / d.h;
+        double xt = 0.0, xm = 0.0;
+        if (t < d.ni) xt = (d.A[iv] + d.lam[iv] - (DIV ? d.mu[iv] / dv : d.mu[iv])) * m;
+        if (t > 0) xm = (d.A[iv - 1] + d.lam[iv - 1] - (DIV ? d.mu[iv - 1] / dv : d.mu[iv - 1])) * m;
+        else if (has_prev_interval(d, t)) xm = d.X_lo[v] * m;      // interval t0 - 1 lives in the previous time slab
+        dt[0] = (xt - xm) * ih;
     } else {
-        for (int j = d.cptr[v]; j < d.cptr[v + 1]; ++j) {
-            const int f = d.cidx[j] / 3;
-            double g[3];
+        const DN<N> A = ldn<N>(d.A + iv), L = ldn<N>(d.lam + iv);
+        P = ldn<N>(d.phi + iv);
+        DN<N> M = ldn<N>(d.mu + iv);
+        double xp = 0.0;
+        if (t > 0) xp = (d.A[iv - 1] + d.lam[iv - 1] - (DIV ? d.mu[iv - 1] / dv : d.mu[iv - 1])) * m;
+        if (DIV) {
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int64_t i = idxF(d, f, c, t);
-                g[c] = d.c_gA[j * 3 + c] * (d.B[i] - (DIV ? d.E[i] / dv : d.E[i]));
-            }
-            ds += sum3(g[0], g[1], g[2]);
+            for (int u = 0; u < N; ++u) M.v[u] /= dv;
         }
+        rhs_div_time<N>(d, t, m, xp, A, L, M, dt);
     }
-    rhs -= ds;
-    if (first_node(d, t)) rhs += d.mu0[v] / (r * d.h);
-    if (last_node(d, t)) rhs -= d.mu1[v] / (r * d.h);
-    rhs -= eps * m * d.phi[iv];
-    return -rhs;
+    const int j0 = d.cptr[v], j1 = d.cptr[v + 1];
+    if (CARRIED) carried_gather<N, CARRY_BATCH, 1>(d, d.cn_g + t, j0, j1, ds);
+    for (int j = CARRIED ? j1 : j0; j < j1; ++j) {
+        const int f = d.cidx[j] / 3;
+        double g[N][3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double ga = d.c_gA[j * 3 + c];
+            const int64_t i = idxF(d, f, c, t);
+            const DN<N> b = ldn<N>(d.B + i), e = ldn<N>(d.E + i);
+#pragma unroll
+            for (int u = 0; u < N; ++u) g[u][c] = ga * (b.v[u] - (DIV ? e.v[u] / dv : e.v[u]));
+        }
+#pragma unroll
+        for (int u = 0; u < N; ++u) ds[0][u] += sum3(g[u][0], g[u][1], g[u][2]);
+    }
+    if constexpr (N == 1) P = ldn<N>(d.phi + iv);
+    rhs_finish<N>(d, t, r, eps, m, dt, P, ds, d.mu0, d.mu1, v, out);
+}
+template <bool CARRIED = false, bool DIV = false>
+__device__ __forceinline__ double rhs_value(const Dev &d, int v, int t, double r, double eps, double dv = 1.0) {
+    double b[1];
+    rhs_lane<1, CARRIED, DIV>(d, v, t, r, eps, b, dv);
+    return b[0];
 }
 
 // Workgroups [n_rhs, gridDim.x) (when there are any): the cone projection, a quarter tile each, as in k_rhs_modes.
@@ -371,7 +384,7 @@ __global__ __launch_bounds__(BLOCK) void k_rhs(Dev d, double r, double eps, int 
         const int st = xcd_tile(b % G8, d.n_vtiles);
         if (st >= d.n_vtiles) return;
         const int e = (b / G8) * BLOCK + threadIdx.x, v = st * d.VT + (e >> d.tp_shift), t = e & (d.TP - 1);
-        if (v < d.V && t < d.ni) soc_element<true, CARRIED>(d, v, t, sz, cd);
+        if (v < d.V && t < d.ni) soc_lane<1, true, CARRIED>(d, v, t, sz, cd);
         return;
     }
     const int tile = xcd_tile(blockIdx.x, d.n_vtiles);
@@ -401,7 +414,7 @@ __global__ __launch_bounds__(RHS_NB) void k_rhs_modes(Dev d, double r, double ep
         const int st = xcd_tile(blockIdx.x - n_rhs, d.n_vtiles);
         if (st >= d.n_vtiles) return;
         const int e = threadIdx.x, v = st * d.VT + (e >> d.tp_shift), t = e & (d.TP - 1);
-        if (v < d.V && t < d.ni) soc_element<true>(d, v, t, sz, cd);
+        if (v < d.V && t < d.ni) soc_lane<1, true>(d, v, t, sz, cd);
         return;
     }
     extern __shared__ double tm_lds[];
@@ -419,71 +432,6 @@ __global__ __launch_bounds__(RHS_NB) void k_rhs_modes(Dev d, double r, double ep
     modes_from_tile<true, RHS_NB>(d, d.Q, xs, Qs, IC, v0, bhat, -1, 0, 1 << 30, true);
 }
 
-// The right-hand side at the nodes t and t + 1 (t even) of a vertex by one lane (one GPU), node for node the arithmetic of
-// rhs_value: B and E of both nodes in one 16-byte word per row.
-template <bool CARRIED = false, bool DIV = false>
-__device__ __forceinline__ void rhs_value2(const Dev &d, int v, int t, double r, double eps, double (&out)[2], double dv = 1.0) {
-    const int iv = idxV(d, v, t);
-    const double m = d.mass_v[v];
-    const double ih = 1.0 / d.h;
-    const D2 A = ld2(d.A + iv), L = ld2(d.lam + iv), P = ld2(d.phi + iv);
-    D2 M = ld2(d.mu + iv);
-    double mp = t > 0 ? d.mu[iv - 1] : 0.0;
-    if (DIV) {
-        M.v[0] /= dv; M.v[1] /= dv;
-        mp /= dv;
-    }
-    const double xp = t > 0 ? (d.A[iv - 1] + d.lam[iv - 1] - mp) * m : 0.0;      // interval t - 1
-    const double x0 = t < d.ni ? (A.v[0] + L.v[0] - M.v[0]) * m : 0.0;                      // interval t
-    const double x1 = t + 1 < d.ni ? (A.v[1] + L.v[1] - M.v[1]) * m : 0.0;                  // interval t + 1
-    double rhs[2] = {(x0 - xp) * ih, (x1 - x0) * ih};
-    double ds[2] = {0.0, 0.0};
-    const int jc0 = d.cptr[v], jc1 = d.cptr[v + 1];
-    if (CARRIED) {
-        const double *__restrict__ g = d.cn_g + t;
-        for (int j = jc0; j < jc1; j += CARRY_BATCH) {
-            D2 gj[CARRY_BATCH];
-#pragma unroll
-            for (int i = 0; i < CARRY_BATCH; ++i) gj[i] = ld2_nt(g + ((int64_t)min(j + i, jc1 - 1) << d.tp_shift));
-#pragma unroll
-            for (int i = 0; i < CARRY_BATCH; ++i) {
-                if (j + i >= jc1) break;
-                ds[0] += gj[i].v[0];
-                ds[1] += gj[i].v[1];
-            }
-        }
-    }
-    for (int j = CARRIED ? jc1 : jc0; j < jc1; ++j) {
-        const int f = d.cidx[j] / 3;
-        D2 b[3], e[3];
-        double ga[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            ga[c] = d.c_gA[j * 3 + c];
-            const int64_t i = idxF(d, f, c, t);
-            b[c] = ld2(d.B + i);
-            e[c] = ld2(d.E + i);
-            if (DIV) { e[c].v[0] /= dv; e[c].v[1] /= dv; }
-        }
-        double g0[3], g1[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            g0[c] = ga[c] * (b[c].v[0] - e[c].v[0]);
-            g1[c] = ga[c] * (b[c].v[1] - e[c].v[1]);
-        }
-        ds[0] += sum3(g0[0], g0[1], g0[2]);
-        ds[1] += sum3(g1[0], g1[1], g1[2]);
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        rhs[u] -= ds[u];
-        if (t + u == 0) rhs[u] += d.mu0[v] / (r * d.h);
-        if (t + u == d.T) rhs[u] -= d.mu1[v] / (r * d.h);
-        rhs[u] -= eps * m * P.v[u];
-        out[u] = -rhs[u];
-    }
-}
-
 // k_rhs_modes with two time columns per lane (one GPU, direct solver): 512 threads per tile.
 constexpr int RHS_NB2 = RHS_NB / 2;
 template <bool CARRIED, bool DIV = false>
@@ -493,7 +441,7 @@ __global__ __launch_bounds__(RHS_NB2) void k_rhs_modes2(Dev d, double r, double 
         const int st = xcd_tile(blockIdx.x - n_rhs, d.n_vtiles);
         if (st >= d.n_vtiles) return;
         const int v = st * d.VT + vl;
-        if (v < d.V && t < d.ni) soc_element2<CARRIED, DIV>(d, v, t, sz, cd, dv);
+        if (v < d.V && t < d.ni) soc_lane<2, true, CARRIED, DIV>(d, v, t, sz, cd, dv);
         return;
     }
     extern __shared__ double tm_lds[];
@@ -508,7 +456,7 @@ __global__ __launch_bounds__(RHS_NB2) void k_rhs_modes2(Dev d, double r, double 
         const int vv = ee >> d.tp_shift, tt = ee & (TP - 1);
         const int v = v0 + vv;
         double b[2] = {0.0, 0.0};
-        if (v < d.V && tt < n) rhs_value2<CARRIED, DIV>(d, v, tt, r, eps, b, dv);
+        if (v < d.V && tt < n) rhs_lane<2, CARRIED, DIV>(d, v, tt, r, eps, b, dv);
         xs[vv * TPp + tt] = b[0];
         xs[vv * TPp + tt + 1] = tt + 1 < n ? b[1] : 0.0;
     }
@@ -520,91 +468,28 @@ __global__ __launch_bounds__(RHS_NB2) void k_rhs_modes2(Dev d, double r, double 
 // branch, cptr, the carried rows CARRY_BATCH at a time, mu0 / mu1 behind theirs -- and the workgroup's barrier waits for the slowest
 // lane.  Here a lane issues cptr together with everything that does not depend on it (addresses clamped instead of branches: every
 // load is unconditional, what it must not use is dropped by a select), then ALL carried rows of its vertex: DEEP_BATCH corners per
-// pass, rows clamped to the list, added in list order -- value for value the sums of rhs_value2<true> / soc_element2<true>.
+// pass, rows clamped to the list, added in list order -- carried_gather with DEEP_BATCH; the rest is rhs_finish / soc_finish, as in rhs_lane<2, true> / soc_lane<2, true, true>.
 // The rows in flight cost registers (occupancy): launch_rhs takes this form while a CU gets few workgroups (deep_launch_wins).
 constexpr int DEEP_BATCH = 8;      // corners per pass (closed surfaces: valence ~ 6: one pass)
-__device__ __forceinline__ void rhs_value2_deep(const Dev &d, int v, int t, double r, double eps, double (&out)[2]) {
+__device__ __forceinline__ void rhs_lane2_deep(const Dev &d, int v, int t, double r, double eps, double (&out)[2]) {
     const int iv = idxV(d, v, t), ip = t > 0 ? iv - 1 : iv;
     const int jc0 = d.cptr[v], jc1 = d.cptr[v + 1];
     const double m = d.mass_v[v];
     const D2 A = ld2(d.A + iv), L = ld2(d.lam + iv), P = ld2(d.phi + iv), M = ld2(d.mu + iv);
     const double Ap = d.A[ip], Lp = d.lam[ip], Mp = d.mu[ip];
     const double m0 = d.mu0[v], m1 = d.mu1[v];
-    const double *__restrict__ g = d.cn_g + t;
-    double ds[2] = {0.0, 0.0};
-    for (int j = jc0; j < jc1; j += DEEP_BATCH) {
-        D2 gj[DEEP_BATCH];
-#pragma unroll
-        for (int i = 0; i < DEEP_BATCH; ++i) gj[i] = ld2_nt(g + ((int64_t)min(j + i, jc1 - 1) << d.tp_shift));
-#pragma unroll
-        for (int i = 0; i < DEEP_BATCH; ++i) {
-            const double s0 = ds[0] + gj[i].v[0], s1 = ds[1] + gj[i].v[1];
-            ds[0] = j + i < jc1 ? s0 : ds[0];
-            ds[1] = j + i < jc1 ? s1 : ds[1];
-        }
-    }
-    const double ih = 1.0 / d.h;
-    const double xp = t > 0 ? (Ap + Lp - Mp) * m : 0.0;                                      // interval t - 1
-    const double x0 = t < d.ni ? (A.v[0] + L.v[0] - M.v[0]) * m : 0.0;                      // interval t
-    const double x1 = t + 1 < d.ni ? (A.v[1] + L.v[1] - M.v[1]) * m : 0.0;                  // interval t + 1
-    double rhs[2] = {(x0 - xp) * ih, (x1 - x0) * ih};
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        rhs[u] -= ds[u];
-        if (t + u == 0) rhs[u] += m0 / (r * d.h);
-        if (t + u == d.T) rhs[u] -= m1 / (r * d.h);
-        rhs[u] -= eps * m * P.v[u];
-        out[u] = -rhs[u];
-    }
+    double dt[2], ds[1][2] = {};
+    carried_gather<2, DEEP_BATCH, 1>(d, d.cn_g + t, jc0, jc1, ds);
+    rhs_div_time<2>(d, t, m, t > 0 ? (Ap + Lp - Mp) * m : 0.0, A, L, M, dt);
+    rhs_finish<2>(d, t, r, eps, m, dt, P, ds, &m0, &m1, 0, out);
 }
-__device__ __forceinline__ void soc_element2_deep(const Dev &d, int v, int t, double sz, double cd) {
+__device__ __forceinline__ void soc_lane2_deep(const Dev &d, int v, int t, double sz, double cd) {
     const int iv = idxV(d, v, t);
-    const bool two = t + 1 < d.ni;                 // the second interval exists (T odd: not for the last pair)
     const int j0 = d.cptr[v], j1 = d.cptr[v + 1];
     const D2 A = ld2(d.A + iv), bf = ld2(d.bf + iv), be = ld2(d.be + iv);
-    double a0[2] = {0.0, 0.0}, a1[2] = {0.0, 0.0};
-    const double *__restrict__ q = d.cn_sq + t;
-    for (int j = j0; j < j1; j += DEEP_BATCH) {
-        D2 q0[DEEP_BATCH], q1[DEEP_BATCH];
-#pragma unroll
-        for (int i = 0; i < DEEP_BATCH; ++i) {
-            const int64_t row = (int64_t)(2 * min(j + i, j1 - 1)) << d.tp_shift;
-            q0[i] = ld2_nt(q + row);
-            q1[i] = ld2_nt(q + row + d.TP);
-        }
-#pragma unroll
-        for (int i = 0; i < DEEP_BATCH; ++i) {
-            const bool in = j + i < j1;
-            const double s00 = a0[0] + q0[i].v[0], s10 = a1[0] + q1[i].v[0], s01 = a0[1] + q0[i].v[1], s11 = a1[1] + q1[i].v[1];
-            a0[0] = in ? s00 : a0[0];
-            a1[0] = in ? s10 : a1[0];
-            a0[1] = in ? s01 : a0[1];
-            a1[1] = in ? s11 : a1[1];
-        }
-    }
-    D2 zf, ze, lm;
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const double acc = a0[u] + a1[u];
-        const double a = A.v[u];
-        const double w_fst = cd - sz * a - bf.v[u];
-        const double w_end = cd + sz * a - be.v[u];
-        const double nrm = sqrt(acc + w_end * w_end);
-        double lam = 0.5 * (1.0 + w_fst / nrm);          // 0/0 -> NaN when the pre-image is 0, as in the reference (:1018)
-        if (lam == lam) lam = fmin(fmax(lam, 0.0), 1.0);  // np.clip keeps NaN; fmin/fmax would drop it
-        zf.v[u] = (lam >= 1.0) ? w_fst : lam * nrm;
-        ze.v[u] = lam * w_end;
-        lm.v[u] = lam;
-    }
-    if (two) {
-        st2(d.zf + iv, zf);
-        st2(d.ze + iv, ze);
-        st2(d.lamc + iv, lm);
-    } else {
-        d.zf[iv] = zf.v[0];
-        d.ze[iv] = ze.v[0];
-        d.lamc[iv] = lm.v[0];
-    }
+    double acc[2][2] = {};
+    carried_gather<2, DEEP_BATCH, 2>(d, d.cn_sq + t, j0, j1, acc);
+    soc_finish<2, true>(d, iv, t, sz, cd, acc, A, bf, be);
 }
 
 // k_rhs_modes2<true> in that form: Q is loaded first and held in registers while the walk's loads are in flight, written to LDS with
@@ -616,7 +501,7 @@ __global__ __launch_bounds__(RHS_NB2) void k_rhs_modes2_deep(Dev d, double r, do
         const int st = xcd_tile(blockIdx.x - n_rhs, d.n_vtiles);
         if (st >= d.n_vtiles) return;
         const int v = st * d.VT + vl;
-        if (v < d.V && t < d.ni) soc_element2_deep(d, v, t, sz, cd);
+        if (v < d.V && t < d.ni) soc_lane2_deep(d, v, t, sz, cd);
         return;
     }
     extern __shared__ dots_d2v tm_lds_deep[];
@@ -630,7 +515,7 @@ __global__ __launch_bounds__(RHS_NB2) void k_rhs_modes2_deep(Dev d, double r, do
     QStage<true, RHS_NB2, TPC> qs;
     qs.load(d, d.Q);
     double b[2] = {0.0, 0.0};
-    if (v < d.V && t < n) rhs_value2_deep(d, v, t, r, eps, b);
+    if (v < d.V && t < n) rhs_lane2_deep(d, v, t, r, eps, b);
     qs.store(Qs);
     dots_d2v bb;
     bb.x = b[0];
@@ -647,7 +532,7 @@ __global__ __launch_bounds__(RHS_NB) void k_rhs_modes_mfma(Dev d, double r, doub
         const int st = xcd_tile(blockIdx.x - n_rhs, d.n_vtiles);
         if (st >= d.n_vtiles) return;
         const int e = threadIdx.x, v = st * d.VT + (e >> d.tp_shift), t = e & (d.TP - 1);
-        if (v < d.V && t < d.ni) soc_element<true, CARRIED, DIV>(d, v, t, sz, cd, dv);
+        if (v < d.V && t < d.ni) soc_lane<1, true, CARRIED, DIV>(d, v, t, sz, cd, dv);
         return;
     }
     extern __shared__ double xs_m[];                    // [TM_ROWS][TP + 1]
@@ -742,10 +627,10 @@ constexpr int KV_SLOT[KV_N] = {V_DPHI2, V_A2, V_LAM2, V_RESMU2, V_RFST2, V_REND2
 constexpr int KF_N = 7;
 constexpr int KF_SLOT[KF_N] = {F_DX2, F_B2, F_RESE2, F_E2, F_AUX2_2, F_EAUX2_2, F_RMID2};
 
-// KKT: the expressions of kkt_vertex_body (kernels_kkt.hip) on the values this element has just computed, accumulated in ks[KV_N]
+// KKT: the vertex sums that need nothing beyond this element (the slots KV_SLOT), on the values it has just computed; sv is indexed by V_*
 template <bool QONLY, int NB = BLOCK, bool KKT = false, bool DIV = false>
 __device__ __forceinline__ void q_lambda_vertex_tile(const Dev &d, int tile, double sz, double cd, double cr, double tau, const KktArgs *ka = nullptr,
-                                                     double *ks = nullptr, double dv = 1.0) {
+                                                     double *sv = nullptr, double dv = 1.0) {
     const int v0 = tile * d.VT;
     const double a1 = sz * (1.0 + cr);
     const double a2 = 1.0 + 2.0 * sz * a1;
@@ -757,7 +642,7 @@ __device__ __forceinline__ void q_lambda_vertex_tile(const Dev &d, int tile, dou
         const double dphi = (next_node(d, d.phi, d.phi_hi, v, t) - d.phi[iv]) * ih;
         const double zf = d.zf[iv], ze = d.ze[iv];
         double mu = d.mu[iv], bf = d.bf[iv], be = d.be[iv];
-        if (DIV) { mu /= dv; bf /= dv; be /= dv; }      // (a pending penalty update: see soc_element)
+        if (DIV) { mu /= dv; bf /= dv; be /= dv; }      // (a pending penalty update: see soc_lane)
         const double memo = dphi + mu;
         const double a = ia2 * memo + a12 * (ze + be - zf - bf);
         const double lc = cl * (memo - a);
@@ -770,133 +655,47 @@ __device__ __forceinline__ void q_lambda_vertex_tile(const Dev &d, int tile, dou
         d.be[iv] = ben;
         if (KKT) {
             const double m = d.mass_v[v];
-            const double rm = dphi - a - lc;
-            ks[0] += dphi * dphi * m;
-            ks[1] += a * a * m;
-            ks[2] += lc * lc * m;
-            ks[3] += rm * rm * m;
-            const double rf = zf + ka->sz * a - ka->cd, re = ze - ka->sz * a - ka->cd;
-            ks[4] += rf * rf * m;
-            ks[5] += re * re * m;
-            ks[6] += mun * mun * m;
-            const double x1 = ka->sz * (ben - bfn);
-            ks[7] += x1 * x1 * m;
-            ks[8] += (mun + x1) * (mun + x1) * m;
-            const double res = ka->cong * ((ka->ds * ka->r) * mun) - ka->ps * lc;
-            ks[9] += res * res * m;
+            kkt_v_prim_q(sv, dphi, a, lc, m);
+            sv[V_LAM2] += wsq(lc, m);
+            kkt_v_prim_z(sv, *ka, zf, ze, a, m);
+            sv[V_MU2] += wsq(mun, m);
+            kkt_v_dual_beta(sv, *ka, mun, bfn, ben, m);
+            kkt_v_cong(sv, *ka, mun, lc, m);
         }
     }
 }
 
-// ZMODE 0: z_mid is read from memory; 1: rebuilt from the cone multiplier (same expression as the projection
-// kernel: z = (lambda / D) * (D * (sz/sqrt3 * B_old - beta_mid))) and stored; 2: rebuilt, not stored.
-// Workgroups [0, nf8) do the triangle part; with VERTEX_TOO the vertex part (independent of it: different
-// arrays) rides in the same launch as workgroups [nf8, nf8 + nv8).
-template <int ZMODE, bool QONLY = false>
-__global__ __launch_bounds__(BLOCK) void k_q_lambda_mult_triangle(Dev d, double sz, double tau, int nf8, double cd, double cr) {
-    constexpr int SUB = TILE_ELEMS / BLOCK;     // one element per thread: a workgroup takes a quarter of a triangle tile
-    if ((int)blockIdx.x >= nf8 * SUB) {
-        const int vt = xcd_tile(blockIdx.x - nf8 * SUB, d.n_vtiles);
-        if (vt < d.n_vtiles) q_lambda_vertex_tile<QONLY>(d, vt, sz, cd, cr, tau);
-        return;
-    }
-    const int tile = xcd_tile(blockIdx.x % nf8, d.n_ftiles);
-    if (tile >= d.n_ftiles) return;
-    const int row0 = tile * d.FT;
-    const double sB = sz * INV_SQRT3;
-    const double diag_in = 1.0 + 2.0 * sz * sz, diag_bd = 1.0 + sz * sz;
-    for (int e = (blockIdx.x / nf8) * BLOCK + threadIdx.x; e < TILE_ELEMS; e += TILE_ELEMS) {
-        const int row = row0 + (e >> d.tp_shift), t = e & (d.TP - 1);
-        if (row >= 3 * d.F || t >= d.nl) continue;
-        const int f = row / 3, c = row - 3 * f;
-        // All loads first and unconditional: the compiler then issues them back to back instead of one wait per guarded
-        // load.  Both corner entries of this node sit in ITS column (idxM), whether their interval exists or not (then the
-        // slot holds a zero that is masked below); the multiplier of interval t - 1 comes from the previous time slab's
-        // halo when this is the slab's first node.
-        const bool has0 = t < d.ni, has1 = has_prev_interval(d, t);
-        const int64_t ie = idxF(d, f, c, t);
-        int vk[3];
-        double hk[3], Dk[3], phik[3], l0[3], l1[3], b0[3], b1[3], z0[3], z1[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            vk[k] = d.tri[f * 3 + k];
-            hk[k] = d.hat[(f * 3 + k) * 3 + c];
-            Dk[k] = ZMODE ? d.fk_D[f * 3 + k] : 1.0;
-        }
-        const double Bold = ZMODE ? d.B[ie] : 0.0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            phik[k] = d.phi[idxV(d, vk[k], t)];
-            b0[k] = d.bm[idxM(d, f * 3 + k, 0, c, t)];
-            b1[k] = d.bm[idxM(d, f * 3 + k, 1, c, t - 1)];
-            if (ZMODE) {
-                l0[k] = d.lamc[idxV(d, vk[k], t)];
-                const double *pl = t > 0 ? d.lamc + idxV(d, vk[k], t - 1) : (has1 ? d.lamc_lo + vk[k] : d.lamc + idxV(d, vk[k], t));
-                l1[k] = *pl;
-            } else {
-                z0[k] = d.zm[idxM(d, f * 3 + k, 0, c, t)];
-                z1[k] = d.zm[idxM(d, f * 3 + k, 1, c, t - 1)];
-            }
-        }
-        double gx = 0.0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) gx += hk[k] * phik[k];
-        double S = 0.0;
-        const double sBold = sB * Bold;   // both pre-images of this thread's corners use B_old at ITS node
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            if (ZMODE) {
-                z0[k] = (l0[k] / Dk[k]) * (Dk[k] * (sBold - b0[k]));
-                z1[k] = (l1[k] / Dk[k]) * (Dk[k] * (sBold - b1[k]));
-            }
-            if (!has0) z0[k] = b0[k] = 0.0;
-            if (!has1) z1[k] = b1[k] = 0.0;
-            if (ZMODE == 1) {
-                if (has0) d.zm[idxM(d, f * 3 + k, 0, c, t)] = z0[k];
-                if (has1) d.zm[idxM(d, f * 3 + k, 1, c, t - 1)] = z1[k];
-            }
-            S += (z0[k] + b0[k]) + (z1[k] + b1[k]);
-        }
-        const double Eo = d.E[ie];
-        const double Bn = (gx + Eo + sB * S) / ((first_node(d, t) || last_node(d, t)) ? diag_bd : diag_in);
-        d.B[ie] = Bn;
-        if (QONLY) continue;
-        d.E[ie] = Eo + tau * (gx - Bn);
-        const double sBn = sB * Bn;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            if (has0) d.bm[idxM(d, f * 3 + k, 0, c, t)] = b0[k] + tau * (z0[k] - sBn);
-            if (has1) d.bm[idxM(d, f * 3 + k, 1, c, t - 1)] = b1[k] + tau * (z1[k] - sBn);
-        }
-    }
-}
-
-// The same kernel with TWO consecutive nodes (t, t + 1; t even) per lane: every array of the triangle part is read and written in
-// the column of the node (idxM), so both nodes of a lane sit in one aligned 16-byte word of every row; the mesh constants of
-// (f, c) are loaded once for both.  Half the waves for the same bytes: these launches are latency-bound at full occupancy on
-// the small meshes (time ~ waves x chain / resident waves).  Element for element the arithmetic of k_q_lambda_mult_triangle.
-// (118 VGPRs = 4 waves per SIMD.  Forcing 5 / 6 with amdgpu_waves_per_eu spills 44 / 132 bytes per lane and loses: torus100k 571 -> 553 / 472 it/s,
-// knot 10 530 -> 9 750 / 7 980: profiles/studies/r03_steps23_forced_occupancy.txt)
-// The lane of k_q_lambda_mult_triangle2 (below) as a function, statement for statement the same arithmetic; that kernel keeps its
-// own copy: the register allocation of its ZMODE = 2 instantiation (118 VGPRs = 4 waves per SIMD) did not survive the call.
+// The triangle part for the N consecutive nodes (t .. t + N - 1) of row (f, c) that one lane owns.
+// ZMODE 0: z_mid is read from memory; 1: rebuilt from the cone multiplier (zmid_of) and stored; 2: rebuilt, not stored.
+// N = 1 (k_q_lambda_mult_triangle: time slabs, pitch 2, PALM stage 0): 8-byte accesses; entries whose interval does not exist are not stored.
+// N = 2 (t even; k_q_lambda_mult_triangle2, k_q_lambda_mult_carry): every array of the triangle part is read and written in the column of
+// the node (idxM), so both nodes of a lane sit in one aligned 16-byte word of every row; the mesh constants of (f, c) are loaded once for both.
+// Half the waves for the same bytes: these launches are latency-bound at full occupancy on the small meshes (time ~ waves x chain / resident waves).
+// (k_q_lambda_mult_triangle2: 120-122 VGPRs = 4 waves per SIMD.  Forcing 5 / 6 with amdgpu_waves_per_eu spills 44 / 132 bytes per lane and loses:
+// torus100k 571 -> 553 / 472 it/s, knot 10 530 -> 9 750 / 7 980: profiles/studies/r03_steps23_forced_occupancy.txt)
+// All loads come first and unconditional: the compiler then issues them back to back instead of one wait per guarded load.  Both corner entries of a
+// node sit in ITS column, whether their interval exists or not (then the slot holds a zero that is masked below); the multiplier of interval t - 1
+// comes from the previous time slab's halo when t is the slab's first node.
 // CARRY (k_q_lambda_mult_carry): the lane also forms, from the registers that hold the NEW B, E and beta_mid, what the next
 // iteration's right-hand side and cone projection would gather from memory -- per corner k of its triangle and node u its
 // xyz component's share of  |D (sB B - beta_mid)|^2  (both halves: s = 0 of interval t + u, s = 1 of interval t + u - 1) and of
-// area * hat . (B - E) -- and leaves them in LDS (xl: this lane's column, stride NBX) for the fold over xyz.
+// area * hat . (B - E) -- and leaves them in LDS (xl: this lane's column, stride NBX) for the fold over xyz; its z_mid stores are non-temporal
+// (z_mid is not read again inside the loop).
 constexpr int CARRY_NB = 192;         // 3 wavefronts: 2 * 192 / TP rows = whole triangles for every pitch <= 128
 constexpr int CARRY_VALUES = 18;      // per lane: 3 corners x (2 halves + 1 divergence share) x 2 nodes
-// KKT: the lane also accumulates the sums of kkt_triangle_body2 that need no gather (ks[KF_N]; sz = scale_factor_z).
+// KKT: the lane also accumulates the triangle sums that need no gather (sf, indexed by F_* - N_VSUMS: the slots KF_SLOT; sz = scale_factor_z).
 // BMNT: beta_mid is loaded and stored with the non-temporal hint (FrontSchedule::bm_nt: where the factor can live in the 256 MB Infinity Cache if the
 // 36 T F values of beta_mid that stream through every iteration do not displace it -- sphere10k: 5 130-5 190 -> 5 490-5 500 it/s; where
 // everything fits (knot) the hint costs 2 %, where nothing does (torus100k) it changes nothing: profiles/studies/r04_nontemporal.txt)
-template <int ZMODE, bool QONLY, bool CARRY, bool KKT = false, bool DIV = false, bool BMNT = false>
-__device__ __forceinline__ void ql2_lane(const Dev &d, int f, int c, int t, double sB, double diag_in, double diag_bd, double tau, double *xl = nullptr,
-                                         double sz = 0.0, double *ks = nullptr, double dv = 1.0) {
-    const bool two = t + 1 < d.nl;                  // the second node exists (always, unless the slab holds an odd number of nodes)
+template <int N, int ZMODE, bool QONLY, bool CARRY, bool KKT = false, bool DIV = false, bool BMNT = false>
+__device__ __forceinline__ void ql_lane(const Dev &d, int f, int c, int t, double sB, double diag_in, double diag_bd, double tau, double *xl = nullptr,
+                                        double sz = 0.0, double *sf = nullptr, double dv = 1.0) {
+    static_assert(N == 2 || !(CARRY || KKT), "the carried shares and the fused sums are laid out for two nodes per lane");
+    const bool whole = N == 2 && t + 1 < d.nl;      // the lane's 16-byte words are stored whole (always, unless the slab holds an odd number of nodes)
     const int64_t ie = idxF(d, f, c, t);
     int vk[3];
     double hk[3], Dk[3];
-    D2 phik[3], l0[3], b0[3], b1[3], z0[3], z1[3];
+    DN<N> phik[3], l0[3], b0[3], b1[3], z0[3], z1[3];
     double lm1[3];                                  // the multiplier of interval t - 1 (that of interval t is l0[.].v[0])
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -906,47 +705,49 @@ __device__ __forceinline__ void ql2_lane(const Dev &d, int f, int c, int t, doub
     }
     const double area = (CARRY || KKT) ? d.area_f[f] : 0.0;
     const bool has1_0 = has_prev_interval(d, t);
-    D2 Bold = {{0.0, 0.0}};
-    if (ZMODE) Bold = ld2(d.B + ie);
+    DN<N> Bold = {};
+    if (ZMODE) Bold = ldn<N>(d.B + ie);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        phik[k] = ld2(d.phi + idxV(d, vk[k], t));
-        b0[k] = BMNT ? ld2_nt(d.bm + idxM(d, f * 3 + k, 0, c, t)) : ld2(d.bm + idxM(d, f * 3 + k, 0, c, t));
-        b1[k] = BMNT ? ld2_nt(d.bm + idxM(d, f * 3 + k, 1, c, t - 1)) : ld2(d.bm + idxM(d, f * 3 + k, 1, c, t - 1));
-        if (DIV) {      // (a pending penalty update: see soc_element)
-            b0[k].v[0] /= dv; b0[k].v[1] /= dv;
-            b1[k].v[0] /= dv; b1[k].v[1] /= dv;
+        phik[k] = ldn<N>(d.phi + idxV(d, vk[k], t));
+        b0[k] = BMNT ? ldn_nt<N>(d.bm + idxM(d, f * 3 + k, 0, c, t)) : ldn<N>(d.bm + idxM(d, f * 3 + k, 0, c, t));
+        b1[k] = BMNT ? ldn_nt<N>(d.bm + idxM(d, f * 3 + k, 1, c, t - 1)) : ldn<N>(d.bm + idxM(d, f * 3 + k, 1, c, t - 1));
+        if (DIV) {      // (a pending penalty update: see soc_lane)
+#pragma unroll
+            for (int u = 0; u < N; ++u) { b0[k].v[u] /= dv; b1[k].v[u] /= dv; }
         }
         if (ZMODE) {
-            l0[k] = ld2(d.lamc + idxV(d, vk[k], t));
+            l0[k] = ldn<N>(d.lamc + idxV(d, vk[k], t));
             const double *pl = t > 0 ? d.lamc + idxV(d, vk[k], t - 1) : (has1_0 ? d.lamc_lo + vk[k] : d.lamc + idxV(d, vk[k], t));
             lm1[k] = *pl;
         } else {
-            z0[k] = ld2(d.zm + idxM(d, f * 3 + k, 0, c, t));
-            z1[k] = ld2(d.zm + idxM(d, f * 3 + k, 1, c, t - 1));
+            z0[k] = ldn<N>(d.zm + idxM(d, f * 3 + k, 0, c, t));
+            z1[k] = ldn<N>(d.zm + idxM(d, f * 3 + k, 1, c, t - 1));
         }
     }
-    D2 Eo = ld2(d.E + ie);
-    if (DIV) { Eo.v[0] /= dv; Eo.v[1] /= dv; }
-    D2 Bn, En, n0[3], n1[3];
+    DN<N> Eo = ldn<N>(d.E + ie);
+    if (DIV) {
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
+        for (int u = 0; u < N; ++u) Eo.v[u] /= dv;
+    }
+    DN<N> Bn, En, n0[3], n1[3];
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
         const int tu = t + u;
         const bool has0 = tu < d.ni, has1 = has_prev_interval(d, tu);
         double gx = 0.0;
 #pragma unroll
         for (int k = 0; k < 3; ++k) gx += hk[k] * phik[k].v[u];
         double S = 0.0;
-        const double sBold = sB * Bold.v[u];
+        const double sBold = sB * Bold.v[u];      // both pre-images of a node's corners use B_old at ITS node
         double zz0[3], zz1[3], bb0[3], bb1[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             bb0[k] = b0[k].v[u];
             bb1[k] = b1[k].v[u];
             if (ZMODE) {
-                const double l1 = u == 0 ? lm1[k] : l0[k].v[0];
-                zz0[k] = (l0[k].v[u] / Dk[k]) * (Dk[k] * (sBold - bb0[k]));
-                zz1[k] = (l1 / Dk[k]) * (Dk[k] * (sBold - bb1[k]));
+                zz0[k] = zmid_of(l0[k].v[u], Dk[k], sBold, bb0[k]);
+                zz1[k] = zmid_of(u == 0 ? lm1[k] : l0[k].v[0], Dk[k], sBold, bb1[k]);
             } else {
                 zz0[k] = z0[k].v[u];
                 zz1[k] = z1[k].v[u];
@@ -963,41 +764,31 @@ __device__ __forceinline__ void ql2_lane(const Dev &d, int f, int c, int t, doub
         const double sBn = sB * bn;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            // slots whose interval does not exist keep what they hold (zeros): the scalar kernel does not store them either
+            // slots whose interval does not exist keep what they hold (zeros)
             n0[k].v[u] = has0 ? bb0[k] + tau * (zz0[k] - sBn) : b0[k].v[u];
             n1[k].v[u] = has1 ? bb1[k] + tau * (zz1[k] - sBn) : b1[k].v[u];
         }
-        if (KKT && tu < d.nl) {      // kkt_triangle_body2, conditions 0, 3 and the z_mid part of 1, on the values just computed
-            ks[0] += gx * gx * area;
-            ks[1] += bn * bn * area;
-            ks[2] += (gx - bn) * (gx - bn) * area;
+        if (KKT && tu < d.nl) {      // conditions 0, 3 and the z_mid part of 1, on the values just computed
             const double en = En.v[u];
-            ks[3] += en * en * area;
+            kkt_f_prim_q(sf, gx, bn, area);
+            sf[F_E2 - N_VSUMS] += wsq(en, area);
             double s0 = 0.0, s1 = 0.0;
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 if (has0) s0 += n0[k].v[u];
                 if (has1) s1 += n1[k].v[u];
             }
-            const double x2 = sB * (s0 + s1);
-            ks[4] += x2 * x2 * area;
-            ks[5] += (en + x2) * (en + x2) * area;
+            kkt_f_dual_beta(sf, sB, en, s0, s1, area);
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
-                if (has0) {
-                    const double q = sz * (zz0[k] - sBn);
-                    ks[6] += q * q * area;
-                }
-                if (has1) {
-                    const double q = sz * (zz1[k] - sBn);
-                    ks[6] += q * q * area;
-                }
+                if (has0) kkt_f_rmid(sf, sz, zz0[k], sBn, area);
+                if (has1) kkt_f_rmid(sf, sz, zz1[k], sBn, area);
             }
         }
-        if (CARRY) {      // the expressions of soc_element2 / rhs_value2 on the values those will find in memory
+        if (CARRY) {      // the expressions of soc_lane / rhs_lane on the values those will find in memory
             const bool node = tu < d.nl;
             const double de = bn - En.v[u];
-            if (KKT) {    // ... and of Dual(alpha)'s gather (kkt_vertex_body2: sum over the corners of area * hat . E)
+            if (KKT) {    // ... and of Dual(alpha)'s gather (kkt_vertex_body: sum over the corners of area * hat . E)
 #pragma unroll
                 for (int k = 0; k < 3; ++k) xl[(CARRY_VALUES + k * 2 + u) * CARRY_NB] = node ? (hk[k] * area) * En.v[u] : 0.0;
             }
@@ -1009,29 +800,26 @@ __device__ __forceinline__ void ql2_lane(const Dev &d, int f, int c, int t, doub
             }
         }
     }
-    if (two) {
+    if (whole) {
         if (ZMODE == 1) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 // (entries of intervals that do not exist are stored as the zeros computed above; their slots are never read as data)
-                st2_nt(d.zm + idxM(d, f * 3 + k, 0, c, t), z0[k]);      // (not read again inside the loop)
-                st2_nt(d.zm + idxM(d, f * 3 + k, 1, c, t - 1), z1[k]);
+                double *p0 = d.zm + idxM(d, f * 3 + k, 0, c, t), *p1 = d.zm + idxM(d, f * 3 + k, 1, c, t - 1);
+                if (CARRY) { stn_nt<N>(p0, z0[k]); stn_nt<N>(p1, z1[k]); }
+                else { stn<N>(p0, z0[k]); stn<N>(p1, z1[k]); }
             }
         }
-        st2(d.B_st + ie, Bn);
+        stn<N>(d.B_st + ie, Bn);
         if (QONLY) return;
-        st2(d.E + ie, En);
+        stn<N>(d.E + ie, En);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            if (BMNT) {
-                st2_nt(d.bm_st + idxM(d, f * 3 + k, 0, c, t), n0[k]);
-                st2_nt(d.bm_st + idxM(d, f * 3 + k, 1, c, t - 1), n1[k]);
-            } else {
-                st2(d.bm_st + idxM(d, f * 3 + k, 0, c, t), n0[k]);
-                st2(d.bm_st + idxM(d, f * 3 + k, 1, c, t - 1), n1[k]);
-            }
+            double *p0 = d.bm_st + idxM(d, f * 3 + k, 0, c, t), *p1 = d.bm_st + idxM(d, f * 3 + k, 1, c, t - 1);
+            if (BMNT) { stn_nt<N>(p0, n0[k]); stn_nt<N>(p1, n1[k]); }
+            else { stn<N>(p0, n0[k]); stn<N>(p1, n1[k]); }
         }
-    } else {      // only the first node of the pair exists: element-wise stores
+    } else {      // one node (N = 1, or only the first node of the pair exists): element-wise stores, none to an entry whose interval does not exist
         const bool has0 = t < d.ni, has1 = has1_0;
         if (ZMODE == 1) {
 #pragma unroll
@@ -1051,9 +839,11 @@ __device__ __forceinline__ void ql2_lane(const Dev &d, int f, int c, int t, doub
     }
 }
 
-template <int ZMODE, bool QONLY = false>
-__global__ __launch_bounds__(BLOCK) void k_q_lambda_mult_triangle2(Dev d, double sz, double tau, int nf8, double cd, double cr) {
-    constexpr int SUB = TILE_ELEMS / (2 * BLOCK);     // two elements per thread: a workgroup takes half of a triangle tile
+// Workgroups [0, nf8 * SUB) do the triangle part, N elements per thread: a workgroup takes a quarter (N = 1) or half (N = 2) of a triangle tile;
+// the vertex part (independent of it: different arrays) rides in the same launch as workgroups [nf8 * SUB, nf8 * SUB + nv8).
+template <int N, int ZMODE, bool QONLY>
+__device__ __forceinline__ void ql_tile_kernel(const Dev &d, double sz, double tau, int nf8, double cd, double cr) {
+    constexpr int SUB = TILE_ELEMS / (N * BLOCK);
     if ((int)blockIdx.x >= nf8 * SUB) {
         const int vt = xcd_tile(blockIdx.x - nf8 * SUB, d.n_vtiles);
         if (vt < d.n_vtiles) q_lambda_vertex_tile<QONLY>(d, vt, sz, cd, cr, tau);
@@ -1061,118 +851,18 @@ __global__ __launch_bounds__(BLOCK) void k_q_lambda_mult_triangle2(Dev d, double
     }
     const int tile = xcd_tile(blockIdx.x % nf8, d.n_ftiles);
     if (tile >= d.n_ftiles) return;
-    const int row0 = tile * d.FT;
-    const double sB = sz * INV_SQRT3;
-    const double diag_in = 1.0 + 2.0 * sz * sz, diag_bd = 1.0 + sz * sz;
-    const int e = ((blockIdx.x / nf8) * BLOCK + threadIdx.x) * 2;          // first of the lane's two elements in the tile
-    const int row = row0 + (e >> d.tp_shift), t = e & (d.TP - 1);
+    const int e = ((blockIdx.x / nf8) * BLOCK + threadIdx.x) * N;          // first of the lane's elements in the tile
+    const int row = tile * d.FT + (e >> d.tp_shift), t = e & (d.TP - 1);
     if (row >= 3 * d.F || t >= d.nl) return;
-    const int f = row / 3, c = row - 3 * f;
-    const bool two = t + 1 < d.nl;                  // the second node exists (always, unless the slab holds an odd number of nodes)
-    const int64_t ie = idxF(d, f, c, t);
-    int vk[3];
-    double hk[3], Dk[3];
-    D2 phik[3], l0[3], b0[3], b1[3], z0[3], z1[3];
-    double lm1[3];                                  // the multiplier of interval t - 1 (that of interval t is l0[.].v[0])
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        vk[k] = d.tri[f * 3 + k];
-        hk[k] = d.hat[(f * 3 + k) * 3 + c];
-        Dk[k] = ZMODE ? d.fk_D[f * 3 + k] : 1.0;
-    }
-    const bool has1_0 = has_prev_interval(d, t);
-    D2 Bold = {{0.0, 0.0}};
-    if (ZMODE) Bold = ld2(d.B + ie);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        phik[k] = ld2(d.phi + idxV(d, vk[k], t));
-        b0[k] = ld2(d.bm + idxM(d, f * 3 + k, 0, c, t));
-        b1[k] = ld2(d.bm + idxM(d, f * 3 + k, 1, c, t - 1));
-        if (ZMODE) {
-            l0[k] = ld2(d.lamc + idxV(d, vk[k], t));
-            const double *pl = t > 0 ? d.lamc + idxV(d, vk[k], t - 1) : (has1_0 ? d.lamc_lo + vk[k] : d.lamc + idxV(d, vk[k], t));
-            lm1[k] = *pl;
-        } else {
-            z0[k] = ld2(d.zm + idxM(d, f * 3 + k, 0, c, t));
-            z1[k] = ld2(d.zm + idxM(d, f * 3 + k, 1, c, t - 1));
-        }
-    }
-    const D2 Eo = ld2(d.E + ie);
-    D2 Bn, En, n0[3], n1[3];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const int tu = t + u;
-        const bool has0 = tu < d.ni, has1 = has_prev_interval(d, tu);
-        double gx = 0.0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) gx += hk[k] * phik[k].v[u];
-        double S = 0.0;
-        const double sBold = sB * Bold.v[u];
-        double zz0[3], zz1[3], bb0[3], bb1[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            bb0[k] = b0[k].v[u];
-            bb1[k] = b1[k].v[u];
-            if (ZMODE) {
-                const double l1 = u == 0 ? lm1[k] : l0[k].v[0];
-                zz0[k] = (l0[k].v[u] / Dk[k]) * (Dk[k] * (sBold - bb0[k]));
-                zz1[k] = (l1 / Dk[k]) * (Dk[k] * (sBold - bb1[k]));
-            } else {
-                zz0[k] = z0[k].v[u];
-                zz1[k] = z1[k].v[u];
-            }
-            if (!has0) zz0[k] = bb0[k] = 0.0;
-            if (!has1) zz1[k] = bb1[k] = 0.0;
-            z0[k].v[u] = zz0[k];
-            z1[k].v[u] = zz1[k];
-            S += (zz0[k] + bb0[k]) + (zz1[k] + bb1[k]);
-        }
-        const double bn = (gx + Eo.v[u] + sB * S) / ((first_node(d, tu) || last_node(d, tu)) ? diag_bd : diag_in);
-        Bn.v[u] = bn;
-        En.v[u] = Eo.v[u] + tau * (gx - bn);
-        const double sBn = sB * bn;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            // slots whose interval does not exist keep what they hold (zeros): the scalar kernel does not store them either
-            n0[k].v[u] = has0 ? bb0[k] + tau * (zz0[k] - sBn) : b0[k].v[u];
-            n1[k].v[u] = has1 ? bb1[k] + tau * (zz1[k] - sBn) : b1[k].v[u];
-        }
-    }
-    if (two) {
-        if (ZMODE == 1) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                // (entries of intervals that do not exist are stored as the zeros computed above; their slots are never read as data)
-                st2(d.zm + idxM(d, f * 3 + k, 0, c, t), z0[k]);
-                st2(d.zm + idxM(d, f * 3 + k, 1, c, t - 1), z1[k]);
-            }
-        }
-        st2(d.B + ie, Bn);
-        if (QONLY) return;
-        st2(d.E + ie, En);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            st2(d.bm + idxM(d, f * 3 + k, 0, c, t), n0[k]);
-            st2(d.bm + idxM(d, f * 3 + k, 1, c, t - 1), n1[k]);
-        }
-    } else {      // only the first node of the pair exists: element-wise stores
-        const bool has0 = t < d.ni, has1 = has1_0;
-        if (ZMODE == 1) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                if (has0) d.zm[idxM(d, f * 3 + k, 0, c, t)] = z0[k].v[0];
-                if (has1) d.zm[idxM(d, f * 3 + k, 1, c, t - 1)] = z1[k].v[0];
-            }
-        }
-        d.B[ie] = Bn.v[0];
-        if (QONLY) return;
-        d.E[ie] = En.v[0];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            if (has0) d.bm[idxM(d, f * 3 + k, 0, c, t)] = n0[k].v[0];
-            if (has1) d.bm[idxM(d, f * 3 + k, 1, c, t - 1)] = n1[k].v[0];
-        }
-    }
+    ql_lane<N, ZMODE, QONLY, false>(d, row / 3, row % 3, t, sz * INV_SQRT3, 1.0 + 2.0 * sz * sz, 1.0 + sz * sz, tau);
+}
+template <int ZMODE, bool QONLY = false>
+__global__ __launch_bounds__(BLOCK) void k_q_lambda_mult_triangle(Dev d, double sz, double tau, int nf8, double cd, double cr) {
+    ql_tile_kernel<1, ZMODE, QONLY>(d, sz, tau, nf8, cd, cr);
+}
+template <int ZMODE, bool QONLY = false>
+__global__ __launch_bounds__(BLOCK) void k_q_lambda_mult_triangle2(Dev d, double sz, double tau, int nf8, double cd, double cr) {
+    ql_tile_kernel<2, ZMODE, QONLY>(d, sz, tau, nf8, cd, cr);
 }
 
 // Steps 2+3 that also CARRY the next iteration's gathers (DOTS_STEP_CARRY; one GPU, pitch <= 128).  A workgroup of 192 lanes takes
@@ -1182,14 +872,20 @@ __global__ __launch_bounds__(BLOCK) void k_q_lambda_mult_triangle2(Dev d, double
 //     cn_sq[j][1][interval]   the s = 1 half (formed at node interval + 1: it comes from the next lane of the row),
 //     cn_g[j][node]           area * hat_k . (B - E),
 // j = cpos[f * 3 + k]: the rows of a vertex's corners are CONTIGUOUS, so the next right-hand-side / projection launch streams
-// them (soc_element2 / rhs_value2 <CARRIED>) instead of walking index lists into B, E and beta_mid.
+// them (soc_lane / rhs_lane <CARRIED>) instead of walking index lists into B, E and beta_mid.
 // Replaces one of the three passes over beta_mid per iteration (solver_socp.py:997-1017 reads what :716-722 just wrote).
 // 148-152 VGPRs = 3 waves per SIMD by themselves; the instantiation with the KKT sums is held there (170 otherwise).
 // (Measured: 4 waves per SIMD capped the registers at 128 and spilled 20: knot 10 900 -> 9 500 it/s, torus100k 630 -> 585)
 #define CARRY_OCCUPANCY __attribute__((amdgpu_waves_per_eu(3)))
-// this workgroup's partial sums (thread 0 holds the totals) into the fused-KKT buffers: slot SLOT[i] of block `bid` of `nblk`
+// the fused slots of a lane's sums (s, indexed by slot - first) added over the workgroup and stored into the fused-KKT buffers: slot SLOT[i] of
+// block `bid` of `nblk`
 template <int N>
-__device__ __forceinline__ void store_fused(const double (&v)[N], const int (&slot)[N], int first, double *__restrict__ part, int nblk, int bid) {
+__device__ __forceinline__ void store_fused(const double *s, const int (&slot)[N], int first, double *__restrict__ part, int nblk, int bid, double *lds) {
+    double v[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = s[slot[i] - first];
+    block_sum<N, CARRY_NB / 64>(v, lds);
+    if (threadIdx.x != 0) return;
 #pragma unroll
     for (int i = 0; i < N; ++i) part[(int64_t)(slot[i] - first) * nblk + bid] = v[i];
 }
@@ -1202,12 +898,9 @@ __global__ __launch_bounds__(CARRY_NB) CARRY_OCCUPANCY void k_q_lambda_mult_carr
     const int tid = threadIdx.x;
     if ((int)blockIdx.x >= n_fwg) {
         const int vb = blockIdx.x - n_fwg, vt = xcd_tile(vb, d.n_vtiles);
-        double ks[KV_N] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        if (vt < d.n_vtiles) q_lambda_vertex_tile<false, CARRY_NB, KKT, DIV>(d, vt, sz, cd, cr, tau, &ka, ks, dv);
-        if (KKT) {
-            block_sum<KV_N, CARRY_NB / 64>(ks, xs);
-            if (tid == 0) store_fused<KV_N>(ks, KV_SLOT, 0, kf.part_v, kf.nv, vb);
-        }
+        double sv[N_VSUMS] = {};
+        if (vt < d.n_vtiles) q_lambda_vertex_tile<false, CARRY_NB, KKT, DIV>(d, vt, sz, cd, cr, tau, &ka, sv, dv);
+        if (KKT) store_fused<KV_N>(sv, KV_SLOT, 0, kf.part_v, kf.nv, vb, xs);
         return;
     }
     const int wg = xcd_tile(blockIdx.x, (d.F + tri_per_wg - 1) / tri_per_wg);
@@ -1215,8 +908,8 @@ __global__ __launch_bounds__(CARRY_NB) CARRY_OCCUPANCY void k_q_lambda_mult_carr
     const int f = wg * tri_per_wg + lr / 3, c = lr - 3 * (lr / 3);
     const bool active = f < d.F && t < d.nl;      // (a whole triangle is active or not; so is a column over its three rows)
     const int j = active ? d.cpos[f * 3 + c] : 0; // row of this lane's corner k = c in the carried arrays (loaded with the lane's other constants)
-    double kt[KF_N] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if (active) ql2_lane<ZMODE, false, true, KKT, DIV, BMNT>(d, f, c, t, sz * INV_SQRT3, 1.0 + 2.0 * sz * sz, 1.0 + sz * sz, tau, xs + tid, sz, kt, dv);
+    double sf[N_FSUMS] = {};
+    if (active) ql_lane<2, ZMODE, false, true, KKT, DIV, BMNT>(d, f, c, t, sz * INV_SQRT3, 1.0 + 2.0 * sz * sz, 1.0 + sz * sz, tau, xs + tid, sz, sf, dv);
     __syncthreads();
     const int L = d.TP >> 1;                      // lanes per row
     const int t0 = tid - c * L;                   // the lane of component 0 of this triangle and column
@@ -1243,13 +936,12 @@ __global__ __launch_bounds__(CARRY_NB) CARRY_OCCUPANCY void k_q_lambda_mult_carr
     }
     if (KKT) {
         __syncthreads();      // (the exchange values in xs have been read)
-        block_sum<KF_N, CARRY_NB / 64>(kt, xs);
-        if (tid == 0) store_fused<KF_N>(kt, KF_SLOT, N_VSUMS, kf.part_f, kf.nf, blockIdx.x);
+        store_fused<KF_N>(sf, KF_SLOT, N_VSUMS, kf.part_f, kf.nf, blockIdx.x, xs);
     }
 }
 
 // z_mid on demand (Carried::zmid): in place on z_mid's storage, which holds the beta_mid the last projection read;
-// Bold: the B it read.  One node per lane; the expression of the steps-2+3 kernels (ZMODE 1), entry for entry.
+// Bold: the B it read.  One node per lane; zmid_of, as the steps-2+3 kernels rebuild it (ZMODE 1).
 __global__ __launch_bounds__(BLOCK) void k_rebuild_zmid(Dev d, const double *__restrict__ Bold, double sz, double dv) {
     const int tile = xcd_tile(blockIdx.x, d.n_ftiles);
     if (tile >= d.n_ftiles) return;
@@ -1267,12 +959,12 @@ __global__ __launch_bounds__(BLOCK) void k_rebuild_zmid(Dev d, const double *__r
             if (has0) {
                 double b = d.zm[idxM(d, f * 3 + k, 0, c, t)];
                 if (dv != 0.0) b /= dv;
-                d.zm[idxM(d, f * 3 + k, 0, c, t)] = (d.lamc[idxV(d, vk, t)] / Dk) * (Dk * (sBold - b));
+                d.zm[idxM(d, f * 3 + k, 0, c, t)] = zmid_of(d.lamc[idxV(d, vk, t)], Dk, sBold, b);
             }
             if (has1) {
                 double b = d.zm[idxM(d, f * 3 + k, 1, c, t - 1)];
                 if (dv != 0.0) b /= dv;
-                d.zm[idxM(d, f * 3 + k, 1, c, t - 1)] = (d.lamc[idxV(d, vk, t - 1)] / Dk) * (Dk * (sBold - b));
+                d.zm[idxM(d, f * 3 + k, 1, c, t - 1)] = zmid_of(d.lamc[idxV(d, vk, t - 1)], Dk, sBold, b);
             }
         }
     }
@@ -1330,11 +1022,8 @@ int launch_q_lambda_mult(Ctx *c, int zmid_mode, double dv) {
                     hipLaunchKernelGGL((k_q_lambda_mult_carry<Z, K, DIV, BMNT>), g, dim3(CARRY_NB), 0, c->stream, dk, p.scale_z, p.tau, n_fwg, tw, cd, cr, ka, kf, DIV ? dv : 1.0, emit);
                 }); }); }); });
         };
-        if (zmid_mode == 2) carry_launch(2, false);
-        else if (defer && k) carry_launch(2, true);
-        else if (defer) carry_launch(2, false);
-        else if (k) carry_launch(1, true);
-        else carry_launch(1, false);
+        assert(!k || zmid_mode == 1);      // (kkt above: the fused sums go with a stored or deferred z_mid only)
+        carry_launch((zmid_mode == 2 || defer) ? 2 : 1, k);      // (k: only with zmid_mode 1)
         DOTS_HIP(hipGetLastError());
         if (defer) {
             std::swap(c->d.B, c->B_alt);          // B_alt: the B the projection read
@@ -1354,17 +1043,13 @@ int launch_q_lambda_mult(Ctx *c, int zmid_mode, double dv) {
     if (c->d.TP >= 4) {      // two nodes per lane (16-byte accesses): k_q_lambda_mult_triangle2
         const dim3 g2(nf8 * (TILE_ELEMS / (2 * BLOCK)) + nv8);
         c->carried.step_path |= STEP_PATH_QL_TRIANGLE2 | (zmid_mode << STEP_PATH_QL_Z_SHIFT);
-        if (zmid_mode == 2) hipLaunchKernelGGL((k_q_lambda_mult_triangle2<2>), g2, dim3(BLOCK), 0, c->stream, c->d, p.scale_z, p.tau, nf8, cd, cr);
-        else if (zmid_mode == 1) hipLaunchKernelGGL((k_q_lambda_mult_triangle2<1>), g2, dim3(BLOCK), 0, c->stream, c->d, p.scale_z, p.tau, nf8, cd, cr);
-        else hipLaunchKernelGGL((k_q_lambda_mult_triangle2<0>), g2, dim3(BLOCK), 0, c->stream, c->d, p.scale_z, p.tau, nf8, cd, cr);
+        with_constant<2, 1, 0>(zmid_mode, [&](auto Z) { hipLaunchKernelGGL((k_q_lambda_mult_triangle2<Z>), g2, dim3(BLOCK), 0, c->stream, c->d, p.scale_z, p.tau, nf8, cd, cr); });
         DOTS_HIP(hipGetLastError());
         return 0;
     }
     const dim3 gf(nf8 * (TILE_ELEMS / BLOCK) + nv8);
     c->carried.step_path |= STEP_PATH_QL_TRIANGLE | (zmid_mode << STEP_PATH_QL_Z_SHIFT);
-    if (zmid_mode == 2) hipLaunchKernelGGL((k_q_lambda_mult_triangle<2>), gf, dim3(BLOCK), 0, c->stream, c->d, p.scale_z, p.tau, nf8, cd, cr);
-    else if (zmid_mode == 1) hipLaunchKernelGGL((k_q_lambda_mult_triangle<1>), gf, dim3(BLOCK), 0, c->stream, c->d, p.scale_z, p.tau, nf8, cd, cr);
-    else hipLaunchKernelGGL((k_q_lambda_mult_triangle<0>), gf, dim3(BLOCK), 0, c->stream, c->d, p.scale_z, p.tau, nf8, cd, cr);
+    with_constant<2, 1, 0>(zmid_mode, [&](auto Z) { hipLaunchKernelGGL((k_q_lambda_mult_triangle<Z>), gf, dim3(BLOCK), 0, c->stream, c->d, p.scale_z, p.tau, nf8, cd, cr); });
     DOTS_HIP(hipGetLastError());
     return 0;
 }

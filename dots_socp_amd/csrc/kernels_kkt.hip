@@ -6,6 +6,7 @@
 // in a fixed order (wave64 __shfl reductions inside the workgroup, no atomics -> deterministic) and
 // the ~20 scalars are combined on the host side of the C ABI exactly as the reference's closures do.
 #include "dots_dev.h"
+#include "kkt_slots.h"
 
 #include <atomic>
 
@@ -16,287 +17,108 @@ namespace dots {
 using S = CgScalOffsets;
 
 
-// One element per thread (a workgroup takes a quarter of a tile, as the cone projection does): the corner walks of
-// Comp(rho, f(q)) and Dual(alpha) are chains of dependent loads, and these kernels run on the iterations whose
-// residuals the host waits for.
-// (bid of nblk workgroups: the kernels below run it alone or beside the triangle part in one launch)
+// N nodes per lane (bid of nblk workgroups: the kernels below run a body alone or beside the other one in one launch).
+// N = 1: one element per thread, a workgroup takes a quarter of a tile, as the cone projection does: the corner walks of
+// Comp(rho, f(q)) and Dual(alpha) are chains of dependent loads, and these kernels run on the iterations whose residuals the
+// host waits for.  The only form on a time slab: what belongs to a neighbouring slab is read from the halos (phi_hi, B_hi, mu_lo).
+// N = 2: the nodes t, t + 1 (t even), one GPU only (no halos): every array is read in the column of its node or interval, so both
+// sit in one aligned 16-byte word of the row; the corner walks load the mesh constants once for both.  Half the waves for the
+// same bytes.  A lane adds its first node's terms, then its second's.
+// node t + N of a lane's row of a node array: the next slab's first node comes from the halo (N = 1); column t + 2 is read when
+// the lane's second interval exists (N = 2)
+template <int N>
+__device__ __forceinline__ double node_after(const Dev &d, const double *x, const double *hi, int64_t row, int t) {
+    if constexpr (N == 1) return next_node(d, x, hi, row, t);
+    else return t + 1 < d.ni ? x[(row << d.tp_shift) + t + 2] : 0.0;
+}
+// the multiplier of interval t - 1 beside a lane's first node (N = 1: from the previous slab's halo at the slab's first node)
+template <int N>
+__device__ __forceinline__ double mu_before(const Dev &d, int v, int t) {
+    if (t > 0) return d.mu[idxV(d, v, t) - 1];
+    if constexpr (N == 1) { if (has_prev_interval(d, t)) return d.mu_lo[v]; }
+    return 0.0;
+}
+
+template <int N>
 __device__ __forceinline__ void kkt_vertex_body(const Dev &d, const KktArgs &a, int bid, int nblk, double *__restrict__ part, double *lds) {
-    constexpr int SUB = TILE_ELEMS / BLOCK;
+    constexpr int SUB = TILE_ELEMS / (N * BLOCK);
     const int G8 = nblk / SUB;
     const int tile = xcd_tile(bid % G8, d.n_vtiles);
     double s[N_VSUMS];
 #pragma unroll
     for (int i = 0; i < N_VSUMS; ++i) s[i] = 0.0;
     const bool c0 = a.mask & 1u, c1 = a.mask & 2u, c2 = a.mask & 4u, c3 = a.mask & 8u, c4 = a.mask & 16u, c6 = a.mask & 64u;
-    if (tile < d.n_vtiles) {
-        const double ih = 1.0 / d.h, rho_s = a.ds * a.r;
-        for (int e = (bid / G8) * BLOCK + threadIdx.x; e < TILE_ELEMS; e += TILE_ELEMS) {
-            const int v = tile * d.VT + (e >> d.tp_shift), t = e & (d.TP - 1);
-            if (v >= d.V || t >= d.nl) continue;
-            const int iv = idxV(d, v, t);
-            const double m = d.mass_v[v];
-            if (t < d.ni) {
-                const double A = d.A[iv], mu = d.mu[iv], lc = d.lam[iv];
-                if (c0) {   // Prim(phi, q): solver_socp.py:433-450, residuals of :592-593
-                    const double dphi = (next_node(d, d.phi, d.phi_hi, v, t) - d.phi[iv]) * ih;
-                    const double rm = dphi - A - lc;
-                    s[V_DPHI2] += dphi * dphi * m;
-                    s[V_A2] += A * A * m;
-                    s[V_RESMU2] += rm * rm * m;
-                }
-                if (c0 || c6) s[V_LAM2] += lc * lc * m;
-                if (c1) {   // Prim(q, z): :452-464 with :598-600
-                    const double rf = d.zf[iv] + a.sz * A - a.cd, re = d.ze[iv] - a.sz * A - a.cd;
-                    s[V_RFST2] += rf * rf * m;
-                    s[V_REND2] += re * re * m;
-                }
-                if (c3 || c4 || c6) s[V_MU2] += mu * mu * m;
-                if (c3) {   // Dual(beta): :484-503
-                    const double a1 = a.sz * (d.be[iv] - d.bf[iv]);
-                    s[V_AUX1_2] += a1 * a1 * m;
-                    s[V_MUAUX1_2] += (mu + a1) * (mu + a1) * m;
-                }
-                if (c4) {   // Comp(rho, f(q)): :505-526 with :615-619
-                    double q = 0.0;
-                    for (int j = d.cptr[v]; j < d.cptr[v + 1]; ++j) {
-                        const int f = d.cidx[j] / 3;
-                        double sq = 0.0;
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) {
-                            const double b0 = a.ps * d.B[idxF(d, f, c, t)], b1 = a.ps * next_node(d, d.B, d.B_hi, f * 3 + c, t);
-                            sq += b0 * b0 + b1 * b1;
-                        }
-                        q += d.c_area[j] * sq * (1.0 / 3.0);
-                    }
-                    const double rho = rho_s * mu;
-                    const double aux = a.ps * A + 0.25 * q / m;
-                    const double res = fmax(0.0, aux + rho) - rho;
-                    s[V_COMP_AUX2] += aux * aux * m;
-                    s[V_COMP_RES2] += res * res * m;
-                }
-                if (c6) {   // Comp(rho, cong.): :549-559 with :633-636
-                    const double res = a.cong * (rho_s * mu) - a.ps * lc;
-                    s[V_CONG_RES2] += res * res * m;
-                }
-            }
-            if (c2) {       // Dual(alpha): :466-482
-                double x = 0.0;
-                if (t < d.ni) x += d.mu[iv] * m;
-                if (t > 0) x -= d.mu[iv - 1] * m;
-                else if (has_prev_interval(d, t)) x -= d.mu_lo[v] * m;
-                x *= ih;
-                double dsx = 0.0;
-                for (int j = d.cptr[v]; j < d.cptr[v + 1]; ++j) {
-                    const int f = d.cidx[j] / 3;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) dsx += d.c_gA[j * 3 + c] * d.E[idxF(d, f, c, t)];
-                }
-                x -= dsx;
-                if (first_node(d, t)) x -= a.bs * d.mu0[v] / (a.r * d.h);
-                if (last_node(d, t)) x += a.bs * d.mu1[v] / (a.r * d.h);
-                const double aux = (a.r * d.h) * x / m;
-                s[V_DUALAUX2] += aux * aux * m;
-            }
-        }
-    }
-    block_sum<N_VSUMS>(s, lds);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int i = 0; i < N_VSUMS; ++i) part[(int64_t)i * nblk + bid] = s[i];
-    }
-}
-
-__device__ __forceinline__ void kkt_triangle_body(const Dev &d, const KktArgs &a, int bid, int nblk, double *__restrict__ part, double *lds) {
-    constexpr int SUB = TILE_ELEMS / BLOCK;
-    const int G8 = nblk / SUB;
-    const int tile = xcd_tile(bid % G8, d.n_ftiles);
-    double s[N_FSUMS];
-#pragma unroll
-    for (int i = 0; i < N_FSUMS; ++i) s[i] = 0.0;
-    const bool c0 = a.mask & 1u, c1 = a.mask & 2u, c3 = a.mask & 8u, c5 = a.mask & 32u;
-    if (tile < d.n_ftiles) {
-        const double sB = a.sz * INV_SQRT3, rho_s = a.ds * a.r;
-        for (int e = (bid / G8) * BLOCK + threadIdx.x; e < TILE_ELEMS; e += TILE_ELEMS) {
-            const int row = tile * d.FT + (e >> d.tp_shift), t = e & (d.TP - 1);
-            if (row >= 3 * d.F || t >= d.nl) continue;
-            const int f = row / 3, c = row - 3 * f;
-            const double w = d.area_f[f];
-            const int64_t ie = idxF(d, f, c, t);
-            const double B = d.B[ie];
-            if (c0) {
-                double gx = 0.0;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) gx += d.hat[(f * 3 + k) * 3 + c] * d.phi[idxV(d, d.tri[f * 3 + k], t)];
-                s[F_DX2 - N_VSUMS] += gx * gx * w;
-                s[F_B2 - N_VSUMS] += B * B * w;
-                s[F_RESE2 - N_VSUMS] += (gx - B) * (gx - B) * w;
-            }
-            if (c3 || c5) {
-                const double E = d.E[ie];
-                s[F_E2 - N_VSUMS] += E * E * w;
-                if (c3) {
-                    double s0 = 0.0, s1 = 0.0;
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        if (t < d.ni) s0 += d.bm[idxM(d, f * 3 + k, 0, c, t)];
-                        if (has_prev_interval(d, t)) s1 += d.bm[idxM(d, f * 3 + k, 1, c, t - 1)];
-                    }
-                    const double a2 = sB * (s0 + s1);
-                    s[F_AUX2_2 - N_VSUMS] += a2 * a2 * w;
-                    s[F_EAUX2_2 - N_VSUMS] += (E + a2) * (E + a2) * w;
-                }
-                if (c5) {   // Comp(m, rho o B): :528-547 with :624-628
-                    double rn = 0.0;
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        const int vk = d.tri[f * 3 + k];
-                        const int iv = idxV(d, vk, t);
-                        double r2 = 0.0;
-                        if (t < d.ni) r2 += d.mu[iv];
-                        if (t > 0) r2 += d.mu[iv - 1];
-                        else if (has_prev_interval(d, t)) r2 += d.mu_lo[vk];
-                        rn += 0.5 * rho_s * r2;
-                    }
-                    const double aux = (rn * (1.0 / 3.0)) * (a.ps * B);
-                    const double mm = rho_s * E;
-                    s[F_AUX5_2 - N_VSUMS] += aux * aux * w;
-                    s[F_AUX5M_2 - N_VSUMS] += (aux - mm) * (aux - mm) * w;
-                }
-            }
-            if (c1) {       // z_mid part of Prim(q, z): sz (z_mid - L B)
-                const double sb = sB * B;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    if (t < d.ni) {
-                        const double q = a.sz * (d.zm[idxM(d, f * 3 + k, 0, c, t)] - sb);
-                        s[F_RMID2 - N_VSUMS] += q * q * w;
-                    }
-                    if (has_prev_interval(d, t)) {
-                        const double q = a.sz * (d.zm[idxM(d, f * 3 + k, 1, c, t - 1)] - sb);
-                        s[F_RMID2 - N_VSUMS] += q * q * w;
-                    }
-                }
-            }
-        }
-    }
-    block_sum<N_FSUMS>(s, lds);
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int i = 0; i < N_FSUMS; ++i) part[(int64_t)i * nblk + bid] = s[i];
-    }
-}
-
-// ---- the same sums with TWO consecutive nodes (t, t + 1; t even) per lane, one GPU only (no halos): every array is read in the
-// column of its node or interval, so both sit in one aligned 16-byte word of the row; the corner walks load the mesh constants
-// once for both.  Half the waves for the same bytes (these launches run on the iterations the host waits for).  Element for
-// element the expressions of the bodies above; a lane adds its first node's terms, then its second's. -----------------------
-__device__ __forceinline__ void kkt_vertex_body2(const Dev &d, const KktArgs &a, int bid, int nblk, double *__restrict__ part, double *lds) {
-    constexpr int SUB = TILE_ELEMS / (2 * BLOCK);
-    const int G8 = nblk / SUB;
-    const int tile = xcd_tile(bid % G8, d.n_vtiles);
-    double s[N_VSUMS];
-#pragma unroll
-    for (int i = 0; i < N_VSUMS; ++i) s[i] = 0.0;
-    const bool c0 = a.mask & 1u, c1 = a.mask & 2u, c2 = a.mask & 4u, c3 = a.mask & 8u, c4 = a.mask & 16u, c6 = a.mask & 64u;
-    const int e = ((bid / G8) * BLOCK + threadIdx.x) * 2;
+    const int e = ((bid / G8) * BLOCK + threadIdx.x) * N;
     const int v = tile * d.VT + (e >> d.tp_shift), t = e & (d.TP - 1);
     if (tile < d.n_vtiles && v < d.V && t < d.nl) {
-        const double ih = 1.0 / d.h, rho_s = a.ds * a.r;
+        const double ih = 1.0 / d.h;
         const int iv = idxV(d, v, t);
         const double m = d.mass_v[v];
-        const bool has[2] = {t < d.ni, t + 1 < d.ni};          // the intervals t, t + 1 exist
-        const bool node1 = t + 1 < d.nl;                        // the second node exists
-        const D2 A = ld2(d.A + iv), mu = ld2(d.mu + iv), lc = ld2(d.lam + iv);
+        bool has[N];                                            // the lane's intervals exist
+#pragma unroll
+        for (int u = 0; u < N; ++u) has[u] = t + u < d.ni;
+        DN<N> A = {}, mu = {}, lc = {};      // (one node per lane: column ni of an interval array is padding and is not read)
+        if (N == 2 || has[0]) { A = ldn<N>(d.A + iv); mu = ldn<N>(d.mu + iv); lc = ldn<N>(d.lam + iv); }
         if (has[0]) {
-            D2 ph = {{0.0, 0.0}}, zf = ph, ze = ph, be = ph, bf = ph;
-            double ph2 = 0.0;
-            if (c0) { ph = ld2(d.phi + iv); if (has[1]) ph2 = d.phi[iv + 2]; }
-            if (c1) { zf = ld2(d.zf + iv); ze = ld2(d.ze + iv); }
-            if (c3) { be = ld2(d.be + iv); bf = ld2(d.bf + iv); }
-            double q[2] = {0.0, 0.0};
-            if (c4) {   // one corner walk for both intervals: B at the nodes t, t + 1, t + 2
+            DN<N> zf = {}, ze = {}, be = {}, bf = {};
+            double ph[N + 1] = {}, q[N] = {};
+            if (c0) {
+                const DN<N> p = ldn<N>(d.phi + iv);
+#pragma unroll
+                for (int u = 0; u < N; ++u) ph[u] = p.v[u];
+                ph[N] = node_after<N>(d, d.phi, d.phi_hi, v, t);
+            }
+            if (c1) { zf = ldn<N>(d.zf + iv); ze = ldn<N>(d.ze + iv); }
+            if (c3) { be = ldn<N>(d.be + iv); bf = ldn<N>(d.bf + iv); }
+            if (c4) {   // one corner walk for the lane's intervals: B at the nodes t .. t + N
                 for (int j = d.cptr[v]; j < d.cptr[v + 1]; ++j) {
                     const int f = d.cidx[j] / 3;
-                    double sq[2] = {0.0, 0.0};
+                    double sq[N] = {};
 #pragma unroll
                     for (int c = 0; c < 3; ++c) {
-                        const int64_t i = idxF(d, f, c, t);
-                        const D2 b = ld2(d.B + i);
-                        const double b0 = a.ps * b.v[0], b1 = a.ps * b.v[1];
-                        sq[0] += b0 * b0 + b1 * b1;
-                        if (has[1]) {
-                            const double b2 = a.ps * d.B[i + 2];
-                            sq[1] += b1 * b1 + b2 * b2;
-                        }
+                        const DN<N> bl = ldn<N>(d.B + idxF(d, f, c, t));
+                        double b[N + 1];
+#pragma unroll
+                        for (int u = 0; u < N; ++u) b[u] = a.ps * bl.v[u];
+                        b[N] = a.ps * node_after<N>(d, d.B, d.B_hi, f * 3 + c, t);
+#pragma unroll
+                        for (int u = 0; u < N; ++u)
+                            if (has[u]) sq[u] += b[u] * b[u] + b[u + 1] * b[u + 1];
                     }
                     const double ca = d.c_area[j];
-                    q[0] += ca * sq[0] * (1.0 / 3.0);
-                    q[1] += ca * sq[1] * (1.0 / 3.0);
+#pragma unroll
+                    for (int u = 0; u < N; ++u) q[u] += ca * sq[u] * (1.0 / 3.0);
                 }
             }
 #pragma unroll
-            for (int u = 0; u < 2; ++u) {
+            for (int u = 0; u < N; ++u) {
                 if (!has[u]) continue;
                 const double Au = A.v[u], muu = mu.v[u], lcu = lc.v[u];
-                if (c0) {
-                    const double dphi = ((u == 0 ? ph.v[1] : ph2) - ph.v[u]) * ih;
-                    const double rm = dphi - Au - lcu;
-                    s[V_DPHI2] += dphi * dphi * m;
-                    s[V_A2] += Au * Au * m;
-                    s[V_RESMU2] += rm * rm * m;
-                }
-                if (c0 || c6) s[V_LAM2] += lcu * lcu * m;
-                if (c1) {
-                    const double rf = zf.v[u] + a.sz * Au - a.cd, re = ze.v[u] - a.sz * Au - a.cd;
-                    s[V_RFST2] += rf * rf * m;
-                    s[V_REND2] += re * re * m;
-                }
-                if (c3 || c4 || c6) s[V_MU2] += muu * muu * m;
-                if (c3) {
-                    const double a1 = a.sz * (be.v[u] - bf.v[u]);
-                    s[V_AUX1_2] += a1 * a1 * m;
-                    s[V_MUAUX1_2] += (muu + a1) * (muu + a1) * m;
-                }
-                if (c4) {
-                    const double rho = rho_s * muu;
-                    const double aux = a.ps * Au + 0.25 * q[u] / m;
-                    const double res = fmax(0.0, aux + rho) - rho;
-                    s[V_COMP_AUX2] += aux * aux * m;
-                    s[V_COMP_RES2] += res * res * m;
-                }
-                if (c6) {
-                    const double res = a.cong * (rho_s * muu) - a.ps * lcu;
-                    s[V_CONG_RES2] += res * res * m;
-                }
+                if (c0) kkt_v_prim_q(s, (ph[u + 1] - ph[u]) * ih, Au, lcu, m);
+                if (c0 || c6) s[V_LAM2] += wsq(lcu, m);
+                if (c1) kkt_v_prim_z(s, a, zf.v[u], ze.v[u], Au, m);
+                if (c3 || c4 || c6) s[V_MU2] += wsq(muu, m);
+                if (c3) kkt_v_dual_beta(s, a, muu, bf.v[u], be.v[u], m);
+                if (c4) kkt_v_comp_rho(s, a, Au, muu, q[u], m);
+                if (c6) kkt_v_cong(s, a, muu, lcu, m);
             }
         }
-        if (c2) {       // Dual(alpha) at the nodes t and t + 1
-            const double mum1 = t > 0 ? d.mu[iv - 1] : 0.0;
-            double dsx[2] = {0.0, 0.0};
+        if (c2) {       // Dual(alpha) at the lane's nodes
+            const double mum1 = mu_before<N>(d, v, t);
+            double dsx[N] = {};
             for (int j = d.cptr[v]; j < d.cptr[v + 1]; ++j) {
                 const int f = d.cidx[j] / 3;
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
                     const double ga = d.c_gA[j * 3 + c];
-                    const D2 E = ld2(d.E + idxF(d, f, c, t));
-                    dsx[0] += ga * E.v[0];
-                    dsx[1] += ga * E.v[1];
+                    const DN<N> E = ldn<N>(d.E + idxF(d, f, c, t));
+#pragma unroll
+                    for (int u = 0; u < N; ++u) dsx[u] += ga * E.v[u];
                 }
             }
 #pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                if (u == 1 && !node1) continue;
-                const int tu = t + u;
-                double x = 0.0;
-                if (tu < d.ni) x += mu.v[u] * m;
-                if (tu > 0) x -= (u == 0 ? mum1 : mu.v[0]) * m;
-                x *= ih;
-                x -= dsx[u];
-                if (tu == 0) x -= a.bs * d.mu0[v] / (a.r * d.h);
-                if (tu == d.T) x += a.bs * d.mu1[v] / (a.r * d.h);
-                const double aux = (a.r * d.h) * x / m;
-                s[V_DUALAUX2] += aux * aux * m;
-            }
+            for (int u = 0; u < N; ++u)
+                if (t + u < d.nl) s[V_DUALAUX2] += kkt_v_dual_alpha(d, a, v, t + u, mu.v[u], u == 0 ? mum1 : mu.v[0], dsx[u], m);
         }
     }
     block_sum<N_VSUMS>(s, lds);
@@ -306,57 +128,52 @@ __device__ __forceinline__ void kkt_vertex_body2(const Dev &d, const KktArgs &a,
     }
 }
 
-__device__ __forceinline__ void kkt_triangle_body2(const Dev &d, const KktArgs &a, int bid, int nblk, double *__restrict__ part, double *lds) {
-    constexpr int SUB = TILE_ELEMS / (2 * BLOCK);
+template <int N>
+__device__ __forceinline__ void kkt_triangle_body(const Dev &d, const KktArgs &a, int bid, int nblk, double *__restrict__ part, double *lds) {
+    constexpr int SUB = TILE_ELEMS / (N * BLOCK);
     const int G8 = nblk / SUB;
     const int tile = xcd_tile(bid % G8, d.n_ftiles);
     double s[N_FSUMS];
 #pragma unroll
     for (int i = 0; i < N_FSUMS; ++i) s[i] = 0.0;
     const bool c0 = a.mask & 1u, c1 = a.mask & 2u, c3 = a.mask & 8u, c5 = a.mask & 32u;
-    const int e = ((bid / G8) * BLOCK + threadIdx.x) * 2;
+    const int e = ((bid / G8) * BLOCK + threadIdx.x) * N;
     const int row = tile * d.FT + (e >> d.tp_shift), t = e & (d.TP - 1);
     if (tile < d.n_ftiles && row < 3 * d.F && t < d.nl) {
         const double sB = a.sz * INV_SQRT3, rho_s = a.ds * a.r;
         const int f = row / 3, c = row - 3 * f;
         const double w = d.area_f[f];
         const int64_t ie = idxF(d, f, c, t);
-        const int nu = t + 1 < d.nl ? 2 : 1;                    // nodes of this lane
-        const D2 B = ld2(d.B + ie);
+        const DN<N> B = ldn<N>(d.B + ie);
         int vk[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) vk[k] = d.tri[f * 3 + k];
-        D2 E = {{0.0, 0.0}}, phik[3], b0[3], b1[3], z0[3], z1[3], muk[3];
+        // both corner entries of a node sit in ITS column (idxM), whether their interval exists or not
+        DN<N> E = {}, phik[3], b0[3], b1[3], z0[3], z1[3], muk[3];
         double mum1[3] = {0.0, 0.0, 0.0}, hk[3] = {0.0, 0.0, 0.0};
-        if (c3 || c5) E = ld2(d.E + ie);
+        if (c3 || c5) E = ldn<N>(d.E + ie);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            if (c0) { hk[k] = d.hat[(f * 3 + k) * 3 + c]; phik[k] = ld2(d.phi + idxV(d, vk[k], t)); }
-            if (c3) { b0[k] = ld2(d.bm + idxM(d, f * 3 + k, 0, c, t)); b1[k] = ld2(d.bm + idxM(d, f * 3 + k, 1, c, t - 1)); }
-            if (c1) { z0[k] = ld2(d.zm + idxM(d, f * 3 + k, 0, c, t)); z1[k] = ld2(d.zm + idxM(d, f * 3 + k, 1, c, t - 1)); }
-            if (c5) {
-                const int iv = idxV(d, vk[k], t);
-                muk[k] = ld2(d.mu + iv);
-                if (t > 0) mum1[k] = d.mu[iv - 1];
-            }
+            if (c0) { hk[k] = d.hat[(f * 3 + k) * 3 + c]; phik[k] = ldn<N>(d.phi + idxV(d, vk[k], t)); }
+            if (c3) { b0[k] = ldn<N>(d.bm + idxM(d, f * 3 + k, 0, c, t)); b1[k] = ldn<N>(d.bm + idxM(d, f * 3 + k, 1, c, t - 1)); }
+            if (c1) { z0[k] = ldn<N>(d.zm + idxM(d, f * 3 + k, 0, c, t)); z1[k] = ldn<N>(d.zm + idxM(d, f * 3 + k, 1, c, t - 1)); }
+            if (c5) { muk[k] = ldn<N>(d.mu + idxV(d, vk[k], t)); mum1[k] = mu_before<N>(d, vk[k], t); }
         }
 #pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            if (u >= nu) continue;
+        for (int u = 0; u < N; ++u) {
             const int tu = t + u;
-            const bool has0 = tu < d.ni, has1 = tu > 0;          // the intervals tu and tu - 1 exist
+            if (tu >= d.nl) continue;
+            const bool has0 = tu < d.ni, has1 = has_prev_interval(d, tu);      // the intervals tu and tu - 1 exist
             const double Bu = B.v[u];
             if (c0) {
                 double gx = 0.0;
 #pragma unroll
                 for (int k = 0; k < 3; ++k) gx += hk[k] * phik[k].v[u];
-                s[F_DX2 - N_VSUMS] += gx * gx * w;
-                s[F_B2 - N_VSUMS] += Bu * Bu * w;
-                s[F_RESE2 - N_VSUMS] += (gx - Bu) * (gx - Bu) * w;
+                kkt_f_prim_q(s, gx, Bu, w);
             }
             if (c3 || c5) {
                 const double Eu = E.v[u];
-                s[F_E2 - N_VSUMS] += Eu * Eu * w;
+                s[F_E2 - N_VSUMS] += wsq(Eu, w);
                 if (c3) {
                     double s0 = 0.0, s1 = 0.0;
 #pragma unroll
@@ -364,9 +181,7 @@ __device__ __forceinline__ void kkt_triangle_body2(const Dev &d, const KktArgs &
                         if (has0) s0 += b0[k].v[u];
                         if (has1) s1 += b1[k].v[u];
                     }
-                    const double a2 = sB * (s0 + s1);
-                    s[F_AUX2_2 - N_VSUMS] += a2 * a2 * w;
-                    s[F_EAUX2_2 - N_VSUMS] += (Eu + a2) * (Eu + a2) * w;
+                    kkt_f_dual_beta(s, sB, Eu, s0, s1, w);
                 }
                 if (c5) {
                     double rn = 0.0;
@@ -377,24 +192,15 @@ __device__ __forceinline__ void kkt_triangle_body2(const Dev &d, const KktArgs &
                         if (has1) r2 += (u == 0 ? mum1[k] : muk[k].v[0]);
                         rn += 0.5 * rho_s * r2;
                     }
-                    const double aux = (rn * (1.0 / 3.0)) * (a.ps * Bu);
-                    const double mm = rho_s * Eu;
-                    s[F_AUX5_2 - N_VSUMS] += aux * aux * w;
-                    s[F_AUX5M_2 - N_VSUMS] += (aux - mm) * (aux - mm) * w;
+                    kkt_f_comp_m(s, a, rn, Bu, Eu, w);
                 }
             }
             if (c1) {
                 const double sb = sB * Bu;
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
-                    if (has0) {
-                        const double q = a.sz * (z0[k].v[u] - sb);
-                        s[F_RMID2 - N_VSUMS] += q * q * w;
-                    }
-                    if (has1) {
-                        const double q = a.sz * (z1[k].v[u] - sb);
-                        s[F_RMID2 - N_VSUMS] += q * q * w;
-                    }
+                    if (has0) kkt_f_rmid(s, a.sz, z0[k].v[u], sb, w);
+                    if (has1) kkt_f_rmid(s, a.sz, z1[k].v[u], sb, w);
                 }
             }
         }
@@ -406,9 +212,9 @@ __device__ __forceinline__ void kkt_triangle_body2(const Dev &d, const KktArgs &
     }
 }
 
-// Dual(alpha) (solver_socp.py:466-482) from the per-corner sums sum_xyz area * hat * E that the last steps-2+3 launch left in cn_e
-// (corner-list order: a vertex's rows are contiguous): two nodes per lane, no walk over E.  The expression of kkt_vertex_body2;
-// the corner sums are added in list order (a corner's xyz share first: the residual agrees with that body to rounding).
+// Dual(alpha) from the per-corner sums sum_xyz area * hat * E that the last steps-2+3 launch left in cn_e (corner-list order: a
+// vertex's rows are contiguous): two nodes per lane, no walk over E.  The corner sums are added in list order (a corner's xyz
+// share first: the residual agrees with kkt_vertex_body<2> to rounding).
 __global__ __launch_bounds__(BLOCK) void k_kkt_dual_alpha_carried(Dev d, KktArgs a, int nblk, double *__restrict__ part) {
     __shared__ double lds[4];
     constexpr int SUB = TILE_ELEMS / (2 * BLOCK);
@@ -418,10 +224,9 @@ __global__ __launch_bounds__(BLOCK) void k_kkt_dual_alpha_carried(Dev d, KktArgs
     const int e = ((bid / G8) * BLOCK + threadIdx.x) * 2;
     const int v = tile * d.VT + (e >> d.tp_shift), t = e & (d.TP - 1);
     if (tile < d.n_vtiles && v < d.V && t < d.nl) {
-        const double ih = 1.0 / d.h, m = d.mass_v[v];
-        const int iv = idxV(d, v, t);
-        const D2 mu = ld2(d.mu + iv);
-        const double mum1 = t > 0 ? d.mu[iv - 1] : 0.0;
+        const double m = d.mass_v[v];
+        const D2 mu = ld2(d.mu + idxV(d, v, t));
+        const double mum1 = mu_before<2>(d, v, t);
         double dsx[2] = {0.0, 0.0};
         const int j0 = d.cptr[v], j1 = d.cptr[v + 1];
         const double *__restrict__ g = d.cn_e + t;
@@ -435,19 +240,8 @@ __global__ __launch_bounds__(BLOCK) void k_kkt_dual_alpha_carried(Dev d, KktArgs
             }
         }
 #pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int tu = t + u;
-            if (tu >= d.nl) continue;
-            double x = 0.0;
-            if (tu < d.ni) x += mu.v[u] * m;
-            if (tu > 0) x -= (u == 0 ? mum1 : mu.v[0]) * m;
-            x *= ih;
-            x -= dsx[u];
-            if (tu == 0) x -= a.bs * d.mu0[v] / (a.r * d.h);
-            if (tu == d.T) x += a.bs * d.mu1[v] / (a.r * d.h);
-            const double aux = (a.r * d.h) * x / m;
-            s[0] += aux * aux * m;
-        }
+        for (int u = 0; u < 2; ++u)
+            if (t + u < d.nl) s[0] += kkt_v_dual_alpha(d, a, v, t + u, mu.v[u], u == 0 ? mum1 : mu.v[0], dsx[u], m);
     }
     block_sum<1>(s, lds);
     if (threadIdx.x == 0) part[bid] = s[0];
@@ -458,13 +252,8 @@ __global__ __launch_bounds__(BLOCK) void k_kkt_dual_alpha_carried(Dev d, KktArgs
 template <bool TWO>
 __global__ __launch_bounds__(BLOCK) void k_kkt_sums(Dev d, KktArgs a, int nv, double *__restrict__ part_v, double *__restrict__ part_f) {
     __shared__ double lds[(N_VSUMS > N_FSUMS ? N_VSUMS : N_FSUMS) * 4];
-    if (TWO) {
-        if ((int)blockIdx.x < nv) kkt_vertex_body2(d, a, blockIdx.x, nv, part_v, lds);
-        else kkt_triangle_body2(d, a, blockIdx.x - nv, gridDim.x - nv, part_f, lds);
-    } else {
-        if ((int)blockIdx.x < nv) kkt_vertex_body(d, a, blockIdx.x, nv, part_v, lds);
-        else kkt_triangle_body(d, a, blockIdx.x - nv, gridDim.x - nv, part_f, lds);
-    }
+    if ((int)blockIdx.x < nv) kkt_vertex_body<TWO ? 2 : 1>(d, a, blockIdx.x, nv, part_v, lds);
+    else kkt_triangle_body<TWO ? 2 : 1>(d, a, blockIdx.x - nv, gridDim.x - nv, part_f, lds);
 }
 
 // one workgroup per slot: scal[SUMS + first + slot] = sum_blk part[slot][blk]
@@ -595,8 +384,7 @@ int kkt_sums_device(Ctx *c, uint32_t mask, double *out) {
         DOTS_HIP(hipMemsetAsync(out, 0, sizeof(double) * N_SUMS, c->stream));
         return 0;
     }
-    if (two) hipLaunchKernelGGL(k_kkt_sums<true>, dim3(nv + nf), dim3(BLOCK), 0, c->stream, d, a, nv, d.partials, part_f);
-    else hipLaunchKernelGGL(k_kkt_sums<false>, dim3(nv + nf), dim3(BLOCK), 0, c->stream, d, a, nv, d.partials, part_f);
+    with_constant<true, false>(two, [&](auto TWO) { hipLaunchKernelGGL(k_kkt_sums<TWO>, dim3(nv + nf), dim3(BLOCK), 0, c->stream, d, a, nv, d.partials, part_f); });
     // (a part that did not run sums zero blocks: its slots are zero)
     hipLaunchKernelGGL(k_reduce_mail, dim3(N_SUMS), dim3(BLOCK), 0, c->stream, reduce_src(d.partials, nv, part_f, nf), out, (double *)nullptr, 0.0, (int *)nullptr);
     DOTS_HIP(hipGetLastError());
@@ -608,7 +396,7 @@ int kkt_sums(Ctx *c, uint32_t mask, double *sums) {
     const Dev &d = c->d;
     const dots_params &p = c->prm;
     KktArgs a{mask, p.r, p.scale_z, p.const_d, p.congestion, p.prim_scale, p.dual_scale, p.boundary_scale};
-    const bool two = c->kkt_two && !d.slab && d.TP >= 4;      // two nodes per lane (kkt_*_body2)
+    const bool two = c->kkt_two && !d.slab && d.TP >= 4;      // two nodes per lane (kkt_*_body<2>)
     const int per_tile = two ? TILE_ELEMS / (2 * BLOCK) : TILE_ELEMS / BLOCK;
     const int gv = xcd_grid(d.n_vtiles) * per_tile, gf = xcd_grid(d.n_ftiles) * per_tile;
     double *part_f = d.partials + (int64_t)N_VSUMS * gv;
@@ -640,13 +428,9 @@ int kkt_sums(Ctx *c, uint32_t mask, double *sums) {
             if (f_slot) { src.p[i] = kf.part_f + (int64_t)(i - N_VSUMS) * kf.nf; src.n[i] = kf.nf; have[i] = true; }
         }
         if (nv && two && d.cn_e) hipLaunchKernelGGL(k_kkt_dual_alpha_carried, dim3(nv), dim3(BLOCK), 0, c->stream, d, a, nv, d.partials + (int64_t)V_DUALAUX2 * nv);
-        else if (nv) {
-            if (two) hipLaunchKernelGGL(k_kkt_sums<true>, dim3(nv), dim3(BLOCK), 0, c->stream, d, a, nv, d.partials, part_f);
-            else hipLaunchKernelGGL(k_kkt_sums<false>, dim3(nv), dim3(BLOCK), 0, c->stream, d, a, nv, d.partials, part_f);
-        }
+        else if (nv) with_constant<true, false>(two, [&](auto TWO) { hipLaunchKernelGGL(k_kkt_sums<TWO>, dim3(nv), dim3(BLOCK), 0, c->stream, d, a, nv, d.partials, part_f); });
     } else {
-        if (two) hipLaunchKernelGGL(k_kkt_sums<true>, dim3(nv + nf), dim3(BLOCK), 0, c->stream, d, a, nv, d.partials, part_f);
-        else hipLaunchKernelGGL(k_kkt_sums<false>, dim3(nv + nf), dim3(BLOCK), 0, c->stream, d, a, nv, d.partials, part_f);
+        with_constant<true, false>(two, [&](auto TWO) { hipLaunchKernelGGL(k_kkt_sums<TWO>, dim3(nv + nf), dim3(BLOCK), 0, c->stream, d, a, nv, d.partials, part_f); });
     }
     int rc;
     if (c->h_mail && c->kkt_counter) {

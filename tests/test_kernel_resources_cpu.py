@@ -135,6 +135,23 @@ def test_sweep_instantiations_match_the_right_hand_side_caps(kernels):
     assert ("k_front_fwd_rows", True) not in nr_by
 
 
+def test_elementwise_kernels_are_the_lane_bodies_instantiations(kernels):
+    """The element-wise half of the iteration is one lane body per step (csrc/kernels_alm.hip: ql_lane, soc_lane, rhs_lane; csrc/kernels_kkt.hip:
+    kkt_vertex_body, kkt_triangle_body), instantiated for one and two nodes per lane by these kernels and no others.  A family that splits
+    again, or an instantiation a launcher no longer reaches (or reaches anew), changes this set."""
+    want = ["k_rhs_modes"]
+    want += [f"k_q_lambda_mult_triangle<{z},0>" for z in (0, 1, 2)] + ["k_q_lambda_mult_triangle<0,1>"]                    # <ZMODE, QONLY>
+    want += [f"k_q_lambda_mult_triangle2<{z},0>" for z in (0, 1, 2)]
+    want += [f"k_q_lambda_mult_carry<{z},{k},{div},{nt}>" for z in (1, 2) for k in (0, 1) for div in (0, 1) for nt in (0, 1)]  # <ZMODE, KKT, DIV, BMNT>
+    want += [f"{base}<{v}>" for base in ("k_rhs", "k_slab_pack_iteration", "k_kkt_sums") for v in (0, 1)]                     # <CARRIED>, <CARRIED>, <TWO>
+    want += [f"{base}<{c},{div}>" for base in ("k_rhs_modes2", "k_rhs_modes_mfma") for c, div in ((0, 0), (1, 0), (0, 1))]    # <CARRIED, DIV>
+    want += [f"k_rhs_modes2_deep<{tp}>" for tp in (8, 16, 32)]
+    want += ["k_soc_projection<0,0>", "k_soc_projection<1,0>", "k_soc_projection<1,1>"]                                     # <ONLY_MULTIPLIER, CARRIED>
+    families = {w.split("<")[0] for w in want}
+    got = sorted(r["short"] for r in kernels if r["short"].split("<")[0] in families)
+    assert got == sorted(want)
+
+
 def test_flow_kernels_are_one_tracer_family(kernels):
     """Every trace is a span: the tracer with and without the sliding mode, each bare and with the deposits of 0 .. 4 attributes, and
     the conversion of the sums.  A family that comes back or an instantiation that drops out changes this set."""
