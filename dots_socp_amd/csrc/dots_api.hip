@@ -1298,7 +1298,7 @@ int dots_laplacian_solve_many(dots_ctx *const *cs, int n, const double *const *h
         for (int k = 0; k < n; ++k) {
             Ctx *c = cs[k];
             if ((r = batch_wait(c, cs[0]))) return r;
-            modes_inverse(c, c->dcg.cg_x, dout[k], true);
+            if ((r = modes_inverse(c, c->dcg.cg_x, dout[k], true))) return r;
             if ((r = launch_from_device_layout(c, DOTS_PHI, dout[k], c->stage))) return r;
             DOTS_HIP(hipMemcpyAsync(host_out[k], c->stage, sizeof(double) * (size_t)nh, hipMemcpyDeviceToHost, c->stream));
         }
@@ -1344,7 +1344,7 @@ int dots_step_many(dots_ctx *const *cs, int n, dots_step_stats *stats) {
     for (int k = 0; k < n; ++k) {
         Ctx *c = cv[k];
         if ((rc = batch_wait(c, c0))) return rc;
-        if (!plan[(size_t)k].fuse) modes_inverse(c, c->dcg.cg_x, c->d.phi, true);
+        if (!plan[(size_t)k].fuse && (rc = modes_inverse(c, c->dcg.cg_x, c->d.phi, true))) return rc;
         if ((rc = iteration_after(c, plan[(size_t)k], nullptr))) return rc;
     }
     DOTS_HIP(hipGetLastError());

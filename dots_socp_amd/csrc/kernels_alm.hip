@@ -1,7 +1,7 @@
 // ALM element-wise / gather kernels for gfx950: second-order-cone projection, right-hand side
 // of the phi step, the fused (q, lambda_c) + multiplier update, scaling tools, layout conversion.
 // All HBM-bound fp64; one thread per (row, time) element, rows = vertices or (triangle, xyz).
-#include "dots_dev.h"
+#include "modes_dev.h"
 #include "kkt_slots.h"
 
 #include <algorithm>
@@ -191,17 +191,9 @@ template <bool ONLY_MULTIPLIER, bool CARRIED = false>
 __global__ __launch_bounds__(BLOCK) void k_soc_projection(Dev d, double sz, double cd, int n_soc, int IC) {
     // Workgroups [n_soc, gridDim.x): the modes -> time transform of phi (independent of the projection, same launch)
     if ((int)blockIdx.x >= n_soc) {
-        extern __shared__ double tm_lds[];
-        const int n = d.T + 1, TP = d.TP, TPp = TP + 1;
-        double *Qs = tm_lds, *xs = tm_lds + IC * TP;
         const int tile = xcd_tile(blockIdx.x - n_soc, d.n_vtiles);
         if (tile >= d.n_vtiles) return;
-        const int v0 = tile * d.VT;
-        for (int e = threadIdx.x; e < TILE_ELEMS; e += BLOCK) {
-            const int vl = e >> d.tp_shift, t = e & (TP - 1);
-            xs[vl * TPp + t] = (v0 + vl < d.V && t < n) ? d.cg_x[idxV(d, v0 + vl, t)] : 0.0;
-        }
-        modes_from_tile<false>(d, d.Q, xs, Qs, IC, v0, d.phi);
+        modes_of_tile<false>(d, IC, tile * d.VT, NodeRows{d.cg_x, d.tp_shift}, d.phi);
         return;
     }
     // one element per thread: a workgroup takes a quarter of a tile (the corner walk is a chain of dependent

@@ -17,7 +17,9 @@
 //              per-column scalars; converged columns are frozen and skipped.  Preconditioner: Jacobi,
 //              or the multigrid V-cycle of kernels_mg.hip when a hierarchy has been uploaded.  The kernels hold 256 columns;
 //              above, a context that opted in (dots_pcg_windows) runs them window by window of 256 modes through
-//              pitch-256 views (pcg_window_view), between the windowed time transforms (k_time_modes_windows).
+//              pitch-256 views (pcg_window_view), between the windowed time transforms.
+//              The transforms into and out of mode space are kernels_modes.hip's (modes_forward, modes_inverse): this file asks for
+//              them and for the number of partial sums the forward one left (modes_forward_sums), and launches none itself.
 //
 // One Jacobi-PCG iteration is TWO kernels and no host round trip:
 //   k_cg_apply   beta from the r.z partial sums of the previous kernel; p = z + beta p_old formed on the
@@ -402,260 +404,6 @@ __global__ __launch_bounds__(BLOCK) void k_cg_bmean(Dev d, int nblk, int nc, dou
     for (int c = 1 + threadIdx.x; c < nc; c += BLOCK) d.scal[S::BMEAN + c] = 0.0;
 }
 
-// Time-mode transform of node arrays: FWD  y[v][a] = sum_t Q[t][a] x[v][t]   (time -> modes)
-//                                     INV  y[v][t] = sum_a Q[t][a] x[v][a]   (modes -> time)
-// The forward transform also emits the partial sums of column 0 (mean removal of the singular mode).
-template <bool FWD>
-__global__ __launch_bounds__(BLOCK) void k_time_modes(Dev d, const double *__restrict__ x, double *__restrict__ y, int emit_col0) {
-    __shared__ double lds[4];
-    const int tile = xcd_tile(blockIdx.x, d.n_vtiles);
-    const int n = d.T + 1;
-    double part[1] = {0.0};
-    if (tile < d.n_vtiles) {
-        for (int e = threadIdx.x; e < TILE_ELEMS; e += BLOCK) {
-            const int v = tile * d.VT + (e >> d.tp_shift), j = e & (d.TP - 1);
-            if (v >= d.V || j >= n) continue;
-            const double *row = x + idxV(d, v, 0);
-            double s = 0.0;
-            if (FWD) {
-                for (int i = 0; i < n; ++i) s += d.Q[i * n + j] * row[i];
-            } else {
-                for (int i = 0; i < n; ++i) s += d.Q[j * n + i] * row[i];
-            }
-            y[idxV(d, v, j)] = s;
-            if (FWD && j == 0) part[0] += s;
-        }
-    }
-    if (FWD && emit_col0) {
-        block_sum<1>(part, lds);
-        if (threadIdx.x == 0) d.partials[blockIdx.x] = part[0];
-    }
-}
-
-// The same transform with the tile of x and Q (in chunks) staged in LDS: every x row and every Q entry is read
-// from memory once per workgroup instead of once per output; a thread computes four outputs that share their Q
-// column.  x rows are padded by one double so that the rows a wavefront broadcasts sit in different banks.
-// NB = 1024 (one output per thread) where the launch is latency-bound: the inverse transform after the direct solve.
-template <bool FWD, int NB = BLOCK>
-__global__ __launch_bounds__(NB) void k_time_modes_tile(Dev d, const double *__restrict__ x, double *__restrict__ y, int IC) {
-    extern __shared__ double tm_lds[];
-    const int n = d.T + 1, TP = d.TP, TPp = TP + 1;
-    double *Qs = tm_lds;                 // [IC][TP]
-    double *xs = tm_lds + IC * TP;       // [VT][TPp]
-    const int tile = xcd_tile(blockIdx.x, d.n_vtiles);
-    if (tile >= d.n_vtiles) return;
-    const int v0 = tile * d.VT;
-    stage_q_chunk<FWD, NB>(d, d.Q, Qs, 0, min(IC, n));      // one barrier for Q and the tile (as compiled, two round trips: Q is waited for and written before the tile's loads are issued)
-    for (int e = threadIdx.x; e < TILE_ELEMS; e += NB) {
-        const int vl = e >> d.tp_shift, t = e & (TP - 1);
-        xs[vl * TPp + t] = (v0 + vl < d.V && t < n) ? x[idxV(d, v0 + vl, t)] : 0.0;
-    }
-    modes_from_tile<FWD, NB>(d, d.Q, xs, Qs, IC, v0, y, -1, 0, 1 << 30, true);
-}
-
-// The same launch for a pitch of TPC = 8, 16 or 32 (modes_from_tile_fast in dots_dev.h): Q and the tile are loaded before either is
-// written to LDS -- one round trip -- and the transform waits once for its column of Q instead of once per term.
-template <bool FWD, int NB, int TPC>
-__global__ __launch_bounds__(NB) void k_time_modes_tile_fast(Dev d, const double *__restrict__ x, double *__restrict__ y) {
-    extern __shared__ dots_d2v tm_lds_fast[];
-    constexpr int R = TILE_ELEMS / NB, XP = fast_tile_pitch(TPC);
-    double *Qs = reinterpret_cast<double *>(tm_lds_fast);      // [TPC][TPC]
-    double *xs = Qs + TPC * TPC;                                // [VT][XP]
-    const int n = d.T + 1;
-    const int tile = xcd_tile(blockIdx.x, d.n_vtiles);
-    if (tile >= d.n_vtiles) return;
-    const int v0 = tile * d.VT;
-    QStage<FWD, NB, TPC> qs;
-    qs.load(d, d.Q);
-    double xv[R];
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-        const int e = threadIdx.x + k * NB, vl = e / TPC, t = e & (TPC - 1);
-        const double v = x[idxV(d, min(v0 + vl, d.V - 1), t)];
-        xv[k] = ((v0 + vl < d.V) & (t < n)) ? v : 0.0;
-    }
-    qs.store(Qs);
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-        const int e = threadIdx.x + k * NB;
-        xs[(e / TPC) * XP + (e & (TPC - 1))] = xv[k];
-    }
-    __syncthreads();
-    modes_from_tile_fast<NB, TPC>(d, xs, Qs, v0, y);
-}
-
-// The transform as a GEMM on the matrix cores (T + 1 >= 64; modes_from_tile_mfma in dots_dev.h): a workgroup
-// stages the rows of 32 vertices in LDS, its four wavefronts split the 16 x 16 output tiles.
-__global__ __launch_bounds__(BLOCK) void k_time_modes_mfma(Dev d, const double *__restrict__ Qe, const double *__restrict__ x, double *__restrict__ y) {
-    extern __shared__ double xs_m[];                    // [TM_ROWS][TP + 1]
-    const int n = d.T + 1, TP = d.TP, TPp = TP + 1;
-    const int v0 = blockIdx.x * TM_ROWS;
-    for (int e = threadIdx.x; e < TM_ROWS * TP; e += BLOCK) {
-        const int vl = e >> d.tp_shift, t = e & (TP - 1);
-        xs_m[vl * TPp + t] = (v0 + vl < d.V && t < n) ? x[idxV(d, v0 + vl, t)] : 0.0;
-    }
-    __syncthreads();
-    modes_from_tile_mfma<BLOCK / 64>(d, Qe, xs_m, v0, y);
-}
-
-// The transform at pitch 512 / 1024 (T + 1 in (256, 1024]): Q of 2 / 8 MB does not fit in LDS, nor does a tile of rows with
-// all their columns beside it.  A workgroup of TPC threads owns TM_ROWS = 32 vertices and ALL their TPC outputs; wavefront w
-// owns the columns [64 w, 64 w + 64): 2 row tiles x 4 column tiles of 16 x 16, 8 accumulators of v_mfma_f64_16x16x4_f64
-// (operand layout of modes_from_tile_mfma).  The k axis runs in slices of KS: per slice the workgroup stages KS rows of the
-// zero-padded Qe and the KS columns of its 32 rows (zero past T + 1) in LDS (36 KB), then every wavefront multiplies.  Each Qe entry
-// staged serves 32 vertices; x is read once.  Fixed order of the k steps: deterministic.
-template <int TPC>
-__global__ __launch_bounds__(TPC) void k_time_modes_wide(Dev d, const double *__restrict__ Qe, const double *__restrict__ x, double *__restrict__ y) {
-    constexpr int KS = 4096 / TPC;              // rows of Qe per slice: 32 KB of LDS (with x: < 64 KB, no opt-in needed)
-    constexpr int QLD = TPC + 16;               // (16 doubles of padding: the four k rows an instruction reads sit in different banks)
-    constexpr int XLD = KS + 1;
-    extern __shared__ double tw_lds[];
-    double *Qs = tw_lds;                        // [KS][QLD]
-    double *xs = tw_lds + KS * QLD;             // [TM_ROWS][XLD]
-    const int n = d.T + 1, tid = threadIdx.x;
-    const int lane = tid & 63, w = tid >> 6, li = lane & 15, lk = lane >> 4;
-    const int v0 = blockIdx.x * TM_ROWS;
-    mfma_f64x4 acc[2][4];
-#pragma unroll
-    for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = mfma_f64x4{0.0, 0.0, 0.0, 0.0};
-    for (int k0 = 0; k0 < n; k0 += KS) {
-        if (k0 > 0) __syncthreads();            // every wavefront is done with the slice before
-#pragma unroll
-        for (int i = 0; i < KS; ++i) Qs[i * QLD + tid] = Qe[(int64_t)(k0 + i) * TPC + tid];      // rows past T + 1 are zero
-        for (int e = tid; e < TM_ROWS * KS; e += TPC) {
-            const int vl = e / KS, kk = e % KS, v = v0 + vl;
-            xs[vl * XLD + kk] = (v < d.V && k0 + kk < n) ? x[idxV(d, v, k0 + kk)] : 0.0;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < KS; kk += 4) {
-            const double a0 = xs[li * XLD + kk + lk], a1 = xs[(16 + li) * XLD + kk + lk];
-            const double *bq = Qs + (kk + lk) * QLD + w * 64 + li;
-#pragma unroll
-            for (int ct = 0; ct < 4; ++ct) {
-                const double b = bq[ct * 16];
-                acc[0][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b, acc[0][ct], 0, 0, 0);
-                acc[1][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b, acc[1][ct], 0, 0, 0);
-            }
-        }
-    }
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct) {
-        const int j = w * 64 + ct * 16 + li;
-        if (j >= n) continue;
-#pragma unroll
-        for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int v = v0 + rt * 16 + lk + 4 * r;
-                if (v < d.V) y[idxV(d, v, j)] = acc[rt][ct][r];
-            }
-    }
-}
-template <int TPC>
-static size_t time_modes_wide_lds() { return sizeof(double) * ((size_t)(4096 / TPC) * (TPC + 16) + (size_t)TM_ROWS * (4096 / TPC + 1)); }
-static void launch_time_modes_wide(Ctx *c, const double *Qe, const double *x, double *y) {
-    const Dev &d = c->d;
-    const dim3 grid((d.V + TM_ROWS - 1) / TM_ROWS);
-    if (d.TP == 512) hipLaunchKernelGGL(k_time_modes_wide<512>, grid, dim3(512), time_modes_wide_lds<512>(), c->stream, d, Qe, x, y);
-    else hipLaunchKernelGGL(k_time_modes_wide<1024>, grid, dim3(1024), time_modes_wide_lds<1024>(), c->stream, d, Qe, x, y);
-}
-
-// The transforms of a WINDOWED context (dots_pcg_windows: T + 1 in (256, 1024], no factor): k_time_modes_wide's tiling, k slices and
-// fixed order of the k steps, with the mode side compact -- mode a of vertex v lives at (a >> 8) V 256 + (v << 8) + (a & 255), so
-// that window k = modes [256 k, 256 k + 256) is the [V][256] array the PCG's pitch-256 view indexes.  A wavefront's 64 columns lie in one window.
-//   FWD   x: time space at the full pitch; y: windows.  Columns past T + 1 are not stored: a window without a live mode is never written.
-//         emit_col0: the workgroup's sum of mode 0 over its 32 vertices goes to d.partials[blockIdx.x], summed in vertex order (k_cg_bmean)
-//   !FWD  x: windows; y: time space at the full pitch (Qe = the transposed, zero-padded Q)
-template <int TPC, bool FWD>
-__global__ __launch_bounds__(TPC) void k_time_modes_windows(Dev d, const double *__restrict__ Qe, const double *__restrict__ x, double *__restrict__ y,
-                                                            int emit_col0) {
-    constexpr int KS = 4096 / TPC;
-    constexpr int QLD = TPC + 16;
-    constexpr int XLD = KS + 1;
-    extern __shared__ double tw_lds[];
-    double *Qs = tw_lds;                        // [KS][QLD]
-    double *xs = tw_lds + KS * QLD;             // [TM_ROWS][XLD]
-    const int n = d.T + 1, tid = threadIdx.x;
-    const int lane = tid & 63, w = tid >> 6, li = lane & 15, lk = lane >> 4;
-    const int v0 = blockIdx.x * TM_ROWS;
-    const int64_t wstride = (int64_t)d.V << PCG_WINDOW_SHIFT;      // doubles per window
-    const bool live = w * 64 < n;               // this wavefront stores at least one column (the others only help to stage)
-    mfma_f64x4 acc[2][4];
-#pragma unroll
-    for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = mfma_f64x4{0.0, 0.0, 0.0, 0.0};
-    for (int k0 = 0; k0 < n; k0 += KS) {
-        if (k0 > 0) __syncthreads();
-#pragma unroll
-        for (int i = 0; i < KS; ++i) Qs[i * QLD + tid] = Qe[(int64_t)(k0 + i) * TPC + tid];      // rows past T + 1 are zero
-        for (int e = tid; e < TM_ROWS * KS; e += TPC) {
-            const int vl = e / KS, kk = e % KS, v = v0 + vl, a = k0 + kk;
-            double xv = 0.0;
-            if (v < d.V && a < n)
-                xv = FWD ? x[idxV(d, v, a)] : x[(a >> PCG_WINDOW_SHIFT) * wstride + ((int64_t)v << PCG_WINDOW_SHIFT) + (a & (PCG_WINDOW - 1))];
-            xs[vl * XLD + kk] = xv;
-        }
-        __syncthreads();
-        if (live) {
-#pragma unroll
-            for (int kk = 0; kk < KS; kk += 4) {
-                const double a0 = xs[li * XLD + kk + lk], a1 = xs[(16 + li) * XLD + kk + lk];
-                const double *bq = Qs + (kk + lk) * QLD + w * 64 + li;
-#pragma unroll
-                for (int ct = 0; ct < 4; ++ct) {
-                    const double b = bq[ct * 16];
-                    acc[0][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b, acc[0][ct], 0, 0, 0);
-                    acc[1][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b, acc[1][ct], 0, 0, 0);
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct) {
-        const int j = w * 64 + ct * 16 + li;
-        if (j >= n) continue;
-#pragma unroll
-        for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int v = v0 + rt * 16 + lk + 4 * r;
-                if (v >= d.V) continue;
-                if (FWD) y[(j >> PCG_WINDOW_SHIFT) * wstride + ((int64_t)v << PCG_WINDOW_SHIFT) + (j & (PCG_WINDOW - 1))] = acc[rt][ct][r];
-                else y[idxV(d, v, j)] = acc[rt][ct][r];
-            }
-    }
-    if (FWD && emit_col0) {      // mode 0 of the 32 vertices sits in wavefront 0, column tile 0, lanes 0, 16, 32, 48 (rows past V are zero)
-        __syncthreads();         // every wavefront is done with the last slice: xs is free
-        if (w == 0 && li == 0) {
-#pragma unroll
-            for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) xs[rt * 16 + lk + 4 * r] = acc[rt][0][r];
-        }
-        __syncthreads();
-        if (tid == 0) {
-            double s = 0.0;
-            for (int i = 0; i < TM_ROWS; ++i) s += xs[i];
-            d.partials[blockIdx.x] = s;
-        }
-    }
-}
-static int windows_transform_grid(const Dev &d) { return (d.V + TM_ROWS - 1) / TM_ROWS; }
-template <bool FWD>
-static void launch_time_modes_windows(Ctx *c, const double *x, double *y, int emit_col0) {
-    const Dev &d = c->d;
-    const double *Qe = FWD ? d.Qpad : d.QpadT;
-    const dim3 grid(windows_transform_grid(d));
-    if (d.TP == 512)
-        hipLaunchKernelGGL((k_time_modes_windows<512, FWD>), grid, dim3(512), time_modes_wide_lds<512>(), c->stream, d, Qe, x, y, emit_col0);
-    else
-        hipLaunchKernelGGL((k_time_modes_windows<1024, FWD>), grid, dim3(1024), time_modes_wide_lds<1024>(), c->stream, d, Qe, x, y, emit_col0);
-}
-
 // ------------------------------------------------------------------------------------------
 // host driver
 // ------------------------------------------------------------------------------------------
@@ -729,7 +477,7 @@ int64_t cg_partials_needed(const Dev &d) {
     if (d.TP <= PCG_WINDOW) return own;
     // a wide context may solve in windows (dots_pcg_windows): the pitch-256 view has its own tiling, and the windowed forward
     // transform leaves one column-0 sum per workgroup in front
-    return std::max<int64_t>({own, cg_partials_needed(pcg_window_view(d, 0)), (int64_t)windows_transform_grid(d)});
+    return std::max<int64_t>({own, cg_partials_needed(pcg_window_view(d, 0)), (int64_t)modes_windows_sums(d)});
 }
 
 // sum partial array k into its collapsed row (no-op for problems small enough to re-reduce in the consumers)
@@ -843,129 +591,12 @@ static int cg_core(Ctx *c, const Dev &d, CgCache &k, const double *coarse_inv, i
     return 0;
 }
 
-// ---- transforms of a time-slab context (multi-GPU) -------------------------------------------------------------
-// Both read an all-gathered buffer of R chunks: chunk p holds [V][pitch] doubles with `stride` live columns, column j of
-// chunk p = global index p * stride + j (time node for the right-hand side, time mode for the solution).
-struct Gathered {
-    const double *base;
-    int64_t chunk;       // doubles per rank
-    int shift;           // log2 of the pitch inside a chunk
-    int stride;          // live columns per chunk
-};
-__device__ __forceinline__ double gathered_at(const Gathered &G, int v, int i) {
-    const int p = i / G.stride, j = i - p * G.stride;
-    return G.base[p * G.chunk + ((int64_t)v << G.shift) + j];
-}
-
-// Forward transform restricted to the modes [a0, a0 + g.cg_ncol) this context solves, from the gathered right-hand
-// side:  y[v][j] = sum_t Q[t][a0 + j] b[v][t]  (pitch of the PCG view).  Emits the column-0 partial sums (mean removal
-// of the singular mode) when asked to.   dt: the global-time view (T, Q).
-__global__ __launch_bounds__(BLOCK) void k_time_modes_fwd_sub(Dev dt, Dev g, int a0, Gathered x, double *__restrict__ y, int emit_col0) {
-    __shared__ double lds[4];
-    const int n = dt.T + 1, nloc = g.cg_ncol;
-    double part[1] = {0.0};
-    const int64_t total = (int64_t)dt.V << g.tp_shift;
-    for (int64_t e = (int64_t)blockIdx.x * BLOCK + threadIdx.x; e < total; e += (int64_t)gridDim.x * BLOCK) {
-        const int v = (int)(e >> g.tp_shift), j = (int)(e & (g.TP - 1));
-        if (j >= nloc) continue;
-        double s = 0.0;
-        for (int i = 0; i < n; ++i) s += dt.Q[i * n + a0 + j] * gathered_at(x, v, i);
-        y[idxV(g, v, j)] = s;
-        if (emit_col0 && j == 0) part[0] += s;
-    }
-    if (emit_col0) {
-        block_sum<1>(part, lds);
-        if (threadIdx.x == 0) dt.partials[blockIdx.x] = part[0];
-    }
-}
-
-// Tiled forms (same staging as k_time_modes_tile; dt = the global-time view: pitch >= T + 1).  Forward: stores only
-// this context's modes with the PCG view's pitch.
-__global__ __launch_bounds__(BLOCK) void k_time_modes_fwd_sub_tile(Dev dt, int a0, int nloc, int out_shift, Gathered x, double *__restrict__ y, int IC) {
-    extern __shared__ double tm_lds[];
-    const int n = dt.T + 1, TP = dt.TP, TPp = TP + 1;
-    double *Qs = tm_lds, *xs = tm_lds + IC * TP;
-    const int tile = xcd_tile(blockIdx.x, dt.n_vtiles);
-    if (tile >= dt.n_vtiles) return;
-    const int v0 = tile * dt.VT;
-    for (int e = threadIdx.x; e < TILE_ELEMS; e += BLOCK) {
-        const int vl = e >> dt.tp_shift, t = e & (TP - 1);
-        xs[vl * TPp + t] = (v0 + vl < dt.V && t < n) ? gathered_at(x, v0 + vl, t) : 0.0;
-    }
-    modes_from_tile<true>(dt, dt.Q, xs, Qs, IC, v0, y, out_shift, a0, nloc);
-}
-
-// Inverse: phi of this slab's nodes [t0, t0 + nl) (pitch of the slab, 1 << out_shift) from the gathered mode-space
-// solution, and phi at node t0 + nl (the next slab's first node) into phi_hi: the same sum, in the same order, as the
-// owner of that node forms -- no exchange of phi is ever needed.
-__global__ __launch_bounds__(BLOCK) void k_time_modes_inv_gathered_tile(Dev dt, Gathered x, double *__restrict__ y, int out_shift, int t0, int nl,
-                                                                        double *__restrict__ phi_hi, int IC) {
-    extern __shared__ double tm_lds[];
-    const int n = dt.T + 1, TP = dt.TP, TPp = TP + 1;
-    double *Qs = tm_lds, *xs = tm_lds + IC * TP;
-    const int tile = xcd_tile(blockIdx.x, dt.n_vtiles);
-    if (tile >= dt.n_vtiles) return;
-    const int v0 = tile * dt.VT;
-    for (int e = threadIdx.x; e < TILE_ELEMS; e += BLOCK) {
-        const int vl = e >> dt.tp_shift, a = e & (TP - 1);
-        xs[vl * TPp + a] = (v0 + vl < dt.V && a < n) ? gathered_at(x, v0 + vl, a) : 0.0;
-    }
-    modes_from_tile<false>(dt, dt.Q, xs, Qs, IC, v0, y, out_shift, t0, nl);
-    const int th = t0 + nl;      // first node of the next slab
-    if (th < n && (int)threadIdx.x < dt.VT && v0 + (int)threadIdx.x < dt.V) {
-        const double *x0 = xs + threadIdx.x * TPp;
-        double acc = 0.0;
-        for (int a = 0; a < n; ++a) acc += dt.Q[th * n + a] * x0[a];
-        phi_hi[v0 + threadIdx.x] = acc;
-    }
-}
-
-// The time transforms around the solve of one GPU: b^ = Q^T b of `in` into `out` (mode space), and phi = Q x^ back.  `direct`: the
-// sweeps solve (no warm start, no mean removal); the kernels are chosen as step 1 chooses them (cg_solve_impl, dots_laplacian_solve_many)
-void modes_forward(Ctx *c, const double *in, double *out, bool direct) {
-    const Dev &d = c->d;
-    const int gt = xcd_grid(d.n_vtiles);
-    if (!direct && pcg_windowed(c))
-        launch_time_modes_windows<true>(c, in, out, 1);      // `out` in compact windows, column-0 sums for k_cg_bmean
-    else if (direct && time_modes_wide_ok(d))
-        launch_time_modes_wide(c, d.Qpad, in, out);
-    else if (direct && time_modes_tile_ok(d))
-        hipLaunchKernelGGL((k_time_modes_tile<true>), dim3(gt), dim3(BLOCK), time_modes_tile_lds(d), c->stream, d, in, out, time_modes_chunk(d));
-    else
-        hipLaunchKernelGGL((k_time_modes<true>), dim3(gt), dim3(BLOCK), 0, c->stream, d, in, out, 1);
-}
-void modes_inverse(Ctx *c, const double *x, double *phi, bool direct) {
-    const Dev &d = c->d;
-    const int gt = xcd_grid(d.n_vtiles);
-    c->carried.deep_path &= ~DEEP_PATH_INVERSE;
-    if (!direct && pcg_windowed(c))
-        launch_time_modes_windows<false>(c, x, phi, 0);      // `x` in compact windows
-    else if (direct && time_modes_wide_ok(d))
-        launch_time_modes_wide(c, d.QpadT, x, phi);
-    else if (time_modes_mfma_ok(d))
-        hipLaunchKernelGGL(k_time_modes_mfma, dim3((d.V + TM_ROWS - 1) / TM_ROWS), dim3(BLOCK), sizeof(double) * TM_ROWS * (d.TP + 1), c->stream, d, d.QpadT,
-                           x, phi);
-    else if (time_modes_tile_ok(d) && direct && d.n_vtiles <= 512 && deep_launch_wins(c, gt)) {      // ... with its reads in flight (pitch 8, 16, 32)
-        with_constant<8, 16, 32>(d.TP, [&](auto TPC) {
-            hipLaunchKernelGGL((k_time_modes_tile_fast<false, 1024, TPC>), dim3(gt), dim3(1024), time_modes_fast_lds(d), c->stream, d, x, phi);
-        });
-        c->carried.deep_path |= DEEP_PATH_INVERSE;
-    }
-    else if (time_modes_tile_ok(d) && direct && d.n_vtiles <= 512)      // small meshes, behind the sweeps: latency-bound, one output per thread (knot: 9.5 -> 6 us; no gain at 10^5 vertices)
-        hipLaunchKernelGGL((k_time_modes_tile<false, 1024>), dim3(gt), dim3(1024), time_modes_tile_lds(d), c->stream, d, x, phi, time_modes_chunk(d));
-    else if (time_modes_tile_ok(d))
-        hipLaunchKernelGGL((k_time_modes_tile<false>), dim3(gt), dim3(BLOCK), time_modes_tile_lds(d), c->stream, d, x, phi, time_modes_chunk(d));
-    else
-        hipLaunchKernelGGL((k_time_modes<false>), dim3(gt), dim3(BLOCK), 0, c->stream, d, x, phi, 0);
-}
-
 // Step 1 for the modes of this context.  Unsharded: also transforms back (phi is complete on return).
 // Sharded: the local mode-space solution stays in dcg.cg_x for the caller to exchange (cg_finish_sharded).
 template <bool MODAL>
 static int cg_solve_impl(Ctx *c, dots_step_stats *stats, bool defer_inverse) {
     const Dev &d = c->d;
     const Dev &g = c->dcg;
-    const int gt = xcd_grid(d.n_vtiles);
     const bool singular = (c->prm.eps == 0.0);
     double *x = MODAL ? g.cg_x : d.phi;
     const double *b = d.cg_b;
@@ -979,33 +610,26 @@ static int cg_solve_impl(Ctx *c, dots_step_stats *stats, bool defer_inverse) {
         return DOTS_ERR_STATE;
     }
     if (sharded) {
-        // time-slab context: the right-hand side of ALL nodes was all-gathered into slab.b_recv; this rank transforms the
-        // modes it solves.  The PCG warm start is its own mode-space solution of the previous iteration (g.cg_x).
-        const Dev &dt = c->dgt;
-        const Gathered bg{c->slab.b_recv, c->slab_b_chunk, d.tp_shift, c->shard_stride};
-        const int gs = 1024;   // grid-stride; k_cg_bmean sums exactly this many partial sums
-        if (direct && time_modes_tile_ok(dt))     // no mean removal with the direct solver: the tiled transform
-            hipLaunchKernelGGL(k_time_modes_fwd_sub_tile, dim3(xcd_grid(dt.n_vtiles)), dim3(BLOCK), time_modes_tile_lds(dt), c->stream, dt, c->shard_begin,
-                               g.cg_ncol, g.tp_shift, bg, g.cg_p0, time_modes_chunk(dt));
-        else
-            hipLaunchKernelGGL(k_time_modes_fwd_sub, dim3(gs), dim3(BLOCK), 0, c->stream, dt, g, c->shard_begin, bg, g.cg_p0, owns_mode0 ? 1 : 0);
+        // time-slab context: this rank transforms the modes it solves of the all-gathered right-hand side.  The PCG warm start is its
+        // own mode-space solution of the previous iteration (g.cg_x).
+        modes_forward_sharded(c, direct);
         b = g.cg_p0;
         const double mean_scale = (singular && owns_mode0) ? 1.0 / d.V : 0.0;
-        if (!direct) hipLaunchKernelGGL(k_cg_bmean, dim3(1), dim3(BLOCK), 0, c->stream, d, owns_mode0 ? gs : 0, g.cg_ncol, mean_scale);
+        if (!direct) hipLaunchKernelGGL(k_cg_bmean, dim3(1), dim3(BLOCK), 0, c->stream, d, modes_forward_sums(c), g.cg_ncol, mean_scale);
     } else {
         if (MODAL) {
             // b^ = Q^T b (into p0 as scratch), x^ = Q^T phi (warm start in mode space)
             if (rhs_writes_modes(c)) {
                 // k_rhs_modes (kernels_alm.hip) already left the mode-space right-hand side in cg_p0
             } else modes_forward(c, d.cg_b, d.cg_p0, direct);
-            if (windowed) launch_time_modes_windows<true>(c, d.phi, d.cg_x, 0);
-            else if (!direct) hipLaunchKernelGGL((k_time_modes<true>), dim3(gt), dim3(BLOCK), 0, c->stream, d, d.phi, d.cg_x, 0);
+            if (!direct) modes_forward(c, d.phi, d.cg_x, false, false);
             b = d.cg_p0;   // consumed by k_cg_r0 before iteration 0 (which reads no p_old: beta = 0) writes p1
         }
         const double mean_scale = !singular ? 0.0 : (MODAL ? 1.0 / d.V : 1.0 / ((double)d.V * (d.T + 1)));
-        // (windowed: the forward transform left one sum per workgroup; the scalar block holds one window's columns)
+        // the partial sums of b: the forward transform's of mode 0 (MODAL), the right-hand-side kernel's one per tile otherwise
+        // (windowed: the scalar block holds one window's columns)
         if (!direct)
-            hipLaunchKernelGGL(k_cg_bmean, dim3(1), dim3(BLOCK), 0, c->stream, d, windowed ? windows_transform_grid(d) : gt,
+            hipLaunchKernelGGL(k_cg_bmean, dim3(1), dim3(BLOCK), 0, c->stream, d, MODAL ? modes_forward_sums(c) : xcd_grid(d.n_vtiles),
                                windowed ? PCG_WINDOW : (MODAL ? d.cg_ncol : 1), mean_scale);
     }
     DOTS_HIP(hipGetLastError());
@@ -1045,7 +669,7 @@ static int cg_solve_impl(Ctx *c, dots_step_stats *stats, bool defer_inverse) {
     }
     if (rc) return rc;
     if (MODAL && !sharded && !defer_inverse) {
-        modes_inverse(c, d.cg_x, d.phi, direct);
+        if ((rc = modes_inverse(c, d.cg_x, d.phi, direct))) return rc;
         DOTS_HIP(hipGetLastError());
     }
     return 0;
@@ -1053,18 +677,6 @@ static int cg_solve_impl(Ctx *c, dots_step_stats *stats, bool defer_inverse) {
 
 int cg_solve(Ctx *c, dots_step_stats *stats, bool defer_inverse) {
     return c->lap_solver == DOTS_LAP_MODAL_PCG ? cg_solve_impl<true>(c, stats, defer_inverse) : cg_solve_impl<false>(c, stats, false);
-}
-
-// phi of this slab from the mode-space solutions of all ranks (slab.x_recv = [n_ranks][V][mode pitch])
-int cg_finish_sharded(Ctx *c) {
-    const Dev &d = c->d, &dt = c->dgt;
-    if (d.nl == 0) return 0;
-    if (!time_modes_tile_ok(dt)) { set_error("time slabs need T + 1 <= 256"); return DOTS_ERR_STATE; }
-    const Gathered xg{c->slab.x_recv, c->slab_x_chunk, c->dcg.tp_shift, c->shard_stride};
-    hipLaunchKernelGGL(k_time_modes_inv_gathered_tile, dim3(xcd_grid(dt.n_vtiles)), dim3(BLOCK), time_modes_tile_lds(dt), c->stream, dt, xg, d.phi,
-                       d.tp_shift, d.t0, d.nl, d.phi_hi, time_modes_chunk(dt));
-    DOTS_HIP(hipGetLastError());
-    return 0;
 }
 
 // y = K x on node-layout arrays with the coupled space-time operator (tests, operator parity)
@@ -1206,20 +818,6 @@ int cg_bench(Ctx *c, int which, int reps, double *ms, double *bytes) {
     else if (which == 1) *bytes = 8.0 * N * (a.mg ? 6.0 : 7.0) + 16.0 * d.V;       // x,p,r,Ap read; x,r(,z) written
     else *bytes = 12.0 * c->nnz + 4.0 * (d.V + 1) + 16.0 * d.V + 8.0 * N * 4.0;    // CSR + z,p_old read; p_new,Ap written
     return 0;
-}
-
-void preload_transform_kernels() {      // (see preload_alm_kernels)
-    const void *fns[] = {(const void *)k_time_modes_tile<true, BLOCK>, (const void *)k_time_modes_tile<false, BLOCK>,
-                         (const void *)k_time_modes_tile<false, 1024>, (const void *)k_time_modes_mfma,
-                         (const void *)k_time_modes_tile_fast<false, 1024, 8>, (const void *)k_time_modes_tile_fast<false, 1024, 16>,
-                         (const void *)k_time_modes_tile_fast<false, 1024, 32>,
-                         (const void *)k_time_modes<true>, (const void *)k_time_modes<false>,
-                         (const void *)k_time_modes_wide<512>, (const void *)k_time_modes_wide<1024>,
-                         (const void *)k_time_modes_windows<512, true>, (const void *)k_time_modes_windows<512, false>,
-                         (const void *)k_time_modes_windows<1024, true>, (const void *)k_time_modes_windows<1024, false>};
-    hipFuncAttributes a;
-    for (const void *f : fns) (void)hipFuncGetAttributes(&a, f);
-    (void)hipGetLastError();
 }
 
 }  // namespace dots

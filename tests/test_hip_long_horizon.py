@@ -1,7 +1,7 @@
 """GPU tests of the direct solver at long time horizons: T + 1 in (256, 1024], mode pitches 512 and 1024.
 
 Above 256 time nodes the factorisation and the sweeps cut the mode axis into chunks of 256 (kernels_factor.hip, kernels_front.hip) and the
-time transforms run as k_time_modes_wide (kernels_cg.hip).  Whole runs against the reference's recorded runs (tests/golden/long_*.npz,
+time transforms run as k_time_modes_wide (kernels_modes.hip).  Whole runs against the reference's recorded runs (tests/golden/long_*.npz,
 make_long_horizon.py), the Laplacian phase against the oracle's per-mode SuperLU, the element-wise phases against the oracle, the batched
 solver against runs alone, and the error contract of the limits."""
 import glob

@@ -1,6 +1,6 @@
 """GPU: the windowed modal PCG (dots_pcg_windows) -- long horizons without a factor.  Above 256 time nodes the T + 1 modal problems
 are solved in windows of 256 modes, each through the PCG kernels at pitch 256, between the windowed time transforms
-(k_time_modes_windows: time space at the full pitch, mode space in compact windows).
+(k_time_modes_windows in kernels_modes.hip: time space at the full pitch, mode space in compact windows).
 
 Iterates: phi after cg_max_iter = 8 and 16 against the fp64 host PCG of pcg_checks.py, whose single loop over all T + 1 columns is the
 reference of every window (per-column scalars; a frozen column changes nothing).  The random warm start catches a wrong Q^T phi, the

@@ -152,6 +152,20 @@ def test_elementwise_kernels_are_the_lane_bodies_instantiations(kernels):
     assert got == sorted(want)
 
 
+def test_time_transform_kernels_are_the_ladders_rungs(kernels):
+    """The kernels that only transform between time and mode space (csrc/kernels_modes.hip) are the rungs modes_forward, modes_inverse and
+    the two time-slab launches choose among, and no others: the forward form straight from memory, the chunked tile form <FWD, NB>, its
+    deep form <FWD, NB, pitch>, the MFMA form, the wide body as k_time_modes_wide<pitch> and k_time_modes_windows<pitch, FWD>, and the
+    three gathered forms.  An inverse straight from memory that comes back, or a wide body that splits again, changes this set."""
+    want = ["k_time_modes", "k_time_modes_tile<1,256>", "k_time_modes_tile<0,256>", "k_time_modes_tile<0,1024>", "k_time_modes_mfma"]
+    want += [f"k_time_modes_tile_fast<0,1024,{tp}>" for tp in (8, 16, 32)]
+    want += [f"k_time_modes_wide<{tp}>" for tp in (512, 1024)]
+    want += [f"k_time_modes_windows<{tp},{fwd}>" for tp in (512, 1024) for fwd in (0, 1)]
+    want += ["k_time_modes_fwd_sub", "k_time_modes_fwd_sub_tile", "k_time_modes_inv_gathered_tile"]
+    got = sorted(r["short"] for r in kernels if r["short"].startswith("k_time_modes"))
+    assert got == sorted(want)
+
+
 def test_flow_kernels_are_one_tracer_family(kernels):
     """Every trace is a span: the tracer with and without the sliding mode, each bare and with the deposits of 0 .. 4 attributes, and
     the conversion of the sums.  A family that comes back or an instantiation that drops out changes this set."""
