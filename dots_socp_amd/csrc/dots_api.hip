@@ -294,11 +294,9 @@ static int build(Ctx *c, const dots_problem_desc *p) {
     if ((rc = c->pinned.alloc(&c->h_mail, MAX_SUMS + 8, hipHostMallocCoherent | hipHostMallocMapped))) return rc;
     for (int i = 0; i < MAX_SUMS + 8; ++i) c->h_mail[i] = 0.0;
 
-    // the PCG's view of the device data (see Ctx::dcg), and on a slab the global-time view of the transforms
-    c->dcg = d;
-    c->dgt = d;
+    // what the PCG's view and, on a slab, the global-time view of the transforms hold besides d (pcg_view, time_view)
     if (sharded) {
-        Dev &g = c->dcg;           // modes [shard_begin, shard_begin + shard_count): same partition, same pitch as the slab
+        PcgRecord &g = c->pcg;     // modes [shard_begin, shard_begin + shard_count): same partition, same pitch as the slab
         g.cg_ncol = p->slab_count;
         std::vector<double> sig(tp, 0.0);
         for (int i = 0; i < p->slab_count; ++i) sig[i] = p->time_eigs[p->slab_begin + i];
@@ -306,7 +304,7 @@ static int build(Ctx *c, const dots_problem_desc *p) {
         double **cgv[5] = {&g.cg_r, &g.cg_z, &g.cg_p0, &g.cg_p1, &g.cg_Ap};     // cg_x = slab.x_send (dots_slab_set_buffers)
         for (auto q : cgv)
             if ((rc = dev_alloc(c, q, nnode))) return rc;
-        Dev &t = c->dgt;
+        TimeRecord &t = c->gt;
         t.TP = tpg; t.tp_shift = shg; t.t0 = 0; t.nl = d.T + 1; t.ni = d.T; t.slab = 0;
         t.VT = t.FT = TILE_ELEMS / tpg;
         t.n_vtiles = (d.V + t.VT - 1) / t.VT;
@@ -338,7 +336,7 @@ static int flush_division(Ctx *c) { return flush_division(c->carried, RUNTIME, c
 // The modal PCG keeps per-mode scalars for NC <= CgScalOffsets::NCMAX = 256 modes: a modal context of T + 1 > 256 steps with the
 // direct solver only (a factor installed or shared, and enabled), unless the caller switched the windowed PCG on (dots_pcg_windows).
 static int modal_needs_factor(const Ctx *c, const char *what) {
-    if (c->lap_solver != DOTS_LAP_MODAL_PCG || c->dcg.cg_ncol <= CgScalOffsets::NCMAX || (c->use_front && c->front.n_nodes > 0)) return 0;
+    if (c->lap_solver != DOTS_LAP_MODAL_PCG || pcg_ncol(c) <= CgScalOffsets::NCMAX || (c->use_front && c->front.n_nodes > 0)) return 0;
     if (pcg_windowed(c)) return 0;      // dots_pcg_windows: the PCG takes the modes in windows of 256
     set_error(std::string(what) + ": T + 1 > 256 needs the direct solver (dots_front_setup); the modal PCG takes T + 1 <= 256");
     return DOTS_ERR_STATE;
@@ -415,6 +413,16 @@ static hipEvent_t *time_slot(Ctx *c, int kind) {
     return c->tev[s];
 }
 
+// the milliseconds of one stage of a slab's iteration, booked where dots_slab_stage (with stats) and dots_step_times report them
+static void book_stage(dots_step_stats &st, int stage, float t) {
+    st.ms_total = t;
+    if (stage == 0 || stage == 6) st.ms_rhs = t;                // packing the halos; the right-hand side alone
+    if (stage == 5) st.ms_soc = t;
+    if (stage == 1) st.ms_rhs = st.ms_soc = 0.5 * t;            // one launch: right-hand side and projection together
+    if (stage == 2) st.ms_laplacian = t;
+    if (stage == 3) { st.ms_q_lambda_multiplier = t; st.alm_iterations = 1; }
+}
+
 // What the first half of an iteration decided, for its second half (iteration_before / iteration_after)
 struct IterPlan {
     double dv = 0.0;          // a pending penalty division the iteration's kernels apply as they read
@@ -455,14 +463,7 @@ static int iteration_before(Ctx *c, bool timed, IterPlan &p, hipEvent_t *tv) {
     p.ahead_kind = (c->step_palm || k.rhs_ahead > 2) ? 0 : k.rhs_ahead;      // (3, 4: an anticipated penalty update the caller did not confirm)
     const bool ahead = p.ahead_kind != 0;
     k.rhs_ahead = 0;
-    if (p.ahead_kind == 2) {      // the projection ran ahead too: its results become the current z_fst, z_end and cone multiplier
-        std::swap(c->d.zf, c->zf_alt);
-        std::swap(c->d.ze, c->ze_alt);
-        std::swap(c->d.lamc, c->lamc_alt);
-        c->dcg.zf = c->dgt.zf = c->d.zf;
-        c->dcg.ze = c->dgt.ze = c->d.ze;
-        c->dcg.lamc = c->dgt.lamc = c->d.lamc;
-    }
+    if (p.ahead_kind == 2) c->swap_ahead_projection();      // the projection ran ahead too: its results become the current z_fst, z_end and cone multiplier
     if (timed) return 0;      // (the timed path of run_iteration_body goes on itself)
     k.stepped(c->step_skip_zmid);
     p.fused_rhs = rhs_writes_modes(c) && !ahead;      // [right-hand side + projection] -> sweeps -> inverse transform -> steps 2+3
@@ -721,14 +722,7 @@ int dots_slab_set_buffers(dots_ctx *c, const dots_slab_buffers *b) {
     // the previous slab appended its last interval's cone multipliers to its chunk of the SOLUTION all-gather (they are needed by
     // steps 2+3, after it: the right-hand-side all-gather can then start before the projection has run)
     d.lamc_lo = (rank > 0 && d.nl > 0) ? b->x_recv + (int64_t)(rank - 1) * c->slab_x_chunk + ((int64_t)d.V << d.tp_shift) : b->recv_x;
-    const Dev g0 = c->dcg, t0 = c->dgt;
-    c->dcg = d;                                 // the solver's view: same pitch, its own vectors, sigma slice, mode count
-    c->dcg.cg_ncol = g0.cg_ncol; c->dcg.sigma = g0.sigma;
-    c->dcg.cg_r = g0.cg_r; c->dcg.cg_z = g0.cg_z; c->dcg.cg_p0 = g0.cg_p0; c->dcg.cg_p1 = g0.cg_p1; c->dcg.cg_Ap = g0.cg_Ap;
-    c->dcg.cg_x = b->x_send;                    // ... the mode-space solution is written where the second all-gather reads it
-    c->dgt = d;                                 // the transforms' view: same pointers, global-time geometry
-    c->dgt.TP = t0.TP; c->dgt.tp_shift = t0.tp_shift; c->dgt.t0 = 0; c->dgt.nl = d.T + 1; c->dgt.ni = d.T; c->dgt.slab = 0;
-    c->dgt.VT = t0.VT; c->dgt.FT = t0.FT; c->dgt.n_vtiles = t0.n_vtiles; c->dgt.n_ftiles = t0.n_ftiles;
+    c->pcg.cg_x = b->x_send;                    // the solver's view: the mode-space solution is written where the second all-gather reads it
     // the PCG's warm start (its own previous solution) and the buffers' padding start from zero
     DOTS_HIP(hipMemsetAsync(b->x_send, 0, sizeof(double) * (size_t)c->slab_x_chunk, c->stream));
     DOTS_HIP(hipMemsetAsync(b->b_send, 0, sizeof(double) * (size_t)c->slab_b_chunk, c->stream));
@@ -765,12 +759,8 @@ int dots_slab_stage(dots_ctx *c, int stage, dots_step_stats *stats) {
         float t;
         DOTS_HIP(hipEventElapsedTime(&t, c->ev[0], c->ev[1]));
         memset(stats, 0, sizeof *stats);
-        stats->ms_total = t;
-        if (stage == 0 || stage == 6) stats->ms_rhs = t;              // packing the halos (as dots_step_times books it); the right-hand side alone
-        if (stage == 5) stats->ms_soc = t;
-        if (stage == 1) stats->ms_rhs = stats->ms_soc = 0.5 * t;      // one launch: right-hand side and projection together
-        if (stage == 2) { stats->ms_laplacian = t; stats->cg_iterations = stats->cg_last_iterations = c->last_cg_iters; }
-        if (stage == 3) { stats->ms_q_lambda_multiplier = t; stats->alm_iterations = 1; }
+        book_stage(*stats, stage, t);
+        if (stage == 2) stats->cg_iterations = stats->cg_last_iterations = c->last_cg_iters;
     }
     if (stage <= 3) c->slab_stage = (stage + 1) & 3;
     else if (stage == 6) c->slab_stage = 5;
@@ -864,12 +854,7 @@ int dots_step_times(dots_ctx *c, dots_step_stats *out, int capacity, int wait, i
         } else {
             const int stage = kind - 1;
             DOTS_HIP(hipEventElapsedTime(&t, tv[0], tv[1]));
-            st.ms_total = t;
-            if (stage == 0 || stage == 6) st.ms_rhs = t;                // packing the halos; the right-hand side alone
-            if (stage == 5) st.ms_soc = t;
-            if (stage == 1) st.ms_rhs = st.ms_soc = 0.5 * t;            // one launch: right-hand side and projection together
-            if (stage == 2) st.ms_laplacian = t;
-            if (stage == 3) { st.ms_q_lambda_multiplier = t; st.alm_iterations = 1; }
+            book_stage(st, stage, t);
         }
         c->t_head = (c->t_head + 1) % Ctx::TIME_SLOTS;
         c->t_count -= 1;
@@ -1051,14 +1036,14 @@ int dots_mg_setup(dots_ctx *c, const dots_mg_desc *m) {
     if (rc) return rc;
     if (!m || m->n_levels < 2 || m->n_levels > 10 || !m->levels || !m->coarse_inverse) { set_error("mg_setup: bad description"); return DOTS_ERR_ARGUMENT; }
     if (c->lap_solver != DOTS_LAP_MODAL_PCG) { set_error("multigrid needs the modal solver"); return DOTS_ERR_ARGUMENT; }
-    const bool windowed = c->pcg_windows && c->shard_stride == 0 && c->dcg.cg_ncol > CgScalOffsets::NCMAX;      // one coarse inverse per window of 256 modes
-    if (c->dcg.cg_ncol > CgScalOffsets::NCMAX && !windowed) { set_error("mg_setup: the modal PCG takes T + 1 <= 256; above, use the direct solver (dots_front_setup)"); return DOTS_ERR_STATE; }
-    if (m->levels[0].n != c->d.V || m->n_cols != c->dcg.cg_ncol) { set_error("mg_setup: level 0 / mode count mismatch"); return DOTS_ERR_ARGUMENT; }
+    const bool windowed = c->pcg_windows && c->shard_stride == 0 && pcg_ncol(c) > CgScalOffsets::NCMAX;      // one coarse inverse per window of 256 modes
+    if (pcg_ncol(c) > CgScalOffsets::NCMAX && !windowed) { set_error("mg_setup: the modal PCG takes T + 1 <= 256; above, use the direct solver (dots_front_setup)"); return DOTS_ERR_STATE; }
+    if (m->levels[0].n != c->d.V || m->n_cols != pcg_ncol(c)) { set_error("mg_setup: level 0 / mode count mismatch"); return DOTS_ERR_ARGUMENT; }
     DOTS_HIP(hipStreamSynchronize(c->stream));
     c->cg_graphs_release();
     mg_release(c);
     // level vectors and the coarse inverse use the PCG view's pitch; windowed: a window's (256 columns), the vectors reused by every window
-    const Dev d = windowed ? pcg_window_view(c->dcg, 0) : c->dcg;
+    const Dev pv = pcg_view(c), d = windowed ? pcg_window_view(pv, 0) : pv;
     MgDev g{};
     g.nlev = m->n_levels;
     g.omega = m->omega;
@@ -1108,7 +1093,7 @@ int dots_mg_setup(dots_ctx *c, const dots_mg_desc *m) {
     // coarse inverse: host [nL][nL][n_cols] -> device [nL][nL][TP]
     // (windowed: block w = the modes [256 w, 256 w + 256), [nL][nL][256] each, one after the other)
     const int nL = m->levels[m->n_levels - 1].n;
-    const int n_win = windowed ? pcg_window_count(c->dcg) : 1;
+    const int n_win = windowed ? pcg_window_count(pv) : 1;
     const size_t block = (size_t)nL * nL * d.TP;
     std::vector<double> inv(block * n_win, 0.0);
     for (int64_t ij = 0; ij < (int64_t)nL * nL; ++ij)
@@ -1138,10 +1123,10 @@ int dots_mg_apply(dots_ctx *c, const double *r, double *z, double *rz, const int
     if (rc) return rc;
     if (c->lap_solver != DOTS_LAP_MODAL_PCG) { set_error("mg_apply: the V-cycle belongs to the modal solver"); return DOTS_ERR_STATE; }
     if (c->shard_stride != 0) { set_error("mg_apply: not on a time slab"); return DOTS_ERR_STATE; }
-    if (c->dcg.cg_ncol > CgScalOffsets::NCMAX) { set_error("mg_apply: one V-cycle on all modes takes T + 1 <= 256 (a windowed context cycles inside its solves only)"); return DOTS_ERR_STATE; }
+    if (pcg_ncol(c) > CgScalOffsets::NCMAX) { set_error("mg_apply: one V-cycle on all modes takes T + 1 <= 256 (a windowed context cycles inside its solves only)"); return DOTS_ERR_STATE; }
     if (c->mg.nlev < 2) { set_error("mg_apply: no multigrid hierarchy on this context (dots_mg_setup)"); return DOTS_ERR_STATE; }
     if (!r || !z || !rz) { set_error("mg_apply: null array"); return DOTS_ERR_ARGUMENT; }
-    const Dev &g = c->dcg;
+    const Dev &g = c->d;      // (not a time slab: the PCG view is d)
     const int64_t nh = array_count_host(c->d, DOTS_PHI);      // [n_modes][V], the layout of phi
     for (int k = 0; k < FLAG_TOTAL; ++k) c->h_flags[k] = (k < g.cg_ncol && frozen && frozen[k]) ? 1 : 0;
     DOTS_HIP(hipMemcpyAsync(g.flags, c->h_flags, sizeof(int) * FLAG_TOTAL, hipMemcpyHostToDevice, c->stream));
@@ -1212,7 +1197,7 @@ static int batch_members(Entry e, dots_ctx *const *cs, int n, BatchMembers &out,
             if (cs[j] == cs[k]) { set_error(w + ": a context is listed twice"); return DOTS_ERR_ARGUMENT; }
     }
     out.cv.assign(cs, cs + n);
-    for (Ctx *c : out.cv) { out.bh.push_back(c->d.cg_p0); out.ys.push_back(c->dcg.cg_z); out.xs.push_back(c->dcg.cg_x); }
+    for (Ctx *c : out.cv) { out.bh.push_back(c->d.cg_p0); out.ys.push_back(c->d.cg_z); out.xs.push_back(c->d.cg_x); }      // (front_batchable: one GPU, the PCG view is d)
     return 0;
 }
 
@@ -1253,7 +1238,7 @@ int dots_front_share(dots_ctx *c, dots_ctx *owner) {
     else if (a.V != b.V || a.F != b.F || a.T != b.T) snprintf(buf, sizeof buf, "V, F, T = %d, %d, %d, the owner's %d, %d, %d", a.V, a.F, a.T, b.V, b.F, b.T);
     else if (c->nnz != owner->nnz) snprintf(buf, sizeof buf, "%d Laplacian entries, the owner's %d", c->nnz, owner->nnz);
     else if (c->prm.eps != owner->sched.eps) snprintf(buf, sizeof buf, "eps %.17g, the owner's factor was built with %.17g", c->prm.eps, owner->sched.eps);
-    else if (c->dcg.TP != owner->dcg.TP || c->dcg.cg_ncol != owner->dcg.cg_ncol) snprintf(buf, sizeof buf, "mode pitch %d, the owner's %d", c->dcg.TP, owner->dcg.TP);
+    else if (a.TP != b.TP || a.cg_ncol != b.cg_ncol) snprintf(buf, sizeof buf, "mode pitch %d, the owner's %d", a.TP, b.TP);      // (neither is a time slab)
     else if (c->lap_hash != owner->lap_hash) snprintf(buf, sizeof buf, "another mesh or vertex numbering (the Laplacian or the vertex masses differ)");
     if (buf[0]) { set_error(std::string("front_share: the factor does not fit this context: ") + buf); return DOTS_ERR_ARGUMENT; }
     // what every sharer reads is the owner's store; the update planes and the carried gathers are the sharer's own
@@ -1263,7 +1248,7 @@ int dots_front_share(dots_ctx *c, dots_ctx *owner) {
     c->front.W = nullptr;
     c->sched = owner->sched;
     const double *w = nullptr;
-    if ((rc = c->front_own.upload<double>(&w, nullptr, owner->sched.w_rows << c->dcg.tp_shift, c->stream))) { front_release(c); return rc; }
+    if ((rc = c->front_own.upload<double>(&w, nullptr, owner->sched.w_rows << c->d.tp_shift, c->stream))) { front_release(c); return rc; }
     c->front.W = const_cast<double *>(w);
     c->front_store = owner->front_store;
     c->front_record = owner->front_record;      // (dots_move_vertices_many refreshes the store from whichever holder is listed first)
@@ -1298,7 +1283,7 @@ int dots_laplacian_solve_many(dots_ctx *const *cs, int n, const double *const *h
         for (int k = 0; k < n; ++k) {
             Ctx *c = cs[k];
             if ((r = batch_wait(c, cs[0]))) return r;
-            if ((r = modes_inverse(c, c->dcg.cg_x, dout[k], true))) return r;
+            if ((r = modes_inverse(c, c->d.cg_x, dout[k], true))) return r;
             if ((r = launch_from_device_layout(c, DOTS_PHI, dout[k], c->stage))) return r;
             DOTS_HIP(hipMemcpyAsync(host_out[k], c->stage, sizeof(double) * (size_t)nh, hipMemcpyDeviceToHost, c->stream));
         }
@@ -1344,7 +1329,7 @@ int dots_step_many(dots_ctx *const *cs, int n, dots_step_stats *stats) {
     for (int k = 0; k < n; ++k) {
         Ctx *c = cv[k];
         if ((rc = batch_wait(c, c0))) return rc;
-        if (!plan[(size_t)k].fuse && (rc = modes_inverse(c, c->dcg.cg_x, c->d.phi, true))) return rc;
+        if (!plan[(size_t)k].fuse && (rc = modes_inverse(c, c->d.cg_x, c->d.phi, true))) return rc;
         if ((rc = iteration_after(c, plan[(size_t)k], nullptr))) return rc;
     }
     DOTS_HIP(hipGetLastError());
@@ -2263,7 +2248,7 @@ int dots_pcg_windows(dots_ctx *c, int on) {
     on = on ? 1 : 0;
     if (on == c->pcg_windows) return 0;
     // a hierarchy installed under the other setting has the other layout (level vectors and coarse inverse per window): it goes, with the graphs
-    if (c->dcg.cg_ncol > CgScalOffsets::NCMAX) {
+    if (c->d.cg_ncol > CgScalOffsets::NCMAX) {
         DOTS_HIP(hipStreamSynchronize(c->stream));
         c->cg_graphs_release();
         mg_release(c);
@@ -2291,7 +2276,7 @@ int dots_front_info(dots_ctx *c, double *out) {
 
 int dots_front_pitch(dots_ctx *c) {
     if (admit(c, E_FRONT_PITCH)) return -1;
-    return c->dcg.TP;
+    return c->d.TP;      // (the PCG view's pitch is d's)
 }
 
 int64_t dots_debug_counter(dots_ctx *c, int which) {

@@ -22,10 +22,12 @@
 #include <memory>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/dots_socp_hip.h"
 #include "admission.h"
+#include "step_choice.h"
 
 namespace dots {
 
@@ -145,30 +147,6 @@ enum {
     CG_PATH_VT_SHIFT = 8,        // vertices per tile, bits 8-19
     CG_PATH_CAP_SHIFT = 20,      // staged CSR entries per tile, bits 20-31
     CG_PATH_G_SHIFT = 32         // workgroups, from bit 32
-};
-// Launches the last iteration took (Carried::step_path, dots_debug_counter 12), recorded where launch_rhs, launch_soc_projection and
-// launch_q_lambda_mult choose: a test of one kernel variant asserts that the step ran it.  Host bookkeeping only.
-enum {
-    STEP_PATH_RHS = 1,              // k_rhs
-    STEP_PATH_RHS_MODES = 2,        // k_rhs_modes
-    STEP_PATH_RHS_MODES2 = 4,       // k_rhs_modes2
-    STEP_PATH_RHS_MFMA = 8,         // k_rhs_modes_mfma
-    STEP_PATH_RHS_CARRIED = 16,     // ... its CARRIED argument
-    STEP_PATH_RHS_DIV = 32,         // ... its DIV argument
-    STEP_PATH_SOC_RIDER = 64,       // the cone projection rode in the right-hand-side launch
-    STEP_PATH_SOC_ALONE = 128,      // ... or ran as k_soc_projection
-    STEP_PATH_QL_TRIANGLE = 256,    // k_q_lambda_mult_triangle
-    STEP_PATH_QL_TRIANGLE2 = 512,   // k_q_lambda_mult_triangle2
-    STEP_PATH_QL_CARRY = 1024,      // k_q_lambda_mult_carry
-    STEP_PATH_QL_Z_SHIFT = 11,      // the Z mode of steps 2+3 (0 read z_mid, 1 rebuild and store, 2 rebuild only), bits 11-12
-    STEP_PATH_QL_KKT = 1 << 13,     // K: the fused KKT sums
-    STEP_PATH_QL_DIV = 1 << 14,     // DIV: a pending penalty division applied
-    STEP_PATH_QL_BMNT = 1 << 15,    // BMNT: beta_mid streamed around the caches
-    STEP_PATH_QL_DEFER = 1 << 16,   // z_mid deferred (Carried::zmid)
-    STEP_PATH_RHS_MASK = 0xff, STEP_PATH_QL_MASK = 0x1ff00,
-    // Carried::deep_path, dots_debug_counter 15: which form of the launches around the direct solve ran last
-    DEEP_PATH_RHS = 1,              // k_rhs_modes2_deep took the right-hand side (and the projection riders)
-    DEEP_PATH_INVERSE = 2           // k_time_modes_tile_fast took the inverse time transform
 };
 struct MgDev {
     int nlev = 0;
@@ -326,7 +304,11 @@ struct KktFused {
 constexpr uint32_t KKT_FUSED_MASK = 1u | 2u | 8u | 64u;
 
 // What the PCG keeps between solves per set of columns it iterates on: the instantiated hipGraph of `iters` iterations (Dev is captured by
-// value, so a window of modes has its own) and the iteration count that sizes the next solve's first burst
+// value, so a window of modes has its own) and the iteration count that sizes the next solve's first burst.
+// The captured Dev is a derived view (pcg_view): it carries d's state, cn_* and halo pointers as they were at capture.  That is sound
+// because the kernels in the graph (k_cg_apply, k_cg_update, k_collapse, the k_mg_* of the V-cycle) read none of them: neither the
+// pointers the two swaps of Ctx move (zf, ze, lamc, B, bm, zm, B_st, bm_st) nor cn_sq / cn_g / cn_e / cn_lo nor a halo -- only the mesh
+// constants, sigma, the PCG vectors, partials, scal and flags (profiles/device_views/README.md has the list per view).
 struct CgCache {
     hipGraphExec_t graph = nullptr;
     int iters = 0;
@@ -346,7 +328,10 @@ int launch_soc_projection(Ctx *c, int zmid_mode = 0, bool with_inverse = false);
 void preload_alm_kernels();
 void preload_kkt_kernels();
 void preload_transform_kernels();
-int launch_rhs(Ctx *c, bool with_soc = false, double dv = 0.0);   // with_soc (only when rhs_writes_modes): the cone projection rides in the same launch; dv != 0 (only when rhs_divides): a pending penalty division is applied to what is read
+struct RhsAhead;
+// with_soc (only when rhs_writes_modes): the cone projection rides in the same launch; dv != 0 (only when rhs_divides: DOTS_ERR_STATE otherwise): a
+// pending penalty division is applied to what is read; ahead: a launch ahead of its iteration names where the rider writes and the penalty
+int launch_rhs(Ctx *c, bool with_soc = false, double dv = 0.0, const RhsAhead *ahead = nullptr);
 bool rhs_divides(const Ctx *c);
 bool ql_divides(const Ctx *c, int zmid_mode);
 int launch_q_lambda_mult(Ctx *c, int zmid_mode = 0, double dv = 0.0);    // 0: read z_mid; 1: rebuild it from the multiplier and store it; 2: rebuild, do not store; dv != 0 (only when ql_divides): the dual arrays are divided as they are read and written back divided
@@ -392,12 +377,12 @@ int front_solve_many(Ctx *const *cs, int n, const double *const *bhat, double *c
 // the time transforms around step 1's solve (kernels_modes.hip).  One GPU: b^ = Q^T `in` into `out`, and phi = Q x^ back
 void modes_forward(Ctx *c, const double *in, double *out, bool direct, bool col0_sums = true);   // col0_sums: the PCG's forms leave the partial sums of mode 0 (mean removal)
 int modes_inverse(Ctx *c, const double *x, double *phi, bool direct);
-void modes_forward_sharded(Ctx *c, bool direct);   // time slab: this rank's modes of the all-gathered right-hand side (slab.b_recv) into dcg.cg_p0
+void modes_forward_sharded(Ctx *c, bool direct);   // time slab: this rank's modes of the all-gathered right-hand side (slab.b_recv) into the PCG view's cg_p0
 int modes_forward_sums(const Ctx *c);              // partial sums of mode 0 the PCG's forward transform of this context leaves in Dev::partials (k_cg_bmean adds them)
 int modes_windows_sums(const Dev &d);              // ... of a windowed context (cg_partials_needed: they lie in front of the PCG's own)
 // enqueue z = MG(r) on the PCG view d (the context's own, or one window of it) with that view's coarse inverse; z holds D^-1 r on entry
 int mg_vcycle(Ctx *c, const Dev &d, const double *coarse_inv, const double *r, double *z, double *t0, double *rz_part, int nb, int ept, int vt, int G);
-int cg_mg_apply(Ctx *c, double *rz);        // dots_mg_apply: one V-cycle on what dcg.cg_r holds, as the PCG launches it; rz[mode] = sum of the r.z partial rows
+int cg_mg_apply(Ctx *c, double *rz);        // dots_mg_apply: one V-cycle on what the PCG view's cg_r holds, as the PCG launches it; rz[mode] = sum of the r.z partial rows
 int kkt_evaluate(Ctx *c, uint32_t mask, double *out);
 int kkt_sums(Ctx *c, uint32_t mask, double *sums);                          // the weighted sums of this context's time slab
 int kkt_sums_device(Ctx *c, uint32_t mask, double *device_sums);            // the same, left in the caller's device buffer (enqueue only)
@@ -581,18 +566,34 @@ private:
     std::vector<void *> held;
 };
 
+// What the two derived views of a context's device data hold besides `d` (pcg_view, time_view below).  Zero on one GPU, where both
+// views ARE d; on a time slab build fills them (cg_x: dots_slab_set_buffers) and nothing else writes them.
+struct PcgRecord {          // the PCG's view: this rank's mode count and sigma slice, its own vectors; same partition and pitch as the slab
+    int cg_ncol = 0;
+    const double *sigma = nullptr;
+    double *cg_r = nullptr, *cg_z = nullptr, *cg_p0 = nullptr, *cg_p1 = nullptr, *cg_Ap = nullptr;
+    double *cg_x = nullptr; // slab.x_send: the mode-space solution is written where the second all-gather reads it
+};
+struct TimeRecord {         // the transforms' view: the same pointers under the geometry of the whole time axis (pitch >= T + 1)
+    int TP = 0, tp_shift = 0, t0 = 0, nl = 0, ni = 0, slab = 0, VT = 0, FT = 0, n_vtiles = 0, n_ftiles = 0;
+};
+// Where a right-hand-side launch that runs ahead of its iteration puts what the riding projection writes (z_fst, z_end, the cone
+// multiplier), and the penalty it forms the boundary term with: laid over launch_rhs's own copy of the device data, never over the context's
+struct RhsAhead {
+    double *zf, *ze, *lamc;
+    double r;
+};
+
 struct Ctx {
-    Dev d{};
-    // The PCG's view of the device data.  Identical to `d` on one GPU.  When the time modes are sharded
-    // over ranks it has this rank's column count, its own (smaller) pitch, PCG vectors and sigma slice.
-    Dev dcg{};
+    Dev d{};                // the one stored view of the device data; pcg_view and time_view derive the other two
     // Multi-GPU: this context is one TIME SLAB of the problem.  Rank r holds the nodes [r * stride, r * stride + count) of
-    // every state array (d: local pitch, t0, nl, ni) AND solves the time modes with the same indices (dcg).
+    // every state array (d: local pitch, t0, nl, ni) AND solves the time modes with the same indices (pcg_view).
     int shard_begin = 0;    // first node = first time mode of this context
     int shard_count = 0;    // nodes = modes of this context (may be 0 on trailing ranks)
     int shard_stride = 0;   // nodes per rank (same on every rank) = layout of the gathered buffers; 0 = not sharded
     int shard_ranks = 0;    // ranks with at least one node
-    Dev dgt{};              // global-time view for the transforms of a slab context: pitch >= T + 1, Q
+    PcgRecord pcg{};
+    TimeRecord gt{};
     dots_slab_buffers slab{};     // exchange buffers (caller's device memory, dots_slab_set_buffers)
     int64_t slab_b_chunk = 0;     // doubles one rank contributes to the right-hand-side all-gather: V * pitch
     int64_t slab_x_chunk = 0;     // ... to the all-gather of the mode-space solution: V * pitch + V (the last interval's cone multipliers)
@@ -700,6 +701,22 @@ struct Ctx {
         for (CgCache *k : {&cgc, &cgw[0], &cgw[1], &cgw[2], &cgw[3]})
             if (k->graph) { (void)hipGraphExecDestroy(k->graph); k->graph = nullptr; }
     }
+    // The two places that move state pointers of `d` after build.  The taken launch ahead: the projection ran with the right-hand side
+    // (RhsAhead), its results become the current z_fst, z_end and cone multiplier
+    void swap_ahead_projection() {
+        std::swap(d.zf, zf_alt);
+        std::swap(d.ze, ze_alt);
+        std::swap(d.lamc, lamc_alt);
+    }
+    RhsAhead ahead_target(double r) const { return RhsAhead{zf_alt, ze_alt, lamc_alt, r}; }
+    // The deferred z_mid: steps 2+3 wrote the new B into B_alt and the new beta_mid into z_mid's storage.  Afterwards B_alt holds the B
+    // the projection read, z_mid's storage the beta_mid it read, and B_st == B, bm_st == bm again
+    void swap_deferred_zmid() {
+        std::swap(d.B, B_alt);
+        std::swap(d.bm, d.zm);
+        d.B_st = d.B;
+        d.bm_st = d.bm;
+    }
     double *arr(int id) {
         double *t[12] = {d.phi, d.A, d.B, d.lam, d.zf, d.zm, d.ze, d.mu, d.E, d.bf, d.bm, d.be};
         return t[id];
@@ -756,7 +773,7 @@ inline bool soc_takes_inverse(const Ctx *c) { return rhs_writes_modes(c) && !tim
 // Windowed modal PCG (dots_pcg_windows): one GPU, more than 256 modes, no enabled factor.  Mode space is then COMPACT: window k = modes
 // [256 k, 256 k + 256) of a PCG vector is a [V][256] array at base + k V 256 (the windows of a pitch-512 / 1024 array fill it exactly).
 inline bool pcg_windowed(const Ctx *c) {
-    return c->pcg_windows && c->lap_solver == DOTS_LAP_MODAL_PCG && c->shard_stride == 0 && c->dcg.cg_ncol > PCG_WINDOW &&
+    return c->pcg_windows && c->lap_solver == DOTS_LAP_MODAL_PCG && c->shard_stride == 0 && c->d.cg_ncol > PCG_WINDOW &&
            !(c->use_front && c->front.n_nodes > 0);
 }
 inline int pcg_window_count(const Dev &g) { return (g.cg_ncol + PCG_WINDOW - 1) / PCG_WINDOW; }
@@ -774,6 +791,27 @@ inline Dev pcg_window_view(const Dev &g, int k) {
     w.cg_r = g.cg_r + off; w.cg_z = g.cg_z + off; w.cg_p0 = g.cg_p0 + off; w.cg_p1 = g.cg_p1 + off; w.cg_Ap = g.cg_Ap + off; w.cg_x = g.cg_x + off;
     return w;
 }
+// The PCG's view of a context: d with the PcgRecord laid over it (one GPU: d unchanged).  By value, like pcg_window_view: it carries d's
+// pointers as they are now, whatever was swapped or installed since the record was filled.
+inline Dev pcg_view(const Ctx *c) {
+    Dev g = c->d;
+    if (c->shard_stride == 0) return g;
+    const PcgRecord &p = c->pcg;
+    g.cg_ncol = p.cg_ncol; g.sigma = p.sigma;
+    g.cg_r = p.cg_r; g.cg_z = p.cg_z; g.cg_p0 = p.cg_p0; g.cg_p1 = p.cg_p1; g.cg_Ap = p.cg_Ap; g.cg_x = p.cg_x;
+    return g;
+}
+// ... and the view of the time transforms of a slab: d with the TimeRecord laid over it (one GPU: d unchanged)
+inline Dev time_view(const Ctx *c) {
+    Dev t = c->d;
+    if (c->shard_stride == 0) return t;
+    const TimeRecord &r = c->gt;
+    t.TP = r.TP; t.tp_shift = r.tp_shift; t.t0 = r.t0; t.nl = r.nl; t.ni = r.ni; t.slab = r.slab;
+    t.VT = r.VT; t.FT = r.FT; t.n_vtiles = r.n_vtiles; t.n_ftiles = r.n_ftiles;
+    return t;
+}
+// the scalars of the PCG view a site may want alone: its mode count; its pitch is d's (PcgRecord)
+inline int pcg_ncol(const Ctx *c) { return c->shard_stride == 0 ? c->d.cg_ncol : c->pcg.cg_ncol; }
 // steps 2+3 can form the next iteration's per-corner gathers (k_q_lambda_mult_carry: whole triangles per 192-lane workgroup)
 // (one GPU or a time slab; the direct solver's iteration)
 inline bool carry_possible(const Ctx *c) {

@@ -540,59 +540,56 @@ __global__ __launch_bounds__(RHS_NB) void k_rhs_modes_mfma(Dev d, double r, doub
     modes_from_tile_mfma<RHS_NB / 64>(d, d.Qpad, xs_m, v0, bhat);
 }
 
-// the right-hand-side (+ projection) launch that launch_rhs would pick can divide the dual arrays as it reads them
-bool rhs_divides(const Ctx *c) {
-    if (!rhs_writes_modes(c) || c->carried.carry_valid) return false;
-    if (time_modes_mfma_ok(c->d)) return true;
-    return c->d.TP >= 4;
+// The facts rhs_choice decides from (step_choice.h), for a launch with or without the riding projection and a division or none
+static RhsFacts rhs_facts(const Ctx *c, bool with_soc, bool pending) {
+    const int g = xcd_grid(c->d.n_vtiles);
+    return RhsFacts{rhs_writes_modes(c), time_modes_mfma_ok(c->d), c->d.TP >= 4, c->carried.carry_valid != 0, deep_launch_wins(c, with_soc ? 2 * g : g), with_soc, pending};
 }
+// the right-hand-side (+ projection) launch that launch_rhs would pick can divide the dual arrays as it reads them
+bool rhs_divides(const Ctx *c) { return rhs_choice(rhs_facts(c, true, true)).divides; }
 
-int launch_rhs(Ctx *c, bool with_soc, double dv) {
-    const Dev &d = c->d;
+int launch_rhs(Ctx *c, bool with_soc, double dv, const RhsAhead *ahead) {
+    Dev d = c->d;
+    double r = c->prm.r;
+    if (ahead) { d.zf = ahead->zf; d.ze = ahead->ze; d.lamc = ahead->lamc; r = ahead->r; }
+    r /= c->prm.boundary_scale;
     const int g = xcd_grid(d.n_vtiles);
-    const double r = c->prm.r / c->prm.boundary_scale, eps = c->prm.eps, sz = c->prm.scale_z, cd = c->prm.const_d;
-    const bool modes = rhs_writes_modes(c), carried = c->carried.carry_valid != 0;
-    int path = with_soc ? STEP_PATH_SOC_RIDER : 0;      // (dots_debug_counter 12)
-    int deep = 0;                                       // (dots_debug_counter 15)
-    // the mode kernels' variants: 0 CARRIED (the corners' shares come from the last steps-2+3 launch), 1 DIV (a penalty update is pending: the dual
-    // arrays are divided as they are read; rhs_divides told the caller this launch can), 2 neither
-    auto modes2 = [&](int variant) {      // two time columns per lane (16-byte accesses)
-        path |= STEP_PATH_RHS_MODES2 | (variant == 0 ? STEP_PATH_RHS_CARRIED : 0) | (variant == 1 ? STEP_PATH_RHS_DIV : 0);
-        with_constant<0, 1, 2>(variant, [&](auto V) {
-            hipLaunchKernelGGL((k_rhs_modes2<V == 0, V == 1>), dim3(with_soc ? 2 * g : g), dim3(RHS_NB2), time_modes_tile_lds(d), c->stream, d, r, eps, d.cg_p0,
-                               time_modes_chunk(d), g, sz, cd, V == 1 ? dv : 1.0);
-        });
-    };
-    if (modes && time_modes_mfma_ok(d)) {      // (two time columns per lane measured here too: knot63 -1.5 %, torus65k_T127 +1.5 %: not kept)
-        const int n_tiles = (d.V + TM_ROWS - 1) / TM_ROWS, n_rhs = xcd_grid(n_tiles);
-        path |= STEP_PATH_RHS_MFMA | (carried ? STEP_PATH_RHS_CARRIED : (dv != 0.0 ? STEP_PATH_RHS_DIV : 0));
-        with_constant<0, 1, 2>(carried ? 0 : (dv != 0.0 ? 1 : 2), [&](auto V) {
-            hipLaunchKernelGGL((k_rhs_modes_mfma<V == 0, V == 1>), dim3(n_rhs + (with_soc ? g : 0)), dim3(RHS_NB), sizeof(double) * TM_ROWS * (d.TP + 1), c->stream, d, r, eps,
-                               d.cg_p0, n_rhs, n_tiles, sz, cd, V == 1 ? dv : 1.0);
-        });
-    }
-    else if (modes && carried && deep_launch_wins(c, with_soc ? 2 * g : g)) {      // the carried walks with every row in flight (pitch 8, 16, 32)
-        path |= STEP_PATH_RHS_MODES2 | STEP_PATH_RHS_CARRIED;
-        deep = DEEP_PATH_RHS;
-        with_constant<8, 16, 32>(d.TP, [&](auto TPC) {
-            hipLaunchKernelGGL((k_rhs_modes2_deep<TPC>), dim3(with_soc ? 2 * g : g), dim3(RHS_NB2), time_modes_fast_lds(d), c->stream, d, r, eps, d.cg_p0, g, sz, cd);
-        });
-    }
-    else if (modes && d.TP >= 4 && carried) modes2(0);
-    else if (dv != 0.0) modes2(1);
-    else if (modes && d.TP >= 4) modes2(2);
-    else if (modes) {
-        path |= STEP_PATH_RHS_MODES;
-        hipLaunchKernelGGL(k_rhs_modes, dim3(with_soc ? 2 * g : g), dim3(RHS_NB), time_modes_tile_lds(d), c->stream, d, r, eps, d.cg_p0, time_modes_chunk(d), g, sz, cd);
-    } else {      // (carried: a time slab of the direct solver's iteration)
-        path |= STEP_PATH_RHS | (carried ? STEP_PATH_RHS_CARRIED : 0);
-        with_constant<true, false>(carried, [&](auto CARRIED) {
-            hipLaunchKernelGGL(k_rhs<CARRIED>, dim3(with_soc ? g + g * (TILE_ELEMS / BLOCK) : g), dim3(BLOCK), 0, c->stream, d, r, eps, g, sz, cd);
-        });
+    const double eps = c->prm.eps, sz = c->prm.scale_z, cd = c->prm.const_d;
+    const RhsChoice ch = rhs_choice(rhs_facts(c, with_soc, dv != 0.0));
+    if (ch.refused) { set_error("launch_rhs: a pending penalty division was handed to a right-hand-side launch that cannot apply it"); return DOTS_ERR_STATE; }
+    const double dvk = ch.variant == RHS_DIVIDING ? dv : 1.0;
+    switch (ch.kernel) {
+        case RHS_MFMA: {      // (two time columns per lane measured here too: knot63 -1.5 %, torus65k_T127 +1.5 %: not kept)
+            const int n_tiles = (d.V + TM_ROWS - 1) / TM_ROWS, n_rhs = xcd_grid(n_tiles);
+            with_constant<RHS_CARRIED, RHS_DIVIDING, RHS_NEITHER>(ch.variant, [&](auto V) {
+                hipLaunchKernelGGL((k_rhs_modes_mfma<V == RHS_CARRIED, V == RHS_DIVIDING>), dim3(n_rhs + (with_soc ? g : 0)), dim3(RHS_NB), sizeof(double) * TM_ROWS * (d.TP + 1), c->stream,
+                                   d, r, eps, d.cg_p0, n_rhs, n_tiles, sz, cd, dvk);
+            });
+            break;
+        }
+        case RHS_MODES2_DEEP:
+            with_constant<8, 16, 32>(d.TP, [&](auto TPC) {
+                hipLaunchKernelGGL((k_rhs_modes2_deep<TPC>), dim3(with_soc ? 2 * g : g), dim3(RHS_NB2), time_modes_fast_lds(d), c->stream, d, r, eps, d.cg_p0, g, sz, cd);
+            });
+            break;
+        case RHS_MODES2:      // two time columns per lane (16-byte accesses)
+            with_constant<RHS_CARRIED, RHS_DIVIDING, RHS_NEITHER>(ch.variant, [&](auto V) {
+                hipLaunchKernelGGL((k_rhs_modes2<V == RHS_CARRIED, V == RHS_DIVIDING>), dim3(with_soc ? 2 * g : g), dim3(RHS_NB2), time_modes_tile_lds(d), c->stream, d, r, eps, d.cg_p0,
+                                   time_modes_chunk(d), g, sz, cd, dvk);
+            });
+            break;
+        case RHS_MODES:
+            hipLaunchKernelGGL(k_rhs_modes, dim3(with_soc ? 2 * g : g), dim3(RHS_NB), time_modes_tile_lds(d), c->stream, d, r, eps, d.cg_p0, time_modes_chunk(d), g, sz, cd);
+            break;
+        case RHS_PLAIN:       // (carried: a time slab of the direct solver's iteration)
+            with_constant<true, false>(ch.variant == RHS_CARRIED, [&](auto CARRIED) {
+                hipLaunchKernelGGL(k_rhs<CARRIED>, dim3(with_soc ? g + g * (TILE_ELEMS / BLOCK) : g), dim3(BLOCK), 0, c->stream, d, r, eps, g, sz, cd);
+            });
+            break;
     }
     DOTS_HIP(hipGetLastError());
-    c->carried.step_path = path;      // the first launch of an iteration: a new record
-    c->carried.deep_path = deep;
+    c->carried.step_path = ch.path;      // the first launch of an iteration: a new record (dots_debug_counter 12)
+    c->carried.deep_path = ch.deep;      // (dots_debug_counter 15)
     return 0;
 }
 
@@ -977,72 +974,63 @@ int launch_q_lambda_only(Ctx *c) {
     return 0;
 }
 
-// steps 2+3 as launch_q_lambda_mult would run them can divide the dual arrays as they read them (the carry kernels)
-bool ql_divides(const Ctx *c, int zmid_mode) {
-    return carry_possible(c) && ((c->step_carry && zmid_mode >= 1) || (c->step_kkt && zmid_mode == 1 && c->kkt_fused.part_v && !c->d.slab));
+// The facts ql_choice decides from (step_choice.h); tw, n_fwg: the carry mapping's triangles per workgroup and triangle workgroups (0 where
+// the mapping does not exist)
+static QlFacts ql_facts(const Ctx *c, int zmid_mode, bool pending, int *tw = nullptr, int *n_fwg = nullptr) {
+    const bool possible = carry_possible(c);      // (pitch 4 .. 128)
+    const int w = possible ? (2 * CARRY_NB / c->d.TP) / 3 : 0, nf = possible ? xcd_grid((c->d.F + w - 1) / w) : 0;
+    if (tw) *tw = w;
+    if (n_fwg) *n_fwg = nf;
+    return QlFacts{possible, c->step_carry != 0, c->step_kkt != 0, zmid_mode, c->kkt_fused.part_v != nullptr,
+                   xcd_grid(c->d.n_vtiles) <= c->kkt_fused_cap_v && nf <= c->kkt_fused_cap_f, c->d.slab != 0, c->step_palm != 0,
+                   c->zmid_defer && c->B_alt, c->d.TP >= 4, c->sched.bm_nt != 0, pending};
 }
+// steps 2+3 as launch_q_lambda_mult would run them can divide the dual arrays as they read them (the carry kernels)
+bool ql_divides(const Ctx *c, int zmid_mode) { return ql_choice(ql_facts(c, zmid_mode, true)).divides; }
 
 int launch_q_lambda_mult(Ctx *c, int zmid_mode, double dv) {
     const dots_params &p = c->prm;
     const int nf8 = xcd_grid(c->d.n_ftiles), nv8 = xcd_grid(c->d.n_vtiles);
     const double cd = p.const_d, cr = p.congestion * p.r;
+    int tw, n_fwg;
+    const QlChoice ch = ql_choice(ql_facts(c, zmid_mode, dv != 0.0, &tw, &n_fwg));
+    if (ch.refused) { set_error("launch_q_lambda_mult: a pending penalty division was handed to a steps-2+3 launch that cannot apply it"); return DOTS_ERR_STATE; }
     c->carried.drop_for_steps23();
-    c->carried.step_path &= ~STEP_PATH_QL_MASK;
-    // DOTS_STEP_KKT_SUMS: the launch also leaves the sums of the KKT conditions it can form from its registers (kkt_fused) and the
-    // per-corner gather of Dual(alpha) (cn_e); it takes the carry mapping (whole triangles per workgroup) whether or not the next
-    // iteration's gathers are wanted (emit)
-    const bool kkt = c->step_kkt && zmid_mode == 1 && c->kkt_fused.part_v && carry_possible(c) && !c->d.slab;
+    c->carried.step_path = (c->carried.step_path & ~STEP_PATH_QL_MASK) | ch.path;
+    if (ch.kernel == QL_TRIANGLE2) {      // two nodes per lane (16-byte accesses)
+        const dim3 g2(nf8 * (TILE_ELEMS / (2 * BLOCK)) + nv8);
+        with_constant<2, 1, 0>(ch.Z, [&](auto Z) { hipLaunchKernelGGL((k_q_lambda_mult_triangle2<Z>), g2, dim3(BLOCK), 0, c->stream, c->d, p.scale_z, p.tau, nf8, cd, cr); });
+        DOTS_HIP(hipGetLastError());
+        return 0;
+    }
+    if (ch.kernel == QL_TRIANGLE) {
+        const dim3 gf(nf8 * (TILE_ELEMS / BLOCK) + nv8);
+        with_constant<2, 1, 0>(ch.Z, [&](auto Z) { hipLaunchKernelGGL((k_q_lambda_mult_triangle<Z>), gf, dim3(BLOCK), 0, c->stream, c->d, p.scale_z, p.tau, nf8, cd, cr); });
+        DOTS_HIP(hipGetLastError());
+        return 0;
+    }
+    // k_q_lambda_mult_carry
     const KktArgs ka{KKT_FUSED_MASK, p.r, p.scale_z, p.const_d, p.congestion, p.prim_scale, p.dual_scale, p.boundary_scale};
     KktFused kf = c->kkt_fused;
     kf.nv = nv8;
-    const bool carry = carry_possible(c) && c->step_carry && zmid_mode >= 1;
-    if (carry || kkt) {      // k_q_lambda_mult_carry
-        const int tw = (2 * CARRY_NB / c->d.TP) / 3, n_fwg = xcd_grid((c->d.F + tw - 1) / tw);
-        const dim3 g(n_fwg + nv8);
-        kf.nf = n_fwg;
-        const bool k = kkt && nv8 <= c->kkt_fused_cap_v && n_fwg <= c->kkt_fused_cap_f;
-        const int emit = (carry ? 1 : 0) | (k ? 2 : 0);
-        // z_mid on demand: nothing of it is stored; the new B / beta_mid go to the alternate buffers, the old ones stay (Carried::zmid)
-        const bool defer = zmid_mode == 1 && c->zmid_defer && c->B_alt && !c->d.slab && !c->step_palm;
-        Dev dk = c->d;
-        if (defer) { dk.B_st = c->B_alt; dk.bm_st = c->d.zm; }
-        auto carry_launch = [&](int zmode, bool with_kkt) {
-            c->carried.step_path |= STEP_PATH_QL_CARRY | (zmode << STEP_PATH_QL_Z_SHIFT) | (with_kkt ? STEP_PATH_QL_KKT : 0) | (dv != 0.0 ? STEP_PATH_QL_DIV : 0) |
-                            (c->sched.bm_nt != 0 ? STEP_PATH_QL_BMNT : 0) | (defer ? STEP_PATH_QL_DEFER : 0);
-            with_constant<1, 2>(zmode, [&](auto Z) { with_constant<true, false>(with_kkt, [&](auto K) { with_constant<true, false>(dv != 0.0, [&](auto DIV) {
-                with_constant<true, false>(c->sched.bm_nt != 0, [&](auto BMNT) {
-                    hipLaunchKernelGGL((k_q_lambda_mult_carry<Z, K, DIV, BMNT>), g, dim3(CARRY_NB), 0, c->stream, dk, p.scale_z, p.tau, n_fwg, tw, cd, cr, ka, kf, DIV ? dv : 1.0, emit);
-                }); }); }); });
-        };
-        assert(!k || zmid_mode == 1);      // (kkt above: the fused sums go with a stored or deferred z_mid only)
-        carry_launch((zmid_mode == 2 || defer) ? 2 : 1, k);      // (k: only with zmid_mode 1)
-        DOTS_HIP(hipGetLastError());
-        if (defer) {
-            std::swap(c->d.B, c->B_alt);          // B_alt: the B the projection read
-            std::swap(c->d.bm, c->d.zm);          // z_mid's storage: the beta_mid it read
-            c->d.B_st = c->d.B;
-            c->d.bm_st = c->d.bm;
-            c->dcg.B = c->dgt.B = c->d.B; c->dcg.bm = c->dgt.bm = c->d.bm; c->dcg.zm = c->dgt.zm = c->d.zm;
-            c->dcg.B_st = c->dgt.B_st = c->d.B; c->dcg.bm_st = c->dgt.bm_st = c->d.bm;
-            c->carried.zmid = ZMID_DEFERRED;
-            c->zmid_dv = dv;
-            c->zmid_sz = p.scale_z;
-        }
-        c->carried.carry_valid = carry ? 1 : 0;
-        if (k) { c->kkt_fused = kf; c->carried.kkt_fused_valid = 1; }
-        return 0;
-    }
-    if (c->d.TP >= 4) {      // two nodes per lane (16-byte accesses): k_q_lambda_mult_triangle2
-        const dim3 g2(nf8 * (TILE_ELEMS / (2 * BLOCK)) + nv8);
-        c->carried.step_path |= STEP_PATH_QL_TRIANGLE2 | (zmid_mode << STEP_PATH_QL_Z_SHIFT);
-        with_constant<2, 1, 0>(zmid_mode, [&](auto Z) { hipLaunchKernelGGL((k_q_lambda_mult_triangle2<Z>), g2, dim3(BLOCK), 0, c->stream, c->d, p.scale_z, p.tau, nf8, cd, cr); });
-        DOTS_HIP(hipGetLastError());
-        return 0;
-    }
-    const dim3 gf(nf8 * (TILE_ELEMS / BLOCK) + nv8);
-    c->carried.step_path |= STEP_PATH_QL_TRIANGLE | (zmid_mode << STEP_PATH_QL_Z_SHIFT);
-    with_constant<2, 1, 0>(zmid_mode, [&](auto Z) { hipLaunchKernelGGL((k_q_lambda_mult_triangle<Z>), gf, dim3(BLOCK), 0, c->stream, c->d, p.scale_z, p.tau, nf8, cd, cr); });
+    kf.nf = n_fwg;
+    const bool k = (ch.emit & 2) != 0;
+    // z_mid on demand: nothing of it is stored; the new B / beta_mid go to the alternate buffers, the old ones stay (Carried::zmid)
+    Dev dk = c->d;
+    if (ch.defer) { dk.B_st = c->B_alt; dk.bm_st = c->d.zm; }
+    with_constant<1, 2>(ch.Z, [&](auto Z) { with_constant<true, false>(k, [&](auto K) { with_constant<true, false>(dv != 0.0, [&](auto DIV) {
+        with_constant<true, false>(c->sched.bm_nt != 0, [&](auto BMNT) {
+            hipLaunchKernelGGL((k_q_lambda_mult_carry<Z, K, DIV, BMNT>), dim3(n_fwg + nv8), dim3(CARRY_NB), 0, c->stream, dk, p.scale_z, p.tau, n_fwg, tw, cd, cr, ka, kf, DIV ? dv : 1.0, ch.emit);
+        }); }); }); });
     DOTS_HIP(hipGetLastError());
+    if (ch.defer) {
+        c->swap_deferred_zmid();
+        c->carried.zmid = ZMID_DEFERRED;
+        c->zmid_dv = dv;
+        c->zmid_sz = p.scale_z;
+    }
+    c->carried.carry_valid = ch.emit & 1;
+    if (k) { c->kkt_fused = kf; c->carried.kkt_fused_valid = 1; }
     return 0;
 }
 

@@ -467,7 +467,7 @@ static CgArgs make_args(Ctx *c, const Dev &d, bool modal) {
                  ((int64_t)a.vt << CG_PATH_VT_SHIFT) | ((int64_t)a.cap << CG_PATH_CAP_SHIFT) | ((int64_t)a.G << CG_PATH_G_SHIFT);
     return a;
 }
-static CgArgs make_args(Ctx *c, bool modal) { return make_args(c, modal ? c->dcg : c->d, modal); }
+static CgArgs make_args(Ctx *c, bool modal) { return make_args(c, modal ? pcg_view(c) : c->d, modal); }
 
 int64_t cg_partials_needed(const Dev &d) {
     int nb, ept, vt, G, collapse;
@@ -592,11 +592,11 @@ static int cg_core(Ctx *c, const Dev &d, CgCache &k, const double *coarse_inv, i
 }
 
 // Step 1 for the modes of this context.  Unsharded: also transforms back (phi is complete on return).
-// Sharded: the local mode-space solution stays in dcg.cg_x for the caller to exchange (cg_finish_sharded).
+// Sharded: the local mode-space solution stays in the PCG view's cg_x for the caller to exchange (cg_finish_sharded).
 template <bool MODAL>
 static int cg_solve_impl(Ctx *c, dots_step_stats *stats, bool defer_inverse) {
     const Dev &d = c->d;
-    const Dev &g = c->dcg;
+    const Dev g = pcg_view(c);
     const bool singular = (c->prm.eps == 0.0);
     double *x = MODAL ? g.cg_x : d.phi;
     const double *b = d.cg_b;
@@ -664,7 +664,7 @@ static int cg_solve_impl(Ctx *c, dots_step_stats *stats, bool defer_inverse) {
             if (any_open) stats->cg_not_converged += 1;
         }
     } else {
-        rc = cg_core<MODAL>(c, MODAL ? c->dcg : c->d, c->cgc, c->mg.coarse_inv, &c->last_cg_iters, b, x, stats);
+        rc = cg_core<MODAL>(c, MODAL ? g : d, c->cgc, c->mg.coarse_inv, &c->last_cg_iters, b, x, stats);
         if (MODAL) c->pcg_windows_ran = 0;
     }
     if (rc) return rc;
@@ -701,11 +701,11 @@ __global__ __launch_bounds__(BLOCK) void k_mg_entry(Dev d, double eps) {
 }
 
 // One V-cycle exactly as cg_core enqueues its first one (tests, diagnosis: dots_mg_apply; never on the product path): the caller left r in
-// dcg.cg_r and the frozen marks in dcg.flags.  z lands in dcg.cg_z; rz[mode] = the r.z partial rows the next k_cg_apply would re-reduce, summed.
+// the PCG view's cg_r and the frozen marks in its flags.  z lands in its cg_z; rz[mode] = the r.z partial rows the next k_cg_apply would re-reduce, summed.
 // Everything written here (cg_r, cg_z, cg_Ap, the parity-0 r.z rows, the level vectors, the flags) is rewritten by k_cg_r0 / k_cg_begin / the
 // first V-cycle of the next solve before it is read.
 int cg_mg_apply(Ctx *c, double *rz) {
-    const Dev &d = c->dcg;
+    const Dev d = pcg_view(c);
     const CgArgs a = make_args(c, true);
     const int64_t n = (int64_t)d.V << d.tp_shift;
     hipLaunchKernelGGL(k_mg_entry, dim3((unsigned)std::min<int64_t>((n + BLOCK - 1) / BLOCK, 4096)), dim3(BLOCK), 0, c->stream, d, a.eps);
@@ -727,7 +727,7 @@ int cg_mg_apply(Ctx *c, double *rz) {
 //   which 0: k_cg_apply (fused direction update + operator + p.Ap)     1: k_cg_update     2: one multigrid V-cycle
 int cg_bench(Ctx *c, int which, int reps, double *ms, double *bytes) {
     const bool modal = c->lap_solver == DOTS_LAP_MODAL_PCG;
-    const Dev &d = modal ? c->dcg : c->d;
+    const Dev d = modal ? pcg_view(c) : c->d;
     CgArgs a = make_args(c, modal);
     const size_t lds = cg_lds_bytes(a.cap, a.vt, a.nb);
     if (which == 4) {   // one streaming launch of known size (calibrates the PMC traffic counters)

@@ -260,7 +260,7 @@ __global__ __launch_bounds__(256) void k_fact_gmat(FactArgs g, FrontDev f) {
 // n_entries << sh doubles) receives the factor; with `zero_entries` it holds an old factor and that many entries (the original and the
 // merged blocks) are zeroed here, once the temporaries are allocated.  Host arrays: per-level node lists and the pull maps.
 int front_factorize(Ctx *c, const dots_front_desc *h, FrontDev &f, const std::vector<FrontNode> &nodes, double *T, const int *grounded_host, int64_t zero_entries) {
-    const Dev &d = c->dcg;
+    const Dev d = pcg_view(c);
     const int sh = d.tp_shift;
     int rc = 0;
     DevicePool tmp(c->device);      // (freed behind the stream synchronisation that ends the function)

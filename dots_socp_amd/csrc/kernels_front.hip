@@ -63,6 +63,8 @@ static inline FrontArgs front_args(const Dev &d) {
     const int wsh = d.tp_shift < 8 ? d.tp_shift : 8;
     return FrontArgs{d.tp_shift, d.TP, d.cg_ncol, wsh, 1 << wsh};
 }
+// ... of a context's PCG view: the pitch is d's, the mode count its own (pcg_ncol)
+static inline FrontArgs front_args(const Ctx *c) { FrontArgs g = front_args(c->d); g.ncol = pcg_ncol(c); return g; }
 static inline unsigned front_chunks(const Dev &d) { return 1u << (d.tp_shift - front_args(d).wsh); }
 
 __device__ __forceinline__ int64_t front_row(const FrontDev &f, int k) { return f.vmap ? f.vmap[k] : k; }
@@ -908,7 +910,7 @@ __global__ __launch_bounds__(256) void k_flush_read(const double *__restrict__ x
 // -2 % on the latency-bound sphere10k; with merged bands it pays there too (knot solve 53.6 -> 51.9 us, sphere10k 97 -> 95.5 us):
 // on wherever the pitch allows (DOTS_FRONT_VEC2=0 turns it off).
 static bool front_two_modes(const Ctx *c) {
-    const Dev &d = c->dcg;
+    const Dev &d = c->d;
     return c->sched.vec2 && d.TP >= 4 && d.TP <= 128;
 }
 
@@ -918,8 +920,8 @@ constexpr int FRONT_NR_1024_FWD = 2, FRONT_NR_1024 = 4;
 // one band of the forward sweep: n workgroups of nbt threads, blk rows each, kp update planes per node (NR right-hand sides: mr their vectors 1 ..)
 template <int NR>
 static void front_launch_fwd(Ctx *c, const FrontDev &f, const FrontWork *ptr, int n, int nbt, int blk, int kp, const double *bhat, double *y, const MoreRhs<NR> &mr) {
-    const Dev &d = c->dcg;
-    const FrontArgs g = front_args(d);
+    const Dev &d = c->d;      // (the PCG view has d's pitch: only its mode count differs, front_args(c))
+    const FrontArgs g = front_args(c);
     const dim3 grid(n, front_chunks(d));
     with_constant<1024, 256>(nbt, [&](auto NB) {
         if constexpr (NB == 1024 && NR > FRONT_NR_1024_FWD) c->front_cap_fault = 1;      // (front_solve_many splits such launches: never reached)
@@ -934,8 +936,8 @@ static void front_launch_fwd(Ctx *c, const FrontDev &f, const FrontWork *ptr, in
 template <int NR>
 static void front_launch_fwd_rows(Ctx *c, const FrontDev &f, const FrontWork *ptr, int n, int qw_shift, int kp, int lds_cols, const double *bhat, double *y,
                                   const MoreRhs<NR> &mr) {
-    const Dev &d = c->dcg;
-    const FrontArgs g = front_args(d);      // (a row of modes within a wavefront: one chunk)
+    const Dev &d = c->d;      // (the PCG view has d's pitch: only its mode count differs, front_args(c))
+    const FrontArgs g = front_args(c);      // (a row of modes within a wavefront: one chunk)
     const size_t lds = NR * sizeof(double) * (size_t)std::max(lds_cols, 1) * (size_t)(d.TP + FWD_ROWS_PAD);
     with_constant<0, 2, 4, 8>(kp, [&](auto KP) { with_constant<true, false>(f.vmap != nullptr, [&](auto VM) { with_constant<2, 1>(front_two_modes(c) ? 2 : 1, [&](auto VEC) {
         hipLaunchKernelGGL((k_front_fwd_rows<VM, KP, VEC, NR>), dim3(n), dim3(256), lds, c->stream, g, f, ptr, qw_shift, bhat, y, mr);
@@ -944,8 +946,8 @@ static void front_launch_fwd_rows(Ctx *c, const FrontDev &f, const FrontWork *pt
 
 template <int NR>
 static void front_launch_bwd(Ctx *c, const FrontDev &f, const FrontWork *ptr, int n, int nbt, int blk, const double *y, double *x, const MoreRhs<NR> &mr) {
-    const Dev &d = c->dcg;
-    const FrontArgs g = front_args(d);
+    const Dev &d = c->d;      // (the PCG view has d's pitch: only its mode count differs, front_args(c))
+    const FrontArgs g = front_args(c);
     const dim3 grid(n, front_chunks(d));
     with_constant<1024, 256>(nbt, [&](auto NB) {
         if constexpr (NB == 1024 && NR > FRONT_NR_1024) c->front_cap_fault = 1;
@@ -1365,7 +1367,7 @@ int group_bands(const Dev &d, const dots_front_desc *h, FrontPlan &P) {
 
 // ---- choose_shapes: the leaf-inverse precondition, the planes' buckets and W, threads and rows per workgroup of each band ------
 void choose_shapes(Ctx *c, const dots_front_desc *h, FrontPlan &P) {
-    const Dev &d = c->dcg;
+    const Dev d = pcg_view(c);
     const int nb = P.nb;
     const std::vector<Group> &groups = P.groups;
     FrontBand *const band = c->sched.band;
@@ -1574,7 +1576,7 @@ int upload_tree(Ctx *c, const FrontPlan &P, FrontDev &f0) {      // the original
     DevicePool &store = *c->front_store;
     int rc;
     if ((rc = store.upload(&f0.nodes, P.nodes.data(), (int64_t)P.nn, c->stream))) return rc;
-    if (!P.identity0 && (rc = store.upload(&f0.vmap, P.vmap0.data(), (int64_t)c->dcg.V, c->stream))) return rc;
+    if (!P.identity0 && (rc = store.upload(&f0.vmap, P.vmap0.data(), (int64_t)c->d.V, c->stream))) return rc;
     return store.upload(&f0.bd_vertex, P.bd_vertex, c->stream);
 }
 
@@ -1583,7 +1585,7 @@ int upload_tree(Ctx *c, const FrontPlan &P, FrontDev &f0) {      // the original
 // reference just factorises (laplacian_inverse_socp.py:34-41); here the caller gets a status it can act on
 // (the Python driver falls back to the multigrid-PCG) instead of a failed allocation halfway through.
 int check_memory(Ctx *c, const dots_front_desc *h, const FrontPlan &P) {
-    const Dev &d = c->dcg;
+    const Dev d = pcg_view(c);
     int64_t srows = 0;
     for (const FrontNode &nd : P.nodes) srows += (int64_t)nd.b * nd.b;
     const double per = 8.0 * (double)d.TP;
@@ -1611,7 +1613,7 @@ int check_memory(Ctx *c, const dots_front_desc *h, const FrontPlan &P) {
 
 // the factor's blocks (room for the merged ones behind them): the caller's values, or the numeric factorisation on the device (kernels_factor.hip)
 int install_factor(Ctx *c, const dots_front_desc *h, const FrontPlan &P, FrontDev &f0, const double **F) {
-    const Dev &d = c->dcg;
+    const Dev d = pcg_view(c);
     int rc;
     if ((rc = c->front_store->upload<double>(F, nullptr, (h->n_entries + P.merged_entries) << d.tp_shift, c->stream))) return rc;
     if (h->values) {
@@ -1627,7 +1629,7 @@ int install_factor(Ctx *c, const dots_front_desc *h, const FrontPlan &P, FrontDe
 
 // merged bands: one launch per tree height inside a band, children first
 int merge_bands(Ctx *c, const dots_front_desc *h, const FrontPlan &P, const double *F) {
-    const Dev &d = c->dcg;
+    const Dev d = pcg_view(c);
     const std::vector<MergeMember> &members = P.members;
     if (members.empty()) return 0;
     std::vector<int> order;                      // member records sorted by (band, tree height)
@@ -1673,7 +1675,7 @@ int merge_bands(Ctx *c, const dots_front_desc *h, const FrontPlan &P, const doub
 // S^-1 = L^-T L^-1 (k_top_inverse) of the n[k] x n[k] blocks at foff[k] of F, one after the other into `out`: full squares, or with
 // `packed` their lower triangles packed by rows.  out = null (full squares only): in place -- into a temporary, then copied over the blocks in F.
 int explicit_inverses(Ctx *c, const double *F, const std::vector<int64_t> &foff, const std::vector<int> &n, bool packed, double *out, const char *what) {
-    const Dev &d = c->dcg;
+    const Dev d = pcg_view(c);
     if (n.empty()) return 0;
     std::vector<int64_t> ooff;
     int64_t total = 0, biggest = 1;
@@ -1725,7 +1727,7 @@ int invert_top_band(Ctx *c, const FrontPlan &P, const double *F) {
 
 // the sweeps' own tables: the order of the merged tree, where the update rows land, the update planes W
 int upload_sweep_maps(Ctx *c, const FrontPlan &P, FrontDev &f) {
-    const Dev &d = c->dcg;
+    const Dev d = pcg_view(c);
     int rc;
     if (!P.identity && (rc = c->front_store->upload(&f.vmap, P.vmap.data(), (int64_t)d.V, c->stream))) return rc;
     if ((rc = c->front_store->upload(&f.cmap, P.cmap, c->stream))) return rc;
@@ -1738,7 +1740,7 @@ int upload_sweep_maps(Ctx *c, const FrontPlan &P, FrontDev &f) {
 
 // coupling records of the leaves (a row with more entries than a record holds: the kernels walk the CSR instead)
 int leaf_tables(Ctx *c, FrontDev &f, int64_t bd_rows) {
-    const Dev &d = c->dcg;
+    const Dev d = pcg_view(c);
     const LeafBdRow *dbt = nullptr;
     const LeafSepRow *dst = nullptr;
     const int *dov = nullptr;
@@ -1759,7 +1761,7 @@ int leaf_tables(Ctx *c, FrontDev &f, int64_t bd_rows) {
 
 // ---- the leaves as explicit local inverses (P.leaf_inv; w and t of the largest leaf must fit the LDS a workgroup may take)
 int install_leaves(Ctx *c, const dots_front_desc *h, FrontPlan &P, FrontDev &f) {
-    const Dev &d = c->dcg;
+    const Dev d = pcg_view(c);
     std::vector<LeafWork> leaves;
     std::vector<int64_t> foff;
     std::vector<int> n;
@@ -1839,7 +1841,7 @@ int apply_cfg(Ctx *c, const FrontPlan &P) {
 
 // DOTS_FRONT_TUNE: time every (threads, rows) choice per band and sweep on this device; prints the table (2: also applies the fastest)
 void tune_bands(Ctx *c, const dots_front_desc *h, const FrontPlan &P, const FrontDev &f) {
-    const Dev &d = c->dcg;
+    const Dev d = pcg_view(c);
     FrontBand *const band = c->sched.band;
     DevicePool tmp(c->device);      // (freed behind the stream synchronisation that ends the function)
     double *vec[3] = {nullptr, nullptr, nullptr};
@@ -1949,7 +1951,7 @@ int install_schedule(Ctx *c, const dots_front_desc *h, const FrontPlan &P, Front
         bd.bwd_first = (int)bwd.size();
         if (bd.fwd_qw >= 0) {
             bd.fwd_lds = make_fwd_rows(h, P, k, P.rows_per_wg(bd.fwd_qw), fwd);
-            if (!rows_fit_lds(c->dcg, bd.fwd_lds)) return bad("DOTS_FRONT_CFG: the row kernel does not fit a band it was forced on (its right-hand side exceeds the LDS budget)");
+            if (!rows_fit_lds(c->d, bd.fwd_lds)) return bad("DOTS_FRONT_CFG: the row kernel does not fit a band it was forced on (its right-hand side exceeds the LDS budget)");
         } else {
             make_fwd(h, P, k, bd.fwd_rb, fwd);
         }
@@ -1993,7 +1995,7 @@ struct FrontRecord {
 // The direct solver's setup: a host plan (FrontPlan) filled phase by phase, then the device work in a fixed order -- allocate, factorise,
 // merge, top inverse, W, leaf inverses, leaf tables, tuner, lists.  What a sharer of the factor reads goes into the store, W into front_own.
 int front_setup(Ctx *c, const dots_front_desc *h) {
-    const Dev &d = c->dcg;
+    const Dev d = pcg_view(c);
     FrontPlan P;
     int rc;
     if ((rc = check_desc(d, h, P))) return rc;
@@ -2050,7 +2052,7 @@ int front_setup(Ctx *c, const dots_front_desc *h) {
 static double refresh_work_bytes(const Ctx *c, const FrontRecord &R) {
     int64_t srows = 0;
     for (const FrontNode &nd : R.P.nodes) srows = std::max(srows, nd.soff + (int64_t)nd.b * nd.b);
-    return 8.0 * (double)c->dcg.TP * (double)(R.n_entries + std::max<int64_t>(srows, 1));
+    return 8.0 * (double)c->d.TP * (double)(R.n_entries + std::max<int64_t>(srows, 1));
 }
 
 int front_refresh_check(Ctx *c) {
@@ -2097,7 +2099,7 @@ int front_refresh(Ctx *c) {
     const FrontDev &f = c->front;
     if (f.n_leaves > 0 && (rc = explicit_inverses(c, F, P.leaf_foff, P.leaf_n, true, const_cast<double *>(f.leafS), "leaf inverses"))) return rc;
     if (f.n_leaves > 0 && f.leaf_bd) {
-        const Dev &d = c->dcg;
+        const Dev d = pcg_view(c);
         DevicePool tmp(c->device);      // (freed behind the stream synchronisation below)
         int *over = nullptr;
         if ((rc = tmp.alloc(&over, 1, c->stream))) return rc;
@@ -2112,15 +2114,15 @@ int front_refresh(Ctx *c) {
 
 // the leaves' band as explicit local inverses: one workgroup per leaf
 static int front_leaf_threads(const Ctx *c) {
-    const int lanes = c->dcg.TP / (front_two_modes(c) ? 2 : 1);
+    const int lanes = c->d.TP / (front_two_modes(c) ? 2 : 1);
     // (sixteen rows in flight per workgroup at every pitch -- 1024 threads at a pitch of 128 -- lose: torus65k_T127 110 / 87 -> 115 / 110 us per launch,
     // one workgroup per CU instead of four; workgroups grow only where a row of modes needs more than 256 lanes)
     return lanes <= 256 ? 256 : (lanes <= 512 ? 512 : 1024);
 }
 template <int NR>
 static void front_launch_leaves(Ctx *c, const FrontDev &f, bool forward, const double *bhat, double *x, const MoreRhs<NR> &mr) {
-    const Dev &d = c->dcg;
-    const FrontArgs g = front_args(d);      // (pitch <= 256: one chunk)
+    const Dev &d = c->d;      // (the PCG view has d's pitch: only its mode count differs, front_args(c))
+    const FrontArgs g = front_args(c);      // (pitch <= 256: one chunk)
     const size_t lds = NR * sizeof(double) * (forward ? 2 : 1) * (size_t)f.leaf_nmax * (size_t)d.TP;
     with_constant<1024, 512, 256>(front_leaf_threads(c), [&](auto NB) {
         if constexpr (NB == 1024 && NR > FRONT_NR_1024) c->front_cap_fault = 1;
@@ -2176,7 +2178,7 @@ static void many_launch(Ctx *c, const ManyView &v, size_t lds_per_rhs, int cap, 
 // both sweeps of the chunk on c's stream, band by band as the schedule says
 template <int NR>
 static void front_sweeps(Ctx *c, const FrontSchedule &s, const ManyView &v) {
-    const Dev &d = c->dcg;
+    const Dev &d = c->d;
     const int n_leaves = v.cs[0]->front.n_leaves;
     const size_t leaf_fwd = sizeof(double) * 2 * (size_t)v.cs[0]->front.leaf_nmax * (size_t)d.TP, leaf_bwd = leaf_fwd / 2;
     const int leaf_cap = front_leaf_threads(c) == 1024 ? FRONT_NR_1024 : NR;

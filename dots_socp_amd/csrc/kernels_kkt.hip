@@ -443,13 +443,8 @@ int kkt_sums(Ctx *c, uint32_t mask, double *sums) {
         if (c->carried.rhs_ahead_armed) {
             c->carried.rhs_ahead_armed = 0;
             if (rhs_writes_modes(c) && c->zf_alt) {      // ... and its cone projection, into the alternate buffers (a dropped launch leaves the state as it is)
-                Dev keep = c->d;
-                c->d.zf = c->zf_alt;
-                c->d.ze = c->ze_alt;
-                c->d.lamc = c->lamc_alt;
-                rc = launch_rhs(c, true);
-                c->d = keep;
-                if (rc) return rc;
+                const RhsAhead target = c->ahead_target(c->prm.r);
+                if ((rc = launch_rhs(c, true, 0.0, &target))) return rc;
                 c->carried.rhs_ahead = 2;
             } else {
                 if ((rc = launch_rhs(c))) return rc;
@@ -509,15 +504,8 @@ int penalty_decision_ahead(Ctx *c, uint32_t mask, const double *sums) {
     const double dv = r_new / r;          // what the driver hands to dots_adjust_penalty ...
     const double r_next = r * dv;         // ... and the penalty it then sets (solver_socp.py: r *= factor)
     if (!(dv > 0.0) || !std::isfinite(dv)) return 0;
-    Dev keep = c->d;
-    c->d.zf = c->zf_alt;
-    c->d.ze = c->ze_alt;
-    c->d.lamc = c->lamc_alt;
-    c->prm.r = r_next;
-    rc = launch_rhs(c, true, dv);
-    c->prm.r = r;
-    c->d = keep;
-    if (rc) return rc;
+    const RhsAhead target = c->ahead_target(r_next);      // (the penalty dots_set_params will set: the boundary term is formed with it)
+    if ((rc = launch_rhs(c, true, dv, &target))) return rc;
     c->carried.rhs_ahead = 3;
     c->penalty_ahead_started += 1;
     c->ahead_dv = dv;

@@ -313,9 +313,10 @@ int modes_inverse(Ctx *c, const double *x, double *phi, bool direct) {
     return 0;
 }
 
-// Time slab: the right-hand side of ALL nodes was all-gathered into slab.b_recv; this rank transforms the modes it solves, into dcg.cg_p0
+// Time slab: the right-hand side of ALL nodes was all-gathered into slab.b_recv; this rank transforms the modes it solves, into the PCG view's cg_p0
 void modes_forward_sharded(Ctx *c, bool direct) {
-    const Dev &d = c->d, &g = c->dcg, &dt = c->dgt;
+    const Dev &d = c->d;
+    const Dev g = pcg_view(c), dt = time_view(c);
     const Gathered bg{c->slab.b_recv, c->slab_b_chunk, d.tp_shift, c->shard_stride};
     if (direct && time_modes_tile_ok(dt))     // no mean removal with the direct solver: the tiled transform
         hipLaunchKernelGGL(k_time_modes_fwd_sub_tile, dim3(xcd_grid(dt.n_vtiles)), dim3(BLOCK), time_modes_tile_lds(dt), c->stream, dt, c->shard_begin,
@@ -325,10 +326,11 @@ void modes_forward_sharded(Ctx *c, bool direct) {
 }
 // phi of this slab from the mode-space solutions of all ranks (slab.x_recv = [n_ranks][V][mode pitch])
 int cg_finish_sharded(Ctx *c) {
-    const Dev &d = c->d, &dt = c->dgt;
+    const Dev &d = c->d;
+    const Dev dt = time_view(c);
     if (d.nl == 0) return 0;
     if (!time_modes_tile_ok(dt)) { set_error("time slabs need T + 1 <= 256"); return DOTS_ERR_STATE; }
-    const Gathered xg{c->slab.x_recv, c->slab_x_chunk, c->dcg.tp_shift, c->shard_stride};
+    const Gathered xg{c->slab.x_recv, c->slab_x_chunk, d.tp_shift, c->shard_stride};
     hipLaunchKernelGGL(k_time_modes_inv_gathered_tile, dim3(xcd_grid(dt.n_vtiles)), dim3(BLOCK), time_modes_tile_lds(dt), c->stream, dt, xg, d.phi,
                        d.tp_shift, d.t0, d.nl, d.phi_hi, time_modes_chunk(dt));
     DOTS_HIP(hipGetLastError());

@@ -146,9 +146,10 @@ class NumpyBuffers:
 
 class SlabGroup:
     """n time-slab contexts driven from ONE thread of one process: the exchanges are plain copies.  ``rank_class``: ``DeviceProblem``
-    (default) or ``fake_device.FakeDeviceProblem``; ``buffers``: ``TorchBuffers()`` (default) or ``NumpyBuffers()``."""
+    (default) or ``fake_device.FakeDeviceProblem``; ``buffers``: ``TorchBuffers()`` (default) or ``NumpyBuffers()``.  ``defer_buffers``: the
+    ranks get their exchange buffers only with ``set_buffers()`` (after a factor was installed, say), not here."""
 
-    def __init__(self, T, geom, n_ranks, rank_class=None, buffers=None, **kw):
+    def __init__(self, T, geom, n_ranks, rank_class=None, buffers=None, defer_buffers=False, **kw):
         if rank_class is None:
             from dots_socp_amd.device import DeviceProblem as rank_class
         self.buffers = buffers if buffers is not None else TorchBuffers()
@@ -160,9 +161,14 @@ class SlabGroup:
             nv, nf, nb, nx = (d.slab_elems(k) for k in ("vertex_halo", "triangle_halo", "b_chunk", "x_chunk"))
             b = {"send_x": z(nv), "send_nsq": z(nv), "recv_x": z(nv), "recv_nsq": z(nv), "b_send": z(nb), "b_recv": z(nb * n_ranks),
                  "x_send": z(nx), "x_recv": z(nx * n_ranks), "send_mu": z(nv), "send_b": z(nf), "recv_mu": z(nv), "recv_b": z(nf)}
-            d.slab_set_buffers(**{k: self.buffers.ptr(t) for k, t in b.items()})
             self.bufs.append(b)
+        if not defer_buffers:
+            self.set_buffers()
         self.active = self.devs[0].active_ranks
+
+    def set_buffers(self):
+        for d, b in zip(self.devs, self.bufs):
+            d.slab_set_buffers(**{k: self.buffers.ptr(t) for k, t in b.items()})
 
     def each(self, fn):
         return [fn(d) for d in self.devs]

@@ -48,7 +48,7 @@ pytestmark = pytest.mark.gpu
 MESHES = ("ops_ico1", "fan")      # closed, valence 5 (V = 12); a boundary and valences 1, 2 and 9 (V = 11)
 ALL = list(sl.PARTITIONS)
 
-# dots_debug_counter 12 (csrc/dots_dev.h: STEP_PATH_*), written out
+# dots_debug_counter 12 (csrc/step_choice.h: STEP_PATH_*), written out
 RHS, RHS_CARRIED, SOC_RIDER, SOC_ALONE, QL_TRIANGLE2, QL_CARRY, QL_BMNT = 1, 16, 64, 128, 512, 1024, 1 << 15
 Z1, Z2 = 1 << 11, 2 << 11
 
@@ -76,13 +76,16 @@ def geoms():
     return {m: sc.geometry(m) for m in MESHES}
 
 
-def device_group(T, geom, n_ranks, direct=True, eps=0.0):
-    group = sl.SlabGroup(T, geom, n_ranks)
+def device_group(T, geom, n_ranks, direct=True, eps=0.0, buffers_last=False):
+    """``buffers_last``: the exchange buffers are set after the factor is installed (ShardedAlmSolver's order), not before."""
+    group = sl.SlabGroup(T, geom, n_ranks, defer_buffers=buffers_last)
     for d in group.devs:
         if direct and d.nl:
             assert d.setup_frontal(eps=eps, leaf=4)["levels"] >= 1      # (the factor is that of K + (sigma + eps) M)
         elif not direct:
             d.set_params(cg_tol=1e-13)                              # Jacobi PCG
+    if buffers_last:
+        group.set_buffers()
     return group
 
 
@@ -228,3 +231,37 @@ def test_rank_counts_of_equal_slab_pitch_are_bit_identical(geoms):
             group.close()
     for k in sc.STATE:
         assert np.array_equal(out[0][k], out[1][k]), k
+
+
+def test_factor_and_buffers_in_either_order_are_bit_identical(geoms):
+    """The factor installed before dots_slab_set_buffers (the driver's order) and after it (this module's): direct solver, two carried
+    steps on T6x3.  The installation allocates the carried gathers (cn_sq, cn_g, cn_lo, cn_e) and the buffers set the halo pointers; the
+    PCG's and the transforms' views of a slab are derived from the context's one Dev when a launch needs them, so neither call can leave
+    a view behind the other.  After each step all twelve arrays of every rank carry the same bits and every rank took the same launches."""
+    from dots_socp_amd import _lib
+
+    partition, mesh = sl.SMALL_PITCH, "fan"
+    assert sl.partition_id(partition) == "T6x3"
+    T, n_ranks = partition
+    seen = []
+    for buffers_last in (True, False):
+        s = sl.make_oracle(T, geoms[mesh])
+        group = device_group(T, geoms[mesh], n_ranks, buffers_last=buffers_last)
+        holders = [d for d in group.devs if d.nl]
+        steps = []
+
+        def expect(dev, **_single_context_bits):
+            steps.append(([d.debug_counter(_lib.STEP_PATH_COUNTER) for d in holders], [{k: d.download(k) for k in sc.STATE} for d in holders]))
+
+        try:
+            sl.run_scenario(group, "carry", s, partition, sl.seed_for(mesh, partition), expect=expect)
+        finally:
+            group.close()
+        assert len(steps) == 2 and all(p & QL_CARRY for p in steps[0][0]) and all(p & RHS_CARRIED for p in steps[1][0])
+        seen.append(steps)
+    for (paths_a, ranks_a), (paths_b, ranks_b) in zip(*seen):
+        assert paths_a == paths_b
+        assert len(ranks_a) == len(ranks_b) == 3
+        for a, b in zip(ranks_a, ranks_b):
+            for k in sc.STATE:
+                assert a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes(), k
