@@ -599,6 +599,7 @@ int dots_create(const dots_problem_desc *desc, dots_ctx **out) {
     preload_transform_kernels();
     preload_readout_kernels();
     preload_restart_kernels();
+    preload_barycenter_kernels();
     preload_geometry_kernels();
     *out = c.release();
     return 0;
@@ -2230,6 +2231,78 @@ int dots_sensitivity(dots_ctx *c, const dots_sensitivity_desc *desc) {
     }
     if (!on_device) c->d2h_bytes += (int64_t)sizeof(double) * ((desc->phi0 ? V : 0) + (desc->phiT ? V : 0) + (desc->stress ? 18 * F : 0));
     return 0;
+}
+
+// ---- dots_barycenter_update: takes no context (include/dots_socp_hip.h) ----------------------------------------------------------
+static int64_t bary_scratch(int64_t V, int64_t *o_mean, int64_t *o_part, int64_t *o_out) {
+    const int G = barycenter_workgroups((int)V);
+    *o_mean = (V + 1) & ~(int64_t)1;
+    *o_part = *o_mean + BARY_MAX_N;
+    *o_out = *o_part + 6 * (int64_t)G;
+    return *o_out + 4;
+}
+
+int64_t dots_barycenter_scratch(int32_t n_vertices) {
+    int64_t a, b, c;
+    return n_vertices < 1 ? -1 : bary_scratch(n_vertices, &a, &b, &c);
+}
+
+int dots_barycenter_update(const dots_barycenter_desc *desc) {
+    if (!desc || !desc->phi0 || !desc->weights || !desc->nu || !desc->scalars || !desc->scratch) { set_error("barycenter_update: null argument"); return DOTS_ERR_ARGUMENT; }
+    if (desc->n < 1 || desc->n > BARY_MAX_N) { set_error("barycenter_update: n must be 1 .. 16"); return DOTS_ERR_ARGUMENT; }
+    if (desc->n_vertices < 1) { set_error("barycenter_update: n_vertices must be positive"); return DOTS_ERR_ARGUMENT; }
+    for (int k = 0; k < desc->n; ++k) {
+        if (!desc->phi0[k]) { set_error("barycenter_update: a null potential"); return DOTS_ERR_ARGUMENT; }
+        if (!std::isfinite(desc->weights[k])) { set_error("barycenter_update: a weight that is not finite"); return DOTS_ERR_ARGUMENT; }
+    }
+    if (!std::isfinite(desc->eta) || !std::isfinite(desc->mass)) { set_error("barycenter_update: eta and mass must be finite"); return DOTS_ERR_ARGUMENT; }
+    const int64_t V = desc->n_vertices;
+    if (desc->vertex_row && !desc->nu_device_order) { set_error("barycenter_update: vertex_row without nu_device_order"); return DOTS_ERR_ARGUMENT; }
+    int64_t o_mean, o_part, o_out;
+    const int64_t total = bary_scratch(V, &o_mean, &o_part, &o_out);
+    auto overlap = [](const double *a, int64_t na, const double *b, int64_t nb) { return a < b + nb && b < a + na; };
+    if ((desc->nu_device_order && overlap(desc->nu_device_order, V, desc->nu, V)) || overlap(desc->scratch, total, desc->nu, V)
+        || (desc->nu_device_order && overlap(desc->scratch, total, desc->nu_device_order, V))) {
+        set_error("barycenter_update: nu, nu_device_order and scratch overlap");
+        return DOTS_ERR_ARGUMENT;
+    }
+    DOTS_HIP(hipSetDevice(desc->device));
+    hipStream_t stream = static_cast<hipStream_t>(desc->stream);
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    auto enqueue = [&]() -> int {
+        BaryArgs a{};
+        for (int k = 0; k < desc->n; ++k) {
+            a.phi[k] = desc->phi0[k];
+            a.w[k] = desc->weights[k];
+        }
+        a.eta = desc->eta; a.mass = desc->mass;
+        a.nu = desc->nu; a.nu_dev = desc->nu_device_order; a.inv_v = desc->vertex_row;
+        a.y = desc->scratch; a.mean = desc->scratch + o_mean; a.part = desc->scratch + o_part; a.out = desc->scratch + o_out;
+        a.n = desc->n; a.V = (int)V; a.G = barycenter_workgroups((int)V);
+        if (desc->ms) {
+            DOTS_HIP(hipEventCreate(&ev[0]));
+            DOTS_HIP(hipEventCreate(&ev[1]));
+            DOTS_HIP(hipEventRecord(ev[0], stream));
+        }
+        int r = launch_barycenter(stream, a);
+        if (r) return r;
+        if (desc->ms) DOTS_HIP(hipEventRecord(ev[1], stream));
+        // (pageable host memory: the copy is complete when the stream is idle, which the call waits for below)
+        DOTS_HIP(hipMemcpyAsync(desc->scalars, a.out, 4 * sizeof(double), hipMemcpyDeviceToHost, stream));
+        return 0;
+    };
+    int rc = enqueue();      // (every path out of the call waits for the stream first: the kernels use the caller's arrays)
+    const hipError_t es = hipStreamSynchronize(stream);
+    if (!rc && es != hipSuccess) rc = hip_fail(es, "hipStreamSynchronize", __FILE__, __LINE__);
+    if (!rc && desc->ms) {
+        float t = 0.f;
+        const hipError_t et = hipEventElapsedTime(&t, ev[0], ev[1]);
+        if (et != hipSuccess) rc = hip_fail(et, "hipEventElapsedTime", __FILE__, __LINE__);
+        *desc->ms = t;
+    }
+    for (hipEvent_t e : ev)
+        if (e) (void)hipEventDestroy(e);
+    return rc;
 }
 
 int dots_front_enable(dots_ctx *c, int on) {

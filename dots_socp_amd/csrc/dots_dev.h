@@ -424,6 +424,26 @@ int launch_restart_scale(Ctx *c, const double factor[4], double *bytes);
 // sum over v of (mu0[v]^2 + mu1[v]^2) / mass_v[v] of two DEVICE arrays in a fixed order, left in *out on the host (waits for the stream)
 int restart_boundary_sum(Ctx *c, const double *mu0, const double *mu1, double *out);
 void preload_restart_kernels();
+// dots_barycenter_update (kernels_barycenter.hip): nu <- nu * exp(-eta * sum_k w_k * (-(phi_k - mean_k))), renormalised to `mass`, in
+// four launches on the caller's stream.  Every array in the CALLER's numbering except nu_dev (a second one); scratch from the caller.
+constexpr int BARY_MAX_N = 16;                 // dots_barycenter_desc.n
+constexpr int BARY_MAX_WORKGROUPS = 1024;      // of the update and the finish: the partial sums one workgroup folds
+struct BaryArgs {
+    const double *phi[BARY_MAX_N];      // [n] potentials, [V] each
+    double w[BARY_MAX_N];
+    double eta, mass;
+    double *nu;                  // [V], updated in place
+    double *nu_dev;              // [V] the same values in a second numbering, or null
+    const int *inv_v;            // caller vertex -> row of nu_dev, or null (same numbering)
+    double *y;                   // scratch [V]
+    double *mean;                // scratch [BARY_MAX_N]
+    double *part;                // scratch [6][G]
+    double *out;                 // [4] sum, change, gmax, min
+    int n, V, G;                 // G = barycenter_workgroups(V)
+};
+int barycenter_workgroups(int V);
+int launch_barycenter(hipStream_t stream, const BaryArgs &a);
+void preload_barycenter_kernels();
 
 // ---- dots_move_vertices (kernels_geometry.hip): the geometry tables from vertex positions, dots_assemble's and dots_create's bits
 struct GeomScratch {

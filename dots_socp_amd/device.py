@@ -504,16 +504,21 @@ class DeviceProblem:
         return ms
 
     # ---- solve session: the next problem on this context
-    def restart(self, mu0, mu1, mode="cold", factors=None, device_pointers=False):
+    def restart(self, mu0, mu1, mode="cold", factors=None, device_pointers=False, device_order=False):
         """Take the end masses of another problem on the same surface and start over on the live context (dots_restart): the factor,
         the hierarchy and every allocation are kept, the parameters go back to a new context's (``self.params`` is read again).
         ``mode="cold"``: the state is zeroed; ``"warm"``: every state array is multiplied in place by its entry of ``factors``, the
         four of ``AlmSolver.recovery_factors()`` -- the bits that downloading, ``recovered`` and ``init_solution=`` leave.  ``mu0`` /
         ``mu1`` (V,) in the caller's numbering: arrays, or with ``device_pointers`` torch tensors on the context's device (permuted
         there; nothing crosses to the host except that ``self.plan``'s copies are refreshed for ``_initial_constant_scaling``).
+        ``device_order`` (with ``device_pointers``): the tensors are in the CONTEXT's vertex numbering already, where
+        ``barycenter_update`` writes ``nu_device_order``: they are read as they are, nothing is permuted and nothing is copied to the
+        host -- ``self.plan`` then holds no end masses (None), and a run that reads them there (``is_constant_scaling``) cannot start.
         Returns the device milliseconds of the call."""
         if self.slab:
             raise ValueError("restart: not available on time slabs")
+        if device_order and not device_pointers:
+            raise ValueError("restart: device_order is for tensors on the device (device_pointers)")
         if mode not in ("cold", "warm"):
             raise ValueError("restart: mode must be 'cold' or 'warm'")
         if mode == "warm" and (factors is None or len(factors) != 4):
@@ -529,10 +534,10 @@ class DeviceProblem:
                 if not isinstance(a, torch.Tensor) or a.device != where or a.dtype != torch.float64 or tuple(a.shape) != (self.V,):
                     raise ValueError(f"restart: {name} must be a float64 tensor of shape ({self.V},) on {where}")
                 a = a.detach()
-                dev.append((a if perm is None else a[torch.as_tensor(perm, device=where, dtype=torch.int64)]).contiguous())
+                dev.append((a if perm is None or device_order else a[torch.as_tensor(perm, device=where, dtype=torch.int64)]).contiguous())
             torch.cuda.current_stream(where).synchronize()      # (the call reads them on the context's stream)
             d.mu0, d.mu1 = dev[0].data_ptr(), dev[1].data_ptr()
-            host = [t.cpu().numpy() for t in dev]
+            host = [None, None] if device_order else [t.cpu().numpy() for t in dev]
         else:
             host = []
             for name, a in (("mu0", mu0), ("mu1", mu1)):
@@ -553,6 +558,24 @@ class DeviceProblem:
         _lib.check(self.lib.dots_get_params(self._h, C.byref(self.params)), "dots_get_params")
         self.restart_ms = ms.value
         return ms.value
+
+    def barycenter_update(self, potentials, weights, eta, mass, nu, nu_device_order=None):
+        """One mirror-descent step of a barycentre on this context's surface and device (``barycenter_update`` below with the
+        context's vertex numbering): ``nu_device_order`` receives ``nu`` in the numbering ``restart(device_pointers=True,
+        device_order=True)`` reads.  The context itself is not involved -- the library call takes none --: its iterate, parameters and
+        stream are untouched.  ``self.barycenter_ms``: device milliseconds of the launches."""
+        if self.slab:
+            raise ValueError("barycenter_update: not available on time slabs")
+        import torch
+
+        if getattr(self, "_vertex_row", None) is None:      # caller vertex -> row of the context's numbering: the inverse of perm_vert
+            perm = self.plan.perm_vert
+            row = np.arange(self.V, dtype=np.int32)
+            if perm is not None:
+                row[np.asarray(perm, dtype=np.int64)] = np.arange(self.V, dtype=np.int32)
+            self._vertex_row = torch.as_tensor(row, device=torch.device("cuda", self.device))
+        scalars, self.barycenter_ms = barycenter_update(potentials, weights, eta, mass, nu, nu_device_order, self._vertex_row)
+        return scalars
 
     def move_vertices(self, vertices, device_pointers=False):
         """Move the vertices of the live context to ``vertices`` (V, 3), caller's numbering (dots_move_vertices): every geometry table
@@ -1050,3 +1073,47 @@ def bench_many(problems, reps=20):
     ms = C.c_double()
     _lib.check(problems[0].lib.dots_bench_many(hs, len(problems), int(reps), C.byref(ms)), "dots_bench_many")
     return ms.value
+
+
+
+_barycenter_scratch = {}      # (device ordinal, V) -> the scratch tensor of dots_barycenter_update
+
+
+def barycenter_update(potentials, weights, eta, mass, nu, nu_device_order=None, vertex_row=None):
+    """One mirror-descent step of a barycentre on the device (dots_barycenter_update, which takes no context;
+    ``barycenter.update_host`` is the specification): ``nu`` (V,), a contiguous float64 tensor on a GPU, is updated in place from the
+    ``potentials`` -- a list of 1 to 16 such tensors, ``phi0`` of each problem as ``sensitivity(to_device=True)`` left it --,
+    ``weights``, ``eta`` and the total ``mass``, on torch's current stream of that device.  ``nu_device_order``: None, or a tensor that
+    receives ``nu_device_order[vertex_row[v]] = nu[v]``; ``vertex_row``: an int32 tensor (V,) on the device, or None (the identity).
+    Returns ``({"sum", "change", "gmax", "min"}, device milliseconds of the launches)``."""
+    import torch
+
+    if not isinstance(nu, torch.Tensor) or not nu.is_cuda or nu.ndim != 1:
+        raise ValueError("barycenter_update: nu must be a float64 tensor of shape (V,) on a GPU")
+    where, V = nu.device, int(nu.shape[0])
+    for a in list(potentials) + [nu] + ([] if nu_device_order is None else [nu_device_order]):
+        if not isinstance(a, torch.Tensor) or a.device != where or a.dtype != torch.float64 or tuple(a.shape) != (V,) or not a.is_contiguous():
+            raise ValueError(f"barycenter_update: potentials, nu and nu_device_order must be contiguous float64 tensors of shape ({V},) on {where}")
+    if vertex_row is not None and (not isinstance(vertex_row, torch.Tensor) or vertex_row.device != where or vertex_row.dtype != torch.int32
+                                   or tuple(vertex_row.shape) != (V,) or not vertex_row.is_contiguous()):
+        raise ValueError(f"barycenter_update: vertex_row must be a contiguous int32 tensor of shape ({V},) on {where}")
+    n = len(potentials)
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if w.shape != (n,):
+        raise ValueError(f"barycenter_update: weights must have shape ({n},), got {w.shape}")
+    lib = _lib.load()
+    key = (where.index, V)
+    if key not in _barycenter_scratch:
+        _barycenter_scratch[key] = torch.empty(int(lib.dots_barycenter_scratch(V)), dtype=torch.float64, device=where)
+    pointers = (C.c_void_p * max(n, 1))(*[a.data_ptr() for a in potentials])
+    scalars, ms = np.empty(4), C.c_double()
+    d = _lib.BarycenterDesc()
+    d.n, d.device, d.n_vertices = n, where.index, V
+    d.phi0, d.weights = pointers, _ptr(w, C.c_double)
+    d.eta, d.mass = float(eta), float(mass)
+    d.nu, d.nu_device_order = nu.data_ptr(), None if nu_device_order is None else nu_device_order.data_ptr()
+    d.vertex_row = None if vertex_row is None or nu_device_order is None else vertex_row.data_ptr()
+    d.scratch, d.stream = _barycenter_scratch[key].data_ptr(), torch.cuda.current_stream(where).cuda_stream
+    d.scalars, d.ms = _ptr(scalars, C.c_double), C.pointer(ms)
+    _lib.check(lib.dots_barycenter_update(C.byref(d)), "dots_barycenter_update")
+    return {"sum": float(scalars[0]), "change": float(scalars[1]), "gmax": float(scalars[2]), "min": float(scalars[3])}, ms.value

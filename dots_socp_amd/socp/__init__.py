@@ -13,6 +13,9 @@
 ``SolveSession``   one live context and one factor for a sequence of problems on one surface whose end masses change:
                    ``with SolveSession(n_time, geometry, **options) as s: solution, hist = s.solve(mu0, mu1, warm=True)`` (dots_restart)
 
+``barycenter``     the Wasserstein barycentre of several measures on one surface, iterated on the device over one ``BatchSession``:
+                   ``socp.barycenter(n_time, geometry, measures, weights)`` (dots_barycenter_update; ``dots_socp_amd.barycenter``)
+
 Both take ``(n_time, geometry, **kwargs)`` and return ``(solution, run_history)``; they can be
 passed as ``solver=`` to the reference's ``run_dot_surface`` (interface.py:106-134).
 
@@ -33,10 +36,11 @@ not with congestion.
 import numpy as np
 
 from ..sensitivity import check_sensitivity
-from .solver_socp import (BatchSession, SolveSession, check_flow_map, solver_socp, solver_socp_auto_cascade, solver_socp_cascade, solver_socp_many,
+from .solver_socp import (BatchSession, DeviceOrdered, SolveSession, barycenter, check_flow_map, solver_socp, solver_socp_auto_cascade, solver_socp_cascade, solver_socp_many,
                           solver_socp_mesh_cascade, solver_socp_spacetime_cascade)
 
 __all__ = ["solver_socp", "solver_raw", "solver", "solver_socp_many", "solver_raw_many", "solver_many", "SolveSession", "BatchSession",
+           "barycenter", "DeviceOrdered",
            "solver_socp_cascade", "solver_raw_cascade", "solver_cascade",
            "solver_socp_mesh_cascade", "solver_raw_mesh_cascade", "solver_mesh_cascade",
            "solver_socp_spacetime_cascade", "solver_raw_spacetime_cascade", "solver_spacetime_cascade",

@@ -929,8 +929,11 @@ class AlmSolver:
         if batch_member and vertices is not None:
             raise ValueError("restart: a member of a batch moves with all holders of its factor (BatchSession.solve_many(vertices=))")
         V = int(np.asarray(self.geometry["vertices"]).shape[0])
-        on_device = _is_device_tensor(mu0) and _is_device_tensor(mu1)      # (one of each: both are read on the host)
+        ordered = isinstance(mu0, DeviceOrdered) or isinstance(mu1, DeviceOrdered)      # (in the context's numbering: read as they lie)
+        on_device = ordered or (_is_device_tensor(mu0) and _is_device_tensor(mu1))      # (one of each: both are read on the host)
         masses = _end_masses("restart", mu0, mu1, V, to_host=not on_device)
+        if ordered and self.is_constant_scaling:
+            raise ValueError("restart: is_constant_scaling reads the end masses on the host: not with masses in the context's numbering (DeviceOrdered)")
         if warm and self._warm_refusal():
             raise ValueError(self._warm_refusal())
         factors = self.recovery_factors() if warm else None
@@ -940,11 +943,15 @@ class AlmSolver:
                 given = vertices if _is_device_tensor(vertices) else _host_array(vertices)
                 self.move_ms = self.dev.move_vertices(given, device_pointers=_is_device_tensor(given))
                 self._geometry_moved(np.array(_host_array(given)))
-        ms = self.dev.restart(masses[0], masses[1], "warm" if warm else "cold", factors, device_pointers=on_device)
-        if on_device:      # (the plan's host copies, back in the caller's numbering: read_out and flow_map take the end masses from the geometry)
-            order = self._caller_order()
-            masses = [self.dev.plan.mu0[order], self.dev.plan.mu1[order]]
-        self.geometry = {**self.geometry, "mu0": np.array(masses[0]), "mu1": np.array(masses[1])}
+        if ordered:      # (nothing crosses to the host: the solver holds no copy of these masses)
+            ms = self.dev.restart(masses[0].tensor, masses[1].tensor, "warm" if warm else "cold", factors, device_pointers=True, device_order=True)
+            self.geometry = _without_masses(self.geometry)
+        else:
+            ms = self.dev.restart(masses[0], masses[1], "warm" if warm else "cold", factors, device_pointers=on_device)
+            if on_device:      # (the plan's host copies, back in the caller's numbering: read_out and flow_map take the end masses from the geometry)
+                order = self._caller_order()
+                masses = [self.dev.plan.mu0[order], self.dev.plan.mu1[order]]
+            self.geometry = {**self.geometry, "mu0": np.array(masses[0]), "mu1": np.array(masses[1])}
         if nit is not None:
             self.nit = int(nit)
         if time_limit is not None:
@@ -1043,6 +1050,17 @@ def _is_device_tensor(a):
     return type(a).__module__.startswith("torch") and bool(getattr(a, "is_cuda", False))
 
 
+class DeviceOrdered:
+    """An end mass that lies on the context's device in the CONTEXT's vertex numbering (``plan.perm_vert`` applied): ``tensor``, a
+    float64 tensor of shape (V,), as ``DeviceProblem.barycenter_update`` writes ``nu_device_order``.  ``AlmSolver.restart`` and
+    ``BatchSession.solve_many`` read such masses where they lie -- no permutation, no copy to the host --, so the solver then holds
+    no host copy of its end masses: ``geometry`` has none, and what needs one (``read_out``, ``flow_map``, ``is_constant_scaling``) is
+    not available for that solve.  Only a live context takes them (a restart), and both masses of a problem must be of this kind."""
+
+    def __init__(self, tensor):
+        self.tensor = tensor
+
+
 def _host_array(a):
     """``a``, an array or a torch tensor wherever it lives, as a float64 array on the host"""
     return np.asarray(a.detach().cpu().numpy() if type(a).__module__.startswith("torch") else a, dtype=np.float64)
@@ -1057,6 +1075,13 @@ def _end_masses(who, mu0, mu1, V, to_host):
     """The end masses as a driver takes them: float64 host arrays of shape (V,) with finite entries; a tensor on a device passes as it
     is, checked for its shape alone (its entries are the caller's business), unless ``to_host``.  ``who`` opens the messages."""
     out = []
+    if isinstance(mu0, DeviceOrdered) or isinstance(mu1, DeviceOrdered):
+        if to_host or not (isinstance(mu0, DeviceOrdered) and isinstance(mu1, DeviceOrdered)):
+            raise ValueError(f"{who}: masses in the context's numbering (DeviceOrdered) are for a restart of a live context, both of them")
+        for name, a in (("mu0", mu0), ("mu1", mu1)):
+            if not _is_device_tensor(a.tensor) or tuple(a.tensor.shape) != (V,):
+                raise ValueError(f"{who}: {name} must hold a tensor of shape ({V},) on the context's device")
+        return [mu0, mu1]
     for name, a in (("mu0", mu0), ("mu1", mu1)):
         if to_host or not _is_device_tensor(a):
             a = _host_array(a)
@@ -1477,7 +1502,8 @@ class BatchSession(_Session):
                     if k not in self.default_masses:
                         raise ValueError(f"BatchSession.solve_many: problem {i} has no {k}")
                     p[k] = self.default_masses[k]
-            p["mu0"], p["mu1"] = _end_masses(f"BatchSession.solve_many: problem {i}", p["mu0"], p["mu1"], self.n_vertices, to_host=True)
+            ordered = isinstance(p["mu0"], DeviceOrdered) or isinstance(p["mu1"], DeviceOrdered)      # (read where they lie, by a restart)
+            p["mu0"], p["mu1"] = _end_masses(f"BatchSession.solve_many: problem {i}", p["mu0"], p["mu1"], self.n_vertices, to_host=not ordered)
             p = {**BATCH_SOLVE_DEFAULTS, **p}
             _validate_checkpoints(p["tol_checkpoints"], p["tol"])
             if int(p["nit"]) < 1:
@@ -1509,6 +1535,8 @@ class BatchSession(_Session):
         run = {k: p[k] for k in SESSION_SOLVE_KEYS}
         alm, restart_ms = self.solvers[slot], None
         built = alm is None
+        if built and isinstance(p["mu0"], DeviceOrdered):
+            raise ValueError("BatchSession.solve_many: masses in the context's numbering (DeviceOrdered) need a slot that holds a context: solve with host masses first")
         if built:
             if self.base is None:
                 self.base = _base_plan(self.n_time, self.geometry, p, self.solver_kw)
@@ -1534,6 +1562,8 @@ class BatchSession(_Session):
         ``vertices`` (V, 3; an array or a tensor on the contexts' device): the surface moves before the solves, same triangles: every
         live context takes the positions and the shared factor is refreshed once (``device.move_vertices_many``); contexts created
         later are built on the moved plan; ``self.geometry`` follows.  On the first call they replace the session's positions.
+        A problem whose ``mu0`` and ``mu1`` are both ``DeviceOrdered`` (tensors on the device in the contexts' vertex numbering) is
+        taken by its slot's restart where the masses lie, with no copy to the host; its slot must hold a context already.
         ``outputs``, ``read_out``, ``flow_map``, ``sensitivity``: as for ``solver_socp_many``.
         ``run_history.solver_stats["batch"]`` as ``solver_socp_many`` writes it; ``solver_stats["session"]`` = {"index" (problems the
         session admitted before this one), "warm", "restart_ms" (None where the context was built for this problem), "setup_seconds",
@@ -1902,3 +1932,96 @@ def solver_socp_auto_cascade(n_time, geometry, coarse_levels=2, ratio=4.0, locat
         solution, hist = solver_socp_mesh_cascade(n_time, geometries, level_tol=level_tol, read_out=read_out, flow_map=flow_map, sensitivity=sensitivity, **opts)
     hist.solver_stats["auto_cascade"] = {"levels": records, "build_seconds": build}
     return solution, hist
+
+
+# ---- Wasserstein barycentres: mirror descent over one batch session, iterated on the device -------------------------------------------
+BARYCENTER_SOLVE_KEYS = ("tol", "nit", "congestion")      # per problem, the same for all K
+
+
+def barycenter(n_time, geometry, measures, weights=None, steps=20, eta=100.0, tol_change=None, init=None, to_device=False, **options):
+    """The Wasserstein barycentre ``nu`` of ``measures`` on the surface of ``geometry``: the minimiser of ``sum_k w_k cost(nu, mu_k)``,
+    by mirror descent on the simplex (``dots_socp_amd.barycenter``: ``barycenter_host`` is this loop on the host, ``update_host`` the
+    specification of the update).  ``measures``: (K, V) or a list of K arrays (V,) of one total mass, 1 <= K <= 16; ``weights`` (K,),
+    default ``1 / K`` -- with two measures and the weights ``(1 - t, t)`` the displacement interpolation at ``t``.
+
+    One ``BatchSession`` carries the loop.  Per outer step the K problems ``(nu -> mu_k)`` are solved together (``solve_many``: cold
+    in step 0, from their last iterates afterwards), their potentials at the first end are read out on the device
+    (``sensitivity(to_device=True)``), ``DeviceProblem.barycenter_update`` (dots_barycenter_update, a call without a context) moves ``nu`` where it lies, and
+    the next solves restart from it there (``DeviceOrdered``).  From step 1 on only scalars cross to the host: the residuals and
+    costs of the solves, the four scalars of the update.  The costs of step s belong to the ``nu`` before its update; if the
+    objective of step s exceeds that of step s - 1, ``eta`` is halved for the updates from step s on.  Ends after ``steps`` steps or
+    when ``change < tol_change * mass``.
+
+    ``init`` (V,): the start, every entry positive (a multiplicative update cannot create support); default ``0.5 * sum_k w_k mu_k +
+    0.5 * mass * area_vertices / sum(area_vertices)``.  ``eta`` = 100 suits masses of total 1 on a surface of diameter about 1: the
+    potentials scale with the squared distances, and ``eta * gmax`` (``solver_stats["updates"]``) of order 1 is the working range.
+    ``options``: those of ``BatchSession`` (``max_batch`` and ``slots`` default to K) and ``tol``, ``nit``, ``congestion`` of every solve.
+
+    Returns ``{"nu" (V,) (a torch tensor on the device with ``to_device``), "objective" [per step], "change" [per step], "costs" (K,)
+    of the last step, "eta" [per step], "iterations" [per step, summed over the K problems], "solver_stats": {"updates" [per step:
+    sum, change, gmax, min], "update_ms" [per step], "solve_seconds" and "step_seconds" [per step], "bytes_to_host" [per step:
+    dots_debug_counter 9 of the session's contexts and the 32 bytes of the update's scalars], "session" (of the last solves)}}``."""
+    import torch
+
+    from .. import barycenter as bary
+    from . import _geometry_with_areas
+
+    who = "barycenter"
+    if not isinstance(geometry, dict) or "vertices" not in geometry or "triangles" not in geometry:
+        raise ValueError(f"{who}: geometry must be a dict with 'vertices' and 'triangles'")
+    V = int(np.asarray(geometry["vertices"]).shape[0])
+    m, w, mass = bary.check_measures(who, measures, weights, V)
+    K = m.shape[0]
+    if int(steps) < 1:
+        raise ValueError(f"{who}: steps must be at least 1")
+    if not (math.isfinite(float(eta)) and float(eta) >= 0.0):
+        raise ValueError(f"{who}: eta must be finite and not negative")
+    if options.get("is_constant_scaling"):
+        raise ValueError(f"{who}: is_constant_scaling reads the end masses on the host: not available")
+    per_solve = {k: options.pop(k) for k in BARYCENTER_SOLVE_KEYS if k in options}
+    session_kw = {"max_batch": K, "slots": K, **options}
+    g = _geometry_with_areas(geometry)
+    nu0 = bary.default_start(m, w, g["area_vertices"], mass) if init is None else _host_array(init)
+    nu0 = bary.check_start(who, nu0, V)
+    request = {"potentials": True, "stress": False, "to_device": True}
+    rule = bary.StepRule(eta)
+    out = {"objective": [], "change": [], "eta": [], "iterations": [], "costs": None}
+    stats = {"updates": [], "update_ms": [], "solve_seconds": [], "step_seconds": [], "bytes_to_host": []}
+    with BatchSession(n_time, _without_masses(g), **session_kw) as bs:
+        nu = nu_ordered = targets = dev = None
+        for step in range(int(steps)):
+            t0 = time.perf_counter()
+            copied = sum(alm.dev.debug_counter(9) for alm in bs._live())
+            if step == 0:
+                problems = [{"mu0": nu0, "mu1": m[k], **per_solve} for k in range(K)]
+            else:
+                problems = [{"mu0": DeviceOrdered(nu_ordered), "mu1": DeviceOrdered(targets[k]), **per_solve} for k in range(K)]
+            results = bs.solve_many(problems, warm=step > 0, outputs=(), sensitivity=request)
+            stats["solve_seconds"].append(time.perf_counter() - t0)
+            if step == 0:      # the masses move to the device once: nu in the caller's numbering, the targets in the contexts'
+                dev = bs.solvers[0].dev
+                where = torch.device("cuda", dev.device)
+                perm = dev.plan.perm_vert
+                nu = torch.as_tensor(nu0, dtype=torch.float64, device=where).contiguous()
+                nu_ordered = torch.empty_like(nu)
+                targets = [torch.as_tensor(np.ascontiguousarray(m[k] if perm is None else m[k][perm]), dtype=torch.float64, device=where) for k in range(K)]
+            costs = [float(hist.history["Transportation cost"][-1]) for _, hist in results]
+            potentials = [sol["sensitivity"]["phi0"] for sol, _ in results]
+            objective = bary.objective_of(costs, w)
+            step_eta = rule.take(objective)
+            scalars = dev.barycenter_update(potentials, w, step_eta, mass, nu, nu_ordered)
+            out["objective"].append(objective)
+            out["change"].append(scalars["change"])
+            out["eta"].append(step_eta)
+            out["iterations"].append(int(sum(int(hist.kkt_iteration[-1]) + 1 for _, hist in results)))
+            out["costs"] = np.asarray(costs)
+            stats["updates"].append(scalars)
+            stats["update_ms"].append(dev.barycenter_ms)
+            stats["session"] = [hist.solver_stats.get("session") for _, hist in results]
+            stats["step_seconds"].append(time.perf_counter() - t0)
+            stats["bytes_to_host"].append(int(sum(alm.dev.debug_counter(9) for alm in bs._live()) - copied) + 32)      # (+ the update's four scalars)
+            if tol_change is not None and scalars["change"] < float(tol_change) * mass:
+                break
+        out["nu"] = nu.clone() if to_device else nu.cpu().numpy()
+    out["solver_stats"] = stats
+    return out

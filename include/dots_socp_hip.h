@@ -886,6 +886,48 @@ typedef struct dots_restart_desc {
 } dots_restart_desc;
 int dots_restart(dots_ctx *ctx, const dots_restart_desc *desc);
 
+/* ---- Wasserstein barycentres: one mirror-descent step on the device ---------------------------------------------------------------
+ * dots_barycenter_update moves the common first end mass nu of n transport problems (nu -> mu_k) on one surface along the weighted
+ * sum of their cost gradients and renormalises it (dots_socp_amd/barycenter.py: update_host is the specification), from potentials
+ * and masses that are device memory: phi0[k] is what dots_sensitivity(device_pointers = 1) wrote for problem k, as stored (no gauge
+ * fixed).  With V = n_vertices, in this order:
+ *   m_k = sum(phi0[k]) / V
+ *   g[v] = 0; for k ascending: g[v] = g[v] + weights[k] * (-(phi0[k][v] - m_k))
+ *   y[v] = nu[v] * exp((-eta) * g[v]);  S = sum(y);  nu[v] = y[v] * (mass / S)
+ *   scalars = { S, sum |nu_new - nu|, max |g|, min nu_new }
+ * Element by element the operations of update_host in its order; exp is the device library's (within 1 ulp), and every sum is a
+ * two-stage reduction in a fixed order carried with error-free additions, so it equals the host's exactly rounded sum to an ulp:
+ * reproducible from call to call, equal to update_host to rounding.  Four launches (csrc/kernels_barycenter.hip), plain loads and
+ * stores; 32 bytes cross to the host.
+ * The call takes NO context: it needs nothing of a solve's state, so it reads and changes none, and what a call does to the deferred
+ * work of a context (csrc/admission.h) does not arise.  What it needs of the surface comes in the descriptor: the device, the
+ * vertex count, the stream its launches run on (the caller orders it against whatever wrote the inputs; the call returns with that
+ * stream synchronised), scratch of dots_barycenter_scratch(V) doubles, and -- for nu_device_order, the values in the vertex
+ * numbering of the contexts, which dots_restart(device_pointers = 1) reads -- the row of every caller vertex in that numbering
+ * (the inverse of dots_problem_desc.perm_vert; an entry outside [0, V) is not written).
+ * DOTS_ERR_ARGUMENT (nothing launched, nu untouched): a NULL desc, phi0, phi0[k], weights, nu, scratch or scalars; n outside 1 .. 16;
+ * n_vertices < 1; a weight, eta or mass that is not finite; vertex_row without nu_device_order; nu, nu_device_order and scratch that
+ * overlap.  An entry of nu that is not positive is the caller's business (update_host refuses it). */
+typedef struct dots_barycenter_desc {
+    int32_t n;                   /* potentials, 1 .. 16                                                                         */
+    int32_t device;              /* HIP device ordinal of every device pointer below                                            */
+    int32_t n_vertices;          /* V                                                                                           */
+    int32_t reserved;
+    const double *const *phi0;   /* HOST [n] of DEVICE pointers to [V] doubles, caller numbering                                */
+    const double *weights;       /* HOST [n]                                                                                    */
+    double eta;                  /* step                                                                                        */
+    double mass;                 /* the total mass nu is normalised to                                                          */
+    double *nu;                  /* DEVICE [V], caller numbering, updated in place                                              */
+    double *nu_device_order;     /* DEVICE [V] or NULL: out, nu_device_order[vertex_row[v]] = nu[v]                             */
+    const int32_t *vertex_row;   /* DEVICE [V] or NULL (the identity): caller vertex -> row of nu_device_order                  */
+    double *scratch;             /* DEVICE [dots_barycenter_scratch(V)], contents unspecified before and after                  */
+    void *stream;                /* the HIP stream of the launches; NULL = the legacy default stream                            */
+    double *scalars;             /* HOST out [4]: sum, change, gmax, min                                                        */
+    double *ms;                  /* NULL, or HOST out: device milliseconds of the launches                                      */
+} dots_barycenter_desc;
+int64_t dots_barycenter_scratch(int32_t n_vertices);      /* doubles; -1 if n_vertices < 1 */
+int dots_barycenter_update(const dots_barycenter_desc *desc);
+
 /* ---- solve session: moved vertices on a live context ----------------------------------------------------------------------------
  * dots_move_vertices: the context takes other vertex positions of the SAME triangulation.  Everything that depends on the mesh graph
  * only is kept (tri, the corner lists, the CSR pattern, the permutations, the time modes, the elimination tree, the band plan, the
