@@ -38,6 +38,7 @@ EXPORTS = [
     "dots_flow_map", "dots_flow_push", "dots_flow_trace", "dots_flow_slide",
     "dots_sensitivity",
     "dots_restart", "dots_barycenter_update", "dots_barycenter_scratch",
+    "dots_tangent_velocities", "dots_tangent_weights", "dots_tangent_gram_scratch", "dots_tangent_gram",
     "dots_move_vertices", "dots_geometry_copy", "dots_move_vertices_many",
 ]
 RESTART_COLD, RESTART_WARM = 0, 1      # dots_restart_desc.mode
@@ -205,6 +206,11 @@ class BarycenterDesc(C.Structure):      # dots_barycenter_desc
     _fields_ = [("n", C.c_int32), ("device", C.c_int32), ("n_vertices", C.c_int32), ("reserved", C.c_int32), ("phi0", C.POINTER(C.c_void_p)),
                 ("weights", _f64p), ("eta", C.c_double), ("mass", C.c_double), ("nu", C.c_void_p), ("nu_device_order", C.c_void_p),
                 ("vertex_row", C.c_void_p), ("scratch", C.c_void_p), ("stream", C.c_void_p), ("scalars", _f64p), ("ms", _f64p)]
+
+
+class TangentDesc(C.Structure):      # dots_tangent_desc
+    _fields_ = [("device", C.c_int32), ("n_vertices", C.c_int32), ("n_triangles", C.c_int32), ("reserved", C.c_int32), ("triangles", C.c_void_p),
+                ("hat_grad", C.c_void_p), ("area_tri", C.c_void_p), ("mass_vert", C.c_void_p), ("stream", C.c_void_p), ("ms", _f64p)]
 
 
 class RestartDesc(C.Structure):      # dots_restart_desc
@@ -420,6 +426,11 @@ def load(host_only=False):
     lib.dots_barycenter_update.argtypes = [C.POINTER(BarycenterDesc)]
     lib.dots_barycenter_scratch.argtypes = [C.c_int32]
     lib.dots_barycenter_scratch.restype = C.c_int64
+    lib.dots_tangent_velocities.argtypes = [C.POINTER(TangentDesc), C.c_int32, C.POINTER(C.c_void_p), C.c_void_p]
+    lib.dots_tangent_weights.argtypes = [C.POINTER(TangentDesc), C.c_void_p, C.c_void_p]
+    lib.dots_tangent_gram_scratch.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.dots_tangent_gram_scratch.restype = C.c_int64
+    lib.dots_tangent_gram.argtypes = [C.POINTER(TangentDesc), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, _f64p]
     lib.dots_move_vertices.argtypes = [vp, C.POINTER(MoveDesc)]
     lib.dots_geometry_copy.argtypes = [vp, C.POINTER(GeometryTables)]
     lib.dots_move_vertices_many.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(MoveDesc)]
@@ -439,7 +450,7 @@ def load(host_only=False):
     lib.dots_device_bytes.restype = C.c_int64
     for n in EXPORTS:
         f = getattr(lib, n)
-        if n not in ("dots_last_error", "dots_array_count", "dots_device_bytes", "dots_slab_elems", "dots_tree_nodes", "dots_tree_free", "dots_debug_counter", "dots_barycenter_scratch",
+        if n not in ("dots_last_error", "dots_array_count", "dots_device_bytes", "dots_slab_elems", "dots_tree_nodes", "dots_tree_free", "dots_debug_counter", "dots_barycenter_scratch", "dots_tangent_gram_scratch",
                      "dots_symbolic_front_rows", "dots_symbolic_free", "dots_assemble_nnz", "dots_assemble_free", "dots_coarsen_vertices",
                      "dots_coarsen_triangles", "dots_coarsen_free"):
             f.restype = C.c_int

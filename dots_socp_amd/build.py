@@ -15,9 +15,9 @@ from concurrent.futures import ThreadPoolExecutor
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libdotsocp_hip.so")
-SOURCES = ["dots_api.hip", "kernels_alm.hip", "kernels_cg.hip", "kernels_modes.hip", "kernels_mg.hip", "kernels_front.hip", "kernels_factor.hip", "dissect.hip", "kernels_kkt.hip", "kernels_readout.hip", "coarsen.hip", "kernels_locate.hip", "kernels_flow.hip", "kernels_carry.hip", "kernels_sensitivity.hip", "kernels_restart.hip", "kernels_geometry.hip", "kernels_barycenter.hip"]
+SOURCES = ["dots_api.hip", "kernels_alm.hip", "kernels_cg.hip", "kernels_modes.hip", "kernels_mg.hip", "kernels_front.hip", "kernels_factor.hip", "dissect.hip", "kernels_kkt.hip", "kernels_readout.hip", "coarsen.hip", "kernels_locate.hip", "kernels_flow.hip", "kernels_carry.hip", "kernels_sensitivity.hip", "kernels_restart.hip", "kernels_geometry.hip", "kernels_barycenter.hip", "kernels_tangent.hip"]
 EXPORTS = os.path.join(CSRC, "exports.map")      # linker version script: only dots_* is exported
-HEADERS = [os.path.join(CSRC, "dots_dev.h"), os.path.join(CSRC, "modes_dev.h"), os.path.join(CSRC, "admission.h"), os.path.join(CSRC, "step_choice.h"), os.path.join(CSRC, "kkt_slots.h"), os.path.join(PKG_DIR, "..", "include", "dots_socp_hip.h")]
+HEADERS = [os.path.join(CSRC, "dots_dev.h"), os.path.join(CSRC, "modes_dev.h"), os.path.join(CSRC, "admission.h"), os.path.join(CSRC, "step_choice.h"), os.path.join(CSRC, "kkt_slots.h"), os.path.join(CSRC, "pairs_dev.h"), os.path.join(PKG_DIR, "..", "include", "dots_socp_hip.h")]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function", "-ffp-contract=off", "-fvisibility=hidden"]      # (the header's declarations are the exports)
 FLAGS += os.environ.get("DOTS_HIPCC_FLAGS", "").split()      # extra -D switches for A/B measurements of compile-time variants

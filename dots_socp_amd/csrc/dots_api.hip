@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -600,6 +601,7 @@ int dots_create(const dots_problem_desc *desc, dots_ctx **out) {
     preload_readout_kernels();
     preload_restart_kernels();
     preload_barycenter_kernels();
+    preload_tangent_kernels();
     preload_geometry_kernels();
     *out = c.release();
     return 0;
@@ -2303,6 +2305,121 @@ int dots_barycenter_update(const dots_barycenter_desc *desc) {
     for (hipEvent_t e : ev)
         if (e) (void)hipEventDestroy(e);
     return rc;
+}
+
+// ---- dots_tangent_*: linearised transport; the calls take no context (include/dots_socp_hip.h) ------------------------------------------
+static bool tangent_overlap(const void *a, int64_t bytes_a, const void *b, int64_t bytes_b) {
+    const char *p = static_cast<const char *>(a), *q = static_cast<const char *>(b);
+    return p < q + bytes_b && q < p + bytes_a;
+}
+
+// The launches of `enqueue` on the descriptor's device and stream, timed if asked for; `after` (may be empty) enqueues what follows
+// the timed part.  Every path out waits for the stream first: the kernels use the caller's arrays.
+using TangentWork = std::function<int(hipStream_t)>;
+static int tangent_run(const dots_tangent_desc *desc, const TangentWork &enqueue, const TangentWork &after) {
+    DOTS_HIP(hipSetDevice(desc->device));
+    hipStream_t stream = static_cast<hipStream_t>(desc->stream);
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    auto all = [&]() -> int {
+        if (desc->ms) {
+            DOTS_HIP(hipEventCreate(&ev[0]));
+            DOTS_HIP(hipEventCreate(&ev[1]));
+            DOTS_HIP(hipEventRecord(ev[0], stream));
+        }
+        int r = enqueue(stream);
+        if (r) return r;
+        if (desc->ms) DOTS_HIP(hipEventRecord(ev[1], stream));
+        return after(stream);
+    };
+    int rc = all();
+    const hipError_t es = hipStreamSynchronize(stream);
+    if (!rc && es != hipSuccess) rc = hip_fail(es, "hipStreamSynchronize", __FILE__, __LINE__);
+    if (!rc && desc->ms) {
+        float t = 0.f;
+        const hipError_t et = hipEventElapsedTime(&t, ev[0], ev[1]);
+        if (et != hipSuccess) rc = hip_fail(et, "hipEventElapsedTime", __FILE__, __LINE__);
+        *desc->ms = t;
+    }
+    for (hipEvent_t e : ev)
+        if (e) (void)hipEventDestroy(e);
+    return rc;
+}
+
+static bool tangent_sizes_ok(const dots_tangent_desc *desc, const char *who) {
+    if (!desc) { set_error(std::string(who) + ": null argument"); return false; }
+    if (desc->n_vertices < 1 || desc->n_triangles < 1) { set_error(std::string(who) + ": n_vertices and n_triangles must be positive"); return false; }
+    return true;
+}
+
+int dots_tangent_velocities(const dots_tangent_desc *desc, int32_t n, const double *const *phi0, double *velocities) {
+    const char *who = "tangent_velocities";
+    if (!tangent_sizes_ok(desc, who)) return DOTS_ERR_ARGUMENT;
+    if (!desc->triangles || !desc->hat_grad || !phi0 || !velocities) { set_error("tangent_velocities: null argument"); return DOTS_ERR_ARGUMENT; }
+    if (n < 1) { set_error("tangent_velocities: n must be at least 1"); return DOTS_ERR_ARGUMENT; }
+    const int64_t V = desc->n_vertices, F = desc->n_triangles, out_bytes = (int64_t)n * F * 24;
+    if (tangent_overlap(velocities, out_bytes, desc->triangles, F * 12) || tangent_overlap(velocities, out_bytes, desc->hat_grad, F * 72)) {
+        set_error("tangent_velocities: velocities overlaps the mesh tables");
+        return DOTS_ERR_ARGUMENT;
+    }
+    for (int k = 0; k < n; ++k) {
+        if (!phi0[k]) { set_error("tangent_velocities: a null potential"); return DOTS_ERR_ARGUMENT; }
+        if (tangent_overlap(velocities, out_bytes, phi0[k], V * 8)) { set_error("tangent_velocities: velocities overlaps a potential"); return DOTS_ERR_ARGUMENT; }
+    }
+    return tangent_run(desc, [&](hipStream_t stream) -> int {
+        for (int at = 0; at < n; at += TANGENT_VEL_N) {
+            TangentVelArgs a{};
+            a.n = std::min(n - at, TANGENT_VEL_N);
+            for (int k = 0; k < a.n; ++k) a.phi[k] = phi0[at + k];
+            a.tri = desc->triangles; a.hat = desc->hat_grad; a.F = (int)F;
+            a.out = velocities + (int64_t)at * F * 3;
+            int r = launch_tangent_velocities(stream, a);
+            if (r) return r;
+        }
+        return 0;
+    }, [](hipStream_t) -> int { return 0; });
+}
+
+int dots_tangent_weights(const dots_tangent_desc *desc, const double *sigma, double *w) {
+    const char *who = "tangent_weights";
+    if (!tangent_sizes_ok(desc, who)) return DOTS_ERR_ARGUMENT;
+    if (!desc->triangles || !desc->area_tri || !desc->mass_vert || !sigma || !w) { set_error("tangent_weights: null argument"); return DOTS_ERR_ARGUMENT; }
+    const int64_t V = desc->n_vertices, F = desc->n_triangles;
+    if (tangent_overlap(w, F * 8, sigma, V * 8) || tangent_overlap(w, F * 8, desc->triangles, F * 12) || tangent_overlap(w, F * 8, desc->area_tri, F * 8)
+        || tangent_overlap(w, F * 8, desc->mass_vert, V * 8)) {
+        set_error("tangent_weights: w overlaps an input");
+        return DOTS_ERR_ARGUMENT;
+    }
+    return tangent_run(desc, [&](hipStream_t stream) -> int {
+        return launch_tangent_weights(stream, desc->triangles, sigma, desc->mass_vert, desc->area_tri, w, (int)F);
+    }, [](hipStream_t) -> int { return 0; });
+}
+
+int64_t dots_tangent_gram_scratch(int32_t na, int32_t nb, int32_t n_triangles) {
+    if (na < 1 || nb < 1 || na > TANGENT_MAX_N || nb > TANGENT_MAX_N || n_triangles < 1) return -1;
+    return (2 * (int64_t)tangent_chunks(n_triangles) + 1) * na * nb;      // the partial pairs, then G
+}
+
+int dots_tangent_gram(const dots_tangent_desc *desc, int32_t na, const double *A, int32_t nb, const double *B, const double *w, double *scratch, double *G) {
+    const char *who = "tangent_gram";
+    if (!tangent_sizes_ok(desc, who)) return DOTS_ERR_ARGUMENT;
+    if (!A || !w || !scratch || !G) { set_error("tangent_gram: null argument"); return DOTS_ERR_ARGUMENT; }
+    const int64_t F = desc->n_triangles, total = dots_tangent_gram_scratch(na, nb, (int32_t)F);
+    if (total < 0) { set_error("tangent_gram: na and nb must be 1 .. 4096"); return DOTS_ERR_ARGUMENT; }
+    if (!B && nb != na) { set_error("tangent_gram: B = NULL means B = A: nb must equal na"); return DOTS_ERR_ARGUMENT; }
+    if (tangent_overlap(scratch, total * 8, A, (int64_t)na * F * 24) || (B && tangent_overlap(scratch, total * 8, B, (int64_t)nb * F * 24))
+        || tangent_overlap(scratch, total * 8, w, F * 8)) {
+        set_error("tangent_gram: scratch overlaps an input");
+        return DOTS_ERR_ARGUMENT;
+    }
+    TangentGramArgs a{};
+    a.A = A; a.B = B ? B : A; a.w = w;
+    a.na = na; a.nb = nb; a.F = (int)F; a.C = tangent_chunks((int)F);
+    a.part = scratch; a.G = scratch + 2 * (int64_t)a.C * na * nb;
+    return tangent_run(desc, [&](hipStream_t stream) -> int { return launch_tangent_gram(stream, a); }, [&](hipStream_t stream) -> int {
+        // (pageable host memory: the copy is complete when the stream is idle, which the call waits for)
+        DOTS_HIP(hipMemcpyAsync(G, a.G, sizeof(double) * (size_t)na * nb, hipMemcpyDeviceToHost, stream));
+        return 0;
+    });
 }
 
 int dots_front_enable(dots_ctx *c, int on) {

@@ -444,6 +444,32 @@ struct BaryArgs {
 int barycenter_workgroups(int V);
 int launch_barycenter(hipStream_t stream, const BaryArgs &a);
 void preload_barycenter_kernels();
+// dots_tangent_velocities / _weights / _gram (kernels_tangent.hip): the gradients of potentials per triangle, the reference measure's
+// mass per triangle and the weighted Gram matrix of such fields, on the caller's stream, every array in the CALLER's numbering.
+constexpr int TANGENT_VEL_N = 16;              // potentials per launch of k_tangent_velocities
+constexpr int TANGENT_TILE = 4;                // entries per side of the Gram kernel's register tile
+constexpr int TANGENT_CHUNK = 2048;            // triangles per workgroup of the Gram kernel, while the chunks are fewer than
+constexpr int TANGENT_MAX_CHUNKS = 1024;       //   this: then every workgroup takes more
+constexpr int TANGENT_MAX_N = 4096;            // fields per side of one Gram call
+struct TangentVelArgs {
+    const double *phi[TANGENT_VEL_N];      // [n] potentials, [V] each
+    const int *tri;                        // [F][3]
+    const double *hat;                     // [F][3][3]
+    double *out;                           // [n][F][3]
+    int n, F;
+};
+struct TangentGramArgs {
+    const double *A, *B;      // [na][F][3], [nb][F][3] (B may be A)
+    const double *w;          // [F]
+    double *part;             // scratch [C][na * nb][2]
+    double *G;                // [na][nb]
+    int na, nb, F, C;         // C = tangent_chunks(F)
+};
+int tangent_chunks(int F);
+int launch_tangent_velocities(hipStream_t stream, const TangentVelArgs &a);
+int launch_tangent_weights(hipStream_t stream, const int *tri, const double *sigma, const double *mass_v, const double *area, double *w, int F);
+int launch_tangent_gram(hipStream_t stream, const TangentGramArgs &a);
+void preload_tangent_kernels();
 
 // ---- dots_move_vertices (kernels_geometry.hip): the geometry tables from vertex positions, dots_assemble's and dots_create's bits
 struct GeomScratch {

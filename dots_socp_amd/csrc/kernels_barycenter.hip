@@ -16,32 +16,11 @@
 // Traffic: the potentials are read twice (n V doubles from memory, n V from the cache they stayed in), nu and y once each by the
 // update and the finish (3 V), y, nu and the second numbering are written (3 V).
 #include "dots_dev.h"
+#include "pairs_dev.h"      // two_sum, DD, dd_add, dd_merge
 
 #include <algorithm>
 
 namespace dots {
-
-// s + e == a + b exactly
-__device__ __forceinline__ void two_sum(double a, double b, double &s, double &e) {
-    s = a + b;
-    const double bb = s - a;
-    e = (a - (s - bb)) + (b - bb);
-}
-struct DD {
-    double hi, lo;
-};
-__device__ __forceinline__ void dd_add(DD &acc, double x) {
-    double s, e;
-    two_sum(acc.hi, x, s, e);
-    acc.hi = s;
-    acc.lo = acc.lo + e;
-}
-__device__ __forceinline__ void dd_merge(DD &acc, const DD &o) {
-    double s, e;
-    two_sum(acc.hi, o.hi, s, e);
-    acc.hi = s;
-    acc.lo = (acc.lo + o.lo) + e;
-}
 
 enum BaryOp : int { BARY_MAX = 0, BARY_MIN = 1 };
 template <int OP> __device__ __forceinline__ double bary_pick(double a, double b) { return OP == BARY_MAX ? fmax(a, b) : fmin(a, b); }

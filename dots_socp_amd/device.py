@@ -577,6 +577,41 @@ class DeviceProblem:
         scalars, self.barycenter_ms = barycenter_update(potentials, weights, eta, mass, nu, nu_device_order, self._vertex_row)
         return scalars
 
+    # ---- linearised transport: the calls take no context; the context lends its surface and device
+    def tangent_mesh(self):
+        """The four mesh tensors of the ``tangent_*`` calls on the context's device, in the CALLER's numbering -- ``triangles`` (F, 3)
+        int32, ``hat`` (F, 3, 3), ``area`` (F,), ``mass`` (V,) --, taken from the plan's host arrays (the ones the context was built
+        from, permuted back) and cached until the plan changes (``move_vertices``)."""
+        if self.slab:
+            raise ValueError("tangent: not available on time slabs")
+        cached = getattr(self, "_tangent_mesh", None)
+        if cached is None or cached[0] is not self.plan:
+            import torch
+
+            self._tangent_mesh = cached = (self.plan, {k: torch.as_tensor(a, device=torch.device("cuda", self.device))
+                                                       for k, a in caller_tables(self.plan).items()})
+        return cached[1]
+
+    def tangent_velocities(self, potentials):
+        """``grad phi`` per triangle of every potential, (n, F, 3) on the device (``tangent_velocities`` below on this context's
+        surface): ``potentials`` as ``sensitivity(to_device=True)`` left them.  ``self.tangent_ms["velocities"]``: device milliseconds."""
+        out, ms = tangent_velocities(self.tangent_mesh(), potentials)
+        self.tangent_ms = {**getattr(self, "tangent_ms", {}), "velocities": ms}
+        return out
+
+    def tangent_weights(self, sigma):
+        """The mass of ``sigma`` (V,), a tensor on the device in the caller's numbering, on every triangle: (F,) on the device."""
+        out, ms = tangent_weights(self.tangent_mesh(), sigma)
+        self.tangent_ms = {**getattr(self, "tangent_ms", {}), "weights": ms}
+        return out
+
+    def tangent_gram(self, A, B, w):
+        """The Gram matrix (na, nb) of the fields ``A`` and ``B`` (None: ``A``) with the triangle weights ``w``, all on the device;
+        a host array: only it crosses."""
+        out, ms = tangent_gram(A, B, w)
+        self.tangent_ms = {**getattr(self, "tangent_ms", {}), "gram": ms}
+        return out
+
     def move_vertices(self, vertices, device_pointers=False):
         """Move the vertices of the live context to ``vertices`` (V, 3), caller's numbering (dots_move_vertices): every geometry table
         is assembled again on the device and a factor the context owns is computed again into its allocations; the tree, the plan of
@@ -1117,3 +1152,119 @@ def barycenter_update(potentials, weights, eta, mass, nu, nu_device_order=None, 
     d.scalars, d.ms = _ptr(scalars, C.c_double), C.pointer(ms)
     _lib.check(lib.dots_barycenter_update(C.byref(d)), "dots_barycenter_update")
     return {"sum": float(scalars[0]), "change": float(scalars[1]), "gmax": float(scalars[2]), "min": float(scalars[3])}, ms.value
+
+
+# ---- linearised transport (dots_tangent_*: calls without a context; dots_socp_amd.tangent holds the specifications) -----------------
+def caller_tables(plan):
+    """``{"triangles" (F, 3) int32, "hat" (F, 3, 3), "area" (F,), "mass" (V,)}``: the mesh tables of ``plan`` -- the ones a context
+    built from it holds, in the device numbering -- in the CALLER's numbering, on the host; nothing is recomputed."""
+    tri = np.asarray(plan.triangles, dtype=np.int32).reshape(-1, 3)
+    hat = np.asarray(plan.hat_grad, dtype=np.float64).reshape(-1, 3, 3)
+    area, mass = np.asarray(plan.area_tri, dtype=np.float64), np.asarray(plan.mass_vert, dtype=np.float64)
+    if plan.perm_vert is not None:      # device vertex i is caller vertex perm_vert[i]; device triangle i is caller triangle perm_tri[i]
+        pv, pf = np.asarray(plan.perm_vert, dtype=np.int64), np.asarray(plan.perm_tri, dtype=np.int64)
+        t, h, a, m = np.empty_like(tri), np.empty_like(hat), np.empty_like(area), np.empty_like(mass)
+        t[pf], h[pf], a[pf], m[pv] = pv[tri].astype(np.int32), hat, area, mass
+        tri, hat, area, mass = t, h, a, m
+    c = np.ascontiguousarray
+    return {"triangles": c(tri), "hat": c(hat), "area": c(area), "mass": c(mass)}
+
+
+def _tangent_desc(who, mesh, need):
+    """The descriptor of a ``tangent_*`` call from the mesh tensors ``need`` names, its ``ms`` and the device"""
+    import torch
+
+    shapes = {"triangles": (torch.int32, lambda V, F: (F, 3)), "hat": (torch.float64, lambda V, F: (F, 3, 3)),
+              "area": (torch.float64, lambda V, F: (F,)), "mass": (torch.float64, lambda V, F: (V,))}
+    if not isinstance(mesh, dict) or any(not isinstance(mesh.get(k), torch.Tensor) or not mesh[k].is_cuda for k in need):
+        raise ValueError(f"{who}: mesh must hold tensors on a GPU under {list(need)} (DeviceProblem.tangent_mesh)")
+    where = mesh[need[0]].device
+    V, F = int(mesh["mass"].shape[0]), int(mesh["triangles"].shape[0])      # (both calls need these two tables)
+    for k in need:
+        a, (dtype, shape) = mesh[k], shapes[k]
+        if a.device != where or a.dtype != dtype or not a.is_contiguous() or tuple(a.shape) != shape(V, F):
+            raise ValueError(f"{who}: mesh['{k}'] must be a contiguous {dtype} tensor of shape {shape('V', 'F')} on {where}")
+    ms = C.c_double()
+    d = _lib.TangentDesc()
+    d.device, d.n_vertices, d.n_triangles = where.index, V, F
+    d.triangles, d.hat_grad = mesh["triangles"].data_ptr(), mesh["hat"].data_ptr() if "hat" in need else None
+    d.area_tri = mesh["area"].data_ptr() if "area" in need else None
+    d.mass_vert = mesh["mass"].data_ptr() if "mass" in need else None
+    d.stream, d.ms = torch.cuda.current_stream(where).cuda_stream, C.pointer(ms)
+    return d, ms, where, V, F
+
+
+def _tangent_tensor(who, name, a, where, shape):
+    import torch
+
+    if not isinstance(a, torch.Tensor) or a.device != where or a.dtype != torch.float64 or not a.is_contiguous() or (shape is not None and tuple(a.shape) != shape):
+        raise ValueError(f"{who}: {name} must be a contiguous float64 tensor" + ("" if shape is None else f" of shape {shape}") + f" on {where}")
+
+
+def tangent_velocities(mesh, potentials):
+    """``(velocities, device milliseconds)``: ``velocities`` (n, F, 3), a new tensor on the device, the gradient of every potential on
+    every triangle (dots_tangent_velocities; ``tangent.velocities_host`` is the specification, bit for bit).  ``mesh``: the tensors of
+    ``DeviceProblem.tangent_mesh`` (caller's numbering); ``potentials``: a list of n >= 1 contiguous float64 tensors (V,) on that
+    device, or one such tensor (n, V).  Needs n F 3 doubles of device memory.  On torch's current stream of that device."""
+    import torch
+
+    who = "tangent_velocities"
+    d, ms, where, V, F = _tangent_desc(who, mesh, ("triangles", "hat", "mass"))
+    rows = list(potentials)
+    if not rows:
+        raise ValueError(f"{who}: no potentials")
+    for a in rows:
+        _tangent_tensor(who, "every potential", a, where, (V,))
+    out = torch.empty((len(rows), F, 3), dtype=torch.float64, device=where)
+    pointers = (C.c_void_p * len(rows))(*[a.data_ptr() for a in rows])
+    _lib.check(_lib.load().dots_tangent_velocities(C.byref(d), len(rows), pointers, out.data_ptr()), "dots_tangent_velocities")
+    return out, ms.value
+
+
+def tangent_weights(mesh, sigma):
+    """``(w, device milliseconds)``: ``w`` (F,), a new tensor on the device, the mass of ``sigma`` (V,) on every triangle
+    (dots_tangent_weights; ``tangent.weights_host`` is the specification, bit for bit)."""
+    import torch
+
+    who = "tangent_weights"
+    d, ms, where, V, F = _tangent_desc(who, mesh, ("triangles", "area", "mass"))
+    _tangent_tensor(who, "sigma", sigma, where, (V,))
+    out = torch.empty((F,), dtype=torch.float64, device=where)
+    _lib.check(_lib.load().dots_tangent_weights(C.byref(d), sigma.data_ptr(), out.data_ptr()), "dots_tangent_weights")
+    return out, ms.value
+
+
+_tangent_scratch = {}      # (device ordinal) -> the largest scratch tensor a Gram call has needed
+
+
+def tangent_gram(A, B, w):
+    """``(G, device milliseconds)``: ``G`` (na, nb), a host array, ``G[i][j] = sum_f w[f] A[i][f] . B[j][f]`` (dots_tangent_gram;
+    ``tangent.gram_host`` is the specification: equal to an ulp, the same from call to call, symmetric bit for bit when ``B`` is
+    None).  ``A`` (na, F, 3), ``B`` (nb, F, 3) or None (``A``), ``w`` (F,): contiguous float64 tensors on one GPU; na, nb <= 4096."""
+    import torch
+
+    who = "tangent_gram"
+    if not isinstance(A, torch.Tensor) or not A.is_cuda or A.ndim != 3 or A.shape[2] != 3 or A.shape[0] < 1 or A.shape[1] < 1:
+        raise ValueError(f"{who}: A must be a float64 tensor of shape (na, F, 3) on a GPU")
+    where, na, F = A.device, int(A.shape[0]), int(A.shape[1])
+    _tangent_tensor(who, "A", A, where, None)
+    if B is not None:
+        _tangent_tensor(who, "B", B, where, None)
+        if B.ndim != 3 or B.shape[0] < 1 or tuple(B.shape[1:]) != (F, 3):
+            raise ValueError(f"{who}: B must have shape (nb, {F}, 3), got {tuple(B.shape)}")
+    _tangent_tensor(who, "w", w, where, (F,))
+    nb = na if B is None else int(B.shape[0])
+    lib = _lib.load()
+    need = int(lib.dots_tangent_gram_scratch(na, nb, F))
+    if need < 0:
+        raise ValueError(f"{who}: na and nb must be 1 .. 4096, got {na} and {nb}")
+    if where.index not in _tangent_scratch or _tangent_scratch[where.index].shape[0] < need:
+        _tangent_scratch[where.index] = torch.empty(need, dtype=torch.float64, device=where)
+    ms = C.c_double()
+    d = _lib.TangentDesc()
+    d.device, d.n_vertices, d.n_triangles = where.index, 1, F      # (the Gram call reads no vertex array)
+    d.stream, d.ms = torch.cuda.current_stream(where).cuda_stream, C.pointer(ms)
+    G = np.empty((na, nb))
+    _lib.check(lib.dots_tangent_gram(C.byref(d), na, A.data_ptr(), nb, None if B is None else B.data_ptr(), w.data_ptr(),
+                                     _tangent_scratch[where.index].data_ptr(), _ptr(G, C.c_double)), "dots_tangent_gram")
+    return G, ms.value

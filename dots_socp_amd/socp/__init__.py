@@ -16,6 +16,10 @@
 ``barycenter``     the Wasserstein barycentre of several measures on one surface, iterated on the device over one ``BatchSession``:
                    ``socp.barycenter(n_time, geometry, measures, weights)`` (dots_barycenter_update; ``dots_socp_amd.barycenter``)
 
+``tangent_embedding`` / ``distance_matrix``   linearised transport: N measures seen from one reference measure, the Gram matrix of
+                   their initial velocities formed on the device: ``socp.tangent_embedding(n_time, geometry, reference, measures)``,
+                   ``socp.distance_matrix(n_time, geometry, measures)`` (dots_tangent_*; ``dots_socp_amd.tangent``)
+
 Both take ``(n_time, geometry, **kwargs)`` and return ``(solution, run_history)``; they can be
 passed as ``solver=`` to the reference's ``run_dot_surface`` (interface.py:106-134).
 
@@ -36,11 +40,11 @@ not with congestion.
 import numpy as np
 
 from ..sensitivity import check_sensitivity
-from .solver_socp import (BatchSession, DeviceOrdered, SolveSession, barycenter, check_flow_map, solver_socp, solver_socp_auto_cascade, solver_socp_cascade, solver_socp_many,
-                          solver_socp_mesh_cascade, solver_socp_spacetime_cascade)
+from .solver_socp import (BatchSession, DeviceOrdered, SolveSession, barycenter, check_flow_map, distance_matrix, solver_socp, solver_socp_auto_cascade, solver_socp_cascade, solver_socp_many,
+                          solver_socp_mesh_cascade, solver_socp_spacetime_cascade, tangent_embedding)
 
 __all__ = ["solver_socp", "solver_raw", "solver", "solver_socp_many", "solver_raw_many", "solver_many", "SolveSession", "BatchSession",
-           "barycenter", "DeviceOrdered",
+           "barycenter", "DeviceOrdered", "tangent_embedding", "distance_matrix",
            "solver_socp_cascade", "solver_raw_cascade", "solver_cascade",
            "solver_socp_mesh_cascade", "solver_raw_mesh_cascade", "solver_mesh_cascade",
            "solver_socp_spacetime_cascade", "solver_raw_spacetime_cascade", "solver_spacetime_cascade",

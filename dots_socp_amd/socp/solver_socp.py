@@ -2025,3 +2025,123 @@ def barycenter(n_time, geometry, measures, weights=None, steps=20, eta=100.0, to
         out["nu"] = nu.clone() if to_device else nu.cpu().numpy()
     out["solver_stats"] = stats
     return out
+
+
+# ---- linearised transport: tangent vectors at one reference measure and their Gram matrix, formed on the device ------------------------
+TANGENT_SOLVE_KEYS = BARYCENTER_SOLVE_KEYS      # per problem, the same for all N
+
+
+def _tangent_arguments(who, geometry, options):
+    """The checks the two drivers share, before the library loads: the mesh's vertex count, the options split into those of every
+    solve and those of the session."""
+    if not isinstance(geometry, dict) or "vertices" not in geometry or "triangles" not in geometry:
+        raise ValueError(f"{who}: geometry must be a dict with 'vertices' and 'triangles'")
+    if options.get("time_slab") is not None:
+        raise ValueError(f"{who}: not available on time slabs")
+    if options.get("is_constant_scaling"):
+        raise ValueError(f"{who}: is_constant_scaling is not available: the problems share one session whose contexts are restarted")
+    options = {k: v for k, v in options.items() if k != "time_slab"}
+    per_solve = {k: options.pop(k) for k in TANGENT_SOLVE_KEYS if k in options}
+    unknown = set(options) - set(COMMON_KEYS) - set(BATCH_SESSION_FIXED) - {"max_batch"}
+    if unknown:
+        raise ValueError(f"{who}: unknown option(s) {sorted(unknown)}")
+    return int(np.asarray(geometry["vertices"]).shape[0]), per_solve, options
+
+
+def _tangent_session(n_problems, slots, session_kw):
+    """``max_batch`` and ``slots`` of a session for ``n_problems`` cold problems: at most 8 run at a time unless asked otherwise; a
+    slot that finishes takes the next problem, so the problems are not limited to the slots."""
+    max_batch = int(session_kw.pop("max_batch", min(n_problems, 8)))
+    return {"max_batch": max_batch, "slots": max(max_batch, min(n_problems, int(slots))) if slots is not None else max_batch, **session_kw}
+
+
+def tangent_embedding(n_time, geometry, reference, measures, velocities=False, to_device=False, slots=None, **options):
+    """The linearised-transport embedding of ``measures`` at the measure ``reference`` on the surface of ``geometry``
+    (``dots_socp_amd.tangent``: ``tangent_embedding_host`` is this driver on the host, ``velocities_host``, ``weights_host`` and
+    ``gram_host`` the specifications of the device calls).  The N problems ``(reference -> mu_i)`` are solved, their initial velocities
+    ``v_i = +grad phi0_i`` -- the logarithmic map at the reference -- are formed per triangle, and ``G_ij = sum_f w_f v_i[f] . v_j[f]``
+    with ``w_f`` the reference's mass on triangle ``f`` is their Gram matrix in L2(reference): ``G_ii + G_jj - 2 G_ij`` approximates
+    ``W2^2(mu_i, mu_j)`` (half of it is on the scale of "Transportation cost"; ``G_ii / 2`` is the cost of problem i up to the
+    discretisation), and PCA, clustering and kernels need no further solve.
+
+    ``reference`` (V,) and ``measures`` ((N, V) or a list of N arrays (V,)): finite, non-negative, of one total mass; N >= 1 has no
+    upper limit.  One ``BatchSession`` solves the N problems cold (``solve_many``: ``max_batch`` of them at a time, default min(N, 8);
+    ``slots`` contexts, default ``max_batch``; a slot that finishes takes the next problem) with their potentials read out on the
+    device (``sensitivity(to_device=True)``); then the velocities, the weights and the Gram matrix are formed there
+    (``DeviceProblem.tangent_velocities`` / ``tangent_weights`` / ``tangent_gram``: dots_tangent_*, calls without a context).
+    Besides the residuals and costs of the solves only ``G`` crosses to the host, 8 N^2 bytes -- and the weights (8 F) and, if asked
+    for, the velocities (24 N F), unless ``to_device``.  Device memory: N F 3 doubles for the velocities and N V for the potentials,
+    besides the session's.  ``options``: those of ``BatchSession`` and ``tol``, ``nit``, ``congestion`` of every solve.  Not on time
+    slabs, not with ``is_constant_scaling``.
+
+    Returns ``{"gram" (N, N), "costs" (N,), "squared_distances" (N, N), "iterations" (N,), "weights" (F,), "velocities" (N, F, 3) with
+    ``velocities=True`` (else None) -- ``weights`` and ``velocities`` are torch tensors on the device with ``to_device`` --,
+    "solver_stats": {"solve_seconds", "seconds", "tangent_ms" {"velocities", "weights", "gram"}, "bytes_to_host" (after the solves:
+    dots_debug_counter 9 of the session's contexts and the bytes of G, the weights and the velocities that crossed), "session"}}``."""
+    import torch
+
+    from .. import tangent as tg
+
+    who = "tangent_embedding"
+    t0 = time.perf_counter()
+    V, per_solve, session_kw = _tangent_arguments(who, geometry, dict(options))
+    sigma, m, _ = tg.check_embedding(who, reference, measures, V)
+    N = m.shape[0]
+    request = {"potentials": True, "stress": False, "to_device": True}
+    with BatchSession(n_time, _without_masses(geometry), **_tangent_session(N, slots, session_kw)) as bs:
+        results = bs.solve_many([{"mu0": sigma, "mu1": m[i], **per_solve} for i in range(N)], outputs=(), sensitivity=request)
+        solved = time.perf_counter()
+        copied = sum(alm.dev.debug_counter(9) for alm in bs._live())
+        dev = bs.solvers[0].dev
+        potentials = [sol["sensitivity"]["phi0"] for sol, _ in results]
+        vel = dev.tangent_velocities(potentials)
+        w = dev.tangent_weights(torch.as_tensor(sigma, dtype=torch.float64, device=vel.device))
+        G = dev.tangent_gram(vel, None, w)
+        crossed = int(sum(alm.dev.debug_counter(9) for alm in bs._live()) - copied) + G.nbytes
+        tangent_ms = dict(dev.tangent_ms)
+        if not to_device:
+            crossed += 8 * w.numel() + (8 * vel.numel() if velocities else 0)
+            w, vel = w.cpu().numpy(), vel.cpu().numpy() if velocities else None
+    return {"gram": G, "costs": np.array([float(hist.history["Transportation cost"][-1]) for _, hist in results]),
+            "squared_distances": tg.squared_distances(G), "iterations": np.array([int(hist.kkt_iteration[-1]) + 1 for _, hist in results]),
+            "weights": w, "velocities": vel if velocities else None,
+            "solver_stats": {"solve_seconds": solved - t0, "seconds": time.perf_counter() - t0, "tangent_ms": tangent_ms, "bytes_to_host": crossed,
+                             "session": [hist.solver_stats.get("session") for _, hist in results]}}
+
+
+def distance_matrix(n_time, geometry, measures, method="tangent", reference=None, slots=None, **options):
+    """The transport costs between every two of ``measures`` ((N, V), one total mass) on the surface of ``geometry``: (N, N), symmetric,
+    zero on the diagonal, on the scale of "Transportation cost" (``W2^2 / 2``).
+    ``method="tangent"``: ``squared_distances / 2`` of ``tangent_embedding`` at ``reference`` (default: the mean of the measures, summed
+    in their order) -- N solves; an approximation, good where the measures lie near the reference in the transport's sense.
+    ``method="pairs"``: the N (N - 1) / 2 problems ``(mu_i -> mu_j)``, i < j, solved exactly and cold through one ``BatchSession`` -- the
+    yardstick the linearisation is judged by.  ``options``: as for ``tangent_embedding``."""
+    from .. import tangent as tg
+
+    who = "distance_matrix"
+    if method not in ("tangent", "pairs"):
+        raise ValueError(f"{who}: method must be 'tangent' or 'pairs'")
+    V, per_solve, session_kw = _tangent_arguments(who, geometry, dict(options))
+    rows = list(measures)
+    if not rows:
+        raise ValueError(f"{who}: no measures")
+    _, m, _ = tg.check_embedding(who, rows[0], rows, V)
+    N = m.shape[0]
+    if method == "tangent":
+        if reference is None:
+            reference = np.zeros(V)
+            for i in range(N):
+                reference = reference + m[i]
+            reference = reference / N
+        return 0.5 * tangent_embedding(n_time, geometry, reference, m, slots=slots, **options)["squared_distances"]
+    if reference is not None:
+        raise ValueError(f"{who}: method='pairs' takes no reference")
+    D = np.zeros((N, N))
+    pairs = [(i, j) for i in range(N) for j in range(i + 1, N)]
+    if not pairs:
+        return D
+    with BatchSession(n_time, _without_masses(geometry), **_tangent_session(len(pairs), slots, session_kw)) as bs:
+        results = bs.solve_many([{"mu0": m[i], "mu1": m[j], **per_solve} for i, j in pairs], outputs=())
+    for (i, j), (_, hist) in zip(pairs, results):
+        D[i, j] = D[j, i] = float(hist.history["Transportation cost"][-1])
+    return D

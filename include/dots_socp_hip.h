@@ -928,6 +928,53 @@ typedef struct dots_barycenter_desc {
 int64_t dots_barycenter_scratch(int32_t n_vertices);      /* doubles; -1 if n_vertices < 1 */
 int dots_barycenter_update(const dots_barycenter_desc *desc);
 
+/* ---- Linearised transport: tangent vectors at a reference measure and their Gram matrix, on the device ------------------------------
+ * With the N problems (sigma -> mu_i) solved from one reference measure sigma, the initial velocities v_i = grad phi0_i are the
+ * logarithmic map at sigma, and G_ij = sum_f w[f] v_i[f] . v_j[f] -- w[f] the mass of sigma on triangle f -- is their Gram matrix in
+ * L2(sigma): G_ii + G_jj - 2 G_ij approximates W2^2(mu_i, mu_j) with no further solve (dots_socp_amd/tangent.py holds the
+ * specifications velocities_host, weights_host and gram_host).  Three calls, from potentials and masses that are device memory:
+ *   dots_tangent_velocities   velocities[i][f][d] = (hat[f][0][d] * p0 + hat[f][1][d] * p1) + hat[f][2][d] * p2, p_c = phi0[i][triangles[f][c]];
+ *                             phi0[i] is what dots_sensitivity(device_pointers = 1) wrote for problem i, as stored (no gauge is
+ *                             fixed: the hat gradients of a triangle sum to zero).  The specification's bits.
+ *   dots_tangent_weights      rho_c = sigma[v_c] / mass_vert[v_c]; w[f] = ((rho_0 + rho_1) + rho_2) * (area_tri[f] * (1.0 / 3.0)); sigma may
+ *                             have zeros.  The specification's bits.
+ *   dots_tangent_gram         G[i][j] = sum over f of w[f] * ((A[i][f][0] * B[j][f][0] + A[i][f][1] * B[j][f][1]) + A[i][f][2] * B[j][f][2]); B = NULL
+ *                             means B = A.  The terms are the specification's; the sum is a two-stage reduction in an order that
+ *                             depends on F alone, carried with error-free additions, so it equals the host's exactly rounded sum to an
+ *                             ulp, is the same from call to call, is symmetric bit for bit when B is A, and a block of rows and
+ *                             columns computed alone equals that block of the whole.  na * nb doubles cross to the host.
+ * The calls take NO context (as dots_barycenter_update): they need nothing of a solve's state, so what a call does to the deferred
+ * work of a context (csrc/admission.h) does not arise.  What they need of the surface comes in dots_tangent_desc, in the CALLER's
+ * numbering: the device, V, F, the stream of the launches (the caller orders it against whatever wrote the inputs; every call returns
+ * with that stream synchronised), and device pointers to the triangles, the hat gradients, the triangle areas and the vertex masses
+ * (dots_problem_desc's tables, which are in the device numbering, permuted back).  A call reads only the tables it needs and checks
+ * only those.  A triangle index outside [0, V) is not the library's business: the kernels read phi0, sigma and mass_vert at the
+ * indices they find.
+ * DOTS_ERR_ARGUMENT (nothing launched): a NULL desc, table or array; V or F below 1; n, na or nb below 1 or na or nb above 4096; a NULL
+ * phi0[i]; an output (velocities, w, G's scratch) that overlaps an input of the same call.  csrc/kernels_tangent.hip. */
+typedef struct dots_tangent_desc {
+    int32_t device;              /* HIP device ordinal of every device pointer                                                  */
+    int32_t n_vertices;          /* V                                                                                           */
+    int32_t n_triangles;         /* F                                                                                           */
+    int32_t reserved;
+    const int32_t *triangles;    /* DEVICE [F][3], caller numbering         (velocities, weights)                               */
+    const double *hat_grad;      /* DEVICE [F][3][3] [f][corner][xyz]       (velocities)                                        */
+    const double *area_tri;      /* DEVICE [F]                              (weights)                                           */
+    const double *mass_vert;     /* DEVICE [V]                              (weights)                                           */
+    void *stream;                /* the HIP stream of the launches; NULL = the legacy default stream                            */
+    double *ms;                  /* NULL, or HOST out: device milliseconds of the call's launches                               */
+} dots_tangent_desc;
+/* phi0: HOST [n] of DEVICE pointers to [V] doubles; velocities: DEVICE out [n][F][3] */
+int dots_tangent_velocities(const dots_tangent_desc *desc, int32_t n, const double *const *phi0, double *velocities);
+/* sigma: DEVICE [V]; w: DEVICE out [F] */
+int dots_tangent_weights(const dots_tangent_desc *desc, const double *sigma, double *w);
+/* doubles of scratch a Gram call needs; -1 if na, nb or F is out of range */
+int64_t dots_tangent_gram_scratch(int32_t na, int32_t nb, int32_t n_triangles);
+/* A: DEVICE [na][F][3]; B: DEVICE [nb][F][3] or NULL (= A, nb must equal na); w: DEVICE [F]; scratch: DEVICE
+ * [dots_tangent_gram_scratch(na, nb, F)], contents unspecified before and after; G: HOST out [na][nb] */
+int dots_tangent_gram(const dots_tangent_desc *desc, int32_t na, const double *A, int32_t nb, const double *B, const double *w,
+                      double *scratch, double *G);
+
 /* ---- solve session: moved vertices on a live context ----------------------------------------------------------------------------
  * dots_move_vertices: the context takes other vertex positions of the SAME triangulation.  Everything that depends on the mesh graph
  * only is kept (tri, the corner lists, the CSR pattern, the permutations, the time modes, the elimination tree, the band plan, the
